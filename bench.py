@@ -27,7 +27,13 @@ one workload; VERDICT r2: `--gpus N` used to switch workloads silently between N
       timed region.  One process however many GPUs; under torchrun rank 0 drives all N devices and the other ranks
       stay off the GPUs.  `--gpus 1 --mode queue` is this curve's own N = 1 point.
 
-Every line — both modes, every N — carries
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, one pair through the engine,
+W warm-up steps, the K timed steps, the outputs of the last timed step when --dump-outputs DIR is given
+(DIR/hits_per_pair.npy: flagged vectors per pair; DIR/vectors.npy: [pair, x, y, dx, dy] rows, float64; the inputs are
+seeded, so two builds can be compared output for output), and the line with `value`, `ms_per_step` and the set-up-free
+fields.  Everything below — per-kernel hipEvents in the timed region, rooflines, the CPU baseline, the single-pair latency,
+the measured copy rate and every extra — needs --full (off by default; --no-prof / --no-extras / --no-cpu-baseline /
+--no-live-traffic trim a --full run).  With --full, every line — both modes, every N — carries
   roofline      dominant kernel (tw_blur_solve @ level 0): bytes the kernel as built moves per launch / hipEvent-
                 measured average launch duration inside the timed region (every rank's / consumer's engine brackets its
                 launches; the figure is rank 0's in resident mode and the all-consumer average in queue mode), vs the
@@ -36,7 +42,7 @@ Every line — both modes, every N — carries
   cpu_baseline  the CPU oracle (a scalar port of OpenCV 2.4.9's algorithm; OpenCV itself is not installable here)
                 timed on this box's host cores on a bounded sample, by rank 0, outside the timed region (it does not
                 depend on N)
-At N = 1 in pinned / resident mode the line also carries, all measured outside the timed region and never `value`:
+At N = 1 in pinned / resident mode a --full line also carries, all measured outside the timed region and never `value`:
   resident_hbm  (pinned mode) the same steps from HBM-resident pairs, with that run's own level-0 blur roofline
   input_sensitivity   VERDICT r3 #4: pairs/s of the same steps when ALL pairs are warped (|v| <= 6 px), warped by up to
                 48 px, or identical — what the flow-dependent R1 gather costs
@@ -100,7 +106,40 @@ def parse():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the untimed extra steps (kernel breakdown, other configs): a profiler trace then "
                          "holds only the warm-up and the timed launches")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel hipEvents in the timed region (rooflines), the CPU "
+                         "baseline, single-pair latency, copy rate and the extras (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (pinned / resident mode, rank 0) as DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode == "queue":
+        ap.error("--dump-outputs: the queue workload runs in a child process that returns no results")
+    return args
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 0
+
+
+def write_outputs(d, hits, records):
+    """hits: flagged vectors per pair of the last timed step; records: one [n, 4] (x, y, dx, dy) array per pair, as
+    tw_wait hands them to a caller.  Writes DIR/hits_per_pair.npy and DIR/vectors.npy ([pair, x, y, dx, dy] rows),
+    float64.  Should the rows exceed DUMP_MAX_BYTES, a seeded sample of them (kept in order) is written instead."""
+    os.makedirs(d, exist_ok=True)
+    hits = np.asarray(hits, np.float64)
+    rows = [np.column_stack((np.full(len(r), i, np.float64), r)) for i, r in enumerate(records)]
+    vec = np.concatenate(rows) if rows else np.zeros((0, 5), np.float64)
+    limit = (DUMP_MAX_BYTES - hits.nbytes - 256) // (5 * 8)
+    if len(vec) > limit:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(len(vec), size=limit, replace=False))
+        vec = vec[pick]
+    np.save(os.path.join(d, "hits_per_pair.npy"), hits)
+    np.save(os.path.join(d, "vectors.npy"), vec)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -219,7 +258,7 @@ def live_traffic(mode, timeout=300):
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
             cmd = [exe, "--kernel-trace", "--pmc", c, "--output-format", "csv", "-d", os.path.join(d, c), "-o", "run", "--",
                    sys.executable, os.path.abspath(__file__), "--mode", mode, "--steps", "1", "--warmup", "1", "--batch", "128",
-                   "--no-cpu-baseline", "--no-prof", "--no-extras"]
+                   "--full", "--no-cpu-baseline", "--no-prof", "--no-extras"]
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd="/tmp", env=env)
             if r.returncode != 0:
                 return None
@@ -229,7 +268,7 @@ def live_traffic(mode, timeout=300):
         try:
             cmd = [exe, "--kernel-trace", "--pmc"] + VALU_COUNTERS + ["--output-format", "csv", "-d", os.path.join(d, "VALU"), "-o", "run", "--",
                    sys.executable, os.path.abspath(__file__), "--mode", mode, "--steps", "1", "--warmup", "1", "--batch", "128",
-                   "--no-cpu-baseline", "--no-prof", "--no-extras"]
+                   "--full", "--no-cpu-baseline", "--no-prof", "--no-extras"]
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd="/tmp", env=env)
             if r.returncode == 0:
                 vout = os.path.join(d, "valu.json")
@@ -252,7 +291,7 @@ def live_traffic(mode, timeout=300):
             t["_valu"] = valu
         t["_provenance"]["source"] = "live: PMC passes run by this bench.py invocation (child runs of --mode %s --steps 1 --batch 128)" % mode
         t["_provenance"]["command"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py "
-                                       "--mode %s --steps 1 --warmup 1 --batch 128 --no-cpu-baseline --no-prof --no-extras" % mode)
+                                       "--mode %s --steps 1 --warmup 1 --batch 128 --full --no-cpu-baseline --no-prof --no-extras" % mode)
         return t
     except Exception:
         return None
@@ -387,7 +426,7 @@ def queue_mode(args, rehearse):
         "queue_sharded": out,
         "roofline": roof(twflow.K_BLUR_SOLVE, "blur"), "roofline_polyexp": roof(twflow.K_POLYEXP, "polyexp"),
     }
-    if args.no_cpu_baseline:
+    if args.no_cpu_baseline or not args.full:
         line["cpu_baseline"] = None
     else:
         line["cpu_baseline"], _, _ = cpu_baseline(host_pairs, args.cpu_pairs)
@@ -713,9 +752,29 @@ def main():
         cursor[0] += n
         return tickets
 
+    # --dump-outputs: the results of the last timed step as tw_wait hands them to a caller (skip = pairs of the timed
+    # region before that step; None: count hits only)
+    keep = {"skip": None, "hits": [], "records": []}
+    vec_buf = (twflow.Vector * max(twflow.grid_capacity(W, H, SPAN), 1))()
+    vec_view = np.ctypeslib.as_array(vec_buf)
+
+    def wait_and_keep(t):
+        if keep["skip"] > 0:
+            keep["skip"] -= 1
+            return eng.wait_count(t)[0]
+        n, sec = ctypes.c_int(), ctypes.c_float()
+        eng._check(twflow.lib().tw_wait(eng._h, t[0], vec_buf, len(vec_buf), ctypes.byref(n), ctypes.byref(sec)))
+        r = vec_view[:n.value]
+        keep["hits"].append(n.value)
+        keep["records"].append(np.column_stack((r["x"], r["y"], r["dx"], r["dy"])).astype(np.float64))
+        return n.value
+
     def collect(tickets):
         for t in tickets:
-            n, _ = eng.wait_count(t)
+            if keep["skip"] is None:
+                n, _ = eng.wait_count(t)
+            else:
+                n = wait_and_keep(t)
             flagged[0] += n
 
     def run_pairs(total):
@@ -747,41 +806,53 @@ def main():
         torch.cuda.synchronize()
         return args.batch * k / (time.perf_counter() - t)
 
-    # single-pair latency (configs[1]) and a result check before timing
+    # what a plain run measures beyond the headline: nothing (--full: per-kernel events, extras, CPU leg)
+    use_prof = args.full and not args.no_prof
+    use_extras = args.full and not args.no_extras
+
+    # one pair through the engine before anything is timed: an engine error surfaces here, and the plan of the geometry
+    # exists before the warm-up (as it always did; --full checks the latency loop's answers against it)
     res0 = eng.diff(host_pairs[0][0], host_pairs[0][1], SPAN, THRESHOLD)
-    # (median of 300 after 10 unrecorded calls = 0.12 s: the first calls after the host-side set-up run on a card that has been
-    #  idle for seconds — the 7-sample median of rounds 2-5 sat ~6 us above tools/latency.py's 40-sample figure, which itself
-    #  sits ~10 us above the median of 20 000 calls back to back, gpurun_out/r8m)
-    LAT_WARM, LAT_N = 10, 300
-    lat = []
-    for i in range(LAT_WARM + LAT_N):
-        r = eng.wait(eng.submit_dev(dev_pairs[0][0], dev_pairs[0][1], W, H, W, SPAN, THRESHOLD))
-        if i >= LAT_WARM:
-            lat.append(r["time"])
-    assert r["vector"] == res0["vector"]
+    lat = None
+    if args.full:
+        # single-pair latency (configs[1]): median of 300 after 10 unrecorded calls = 0.12 s (the first calls after the
+        # host-side set-up run on a card that has been idle for seconds — the 7-sample median of rounds 2-5 sat ~6 us above
+        # tools/latency.py's 40-sample figure, which itself sits ~10 us above the median of 20 000 calls back to back)
+        LAT_WARM, LAT_N = 10, 300
+        lat = []
+        for i in range(LAT_WARM + LAT_N):
+            r = eng.wait(eng.submit_dev(dev_pairs[0][0], dev_pairs[0][1], W, H, W, SPAN, THRESHOLD))
+            if i >= LAT_WARM:
+                lat.append(r["time"])
+        assert r["vector"] == res0["vector"]
 
     for _ in range(args.warmup):
         step()
-    if not args.no_prof:
+    if use_prof:
         eng.prof_select(twflow.K_BLUR_SOLVE, 0)
         eng.prof_select(twflow.K_POLYEXP, 0)
+    if args.dump_outputs and rank == 0:
+        keep["skip"] = args.batch * (args.steps - 1)
     barrier()
     t0 = time.perf_counter()
     run_steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    keep["skip"] = None
     elapsed, (flagged_total, pairs_total) = shard.reduce_max_sum(
         dist, torch.device("cuda", dev_index) if backend == "nccl" else torch.device("cpu"), elapsed,
         [flagged[0], args.batch * args.steps])
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, keep["hits"], keep["records"])
 
     prof = {}
     breakdown = None
-    if not args.no_prof:
+    if use_prof:
         for kc in (twflow.K_BLUR_SOLVE, twflow.K_POLYEXP):
             ms, n = eng.prof_read(kc)
             prof[kc] = (ms, n)
         eng.prof_select(-1, -2)
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and use_extras:
             # outside the timed region: one more step with every launch of every kernel class bracketed (all
             # levels) -> where the time of a pair goes
             classes = (twflow.K_PYR, twflow.K_POLYEXP, twflow.K_UPDATE_MATRICES, twflow.K_BLUR_SOLVE, twflow.K_SCAN)
@@ -798,7 +869,7 @@ def main():
     # evaluates the last level-0 iteration only at the span-grid points the scan reads (identical status / vectors,
     # the dense flow field of the last iteration is not materialised)
     fused_rate = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and use_extras:
         eng.set_option(twflow.OPT_SCAN_FUSED_FINAL, 1)
         before = flagged[0]
         step()
@@ -815,15 +886,15 @@ def main():
     # the same steps from HBM-resident pairs (rounds 1-3's headline), with that run's own level-0 blur roofline
     resident_extra = None
     sensitivity = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and use_extras:
         nf = max(2, args.steps // 2)
         if pinned_mode:
             nf_res = max(2, args.steps)  # the resident figure over the SAME number of steps as the headline
             source["pinned"] = False
-            if not args.no_prof:
+            if use_prof:
                 eng.prof_select(twflow.K_BLUR_SOLVE, 0)
             r_rate = timed_rate(nf_res)
-            r_prof = eng.prof_read(twflow.K_BLUR_SOLVE) if not args.no_prof else (0.0, 0)
+            r_prof = eng.prof_read(twflow.K_BLUR_SOLVE) if use_prof else (0.0, 0)
             eng.prof_select(-1, -2)
             source["pinned"] = True
             resident_extra = {"pairs_per_s": round(r_rate, 2), "steps": nf_res, "blur_ms_launches": r_prof}
@@ -856,15 +927,16 @@ def main():
         # 10 launches of a float4 HIP copy kernel over 1 GiB on the engine's stream (tw_debug_copy_rate: the shape
         # MI355X_MICROARCH.md quotes 6.29 TB/s for), read + write counted, outside the timed region
         copy_gbs = None
-        try:
-            copy_gbs = round(eng.copy_rate_gbps(1 << 30, 10), 1)
-        except Exception:
-            copy_gbs = None
+        if args.full:
+            try:
+                copy_gbs = round(eng.copy_rate_gbps(1 << 30, 10), 1)
+            except Exception:
+                copy_gbs = None
         traffic = None
-        if world == 1 and not args.no_extras and not args.no_live_traffic and not args.no_prof:
+        if world == 1 and use_extras and not args.no_live_traffic and use_prof:
             traffic = live_traffic(args.mode)  # ~1 minute: two counter passes over a one-step child run
         if traffic is None:
-            traffic = load_traffic()
+            traffic = load_traffic() if use_prof else {}  # only the rooflines read it
 
         def roof(kc):
             if kc not in prof or prof[kc][1] == 0:
@@ -920,10 +992,10 @@ def main():
                        "numa_node_rank0": numa_node, "backend": backend if world > 1 else None,
                        "rehearsal": None if ndev >= world else "%d ranks time-share %d device(s): a rehearsal of the "
                                                               "N-device shape, not a scaling point" % (world, ndev),
-                       "single_pair_latency_ms": round(float(np.median(lat)) * 1e3, 4),
+                       "single_pair_latency_ms": round(float(np.median(lat)) * 1e3, 4) if lat else None,
                        "single_pair_latency_note": "device time of one 1080p pair per call (BASELINE configs[1]), median of %d "
                                                    "calls back to back after %d unrecorded ones; min %.4f ms"
-                                                   % (LAT_N, LAT_WARM, float(np.min(lat)) * 1e3)},
+                                                   % (LAT_N, LAT_WARM, float(np.min(lat)) * 1e3) if lat else None},
             "measured_copy_GBps": copy_gbs,
             # rounds 1-3's `value` was --mode resident (pairs already in HBM); since round 4 it is --mode pinned
             # (uploads inside the timed region).  The resident-equivalent of this run is `resident_hbm.pairs_per_s`.
@@ -958,7 +1030,7 @@ def main():
             resident_extra["note"] = ("the headline's steps with the pairs already resident in HBM (no uploads): rounds "
                                       "1-3's `value`; outside the timed region")
             line["resident_hbm"] = resident_extra
-        extras = world == 1 and not args.no_extras
+        extras = world == 1 and use_extras
         if extras:
             # the other BASELINE configs, outside the timed region (never `value`)
             for key, fn in (("config3_host_pinned", lambda: config3_host_pinned(twflow, host_pairs, dev_index)),
@@ -969,7 +1041,7 @@ def main():
                     line[key] = fn()
                 except Exception as ex:  # an extra must never cost the headline line
                     line[key] = {"error": "%s: %s" % (type(ex).__name__, ex)}
-        if args.no_cpu_baseline:
+        if args.no_cpu_baseline or not args.full:
             line["cpu_baseline"] = None
         else:
             # rank 0, once, at every N (it does not depend on N); on all the CPUs this process was given, not only

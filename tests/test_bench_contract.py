@@ -95,6 +95,16 @@ def test_mode_flag_is_explicit():
     assert r.returncode != 0 and "invalid choice" in r.stderr
 
 
+def test_steps_and_dump_arguments_are_checked():
+    """--steps sets the number of timed steps, so it must be at least 1; --dump-outputs needs the results in this process,
+    which the queue workload (a child process) does not return."""
+    for extra in (["--steps", "0"], ["--mode", "queue", "--dump-outputs", "out"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 2 and "error:" in r.stderr, (extra, r.stderr)
+        assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
 def _line(r):
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-3000:])
@@ -110,7 +120,7 @@ def test_two_gpu_shape_rehearsed_on_one_card_is_a_creditable_line(mode):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["TW_BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--mode", mode, "--steps", "5", "--warmup", "1",
-           "--batch", "64", "--slots", "32", "--cpu-pairs", "4", "--no-extras"]
+           "--batch", "64", "--slots", "32", "--cpu-pairs", "4", "--full", "--no-extras"]
     d = _line(subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900))
     one = _line(subprocess.run([a if a != "2" else "1" for a in cmd], capture_output=True, text=True, env=env, timeout=900))
     for x, n in ((d, 2), (one, 1)):
@@ -128,3 +138,29 @@ def test_two_gpu_shape_rehearsed_on_one_card_is_a_creditable_line(mode):
         assert q["consumers"] == 2 and q["all_consumers_warm"] is True and q["errors"] == 0
         assert all(c["pairs"] > 0 for c in q["per_consumer"]), q["per_consumer"]   # no idle consumer in the timed region
         assert sum(c["pairs"] for c in q["per_consumer"]) == q["pairs"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path, twflow):
+    """A plain run times exactly --steps steps and measures nothing else (no per-kernel events, CPU leg, latency, copy rate
+    or extras); --dump-outputs writes what the last timed step returned, which equals the engine's own answer for the same
+    seeded pairs (pinned mode: pair j of a step is synthetic pair j % --distinct)."""
+    import numpy as np
+    import synth
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64",
+           "--slots", "32", "--dump-outputs", str(out)]
+    d = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=900))
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "pairs/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01
+    for k in ("roofline", "roofline_polyexp", "cpu_baseline", "kernel_breakdown", "measured_copy_GBps", "input_sensitivity"):
+        assert d[k] is None, k
+    assert d["config"]["single_pair_latency_ms"] is None and "config5_4k" not in d and "resident_hbm" not in d
+    hits = np.load(out / "hits_per_pair.npy")
+    vec = np.load(out / "vectors.npy")
+    assert hits.dtype == np.float64 and hits.shape == (64,) and vec.dtype == np.float64 and vec.shape == (hits.sum(), 5)
+    with twflow.Engine(0, twflow.default_params(), slots=2) as e:
+        want = [e.diff(*synth.make_pair(i, 1080, 1920), span=10, threshold=5.0)["vector"] for i in range(4)]
+    for j in range(64):
+        got = vec[vec[:, 0] == j][:, 1:]
+        assert hits[j] == len(want[j % 4]) and np.array_equal(got, np.array(want[j % 4], np.float64).reshape(-1, 4)), j

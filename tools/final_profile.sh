@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything profiles/ is built from, in one GPU call:  tools/final_profile.sh <outdir under gpurun_out> [tag]
-#   1. the default bench line (CPU baseline and the config-3 / config-5 / queue-sharded extras included)
+#   1. the --full bench line (CPU baseline and the config-3 / config-5 / queue-sharded extras included)
 #   2. rocprofv3 --kernel-trace --stats of the same bench (no CPU leg, no extras)
 #   3. HBM traffic: two --pmc passes (FETCH_SIZE, WRITE_SIZE), kernel trace only
 #   4. SQ / GRBM counter passes of the level-0 polyexp and blur launches (tools/sq_probe.sh over tools/kbench.py)
@@ -10,13 +10,13 @@
 out=${1:-gpurun_out/final}
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 600 python3 bench.py > "$out/bench.log" 2>&1; grep '^{' "$out/bench.log" | tail -1 > "$out/bench.json"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > "$out/trace.log" 2>&1
-python3 tools/rocprof_summary.py "$out/trace" "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras (default mode: 256-pair steps from page-locked host memory, uploads on the copy stream; single compute stream, 2 engine batches of 128 per step, one launch per kernel and level for a whole batch)" > "$out/kernel_trace_summary.md"
+timeout -k 10 600 python3 bench.py --full > "$out/bench.log" 2>&1; grep '^{' "$out/bench.log" | tail -1 > "$out/bench.json"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > "$out/trace.log" 2>&1
+python3 tools/rocprof_summary.py "$out/trace" "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras (default mode: 256-pair steps from page-locked host memory, uploads on the copy stream; single compute stream, 2 engine batches of 128 per step, one launch per kernel and level for a whole batch)" > "$out/kernel_trace_summary.md"
 cp "$out"/trace/*kernel_stats.csv "$out/kernel_stats.csv" 2>/dev/null
 grep '^{' "$out/trace.log" | tail -1 > "$out/bench_under_rocprof.json"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$out/pmc_$c" -o run -- python3 bench.py --steps 1 --warmup 1 --batch 128 --no-cpu-baseline --no-prof --no-extras > "$out/pmc_$c.log" 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$out/pmc_$c" -o run -- python3 bench.py --steps 1 --warmup 1 --batch 128 --full --no-cpu-baseline --no-prof --no-extras > "$out/pmc_$c.log" 2>&1
 done
 python3 tools/pmc_traffic.py "$out/pmc_FETCH_SIZE" "$out/pmc_WRITE_SIZE" "$out/traffic.json" "$out/pmc_hbm_traffic.md"
 tools/sq_probe.sh "$out/sq_polyexp" 8 1 0 > "$out/sq_polyexp.txt" 2>&1
@@ -45,7 +45,7 @@ try:
 except Exception as e:
     print("no _valu for config 5:", e)
 PY
-python3 tools/clock_watch.py "$out/clock_power.json" -- python3 bench.py --steps 40 --warmup 4 --no-cpu-baseline --no-extras > "$out/clock_power.log" 2>&1
+python3 tools/clock_watch.py "$out/clock_power.json" -- python3 bench.py --steps 40 --warmup 4 --full --no-cpu-baseline --no-extras > "$out/clock_power.log" 2>&1
 python3 tools/latency.py 40 > "$out/latency.txt" 2>&1
 echo "two-stream schedule (TW_LAT_FUSED=0):" >> "$out/latency.txt"; TW_LAT_FUSED=0 python3 tools/latency.py 40 >> "$out/latency.txt" 2>&1
 timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d "$out/lat_trace" -o run -- python3 tools/latency.py 10 1 > "$out/lat_trace.log" 2>&1

@@ -51,7 +51,7 @@ def main():
     out["_provenance"] = {"measured_utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),
                           "commit": os.environ.get("TW_GIT_COMMIT", "unknown"),
                           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 "
-                                     "bench.py --steps 1 --warmup 1 --batch 128 --no-cpu-baseline --no-prof --no-extras "
+                                     "bench.py --steps 1 --warmup 1 --batch 128 --full --no-cpu-baseline --no-prof --no-extras "
                                      "(tools/final_profile.sh)"}
     # round 5: the level's iterations are tw_flow_iter launches (no M in HBM) unless TW_MFREE=0; the plain iteration
     # (<15, 0>: 2 of the 3 launches of a level) is then the dominant kernel and takes the "tw_blur_solve" slot bench.py reads
