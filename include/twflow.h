@@ -145,6 +145,35 @@ tw_status tw_submit_dev(tw_engine* e, const void* d_expect, const void* d_target
 tw_status tw_flush(tw_engine* e);
 tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* n, float* seconds);
 
+/* Dense flow fields from batched submissions (additive within ABI 4; a consumer detects them by the symbols).
+ * The tw_submit_*_flow calls are tw_submit_u8 / tw_submit_png8 / tw_submit_dev plus a destination for the pair's final
+ * level-0 flow.  When tw_wait returns TW_OK for the ticket, the field is in out->data, bit-identical to what tw_flow_u8
+ * returns for the same pair; vectors, status and ticket order are those of the plain call (span 0: flow only, no scan).
+ * Bytes of the row pitch beyond a row are never written.  `seconds` stays the batch's device compute time (the copy of
+ * a field to host memory is not in it).  out == NULL is the plain call.  The destination is given at submit time
+ * because a batch launches inside tw_submit_* when it fills.
+ * out->data is device memory of the engine's device, or a page-locked host block the library knows (tw_host_alloc /
+ * tw_host_register) that the caller keeps until tw_wait of the ticket returns.  Rejected with TW_E_BAD_PARAMETER before
+ * anything is queued: a null data, a pitch below the row or not a multiple of 4, an unknown layout, any other host
+ * memory (the runtime is never handed a pageable pointer), memory of another device, or a field that does not fit
+ * inside the device allocation. */
+enum {
+    TW_FLOW_PLANAR = 0,     /* flowx rows, then flowy rows: plane y starts at data + pitch * height */
+    TW_FLOW_INTERLEAVED = 1 /* (dx, dy) float pairs per pixel, CV_32FC2 — what cv::calcOpticalFlowFarneback writes */
+};
+typedef struct tw_flow_out {
+    void* data;      /* device memory of the engine's device, or page-locked host memory the library knows */
+    ptrdiff_t pitch; /* bytes between rows; >= width*4 (planar) or width*8 (interleaved), multiple of 4 */
+    int layout;      /* TW_FLOW_PLANAR / TW_FLOW_INTERLEAVED */
+} tw_flow_out;
+tw_status tw_submit_u8_flow(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
+                            ptrdiff_t stride, int span, double threshold, const tw_flow_out* out, tw_ticket* ticket);
+tw_status tw_submit_png8_flow(tw_engine* e, const uint8_t* expect, int expect_channels, const uint8_t* target,
+                              int target_channels, int width, int height, int span, double threshold,
+                              const tw_flow_out* out, tw_ticket* ticket);
+tw_status tw_submit_dev_flow(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
+                             ptrdiff_t stride, int span, double threshold, const tw_flow_out* out, tw_ticket* ticket);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 
@@ -152,6 +181,9 @@ int tw_grid_capacity(int width, int height, int span);
 tw_status tw_dev_alloc(tw_engine* e, size_t bytes, void** dptr);
 tw_status tw_dev_free(tw_engine* e, void* dptr);
 tw_status tw_dev_upload(tw_engine* e, void* dptr, const void* host, size_t bytes);
+/* Counterpart of tw_dev_upload: synchronous device -> host copy into any host memory (pageable memory goes through the
+ * engine's page-locked bounce buffer). */
+tw_status tw_dev_download(tw_engine* e, void* host, const void* dptr, size_t bytes);
 
 /* Engine options.
  * TW_OPT_SCAN_FUSED_FINAL (default 0): tw_submit_* / tw_diff_u8 with span 10 and winSize 30/31 evaluate the last

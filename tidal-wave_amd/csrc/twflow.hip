@@ -257,6 +257,8 @@ struct Job {
     long long stride = 0;
     bool waited = false;
     int png_ch[2] = {0, 0};  // tw_submit_png8: channels of the filtered rows staged in Ctx::d_filt (0: plain gray)
+    tw_flow_out fout = {nullptr, 0, 0};  // tw_submit_*_flow: where the pair's final flow goes (data null: nowhere)
+    bool fout_host = false;              // ... page-locked host memory: through Ctx::d_fstage and the engine's d2h_stream
 };
 
 // One batch of pairs: host-side state that must outlive the asynchronous execution.
@@ -298,6 +300,16 @@ struct Ctx {
     const uint8_t** h_ptrs = nullptr;  // [2*cap]
     int* h_count = nullptr;            // [cap]
     ScanRec* h_rec = nullptr;          // [cap][HOST_RECS]
+    // tw_submit_*_flow (all created on first use): the per-pair destination table (pinned, [cap]; uploaded to
+    // tw_engine::d_fdst), and for host destinations the HBM staging the export writes (cap slots of dense rows in the
+    // destination's layout), the event behind each chunk's export that the device-to-host copies wait for, and the
+    // event behind the batch's last copy that tw_wait waits for
+    bool any_fout = false, any_fout_host = false;
+    FlowDst* h_fdst = nullptr;
+    char* d_fstage = nullptr;
+    size_t d_fstage_cap = 0;
+    hipEvent_t ev_fexp = nullptr, ev_d2h = nullptr;
+    long long d2h_ops_at_flush = 0;  // tw_engine::d2h_ops when this batch was launched
 };
 
 struct ProfPair {
@@ -431,6 +443,13 @@ struct tw_engine {
                         // ROCm 7.2: 0.55 ms vs 0.37 ms — profiles/r03_latency.md — so it is opt-in, kept for re-measuring)
     std::map<GraphKey, hipGraphExec_t> lat_graphs;  // captured single-pair schedules (dropped whenever a buffer moves)
     hipStream_t copy_stream = nullptr;  // host -> device image uploads, overlapped with the compute stream
+    // tw_submit_*_flow: device -> host copies of the flow fields (created when a host destination is first seen, so that
+    // an engine that never asks for one keeps its queue use), the copies queued there so far, batches since the host last
+    // synchronised it, and the device copy of a batch's destination table ([cap], created on first use)
+    hipStream_t d2h_stream = nullptr;
+    long long d2h_ops = 0;
+    int d2h_sync_skipped = 0;
+    FlowDst* d_fdst = nullptr;
     const uint8_t** d_ptrs = nullptr;  // [2*cap]
     int* d_count = nullptr;            // [cap]
     float2* d_grid = nullptr;          // [cap][G] dense grid samples (dx,dy)
@@ -1525,6 +1544,49 @@ void launch_update(tw_engine* e, hipStream_t st, const Plan* pl, int k, const fl
     }
 }
 
+// bytes of one pair's slot in a context's flow staging: the field as dense rows of either layout
+size_t flow_stage_slot(int w, int h) { return ((size_t)w * h * 8 + 255) / 256 * 256; }
+
+// tw_submit_*_flow: pairs [j0, j0 + nc) of the batch have their final flow in the level-0 chunk buffer `flow` (before the
+// next chunk reuses it): tw_flow_export copies it to the pairs' destinations, and the fields of host destinations go on
+// from the context's staging to the caller's page-locked memory on the device-to-host stream, behind this export only
+tw_status export_chunk(tw_engine* e, Ctx& c, hipStream_t st, const LevelPlan& L, const float* flow, int j0, int nc, size_t fslot)
+{
+    bool any = false, host = false;
+    for (int j = j0; j < j0 + nc; j++) {
+        any = any || c.jobs[j].fout.data;
+        host = host || c.jobs[j].fout_host;
+    }
+    if (!any) return TW_OK;
+    ExportArgs a;
+    a.flow = flow;
+    a.fzs = 2 * L.ps;
+    a.fps = L.ps;
+    a.ld = L.ld;
+    a.w = L.w;
+    a.h = L.h;
+    a.qpr = (L.w + 3) / 4;
+    a.dst = e->d_fdst + j0;
+    const unsigned nq = (unsigned)a.qpr * (unsigned)L.h;
+    TW_LAUNCH(e, TW_DF_FLOW_EXPORT, tw_flow_export, dim3((nq + 255) / 256, 1, nc), dim3(256), 0, st, a);
+    if (!host) return TW_OK;
+    TW_HIP(e, hipEventRecord(c.ev_fexp, st));
+    TW_HIP(e, hipStreamWaitEvent(e->d2h_stream, c.ev_fexp, 0));
+    for (int j = j0; j < j0 + nc; j++) {
+        const Job& jb = c.jobs[j];
+        if (!jb.fout_host) continue;
+        const size_t row = (size_t)L.w * (jb.fout.layout ? 8 : 4), rows = (size_t)L.h * (jb.fout.layout ? 1 : 2);
+        const char* src = c.d_fstage + fslot * j;
+        if ((size_t)jb.fout.pitch == row)  // dense rows: one plain transfer (the DMA engines)
+            TW_HIP(e, hipMemcpyAsync(jb.fout.data, src, row * rows, hipMemcpyDeviceToHost, e->d2h_stream));
+        else
+            TW_HIP(e, hipMemcpy2DAsync(jb.fout.data, (size_t)jb.fout.pitch, src, row, row, rows, hipMemcpyDeviceToHost,
+                                       e->d2h_stream));
+        e->d2h_ops++;
+    }
+    return TW_OK;
+}
+
 // Enqueue a whole batch, level-major: every level is processed for all pairs (in chunks sized to fill the
 // chip) before the next finer level starts; level 0 chunks are scanned as soon as their flow exists.
 tw_status flush_ctx(tw_engine* e, Ctx& c)
@@ -1545,6 +1607,15 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
             TW_HIP(e, hipMalloc((void**)&c.d_rec, need_rec * sizeof(ScanRec) + 256));
             c.d_rec_cap = need_rec;
         }
+    }
+    const size_t fslot = flow_stage_slot(c.w, c.h);
+    if (c.any_fout_host && fslot * e->cap > c.d_fstage_cap) {
+        // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
+        if (c.d_fstage) (void)hipFree(c.d_fstage);
+        c.d_fstage = nullptr;
+        c.d_fstage_cap = 0;
+        TW_HIP(e, hipMalloc((void**)&c.d_fstage, fslot * e->cap + 256));
+        c.d_fstage_cap = fslot * e->cap;
     }
     const int n = (int)c.jobs.size();
     int ramp_b[4] = {0, 0, 0, 0}, ramp_n = 1;  // cold-start ramp: piece i = pairs [ramp_b[i], ramp_b[i + 1]); ramp_n - 1 pieces
@@ -1608,6 +1679,19 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     }
     e->img_aligned4 = al4 ? 1 : 0;
     TW_HIP(e, hipMemcpyAsync((void*)e->d_ptrs, c.h_ptrs, sizeof(void*) * 2 * n, hipMemcpyHostToDevice, st));
+    if (c.any_fout) {
+        // tw_flow_export's destination table: the caller's device memory, or this context's staging slot (dense rows in
+        // the destination's layout) for a host destination
+        for (int j = 0; j < n; j++) {
+            const Job& jb = c.jobs[j];
+            FlowDst& d = c.h_fdst[j];
+            d.p = jb.fout_host ? c.d_fstage + fslot * j : (char*)jb.fout.data;
+            d.pitch = jb.fout_host ? (long long)c.w * (jb.fout.layout ? 8 : 4) : (long long)jb.fout.pitch;
+            d.layout = jb.fout.layout;
+            d.pad = 0;
+        }
+        TW_HIP(e, hipMemcpyAsync((void*)e->d_fdst, c.h_fdst, sizeof(FlowDst) * n, hipMemcpyHostToDevice, st));
+    }
     TW_HIP(e, hipEventRecord(c.ev_start, st));
     const int it = e->p.pyrIterations;
     const int nlanes = (e->lanes > 1 && n >= 2) ? e->lanes : 1;
@@ -1643,9 +1727,11 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     // Everything between the batch's start event and the ordered scan, as one function: the single-pair schedule
     // replays it from a captured hipGraph (below), every other batch enqueues it directly.
     // does level k of a launch of nc pairs run tw_flow_iter?  (level_runs_flow_iter: the predicate the byte model shares)
+    // (a batch with a flow destination needs the last level-0 field itself: never the scan-fused final iteration)
+    const bool fused_final = scan_fused_level0(e, c.span) && !c.any_fout;
     auto level_mfree = [&](int k, int nc) -> bool {
         const LevelPlan& L = pl->lv[k];
-        return level_runs_flow_iter(e, L.w, L.h, nc, lat, k == 0 && scan_fused_level0(e, c.span));
+        return level_runs_flow_iter(e, L.w, L.h, nc, lat, k == 0 && fused_final);
     };
     auto enqueue_levels = [&]() -> tw_status {
     if (lat && !lat2) {
@@ -1836,7 +1922,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
                 // flow buffer and the (now unused) M0 workspace so that the last iteration lands in the flow buffer.
                 // scan-fused final iteration (option TW_OPT_SCAN_FUSED_FINAL): nothing but the span grid of the last
                 // level-0 flow is read afterwards, so the last window average + solve runs at the grid points only
-                const bool grid_only = k == 0 && scan_fused_level0(e, c.span);
+                const bool grid_only = k == 0 && fused_final;
                 bool iterated = false;
                 bool grid_stored = false;  // the last window launch wrote the span-grid samples itself (single pair)
                 // (with the scan-fused last iteration: it - 1 iterations here, then the M of the last flow from
@@ -1949,6 +2035,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
                     ProfScope pscope(e, ls, TW_K_SCAN, 0);
                     TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((g.gw + 63) / 64, (g.gh + 3) / 4, nc), dim3(256), 0, ls, g);
                 }
+                if (k == 0 && c.any_fout && (r = export_chunk(e, c, ls, L, flow_cur, j0, nc, fslot))) return r;
                 // the image-only work two levels below goes out once this level's chain is enqueued
                 if (lat && !lat2 && k >= 2 && (r = lat_images(k - 2))) return r;
             }
@@ -1969,7 +2056,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     // is slower (0.55 ms: kernels of the forked branch stretch to ~40 us quanta behind cross-queue signals), so the
     // direct path is the default and the graph an opt-in A/B switch (profiles/r03_latency.md).
     bool launched_graph = false;
-    if (lat && e->lat_graph && !prof_on) {
+    if (lat && e->lat_graph && !prof_on && !c.any_fout) {  // (destinations would be baked into the graph)
         const GraphKey key{c.w, c.h, c.span, stride, e->img_aligned4, e->scan_fused, e->poly_f32};
         auto git = e->lat_graphs.find(key);
         if (git == e->lat_graphs.end()) {
@@ -2050,6 +2137,10 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
         TW_HIP(e, hipMemcpy2DAsync(c.h_rec, HOST_RECS * sizeof(ScanRec), c.d_rec, G * sizeof(ScanRec),
                                    nrec * sizeof(ScanRec), n, hipMemcpyDeviceToHost, st));
     }
+    if (c.any_fout_host) {
+        TW_HIP(e, hipEventRecord(c.ev_d2h, e->d2h_stream));
+        c.d2h_ops_at_flush = e->d2h_ops;
+    }
     TW_HIP(e, hipGetLastError());
     TW_HIP(e, hipEventRecord(c.ev_done, st));
     c.launched = true;
@@ -2121,10 +2212,51 @@ bool host_range_is_page_locked(const void* p, size_t n) { return pin_registry().
 
 size_t png_rows_bytes(int width, int height, int ch) { return (size_t)height * ((size_t)width * (size_t)ch + 1); }
 
+// A tw_submit_*_flow destination, checked before anything is queued: *host = a page-locked block the library knows
+// (the export goes through the context's staging), otherwise device memory of this engine's device that holds the
+// whole field.  Anything else — pageable memory above all — is refused.
+tw_status check_flow_out(tw_engine* e, const tw_flow_out* o, int w, int h, bool* host)
+{
+    const size_t row = (size_t)w * (o->layout == TW_FLOW_INTERLEAVED ? 8 : 4);
+    if (!o->data || (o->layout != TW_FLOW_PLANAR && o->layout != TW_FLOW_INTERLEAVED) || o->pitch < (ptrdiff_t)row ||
+        o->pitch % 4 != 0) {
+        e->err = "bad flow destination (null data, unknown layout, or a pitch below the row or not a multiple of 4)";
+        return TW_E_BAD_PARAMETER;
+    }
+    const size_t rows = (size_t)h * (o->layout == TW_FLOW_INTERLEAVED ? 1 : 2);
+    const size_t extent = (size_t)o->pitch * (rows - 1) + row;
+    if (pin_registry().covers(o->data, extent)) {
+        *host = true;
+        return TW_OK;
+    }
+    *host = false;
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, o->data) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        e->err = "flow destination is neither device memory nor a page-locked block of tw_host_alloc / tw_host_register";
+        return TW_E_BAD_PARAMETER;
+    }
+    if (at.device != e->device) {
+        e->err = "flow destination is memory of another device";
+        return TW_E_BAD_PARAMETER;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, o->data) != hipSuccess ||
+        (uintptr_t)o->data + extent > (uintptr_t)base + size) {
+        (void)hipGetLastError();
+        e->err = "flow destination does not hold the whole field";
+        return TW_E_BAD_PARAMETER;
+    }
+    return TW_OK;
+}
+
 // ch_a / ch_b > 0 (tw_submit_png8): that host image is `height` filtered PNG rows of 1 + width * ch bytes
+// fo (tw_submit_*_flow): where the pair's final flow goes, null for the plain calls
 tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, const void* d_a, const void* d_b,
                         int width, int height, ptrdiff_t stride, int span, double threshold, tw_ticket* ticket,
-                        int ch_a = 0, int ch_b = 0)
+                        int ch_a = 0, int ch_b = 0, const tw_flow_out* fo = nullptr)
 {
     if (!e) return TW_E_BAD_PARAMETER;
     e->err.clear();
@@ -2156,6 +2288,13 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
     }
     const size_t filt_need = png ? (png_rows_bytes(width, height, std::max(ch_a, ch_b)) + 255) / 256 * 256 : 0;
     TW_HIP(e, hipSetDevice(e->device));
+    bool fo_host = false;
+    if (fo) {
+        TW_TRY(check_flow_out(e, fo, width, height, &fo_host));
+        // what the destinations need, made once per engine / context (a failure books nothing)
+        if (!e->d_fdst) TW_HIP(e, hipMalloc((void**)&e->d_fdst, sizeof(FlowDst) * (size_t)e->cap + 256));
+        if (fo_host && !e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
+    }
     // host images are staged densely; device images are read in place with their own row stride
     const long long eff_stride = h_a ? (long long)width : (long long)stride;
     Ctx* c = &e->ctx[e->cur];
@@ -2188,9 +2327,16 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
         c->threshold = threshold;
         c->any_host = false;
         c->any_png = false;
+        c->any_fout = false;
+        c->any_fout_host = false;
         c->filt_slot = 0;
         c->nseg = 0;
         c->first_ticket = e->next_ticket;
+    }
+    if (fo) {
+        if (!c->h_fdst) TW_HIP(e, hipHostMalloc((void**)&c->h_fdst, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
+        if (!c->ev_fexp) TW_HIP(e, hipEventCreateWithFlags(&c->ev_fexp, hipEventDisableTiming));
+        if (!c->ev_d2h) TW_HIP(e, hipEventCreateWithFlags(&c->ev_d2h, hipEventDisableTiming));
     }
     Job jb;
     jb.stride = eff_stride;
@@ -2314,6 +2460,12 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
             TW_HIP(e, hipEventRecord(c->ev_seg[c->nseg], e->copy_stream));
             c->seg_at[c->nseg++] = sz;
         }
+    }
+    if (fo) {
+        jb.fout = *fo;
+        jb.fout_host = fo_host;
+        c->any_fout = true;
+        c->any_fout_host = c->any_fout_host || fo_host;
     }
     c->jobs.push_back(jb);
     c->pending++;
@@ -2565,6 +2717,10 @@ void tw_engine_destroy(tw_engine* e)
         if (c.h_ptrs) (void)hipHostFree((void*)c.h_ptrs);
         if (c.h_count) (void)hipHostFree(c.h_count);
         if (c.h_rec) (void)hipHostFree(c.h_rec);
+        if (c.d_fstage) (void)hipFree(c.d_fstage);
+        if (c.h_fdst) (void)hipHostFree(c.h_fdst);
+        if (c.ev_fexp) (void)hipEventDestroy(c.ev_fexp);
+        if (c.ev_d2h) (void)hipEventDestroy(c.ev_d2h);
         if (c.ev_start) (void)hipEventDestroy(c.ev_start);
         if (c.ev_stop) (void)hipEventDestroy(c.ev_stop);
         if (c.ev_done) (void)hipEventDestroy(c.ev_done);
@@ -2572,6 +2728,8 @@ void tw_engine_destroy(tw_engine* e)
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->stream2) (void)hipStreamDestroy(e->stream2);
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
+    if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
+    if (e->d_fdst) (void)hipFree(e->d_fdst);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
     for (auto& kv : e->plans) free_plan(kv.second);
@@ -2605,6 +2763,29 @@ tw_status tw_submit_dev(tw_engine* e, const void* d_expect, const void* d_target
 {
     if (!d_expect || !d_target) return TW_E_BAD_PARAMETER;
     return submit_common(e, nullptr, nullptr, d_expect, d_target, width, height, stride, span, threshold, ticket);
+}
+
+tw_status tw_submit_u8_flow(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
+                            ptrdiff_t stride, int span, double threshold, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!expect || !target) return TW_E_BAD_PARAMETER;
+    return submit_common(e, expect, target, nullptr, nullptr, width, height, stride, span, threshold, ticket, 0, 0, out);
+}
+
+tw_status tw_submit_png8_flow(tw_engine* e, const uint8_t* expect, int expect_channels, const uint8_t* target,
+                              int target_channels, int width, int height, int span, double threshold,
+                              const tw_flow_out* out, tw_ticket* ticket)
+{
+    // (two plain gray images take the ordinary host path, as in tw_submit_png8)
+    return submit_common(e, expect, target, nullptr, nullptr, width, height, width, span, threshold, ticket,
+                         expect_channels, target_channels, out);
+}
+
+tw_status tw_submit_dev_flow(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
+                             ptrdiff_t stride, int span, double threshold, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!d_expect || !d_target) return TW_E_BAD_PARAMETER;
+    return submit_common(e, nullptr, nullptr, d_expect, d_target, width, height, stride, span, threshold, ticket, 0, 0, out);
 }
 
 tw_status tw_flush(tw_engine* e)
@@ -2645,6 +2826,17 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
         if (e->copy_ops == c->copy_ops_at_flush || ++e->copy_sync_skipped >= 16) {
             (void)hipStreamSynchronize(e->copy_stream);
             e->copy_sync_skipped = 0;
+        }
+    }
+    if (herr == hipSuccess && c->any_fout_host) {
+        // the batch's flow fields on their way to host memory (the compute stream never waits for these copies)
+        herr = hipEventSynchronize(c->ev_d2h);
+        // as for the copy stream above: a host-side synchronise of the stream releases its bookkeeping — free when no later
+        // batch has queued copies behind this one's, otherwise every 16th batch
+        if (herr == hipSuccess && c->pending == (int)c->jobs.size() &&
+            (e->d2h_ops == c->d2h_ops_at_flush || ++e->d2h_sync_skipped >= 16)) {
+            herr = hipStreamSynchronize(e->d2h_stream);
+            e->d2h_sync_skipped = 0;
         }
     }
     c->jobs[j].waited = true;
@@ -2765,6 +2957,13 @@ tw_status tw_dev_upload(tw_engine* e, void* dptr, const void* host, size_t bytes
     if (!e || !dptr || !host) return TW_E_BAD_PARAMETER;
     TW_HIP(e, hipSetDevice(e->device));
     TW_TRY(h2d_sync(e, dptr, host, bytes));
+    return TW_OK;
+}
+tw_status tw_dev_download(tw_engine* e, void* host, const void* dptr, size_t bytes)
+{
+    if (!e || !dptr || !host) return TW_E_BAD_PARAMETER;
+    TW_HIP(e, hipSetDevice(e->device));
+    TW_TRY(d2h_sync(e, host, dptr, bytes));
     return TW_OK;
 }
 
@@ -3086,7 +3285,7 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q"};
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
 }
 
@@ -3096,7 +3295,7 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // device: the level workspace (I + 5 I for R + 2 x 2.5 I for M), the single-pair schedule's I / R, the box window's column
     // sums, flow planes, the dense grid, pointer / count tables, debug stamps, every context's images, filtered rows, PNG job
-    // table and records, and the plans' tables (each allocation with the slack it was made with)
+    // table, records and flow staging, the flow destination table, and the plans' tables (each allocation with the slack it was made with)
     if (e->I) v[0] += (e->ws_elems * 4 + 256) + (e->ws_elems * 5 * 4 + 256) + 2 * (e->ws_elems / 2 * 5 * 4 + 256);
     if (e->lat_I) v[0] += (e->lat_cap * 4 + 256) + (e->lat_cap * 5 * 4 + 256);
     if (e->Vd) v[0] += e->Vd_cap * sizeof(double) + 256;
@@ -3106,7 +3305,10 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     if (e->d_ptrs) v[0] += sizeof(void*) * 2 * (size_t)e->cap + 256;
     if (e->d_count) v[0] += sizeof(int) * (size_t)e->cap + 256;
     if (e->dbg_stamps) v[0] += 4096 * sizeof(unsigned long long);
+    if (e->d_fdst) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
     for (const Ctx& c : e->ctx) {
+        if (c.d_fstage) v[0] += c.d_fstage_cap + 256;
+        if (c.h_fdst) v[1] += sizeof(FlowDst) * (size_t)e->cap;
         if (c.d_img) v[0] += c.d_img_cap + 256;
         if (c.d_filt_raw) v[0] += c.d_filt_cap + 512;
         if (c.d_png) v[0] += sizeof(PngJob) * 2 * (size_t)e->cap + 256;

@@ -4079,6 +4079,73 @@ __global__ __launch_bounds__(256) void tw_span_gather(GatherArgs a)
     a.g[(long long)blockIdx.z * a.gw * a.gh + gy * a.gw + gx] = v;
 }
 
+// -----------------------------------------------------------------------------------------------------
+// tw_flow_export : a level-0 chunk's final flow (planar, rows ld floats apart — ld a multiple of 32, so every row starts
+//   128-byte aligned) -> each pair's tw_submit_*_flow destination, planar or (dx, dy)-interleaved, at the destination's
+//   own row pitch.  Grid z = the pair in the chunk; a pair without a destination (null entry) exits at once.  One lane
+//   per 4 pixels of a row: two 16-byte loads, two 16-byte stores (dword stores when the destination base or pitch is
+//   not 16-byte aligned, and for the last, partial quad of a row: nothing beyond column w - 1 is written).
+//   Destination offsets in 64 bits.
+// -----------------------------------------------------------------------------------------------------
+struct FlowDst {
+    char* p;           // null: the pair has no destination
+    long long pitch;   // bytes between rows
+    int layout;        // 0 planar (plane y at p + pitch * h), 1 interleaved
+    int pad;
+};
+struct ExportArgs {
+    const float* flow;  // pair z: 2 planes at flow + z*fzs
+    long long fzs, fps;
+    int ld, w, h, qpr;  // qpr = ceil(w / 4)
+    const FlowDst* dst; // pair z: dst[z]
+};
+
+__global__ __launch_bounds__(256) void tw_flow_export(ExportArgs a)
+{
+    const FlowDst d = a.dst[blockIdx.z];
+    if (!d.p) return;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    const unsigned y = i / (unsigned)a.qpr;
+    if (y >= (unsigned)a.h) return;
+    const int x = (int)(i - y * (unsigned)a.qpr) * 4;
+    const float* __restrict__ src = a.flow + (long long)blockIdx.z * a.fzs + (long long)y * a.ld + x;
+    // (x + 3 < ld: ld is a multiple of 32 >= w, so the last quad's loads stay inside the padded row)
+    const float4 fx = *(const float4*)src;
+    const float4 fy = *(const float4*)(src + a.fps);
+    const bool full = x + 4 <= a.w;
+    const bool al16 = (((unsigned long long)(uintptr_t)d.p | (unsigned long long)d.pitch) & 15ull) == 0;
+    if (d.layout == 1) {
+        float* o = (float*)(d.p + (long long)y * d.pitch + (long long)x * 8);
+        if (full && al16) {
+            *(float4*)o = make_float4(fx.x, fy.x, fx.y, fy.y);
+            *(float4*)(o + 4) = make_float4(fx.z, fy.z, fx.w, fy.w);
+        } else {
+            const float vx[4] = {fx.x, fx.y, fx.z, fx.w}, vy[4] = {fy.x, fy.y, fy.z, fy.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (x + k < a.w) {
+                    o[2 * k] = vx[k];
+                    o[2 * k + 1] = vy[k];
+                }
+        }
+    } else {
+        float* ox = (float*)(d.p + (long long)y * d.pitch + (long long)x * 4);
+        float* oy = (float*)(d.p + ((long long)a.h + y) * d.pitch + (long long)x * 4);
+        if (full && al16) {
+            *(float4*)ox = fx;
+            *(float4*)oy = fy;
+        } else {
+            const float vx[4] = {fx.x, fx.y, fx.z, fx.w}, vy[4] = {fy.x, fy.y, fy.z, fy.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (x + k < a.w) {
+                    ox[k] = vx[k];
+                    oy[k] = vy[k];
+                }
+        }
+    }
+}
+
 struct ScanArgs {
     const float2* g;  // pair z: dense grid samples at g + z*G
     int span, gw, gh;

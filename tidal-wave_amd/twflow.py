@@ -35,6 +35,14 @@ class Vector(C.Structure):
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("dx", C.c_double), ("dy", C.c_double)]
 
 
+class FlowOut(C.Structure):
+    # tw_flow_out (include/twflow.h): destination of a pair's final flow for the tw_submit_*_flow calls
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_ssize_t), ("layout", C.c_int)]
+
+
+FLOW_PLANAR, FLOW_INTERLEAVED = 0, 1
+
+
 class TwError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("twflow status %d: %s" % (code, msg))
@@ -50,7 +58,8 @@ OPT_POLYEXP_F32 = 2
 SYMBOLS = [
     "tw_default_params", "tw_abi_version", "tw_has_variants", "tw_device_count", "tw_device_pci_bus_id", "tw_engine_create", "tw_engine_destroy", "tw_strerror",
     "tw_last_error", "tw_flow_u8", "tw_diff_u8", "tw_submit_u8", "tw_submit_png8", "tw_submit_dev", "tw_flush", "tw_wait",
-    "tw_grid_capacity", "tw_dev_alloc", "tw_dev_free", "tw_dev_upload", "tw_host_alloc", "tw_host_free", "tw_host_register", "tw_host_unregister", "tw_set_option",
+    "tw_submit_u8_flow", "tw_submit_png8_flow", "tw_submit_dev_flow",
+    "tw_grid_capacity", "tw_dev_alloc", "tw_dev_free", "tw_dev_upload", "tw_dev_download", "tw_host_alloc", "tw_host_free", "tw_host_register", "tw_host_unregister", "tw_set_option",
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
@@ -122,6 +131,10 @@ def _bind(path):
     L.tw_stage_png_unfilter.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_int, C.c_int, u8p]
     L.tw_submit_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_double,
                                 C.POINTER(C.c_int64)]
+    fop, tkp = C.POINTER(FlowOut), C.POINTER(C.c_int64)
+    L.tw_submit_u8_flow.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_double, fop, tkp]
+    L.tw_submit_png8_flow.argtypes = [vp, u8p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, fop, tkp]
+    L.tw_submit_dev_flow.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_double, fop, tkp]
     L.tw_wait.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, fp]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
@@ -130,6 +143,7 @@ def _bind(path):
     L.tw_dev_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.tw_dev_free.argtypes = [vp, vp]
     L.tw_dev_upload.argtypes = [vp, vp, vp, C.c_size_t]
+    L.tw_dev_download.argtypes = [vp, vp, vp, C.c_size_t]
     L.tw_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.tw_host_free.argtypes = [vp, vp]
     L.tw_host_register.argtypes = [vp, vp, C.c_size_t]
@@ -214,6 +228,35 @@ def _u8(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
+def _flow_out(flow, w, h):
+    """A submit's `flow=` argument -> FlowOut (None: no destination).  Accepted: a float32 numpy array in page-locked
+    memory (Engine.host_array) or a float32 torch tensor on the engine's device, shaped (2, h, w) planar or (h, w, 2)
+    interleaved (rows may be padded: any row stride, unit stride within a row), or a raw (pointer, pitch, layout) tuple.
+    The library itself refuses pageable host memory and memory of another device."""
+    if flow is None:
+        return None
+    if isinstance(flow, tuple):
+        ptr, pitch, layout = flow
+        return FlowOut(ptr, pitch, layout)
+    if isinstance(flow, np.ndarray):
+        if flow.dtype != np.float32:
+            raise TwError(TW_E_BAD_PARAMETER, "flow destination must be float32")
+        shape, strides, ptr = flow.shape, flow.strides, flow.ctypes.data
+    elif type(flow).__module__.startswith("torch"):
+        import torch
+        if flow.dtype != torch.float32 or not flow.is_cuda:
+            raise TwError(TW_E_BAD_PARAMETER, "flow destination tensor must be float32 on the GPU")
+        shape, strides, ptr = tuple(flow.shape), tuple(s * 4 for s in flow.stride()), flow.data_ptr()
+    else:
+        raise TwError(TW_E_BAD_PARAMETER, "unsupported flow destination %r" % type(flow))
+    if shape == (2, h, w) and strides[2] == 4 and strides[0] == strides[1] * h:
+        return FlowOut(ptr, strides[1], FLOW_PLANAR)
+    if shape == (h, w, 2) and strides[2] == 4 and strides[1] == 8:
+        return FlowOut(ptr, strides[0], FLOW_INTERLEAVED)
+    raise TwError(TW_E_BAD_PARAMETER, "flow destination must be (2, %d, %d) planar or (%d, %d, 2) interleaved with "
+                  "unit-stride rows, got shape %r strides %r" % (h, w, h, w, shape, strides))
+
+
 def _gray(a):
     a = np.asarray(a)
     if a.dtype != np.uint8 or a.ndim != 2:
@@ -288,7 +331,8 @@ class Engine:
         t = self.submit(expect, target, span, threshold)
         return self.wait(t)
 
-    def submit(self, expect, target, span=10, threshold=5.0):
+    def submit(self, expect, target, span=10, threshold=5.0, *, flow=None):
+        """flow: where the pair's final flow goes (tw_submit_u8_flow; see _flow_out), kept alive by the caller until wait()."""
         a, b = _gray(expect), _gray(target)
         if a.shape != b.shape:
             raise TwError(TW_E_DONT_MATCH_SIZE, "Don't match image size")
@@ -296,7 +340,12 @@ class Engine:
             a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
         h, w = a.shape
         tk = C.c_int64()
-        self._check(self._L.tw_submit_u8(self._h, _u8(a), _u8(b), w, h, a.strides[0], span, threshold, C.byref(tk)))
+        fo = _flow_out(flow, w, h)
+        if fo is None:
+            self._check(self._L.tw_submit_u8(self._h, _u8(a), _u8(b), w, h, a.strides[0], span, threshold, C.byref(tk)))
+        else:
+            self._check(self._L.tw_submit_u8_flow(self._h, _u8(a), _u8(b), w, h, a.strides[0], span, threshold,
+                                                  C.byref(fo), C.byref(tk)))
         return (tk.value, w, h, span, threshold)
 
     def submit_ptr(self, p_expect, p_target, w, h, stride, span=10, threshold=5.0):
@@ -306,13 +355,18 @@ class Engine:
         self._check(self._L.tw_submit_u8(self._h, p_expect, p_target, w, h, stride, span, threshold, C.byref(tk)))
         return (tk.value, w, h, span, threshold)
 
-    def submit_png8(self, expect, ch_a, target, ch_b, w, h, span=10, threshold=5.0):
+    def submit_png8(self, expect, ch_a, target, ch_b, w, h, span=10, threshold=5.0, *, flow=None):
         """tw_submit_png8: each image is either filtered PNG rows (uint8 array of h * (1 + w * ch) bytes, ch 1-4) or a
-        plain gray image (ch 0, shape (h, w))."""
+        plain gray image (ch 0, shape (h, w)).  flow: as for submit (tw_submit_png8_flow)."""
         a = np.ascontiguousarray(expect, np.uint8)
         b = np.ascontiguousarray(target, np.uint8)
         tk = C.c_int64()
-        self._check(self._L.tw_submit_png8(self._h, _u8(a), ch_a, _u8(b), ch_b, w, h, span, threshold, C.byref(tk)))
+        fo = _flow_out(flow, w, h)
+        if fo is None:
+            self._check(self._L.tw_submit_png8(self._h, _u8(a), ch_a, _u8(b), ch_b, w, h, span, threshold, C.byref(tk)))
+        else:
+            self._check(self._L.tw_submit_png8_flow(self._h, _u8(a), ch_a, _u8(b), ch_b, w, h, span, threshold,
+                                                    C.byref(fo), C.byref(tk)))
         return (tk.value, w, h, span, threshold)
 
     def stage_png_unfilter(self, rows, ch, w, h, waves=0):
@@ -322,10 +376,52 @@ class Engine:
         self._check(self._L.tw_stage_png_unfilter(self._h, _u8(rows), ch, w, h, waves, _u8(out)))
         return out
 
-    def submit_dev(self, d_expect, d_target, w, h, stride, span=10, threshold=5.0):
+    def submit_dev(self, d_expect, d_target, w, h, stride, span=10, threshold=5.0, *, flow=None):
+        """flow: as for submit (tw_submit_dev_flow)."""
         tk = C.c_int64()
-        self._check(self._L.tw_submit_dev(self._h, d_expect, d_target, w, h, stride, span, threshold, C.byref(tk)))
+        fo = _flow_out(flow, w, h)
+        if fo is None:
+            self._check(self._L.tw_submit_dev(self._h, d_expect, d_target, w, h, stride, span, threshold, C.byref(tk)))
+        else:
+            self._check(self._L.tw_submit_dev_flow(self._h, d_expect, d_target, w, h, stride, span, threshold,
+                                                   C.byref(fo), C.byref(tk)))
         return (tk.value, w, h, span, threshold)
+
+    def flow_batch(self, expects, targets, layout="interleaved", span=0, threshold=5.0):
+        """Dense flow fields of N pairs through the batched API.  numpy inputs (N 2-D uint8 images each): returns a
+        page-locked float32 array [N, H, W, 2] ("interleaved") or [N, 2, H, W] ("planar") — freed with the engine —
+        and the per-pair result dicts of wait().  torch uint8 tensors [N, H, W] on the engine's device: submitted in place
+        (tw_submit_dev_flow), the fields come back as a float32 tensor on that device (a torch program imports torch before
+        this module loads the library, as bench.py does: the process's HIP runtime must be torch's)."""
+        if layout not in ("interleaved", "planar"):
+            raise TwError(TW_E_BAD_PARAMETER, "layout must be 'interleaved' or 'planar'")
+        inter = layout == "interleaved"
+        if type(expects).__module__.startswith("torch"):
+            import torch
+            if expects.shape != targets.shape or expects.dim() != 3 or expects.dtype != torch.uint8:
+                raise TwError(TW_E_BAD_IMAGE_FORMAT, "expected two uint8 tensors [N, H, W] of one shape")
+            if expects.stride(2) != 1 or targets.stride() != expects.stride():
+                expects, targets = expects.contiguous(), targets.contiguous()
+            n, h, w = expects.shape
+            out = torch.empty((n, h, w, 2) if inter else (n, 2, h, w), dtype=torch.float32, device=expects.device)
+            # the ABI takes no stream: the inputs and `out` may still be in flight on torch's stream
+            torch.cuda.current_stream(expects.device).synchronize()
+            sub = lambda i: self.submit_dev(expects[i].data_ptr(), targets[i].data_ptr(), w, h, expects.stride(1),  # noqa: E731
+                                            span, threshold, flow=out[i])
+        else:
+            a0 = _gray(expects[0])
+            n, (h, w) = len(expects), a0.shape
+            out = self.host_array((n, h, w, 2) if inter else (n, 2, h, w), np.float32)
+            sub = lambda i: self.submit(expects[i], targets[i], span, threshold, flow=out[i])  # noqa: E731
+        res, pending = [None] * n, []
+        for i in range(n):
+            if len(pending) >= 2 * self.slots:  # (at most NCTX batches in flight: collect the oldest first)
+                j, t = pending.pop(0)
+                res[j] = self.wait(t)
+            pending.append((i, sub(i)))
+        for j, t in pending:
+            res[j] = self.wait(t)
+        return out, res
 
     def bench_stage(self, kclass, w, h, level, npairs=1, iters=20, flags=0):
         """Average microseconds per launch of one kernel class on synthetic resident data."""
@@ -370,14 +466,21 @@ class Engine:
     def set_option(self, option, value):
         self._check(self._L.tw_set_option(self._h, option, int(value)))
 
-    def host_array(self, shape):
-        """uint8 array in page-locked memory (tw_host_alloc): submit() DMAs straight from it, without staging.
-        Freed with the engine."""
-        n = int(np.prod(shape))
+    def host_array(self, shape, dtype=np.uint8):
+        """Array in page-locked memory (tw_host_alloc): submit() DMAs straight from it, without staging, and it can take
+        a flow field (dtype float32).  Freed with the engine."""
+        dt = np.dtype(dtype)
+        n = int(np.prod(shape)) * dt.itemsize
         h = C.c_void_p()
         self._check(self._L.tw_host_alloc(self._h, n, C.byref(h)))
         self._hostbufs.append(h)
-        return np.ctypeslib.as_array(C.cast(h, C.POINTER(C.c_uint8)), shape=(n,)).reshape(shape)
+        return np.ctypeslib.as_array(C.cast(h, C.POINTER(C.c_uint8)), shape=(n,)).view(dt).reshape(shape)
+
+    def dev_download(self, dptr, nbytes):
+        """tw_dev_download: nbytes of device memory as a uint8 numpy array."""
+        out = np.empty(nbytes, np.uint8)
+        self._check(self._L.tw_dev_download(self._h, out.ctypes.data_as(C.c_void_p), dptr, nbytes))
+        return out
 
     # ---- instrumentation -------------------------------------------------------------------------------
     def prof_select(self, kclass, level=-1):
