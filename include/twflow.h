@@ -174,6 +174,35 @@ tw_status tw_submit_png8_flow(tw_engine* e, const uint8_t* expect, int expect_ch
 tw_status tw_submit_dev_flow(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
                              ptrdiff_t stride, int span, double threshold, const tw_flow_out* out, tw_ticket* ticket);
 
+/* Initial flow fields (OPTFLOW_USE_INITIAL_FLOW; additive within ABI 4, detected by the symbols).
+ * The tw_submit_*_flow_init calls are tw_submit_*_flow plus a full-resolution field that seeds the coarsest pyramid level,
+ * as cv::calcOpticalFlowFarneback does with OPTFLOW_USE_INITIAL_FLOW: the field is resized to the coarsest level with
+ * INTER_AREA and multiplied by that level's scale (pyrScale^levels); everything after is unchanged.  A non-NULL init
+ * turns the initial flow on for that pair whatever params.flags says; without one (init == NULL, or the plain calls)
+ * the pair starts from zero as before — flags & 4 alone still means a zero start (the reference passes an
+ * uninitialised field).  init and out may each be NULL.
+ * init->data is device memory of the engine's device (read in place), a page-locked host block the library knows
+ * (DMA-ed from in place), or any other host memory (copied before the call returns; the runtime is never handed a
+ * pageable pointer).  The field is read when its batch launches, so the caller keeps it unchanged until tw_wait of the
+ * ticket returns; a field that is another ticket's destination needs that ticket waited first.  Non-finite values are
+ * passed through.  Rejected with TW_E_BAD_PARAMETER before anything is queued: a null data, a pitch below the row or
+ * not a multiple of 4, an unknown layout, memory of another device, or a field that does not fit inside its device
+ * allocation. */
+typedef struct tw_flow_in {
+    const void* data; /* device memory of the engine's device, or host memory */
+    ptrdiff_t pitch;  /* bytes between rows; >= width*4 (planar) or width*8 (interleaved), multiple of 4 */
+    int layout;       /* TW_FLOW_PLANAR / TW_FLOW_INTERLEAVED */
+} tw_flow_in;
+tw_status tw_submit_u8_flow_init(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
+                                 ptrdiff_t stride, int span, double threshold, const tw_flow_in* init,
+                                 const tw_flow_out* out, tw_ticket* ticket);
+tw_status tw_submit_png8_flow_init(tw_engine* e, const uint8_t* expect, int expect_channels, const uint8_t* target,
+                                   int target_channels, int width, int height, int span, double threshold,
+                                   const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket);
+tw_status tw_submit_dev_flow_init(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
+                                  ptrdiff_t stride, int span, double threshold, const tw_flow_in* init,
+                                  const tw_flow_out* out, tw_ticket* ticket);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 

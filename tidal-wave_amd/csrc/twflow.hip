@@ -42,6 +42,12 @@ inline int cv_floor(double v)
     int i = (int)lrint(v);
     return i - (v < (double)i);
 }
+inline int cv_ceil(double v)
+{
+    if (!(v > -2147483648.0 && v < 2147483648.0)) return INT32_MIN;
+    int i = (int)lrint(v);
+    return i + (i < v);
+}
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // cv::getGaussianKernel(n, sigma, CV_32F) — imgproc/smooth.cpp
@@ -121,6 +127,62 @@ void make_resize_tab(int sw, int sh, int dw, int dh, ResizeTab& t)
         t.beta[2 * dy] = 1.f - fy;
         t.beta[2 * dy + 1] = fy;
     }
+}
+
+// cv::resize(INTER_AREA) of a full-resolution initial flow field to the coarsest level — imgproc/imgwarp.cpp (2.4.9):
+// mode 0 same size (a copy), 1 both scales integers within DBL_EPSILON (resizeAreaFast_Invoker), 2 computeResizeAreaTab's
+// tables (ResizeArea_Invoker), computed in double exactly as there
+struct AreaTab {
+    int mode = 2, ix = 1, iy = 1;
+    std::vector<int> xstart, xsi, ystart, ysi;  // output x's entries: [xstart[x], xstart[x + 1])
+    std::vector<float> xalpha, ybeta;
+};
+void area_tab_1d(int ssize, int dsize, double scale, std::vector<int>& start, std::vector<int>& si, std::vector<float>& alpha)
+{
+    start.assign(dsize + 1, 0);
+    si.clear();
+    alpha.clear();
+    for (int dx = 0; dx < dsize; dx++) {
+        start[dx] = (int)si.size();
+        const double fsx1 = dx * scale;
+        const double fsx2 = fsx1 + scale;
+        const double cellWidth = std::min(scale, ssize - fsx1);
+        int sx1 = cv_ceil(fsx1), sx2 = cv_floor(fsx2);
+        sx2 = std::min(sx2, ssize - 1);
+        sx1 = std::min(sx1, sx2);
+        if (sx1 - fsx1 > 1e-3) {
+            si.push_back(sx1 - 1);
+            alpha.push_back((float)((sx1 - fsx1) / cellWidth));
+        }
+        for (int sx = sx1; sx < sx2; sx++) {
+            si.push_back(sx);
+            alpha.push_back(float(1.0 / cellWidth));
+        }
+        if (fsx2 - sx2 > 1e-3) {
+            si.push_back(sx2);
+            alpha.push_back((float)(std::min(std::min(fsx2 - sx2, 1.), cellWidth) / cellWidth));
+        }
+    }
+    start[dsize] = (int)si.size();
+}
+void make_area_tab(int sw, int sh, int dw, int dh, AreaTab& t)
+{
+    if (sw == dw && sh == dh) {
+        t.mode = 0;
+        return;
+    }
+    const double inv_scale_x = (double)dw / sw, inv_scale_y = (double)dh / sh;
+    const double scale_x = 1. / inv_scale_x, scale_y = 1. / inv_scale_y;
+    const int iscale_x = cv_round(scale_x), iscale_y = cv_round(scale_y);
+    if (fabs(scale_x - iscale_x) < DBL_EPSILON && fabs(scale_y - iscale_y) < DBL_EPSILON) {
+        t.mode = 1;
+        t.ix = iscale_x;
+        t.iy = iscale_y;
+        return;
+    }
+    t.mode = 2;
+    area_tab_1d(sw, dw, scale_x, t.xstart, t.xsi, t.xalpha);
+    area_tab_1d(sh, dh, scale_y, t.ystart, t.ysi, t.ybeta);
 }
 
 // FarnebackPolyExp constants — video/optflowgf.cpp; invG = G.inv(DECOMP_CHOLESKY) — core/lapack.cpp
@@ -243,6 +305,11 @@ struct Plan {
     float k19[24] = {0}, k9[16] = {0};
     int levels = 0;  // index of the coarsest level
     std::vector<LevelPlan> lv;
+    // tw_flow_area_init (initial flow fields -> the coarsest level): make_area_tab's mode, ratios, the output columns a
+    // workgroup stages through LDS (mode 1), and the device tables (mode 2)
+    int init_mode = 0, init_ix = 1, init_iy = 1, init_tw = 0;
+    int *d_ixs = nullptr, *d_ixi = nullptr, *d_iys = nullptr, *d_iyi = nullptr;
+    float *d_ixa = nullptr, *d_iyb = nullptr;
     std::vector<void*> owned;  // device allocations
     size_t owned_bytes = 0;    // ... and their total size (tw_debug_memory)
     unsigned long long last_use = 0;  // engine's plan clock at the last get_plan (LRU eviction)
@@ -259,6 +326,8 @@ struct Job {
     int png_ch[2] = {0, 0};  // tw_submit_png8: channels of the filtered rows staged in Ctx::d_filt (0: plain gray)
     tw_flow_out fout = {nullptr, 0, 0};  // tw_submit_*_flow: where the pair's final flow goes (data null: nowhere)
     bool fout_host = false;              // ... page-locked host memory: through Ctx::d_fstage and the engine's d2h_stream
+    tw_flow_in fin = {nullptr, 0, 0};    // tw_submit_*_flow_init: the pair's initial field (data null: zero start)
+    bool fin_staged = false;             // ... host memory, uploaded to Ctx::d_istage as dense rows
 };
 
 // One batch of pairs: host-side state that must outlive the asynchronous execution.
@@ -310,6 +379,13 @@ struct Ctx {
     size_t d_fstage_cap = 0;
     hipEvent_t ev_fexp = nullptr, ev_d2h = nullptr;
     long long d2h_ops_at_flush = 0;  // tw_engine::d2h_ops when this batch was launched
+    // tw_submit_*_flow_init (created on first use): the per-pair source table of tw_flow_area_init (pinned, [cap]; uploaded
+    // to tw_engine::d_fsrc), and the HBM staging of host fields (cap slots of dense rows in the field's layout), filled on
+    // the copy stream behind the same marks as the pairs' images
+    bool any_init = false, any_init_host = false;
+    FlowDst* h_fsrc = nullptr;
+    char* d_istage = nullptr;
+    size_t d_istage_cap = 0;
 };
 
 struct ProfPair {
@@ -450,6 +526,7 @@ struct tw_engine {
     long long d2h_ops = 0;
     int d2h_sync_skipped = 0;
     FlowDst* d_fdst = nullptr;
+    FlowDst* d_fsrc = nullptr;  // tw_submit_*_flow_init: the device copy of a batch's init source table ([cap], on first use)
     const uint8_t** d_ptrs = nullptr;  // [2*cap]
     int* d_count = nullptr;            // [cap]
     float2* d_grid = nullptr;          // [cap][G] dense grid samples (dx,dy)
@@ -761,6 +838,28 @@ tw_status get_plan(tw_engine* e, int w0, int h0, Plan** out)
                 free_plan(pl);
                 return s;
             }
+        }
+    }
+    {
+        // tw_flow_area_init: full resolution -> the coarsest level (INTER_AREA).  Mode 1 stages a tile of tw output columns'
+        // iy source rows (both channels) in at most 32 KB of LDS; blocks too large for that read memory directly (tw = 0)
+        const LevelPlan& C = pl->lv[pl->levels];
+        AreaTab t;
+        make_area_tab(w0, h0, C.w, C.h, t);
+        pl->init_mode = t.mode;
+        pl->init_ix = t.ix;
+        pl->init_iy = t.iy;
+        if (t.mode == 1) {
+            const int fit = 32768 / (t.ix * t.iy * 8);
+            pl->init_tw = fit >= 4 ? std::min(128, fit / 4 * 4) : 0;
+        }
+        tw_status s;
+        if (t.mode == 2 &&
+            ((s = upload_vec(e, pl, t.xstart, &pl->d_ixs)) || (s = upload_vec(e, pl, t.xsi, &pl->d_ixi)) ||
+             (s = upload_vec(e, pl, t.xalpha, &pl->d_ixa)) || (s = upload_vec(e, pl, t.ystart, &pl->d_iys)) ||
+             (s = upload_vec(e, pl, t.ysi, &pl->d_iyi)) || (s = upload_vec(e, pl, t.ybeta, &pl->d_iyb)))) {
+            free_plan(pl);
+            return s;
         }
     }
     // tw_pyr_23 eligibility: both levels are exact INTER_LINEAR reductions by 4 and 8 (sample columns s*x + s/2 - 1 and
@@ -1508,8 +1607,10 @@ void launch_blur(tw_engine* e, hipStream_t st, int w, int h, int ld, long long p
     }
 }
 
+// init_flow: the coarsest level's flow buffer already holds the pairs' first flow (tw_flow_area_init), not zero
 void launch_update(tw_engine* e, hipStream_t st, const Plan* pl, int k, const float* R, float* flow,
-                   const float* prev, float* M, int npairs, const SideJob* side = nullptr, bool* side_used = nullptr)
+                   const float* prev, float* M, int npairs, const SideJob* side = nullptr, bool* side_used = nullptr,
+                   bool init_flow = false)
 {
     const LevelPlan& L = pl->lv[k];
     UpdArgs a;
@@ -1539,8 +1640,44 @@ void launch_update(tw_engine* e, hipStream_t st, const Plan* pl, int k, const fl
         a.scale = (float)(1. / e->p.pyrScale);
         launch_upd_kernel<true>(e, st, L.w, L.h, npairs, a, side, side_used);
     } else {
-        a.zero_flow = 1;
+        a.zero_flow = init_flow ? 0 : 1;
         launch_upd_kernel<false>(e, st, L.w, L.h, npairs, a, side, side_used);
+    }
+}
+
+// tw_submit_*_flow_init: the first flow of pairs [j0, j0 + nc) at the coarsest level — each pair's init field resized and
+// scaled (tw_flow_area_init), zeros for a pair without one — into `flow` (planar, the level's ld / ps), the buffer the
+// level's first FarnebackUpdateMatrices or first tw_flow_iter reads
+void launch_area_init(tw_engine* e, hipStream_t st, const Plan* pl, float* flow, int j0, int nc)
+{
+    const LevelPlan& L = pl->lv[pl->levels];
+    AreaInitArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = e->d_fsrc + j0;
+    a.flow = flow;
+    a.fps = L.ps;
+    a.ld = L.ld;
+    a.w = L.w;
+    a.h = L.h;
+    a.h0 = pl->h0;
+    a.mode = pl->init_mode;
+    a.ix = pl->init_ix;
+    a.iy = pl->init_iy;
+    a.inv_area = 1.f / (float)(pl->init_ix * pl->init_iy);  // (resizeAreaFast_Invoker: float scale = 1.f/(area))
+    a.tw = pl->init_tw;
+    a.scaled = fabs(L.scale - 1) >= DBL_EPSILON ? 1 : 0;  // convertTo's noScale: a copy
+    a.scale = (float)L.scale;
+    a.xstart = pl->d_ixs;
+    a.xsi = pl->d_ixi;
+    a.xalpha = pl->d_ixa;
+    a.ystart = pl->d_iys;
+    a.ysi = pl->d_iyi;
+    a.ybeta = pl->d_iyb;
+    if (a.mode == 1 && a.tw > 0) {
+        const size_t lds = (size_t)a.tw * a.ix * a.iy * 2 * sizeof(float);
+        TW_LAUNCH(e, TW_DF_FLOW_INIT, tw_flow_area_init, dim3((L.w + a.tw - 1) / a.tw, L.h, nc), dim3(256), lds, st, a);
+    } else {
+        TW_LAUNCH(e, TW_DF_FLOW_INIT, tw_flow_area_init, dim3((L.w + 63) / 64, (L.h + 3) / 4, nc), dim3(256), 0, st, a);
     }
 }
 
@@ -1644,8 +1781,8 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
         else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(2 * n), dim3(64), 0, e->copy_stream, pa);
     }
     c.copy_ops_at_flush = e->copy_ops;
-    if (c.any_host) {
-        // the uploads were queued on the copy stream as the jobs came in (submit_common)
+    if (c.any_host || c.any_init_host) {
+        // the uploads (images, and host initial flow fields) were queued on the copy stream as the jobs came in (submit_common)
         TW_HIP(e, hipEventRecord(c.ev_h2d, e->copy_stream));
         // cold-start ramp: nothing of an earlier batch is still running on the compute stream (the first batch after a
         // pause, or a pipeline the host cannot keep filled) — the pairs whose uploads are already marked start now, the
@@ -1663,7 +1800,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
         }
         ramp_b[ramp_n++] = n;
         if (ramp_n == 2) TW_HIP(e, hipStreamWaitEvent(st, c.ev_h2d, 0));  // (no ramp: the whole batch behind its last upload)
-        stride = c.w;
+        if (c.any_host) stride = c.w;
     }
     bool al4 = (stride % 4) == 0;
     for (int j = 0; j < n; j++) {
@@ -1691,6 +1828,19 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
             d.pad = 0;
         }
         TW_HIP(e, hipMemcpyAsync((void*)e->d_fdst, c.h_fdst, sizeof(FlowDst) * n, hipMemcpyHostToDevice, st));
+    }
+    if (c.any_init) {
+        // tw_flow_area_init's source table: the caller's device memory in place, this context's staging slot (dense rows
+        // in the field's layout) for a host field, null (zeros) for a pair without one
+        for (int j = 0; j < n; j++) {
+            const Job& jb = c.jobs[j];
+            FlowDst& d = c.h_fsrc[j];
+            d.p = !jb.fin.data ? nullptr : jb.fin_staged ? c.d_istage + fslot * j : (char*)jb.fin.data;
+            d.pitch = jb.fin_staged ? (long long)c.w * (jb.fin.layout ? 8 : 4) : (long long)jb.fin.pitch;
+            d.layout = jb.fin.layout;
+            d.pad = 0;
+        }
+        TW_HIP(e, hipMemcpyAsync((void*)e->d_fsrc, c.h_fsrc, sizeof(FlowDst) * n, hipMemcpyHostToDevice, st));
     }
     TW_HIP(e, hipEventRecord(c.ev_start, st));
     const int it = e->p.pyrIterations;
@@ -1925,12 +2075,16 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
                 const bool grid_only = k == 0 && fused_final;
                 bool iterated = false;
                 bool grid_stored = false;  // the last window launch wrote the span-grid samples itself (single pair)
+                // a batch with initial flow fields: every chunk of the coarsest level starts from tw_flow_area_init's output
+                // (zeros for its pairs without a field) through the non-zero-flow kernels
+                const bool init_lv = c.any_init && k == pl->levels;
                 // (with the scan-fused last iteration: it - 1 iterations here, then the M of the last flow from
                 // tw_update_matrices<false> into M1 — tw_blur_grid evaluates the window average + solve at the span-grid
                 // points from it; a single iteration has no flow of this level to start from and takes the old launches)
                 if (level_mfree(k, nc)) {
                     const int nfi = grid_only ? it - 1 : it;
                     float* buf[2] = {flow_cur, M0};  // iteration i writes buf[(nfi - 1 - i) & 1]: the last one the flow buffer
+                    if (init_lv) launch_area_init(e, ls, pl, buf[nfi & 1], j0, nc);  // (what iteration 0 reads)
                     FlowUps ups;
                     if (k < pl->levels) {
                         const LevelPlan& Pv = pl->lv[k + 1];
@@ -1939,7 +2093,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
                     }
                     for (int i = 0; i < nfi; i++) {
                         float* out = buf[(nfi - 1 - i) & 1];
-                        const float* in = i == 0 ? nullptr : buf[(nfi - i) & 1];
+                        const float* in = i == 0 ? (init_lv ? buf[nfi & 1] : nullptr) : buf[(nfi - i) & 1];
                         launch_flow_iter(e, ls, L.w, L.h, L.ld, L.ps, R, in, L.ps, out, L.ps,
                                          (i == 0 && k < pl->levels) ? &ups : nullptr, nc, k);
                     }
@@ -1975,12 +2129,13 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
                     iterated = true;
                 }
                 if (!iterated) {
+                    if (init_lv) launch_area_init(e, ls, pl, flow_cur, j0, nc);
                     if (lat2 && k >= 1 && side_ok(k, false)) {
                         bool used = false;
-                        launch_update(e, ls, pl, k, R, flow_cur, flow_prev, M0, nc, side_peek(), &used);
+                        launch_update(e, ls, pl, k, R, flow_cur, flow_prev, M0, nc, side_peek(), &used, init_lv);
                         side_done(used);
                     } else {
-                        launch_update(e, ls, pl, k, R, flow_cur, flow_prev, M0, nc);
+                        launch_update(e, ls, pl, k, R, flow_cur, flow_prev, M0, nc, nullptr, nullptr, init_lv);
                     }
                 }
                 for (int i = 0; i < it && !iterated; i++) {
@@ -2056,7 +2211,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     // is slower (0.55 ms: kernels of the forked branch stretch to ~40 us quanta behind cross-queue signals), so the
     // direct path is the default and the graph an opt-in A/B switch (profiles/r03_latency.md).
     bool launched_graph = false;
-    if (lat && e->lat_graph && !prof_on && !c.any_fout) {  // (destinations would be baked into the graph)
+    if (lat && e->lat_graph && !prof_on && !c.any_fout && !c.any_init) {  // (destinations / fields would be baked into the graph)
         const GraphKey key{c.w, c.h, c.span, stride, e->img_aligned4, e->scan_fused, e->poly_f32};
         auto git = e->lat_graphs.find(key);
         if (git == e->lat_graphs.end()) {
@@ -2212,43 +2367,59 @@ bool host_range_is_page_locked(const void* p, size_t n) { return pin_registry().
 
 size_t png_rows_bytes(int width, int height, int ch) { return (size_t)height * ((size_t)width * (size_t)ch + 1); }
 
-// A tw_submit_*_flow destination, checked before anything is queued: *host = a page-locked block the library knows
-// (the export goes through the context's staging), otherwise device memory of this engine's device that holds the
-// whole field.  Anything else — pageable memory above all — is refused.
-tw_status check_flow_out(tw_engine* e, const tw_flow_out* o, int w, int h, bool* host)
+// A flow field of w x h at (data, pitch, layout) — a tw_submit_*_flow destination or a tw_submit_*_flow_init source —
+// checked before anything is queued.  *kind = 1: a page-locked host block the library knows; 0: device memory of this
+// engine's device that holds the whole field; 2: any other host memory (the caller decides: a destination refuses it).
+// A bad pitch or layout, memory of another device, or a device field that overruns its allocation is refused here.
+tw_status check_flow_field(tw_engine* e, const void* data, ptrdiff_t pitch, int layout, int w, int h, const char* what,
+                           int* kind)
 {
-    const size_t row = (size_t)w * (o->layout == TW_FLOW_INTERLEAVED ? 8 : 4);
-    if (!o->data || (o->layout != TW_FLOW_PLANAR && o->layout != TW_FLOW_INTERLEAVED) || o->pitch < (ptrdiff_t)row ||
-        o->pitch % 4 != 0) {
-        e->err = "bad flow destination (null data, unknown layout, or a pitch below the row or not a multiple of 4)";
+    const size_t row = (size_t)w * (layout == TW_FLOW_INTERLEAVED ? 8 : 4);
+    if (!data || (layout != TW_FLOW_PLANAR && layout != TW_FLOW_INTERLEAVED) || pitch < (ptrdiff_t)row || pitch % 4 != 0) {
+        e->err = std::string("bad ") + what + " (null data, unknown layout, or a pitch below the row or not a multiple of 4)";
         return TW_E_BAD_PARAMETER;
     }
-    const size_t rows = (size_t)h * (o->layout == TW_FLOW_INTERLEAVED ? 1 : 2);
-    const size_t extent = (size_t)o->pitch * (rows - 1) + row;
-    if (pin_registry().covers(o->data, extent)) {
-        *host = true;
+    const size_t rows = (size_t)h * (layout == TW_FLOW_INTERLEAVED ? 1 : 2);
+    const size_t extent = (size_t)pitch * (rows - 1) + row;
+    if (pin_registry().covers(data, extent)) {
+        *kind = 1;
         return TW_OK;
     }
-    *host = false;
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof(at));
-    if (hipPointerGetAttributes(&at, o->data) != hipSuccess || at.type != hipMemoryTypeDevice) {
+    if (hipPointerGetAttributes(&at, data) != hipSuccess || at.type != hipMemoryTypeDevice) {
         (void)hipGetLastError();
-        e->err = "flow destination is neither device memory nor a page-locked block of tw_host_alloc / tw_host_register";
-        return TW_E_BAD_PARAMETER;
+        *kind = 2;
+        return TW_OK;
     }
     if (at.device != e->device) {
-        e->err = "flow destination is memory of another device";
+        e->err = std::string(what) + " is memory of another device";
         return TW_E_BAD_PARAMETER;
     }
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, o->data) != hipSuccess ||
-        (uintptr_t)o->data + extent > (uintptr_t)base + size) {
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(data)) != hipSuccess ||
+        (uintptr_t)data + extent > (uintptr_t)base + size) {
         (void)hipGetLastError();
-        e->err = "flow destination does not hold the whole field";
+        e->err = std::string(what) + " does not hold the whole field";
         return TW_E_BAD_PARAMETER;
     }
+    *kind = 0;
+    return TW_OK;
+}
+
+// A tw_submit_*_flow destination: *host = a page-locked block the library knows (the export goes through the context's
+// staging), otherwise device memory of this engine's device.  Anything else — pageable memory above all
+// — is refused.
+tw_status check_flow_out(tw_engine* e, const tw_flow_out* o, int w, int h, bool* host)
+{
+    int kind = 0;
+    TW_TRY(check_flow_field(e, o->data, o->pitch, o->layout, w, h, "flow destination", &kind));
+    if (kind == 2) {
+        e->err = "flow destination is neither device memory nor a page-locked block of tw_host_alloc / tw_host_register";
+        return TW_E_BAD_PARAMETER;
+    }
+    *host = kind == 1;
     return TW_OK;
 }
 
@@ -2256,7 +2427,7 @@ tw_status check_flow_out(tw_engine* e, const tw_flow_out* o, int w, int h, bool*
 // fo (tw_submit_*_flow): where the pair's final flow goes, null for the plain calls
 tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, const void* d_a, const void* d_b,
                         int width, int height, ptrdiff_t stride, int span, double threshold, tw_ticket* ticket,
-                        int ch_a = 0, int ch_b = 0, const tw_flow_out* fo = nullptr)
+                        int ch_a = 0, int ch_b = 0, const tw_flow_out* fo = nullptr, const tw_flow_in* fi = nullptr)
 {
     if (!e) return TW_E_BAD_PARAMETER;
     e->err.clear();
@@ -2295,6 +2466,11 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
         if (!e->d_fdst) TW_HIP(e, hipMalloc((void**)&e->d_fdst, sizeof(FlowDst) * (size_t)e->cap + 256));
         if (fo_host && !e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
     }
+    int fi_kind = 0;  // tw_submit_*_flow_init: 0 device memory (read in place), 1 page-locked, 2 other host memory
+    if (fi) {
+        TW_TRY(check_flow_field(e, fi->data, fi->pitch, fi->layout, width, height, "initial flow field", &fi_kind));
+        if (!e->d_fsrc) TW_HIP(e, hipMalloc((void**)&e->d_fsrc, sizeof(FlowDst) * (size_t)e->cap + 256));
+    }
     // host images are staged densely; device images are read in place with their own row stride
     const long long eff_stride = h_a ? (long long)width : (long long)stride;
     Ctx* c = &e->ctx[e->cur];
@@ -2329,6 +2505,8 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
         c->any_png = false;
         c->any_fout = false;
         c->any_fout_host = false;
+        c->any_init = false;
+        c->any_init_host = false;
         c->filt_slot = 0;
         c->nseg = 0;
         c->first_ticket = e->next_ticket;
@@ -2337,6 +2515,42 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
         if (!c->h_fdst) TW_HIP(e, hipHostMalloc((void**)&c->h_fdst, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
         if (!c->ev_fexp) TW_HIP(e, hipEventCreateWithFlags(&c->ev_fexp, hipEventDisableTiming));
         if (!c->ev_d2h) TW_HIP(e, hipEventCreateWithFlags(&c->ev_d2h, hipEventDisableTiming));
+    }
+    if (fi && !c->h_fsrc) TW_HIP(e, hipHostMalloc((void**)&c->h_fsrc, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
+    if (fi && fi_kind != 0) {
+        // a host field: to this context's staging slot on the copy stream, queued before the pair's ramp mark below —
+        // DMA-ed in place from a page-locked block (the caller keeps it until tw_wait), through the engine's pinned bounce
+        // buffer from any other memory (copied before this call returns, as pageable images are)
+        const size_t fslot = flow_stage_slot(width, height);
+        if (fslot * e->cap > c->d_istage_cap) {
+            // only on the first host field of a batch (one size per batch); this context's earlier batches are waited
+            TW_HIP(e, hipStreamSynchronize(e->copy_stream));
+            if (c->d_istage) (void)hipFree(c->d_istage);
+            c->d_istage = nullptr;
+            c->d_istage_cap = 0;
+            TW_HIP(e, hipMalloc((void**)&c->d_istage, fslot * e->cap + 256));
+            c->d_istage_cap = fslot * e->cap;
+        }
+        char* dst = c->d_istage + fslot * c->jobs.size();
+        const size_t row = (size_t)width * (fi->layout ? 8 : 4), rows = (size_t)height * (fi->layout ? 1 : 2);
+        if (fi_kind == 1) {
+            if ((size_t)fi->pitch == row)
+                TW_HIP(e, hipMemcpyAsync(dst, fi->data, row * rows, hipMemcpyHostToDevice, e->copy_stream));
+            else
+                TW_HIP(e, hipMemcpy2DAsync(dst, row, fi->data, (size_t)fi->pitch, row, rows, hipMemcpyHostToDevice,
+                                           e->copy_stream));
+        } else {
+            const size_t per = std::max<size_t>(1, BOUNCE_CHUNK / row);  // rows per bounce transfer
+            TW_TRY(bounce_reserve(e, std::min(rows, per) * row));
+            for (size_t r0 = 0; r0 < rows; r0 += per) {
+                const size_t nr = std::min(per, rows - r0);
+                for (size_t y = 0; y < nr; y++)
+                    memcpy(e->h_bounce + y * row, (const char*)fi->data + (r0 + y) * (size_t)fi->pitch, row);
+                TW_HIP(e, hipMemcpyAsync(dst + r0 * row, e->h_bounce, nr * row, hipMemcpyHostToDevice, e->copy_stream));
+                TW_HIP(e, hipStreamSynchronize(e->copy_stream));
+            }
+        }
+        e->copy_ops++;
     }
     Job jb;
     jb.stride = eff_stride;
@@ -2466,6 +2680,12 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
         jb.fout_host = fo_host;
         c->any_fout = true;
         c->any_fout_host = c->any_fout_host || fo_host;
+    }
+    if (fi) {
+        jb.fin = *fi;
+        jb.fin_staged = fi_kind != 0;
+        c->any_init = true;
+        c->any_init_host = c->any_init_host || fi_kind != 0;
     }
     c->jobs.push_back(jb);
     c->pending++;
@@ -2719,6 +2939,8 @@ void tw_engine_destroy(tw_engine* e)
         if (c.h_rec) (void)hipHostFree(c.h_rec);
         if (c.d_fstage) (void)hipFree(c.d_fstage);
         if (c.h_fdst) (void)hipHostFree(c.h_fdst);
+        if (c.d_istage) (void)hipFree(c.d_istage);
+        if (c.h_fsrc) (void)hipHostFree(c.h_fsrc);
         if (c.ev_fexp) (void)hipEventDestroy(c.ev_fexp);
         if (c.ev_d2h) (void)hipEventDestroy(c.ev_d2h);
         if (c.ev_start) (void)hipEventDestroy(c.ev_start);
@@ -2730,6 +2952,7 @@ void tw_engine_destroy(tw_engine* e)
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
     if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
     if (e->d_fdst) (void)hipFree(e->d_fdst);
+    if (e->d_fsrc) (void)hipFree(e->d_fsrc);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
     for (auto& kv : e->plans) free_plan(kv.second);
@@ -2788,6 +3011,32 @@ tw_status tw_submit_dev_flow(tw_engine* e, const void* d_expect, const void* d_t
     return submit_common(e, nullptr, nullptr, d_expect, d_target, width, height, stride, span, threshold, ticket, 0, 0, out);
 }
 
+tw_status tw_submit_u8_flow_init(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
+                                 ptrdiff_t stride, int span, double threshold, const tw_flow_in* init,
+                                 const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!expect || !target) return TW_E_BAD_PARAMETER;
+    return submit_common(e, expect, target, nullptr, nullptr, width, height, stride, span, threshold, ticket, 0, 0, out,
+                         init);
+}
+
+tw_status tw_submit_png8_flow_init(tw_engine* e, const uint8_t* expect, int expect_channels, const uint8_t* target,
+                                   int target_channels, int width, int height, int span, double threshold,
+                                   const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    return submit_common(e, expect, target, nullptr, nullptr, width, height, width, span, threshold, ticket,
+                         expect_channels, target_channels, out, init);
+}
+
+tw_status tw_submit_dev_flow_init(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
+                                  ptrdiff_t stride, int span, double threshold, const tw_flow_in* init,
+                                  const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!d_expect || !d_target) return TW_E_BAD_PARAMETER;
+    return submit_common(e, nullptr, nullptr, d_expect, d_target, width, height, stride, span, threshold, ticket, 0, 0,
+                         out, init);
+}
+
 tw_status tw_flush(tw_engine* e)
 {
     if (!e) return TW_E_BAD_PARAMETER;
@@ -2813,7 +3062,7 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
         return r;
     }
     hipError_t herr = hipEventSynchronize(c->ev_done);
-    if (c->any_host && c->pending == (int)c->jobs.size()) {
+    if ((c->any_host || c->any_init_host) && c->pending == (int)c->jobs.size()) {
         // Once per batch the host synchronises the copy stream.  Nothing else ever waits on it from the host (the
         // compute stream does, through ev_h2d), and this runtime releases a stream's per-command bookkeeping only on
         // a host-side hipStreamSynchronize: without it the process grew by ~1 KB per uploaded image (found by a
@@ -3285,7 +3534,8 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_export"};
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_area_init",
+        "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
 }
 
@@ -3295,7 +3545,8 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // device: the level workspace (I + 5 I for R + 2 x 2.5 I for M), the single-pair schedule's I / R, the box window's column
     // sums, flow planes, the dense grid, pointer / count tables, debug stamps, every context's images, filtered rows, PNG job
-    // table, records and flow staging, the flow destination table, and the plans' tables (each allocation with the slack it was made with)
+    // table, records, flow staging and initial-field staging, the flow destination and source tables, and the plans' tables
+    // (each allocation with the slack it was made with)
     if (e->I) v[0] += (e->ws_elems * 4 + 256) + (e->ws_elems * 5 * 4 + 256) + 2 * (e->ws_elems / 2 * 5 * 4 + 256);
     if (e->lat_I) v[0] += (e->lat_cap * 4 + 256) + (e->lat_cap * 5 * 4 + 256);
     if (e->Vd) v[0] += e->Vd_cap * sizeof(double) + 256;
@@ -3306,7 +3557,10 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     if (e->d_count) v[0] += sizeof(int) * (size_t)e->cap + 256;
     if (e->dbg_stamps) v[0] += 4096 * sizeof(unsigned long long);
     if (e->d_fdst) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
+    if (e->d_fsrc) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
     for (const Ctx& c : e->ctx) {
+        if (c.d_istage) v[0] += c.d_istage_cap + 256;
+        if (c.h_fsrc) v[1] += sizeof(FlowDst) * (size_t)e->cap;
         if (c.d_fstage) v[0] += c.d_fstage_cap + 256;
         if (c.h_fdst) v[1] += sizeof(FlowDst) * (size_t)e->cap;
         if (c.d_img) v[0] += c.d_img_cap + 256;

@@ -4146,6 +4146,159 @@ __global__ __launch_bounds__(256) void tw_flow_export(ExportArgs a)
     }
 }
 
+// -----------------------------------------------------------------------------------------------------
+// tw_flow_area_init : OPTFLOW_USE_INITIAL_FLOW.  Each pair's full-resolution init field (tw_submit_*_flow_init; planar or
+//   (dx, dy)-interleaved at its own row pitch) -> resize(flow0, coarsest size, INTER_AREA) * scale, into the coarsest
+//   level's planar flow buffer (rows ld floats apart) that the level's first FarnebackUpdateMatrices / first iteration
+//   reads.  A pair without a field (null source) gets zeros.  OpenCV 2.4.9 imgwarp.cpp on CV_32FC2, every channel alike:
+//   mode 0 (same size): a copy.
+//   mode 1 (both ratios integers: resizeAreaFast_Invoker<float,float>): the ix x iy block, offsets row-major, summed as
+//     sum += ((S0 + S1) + S2) + S3 per group of four (CV_ENABLE_UNROLLED), then the rest one by one, then sum * (1.f/area).
+//     A workgroup stages its tile's iy source rows through LDS with 16-byte loads (the kernel is a read stream: 16.6 MB
+//     per 1080p pair for 0.26 MB written), then each output lane sums its block from LDS in that order — no cross-lane
+//     reduction, which would change the order.  tw = 0: blocks too large for the LDS budget read memory directly.
+//   mode 2 (ResizeArea_Invoker with computeResizeAreaTab's tables, made on the host in double): per output row
+//     entry j, buf = buf + S * alpha over the column's entries (buf from 0), then sum = beta_0 * buf_0, sum += beta_j * buf_j.
+//   Then convertTo(scale): v * scale + 0.f unless the level's scale is 1 (a plain copy).  Every product is a separate
+//   multiply and add (the library builds with -ffp-contract=off).  Source offsets in 64 bits (a full-resolution field is
+//   up to 2 GB).
+// -----------------------------------------------------------------------------------------------------
+struct AreaInitArgs {
+    const FlowDst* src;   // pair z: src[z] (p null: zero flow)
+    float* flow;          // pair z: 2 planes at flow + z*2*fps
+    long long fps;
+    int ld, w, h;         // the coarsest level
+    int h0;               // full-resolution rows (plane y of a planar field starts at p + pitch * h0)
+    int mode;             // 0 copy, 1 integer ratios, 2 area tables
+    int ix, iy;           // mode 1: ratios
+    float inv_area;       // mode 1: 1.f / (ix * iy)
+    int tw;               // mode 1: output columns per workgroup (a multiple of 4; 0: no LDS staging)
+    int scaled;           // multiply by scale (0: the level's scale is 1)
+    float scale;
+    const int *xstart, *xsi, *ystart, *ysi;  // mode 2: output x's column entries are [xstart[x], xstart[x + 1])
+    const float *xalpha, *ybeta;
+};
+
+__device__ __forceinline__ float area_src(const FlowDst& d, int h0, long long y, long long x, int c)
+{
+    const char* p = d.layout == 1 ? d.p + y * d.pitch + (2 * x + c) * 4 : d.p + ((long long)c * h0 + y) * d.pitch + x * 4;
+    return *(const float*)p;
+}
+__device__ __forceinline__ float area_scale(const AreaInitArgs& a, float v)
+{
+    if (!a.scaled) return v;
+    const float t = v * a.scale;
+    return t + 0.f;
+}
+// the ix x iy block sum in resizeAreaFast_Invoker's order; S(k) = element k of the block, row-major
+template <typename F>
+__device__ __forceinline__ float area_fast_sum(int area, F S)
+{
+    float sum = 0.f;
+    int k = 0;
+    for (; k <= area - 4; k += 4) {
+        const float g = ((S(k) + S(k + 1)) + S(k + 2)) + S(k + 3);
+        sum = sum + g;
+    }
+    for (; k < area; k++) sum = sum + S(k);
+    return sum;
+}
+
+__global__ __launch_bounds__(256) void tw_flow_area_init(AreaInitArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float area_lds[];  // mode 1 staged: [2][iy][tw * ix]
+    const FlowDst d = a.src[blockIdx.z];
+    float* __restrict__ out = a.flow + (long long)blockIdx.z * 2 * a.fps;
+    const int tid = threadIdx.x;
+    if (a.mode == 1 && a.tw > 0) {
+        const int X0 = blockIdx.x * a.tw, nx = min(a.tw, a.w - X0), dy = blockIdx.y;
+        const int rw = nx * a.ix, RW = a.tw * a.ix, area = a.ix * a.iy;
+        if (d.p) {
+            const long long sy0 = (long long)dy * a.iy;
+            // (X0 is a multiple of 4: a tile's first source element is 16-byte aligned when the field's base and pitch are)
+            const bool al = (((unsigned long long)(uintptr_t)d.p | (unsigned long long)d.pitch) & 15ull) == 0;
+            if (d.layout == 1) {
+                const int nf = 2 * rw, nv = al ? nf / 4 : 0;
+                for (int i = tid; i < a.iy * nv; i += 256) {
+                    const int r = i / nv, q = i - r * nv;
+                    const float4 v = *(const float4*)((const float*)(d.p + (sy0 + r) * d.pitch) + 2ll * X0 * a.ix + 4 * q);
+                    float* l0 = area_lds + (long long)r * RW + 2 * q;
+                    float* l1 = l0 + (long long)a.iy * RW;
+                    l0[0] = v.x;
+                    l1[0] = v.y;
+                    l0[1] = v.z;
+                    l1[1] = v.w;
+                }
+                const int tail = nf - 4 * nv;
+                for (int i = tid; i < a.iy * tail; i += 256) {
+                    const int r = i / tail, f = 4 * nv + (i - r * tail);
+                    const float v = ((const float*)(d.p + (sy0 + r) * d.pitch))[2ll * X0 * a.ix + f];
+                    area_lds[((long long)(f & 1) * a.iy + r) * RW + (f >> 1)] = v;
+                }
+            } else {
+                const int nv = al ? rw / 4 : 0, tail = rw - 4 * nv;
+                for (int i = tid; i < 2 * a.iy * nv; i += 256) {
+                    const int rc = i / nv, q = i - rc * nv, c = rc / a.iy, r = rc - c * a.iy;
+                    const float4 v = *(const float4*)((const float*)(d.p + ((long long)c * a.h0 + sy0 + r) * d.pitch) +
+                                                      (long long)X0 * a.ix + 4 * q);
+                    *(float4*)(area_lds + (long long)rc * RW + 4 * q) = v;
+                }
+                for (int i = tid; i < 2 * a.iy * tail; i += 256) {
+                    const int rc = i / tail, f = 4 * nv + (i - rc * tail), c = rc / a.iy, r = rc - c * a.iy;
+                    area_lds[(long long)rc * RW + f] =
+                        ((const float*)(d.p + ((long long)c * a.h0 + sy0 + r) * d.pitch))[(long long)X0 * a.ix + f];
+                }
+            }
+            __syncthreads();
+        }
+        for (int t = tid; t < 2 * nx; t += 256) {
+            const int c = t / nx, x = t - c * nx;
+            float v = 0.f;
+            if (d.p) {
+                const float* B = area_lds + (long long)c * a.iy * RW + x * a.ix;
+                const int ix = a.ix;
+                v = area_fast_sum(area, [&](int k) { const int r = k / ix; return B[r * RW + (k - r * ix)]; });
+                v = area_scale(a, v * a.inv_area);
+            }
+            out[(long long)c * a.fps + (long long)dy * a.ld + X0 + x] = v;
+        }
+        return;
+    }
+    const int x = blockIdx.x * 64 + (tid & 63), y = blockIdx.y * 4 + (tid >> 6);
+    if (x >= a.w || y >= a.h) return;
+    float v[2] = {0.f, 0.f};
+    if (d.p) {
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            float s;
+            if (a.mode == 0) {
+                s = area_src(d, a.h0, y, x, c);
+            } else if (a.mode == 1) {
+                const long long sy0 = (long long)y * a.iy, sx0 = (long long)x * a.ix;
+                const int ix = a.ix;
+                s = area_fast_sum(ix * a.iy, [&](int k) { const int r = k / ix; return area_src(d, a.h0, sy0 + r, sx0 + (k - r * ix), c); });
+                s = s * a.inv_area;
+            } else {
+                s = 0.f;
+                const int j0 = a.ystart[y], j1 = a.ystart[y + 1], k0 = a.xstart[x], k1 = a.xstart[x + 1];
+                for (int j = j0; j < j1; j++) {
+                    const int sy = a.ysi[j];
+                    float b = 0.f;
+                    for (int k = k0; k < k1; k++) {
+                        const float t = area_src(d, a.h0, sy, a.xsi[k], c) * a.xalpha[k];
+                        b = b + t;
+                    }
+                    const float bb = a.ybeta[j] * b;
+                    s = j == j0 ? bb : s + bb;
+                }
+            }
+            v[c] = area_scale(a, s);
+        }
+    }
+    out[(long long)y * a.ld + x] = v[0];
+    out[a.fps + (long long)y * a.ld + x] = v[1];
+}
+
 struct ScanArgs {
     const float2* g;  // pair z: dense grid samples at g + z*G
     int span, gw, gh;

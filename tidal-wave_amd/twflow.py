@@ -40,6 +40,11 @@ class FlowOut(C.Structure):
     _fields_ = [("data", C.c_void_p), ("pitch", C.c_ssize_t), ("layout", C.c_int)]
 
 
+class FlowIn(C.Structure):
+    # tw_flow_in (include/twflow.h): a pair's initial flow field for the tw_submit_*_flow_init calls
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_ssize_t), ("layout", C.c_int)]
+
+
 FLOW_PLANAR, FLOW_INTERLEAVED = 0, 1
 
 
@@ -59,6 +64,7 @@ SYMBOLS = [
     "tw_default_params", "tw_abi_version", "tw_has_variants", "tw_device_count", "tw_device_pci_bus_id", "tw_engine_create", "tw_engine_destroy", "tw_strerror",
     "tw_last_error", "tw_flow_u8", "tw_diff_u8", "tw_submit_u8", "tw_submit_png8", "tw_submit_dev", "tw_flush", "tw_wait",
     "tw_submit_u8_flow", "tw_submit_png8_flow", "tw_submit_dev_flow",
+    "tw_submit_u8_flow_init", "tw_submit_png8_flow_init", "tw_submit_dev_flow_init",
     "tw_grid_capacity", "tw_dev_alloc", "tw_dev_free", "tw_dev_upload", "tw_dev_download", "tw_host_alloc", "tw_host_free", "tw_host_register", "tw_host_unregister", "tw_set_option",
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
@@ -135,6 +141,11 @@ def _bind(path):
     L.tw_submit_u8_flow.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_double, fop, tkp]
     L.tw_submit_png8_flow.argtypes = [vp, u8p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, fop, tkp]
     L.tw_submit_dev_flow.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_double, fop, tkp]
+    fip = C.POINTER(FlowIn)
+    L.tw_submit_u8_flow_init.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_double, fip, fop, tkp]
+    L.tw_submit_png8_flow_init.argtypes = [vp, u8p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, fip,
+                                           fop, tkp]
+    L.tw_submit_dev_flow_init.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_double, fip, fop, tkp]
     L.tw_wait.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, fp]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
@@ -257,6 +268,37 @@ def _flow_out(flow, w, h):
                   "unit-stride rows, got shape %r strides %r" % (h, w, h, w, shape, strides))
 
 
+def _flow_in(init, w, h):
+    """A submit's `init=` argument -> (FlowIn, the object to keep alive) (None: zero start).  Accepted: a float32 numpy
+    array in any host memory (page-locked memory of Engine.host_array is DMA-ed in place, any other is copied by the
+    library before the submit returns), a float32 torch tensor on the engine's device, shaped (2, h, w) planar or
+    (h, w, 2) interleaved (rows may be padded), or a raw (pointer, pitch, layout) tuple (a device pointer, say)."""
+    if init is None:
+        return None, None
+    if isinstance(init, tuple):
+        ptr, pitch, layout = init
+        return FlowIn(ptr, pitch, layout), None
+    if isinstance(init, np.ndarray):
+        if init.dtype != np.float32:
+            raise TwError(TW_E_BAD_PARAMETER, "initial flow must be float32")
+        if init.ndim == 3 and init.strides[-1] != 4:
+            init = np.ascontiguousarray(init)
+        shape, strides, ptr = init.shape, init.strides, init.ctypes.data
+    elif type(init).__module__.startswith("torch"):
+        import torch
+        if init.dtype != torch.float32 or not init.is_cuda:
+            raise TwError(TW_E_BAD_PARAMETER, "initial flow tensor must be float32 on the GPU")
+        shape, strides, ptr = tuple(init.shape), tuple(s * 4 for s in init.stride()), init.data_ptr()
+    else:
+        raise TwError(TW_E_BAD_PARAMETER, "unsupported initial flow %r" % type(init))
+    if shape == (2, h, w) and strides[2] == 4 and strides[0] == strides[1] * h:
+        return FlowIn(ptr, strides[1], FLOW_PLANAR), init
+    if shape == (h, w, 2) and strides[2] == 4 and strides[1] == 8:
+        return FlowIn(ptr, strides[0], FLOW_INTERLEAVED), init
+    raise TwError(TW_E_BAD_PARAMETER, "initial flow must be (2, %d, %d) planar or (%d, %d, 2) interleaved with "
+                  "unit-stride rows, got shape %r strides %r" % (h, w, h, w, shape, strides))
+
+
 def _gray(a):
     a = np.asarray(a)
     if a.dtype != np.uint8 or a.ndim != 2:
@@ -331,8 +373,9 @@ class Engine:
         t = self.submit(expect, target, span, threshold)
         return self.wait(t)
 
-    def submit(self, expect, target, span=10, threshold=5.0, *, flow=None):
-        """flow: where the pair's final flow goes (tw_submit_u8_flow; see _flow_out), kept alive by the caller until wait()."""
+    def submit(self, expect, target, span=10, threshold=5.0, *, flow=None, init=None):
+        """flow: where the pair's final flow goes (tw_submit_u8_flow; see _flow_out), kept alive by the caller until wait().
+        init: the pair's initial flow field (tw_submit_u8_flow_init; see _flow_in), unchanged until wait()."""
         a, b = _gray(expect), _gray(target)
         if a.shape != b.shape:
             raise TwError(TW_E_DONT_MATCH_SIZE, "Don't match image size")
@@ -341,7 +384,11 @@ class Engine:
         h, w = a.shape
         tk = C.c_int64()
         fo = _flow_out(flow, w, h)
-        if fo is None:
+        fi, _keep = _flow_in(init, w, h)
+        if fi is not None:
+            self._check(self._L.tw_submit_u8_flow_init(self._h, _u8(a), _u8(b), w, h, a.strides[0], span, threshold,
+                                                       C.byref(fi), C.byref(fo) if fo is not None else None, C.byref(tk)))
+        elif fo is None:
             self._check(self._L.tw_submit_u8(self._h, _u8(a), _u8(b), w, h, a.strides[0], span, threshold, C.byref(tk)))
         else:
             self._check(self._L.tw_submit_u8_flow(self._h, _u8(a), _u8(b), w, h, a.strides[0], span, threshold,
@@ -355,14 +402,18 @@ class Engine:
         self._check(self._L.tw_submit_u8(self._h, p_expect, p_target, w, h, stride, span, threshold, C.byref(tk)))
         return (tk.value, w, h, span, threshold)
 
-    def submit_png8(self, expect, ch_a, target, ch_b, w, h, span=10, threshold=5.0, *, flow=None):
+    def submit_png8(self, expect, ch_a, target, ch_b, w, h, span=10, threshold=5.0, *, flow=None, init=None):
         """tw_submit_png8: each image is either filtered PNG rows (uint8 array of h * (1 + w * ch) bytes, ch 1-4) or a
-        plain gray image (ch 0, shape (h, w)).  flow: as for submit (tw_submit_png8_flow)."""
+        plain gray image (ch 0, shape (h, w)).  flow, init: as for submit (tw_submit_png8_flow[_init])."""
         a = np.ascontiguousarray(expect, np.uint8)
         b = np.ascontiguousarray(target, np.uint8)
         tk = C.c_int64()
         fo = _flow_out(flow, w, h)
-        if fo is None:
+        fi, _keep = _flow_in(init, w, h)
+        if fi is not None:
+            self._check(self._L.tw_submit_png8_flow_init(self._h, _u8(a), ch_a, _u8(b), ch_b, w, h, span, threshold,
+                                                         C.byref(fi), C.byref(fo) if fo is not None else None, C.byref(tk)))
+        elif fo is None:
             self._check(self._L.tw_submit_png8(self._h, _u8(a), ch_a, _u8(b), ch_b, w, h, span, threshold, C.byref(tk)))
         else:
             self._check(self._L.tw_submit_png8_flow(self._h, _u8(a), ch_a, _u8(b), ch_b, w, h, span, threshold,
@@ -376,23 +427,29 @@ class Engine:
         self._check(self._L.tw_stage_png_unfilter(self._h, _u8(rows), ch, w, h, waves, _u8(out)))
         return out
 
-    def submit_dev(self, d_expect, d_target, w, h, stride, span=10, threshold=5.0, *, flow=None):
-        """flow: as for submit (tw_submit_dev_flow)."""
+    def submit_dev(self, d_expect, d_target, w, h, stride, span=10, threshold=5.0, *, flow=None, init=None):
+        """flow, init: as for submit (tw_submit_dev_flow[_init])."""
         tk = C.c_int64()
         fo = _flow_out(flow, w, h)
-        if fo is None:
+        fi, _keep = _flow_in(init, w, h)
+        if fi is not None:
+            self._check(self._L.tw_submit_dev_flow_init(self._h, d_expect, d_target, w, h, stride, span, threshold,
+                                                        C.byref(fi), C.byref(fo) if fo is not None else None, C.byref(tk)))
+        elif fo is None:
             self._check(self._L.tw_submit_dev(self._h, d_expect, d_target, w, h, stride, span, threshold, C.byref(tk)))
         else:
             self._check(self._L.tw_submit_dev_flow(self._h, d_expect, d_target, w, h, stride, span, threshold,
                                                    C.byref(fo), C.byref(tk)))
         return (tk.value, w, h, span, threshold)
 
-    def flow_batch(self, expects, targets, layout="interleaved", span=0, threshold=5.0):
+    def flow_batch(self, expects, targets, layout="interleaved", span=0, threshold=5.0, init=None):
         """Dense flow fields of N pairs through the batched API.  numpy inputs (N 2-D uint8 images each): returns a
         page-locked float32 array [N, H, W, 2] ("interleaved") or [N, 2, H, W] ("planar") — freed with the engine —
         and the per-pair result dicts of wait().  torch uint8 tensors [N, H, W] on the engine's device: submitted in place
         (tw_submit_dev_flow), the fields come back as a float32 tensor on that device (a torch program imports torch before
-        this module loads the library, as bench.py does: the process's HIP runtime must be torch's)."""
+        this module loads the library, as bench.py does: the process's HIP runtime must be torch's).
+        init: the pairs' initial flow fields (tw_submit_*_flow_init) — a sequence of N fields (None: that pair starts from
+        zero) or one stacked array / tensor [N, ...], each field as submit's init= takes it."""
         if layout not in ("interleaved", "planar"):
             raise TwError(TW_E_BAD_PARAMETER, "layout must be 'interleaved' or 'planar'")
         inter = layout == "interleaved"
@@ -407,12 +464,15 @@ class Engine:
             # the ABI takes no stream: the inputs and `out` may still be in flight on torch's stream
             torch.cuda.current_stream(expects.device).synchronize()
             sub = lambda i: self.submit_dev(expects[i].data_ptr(), targets[i].data_ptr(), w, h, expects.stride(1),  # noqa: E731
-                                            span, threshold, flow=out[i])
+                                            span, threshold, flow=out[i], init=None if init is None else init[i])
         else:
             a0 = _gray(expects[0])
             n, (h, w) = len(expects), a0.shape
             out = self.host_array((n, h, w, 2) if inter else (n, 2, h, w), np.float32)
-            sub = lambda i: self.submit(expects[i], targets[i], span, threshold, flow=out[i])  # noqa: E731
+            sub = lambda i: self.submit(expects[i], targets[i], span, threshold, flow=out[i],  # noqa: E731
+                                        init=None if init is None else init[i])
+        if init is not None and len(init) != n:
+            raise TwError(TW_E_BAD_PARAMETER, "init: %d fields for %d pairs" % (len(init), n))
         res, pending = [None] * n, []
         for i in range(n):
             if len(pending) >= 2 * self.slots:  # (at most NCTX batches in flight: collect the oldest first)
