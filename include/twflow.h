@@ -118,7 +118,10 @@ tw_status tw_diff_u8(tw_engine* e, const uint8_t* expect, const uint8_t* target,
                      float* seconds);
 
 /* Asynchronous pair of the same operation, for batching (the Manager queue keeps `slots` jobs in
- * flight per GPU).  The host images are copied to pinned staging before tw_submit_u8 returns. */
+ * flight per GPU).  The host images are copied to pinned staging before tw_submit_u8 returns.
+ * Sizes (every submit and tw_stage_* call): 1 .. 32768 pixels per side, else TW_E_BAD_PARAMETER; and
+ * round_up(width, 32) * height <= 214 748 364 = (2^32 - 1) / 20, else TW_E_UNSUPPORTED (five float planes behind one
+ * buffer resource with 32-bit offsets: 16384 x 13107 is admitted, 16384 x 13108 is not). */
 tw_status tw_submit_u8(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
                        ptrdiff_t stride, int span, double threshold, tw_ticket* ticket);
 /* The same pair handed over HALF-DECODED (ABI 3): what cv::imread(path, GRAYSCALE) of src/opticalflow.cpp:37,44 does to

@@ -17,6 +17,12 @@ extern "C" {
  * tests/test_gpu_parity.py uses it to prove that the graph path is what really ran. */
 int tw_debug_graphs(tw_engine* e);
 
+/* The size predicate of every submit and every tw_stage_* entry point, without a device: TW_OK when a width x height
+ * image is admitted, TW_E_BAD_PARAMETER outside 1 .. 32768 pixels per side, TW_E_UNSUPPORTED when round_up(width, 32) *
+ * height exceeds (2^32 - 1) / 20 = 214 748 364 — the five float planes that one raw buffer resource with 32-bit offsets
+ * addresses in the stencil kernels (tests/test_abi.py). */
+tw_status tw_debug_check_size(int width, int height);
+
 /* "kernel name: workgroups per CU" lines of the main kernels as the runtime admits them (tools/kbench.py).
  * Returns the number of bytes written to buf (at most cap, NUL-terminated). */
 int tw_debug_occupancy(char* buf, int cap);

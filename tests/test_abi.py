@@ -43,6 +43,46 @@ def test_abi_version_and_launch_families(twflow):
     assert L.tw_debug_launch_counts(None, None, None, 0, 0) == -1
 
 
+def test_size_predicate_matches_the_plane_addressing(twflow):
+    """tw_debug_check_size, the one size predicate of every submit and tw_stage_* entry point (no device): 1 .. 32768
+    pixels per side, and round_up(w, 32) * h * 20 bytes — five float planes behind one raw buffer resource with 32-bit
+    offsets — within 2^32 - 1.  The old bound, w * h <= 2^28, admitted sizes where plane 4's offset wraps to plane 0
+    (16384 x 16384, and 16383 x 16385 through the row padding) or leaves the 32-bit range (16384 x 13108)."""
+    import numpy as np
+    chk = twflow.lib().tw_debug_check_size
+    OK, BAD, UNS = twflow.TW_OK, twflow.TW_E_BAD_PARAMETER, twflow.TW_E_UNSUPPORTED
+    MAX_PS = (2 ** 32 - 1) // 20
+    ld = lambda w: -(-w // 32) * 32  # noqa: E731
+
+    def want(w, h):
+        if not (1 <= w <= 32768 and 1 <= h <= 32768):
+            return BAD
+        return OK if ld(w) * h <= MAX_PS else UNS
+
+    for w, h in ((16384, 16384), (16383, 16385), (16384, 13108)):
+        assert w * h <= 2 ** 28 and chk(w, h) == UNS, (w, h)
+    # ld padding: w = 8192 + r (ld 8224) — one row more than the bound admits, although w * h alone would fit
+    for r in range(1, 32):
+        w, hmax = 8192 + r, MAX_PS // 8224
+        assert chk(w, hmax) == OK and chk(w, hmax + 1) == UNS and w * (hmax + 1) <= MAX_PS, r
+    # the last admitted and the first refused ld * h on each side; 214 748 352 = 7616 x 28197 is the largest admitted
+    assert MAX_PS // 32 * 32 == 7616 * 28197 == 214748352
+    for ok, no in (((7616, 28197), (7616, 28198)), ((7616, 28197), (7617, 28197)), ((16384, 13107), (16384, 13108)),
+                   ((16353, 13107), (16385, 13107)), ((6528, 32768), (6529, 32768)), ((32768, 6553), (32768, 6554))):
+        assert chk(*ok) == OK and chk(*no) == UNS, (ok, no)
+    # 32768 and 32769 in each dimension
+    for w, h, s in ((32768, 1, OK), (1, 32768, OK), (32769, 1, BAD), (1, 32769, BAD), (32769, 32769, BAD),
+                    (32768, 32768, UNS), (0, 1, BAD), (1, 0, BAD), (-1, 5, BAD), (5, -32768, BAD)):
+        assert chk(w, h) == s, (w, h)
+    rng = np.random.default_rng(7)
+    sizes = [(int(w), int(h)) for w, h in rng.integers(-2, 33000, (3000, 2))]
+    for w in rng.integers(1, 32770, 500):
+        hb = MAX_PS // ld(int(w))
+        sizes += [(int(w), hb + d) for d in (-1, 0, 1)]
+    for w, h in sizes:
+        assert chk(w, h) == want(w, h), (w, h)
+
+
 def test_struct_layouts_match_reference(twflow):
     # OpticalFlowParameter (src/opticalflow.h:28-36): double,int,int,int,int,double,int
     assert C.sizeof(twflow.Params) == 40

@@ -93,10 +93,13 @@ def test_stage_png_unfilter_every_filter_type(engine, w, h, ch, waves):
         raw[m, 2] = raw[m, 0]
     # smooth stretches make Paeth / Average predictions that are not simply "left"
     raw[h // 3: h // 2] = (np.cumsum(rng.integers(-2, 3, (max(h // 2 - h // 3, 0), w, ch)), axis=1) + 128).astype(np.uint8)
+    engine.launch_counts(reset=True)
     for types in (rng.integers(0, 5, h), np.full(h, 4), np.full(h, 3), np.arange(h) % 5):
         rows = png_filter(raw, types)
         got = engine.stage_png_unfilter(rows, ch, w, h, waves)
         assert np.array_equal(got, gray15(raw)), "types %s..." % list(types[:6])
+    cnt = engine.launch_counts()
+    assert cnt["tw_png_unfilter"] == 4 and cnt.last_z["tw_png_unfilter"] == 1, cnt
 
 
 def test_bad_filter_type_is_refused(engine, twflow):

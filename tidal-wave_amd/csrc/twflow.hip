@@ -2304,19 +2304,35 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
 
 size_t staged_image_bytes(int w, int h) { return ((size_t)w * h + 255) / 256 * 256; }
 
-tw_status check_dims(tw_engine* e, int width, int height)
+// The one size predicate (check_dims: every submit; every tw_stage_* entry point; tw_debug_check_size).  The stencil
+// kernels reach the five planes of R0, R1 or M through ONE raw buffer resource (make_rsrc: num_records 0xFFFFFFFF) and
+// pick a plane by a 32-bit scalar byte offset c * ps * 4 next to a 32-bit row / column offset, ps = round_up(w, 32) * h.
+// Every byte of the five planes, 20 * ps bytes, must therefore stay inside that 32-bit range: with ps >= 2^28 plane 4's
+// offset wraps to 0, and above (2^32 - 1) / 20 the offsets leave the resource's range (whether the range check counts
+// the scalar offset was never measured on gfx950; the bound keeps both sides).  ld * h <= 214 748 364: 16384 x 13107
+// is admitted, 16384 x 13108 is not.
+const long long TW_MAX_PLANE_ELEMS = 0xFFFFFFFFll / 20;
+
+tw_status size_status(int width, int height, const char** why)
 {
     if (width < 1 || height < 1 || width > 32768 || height > 32768) {
-        e->err = "bad image size";
+        *why = "bad image size";
         return TW_E_BAD_PARAMETER;
     }
-    if ((long long)width * height > (1ll << 28)) {
-        // the stencil kernels address a plane with 32-bit byte offsets (raw buffer loads): planes stay below 4 GiB
-        // with room for the row pitch; 268 Mpixel (16384 x 16384) is far beyond any screenshot
-        e->err = "image larger than 2^28 pixels";
+    if ((long long)round_up(width, 32) * height > TW_MAX_PLANE_ELEMS) {
+        *why = "image too large: five float planes of round_up(width, 32) x height must fit 32-bit buffer offsets "
+               "(round_up(width, 32) * height <= 214748364)";
         return TW_E_UNSUPPORTED;
     }
     return TW_OK;
+}
+
+tw_status check_dims(tw_engine* e, int width, int height)
+{
+    const char* why = "";
+    const tw_status r = size_status(width, height, &why);
+    if (r) e->err = why;
+    return r;
 }
 
 // Page-locked host ranges this library handed out (tw_host_alloc) or was told about (tw_host_register): process-wide,
@@ -3514,6 +3530,12 @@ extern "C" int tw_debug_stamps_ex(tw_engine* e, unsigned long long* out, int n)
 // number of captured single-pair schedules this engine holds (tests: the graph path is really the one that ran)
 extern "C" int tw_debug_graphs(tw_engine* e) { return e ? (int)e->lat_graphs.size() : -1; }
 
+extern "C" tw_status tw_debug_check_size(int width, int height)
+{
+    const char* why = "";
+    return size_status(width, height, &why);
+}
+
 extern "C" int tw_debug_launch_counts(tw_engine* e, unsigned long long* counts, unsigned long long* last_z, int n, int reset)
 {
     if (!e) return -1;
@@ -3789,10 +3811,11 @@ extern "C" {
 tw_status tw_stage_pyr_level(tw_engine* e, const uint8_t* img, int w0, int h0, int level, float* I, int* w, int* h)
 {
     if (!e || !img || !I) return TW_E_BAD_PARAMETER;
+    tw_status r = check_dims(e, w0, h0);
+    if (r) return r;
     TW_HIP(e, hipSetDevice(e->device));
     Plan* pl = nullptr;
-    tw_status r = get_plan(e, w0, h0, &pl);
-    if (r) return r;
+    if ((r = get_plan(e, w0, h0, &pl))) return r;
     if (level < 0 || level > pl->levels) return TW_E_BAD_PARAMETER;
     const LevelPlan& L = pl->lv[level];
     Tmp t;
@@ -3817,10 +3840,11 @@ tw_status tw_stage_pyr_level(tw_engine* e, const uint8_t* img, int w0, int h0, i
 tw_status tw_stage_pyr_fused23(tw_engine* e, const uint8_t* img, int w0, int h0, float* I3, float* I2)
 {
     if (!e || !img || !I3 || !I2) return TW_E_BAD_PARAMETER;
+    tw_status r = check_dims(e, w0, h0);
+    if (r) return r;
     TW_HIP(e, hipSetDevice(e->device));
     Plan* pl = nullptr;
-    tw_status r = get_plan(e, w0, h0, &pl);
-    if (r) return r;
+    if ((r = get_plan(e, w0, h0, &pl))) return r;
     if (!pl->fused23) {
         e->err = "tw_stage_pyr_fused23: levels 2 and 3 of this size are not exact reductions by 4 and 8";
         return TW_E_UNSUPPORTED;
@@ -3848,10 +3872,11 @@ tw_status tw_stage_pyr_fused23(tw_engine* e, const uint8_t* img, int w0, int h0,
 tw_status tw_stage_pyr_fused01(tw_engine* e, const uint8_t* img, int w0, int h0, float* I0, float* I1)
 {
     if (!e || !img || !I0 || !I1) return TW_E_BAD_PARAMETER;
+    tw_status r = check_dims(e, w0, h0);
+    if (r) return r;
     TW_HIP(e, hipSetDevice(e->device));
     Plan* pl = nullptr;
-    tw_status r = get_plan(e, w0, h0, &pl);
-    if (r) return r;
+    if ((r = get_plan(e, w0, h0, &pl))) return r;
     if (!pyr01_fusable(pl)) {
         e->err = "tw_stage_pyr_fused01: level 1 of this size / these parameters is not an exact halving with 3-tap smoothing";
         return TW_E_UNSUPPORTED;
@@ -3919,7 +3944,9 @@ tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels,
 
 tw_status tw_stage_polyexp(tw_engine* e, const float* I, int w, int h, float* R5)
 {
-    if (!e || !I || !R5 || w < 1 || h < 1) return TW_E_BAD_PARAMETER;
+    if (!e || !I || !R5) return TW_E_BAD_PARAMETER;
+    tw_status r = check_dims(e, w, h);
+    if (r) return r;
     TW_HIP(e, hipSetDevice(e->device));
     const int ld = round_up(w, 32);
     const long long ps = (long long)ld * h;
@@ -3927,7 +3954,6 @@ tw_status tw_stage_polyexp(tw_engine* e, const float* I, int w, int h, float* R5
     float* d_I = t.alloc<float>((size_t)ps);
     float* d_R = t.alloc<float>((size_t)ps * 5);
     if (!d_I || !d_R) return TW_E_NOMEM;
-    tw_status r;
     if ((r = up_planes(e, d_I, ld, ps, I, w, h, 1))) return r;
     hipStream_t st = e->stream;
     if ((r = launch_polyexp(e, st, w, h, ld, ps, d_I, d_R, 1, -1))) return r;
@@ -3939,14 +3965,15 @@ tw_status tw_stage_polyexp(tw_engine* e, const float* I, int w, int h, float* R5
 tw_status tw_stage_update_matrices(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow2, int w,
                                    int h, float* M5)
 {
-    if (!e || !R0_5 || !R1_5 || !flow2 || !M5 || w < 1 || h < 1) return TW_E_BAD_PARAMETER;
+    if (!e || !R0_5 || !R1_5 || !flow2 || !M5) return TW_E_BAD_PARAMETER;
+    tw_status r = check_dims(e, w, h);
+    if (r) return r;
     TW_HIP(e, hipSetDevice(e->device));
     const int ld = round_up(w, 32);
     const long long ps = (long long)ld * h;
     Tmp t;
     float *d_R = t.alloc<float>(ps * 10), *d_M = t.alloc<float>(ps * 5), *d_f = t.alloc<float>(ps * 2);
     if (!d_R || !d_M || !d_f) return TW_E_NOMEM;
-    tw_status r;
     if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
         (r = up_planes(e, d_f, ld, ps, flow2, w, h, 2)))
         return r;
@@ -3970,8 +3997,9 @@ tw_status tw_stage_update_matrices(tw_engine* e, const float* R0_5, const float*
 tw_status tw_stage_flow_upsample_update(tw_engine* e, const float* R0_5, const float* R1_5, const float* prevflow2,
                                         int pw, int ph, int w, int h, float* flow2, float* M5)
 {
-    if (!e || !R0_5 || !R1_5 || !prevflow2 || !flow2 || !M5 || w < 1 || h < 1 || pw < 1 || ph < 1)
-        return TW_E_BAD_PARAMETER;
+    if (!e || !R0_5 || !R1_5 || !prevflow2 || !flow2 || !M5) return TW_E_BAD_PARAMETER;
+    tw_status r;
+    if ((r = check_dims(e, w, h)) || (r = check_dims(e, pw, ph))) return r;
     TW_HIP(e, hipSetDevice(e->device));
     const int ld = round_up(w, 32), pld = round_up(pw, 32);
     const long long ps = (long long)ld * h, pps = (long long)pld * ph;
@@ -3984,7 +4012,6 @@ tw_status tw_stage_flow_upsample_update(tw_engine* e, const float* R0_5, const f
     int *d_xo = t.alloc<int>(w), *d_yo = t.alloc<int>(h);
     float *d_al = t.alloc<float>(2 * (size_t)w), *d_be = t.alloc<float>(2 * (size_t)h);
     if (!d_R || !d_M || !d_f || !d_p || !d_xo || !d_yo || !d_al || !d_be) return TW_E_NOMEM;
-    tw_status r;
     if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
         (r = up_planes(e, d_p, pld, pps, prevflow2, pw, ph, 2)))
         return r;
@@ -4025,8 +4052,10 @@ tw_status tw_stage_flow_upsample_update(tw_engine* e, const float* R0_5, const f
 tw_status tw_stage_blur_solve(tw_engine* e, const float* R0_5, const float* R1_5, const float* M5, int w, int h,
                               int update_matrices, float* flow2, float* Mout5)
 {
-    if (!e || !R0_5 || !R1_5 || !M5 || !flow2 || w < 1 || h < 1) return TW_E_BAD_PARAMETER;
+    if (!e || !R0_5 || !R1_5 || !M5 || !flow2) return TW_E_BAD_PARAMETER;
     if (update_matrices && !Mout5) return TW_E_BAD_PARAMETER;
+    tw_status r = check_dims(e, w, h);
+    if (r) return r;
     TW_HIP(e, hipSetDevice(e->device));
     const int ld = round_up(w, 32);
     const long long ps = (long long)ld * h;
@@ -4034,7 +4063,6 @@ tw_status tw_stage_blur_solve(tw_engine* e, const float* R0_5, const float* R1_5
     float *d_R = t.alloc<float>(ps * 10), *d_M = t.alloc<float>(ps * 5), *d_Mo = t.alloc<float>(ps * 5),
           *d_f = t.alloc<float>(ps * 2);
     if (!d_R || !d_M || !d_Mo || !d_f) return TW_E_NOMEM;
-    tw_status r;
     if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
         (r = up_planes(e, d_M, ld, ps, M5, w, h, 5)))
         return r;
@@ -4050,7 +4078,9 @@ tw_status tw_stage_blur_solve(tw_engine* e, const float* R0_5, const float* R1_5
 tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow_in2, const float* prev2,
                              int pw, int ph, int w, int h, float* flow_out2)
 {
-    if (!e || !R0_5 || !R1_5 || !flow_out2 || w < 1 || h < 1 || (flow_in2 && prev2)) return TW_E_BAD_PARAMETER;
+    if (!e || !R0_5 || !R1_5 || !flow_out2 || (flow_in2 && prev2)) return TW_E_BAD_PARAMETER;
+    tw_status r;
+    if ((r = check_dims(e, w, h)) || (prev2 && (r = check_dims(e, pw, ph)))) return r;
     if (!flow_iter_eligible(e, w, h)) {
         e->err = "tw_stage_flow_iter: winSize 30/31 Gaussian window and a level of at least TW_MFREE_MIN_W (320) x 20 pixels";
         return TW_E_UNSUPPORTED;
@@ -4063,7 +4093,6 @@ tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5,
     Tmp t;
     float *d_R = t.alloc<float>(ps * 10), *d_fi = t.alloc<float>(ps * 2), *d_fo = t.alloc<float>(ps * 2);
     if (!d_R || !d_fi || !d_fo) return TW_E_NOMEM;
-    tw_status r;
     if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5))) return r;
     if (flow_in2 && (r = up_planes(e, d_fi, ld, ps, flow_in2, w, h, 2))) return r;
     FlowUps ups;

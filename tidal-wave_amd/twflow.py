@@ -70,7 +70,7 @@ SYMBOLS = [
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
-    "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory",
+    "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size",
 ]
 
 
@@ -193,6 +193,8 @@ def _bind(path):
     L.tw_debug_family_name.restype = C.c_char_p
     L.tw_debug_memory.argtypes = [vp, u64p, C.c_int]
     L.tw_debug_memory.restype = C.c_int
+    L.tw_debug_check_size.argtypes = [C.c_int, C.c_int]
+    L.tw_debug_check_size.restype = C.c_int
     return L
 
 
