@@ -566,6 +566,35 @@ namespace {
 
 size_t staged_image_bytes(int w, int h);
 
+// The one "grow this buffer" step (buffers grow, never shrink): when `new_cap` (in the buffer's own unit) exceeds `cap`,
+// wait for `sync` if one is given (the stream whose queued work may still touch the old buffer), free the buffer and
+// allocate `bytes` (the caller's size, slack included).  Pointer and capacity are cleared BEFORE the allocation, so that
+// a failed one leaves an empty buffer, not a dangling one, and the next call tries again.
+template <typename T>
+tw_status grow_device(tw_engine* e, T*& p, size_t& cap, size_t new_cap, size_t bytes, hipStream_t sync = nullptr)
+{
+    if (new_cap <= cap) return TW_OK;
+    if (sync) TW_HIP(e, hipStreamSynchronize(sync));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    TW_HIP(e, hipMalloc((void**)&p, bytes));
+    cap = new_cap;
+    return TW_OK;
+}
+// ... and the same for page-locked host memory
+template <typename T>
+tw_status grow_pinned(tw_engine* e, T*& p, size_t& cap, size_t bytes)
+{
+    if (bytes <= cap) return TW_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    TW_HIP(e, hipHostMalloc((void**)&p, bytes, hipHostMallocDefault));
+    cap = bytes;
+    return TW_OK;
+}
+
 // ---- the runtime is never handed a pageable host pointer ------------------------------------------------
 // Round 4 recorded a GPU memory-access fault on a malloc-heap address inside a synchronous copy, right after a
 // hipHostRegister / hipHostUnregister cycle on a neighbouring, non-page-aligned heap block: for a
@@ -577,13 +606,7 @@ bool host_range_is_page_locked(const void* p, size_t n);  // PinRegistry::covers
 constexpr size_t BOUNCE_CHUNK = 8u << 20;
 tw_status bounce_reserve(tw_engine* e, size_t bytes)
 {
-    if (bytes <= e->h_bounce_cap) return TW_OK;
-    if (e->h_bounce) (void)hipHostFree(e->h_bounce);
-    e->h_bounce = nullptr;
-    e->h_bounce_cap = 0;
-    TW_HIP(e, hipHostMalloc((void**)&e->h_bounce, bytes, hipHostMallocDefault));
-    e->h_bounce_cap = bytes;
-    return TW_OK;
+    return grow_pinned(e, e->h_bounce, e->h_bounce_cap, bytes);
 }
 // synchronous host -> device / device -> host copies of any host pointer (null stream, like the hipMemcpy they replace)
 tw_status h2d_sync(tw_engine* e, void* d, const void* h, size_t n)
@@ -890,7 +913,7 @@ tw_status get_plan(tw_engine* e, int w0, int h0, Plan** out)
 }
 
 // Device workspace for a plan (grown, never shrunk).  Safe to reallocate only when nothing is queued.
-tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span, bool need_img)
+tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span)
 {
     size_t need = 0;
     for (const LevelPlan& L : pl->lv) need = std::max(need, (size_t)L.ps * 2 * L.chunk);
@@ -901,7 +924,6 @@ tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span, bool need_im
             const size_t fc = (size_t)pl->lv[k].ps * 2 * (k == 0 ? pl->lv[0].chunk * e->lanes : e->cap);
             if (fc > e->flow_cap[k]) grow = true;
         }
-    (void)need_img;  // image regions belong to the batch contexts (submit_common)
     const size_t G = span > 0 ? (size_t)tw_grid_capacity(pl->w0, pl->h0, span) : 0;
     if (G * e->cap > e->d_grid_cap) grow = true;
     size_t need_lat = 0;
@@ -938,35 +960,16 @@ tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span, bool need_im
         TW_HIP(e, hipEventCreateWithFlags(&ev, getenv("TW_LAT_EVTIMING") ? hipEventDefault : hipEventDisableTiming));
         e->lat_ev.push_back(ev);
     }
-    if (e->box && need / 2 * 5 > e->Vd_cap) {
-        if (e->Vd) (void)hipFree(e->Vd);
-        e->Vd = nullptr;
-        e->Vd_cap = 0;
-        TW_HIP(e, hipMalloc((void**)&e->Vd, need / 2 * 5 * sizeof(double) + 256));
-        e->Vd_cap = need / 2 * 5;
-    }
+    if (e->box) TW_TRY(grow_device(e, e->Vd, e->Vd_cap, need / 2 * 5, need / 2 * 5 * sizeof(double) + 256));
     if (e->flow.size() < pl->lv.size()) {
         e->flow.resize(pl->lv.size(), nullptr);
         e->flow_cap.resize(pl->lv.size(), 0);
     }
     for (size_t k = 0; k < pl->lv.size(); k++) {
         const size_t fc = (size_t)pl->lv[k].ps * 2 * (k == 0 ? pl->lv[0].chunk * e->lanes : e->cap);
-        if (fc > e->flow_cap[k]) {
-            if (e->flow[k]) (void)hipFree(e->flow[k]);
-            e->flow[k] = nullptr;
-            e->flow_cap[k] = 0;
-            TW_HIP(e, hipMalloc((void**)&e->flow[k], fc * 4 + 256));
-            e->flow_cap[k] = fc;
-        }
+        TW_TRY(grow_device(e, e->flow[k], e->flow_cap[k], fc, fc * 4 + 256));
     }
-    if (G * e->cap > e->d_grid_cap) {
-        if (e->d_grid) (void)hipFree(e->d_grid);
-        e->d_grid = nullptr;
-        e->d_grid_cap = 0;
-        TW_HIP(e, hipMalloc((void**)&e->d_grid, G * e->cap * sizeof(float2) + 256));
-        e->d_grid_cap = G * e->cap;
-    }
-    return TW_OK;
+    return grow_device(e, e->d_grid, e->d_grid_cap, G * e->cap, G * e->cap * sizeof(float2) + 256);
 }
 
 // ---- profiling hooks -------------------------------------------------------------------------------
@@ -1030,7 +1033,6 @@ TwinGrid make_twin(const dim3& ga, const SideJob& s)
 }
 void launch_side_alone(tw_engine* e, hipStream_t st, const SideJob& s)
 {
-    (void)e;
     if (s.kind == 1) TW_LAUNCH(e, TW_DF_POLYEXP, tw_polyexp_band, dim3(s.n()), dim3(256), 0, st, s.pa, s.g);
     else if (s.kind == 2) TW_LAUNCH(e, TW_DF_PYR_K3F, tw_pyr_k3f, dim3(s.g.gx, s.g.gy, s.g.gz), dim3(256), 0, st, s.ka);
 }
@@ -1724,44 +1726,123 @@ tw_status export_chunk(tw_engine* e, Ctx& c, hipStream_t st, const LevelPlan& L,
     return TW_OK;
 }
 
-// Enqueue a whole batch, level-major: every level is processed for all pairs (in chunks sized to fill the
-// chip) before the next finer level starts; level 0 chunks are scanned as soon as their flow exists.
-tw_status flush_ctx(tw_engine* e, Ctx& c)
+// ---- environment switches of the enqueue path ---------------------------------------------------------
+// Three classes, by WHEN a variable is read: (1) engine fields, read once in tw_engine_create (TW_LANES, TW_MFREE,
+// TW_RAMP, TW_LAT_FUSED, TW_LAT_GRAPH, ...); (2) per batch, below: read at the start of every flush_ctx call, because the
+// tests switch them between two batches of one engine; (3) per process, further below: measurement and diagnostic
+// switches read once, when the process enqueues its first batch.
+struct BatchSwitches {
+    bool lat_quads;  // TW_LAT_QUADS=0: a single pair's 224 x 8-tile window launches take tw_blur_solve4 as in a batch
+    int lat_plan;    // TW_LAT_PLAN: which launches carry the twin schedule's side jobs (plan_twin_side_jobs)
+    bool scan_seg;   // TW_SCAN_SEG=0: a single pair's ordered scan as one workgroup (tw_span_scan) — a test compares the two
+    BatchSwitches()
+        : lat_quads(!getenv("TW_LAT_QUADS") || atoi(getenv("TW_LAT_QUADS")) != 0),
+          lat_plan(getenv("TW_LAT_PLAN") ? atoi(getenv("TW_LAT_PLAN")) : 1),
+          scan_seg(!getenv("TW_SCAN_SEG") || atoi(getenv("TW_SCAN_SEG")) != 0)
+    {
+    }
+};
+struct ProcessSwitches {
+    int side_alone;    // TW_LAT_ALONE — measurement: 1 every side job as its own launch; 2 also the chain kernels through
+                       // their twins (empty side)
+    int bands;         // TW_LAT_BANDS=n: n bands per level-0 image and level 1 per image (plan_twin_side_jobs)
+    bool host_time;    // TW_DEBUG_HOSTTIME — diagnostic: print the host cost of every direct enqueue
+    bool scan_direct;  // TW_SCAN_DIRECT (variants library): tw_span_scan<true> samples the flow planes itself
+};
+const ProcessSwitches& process_switches()
 {
-    if (c.launched || c.jobs.empty()) return TW_OK;
-    hipStream_t st = e->stream;
+    static const ProcessSwitches s = {getenv("TW_LAT_ALONE") ? atoi(getenv("TW_LAT_ALONE")) : 0,
+                                      getenv("TW_LAT_BANDS") ? atoi(getenv("TW_LAT_BANDS")) : 0,
+                                      getenv("TW_DEBUG_HOSTTIME") != nullptr, getenv("TW_SCAN_DIRECT") != nullptr};
+    return s;
+}
+
+// One row of tw_flow_export's destination table / tw_flow_area_init's source table: the caller's device memory in place,
+// or (staged != null) this context's staging slot — dense rows in the field's own layout; null for a pair without a field
+FlowDst flow_table_row(const void* data, ptrdiff_t pitch, int layout, char* staged, int w)
+{
+    FlowDst d;
+    d.p = !data ? nullptr : staged ? staged : (char*)data;
+    d.pitch = staged ? (long long)w * (layout ? 8 : 4) : (long long)pitch;
+    d.layout = layout;
+    d.pad = 0;
+    return d;
+}
+
+// One launch group of the level loop: pairs [j0, j0 + nc) of the batch at level k, on stream ls with lane's workspace
+struct LevelChunk {
+    int k, lane, j0, nc;
+    hipStream_t ls;
+    float* I;          // the lane's image workspace (batch schedule)
+    float* R;          // polynomial expansions of the chunk's images
+    float *M0, *M1;
+    double* Vbox;      // running column sums of the box window (null: Gaussian window)
+    float* flow_cur;   // levels >= 1 keep every pair of the batch, level 0 only the lane's current chunk
+    const float* flow_prev;  // the coarser level's flow of the same pairs (null at the coarsest level)
+    // scan-fused final iteration (option TW_OPT_SCAN_FUSED_FINAL): nothing but the span grid of the last level-0 flow is
+    // read afterwards, so the last window average + solve runs at the grid points only
+    bool grid_only;
+    // a batch with initial flow fields: every chunk of the coarsest level starts from tw_flow_area_init's output (zeros
+    // for its pairs without a field) through the non-zero-flow kernels
+    bool init_lv;
+};
+
+// Everything flush_ctx enqueues for one batch: the steps in the order flush_ctx calls them, then the three schedules
+// of the level loop (enqueue_levels) and the launches they share.  Every step returns on the first error status; the
+// batch's context then stays un-launched and submit_common / tw_wait drop it.
+struct BatchEnqueue {
+    tw_engine* const e;
+    Ctx& c;
+    const BatchSwitches sw;  // (read here: once per flush_ctx call)
+    const hipStream_t st;
+    const int n, it;
+    const size_t npx;    // staged images are 256-byte aligned
+    const size_t fslot;  // bytes of a pair's slot in the flow staging regions
     Plan* pl = nullptr;
-    tw_status r = get_plan(e, c.w, c.h, &pl);
-    if (r) return r;
-    if ((r = reserve_workspace(e, pl, c.span, c.any_host))) return r;
-    if (c.span > 0) {
-        const size_t need_rec = (size_t)tw_grid_capacity(c.w, c.h, c.span) * e->cap;
-        if (need_rec > c.d_rec_cap) {
-            // this context has no results outstanding (it is being launched), nothing on the stream uses its records
-            if (c.d_rec) (void)hipFree(c.d_rec);
-            c.d_rec = nullptr;
-            c.d_rec_cap = 0;
-            TW_HIP(e, hipMalloc((void**)&c.d_rec, need_rec * sizeof(ScanRec) + 256));
-            c.d_rec_cap = need_rec;
-        }
-    }
-    const size_t fslot = flow_stage_slot(c.w, c.h);
-    if (c.any_fout_host && fslot * e->cap > c.d_fstage_cap) {
-        // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
-        if (c.d_fstage) (void)hipFree(c.d_fstage);
-        c.d_fstage = nullptr;
-        c.d_fstage_cap = 0;
-        TW_HIP(e, hipMalloc((void**)&c.d_fstage, fslot * e->cap + 256));
-        c.d_fstage_cap = fslot * e->cap;
-    }
-    const int n = (int)c.jobs.size();
+    long long stride;
+    int gw = 0, gh = 0;  // the span grid of level 0 (span > 0)
     int ramp_b[4] = {0, 0, 0, 0}, ramp_n = 1;  // cold-start ramp: piece i = pairs [ramp_b[i], ramp_b[i + 1]); ramp_n - 1 pieces
-    RoctxRange batch_range("tw_batch %dx%d pairs=%d", c.w, c.h, n);
-    const size_t npx = staged_image_bytes(c.w, c.h);  // staged images are 256-byte aligned
-    long long stride = c.jobs[0].stride;
-    if (c.any_png) {
-        // tw_submit_png8: reconstruct the filtered rows into the gray image slots, on the copy stream behind the
-        // uploads — it runs beside the previous batch's kernels like the uploads themselves
+    // the schedule (choose_schedule)
+    int nlanes = 1;
+    size_t ws_lane = 0;
+    bool prof_on = false, lat = false, lat2 = false, lat_quads = false, fused_final = false;
+    std::vector<size_t> lat_off;  // a level's offset in lat_I (x 5 in lat_R)
+    // the side jobs of the twin schedule, in the order the chain needs their results (empty in every other schedule)
+    std::vector<SideJob> sideq;
+    size_t side_next = 0;
+    SideJob empty_side;  // (a member: engines of several host threads enqueue at once)
+
+    BatchEnqueue(tw_engine* e_, Ctx& c_)
+        : e(e_), c(c_), st(e_->stream), n((int)c_.jobs.size()), it(e_->p.pyrIterations), npx(staged_image_bytes(c_.w, c_.h)),
+          fslot(flow_stage_slot(c_.w, c_.h)), stride(c_.jobs[0].stride)
+    {
+        empty_side.kind = 1;
+        empty_side.g = VGrid{0u, 0u, 0u, 0u, 0u};
+    }
+
+    // ---- the steps of a batch, in order ------------------------------------------------------------------
+
+    tw_status reserve_batch_buffers()
+    {
+        TW_TRY(get_plan(e, c.w, c.h, &pl));
+        TW_TRY(reserve_workspace(e, pl, c.span));
+        if (c.span > 0) {
+            gw = (pl->lv[0].w + c.span - 1) / c.span;
+            gh = (pl->lv[0].h + c.span - 1) / c.span;
+            // this context has no results outstanding (it is being launched), nothing on the stream uses its records
+            const size_t need_rec = (size_t)tw_grid_capacity(c.w, c.h, c.span) * e->cap;
+            TW_TRY(grow_device(e, c.d_rec, c.d_rec_cap, need_rec, need_rec * sizeof(ScanRec) + 256));
+        }
+        // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
+        if (c.any_fout_host) TW_TRY(grow_device(e, c.d_fstage, c.d_fstage_cap, fslot * e->cap, fslot * e->cap + 256));
+        return TW_OK;
+    }
+
+    // tw_submit_png8: reconstruct the filtered rows into the gray image slots, on the copy stream behind the
+    // uploads — it runs beside the previous batch's kernels like the uploads themselves
+    tw_status enqueue_png_unfilter()
+    {
+        if (!c.any_png) return TW_OK;
         for (int j = 0; j < n; j++)
             for (int q = 0; q < 2; q++) {
                 PngJob& pj = c.h_png[2 * j + q];
@@ -1779,9 +1860,13 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
         if (c.w <= PNG_LDS_PIXELS / 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, dim3(2 * n), dim3(1024), 0, e->copy_stream, pa);
         else if (c.w <= PNG_LDS_PIXELS / 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, dim3(2 * n), dim3(256), 0, e->copy_stream, pa);
         else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(2 * n), dim3(64), 0, e->copy_stream, pa);
+        return TW_OK;
     }
-    c.copy_ops_at_flush = e->copy_ops;
-    if (c.any_host || c.any_init_host) {
+
+    tw_status mark_uploads_and_plan_ramp()
+    {
+        c.copy_ops_at_flush = e->copy_ops;
+        if (!c.any_host && !c.any_init_host) return TW_OK;
         // the uploads (images, and host initial flow fields) were queued on the copy stream as the jobs came in (submit_common)
         TW_HIP(e, hipEventRecord(c.ev_h2d, e->copy_stream));
         // cold-start ramp: nothing of an earlier batch is still running on the compute stream (the first batch after a
@@ -1801,109 +1886,413 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
         ramp_b[ramp_n++] = n;
         if (ramp_n == 2) TW_HIP(e, hipStreamWaitEvent(st, c.ev_h2d, 0));  // (no ramp: the whole batch behind its last upload)
         if (c.any_host) stride = c.w;
+        return TW_OK;
     }
-    bool al4 = (stride % 4) == 0;
-    for (int j = 0; j < n; j++) {
-        const Job& jb = c.jobs[j];
-        if (jb.h_a) {
-            c.h_ptrs[2 * j] = c.d_img + npx * (2 * j);
-            c.h_ptrs[2 * j + 1] = c.d_img + npx * (2 * j + 1);
-        } else {
-            c.h_ptrs[2 * j] = jb.d_a;
-            c.h_ptrs[2 * j + 1] = jb.d_b;
-        }
-        al4 = al4 && ((uintptr_t)c.h_ptrs[2 * j] % 4 == 0) && ((uintptr_t)c.h_ptrs[2 * j + 1] % 4 == 0);
-    }
-    e->img_aligned4 = al4 ? 1 : 0;
-    TW_HIP(e, hipMemcpyAsync((void*)e->d_ptrs, c.h_ptrs, sizeof(void*) * 2 * n, hipMemcpyHostToDevice, st));
-    if (c.any_fout) {
-        // tw_flow_export's destination table: the caller's device memory, or this context's staging slot (dense rows in
-        // the destination's layout) for a host destination
+
+    // the batch's tables on the main stream: image pointers, flow destinations, initial-field sources
+    tw_status upload_tables()
+    {
+        bool al4 = (stride % 4) == 0;
         for (int j = 0; j < n; j++) {
             const Job& jb = c.jobs[j];
-            FlowDst& d = c.h_fdst[j];
-            d.p = jb.fout_host ? c.d_fstage + fslot * j : (char*)jb.fout.data;
-            d.pitch = jb.fout_host ? (long long)c.w * (jb.fout.layout ? 8 : 4) : (long long)jb.fout.pitch;
-            d.layout = jb.fout.layout;
-            d.pad = 0;
+            if (jb.h_a) {
+                c.h_ptrs[2 * j] = c.d_img + npx * (2 * j);
+                c.h_ptrs[2 * j + 1] = c.d_img + npx * (2 * j + 1);
+            } else {
+                c.h_ptrs[2 * j] = jb.d_a;
+                c.h_ptrs[2 * j + 1] = jb.d_b;
+            }
+            al4 = al4 && ((uintptr_t)c.h_ptrs[2 * j] % 4 == 0) && ((uintptr_t)c.h_ptrs[2 * j + 1] % 4 == 0);
         }
-        TW_HIP(e, hipMemcpyAsync((void*)e->d_fdst, c.h_fdst, sizeof(FlowDst) * n, hipMemcpyHostToDevice, st));
-    }
-    if (c.any_init) {
-        // tw_flow_area_init's source table: the caller's device memory in place, this context's staging slot (dense rows
-        // in the field's layout) for a host field, null (zeros) for a pair without one
-        for (int j = 0; j < n; j++) {
-            const Job& jb = c.jobs[j];
-            FlowDst& d = c.h_fsrc[j];
-            d.p = !jb.fin.data ? nullptr : jb.fin_staged ? c.d_istage + fslot * j : (char*)jb.fin.data;
-            d.pitch = jb.fin_staged ? (long long)c.w * (jb.fin.layout ? 8 : 4) : (long long)jb.fin.pitch;
-            d.layout = jb.fin.layout;
-            d.pad = 0;
+        e->img_aligned4 = al4 ? 1 : 0;
+        TW_HIP(e, hipMemcpyAsync((void*)e->d_ptrs, c.h_ptrs, sizeof(void*) * 2 * n, hipMemcpyHostToDevice, st));
+        if (c.any_fout) {
+            for (int j = 0; j < n; j++) {
+                const Job& jb = c.jobs[j];
+                c.h_fdst[j] = flow_table_row(jb.fout.data, jb.fout.pitch, jb.fout.layout,
+                                             jb.fout_host ? c.d_fstage + fslot * j : nullptr, c.w);
+            }
+            TW_HIP(e, hipMemcpyAsync((void*)e->d_fdst, c.h_fdst, sizeof(FlowDst) * n, hipMemcpyHostToDevice, st));
         }
-        TW_HIP(e, hipMemcpyAsync((void*)e->d_fsrc, c.h_fsrc, sizeof(FlowDst) * n, hipMemcpyHostToDevice, st));
-    }
-    TW_HIP(e, hipEventRecord(c.ev_start, st));
-    const int it = e->p.pyrIterations;
-    const int nlanes = (e->lanes > 1 && n >= 2) ? e->lanes : 1;
-    if (nlanes > 1) {
-        TW_HIP(e, hipEventRecord(e->ev_fork, st));  // uploads + whatever ran before on the main stream
-        TW_HIP(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
-    }
-    size_t ws_lane = 0;
-    for (const LevelPlan& L : pl->lv) ws_lane = std::max(ws_lane, (size_t)L.ps * 2 * L.chunk);
-    // one pair: image-only work (pyramid, polynomial expansion) of all levels on the second stream
-    // (only worth its cross-stream hand-offs when the image-only work is tens of microseconds: >= 0.1 Mpixel)
-    const bool lat = nlanes == 1 && e->lat_I && single_pair_schedule(e, n, c.w, c.h, pl->levels);
-    bool prof_on = false;
-    for (int i = 0; i < TW_K_COUNT; i++) prof_on = prof_on || e->prof_level[i] != -2;
-    // ... or, for the default parameters at sizes whose pyramid halves exactly (1080p: BASELINE config 2), ONE stream of twin
-    // launches: every coarse-level chain kernel carries a piece of the finer levels' image-only work in its own launch
-    // (twflow_kernels.hip.h: tw_twin_*) — no cross-queue hand-off anywhere in the pair
-    const bool lat2 = lat && e->lat_fused && !e->lat_graph && !prof_on && pl->levels == 3 && pl->fused23 && e->pyr_fused &&
-                      pyr01_fusable(pl) && !e->pyr_generic && e->p.polyN == 7 && !e->poly_f32 && e->poly_variant == 1 &&
-                      e->upd_ny == 2 && e->win_m == 15 && !e->box && it >= 1;
-    // a single pair's 224 x 8-tile window launches take tw_blur_solve4q (launch_blur; TW_LAT_QUADS=0: tw_blur_solve4 as in a batch)
-    const bool lat_quads = lat && (!getenv("TW_LAT_QUADS") || atoi(getenv("TW_LAT_QUADS")) != 0);
-    std::vector<SideJob> sideq;
-    size_t side_next = 0;
-    std::vector<size_t> lat_off(pl->lv.size(), 0);
-    if (lat) {
-        size_t off = 0;
-        for (size_t k = 0; k < pl->lv.size(); k++) {
-            lat_off[k] = off;
-            off += (size_t)pl->lv[k].ps * 2;
+        if (c.any_init) {
+            for (int j = 0; j < n; j++) {
+                const Job& jb = c.jobs[j];
+                c.h_fsrc[j] = flow_table_row(jb.fin.data, jb.fin.pitch, jb.fin.layout,
+                                             jb.fin_staged ? c.d_istage + fslot * j : nullptr, c.w);
+            }
+            TW_HIP(e, hipMemcpyAsync((void*)e->d_fsrc, c.h_fsrc, sizeof(FlowDst) * n, hipMemcpyHostToDevice, st));
         }
+        return TW_OK;
     }
-    // Everything between the batch's start event and the ordered scan, as one function: the single-pair schedule
-    // replays it from a captured hipGraph (below), every other batch enqueues it directly.
+
+    // which of the three schedules the level loop takes: the batch schedule (on one or two lanes), or for one pair
+    // the two-stream schedule (lat) or the twin launches (lat2)
+    tw_status choose_schedule()
+    {
+        nlanes = (e->lanes > 1 && n >= 2) ? e->lanes : 1;
+        if (nlanes > 1) {
+            TW_HIP(e, hipEventRecord(e->ev_fork, st));  // uploads + whatever ran before on the main stream
+            TW_HIP(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
+        }
+        for (const LevelPlan& L : pl->lv) ws_lane = std::max(ws_lane, (size_t)L.ps * 2 * L.chunk);
+        // one pair: image-only work (pyramid, polynomial expansion) of all levels on the second stream
+        // (only worth its cross-stream hand-offs when the image-only work is tens of microseconds: >= 0.1 Mpixel)
+        lat = nlanes == 1 && e->lat_I && single_pair_schedule(e, n, c.w, c.h, pl->levels);
+        for (int i = 0; i < TW_K_COUNT; i++) prof_on = prof_on || e->prof_level[i] != -2;
+        // ... or, for the default parameters at sizes whose pyramid halves exactly (1080p: BASELINE config 2), ONE stream of twin
+        // launches: every coarse-level chain kernel carries a piece of the finer levels' image-only work in its own launch
+        // (twflow_kernels.hip.h: tw_twin_*) — no cross-queue hand-off anywhere in the pair
+        lat2 = lat && e->lat_fused && !e->lat_graph && !prof_on && pl->levels == 3 && pl->fused23 && e->pyr_fused &&
+               pyr01_fusable(pl) && !e->pyr_generic && e->p.polyN == 7 && !e->poly_f32 && e->poly_variant == 1 &&
+               e->upd_ny == 2 && e->win_m == 15 && !e->box && it >= 1;
+        // a single pair's 224 x 8-tile window launches take tw_blur_solve4q (launch_blur; TW_LAT_QUADS=0: tw_blur_solve4 as in a batch)
+        lat_quads = lat && sw.lat_quads;
+        lat_off.assign(pl->lv.size(), 0);
+        if (lat) {
+            size_t off = 0;
+            for (size_t k = 0; k < pl->lv.size(); k++) {
+                lat_off[k] = off;
+                off += (size_t)pl->lv[k].ps * 2;
+            }
+        }
+        // (a batch with a flow destination needs the last level-0 field itself: never the scan-fused final iteration)
+        fused_final = scan_fused_level0(e, c.span) && !c.any_fout;
+        return TW_OK;
+    }
+
+    // Single pair (BASELINE config 2): ~26 launches and ~10 event operations, half of them kernels of 5-10 us.  With
+    // TW_LAT_GRAPH=1 the whole DAG — both streams, their hand-offs — is captured once per (size, span, stride,
+    // alignment, options) and replayed with one hipGraphLaunch; the ordered scan and the result copies stay outside
+    // (their targets belong to the batch context).  Round 3 measured it: the host is NOT what holds the schedule back
+    // (the direct enqueue takes 110 us of host time for 375 us of GPU time, TW_DEBUG_HOSTTIME), and the replayed graph
+    // is slower (0.55 ms: kernels of the forked branch stretch to ~40 us quanta behind cross-queue signals), so the
+    // direct path is the default and the graph an opt-in A/B switch (profiles/r03_latency.md).
+    tw_status enqueue_or_replay_graph()
+    {
+        if (lat && e->lat_graph && !prof_on && !c.any_fout && !c.any_init) {  // (destinations / fields would be baked into the graph)
+            const GraphKey key{c.w, c.h, c.span, stride, e->img_aligned4, e->scan_fused, e->poly_f32};
+            auto git = e->lat_graphs.find(key);
+            if (git == e->lat_graphs.end()) {
+                hipGraph_t graph = nullptr;
+                hipGraphExec_t exec = nullptr;
+                bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) == hipSuccess;
+                tw_status br = TW_OK;
+                if (ok) {
+                    br = enqueue_levels();
+                    ok = hipStreamEndCapture(st, &graph) == hipSuccess && graph != nullptr && br == TW_OK;
+                }
+                if (br != TW_OK) {
+                    if (graph) (void)hipGraphDestroy(graph);
+                    (void)hipGetLastError();
+                    return br;
+                }
+                ok = ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+                if (graph) (void)hipGraphDestroy(graph);
+                if (ok) {
+                    git = e->lat_graphs.emplace(key, exec).first;
+                } else {
+                    (void)hipGetLastError();
+                    e->lat_graph = 0;  // this runtime cannot capture the schedule: direct launches from now on
+                }
+            }
+            if (git != e->lat_graphs.end()) {
+                TW_HIP(e, hipGraphLaunch(git->second, st));
+                return TW_OK;
+            }
+        }
+        const auto t_h0 = std::chrono::steady_clock::now();
+        TW_TRY(enqueue_levels());
+        if (process_switches().host_time)
+            fprintf(stderr, "twflow: enqueue of %d pair(s) %dx%d took %.1f us on the host\n", n, c.w, c.h,
+                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_h0).count());
+        return TW_OK;
+    }
+
+    // the ordered scan of the whole batch's span grids, and the stop event
+    tw_status enqueue_scan()
+    {
+        if (c.span > 0) {
+            const LevelPlan& L = pl->lv[0];
+            ScanArgs a;
+            a.g = e->d_grid;
+            a.span = c.span;
+            a.gw = gw;
+            a.gh = gh;
+            a.thr2 = c.threshold * c.threshold;
+            a.count = e->d_count;
+            a.rec_zs = (long long)a.gw * a.gh;
+            a.rec = c.d_rec;
+            a.flow = e->flow[0];
+            a.fps = L.ps;
+            a.ld = L.ld;
+            ProfScope pscope(e, st, TW_K_SCAN, 0);
+#ifdef TW_VARIANTS
+            // (scan_fused_level0, not fused_final: a batch with a flow destination keeps its gathered grid either way)
+            if (lat && !scan_fused_level0(e, c.span) && process_switches().scan_direct) {
+                TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<true>, dim3(n), dim3(1024), 0, st, a);
+            } else
+#endif
+            {
+                // a single pair: 16 segments, each workgroup counting the hits before its own (tw_span_scan_seg: -5 us of one CU's VALU time)
+                const long long G = (long long)a.gw * a.gh;
+                const int S = (int)(((G + 15) / 16 + 1023) / 1024 * 1024);
+                if (n == 1 && lat && sw.scan_seg && G > 2048 && S <= SCAN_IT * 1024)
+                    TW_LAUNCH(e, TW_DF_SPAN_SCAN_SEG, tw_span_scan_seg, dim3((unsigned)((G + S - 1) / S)), dim3(1024), 0, st, a, S);
+                else
+                    TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<false>, dim3(n), dim3(1024), 0, st, a);
+            }
+        }
+        TW_HIP(e, hipEventRecord(c.ev_stop, st));
+        return TW_OK;
+    }
+
+    tw_status enqueue_result_copies()
+    {
+        if (c.span > 0) {
+            const size_t G = (size_t)tw_grid_capacity(c.w, c.h, c.span);
+            const size_t nrec = std::min((size_t)HOST_RECS, G);
+            TW_HIP(e, hipMemcpyAsync(c.h_count, e->d_count, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+            TW_HIP(e, hipMemcpy2DAsync(c.h_rec, HOST_RECS * sizeof(ScanRec), c.d_rec, G * sizeof(ScanRec),
+                                       nrec * sizeof(ScanRec), n, hipMemcpyDeviceToHost, st));
+        }
+        if (c.any_fout_host) {
+            TW_HIP(e, hipEventRecord(c.ev_d2h, e->d2h_stream));
+            c.d2h_ops_at_flush = e->d2h_ops;
+        }
+        TW_HIP(e, hipGetLastError());
+        TW_HIP(e, hipEventRecord(c.ev_done, st));
+        return TW_OK;
+    }
+
+    // ---- the level loop -----------------------------------------------------------------------------------
+    // Everything between the batch's start event and the ordered scan: the single-pair schedule may replay it from a
+    // captured hipGraph (enqueue_or_replay_graph), every other batch enqueues it directly.
+    tw_status enqueue_levels()
+    {
+        if (lat2) return enqueue_twin_pair();
+        if (lat) return enqueue_two_stream_pair();
+        return enqueue_batch_levels();
+    }
+
+    LevelChunk make_chunk(int k, int lane, int j0, int nc) const
+    {
+        const LevelPlan& L = pl->lv[k];
+        LevelChunk ch;
+        ch.k = k;
+        ch.lane = lane;
+        ch.j0 = j0;
+        ch.nc = nc;
+        ch.ls = lane == 0 ? st : e->stream2;
+        ch.I = e->I + ws_lane * lane;
+        ch.R = e->R + ws_lane * 5 * lane;
+        ch.M0 = e->M[0] + ws_lane / 2 * 5 * lane;
+        ch.M1 = e->M[1] + ws_lane / 2 * 5 * lane;
+        ch.Vbox = e->Vd ? e->Vd + ws_lane / 2 * 5 * lane : nullptr;
+        ch.flow_cur = e->flow[k] + (k == 0 ? (size_t)lane * L.chunk * 2 * L.ps : (size_t)j0 * 2 * L.ps);
+        ch.flow_prev = k < pl->levels ? e->flow[k + 1] + (size_t)j0 * 2 * pl->lv[k + 1].ps : nullptr;
+        ch.grid_only = k == 0 && fused_final;
+        ch.init_lv = c.any_init && k == pl->levels;
+        return ch;
+    }
+    // a single pair's only chunk of level k: every level's R stays in lat_R until the pair is done
+    LevelChunk pair_chunk(int k) const
+    {
+        LevelChunk ch = make_chunk(k, 0, 0, 1);
+        ch.R = e->lat_R + 5 * lat_off[k];
+        return ch;
+    }
     // does level k of a launch of nc pairs run tw_flow_iter?  (level_runs_flow_iter: the predicate the byte model shares)
-    // (a batch with a flow destination needs the last level-0 field itself: never the scan-fused final iteration)
-    const bool fused_final = scan_fused_level0(e, c.span) && !c.any_fout;
-    auto level_mfree = [&](int k, int nc) -> bool {
+    bool level_mfree(int k, int nc) const
+    {
         const LevelPlan& L = pl->lv[k];
         return level_runs_flow_iter(e, L.w, L.h, nc, lat, k == 0 && fused_final);
-    };
-    auto enqueue_levels = [&]() -> tw_status {
-    if (lat && !lat2) {
+    }
+    float2* grid_of(int j0) const { return e->d_grid + (size_t)j0 * gw * gh; }
+
+    // -- the batch schedule: level-major, every level for all pairs of a part before the next finer level starts.  A part
+    // is a lane's half of the batch (TW_LANES=2), or a piece of the cold-start ramp (only with nlanes == 1 and never for a
+    // single pair: see where ramp_b is filled)
+    tw_status enqueue_batch_levels()
+    {
+        const bool ramp = ramp_n > 2;
+        const int nparts = ramp ? ramp_n - 1 : nlanes;
+        for (int part = 0; part < nparts; part++) {
+            const int lane = ramp ? 0 : part;
+            const int lo = ramp ? ramp_b[part] : (int)((long long)n * lane / nlanes);
+            const int hi = ramp ? ramp_b[part + 1] : (int)((long long)n * (lane + 1) / nlanes);
+            if (ramp) TW_HIP(e, hipStreamWaitEvent(st, part + 1 < nparts ? c.ev_seg[part] : c.ev_h2d, 0));
+            for (int k = pl->levels; k >= 0; k--) {
+                const LevelPlan& L = pl->lv[k];
+                RoctxRange level_range("tw_level %d (%dx%d)", k, L.w, L.h);
+                // balanced launches: 64 pairs with a 63-pair chunk are 32 + 32, not 63 + 1
+                const int per = balanced_launch_pairs(hi - lo, L.chunk);
+                for (int j0 = lo; j0 < hi; j0 += per) {
+                    const LevelChunk ch = make_chunk(k, lane, j0, std::min(per, hi - j0));
+                    TW_TRY(enqueue_level_images(ch, hi - lo));
+                    bool grid_stored = false;
+                    if (level_mfree(k, ch.nc)) enqueue_flow_iter_chain(ch);
+                    else enqueue_update_blur_chain(ch, &grid_stored);
+                    TW_TRY(enqueue_level0_outputs(ch, grid_stored));
+                }
+            }
+        }
+        if (nlanes > 1) {
+            TW_HIP(e, hipEventRecord(e->ev_join, e->stream2));
+            TW_HIP(e, hipStreamWaitEvent(st, e->ev_join, 0));
+        }
+        return TW_OK;
+    }
+
+    // pyramid + polynomial expansion of a chunk's images (batch schedule); npart: the pairs of the chunk's part
+    tw_status enqueue_level_images(const LevelChunk& ch, int npart)
+    {
+        const int k = ch.k, nc = ch.nc;
+        const LevelPlan& L = pl->lv[k];
+        // levels 3 and 2 from one read of the images (tw_pyr_23): level 3's launch also writes level 2's
+        // images, behind its own in the workspace (sized for level 0: there is room), and level 2 skips its
+        // pyramid launch.  Only when both levels cover the same pairs per launch.
+        // (one launch per level for this lane: the loop is level-major, a second chunk of level 3 would
+        // overwrite the first chunk's level-2 images before level 2 reads them)
+        const bool f23 = pl->fused23 && e->pyr_fused && pl->lv[3].chunk >= npart && pl->lv[2].chunk >= npart &&
+                         (size_t)(pl->lv[3].ps + pl->lv[2].ps) * 2 * nc <= ws_lane;
+        float* I2side = f23 ? ch.I + (size_t)pl->lv[3].ps * 2 * nc : nullptr;  // (a plan may have fewer than 4 levels: ADVICE r5)
+        // levels 1 and 0 likewise (tw_pyr_k3f): level 0's images wait in the M1 region, which nothing else
+        // touches while levels 1 and 0 both run tw_flow_iter (their iterations ping-pong through M0 only) and
+        // which is large enough (5 planes per pair against 2 images of one)
+        const bool f01 = e->pyr_fused && pyr01_fusable(pl) && !e->pyr_generic && pl->lv[1].chunk >= npart &&
+                         pl->lv[0].chunk >= npart && level_mfree(0, nc) && level_mfree(1, nc);
+        float* I0side = ch.M1;
+        const uint8_t* const* srcs = e->d_ptrs + 2 * ch.j0;
+        if (f23 && k == 3) launch_pyr23(e, ch.ls, pl, srcs, stride, ch.I, I2side, 2 * nc);
+        else if (f01 && k == 1) launch_pyr01(e, ch.ls, pl, srcs, stride, ch.I, I0side, 2 * nc);
+        else if (!(f23 && k == 2) && !(f01 && k == 0)) launch_pyr(e, ch.ls, pl, k, srcs, stride, ch.I, 2 * nc);
+        const float* Isrc = (f23 && k == 2) ? I2side : (f01 && k == 0) ? I0side : ch.I;
+        return launch_polyexp(e, ch.ls, L.w, L.h, L.ld, L.ps, Isrc, ch.R, 2 * nc, k);
+    }
+
+    // -- one pair, two streams: the flow chain walks the levels on the main stream, the image-only work of the finer
+    // levels runs beside it on the second
+    tw_status enqueue_two_stream_pair()
+    {
         TW_HIP(e, hipEventRecord(e->ev_fork, st));  // pointer table + uploads + the previous batch's use of lat_I / lat_R
         TW_HIP(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
+        TW_TRY(enqueue_pair_images(pl->levels));
+        if (pl->levels >= 1) TW_TRY(enqueue_pair_images(pl->levels - 1));
+        for (int k = pl->levels; k >= 0; k--) {
+            RoctxRange level_range("tw_level %d (%dx%d)", k, pl->lv[k].w, pl->lv[k].h);
+            if (k < pl->levels && k <= e->lat_s2_max) TW_HIP(e, hipStreamWaitEvent(st, e->lat_ev[k], 0));
+            const LevelChunk ch = pair_chunk(k);
+            bool grid_stored = false;
+            enqueue_update_blur_chain(ch, &grid_stored);
+            TW_TRY(enqueue_level0_outputs(ch, grid_stored));
+            // the image-only work two levels below goes out once this level's chain is enqueued
+            if (k >= 2) TW_TRY(enqueue_pair_images(k - 2));
+        }
+        return TW_OK;
     }
-    // image-only work of level k in the single-pair schedule: the coarsest level's is needed at once and stays on the
+    // image-only work of level k in the two-stream schedule: the coarsest level's is needed at once and stays on the
     // main stream (no hand-off to wait for); the finer levels' go to the second stream.  It is ENQUEUED one level
     // ahead of the flow chain that consumes it (round 3: with all of it enqueued up front the host needed ~40 us for
     // those launches before the first flow-chain kernel was even submitted — the GPU sat idle behind the host).
-    auto lat_images = [&](int k) -> tw_status {
+    tw_status enqueue_pair_images(int k)
+    {
         const LevelPlan& L = pl->lv[k];
         const bool second = k < pl->levels && k <= e->lat_s2_max;
         hipStream_t ws = second ? e->stream2 : st;
         launch_pyr(e, ws, pl, k, e->d_ptrs, stride, e->lat_I + lat_off[k], 2);
-        tw_status rr = launch_polyexp(e, ws, L.w, L.h, L.ld, L.ps, e->lat_I + lat_off[k], e->lat_R + 5 * lat_off[k], 2, k);
-        if (rr) return rr;
+        TW_TRY(launch_polyexp(e, ws, L.w, L.h, L.ld, L.ps, e->lat_I + lat_off[k], e->lat_R + 5 * lat_off[k], 2, k));
         if (second) TW_HIP(e, hipEventRecord(e->lat_ev[k], e->stream2));
         return TW_OK;
-    };
-    // the side jobs of the twin schedule, in the order the chain needs their results
-    auto side_poly = [&](int k, int z0, int nz, int y0, int ny, int carry_level = -1, bool windows_only = false) {
+    }
+
+    // -- one pair, twin launches: one stream; the chain launches of levels 3..1 carry the side jobs (side queue below)
+    tw_status enqueue_twin_pair()
+    {
+        TW_TRY(enqueue_twin_head());
+        plan_twin_side_jobs();
+        for (int k = pl->levels; k >= 0; k--) {
+            RoctxRange level_range("tw_level %d (%dx%d)", k, pl->lv[k].w, pl->lv[k].h);
+            // whatever this level reads and no chain kernel was left to carry goes out by itself
+            while (side_next < sideq.size() && sideq[side_next].need_level >= k) side_done(false);
+            const LevelChunk ch = pair_chunk(k);
+            bool grid_stored = false;
+            enqueue_update_blur_chain(ch, &grid_stored);
+            TW_TRY(enqueue_level0_outputs(ch, grid_stored));
+        }
+        return TW_OK;
+    }
+    // levels 3 and 2 of both images (tw_pyr_23), then the coarsest level's expansion, which carries the level 0 / 1 images
+    tw_status enqueue_twin_head()
+    {
+        launch_pyr23(e, st, pl, e->d_ptrs, stride, e->lat_I + lat_off[3], e->lat_I + lat_off[2], 2);
+        const LevelPlan &L0 = pl->lv[0], &L1 = pl->lv[1], &L3 = pl->lv[3];
+        SideJob j;
+        j.kind = 2;
+        j.need_level = 1;
+        PyrK3fArgs& a = j.ka;
+        a.srcs = e->d_ptrs;
+        a.dst0 = e->lat_I + lat_off[0];
+        a.dst1 = e->lat_I + lat_off[1];
+        a.zs0 = L0.ps;
+        a.zs1 = L1.ps;
+        a.stride = stride;
+        a.w0 = pl->w0;
+        a.h0 = pl->h0;
+        a.ld0 = L0.ld;
+        a.w1 = L1.w;
+        a.h1 = L1.h;
+        a.ld1 = L1.ld;
+        a.a0 = L0.h_kern[1];
+        a.a1 = L0.h_kern[0];
+        a.b0 = L1.h_kern[1];
+        a.b1 = L1.h_kern[0];
+        a.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
+        j.g = VGrid{(unsigned)((L1.w + 255) / 256), (unsigned)((L1.h + 3) / 4), 2u, 0u, 0u};
+        bool used = false;
+        TW_TRY(launch_polyexp(e, st, L3.w, L3.h, L3.ld, L3.ps, e->lat_I + lat_off[3], e->lat_R + 5 * lat_off[3], 2, 3, &j, &used));
+        if (!used) launch_side_alone(e, st, j);
+        return TW_OK;
+    }
+    // The expansions of levels 2, 1 and 0 as side jobs.  The carriers: the update + `it` window launches of levels 3 and 2,
+    // and level 1's update.
+    void plan_twin_side_jobs()
+    {
+        sideq.clear();
+        side_next = 0;
+        const int gy2 = (pl->lv[2].h + PE_TH - 1) / PE_TH, gy1 = (pl->lv[1].h + PE_TH - 1) / PE_TH, gy0 = (pl->lv[0].h + PE_TH - 1) / PE_TH;
+        // Few, large jobs on the coarsest level's launches: a chain launch stretches to its side job's own duration plus
+        // ~2 us when it has CUs to spare (level 3: 136 workgroups), but by ~0.7 of the job's when it fills the chip itself
+        // (level 2's window launches: 510 five-wave workgroups) — profiles/r05_single_pair.md.  TW_LAT_BANDS=n: n bands per
+        // level-0 image and level 1 per image (n = 3: the first version's nine jobs on nine carriers)
+        const int bands_env = process_switches().bands;
+        push_side_poly(2, 0, 2, 0, gy2);
+        // TW_LAT_PLAN=0: round 5's plan — everything on level 3's launches (level 1's expansion, then level 0's image by image).
+        // 1 (default, round 6): level 1's expansion in `it` bands on level 3's window launches, level 0's in `it` bands (of both
+        // images) on LEVEL 1's window launches (tw_twin_s4_poly: 680 two-wave workgroups leave the chip three quarters idle);
+        // levels 2's launches and level 1's update carry nothing (they fill the chip: a carried job costs 0.7 of itself there).
+        const bool l1_twin = pl->lv[1].w > 480 && (long long)((pl->lv[1].w + 95) / 96) * ((pl->lv[1].h + 7) / 8) * 2 >= e->pp_waves &&
+                             (long long)((pl->lv[1].w + 223) / 224) * ((pl->lv[1].h + 7) / 8) < 1024 && e->blur_small < 0 &&
+                             e->blur_small_lv[1] < 0;  // level 1 takes the 96 x 8 tiles (launch_blur)
+        if (sw.lat_plan >= 1 && l1_twin && bands_env == 0) {
+            push_side_bands(1, gy1, it, 3);
+            push_side_bands(0, gy0, it, 1);  // (unequal bands, two of five bands on level 3's launches: all within the noise of this,
+                                             //  profiles/r06_single_pair.md)
+            return;
+        }
+        if (bands_env >= 2) {
+            push_side_poly(1, 0, 1, 0, gy1);
+            push_side_poly(1, 1, 1, 0, gy1);
+        } else {
+            push_side_poly(1, 0, 2, 0, gy1);
+        }
+        const int nb = std::min(8, std::max(1, bands_env));  // bands per level-0 image
+        const int rows = (gy0 + nb - 1) / nb;
+        for (int z = 0; z < 2; z++)
+            for (int y0 = 0; y0 < gy0; y0 += rows) push_side_poly(0, z, 1, y0, std::min(rows, gy0 - y0));
+    }
+    // a side job: tile rows [y0, y0 + ny) of images [z0, z0 + nz) of level k's polynomial expansion
+    void push_side_poly(int k, int z0, int nz, int y0, int ny, int carry_level = -1, bool windows_only = false)
+    {
         const LevelPlan& L = pl->lv[k];
         SideJob j;
         j.kind = 1;
@@ -1919,385 +2308,180 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
         j.pa.c = e->pc;
         j.g = VGrid{(unsigned)((L.w + PE_TW - 1) / PE_TW), (unsigned)ny, (unsigned)nz, (unsigned)y0, (unsigned)z0};
         sideq.push_back(j);
-    };
+    }
+    // level k's expansion (both images) as nb bands of tile rows, on the window launches of level `carry`
+    void push_side_bands(int k, int gy, int nb, int carry)
+    {
+        const int rows = (gy + nb - 1) / nb;
+        for (int y0 = 0; y0 < gy; y0 += rows) push_side_poly(k, 0, 2, y0, std::min(rows, gy - y0), carry, true);
+    }
     // the next side job, for the launcher of a chain kernel; side_done launches it by itself if the launcher had no twin
-    // measurement: TW_LAT_ALONE=1 every side job as its own launch; =2 also the chain kernels through their twins (empty side)
-    static const int side_alone = getenv("TW_LAT_ALONE") ? atoi(getenv("TW_LAT_ALONE")) : 0;
-    SideJob empty_side = SideJob();  // (a local: engines of several host threads run this function at once)
-    empty_side.kind = 1;
-    empty_side.g = VGrid{0u, 0u, 0u, 0u, 0u};
-    auto side_peek = [&]() -> const SideJob* {
+    const SideJob* side_peek() const
+    {
         if (side_next >= sideq.size()) return nullptr;
-        return side_alone == 2 ? &empty_side : side_alone ? nullptr : &sideq[side_next];
-    };
+        const int alone = process_switches().side_alone;
+        return alone == 2 ? &empty_side : alone ? nullptr : &sideq[side_next];
+    }
     // may a launch of level k's chain (its update launch / one of its window launches) carry the next job?
-    auto side_ok = [&](int k, bool window) -> bool {
+    bool side_ok(int k, bool window) const
+    {
         if (side_next >= sideq.size()) return false;
         const SideJob& j = sideq[side_next];
         return (j.carry_level < 0 || j.carry_level == k) && (window || !j.windows_only);
-    };
-    auto side_done = [&](bool used) {
+    }
+    void side_done(bool used)
+    {
         if (side_next >= sideq.size()) return;
-        if (!used || side_alone) launch_side_alone(e, st, sideq[side_next]);
+        if (!used || process_switches().side_alone) launch_side_alone(e, st, sideq[side_next]);
         side_next++;
-    };
-    if (lat2) {
-        sideq.clear();
-        side_next = 0;
-        launch_pyr23(e, st, pl, e->d_ptrs, stride, e->lat_I + lat_off[3], e->lat_I + lat_off[2], 2);
-        {   // the coarsest level's expansion carries the level 0 / 1 images
-            const LevelPlan &L0 = pl->lv[0], &L1 = pl->lv[1], &L3 = pl->lv[3];
-            SideJob j;
-            j.kind = 2;
-            j.need_level = 1;
-            PyrK3fArgs& a = j.ka;
-            a.srcs = e->d_ptrs;
-            a.dst0 = e->lat_I + lat_off[0];
-            a.dst1 = e->lat_I + lat_off[1];
-            a.zs0 = L0.ps;
-            a.zs1 = L1.ps;
-            a.stride = stride;
-            a.w0 = pl->w0;
-            a.h0 = pl->h0;
-            a.ld0 = L0.ld;
-            a.w1 = L1.w;
-            a.h1 = L1.h;
-            a.ld1 = L1.ld;
-            a.a0 = L0.h_kern[1];
-            a.a1 = L0.h_kern[0];
-            a.b0 = L1.h_kern[1];
-            a.b1 = L1.h_kern[0];
-            a.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
-            j.g = VGrid{(unsigned)((L1.w + 255) / 256), (unsigned)((L1.h + 3) / 4), 2u, 0u, 0u};
-            bool used = false;
-            if ((r = launch_polyexp(e, st, L3.w, L3.h, L3.ld, L3.ps, e->lat_I + lat_off[3], e->lat_R + 5 * lat_off[3], 2, 3, &j, &used)))
-                return r;
-            if (!used) launch_side_alone(e, st, j);
-        }
-        // carriers: the update + `it` window launches of levels 3 and 2, and level 1's update
-        const int carriers = 2 * (it + 1) + 1;
-        const int gy2 = (pl->lv[2].h + PE_TH - 1) / PE_TH, gy1 = (pl->lv[1].h + PE_TH - 1) / PE_TH, gy0 = (pl->lv[0].h + PE_TH - 1) / PE_TH;
-        // Few, large jobs on the coarsest level's launches: a chain launch stretches to its side job's own duration plus
-        // ~2 us when it has CUs to spare (level 3: 136 workgroups), but by ~0.7 of the job's when it fills the chip itself
-        // (level 2's window launches: 510 five-wave workgroups) — profiles/r05_single_pair.md.  TW_LAT_BANDS=n: n bands per
-        // level-0 image and level 1 per image (n = 3: the first version's nine jobs on nine carriers)
-        static const int bands_env = getenv("TW_LAT_BANDS") ? atoi(getenv("TW_LAT_BANDS")) : 0;
-        (void)carriers;
-        side_poly(2, 0, 2, 0, gy2);
-        // TW_LAT_PLAN=0: round 5's plan — everything on level 3's launches (level 1's expansion, then level 0's image by image).
-        // 1 (default, round 6): level 1's expansion in `it` bands on level 3's window launches, level 0's in `it` bands (of both
-        // images) on LEVEL 1's window launches (tw_twin_s4_poly: 680 two-wave workgroups leave the chip three quarters idle);
-        // levels 2's launches and level 1's update carry nothing (they fill the chip: a carried job costs 0.7 of itself there).
-        const int plan_env = getenv("TW_LAT_PLAN") ? atoi(getenv("TW_LAT_PLAN")) : 1;  // (read per batch: the tests switch it)
-        const bool l1_twin = pl->lv[1].w > 480 && (long long)((pl->lv[1].w + 95) / 96) * ((pl->lv[1].h + 7) / 8) * 2 >= e->pp_waves &&
-                             (long long)((pl->lv[1].w + 223) / 224) * ((pl->lv[1].h + 7) / 8) < 1024 && e->blur_small < 0 &&
-                             e->blur_small_lv[1] < 0;  // level 1 takes the 96 x 8 tiles (launch_blur)
-        if (plan_env >= 1 && l1_twin && bands_env == 0) {
-            auto bands = [&](int k, int gy, int nb, int carry) {  // level k's expansion (both images) as nb bands of tile rows
-                const int rows = (gy + nb - 1) / nb;
-                for (int y0 = 0; y0 < gy; y0 += rows) side_poly(k, 0, 2, y0, std::min(rows, gy - y0), carry, true);
-            };
-            bands(1, gy1, it, 3);
-            bands(0, gy0, it, 1);  // (unequal bands, two of five bands on level 3's launches: all within the noise of this,
-                                   //  profiles/r06_single_pair.md)
-        } else {
-        if (bands_env >= 2) {
-            side_poly(1, 0, 1, 0, gy1);
-            side_poly(1, 1, 1, 0, gy1);
-        } else {
-            side_poly(1, 0, 2, 0, gy1);
-        }
-        const int nb = std::min(8, std::max(1, bands_env));  // bands per level-0 image
-        const int rows = (gy0 + nb - 1) / nb;
-        for (int z = 0; z < 2; z++)
-            for (int y0 = 0; y0 < gy0; y0 += rows) side_poly(0, z, 1, y0, std::min(rows, gy0 - y0));
-        }
-    } else if (lat) {
-        if ((r = lat_images(pl->levels))) return r;
-        if (pl->levels >= 1 && (r = lat_images(pl->levels - 1))) return r;
     }
-    const bool ramp = ramp_n > 2;  // (only with nlanes == 1 and never for a single pair: see where ramp_b is filled)
-    const int nparts = ramp ? ramp_n - 1 : nlanes;
-    for (int part = 0; part < nparts; part++) {
-        const int lane = ramp ? 0 : part;
-        hipStream_t ls = lane == 0 ? st : e->stream2;
-        const int lo = ramp ? ramp_b[part] : (int)((long long)n * lane / nlanes);
-        const int hi = ramp ? ramp_b[part + 1] : (int)((long long)n * (lane + 1) / nlanes);
-        if (ramp) TW_HIP(e, hipStreamWaitEvent(st, part + 1 < nparts ? c.ev_seg[part] : c.ev_h2d, 0));
-        float* I = e->I + ws_lane * lane;
-        float* R = e->R + ws_lane * 5 * lane;
-        float* M0 = e->M[0] + ws_lane / 2 * 5 * lane;
-        float* M1 = e->M[1] + ws_lane / 2 * 5 * lane;
-        for (int k = pl->levels; k >= 0; k--) {
-            const LevelPlan& L = pl->lv[k];
-            RoctxRange level_range("tw_level %d (%dx%d)", k, L.w, L.h);
-            // balanced launches: 64 pairs with a 63-pair chunk are 32 + 32, not 63 + 1
-            const int per = balanced_launch_pairs(hi - lo, L.chunk);
-            for (int j0 = lo; j0 < hi; j0 += per) {
-                const int nc = std::min(per, hi - j0);
-                // flow buffers: levels >= 1 keep every pair of the batch, level 0 only the lane's current chunk
-                float* flow_cur = e->flow[k] + (k == 0 ? (size_t)lane * L.chunk * 2 * L.ps : (size_t)j0 * 2 * L.ps);
-                const float* flow_prev =
-                    k < pl->levels ? e->flow[k + 1] + (size_t)j0 * 2 * pl->lv[k + 1].ps : nullptr;
-                if (lat2) {
-                    R = e->lat_R + 5 * lat_off[k];
-                    // whatever this level reads and no chain kernel was left to carry goes out by itself
-                    while (side_next < sideq.size() && sideq[side_next].need_level >= k) side_done(false);
-                } else if (lat) {
-                    R = e->lat_R + 5 * lat_off[k];
-                    if (k < pl->levels && k <= e->lat_s2_max) TW_HIP(e, hipStreamWaitEvent(ls, e->lat_ev[k], 0));
-                } else {
-                    // levels 3 and 2 from one read of the images (tw_pyr_23): level 3's launch also writes level 2's
-                    // images, behind its own in the workspace (sized for level 0: there is room), and level 2 skips its
-                    // pyramid launch.  Only when both levels cover the same pairs per launch.
-                    // (one launch per level for this lane: the loop is level-major, a second chunk of level 3 would
-                    // overwrite the first chunk's level-2 images before level 2 reads them)
-                    const bool f23 = pl->fused23 && e->pyr_fused && pl->lv[3].chunk >= hi - lo && pl->lv[2].chunk >= hi - lo &&
-                                     (size_t)(pl->lv[3].ps + pl->lv[2].ps) * 2 * nc <= ws_lane;
-                    float* I2side = f23 ? I + (size_t)pl->lv[3].ps * 2 * nc : nullptr;  // (a plan may have fewer than 4 levels: ADVICE r5)
-                    // levels 1 and 0 likewise (tw_pyr_k3f): level 0's images wait in the M1 region, which nothing else
-                    // touches while levels 1 and 0 both run tw_flow_iter (their iterations ping-pong through M0 only) and
-                    // which is large enough (5 planes per pair against 2 images of one)
-                    const bool f01 = e->pyr_fused && pyr01_fusable(pl) && !e->pyr_generic && pl->lv[1].chunk >= hi - lo &&
-                                     pl->lv[0].chunk >= hi - lo && level_mfree(0, nc) && level_mfree(1, nc);
-                    float* I0side = M1;
-                    if (f23 && k == 3) launch_pyr23(e, ls, pl, e->d_ptrs + 2 * j0, stride, I, I2side, 2 * nc);
-                    else if (f01 && k == 1) launch_pyr01(e, ls, pl, e->d_ptrs + 2 * j0, stride, I, I0side, 2 * nc);
-                    else if (!(f23 && k == 2) && !(f01 && k == 0)) launch_pyr(e, ls, pl, k, e->d_ptrs + 2 * j0, stride, I, 2 * nc);
-                    const float* Isrc = (f23 && k == 2) ? I2side : (f01 && k == 0) ? I0side : I;
-                    if ((r = launch_polyexp(e, ls, L.w, L.h, L.ld, L.ps, Isrc, R, 2 * nc, k))) return r;
-                }
-                // M-free iterations (tw_flow_iter; TW_MFREE): the level's iterations read the previous flow and recompute M
-                // inside the kernel — no FarnebackUpdateMatrices launch, no M planes.  Flows ping-pong between the level's
-                // flow buffer and the (now unused) M0 workspace so that the last iteration lands in the flow buffer.
-                // scan-fused final iteration (option TW_OPT_SCAN_FUSED_FINAL): nothing but the span grid of the last
-                // level-0 flow is read afterwards, so the last window average + solve runs at the grid points only
-                const bool grid_only = k == 0 && fused_final;
-                bool iterated = false;
-                bool grid_stored = false;  // the last window launch wrote the span-grid samples itself (single pair)
-                // a batch with initial flow fields: every chunk of the coarsest level starts from tw_flow_area_init's output
-                // (zeros for its pairs without a field) through the non-zero-flow kernels
-                const bool init_lv = c.any_init && k == pl->levels;
-                // (with the scan-fused last iteration: it - 1 iterations here, then the M of the last flow from
-                // tw_update_matrices<false> into M1 — tw_blur_grid evaluates the window average + solve at the span-grid
-                // points from it; a single iteration has no flow of this level to start from and takes the old launches)
-                if (level_mfree(k, nc)) {
-                    const int nfi = grid_only ? it - 1 : it;
-                    float* buf[2] = {flow_cur, M0};  // iteration i writes buf[(nfi - 1 - i) & 1]: the last one the flow buffer
-                    if (init_lv) launch_area_init(e, ls, pl, buf[nfi & 1], j0, nc);  // (what iteration 0 reads)
-                    FlowUps ups;
-                    if (k < pl->levels) {
-                        const LevelPlan& Pv = pl->lv[k + 1];
-                        ups = FlowUps{flow_prev, Pv.w, Pv.h, Pv.ld, Pv.ps, L.d_uxofs, L.d_uyofs, L.d_ualpha, L.d_ubeta, L.uxmax,
-                                      (float)(1. / e->p.pyrScale)};
-                    }
-                    for (int i = 0; i < nfi; i++) {
-                        float* out = buf[(nfi - 1 - i) & 1];
-                        const float* in = i == 0 ? (init_lv ? buf[nfi & 1] : nullptr) : buf[(nfi - i) & 1];
-                        launch_flow_iter(e, ls, L.w, L.h, L.ld, L.ps, R, in, L.ps, out, L.ps,
-                                         (i == 0 && k < pl->levels) ? &ups : nullptr, nc, k);
-                    }
-                    if (grid_only) {
-                        UpdArgs u;
-                        memset(&u, 0, sizeof(u));
-                        u.R = R;
-                        u.flow = flow_cur;
-                        u.M = M1;
-                        u.w = L.w;
-                        u.h = L.h;
-                        u.ld = L.ld;
-                        u.ps = L.ps;
-                        u.fps = L.ps;
-                        {
-                            ProfScope pscope(e, ls, TW_K_UPDATE_MATRICES, k);
-                            launch_upd_kernel<false>(e, ls, L.w, L.h, nc, u);
-                        }
-                        BlurGridArgs g;
-                        g.Min = M1;
-                        g.w = L.w;
-                        g.h = L.h;
-                        g.ld = L.ld;
-                        g.ps = L.ps;
-                        g.gw = (L.w + c.span - 1) / c.span;
-                        g.gh = (L.h + c.span - 1) / c.span;
-                        g.gzs = (long long)g.gw * g.gh;
-                        g.g = e->d_grid + (size_t)j0 * g.gw * g.gh;
-                        g.c = e->wc;
-                        ProfScope pscope(e, ls, TW_K_BLUR_SOLVE, 0);
-                        TW_LAUNCH(e, TW_DF_BLUR_GRID, (tw_blur_grid<15, 10, 2>), dim3((g.gw + 21) / 22, (g.gh + 1) / 2, nc), dim3(256), 0, ls, g);
-                    }
-                    iterated = true;
-                }
-                if (!iterated) {
-                    if (init_lv) launch_area_init(e, ls, pl, flow_cur, j0, nc);
-                    if (lat2 && k >= 1 && side_ok(k, false)) {
-                        bool used = false;
-                        launch_update(e, ls, pl, k, R, flow_cur, flow_prev, M0, nc, side_peek(), &used, init_lv);
-                        side_done(used);
-                    } else {
-                        launch_update(e, ls, pl, k, R, flow_cur, flow_prev, M0, nc, nullptr, nullptr, init_lv);
-                    }
-                }
-                for (int i = 0; i < it && !iterated; i++) {
-                    if (grid_only && i == it - 1) {
-                        BlurGridArgs g;
-                        g.Min = (i & 1) ? M1 : M0;
-                        g.w = L.w;
-                        g.h = L.h;
-                        g.ld = L.ld;
-                        g.ps = L.ps;
-                        g.gw = (L.w + c.span - 1) / c.span;
-                        g.gh = (L.h + c.span - 1) / c.span;
-                        g.gzs = (long long)g.gw * g.gh;
-                        g.g = e->d_grid + (size_t)j0 * g.gw * g.gh;
-                        g.c = e->wc;
-                        ProfScope pscope(e, ls, TW_K_BLUR_SOLVE, 0);
-                        TW_LAUNCH(e, TW_DF_BLUR_GRID, (tw_blur_grid<15, 10, 2>), dim3((g.gw + 21) / 22, (g.gh + 1) / 2, nc), dim3(256), 0, ls, g);
-                        break;
-                    }
-                    if (lat2 && k >= 1 && side_ok(k, true)) {
-                        bool used = false;
-                        launch_blur(e, ls, L.w, L.h, L.ld, L.ps, (i & 1) ? M1 : M0, (i & 1) ? M0 : M1, flow_cur, R, i < it - 1, k, nc,
-                                    nullptr, side_peek(), &used);
-                        side_done(used);
-                        continue;
-                    }
-                    if (lat && k == 0 && i == it - 1 && c.span > 0 && !grid_only) {
-                        // the launch that stores the final flow stores its span-grid samples too: no tw_span_gather launch
-                        GridOut go{e->d_grid + (size_t)j0 * ((L.w + c.span - 1) / c.span) * ((L.h + c.span - 1) / c.span), c.span,
-                                   (L.w + c.span - 1) / c.span, (L.h + c.span - 1) / c.span, &grid_stored};
-                        launch_blur(e, ls, L.w, L.h, L.ld, L.ps, (i & 1) ? M1 : M0, (i & 1) ? M0 : M1, flow_cur, R, 0, k, nc,
-                                    e->Vd ? e->Vd + ws_lane / 2 * 5 * lane : nullptr, nullptr, nullptr, &go, lat_quads);
-                        continue;
-                    }
-                    launch_blur(e, ls, L.w, L.h, L.ld, L.ps, (i & 1) ? M1 : M0, (i & 1) ? M0 : M1, flow_cur, R,
-                                i < it - 1, k, nc, e->Vd ? e->Vd + ws_lane / 2 * 5 * lane : nullptr, nullptr, nullptr, nullptr, lat_quads);
-                }
-                if (k == 0 && c.span > 0 && !grid_only && !grid_stored) {
-                    // grid samples of this chunk -> dense per-pair buffer (the ordered scan runs once per batch).
-                    // (A scan that samples the flow planes itself — tw_span_scan<true>, TW_SCAN_DIRECT=1 of the variants library — saves this launch and
-                    // costs more than it: one workgroup's 41 472 scattered dwords are 19.5 us on one CU's memory pipe against
-                    // 4.8 + 7.3 us for the gather on 81 workgroups + the scan; gpurun_out/r7lat)
-                    GatherArgs g;
-                    g.flow = flow_cur;
-                    g.fzs = 2 * L.ps;
-                    g.fps = L.ps;
-                    g.ld = L.ld;
-                    g.span = c.span;
-                    g.gw = (L.w + c.span - 1) / c.span;
-                    g.gh = (L.h + c.span - 1) / c.span;
-                    g.g = e->d_grid + (size_t)j0 * g.gw * g.gh;
-                    ProfScope pscope(e, ls, TW_K_SCAN, 0);
-                    TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((g.gw + 63) / 64, (g.gh + 3) / 4, nc), dim3(256), 0, ls, g);
-                }
-                if (k == 0 && c.any_fout && (r = export_chunk(e, c, ls, L, flow_cur, j0, nc, fslot))) return r;
-                // the image-only work two levels below goes out once this level's chain is enqueued
-                if (lat && !lat2 && k >= 2 && (r = lat_images(k - 2))) return r;
-            }
-        }
-    }
-    if (nlanes > 1) {
-        TW_HIP(e, hipEventRecord(e->ev_join, e->stream2));
-        TW_HIP(e, hipStreamWaitEvent(st, e->ev_join, 0));
-    }
-    return TW_OK;
-    };  // enqueue_levels
 
-    // Single pair (BASELINE config 2): ~26 launches and ~10 event operations, half of them kernels of 5-10 us.  With
-    // TW_LAT_GRAPH=1 the whole DAG — both streams, their hand-offs — is captured once per (size, span, stride,
-    // alignment, options) and replayed with one hipGraphLaunch; the ordered scan and the result copies stay outside
-    // (their targets belong to the batch context).  Round 3 measured it: the host is NOT what holds the schedule back
-    // (the direct enqueue takes 110 us of host time for 375 us of GPU time, TW_DEBUG_HOSTTIME), and the replayed graph
-    // is slower (0.55 ms: kernels of the forked branch stretch to ~40 us quanta behind cross-queue signals), so the
-    // direct path is the default and the graph an opt-in A/B switch (profiles/r03_latency.md).
-    bool launched_graph = false;
-    if (lat && e->lat_graph && !prof_on && !c.any_fout && !c.any_init) {  // (destinations / fields would be baked into the graph)
-        const GraphKey key{c.w, c.h, c.span, stride, e->img_aligned4, e->scan_fused, e->poly_f32};
-        auto git = e->lat_graphs.find(key);
-        if (git == e->lat_graphs.end()) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) == hipSuccess;
-            tw_status br = TW_OK;
-            if (ok) {
-                br = enqueue_levels();
-                ok = hipStreamEndCapture(st, &graph) == hipSuccess && graph != nullptr && br == TW_OK;
-            }
-            if (br != TW_OK) {
-                if (graph) (void)hipGraphDestroy(graph);
-                (void)hipGetLastError();
-                return br;
-            }
-            ok = ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (ok) {
-                git = e->lat_graphs.emplace(key, exec).first;
-            } else {
-                (void)hipGetLastError();
-                e->lat_graph = 0;  // this runtime cannot capture the schedule: direct launches from now on
-            }
+    // ---- the launches of a chunk's flow chain (shared by the schedules) ------------------------------------
+
+    // M-free iterations (tw_flow_iter; TW_MFREE): the level's iterations read the previous flow and recompute M
+    // inside the kernel — no FarnebackUpdateMatrices launch, no M planes.  Flows ping-pong between the level's
+    // flow buffer and the (now unused) M0 workspace so that the last iteration lands in the flow buffer.
+    // (with the scan-fused last iteration: it - 1 iterations here, then the M of the last flow from
+    // tw_update_matrices<false> into M1 — tw_blur_grid evaluates the window average + solve at the span-grid
+    // points from it; a single iteration has no flow of this level to start from and takes the old launches)
+    void enqueue_flow_iter_chain(const LevelChunk& ch)
+    {
+        const int k = ch.k, nc = ch.nc;
+        const LevelPlan& L = pl->lv[k];
+        const int nfi = ch.grid_only ? it - 1 : it;
+        float* buf[2] = {ch.flow_cur, ch.M0};  // iteration i writes buf[(nfi - 1 - i) & 1]: the last one the flow buffer
+        if (ch.init_lv) launch_area_init(e, ch.ls, pl, buf[nfi & 1], ch.j0, nc);  // (what iteration 0 reads)
+        FlowUps ups;
+        if (k < pl->levels) {
+            const LevelPlan& Pv = pl->lv[k + 1];
+            ups = FlowUps{ch.flow_prev, Pv.w, Pv.h, Pv.ld, Pv.ps, L.d_uxofs, L.d_uyofs, L.d_ualpha, L.d_ubeta, L.uxmax,
+                          (float)(1. / e->p.pyrScale)};
         }
-        if (git != e->lat_graphs.end()) {
-            TW_HIP(e, hipGraphLaunch(git->second, st));
-            launched_graph = true;
+        for (int i = 0; i < nfi; i++) {
+            float* out = buf[(nfi - 1 - i) & 1];
+            const float* in = i == 0 ? (ch.init_lv ? buf[nfi & 1] : nullptr) : buf[(nfi - i) & 1];
+            launch_flow_iter(e, ch.ls, L.w, L.h, L.ld, L.ps, ch.R, in, L.ps, out, L.ps,
+                             (i == 0 && k < pl->levels) ? &ups : nullptr, nc, k);
         }
-    }
-    if (!launched_graph) {
-        static const bool host_time = getenv("TW_DEBUG_HOSTTIME") != nullptr;  // diagnostic: host cost of the enqueue
-        const auto t_h0 = std::chrono::steady_clock::now();
-        if ((r = enqueue_levels())) return r;
-        if (host_time)
-            fprintf(stderr, "twflow: enqueue of %d pair(s) %dx%d took %.1f us on the host\n", n, c.w, c.h,
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_h0).count());
-    }
-    if (c.span > 0) {
-        const LevelPlan& L = pl->lv[0];
-        ScanArgs a;
-        a.g = e->d_grid;
-        a.span = c.span;
-        a.gw = (L.w + c.span - 1) / c.span;
-        a.gh = (L.h + c.span - 1) / c.span;
-        a.thr2 = c.threshold * c.threshold;
-        a.count = e->d_count;
-        a.rec_zs = (long long)a.gw * a.gh;
-        a.rec = c.d_rec;
-        a.flow = e->flow[0];
-        a.fps = L.ps;
-        a.ld = L.ld;
-        const bool grid_only = e->p.pyrIterations > 0 && e->scan_fused && c.span == 10 && e->win_m == 15 && !e->box;
-        (void)grid_only;
-        ProfScope pscope(e, st, TW_K_SCAN, 0);
-#ifdef TW_VARIANTS
-        static const bool scan_direct = getenv("TW_SCAN_DIRECT") != nullptr;
-        if (lat && !grid_only && scan_direct) {
-            TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<true>, dim3(n), dim3(1024), 0, st, a);
-        } else
-#endif
+        if (!ch.grid_only) return;
+        UpdArgs u;
+        memset(&u, 0, sizeof(u));
+        u.R = ch.R;
+        u.flow = ch.flow_cur;
+        u.M = ch.M1;
+        u.w = L.w;
+        u.h = L.h;
+        u.ld = L.ld;
+        u.ps = L.ps;
+        u.fps = L.ps;
         {
-            // a single pair: 16 segments, each workgroup counting the hits before its own (tw_span_scan_seg: -5 us of one CU's VALU time)
-            const long long G = (long long)a.gw * a.gh;
-            const int S = (int)(((G + 15) / 16 + 1023) / 1024 * 1024);
-            const bool scan_seg = !getenv("TW_SCAN_SEG") || atoi(getenv("TW_SCAN_SEG")) != 0;  // (read per batch: a test compares the two kernels)
-            if (n == 1 && lat && scan_seg && G > 2048 && S <= SCAN_IT * 1024)
-                TW_LAUNCH(e, TW_DF_SPAN_SCAN_SEG, tw_span_scan_seg, dim3((unsigned)((G + S - 1) / S)), dim3(1024), 0, st, a, S);
-            else
-                TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<false>, dim3(n), dim3(1024), 0, st, a);
+            ProfScope pscope(e, ch.ls, TW_K_UPDATE_MATRICES, k);
+            launch_upd_kernel<false>(e, ch.ls, L.w, L.h, nc, u);
+        }
+        enqueue_grid_tail(ch, ch.M1);
+    }
+
+    // FarnebackUpdateMatrices, then `it` window launches ping-ponging M0 / M1.  In the twin schedule a launch of levels
+    // 3..1 carries the next side job when it may; a single pair's last level-0 launch stores the span-grid samples too
+    // (*grid_stored: no tw_span_gather launch needed)
+    void enqueue_update_blur_chain(const LevelChunk& ch, bool* grid_stored)
+    {
+        const int k = ch.k, nc = ch.nc;
+        const LevelPlan& L = pl->lv[k];
+        if (ch.init_lv) launch_area_init(e, ch.ls, pl, ch.flow_cur, ch.j0, nc);
+        if (k >= 1 && side_ok(k, false)) {
+            bool used = false;
+            launch_update(e, ch.ls, pl, k, ch.R, ch.flow_cur, ch.flow_prev, ch.M0, nc, side_peek(), &used, ch.init_lv);
+            side_done(used);
+        } else {
+            launch_update(e, ch.ls, pl, k, ch.R, ch.flow_cur, ch.flow_prev, ch.M0, nc, nullptr, nullptr, ch.init_lv);
+        }
+        for (int i = 0; i < it; i++) {
+            const float* Min = (i & 1) ? ch.M1 : ch.M0;
+            float* Mout = (i & 1) ? ch.M0 : ch.M1;
+            const bool last = i == it - 1;
+            if (ch.grid_only && last) {
+                enqueue_grid_tail(ch, Min);
+            } else if (k >= 1 && side_ok(k, true)) {
+                bool used = false;
+                launch_blur(e, ch.ls, L.w, L.h, L.ld, L.ps, Min, Mout, ch.flow_cur, ch.R, !last, k, nc, nullptr, side_peek(), &used);
+                side_done(used);
+            } else if (lat && k == 0 && last && c.span > 0) {
+                // the launch that stores the final flow stores its span-grid samples too: no tw_span_gather launch
+                GridOut go{grid_of(ch.j0), c.span, gw, gh, grid_stored};
+                launch_blur(e, ch.ls, L.w, L.h, L.ld, L.ps, Min, Mout, ch.flow_cur, ch.R, 0, k, nc, ch.Vbox, nullptr, nullptr, &go, lat_quads);
+            } else {
+                launch_blur(e, ch.ls, L.w, L.h, L.ld, L.ps, Min, Mout, ch.flow_cur, ch.R, !last, k, nc, ch.Vbox, nullptr, nullptr, nullptr,
+                            lat_quads);
+            }
         }
     }
-    TW_HIP(e, hipEventRecord(c.ev_stop, st));
-    if (c.span > 0) {
-        const size_t G = (size_t)tw_grid_capacity(c.w, c.h, c.span);
-        const size_t nrec = std::min((size_t)HOST_RECS, G);
-        TW_HIP(e, hipMemcpyAsync(c.h_count, e->d_count, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-        TW_HIP(e, hipMemcpy2DAsync(c.h_rec, HOST_RECS * sizeof(ScanRec), c.d_rec, G * sizeof(ScanRec),
-                                   nrec * sizeof(ScanRec), n, hipMemcpyDeviceToHost, st));
+
+    // the scan-fused final iteration: window average + solve of M at the span-grid points only (the one tw_blur_grid launch)
+    void enqueue_grid_tail(const LevelChunk& ch, const float* Min)
+    {
+        const LevelPlan& L = pl->lv[ch.k];
+        BlurGridArgs g;
+        g.Min = Min;
+        g.w = L.w;
+        g.h = L.h;
+        g.ld = L.ld;
+        g.ps = L.ps;
+        g.gw = gw;
+        g.gh = gh;
+        g.gzs = (long long)g.gw * g.gh;
+        g.g = grid_of(ch.j0);
+        g.c = e->wc;
+        ProfScope pscope(e, ch.ls, TW_K_BLUR_SOLVE, 0);
+        TW_LAUNCH(e, TW_DF_BLUR_GRID, (tw_blur_grid<15, 10, 2>), dim3((g.gw + 21) / 22, (g.gh + 1) / 2, ch.nc), dim3(256), 0, ch.ls, g);
     }
-    if (c.any_fout_host) {
-        TW_HIP(e, hipEventRecord(c.ev_d2h, e->d2h_stream));
-        c.d2h_ops_at_flush = e->d2h_ops;
+
+    // grid samples of this chunk -> dense per-pair buffer (the ordered scan runs once per batch).
+    // (A scan that samples the flow planes itself — tw_span_scan<true>, TW_SCAN_DIRECT=1 of the variants library — saves this launch and
+    // costs more than it: one workgroup's 41 472 scattered dwords are 19.5 us on one CU's memory pipe against
+    // 4.8 + 7.3 us for the gather on 81 workgroups + the scan; gpurun_out/r7lat)
+    void enqueue_span_gather(const LevelChunk& ch)
+    {
+        const LevelPlan& L = pl->lv[ch.k];
+        GatherArgs g;
+        g.flow = ch.flow_cur;
+        g.fzs = 2 * L.ps;
+        g.fps = L.ps;
+        g.ld = L.ld;
+        g.span = c.span;
+        g.gw = gw;
+        g.gh = gh;
+        g.g = grid_of(ch.j0);
+        ProfScope pscope(e, ch.ls, TW_K_SCAN, 0);
+        TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((g.gw + 63) / 64, (g.gh + 3) / 4, ch.nc), dim3(256), 0, ch.ls, g);
     }
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipEventRecord(c.ev_done, st));
+
+    // what leaves a level-0 chunk once its chain is enqueued: the span-grid samples, the flow fields
+    tw_status enqueue_level0_outputs(const LevelChunk& ch, bool grid_stored)
+    {
+        if (ch.k != 0) return TW_OK;
+        if (c.span > 0 && !ch.grid_only && !grid_stored) enqueue_span_gather(ch);
+        if (c.any_fout) return export_chunk(e, c, ch.ls, pl->lv[0], ch.flow_cur, ch.j0, ch.nc, fslot);
+        return TW_OK;
+    }
+};
+
+// Enqueue a whole batch, level-major: every level is processed for all pairs (in chunks sized to fill the
+// chip) before the next finer level starts; level 0 chunks are scanned as soon as their flow exists.
+tw_status flush_ctx(tw_engine* e, Ctx& c)
+{
+    if (c.launched || c.jobs.empty()) return TW_OK;
+    BatchEnqueue b(e, c);
+    TW_TRY(b.reserve_batch_buffers());
+    RoctxRange batch_range("tw_batch %dx%d pairs=%d", c.w, c.h, b.n);
+    TW_TRY(b.enqueue_png_unfilter());
+    TW_TRY(b.mark_uploads_and_plan_ramp());
+    TW_TRY(b.upload_tables());
+    TW_HIP(e, hipEventRecord(c.ev_start, e->stream));
+    TW_TRY(b.choose_schedule());
+    TW_TRY(b.enqueue_or_replay_graph());
+    TW_TRY(b.enqueue_scan());
+    TW_TRY(b.enqueue_result_copies());
     c.launched = true;
     return TW_OK;
 }
@@ -2538,15 +2722,8 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
         // DMA-ed in place from a page-locked block (the caller keeps it until tw_wait), through the engine's pinned bounce
         // buffer from any other memory (copied before this call returns, as pageable images are)
         const size_t fslot = flow_stage_slot(width, height);
-        if (fslot * e->cap > c->d_istage_cap) {
-            // only on the first host field of a batch (one size per batch); this context's earlier batches are waited
-            TW_HIP(e, hipStreamSynchronize(e->copy_stream));
-            if (c->d_istage) (void)hipFree(c->d_istage);
-            c->d_istage = nullptr;
-            c->d_istage_cap = 0;
-            TW_HIP(e, hipMalloc((void**)&c->d_istage, fslot * e->cap + 256));
-            c->d_istage_cap = fslot * e->cap;
-        }
+        // (grows only on the first host field of a batch — one size per batch; this context's earlier batches are waited)
+        TW_TRY(grow_device(e, c->d_istage, c->d_istage_cap, fslot * e->cap, fslot * e->cap + 256, e->copy_stream));
         char* dst = c->d_istage + fslot * c->jobs.size();
         const size_t row = (size_t)width * (fi->layout ? 8 : 4), rows = (size_t)height * (fi->layout ? 1 : 2);
         if (fi_kind == 1) {
@@ -2574,15 +2751,8 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
         const size_t npx = staged_image_bytes(width, height);
         const size_t need = npx * 2 * e->cap;
         const size_t j = c->jobs.size();
-        if (need > c->d_img_cap) {
-            // only ever happens on the first job of a batch (all jobs of a batch have one size)
-            TW_HIP(e, hipStreamSynchronize(e->copy_stream));
-            if (c->d_img) (void)hipFree(c->d_img);
-            c->d_img = nullptr;
-            c->d_img_cap = 0;
-            TW_HIP(e, hipMalloc((void**)&c->d_img, need + 256));
-            c->d_img_cap = need;
-        }
+        // (grows only on the first job of a batch: all jobs of a batch have one size)
+        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, need, need + 256, e->copy_stream));
         uint8_t* dst_a = c->d_img + npx * (2 * j);
         uint8_t* dst_b = c->d_img + npx * (2 * j + 1);
         if (png) {
@@ -2592,17 +2762,12 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
                 // first filtered image of this batch: slots as large as the region allows, at least what it needs
                 const size_t have = c->d_filt_cap / (2 * (size_t)e->cap) / 256 * 256;
                 const size_t slot = std::max(filt_need, have);
-                if (slot * 2 * (size_t)e->cap > c->d_filt_cap) {
-                    TW_HIP(e, hipStreamSynchronize(e->copy_stream));
-                    if (c->d_filt_raw) (void)hipFree(c->d_filt_raw);
-                    c->d_filt = c->d_filt_raw = nullptr;
-                    c->d_filt_cap = 0;
-                    // 256 bytes of slack on either side: tw_png_unfilter fetches whole 16-byte groups and may read a few
-                    // bytes before the first and after the last row of an image
-                    TW_HIP(e, hipMalloc((void**)&c->d_filt_raw, slot * 2 * (size_t)e->cap + 512));
-                    c->d_filt = c->d_filt_raw + 256;
-                    c->d_filt_cap = slot * 2 * (size_t)e->cap;
-                }
+                // 256 bytes of slack on either side: tw_png_unfilter fetches whole 16-byte groups and may read a few
+                // bytes before the first and after the last row of an image
+                const size_t filt_bytes = slot * 2 * (size_t)e->cap;
+                r = grow_device(e, c->d_filt_raw, c->d_filt_cap, filt_bytes, filt_bytes + 512, e->copy_stream);
+                c->d_filt = c->d_filt_raw ? c->d_filt_raw + 256 : nullptr;  // (whatever became of the region)
+                if (r) return r;
                 // (only now — a failed synchronise / allocation above leaves filt_slot at 0, so that the next
                 // filtered image of this batch tries again instead of copying to a null region)
                 c->filt_slot = slot;
@@ -2625,13 +2790,7 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
                 // a pointer it would have to page-lock on the fly — the image goes through the engine's own pinned bounce
                 // buffer and the copy is over before the next one starts (the host layer hands over page-locked arenas;
                 // this is the slow, always-correct path)
-                if (nb > e->h_bounce_cap) {
-                    if (e->h_bounce) (void)hipHostFree(e->h_bounce);
-                    e->h_bounce = nullptr;
-                    e->h_bounce_cap = 0;
-                    TW_HIP(e, hipHostMalloc((void**)&e->h_bounce, nb, hipHostMallocDefault));
-                    e->h_bounce_cap = nb;
-                }
+                TW_TRY(bounce_reserve(e, nb));
                 memcpy(e->h_bounce, src[q], nb);
                 TW_HIP(e, hipMemcpyAsync(dst, e->h_bounce, nb, hipMemcpyHostToDevice, e->copy_stream));
                 TW_HIP(e, hipStreamSynchronize(e->copy_stream));
@@ -2656,13 +2815,7 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
                                            hipMemcpyHostToDevice, e->copy_stream));
             }
         } else {
-            if (need > c->h_img_cap) {
-                if (c->h_img) (void)hipHostFree(c->h_img);
-                c->h_img = nullptr;
-                c->h_img_cap = 0;
-                TW_HIP(e, hipHostMalloc((void**)&c->h_img, need, hipHostMallocDefault));
-                c->h_img_cap = need;
-            }
+            TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, need));
             uint8_t* da = c->h_img + npx * (2 * j);
             uint8_t* db = c->h_img + npx * (2 * j + 1);
             for (int y = 0; y < height; y++) {
