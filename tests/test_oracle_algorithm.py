@@ -11,6 +11,13 @@ wrong, by checking the oracle against what the ALGORITHM must produce, computed 
   (c) a pyramid level equals scipy's mirror-border Gaussian correlation of the full-resolution image followed by the
       explicit 2x2 mean the bilinear resize degenerates to at power-of-two ratios (ksize 3 / 9 / 19 / 39 / 79).
 
+Since then tests/test_oracle_stages_f64.py checks EVERY stage, on every pixel, against an independent float64 reference
+(tests/farneback_f64.py) within that reference's propagated float32 bound: FarnebackUpdateMatrices, the Gaussian and box
+windows with the solve, the flow upsample, INTER_AREA seeding, pyramid levels at any pyrScale, the level plan, the span
+scan and the expansion at every pixel.  What stays here: the multi-level, multi-iteration warp recovery (a chain no
+bound crosses, because each iteration floors its sample position), the sparse least-squares fit and the 0.5-scale
+pyramid.  Bit-for-bit parity with a real OpenCV 2.4.9 build remains unpinned.
+
 Reference call site: /root/reference/src/opticalflow.cpp:83-85.  CPU only.
 """
 import numpy as np
