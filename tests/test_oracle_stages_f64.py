@@ -415,7 +415,9 @@ def test_one_iteration_one_level_end_to_end(oracle, h, w, gaussian):
 
 
 def test_polyexp_every_pixel(oracle):
-    """The expansion on every pixel (test_oracle_algorithm.py solves the least-squares fit at 68 of them)."""
+    """The expansion on every pixel (test_oracle_algorithm.py solves the least-squares fit at 68 of them).  Three points of
+    the parameter axis; tests/test_oracle_params.py runs polyN 1..7 x five sigmas with this same judge, and
+    tests/test_gpu_params.py the kernels — a case added here belongs there too."""
     for (h, w, n, sg) in ((40, 52, 7, 1.5), (117, 180, 5, 1.1), (33, 47, 7, 0.0)):
         I = (ndimage.gaussian_filter(np.random.default_rng(h).random((h, w)), 1.0) * 255).astype(F32)
         ref, bound = F.polyexp(I, 0.0, n, sg)
