@@ -76,6 +76,13 @@ enum tw_debug_family {
  * reset != 0 zeroes the counters after copying them.  Returns TW_DF_COUNT, -1 for a null engine. */
 int tw_debug_launch_counts(tw_engine* e, unsigned long long* counts, unsigned long long* last_z, int n, int reset);
 
+/* The geometry of one tw_flow_iter launch of npairs pairs at a level of width x height pixels, from the one function the
+ * launch itself takes its grid from: out[0] strips (grid x), out[1] row segments per strip (grid y), out[2] steps of 5 rows
+ * per segment, out[3] steps of the last segment.  It depends on the engine's CU count and on TW_FI_MAXSEG / TW_FI_MINSTEPS
+ * as tw_engine_create read them.  Returns the number of values written (at most min(n, 4); 0 for a null `out` or a
+ * non-positive size), -1 for a null engine.  tests/test_gpu_flow_iter_geometry.py proves from it which geometry ran. */
+int tw_debug_flow_iter_plan(const tw_engine* e, int width, int height, int npairs, int* out, int n);
+
 /* Name of a family ("tw_flow_iter", ...), NULL past the end. */
 const char* tw_debug_family_name(int family);
 

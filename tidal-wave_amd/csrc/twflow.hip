@@ -1320,6 +1320,39 @@ struct FlowUps {  // the coarser level's flow and the resize tables to this leve
     int xmax;
     float scale;
 };
+// The geometry of one tw_flow_iter launch — the ONE place the strip / row-segment rule lives: launch_flow_iter takes its
+// grid (strips, segments, pairs) and the kernel's steps per segment from it, and tw_debug_flow_iter_plan shows it to the tests.
+struct FlowIterPlan {
+    int strips, segments, nt, nt_last;  // nt: steps of FI_TH rows per segment; nt_last: steps of the last segment
+};
+FlowIterPlan flow_iter_plan(const tw_engine* e, int w, int h, int npairs)
+{
+    const int OUT = (e->fi_nt == 512 ? FI_SC_512 : FI_SC) - 30;
+    const int slots = e->cu_count * (e->fi_nt == 512 ? 2 : 1);  // workgroups resident at once
+    const int nstrips = (w + OUT - 1) / OUT, nsteps = (h + FI_TH - 1) / FI_TH;
+    // Row segments per strip: one 1024-thread workgroup per CU is resident, so the launch runs in rounds of (CU count)
+    // workgroups; a segment pays NCH = 7 chunks of M for its window's warm-up.  Take the split (1 .. 4) with the least
+    // (rounds x (steps + warm-up)) — 128 pairs x 12 strips of 1080p: 2 segments = 12.0 rounds of 108 + 7 steps.
+    int best_seg = 1;
+    double best_cost = 1e300;
+    for (int sg = 1; sg <= e->fi_maxseg; sg++) {
+        const int nt = (nsteps + sg - 1) / sg;
+        if (sg > 1 && nt < e->fi_minsteps) break;
+        const long long wgs = (long long)nstrips * sg * npairs;
+        const long long rounds = (wgs + slots - 1) / slots;
+        const double cost = (double)rounds * (nt + 7 * 0.25);  // a warm-up chunk is a quarter of a step (phase C only)
+        if (cost < best_cost) {
+            best_cost = cost;
+            best_seg = sg;
+        }
+    }
+    FlowIterPlan fp;
+    fp.strips = nstrips;
+    fp.nt = (nsteps + best_seg - 1) / best_seg;
+    fp.segments = (nsteps + fp.nt - 1) / fp.nt;
+    fp.nt_last = nsteps - (fp.segments - 1) * fp.nt;
+    return fp;
+}
 void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long long ps, const float* R, const float* flow_in,
                       long long fps_in, float* flow_out, long long fps_out, const FlowUps* ups, int npairs, int level)
 {
@@ -1340,28 +1373,9 @@ void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long l
     a.dbg_skip = e->fi_skip;                     // TW_FI_SKIP (timing experiments; read once in tw_engine_create)
     a.dbg = (unsigned long long*)e->dbg_stamps;  // TW_DEBUG_STAMPS=1
 #endif
-    const int OUT = (e->fi_nt == 512 ? FI_SC_512 : FI_SC) - 30;
-    const int slots = e->cu_count * (e->fi_nt == 512 ? 2 : 1);  // workgroups resident at once
-    const int nstrips = (w + OUT - 1) / OUT, nsteps = (h + FI_TH - 1) / FI_TH;
-    // Row segments per strip: one 1024-thread workgroup per CU is resident, so the launch runs in rounds of (CU count)
-    // workgroups; a segment pays NCH = 7 chunks of M for its window's warm-up.  Take the split (1 .. 4) with the least
-    // (rounds x (steps + warm-up)) — 128 pairs x 12 strips of 1080p: 2 segments = 12.0 rounds of 108 + 7 steps.
-    int best_seg = 1;
-    double best_cost = 1e300;
-    for (int sg = 1; sg <= e->fi_maxseg; sg++) {
-        const int nt = (nsteps + sg - 1) / sg;
-        if (sg > 1 && nt < e->fi_minsteps) break;
-        const long long wgs = (long long)nstrips * sg * npairs;
-        const long long rounds = (wgs + slots - 1) / slots;
-        const double cost = (double)rounds * (nt + 7 * 0.25);  // a warm-up chunk is a quarter of a step (phase C only)
-        if (cost < best_cost) {
-            best_cost = cost;
-            best_seg = sg;
-        }
-    }
-    a.nt = (nsteps + best_seg - 1) / best_seg;
-    const int nseg = (nsteps + a.nt - 1) / a.nt;
-    const dim3 grid(nstrips, nseg, npairs);
+    const FlowIterPlan fp = flow_iter_plan(e, w, h, npairs);
+    a.nt = fp.nt;
+    const dim3 grid(fp.strips, fp.segments, npairs);
     ProfScope pscope(e, st, TW_K_BLUR_SOLVE, level);
     if (ups) {
         a.prev = ups->prev;
@@ -3687,6 +3701,17 @@ extern "C" tw_status tw_debug_check_size(int width, int height)
 {
     const char* why = "";
     return size_status(width, height, &why);
+}
+
+extern "C" int tw_debug_flow_iter_plan(const tw_engine* e, int width, int height, int npairs, int* out, int n)
+{
+    if (!e) return -1;
+    if (!out || width < 1 || height < 1 || npairs < 1) return 0;
+    const FlowIterPlan fp = flow_iter_plan(e, width, height, npairs);
+    const int v[4] = {fp.strips, fp.segments, fp.nt, fp.nt_last};
+    int i = 0;
+    for (; i < n && i < 4; i++) out[i] = v[i];
+    return i;
 }
 
 extern "C" int tw_debug_launch_counts(tw_engine* e, unsigned long long* counts, unsigned long long* last_z, int n, int reset)

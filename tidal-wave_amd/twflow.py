@@ -8,6 +8,7 @@ Names follow the reference: `Engine.calculate_internal` is OpticalFlow::calculat
 Consumer::run (/root/reference/src/consumer.cpp:54-84) and returns the fields of `Response`
 (/root/reference/src/message_queue.h:27-42).
 """
+import collections
 import ctypes as C
 import os
 
@@ -70,7 +71,7 @@ SYMBOLS = [
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
-    "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size",
+    "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
 ]
 
 
@@ -195,7 +196,12 @@ def _bind(path):
     L.tw_debug_memory.restype = C.c_int
     L.tw_debug_check_size.argtypes = [C.c_int, C.c_int]
     L.tw_debug_check_size.restype = C.c_int
+    L.tw_debug_flow_iter_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int]
+    L.tw_debug_flow_iter_plan.restype = C.c_int
     return L
+
+
+FlowIterPlan = collections.namedtuple("FlowIterPlan", "strips segments nt nt_last")
 
 
 class LaunchCounts(dict):
@@ -569,6 +575,16 @@ class Engine:
     def level_runs_flow_iter(self, w, h, level, npairs):
         """Does `level` of a batch of npairs pairs run tw_flow_iter (the schedule's own predicate)?"""
         return self._L.tw_level_runs_flow_iter(self._h, w, h, level, npairs) == 1
+
+    def flow_iter_plan(self, w, h, npairs=1):
+        """Geometry of a tw_flow_iter launch of npairs pairs at a level of w x h pixels, from the function the launch
+        itself uses (twflow_debug.h: tw_debug_flow_iter_plan): strips, segments per strip, steps of 5 rows per segment,
+        steps of the last segment."""
+        v = (C.c_int * 4)()
+        n = self._L.tw_debug_flow_iter_plan(self._h, w, h, npairs, v, 4)
+        if n != 4:
+            raise TwError(TW_E_BAD_PARAMETER, "tw_debug_flow_iter_plan(%d, %d, %d) returned %d" % (w, h, npairs, n))
+        return FlowIterPlan(*v)
 
     def launch_counts(self, reset=False):
         """{family name: launches} since creation / the last reset, every family (twflow_debug.h)."""
