@@ -83,6 +83,18 @@ int tw_debug_launch_counts(tw_engine* e, unsigned long long* counts, unsigned lo
  * non-positive size), -1 for a null engine.  tests/test_gpu_flow_iter_geometry.py proves from it which geometry ran. */
 int tw_debug_flow_iter_plan(const tw_engine* e, int width, int height, int npairs, int* out, int n);
 
+/* The choice of one window average + solve launch of npairs pairs at a level of width x height pixels, from the one function
+ * the launch itself takes its kernel and grid from (choose_blur): out[0] the kernel's family (tw_debug_family), out[1] threads
+ * per workgroup, out[2] tile columns, out[3] rows per workgroup, out[4] xsh (pixels the tile grid starts left of the image),
+ * out[5] grid x, out[6] grid y, out[7] the 31-tap window's small-grid class (0: 224 x 8 / 96 x 8 tiles, 1: 96 x 8 two-wave tiles
+ * on a wide level, 2: 96 x 4, 3: 32 x 4, 4: plane-parallel 32 x 8, 5: plane-parallel 96 x 8), out[8] 1 when TW_BLUR_SMALL /
+ * TW_BLUR_SMALL_LEVELS set that class, 0 when the grid's size did.  `level` is the pyramid level (-1: a tw_stage_* call),
+ * `update` whether the launch refreshes M, `quads` whether the caller is the single-pair schedule.  A launch that carries a
+ * side job (TW_DF_TWIN) keeps this geometry for its own part.  The box window reports tw_box_vscan's block, columns and grid.
+ * Returns the number of values written (at most min(n, 9); 0 for a null `out` or a non-positive size), -1 for a null engine.
+ * tests/test_gpu_blur_dispatch.py proves from it which side of each edge of the choice ran. */
+int tw_debug_blur_plan(const tw_engine* e, int width, int height, int level, int npairs, int update, int quads, int* out, int n);
+
 /* Name of a family ("tw_flow_iter", ...), NULL past the end. */
 const char* tw_debug_family_name(int family);
 

@@ -41,6 +41,8 @@ def test_abi_version_and_launch_families(twflow):
     assert all(names) and len(set(names)) == len(names)
     assert L.tw_debug_family_name(len(fams) - 1) is None and L.tw_debug_family_name(-1) is None
     assert L.tw_debug_launch_counts(None, None, None, 0, 0) == -1
+    # the window launches' choice (choose_blur) is exported next to them: a null engine is refused, not dereferenced
+    assert "tw_debug_blur_plan" in twflow.SYMBOLS and L.tw_debug_blur_plan(None, 64, 64, -1, 1, 0, 0, None, 0) == -1
 
 
 def test_size_predicate_matches_the_plane_addressing(twflow):

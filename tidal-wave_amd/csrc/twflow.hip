@@ -1320,6 +1320,37 @@ struct FlowUps {  // the coarser level's flow and the resize tables to this leve
     int xmax;
     float scale;
 };
+// the common block of UpdArgs (everything else zero) and, with `ups`, its upsample source
+template <typename A>
+void set_upsample(A& a, const FlowUps& u)  // UpdArgs and FlowIterArgs name these fields alike
+{
+    a.prev = u.prev;
+    a.pw = u.pw;
+    a.ph = u.ph;
+    a.pld = u.pld;
+    a.pfps = u.pfps;
+    a.xofs = u.xofs;
+    a.alpha = u.alpha;
+    a.yofs = u.yofs;
+    a.beta = u.beta;
+    a.xmax = u.xmax;
+    a.scale = u.scale;
+}
+UpdArgs upd_args(const float* R, float* flow, float* M, int w, int h, int ld, long long ps, const FlowUps* ups = nullptr)
+{
+    UpdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.R = R;
+    a.flow = flow;
+    a.M = M;
+    a.w = w;
+    a.h = h;
+    a.ld = ld;
+    a.ps = ps;
+    a.fps = ps;
+    if (ups) set_upsample(a, *ups);
+    return a;
+}
 // The geometry of one tw_flow_iter launch — the ONE place the strip / row-segment rule lives: launch_flow_iter takes its
 // grid (strips, segments, pairs) and the kernel's steps per segment from it, and tw_debug_flow_iter_plan shows it to the tests.
 struct FlowIterPlan {
@@ -1377,19 +1408,7 @@ void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long l
     a.nt = fp.nt;
     const dim3 grid(fp.strips, fp.segments, npairs);
     ProfScope pscope(e, st, TW_K_BLUR_SOLVE, level);
-    if (ups) {
-        a.prev = ups->prev;
-        a.pw = ups->pw;
-        a.ph = ups->ph;
-        a.pld = ups->pld;
-        a.pfps = ups->pfps;
-        a.xofs = ups->xofs;
-        a.alpha = ups->alpha;
-        a.yofs = ups->yofs;
-        a.beta = ups->beta;
-        a.xmax = ups->xmax;
-        a.scale = ups->scale;
-    }
+    if (ups) set_upsample(a, *ups);
 #ifdef TW_VARIANTS
     if (e->fi_nt == 512) {  // measured 23 % slower (profiles/r05_m_free.md): variants library only
         if (ups) TW_LAUNCH(e, TW_DF_FLOW_ITER_UPS, (tw_flow_iter<15, 1, 512>), grid, dim3(512), 0, st, a);
@@ -1407,30 +1426,197 @@ void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long l
     }
 }
 
+// ---- the window average + solve launches ------------------------------------------------------------------------------
+// One row per fixed-window kernel: what it is (kernel, counter family, block, the tile a workgroup owns) and when it runs.
+// choose_blur takes the first row whose predicate holds, the variants rows before the product rows.
+#ifndef TW_4Y_ILP  // (A/B builds: vertical / horizontal interleave and solve unroll of the 51-tap kernel)
+#define TW_4Y_ILP 2, 2, 2
+#endif
+struct BlurKernel {
+    void (*kern)(BlurArgs);
+    int family;      // TW_DF_*
+    int block;       // threads
+    int tw, th;      // tile columns, rows per workgroup
+    bool shift;      // the tile grid may start 16 px left of the image (tile_shift)
+    bool grid_out;   // stores the span-grid samples next to the flow when asked to (GridOut)
+    int twin;        // carries a side job as 1: tw_twin_s4_poly, 2: tw_twin_pp_poly (0: never)
+    // -- the predicate: every field that is not "any" must hold
+    int m;           // winSize / 2
+    int wide;        // 1: w > 480, 0: narrower, -1: any
+    int small;       // the small-grid class (choose_blur), -1: any
+    bool quads;      // only when the caller asks for the quad kernel (the single-pair schedule)
+    int variant;     // TW_BLUR_VARIANT, 0: any
+    int pipe;        // TW_BLUR_PIPE on a refreshing launch, 0: any
+    int min_w;
+};
+constexpr int ANY = -1;
+const BlurKernel kBlurKernels[] = {
+    // small grids: 96 x 8 tiles of two waves, plane-parallel 32 x 8 tiles of five waves
+    {tw_blur_solve4<15, 128, 16, 8, true>, TW_DF_BLUR_SOLVE4, 128, 96, 8, true, true, 1, 15, ANY, 1, false, 0, 0, 0},
+    {tw_blur_solve_pp<15, 64, 16, 8>, TW_DF_BLUR_PP, 320, 32, 8, true, false, 2, 15, ANY, 4, false, 0, 0, 0},
+    // quads (the single-pair schedule): the launch is bound by its workgroups' serial chain, not by throughput — the kernel
+    // that solves and refreshes in the horizontal item's owner (two barriers and an LDS round trip fewer) is 6 % shorter there
+    {tw_blur_solve4q<15, 256, 16, 8, true>, TW_DF_BLUR_SOLVE4Q, 256, 224, 8, true, true, 0, 15, 1, 0, true, 0, 0, 0},
+    // 224-column tiles; narrow levels use 96-column tiles (less edge waste)
+    {tw_blur_solve4<15, 256, 16, 8, true>, TW_DF_BLUR_SOLVE4, 256, 224, 8, true, true, 0, 15, 1, 0, false, 0, 0, 0},
+    {tw_blur_solve4<15, 128, 16, 8, true>, TW_DF_BLUR_SOLVE4, 128, 96, 8, true, true, 0, 15, 0, 0, false, 0, 0, 0},
+    // winSize 50/51 (BASELINE config 5).  Wide levels: two vertically adjacent 8-row sub-tiles share one 66-row register window
+    // (round 3: -7 % against the one-sub-tile kernel with its 58-row window per 8 rows, which TW_BLUR_VARIANT=41 selects);
+    // narrow levels: packed-f32 structure, single 58-row register window
+    {tw_blur_solve4y<25, 256, 32, 8, 2, TW_4Y_ILP>, TW_DF_BLUR_SOLVE4Y, 256, 192, 16, false, false, 0, 25, 1, ANY, false, 0, 0, 0},
+    {tw_blur_solve8<25, 128, 32, 8, true, false>, TW_DF_BLUR_SOLVE8, 128, 64, 8, false, false, 0, 25, 0, ANY, false, 0, 0, 0},
+#ifdef TW_VARIANTS
+    // packed-f32 structure (same speed as v4 at 1080p, lower VALU load); TW_BLUR_VARIANT=8 for A/B
+    {tw_blur_solve8<15, 256, 16, 8, true, true>, TW_DF_BLUR_SOLVE8, 256, 224, 8, false, false, 0, 15, 1, ANY, false, 8, 0, 0},
+    {tw_blur_solve8<15, 128, 16, 8, true, true>, TW_DF_BLUR_SOLVE8, 128, 96, 8, false, false, 0, 15, 0, ANY, false, 8, 0, 0},
+    // small-grid classes 2 (96 x 4, 128 threads), 3 (32 x 4, 64 threads) and 5 (plane-parallel 96 x 8, 640 threads)
+    {tw_blur_solve4<15, 128, 16, 4, true>, TW_DF_BLUR_SOLVE4, 128, 96, 4, true, false, 0, 15, ANY, 2, false, 0, 0, 0},
+    {tw_blur_solve4<15, 64, 16, 4, true>, TW_DF_BLUR_SOLVE4, 64, 32, 4, true, false, 0, 15, ANY, 3, false, 0, 0, 0},
+    {tw_blur_solve_pp<15, 128, 16, 8>, TW_DF_BLUR_PP, 640, 96, 8, true, false, 0, 15, ANY, 5, false, 0, 0, 0},
+    // plane pipeline through a two-plane LDS ring (tw_blur_solve6), A/B
+    {tw_blur_solve6<15, 256, 16, 8, 5>, TW_DF_BLUR_VARIANT, 256, 224, 8, true, false, 0, 15, 1, 0, false, 60, 0, 0},
+    {tw_blur_solve6<15, 256, 16, 8, 4>, TW_DF_BLUR_VARIANT, 256, 224, 8, true, false, 0, 15, 1, 0, false, 61, 0, 0},
+    // 480-column tiles (512 threads, 80 KB LDS, two workgroups per CU): 93.75 % of the columns of the vertical pass and of
+    // the lanes of the horizontal pass are useful (87.5 % with 224-column tiles), and 1920 / 960 / 3840-pixel rows are
+    // covered exactly (nine 224-column tiles cover 2016)
+    {tw_blur_solve4<15, 512, 16, 8, true>, TW_DF_BLUR_SOLVE4, 512, 480, 8, true, false, 0, 15, 1, 0, false, 5, 0, 960},
+    // round 4: solve + refresh by the horizontal item's owner, 16-byte R0 / M accesses
+    {tw_blur_solve4q<15, 256, 16, 8, true>, TW_DF_BLUR_VARIANT, 256, 224, 8, true, false, 0, 15, 1, 0, false, 9, 0, 0},
+    {tw_blur_solve4q<15, 128, 16, 8, true>, TW_DF_BLUR_VARIANT, 128, 96, 8, true, false, 0, 15, 0, 0, false, 9, 0, 0},
+    {tw_blur_solve4y<15, 256, 16, 8, 2>, TW_DF_BLUR_SOLVE4Y, 256, 224, 16, true, false, 0, 15, 1, 0, false, 2, 0, 0},
+    {tw_blur_solve4<15, 256, 16, 8, true, 2, 2, 2, true, false>, TW_DF_BLUR_SOLVE4, 256, 224, 8, true, false, 0, 15, 1, 0, false, 7, 0, 0},
+    {tw_blur_solve4<15, 256, 16, 8, true, 2, 2, 2, false>, TW_DF_BLUR_SOLVE4, 256, 224, 8, true, false, 0, 15, 1, 0, false, 6, 0, 0},
+    // refreshing launch as a cross-tile pipeline: a workgroup walks TW_BLUR_PIPE vertically adjacent tiles (109: 9 tiles, WPE 3)
+    {tw_blur_solve4p<15, 256, 16, 8, 3>, TW_DF_BLUR_VARIANT, 256, 224, 8 * 3, true, false, 0, 15, 1, 0, false, 0, 3, 0},
+    {tw_blur_solve4p<15, 256, 16, 8, 5>, TW_DF_BLUR_VARIANT, 256, 224, 8 * 5, true, false, 0, 15, 1, 0, false, 0, 5, 0},
+    {tw_blur_solve4p<15, 256, 16, 8, 9>, TW_DF_BLUR_VARIANT, 256, 224, 8 * 9, true, false, 0, 15, 1, 0, false, 0, 9, 0},
+    {tw_blur_solve4p<15, 256, 16, 8, 15>, TW_DF_BLUR_VARIANT, 256, 224, 8 * 15, true, false, 0, 15, 1, 0, false, 0, 15, 0},
+    {tw_blur_solve4p<15, 256, 16, 8, 9, 3>, TW_DF_BLUR_VARIANT, 256, 224, 8 * 9, true, false, 0, 15, 1, 0, false, 0, 109, 0},
+    // winSize 50/51: the packed-f32 kernel on wide levels too, and round 3's trials for config 5: shorter
+    // tiles make room for the R0 prefetch (QPRE)
+    {tw_blur_solve8<25, 256, 32, 8, true, false>, TW_DF_BLUR_SOLVE8, 256, 192, 8, false, false, 0, 25, 1, ANY, false, 8, 0, 0},
+    {tw_blur_solve4<25, 256, 32, 6, true, 2, 2, 2, true, false>, TW_DF_BLUR_SOLVE4, 256, 192, 6, false, false, 0, 25, 1, ANY, false, 256, 0, 0},
+    {tw_blur_solve4<25, 256, 32, 5, true, 2, 2, 2, true, false>, TW_DF_BLUR_SOLVE4, 256, 192, 5, false, false, 0, 25, 1, ANY, false, 255, 0, 0},
+    {tw_blur_solve4<25, 256, 32, 4, true, 2, 2, 2, true, false>, TW_DF_BLUR_SOLVE4, 256, 192, 4, false, false, 0, 25, 1, ANY, false, 254, 0, 0},
+    {tw_blur_solve4<25, 256, 32, 8, true, 2, 2, 2, true, false>, TW_DF_BLUR_SOLVE4, 256, 192, 8, false, false, 0, 25, 1, ANY, false, 258, 0, 0},
+    {tw_blur_solve4<25, 256, 32, 8, true, 2, 2, 2, false, false>, TW_DF_BLUR_SOLVE4, 256, 192, 8, false, false, 0, 25, 1, ANY, false, 41, 0, 0},
+    {tw_blur_solve4<25, 256, 32, 5, true, 2, 2, 2, false, false>, TW_DF_BLUR_SOLVE4, 256, 192, 5, false, false, 0, 25, 1, ANY, false, 259, 0, 0},
+#endif
+};
+constexpr int kBlurKernelRows = (int)(sizeof(kBlurKernels) / sizeof(kBlurKernels[0])), kProductBlurRows = 7;
+static_assert(kBlurKernelRows >= kProductBlurRows, "the product rows come first");
+// ... and the two window launches that are no table kernel: any other window size (same arithmetic, runtime loops, dynamic
+// LDS) and the box window (launch_box_window; block / tile of tw_box_vscan)
+const BlurKernel kGenericWindow = {tw_blur_solve_generic, TW_DF_BLUR_GENERIC, 256, 64, BS_TH, false, false, 0, ANY, ANY, ANY, false, 0, 0, 0};
+const BlurKernel kBoxWindow = {nullptr, TW_DF_BOX, 64, 64, 1, false, false, 0, ANY, ANY, ANY, false, 0, 0, 0};
+
+// shift the tile grid 16 px left when that costs no extra tile column (see tw_blur_solve4)
+int tile_shift(int w, int tw) { return ((w + 16 + tw - 1) / tw == (w + tw - 1) / tw) ? 16 : 0; }
+
+// The choice of one window launch — the ONE place it is made: launch_blur launches it, plan_twin_side_jobs asks it which
+// tiles level 1 takes, and tw_debug_blur_plan shows it to the tests.
+struct BlurChoice {
+    const BlurKernel* k;  // a row of kBlurKernels, kGenericWindow or kBoxWindow
+    int xsh;
+    dim3 grid;            // (box window: of tw_box_vscan)
+    size_t lds;           // dynamic LDS bytes (the generic kernel)
+    int small;            // 31-tap window: 0: 224x8 / 96x8 tiles, 1: 96x8 (128 threads), 2: 96x4 (128 threads), 3: 32x4 (64 threads),
+                          // 4: plane-parallel 32x8 (320 threads), 5: plane-parallel 96x8 (640 threads)
+    bool forced;          // ... set by TW_BLUR_SMALL_LEVELS / TW_BLUR_SMALL, not by the grid's size
+};
+BlurChoice choose_blur(const tw_engine* e, int w, int h, int npairs, int level, bool update, bool quads)
+{
+    BlurChoice c{&kGenericWindow, 0, dim3(), 0, 0, false};
+    if (e->box) {
+        c.k = &kBoxWindow;
+        c.grid = dim3((w + 63) / 64, 5, npairs);
+        return c;
+    }
+    const bool wide = w > 480;
+    if (e->win_m == 15) {
+        // Small grids (a single pair, the coarse levels): a level that would launch fewer than two workgroups per
+        // CU takes smaller tiles, so that more CUs share it and each workgroup's serial V -> H -> S chain is shorter
+        // (BASELINE config 2, single-pair latency).  Batched launches always have enough tiles and keep the big ones.
+        auto nwg = [&](int tw, int th) { return (long long)((w + tw - 1) / tw) * ((h + th - 1) / th) * npairs; };
+        c.forced = true;
+        if (level >= 0 && level < 8 && e->blur_small_lv[level] >= 0) c.small = e->blur_small_lv[level];
+        else if (e->blur_small >= 0) c.small = e->blur_small;
+        else {
+            c.forced = false;
+            if (wide && nwg(224, 8) >= 1024) c.small = 0;  // four 256-thread workgroups per CU: throughput regime
+            else if (nwg(96, 8) * 2 >= e->pp_waves) c.small = wide ? 1 : 0;  // enough 2-wave workgroups to keep every SIMD busy
+            else c.small = 4;  // otherwise many small plane-parallel workgroups (5 waves per 32x8 pixels)
+        }
+        if (c.small > 5) c.small = 4;
+    }
+    for (int i = 0; i < kBlurKernelRows; i++) {
+        const BlurKernel& r = kBlurKernels[(kProductBlurRows + i) % kBlurKernelRows];  // the variants rows first
+        if (r.m == e->win_m && (r.wide == ANY || r.wide == (int)wide) && (r.small == ANY || r.small == c.small) && (!r.quads || quads) &&
+            (!r.variant || r.variant == e->blur_variant) && (!r.pipe || (update && r.pipe == e->blur_pipe)) && w >= r.min_w) {
+            c.k = &r;
+            break;
+        }
+    }
+    if (c.k->shift) c.xsh = tile_shift(w, c.k->tw);
+    c.grid = dim3((w + c.xsh + c.k->tw - 1) / c.k->tw, (h + c.k->th - 1) / c.k->th, npairs);
+    if (c.k == &kGenericWindow) c.lds = (size_t)5 * BS_TH * (64 + 2 * e->win_m) * 4;
+    return c;
+}
+
 // span-grid samples a tw_blur_solve4 launch stores next to the flow (the single-pair schedule's last level-0 launch)
 struct GridOut {
     float2* g;
     int span, gw, gh;
     bool* used;  // set if the launch took a kernel that stores them (the caller launches tw_span_gather otherwise)
 };
-void launch_blur(tw_engine* e, hipStream_t st, int w, int h, int ld, long long ps, const float* Min, float* Mout,
-                 float* flow, const float* R, int update, int level, int npairs, double* Vbox = nullptr,
-                 const SideJob* side = nullptr, bool* side_used = nullptr, const GridOut* go = nullptr, bool quads = false)
+// one window launch: the level's buffers and geometry, and what only some callers have
+struct BlurLaunch {
+    int w, h, ld;
+    long long ps;
+    const float* Min;
+    float* Mout;
+    float* flow;
+    const float* R;
+    int update;               // refresh M for the next iteration
+    int level;                // (ProfScope, TW_BLUR_SMALL_LEVELS; -1: a per-stage entry point)
+    int npairs;
+    int store_flow = 0;       // store the flow of a refreshing launch too
+    double* Vbox = nullptr;   // box window: the column sums' workspace, [5 ps npairs] (null: the engine's)
+    const SideJob* side = nullptr;  // the twin schedule: a side job this launch may carry, *side_used set if it did
+    bool* side_used = nullptr;
+    const GridOut* go = nullptr;
+    bool quads = false;
+};
+// box window: sequential double running sums (two scan kernels) + the standard refresh kernel
+void launch_box_window(tw_engine* e, hipStream_t st, const BlurLaunch& in)
+{
+    double* V = in.Vbox ? in.Vbox : e->Vd;  // TW_LANES=2: each lane (stream) has its own column sums
+    const BoxArgs b{in.Min, V, in.flow, in.w, in.h, in.ld, in.ps, in.ps, e->win_m, 1. / ((double)e->p.winSize * e->p.winSize)};
+    {
+        ProfScope pscope(e, st, TW_K_BLUR_SOLVE, in.level);
+        TW_LAUNCH(e, TW_DF_BOX, tw_box_vscan, dim3((in.w + 63) / 64, 5, in.npairs), dim3(64), 0, st, b);
+        TW_LAUNCH(e, TW_DF_BOX, tw_box_hscan_solve, dim3((in.h + 11) / 12, 1, in.npairs), dim3(64), 0, st, b);
+    }
+    if (in.update) {
+        const UpdArgs u = upd_args(in.R, in.flow, in.Mout, in.w, in.h, in.ld, in.ps);
+        ProfScope pscope(e, st, TW_K_UPDATE_MATRICES, in.level);
+        launch_upd_kernel<false>(e, st, in.w, in.h, in.npairs, u);
+    }
+}
+void launch_blur(tw_engine* e, hipStream_t st, const BlurLaunch& in)
 {
     BlurArgs a;
-    a.Min = Min;
-    a.Mout = Mout;
-    a.flow = flow;
-    a.R = R;
-    a.w = w;
-    a.h = h;
-    a.ld = ld;
-    a.ps = ps;
-    a.fps = ps;
-    a.update = update;
-    a.xsh = 0;
-    a.rot = 0;
-    a.store_flow = level < 0 ? 1 : 0;  // level -1: the per-stage test entry point, which returns the flow as well
+    a.Min = in.Min;
+    a.Mout = in.Mout;
+    a.flow = in.flow;
+    a.R = in.R;
+    a.w = in.w;
+    a.h = in.h;
+    a.ld = in.ld;
+    a.ps = in.ps;
+    a.fps = in.ps;
+    a.update = in.update;
+    a.store_flow = in.store_flow;
     a.m = e->win_m;
     a.nomask = e->blur_nomask;
     a.cm = e->blur_cm;
@@ -1438,188 +1624,27 @@ void launch_blur(tw_engine* e, hipStream_t st, int w, int h, int ld, long long p
     a.gspan = a.gw = a.gh = 0;
     a.gmagic = 0;
     a.c = e->wc;
-    // tw_blur_solve4<15, ...> stores the span-grid samples next to the flow when asked to (GridOut)
-    auto set_grid_out = [&]() {
-        if (go && go->span > 1 && w < 65536 && h < 65536) {
-            a.grid = go->g;
-            a.gspan = go->span;
-            a.gw = go->gw;
-            a.gh = go->gh;
-            a.gmagic = (unsigned)((0x100000000ull + (unsigned)go->span - 1) / (unsigned)go->span);
-            *go->used = true;
-        }
-    };
-    const int gy = (h + BS_TH - 1) / BS_TH;
-    const bool wide = w > 480;  // 224-column tiles; narrow levels use 96-column tiles (less edge waste)
-    if (e->box) {
-        // box window: sequential double running sums (two scan kernels) + the standard refresh kernel
-        double* V = Vbox ? Vbox : e->Vd;  // TW_LANES=2: each lane (stream) has its own column sums
-        Tmp tmp;
-        if (level < 0) {  // per-stage test entry: no engine workspace
-            V = tmp.alloc<double>((size_t)ps * 5 * npairs);
-            if (!V) return;
-        }
-        BoxArgs b;
-        b.Min = Min;
-        b.V = V;
-        b.flow = flow;
-        b.w = w;
-        b.h = h;
-        b.ld = ld;
-        b.ps = ps;
-        b.fps = ps;
-        b.m = e->win_m;
-        b.scale = 1. / ((double)e->p.winSize * e->p.winSize);
-        {
-            ProfScope pscope(e, st, TW_K_BLUR_SOLVE, level);
-            TW_LAUNCH(e, TW_DF_BOX, tw_box_vscan, dim3((w + 63) / 64, 5, npairs), dim3(64), 0, st, b);
-            TW_LAUNCH(e, TW_DF_BOX, tw_box_hscan_solve, dim3((h + 11) / 12, 1, npairs), dim3(64), 0, st, b);
-        }
-        if (update) {
-            UpdArgs u;
-            memset(&u, 0, sizeof(u));
-            u.R = R;
-            u.flow = flow;
-            u.M = Mout;
-            u.w = w;
-            u.h = h;
-            u.ld = ld;
-            u.ps = ps;
-            u.fps = ps;
-            ProfScope pscope(e, st, TW_K_UPDATE_MATRICES, level);
-            launch_upd_kernel<false>(e, st, w, h, npairs, u);
-        }
-        if (level < 0) (void)hipStreamSynchronize(st);  // tmp is freed on return
-        return;
+    const BlurChoice c = choose_blur(e, in.w, in.h, in.npairs, in.level, in.update != 0, in.quads);
+    if (c.k == &kBoxWindow) return launch_box_window(e, st, in);
+    a.xsh = a.rot = c.xsh;
+    if (c.k->grid_out && in.go && in.go->span > 1 && in.w < 65536 && in.h < 65536) {
+        a.grid = in.go->g;
+        a.gspan = in.go->span;
+        a.gw = in.go->gw;
+        a.gh = in.go->gh;
+        a.gmagic = (unsigned)((0x100000000ull + (unsigned)in.go->span - 1) / (unsigned)in.go->span);
+        *in.go->used = true;
     }
-    ProfScope pscope(e, st, TW_K_BLUR_SOLVE, level);
-#ifdef TW_VARIANTS
-    if (e->win_m == 15 && e->blur_variant == 8) {
-        // packed-f32 structure (same speed as v4 at 1080p, lower VALU load); TW_BLUR_VARIANT=8 for A/B
-        if (wide) TW_LAUNCH(e, TW_DF_BLUR_SOLVE8, (tw_blur_solve8<15, 256, 16, 8, true, true>), dim3((w + 223) / 224, gy, npairs), dim3(256), 0, st, a);
-        else TW_LAUNCH(e, TW_DF_BLUR_SOLVE8, (tw_blur_solve8<15, 128, 16, 8, true, true>), dim3((w + 95) / 96, gy, npairs), dim3(128), 0, st, a);
-        return;
-    }
-#endif
-    if (e->win_m == 15) {
-        // Small grids (a single pair, the coarse levels): a level that would launch fewer than two workgroups per
-        // CU takes smaller tiles, so that more CUs share it and each workgroup's serial V -> H -> S chain is shorter
-        // (BASELINE config 2, single-pair latency).  Batched launches always have enough tiles and keep the big ones.
-        auto nwg = [&](int tw, int th) { return (long long)((w + tw - 1) / tw) * ((h + th - 1) / th) * npairs; };
-        int small = 0;  // 0: 224x8 / 96x8 tiles as below, 1: 96x8 (128 threads), 2: 96x4 (128 threads), 3: 32x4 (64 threads)
-                        // 4: plane-parallel 32x8 (320 threads), 5: plane-parallel 96x8 (640 threads)
-        if (level >= 0 && level < 8 && e->blur_small_lv[level] >= 0) small = e->blur_small_lv[level];
-        else if (e->blur_small >= 0) small = e->blur_small;
-        else if (wide && nwg(224, 8) >= 1024) small = 0;   // four 256-thread workgroups per CU: throughput regime
-        else if (nwg(96, 8) * 2 >= e->pp_waves) small = wide ? 1 : 0;  // enough 2-wave workgroups to keep every SIMD busy
-        else small = 4;  // otherwise many small plane-parallel workgroups (5 waves per 32x8 pixels)
-        if (small) {
-            const int tw = (small == 3 || small == 4) ? 32 : 96, th = (small == 2 || small == 3) ? 4 : 8;
-            a.xsh = ((w + 16 + tw - 1) / tw == (w + tw - 1) / tw) ? 16 : 0;
-            a.rot = a.xsh;
-            const dim3 grid((w + a.xsh + tw - 1) / tw, (h + th - 1) / th, npairs);
-            if (small == 1) {
-                set_grid_out();
-                if (side && side_used && side->kind == 1) {
-                    // (round 6) two-wave workgroups that leave most of the chip idle: a band of a finer level's expansion rides along
-                    const TwinGrid t = make_twin(grid, *side);
-                    TW_LAUNCH(e, TW_DF_TWIN, tw_twin_s4_poly, dim3(t.nA8 + side->n()), dim3(256), 0, st, a, side->pa, t);
-                    *side_used = true;
-                } else {
-                    TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<15, 128, 16, 8, true>), grid, dim3(128), 0, st, a);
-                }
-            }
-#ifdef TW_VARIANTS
-            else if (small == 2) TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<15, 128, 16, 4, true>), grid, dim3(128), 0, st, a);
-            else if (small == 3) TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<15, 64, 16, 4, true>), grid, dim3(64), 0, st, a);
-            else if (small == 5) TW_LAUNCH(e, TW_DF_BLUR_PP, (tw_blur_solve_pp<15, 128, 16, 8>), grid, dim3(640), 0, st, a);
-#endif
-            else if (side && side_used && side->kind == 1) {
-                const TwinGrid t = make_twin(grid, *side);
-                TW_LAUNCH(e, TW_DF_TWIN, tw_twin_pp_poly, dim3(t.nA8 + side->n()), dim3(320), 0, st, a, side->pa, t);
-                *side_used = true;
-            }
-            else TW_LAUNCH(e, TW_DF_BLUR_PP, (tw_blur_solve_pp<15, 64, 16, 8>), grid, dim3(320), 0, st, a);
-            return;
-        }
-#ifdef TW_VARIANTS
-        if (wide && (e->blur_variant == 60 || e->blur_variant == 61)) {
-            // plane pipeline through a two-plane LDS ring (tw_blur_solve6), A/B
-            a.xsh = ((w + 16 + 223) / 224 == (w + 223) / 224) ? 16 : 0;
-            a.rot = a.xsh;
-            const dim3 grid((w + a.xsh + 223) / 224, gy, npairs);
-            if (e->blur_variant == 60) TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve6<15, 256, 16, 8, 5>), grid, dim3(256), 0, st, a);
-            else TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve6<15, 256, 16, 8, 4>), grid, dim3(256), 0, st, a);
-            return;
-        }
-        if (wide && e->blur_variant == 5 && w >= 960) {
-            // 480-column tiles (512 threads, 80 KB LDS, two workgroups per CU): 93.75 % of the columns of the vertical
-            // pass and of the lanes of the horizontal pass are useful (87.5 % with 224-column tiles), and 1920 / 960 /
-            // 3840-pixel rows are covered exactly (nine 224-column tiles cover 2016)
-            a.xsh = ((w + 16 + 479) / 480 == (w + 479) / 480) ? 16 : 0;
-            a.rot = a.xsh;
-            TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<15, 512, 16, 8, true>), dim3((w + a.xsh + 479) / 480, gy, npairs), dim3(512), 0, st, a);
-            return;
-        }
-#endif
-        // shift the tile grid 16 px left when that costs no extra tile column (see the kernel)
-        const int tw = wide ? 224 : 96;
-        a.xsh = ((w + 16 + tw - 1) / tw == (w + tw - 1) / tw) ? 16 : 0;
-        a.rot = a.xsh;
-#ifdef TW_VARIANTS
-        if (e->blur_variant == 9) {  // round 4: solve + refresh by the horizontal item's owner, 16-byte R0 / M accesses
-            if (wide) TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve4q<15, 256, 16, 8, true>), dim3((w + a.xsh + 223) / 224, gy, npairs), dim3(256), 0, st, a);
-            else TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve4q<15, 128, 16, 8, true>), dim3((w + a.xsh + 95) / 96, gy, npairs), dim3(128), 0, st, a);
-            return;
-        }
-        if (wide && e->blur_variant == 2) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4Y, (tw_blur_solve4y<15, 256, 16, 8, 2>), dim3((w + a.xsh + 223) / 224, (h + 15) / 16, npairs), dim3(256), 0, st, a); return; }
-        if (wide && e->blur_variant == 7) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<15, 256, 16, 8, true, 2, 2, 2, true, false>), dim3((w + a.xsh + 223) / 224, gy, npairs), dim3(256), 0, st, a); return; }
-        if (wide && e->blur_variant == 6) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<15, 256, 16, 8, true, 2, 2, 2, false>), dim3((w + a.xsh + 223) / 224, gy, npairs), dim3(256), 0, st, a); return; }
-#endif
-#ifdef TW_VARIANTS
-        if (wide && update && e->blur_pipe > 0) {
-            // refreshing launch as a cross-tile pipeline: a workgroup walks blur_pipe vertically adjacent tiles
-            const int nt = e->blur_pipe;
-            const dim3 grid((w + a.xsh + 223) / 224, (gy + nt - 1) / nt, npairs);
-            switch (nt) {
-                case 3: TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve4p<15, 256, 16, 8, 3>), grid, dim3(256), 0, st, a); return;
-                case 5: TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve4p<15, 256, 16, 8, 5>), grid, dim3(256), 0, st, a); return;
-                case 9: TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve4p<15, 256, 16, 8, 9>), grid, dim3(256), 0, st, a); return;
-                case 15: TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve4p<15, 256, 16, 8, 15>), grid, dim3(256), 0, st, a); return;
-                case 109: TW_LAUNCH(e, TW_DF_BLUR_VARIANT, (tw_blur_solve4p<15, 256, 16, 8, 9, 3>), dim3(grid.x, (gy + 8) / 9, npairs), dim3(256), 0, st, a); return;
-                default: break;
-            }
-        }
-#endif
-        set_grid_out();
-        // quads (the single-pair schedule): the launch is bound by its workgroups' serial chain, not by throughput — the kernel
-        // that solves and refreshes in the horizontal item's owner (two barriers and an LDS round trip fewer) is 6 % shorter there
-        if (wide && quads) TW_LAUNCH(e, TW_DF_BLUR_SOLVE4Q, (tw_blur_solve4q<15, 256, 16, 8, true>), dim3((w + a.xsh + 223) / 224, gy, npairs), dim3(256), 0, st, a);
-        else if (wide) TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<15, 256, 16, 8, true>), dim3((w + a.xsh + 223) / 224, gy, npairs), dim3(256), 0, st, a);
-        else TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<15, 128, 16, 8, true>), dim3((w + a.xsh + 95) / 96, gy, npairs), dim3(128), 0, st, a);
-    } else if (e->win_m == 25) {
-        // winSize 50/51 (BASELINE config 5): packed-f32 structure, single 58-row register window
-#ifdef TW_VARIANTS
-        if (wide && e->blur_variant == 8) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE8, (tw_blur_solve8<25, 256, 32, 8, true, false>), dim3((w + 191) / 192, gy, npairs), dim3(256), 0, st, a); return; }
-        // round 3 trials for config 5: shorter tiles make room for the R0 prefetch (QPRE)
-        if (wide && e->blur_variant == 256) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<25, 256, 32, 6, true, 2, 2, 2, true, false>), dim3((w + 191) / 192, (h + 5) / 6, npairs), dim3(256), 0, st, a); return; }
-        if (wide && e->blur_variant == 255) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<25, 256, 32, 5, true, 2, 2, 2, true, false>), dim3((w + 191) / 192, (h + 4) / 5, npairs), dim3(256), 0, st, a); return; }
-        if (wide && e->blur_variant == 254) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<25, 256, 32, 4, true, 2, 2, 2, true, false>), dim3((w + 191) / 192, (h + 3) / 4, npairs), dim3(256), 0, st, a); return; }
-        if (wide && e->blur_variant == 258) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<25, 256, 32, 8, true, 2, 2, 2, true, false>), dim3((w + 191) / 192, gy, npairs), dim3(256), 0, st, a); return; }
-        if (wide && e->blur_variant == 41) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<25, 256, 32, 8, true, 2, 2, 2, false, false>), dim3((w + 191) / 192, gy, npairs), dim3(256), 0, st, a); return; }
-        if (wide && e->blur_variant == 259) { TW_LAUNCH(e, TW_DF_BLUR_SOLVE4, (tw_blur_solve4<25, 256, 32, 5, true, 2, 2, 2, false, false>), dim3((w + 191) / 192, (h + 4) / 5, npairs), dim3(256), 0, st, a); return; }
-#endif
-        // wide levels: two vertically adjacent 8-row sub-tiles share one 66-row register window (round 3: -7 % against the
-        // one-sub-tile kernel with its 58-row window per 8 rows, which TW_BLUR_VARIANT=41 of the variants library selects)
-#ifndef TW_4Y_ILP  // (A/B builds: vertical / horizontal interleave and solve unroll of the 51-tap kernel)
-#define TW_4Y_ILP 2, 2, 2
-#endif
-        if (wide) TW_LAUNCH(e, TW_DF_BLUR_SOLVE4Y, (tw_blur_solve4y<25, 256, 32, 8, 2, TW_4Y_ILP>), dim3((w + 191) / 192, (h + 15) / 16, npairs), dim3(256), 0, st, a);
-        else TW_LAUNCH(e, TW_DF_BLUR_SOLVE8, (tw_blur_solve8<25, 128, 32, 8, true, false>), dim3((w + 63) / 64, gy, npairs), dim3(128), 0, st, a);
+    ProfScope pscope(e, st, TW_K_BLUR_SOLVE, in.level);
+    if (c.k->twin && in.side && in.side_used && in.side->kind == 1) {
+        // workgroups that leave most of the chip idle: a band of a finer level's expansion rides along
+        const TwinGrid t = make_twin(c.grid, *in.side);
+        if (c.k->twin == 1) TW_LAUNCH(e, TW_DF_TWIN, tw_twin_s4_poly, dim3(t.nA8 + in.side->n()), dim3(256), 0, st, a, in.side->pa, t);
+        else TW_LAUNCH(e, TW_DF_TWIN, tw_twin_pp_poly, dim3(t.nA8 + in.side->n()), dim3(320), 0, st, a, in.side->pa, t);
+        *in.side_used = true;
     } else {
-        // any other window size: generic kernel (same arithmetic, runtime loops)
-        const size_t lds = (size_t)5 * BS_TH * (64 + 2 * e->win_m) * 4;
-        TW_LAUNCH(e, TW_DF_BLUR_GENERIC, tw_blur_solve_generic, dim3((w + 63) / 64, gy, npairs), dim3(256), lds, st, a);
+        void (*const kern)(BlurArgs) = c.k->kern;
+        TW_LAUNCH(e, c.k->family, kern, c.grid, dim3(c.k->block), c.lds, st, a);
     }
 }
 
@@ -1629,31 +1654,16 @@ void launch_update(tw_engine* e, hipStream_t st, const Plan* pl, int k, const fl
                    bool init_flow = false)
 {
     const LevelPlan& L = pl->lv[k];
-    UpdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.R = R;
-    a.flow = flow;
-    a.M = M;
-    a.w = L.w;
-    a.h = L.h;
-    a.ld = L.ld;
-    a.ps = L.ps;
-    a.fps = L.ps;
+    const bool up = k < pl->levels;
+    FlowUps ups;
+    if (up) {
+        const LevelPlan& P = pl->lv[k + 1];
+        ups = FlowUps{prev, P.w, P.h, P.ld, P.ps, L.d_uxofs, L.d_uyofs, L.d_ualpha, L.d_ubeta, L.uxmax, (float)(1. / e->p.pyrScale)};
+    }
+    UpdArgs a = upd_args(R, flow, M, L.w, L.h, L.ld, L.ps, up ? &ups : nullptr);
     a.store_flow = e->p.pyrIterations == 0 ? 1 : 0;
     ProfScope pscope(e, st, TW_K_UPDATE_MATRICES, k);
-    if (k < pl->levels) {
-        const LevelPlan& P = pl->lv[k + 1];
-        a.prev = prev;
-        a.pw = P.w;
-        a.ph = P.h;
-        a.pld = P.ld;
-        a.pfps = P.ps;
-        a.xofs = L.d_uxofs;
-        a.alpha = L.d_ualpha;
-        a.yofs = L.d_uyofs;
-        a.beta = L.d_ubeta;
-        a.xmax = L.uxmax;
-        a.scale = (float)(1. / e->p.pyrScale);
+    if (up) {
         launch_upd_kernel<true>(e, st, L.w, L.h, npairs, a, side, side_used);
     } else {
         a.zero_flow = init_flow ? 0 : 1;
@@ -2284,9 +2294,8 @@ struct BatchEnqueue {
         // 1 (default, round 6): level 1's expansion in `it` bands on level 3's window launches, level 0's in `it` bands (of both
         // images) on LEVEL 1's window launches (tw_twin_s4_poly: 680 two-wave workgroups leave the chip three quarters idle);
         // levels 2's launches and level 1's update carry nothing (they fill the chip: a carried job costs 0.7 of itself there).
-        const bool l1_twin = pl->lv[1].w > 480 && (long long)((pl->lv[1].w + 95) / 96) * ((pl->lv[1].h + 7) / 8) * 2 >= e->pp_waves &&
-                             (long long)((pl->lv[1].w + 223) / 224) * ((pl->lv[1].h + 7) / 8) < 1024 && e->blur_small < 0 &&
-                             e->blur_small_lv[1] < 0;  // level 1 takes the 96 x 8 tiles (launch_blur)
+        const BlurChoice c1 = choose_blur(e, pl->lv[1].w, pl->lv[1].h, 1, 1, true, false);
+        const bool l1_twin = c1.small == 1 && !c1.forced;  // level 1 takes the 96 x 8 tiles by its size, not by a switch
         if (sw.lat_plan >= 1 && l1_twin && bands_env == 0) {
             push_side_bands(1, gy1, it, 3);
             push_side_bands(0, gy0, it, 1);  // (unequal bands, two of five bands on level 3's launches: all within the noise of this,
@@ -2416,18 +2425,26 @@ struct BatchEnqueue {
             const bool last = i == it - 1;
             if (ch.grid_only && last) {
                 enqueue_grid_tail(ch, Min);
-            } else if (k >= 1 && side_ok(k, true)) {
-                bool used = false;
-                launch_blur(e, ch.ls, L.w, L.h, L.ld, L.ps, Min, Mout, ch.flow_cur, ch.R, !last, k, nc, nullptr, side_peek(), &used);
-                side_done(used);
-            } else if (lat && k == 0 && last && c.span > 0) {
-                // the launch that stores the final flow stores its span-grid samples too: no tw_span_gather launch
-                GridOut go{grid_of(ch.j0), c.span, gw, gh, grid_stored};
-                launch_blur(e, ch.ls, L.w, L.h, L.ld, L.ps, Min, Mout, ch.flow_cur, ch.R, 0, k, nc, ch.Vbox, nullptr, nullptr, &go, lat_quads);
-            } else {
-                launch_blur(e, ch.ls, L.w, L.h, L.ld, L.ps, Min, Mout, ch.flow_cur, ch.R, !last, k, nc, ch.Vbox, nullptr, nullptr, nullptr,
-                            lat_quads);
+                continue;
             }
+            BlurLaunch b{L.w, L.h, L.ld, L.ps, Min, Mout, ch.flow_cur, ch.R, !last, k, nc};
+            if (k >= 1 && side_ok(k, true)) {
+                bool used = false;
+                b.side = side_peek();
+                b.side_used = &used;
+                launch_blur(e, ch.ls, b);
+                side_done(used);
+                continue;
+            }
+            b.Vbox = ch.Vbox;
+            b.quads = lat_quads;
+            GridOut go;
+            if (lat && k == 0 && last && c.span > 0) {
+                // the launch that stores the final flow stores its span-grid samples too: no tw_span_gather launch
+                go = GridOut{grid_of(ch.j0), c.span, gw, gh, grid_stored};
+                b.go = &go;
+            }
+            launch_blur(e, ch.ls, b);
         }
     }
 
@@ -3714,6 +3731,17 @@ extern "C" int tw_debug_flow_iter_plan(const tw_engine* e, int width, int height
     return i;
 }
 
+extern "C" int tw_debug_blur_plan(const tw_engine* e, int width, int height, int level, int npairs, int update, int quads, int* out, int n)
+{
+    if (!e) return -1;
+    if (!out || width < 1 || height < 1 || npairs < 1) return 0;
+    const BlurChoice c = choose_blur(e, width, height, npairs, level, update != 0, quads != 0);
+    const int v[9] = {c.k->family, c.k->block, c.k->tw, c.k->th, c.xsh, (int)c.grid.x, (int)c.grid.y, c.small, c.forced ? 1 : 0};
+    int i = 0;
+    for (; i < n && i < 9; i++) out[i] = v[i];
+    return i;
+}
+
 extern "C" int tw_debug_launch_counts(tw_engine* e, unsigned long long* counts, unsigned long long* last_z, int n, int reset)
 {
     if (!e) return -1;
@@ -3950,8 +3978,8 @@ extern "C" tw_status tw_bench_stage(tw_engine* e, int kclass, int width, int hei
                                      npairs, level);
                     break;
                 }
-                launch_blur(e, st, L.w, L.h, L.ld, L.ps, (i & 1) ? M1 : M0, (i & 1) ? M0 : M1, fl, R, (flags & 2) ? 0 : 1,
-                            level, npairs);
+                launch_blur(e, st, BlurLaunch{L.w, L.h, L.ld, L.ps, (i & 1) ? M1 : M0, (i & 1) ? M0 : M1, fl, R, (flags & 2) ? 0 : 1,
+                                              level, npairs});
                 break;
             case TW_K_SCAN: {
                 GatherArgs g;
@@ -3984,6 +4012,57 @@ extern "C" tw_status tw_bench_stage(tw_engine* e, int kclass, int width, int hei
     return TW_OK;
 }
 
+namespace {
+// The pyramid stage entry points: upload the image and the one-entry pointer table the kernels read it through, run `launch`
+// (table, device planes) into one plane per entry of `levels`, and download them to `out`.
+template <size_t N, typename F>
+tw_status run_pyr_stage(tw_engine* e, const Plan* pl, const uint8_t* img, int w0, int h0, const int (&levels)[N], float* const (&out)[N],
+                        F launch)
+{
+    Tmp t;
+    uint8_t* d_img = t.alloc<uint8_t>((size_t)w0 * h0);
+    float* d_I[N];
+    bool ok = d_img != nullptr;
+    for (size_t i = 0; i < N; i++) ok = (d_I[i] = t.alloc<float>((size_t)pl->lv[levels[i]].ps)) && ok;
+    const uint8_t** d_tab = t.alloc<const uint8_t*>(1);
+    if (!ok || !d_tab) return TW_E_NOMEM;
+    TW_TRY(h2d_sync(e, d_img, img, (size_t)w0 * h0));
+    const uint8_t* hp = d_img;
+    TW_TRY(h2d_sync(e, (void*)d_tab, &hp, sizeof(hp)));
+    hipStream_t st = e->stream;
+    e->img_aligned4 = 1;  // hipMalloc'ed image, dense rows: the kernel itself checks stride % 4
+    launch(st, d_tab, d_I);
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    for (size_t i = 0; i < N; i++) {
+        const LevelPlan& L = pl->lv[levels[i]];
+        TW_TRY(down_planes(e, out[i], d_I[i], L.ld, L.ps, L.w, L.h, 1));
+    }
+    return TW_OK;
+}
+// The coarser level's flow (pw x ph) and the resize tables to a w x h level, uploaded into `t`: TW_E_UNSUPPORTED for an
+// area-fast resize, which no kernel upsamples
+tw_status stage_flow_ups(tw_engine* e, Tmp& t, const float* prev2, int pw, int ph, int w, int h, FlowUps* ups)
+{
+    ResizeTab u;
+    make_resize_tab(pw, ph, w, h, u);
+    if (u.mode == 2) return TW_E_UNSUPPORTED;
+    const int pld = round_up(pw, 32);
+    const long long pps = (long long)pld * ph;
+    float* d_p = t.alloc<float>(pps * 2);
+    int *d_xo = t.alloc<int>(w), *d_yo = t.alloc<int>(h);
+    float *d_al = t.alloc<float>(2 * (size_t)w), *d_be = t.alloc<float>(2 * (size_t)h);
+    if (!d_p || !d_xo || !d_yo || !d_al || !d_be) return TW_E_NOMEM;
+    TW_TRY(up_planes(e, d_p, pld, pps, prev2, pw, ph, 2));
+    TW_TRY(h2d_sync(e, d_xo, u.xofs.data(), (size_t)w * 4));
+    TW_TRY(h2d_sync(e, d_yo, u.yofs.data(), (size_t)h * 4));
+    TW_TRY(h2d_sync(e, d_al, u.alpha.data(), (size_t)w * 8));
+    TW_TRY(h2d_sync(e, d_be, u.beta.data(), (size_t)h * 8));
+    *ups = FlowUps{d_p, pw, ph, pld, pps, d_xo, d_yo, d_al, d_be, u.xmax, (float)(1. / e->p.pyrScale)};
+    return TW_OK;
+}
+}  // namespace
+
 extern "C" {
 
 tw_status tw_stage_pyr_level(tw_engine* e, const uint8_t* img, int w0, int h0, int level, float* I, int* w, int* h)
@@ -3995,23 +4074,14 @@ tw_status tw_stage_pyr_level(tw_engine* e, const uint8_t* img, int w0, int h0, i
     Plan* pl = nullptr;
     if ((r = get_plan(e, w0, h0, &pl))) return r;
     if (level < 0 || level > pl->levels) return TW_E_BAD_PARAMETER;
-    const LevelPlan& L = pl->lv[level];
-    Tmp t;
-    uint8_t* d_img = t.alloc<uint8_t>((size_t)w0 * h0);
-    float* d_I = t.alloc<float>((size_t)L.ps);
-    const uint8_t** d_tab = t.alloc<const uint8_t*>(1);
-    if (!d_img || !d_I || !d_tab) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_img, img, (size_t)w0 * h0));
-    const uint8_t* hp = d_img;
-    TW_TRY(h2d_sync(e, (void*)d_tab, &hp, sizeof(hp)));
-    hipStream_t st = e->stream;
-    e->img_aligned4 = 1;  // hipMalloc'ed image, dense rows: the kernel itself checks stride % 4
-    launch_pyr(e, st, pl, level, d_tab, w0, d_I, 1);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    if ((r = down_planes(e, I, d_I, L.ld, L.ps, L.w, L.h, 1))) return r;
-    if (w) *w = L.w;
-    if (h) *h = L.h;
+    const int levels[1] = {level};
+    float* const out[1] = {I};
+    if ((r = run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
+            launch_pyr(e, st, pl, level, d_tab, w0, d_I[0], 1);
+        })))
+        return r;
+    if (w) *w = pl->lv[level].w;
+    if (h) *h = pl->lv[level].h;
     return TW_OK;
 }
 
@@ -4027,24 +4097,11 @@ tw_status tw_stage_pyr_fused23(tw_engine* e, const uint8_t* img, int w0, int h0,
         e->err = "tw_stage_pyr_fused23: levels 2 and 3 of this size are not exact reductions by 4 and 8";
         return TW_E_UNSUPPORTED;
     }
-    const LevelPlan &L3 = pl->lv[3], &L2 = pl->lv[2];
-    Tmp t;
-    uint8_t* d_img = t.alloc<uint8_t>((size_t)w0 * h0);
-    float* d_I3 = t.alloc<float>((size_t)L3.ps);
-    float* d_I2 = t.alloc<float>((size_t)L2.ps);
-    const uint8_t** d_tab = t.alloc<const uint8_t*>(1);
-    if (!d_img || !d_I3 || !d_I2 || !d_tab) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_img, img, (size_t)w0 * h0));
-    const uint8_t* hp = d_img;
-    TW_TRY(h2d_sync(e, (void*)d_tab, &hp, sizeof(hp)));
-    hipStream_t st = e->stream;
-    e->img_aligned4 = 1;  // hipMalloc'ed image, dense rows: the kernel itself checks stride % 4
-    launch_pyr23(e, st, pl, d_tab, w0, d_I3, d_I2, 1);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    if ((r = down_planes(e, I3, d_I3, L3.ld, L3.ps, L3.w, L3.h, 1))) return r;
-    if ((r = down_planes(e, I2, d_I2, L2.ld, L2.ps, L2.w, L2.h, 1))) return r;
-    return TW_OK;
+    const int levels[2] = {3, 2};
+    float* const out[2] = {I3, I2};
+    return run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
+        launch_pyr23(e, st, pl, d_tab, w0, d_I[0], d_I[1], 1);
+    });
 }
 
 tw_status tw_stage_pyr_fused01(tw_engine* e, const uint8_t* img, int w0, int h0, float* I0, float* I1)
@@ -4059,24 +4116,11 @@ tw_status tw_stage_pyr_fused01(tw_engine* e, const uint8_t* img, int w0, int h0,
         e->err = "tw_stage_pyr_fused01: level 1 of this size / these parameters is not an exact halving with 3-tap smoothing";
         return TW_E_UNSUPPORTED;
     }
-    const LevelPlan &L0 = pl->lv[0], &L1 = pl->lv[1];
-    Tmp t;
-    uint8_t* d_img = t.alloc<uint8_t>((size_t)w0 * h0);
-    float* d_I0 = t.alloc<float>((size_t)L0.ps);
-    float* d_I1 = t.alloc<float>((size_t)L1.ps);
-    const uint8_t** d_tab = t.alloc<const uint8_t*>(1);
-    if (!d_img || !d_I0 || !d_I1 || !d_tab) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_img, img, (size_t)w0 * h0));
-    const uint8_t* hp = d_img;
-    TW_TRY(h2d_sync(e, (void*)d_tab, &hp, sizeof(hp)));
-    hipStream_t st = e->stream;
-    e->img_aligned4 = 1;  // hipMalloc'ed image, dense rows: the kernel itself checks stride % 4
-    launch_pyr01(e, st, pl, d_tab, w0, d_I1, d_I0, 1);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    if ((r = down_planes(e, I0, d_I0, L0.ld, L0.ps, L0.w, L0.h, 1))) return r;
-    if ((r = down_planes(e, I1, d_I1, L1.ld, L1.ps, L1.w, L1.h, 1))) return r;
-    return TW_OK;
+    const int levels[2] = {0, 1};
+    float* const out[2] = {I0, I1};
+    return run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
+        launch_pyr01(e, st, pl, d_tab, w0, d_I[1], d_I[0], 1);
+    });
 }
 
 tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels, int w, int h, int waves, uint8_t* gray)
@@ -4155,16 +4199,7 @@ tw_status tw_stage_update_matrices(tw_engine* e, const float* R0_5, const float*
     if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
         (r = up_planes(e, d_f, ld, ps, flow2, w, h, 2)))
         return r;
-    UpdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.R = d_R;
-    a.flow = d_f;
-    a.M = d_M;
-    a.w = w;
-    a.h = h;
-    a.ld = ld;
-    a.ps = ps;
-    a.fps = ps;
+    const UpdArgs a = upd_args(d_R, d_f, d_M, w, h, ld, ps);
     hipStream_t st = e->stream;
     launch_upd_kernel<false>(e, st, w, h, 1, a);
     TW_HIP(e, hipGetLastError());
@@ -4179,45 +4214,15 @@ tw_status tw_stage_flow_upsample_update(tw_engine* e, const float* R0_5, const f
     tw_status r;
     if ((r = check_dims(e, w, h)) || (r = check_dims(e, pw, ph))) return r;
     TW_HIP(e, hipSetDevice(e->device));
-    const int ld = round_up(w, 32), pld = round_up(pw, 32);
-    const long long ps = (long long)ld * h, pps = (long long)pld * ph;
-    ResizeTab u;
-    make_resize_tab(pw, ph, w, h, u);
-    if (u.mode == 2) return TW_E_UNSUPPORTED;
+    const int ld = round_up(w, 32);
+    const long long ps = (long long)ld * h;
     Tmp t;
-    float *d_R = t.alloc<float>(ps * 10), *d_M = t.alloc<float>(ps * 5), *d_f = t.alloc<float>(ps * 2),
-          *d_p = t.alloc<float>(pps * 2);
-    int *d_xo = t.alloc<int>(w), *d_yo = t.alloc<int>(h);
-    float *d_al = t.alloc<float>(2 * (size_t)w), *d_be = t.alloc<float>(2 * (size_t)h);
-    if (!d_R || !d_M || !d_f || !d_p || !d_xo || !d_yo || !d_al || !d_be) return TW_E_NOMEM;
-    if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
-        (r = up_planes(e, d_p, pld, pps, prevflow2, pw, ph, 2)))
-        return r;
-    TW_TRY(h2d_sync(e, d_xo, u.xofs.data(), (size_t)w * 4));
-    TW_TRY(h2d_sync(e, d_yo, u.yofs.data(), (size_t)h * 4));
-    TW_TRY(h2d_sync(e, d_al, u.alpha.data(), (size_t)w * 8));
-    TW_TRY(h2d_sync(e, d_be, u.beta.data(), (size_t)h * 8));
-    UpdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.R = d_R;
-    a.flow = d_f;
-    a.M = d_M;
-    a.w = w;
-    a.h = h;
-    a.ld = ld;
-    a.ps = ps;
-    a.fps = ps;
-    a.prev = d_p;
-    a.pw = pw;
-    a.ph = ph;
-    a.pld = pld;
-    a.pfps = pps;
-    a.xofs = d_xo;
-    a.alpha = d_al;
-    a.yofs = d_yo;
-    a.beta = d_be;
-    a.xmax = u.xmax;
-    a.scale = (float)(1. / e->p.pyrScale);
+    FlowUps ups;
+    if ((r = stage_flow_ups(e, t, prevflow2, pw, ph, w, h, &ups))) return r;
+    float *d_R = t.alloc<float>(ps * 10), *d_M = t.alloc<float>(ps * 5), *d_f = t.alloc<float>(ps * 2);
+    if (!d_R || !d_M || !d_f) return TW_E_NOMEM;
+    if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5))) return r;
+    UpdArgs a = upd_args(d_R, d_f, d_M, w, h, ld, ps, &ups);
     a.store_flow = 1;
     hipStream_t st = e->stream;
     launch_upd_kernel<true>(e, st, w, h, 1, a);
@@ -4244,8 +4249,11 @@ tw_status tw_stage_blur_solve(tw_engine* e, const float* R0_5, const float* R1_5
     if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
         (r = up_planes(e, d_M, ld, ps, M5, w, h, 5)))
         return r;
+    BlurLaunch b{w, h, ld, ps, d_M, d_Mo, d_f, d_R, update_matrices ? 1 : 0, -1, 1};
+    b.store_flow = 1;  // the stage returns the flow of a refreshing launch as well
+    if (e->box && !(b.Vbox = t.alloc<double>((size_t)ps * 5))) return TW_E_NOMEM;  // no engine workspace here
     hipStream_t st = e->stream;
-    launch_blur(e, st, w, h, ld, ps, d_M, d_Mo, d_f, d_R, update_matrices ? 1 : 0, -1, 1);
+    launch_blur(e, st, b);
     TW_HIP(e, hipGetLastError());
     TW_HIP(e, hipStreamSynchronize(st));
     if ((r = down_planes(e, flow2, d_f, ld, ps, w, h, 2))) return r;
@@ -4266,8 +4274,6 @@ tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5,
     TW_HIP(e, hipSetDevice(e->device));
     const int ld = round_up(w, 32);
     const long long ps = (long long)ld * h;
-    const int pld = prev2 ? round_up(pw, 32) : 0;
-    const long long pps = (long long)pld * ph;
     Tmp t;
     float *d_R = t.alloc<float>(ps * 10), *d_fi = t.alloc<float>(ps * 2), *d_fo = t.alloc<float>(ps * 2);
     if (!d_R || !d_fi || !d_fo) return TW_E_NOMEM;
@@ -4276,19 +4282,7 @@ tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5,
     FlowUps ups;
     if (prev2) {
         if (pw < 1 || ph < 1) return TW_E_BAD_PARAMETER;
-        ResizeTab u;
-        make_resize_tab(pw, ph, w, h, u);
-        if (u.mode == 2) return TW_E_UNSUPPORTED;
-        float* d_p = t.alloc<float>(pps * 2);
-        int *d_xo = t.alloc<int>(w), *d_yo = t.alloc<int>(h);
-        float *d_al = t.alloc<float>(2 * (size_t)w), *d_be = t.alloc<float>(2 * (size_t)h);
-        if (!d_p || !d_xo || !d_yo || !d_al || !d_be) return TW_E_NOMEM;
-        if ((r = up_planes(e, d_p, pld, pps, prev2, pw, ph, 2))) return r;
-        TW_TRY(h2d_sync(e, d_xo, u.xofs.data(), (size_t)w * 4));
-        TW_TRY(h2d_sync(e, d_yo, u.yofs.data(), (size_t)h * 4));
-        TW_TRY(h2d_sync(e, d_al, u.alpha.data(), (size_t)w * 8));
-        TW_TRY(h2d_sync(e, d_be, u.beta.data(), (size_t)h * 8));
-        ups = FlowUps{d_p, pw, ph, pld, pps, d_xo, d_yo, d_al, d_be, u.xmax, (float)(1. / e->p.pyrScale)};
+        if ((r = stage_flow_ups(e, t, prev2, pw, ph, w, h, &ups))) return r;
     }
     hipStream_t st = e->stream;
     launch_flow_iter(e, st, w, h, ld, ps, d_R, flow_in2 ? d_fi : nullptr, ps, d_fo, ps, prev2 ? &ups : nullptr, 1, -1);

@@ -72,6 +72,7 @@ SYMBOLS = [
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
+    "tw_debug_blur_plan",
 ]
 
 
@@ -198,10 +199,13 @@ def _bind(path):
     L.tw_debug_check_size.restype = C.c_int
     L.tw_debug_flow_iter_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.tw_debug_flow_iter_plan.restype = C.c_int
+    L.tw_debug_blur_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
+    L.tw_debug_blur_plan.restype = C.c_int
     return L
 
 
 FlowIterPlan = collections.namedtuple("FlowIterPlan", "strips segments nt nt_last")
+BlurPlan = collections.namedtuple("BlurPlan", "family block tile_cols rows xsh grid_x grid_y small forced")
 
 
 class LaunchCounts(dict):
@@ -585,6 +589,16 @@ class Engine:
         if n != 4:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_flow_iter_plan(%d, %d, %d) returned %d" % (w, h, npairs, n))
         return FlowIterPlan(*v)
+
+    def blur_plan(self, w, h, level=-1, npairs=1, update=False, quads=False):
+        """The choice of one window average + solve launch at a level of w x h pixels, from the function the launch itself
+        uses (twflow_debug.h: tw_debug_blur_plan): the kernel's family name, threads, tile columns, rows per workgroup, xsh,
+        grid x / y, the small-grid class and whether TW_BLUR_SMALL / TW_BLUR_SMALL_LEVELS forced it."""
+        v = (C.c_int * 9)()
+        n = self._L.tw_debug_blur_plan(self._h, w, h, level, npairs, int(bool(update)), int(bool(quads)), v, 9)
+        if n != 9:
+            raise TwError(TW_E_BAD_PARAMETER, "tw_debug_blur_plan(%d, %d, %d, %d) returned %d" % (w, h, level, npairs, n))
+        return BlurPlan(self._L.tw_debug_family_name(v[0]).decode(), *v[1:8], bool(v[8]))
 
     def launch_counts(self, reset=False):
         """{family name: launches} since creation / the last reset, every family (twflow_debug.h)."""
