@@ -2184,8 +2184,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // issued — two tap register sets that swap roles like the two R0 sets did.  A chunk's taps then have a whole step
     // (~9 000 cycles) to arrive and may be issued in ANY phase, phase B2 included; before, all of them had to go out in phases
     // A and H of the step whose B2 combines them (195 of a step's 255 wave-loads in phase A alone).  R0 is loaded in the step
-    // that uses it.  The upsampling first iteration (MODE 1) carries eight coarse taps per pixel as well and keeps the old
-    // schedule: a second tap set does not fit its registers.
+    // that uses it.  The upsampling first iteration (MODE 1) carries eight coarse taps per pixel as well and keeps the
+    // one-set schedule (step below; its loads placed by UDIST): a second tap set does not fit its registers.
 #ifndef TW_FI_DEEP
 #define TW_FI_DEEP 1
 #endif
@@ -2207,6 +2207,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         {TW_FI_P(0, 1), TW_FI_P(0, 3), TW_FI_P(1, 0), TW_FI_P(1, 1), TW_FI_P(1, 2), TW_FI_P(1, 3), TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 1), TW_FI_P(2, 1)},
         {TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 0), TW_FI_P(2, 0)},
         {TW_FI_P(0, 0), TW_FI_P(0, 0), TW_FI_P(0, 1), TW_FI_P(0, 1), TW_FI_P(0, 2), TW_FI_P(0, 2), TW_FI_P(0, 3), TW_FI_P(0, 3), TW_FI_P(0, 4), TW_FI_P(0, 4)},
+    };
+    // MODE 1 (no second tap set): where a step's fifteen R loads go out — the ten tap halves of the chunk this step combines
+    // (phases 0 and 1 only: phase B2 consumes them), then the five R0 planes of the chunk after it (phase 2 slot 1 = behind the
+    // combine: they have the whole next step to arrive).  The coarse taps and the row's table entry stay at the head of phase A
+    // (issued late they measured +5 %).  Preset 0 is the schedule of rounds 5 / 6: 22 of a step's 26 loads in phase A; preset 1
+    // leaves 17 there, one tap half per V row and H pixel, and measures -1.8 % on the launch alone, -3.6 ... -4.9 % in the
+    // batch (profiles/flow_iter_ups.md; a third placement that lost is in its experiment diff).  TW_FI_UDIST picks a preset
+    // (A/B builds).
+#ifndef TW_FI_UDIST
+#define TW_FI_UDIST 1
+#endif
+    constexpr int UDIST[2][15] = {
+        {TW_FI_P(0, 0), TW_FI_P(0, 0), TW_FI_P(0, 1), TW_FI_P(0, 1), TW_FI_P(0, 2), TW_FI_P(0, 2), TW_FI_P(1, 0), TW_FI_P(1, 0), TW_FI_P(1, 1), TW_FI_P(1, 1),
+         TW_FI_P(0, 0), TW_FI_P(0, 1), TW_FI_P(0, 2), TW_FI_P(0, 3), TW_FI_P(0, 4)},
+        // 1: two tap halves behind V's first row, one behind each other row and each of H's pixels; R0 behind the combine
+        {TW_FI_P(0, 0), TW_FI_P(0, 0), TW_FI_P(0, 1), TW_FI_P(0, 2), TW_FI_P(0, 3), TW_FI_P(0, 4), TW_FI_P(1, 0), TW_FI_P(1, 1), TW_FI_P(1, 2), TW_FI_P(1, 3),
+         TW_FI_P(2, 1), TW_FI_P(2, 1), TW_FI_P(2, 1), TW_FI_P(2, 1), TW_FI_P(2, 1)},
     };
     constexpr int TH = FI_TH, SC = NT == 1024 ? FI_SC : FI_SC_512, P = NT == 1024 ? FI_PITCH : FI_PITCH_512, OUT = SC - 2 * MH,
                   RING = TH + 2 * MH, NCH = RING / TH, NB = NCH + 1;
@@ -2448,13 +2465,26 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
     // H of one item: (plane hp, row hr, 4-pixel group hq): 36-value window of block bX, four sums into block s0; WITH_LOADS:
     // the taps of planes 3 and 4 of the thread's phase-C pixel behind the first two pixels (main waves only)
-    auto h_phase = [&](int s0, int bX, auto with_loads_c, UpdTaps& Tl) {
+    auto h_phase = [&](int s0, int bX, auto with_loads_c, UpdTaps& Tl, float (&ql)[5]) {
         constexpr bool WITH_LOADS = decltype(with_loads_c)::value;
         constexpr int HPLANE0 = DEEP ? 1 : 3;  // the tap planes that go out behind H's first two pixels
         float v[4 + 2 * MH + 2];
         const f32x4* W4 = (const f32x4*)&blk[bX][hp][hr][4 * hq];
 #pragma unroll
         for (int u = 0; u < (4 + 2 * MH + 2) / 4; u++) {
+            // MODE 1: the window's last two values as 8 bytes.  The 16-byte read leaves two dead registers, the compiler
+            // put a tap pair of the combine there, and every step then waited for ALL of phase A's loads, vmcnt(0), before
+            // this read might overwrite them (-1.2 % on the launch with preset 1).  Nothing but the ISA guards this: after a
+            // compiler update look for s_waitcnt vmcnt(0) between the step's first barrier and H's buffer loads
+            // (profiles/flow_iter_ups.md has the sequence to expect)
+            if constexpr (UPS && !DEEP) {
+                if (u == (4 + 2 * MH + 2) / 4 - 1) {
+                    const f32x2 t2 = *(const f32x2*)&W4[u];
+                    v[4 * u] = t2.x;
+                    v[4 * u + 1] = t2.y;
+                    continue;
+                }
+            }
             const f32x4 t = W4[u];
             v[4 * u] = t[0];
             v[4 * u + 1] = t[1];
@@ -2477,6 +2507,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
                     for (int u = 0; u < 10; u++)
                         if (DIST[TW_FI_DIST][u] == TW_FI_P(1, j)) gather_half(u >> 1, u & 1, Tl);
+                } else if constexpr (UPS) {
+#pragma unroll
+                    for (int u = 0; u < 15; u++)
+                        if (UDIST[TW_FI_UDIST][u] == TW_FI_P(1, j)) {
+                            if (u < 10) gather_half(u >> 1, u & 1, Tl);
+                            else gather_r0(u - 10, ql);
+                        }
                 } else {
                     if (j < 2) gather_plane(HPLANE0 + j, Tl);
                 }
@@ -2496,7 +2533,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         for (int st = 0; st < nsteps; st++) {
             const int s0 = st & (NB - 1), bX = (st + NCH) & (NB - 1);
             TW_FI_SYNC();  // (V)
-            if (hth && !TW_FI_SKIP(4)) h_phase(s0, bX, std::false_type(), T);
+            if (hth && !TW_FI_SKIP(4)) h_phase(s0, bX, std::false_type(), T, q);
             TW_FI_SYNC();  // (H)
             s_phase(st, s0);
             TW_FI_SYNC();  // (C, S)
@@ -2510,6 +2547,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // costs an s_waitcnt in place).  With it NO load is left in phase B2 (stamps: seven head loads issued there by all 15
     // waves at once blocked every wave for ~1 000 cycles): the next chunk's flow before V's first row, its R0 behind V's
     // rows, this chunk's taps of planes 0-2 behind rows 0-2 and of planes 3-4 behind H's first pixels.
+    // (MODE 1 places the same fifteen loads by UDIST; its preset 1 does put the next chunk's R0 behind the combine — five
+    // loads with nothing waiting for them in that phase.)
     auto step = [&](int st, float (&qc)[5], float (&qn)[5]) {
         const bool more = st + 1 < nsteps;  // V(st + 1) will run: it needs chunk st + NCH
         const int s0 = st & (NB - 1), bX = (st + NCH) & (NB - 1);
@@ -2549,8 +2588,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 for (int i = 1; i <= MH; i++) sv += (wv[r + MH + i] + wv[r + MH - i]) * c.k[i];
                 vout[r * P] = sv;
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (UPS) {
+#pragma unroll
+                    for (int u = 0; u < 15; u++)
+                        if (UDIST[TW_FI_UDIST][u] == TW_FI_P(0, r)) {
+                            if (u < 10) gather_half(u >> 1, u & 1, T);  // (taps of chunk st + NCH)
+                            else gather_r0(u - 10, qn);                 // (R0 of chunk st + NCH + 1)
+                        }
+                } else {
                 if (r < 3) gather_plane(r, T);  // (the taps of planes 0-2 of chunk st + NCH behind rows 0-2; planes 3, 4 inside H)
                 gather_r0(r, qn);               // (TH == 5 planes: R0 plane r of chunk st + NCH + 1 behind row r)
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -2561,7 +2609,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         // ---- phase B1: H — (plane, row, 4-pixel group): 36-value window from block X, four sums into block Y ----
         // (every H thread of these waves issues the tap loads: the few that have no pixel in phase C load from offset 0 of
         // the plane — valid, unused — rather than make the load conditional: see above)
-        if (!TW_FI_SKIP(4)) h_phase(s0, bX, std::true_type(), T);
+        if (!TW_FI_SKIP(4)) h_phase(s0, bX, std::true_type(), T, qn);
         TW_FI_STAMP(3);
         TW_FI_SYNC();
         TW_FI_STAMP(4);
@@ -2575,6 +2623,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         if (cth) {
             if (more && !TW_FI_SKIP(1)) combine_store(st + NCH, dx, dy, qc, T);
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (UPS) {
+#pragma unroll
+                for (int u = 10; u < 15; u++)
+                    if (UDIST[TW_FI_UDIST][u] == TW_FI_P(2, 1)) gather_r0(u - 10, qn);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             TW_FI_STAMP(6);
             // the next chunk's flow value and tap addresses (no load: its R0 is on its way into qn, its taps follow in V / H)
             flow_value(fnext, dx, dy);
@@ -2623,7 +2677,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         TW_FI_STAMP(1);
         TW_FI_SYNC();
         TW_FI_STAMP(2);
-        if (!TW_FI_SKIP(4)) h_phase(s0, bX, std::true_type(), Tn);
+        if (!TW_FI_SKIP(4)) h_phase(s0, bX, std::true_type(), Tn, q);
         TW_FI_STAMP(3);
         TW_FI_SYNC();
         TW_FI_STAMP(4);
