@@ -66,6 +66,7 @@ enum tw_debug_family {
     TW_DF_PNG_UNFILTER,
     TW_DF_SPAN_SCAN_SEG,   /* tw_span_scan_seg: a single pair's ordered scan in 16 independent segments (round 6) */
     TW_DF_BLUR_SOLVE4Q,    /* tw_blur_solve4q: solve + refresh by the horizontal item's owner — a single pair's level-0 launches (round 6) */
+    TW_DF_PAIR_SAME,       /* tw_pair_same: which pairs of a batch part have two byte-identical images */
     TW_DF_FLOW_INIT,       /* tw_flow_area_init: tw_submit_*_flow_init fields -> the coarsest level's first flow (zeros without one) */
     TW_DF_FLOW_EXPORT,     /* tw_flow_export: a level-0 chunk's final flow -> the pairs' tw_submit_*_flow destinations */
     TW_DF_COUNT
@@ -94,6 +95,14 @@ int tw_debug_flow_iter_plan(const tw_engine* e, int width, int height, int npair
  * Returns the number of values written (at most min(n, 9); 0 for a null `out` or a non-positive size), -1 for a null engine.
  * tests/test_gpu_blur_dispatch.py proves from it which side of each edge of the choice ran. */
 int tw_debug_blur_plan(const tw_engine* e, int width, int height, int level, int npairs, int update, int quads, int* out, int n);
+
+/* tw_pair_same's flags of the batch this engine enqueued last: out[j] = 1 where pair j's second image is byte for byte its
+ * first over the visible width x height pixels (the batch schedule then computed that pair's polynomial expansions once at
+ * the levels tw_flow_iter runs), 0 otherwise — and 0 for every pair of a batch that launched no tw_pair_same (TW_SAME_IMAGE=0,
+ * the single-pair schedules).  Waits for the batch.  Returns the number of values written (at most min(n, pairs of that
+ * batch); 0 for a null `out`), -1 for a null engine, -2 when the device refuses the wait or the copy (`out` then holds
+ * zeros that are no flags).  Engine-level state: it describes whichever batch the engine enqueued LAST, not a ticket. */
+int tw_debug_same_flags(tw_engine* e, unsigned* out, int n);
 
 /* Name of a family ("tw_flow_iter", ...), NULL past the end. */
 const char* tw_debug_family_name(int family);

@@ -529,6 +529,12 @@ struct tw_engine {
     FlowDst* d_fsrc = nullptr;  // tw_submit_*_flow_init: the device copy of a batch's init source table ([cap], on first use)
     const uint8_t** d_ptrs = nullptr;  // [2*cap]
     int* d_count = nullptr;            // [cap]
+    // identical pairs (tw_pair_same): 1 where a pair's second image is byte for byte its first — the batch schedule then
+    // computes that pair's pyramid levels and polynomial expansions once, at the levels tw_flow_iter runs (it reads R0 as R1)
+    unsigned* d_same = nullptr;        // [cap], of the batch enqueued last; all 0 until a batch schedule fills it
+    int same_image = 1;                // TW_SAME_IMAGE=0: no tw_pair_same launch, both images of every pair processed (A/B)
+    int same_n = 0;                    // pairs of the batch enqueued last (tw_debug_same_flags)
+    bool same_valid = false;           // ... and whether tw_pair_same ran for it
     float2* d_grid = nullptr;          // [cap][G] dense grid samples (dx,dy)
     size_t d_grid_cap = 0;
     // profiling: per kernel class, -2 = off, -1 = every level, k = level k only
@@ -1059,8 +1065,10 @@ void launch_upd_kernel(tw_engine* e, hipStream_t st, int w, int h, int npairs, c
 }
 
 // ---- kernel launch helpers (nz = images or pairs in this launch) -------------------------------------
+// same: tw_pair_same's flags of the launch's pairs where the level's only reader of the second images honours them (null:
+// every image) — the 3-tap register kernel skips those images, the other kernels compute them as ever
 void launch_pyr(tw_engine* e, hipStream_t st, const Plan* pl, int k, const uint8_t* const* d_srcs, long long stride,
-                float* I, int nimg)
+                float* I, int nimg, const unsigned* same = nullptr)
 {
     const LevelPlan& L = pl->lv[k];
     PyrArgs a;
@@ -1102,6 +1110,7 @@ void launch_pyr(tw_engine* e, hipStream_t st, const Plan* pl, int k, const uint8
         b.k0 = L.h_kern[1];
         b.k1 = L.h_kern[0];
         b.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
+        b.same = same;
         if (L.mode == 0) TW_LAUNCH(e, TW_DF_PYR_K3, tw_pyr_k3<0>, dim3((L.w + 255) / 256, (L.h + 7) / 8, nimg), dim3(256), 0, st, b);
         else TW_LAUNCH(e, TW_DF_PYR_K3, tw_pyr_k3<2>, dim3((L.w + 255) / 256, (L.h + 3) / 4, nimg), dim3(256), 0, st, b);
         return;
@@ -1174,9 +1183,11 @@ void launch_pyr23(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* c
 }
 
 tw_status launch_polyexp(tw_engine* e, hipStream_t st, int w, int h, int ld, long long ps, const float* I, float* R,
-                         int nimg, int level, const SideJob* side = nullptr, bool* side_used = nullptr)
+                         int nimg, int level, const SideJob* side = nullptr, bool* side_used = nullptr,
+                         const unsigned* same = nullptr)
 {
     PolyArgs a;
+    a.same = same;
     a.src = I;
     a.dst = R;
     a.w = w;
@@ -1249,7 +1260,7 @@ bool pyr01_fusable(const Plan* pl)
            pl->w0 == 2 * pl->lv[1].w && pl->h0 == 2 * pl->lv[1].h && pl->w0 >= 16;
 }
 void launch_pyr01(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* const* d_srcs, long long stride, float* I1,
-                  float* I0, int nimg)
+                  float* I0, int nimg, const unsigned* same = nullptr)
 {
     const LevelPlan &L0 = pl->lv[0], &L1 = pl->lv[1];
     PyrK3fArgs a;
@@ -1270,6 +1281,7 @@ void launch_pyr01(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* c
     a.b0 = L1.h_kern[1];
     a.b1 = L1.h_kern[0];
     a.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
+    a.same = same;
     ProfScope ps(e, st, TW_K_PYR, 1);
     TW_LAUNCH(e, TW_DF_PYR_K3F, tw_pyr_k3f, dim3((L1.w + 255) / 256, (L1.h + 3) / 4, nimg), dim3(256), 0, st, a);
 }
@@ -1385,10 +1397,12 @@ FlowIterPlan flow_iter_plan(const tw_engine* e, int w, int h, int npairs)
     return fp;
 }
 void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long long ps, const float* R, const float* flow_in,
-                      long long fps_in, float* flow_out, long long fps_out, const FlowUps* ups, int npairs, int level)
+                      long long fps_in, float* flow_out, long long fps_out, const FlowUps* ups, int npairs, int level,
+                      const unsigned* same = nullptr)
 {
     FlowIterArgs a;
     memset(&a, 0, sizeof(a));
+    a.same = same;
     a.R = R;
     a.flow_in = flow_in;
     a.flow_out = flow_out;
@@ -2145,6 +2159,7 @@ struct BatchEnqueue {
             const int lo = ramp ? ramp_b[part] : (int)((long long)n * lane / nlanes);
             const int hi = ramp ? ramp_b[part + 1] : (int)((long long)n * (lane + 1) / nlanes);
             if (ramp) TW_HIP(e, hipStreamWaitEvent(st, part + 1 < nparts ? c.ev_seg[part] : c.ev_h2d, 0));
+            TW_TRY(enqueue_pair_same(lane == 0 ? st : e->stream2, lo, hi));
             for (int k = pl->levels; k >= 0; k--) {
                 const LevelPlan& L = pl->lv[k];
                 RoctxRange level_range("tw_level %d (%dx%d)", k, L.w, L.h);
@@ -2167,6 +2182,31 @@ struct BatchEnqueue {
         return TW_OK;
     }
 
+    // which pairs [lo, hi) of a part have two byte-identical images: the flags every later launch of the part may read
+    // (behind the part's uploads, on the part's stream)
+    tw_status enqueue_pair_same(hipStream_t ls, int lo, int hi)
+    {
+        if (!e->same_image || hi <= lo) return TW_OK;
+        TW_HIP(e, hipMemsetD32Async((hipDeviceptr_t)(e->d_same + lo), 1, hi - lo, ls));
+        PairSameArgs a;
+        a.srcs = e->d_ptrs + 2 * lo;
+        a.same = e->d_same + lo;
+        a.stride = stride;
+        a.w = c.w;
+        a.h = c.h;
+        TW_LAUNCH(e, TW_DF_PAIR_SAME, tw_pair_same, dim3((c.h + PS_ROWS - 1) / PS_ROWS, 1, hi - lo), dim3(256), 0, ls, a);
+        e->same_valid = true;
+        return TW_OK;
+    }
+    // the flags of a chunk's pairs for the launches of level k — only where EVERY reader of the level's second expansions
+    // takes the first in their place: tw_flow_iter does, the update / window kernels (enqueue_update_blur_chain, and the
+    // scan-fused last iteration's tw_update_matrices at level 0) do not, and their levels get both expansions as before
+    const unsigned* same_flags_of(const LevelChunk& ch) const { return same_flags_of(ch.k, ch.j0, ch.nc); }
+    const unsigned* same_flags_of(int k, int j0, int nc) const
+    {
+        return (e->same_image && level_mfree(k, nc) && !(k == 0 && fused_final)) ? e->d_same + j0 : nullptr;
+    }
+
     // pyramid + polynomial expansion of a chunk's images (batch schedule); npart: the pairs of the chunk's part
     tw_status enqueue_level_images(const LevelChunk& ch, int npart)
     {
@@ -2187,11 +2227,14 @@ struct BatchEnqueue {
                          pl->lv[0].chunk >= npart && level_mfree(0, nc) && level_mfree(1, nc);
         float* I0side = ch.M1;
         const uint8_t* const* srcs = e->d_ptrs + 2 * ch.j0;
+        // (tw_pyr_k3f writes levels 1 and 0 together: it may skip an image only when both levels skip its expansion)
+        const unsigned* same = same_flags_of(ch);
+        const unsigned* same01 = same_flags_of(0, ch.j0, nc) ? same : nullptr;
         if (f23 && k == 3) launch_pyr23(e, ch.ls, pl, srcs, stride, ch.I, I2side, 2 * nc);
-        else if (f01 && k == 1) launch_pyr01(e, ch.ls, pl, srcs, stride, ch.I, I0side, 2 * nc);
-        else if (!(f23 && k == 2) && !(f01 && k == 0)) launch_pyr(e, ch.ls, pl, k, srcs, stride, ch.I, 2 * nc);
+        else if (f01 && k == 1) launch_pyr01(e, ch.ls, pl, srcs, stride, ch.I, I0side, 2 * nc, same01);
+        else if (!(f23 && k == 2) && !(f01 && k == 0)) launch_pyr(e, ch.ls, pl, k, srcs, stride, ch.I, 2 * nc, same);
         const float* Isrc = (f23 && k == 2) ? I2side : (f01 && k == 0) ? I0side : ch.I;
-        return launch_polyexp(e, ch.ls, L.w, L.h, L.ld, L.ps, Isrc, ch.R, 2 * nc, k);
+        return launch_polyexp(e, ch.ls, L.w, L.h, L.ld, L.ps, Isrc, ch.R, 2 * nc, k, nullptr, nullptr, same);
     }
 
     // -- one pair, two streams: the flow chain walks the levels on the main stream, the image-only work of the finer
@@ -2384,7 +2427,7 @@ struct BatchEnqueue {
             float* out = buf[(nfi - 1 - i) & 1];
             const float* in = i == 0 ? (ch.init_lv ? buf[nfi & 1] : nullptr) : buf[(nfi - i) & 1];
             launch_flow_iter(e, ch.ls, L.w, L.h, L.ld, L.ps, ch.R, in, L.ps, out, L.ps,
-                             (i == 0 && k < pl->levels) ? &ups : nullptr, nc, k);
+                             (i == 0 && k < pl->levels) ? &ups : nullptr, nc, k, same_flags_of(ch));
         }
         if (!ch.grid_only) return;
         UpdArgs u;
@@ -2510,6 +2553,8 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     TW_TRY(b.upload_tables());
     TW_HIP(e, hipEventRecord(c.ev_start, e->stream));
     TW_TRY(b.choose_schedule());
+    e->same_n = b.n;
+    e->same_valid = false;  // (until the batch schedule launches tw_pair_same)
     TW_TRY(b.enqueue_or_replay_graph());
     TW_TRY(b.enqueue_scan());
     TW_TRY(b.enqueue_result_copies());
@@ -3069,6 +3114,7 @@ tw_status tw_engine_create(int device, const tw_params* params, int slots, tw_en
 #endif
     if (const char* ev = getenv("TW_LAT_S2_LEVELS")) e->lat_s2_max = atoi(ev);
     if (const char* ev = getenv("TW_RAMP")) e->ramp = atoi(ev) ? 1 : 0;
+    if (const char* ev = getenv("TW_SAME_IMAGE")) e->same_image = atoi(ev) ? 1 : 0;
     if (const char* ev = getenv("TW_FI_MAXSEG")) e->fi_maxseg = std::min(64, std::max(1, atoi(ev)));
     if (const char* ev = getenv("TW_FI_MINSTEPS")) e->fi_minsteps = std::max(2, atoi(ev));
     // the main stream carries the dependent flow chain: highest priority, so that its small launches are not queued
@@ -3081,7 +3127,9 @@ tw_status tw_engine_create(int device, const tw_params* params, int slots, tw_en
               hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) == hipSuccess &&
               hipMalloc((void**)&e->d_ptrs, sizeof(void*) * 2 * slots + 256) == hipSuccess &&
-              hipMalloc((void**)&e->d_count, sizeof(int) * slots + 256) == hipSuccess;
+              hipMalloc((void**)&e->d_count, sizeof(int) * slots + 256) == hipSuccess &&
+              hipMalloc((void**)&e->d_same, sizeof(unsigned) * slots + 256) == hipSuccess &&
+              hipMemset(e->d_same, 0, sizeof(unsigned) * slots + 256) == hipSuccess;
     for (Ctx& c : e->ctx) {
         ok = ok && hipEventCreate(&c.ev_start) == hipSuccess && hipEventCreate(&c.ev_stop) == hipSuccess &&
              hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming) == hipSuccess &&
@@ -3117,6 +3165,7 @@ void tw_engine_destroy(tw_engine* e)
         if (f) (void)hipFree(f);
     if (e->d_ptrs) (void)hipFree((void*)e->d_ptrs);
     if (e->d_count) (void)hipFree(e->d_count);
+    if (e->d_same) (void)hipFree(e->d_same);
     if (e->d_grid) (void)hipFree(e->d_grid);
     if (e->Vd) (void)hipFree(e->Vd);
     if (e->h_bounce) (void)hipHostFree(e->h_bounce);
@@ -3756,14 +3805,30 @@ extern "C" int tw_debug_launch_counts(tw_engine* e, unsigned long long* counts, 
     return TW_DF_COUNT;
 }
 
+extern "C" int tw_debug_same_flags(tw_engine* e, unsigned* out, int n)
+{
+    if (!e) return -1;
+    if (!out || n < 1) return 0;
+    const int m = std::min(n, e->same_n);
+    for (int i = 0; i < m; i++) out[i] = 0;
+    if (m < 1 || !e->same_valid) return std::max(m, 0);
+    // (both lanes' launches are joined into the main stream before the batch's scan)
+    if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
+        hipMemcpy(out, e->d_same, sizeof(unsigned) * m, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return -2;  // (out holds zeros, none of them a flag)
+    }
+    return m;
+}
+
 extern "C" const char* tw_debug_family_name(int family)
 {
     static const char* const names[TW_DF_COUNT] = {
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_area_init",
-        "tw_flow_export"};
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pair_same",
+        "tw_flow_area_init", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
 }
 
@@ -3783,6 +3848,7 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     if (e->d_grid) v[0] += e->d_grid_cap * sizeof(float2) + 256;
     if (e->d_ptrs) v[0] += sizeof(void*) * 2 * (size_t)e->cap + 256;
     if (e->d_count) v[0] += sizeof(int) * (size_t)e->cap + 256;
+    if (e->d_same) v[0] += sizeof(unsigned) * (size_t)e->cap + 256;
     if (e->dbg_stamps) v[0] += 4096 * sizeof(unsigned long long);
     if (e->d_fdst) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
     if (e->d_fsrc) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;

@@ -73,6 +73,7 @@ __device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, unsigned voff, 
 }
 typedef float __attribute__((ext_vector_type(2))) f32x2;
 typedef unsigned __attribute__((ext_vector_type(2))) u32x2;
+typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
 __device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v)
 {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
@@ -865,7 +866,55 @@ struct PyrK3Args {
     int w0, h0, w, h, ld;
     float k0, k1;  // centre / side tap
     int aligned4;  // rows start 4-byte aligned: whole-dword loads allowed
+    const unsigned* same = nullptr;  // tw_pair_same's flags of the launch's pairs (image z belongs to pair z >> 1); null: every image
 };
+
+// Does this workgroup's image need no work of its own?  The second image (odd z) of a pair whose flag says it is
+// byte-identical to the first: every reader of its level takes the first image's result instead (tw_flow_iter's R1).
+__device__ __forceinline__ bool second_image_same(const unsigned* same, int z) { return (z & 1) && same && same[z >> 1]; }
+
+// -----------------------------------------------------------------------------------------------------
+// tw_pair_same : same[z] = 0 where pair z's second image differs from its first in any of the visible w x h bytes (row
+//   padding of a strided image is not compared).  The flags are 1 when the launch starts (the host sets them in stream
+//   order); a workgroup compares a band of PS_ROWS rows, one wave per row, and a lane that meets a difference clears the flag
+//   with a plain store — every writer stores the same 0.  (Leaving at once when the flag is already cleared measured
+//   nothing, 88.6 against 89.3 us per 128 pairs of 1080p: the launch streams at the copy rate either way — profiles/same_image.md.)
+//   16-byte loads wherever the two images' rows are aligned alike (both pointers equal mod 16: staged images always are),
+//   the bytes before a row's first 16-byte boundary and behind its last whole vector one by one; byte loads otherwise.
+// -----------------------------------------------------------------------------------------------------
+constexpr int PS_ROWS = 16;
+struct PairSameArgs {
+    const uint8_t* const* srcs;  // pair z: images srcs[2z], srcs[2z + 1]
+    unsigned* same;              // pair z's flag
+    long long stride;
+    int w, h;
+};
+__global__ __launch_bounds__(256) void tw_pair_same(PairSameArgs a)
+{
+    const int z = blockIdx.z;
+    const uint8_t* __restrict__ A = a.srcs[2 * z];
+    const uint8_t* __restrict__ B = a.srcs[2 * z + 1];
+    if (A == B) return;  // one image given twice
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const bool vec = (((uintptr_t)A ^ (uintptr_t)B) & 15u) == 0;
+    const int y1 = min(a.h, ((int)blockIdx.x + 1) * PS_ROWS);
+    unsigned diff = 0;
+    for (int y = blockIdx.x * PS_ROWS + ty; y < y1; y += 4) {
+        const uint8_t* __restrict__ ra = A + (long long)y * a.stride;
+        const uint8_t* __restrict__ rb = B + (long long)y * a.stride;
+        const int head = vec ? min(a.w, (int)((0 - (uintptr_t)ra) & 15u)) : a.w;  // bytes before the first 16-byte boundary
+        const int nv = (a.w - head) >> 4, tail0 = head + 16 * nv;
+        for (int i = tx; i < nv; i += 64) {
+            const u32x4 va = *(const u32x4*)(ra + head + 16 * i), vb = *(const u32x4*)(rb + head + 16 * i);
+            diff |= (va.x ^ vb.x) | (va.y ^ vb.y) | (va.z ^ vb.z) | (va.w ^ vb.w);
+        }
+        for (int i = tx; i < head + (a.w - tail0); i += 64) {
+            const int x = i < head ? i : tail0 + (i - head);
+            diff |= (unsigned)(ra[x] ^ rb[x]);
+        }
+    }
+    if (diff) a.same[z] = 0;
+}
 
 // v[j] = (float)S[reflect101(xs + j)], j = 0..NV-1, where xs = 4*m - 1 (so xs+1 is dword aligned)
 template <int NV>
@@ -906,6 +955,7 @@ __global__ __launch_bounds__(256) void tw_pyr_k3(PyrK3Args a)
 {
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // tx = lane: a wave is 64 consecutive 4-pixel groups
     const int ox = (blockIdx.x * 64 + tx) * 4;
+    if (second_image_same(a.same, (int)blockIdx.z)) return;  // workgroup-uniform
     const uint8_t* __restrict__ src = a.srcs[blockIdx.z];
     float* __restrict__ dst = a.dst + blockIdx.z * a.dst_zs;
     const bool in_w = ox < a.w;  // lanes past the row end stay active for the lane exchange, they only skip memory
@@ -1041,12 +1091,14 @@ struct PyrK3fArgs {
     float a0, a1;      // level 0's centre / side tap
     float b0, b1;      // level 1's
     int aligned4;
+    const unsigned* same = nullptr;  // as PyrK3Args: the image is skipped at BOTH levels
 };
 
 __device__ __forceinline__ void tw_pyr_k3f_body(const PyrK3fArgs& a, const int bx_, const int by_, const int bz_)
 {
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // tx = lane: a wave is 64 consecutive 4-pixel groups of level 1
     const int ox = (bx_ * 64 + tx) * 4;
+    if (second_image_same(a.same, bz_)) return;  // workgroup-uniform
     const uint8_t* __restrict__ src = a.srcs[bz_];
     const bool in_w = ox < a.w1;  // lanes past the row end stay active for the lane exchange, they only skip memory
     const int oy = by_ * 4 + ty;
@@ -1157,6 +1209,7 @@ struct PolyArgs {
     int w, h, ld;
     long long ps;  // plane stride (elements)
     PolyCoef c;
+    const unsigned* same = nullptr;  // as PyrK3Args: no expansion of a second image identical to its pair's first
 };
 
 #ifdef TW_VARIANTS  // A/B kernel (TW_POLY_VARIANT=0): only in `make VARIANTS=1` builds (libtwflow_variants.so)
@@ -1167,6 +1220,7 @@ __global__ __launch_bounds__(256) void tw_polyexp(PolyArgs a)
     const int tid = threadIdx.x;
     int bx, by, bz;
     xcd_remap(bx, by, bz);
+    if (second_image_same(a.same, bz)) return;  // workgroup-uniform
     const int x0 = bx * PE_TW, y0 = by * PE_TH;
     const float* __restrict__ src = a.src + bz * a.ps;
     float* __restrict__ dst = a.dst + bz * 5 * a.ps;
@@ -1307,6 +1361,7 @@ __device__ __forceinline__ void tw_polyexp_pk_body(const PolyArgs& a, const VGri
     const int tid = threadIdx.x;
     int bx, by, bz;
     xcd_remap_v(vg, vb, bx, by, bz);
+    if (second_image_same(a.same, bz)) return;  // workgroup-uniform
     const int x0 = bx * PE_TW, y0 = by * TH;
     const float* __restrict__ src = a.src + bz * a.ps;
     float* __restrict__ dst = a.dst + bz * 5 * a.ps;
@@ -2135,7 +2190,7 @@ constexpr int FI_TH = 5, FI_SC = 190, FI_PITCH = 192;
 // LDS each — a workgroup's barrier phases then overlap with the other workgroup's, for 1.47 x instead of 1.19 x halo columns
 constexpr int FI_SC_512 = 94, FI_PITCH_512 = 96;
 struct FlowIterArgs {
-    const float* R;        // pair z: R0 = R + (2z)*5ps, R1 = R0 + 5ps
+    const float* R;        // pair z: R0 = R + (2z)*5ps, R1 = R0 + 5ps (R1 = R0 where same[z] is set)
     const float* flow_in;  // pair z: 2 planes at flow_in + z*2*fps_in
     float* flow_out;       // pair z: 2 planes at flow_out + z*2*fps_out
     int w, h, ld;
@@ -2155,6 +2210,9 @@ struct FlowIterArgs {
     unsigned long long* dbg;  // measurement builds (TW_VARIANTS): s_memtime stamps of steps 40-47 of the first 32 workgroups
     int dbg_skip;  // measurement builds (TW_VARIANTS, TW_FI_SKIP): 1 no C (combine), 4 no H, 8 no S — timing only
     WinCoef c;
+    const unsigned* same;  // tw_pair_same's flags of the launch's pairs: pair z's second expansion was not computed and IS its
+                           // first (identical images); null: every pair has both.  (No `= nullptr` as PolyArgs has: the
+                           // struct's one construction site, launch_flow_iter, memsets it, which wants a trivial type)
 };
 
 #ifdef TW_VARIANTS
@@ -2243,7 +2301,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     (void)fi_blin;
     const WinCoef& c = a.c;
     const float* __restrict__ R0 = a.R + (long long)(2 * z) * 5 * a.ps;
-    const float* __restrict__ R1 = R0 + 5 * a.ps;
+    // one scalar select ahead of the resource.  R1 == R0 for a flagged pair ON PURPOSE: both are only ever read, so the two
+    // __restrict__ pointers may alias
+    const float* __restrict__ R1 = R0 + ((a.same && a.same[z]) ? 0 : 5 * a.ps);
     const float* __restrict__ fin = a.flow_in + (long long)z * 2 * a.fps_in;
     float* __restrict__ fout = a.flow_out + (long long)z * 2 * a.fps_out;
     // thread = (row cr of a chunk, strip column cc) in phase C and = (plane cr, column cc) in phase A (TH == 5 planes)

@@ -72,7 +72,7 @@ SYMBOLS = [
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
-    "tw_debug_blur_plan",
+    "tw_debug_blur_plan", "tw_debug_same_flags",
 ]
 
 
@@ -201,6 +201,8 @@ def _bind(path):
     L.tw_debug_flow_iter_plan.restype = C.c_int
     L.tw_debug_blur_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.tw_debug_blur_plan.restype = C.c_int
+    L.tw_debug_same_flags.argtypes = [vp, C.POINTER(C.c_uint), C.c_int]
+    L.tw_debug_same_flags.restype = C.c_int
     return L
 
 
@@ -599,6 +601,17 @@ class Engine:
         if n != 9:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_blur_plan(%d, %d, %d, %d) returned %d" % (w, h, level, npairs, n))
         return BlurPlan(self._L.tw_debug_family_name(v[0]).decode(), *v[1:8], bool(v[8]))
+
+    def same_flags(self):
+        """tw_pair_same's flags of the batch enqueued last, one per pair: 1 where the pair's second image is byte for byte
+        its first (twflow_debug.h: tw_debug_same_flags); all 0 when no tw_pair_same ran (TW_SAME_IMAGE=0, a single pair).
+        A debug hook on engine-level state: it describes whichever batch the engine enqueued LAST (a full batch, or the
+        one a wait() flushed), not a ticket — ask before the next submit fills another batch.  Waits for that batch."""
+        v = (C.c_uint * self.slots)()
+        n = self._L.tw_debug_same_flags(self._h, v, self.slots)
+        if n < 0:
+            raise TwError(TW_E_DEVICE, "tw_debug_same_flags returned %d" % n)
+        return [int(v[i]) for i in range(n)]
 
     def launch_counts(self, reset=False):
         """{family name: launches} since creation / the last reset, every family (twflow_debug.h)."""
