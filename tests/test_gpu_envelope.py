@@ -254,7 +254,7 @@ def test_one_step_past_the_bound_is_refused_everywhere(twflow):
     """Sizes the old w * h <= 2^28 bound admitted (or nearly) and the plane offsets cannot address: every host submit
     flavour and every stage entry point answers TW_E_UNSUPPORTED before it reads an input (the arrays are zero pages
     nobody touches), and 32769 in either dimension is TW_E_BAD_PARAMETER.  tw_submit_dev[_flow[_init]] runs the same
-    submit_common check first, before it could dereference a device pointer."""
+    Submit::check_arguments first, before it could dereference a device pointer."""
     L = twflow.lib()
     past = [(13108, 16384), (28198, 7616), (16385, 16383), (16384, 16384), (13082, 16385)]
     for h, w in past:

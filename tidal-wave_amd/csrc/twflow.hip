@@ -346,7 +346,7 @@ struct Ctx {
     size_t d_img_cap = 0;
     hipEvent_t ev_h2d = nullptr;
     // cold-start ramp (round 6): the copy stream is marked when a quarter and a half of a full batch's uploads have been
-    // queued (submit_common); a batch that is launched into an IDLE compute stream goes out in up to three pieces, each
+    // queued (Submit::mark_ramp); a batch that is launched into an IDLE compute stream goes out in up to three pieces, each
     // behind its own mark, instead of waiting for the last upload of the whole batch (flush_ctx)
     hipEvent_t ev_seg[2] = {nullptr, nullptr};
     int seg_at[2] = {0, 0};  // pairs queued when the mark was recorded
@@ -386,6 +386,23 @@ struct Ctx {
     FlowDst* h_fsrc = nullptr;
     char* d_istage = nullptr;
     size_t d_istage_cap = 0;
+
+    // A new batch in this context: what describes the batch starts over; the device and pinned regions, their capacities
+    // and the events survive.
+    void begin_batch(int width, int height, int span_, double threshold_, int64_t first)
+    {
+        jobs.clear();
+        launched = false;
+        pending = 0;
+        w = width;
+        h = height;
+        span = span_;
+        threshold = threshold_;
+        any_host = any_png = any_fout = any_fout_host = any_init = any_init_host = false;
+        filt_slot = 0;
+        nseg = 0;
+        first_ticket = first;
+    }
 };
 
 struct ProfPair {
@@ -1721,6 +1738,10 @@ void launch_area_init(tw_engine* e, hipStream_t st, const Plan* pl, float* flow,
     }
 }
 
+// a flow field's rows in either layout: bytes of a row of w pixels, rows of a field of h pixel rows
+size_t flow_row_bytes(int w, int layout) { return (size_t)w * (layout == TW_FLOW_INTERLEAVED ? 8 : 4); }
+size_t flow_rows(int h, int layout) { return (size_t)h * (layout == TW_FLOW_INTERLEAVED ? 1 : 2); }
+
 // bytes of one pair's slot in a context's flow staging: the field as dense rows of either layout
 size_t flow_stage_slot(int w, int h) { return ((size_t)w * h * 8 + 255) / 256 * 256; }
 
@@ -1752,7 +1773,7 @@ tw_status export_chunk(tw_engine* e, Ctx& c, hipStream_t st, const LevelPlan& L,
     for (int j = j0; j < j0 + nc; j++) {
         const Job& jb = c.jobs[j];
         if (!jb.fout_host) continue;
-        const size_t row = (size_t)L.w * (jb.fout.layout ? 8 : 4), rows = (size_t)L.h * (jb.fout.layout ? 1 : 2);
+        const size_t row = flow_row_bytes(L.w, jb.fout.layout), rows = flow_rows(L.h, jb.fout.layout);
         const char* src = c.d_fstage + fslot * j;
         if ((size_t)jb.fout.pitch == row)  // dense rows: one plain transfer (the DMA engines)
             TW_HIP(e, hipMemcpyAsync(jb.fout.data, src, row * rows, hipMemcpyDeviceToHost, e->d2h_stream));
@@ -1801,7 +1822,7 @@ FlowDst flow_table_row(const void* data, ptrdiff_t pitch, int layout, char* stag
 {
     FlowDst d;
     d.p = !data ? nullptr : staged ? staged : (char*)data;
-    d.pitch = staged ? (long long)w * (layout ? 8 : 4) : (long long)pitch;
+    d.pitch = staged ? (long long)flow_row_bytes(w, layout) : (long long)pitch;
     d.layout = layout;
     d.pad = 0;
     return d;
@@ -1827,7 +1848,7 @@ struct LevelChunk {
 
 // Everything flush_ctx enqueues for one batch: the steps in the order flush_ctx calls them, then the three schedules
 // of the level loop (enqueue_levels) and the launches they share.  Every step returns on the first error status; the
-// batch's context then stays un-launched and submit_common / tw_wait drop it.
+// batch's context then stays un-launched and Submit / tw_wait drop it (drop_batch).
 struct BatchEnqueue {
     tw_engine* const e;
     Ctx& c;
@@ -1905,7 +1926,7 @@ struct BatchEnqueue {
     {
         c.copy_ops_at_flush = e->copy_ops;
         if (!c.any_host && !c.any_init_host) return TW_OK;
-        // the uploads (images, and host initial flow fields) were queued on the copy stream as the jobs came in (submit_common)
+        // the uploads (images, and host initial flow fields) were queued on the copy stream as the jobs came in (Submit)
         TW_HIP(e, hipEventRecord(c.ev_h2d, e->copy_stream));
         // cold-start ramp: nothing of an earlier batch is still running on the compute stream (the first batch after a
         // pause, or a pipeline the host cannot keep filled) — the pairs whose uploads are already marked start now, the
@@ -2650,13 +2671,12 @@ size_t png_rows_bytes(int width, int height, int ch) { return (size_t)height * (
 tw_status check_flow_field(tw_engine* e, const void* data, ptrdiff_t pitch, int layout, int w, int h, const char* what,
                            int* kind)
 {
-    const size_t row = (size_t)w * (layout == TW_FLOW_INTERLEAVED ? 8 : 4);
+    const size_t row = flow_row_bytes(w, layout);
     if (!data || (layout != TW_FLOW_PLANAR && layout != TW_FLOW_INTERLEAVED) || pitch < (ptrdiff_t)row || pitch % 4 != 0) {
         e->err = std::string("bad ") + what + " (null data, unknown layout, or a pitch below the row or not a multiple of 4)";
         return TW_E_BAD_PARAMETER;
     }
-    const size_t rows = (size_t)h * (layout == TW_FLOW_INTERLEAVED ? 1 : 2);
-    const size_t extent = (size_t)pitch * (rows - 1) + row;
+    const size_t extent = (size_t)pitch * (flow_rows(h, layout) - 1) + row;
     if (pin_registry().covers(data, extent)) {
         *kind = 1;
         return TW_OK;
@@ -2699,69 +2719,137 @@ tw_status check_flow_out(tw_engine* e, const tw_flow_out* o, int w, int h, bool*
     return TW_OK;
 }
 
-// ch_a / ch_b > 0 (tw_submit_png8): that host image is `height` filtered PNG rows of 1 + width * ch bytes
-// fo (tw_submit_*_flow): where the pair's final flow goes, null for the plain calls
-tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, const void* d_a, const void* d_b,
-                        int width, int height, ptrdiff_t stride, int span, double threshold, tw_ticket* ticket,
-                        int ch_a = 0, int ch_b = 0, const tw_flow_out* fo = nullptr, const tw_flow_in* fi = nullptr)
+// What a tw_submit_* entry point hands over: one pair as host images (h_a, h_b) or device images (d_a, d_b).
+struct Submission {
+    const uint8_t *h_a = nullptr, *h_b = nullptr;
+    const void *d_a = nullptr, *d_b = nullptr;
+    int width = 0, height = 0;
+    ptrdiff_t stride = 0;
+    int span = 0;
+    double threshold = 0;
+    int ch_a = 0, ch_b = 0;  // > 0 (tw_submit_png8): that image is `height` filtered PNG rows of 1 + width * ch bytes
+    const tw_flow_out* fo = nullptr;  // tw_submit_*_flow: where the pair's final flow goes, null for the plain calls
+    const tw_flow_in* fi = nullptr;   // tw_submit_*_flow_init: the field the pair starts from, null for a zero start
+    tw_ticket* ticket = nullptr;
+};
+
+// A batch that cannot be launched (unsupported plan, out of memory) is dropped, not retried by every later submit or
+// wait, so that the engine stays usable; its tickets answer "unknown ticket".
+void drop_batch(Ctx& c)
 {
-    if (!e) return TW_E_BAD_PARAMETER;
-    e->err.clear();
-    tw_status r = check_dims(e, width, height);
-    if (r) return r;
-    if (span < 0 || stride < width || (!h_a && !d_a) || (!h_b && !d_b)) {
-        e->err = "bad argument";
-        return TW_E_BAD_PARAMETER;
+    c.pending = 0;
+    c.jobs.clear();
+}
+
+// One submission on its way into a batch: the steps in the order submit() calls them.  Every step returns on the first
+// error status, and what it leaves behind then is the step's own business: nothing before book_job books the job, so a
+// refused submission consumes no ticket and leaves the open batch as it was.
+struct Submit {
+    tw_engine* const e;
+    const Submission& s;
+    const bool png;
+    const long long eff_stride;  // host images are staged densely; device images are read in place with their stride
+    Ctx* c = nullptr;
+    bool fo_host = false;
+    int fi_kind = 0;  // tw_submit_*_flow_init: 0 device memory (read in place), 1 page-locked, 2 other host memory
+    Job jb;
+
+    Submit(tw_engine* e_, const Submission& s_)
+        : e(e_), s(s_), png(s_.ch_a > 0 || s_.ch_b > 0), eff_stride(s_.h_a ? (long long)s_.width : (long long)s_.stride)
+    {
     }
-    const bool png = ch_a > 0 || ch_b > 0;
-    if (png) {
-        if (!h_a || !h_b || ch_a < 0 || ch_a > 4 || ch_b < 0 || ch_b > 4 || stride != width) {
+
+    // bytes of a filtered image's slot in Ctx::d_filt
+    size_t filt_need() const { return (png_rows_bytes(s.width, s.height, std::max(s.ch_a, s.ch_b)) + 255) / 256 * 256; }
+
+    // ---- host memory to dense rows at dst, on the copy stream: `rows` rows of `row` bytes, `pitch` apart ----------
+    // Page-locked caller memory (tw_host_alloc / tw_host_register): DMA straight from it.  The caller keeps the block
+    // unchanged until tw_wait() of this ticket returns.  Dense rows are a plain 1-D transfer (the DMA engines; a
+    // pitched 2-D copy may run as a blit kernel on the CUs the flow kernels are using).
+    tw_status upload_in_place(void* dst, const void* src, size_t pitch, size_t row, size_t rows)
+    {
+        if (pitch == row) TW_HIP(e, hipMemcpyAsync(dst, src, row * rows, hipMemcpyHostToDevice, e->copy_stream));
+        else TW_HIP(e, hipMemcpy2DAsync(dst, row, src, pitch, row, rows, hipMemcpyHostToDevice, e->copy_stream));
+        return TW_OK;
+    }
+
+    // Pageable memory: the caller may reuse it as soon as this call returns, and the runtime is never handed a pointer
+    // it would have to page-lock on the fly: the rows go through the engine's own pinned bounce buffer,
+    // in groups of whole rows of at most BOUNCE_CHUNK bytes (at least one row), and each copy is over before the next
+    // one starts (the host layer hands over page-locked arenas; this is the slow, always-correct path)
+    tw_status upload_through_bounce(char* dst, const void* src, size_t pitch, size_t row, size_t rows)
+    {
+        const size_t per = std::max<size_t>(1, BOUNCE_CHUNK / row);  // rows per bounce transfer
+        TW_TRY(bounce_reserve(e, std::min(rows, per) * row));
+        for (size_t r0 = 0; r0 < rows; r0 += per) {
+            const size_t nr = std::min(per, rows - r0);
+            for (size_t y = 0; y < nr; y++) memcpy(e->h_bounce + y * row, (const char*)src + (r0 + y) * pitch, row);
+            TW_HIP(e, hipMemcpyAsync(dst + r0 * row, e->h_bounce, nr * row, hipMemcpyHostToDevice, e->copy_stream));
+            TW_HIP(e, hipStreamSynchronize(e->copy_stream));
+        }
+        return TW_OK;
+    }
+
+    // ---- the steps of a submission, in order ---------------------------------------------------------------
+
+    // no HIP call, nothing booked
+    tw_status check_arguments()
+    {
+        TW_TRY(check_dims(e, s.width, s.height));
+        const bool png_ok = s.h_a && s.h_b && s.ch_a >= 0 && s.ch_a <= 4 && s.ch_b >= 0 && s.ch_b <= 4;
+        if (s.span < 0 || s.stride < s.width || (!s.h_a && !s.d_a) || (!s.h_b && !s.d_b) ||
+            (png && (!png_ok || s.stride != s.width))) {
             e->err = "bad argument";
             return TW_E_BAD_PARAMETER;
         }
+        if (!png) return TW_OK;
         // the filter type byte of every row (ISO/IEC 15948 §9.2: 0-4): checked here, on the host, so that the kernel
         // never has to answer for a damaged stream (libpng: "bad adaptive filter value" -> imread fails)
-        const uint8_t* img[2] = {h_a, h_b};
-        const int chs[2] = {ch_a, ch_b};
-        for (int q = 0; q < 2; q++) {
-            if (!chs[q]) continue;
-            const size_t rs = (size_t)width * (size_t)chs[q] + 1;
-            for (int y = 0; y < height; y++)
-                if (img[q][(size_t)y * rs] > 4) {
+        const uint8_t* img[2] = {s.h_a, s.h_b};
+        const int chs[2] = {s.ch_a, s.ch_b};
+        for (int q = 0; q < 2; q++)
+            for (int y = 0; chs[q] && y < s.height; y++)
+                if (img[q][(size_t)y * ((size_t)s.width * (size_t)chs[q] + 1)] > 4) {
                     e->err = "bad PNG filter type";
                     return TW_E_BAD_IMAGE_FORMAT;
                 }
+        return TW_OK;
+    }
+
+    // the fields, and what they need once per engine: before the open batch is looked at (a failure books nothing)
+    tw_status check_fields()
+    {
+        TW_HIP(e, hipSetDevice(e->device));
+        if (s.fo) {
+            TW_TRY(check_flow_out(e, s.fo, s.width, s.height, &fo_host));
+            if (!e->d_fdst) TW_HIP(e, hipMalloc((void**)&e->d_fdst, sizeof(FlowDst) * (size_t)e->cap + 256));
+            if (fo_host && !e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
         }
+        if (s.fi) {
+            TW_TRY(check_flow_field(e, s.fi->data, s.fi->pitch, s.fi->layout, s.width, s.height, "initial flow field",
+                                    &fi_kind));
+            if (!e->d_fsrc) TW_HIP(e, hipMalloc((void**)&e->d_fsrc, sizeof(FlowDst) * (size_t)e->cap + 256));
+        }
+        return TW_OK;
     }
-    const size_t filt_need = png ? (png_rows_bytes(width, height, std::max(ch_a, ch_b)) + 255) / 256 * 256 : 0;
-    TW_HIP(e, hipSetDevice(e->device));
-    bool fo_host = false;
-    if (fo) {
-        TW_TRY(check_flow_out(e, fo, width, height, &fo_host));
-        // what the destinations need, made once per engine / context (a failure books nothing)
-        if (!e->d_fdst) TW_HIP(e, hipMalloc((void**)&e->d_fdst, sizeof(FlowDst) * (size_t)e->cap + 256));
-        if (fo_host && !e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
+
+    // a batch is homogeneous: same size, span, threshold and row stride (and a filtered image larger than the slots
+    // this batch's earlier filtered images were given starts a new batch)
+    bool fits(const Ctx& b) const
+    {
+        return !b.launched && !b.jobs.empty() && b.w == s.width && b.h == s.height && b.span == s.span &&
+               b.threshold == s.threshold && b.jobs[0].stride == eff_stride && (int)b.jobs.size() < e->cap &&
+               (!png || b.filt_slot == 0 || filt_need() <= b.filt_slot);
     }
-    int fi_kind = 0;  // tw_submit_*_flow_init: 0 device memory (read in place), 1 page-locked, 2 other host memory
-    if (fi) {
-        TW_TRY(check_flow_field(e, fi->data, fi->pitch, fi->layout, width, height, "initial flow field", &fi_kind));
-        if (!e->d_fsrc) TW_HIP(e, hipMalloc((void**)&e->d_fsrc, sizeof(FlowDst) * (size_t)e->cap + 256));
-    }
-    // host images are staged densely; device images are read in place with their own row stride
-    const long long eff_stride = h_a ? (long long)width : (long long)stride;
-    Ctx* c = &e->ctx[e->cur];
-    // a batch is homogeneous: same size, span, threshold and row stride
-    const bool open = !c->launched && !c->jobs.empty();
-    // (a filtered image larger than the slots this batch's earlier filtered images were given starts a new batch)
-    const bool fits = open && c->w == width && c->h == height && c->span == span && c->threshold == threshold &&
-                      c->jobs[0].stride == eff_stride && (int)c->jobs.size() < e->cap &&
-                      (!png || c->filt_slot == 0 || filt_need <= c->filt_slot);
-    if (!fits) {
-        if (open && (r = flush_ctx(e, *c))) {
-            // the open batch cannot run (unsupported plan, out of memory): drop it as tw_wait does, so that the
-            // engine stays usable; its tickets answer "unknown ticket"
-            c->pending = 0;
-            c->jobs.clear();
+
+    // c = the context whose open batch takes the pair: the current one's if the pair fits, otherwise a new batch
+    tw_status open_batch()
+    {
+        c = &e->ctx[e->cur];
+        if (fits(*c)) return TW_OK;
+        const tw_status r = flush_ctx(e, *c);  // (launches an open batch, nothing else)
+        if (r) {
+            drop_batch(*c);
             return r;
         }
         if (c->pending > 0) {  // still owed to the caller: move on to the next context
@@ -2770,178 +2858,167 @@ tw_status submit_common(tw_engine* e, const uint8_t* h_a, const uint8_t* h_b, co
             e->cur = nxt;
             c = &e->ctx[nxt];
         }
-        c->jobs.clear();
-        c->launched = false;
-        c->pending = 0;
-        c->w = width;
-        c->h = height;
-        c->span = span;
-        c->threshold = threshold;
-        c->any_host = false;
-        c->any_png = false;
-        c->any_fout = false;
-        c->any_fout_host = false;
-        c->any_init = false;
-        c->any_init_host = false;
-        c->filt_slot = 0;
-        c->nseg = 0;
-        c->first_ticket = e->next_ticket;
+        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket);
+        return TW_OK;
     }
-    if (fo) {
-        if (!c->h_fdst) TW_HIP(e, hipHostMalloc((void**)&c->h_fdst, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
-        if (!c->ev_fexp) TW_HIP(e, hipEventCreateWithFlags(&c->ev_fexp, hipEventDisableTiming));
-        if (!c->ev_d2h) TW_HIP(e, hipEventCreateWithFlags(&c->ev_d2h, hipEventDisableTiming));
+
+    // what the fields need once per context
+    tw_status reserve_context_tables()
+    {
+        if (s.fo) {
+            if (!c->h_fdst) TW_HIP(e, hipHostMalloc((void**)&c->h_fdst, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
+            if (!c->ev_fexp) TW_HIP(e, hipEventCreateWithFlags(&c->ev_fexp, hipEventDisableTiming));
+            if (!c->ev_d2h) TW_HIP(e, hipEventCreateWithFlags(&c->ev_d2h, hipEventDisableTiming));
+        }
+        if (s.fi && !c->h_fsrc) TW_HIP(e, hipHostMalloc((void**)&c->h_fsrc, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
+        return TW_OK;
     }
-    if (fi && !c->h_fsrc) TW_HIP(e, hipHostMalloc((void**)&c->h_fsrc, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
-    if (fi && fi_kind != 0) {
-        // a host field: to this context's staging slot on the copy stream, queued before the pair's ramp mark below —
-        // DMA-ed in place from a page-locked block (the caller keeps it until tw_wait), through the engine's pinned bounce
-        // buffer from any other memory (copied before this call returns, as pageable images are)
-        const size_t fslot = flow_stage_slot(width, height);
-        // (grows only on the first host field of a batch — one size per batch; this context's earlier batches are waited)
+
+    // a host field: to this context's staging slot on the copy stream, queued before the pair's ramp mark (a device
+    // field is read in place)
+    tw_status stage_init_field()
+    {
+        if (!s.fi || fi_kind == 0) return TW_OK;
+        const size_t fslot = flow_stage_slot(s.width, s.height);
+        // (grows only on the first host field of a batch: one size per batch; this context's earlier ones are waited)
         TW_TRY(grow_device(e, c->d_istage, c->d_istage_cap, fslot * e->cap, fslot * e->cap + 256, e->copy_stream));
         char* dst = c->d_istage + fslot * c->jobs.size();
-        const size_t row = (size_t)width * (fi->layout ? 8 : 4), rows = (size_t)height * (fi->layout ? 1 : 2);
-        if (fi_kind == 1) {
-            if ((size_t)fi->pitch == row)
-                TW_HIP(e, hipMemcpyAsync(dst, fi->data, row * rows, hipMemcpyHostToDevice, e->copy_stream));
-            else
-                TW_HIP(e, hipMemcpy2DAsync(dst, row, fi->data, (size_t)fi->pitch, row, rows, hipMemcpyHostToDevice,
-                                           e->copy_stream));
-        } else {
-            const size_t per = std::max<size_t>(1, BOUNCE_CHUNK / row);  // rows per bounce transfer
-            TW_TRY(bounce_reserve(e, std::min(rows, per) * row));
-            for (size_t r0 = 0; r0 < rows; r0 += per) {
-                const size_t nr = std::min(per, rows - r0);
-                for (size_t y = 0; y < nr; y++)
-                    memcpy(e->h_bounce + y * row, (const char*)fi->data + (r0 + y) * (size_t)fi->pitch, row);
-                TW_HIP(e, hipMemcpyAsync(dst + r0 * row, e->h_bounce, nr * row, hipMemcpyHostToDevice, e->copy_stream));
-                TW_HIP(e, hipStreamSynchronize(e->copy_stream));
-            }
-        }
+        const size_t row = flow_row_bytes(s.width, s.fi->layout), rows = flow_rows(s.height, s.fi->layout);
+        TW_TRY(fi_kind == 1 ? upload_in_place(dst, s.fi->data, (size_t)s.fi->pitch, row, rows)
+                            : upload_through_bounce(dst, s.fi->data, (size_t)s.fi->pitch, row, rows));
         e->copy_ops++;
+        return TW_OK;
     }
-    Job jb;
-    jb.stride = eff_stride;
-    if (h_a) {
-        const size_t npx = staged_image_bytes(width, height);
-        const size_t need = npx * 2 * e->cap;
-        const size_t j = c->jobs.size();
+
+    // host images go to the pair's two slots of d_img; device inputs only fill the job
+    tw_status stage_images()
+    {
+        jb.stride = eff_stride;
+        jb.d_a = (const uint8_t*)s.d_a;
+        jb.d_b = (const uint8_t*)s.d_b;
+        if (!s.h_a) return TW_OK;
+        const size_t npx = staged_image_bytes(s.width, s.height);
         // (grows only on the first job of a batch: all jobs of a batch have one size)
-        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, need, need + 256, e->copy_stream));
-        uint8_t* dst_a = c->d_img + npx * (2 * j);
-        uint8_t* dst_b = c->d_img + npx * (2 * j + 1);
-        if (png) {
-            // tw_submit_png8: filtered rows go to the batch's d_filt slots (tw_png_unfilter writes d_img when the batch
-            // is launched), plain gray images of the pair straight to d_img
-            if (c->filt_slot == 0) {
-                // first filtered image of this batch: slots as large as the region allows, at least what it needs
-                const size_t have = c->d_filt_cap / (2 * (size_t)e->cap) / 256 * 256;
-                const size_t slot = std::max(filt_need, have);
-                // 256 bytes of slack on either side: tw_png_unfilter fetches whole 16-byte groups and may read a few
-                // bytes before the first and after the last row of an image
-                const size_t filt_bytes = slot * 2 * (size_t)e->cap;
-                r = grow_device(e, c->d_filt_raw, c->d_filt_cap, filt_bytes, filt_bytes + 512, e->copy_stream);
-                c->d_filt = c->d_filt_raw ? c->d_filt_raw + 256 : nullptr;  // (whatever became of the region)
-                if (r) return r;
-                // (only now — a failed synchronise / allocation above leaves filt_slot at 0, so that the next
-                // filtered image of this batch tries again instead of copying to a null region)
-                c->filt_slot = slot;
-            }
-            if (!c->d_filt) {
-                e->err = "tw_submit_png8: no device region for the filtered rows";
-                return TW_E_NOMEM;
-            }
-            const uint8_t* src[2] = {h_a, h_b};
-            const int chs[2] = {ch_a, ch_b};
-            uint8_t* gray_dst[2] = {dst_a, dst_b};
-            for (int q = 0; q < 2; q++) {
-                const size_t nb = chs[q] ? png_rows_bytes(width, height, chs[q]) : (size_t)width * height;
-                uint8_t* dst = chs[q] ? c->d_filt + c->filt_slot * (2 * j + q) : gray_dst[q];
-                if (pin_registry().covers(src[q], nb)) {
-                    TW_HIP(e, hipMemcpyAsync(dst, src[q], nb, hipMemcpyHostToDevice, e->copy_stream));
-                    continue;
-                }
-                // pageable memory: the caller may reuse it as soon as this call returns, and the runtime is never handed
-                // a pointer it would have to page-lock on the fly — the image goes through the engine's own pinned bounce
-                // buffer and the copy is over before the next one starts (the host layer hands over page-locked arenas;
-                // this is the slow, always-correct path)
-                TW_TRY(bounce_reserve(e, nb));
-                memcpy(e->h_bounce, src[q], nb);
-                TW_HIP(e, hipMemcpyAsync(dst, e->h_bounce, nb, hipMemcpyHostToDevice, e->copy_stream));
-                TW_HIP(e, hipStreamSynchronize(e->copy_stream));
-            }
-            jb.png_ch[0] = ch_a;
-            jb.png_ch[1] = ch_b;
-            c->any_png = true;
-        } else {
-        const size_t span_bytes = (size_t)stride * (size_t)(height - 1) + (size_t)width;
-        if (pin_registry().covers(h_a, span_bytes) && pin_registry().covers(h_b, span_bytes)) {
-            // page-locked caller memory (tw_host_alloc / tw_host_register): DMA straight from it.  The caller keeps
-            // the buffers unchanged until tw_wait() of this ticket returns.
-            if (stride == width) {
-                // dense rows: plain 1-D transfers (the DMA engines; a pitched 2-D copy may run as a blit kernel on
-                // the CUs the flow kernels are using)
-                TW_HIP(e, hipMemcpyAsync(dst_a, h_a, (size_t)width * height, hipMemcpyHostToDevice, e->copy_stream));
-                TW_HIP(e, hipMemcpyAsync(dst_b, h_b, (size_t)width * height, hipMemcpyHostToDevice, e->copy_stream));
-            } else {
-                TW_HIP(e, hipMemcpy2DAsync(dst_a, (size_t)width, h_a, (size_t)stride, (size_t)width, (size_t)height,
-                                           hipMemcpyHostToDevice, e->copy_stream));
-                TW_HIP(e, hipMemcpy2DAsync(dst_b, (size_t)width, h_b, (size_t)stride, (size_t)width, (size_t)height,
-                                           hipMemcpyHostToDevice, e->copy_stream));
-            }
-        } else {
-            TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, need));
-            uint8_t* da = c->h_img + npx * (2 * j);
-            uint8_t* db = c->h_img + npx * (2 * j + 1);
-            for (int y = 0; y < height; y++) {
-                memcpy(da + (size_t)y * width, h_a + (size_t)y * stride, width);
-                memcpy(db + (size_t)y * width, h_b + (size_t)y * stride, width);
-            }
-            // both images of the pair in one transfer, queued now: it overlaps the caller's next submit and
-            // whatever the compute stream is still doing for the previous batch
-            TW_HIP(e, hipMemcpyAsync(dst_a, da, npx * 2, hipMemcpyHostToDevice, e->copy_stream));
-        }
-        }  // !png
-        jb.h_a = h_a;
-        jb.h_b = h_b;
+        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, npx * 2 * e->cap, npx * 2 * e->cap + 256, e->copy_stream));
+        TW_TRY(png ? stage_png_rows(npx) : stage_gray_pair(npx));
+        jb.h_a = s.h_a;
+        jb.h_b = s.h_b;
         c->any_host = true;
         e->copy_ops++;
-    } else {
-        jb.d_a = (const uint8_t*)d_a;
-        jb.d_b = (const uint8_t*)d_b;
+        return TW_OK;
     }
-    if (h_a && !png && e->ramp && e->cap >= 64 && c->nseg < 2) {
-        // cold-start ramp: mark the copy stream behind the first quarter / half of a full batch's uploads
-        // (before the job is booked: a failure here leaves the batch as it was)
+
+    // tw_submit_png8: filtered rows go to the batch's d_filt slots (tw_png_unfilter writes d_img when the batch is
+    // launched), plain gray images of the pair straight to d_img
+    tw_status stage_png_rows(size_t npx)
+    {
+        const size_t j = c->jobs.size();
+        if (c->filt_slot == 0) {
+            // first filtered image of this batch: slots as large as the region allows, at least what it needs
+            const size_t slot = std::max(filt_need(), c->d_filt_cap / (2 * (size_t)e->cap) / 256 * 256);
+            // 256 bytes of slack on either side: tw_png_unfilter fetches whole 16-byte groups and may read a few
+            // bytes before the first and after the last row of an image
+            const size_t nbytes = slot * 2 * (size_t)e->cap;
+            const tw_status r = grow_device(e, c->d_filt_raw, c->d_filt_cap, nbytes, nbytes + 512, e->copy_stream);
+            c->d_filt = c->d_filt_raw ? c->d_filt_raw + 256 : nullptr;  // (whatever became of the region)
+            if (r) return r;
+            // (only now — a failed synchronise / allocation above leaves filt_slot at 0, so that the next
+            // filtered image of this batch tries again instead of copying to a null region)
+            c->filt_slot = slot;
+        }
+        if (!c->d_filt) {
+            e->err = "tw_submit_png8: no device region for the filtered rows";
+            return TW_E_NOMEM;
+        }
+        const uint8_t* src[2] = {s.h_a, s.h_b};
+        const int chs[2] = {s.ch_a, s.ch_b};
+        for (int q = 0; q < 2; q++) {
+            // an image is handed over as ONE row: it goes through the bounce buffer whole, whatever its size
+            const size_t nb = chs[q] ? png_rows_bytes(s.width, s.height, chs[q]) : (size_t)s.width * s.height;
+            uint8_t* dst = chs[q] ? c->d_filt + c->filt_slot * (2 * j + q) : c->d_img + npx * (2 * j + q);
+            TW_TRY(pin_registry().covers(src[q], nb) ? upload_in_place(dst, src[q], nb, nb, 1)
+                                                     : upload_through_bounce((char*)dst, src[q], nb, nb, 1));
+        }
+        jb.png_ch[0] = s.ch_a;
+        jb.png_ch[1] = s.ch_b;
+        c->any_png = true;
+        return TW_OK;
+    }
+
+    tw_status stage_gray_pair(size_t npx)
+    {
+        const size_t at = npx * 2 * c->jobs.size();  // the pair's two slots, in d_img and in h_img
+        uint8_t *dst_a = c->d_img + at, *dst_b = dst_a + npx;
+        const size_t w = (size_t)s.width, h = (size_t)s.height, span_bytes = (size_t)s.stride * (h - 1) + w;
+        if (pin_registry().covers(s.h_a, span_bytes) && pin_registry().covers(s.h_b, span_bytes)) {
+            TW_TRY(upload_in_place(dst_a, s.h_a, (size_t)s.stride, w, h));
+            return upload_in_place(dst_b, s.h_b, (size_t)s.stride, w, h);
+        }
+        // pageable: not through the bounce buffer — the pair is copied to its own slots of the context's pinned ring
+        // (nothing to wait for) and goes up as one transfer of both images, queued now: it overlaps the caller's next
+        // submit and whatever the compute stream is still doing for the previous batch
+        TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, npx * 2 * e->cap));
+        uint8_t* da = c->h_img + at;
+        for (size_t y = 0; y < h; y++) {
+            memcpy(da + y * w, s.h_a + y * (size_t)s.stride, w);
+            memcpy(da + npx + y * w, s.h_b + y * (size_t)s.stride, w);
+        }
+        TW_HIP(e, hipMemcpyAsync(dst_a, da, npx * 2, hipMemcpyHostToDevice, e->copy_stream));
+        return TW_OK;
+    }
+
+    // cold-start ramp: mark the copy stream behind the first quarter / half of a full batch's uploads
+    // (before the job is booked: a failure here leaves the batch as it was)
+    tw_status mark_ramp()
+    {
         const int sz = (int)c->jobs.size() + 1;
-        if (sz == e->cap / 4 || sz == e->cap / 2) {
+        if (s.h_a && !png && e->ramp && e->cap >= 64 && c->nseg < 2 && (sz == e->cap / 4 || sz == e->cap / 2)) {
             TW_HIP(e, hipEventRecord(c->ev_seg[c->nseg], e->copy_stream));
             c->seg_at[c->nseg++] = sz;
         }
+        return TW_OK;
     }
-    if (fo) {
-        jb.fout = *fo;
-        jb.fout_host = fo_host;
-        c->any_fout = true;
-        c->any_fout_host = c->any_fout_host || fo_host;
-    }
-    if (fi) {
-        jb.fin = *fi;
+
+    // from here on the submission cannot be refused: the job, its ticket
+    void book_job()
+    {
+        if (s.fo) jb.fout = *s.fo;
+        if (s.fi) jb.fin = *s.fi;
+        jb.fout_host = fo_host;  // (false, and fi_kind 0, without the field)
         jb.fin_staged = fi_kind != 0;
-        c->any_init = true;
+        c->any_fout = c->any_fout || s.fo;
+        c->any_fout_host = c->any_fout_host || fo_host;
+        c->any_init = c->any_init || s.fi;
         c->any_init_host = c->any_init_host || fi_kind != 0;
+        c->jobs.push_back(jb);
+        c->pending++;
+        if (s.ticket) *s.ticket = e->next_ticket;
+        e->next_ticket++;
     }
-    c->jobs.push_back(jb);
-    c->pending++;
-    if (ticket) *ticket = e->next_ticket;
-    e->next_ticket++;
-    if ((int)c->jobs.size() == e->cap && (r = flush_ctx(e, *c))) {
-        c->pending = 0;  // as above: a batch that cannot be launched is dropped, not retried by every later submit
-        c->jobs.clear();
+
+    tw_status launch_if_full()
+    {
+        const tw_status r = (int)c->jobs.size() == e->cap ? flush_ctx(e, *c) : TW_OK;
+        if (r) drop_batch(*c);
         return r;
     }
-    return TW_OK;
+};
+
+// Every tw_submit_* entry point: one pair into the engine's open batch, its uploads queued on the copy stream
+tw_status submit(tw_engine* e, const Submission& s)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    Submit b(e, s);
+    TW_TRY(b.check_arguments());
+    TW_TRY(b.check_fields());
+    TW_TRY(b.open_batch());
+    TW_TRY(b.reserve_context_tables());
+    TW_TRY(b.stage_init_field());
+    TW_TRY(b.stage_images());
+    TW_TRY(b.mark_ramp());
+    b.book_job();
+    return b.launch_if_full();
 }
 
 Ctx* find_ctx(tw_engine* e, tw_ticket t, int* idx)
@@ -3218,46 +3295,49 @@ tw_status tw_submit_u8(tw_engine* e, const uint8_t* expect, const uint8_t* targe
                        ptrdiff_t stride, int span, double threshold, tw_ticket* ticket)
 {
     if (!expect || !target) return TW_E_BAD_PARAMETER;
-    return submit_common(e, expect, target, nullptr, nullptr, width, height, stride, span, threshold, ticket);
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = stride, .span = span,
+                      .threshold = threshold, .ticket = ticket});
 }
 
+// (the png8 calls: two plain gray images, both channel counts 0, take the ordinary host path with stride == width)
 tw_status tw_submit_png8(tw_engine* e, const uint8_t* expect, int expect_channels, const uint8_t* target,
                          int target_channels, int width, int height, int span, double threshold, tw_ticket* ticket)
 {
-    if (expect_channels == 0 && target_channels == 0)  // two plain gray images: the ordinary host path
-        return submit_common(e, expect, target, nullptr, nullptr, width, height, width, span, threshold, ticket);
-    return submit_common(e, expect, target, nullptr, nullptr, width, height, width, span, threshold, ticket,
-                         expect_channels, target_channels);
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = width, .span = span,
+                      .threshold = threshold, .ch_a = expect_channels, .ch_b = target_channels, .ticket = ticket});
 }
 
 tw_status tw_submit_dev(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
                         ptrdiff_t stride, int span, double threshold, tw_ticket* ticket)
 {
     if (!d_expect || !d_target) return TW_E_BAD_PARAMETER;
-    return submit_common(e, nullptr, nullptr, d_expect, d_target, width, height, stride, span, threshold, ticket);
+    return submit(e, {.d_a = d_expect, .d_b = d_target, .width = width, .height = height, .stride = stride,
+                      .span = span, .threshold = threshold, .ticket = ticket});
 }
 
 tw_status tw_submit_u8_flow(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
                             ptrdiff_t stride, int span, double threshold, const tw_flow_out* out, tw_ticket* ticket)
 {
     if (!expect || !target) return TW_E_BAD_PARAMETER;
-    return submit_common(e, expect, target, nullptr, nullptr, width, height, stride, span, threshold, ticket, 0, 0, out);
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = stride, .span = span,
+                      .threshold = threshold, .fo = out, .ticket = ticket});
 }
 
 tw_status tw_submit_png8_flow(tw_engine* e, const uint8_t* expect, int expect_channels, const uint8_t* target,
                               int target_channels, int width, int height, int span, double threshold,
                               const tw_flow_out* out, tw_ticket* ticket)
 {
-    // (two plain gray images take the ordinary host path, as in tw_submit_png8)
-    return submit_common(e, expect, target, nullptr, nullptr, width, height, width, span, threshold, ticket,
-                         expect_channels, target_channels, out);
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = width, .span = span,
+                      .threshold = threshold, .ch_a = expect_channels, .ch_b = target_channels, .fo = out,
+                      .ticket = ticket});
 }
 
 tw_status tw_submit_dev_flow(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
                              ptrdiff_t stride, int span, double threshold, const tw_flow_out* out, tw_ticket* ticket)
 {
     if (!d_expect || !d_target) return TW_E_BAD_PARAMETER;
-    return submit_common(e, nullptr, nullptr, d_expect, d_target, width, height, stride, span, threshold, ticket, 0, 0, out);
+    return submit(e, {.d_a = d_expect, .d_b = d_target, .width = width, .height = height, .stride = stride,
+                      .span = span, .threshold = threshold, .fo = out, .ticket = ticket});
 }
 
 tw_status tw_submit_u8_flow_init(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
@@ -3265,16 +3345,17 @@ tw_status tw_submit_u8_flow_init(tw_engine* e, const uint8_t* expect, const uint
                                  const tw_flow_out* out, tw_ticket* ticket)
 {
     if (!expect || !target) return TW_E_BAD_PARAMETER;
-    return submit_common(e, expect, target, nullptr, nullptr, width, height, stride, span, threshold, ticket, 0, 0, out,
-                         init);
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = stride, .span = span,
+                      .threshold = threshold, .fo = out, .fi = init, .ticket = ticket});
 }
 
 tw_status tw_submit_png8_flow_init(tw_engine* e, const uint8_t* expect, int expect_channels, const uint8_t* target,
                                    int target_channels, int width, int height, int span, double threshold,
                                    const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
 {
-    return submit_common(e, expect, target, nullptr, nullptr, width, height, width, span, threshold, ticket,
-                         expect_channels, target_channels, out, init);
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = width, .span = span,
+                      .threshold = threshold, .ch_a = expect_channels, .ch_b = target_channels, .fo = out, .fi = init,
+                      .ticket = ticket});
 }
 
 tw_status tw_submit_dev_flow_init(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
@@ -3282,8 +3363,8 @@ tw_status tw_submit_dev_flow_init(tw_engine* e, const void* d_expect, const void
                                   const tw_flow_out* out, tw_ticket* ticket)
 {
     if (!d_expect || !d_target) return TW_E_BAD_PARAMETER;
-    return submit_common(e, nullptr, nullptr, d_expect, d_target, width, height, stride, span, threshold, ticket, 0, 0,
-                         out, init);
+    return submit(e, {.d_a = d_expect, .d_b = d_target, .width = width, .height = height, .stride = stride,
+                      .span = span, .threshold = threshold, .fo = out, .fi = init, .ticket = ticket});
 }
 
 tw_status tw_flush(tw_engine* e)
@@ -3305,9 +3386,7 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
     TW_HIP(e, hipSetDevice(e->device));
     tw_status r;
     if (!c->launched && (r = flush_ctx(e, *c))) {
-        // the batch cannot run: drop it so that the engine stays usable
-        c->pending = 0;
-        c->jobs.clear();
+        drop_batch(*c);
         return r;
     }
     hipError_t herr = hipEventSynchronize(c->ev_done);
@@ -3413,13 +3492,7 @@ tw_status tw_flow_u8(tw_engine* e, const uint8_t* expect, const uint8_t* target,
     size_t need = 0;
     for (int q = 0; q < 2; q++)
         if (dst[q] && !pin_registry().covers(dst[q], plane)) need += plane;
-    if (need > e->h_bounce_cap) {
-        if (e->h_bounce) (void)hipHostFree(e->h_bounce);
-        e->h_bounce = nullptr;
-        e->h_bounce_cap = 0;
-        TW_HIP(e, hipHostMalloc((void**)&e->h_bounce, need, hipHostMallocDefault));
-        e->h_bounce_cap = need;
-    }
+    if ((r = bounce_reserve(e, need))) return r;
     size_t off = 0;
     for (int q = 0; q < 2; q++) {
         if (!dst[q]) continue;
