@@ -105,8 +105,8 @@ const char* tw_last_error(const tw_engine* e);
 /* OpticalFlow::calculateInternal, /root/reference/src/opticalflow.h:49 / src/opticalflow.cpp:97-119:
  * dense flow of one 8-bit gray pair (row stride in bytes), planar flowx/flowy out (w*h floats each,
  * either may be NULL).  `seconds` = device compute time, the meaning of OpticalFlowStatus::time
- * (src/opticalflow.cpp:112-118).  Both images must already have equal size (the <=5 px reconcile of
- * src/opticalflow.cpp:52-68 is host-layer work). */
+ * (src/opticalflow.cpp:112-118).  Both images have one size here: the <= 5 px reconcile of
+ * src/opticalflow.cpp:52-68 is what the tw_submit_*_sized calls below do, on the device. */
 tw_status tw_flow_u8(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
                      ptrdiff_t stride, float* flowx, float* flowy, float* seconds);
 
@@ -205,6 +205,33 @@ tw_status tw_submit_png8_flow_init(tw_engine* e, const uint8_t* expect, int expe
 tw_status tw_submit_dev_flow_init(tw_engine* e, const void* d_expect, const void* d_target, int width, int height,
                                   ptrdiff_t stride, int span, double threshold, const tw_flow_in* init,
                                   const tw_flow_out* out, tw_ticket* ticket);
+
+/* Pairs of unequal size (OpticalFlow::calculate's rule, src/opticalflow.cpp:52-68; additive within ABI 4, detected by the
+ * symbols).  The tw_submit_*_sized calls are the tw_submit_*_flow_init calls plus a size (and, for gray images, a row
+ * stride) of the target's own.  `width, height` is the PAIR's size — the expected image's: the flow, init, out, the span
+ * grid, the vector coordinates and the batch's homogeneity all use it, and a reconciled pair joins the open batch of that
+ * size like any other pair.  A target that differs by at most 5 pixels in width and in height is resized to the pair's
+ * size on the device as cv::resize does it (8-bit, INTER_LINEAR: kernel tw_resize_u8) before anything else reads it; the
+ * result equals tw_submit_u8 on the host-resized target bit for bit.  abs(width - target_width) > 5 or abs(height -
+ * target_height) > 5 answers TW_E_DONT_MATCH_SIZE: nothing is queued, no ticket is consumed, the open batch stays as it
+ * was.  The target's size goes through the same size predicate as the pair's; target_stride < target_width answers
+ * TW_E_BAD_PARAMETER; the PNG call checks the filter type bytes of the target's rows at the target's row length.  With
+ * equal sizes the call IS the _flow_init call: the same launches, copies and events, no tw_resize_u8 launch, no staging
+ * (a device target whose stride differs from the expected image's is re-pitched by the same kernel).  `seconds` keeps its
+ * meaning: the resize runs where the uploads and tw_png_unfilter run and is not in it.  A device target is read when
+ * its batch launches and is never written. */
+tw_status tw_submit_u8_sized(tw_engine* e, const uint8_t* expect, int width, int height, ptrdiff_t stride,
+                             const uint8_t* target, int target_width, int target_height, ptrdiff_t target_stride,
+                             int span, double threshold, const tw_flow_in* init, const tw_flow_out* out,
+                             tw_ticket* ticket);
+tw_status tw_submit_png8_sized(tw_engine* e, const uint8_t* expect, int expect_channels, int width, int height,
+                               const uint8_t* target, int target_channels, int target_width, int target_height,
+                               int span, double threshold, const tw_flow_in* init, const tw_flow_out* out,
+                               tw_ticket* ticket);
+tw_status tw_submit_dev_sized(tw_engine* e, const void* d_expect, int width, int height, ptrdiff_t stride,
+                              const void* d_target, int target_width, int target_height, ptrdiff_t target_stride,
+                              int span, double threshold, const tw_flow_in* init, const tw_flow_out* out,
+                              tw_ticket* ticket);
 
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
@@ -319,6 +346,9 @@ tw_status tw_stage_pyr_fused01(tw_engine* e, const uint8_t* img, int w0, int h0,
  * 1 + w * channels bytes, channels 1-4; `waves` = 0 (the engine's choice for this width), 1, 4 or 16 waves per image. */
 tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels, int w, int h, int waves,
                                 uint8_t* gray);
+/* The size reconcile's kernel alone (tw_resize_u8): dense src (sw x sh) -> dense dst (dw x dh), cv::resize's 8-bit
+ * INTER_LINEAR.  Sizes more than 5 pixels apart answer TW_E_DONT_MATCH_SIZE. */
+tw_status tw_stage_resize_u8(tw_engine* e, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh);
 tw_status tw_stage_polyexp(tw_engine* e, const float* I, int w, int h, float* R5);
 tw_status tw_stage_update_matrices(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow2,
                                    int w, int h, float* M5);

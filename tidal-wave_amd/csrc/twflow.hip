@@ -328,7 +328,16 @@ struct Job {
     bool fout_host = false;              // ... page-locked host memory: through Ctx::d_fstage and the engine's d2h_stream
     tw_flow_in fin = {nullptr, 0, 0};    // tw_submit_*_flow_init: the pair's initial field (data null: zero start)
     bool fin_staged = false;             // ... host memory, uploaded to Ctx::d_istage as dense rows
+    // tw_submit_*_sized: the target's own size and row stride (the pair's when equal), and who resizes it to the pair's
+    // size (tw_resize_u8): RSZ_NONE nobody; RSZ_SUBMIT a gray host target, on the copy stream right behind its upload;
+    // RSZ_FLUSH_COPY a tw_submit_png8_sized target, on the copy stream behind its own tw_png_unfilter when the batch is
+    // launched; RSZ_FLUSH_DEV a device target (t_src: the caller's memory), on the compute stream in front of the pyramid
+    int tw = 0, th = 0;
+    long long tstride = 0;
+    int rkind = 0;
+    const uint8_t* t_src = nullptr;
 };
+enum { RSZ_NONE = 0, RSZ_SUBMIT = 1, RSZ_FLUSH_COPY = 2, RSZ_FLUSH_DEV = 3 };
 
 // One batch of pairs: host-side state that must outlive the asynchronous execution.
 struct Ctx {
@@ -386,6 +395,16 @@ struct Ctx {
     FlowDst* h_fsrc = nullptr;
     char* d_istage = nullptr;
     size_t d_istage_cap = 0;
+    // tw_submit_*_sized (all created on the first reconciled pair of this context): d_tsrc = `cap` slots of tsrc_slot bytes
+    // for host targets of up to (w + 5) x (h + 5) pixels at their own size (d_tsrc = d_tsrc_raw + 256), and tw_resize_u8's
+    // job tables, three of [cap] each — one entry per launch at submit time, the batch's PNG targets, the batch's device
+    // targets (three, because each is written while the one before may still be on its way to the device) — with the
+    // table of the PNG targets' own tw_png_unfilter launches
+    uint8_t *d_tsrc = nullptr, *d_tsrc_raw = nullptr;
+    size_t d_tsrc_cap = 0, tsrc_slot = 0;
+    ResizeJob *d_rsz = nullptr, *h_rsz = nullptr;  // [3 * cap]
+    PngJob *d_rpng = nullptr, *h_rpng = nullptr;   // [cap]
+    bool any_resize = false, any_resize_png = false, any_resize_dev = false;
 
     // A new batch in this context: what describes the batch starts over; the device and pinned regions, their capacities
     // and the events survive.
@@ -399,6 +418,7 @@ struct Ctx {
         span = span_;
         threshold = threshold_;
         any_host = any_png = any_fout = any_fout_host = any_init = any_init_host = false;
+        any_resize = any_resize_png = any_resize_dev = false;
         filt_slot = 0;
         nseg = 0;
         first_ticket = first;
@@ -588,6 +608,24 @@ namespace {
     } while (0)
 
 size_t staged_image_bytes(int w, int h);
+
+// One row of tw_resize_u8's job table: sw x sh at src -> dw x dh at dst, with cv::resize's scales (inv_scale = (double)dsize /
+// ssize, scale = 1. / inv_scale: computed here, in double, once per job)
+ResizeJob resize_job(const uint8_t* src, int sw, int sh, long long spitch, uint8_t* dst, int dw, int dh, long long dpitch)
+{
+    ResizeJob rj;
+    rj.src = src;
+    rj.dst = dst;
+    rj.spitch = spitch;
+    rj.dpitch = dpitch;
+    rj.scale_x = 1. / ((double)dw / sw);
+    rj.scale_y = 1. / ((double)dh / sh);
+    rj.sw = sw;
+    rj.sh = sh;
+    rj.dw = dw;
+    rj.dh = dh;
+    return rj;
+}
 
 // The one "grow this buffer" step (buffers grow, never shrink): when `new_cap` (in the buffer's own unit) exceeds `cap`,
 // wait for `sync` if one is given (the stream whose queued work may still touch the old buffer), free the buffer and
@@ -1905,7 +1943,8 @@ struct BatchEnqueue {
         for (int j = 0; j < n; j++)
             for (int q = 0; q < 2; q++) {
                 PngJob& pj = c.h_png[2 * j + q];
-                pj.ch = c.jobs[j].png_ch[q];
+                // (a target of another size has a launch of its own below: the batch-wide one sees a gray image)
+                pj.ch = q && c.jobs[j].rkind == RSZ_FLUSH_COPY ? 0 : c.jobs[j].png_ch[q];
                 pj.src = c.d_filt ? c.d_filt + c.filt_slot * (size_t)(2 * j + q) : nullptr;
                 pj.dst = c.d_img + npx * (size_t)(2 * j + q);
                 pj.pad = 0;
@@ -1919,6 +1958,80 @@ struct BatchEnqueue {
         if (c.w <= PNG_LDS_PIXELS / 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, dim3(2 * n), dim3(1024), 0, e->copy_stream, pa);
         else if (c.w <= PNG_LDS_PIXELS / 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, dim3(2 * n), dim3(256), 0, e->copy_stream, pa);
         else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(2 * n), dim3(64), 0, e->copy_stream, pa);
+        return enqueue_png_target_resizes();
+    }
+
+    void launch_resize(hipStream_t ls, const ResizeJob* jobs, int nz)
+    {
+        ResizeArgs ra;
+        ra.jobs = jobs;
+        TW_LAUNCH(e, TW_DF_RESIZE_U8, tw_resize_u8, dim3((c.w + 255) / 256, (c.h + RSZ_ROWS - 1) / RSZ_ROWS, nz),
+                  dim3(64, RSZ_ROWS), 0, ls, ra);
+    }
+    // tw_submit_png8_sized: the targets of another size get one more launch of tw_png_unfilter per distinct size, at that
+    // size, into their d_tsrc slots (a target that came as gray is there already); one tw_resize_u8 launch then takes them
+    // all to their d_img slots — on the copy stream, behind the batch-wide launch and in front of ev_h2d
+    tw_status enqueue_png_target_resizes()
+    {
+        if (!c.any_resize_png) return TW_OK;
+        ResizeJob* hr = c.h_rsz + e->cap;
+        // the filtered targets in order of their size: targets of one size share a launch (a page that grew by a few
+        // pixels grew in every screenshot of a run), one workgroup per image as in the batch-wide launch
+        std::vector<int> order;
+        for (int j = 0; j < n; j++) {
+            const Job& jb = c.jobs[j];
+            const bool on = jb.rkind == RSZ_FLUSH_COPY;
+            hr[j] = ResizeJob{};
+            if (on) hr[j] = resize_job(c.d_tsrc + c.tsrc_slot * (size_t)j, jb.tw, jb.th, jb.tw,
+                                       c.d_img + npx * (size_t)(2 * j + 1), c.w, c.h, c.w);
+            if (on && jb.png_ch[1] > 0) order.push_back(j);
+        }
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+            return std::make_pair(c.jobs[x].tw, c.jobs[x].th) < std::make_pair(c.jobs[y].tw, c.jobs[y].th);
+        });
+        for (size_t k = 0; k < order.size(); k++) {
+            const int j = order[k];
+            PngJob& pj = c.h_rpng[k];
+            pj.ch = c.jobs[j].png_ch[1];
+            pj.src = c.d_filt + c.filt_slot * (size_t)(2 * j + 1);
+            pj.dst = c.d_tsrc + c.tsrc_slot * (size_t)j;
+            pj.pad = 0;
+        }
+        if (!order.empty())
+            TW_HIP(e, hipMemcpyAsync(c.d_rpng, c.h_rpng, sizeof(PngJob) * order.size(), hipMemcpyHostToDevice, e->copy_stream));
+        TW_HIP(e, hipMemcpyAsync(c.d_rsz + e->cap, hr, sizeof(ResizeJob) * (size_t)n, hipMemcpyHostToDevice, e->copy_stream));
+        for (size_t k0 = 0; k0 < order.size();) {
+            const Job& jb = c.jobs[order[k0]];
+            size_t k1 = k0 + 1;
+            while (k1 < order.size() && c.jobs[order[k1]].tw == jb.tw && c.jobs[order[k1]].th == jb.th) k1++;
+            PngArgs pa;
+            pa.jobs = c.d_rpng + k0;
+            pa.w = jb.tw;
+            pa.h = jb.th;
+            const dim3 grid((unsigned)(k1 - k0));
+            if (jb.tw <= PNG_LDS_PIXELS / 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, grid, dim3(1024), 0, e->copy_stream, pa);
+            else if (jb.tw <= PNG_LDS_PIXELS / 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, grid, dim3(256), 0, e->copy_stream, pa);
+            else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, grid, dim3(64), 0, e->copy_stream, pa);
+            k0 = k1;
+        }
+        launch_resize(e->copy_stream, c.d_rsz + e->cap, n);
+        return TW_OK;
+    }
+
+    // tw_submit_dev_sized: the batch's device targets of another size (or row pitch) from the caller's memory into their
+    // d_img slots, on the compute stream in front of the batch's start event: everything downstream reads a finished slot
+    tw_status enqueue_device_target_resizes()
+    {
+        if (!c.any_resize_dev) return TW_OK;
+        ResizeJob* hr = c.h_rsz + 2 * (size_t)e->cap;
+        for (int j = 0; j < n; j++) {
+            const Job& jb = c.jobs[j];
+            hr[j] = ResizeJob{};
+            if (jb.rkind == RSZ_FLUSH_DEV)
+                hr[j] = resize_job(jb.t_src, jb.tw, jb.th, jb.tstride, const_cast<uint8_t*>(jb.d_b), c.w, c.h, jb.stride);
+        }
+        TW_HIP(e, hipMemcpyAsync(c.d_rsz + 2 * (size_t)e->cap, hr, sizeof(ResizeJob) * (size_t)n, hipMemcpyHostToDevice, st));
+        launch_resize(st, c.d_rsz + 2 * (size_t)e->cap, n);
         return TW_OK;
     }
 
@@ -2028,7 +2141,8 @@ struct BatchEnqueue {
     // direct path is the default and the graph an opt-in A/B switch (profiles/r03_latency.md).
     tw_status enqueue_or_replay_graph()
     {
-        if (lat && e->lat_graph && !prof_on && !c.any_fout && !c.any_init) {  // (destinations / fields would be baked into the graph)
+        // (destinations / fields would be baked into the graph; a reconciled pair's slots are not what the key describes)
+        if (lat && e->lat_graph && !prof_on && !c.any_fout && !c.any_init && !c.any_resize) {
             const GraphKey key{c.w, c.h, c.span, stride, e->img_aligned4, e->scan_fused, e->poly_f32};
             auto git = e->lat_graphs.find(key);
             if (git == e->lat_graphs.end()) {
@@ -2572,6 +2686,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     TW_TRY(b.enqueue_png_unfilter());
     TW_TRY(b.mark_uploads_and_plan_ramp());
     TW_TRY(b.upload_tables());
+    TW_TRY(b.enqueue_device_target_resizes());
     TW_HIP(e, hipEventRecord(c.ev_start, e->stream));
     TW_TRY(b.choose_schedule());
     e->same_n = b.n;
@@ -2728,6 +2843,9 @@ struct Submission {
     int span = 0;
     double threshold = 0;
     int ch_a = 0, ch_b = 0;  // > 0 (tw_submit_png8): that image is `height` filtered PNG rows of 1 + width * ch bytes
+    // tw_submit_*_sized: the target's own size and row stride; 0 = same as the pair (every other entry point)
+    int t_width = 0, t_height = 0;
+    ptrdiff_t t_stride = 0;
     const tw_flow_out* fo = nullptr;  // tw_submit_*_flow: where the pair's final flow goes, null for the plain calls
     const tw_flow_in* fi = nullptr;   // tw_submit_*_flow_init: the field the pair starts from, null for a zero start
     tw_ticket* ticket = nullptr;
@@ -2749,18 +2867,28 @@ struct Submit {
     const Submission& s;
     const bool png;
     const long long eff_stride;  // host images are staged densely; device images are read in place with their stride
+    const int tw, th;            // the target's own size (the pair's unless a _sized call says otherwise)
+    const ptrdiff_t tstride;
+    const bool resize;           // the target goes through tw_resize_u8 (a device target also to change its row pitch)
     Ctx* c = nullptr;
     bool fo_host = false;
     int fi_kind = 0;  // tw_submit_*_flow_init: 0 device memory (read in place), 1 page-locked, 2 other host memory
     Job jb;
 
     Submit(tw_engine* e_, const Submission& s_)
-        : e(e_), s(s_), png(s_.ch_a > 0 || s_.ch_b > 0), eff_stride(s_.h_a ? (long long)s_.width : (long long)s_.stride)
+        : e(e_), s(s_), png(s_.ch_a > 0 || s_.ch_b > 0), eff_stride(s_.h_a ? (long long)s_.width : (long long)s_.stride),
+          tw(s_.t_width ? s_.t_width : s_.width), th(s_.t_height ? s_.t_height : s_.height),
+          tstride(s_.t_stride ? s_.t_stride : s_.stride),
+          resize(tw != s_.width || th != s_.height || (!s_.h_a && tstride != s_.stride))
     {
     }
 
-    // bytes of a filtered image's slot in Ctx::d_filt
-    size_t filt_need() const { return (png_rows_bytes(s.width, s.height, std::max(s.ch_a, s.ch_b)) + 255) / 256 * 256; }
+    // bytes of a filtered image's slot in Ctx::d_filt (each image at its own size)
+    size_t filt_need() const
+    {
+        const size_t need = std::max(png_rows_bytes(s.width, s.height, s.ch_a), png_rows_bytes(tw, th, s.ch_b));
+        return (need + 255) / 256 * 256;
+    }
 
     // ---- host memory to dense rows at dst, on the copy stream: `rows` rows of `row` bytes, `pitch` apart ----------
     // Page-locked caller memory (tw_host_alloc / tw_host_register): DMA straight from it.  The caller keeps the block
@@ -2796,9 +2924,15 @@ struct Submit {
     tw_status check_arguments()
     {
         TW_TRY(check_dims(e, s.width, s.height));
+        // OpticalFlow::calculate's rule (src/opticalflow.cpp:52-68): more than 5 pixels apart is DontMatchSize
+        if (std::abs(s.width - tw) > 5 || std::abs(s.height - th) > 5) {
+            e->err = "Don't match image size";
+            return TW_E_DONT_MATCH_SIZE;
+        }
+        if (tw != s.width || th != s.height) TW_TRY(check_dims(e, tw, th));
         const bool png_ok = s.h_a && s.h_b && s.ch_a >= 0 && s.ch_a <= 4 && s.ch_b >= 0 && s.ch_b <= 4;
-        if (s.span < 0 || s.stride < s.width || (!s.h_a && !s.d_a) || (!s.h_b && !s.d_b) ||
-            (png && (!png_ok || s.stride != s.width))) {
+        if (s.span < 0 || s.stride < s.width || tstride < tw || (!s.h_a && !s.d_a) || (!s.h_b && !s.d_b) ||
+            (png && (!png_ok || s.stride != s.width || tstride != tw))) {
             e->err = "bad argument";
             return TW_E_BAD_PARAMETER;
         }
@@ -2806,10 +2940,10 @@ struct Submit {
         // the filter type byte of every row (ISO/IEC 15948 §9.2: 0-4): checked here, on the host, so that the kernel
         // never has to answer for a damaged stream (libpng: "bad adaptive filter value" -> imread fails)
         const uint8_t* img[2] = {s.h_a, s.h_b};
-        const int chs[2] = {s.ch_a, s.ch_b};
+        const int chs[2] = {s.ch_a, s.ch_b}, ws[2] = {s.width, tw}, hs[2] = {s.height, th};
         for (int q = 0; q < 2; q++)
-            for (int y = 0; chs[q] && y < s.height; y++)
-                if (img[q][(size_t)y * ((size_t)s.width * (size_t)chs[q] + 1)] > 4) {
+            for (int y = 0; chs[q] && y < hs[q]; y++)
+                if (img[q][(size_t)y * ((size_t)ws[q] * (size_t)chs[q] + 1)] > 4) {
                     e->err = "bad PNG filter type";
                     return TW_E_BAD_IMAGE_FORMAT;
                 }
@@ -2896,7 +3030,11 @@ struct Submit {
         jb.stride = eff_stride;
         jb.d_a = (const uint8_t*)s.d_a;
         jb.d_b = (const uint8_t*)s.d_b;
-        if (!s.h_a) return TW_OK;
+        jb.tw = tw;
+        jb.th = th;
+        jb.tstride = s.h_a ? (long long)tw : (long long)tstride;
+        if (resize) TW_TRY(reserve_resize_tables());
+        if (!s.h_a) return resize ? stage_device_target() : TW_OK;
         const size_t npx = staged_image_bytes(s.width, s.height);
         // (grows only on the first job of a batch: all jobs of a batch have one size)
         TW_TRY(grow_device(e, c->d_img, c->d_img_cap, npx * 2 * e->cap, npx * 2 * e->cap + 256, e->copy_stream));
@@ -2934,14 +3072,21 @@ struct Submit {
         const int chs[2] = {s.ch_a, s.ch_b};
         for (int q = 0; q < 2; q++) {
             // an image is handed over as ONE row: it goes through the bounce buffer whole, whatever its size
-            const size_t nb = chs[q] ? png_rows_bytes(s.width, s.height, chs[q]) : (size_t)s.width * s.height;
-            uint8_t* dst = chs[q] ? c->d_filt + c->filt_slot * (2 * j + q) : c->d_img + npx * (2 * j + q);
+            const int wq = q ? tw : s.width, hq = q ? th : s.height;
+            const size_t nb = chs[q] ? png_rows_bytes(wq, hq, chs[q]) : (size_t)wq * hq;
+            // (a gray target of another size waits in its d_tsrc slot for the batch's tw_resize_u8 launch)
+            uint8_t* dst = chs[q] ? c->d_filt + c->filt_slot * (2 * j + q)
+                                  : (q && resize) ? c->d_tsrc + c->tsrc_slot * j : c->d_img + npx * (2 * j + q);
             TW_TRY(pin_registry().covers(src[q], nb) ? upload_in_place(dst, src[q], nb, nb, 1)
                                                      : upload_through_bounce((char*)dst, src[q], nb, nb, 1));
         }
         jb.png_ch[0] = s.ch_a;
         jb.png_ch[1] = s.ch_b;
         c->any_png = true;
+        if (resize) {
+            jb.rkind = RSZ_FLUSH_COPY;
+            c->any_resize = c->any_resize_png = true;
+        }
         return TW_OK;
     }
 
@@ -2950,9 +3095,11 @@ struct Submit {
         const size_t at = npx * 2 * c->jobs.size();  // the pair's two slots, in d_img and in h_img
         uint8_t *dst_a = c->d_img + at, *dst_b = dst_a + npx;
         const size_t w = (size_t)s.width, h = (size_t)s.height, span_bytes = (size_t)s.stride * (h - 1) + w;
-        if (pin_registry().covers(s.h_a, span_bytes) && pin_registry().covers(s.h_b, span_bytes)) {
+        if (resize) return stage_gray_pair_resized(dst_a, dst_b);
+        const size_t span_b = (size_t)tstride * (h - 1) + w;
+        if (pin_registry().covers(s.h_a, span_bytes) && pin_registry().covers(s.h_b, span_b)) {
             TW_TRY(upload_in_place(dst_a, s.h_a, (size_t)s.stride, w, h));
-            return upload_in_place(dst_b, s.h_b, (size_t)s.stride, w, h);
+            return upload_in_place(dst_b, s.h_b, (size_t)tstride, w, h);
         }
         // pageable: not through the bounce buffer — the pair is copied to its own slots of the context's pinned ring
         // (nothing to wait for) and goes up as one transfer of both images, queued now: it overlaps the caller's next
@@ -2961,9 +3108,68 @@ struct Submit {
         uint8_t* da = c->h_img + at;
         for (size_t y = 0; y < h; y++) {
             memcpy(da + y * w, s.h_a + y * (size_t)s.stride, w);
-            memcpy(da + npx + y * w, s.h_b + y * (size_t)s.stride, w);
+            memcpy(da + npx + y * w, s.h_b + y * (size_t)tstride, w);
         }
         TW_HIP(e, hipMemcpyAsync(dst_a, da, npx * 2, hipMemcpyHostToDevice, e->copy_stream));
+        return TW_OK;
+    }
+
+    // ---- tw_submit_*_sized: a target of another size ---------------------------------------------------------
+    // what tw_resize_u8 needs once per context, and the staging region at this batch's size (it grows only on the first
+    // reconciled pair of a batch: all of a batch's slots have one size; this context's earlier batches are waited)
+    tw_status reserve_resize_tables()
+    {
+        const size_t n = (size_t)e->cap;
+        if (!c->h_rsz) TW_HIP(e, hipHostMalloc((void**)&c->h_rsz, sizeof(ResizeJob) * 3 * n, hipHostMallocDefault));
+        if (!c->d_rsz) TW_HIP(e, hipMalloc((void**)&c->d_rsz, sizeof(ResizeJob) * 3 * n + 256));
+        if (!c->h_rpng) TW_HIP(e, hipHostMalloc((void**)&c->h_rpng, sizeof(PngJob) * n, hipHostMallocDefault));
+        if (!c->d_rpng) TW_HIP(e, hipMalloc((void**)&c->d_rpng, sizeof(PngJob) * n + 256));
+        if (!s.h_a) return TW_OK;  // (a device target is read in place)
+        const size_t slot = staged_image_bytes(s.width + 5, s.height + 5), nbytes = slot * n;
+        const tw_status r = grow_device(e, c->d_tsrc_raw, c->d_tsrc_cap, nbytes, nbytes + 512, e->copy_stream);
+        c->d_tsrc = c->d_tsrc_raw ? c->d_tsrc_raw + 256 : nullptr;
+        if (r) return r;
+        c->tsrc_slot = slot;
+        return TW_OK;
+    }
+
+    // one host image as dense rows, DMA-ed in place when page-locked, through the bounce buffer otherwise
+    tw_status upload_rows(uint8_t* dst, const uint8_t* src, size_t pitch, size_t row, size_t rows)
+    {
+        return pin_registry().covers(src, pitch * (rows - 1) + row) ? upload_in_place(dst, src, pitch, row, rows)
+                                                                    : upload_through_bounce((char*)dst, src, pitch, row, rows);
+    }
+
+    // a gray host pair whose target has another size: the expected image to its d_img slot, the target to its d_tsrc slot
+    // and, right behind that upload on the copy stream, tw_resize_u8 into the pair's second d_img slot — in front of the
+    // pair's ramp mark and of ev_h2d, so that everything downstream sees a finished slot
+    tw_status stage_gray_pair_resized(uint8_t* dst_a, uint8_t* dst_b)
+    {
+        const size_t j = c->jobs.size();
+        uint8_t* tsrc = c->d_tsrc + c->tsrc_slot * j;
+        TW_TRY(upload_rows(dst_a, s.h_a, (size_t)s.stride, (size_t)s.width, (size_t)s.height));
+        TW_TRY(upload_rows(tsrc, s.h_b, (size_t)tstride, (size_t)tw, (size_t)th));
+        c->h_rsz[j] = resize_job(tsrc, tw, th, tw, dst_b, s.width, s.height, s.width);
+        TW_HIP(e, hipMemcpyAsync(c->d_rsz + j, c->h_rsz + j, sizeof(ResizeJob), hipMemcpyHostToDevice, e->copy_stream));
+        ResizeArgs ra;
+        ra.jobs = c->d_rsz + j;
+        TW_LAUNCH(e, TW_DF_RESIZE_U8, tw_resize_u8, dim3((s.width + 255) / 256, (s.height + RSZ_ROWS - 1) / RSZ_ROWS, 1),
+                  dim3(64, RSZ_ROWS), 0, e->copy_stream, ra);
+        jb.rkind = RSZ_SUBMIT;
+        c->any_resize = true;
+        return TW_OK;
+    }
+
+    // a device target of another size (or row pitch): read in place when the batch launches, resized into the pair's
+    // second d_img slot, whose pitch is the batch's row stride — the slot is sized for the stride, not the width
+    tw_status stage_device_target()
+    {
+        const size_t dslot = ((size_t)eff_stride * (size_t)s.height + 255) / 256 * 256;
+        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, dslot * 2 * e->cap, dslot * 2 * e->cap + 256, e->copy_stream));
+        jb.t_src = (const uint8_t*)s.d_b;
+        jb.d_b = c->d_img + dslot * (2 * c->jobs.size() + 1);
+        jb.rkind = RSZ_FLUSH_DEV;
+        c->any_resize = c->any_resize_dev = true;
         return TW_OK;
     }
 
@@ -3267,6 +3473,11 @@ void tw_engine_destroy(tw_engine* e)
         if (c.h_fdst) (void)hipHostFree(c.h_fdst);
         if (c.d_istage) (void)hipFree(c.d_istage);
         if (c.h_fsrc) (void)hipHostFree(c.h_fsrc);
+        if (c.d_tsrc_raw) (void)hipFree(c.d_tsrc_raw);
+        if (c.d_rsz) (void)hipFree(c.d_rsz);
+        if (c.h_rsz) (void)hipHostFree(c.h_rsz);
+        if (c.d_rpng) (void)hipFree(c.d_rpng);
+        if (c.h_rpng) (void)hipHostFree(c.h_rpng);
         if (c.ev_fexp) (void)hipEventDestroy(c.ev_fexp);
         if (c.ev_d2h) (void)hipEventDestroy(c.ev_d2h);
         if (c.ev_start) (void)hipEventDestroy(c.ev_start);
@@ -3365,6 +3576,37 @@ tw_status tw_submit_dev_flow_init(tw_engine* e, const void* d_expect, const void
     if (!d_expect || !d_target) return TW_E_BAD_PARAMETER;
     return submit(e, {.d_a = d_expect, .d_b = d_target, .width = width, .height = height, .stride = stride,
                       .span = span, .threshold = threshold, .fo = out, .fi = init, .ticket = ticket});
+}
+
+// (equal sizes: t_width / t_height name the pair's own size, and the call is the _flow_init call)
+tw_status tw_submit_u8_sized(tw_engine* e, const uint8_t* expect, int width, int height, ptrdiff_t stride,
+                             const uint8_t* target, int target_width, int target_height, ptrdiff_t target_stride,
+                             int span, double threshold, const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!expect || !target || target_width < 1 || target_height < 1 || target_stride < 1) return TW_E_BAD_PARAMETER;
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = stride, .span = span,
+                      .threshold = threshold, .t_width = target_width, .t_height = target_height,
+                      .t_stride = target_stride, .fo = out, .fi = init, .ticket = ticket});
+}
+
+tw_status tw_submit_png8_sized(tw_engine* e, const uint8_t* expect, int expect_channels, int width, int height,
+                               const uint8_t* target, int target_channels, int target_width, int target_height,
+                               int span, double threshold, const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (target_width < 1 || target_height < 1) return TW_E_BAD_PARAMETER;
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = width, .span = span,
+                      .threshold = threshold, .ch_a = expect_channels, .ch_b = target_channels, .t_width = target_width,
+                      .t_height = target_height, .t_stride = target_width, .fo = out, .fi = init, .ticket = ticket});
+}
+
+tw_status tw_submit_dev_sized(tw_engine* e, const void* d_expect, int width, int height, ptrdiff_t stride,
+                              const void* d_target, int target_width, int target_height, ptrdiff_t target_stride,
+                              int span, double threshold, const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!d_expect || !d_target || target_width < 1 || target_height < 1 || target_stride < 1) return TW_E_BAD_PARAMETER;
+    return submit(e, {.d_a = d_expect, .d_b = d_target, .width = width, .height = height, .stride = stride,
+                      .span = span, .threshold = threshold, .t_width = target_width, .t_height = target_height,
+                      .t_stride = target_stride, .fo = out, .fi = init, .ticket = ticket});
 }
 
 tw_status tw_flush(tw_engine* e)
@@ -3901,7 +4143,7 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
         "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pair_same",
-        "tw_flow_area_init", "tw_flow_export"};
+        "tw_resize_u8", "tw_flow_area_init", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
 }
 
@@ -3931,6 +4173,11 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
         if (c.d_fstage) v[0] += c.d_fstage_cap + 256;
         if (c.h_fdst) v[1] += sizeof(FlowDst) * (size_t)e->cap;
         if (c.d_img) v[0] += c.d_img_cap + 256;
+        if (c.d_tsrc_raw) v[0] += c.d_tsrc_cap + 512;
+        if (c.d_rsz) v[0] += sizeof(ResizeJob) * 3 * (size_t)e->cap + 256;
+        if (c.h_rsz) v[1] += sizeof(ResizeJob) * 3 * (size_t)e->cap;
+        if (c.d_rpng) v[0] += sizeof(PngJob) * (size_t)e->cap + 256;
+        if (c.h_rpng) v[1] += sizeof(PngJob) * (size_t)e->cap;
         if (c.d_filt_raw) v[0] += c.d_filt_cap + 512;
         if (c.d_png) v[0] += sizeof(PngJob) * 2 * (size_t)e->cap + 256;
         if (c.d_rec) v[0] += c.d_rec_cap * sizeof(ScanRec) + 256;
@@ -4300,6 +4547,35 @@ tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels,
     TW_HIP(e, hipGetLastError());
     TW_HIP(e, hipStreamSynchronize(st));
     TW_TRY(d2h_sync(e, gray, d_gray, (size_t)w * h));
+    return TW_OK;
+}
+
+tw_status tw_stage_resize_u8(tw_engine* e, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh)
+{
+    if (!e || !src || !dst) return TW_E_BAD_PARAMETER;
+    TW_TRY(check_dims(e, sw, sh));
+    TW_TRY(check_dims(e, dw, dh));
+    if (std::abs(sw - dw) > 5 || std::abs(sh - dh) > 5) {
+        e->err = "Don't match image size";
+        return TW_E_DONT_MATCH_SIZE;
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    Tmp t;
+    uint8_t* d_src = t.alloc<uint8_t>(staged_image_bytes(sw, sh));
+    uint8_t* d_dst = t.alloc<uint8_t>(staged_image_bytes(dw, dh));
+    ResizeJob* d_job = t.alloc<ResizeJob>(1);
+    if (!d_src || !d_dst || !d_job) return TW_E_NOMEM;
+    TW_TRY(h2d_sync(e, d_src, src, (size_t)sw * sh));
+    const ResizeJob rj = resize_job(d_src, sw, sh, sw, d_dst, dw, dh, dw);
+    TW_TRY(h2d_sync(e, d_job, &rj, sizeof(rj)));
+    ResizeArgs ra;
+    ra.jobs = d_job;
+    hipStream_t st = e->stream;
+    TW_LAUNCH(e, TW_DF_RESIZE_U8, tw_resize_u8, dim3((dw + 255) / 256, (dh + RSZ_ROWS - 1) / RSZ_ROWS, 1), dim3(64, RSZ_ROWS),
+              0, st, ra);
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    TW_TRY(d2h_sync(e, dst, d_dst, (size_t)dw * dh));
     return TW_OK;
 }
 

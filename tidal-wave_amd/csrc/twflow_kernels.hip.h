@@ -4745,4 +4745,120 @@ __global__ __launch_bounds__(64 * NWV) void tw_png_unfilter(PngArgs a)
     }
 }
 
+// =====================================================================================================
+// tw_resize_u8 — OpticalFlow::calculate's size reconcile (src/opticalflow.cpp:52-68): cv::resize of an 8-bit gray target
+//   whose size is within 5 pixels of the expected image's, INTER_LINEAR, OpenCV 2.4.9's fixed-point CV_8U path restated
+//   per output pixel (the host layer's resize_u8_linear computes the same bytes; tests/test_gpu_resize_u8.py):
+//     f = (float)((d + 0.5) * scale - 0.5) in double, s = floor(f), f -= s in float; x only: s clamped to [0, sw - 1] with
+//     f = 0, in y the rows are clipped and the weights kept; weights = saturate_cast<short>(cvRound(w * 2048)), float
+//     product, round half to even; horizontal S[sx] * a0 + S[sx + 1] * a1 (S[sx] * 2048 when sx + 1 >= sw); vertical
+//     uchar((((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2).  The exact 2 x 2 reduction cv::resize hands to
+//     INTER_AREA needs no branch: both weights are 1024 there and the arithmetic above gives (S00 + S01 + S10 + S11 + 2) >> 2.
+//   Grid z is the job (one target image each, with its own sizes, pitches and scales); a job without a source exits.
+//   A lane owns four adjacent outputs of one row.  Their sources are at most eight contiguous bytes of each of two rows
+//   whenever the scale is near 1: two unaligned dword loads per row, taken only when all eight bytes lie inside the row
+//   (nothing is ever read outside the sw x sh pixels: a device target is the caller's memory); otherwise byte loads.  One
+//   dword store where the four outputs exist and their address is 4-aligned, byte stores elsewhere.  ~2 B/px.
+// =====================================================================================================
+struct ResizeJob {
+    const uint8_t* src;  // sw x sh pixels, spitch bytes between rows; null: nothing to do
+    uint8_t* dst;        // dw x dh pixels, dpitch bytes between rows
+    long long spitch, dpitch;
+    double scale_x, scale_y;  // 1. / ((double)d / s), computed on the host
+    int sw, sh, dw, dh;
+};
+struct ResizeArgs {
+    const ResizeJob* jobs;
+};
+typedef __attribute__((address_space(1))) uint8_t rsz_gu8;                       // a byte of global memory
+typedef __attribute__((address_space(1), aligned(1))) unsigned rsz_gu32;  // a dword of it at any byte address
+constexpr int RSZ_ROWS = 4;  // rows per workgroup (64 lanes x 4 pixels across)
+
+__device__ __forceinline__ int resize_coef(float w)
+{
+    const int r = (int)rintf(w * 2048.f);  // cvRound: round half to even
+    return min(max(r, -32768), 32767);     // saturate_cast<short>
+}
+
+__global__ __launch_bounds__(64 * RSZ_ROWS) void tw_resize_u8(ResizeArgs a)
+{
+    const ResizeJob job = a.jobs[blockIdx.z];
+    if (!job.src) return;  // (workgroup-uniform)
+    const int dy = (int)blockIdx.y * RSZ_ROWS + (int)threadIdx.y;
+    const int dx0 = ((int)blockIdx.x * 64 + (int)threadIdx.x) * 4;
+    if (dy >= job.dh || dx0 >= job.dw) return;
+    const int sw = job.sw, nout = min(4, job.dw - dx0);
+
+    float fy = (float)(((double)dy + 0.5) * job.scale_y - 0.5);
+    const int sy = (int)floorf(fy);
+    fy -= (float)sy;
+    const int b0 = resize_coef(1.f - fy), b1 = resize_coef(fy);
+    const int r0 = min(max(sy, 0), job.sh - 1), r1 = min(max(sy + 1, 0), job.sh - 1);
+    // (pointers out of a table are generic to the compiler: say that they are global memory, as kernel arguments are)
+    const rsz_gu8* __restrict__ S0 = (const rsz_gu8*)job.src + (long long)r0 * job.spitch;
+    const rsz_gu8* __restrict__ S1 = (const rsz_gu8*)job.src + (long long)r1 * job.spitch;
+
+    int sx[4], sx1[4], a0[4], a1[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int dx = min(dx0 + k, job.dw - 1);  // (a lane past the row's end repeats the last pixel and stores nothing)
+        float fx = (float)(((double)dx + 0.5) * job.scale_x - 0.5);
+        int s = (int)floorf(fx);
+        fx -= (float)s;
+        if (s < 0) {
+            fx = 0.f;
+            s = 0;
+        }
+        if (s >= sw - 1) {
+            fx = 0.f;
+            s = sw - 1;
+        }
+        const bool last = s + 1 >= sw;  // HResizeLinear's dx >= xmax: S[sx] * 2048
+        sx[k] = s;
+        sx1[k] = last ? s : s + 1;
+        a0[k] = last ? 2048 : resize_coef(1.f - fx);
+        a1[k] = last ? 0 : resize_coef(fx);
+    }
+
+    unsigned p0[4], p1[4], q0[4], q1[4];  // S0[sx], S0[sx + 1], S1[sx], S1[sx + 1]
+    const int base = sx[0];
+    if (sx1[3] - base < 8 && base + 8 <= sw) {
+        unsigned lo0, hi0, lo1, hi1;
+        lo0 = *(const rsz_gu32*)(S0 + base);
+        hi0 = *(const rsz_gu32*)(S0 + base + 4);
+        lo1 = *(const rsz_gu32*)(S1 + base);
+        hi1 = *(const rsz_gu32*)(S1 + base + 4);
+        const unsigned long long v0 = ((unsigned long long)hi0 << 32) | lo0, v1 = ((unsigned long long)hi1 << 32) | lo1;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int o = 8 * (sx[k] - base), o1 = 8 * (sx1[k] - base);
+            p0[k] = (unsigned)(v0 >> o) & 255u;
+            p1[k] = (unsigned)(v0 >> o1) & 255u;
+            q0[k] = (unsigned)(v1 >> o) & 255u;
+            q1[k] = (unsigned)(v1 >> o1) & 255u;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            p0[k] = S0[sx[k]];
+            p1[k] = S0[sx1[k]];
+            q0[k] = S1[sx[k]];
+            q1[k] = S1[sx1[k]];
+        }
+    }
+
+    unsigned out[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int h0 = (int)p0[k] * a0[k] + (int)p1[k] * a1[k], h1 = (int)q0[k] * a0[k] + (int)q1[k] * a1[k];
+        out[k] = (unsigned)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) & 255u;
+    }
+    rsz_gu8* __restrict__ D = (rsz_gu8*)job.dst + (long long)dy * job.dpitch + dx0;
+    if (nout == 4 && ((uintptr_t)D & 3u) == 0) {
+        *(rsz_gu32*)D = out[0] | (out[1] << 8) | (out[2] << 16) | (out[3] << 24);
+    } else {
+        for (int k = 0; k < nout; k++) D[k] = (uint8_t)out[k];
+    }
+}
+
 }  // namespace twk

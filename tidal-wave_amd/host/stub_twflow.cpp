@@ -138,6 +138,28 @@ tw_status tw_submit_png8(tw_engine* e, const uint8_t* a, int cha, const uint8_t*
     // filtered rows: byte 0 is a filter type, byte 1 the first sample — compare those like tw_submit_u8 compares pixel 0
     return tw_submit_u8(e, a + (cha ? 1 : 0), b + (chb ? 1 : 0), w, h, w, span, thr, t);
 }
+// the _sized calls: OpticalFlow::calculate's size rule, then what tw_submit_u8 / tw_submit_png8 do
+static bool stub_sizes_match(int w, int h, int tw, int th) { return abs(w - tw) <= 5 && abs(h - th) <= 5; }
+tw_status tw_submit_u8_sized(tw_engine* e, const uint8_t* a, int w, int h, ptrdiff_t stride, const uint8_t* b, int tw, int th,
+                             ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
+{
+    if (tw < 1 || th < 1 || tstride < tw) return TW_E_BAD_PARAMETER;
+    if (!stub_sizes_match(w, h, tw, th)) return TW_E_DONT_MATCH_SIZE;
+    return tw_submit_u8(e, a, b, w, h, stride, span, thr, t);
+}
+tw_status tw_submit_png8_sized(tw_engine* e, const uint8_t* a, int cha, int w, int h, const uint8_t* b, int chb, int tw, int th,
+                               int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
+{
+    if (tw < 1 || th < 1) return TW_E_BAD_PARAMETER;
+    if (!stub_sizes_match(w, h, tw, th)) return TW_E_DONT_MATCH_SIZE;
+    return tw_submit_png8(e, a, cha, b, chb, w, h, span, thr, t);
+}
+tw_status tw_submit_dev_sized(tw_engine* e, const void* a, int w, int h, ptrdiff_t stride, const void* b, int tw, int th,
+                              ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
+{
+    // (the stub's "device memory" is host memory: tw_submit_u8 reads pixel 0 of both)
+    return tw_submit_u8_sized(e, (const uint8_t*)a, w, h, stride, (const uint8_t*)b, tw, th, tstride, span, thr, nullptr, nullptr, t);
+}
 tw_status tw_flush(tw_engine* e)
 {
     if (e->batch_ms > 0) {

@@ -671,6 +671,7 @@ struct Staged {
     ptrdiff_t stride = 0;
     int w = 0, h = 0;
     int cha = 0, chb = 0;  // > 0: a / b hold filtered PNG rows of that many channels (the device finishes them)
+    int tw = 0, th = 0;    // the target's own size when the device reconciles it (tw_submit_*_sized); 0: the pair's size
     std::string err;
     tw_ticket ticket = 0;
     bool submitted = false;
@@ -694,7 +695,7 @@ void decode_one(Staged& s, int which, int* tw, int* th, std::string* err, bool d
 }
 
 // OpticalFlow::calculate up to (not including) calculateInternal: src/opticalflow.cpp:20-68
-void prepare(Staged& s, int tw, int th, const std::string& err_a, const std::string& err_b)
+void prepare(Staged& s, int tw, int th, const std::string& err_a, const std::string& err_b, bool device_reconcile)
 {
     if (s.req.raw.expect) {  // in-memory pair: nothing to decode
         const RawPair& r = s.req.raw;
@@ -712,9 +713,13 @@ void prepare(Staged& s, int tw, int th, const std::string& err_a, const std::str
     if (!err_a.empty()) { s.err = err_a; return; }
     if (!err_b.empty()) { s.err = err_b; return; }
     if (abs(s.h - th) > 5 || abs(s.w - tw) > 5) { s.err = "Don't match image size"; return; }
-    if (s.h != th || s.w != tw) {
-        // the <= 5 px reconcile resizes the TARGET's gray pixels (src/opticalflow.cpp:64-68): a target that is still
-        // filtered PNG rows is finished on the host first (rare; the expected image may stay as it is)
+    if ((s.h != th || s.w != tw) && device_reconcile) {
+        // the <= 5 px reconcile on the device (tw_submit_*_sized): the target stays as it was decoded, filtered rows included
+        s.tw = tw;
+        s.th = th;
+    } else if (s.h != th || s.w != tw) {
+        // TW_DEVICE_RECONCILE=0: the reconcile resizes the TARGET's gray pixels here (src/opticalflow.cpp:64-68); a target
+        // that is still filtered PNG rows is finished on the host first (the expected image may stay as it is)
         if (s.chb) {
             std::vector<uint8_t> g;
             if (!finish_png_rows_on_host(s.b, tw, th, s.chb, g)) { s.err = "Can't open " + s.req.target_image; return; }
@@ -756,6 +761,11 @@ void Consumer::run()
     // TW_DEVICE_PNG=0 keeps the whole decode on the host (A/B switch; same bytes either way).
     bool device_png = true;
     if (const char* ev = getenv("TW_DEVICE_PNG")) device_png = atoi(ev) != 0;
+    // The <= 5 px size reconcile of OpticalFlow::calculate on the device (tw_submit_*_sized): an unequal pair stays where it
+    // was decoded — page-locked arena, filtered rows — like every other pair.  TW_DEVICE_RECONCILE=0 keeps the host path
+    // (finish_png_rows_on_host + resize_u8_linear on copies outside the arena): A/B switch and fallback, same bytes.
+    bool device_reconcile = true;
+    if (const char* ev = getenv("TW_DEVICE_RECONCILE")) device_reconcile = atoi(ev) != 0;
     tw_engine* eng = nullptr;
     std::string eng_err;
     if (ndev > 0) {
@@ -1041,10 +1051,19 @@ void Consumer::run()
                         s.stride = s.w;
                         continue;
                     }
-                    // sizes differ: the <= 5 px reconcile (or the refusal) of prepare(), on copies outside the arena
+                    if (abs(sa.h - sb.h) > 5 || abs(sa.w - sb.w) > 5) { s.err = "Don't match image size"; continue; }
+                    if (device_reconcile) {  // within 5 px: the pair stays in the arena, the device resizes the target
+                        s.pa = da;
+                        s.pb = db;
+                        s.stride = s.w;
+                        s.tw = sb.w;
+                        s.th = sb.h;
+                        continue;
+                    }
+                    // TW_DEVICE_RECONCILE=0: the reconcile of prepare() on the host, on copies outside the arena
                     s.a.assign(da, da + sa.total);
                     s.b.assign(db, db + sb.total);
-                    prepare(s, sb.w, sb.h, std::string(), std::string());
+                    prepare(s, sb.w, sb.h, std::string(), std::string(), false);
                 }
             } else {
             parallel_for(2 * jobs.size(), [&](size_t i) {
@@ -1054,7 +1073,7 @@ void Consumer::run()
                 std::vector<uint8_t>().swap(op[i].file);
             });
             bt1 = steady_ns();
-            parallel_for(jobs.size(), [&](size_t j) { prepare(jobs[j], tw[j], th[j], ea[j], eb[j]); });
+            parallel_for(jobs.size(), [&](size_t j) { prepare(jobs[j], tw[j], th[j], ea[j], eb[j], device_reconcile); });
             // The arena is sized AFTER prepare(), over the pairs that decoded and reconciled (a header with
             // huge dimensions over a damaged stream must not size it), and it is bounded: a pair larger than
             // kArenaSlotMax, or one the bounded arena has no room for, keeps its pageable buffers (tw_submit_u8 stages
@@ -1093,6 +1112,12 @@ void Consumer::run()
             if (s.err.empty() && !eng) s.err = eng_err;
             if (!s.err.empty()) continue;
             auto submit = [&]() -> tw_status {
+                if (s.tw && (s.cha || s.chb))  // a target within 5 px of the pair's size: the device reconciles it
+                    return tw_submit_png8_sized(eng, s.pa, s.cha, s.w, s.h, s.pb, s.chb, s.tw, s.th, s.req.span, s.req.threshold,
+                                                nullptr, nullptr, &s.ticket);
+                if (s.tw)
+                    return tw_submit_u8_sized(eng, s.pa, s.w, s.h, s.stride, s.pb, s.tw, s.th, s.tw, s.req.span, s.req.threshold,
+                                              nullptr, nullptr, &s.ticket);
                 if (s.cha || s.chb)  // half-decoded PNG(s): the device reconstructs the scanlines
                     return tw_submit_png8(eng, s.pa, s.cha, s.pb, s.chb, s.w, s.h, s.req.span, s.req.threshold, &s.ticket);
                 return tw_submit_u8(eng, s.pa, s.pb, s.w, s.h, s.stride, s.req.span, s.req.threshold, &s.ticket);

@@ -66,6 +66,7 @@ SYMBOLS = [
     "tw_last_error", "tw_flow_u8", "tw_diff_u8", "tw_submit_u8", "tw_submit_png8", "tw_submit_dev", "tw_flush", "tw_wait",
     "tw_submit_u8_flow", "tw_submit_png8_flow", "tw_submit_dev_flow",
     "tw_submit_u8_flow_init", "tw_submit_png8_flow_init", "tw_submit_dev_flow_init",
+    "tw_submit_u8_sized", "tw_submit_png8_sized", "tw_submit_dev_sized", "tw_stage_resize_u8",
     "tw_grid_capacity", "tw_dev_alloc", "tw_dev_free", "tw_dev_upload", "tw_dev_download", "tw_host_alloc", "tw_host_free", "tw_host_register", "tw_host_unregister", "tw_set_option",
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
@@ -148,6 +149,13 @@ def _bind(path):
     L.tw_submit_png8_flow_init.argtypes = [vp, u8p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, fip,
                                            fop, tkp]
     L.tw_submit_dev_flow_init.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_double, fip, fop, tkp]
+    L.tw_submit_u8_sized.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_ssize_t, u8p, C.c_int, C.c_int, C.c_ssize_t, C.c_int,
+                                     C.c_double, fip, fop, tkp]
+    L.tw_submit_png8_sized.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_double, fip, fop, tkp]
+    L.tw_submit_dev_sized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_ssize_t, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_int,
+                                      C.c_double, fip, fop, tkp]
+    L.tw_stage_resize_u8.argtypes = [vp, u8p, C.c_int, C.c_int, u8p, C.c_int, C.c_int]
     L.tw_wait.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, fp]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
@@ -387,10 +395,22 @@ class Engine:
         t = self.submit(expect, target, span, threshold)
         return self.wait(t)
 
-    def submit(self, expect, target, span=10, threshold=5.0, *, flow=None, init=None):
+    def submit(self, expect, target, span=10, threshold=5.0, *, flow=None, init=None, reconcile=False):
         """flow: where the pair's final flow goes (tw_submit_u8_flow; see _flow_out), kept alive by the caller until wait().
-        init: the pair's initial flow field (tw_submit_u8_flow_init; see _flow_in), unchanged until wait()."""
+        init: the pair's initial flow field (tw_submit_u8_flow_init; see _flow_in), unchanged until wait().
+        reconcile: a target of another shape goes to tw_submit_u8_sized, which resizes one within 5 px to the expected
+        image's size on the device and refuses any other (the default refuses every shape mismatch here)."""
         a, b = _gray(expect), _gray(target)
+        if a.shape != b.shape and reconcile:
+            h, w = a.shape
+            tk = C.c_int64()
+            fo = _flow_out(flow, w, h)
+            fi, _keep = _flow_in(init, w, h)
+            self._check(self._L.tw_submit_u8_sized(self._h, _u8(a), w, h, a.strides[0], _u8(b), b.shape[1], b.shape[0],
+                                                   b.strides[0], span, threshold,
+                                                   C.byref(fi) if fi is not None else None,
+                                                   C.byref(fo) if fo is not None else None, C.byref(tk)))
+            return (tk.value, w, h, span, threshold)
         if a.shape != b.shape:
             raise TwError(TW_E_DONT_MATCH_SIZE, "Don't match image size")
         if a.strides[0] != b.strides[0]:
@@ -416,15 +436,22 @@ class Engine:
         self._check(self._L.tw_submit_u8(self._h, p_expect, p_target, w, h, stride, span, threshold, C.byref(tk)))
         return (tk.value, w, h, span, threshold)
 
-    def submit_png8(self, expect, ch_a, target, ch_b, w, h, span=10, threshold=5.0, *, flow=None, init=None):
+    def submit_png8(self, expect, ch_a, target, ch_b, w, h, span=10, threshold=5.0, *, flow=None, init=None,
+                    target_size=None):
         """tw_submit_png8: each image is either filtered PNG rows (uint8 array of h * (1 + w * ch) bytes, ch 1-4) or a
-        plain gray image (ch 0, shape (h, w)).  flow, init: as for submit (tw_submit_png8_flow[_init])."""
+        plain gray image (ch 0, shape (h, w)).  flow, init: as for submit (tw_submit_png8_flow[_init]).
+        target_size: (width, height) of the target's own rows (tw_submit_png8_sized; None: the pair's size)."""
         a = np.ascontiguousarray(expect, np.uint8)
         b = np.ascontiguousarray(target, np.uint8)
         tk = C.c_int64()
         fo = _flow_out(flow, w, h)
         fi, _keep = _flow_in(init, w, h)
-        if fi is not None:
+        if target_size is not None:
+            self._check(self._L.tw_submit_png8_sized(self._h, _u8(a), ch_a, w, h, _u8(b), ch_b, target_size[0],
+                                                     target_size[1], span, threshold,
+                                                     C.byref(fi) if fi is not None else None,
+                                                     C.byref(fo) if fo is not None else None, C.byref(tk)))
+        elif fi is not None:
             self._check(self._L.tw_submit_png8_flow_init(self._h, _u8(a), ch_a, _u8(b), ch_b, w, h, span, threshold,
                                                          C.byref(fi), C.byref(fo) if fo is not None else None, C.byref(tk)))
         elif fo is None:
@@ -441,12 +468,28 @@ class Engine:
         self._check(self._L.tw_stage_png_unfilter(self._h, _u8(rows), ch, w, h, waves, _u8(out)))
         return out
 
-    def submit_dev(self, d_expect, d_target, w, h, stride, span=10, threshold=5.0, *, flow=None, init=None):
-        """flow, init: as for submit (tw_submit_dev_flow[_init])."""
+    def stage_resize_u8(self, img, dw, dh):
+        """The size reconcile's kernel alone (tw_resize_u8): a 2-D uint8 image -> (dh, dw), cv::resize's INTER_LINEAR."""
+        img = np.ascontiguousarray(_gray(img))
+        sh, sw = img.shape
+        out = np.empty((dh, dw), np.uint8)
+        self._check(self._L.tw_stage_resize_u8(self._h, _u8(img), sw, sh, _u8(out), dw, dh))
+        return out
+
+    def submit_dev(self, d_expect, d_target, w, h, stride, span=10, threshold=5.0, *, flow=None, init=None,
+                   target_size=None, target_stride=None):
+        """flow, init: as for submit (tw_submit_dev_flow[_init]).  target_size, target_stride: (width, height) and row
+        stride of the target's own memory (tw_submit_dev_sized; None: the pair's)."""
         tk = C.c_int64()
         fo = _flow_out(flow, w, h)
         fi, _keep = _flow_in(init, w, h)
-        if fi is not None:
+        if target_size is not None or target_stride is not None:
+            tw_, th_ = target_size if target_size is not None else (w, h)
+            self._check(self._L.tw_submit_dev_sized(self._h, d_expect, w, h, stride, d_target, tw_, th_,
+                                                    stride if target_stride is None else target_stride, span, threshold,
+                                                    C.byref(fi) if fi is not None else None,
+                                                    C.byref(fo) if fo is not None else None, C.byref(tk)))
+        elif fi is not None:
             self._check(self._L.tw_submit_dev_flow_init(self._h, d_expect, d_target, w, h, stride, span, threshold,
                                                         C.byref(fi), C.byref(fo) if fo is not None else None, C.byref(tk)))
         elif fo is None:
