@@ -233,6 +233,41 @@ tw_status tw_submit_dev_sized(tw_engine* e, const void* d_expect, int width, int
                               int span, double threshold, const tw_flow_in* init, const tw_flow_out* out,
                               tw_ticket* ticket);
 
+/* PNG kinds on the device (additive within ABI 4, detected by the symbols).  tw_submit_png is tw_submit_png8_sized for
+ * an image described by its IHDR: besides the 8-bit gray, gray + alpha, RGB and RGBA rows of tw_submit_png8 it takes,
+ * non-interlaced,
+ *     colour type 0 (gray)          depths 1, 2, 4 (v * 255 / (2^depth - 1)) and 16 (the high byte)
+ *     colour type 3 (palette)       depths 1, 2, 4, 8 (libpng 1.5's truncating gray formula on PLTE[v], r == g == b kept)
+ *     colour type 4 (gray + alpha)  depth 16 (the high byte of the gray sample)
+ * each converted byte for byte as cv::imread(GRAYSCALE) converts it.  The packed kinds go through a 256-entry gray table
+ * the library builds from the PLTE body (read before the call returns) or from the depth.  16-bit RGB and RGBA (pixels of
+ * 6 and 8 bytes: more than the dword a kernel lane hands to its neighbour) and Adam7 files stay on the host:
+ * tw_png_on_device answers 0 for them and tw_submit_png TW_E_UNSUPPORTED.
+ * The pair's size is the expected image's; a target within 5 pixels is reconciled as tw_submit_png8_sized does it, one
+ * further apart answers TW_E_DONT_MATCH_SIZE.  For the 8-bit kinds the call IS tw_submit_png8_sized: the same launches,
+ * copies and events.  Refused before anything is queued (no ticket consumed): a colour type / depth pair IHDR does not
+ * allow, a palette image without a palette or with palette_entries outside 1..256 (TW_E_BAD_IMAGE_FORMAT); a valid kind
+ * the device does not take (TW_E_UNSUPPORTED); a filter type byte above 4, looked for at the kind's row length
+ * (TW_E_BAD_IMAGE_FORMAT).  A palette index at or above palette_entries — what libpng refuses while it reads the rows —
+ * is found by the kernel: tw_wait of THAT pair's ticket answers TW_E_BAD_IMAGE_FORMAT and tw_last_error names the image
+ * ("expected" or "target"; the expected image wins, as the reference opens it first); the other pairs of the batch are
+ * unaffected. */
+enum { TW_PNG_PLAIN_GRAY = -1 };
+typedef struct tw_png_rows {
+    const uint8_t* rows;    /* inflated IDAT stream: height rows of 1 + ceil(width * channels * bit_depth / 8) bytes,
+                               filter type first; TW_PNG_PLAIN_GRAY: dense gray rows of `width` bytes */
+    int width, height;      /* this image's own size */
+    int color_type;         /* IHDR: 0, 2, 3, 4, 6, or TW_PNG_PLAIN_GRAY */
+    int bit_depth;          /* IHDR: 1, 2, 4, 8, 16 */
+    const uint8_t* palette; /* PLTE body, r g b per entry; colour type 3 only; read before the call returns */
+    int palette_entries;    /* 1 .. 256 */
+} tw_png_rows;
+/* 1: tw_submit_png takes rows of this IHDR colour type, bit depth and interlace method (the table above); 0: every other
+ * triple, valid or not.  Needs no device.  The one predicate: the library and its host layer both ask it. */
+int tw_png_on_device(int color_type, int bit_depth, int interlace);
+tw_status tw_submit_png(tw_engine* e, const tw_png_rows* expect, const tw_png_rows* target, int span, double threshold,
+                        const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 
@@ -346,6 +381,9 @@ tw_status tw_stage_pyr_fused01(tw_engine* e, const uint8_t* img, int w0, int h0,
  * 1 + w * channels bytes, channels 1-4; `waves` = 0 (the engine's choice for this width), 1, 4 or 16 waves per image. */
 tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels, int w, int h, int waves,
                                 uint8_t* gray);
+/* The same kernel for every kind tw_submit_png takes (TW_PNG_PLAIN_GRAY excepted): `gray` = img->width x img->height
+ * bytes.  A palette index without an entry answers TW_E_BAD_IMAGE_FORMAT. */
+tw_status tw_stage_png_decode(tw_engine* e, const tw_png_rows* img, int waves, uint8_t* gray);
 /* The size reconcile's kernel alone (tw_resize_u8): dense src (sw x sh) -> dense dst (dw x dh), cv::resize's 8-bit
  * INTER_LINEAR.  Sizes more than 5 pixels apart answer TW_E_DONT_MATCH_SIZE. */
 tw_status tw_stage_resize_u8(tw_engine* e, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh);

@@ -105,6 +105,11 @@ int tw_debug_blur_plan(const tw_engine* e, int width, int height, int level, int
  * zeros that are no flags).  Engine-level state: it describes whichever batch the engine enqueued LAST, not a ticket. */
 int tw_debug_same_flags(tw_engine* e, unsigned* out, int n);
 
+/* tw_png_unfilter alone on one image of any kind tw_stage_png_decode takes, event-timed: the rows go up once, the kernel
+ * runs once untimed, then `iters` launches back to back between two events on the engine's stream; *avg_us = the time of
+ * one (tools/e2e_files.py --kernel-time, profiles/png_kinds.md).  The statuses of tw_stage_png_decode. */
+tw_status tw_debug_png_kernel_time(tw_engine* e, const tw_png_rows* img, int waves, int iters, float* avg_us);
+
 /* Name of a family ("tw_flow_iter", ...), NULL past the end. */
 const char* tw_debug_family_name(int family);
 

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <array>
 #include <chrono>
 #include <map>
 #include <mutex>
@@ -317,6 +318,8 @@ struct Plan {
 
 constexpr int HOST_RECS = 1024;  // flagged vectors per pair copied back eagerly
 constexpr int NCTX = 3;          // batches that may be in flight (host-side state only)
+// tw_png_unfilter's table of a batch of `cap` pairs: per image a job, a flag word and a 256-byte gray table
+constexpr size_t png_table_bytes(int cap) { return (sizeof(PngJob) + sizeof(unsigned) + 256) * 2 * (size_t)cap; }
 
 struct Job {
     const uint8_t *h_a = nullptr, *h_b = nullptr;  // host inputs already staged (null for device inputs)
@@ -324,6 +327,8 @@ struct Job {
     long long stride = 0;
     bool waited = false;
     int png_ch[2] = {0, 0};  // tw_submit_png8: channels of the filtered rows staged in Ctx::d_filt (0: plain gray)
+    // tw_submit_png: PngJob::bits and ::entries of those rows, and their gray table in Ctx::png_luts (-1: not a table kind)
+    int png_bits[2] = {0, 0}, png_entries[2] = {256, 256}, png_lut[2] = {-1, -1};
     tw_flow_out fout = {nullptr, 0, 0};  // tw_submit_*_flow: where the pair's final flow goes (data null: nowhere)
     bool fout_host = false;              // ... page-locked host memory: through Ctx::d_fstage and the engine's d2h_stream
     tw_flow_in fin = {nullptr, 0, 0};    // tw_submit_*_flow_init: the pair's initial field (data null: zero start)
@@ -364,9 +369,14 @@ struct Ctx {
     // tw_png_unfilter, which reconstructs them into d_img on the copy stream before ev_h2d
     uint8_t *d_filt = nullptr, *d_filt_raw = nullptr;  // d_filt = d_filt_raw + 256 (slack on both sides)
     size_t d_filt_cap = 0, filt_slot = 0;  // filt_slot: bytes per image of the open batch (0: no filtered image yet)
+    // Both tables are png_table_bytes(cap) long: behind the 2n jobs of a batch with table kinds (tw_submit_png: palette,
+    // 1- / 2- / 4-bit gray) go one flag word per image, zero, and the batch's 256-byte gray tables — one upload, as before.
+    // The flag words of a batch with palette images come back to h_pflag behind the batch's results.
     PngJob* d_png = nullptr;
-    PngJob* h_png = nullptr;  // pinned, [2*cap]
-    bool any_png = false;
+    PngJob* h_png = nullptr;  // pinned
+    bool any_png = false, any_plte = false;
+    std::vector<std::array<uint8_t, 256>> png_luts;  // the open batch's gray tables, in the order they were submitted
+    unsigned* h_pflag = nullptr;                     // pinned, [2*cap]
     long long copy_ops_at_flush = 0;  // tw_engine::copy_ops when this batch was launched
     // ordered hit records of the batch [cap][G]: tw_wait reads them late when a pair has more than HOST_RECS hits,
     // so they belong to the context, not to the engine (a later batch must not overwrite them)
@@ -417,7 +427,8 @@ struct Ctx {
         h = height;
         span = span_;
         threshold = threshold_;
-        any_host = any_png = any_fout = any_fout_host = any_init = any_init_host = false;
+        any_host = any_png = any_plte = any_fout = any_fout_host = any_init = any_init_host = false;
+        png_luts.clear();  // (keeps its capacity: tw_engine_create reserved two tables per slot)
         any_resize = any_resize_png = any_resize_dev = false;
         filt_slot = 0;
         nseg = 0;
@@ -1947,9 +1958,16 @@ struct BatchEnqueue {
                 pj.ch = q && c.jobs[j].rkind == RSZ_FLUSH_COPY ? 0 : c.jobs[j].png_ch[q];
                 pj.src = c.d_filt ? c.d_filt + c.filt_slot * (size_t)(2 * j + q) : nullptr;
                 pj.dst = c.d_img + npx * (size_t)(2 * j + q);
-                pj.pad = 0;
+                fill_png_kind(pj, j, q);
             }
-        TW_HIP(e, hipMemcpyAsync(c.d_png, c.h_png, sizeof(PngJob) * 2 * (size_t)n, hipMemcpyHostToDevice, e->copy_stream));
+        // a batch with table kinds: the flag words (zero) and the gray tables ride behind the jobs in the same upload
+        size_t nbytes = sizeof(PngJob) * 2 * (size_t)n;
+        if (!c.png_luts.empty()) {
+            memset(c.h_png + 2 * (size_t)n, 0, sizeof(unsigned) * 2 * (size_t)n);
+            memcpy((char*)(c.h_png + 2 * (size_t)n) + sizeof(unsigned) * 2 * (size_t)n, c.png_luts.data(), 256 * c.png_luts.size());
+            nbytes += sizeof(unsigned) * 2 * (size_t)n + 256 * c.png_luts.size();
+        }
+        TW_HIP(e, hipMemcpyAsync(c.d_png, c.h_png, nbytes, hipMemcpyHostToDevice, e->copy_stream));
         PngArgs pa;
         pa.jobs = c.d_png;
         pa.w = c.w;
@@ -1959,6 +1977,19 @@ struct BatchEnqueue {
         else if (c.w <= PNG_LDS_PIXELS / 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, dim3(2 * n), dim3(256), 0, e->copy_stream, pa);
         else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(2 * n), dim3(64), 0, e->copy_stream, pa);
         return enqueue_png_target_resizes();
+    }
+
+    // the kind of image q of pair j, as tw_png_unfilter reads it; the flag words and the gray tables of the batch lie
+    // behind the 2n jobs of Ctx::d_png (enqueue_png_unfilter uploads them)
+    void fill_png_kind(PngJob& pj, int j, int q) const
+    {
+        const Job& jb = c.jobs[j];
+        unsigned* d_flags = (unsigned*)(c.d_png + 2 * (size_t)n);
+        pj.bits = jb.png_bits[q];
+        pj.entries = jb.png_entries[q];
+        pj.flag = d_flags + (2 * j + q);
+        pj.lut = jb.png_lut[q] >= 0 ? (const uint8_t*)(d_flags + 2 * (size_t)n) + 256 * (size_t)jb.png_lut[q] : nullptr;
+        pj.pad = 0;
     }
 
     void launch_resize(hipStream_t ls, const ResizeJob* jobs, int nz)
@@ -1995,7 +2026,7 @@ struct BatchEnqueue {
             pj.ch = c.jobs[j].png_ch[1];
             pj.src = c.d_filt + c.filt_slot * (size_t)(2 * j + 1);
             pj.dst = c.d_tsrc + c.tsrc_slot * (size_t)j;
-            pj.pad = 0;
+            fill_png_kind(pj, j, 1);
         }
         if (!order.empty())
             TW_HIP(e, hipMemcpyAsync(c.d_rpng, c.h_rpng, sizeof(PngJob) * order.size(), hipMemcpyHostToDevice, e->copy_stream));
@@ -2228,6 +2259,9 @@ struct BatchEnqueue {
             TW_HIP(e, hipMemcpy2DAsync(c.h_rec, HOST_RECS * sizeof(ScanRec), c.d_rec, G * sizeof(ScanRec),
                                        nrec * sizeof(ScanRec), n, hipMemcpyDeviceToHost, st));
         }
+        // a batch with palette images: the flag words tw_png_unfilter set for an index without a PLTE entry (tw_wait)
+        if (c.any_plte)
+            TW_HIP(e, hipMemcpyAsync(c.h_pflag, c.d_png + 2 * (size_t)n, sizeof(unsigned) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
         if (c.any_fout_host) {
             TW_HIP(e, hipEventRecord(c.ev_d2h, e->d2h_stream));
             c.d2h_ops_at_flush = e->d2h_ops;
@@ -2777,7 +2811,62 @@ PinRegistry& pin_registry()
 }
 bool host_range_is_page_locked(const void* p, size_t n) { return pin_registry().covers(p, n); }
 
-size_t png_rows_bytes(int width, int height, int ch) { return (size_t)height * ((size_t)width * (size_t)ch + 1); }
+// bytes of `height` filtered rows: the filter type byte and `width` units of ch bytes — or, for a table kind of less than
+// 8 bits per pixel (PngJob::bits 1, 2, 4), the ceil(width * bits / 8) bytes the pixels are packed into
+size_t png_row_bytes(int width, int ch, int bits = 0)
+{
+    return 1 + (bits == 1 || bits == 2 || bits == 4 ? ((size_t)width * (size_t)bits + 7) / 8 : (size_t)width * (size_t)ch);
+}
+size_t png_rows_bytes(int width, int height, int ch, int bits = 0) { return (size_t)height * png_row_bytes(width, ch, bits); }
+
+// libpng 1.5.12 png_do_rgb_to_gray as OpenCV 2.4.9 configures it (the kernel's formula, for the palette's gray table)
+uint8_t png_rgb_to_gray(unsigned r, unsigned g, unsigned b)
+{
+    return (uint8_t)(r == g && g == b ? r : (9797u * r + 19234u * g + 3737u * b) >> 15);
+}
+
+// One image of a tw_submit_png / tw_stage_png_decode call as tw_png_unfilter takes it: PngJob's ch, bits and entries, and for
+// a table kind (palette, 1- / 2- / 4-bit gray) its 256 gray values in lut.  Refuses what IHDR does not allow and what the
+// device does not take (tw_png_on_device: the one predicate).
+struct PngKind {
+    int ch = 0, bits = 0, entries = 256;
+    bool table = false;
+};
+tw_status describe_png(tw_engine* e, const tw_png_rows* r, const char* what, PngKind* k, uint8_t* lut)
+{
+    *k = PngKind();
+    if (!r || !r->rows) return TW_E_BAD_PARAMETER;
+    const int ct = r->color_type, d = r->bit_depth;
+    if (ct == TW_PNG_PLAIN_GRAY) return TW_OK;
+    const bool pow2 = d == 1 || d == 2 || d == 4 || d == 8 || d == 16;
+    const bool ihdr_ok = pow2 && ((ct == 0) || (ct == 3 && d <= 8) || ((ct == 2 || ct == 4 || ct == 6) && d >= 8));
+    if (!ihdr_ok || (ct == 3 && (!r->palette || r->palette_entries < 1 || r->palette_entries > 256))) {
+        e->err = std::string(what) + (ihdr_ok ? " image: a palette image needs 1 to 256 palette entries"
+                                              : " image: IHDR allows no such colour type and bit depth");
+        return TW_E_BAD_IMAGE_FORMAT;
+    }
+    if (!tw_png_on_device(ct, d, 0)) {
+        e->err = std::string(what) + " image: this PNG kind is not decoded on the device (16-bit RGB / RGBA)";
+        return TW_E_UNSUPPORTED;
+    }
+    if (ct == 3 || (ct == 0 && d < 8)) {
+        k->ch = 1;
+        k->bits = d;
+        k->table = true;
+        memset(lut, 0, 256);
+        if (ct == 3) {
+            k->entries = r->palette_entries;
+            for (int i = 0; i < k->entries; i++) lut[i] = png_rgb_to_gray(r->palette[3 * i], r->palette[3 * i + 1], r->palette[3 * i + 2]);
+        } else {
+            for (int v = 0; v < (1 << d); v++) lut[v] = (uint8_t)(v * 255 / ((1 << d) - 1));
+        }
+        return TW_OK;
+    }
+    const int samples = ct == 0 ? 1 : ct == 4 ? 2 : ct == 2 ? 3 : 4;
+    k->ch = samples * d / 8;              // 16-bit gray: the two-byte unit whose byte 0 is the high byte
+    k->bits = ct == 4 && d == 16 ? 16 : 0;  // 16-bit gray + alpha: a four-byte unit without the RGB formula
+    return TW_OK;
+}
 
 // A flow field of w x h at (data, pitch, layout) — a tw_submit_*_flow destination or a tw_submit_*_flow_init source —
 // checked before anything is queued.  *kind = 1: a page-locked host block the library knows; 0: device memory of this
@@ -2843,6 +2932,10 @@ struct Submission {
     int span = 0;
     double threshold = 0;
     int ch_a = 0, ch_b = 0;  // > 0 (tw_submit_png8): that image is `height` filtered PNG rows of 1 + width * ch bytes
+    // tw_submit_png: PngJob::bits of those rows; for a table kind its 256 gray values and the number of valid ones
+    int bits_a = 0, bits_b = 0;
+    const uint8_t *lut_a = nullptr, *lut_b = nullptr;
+    int entries_a = 256, entries_b = 256;
     // tw_submit_*_sized: the target's own size and row stride; 0 = same as the pair (every other entry point)
     int t_width = 0, t_height = 0;
     ptrdiff_t t_stride = 0;
@@ -2886,7 +2979,7 @@ struct Submit {
     // bytes of a filtered image's slot in Ctx::d_filt (each image at its own size)
     size_t filt_need() const
     {
-        const size_t need = std::max(png_rows_bytes(s.width, s.height, s.ch_a), png_rows_bytes(tw, th, s.ch_b));
+        const size_t need = std::max(png_rows_bytes(s.width, s.height, s.ch_a, s.bits_a), png_rows_bytes(tw, th, s.ch_b, s.bits_b));
         return (need + 255) / 256 * 256;
     }
 
@@ -2940,10 +3033,10 @@ struct Submit {
         // the filter type byte of every row (ISO/IEC 15948 §9.2: 0-4): checked here, on the host, so that the kernel
         // never has to answer for a damaged stream (libpng: "bad adaptive filter value" -> imread fails)
         const uint8_t* img[2] = {s.h_a, s.h_b};
-        const int chs[2] = {s.ch_a, s.ch_b}, ws[2] = {s.width, tw}, hs[2] = {s.height, th};
+        const int chs[2] = {s.ch_a, s.ch_b}, bits[2] = {s.bits_a, s.bits_b}, ws[2] = {s.width, tw}, hs[2] = {s.height, th};
         for (int q = 0; q < 2; q++)
             for (int y = 0; chs[q] && y < hs[q]; y++)
-                if (img[q][(size_t)y * ((size_t)ws[q] * (size_t)chs[q] + 1)] > 4) {
+                if (img[q][(size_t)y * png_row_bytes(ws[q], chs[q], bits[q])] > 4) {
                     e->err = "bad PNG filter type";
                     return TW_E_BAD_IMAGE_FORMAT;
                 }
@@ -3069,11 +3162,12 @@ struct Submit {
             return TW_E_NOMEM;
         }
         const uint8_t* src[2] = {s.h_a, s.h_b};
-        const int chs[2] = {s.ch_a, s.ch_b};
+        const int chs[2] = {s.ch_a, s.ch_b}, bits[2] = {s.bits_a, s.bits_b}, entries[2] = {s.entries_a, s.entries_b};
+        const uint8_t* luts[2] = {s.lut_a, s.lut_b};
         for (int q = 0; q < 2; q++) {
             // an image is handed over as ONE row: it goes through the bounce buffer whole, whatever its size
             const int wq = q ? tw : s.width, hq = q ? th : s.height;
-            const size_t nb = chs[q] ? png_rows_bytes(wq, hq, chs[q]) : (size_t)wq * hq;
+            const size_t nb = chs[q] ? png_rows_bytes(wq, hq, chs[q], bits[q]) : (size_t)wq * hq;
             // (a gray target of another size waits in its d_tsrc slot for the batch's tw_resize_u8 launch)
             uint8_t* dst = chs[q] ? c->d_filt + c->filt_slot * (2 * j + q)
                                   : (q && resize) ? c->d_tsrc + c->tsrc_slot * j : c->d_img + npx * (2 * j + q);
@@ -3082,6 +3176,16 @@ struct Submit {
         }
         jb.png_ch[0] = s.ch_a;
         jb.png_ch[1] = s.ch_b;
+        for (int q = 0; q < 2; q++) {
+            jb.png_bits[q] = bits[q];
+            jb.png_entries[q] = entries[q];
+            if (!luts[q]) continue;
+            // (nothing after this point refuses the submission: at most two tables per booked job)
+            jb.png_lut[q] = (int)c->png_luts.size();
+            c->png_luts.emplace_back();
+            memcpy(c->png_luts.back().data(), luts[q], 256);
+            c->any_plte = c->any_plte || entries[q] < 256;
+        }
         c->any_png = true;
         if (resize) {
             jb.rkind = RSZ_FLUSH_COPY;
@@ -3421,8 +3525,10 @@ tw_status tw_engine_create(int device, const tw_params* params, int slots, tw_en
              hipEventCreateWithFlags(&c.ev_seg[1], hipEventDisableTiming) == hipSuccess &&
              hipHostMalloc((void**)&c.h_ptrs, sizeof(void*) * 2 * slots, hipHostMallocDefault) == hipSuccess &&
              hipHostMalloc((void**)&c.h_count, sizeof(int) * slots, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&c.h_png, sizeof(PngJob) * 2 * (size_t)slots, hipHostMallocDefault) == hipSuccess &&
-             hipMalloc((void**)&c.d_png, sizeof(PngJob) * 2 * (size_t)slots + 256) == hipSuccess &&
+             (c.png_luts.reserve(2 * (size_t)slots), true) &&
+             hipHostMalloc((void**)&c.h_png, png_table_bytes(slots), hipHostMallocDefault) == hipSuccess &&
+             hipHostMalloc((void**)&c.h_pflag, sizeof(unsigned) * 2 * (size_t)slots, hipHostMallocDefault) == hipSuccess &&
+             hipMalloc((void**)&c.d_png, png_table_bytes(slots) + 256) == hipSuccess &&
              hipHostMalloc((void**)&c.h_rec, sizeof(ScanRec) * HOST_RECS * (size_t)slots, hipHostMallocDefault) ==
                  hipSuccess;
     }
@@ -3463,6 +3569,7 @@ void tw_engine_destroy(tw_engine* e)
         if (c.d_filt_raw) (void)hipFree(c.d_filt_raw);
         if (c.d_png) (void)hipFree(c.d_png);
         if (c.h_png) (void)hipHostFree(c.h_png);
+        if (c.h_pflag) (void)hipHostFree(c.h_pflag);
         if (c.ev_h2d) (void)hipEventDestroy(c.ev_h2d);
         for (hipEvent_t ev : c.ev_seg)
             if (ev) (void)hipEventDestroy(ev);
@@ -3599,6 +3706,55 @@ tw_status tw_submit_png8_sized(tw_engine* e, const uint8_t* expect, int expect_c
                       .t_height = target_height, .t_stride = target_width, .fo = out, .fi = init, .ticket = ticket});
 }
 
+int tw_png_on_device(int color_type, int bit_depth, int interlace)
+{
+    if (interlace != 0) return 0;
+    switch (color_type) {
+        case 0: return bit_depth == 1 || bit_depth == 2 || bit_depth == 4 || bit_depth == 8 || bit_depth == 16;
+        case 3: return bit_depth == 1 || bit_depth == 2 || bit_depth == 4 || bit_depth == 8;
+        case 4: return bit_depth == 8 || bit_depth == 16;
+        case 2:
+        case 6: return bit_depth == 8;
+        default: return 0;
+    }
+}
+
+// (the 8-bit kinds: exactly the Submission tw_submit_png8_sized builds)
+tw_status tw_submit_png(tw_engine* e, const tw_png_rows* expect, const tw_png_rows* target, int span, double threshold,
+                        const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    PngKind ka, kb;
+    uint8_t lut_a[256], lut_b[256];
+    TW_TRY(describe_png(e, expect, "expected", &ka, lut_a));
+    TW_TRY(describe_png(e, target, "target", &kb, lut_b));
+    if (target->width < 1 || target->height < 1) return TW_E_BAD_PARAMETER;
+    Submission s;
+    s.h_a = expect->rows;
+    s.h_b = target->rows;
+    s.width = expect->width;
+    s.height = expect->height;
+    s.stride = expect->width;
+    s.span = span;
+    s.threshold = threshold;
+    s.ch_a = ka.ch;
+    s.ch_b = kb.ch;
+    s.bits_a = ka.bits;
+    s.bits_b = kb.bits;
+    s.lut_a = ka.table ? lut_a : nullptr;
+    s.lut_b = kb.table ? lut_b : nullptr;
+    s.entries_a = ka.entries;
+    s.entries_b = kb.entries;
+    s.t_width = target->width;
+    s.t_height = target->height;
+    s.t_stride = target->width;
+    s.fo = out;
+    s.fi = init;
+    s.ticket = ticket;
+    return submit(e, s);
+}
+
 tw_status tw_submit_dev_sized(tw_engine* e, const void* d_expect, int width, int height, ptrdiff_t stride,
                               const void* d_target, int target_width, int target_height, ptrdiff_t target_stride,
                               int span, double threshold, const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
@@ -3663,6 +3819,11 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
     if (herr != hipSuccess) {
         e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
         return TW_E_DEVICE;
+    }
+    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
+        // what libpng refuses while it reads the rows (the reference opens the expected image first: it wins)
+        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
+        return TW_E_BAD_IMAGE_FORMAT;
     }
     if (seconds) {
         // device compute time of the batch, shared equally by its pairs (exact for a batch of one)
@@ -4179,12 +4340,13 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
         if (c.d_rpng) v[0] += sizeof(PngJob) * (size_t)e->cap + 256;
         if (c.h_rpng) v[1] += sizeof(PngJob) * (size_t)e->cap;
         if (c.d_filt_raw) v[0] += c.d_filt_cap + 512;
-        if (c.d_png) v[0] += sizeof(PngJob) * 2 * (size_t)e->cap + 256;
+        if (c.d_png) v[0] += png_table_bytes(e->cap) + 256;
         if (c.d_rec) v[0] += c.d_rec_cap * sizeof(ScanRec) + 256;
         if (c.h_img) v[1] += c.h_img_cap;
         if (c.h_ptrs) v[1] += sizeof(void*) * 2 * (size_t)e->cap;
         if (c.h_count) v[1] += sizeof(int) * (size_t)e->cap;
-        if (c.h_png) v[1] += sizeof(PngJob) * 2 * (size_t)e->cap;
+        if (c.h_png) v[1] += png_table_bytes(e->cap);
+        if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cap;
         if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cap;
     }
     for (const auto& kv : e->plans) v[0] += kv.second->owned_bytes;
@@ -4509,15 +4671,17 @@ tw_status tw_stage_pyr_fused01(tw_engine* e, const uint8_t* img, int w0, int h0,
     });
 }
 
-tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels, int w, int h, int waves, uint8_t* gray)
+// one image through tw_png_unfilter, synchronously (lut: the 256 gray values of a table kind, else null)
+// (iters > 0: the launch is repeated that many times between two events and *avg_us is the time of one; gray may be null)
+static tw_status stage_png(tw_engine* e, const uint8_t* rows, int w, int h, const PngKind& k, const uint8_t* lut, int waves,
+                           uint8_t* gray, int iters = 0, float* avg_us = nullptr)
 {
-    if (!e || !rows || !gray || channels < 1 || channels > 4) return TW_E_BAD_PARAMETER;
     tw_status r = check_dims(e, w, h);
     if (r) return r;
     TW_HIP(e, hipSetDevice(e->device));
-    const size_t nb = png_rows_bytes(w, h, channels);
+    const size_t nb = png_rows_bytes(w, h, k.ch, k.bits);
     for (int y = 0; y < h; y++)
-        if (rows[(size_t)y * ((size_t)w * channels + 1)] > 4) {
+        if (rows[(size_t)y * png_row_bytes(w, k.ch, k.bits)] > 4) {
             e->err = "bad PNG filter type";
             return TW_E_BAD_IMAGE_FORMAT;
         }
@@ -4528,12 +4692,22 @@ tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels,
     uint8_t* d_rows = d_rows_raw ? d_rows_raw + 256 : nullptr;
     uint8_t* d_gray = t.alloc<uint8_t>(staged_image_bytes(w, h));
     PngJob* d_job = t.alloc<PngJob>(1);
-    if (!d_rows || !d_gray || !d_job) return TW_E_NOMEM;
+    unsigned* d_tab = lut ? t.alloc<unsigned>(1 + 64) : nullptr;  // the flag word, then the gray table
+    if (!d_rows || !d_gray || !d_job || (lut && !d_tab)) return TW_E_NOMEM;
     TW_TRY(h2d_sync(e, d_rows, rows, nb));
+    unsigned h_tab[1 + 64] = {0u};
+    if (lut) {
+        memcpy(h_tab + 1, lut, 256);
+        TW_TRY(h2d_sync(e, d_tab, h_tab, sizeof(h_tab)));
+    }
     PngJob pj;
     pj.src = d_rows;
     pj.dst = d_gray;
-    pj.ch = channels;
+    pj.ch = k.ch;
+    pj.bits = k.bits;
+    pj.lut = lut ? (const uint8_t*)(d_tab + 1) : nullptr;
+    pj.flag = d_tab;
+    pj.entries = k.entries;
     pj.pad = 0;
     TW_TRY(h2d_sync(e, d_job, &pj, sizeof(pj)));
     PngArgs pa;
@@ -4541,13 +4715,74 @@ tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels,
     pa.w = w;
     pa.h = h;
     hipStream_t st = e->stream;
-    if (waves == 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, dim3(1), dim3(1024), 0, st, pa);
-    else if (waves == 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, dim3(1), dim3(256), 0, st, pa);
-    else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(1), dim3(64), 0, st, pa);
+    auto launch = [&]() -> tw_status {
+        if (waves == 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, dim3(1), dim3(1024), 0, st, pa);
+        else if (waves == 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, dim3(1), dim3(256), 0, st, pa);
+        else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(1), dim3(64), 0, st, pa);
+        return TW_OK;
+    };
+    TW_TRY(launch());
     TW_HIP(e, hipGetLastError());
     TW_HIP(e, hipStreamSynchronize(st));
-    TW_TRY(d2h_sync(e, gray, d_gray, (size_t)w * h));
+    if (iters > 0 && avg_us) {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        TW_HIP(e, hipEventCreate(&ev0));
+        if (hipEventCreate(&ev1) != hipSuccess) {
+            (void)hipEventDestroy(ev0);
+            return TW_E_DEVICE;
+        }
+        tw_status tr = TW_OK;
+        hipError_t he = hipEventRecord(ev0, st);
+        for (int i = 0; i < iters && tr == TW_OK; i++) tr = launch();
+        if (he == hipSuccess) he = hipEventRecord(ev1, st);
+        if (he == hipSuccess) he = hipEventSynchronize(ev1);
+        float ms = 0.f;
+        if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev0, ev1);
+        (void)hipEventDestroy(ev0);
+        (void)hipEventDestroy(ev1);
+        if (tr) return tr;
+        TW_HIP(e, he);
+        *avg_us = ms * 1e3f / (float)iters;
+    }
+    if (gray) TW_TRY(d2h_sync(e, gray, d_gray, (size_t)w * h));
+    if (lut) {
+        TW_TRY(d2h_sync(e, h_tab, d_tab, sizeof(unsigned)));
+        if (h_tab[0]) {
+            e->err = "bad palette index";
+            return TW_E_BAD_IMAGE_FORMAT;
+        }
+    }
     return TW_OK;
+}
+
+tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels, int w, int h, int waves, uint8_t* gray)
+{
+    if (!e || !rows || !gray || channels < 1 || channels > 4) return TW_E_BAD_PARAMETER;
+    PngKind k;
+    k.ch = channels;
+    return stage_png(e, rows, w, h, k, nullptr, waves, gray);
+}
+
+tw_status tw_debug_png_kernel_time(tw_engine* e, const tw_png_rows* img, int waves, int iters, float* avg_us)
+{
+    if (!e || !avg_us || iters < 1) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    PngKind k;
+    uint8_t lut[256];
+    TW_TRY(describe_png(e, img, "the", &k, lut));
+    if (k.ch == 0) return TW_E_BAD_PARAMETER;
+    return stage_png(e, img->rows, img->width, img->height, k, k.table ? lut : nullptr, waves, nullptr, iters, avg_us);
+}
+
+tw_status tw_stage_png_decode(tw_engine* e, const tw_png_rows* img, int waves, uint8_t* gray)
+{
+    if (!e || !gray) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    PngKind k;
+    uint8_t lut[256];
+    TW_TRY(describe_png(e, img, "the", &k, lut));
+    if (k.ch == 0) return TW_E_BAD_PARAMETER;  // (a plain gray image has nothing to decode)
+    return stage_png(e, img->rows, img->width, img->height, k, k.table ? lut : nullptr, waves, gray);
 }
 
 tw_status tw_stage_resize_u8(tw_engine* e, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh)

@@ -4595,7 +4595,8 @@ __global__ __launch_bounds__(1024) void tw_span_scan_seg(ScanArgs a, int S)
 
 // =====================================================================================================
 // K0  tw_png_unfilter<NWV> : PNG scanline reconstruction (ISO/IEC 15948 §9: None / Sub / Up / Average / Paeth) of 8-bit
-//   gray, gray+alpha, RGB or RGBA rows + libpng-1.5 gray conversion, on the device — the part of cv::imread
+//   gray, gray+alpha, RGB or RGBA, 16-bit gray or gray+alpha, palette or 1- / 2- / 4-bit gray rows (non-interlaced;
+//   16-bit RGB / RGBA and Adam7 stay on the host) + libpng-1.5 gray conversion, on the device — the part of cv::imread
 //   (src/opticalflow.cpp:37-48) that is byte arithmetic with a left / up / up-left dependence, taken off the host's
 //   decode threads.  The host inflates; the filtered rows go up as they are.
 //   One workgroup per image, one LANE per ROW, rows skewed by one pixel: at step t lane r of wave v reconstructs pixel
@@ -4608,11 +4609,24 @@ __global__ __launch_bounds__(1024) void tw_span_scan_seg(ScanArgs a, int S)
 //   so a wave advances 64 rows at once and NWV waves 64 NWV rows; a band of 64 NWV rows takes w + 64 NWV + S (NWV - 1)
 //   steps, one barrier every S steps.  A pixel's channels ride in the bytes of one dword.  A band whose rows fill only
 //   some of the waves takes only the steps those waves need.
+//   The kinds (PngJob::ch = bytes per filter unit, PngJob::bits): a unit is one pixel — 8-bit gray, gray + alpha, RGB,
+//   RGBA (bits 0), 16-bit gray (ch 2, bits 0: byte 0 is the high byte) and 16-bit gray + alpha (ch 4, bits 16: byte 0,
+//   no RGB formula) — or, for the TABLE kinds (ch 1, bits 1 / 2 / 4 / 8: palette and 1- / 2- / 4-bit gray), one byte of
+//   8 / bits pixels: the one-byte body runs over the row's ceil(w * bits / 8) bytes and each reconstructed byte emits its
+//   pixels, most significant bits first, through a 256-entry gray table held in LDS; the last byte of a row emits only
+//   the pixels that exist (its pad bits take part in the filter arithmetic and in nothing else).  A value at or above
+//   PngJob::entries (a palette index without a PLTE entry) sets the image's flag word: a plain store, every writer
+//   stores the same 1.
 // =====================================================================================================
 struct PngJob {
-    const uint8_t* src;  // filtered rows: h x (1 + w * ch) bytes (filter type byte first)
+    const uint8_t* src;  // filtered rows: h x (1 + units * ch) bytes (filter type byte first)
     uint8_t* dst;        // gray, w x h, dense
-    int ch;              // 1 gray, 2 gray + alpha, 3 RGB, 4 RGBA; 0: nothing to do (the image came as gray)
+    int ch;              // bytes per filter unit, 1-4; 0: nothing to do (the image came as gray)
+    int bits;            // 0: a unit is a pixel (RGB formula for ch >= 3); 16: a unit is a pixel, gray = byte 0;
+                         // 1, 2, 4, 8: table kind, pixels of that many bits (ch 1)
+    const uint8_t* lut;  // table kinds: 256 gray values (4-byte aligned)
+    unsigned* flag;      // table kinds: set to 1 when a pixel's value is >= entries
+    int entries;         // table kinds: values below this are valid (PLTE entries; 256 for the gray tables)
     int pad;
 };
 struct PngArgs {
@@ -4635,16 +4649,23 @@ __device__ __forceinline__ unsigned png_paeth(unsigned a, unsigned b, unsigned c
 // next four pixels arrive with ONE (unaligned) load issued a whole group earlier, so no step waits for memory — with a
 // byte load per step the kernel ran at the L2's latency, ~1 100 cycles per pixel column (4.2 ms per batch of 64 images).
 // The rows may be read up to 16 bytes before their first and after their last byte: the staging buffers are padded.
-template <int NWV, int CH>
-__device__ __forceinline__ void png_unfilter_band(const PngJob& job, int w, int h, int band, unsigned (*edge)[PNG_LDS_PIXELS / NWV + 4])
+// BITS as PngJob::bits.  A table kind (BITS 1, 2, 4, 8; CH 1) walks the nu = ceil(w * BITS / 8) bytes of its row where the
+// other kinds walk their w pixels (nu = w), and looks its pixels up in lut (LDS).
+template <int NWV, int CH, int BITS>
+__device__ __forceinline__ void png_unfilter_band(const PngJob& job, int w, int h, int band, unsigned (*edge)[PNG_LDS_PIXELS / NWV + 4],
+                                                  const uint8_t* lut)
 {
     constexpr int ROWS = 64 * NWV, S = PNG_S, ND = (4 * CH + 3) / 4;  // ND dwords hold a group's 4 * CH bytes
+    constexpr bool TABLE = BITS == 1 || BITS == 2 || BITS == 4 || BITS == 8;
+    constexpr int PPB = TABLE ? 8 / BITS : 1;  // pixels per unit
+    static_assert(!TABLE || CH == 1, "a table kind is filtered byte by byte");
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const long long stride = (long long)w * CH + 1;
+    const int nu = TABLE && PPB > 1 ? (w + PPB - 1) / PPB : w;  // filter units per row
+    const long long stride = (long long)nu * CH + 1;
     const int off = lane + (64 + S) * wv;
     const int rows_left = h - band * ROWS;
     const int nact = rows_left >= ROWS ? NWV : (rows_left + 63) / 64;  // waves of this band that own a row
-    const int steps = (w + 64 * nact + S * (nact - 1) + S - 1) / S * S;
+    const int steps = (nu + 64 * nact + S * (nact - 1) + S - 1) / S * S;
     const bool dword_out = (w & 3) == 0;  // dst rows then start on a dword (the image slot is 256-byte aligned)
     const int prev_wave = (wv + NWV - 1) % NWV;
     const int row = band * ROWS + tid;
@@ -4657,9 +4678,10 @@ __device__ __forceinline__ void png_unfilter_band(const PngJob& job, int w, int 
                    m_paeth = ft == 4u ? 255u : 0u;
     const bool has_up = row > 0;
     unsigned cur = 0, bprev = 0, acc = 0;
+    bool bad = false;  // (table kinds) a value without a table entry
     unsigned nxt[ND];
-    auto fetch = [&](int x0) {  // the raw bytes of pixels x0 .. x0 + 3 of the lane's row
-        const int xl = min(max(x0, -4), w);
+    auto fetch = [&](int x0) {  // the raw bytes of units x0 .. x0 + 3 of the lane's row
+        const int xl = min(max(x0, -4), nu);
         const uint8_t* q = in + 1 + (long long)xl * CH;
 #pragma unroll
         for (int i = 0; i < ND; i++) __builtin_memcpy(&nxt[i], q + 4 * i, 4);
@@ -4675,7 +4697,7 @@ __device__ __forceinline__ void png_unfilter_band(const PngJob& job, int w, int 
             fetch(x0 + 4);
             // lane 0: the four pixels above, published by the previous wave (or the previous band) at least one barrier ago
             unsigned up4[4] = {0u, 0u, 0u, 0u};
-            if (lane == 0 && has_up && active && x0 >= 0 && x0 < w) {
+            if (lane == 0 && has_up && active && x0 >= 0 && x0 < nu) {
                 const uint4 e = *(const uint4*)&edge[prev_wave][x0];
                 up4[0] = e.x;
                 up4[1] = e.y;
@@ -4685,7 +4707,7 @@ __device__ __forceinline__ void png_unfilter_band(const PngJob& job, int w, int 
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int x = x0 + k;
-                const bool on = active && x >= 0 && x < w;
+                const bool on = active && x >= 0 && x < nu;
                 unsigned b = dpp_from_prev(cur);  // the row above finished pixel x one step ago
                 if (lane == 0) b = up4[k];
                 if (!has_up) b = 0u;
@@ -4709,39 +4731,81 @@ __device__ __forceinline__ void png_unfilter_band(const PngJob& job, int w, int 
                     if (lane == 63) edge[wv][x] = rec;
                     // libpng 1.5.12 png_do_rgb_to_gray as OpenCV 2.4.9 configures it: truncated 15-bit coefficients
                     unsigned gr = rec & 255u;
-                    if (CH >= 3) {
+                    if (CH >= 3 && BITS == 0) {
                         const unsigned gg = (rec >> 8) & 255u, bb = (rec >> 16) & 255u;
                         if (!(gr == gg && gg == bb)) gr = (9797u * gr + 19234u * gg + 3737u * bb) >> 15;
                     }
-                    if (dword_out) {
-                        acc |= gr << (8 * (x & 3));
-                        if ((x & 3) == 3) {
-                            *(unsigned*)(out + x - 3) = acc;
-                            acc = 0;
+                    if constexpr (TABLE) {
+                        // the byte's PPB pixels, most significant bits first; gv = their gray values, one per byte
+                        unsigned gv[2] = {0u, 0u};
+#pragma unroll
+                        for (int i = 0; i < PPB; i++) {
+                            const unsigned v = (rec >> (8 - BITS * (i + 1))) & ((1u << BITS) - 1u);
+                            if (x * PPB + i < w) bad = bad || v >= (unsigned)job.entries;  // (pad bits are no pixels)
+                            gv[i >> 2] |= (unsigned)lut[v] << (8 * (i & 3));
                         }
-                    } else {
-                        out[x] = (uint8_t)gr;
+                        gr = gv[0];
+                        if constexpr (PPB > 1) {
+                            uint8_t* o = out + (long long)x * PPB;
+                            if (!dword_out) {
+#pragma unroll
+                                for (int i = 0; i < PPB; i++)
+                                    if (x * PPB + i < w) o[i] = (uint8_t)(gv[i >> 2] >> (8 * (i & 3)));
+                            } else if (PPB == 2) {  // (w % 4 == 0: an even number of bytes, every pixel exists)
+                                acc |= gv[0] << (16 * (x & 1));
+                                if (x & 1) {
+                                    *(unsigned*)(o - 2) = acc;
+                                    acc = 0;
+                                }
+                            } else {  // (w % 4 == 0: only the second half of a 1-bit row's last byte may be pad)
+                                *(unsigned*)o = gv[0];
+                                if (PPB == 8 && x * 8 + 4 < w) *(unsigned*)(o + 4) = gv[1];
+                            }
+                        }
+                    }
+                    if constexpr (PPB == 1) {
+                        if (dword_out) {
+                            acc |= gr << (8 * (x & 3));
+                            if ((x & 3) == 3) {
+                                *(unsigned*)(out + x - 3) = acc;
+                                acc = 0;
+                            }
+                        } else {
+                            out[x] = (uint8_t)gr;
+                        }
                     }
                 }
             }
         }
         __syncthreads();
     }
+    if (TABLE && bad) *job.flag = 1u;  // (a vector store)
 }
 
 template <int NWV>
 __global__ __launch_bounds__(64 * NWV) void tw_png_unfilter(PngArgs a)
 {
     constexpr int ROWS = 64 * NWV;
-    // edge[v][x]: pixel x of the row lane 63 of wave v reconstructed last (+ 4: lane 0 reads whole groups of four)
+    // edge[v][x]: unit x of the row lane 63 of wave v reconstructed last (+ 4: lane 0 reads whole groups of four)
     __shared__ __attribute__((aligned(16))) unsigned edge[NWV][PNG_LDS_PIXELS / NWV + 4];
+    __shared__ __attribute__((aligned(4))) uint8_t lut[256];  // the gray table of a table kind
     const PngJob job = a.jobs[blockIdx.x];
-    if (job.ch == 0) return;  // (workgroup-uniform)
+    if (job.ch == 0) return;  // (workgroup-uniform, like every branch on the job below)
+    if (job.bits >= 1 && job.bits <= 8) {
+        if (threadIdx.x < 64) ((unsigned*)lut)[threadIdx.x] = ((const unsigned*)job.lut)[threadIdx.x];
+        __syncthreads();
+    }
     for (int band = 0; band * ROWS < a.h; band++) {
-        if (job.ch == 1) png_unfilter_band<NWV, 1>(job, a.w, a.h, band, edge);
-        else if (job.ch == 2) png_unfilter_band<NWV, 2>(job, a.w, a.h, band, edge);
-        else if (job.ch == 3) png_unfilter_band<NWV, 3>(job, a.w, a.h, band, edge);
-        else png_unfilter_band<NWV, 4>(job, a.w, a.h, band, edge);
+        if (job.bits == 0) {
+            if (job.ch == 1) png_unfilter_band<NWV, 1, 0>(job, a.w, a.h, band, edge, lut);
+            else if (job.ch == 2) png_unfilter_band<NWV, 2, 0>(job, a.w, a.h, band, edge, lut);
+            else if (job.ch == 3) png_unfilter_band<NWV, 3, 0>(job, a.w, a.h, band, edge, lut);
+            else png_unfilter_band<NWV, 4, 0>(job, a.w, a.h, band, edge, lut);
+        } else if (job.bits == 16) png_unfilter_band<NWV, 4, 16>(job, a.w, a.h, band, edge, lut);
+        else if (job.bits == 8) png_unfilter_band<NWV, 1, 8>(job, a.w, a.h, band, edge, lut);
+        else if (job.bits == 4) png_unfilter_band<NWV, 1, 4>(job, a.w, a.h, band, edge, lut);
+        else if (job.bits == 2) png_unfilter_band<NWV, 1, 2>(job, a.w, a.h, band, edge, lut);
+        else png_unfilter_band<NWV, 1, 1>(job, a.w, a.h, band, edge, lut);
     }
 }
 

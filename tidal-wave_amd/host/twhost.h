@@ -165,6 +165,27 @@ bool load_gray(const std::string& path, std::vector<uint8_t>& img, int& w, int& 
 // (ch 1-4: h rows of 1 + w * ch bytes for tw_submit_png8; ch 0: `img` is the gray image)
 bool load_gray_or_png_rows(const std::string& path, bool want_rows, std::vector<uint8_t>& img, int& w, int& h, int& ch);
 bool finish_png_rows_on_host(std::vector<uint8_t>& rows, int w, int h, int ch, std::vector<uint8_t>& gray);
+// What an image's bytes are when they are not gray pixels: the IHDR kind (and PLTE body) of inflated, still filtered PNG
+// rows that tw_submit_png finishes on the device.  color_type TW_PNG_PLAIN_GRAY: gray pixels.
+struct PngKind {
+    int color_type = TW_PNG_PLAIN_GRAY, bit_depth = 8;
+    std::vector<uint8_t> plte;
+    bool rows() const { return color_type != TW_PNG_PLAIN_GRAY; }
+    // bytes of one filtered row of `w` pixels, filter type byte included
+    size_t row_bytes(int w) const
+    {
+        const size_t samples = color_type == 2 ? 3 : color_type == 4 ? 2 : color_type == 6 ? 4 : 1;
+        return 1 + ((size_t)w * samples * (size_t)bit_depth + 7) / 8;
+    }
+};
+// load_gray_or_png_rows for every kind tw_png_on_device admits (palette, 1- / 2- / 4-bit and 16-bit gray, 16-bit gray +
+// alpha besides the 8-bit ones; all_kinds = false: the 8-bit ones only): `img` holds the rows and `kind` says what they
+// are, or the gray image (kind.rows() false).  Every row's filter type is checked at the kind's row length.
+bool load_gray_or_png_kind_rows(const std::string& path, bool want_rows, bool all_kinds, std::vector<uint8_t>& img, int& w,
+                                int& h, PngKind& kind);
+// The rest of the decode of such rows on the host (what the device does for tw_submit_png): false for a palette index
+// without an entry, as cv::imread fails on it.
+bool finish_png_kind_on_host(const uint8_t* rows, int w, int h, const PngKind& kind, std::vector<uint8_t>& gray);
 // cv::resize(8-bit, INTER_LINEAR) — the "<= 5 px" reconcile of src/opticalflow.cpp:64-68.
 void resize_u8_linear(const std::vector<uint8_t>& src, int sw, int sh, std::vector<uint8_t>& dst, int dw, int dh);
 

@@ -67,14 +67,43 @@ SYMBOLS = [
     "tw_submit_u8_flow", "tw_submit_png8_flow", "tw_submit_dev_flow",
     "tw_submit_u8_flow_init", "tw_submit_png8_flow_init", "tw_submit_dev_flow_init",
     "tw_submit_u8_sized", "tw_submit_png8_sized", "tw_submit_dev_sized", "tw_stage_resize_u8",
+    "tw_png_on_device", "tw_submit_png", "tw_stage_png_decode",
     "tw_grid_capacity", "tw_dev_alloc", "tw_dev_free", "tw_dev_upload", "tw_dev_download", "tw_host_alloc", "tw_host_free", "tw_host_register", "tw_host_unregister", "tw_set_option",
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
-    "tw_debug_blur_plan", "tw_debug_same_flags",
+    "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time",
 ]
+
+
+PNG_PLAIN_GRAY = -1
+
+
+class PngRows(C.Structure):
+    """tw_png_rows: one image of submit_png / stage_png_decode as its IHDR describes it.  rows: the inflated IDAT stream
+    (height rows of 1 + ceil(width * channels * bit_depth / 8) bytes, filter type first) or, with color_type
+    PNG_PLAIN_GRAY, a gray image of shape (height, width).  palette: the PLTE body (colour type 3), r g b per entry;
+    palette_entries defaults to its length / 3.  The arrays stay alive with the structure."""
+    _fields_ = [("rows", C.POINTER(C.c_uint8)), ("width", C.c_int), ("height", C.c_int), ("color_type", C.c_int),
+                ("bit_depth", C.c_int), ("palette", C.POINTER(C.c_uint8)), ("palette_entries", C.c_int)]
+
+    def __init__(self, rows, width, height, color_type=PNG_PLAIN_GRAY, bit_depth=8, palette=None, palette_entries=None):
+        super().__init__()
+        self._rows = np.ascontiguousarray(rows, np.uint8)
+        self._palette = None if palette is None else np.ascontiguousarray(palette, np.uint8)
+        self.rows = _u8(self._rows)
+        self.width, self.height, self.color_type, self.bit_depth = width, height, color_type, bit_depth
+        if self._palette is not None:
+            self.palette = _u8(self._palette)
+        n = 0 if self._palette is None else self._palette.size // 3
+        self.palette_entries = n if palette_entries is None else palette_entries
+
+
+def png_on_device(color_type, bit_depth, interlace=0):
+    """tw_png_on_device: does submit_png take rows of this IHDR colour type, bit depth and interlace method?"""
+    return bool(lib().tw_png_on_device(color_type, bit_depth, interlace))
 
 
 VARIANTS_LIB_PATH = os.path.join(_HERE, "libtwflow_variants.so")
@@ -156,6 +185,11 @@ def _bind(path):
     L.tw_submit_dev_sized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_ssize_t, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_int,
                                       C.c_double, fip, fop, tkp]
     L.tw_stage_resize_u8.argtypes = [vp, u8p, C.c_int, C.c_int, u8p, C.c_int, C.c_int]
+    L.tw_png_on_device.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.tw_png_on_device.restype = C.c_int
+    L.tw_submit_png.argtypes = [vp, C.POINTER(PngRows), C.POINTER(PngRows), C.c_int, C.c_double, fip, fop, tkp]
+    L.tw_stage_png_decode.argtypes = [vp, C.POINTER(PngRows), C.c_int, u8p]
+    L.tw_debug_png_kernel_time.argtypes = [vp, C.POINTER(PngRows), C.c_int, C.c_int, fp]
     L.tw_wait.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, fp]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
@@ -467,6 +501,30 @@ class Engine:
         out = np.empty((h, w), np.uint8)
         self._check(self._L.tw_stage_png_unfilter(self._h, _u8(rows), ch, w, h, waves, _u8(out)))
         return out
+
+    def submit_png(self, expect, target, span=10, threshold=5.0, *, flow=None, init=None):
+        """tw_submit_png: expect, target are PngRows (any kind png_on_device admits, or PNG_PLAIN_GRAY), each at its own
+        size; the pair's size is the expected image's.  flow, init: as for submit."""
+        w, h = expect.width, expect.height
+        tk = C.c_int64()
+        fo = _flow_out(flow, w, h)
+        fi, _keep = _flow_in(init, w, h)
+        self._check(self._L.tw_submit_png(self._h, C.byref(expect), C.byref(target), span, threshold,
+                                          C.byref(fi) if fi is not None else None,
+                                          C.byref(fo) if fo is not None else None, C.byref(tk)))
+        return (tk.value, w, h, span, threshold)
+
+    def stage_png_decode(self, img, waves=0):
+        """tw_png_unfilter alone on one PngRows image of any admitted kind: the (height, width) gray image."""
+        out = np.empty((img.height, img.width), np.uint8)
+        self._check(self._L.tw_stage_png_decode(self._h, C.byref(img), waves, _u8(out)))
+        return out
+
+    def png_kernel_time(self, img, iters=20, waves=0):
+        """tw_debug_png_kernel_time: microseconds of one tw_png_unfilter launch on this PngRows image (event-timed)."""
+        us = C.c_float()
+        self._check(self._L.tw_debug_png_kernel_time(self._h, C.byref(img), waves, iters, C.byref(us)))
+        return us.value
 
     def stage_resize_u8(self, img, dw, dh):
         """The size reconcile's kernel alone (tw_resize_u8): a 2-D uint8 image -> (dh, dw), cv::resize's INTER_LINEAR."""

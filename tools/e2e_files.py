@@ -1,8 +1,22 @@
 #!/usr/bin/env python3
 """End-to-end service throughput from FILES (decode included): writes N synthetic 1080p pairs as PNG, runs them
-through host/index.js create() (addon -> decode pool -> libtwflow.so) and prints pairs/s.  Needs a GPU + node."""
+through host/index.js create() (addon -> decode pool -> libtwflow.so) and prints pairs/s.  Needs a GPU + node.
+
+    e2e_files.py [N [DECODE_THREADS]] [--corpus gray|rgba|palette|mixed] [--host DIR] [--json]
+    e2e_files.py --kernel-time
+
+  --corpus   the kind of file: 8-bit gray (the default, what this tool has always written), RGBA, palette-8 with the
+             identity gray palette, or mixed = one pair in 32 palette-8 and the rest RGBA
+  --host     the host/ directory whose index.js and addon run (default: this tree's): A/B against another build
+  --json     one JSON line instead of the text
+  --kernel-time   no files: tw_png_unfilter per 1080p image for RGBA, palette-8 and 1-bit gray rows, event-timed
+             (tw_debug_png_kernel_time, 20 launches between two events, the median of 7 such figures)
+The environment goes through unchanged (TW_DEVICE_PNG_KINDS=0 keeps palette files on the host)."""
+import argparse
 import json
 import os
+import shutil
+import statistics
 import subprocess
 import sys
 import tempfile
@@ -13,39 +27,94 @@ sys.path.insert(0, os.path.join(ROOT, "tidal-wave_amd"))
 import synth  # noqa: E402
 
 
-def main():
+def save(img, path, kind):
+    import numpy as np
     from PIL import Image
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-    threads = sys.argv[2] if len(sys.argv) > 2 else ""
+    if kind == "palette":
+        im = Image.fromarray(img, mode="P")
+        im.putpalette([v for i in range(256) for v in (i, i, i)])
+    elif kind == "rgba":
+        im = Image.fromarray(np.dstack([img, img, img, np.full_like(img, 255)]))
+    else:
+        im = Image.fromarray(img)
+    im.save(path, compress_level=3)
+
+
+def kernel_time():
+    import numpy as np
+    import twflow
+    w, h = 1920, 1080
+    rng = np.random.default_rng(1)
+    rows = lambda nb: np.concatenate([(np.arange(h) % 5).astype(np.uint8)[:, None],
+                                      rng.integers(0, 256, (h, nb), dtype=np.uint8)], 1)  # filter types 0-4 in turn
+    ident = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, 1)
+    kinds = (("rgba", twflow.PngRows(rows(w * 4), w, h, 6, 8)), ("palette8", twflow.PngRows(rows(w), w, h, 3, 8, ident)),
+             ("gray1", twflow.PngRows(rows(w // 8), w, h, 0, 1)))
+    out = {}
+    with twflow.Engine(0, twflow.default_params(), slots=2) as e:
+        for rep in range(7):  # the kinds in turn, so that a drift of the clock touches all of them alike
+            for name, img in kinds:
+                out.setdefault(name, []).append(e.png_kernel_time(img, 20))
+    print(json.dumps({"tw_png_unfilter_us_per_1080p_image": {k: {"median": round(statistics.median(v), 1),
+                                                                 "min": round(min(v), 1), "max": round(max(v), 1)}
+                                                             for k, v in out.items()}}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", nargs="?", type=int, default=32)
+    ap.add_argument("threads", nargs="?", default="")
+    ap.add_argument("--corpus", default="gray", choices=("gray", "rgba", "palette", "mixed"))
+    ap.add_argument("--host", default=os.path.join(ROOT, "tidal-wave_amd", "host"))
+    ap.add_argument("--json", action="store_true")
+    ap.add_argument("--kernel-time", action="store_true")
+    a = ap.parse_args()
+    if a.kernel_time:
+        return kernel_time()
+    n, threads = a.n, a.threads
     d = tempfile.mkdtemp(prefix="twe2e_")
-    os.makedirs(os.path.join(d, "expected", "s"))
-    os.makedirs(os.path.join(d, "target", "s"))
-    for i in range(n):
-        pe, pt = os.path.join(d, "expected", "s", "p%04d.png" % i), os.path.join(d, "target", "s", "p%04d.png" % i)
-        if i < 4:
-            a, b = synth.make_pair(i, 1080, 1920)
-            Image.fromarray(a).save(pe, compress_level=3)
-            Image.fromarray(b).save(pt, compress_level=3)
-        else:  # the four distinct pairs again (hard links: the decoder reads and inflates every file all the same)
-            os.link(os.path.join(d, "expected", "s", "p%04d.png" % (i % 4)), pe)
-            os.link(os.path.join(d, "target", "s", "p%04d.png" % (i % 4)), pt)
-    js = ("var T=require('./index'); var t0=Date.now(); var n=0;"
-          "var t=T.create(process.argv[1],{expectDir:process.argv[2], numThreads:8});"
-          "t.on('data',function(){n++}); t.on('error',function(e){console.error(JSON.stringify(e))});"
-          "var rss0=process.memoryUsage().rss, rssMid=0; setTimeout(function(){rssMid=process.memoryUsage().rss}, 3000);"
-          "t.on('finish',function(r){console.log(JSON.stringify({report:r, ms:Date.now()-t0, rss_start_MB:rss0>>20, "
-          "rss_at_3s_MB:rssMid>>20, rss_end_MB:process.memoryUsage().rss>>20}))});")
-    env = dict(os.environ)
-    if threads:
-        env["TW_DECODE_THREADS"] = threads
-    t0 = time.time()
-    r = subprocess.run(["node", "-e", js, os.path.join(d, "target"), os.path.join(d, "expected")],
-                       cwd=os.path.join(ROOT, "tidal-wave_amd", "host"), capture_output=True, text=True, env=env)
-    wall = time.time() - t0
-    print(r.stdout.strip(), r.stderr.strip()[-3000:])
+    try:
+        os.makedirs(os.path.join(d, "expected", "s"))
+        os.makedirs(os.path.join(d, "target", "s"))
+        made = {}  # (pair % 4, kind) -> its two files
+        for i in range(n):
+            kind = {"gray": "gray", "rgba": "rgba", "palette": "palette"}.get(a.corpus) or ("palette" if i % 32 == 5 else "rgba")
+            pe, pt = os.path.join(d, "expected", "s", "p%04d.png" % i), os.path.join(d, "target", "s", "p%04d.png" % i)
+            if (i % 4, kind) not in made:
+                img_a, img_b = synth.make_pair(i % 4, 1080, 1920)
+                save(img_a, pe, kind)
+                save(img_b, pt, kind)
+                made[(i % 4, kind)] = (pe, pt)
+            else:  # the four distinct pairs again (hard links: the decoder reads and inflates every file all the same)
+                os.link(made[(i % 4, kind)][0], pe)
+                os.link(made[(i % 4, kind)][1], pt)
+        js = ("var T=require('./index'); var t0=Date.now(); var n=0, err=0;"
+              "var t=T.create(process.argv[1],{expectDir:process.argv[2], numThreads:8});"
+              "t.on('data',function(){n++}); t.on('error',function(e){err++; console.error(JSON.stringify(e))});"
+              "var rss0=process.memoryUsage().rss, rssMid=0; setTimeout(function(){rssMid=process.memoryUsage().rss}, 3000);"
+              "t.on('finish',function(r){console.log(JSON.stringify({report:r, ms:Date.now()-t0, errors:err, rss_start_MB:rss0>>20, "
+              "rss_at_3s_MB:rssMid>>20, rss_end_MB:process.memoryUsage().rss>>20}))});")
+        env = dict(os.environ)
+        if threads:
+            env["TW_DECODE_THREADS"] = threads
+        t0 = time.time()
+        r = subprocess.run(["node", "-e", js, os.path.join(d, "target"), os.path.join(d, "expected")],
+                           cwd=a.host, capture_output=True, text=True, env=env)
+        wall = time.time() - t0
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    if r.returncode != 0 or not r.stdout.strip():
+        sys.exit("node failed (%d): %s" % (r.returncode, r.stderr.strip()[-3000:]))
     out = json.loads(r.stdout.strip().splitlines()[-1])
-    print("pairs %d  decode_threads %s  service %.1f pairs/s (node wall %.2fs)" %
-          (n, threads or "auto", n / (out["ms"] / 1e3), wall))
+    rate = n / (out["ms"] / 1e3)
+    if a.json:
+        print(json.dumps({"corpus": a.corpus, "pairs": n, "decode_threads": threads or "auto", "host": os.path.relpath(a.host, ROOT),
+                          "png_kinds": os.environ.get("TW_DEVICE_PNG_KINDS", "1"), "pairs_per_s": round(rate, 1), "ms": out["ms"],
+                          "report": out["report"], "errors": out["errors"]}))
+        return
+    print(r.stdout.strip(), r.stderr.strip()[-3000:])
+    print("pairs %d  decode_threads %s  corpus %s  service %.1f pairs/s (node wall %.2fs)" %
+          (n, threads or "auto", a.corpus, rate, wall))
 
 
 if __name__ == "__main__":
