@@ -401,6 +401,11 @@ tw_status tw_stage_blur_solve(tw_engine* e, const float* R0_5, const float* R1_5
  * at least 320 x 20 pixels; TW_E_UNSUPPORTED otherwise. */
 tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow_in2, const float* prev2,
                              int pw, int ph, int w, int h, float* flow_out2);
+/* The same iteration from flow_in2, evaluated at the span-grid points only (tw_flow_iter's grid-only mode, a batch's last
+ * level-0 iteration): grid_out receives ceil(w / span) x ceil(h / span) (dx, dy) pairs, row-major — the values
+ * tw_stage_flow_iter's field holds at (gx * span, gy * span).  span >= 5; the sizes and statuses of tw_stage_flow_iter. */
+tw_status tw_stage_flow_iter_grid(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow_in2, int w, int h,
+                                  int span, float* grid_out);
 
 #ifdef __cplusplus
 }

@@ -1462,9 +1462,15 @@ FlowIterPlan flow_iter_plan(const tw_engine* e, int w, int h, int npairs)
     fp.nt_last = nsteps - (fp.segments - 1) * fp.nt;
     return fp;
 }
+// grid_pts != null: the grid-only iteration (tw_flow_iter<15, 3>) — flow_in's iteration evaluated at the span-grid points
+// alone, into grid_pts->g; flow_out is not written.  The caller has checked span >= FI_TH (at most one grid row per step).
+struct FlowIterGrid {
+    float2* g;  // pair z: gw * gh points at g + z * gw * gh
+    int span, gw, gh;
+};
 void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long long ps, const float* R, const float* flow_in,
                       long long fps_in, float* flow_out, long long fps_out, const FlowUps* ups, int npairs, int level,
-                      const unsigned* same = nullptr)
+                      const unsigned* same = nullptr, const FlowIterGrid* grid_pts = nullptr)
 {
     FlowIterArgs a;
     memset(&a, 0, sizeof(a));
@@ -1489,6 +1495,18 @@ void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long l
     const dim3 grid(fp.strips, fp.segments, npairs);
     ProfScope pscope(e, st, TW_K_BLUR_SOLVE, level);
     if (ups) set_upsample(a, *ups);
+    if (grid_pts) {
+        // counted as the level's MODE 0 iteration that it is, and in a family of its own
+        a.span = grid_pts->span;
+        a.gw = grid_pts->gw;
+        a.gh = grid_pts->gh;
+        a.gzs = (long long)a.gw * a.gh;
+        a.g = grid_pts->g;
+        e->launches[TW_DF_FLOW_ITER_GRID]++;
+        e->last_grid_z[TW_DF_FLOW_ITER_GRID] = grid.z;
+        TW_LAUNCH(e, TW_DF_FLOW_ITER, (tw_flow_iter<15, 3>), grid, dim3(1024), 0, st, a);
+        return;
+    }
 #ifdef TW_VARIANTS
     if (e->fi_nt == 512) {  // measured 23 % slower (profiles/r05_m_free.md): variants library only
         if (ups) TW_LAUNCH(e, TW_DF_FLOW_ITER_UPS, (tw_flow_iter<15, 1, 512>), grid, dim3(512), 0, st, a);
@@ -1843,10 +1861,12 @@ struct BatchSwitches {
     bool lat_quads;  // TW_LAT_QUADS=0: a single pair's 224 x 8-tile window launches take tw_blur_solve4 as in a batch
     int lat_plan;    // TW_LAT_PLAN: which launches carry the twin schedule's side jobs (plan_twin_side_jobs)
     bool scan_seg;   // TW_SCAN_SEG=0: a single pair's ordered scan as one workgroup (tw_span_scan) — a test compares the two
+    bool grid_final; // TW_GRID_FINAL=0: a batch's last level-0 iteration stores the whole field and tw_span_gather samples it
     BatchSwitches()
         : lat_quads(!getenv("TW_LAT_QUADS") || atoi(getenv("TW_LAT_QUADS")) != 0),
           lat_plan(getenv("TW_LAT_PLAN") ? atoi(getenv("TW_LAT_PLAN")) : 1),
-          scan_seg(!getenv("TW_SCAN_SEG") || atoi(getenv("TW_SCAN_SEG")) != 0)
+          scan_seg(!getenv("TW_SCAN_SEG") || atoi(getenv("TW_SCAN_SEG")) != 0),
+          grid_final(!getenv("TW_GRID_FINAL") || atoi(getenv("TW_GRID_FINAL")) != 0)
     {
     }
 };
@@ -1890,6 +1910,9 @@ struct LevelChunk {
     // scan-fused final iteration (option TW_OPT_SCAN_FUSED_FINAL): nothing but the span grid of the last level-0 flow is
     // read afterwards, so the last window average + solve runs at the grid points only
     bool grid_only;
+    // the grid-only last iteration (tw_flow_iter<15, 3>; BatchEnqueue::grid_final): the chunk's last tw_flow_iter launch writes
+    // the span-grid samples and no field — no tw_span_gather launch
+    bool grid_last;
     // a batch with initial flow fields: every chunk of the coarsest level starts from tw_flow_area_init's output (zeros
     // for its pairs without a field) through the non-zero-flow kernels
     bool init_lv;
@@ -1914,6 +1937,7 @@ struct BatchEnqueue {
     int nlanes = 1;
     size_t ws_lane = 0;
     bool prof_on = false, lat = false, lat2 = false, lat_quads = false, fused_final = false;
+    bool grid_final = false;  // level-0 chunks that run tw_flow_iter end in the grid-only iteration (choose_schedule)
     std::vector<size_t> lat_off;  // a level's offset in lat_I (x 5 in lat_R)
     // the side jobs of the twin schedule, in the order the chain needs their results (empty in every other schedule)
     std::vector<SideJob> sideq;
@@ -2160,6 +2184,9 @@ struct BatchEnqueue {
         }
         // (a batch with a flow destination needs the last level-0 field itself: never the scan-fused final iteration)
         fused_final = scan_fused_level0(e, c.span) && !c.any_fout;
+        // the grid-only last level-0 iteration: a batch that returns hit records alone reads the last field at the span-grid
+        // points only.  (it >= 2: a single iteration is the upsampling one; span >= FI_TH: at most one grid row per step)
+        grid_final = sw.grid_final && !lat && !e->scan_fused && !c.any_fout && it >= 2 && c.span >= FI_TH && e->fi_nt == 1024;
         return TW_OK;
     }
 
@@ -2298,6 +2325,7 @@ struct BatchEnqueue {
         ch.flow_cur = e->flow[k] + (k == 0 ? (size_t)lane * L.chunk * 2 * L.ps : (size_t)j0 * 2 * L.ps);
         ch.flow_prev = k < pl->levels ? e->flow[k + 1] + (size_t)j0 * 2 * pl->lv[k + 1].ps : nullptr;
         ch.grid_only = k == 0 && fused_final;
+        ch.grid_last = k == 0 && grid_final && level_mfree(0, nc);
         ch.init_lv = c.any_init && k == pl->levels;
         return ch;
     }
@@ -2595,6 +2623,11 @@ struct BatchEnqueue {
         for (int i = 0; i < nfi; i++) {
             float* out = buf[(nfi - 1 - i) & 1];
             const float* in = i == 0 ? (ch.init_lv ? buf[nfi & 1] : nullptr) : buf[(nfi - i) & 1];
+            if (ch.grid_last && i == nfi - 1) {  // (i >= 1: `in` is the field of iteration i - 1)
+                const FlowIterGrid gp{grid_of(ch.j0), c.span, gw, gh};
+                launch_flow_iter(e, ch.ls, L.w, L.h, L.ld, L.ps, ch.R, in, L.ps, nullptr, L.ps, nullptr, nc, k, same_flags_of(ch), &gp);
+                break;
+            }
             launch_flow_iter(e, ch.ls, L.w, L.h, L.ld, L.ps, ch.R, in, L.ps, out, L.ps,
                              (i == 0 && k < pl->levels) ? &ups : nullptr, nc, k, same_flags_of(ch));
         }
@@ -2703,7 +2736,7 @@ struct BatchEnqueue {
     tw_status enqueue_level0_outputs(const LevelChunk& ch, bool grid_stored)
     {
         if (ch.k != 0) return TW_OK;
-        if (c.span > 0 && !ch.grid_only && !grid_stored) enqueue_span_gather(ch);
+        if (c.span > 0 && !ch.grid_only && !ch.grid_last && !grid_stored) enqueue_span_gather(ch);
         if (c.any_fout) return export_chunk(e, c, ch.ls, pl->lv[0], ch.flow_cur, ch.j0, ch.nc, fslot);
         return TW_OK;
     }
@@ -4303,7 +4336,8 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pair_same",
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_iter_grid",
+        "tw_pair_same",
         "tw_resize_u8", "tw_flow_area_init", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
 }
@@ -4939,6 +4973,39 @@ tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5,
     TW_HIP(e, hipGetLastError());
     TW_HIP(e, hipStreamSynchronize(st));
     return down_planes(e, flow_out2, d_fo, ld, ps, w, h, 2);
+}
+
+tw_status tw_stage_flow_iter_grid(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow_in2, int w, int h, int span,
+                                  float* grid_out)
+{
+    if (!e || !R0_5 || !R1_5 || !flow_in2 || !grid_out || span < FI_TH) return TW_E_BAD_PARAMETER;
+    tw_status r;
+    if ((r = check_dims(e, w, h))) return r;
+    if (!flow_iter_eligible(e, w, h) || e->fi_nt != 1024) {
+        e->err = "tw_stage_flow_iter_grid: winSize 30/31 Gaussian window and a level of at least TW_MFREE_MIN_W (320) x 20 pixels";
+        return TW_E_UNSUPPORTED;
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    const int ld = round_up(w, 32);
+    const long long ps = (long long)ld * h;
+    const int gw = (w + span - 1) / span, gh = (h + span - 1) / span;
+    const size_t npts = (size_t)gw * gh;
+    Tmp t;
+    float *d_R = t.alloc<float>(ps * 10), *d_fi = t.alloc<float>(ps * 2);
+    float2* d_g = t.alloc<float2>(npts);
+    if (!d_R || !d_fi || !d_g) return TW_E_NOMEM;
+    if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
+        (r = up_planes(e, d_fi, ld, ps, flow_in2, w, h, 2)))
+        return r;
+    hipStream_t st = e->stream;
+    // (0xff bytes: a point the launch did not write reads back as NaN)
+    TW_HIP(e, hipMemsetAsync(d_g, 0xff, npts * sizeof(float2), st));
+    const FlowIterGrid gp{d_g, span, gw, gh};
+    launch_flow_iter(e, st, w, h, ld, ps, d_R, d_fi, ps, nullptr, ps, nullptr, 1, -1, nullptr, &gp);
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    TW_HIP(e, hipMemcpy(grid_out, d_g, npts * sizeof(float2), hipMemcpyDeviceToHost));
+    return TW_OK;
 }
 
 }  // extern "C"

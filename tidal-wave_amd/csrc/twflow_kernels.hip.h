@@ -2198,9 +2198,14 @@ struct FlowIterArgs {
     int nt;         // steps (of FI_TH rows) per workgroup; grid.y segments cover the rows
     int zero_flow;  // input flow = 0 (coarsest level), nothing is read
     // UPS: upsample source (the coarser level's final flow) and its resize tables, as UpdArgs
-    const float* prev;
-    int pw, ph, pld;
-    long long pfps;
+    // MODE 3 (the grid-only last iteration never upsamples) keeps its span grid in the first five of them, laid out as
+    // BlurGridArgs / GatherArgs have it — pair z's gw * gh points at g + z * gzs.  Unions, not new members: the struct's size
+    // is part of every mode's code (the offsets of the hidden arguments behind it), and modes 0 - 2 stay the code they were
+    union { const float* prev; float2* g; };
+    union { int pw; int span; };
+    union { int ph; int gw; };
+    union { int pld; int gh; };
+    union { long long pfps; long long gzs; };
     const int* xofs;
     const float* alpha;
     const int* yofs;
@@ -2234,6 +2239,10 @@ struct FlowIterArgs {
 // load at all).  A template parameter, not a runtime flag: with the three sources behind one join the compiler copied the
 // freshly loaded flow into the loop-carried registers AFTER the join — an s_waitcnt vmcnt(0) on loads issued a few
 // instructions earlier, in every step.
+// MODE 3: MODE 0's iteration evaluated at the span-grid points only — the last level-0 iteration of a batch that returns
+// nothing but hit records.  Phase C (FarnebackUpdateMatrices into the ring) runs at every pixel as in MODE 0; V, H and S run
+// only in the steps that hold a grid row, V for that one row, H and S at the grid columns; the samples go to a.g and no flow
+// is stored.  Its code sits in one `if constexpr` block behind the prologue: the other modes compile to what they were.
 template <int MH, int MODE, int NT = 1024>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void tw_flow_iter(FlowIterArgs a)
 {
@@ -2347,7 +2356,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     };
     const __amdgpu_buffer_rsrc_t rsp = make_rsrc(UPS ? (const void*)prev : (const void*)R0);  // UPS: the coarser level's flow
     const unsigned prev_p1 = UPS ? (unsigned)(a.pfps * 4) : 0u, sxb = (unsigned)sx * 4u, sx1b = (unsigned)sx1 * 4u;
-    const __amdgpu_buffer_rsrc_t rsf = make_rsrc(MODE == 0 ? (const void*)fin : (const void*)R0);  // the input flow's two planes
+    const __amdgpu_buffer_rsrc_t rsf = make_rsrc((MODE == 0 || MODE == 3) ? (const void*)fin : (const void*)R0);  // the input flow's two planes
     const unsigned fin_p1 = (unsigned)(a.fps_in * 4);
     auto flow_issue = [&](int k, FlowIn& f) {
         const int yc = row_of(k);
@@ -2497,6 +2506,136 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         // vmcnt(0), before the copy.
     }
     __syncthreads();
+
+    if constexpr (MODE == 3) {
+        // ---- the grid-only iteration: phase C as in step_deep below (same loads, same registers, same ring), the window sums
+        // and the solve only where a span-grid point (gx * span, gy * span) is.  With span >= TH a step of TH rows holds at most
+        // one grid row, r* rows below the step's first:
+        //   grid step      V: thread (plane, column) sums the 31 ring rows around row r* into row 0 of block X;  barrier;
+        //                  H: thread (plane, grid column of the strip; at most 5 x 32) sums the 31 values of X around its column
+        //                  into block Y;  barrier;  S: wave 15, one lane per grid column, the 2x2 solve in double and the
+        //                  float2 store into the grid — beside C on the other waves;  barrier
+        //   any other step C;  barrier
+        // Every value is the expression of MODE 0's V, H and S in their order.  The step's loads go out in three groups (before V,
+        // H and C): there is no arithmetic left that a burst of them could starve.
+        static_assert(NT == 1024 && DEEP && SPLIT && OUT / FI_TH <= 32, "the grid-only iteration: 1024 threads, two tap sets, wave 15 free");
+        const int span = a.span;
+        // THE ONE PLACE that says which steps are grid steps: r* of step st (and its grid row gy), -1 for a step without one.
+        // A function of (ys, st, span, gh) alone — uniform over the workgroup; wave 15's loop and the other waves' both take
+        // their barrier count from it
+        auto grid_row = [&](int st, int& gy) {
+            const int y0 = ys + TH * st;
+            gy = __builtin_amdgcn_readfirstlane((y0 + span - 1) / span);
+            const int r = gy * span - y0;
+            return (r < TH && gy < a.gh) ? r : -1;
+        };
+        // the strip's grid columns: gx0 + i at output column (gx0 + i) * span - bx * OUT < OUT, i < 32
+        const int gx0 = (bx * OUT + span - 1) / span;
+        if (tid >= VWAVES * 64) {
+            // wave 15: S.  Three barriers in a grid step, one in any other — as step_grid below
+            const int gi = tid - VWAVES * 64, gx = gx0 + gi;
+            const bool sth = gi < 32 && gx < a.gw && gx * span - bx * OUT < OUT;
+            float2* __restrict__ gout = a.g + (long long)z * a.gzs;
+#pragma unroll 1
+            for (int st = 0; st < nsteps; st++) {
+                const int s0 = st & (NB - 1);
+                int gy;
+                if (grid_row(st, gy) >= 0) {
+                    TW_FI_SYNC();  // (V)
+                    TW_FI_SYNC();  // (H)
+                    if (sth) {
+                        const double g11 = blk[s0][0][0][gi], g12 = blk[s0][1][0][gi], g22 = blk[s0][2][0][gi],
+                                     h1 = blk[s0][3][0][gi], h2 = blk[s0][4][0][gi];
+                        const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
+                        float2 o;
+                        o.x = (float)((g11 * h2 - g12 * h1) * idet);
+                        o.y = (float)((g22 * h1 - g12 * h2) * idet);
+                        gout[(long long)gy * a.gw + gx] = o;
+                    }
+                }
+                TW_FI_SYNC();  // (C, S)
+            }
+            return;
+        }
+        // H thread: (plane gp, grid column gi of the strip)
+        const int gp = tid >> 5, gi = tid & 31, ghx = (gx0 + gi) * span - bx * OUT;
+        const bool gth = tid < 5 * 32 && gx0 + gi < a.gw && ghx < OUT;
+        // V of the ring's row r* + MH (r* = R): the window's row t is row (R + t) % TH of chunk st + (R + t) / TH
+        auto v_row = [&](auto rc, int s0, int bX) {
+            constexpr int R = decltype(rc)::value;
+            float wv[2 * MH + 1];
+#pragma unroll
+            for (int t = 0; t <= 2 * MH; t++) wv[t] = blk[(s0 + (R + t) / TH) & (NB - 1)][cr][(R + t) % TH][cc];
+            float sv = wv[MH] * c.k[0];
+#pragma unroll
+            for (int i = 1; i <= MH; i++) sv += (wv[MH + i] + wv[MH - i]) * c.k[i];
+            blk[bX][cr][0][cc] = sv;
+        };
+        // One step; the registers' roles are step_deep's: (dxc, dyc, Tc) the chunk this step turns into M (st + NCH), its taps
+        // issued a step ago; Tn the chunk after it, its taps go out during this step; R0 of chunk st + NCH first of all (the
+        // combine waits for nothing younger), the flow of chunk st + NCH + 2 before it.
+        auto step_grid = [&](int st, float& dxc, float& dyc, UpdTaps& Tc, UpdTaps& Tn) {
+            const bool more = st + 1 < nsteps;
+            const int s0 = st & (NB - 1), bX = (st + NCH) & (NB - 1);
+            int gy;
+            const int rs = grid_row(st, gy);
+            if (cth) {
+                flow_issue(st + NCH + 2, fnext);
+                gq = (unsigned)(row_of(st + NCH) * a.ld + xc) * 4u;
+#pragma unroll
+                for (int ch = 0; ch < 5; ch++) gather_r0(ch, q);
+#pragma unroll
+                for (int u = 0; u < 4; u++) gather_half(u >> 1, u & 1, Tn);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (rs >= 0) {
+                if (cth) {
+                    switch (rs) {
+                    case 0: v_row(std::integral_constant<int, 0>(), s0, bX); break;
+                    case 1: v_row(std::integral_constant<int, 1>(), s0, bX); break;
+                    case 2: v_row(std::integral_constant<int, 2>(), s0, bX); break;
+                    case 3: v_row(std::integral_constant<int, 3>(), s0, bX); break;
+                    default: v_row(std::integral_constant<int, 4>(), s0, bX); break;
+                    }
+                }
+                TW_FI_SYNC();  // (V)
+            }
+            if (cth) {
+#pragma unroll
+                for (int u = 4; u < 7; u++) gather_half(u >> 1, u & 1, Tn);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (rs >= 0) {
+                if (gth) {
+                    const float* v = &blk[bX][gp][0][ghx + MH];
+                    float sum = v[0] * c.k[0];
+#pragma unroll
+                    for (int i = 1; i <= MH; i++) sum += c.k[i] * (v[-i] + v[i]);
+                    blk[s0][gp][0][gi] = sum;
+                }
+                TW_FI_SYNC();  // (H)
+            }
+            if (cth) {
+#pragma unroll
+                for (int u = 7; u < 10; u++) gather_half(u >> 1, u & 1, Tn);
+                __builtin_amdgcn_sched_barrier(0);
+                if (more) combine_store(st + NCH, dxc, dyc, q, Tc);
+                __builtin_amdgcn_sched_barrier(0);
+                flow_value(fnext, dxc, dyc);
+                gather_head(st + NCH + 2, dxc, dyc, q, Tc, false);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            TW_FI_SYNC();  // (C, S)
+        };
+        int st = 0;
+#pragma unroll 1
+        for (; st + 1 < nsteps; st += 2) {
+            step_grid(st, dx, dy, T, Tb);
+            step_grid(st + 1, dxb, dyb, Tb, T);
+        }
+        if (st < nsteps) step_grid(st, dx, dy, T, Tb);
+        return;
+    }
 
     // H thread: (plane hp, row hr, 4-pixel group hq) — 1 000 of the 1 024 threads; S thread: one output pixel (sr, sc)
     constexpr int NQ = OUT / 4;

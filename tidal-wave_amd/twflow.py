@@ -72,6 +72,7 @@ SYMBOLS = [
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
+    "tw_stage_flow_iter_grid",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
     "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time",
@@ -217,6 +218,7 @@ def _bind(path):
     L.tw_stage_pyr_fused23.argtypes = [vp, u8p, C.c_int, C.c_int, fp, fp]
     L.tw_stage_pyr_fused01.argtypes = [vp, u8p, C.c_int, C.c_int, fp, fp]
     L.tw_stage_flow_iter.argtypes = [vp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp]
+    L.tw_stage_flow_iter_grid.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, fp]
     L.tw_stage_polyexp.argtypes = [vp, fp, C.c_int, C.c_int, fp]
     L.tw_stage_update_matrices.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, fp]
     L.tw_stage_flow_upsample_update.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp]
@@ -810,6 +812,17 @@ class Engine:
         null = C.POINTER(C.c_float)()
         self._check(self._L.tw_stage_flow_iter(self._h, _f(R0), _f(R1), _f(fin) if fin is not None else null,
                                                _f(pv) if pv is not None else null, pw, ph, w, h, _f(out)))
+        return out
+
+    def stage_flow_iter_grid(self, R0, R1, flow, span):
+        """The same iteration from `flow` (2, h, w), evaluated at the span-grid points only (tw_flow_iter's grid-only mode):
+        (ceil(h / span), ceil(w / span), 2) — (dx, dy) of the points (gx * span, gy * span)."""
+        R0 = np.ascontiguousarray(R0, np.float32)
+        R1 = np.ascontiguousarray(R1, np.float32)
+        flow = np.ascontiguousarray(flow, np.float32)
+        _, h, w = R0.shape
+        out = np.empty((-(-h // span), -(-w // span), 2), np.float32)
+        self._check(self._L.tw_stage_flow_iter_grid(self._h, _f(R0), _f(R1), _f(flow), w, h, int(span), _f(out)))
         return out
 
     def stage_blur_solve(self, R0, R1, M, update_matrices):
