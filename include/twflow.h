@@ -406,6 +406,17 @@ tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5,
  * tw_stage_flow_iter's field holds at (gx * span, gy * span).  span >= 5; the sizes and statuses of tw_stage_flow_iter. */
 tw_status tw_stage_flow_iter_grid(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow_in2, int w, int h,
                                   int span, float* grid_out);
+/* The span-grid threshold scan alone, on the caller's own fields: `fields` = npairs dense planar flow fields
+ * [npairs][2][h][w] (dx plane, dy plane), uploaded into level 0's padded planes; tw_span_gather samples them at every
+ * span-th pixel and the ordered scan a submit of such a batch would launch — tw_span_scan, or tw_span_scan_seg for
+ * single_pair = 1 on a grid large enough (tw_debug_scan_plan) — records every point with
+ * (double)(float)(dx * dx + dy * dy) > threshold * threshold, row-major.  With G = ceil(w / span) * ceil(h / span):
+ * counts[npairs]; xy[npairs][G][2] = (x, y) and dxy[npairs][G][2] = (dx, dy) as the device holds them (floats, not
+ * tw_vector's doubles) — a pair's WHOLE record region: the counts and the records are set to 0xff bytes before the
+ * launches, so an entry from counts[j] on that is not 0xffffffff was written beyond the hits, and a count of -1 was never
+ * stored.  span >= 1; single_pair = 1 takes npairs = 1, else TW_E_BAD_PARAMETER.  (Additive within version 4.) */
+tw_status tw_stage_span_scan(tw_engine* e, const float* fields, int npairs, int w, int h, int span, double threshold,
+                             int single_pair, int* counts, int* xy, float* dxy);
 
 #ifdef __cplusplus
 }

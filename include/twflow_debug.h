@@ -98,6 +98,16 @@ int tw_debug_flow_iter_plan(const tw_engine* e, int width, int height, int npair
  * tests/test_gpu_blur_dispatch.py proves from it which side of each edge of the choice ran. */
 int tw_debug_blur_plan(const tw_engine* e, int width, int height, int level, int npairs, int update, int quads, int* out, int n);
 
+/* The choice of the ordered scan's launch for npairs pairs of width x height pixels at `span`, from the one function the
+ * launch itself takes its kernel from (choose_scan): out[0] the kernel (0: tw_span_scan, one workgroup per pair; 1:
+ * tw_span_scan_seg, one workgroup per segment), out[1] gw, out[2] gh, out[3] G = gw * gh grid points, out[4] S, the points of
+ * a segment, out[5] segments (S and segments are 0 for kernel 0), out[6] rounds of 32 768 points a workgroup runs (1 for
+ * kernel 1).  `single_pair`: whether the batch takes the single-pair schedule (a batch of one pair of at least
+ * TW_LATENCY_MIN_PX = 100 000 pixels does, unless TW_LATENCY_STREAMS=0); TW_SCAN_SEG is read at the call, as every batch reads it.  Returns the number of values
+ * written (at most min(n, 7); 0 for a null `out`, a non-positive size, span or pair count), -1 for a null engine.
+ * tests/test_gpu_span_scan.py takes its grids' seams from it. */
+int tw_debug_scan_plan(const tw_engine* e, int width, int height, int span, int npairs, int single_pair, int* out, int n);
+
 /* tw_pair_same's flags of the batch this engine enqueued last: out[j] = 1 where pair j's second image is byte for byte its
  * first over the visible width x height pixels (the batch schedule then computed that pair's polynomial expansions once at
  * the levels tw_flow_iter runs), 0 otherwise — and 0 for every pair of a batch that launched no tw_pair_same (TW_SAME_IMAGE=0,

@@ -1885,6 +1885,45 @@ const ProcessSwitches& process_switches()
     return s;
 }
 
+// ---- the ordered scan's kernel -----------------------------------------------------------------------------
+// Which kernel compacts the hits of npairs span grids of gw x gh points, as one pure function: enqueue_scan and
+// tw_stage_span_scan launch what it names (launch_scan), and tw_debug_scan_plan shows it to the tests.
+//   kernel 0: tw_span_scan<false>, one workgroup per pair, `rounds` rounds of SCAN_IT * 1024 points each (S and segments 0)
+//   kernel 1: tw_span_scan_seg, a single pair (single_pair: the batch takes the single-pair schedule) of more than 2 048
+//             points in `segments` workgroups of S points — a sixteenth of the grid rounded up to whole iterations of 1 024,
+//             at most one round, so the last segment may hold as little as one point — unless TW_SCAN_SEG=0 (scan_seg)
+struct ScanChoice {
+    int kernel;
+    long long G;
+    int S, segments, rounds;
+};
+ScanChoice choose_scan(int npairs, bool single_pair, int gw, int gh, bool scan_seg)
+{
+    ScanChoice c;
+    c.G = (long long)gw * gh;
+    const int round = SCAN_IT * 1024;
+    const int S = (int)(((c.G + 15) / 16 + 1023) / 1024 * 1024);
+    if (npairs == 1 && single_pair && scan_seg && c.G > 2048 && S <= round) {
+        c.kernel = 1;
+        c.S = S;
+        c.segments = (int)((c.G + S - 1) / S);
+        c.rounds = 1;
+    } else {
+        c.kernel = 0;
+        c.S = 0;
+        c.segments = 0;
+        c.rounds = (int)((c.G + round - 1) / round);
+    }
+    return c;
+}
+void launch_scan(tw_engine* e, hipStream_t st, const ScanArgs& a, const ScanChoice& sc, int npairs)
+{
+    if (sc.kernel == 1)
+        TW_LAUNCH(e, TW_DF_SPAN_SCAN_SEG, tw_span_scan_seg, dim3((unsigned)sc.segments), dim3(1024), 0, st, a, sc.S);
+    else
+        TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<false>, dim3(npairs), dim3(1024), 0, st, a);
+}
+
 // One row of tw_flow_export's destination table / tw_flow_area_init's source table: the caller's device memory in place,
 // or (staged != null) this context's staging slot — dense rows in the field's own layout; null for a pair without a field
 FlowDst flow_table_row(const void* data, ptrdiff_t pitch, int layout, char* staged, int w)
@@ -2265,12 +2304,7 @@ struct BatchEnqueue {
 #endif
             {
                 // a single pair: 16 segments, each workgroup counting the hits before its own (tw_span_scan_seg: -5 us of one CU's VALU time)
-                const long long G = (long long)a.gw * a.gh;
-                const int S = (int)(((G + 15) / 16 + 1023) / 1024 * 1024);
-                if (n == 1 && lat && sw.scan_seg && G > 2048 && S <= SCAN_IT * 1024)
-                    TW_LAUNCH(e, TW_DF_SPAN_SCAN_SEG, tw_span_scan_seg, dim3((unsigned)((G + S - 1) / S)), dim3(1024), 0, st, a, S);
-                else
-                    TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<false>, dim3(n), dim3(1024), 0, st, a);
+                launch_scan(e, st, a, choose_scan(n, lat, a.gw, a.gh, sw.scan_seg), n);
             }
         }
         TW_HIP(e, hipEventRecord(c.ev_stop, st));
@@ -4300,6 +4334,19 @@ extern "C" int tw_debug_blur_plan(const tw_engine* e, int width, int height, int
     return i;
 }
 
+extern "C" int tw_debug_scan_plan(const tw_engine* e, int width, int height, int span, int npairs, int single_pair, int* out, int n)
+{
+    if (!e) return -1;
+    if (!out || width < 1 || height < 1 || span < 1 || npairs < 1) return 0;
+    const int gw = (width + span - 1) / span, gh = (height + span - 1) / span;
+    const ScanChoice c = choose_scan(npairs, single_pair != 0, gw, gh, BatchSwitches().scan_seg);
+    if (c.G > INT32_MAX) return 0;
+    const int v[7] = {c.kernel, gw, gh, (int)c.G, c.S, c.segments, c.rounds};
+    int i = 0;
+    for (; i < n && i < 7; i++) out[i] = v[i];
+    return i;
+}
+
 extern "C" int tw_debug_launch_counts(tw_engine* e, unsigned long long* counts, unsigned long long* last_z, int n, int reset)
 {
     if (!e) return -1;
@@ -5005,6 +5052,69 @@ tw_status tw_stage_flow_iter_grid(tw_engine* e, const float* R0_5, const float* 
     TW_HIP(e, hipGetLastError());
     TW_HIP(e, hipStreamSynchronize(st));
     TW_HIP(e, hipMemcpy(grid_out, d_g, npts * sizeof(float2), hipMemcpyDeviceToHost));
+    return TW_OK;
+}
+
+tw_status tw_stage_span_scan(tw_engine* e, const float* fields, int npairs, int w, int h, int span, double threshold, int single_pair,
+                             int* counts, int* xy, float* dxy)
+{
+    if (!e || !fields || !counts || !xy || !dxy || npairs < 1 || span < 1 || (single_pair != 0 && single_pair != 1) ||
+        (single_pair && npairs != 1))
+        return TW_E_BAD_PARAMETER;
+    tw_status r;
+    if ((r = check_dims(e, w, h))) return r;
+    TW_HIP(e, hipSetDevice(e->device));
+    Plan* pl = nullptr;
+    if ((r = get_plan(e, w, h, &pl))) return r;
+    const LevelPlan& L = pl->lv[0];
+    const int gw = (w + span - 1) / span, gh = (h + span - 1) / span;
+    const size_t G = (size_t)gw * gh, nrec = G * (size_t)npairs;
+    Tmp t;
+    float* d_f = t.alloc<float>((size_t)L.ps * 2 * npairs);
+    float2* d_g = t.alloc<float2>(nrec);
+    ScanRec* d_rec = t.alloc<ScanRec>(nrec);
+    int* d_cnt = t.alloc<int>(npairs);
+    if (!d_f || !d_g || !d_rec || !d_cnt) return TW_E_NOMEM;
+    for (int j = 0; j < npairs; j++)
+        if ((r = up_planes(e, d_f + (size_t)j * 2 * L.ps, L.ld, L.ps, fields + (size_t)j * 2 * w * h, w, h, 2))) return r;
+    hipStream_t st = e->stream;
+    // (0xff bytes: a count the scan did not store reads back as -1, a record it did not write as four 0xffffffff words)
+    TW_HIP(e, hipMemsetAsync(d_cnt, 0xff, sizeof(int) * (size_t)npairs, st));
+    TW_HIP(e, hipMemsetAsync(d_rec, 0xff, nrec * sizeof(ScanRec), st));
+    GatherArgs g;
+    g.flow = d_f;
+    g.fzs = 2 * L.ps;
+    g.fps = L.ps;
+    g.ld = L.ld;
+    g.span = span;
+    g.gw = gw;
+    g.gh = gh;
+    g.g = d_g;
+    TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((gw + 63) / 64, (gh + 3) / 4, npairs), dim3(256), 0, st, g);
+    ScanArgs a;
+    a.g = d_g;
+    a.span = span;
+    a.gw = gw;
+    a.gh = gh;
+    a.thr2 = threshold * threshold;
+    a.count = d_cnt;
+    a.rec_zs = (long long)G;
+    a.rec = d_rec;
+    a.flow = d_f;
+    a.fps = L.ps;
+    a.ld = L.ld;
+    launch_scan(e, st, a, choose_scan(npairs, single_pair != 0, gw, gh, BatchSwitches().scan_seg), npairs);
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    TW_TRY(d2h_sync(e, counts, d_cnt, sizeof(int) * (size_t)npairs));
+    std::vector<ScanRec> hr(nrec);
+    TW_TRY(d2h_sync(e, hr.data(), d_rec, nrec * sizeof(ScanRec)));
+    for (size_t i = 0; i < nrec; i++) {
+        xy[2 * i] = hr[i].x;
+        xy[2 * i + 1] = hr[i].y;
+        dxy[2 * i] = hr[i].dx;
+        dxy[2 * i + 1] = hr[i].dy;
+    }
     return TW_OK;
 }
 

@@ -72,10 +72,10 @@ SYMBOLS = [
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
-    "tw_stage_flow_iter_grid",
+    "tw_stage_flow_iter_grid", "tw_stage_span_scan",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
-    "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time",
+    "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time", "tw_debug_scan_plan",
 ]
 
 
@@ -219,6 +219,7 @@ def _bind(path):
     L.tw_stage_pyr_fused01.argtypes = [vp, u8p, C.c_int, C.c_int, fp, fp]
     L.tw_stage_flow_iter.argtypes = [vp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp]
     L.tw_stage_flow_iter_grid.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, fp]
+    L.tw_stage_span_scan.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, ip, ip, fp]
     L.tw_stage_polyexp.argtypes = [vp, fp, C.c_int, C.c_int, fp]
     L.tw_stage_update_matrices.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, fp]
     L.tw_stage_flow_upsample_update.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp]
@@ -245,6 +246,8 @@ def _bind(path):
     L.tw_debug_flow_iter_plan.restype = C.c_int
     L.tw_debug_blur_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.tw_debug_blur_plan.restype = C.c_int
+    L.tw_debug_scan_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
+    L.tw_debug_scan_plan.restype = C.c_int
     L.tw_debug_same_flags.argtypes = [vp, C.POINTER(C.c_uint), C.c_int]
     L.tw_debug_same_flags.restype = C.c_int
     return L
@@ -252,6 +255,7 @@ def _bind(path):
 
 FlowIterPlan = collections.namedtuple("FlowIterPlan", "strips segments nt nt_last")
 BlurPlan = collections.namedtuple("BlurPlan", "family block tile_cols rows xsh grid_x grid_y small forced")
+ScanPlan = collections.namedtuple("ScanPlan", "kernel gw gh G S segments rounds")
 
 
 class LaunchCounts(dict):
@@ -705,6 +709,16 @@ class Engine:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_blur_plan(%d, %d, %d, %d) returned %d" % (w, h, level, npairs, n))
         return BlurPlan(self._L.tw_debug_family_name(v[0]).decode(), *v[1:8], bool(v[8]))
 
+    def scan_plan(self, w, h, span, npairs=1, single_pair=False):
+        """The choice of the ordered scan's launch for npairs pairs of w x h pixels at `span`, from the function the launch
+        itself uses (twflow_debug.h: tw_debug_scan_plan): the kernel's family name, the grid's width, height and points G,
+        the points S of a segment and the segments (0 for tw_span_scan), the rounds of 32 768 points a workgroup runs."""
+        v = (C.c_int * 7)()
+        n = self._L.tw_debug_scan_plan(self._h, w, h, int(span), npairs, int(bool(single_pair)), v, 7)
+        if n != 7:
+            raise TwError(TW_E_BAD_PARAMETER, "tw_debug_scan_plan(%d, %d, %d, %d) returned %d" % (w, h, span, npairs, n))
+        return ScanPlan(("tw_span_scan", "tw_span_scan_seg")[v[0]], *v[1:7])
+
     def same_flags(self):
         """tw_pair_same's flags of the batch enqueued last, one per pair: 1 where the pair's second image is byte for byte
         its first (twflow_debug.h: tw_debug_same_flags); all 0 when no tw_pair_same ran (TW_SAME_IMAGE=0, a single pair).
@@ -824,6 +838,23 @@ class Engine:
         out = np.empty((-(-h // span), -(-w // span), 2), np.float32)
         self._check(self._L.tw_stage_flow_iter_grid(self._h, _f(R0), _f(R1), _f(flow), w, h, int(span), _f(out)))
         return out
+
+    def stage_span_scan(self, fields, span, threshold, single_pair=False):
+        """The span-grid scan alone (tw_span_gather + the ordered scan scan_plan names) on `fields` (npairs, 2, h, w):
+        (counts [npairs] int32, xy [npairs, G, 2] int32, dxy [npairs, G, 2] float32) — every pair's whole record region;
+        what the kernels did not write holds 0xff bytes (a count of -1)."""
+        fields = np.ascontiguousarray(fields, np.float32)
+        npairs, two, h, w = fields.shape
+        assert two == 2
+        sp = max(int(span), 1)  # (a span below 1 is the library's to refuse)
+        G = (-(-h // sp)) * (-(-w // sp))
+        counts = np.zeros(npairs, np.int32)
+        xy = np.zeros((npairs, G, 2), np.int32)
+        dxy = np.zeros((npairs, G, 2), np.float32)
+        self._check(self._L.tw_stage_span_scan(self._h, _f(fields), npairs, w, h, int(span), float(threshold),
+                                               int(bool(single_pair)), counts.ctypes.data_as(C.POINTER(C.c_int)),
+                                               xy.ctypes.data_as(C.POINTER(C.c_int)), _f(dxy)))
+        return counts, xy, dxy
 
     def stage_blur_solve(self, R0, R1, M, update_matrices):
         R0 = np.ascontiguousarray(R0, np.float32)
