@@ -268,6 +268,31 @@ int tw_png_on_device(int color_type, int bit_depth, int interlace);
 tw_status tw_submit_png(tw_engine* e, const tw_png_rows* expect, const tw_png_rows* target, int span, double threshold,
                         const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket);
 
+/* JPEG on the device (additive within ABI 4, detected by the symbols).  tw_submit_jpeg is tw_submit_u8_sized for images
+ * handed over after their entropy decode: what cv::imread(path, GRAYSCALE) does to a JPEG's luma blocks after the Huffman
+ * work — dequantisation, libjpeg's slow integer inverse DCT (jidctint), level shift and range limit, the crop to the
+ * image — runs on the device (kernel tw_jpeg_idct, on the copy stream where tw_png_unfilter runs: it is not in `seconds`),
+ * so a host decode thread stops at the coefficient plane.  The result equals tw_submit_u8 on the host-decoded images bit
+ * for bit, for every int16 coefficient and uint16 table entry (a damaged file reaches the extremes).
+ * An image is its coefficients (coef != NULL) or a plain gray image (coef == NULL, gray != NULL), so a pair may mix a JPEG
+ * with an image the host decoded; with both coef NULL the call IS tw_submit_u8_sized: the same launches, no tw_jpeg_idct
+ * launch.  The pair's size is the expected image's; a target within 5 pixels is reconciled by tw_resize_u8 as
+ * tw_submit_png8_sized does it, one further apart answers TW_E_DONT_MATCH_SIZE.  Both sizes go through the size predicate
+ * of every submit.  Refused with TW_E_BAD_PARAMETER before anything is queued (no ticket consumed, the open batch
+ * unchanged): an image with both pointers NULL, block counts outside ceil(size / 8) .. ceil(size / 8) + 3.  Page-locked
+ * coefficient planes are DMA-ed in place (keep them until tw_wait); pageable ones are copied before the call returns.  A
+ * batch with JPEG images is launched as a PNG batch is: no cold-start ramp. */
+typedef struct tw_jpeg_luma {
+    const int16_t* coef;    /* blocks_w*blocks_h blocks, row-major, 64 quantised coefficients each, natural order;
+                               NULL: `gray` is a plain gray image, dense rows of `width` bytes */
+    const uint8_t* gray;
+    int width, height;      /* this image's own size */
+    int blocks_w, blocks_h; /* ceil(width/8) .. ceil(width/8)+3, likewise for height (whole MCUs) */
+    uint16_t quant[64];     /* luma table, natural order */
+} tw_jpeg_luma;
+tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* expect, const tw_jpeg_luma* target, int span, double threshold,
+                         const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 
@@ -387,6 +412,11 @@ tw_status tw_stage_png_decode(tw_engine* e, const tw_png_rows* img, int waves, u
 /* The size reconcile's kernel alone (tw_resize_u8): dense src (sw x sh) -> dense dst (dw x dh), cv::resize's 8-bit
  * INTER_LINEAR.  Sizes more than 5 pixels apart answer TW_E_DONT_MATCH_SIZE. */
 tw_status tw_stage_resize_u8(tw_engine* e, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh);
+/* tw_submit_jpeg's kernel alone (tw_jpeg_idct) on one image that has coefficients: `gray` receives width * height bytes.
+ * `guard`, if not NULL, receives 512 bytes: the 256 device bytes in front of the image and the 256 behind it, which the
+ * entry point set to 0xA5 before the launch — a byte that is not 0xA5 was written outside the image.  (Additive within
+ * version 4.) */
+tw_status tw_stage_jpeg_idct(tw_engine* e, const tw_jpeg_luma* img, uint8_t* gray, uint8_t* guard);
 tw_status tw_stage_polyexp(tw_engine* e, const float* I, int w, int h, float* R5);
 tw_status tw_stage_update_matrices(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow2,
                                    int w, int h, float* M5);

@@ -320,6 +320,8 @@ constexpr int HOST_RECS = 1024;  // flagged vectors per pair copied back eagerly
 constexpr int NCTX = 3;          // batches that may be in flight (host-side state only)
 // tw_png_unfilter's table of a batch of `cap` pairs: per image a job, a flag word and a 256-byte gray table
 constexpr size_t png_table_bytes(int cap) { return (sizeof(PngJob) + sizeof(unsigned) + 256) * 2 * (size_t)cap; }
+// tw_jpeg_idct's table of such a batch: per image a job and a quantisation table
+constexpr size_t jpeg_table_bytes(int cap) { return (sizeof(JpegJob) + 128) * 2 * (size_t)cap; }
 
 struct Job {
     const uint8_t *h_a = nullptr, *h_b = nullptr;  // host inputs already staged (null for device inputs)
@@ -329,14 +331,17 @@ struct Job {
     int png_ch[2] = {0, 0};  // tw_submit_png8: channels of the filtered rows staged in Ctx::d_filt (0: plain gray)
     // tw_submit_png: PngJob::bits and ::entries of those rows, and their gray table in Ctx::png_luts (-1: not a table kind)
     int png_bits[2] = {0, 0}, png_entries[2] = {256, 256}, png_lut[2] = {-1, -1};
+    // tw_submit_jpeg: blocks per block row of the coefficients staged in Ctx::d_filt (0: not a coefficient image) and their
+    // table in Ctx::jpg_quants
+    int jpg_bw[2] = {0, 0}, jpg_q[2] = {-1, -1};
     tw_flow_out fout = {nullptr, 0, 0};  // tw_submit_*_flow: where the pair's final flow goes (data null: nowhere)
     bool fout_host = false;              // ... page-locked host memory: through Ctx::d_fstage and the engine's d2h_stream
     tw_flow_in fin = {nullptr, 0, 0};    // tw_submit_*_flow_init: the pair's initial field (data null: zero start)
     bool fin_staged = false;             // ... host memory, uploaded to Ctx::d_istage as dense rows
     // tw_submit_*_sized: the target's own size and row stride (the pair's when equal), and who resizes it to the pair's
     // size (tw_resize_u8): RSZ_NONE nobody; RSZ_SUBMIT a gray host target, on the copy stream right behind its upload;
-    // RSZ_FLUSH_COPY a tw_submit_png8_sized target, on the copy stream behind its own tw_png_unfilter when the batch is
-    // launched; RSZ_FLUSH_DEV a device target (t_src: the caller's memory), on the compute stream in front of the pyramid
+    // RSZ_FLUSH_COPY a tw_submit_png8_sized or tw_submit_jpeg target, on the copy stream behind its own tw_png_unfilter
+    // (or the batch's tw_jpeg_idct) when the batch is launched; RSZ_FLUSH_DEV a device target (t_src: the caller's memory), on the compute stream in front of the pyramid
     int tw = 0, th = 0;
     long long tstride = 0;
     int rkind = 0;
@@ -377,6 +382,12 @@ struct Ctx {
     bool any_png = false, any_plte = false;
     std::vector<std::array<uint8_t, 256>> png_luts;  // the open batch's gray tables, in the order they were submitted
     unsigned* h_pflag = nullptr;                     // pinned, [2*cap]
+    // tw_submit_jpeg (both tables created on the first coefficient image of this context, jpeg_table_bytes(cap) long): the
+    // batch's coefficient planes share the d_filt slots with filtered PNG rows; behind the 2n jobs of tw_jpeg_idct go the
+    // batch's quantisation tables — one upload, as the gray tables above
+    JpegJob *d_jpg = nullptr, *h_jpg = nullptr;  // h_jpg pinned
+    bool any_jpeg = false;
+    std::vector<std::array<uint16_t, 64>> jpg_quants;  // the open batch's tables, in the order they were submitted
     long long copy_ops_at_flush = 0;  // tw_engine::copy_ops when this batch was launched
     // ordered hit records of the batch [cap][G]: tw_wait reads them late when a pair has more than HOST_RECS hits,
     // so they belong to the context, not to the engine (a later batch must not overwrite them)
@@ -429,6 +440,8 @@ struct Ctx {
         threshold = threshold_;
         any_host = any_png = any_plte = any_fout = any_fout_host = any_init = any_init_host = false;
         png_luts.clear();  // (keeps its capacity: tw_engine_create reserved two tables per slot)
+        any_jpeg = false;
+        jpg_quants.clear();
         any_resize = any_resize_png = any_resize_dev = false;
         filt_slot = 0;
         nseg = 0;
@@ -619,6 +632,11 @@ namespace {
     } while (0)
 
 size_t staged_image_bytes(int w, int h);
+// tw_jpeg_idct's grid for `nimg` images of up to w x h pixels: a workgroup takes JPEG_WG_BLOCKS adjacent blocks of a block row
+dim3 jpeg_idct_grid(int w, int h, int nimg)
+{
+    return dim3((unsigned)((w + 8 * JPEG_WG_BLOCKS - 1) / (8 * JPEG_WG_BLOCKS)), (unsigned)((h + 7) / 8), (unsigned)nimg);
+}
 
 // One row of tw_resize_u8's job table: sw x sh at src -> dw x dh at dst, with cv::resize's scales (inv_scale = (double)dsize /
 // ssize, scale = 1. / inv_scale: computed here, in double, once per job)
@@ -2013,7 +2031,7 @@ struct BatchEnqueue {
     // uploads — it runs beside the previous batch's kernels like the uploads themselves
     tw_status enqueue_png_unfilter()
     {
-        if (!c.any_png) return TW_OK;
+        if (!c.any_png) return enqueue_png_target_resizes();  // (a tw_submit_jpeg batch may have targets of another size)
         for (int j = 0; j < n; j++)
             for (int q = 0; q < 2; q++) {
                 PngJob& pj = c.h_png[2 * j + q];
@@ -2040,6 +2058,39 @@ struct BatchEnqueue {
         else if (c.w <= PNG_LDS_PIXELS / 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, dim3(2 * n), dim3(256), 0, e->copy_stream, pa);
         else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(2 * n), dim3(64), 0, e->copy_stream, pa);
         return enqueue_png_target_resizes();
+    }
+
+    // tw_submit_jpeg: the batch's coefficient planes through the inverse DCT into the gray image slots — a target of another
+    // size into its d_tsrc slot, where the batch's tw_resize_u8 launch expects it — in one launch on the copy stream, in
+    // front of enqueue_png_unfilter's launches
+    tw_status enqueue_jpeg_idct()
+    {
+        if (!c.any_jpeg) return TW_OK;
+        const uint16_t* d_quants = (const uint16_t*)(c.d_jpg + 2 * (size_t)n);
+        int wmax = 1, hmax = 1;
+        for (int j = 0; j < n; j++)
+            for (int q = 0; q < 2; q++) {
+                const Job& jb = c.jobs[j];
+                JpegJob& jj = c.h_jpg[2 * j + q];
+                jj = JpegJob{};
+                if (jb.jpg_bw[q] == 0) continue;
+                const bool own_size = q && jb.rkind == RSZ_FLUSH_COPY;
+                jj.coef = (const int16_t*)(c.d_filt + c.filt_slot * (size_t)(2 * j + q));
+                jj.dst = own_size ? c.d_tsrc + c.tsrc_slot * (size_t)j : c.d_img + npx * (size_t)(2 * j + q);
+                jj.quant = d_quants + 64 * (size_t)jb.jpg_q[q];
+                jj.w = own_size ? jb.tw : c.w;
+                jj.h = own_size ? jb.th : c.h;
+                jj.bw = jb.jpg_bw[q];
+                wmax = std::max(wmax, jj.w);
+                hmax = std::max(hmax, jj.h);
+            }
+        memcpy(c.h_jpg + 2 * (size_t)n, c.jpg_quants.data(), 128 * c.jpg_quants.size());
+        TW_HIP(e, hipMemcpyAsync(c.d_jpg, c.h_jpg, sizeof(JpegJob) * 2 * (size_t)n + 128 * c.jpg_quants.size(),
+                                 hipMemcpyHostToDevice, e->copy_stream));
+        JpegArgs ja;
+        ja.jobs = c.d_jpg;
+        TW_LAUNCH(e, TW_DF_JPEG_IDCT, tw_jpeg_idct, jpeg_idct_grid(wmax, hmax, 2 * n), dim3(8 * JPEG_WG_BLOCKS), 0, e->copy_stream, ja);
+        return TW_OK;
     }
 
     // the kind of image q of pair j, as tw_png_unfilter reads it; the flag words and the gray tables of the batch lie
@@ -2139,7 +2190,7 @@ struct BatchEnqueue {
         // pause, or a pipeline the host cannot keep filled) — the pairs whose uploads are already marked start now, the
         // rest behind their own marks, instead of all of them behind the batch's last upload (531 MB for 128 pairs of
         // 1080p: ~14 ms of an idle GPU).  A busy stream takes the whole batch in one launch per kernel and level, as before.
-        if (e->ramp && e->lanes == 1 && !c.any_png && c.nseg > 0 && c.seg_at[0] < n) {
+        if (e->ramp && e->lanes == 1 && !c.any_png && !c.any_jpeg && c.nseg > 0 && c.seg_at[0] < n) {
             bool idle = true;
             for (Ctx& o : e->ctx)
                 if (&o != &c && o.launched && hipEventQuery(o.ev_done) == hipErrorNotReady) idle = false;
@@ -2784,6 +2835,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     BatchEnqueue b(e, c);
     TW_TRY(b.reserve_batch_buffers());
     RoctxRange batch_range("tw_batch %dx%d pairs=%d", c.w, c.h, b.n);
+    TW_TRY(b.enqueue_jpeg_idct());
     TW_TRY(b.enqueue_png_unfilter());
     TW_TRY(b.mark_uploads_and_plan_ramp());
     TW_TRY(b.upload_tables());
@@ -3003,6 +3055,8 @@ struct Submission {
     int bits_a = 0, bits_b = 0;
     const uint8_t *lut_a = nullptr, *lut_b = nullptr;
     int entries_a = 256, entries_b = 256;
+    // tw_submit_jpeg: an image that is its luma coefficients (h_a / h_b point at them), null for every other image
+    const tw_jpeg_luma *jl_a = nullptr, *jl_b = nullptr;
     // tw_submit_*_sized: the target's own size and row stride; 0 = same as the pair (every other entry point)
     int t_width = 0, t_height = 0;
     ptrdiff_t t_stride = 0;
@@ -3026,6 +3080,7 @@ struct Submit {
     tw_engine* const e;
     const Submission& s;
     const bool png;
+    const bool jpeg;             // tw_submit_jpeg with at least one coefficient image
     const long long eff_stride;  // host images are staged densely; device images are read in place with their stride
     const int tw, th;            // the target's own size (the pair's unless a _sized call says otherwise)
     const ptrdiff_t tstride;
@@ -3036,17 +3091,19 @@ struct Submit {
     Job jb;
 
     Submit(tw_engine* e_, const Submission& s_)
-        : e(e_), s(s_), png(s_.ch_a > 0 || s_.ch_b > 0), eff_stride(s_.h_a ? (long long)s_.width : (long long)s_.stride),
+        : e(e_), s(s_), png(s_.ch_a > 0 || s_.ch_b > 0), jpeg(s_.jl_a || s_.jl_b), eff_stride(s_.h_a ? (long long)s_.width : (long long)s_.stride),
           tw(s_.t_width ? s_.t_width : s_.width), th(s_.t_height ? s_.t_height : s_.height),
           tstride(s_.t_stride ? s_.t_stride : s_.stride),
           resize(tw != s_.width || th != s_.height || (!s_.h_a && tstride != s_.stride))
     {
     }
 
-    // bytes of a filtered image's slot in Ctx::d_filt (each image at its own size)
+    static size_t jpeg_coef_bytes(const tw_jpeg_luma* l) { return (size_t)l->blocks_w * (size_t)l->blocks_h * 128; }
+    // bytes of a filtered image's (or a coefficient plane's) slot in Ctx::d_filt (each image at its own size)
     size_t filt_need() const
     {
-        const size_t need = std::max(png_rows_bytes(s.width, s.height, s.ch_a, s.bits_a), png_rows_bytes(tw, th, s.ch_b, s.bits_b));
+        const size_t need = std::max(s.jl_a ? jpeg_coef_bytes(s.jl_a) : png_rows_bytes(s.width, s.height, s.ch_a, s.bits_a),
+                                     s.jl_b ? jpeg_coef_bytes(s.jl_b) : png_rows_bytes(tw, th, s.ch_b, s.bits_b));
         return (need + 255) / 256 * 256;
     }
 
@@ -3092,7 +3149,7 @@ struct Submit {
         if (tw != s.width || th != s.height) TW_TRY(check_dims(e, tw, th));
         const bool png_ok = s.h_a && s.h_b && s.ch_a >= 0 && s.ch_a <= 4 && s.ch_b >= 0 && s.ch_b <= 4;
         if (s.span < 0 || s.stride < s.width || tstride < tw || (!s.h_a && !s.d_a) || (!s.h_b && !s.d_b) ||
-            (png && (!png_ok || s.stride != s.width || tstride != tw))) {
+            ((png || jpeg) && (!png_ok || s.stride != s.width || tstride != tw))) {
             e->err = "bad argument";
             return TW_E_BAD_PARAMETER;
         }
@@ -3133,7 +3190,7 @@ struct Submit {
     {
         return !b.launched && !b.jobs.empty() && b.w == s.width && b.h == s.height && b.span == s.span &&
                b.threshold == s.threshold && b.jobs[0].stride == eff_stride && (int)b.jobs.size() < e->cap &&
-               (!png || b.filt_slot == 0 || filt_need() <= b.filt_slot);
+               (!(png || jpeg) || b.filt_slot == 0 || filt_need() <= b.filt_slot);
     }
 
     // c = the context whose open batch takes the pair: the current one's if the pair fits, otherwise a new batch
@@ -3194,11 +3251,12 @@ struct Submit {
         jb.th = th;
         jb.tstride = s.h_a ? (long long)tw : (long long)tstride;
         if (resize) TW_TRY(reserve_resize_tables());
+        if (jpeg) TW_TRY(reserve_jpeg_tables());
         if (!s.h_a) return resize ? stage_device_target() : TW_OK;
         const size_t npx = staged_image_bytes(s.width, s.height);
         // (grows only on the first job of a batch: all jobs of a batch have one size)
         TW_TRY(grow_device(e, c->d_img, c->d_img_cap, npx * 2 * e->cap, npx * 2 * e->cap + 256, e->copy_stream));
-        TW_TRY(png ? stage_png_rows(npx) : stage_gray_pair(npx));
+        TW_TRY(png || jpeg ? stage_png_rows(npx) : stage_gray_pair(npx));
         jb.h_a = s.h_a;
         jb.h_b = s.h_b;
         c->any_host = true;
@@ -3206,8 +3264,17 @@ struct Submit {
         return TW_OK;
     }
 
+    // what tw_jpeg_idct needs once per context
+    tw_status reserve_jpeg_tables()
+    {
+        if (!c->h_jpg) TW_HIP(e, hipHostMalloc((void**)&c->h_jpg, jpeg_table_bytes(e->cap), hipHostMallocDefault));
+        if (!c->d_jpg) TW_HIP(e, hipMalloc((void**)&c->d_jpg, jpeg_table_bytes(e->cap) + 256));
+        c->jpg_quants.reserve(2 * (size_t)e->cap);
+        return TW_OK;
+    }
+
     // tw_submit_png8: filtered rows go to the batch's d_filt slots (tw_png_unfilter writes d_img when the batch is
-    // launched), plain gray images of the pair straight to d_img
+    // launched), plain gray images of the pair straight to d_img.  tw_submit_jpeg: coefficient planes likewise (tw_jpeg_idct)
     tw_status stage_png_rows(size_t npx)
     {
         const size_t j = c->jobs.size();
@@ -3231,12 +3298,13 @@ struct Submit {
         const uint8_t* src[2] = {s.h_a, s.h_b};
         const int chs[2] = {s.ch_a, s.ch_b}, bits[2] = {s.bits_a, s.bits_b}, entries[2] = {s.entries_a, s.entries_b};
         const uint8_t* luts[2] = {s.lut_a, s.lut_b};
+        const tw_jpeg_luma* jl[2] = {s.jl_a, s.jl_b};
         for (int q = 0; q < 2; q++) {
             // an image is handed over as ONE row: it goes through the bounce buffer whole, whatever its size
             const int wq = q ? tw : s.width, hq = q ? th : s.height;
-            const size_t nb = chs[q] ? png_rows_bytes(wq, hq, chs[q], bits[q]) : (size_t)wq * hq;
+            const size_t nb = jl[q] ? jpeg_coef_bytes(jl[q]) : chs[q] ? png_rows_bytes(wq, hq, chs[q], bits[q]) : (size_t)wq * hq;
             // (a gray target of another size waits in its d_tsrc slot for the batch's tw_resize_u8 launch)
-            uint8_t* dst = chs[q] ? c->d_filt + c->filt_slot * (2 * j + q)
+            uint8_t* dst = chs[q] || jl[q] ? c->d_filt + c->filt_slot * (2 * j + q)
                                   : (q && resize) ? c->d_tsrc + c->tsrc_slot * j : c->d_img + npx * (2 * j + q);
             TW_TRY(pin_registry().covers(src[q], nb) ? upload_in_place(dst, src[q], nb, nb, 1)
                                                      : upload_through_bounce((char*)dst, src[q], nb, nb, 1));
@@ -3253,7 +3321,15 @@ struct Submit {
             memcpy(c->png_luts.back().data(), luts[q], 256);
             c->any_plte = c->any_plte || entries[q] < 256;
         }
-        c->any_png = true;
+        for (int q = 0; q < 2; q++) {
+            if (!jl[q]) continue;
+            jb.jpg_bw[q] = jl[q]->blocks_w;
+            jb.jpg_q[q] = (int)c->jpg_quants.size();
+            c->jpg_quants.emplace_back();
+            memcpy(c->jpg_quants.back().data(), jl[q]->quant, 128);
+        }
+        c->any_png = c->any_png || png;
+        c->any_jpeg = c->any_jpeg || jpeg;
         if (resize) {
             jb.rkind = RSZ_FLUSH_COPY;
             c->any_resize = c->any_resize_png = true;
@@ -3349,7 +3425,7 @@ struct Submit {
     tw_status mark_ramp()
     {
         const int sz = (int)c->jobs.size() + 1;
-        if (s.h_a && !png && e->ramp && e->cap >= 64 && c->nseg < 2 && (sz == e->cap / 4 || sz == e->cap / 2)) {
+        if (s.h_a && !png && !jpeg && e->ramp && e->cap >= 64 && c->nseg < 2 && (sz == e->cap / 4 || sz == e->cap / 2)) {
             TW_HIP(e, hipEventRecord(c->ev_seg[c->nseg], e->copy_stream));
             c->seg_at[c->nseg++] = sz;
         }
@@ -3636,6 +3712,8 @@ void tw_engine_destroy(tw_engine* e)
         if (c.d_filt_raw) (void)hipFree(c.d_filt_raw);
         if (c.d_png) (void)hipFree(c.d_png);
         if (c.h_png) (void)hipHostFree(c.h_png);
+        if (c.d_jpg) (void)hipFree(c.d_jpg);
+        if (c.h_jpg) (void)hipHostFree(c.h_jpg);
         if (c.h_pflag) (void)hipHostFree(c.h_pflag);
         if (c.ev_h2d) (void)hipEventDestroy(c.ev_h2d);
         for (hipEvent_t ev : c.ev_seg)
@@ -3813,6 +3891,43 @@ tw_status tw_submit_png(tw_engine* e, const tw_png_rows* expect, const tw_png_ro
     s.lut_b = kb.table ? lut_b : nullptr;
     s.entries_a = ka.entries;
     s.entries_b = kb.entries;
+    s.t_width = target->width;
+    s.t_height = target->height;
+    s.t_stride = target->width;
+    s.fo = out;
+    s.fi = init;
+    s.ticket = ticket;
+    return submit(e, s);
+}
+
+// one image of a tw_submit_jpeg / tw_stage_jpeg_idct call: no HIP call
+static tw_status check_jpeg_luma(const tw_jpeg_luma* l)
+{
+    if (!l || (!l->coef && !l->gray) || l->width < 1 || l->height < 1) return TW_E_BAD_PARAMETER;
+    if (!l->coef) return TW_OK;
+    const int nbx = (int)(((long long)l->width + 7) / 8), nby = (int)(((long long)l->height + 7) / 8);
+    if (l->blocks_w < nbx || l->blocks_w > nbx + 3 || l->blocks_h < nby || l->blocks_h > nby + 3) return TW_E_BAD_PARAMETER;
+    return TW_OK;
+}
+
+// (both images gray: exactly the Submission tw_submit_u8_sized builds for dense rows)
+tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* expect, const tw_jpeg_luma* target, int span, double threshold,
+                         const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    TW_TRY(check_jpeg_luma(expect));
+    TW_TRY(check_jpeg_luma(target));
+    Submission s;
+    s.h_a = expect->coef ? (const uint8_t*)expect->coef : expect->gray;
+    s.h_b = target->coef ? (const uint8_t*)target->coef : target->gray;
+    s.jl_a = expect->coef ? expect : nullptr;
+    s.jl_b = target->coef ? target : nullptr;
+    s.width = expect->width;
+    s.height = expect->height;
+    s.stride = expect->width;
+    s.span = span;
+    s.threshold = threshold;
     s.t_width = target->width;
     s.t_height = target->height;
     s.t_stride = target->width;
@@ -4384,7 +4499,7 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
         "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_iter_grid",
-        "tw_pair_same",
+        "tw_jpeg_idct", "tw_pair_same",
         "tw_resize_u8", "tw_flow_area_init", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
 }
@@ -4427,6 +4542,8 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
         if (c.h_ptrs) v[1] += sizeof(void*) * 2 * (size_t)e->cap;
         if (c.h_count) v[1] += sizeof(int) * (size_t)e->cap;
         if (c.h_png) v[1] += png_table_bytes(e->cap);
+        if (c.d_jpg) v[0] += jpeg_table_bytes(e->cap) + 256;
+        if (c.h_jpg) v[1] += jpeg_table_bytes(e->cap);
         if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cap;
         if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cap;
     }
@@ -4892,6 +5009,48 @@ tw_status tw_stage_resize_u8(tw_engine* e, const uint8_t* src, int sw, int sh, u
     TW_HIP(e, hipGetLastError());
     TW_HIP(e, hipStreamSynchronize(st));
     TW_TRY(d2h_sync(e, dst, d_dst, (size_t)dw * dh));
+    return TW_OK;
+}
+
+tw_status tw_stage_jpeg_idct(tw_engine* e, const tw_jpeg_luma* img, uint8_t* gray, uint8_t* guard)
+{
+    if (!e || !gray) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    TW_TRY(check_jpeg_luma(img));
+    if (!img->coef) return TW_E_BAD_PARAMETER;  // (a plain gray image has nothing to decode)
+    const int w = img->width, h = img->height;
+    TW_TRY(check_dims(e, w, h));
+    TW_HIP(e, hipSetDevice(e->device));
+    const size_t ncoef = (size_t)img->blocks_w * (size_t)img->blocks_h * 64, npx = (size_t)w * h;
+    Tmp t;
+    int16_t* d_coef = t.alloc<int16_t>(ncoef);
+    uint8_t* d_raw = t.alloc<uint8_t>(npx + 512);  // 256 guard bytes on either side of the image
+    char* d_tab = t.alloc<char>(sizeof(JpegJob) + 128);
+    if (!d_coef || !d_raw || !d_tab) return TW_E_NOMEM;
+    TW_TRY(h2d_sync(e, d_coef, img->coef, ncoef * sizeof(int16_t)));
+    hipStream_t st = e->stream;
+    TW_HIP(e, hipMemsetAsync(d_raw, 0xA5, npx + 512, st));  // (in front of the launch, on its stream)
+    char h_tab[sizeof(JpegJob) + 128];
+    JpegJob jj{};
+    jj.coef = d_coef;
+    jj.dst = d_raw + 256;
+    jj.quant = (const uint16_t*)(d_tab + sizeof(JpegJob));
+    jj.w = w;
+    jj.h = h;
+    jj.bw = img->blocks_w;
+    memcpy(h_tab, &jj, sizeof(jj));
+    memcpy(h_tab + sizeof(JpegJob), img->quant, 128);
+    TW_TRY(h2d_sync(e, d_tab, h_tab, sizeof(h_tab)));
+    JpegArgs ja;
+    ja.jobs = (const JpegJob*)d_tab;
+    TW_LAUNCH(e, TW_DF_JPEG_IDCT, tw_jpeg_idct, jpeg_idct_grid(w, h, 1), dim3(8 * JPEG_WG_BLOCKS), 0, st, ja);
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    TW_TRY(d2h_sync(e, gray, d_raw + 256, npx));
+    if (guard) {
+        TW_TRY(d2h_sync(e, guard, d_raw, 256));
+        TW_TRY(d2h_sync(e, guard + 256, d_raw + 256 + npx, 256));
+    }
     return TW_OK;
 }
 

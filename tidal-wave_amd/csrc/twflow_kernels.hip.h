@@ -5064,4 +5064,141 @@ __global__ __launch_bounds__(64 * RSZ_ROWS) void tw_resize_u8(ResizeArgs a)
     }
 }
 
+// =====================================================================================================
+// tw_jpeg_idct — what is left of cv::imread(path, GRAYSCALE) of a JPEG after the entropy decode (tw_submit_jpeg): the
+//   luma blocks' dequantisation, libjpeg's slow integer inverse DCT (jidctint: column pass with descale 13 - 2, row pass
+//   with descale 13 + 2 + 3), the level shift and the range limit as the `& 1023` map, cropped to the image.  The host
+//   layer's idct_islow (host/jpeg_gray.cpp) is the same arithmetic statement for statement.
+//   Range: the result must equal idct_islow for EVERY int16 coefficient and uint16 table entry (a damaged file reaches
+//   the extremes), and idct_islow computes in int64.  A dequantised value is below 2^31 in magnitude, and an output of a
+//   pass is a sum of its eight inputs times weights whose absolute values add up to less than 2^17.4 (31 520 for the even
+//   part, 137 832 for the odd part's largest term): below 2^49 after the column pass, 2^38 after its descale, 2^56 after
+//   the row pass — beyond 32 bits from the first pass on.  Both passes therefore run in int64 here as well and nothing
+//   wraps.  There is no
+//   32-bit path: it would need the block's range checked first, and the kernel's time is not what a JPEG pair waits for
+//   (profiles/jpeg_device.md).
+//   Geometry: grid z is the image (its own size, block pitch and table: a job without coefficients exits), y the block
+//   row, x groups of JPEG_WG_BLOCKS = 32 adjacent blocks; blocks that lie wholly in the MCU padding have no workgroup
+//   or no active lanes.  Eight adjacent lanes own a block.  Lane r loads row r of the block as one 16-byte access (a
+//   workgroup reads 4 KiB of contiguous coefficients) and leaves it in LDS; lane c then gathers column c, dequantises and
+//   runs the column pass; the 8 x 8 transpose between the passes goes through LDS again (int64 entries); lane r runs the
+//   row pass on row r and stores its 8 gray bytes.  A destination row starts at any byte address (dense w-pitch rows):
+//   one 8-byte store where all eight pixels exist and the address is 8-aligned, byte stores elsewhere.  Nothing outside
+//   the w x h bytes is written.
+//   LDS: the coefficient rows of a block are 144 bytes apart and its int64 workspace 576 (the next block starts 4 resp. 16
+//   banks further on, so the blocks of a 32-lane half do not all meet on one bank): 4608 + 18432 bytes per workgroup.
+// =====================================================================================================
+struct JpegJob {
+    const int16_t* coef;    // bw blocks per block row, 64 coefficients each, natural order; null: nothing to do
+    uint8_t* dst;           // w x h pixels, dense rows of w bytes
+    const uint16_t* quant;  // 64 entries, natural order
+    int w, h, bw, pad;
+};
+struct JpegArgs {
+    const JpegJob* jobs;
+};
+constexpr int JPEG_WG_BLOCKS = 32;  // blocks per workgroup: 256 lanes, 256 pixels across
+constexpr int JPEG_RAW_PITCH = 144, JPEG_WS_PITCH = 72;  // bytes / int64 entries between the blocks of a workgroup in LDS
+typedef __attribute__((address_space(1))) uint8_t jpg_gu8;
+typedef __attribute__((address_space(1))) unsigned long long jpg_gu64;
+
+// one 8-point pass of jidctint: v[8] -> o[8], descaled by `shift` (the host's `pass`)
+__device__ __forceinline__ void jpeg_idct_pass(const long long* v, int shift, long long* o)
+{
+    constexpr long long F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633,
+                        F1_501 = 12299, F1_847 = 15137, F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
+    long long z2 = v[2], z3 = v[6];
+    long long z1 = (z2 + z3) * F0_541;
+    long long tmp2 = z1 + z3 * (-F1_847);
+    long long tmp3 = z1 + z2 * F0_765;
+    z2 = v[0];
+    z3 = v[4];
+    long long tmp0 = (z2 + z3) * 8192, tmp1 = (z2 - z3) * 8192;
+    const long long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = v[7];
+    tmp1 = v[5];
+    tmp2 = v[3];
+    tmp3 = v[1];
+    z1 = tmp0 + tmp3;
+    z2 = tmp1 + tmp2;
+    z3 = tmp0 + tmp2;
+    long long z4 = tmp1 + tmp3;
+    const long long z5 = (z3 + z4) * F1_175;
+    tmp0 *= F0_298;
+    tmp1 *= F2_053;
+    tmp2 *= F3_072;
+    tmp3 *= F1_501;
+    z1 *= -F0_899;
+    z2 *= -F2_562;
+    z3 *= -F1_961;
+    z4 *= -F0_390;
+    z3 += z5;
+    z4 += z5;
+    tmp0 += z1 + z3;
+    tmp1 += z2 + z4;
+    tmp2 += z2 + z3;
+    tmp3 += z1 + z4;
+    const long long rnd = 1ll << (shift - 1);
+    o[0] = (tmp10 + tmp3 + rnd) >> shift;
+    o[7] = (tmp10 - tmp3 + rnd) >> shift;
+    o[1] = (tmp11 + tmp2 + rnd) >> shift;
+    o[6] = (tmp11 - tmp2 + rnd) >> shift;
+    o[2] = (tmp12 + tmp1 + rnd) >> shift;
+    o[5] = (tmp12 - tmp1 + rnd) >> shift;
+    o[3] = (tmp13 + tmp0 + rnd) >> shift;
+    o[4] = (tmp13 - tmp0 + rnd) >> shift;
+}
+
+__global__ __launch_bounds__(8 * JPEG_WG_BLOCKS) void tw_jpeg_idct(JpegArgs a)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[JPEG_WG_BLOCKS * JPEG_RAW_PITCH];
+    __shared__ __attribute__((aligned(16))) long long s_ws[JPEG_WG_BLOCKS * JPEG_WS_PITCH];
+    const JpegJob job = a.jobs[blockIdx.z];
+    const int lb = (int)threadIdx.x >> 3, k = (int)threadIdx.x & 7;  // block of the workgroup, row / column of the block
+    const int bx = (int)blockIdx.x * JPEG_WG_BLOCKS + lb, by = (int)blockIdx.y;
+    // (workgroup-uniform: an image smaller than the batch's grid, or one that came as gray)
+    if (!job.coef || by * 8 >= job.h || (int)blockIdx.x * JPEG_WG_BLOCKS * 8 >= job.w) return;
+    const bool on = bx * 8 < job.w;  // (bx < bw follows: bw >= ceil(w / 8) is checked on the host)
+
+    if (on) {
+        const uint4 row = *(const uint4*)(job.coef + ((size_t)by * job.bw + bx) * 64 + 8 * k);
+        *(uint4*)(s_raw + lb * JPEG_RAW_PITCH + 16 * k) = row;
+    }
+    __syncthreads();
+    if (on) {
+        long long v[8], o[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const int cf = *(const short*)(s_raw + lb * JPEG_RAW_PITCH + 16 * r + 2 * k);
+            v[r] = (long long)cf * (long long)job.quant[8 * r + k];
+        }
+        jpeg_idct_pass(v, 13 - 2, o);
+#pragma unroll
+        for (int r = 0; r < 8; r++) s_ws[lb * JPEG_WS_PITCH + 8 * r + k] = o[r];
+    }
+    __syncthreads();
+    const int y = by * 8 + k;
+    if (!on || y >= job.h) return;
+    long long v[8], o[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) v[c] = s_ws[lb * JPEG_WS_PITCH + 8 * k + c];
+    jpeg_idct_pass(v, 13 + 2 + 3, o);
+    unsigned px[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        // libjpeg's range_limit table indexed with (x & 1023): clamp(x + 128) for any sane x
+        const int t = (int)(o[c] & 1023);
+        px[c] = (unsigned)(t < 128 ? t + 128 : (t < 512 ? 255 : (t < 896 ? 0 : t - 896)));
+    }
+    jpg_gu8* __restrict__ D = (jpg_gu8*)job.dst + (size_t)y * (size_t)job.w + (size_t)bx * 8;
+    const int nout = min(8, job.w - bx * 8);
+    if (nout == 8 && ((uintptr_t)D & 7u) == 0) {
+        const unsigned long long lo = px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24);
+        const unsigned long long hi = px[4] | (px[5] << 8) | (px[6] << 16) | (px[7] << 24);
+        *(jpg_gu64*)D = lo | (hi << 32);
+    } else {
+        for (int c = 0; c < nout; c++) D[c] = (uint8_t)px[c];
+    }
+}
+
 }  // namespace twk

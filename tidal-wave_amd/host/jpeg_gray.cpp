@@ -449,7 +449,9 @@ struct Decoder {
         return q;
     }
 
-    bool run(std::vector<uint8_t>& img, int& w, int& h)
+    // everything up to the inverse DCT: the luma coefficient plane, its table and the sizes (nothing of `out` is set on
+    // failure)
+    bool run(JpegLuma& out)
     {
         if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return false;
         const uint8_t* p = d + 2;
@@ -539,28 +541,48 @@ struct Decoder {
         if (ncomp == 3 && adobe_transform < 0 && comp[0].id == 'R' && comp[1].id == 'G' && comp[2].id == 'B') return false;
         Comp& Y = comp[0];
         if (!qt_present[Y.tq]) return false;
-        // inverse DCT of the luma blocks, cropped to the image
-        const int pw = Y.bw * 8;
-        std::vector<uint8_t> plane((size_t)pw * Y.bh * 8);
-        for (int by = 0; by < Y.bh; by++)
-            for (int bx = 0; bx < Y.bw; bx++)
-                idct_islow(&Y.coef[((size_t)by * Y.bw + bx) * 64], qt[Y.tq], &plane[(size_t)by * 8 * pw + bx * 8], pw);
-        img.resize((size_t)W * H);
-        for (int y = 0; y < H; y++) memcpy(&img[(size_t)y * W], &plane[(size_t)y * pw], (size_t)W);
-        w = W;
-        h = H;
+        out.w = W;
+        out.h = H;
+        out.bw = Y.bw;
+        out.bh = Y.bh;
+        memcpy(out.quant, qt[Y.tq], sizeof(out.quant));
+        out.coef = std::move(Y.coef);
         return true;
     }
 };
 
 }  // namespace
 
-bool decode_jpeg_gray(const uint8_t* data, size_t n, std::vector<uint8_t>& img, int& w, int& h)
+bool decode_jpeg_luma(const uint8_t* data, size_t n, JpegLuma& luma)
 {
     Decoder dec;
     dec.d = data;
     dec.n = n;
-    return dec.run(img, w, h);
+    return dec.run(luma);
+}
+
+// inverse DCT of the luma blocks, cropped to the image (blocks that lie wholly in the MCU padding are never looked at)
+void jpeg_luma_to_gray(const JpegLuma& luma, std::vector<uint8_t>& img)
+{
+    const int W = luma.w, H = luma.h;
+    img.resize((size_t)W * H);
+    uint8_t blk[64];
+    for (int by = 0; by * 8 < H; by++)
+        for (int bx = 0; bx * 8 < W; bx++) {
+            idct_islow(&luma.coef[((size_t)by * luma.bw + bx) * 64], luma.quant, blk, 8);
+            const int nx = std::min(8, W - bx * 8), ny = std::min(8, H - by * 8);
+            for (int y = 0; y < ny; y++) memcpy(&img[(size_t)(by * 8 + y) * W + bx * 8], blk + 8 * y, (size_t)nx);
+        }
+}
+
+bool decode_jpeg_gray(const uint8_t* data, size_t n, std::vector<uint8_t>& img, int& w, int& h)
+{
+    JpegLuma luma;
+    if (!decode_jpeg_luma(data, n, luma)) return false;
+    jpeg_luma_to_gray(luma, img);
+    w = luma.w;
+    h = luma.h;
+    return true;
 }
 
 }  // namespace twhost

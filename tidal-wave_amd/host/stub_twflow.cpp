@@ -32,6 +32,7 @@
 // (weak: the stub built on its own, without twhost.cpp, still loads; tw_submit_png then takes gray images only)
 namespace twhost {
 bool finish_png_kind_on_host(const uint8_t* rows, int w, int h, const PngKind& kind, std::vector<uint8_t>& gray) __attribute__((weak));
+void jpeg_luma_to_gray(const JpegLuma& luma, std::vector<uint8_t>& img) __attribute__((weak));
 }
 
 typedef std::chrono::steady_clock stub_clock;
@@ -68,6 +69,8 @@ static std::atomic<int> g_engines{0};
 // calls so far, for the drivers that report them (tests/test_host_png_kinds.py): pairs that came through tw_submit_png,
 // and through it images that were still PNG rows
 static std::atomic<long> g_png_calls{0}, g_png_row_images{0};
+// likewise pairs that came through tw_submit_jpeg, and through it images that were still coefficients
+static std::atomic<long> g_jpeg_calls{0}, g_jpeg_coef_images{0};
 
 extern "C" {
 void tw_default_params(tw_params* p)
@@ -124,6 +127,11 @@ void tw_stub_png_calls(long* pairs, long* row_images)
 {
     *pairs = g_png_calls;
     *row_images = g_png_row_images;
+}
+void tw_stub_jpeg_calls(long* pairs, long* coef_images)
+{
+    *pairs = g_jpeg_calls;
+    *coef_images = g_jpeg_coef_images;
 }
 int tw_grid_capacity(int w, int h, int span) { return span > 0 ? ((h + span - 1) / span) * ((w + span - 1) / span) : 0; }
 tw_status tw_engine_create(int device, const tw_params*, int slots, tw_engine** out)
@@ -226,6 +234,38 @@ tw_status tw_submit_png(tw_engine* e, const tw_png_rows* a, const tw_png_rows* b
         e->bad[*t] = bad;
     }
     return r;
+}
+// tw_submit_jpeg: the first gray pixel of a coefficient image is the host layer's own inverse DCT of its block 0, then the
+// pair is what tw_submit_u8 sees
+tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* a, const tw_jpeg_luma* b, int span, double thr, const tw_flow_in*,
+                         const tw_flow_out*, tw_ticket* t)
+{
+    const tw_jpeg_luma* im[2] = {a, b};
+    for (int q = 0; q < 2; q++) {
+        if (!im[q] || (!im[q]->coef && !im[q]->gray) || im[q]->width < 1 || im[q]->height < 1) return TW_E_BAD_PARAMETER;
+        const int nbx = (im[q]->width + 7) / 8, nby = (im[q]->height + 7) / 8;
+        if (im[q]->coef && (im[q]->blocks_w < nbx || im[q]->blocks_w > nbx + 3 || im[q]->blocks_h < nby || im[q]->blocks_h > nby + 3))
+            return TW_E_BAD_PARAMETER;
+    }
+    if (!stub_sizes_match(a->width, a->height, b->width, b->height)) return TW_E_DONT_MATCH_SIZE;
+    g_jpeg_calls++;
+    uint8_t first[2] = {0, 0};
+    for (int q = 0; q < 2; q++) {
+        if (!im[q]->coef) {
+            first[q] = im[q]->gray[0];
+            continue;
+        }
+        if (!twhost::jpeg_luma_to_gray) return TW_E_UNSUPPORTED;
+        g_jpeg_coef_images++;
+        twhost::JpegLuma l;
+        l.w = l.h = l.bw = l.bh = 1;
+        memcpy(l.quant, im[q]->quant, sizeof(l.quant));
+        l.coef.assign(im[q]->coef, im[q]->coef + 64);
+        std::vector<uint8_t> g;
+        twhost::jpeg_luma_to_gray(l, g);
+        first[q] = g[0];
+    }
+    return tw_submit_u8(e, &first[0], &first[1], a->width, a->height, a->width, span, thr, t);
 }
 tw_status tw_submit_dev_sized(tw_engine* e, const void* a, int w, int h, ptrdiff_t stride, const void* b, int tw, int th,
                               ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)

@@ -18,7 +18,13 @@
 #include <new>
 #include <sstream>
 
+// additive within ABI 4: an engine library from before tw_submit_jpeg still loads, and JPEGs then stay on the host
+#pragma weak tw_submit_jpeg
+
 namespace twhost {
+
+// TW_DEVICE_JPEG's default (profiles/jpeg_device.md)
+constexpr bool kDeviceJpegDefault = true;
 
 // ---------------------------------------------------------------------------------------------------
 // progress prints of the reference (std::cout in src/manager.cpp:74, src/consumer.cpp:49,55,92), behind TW_LOG
@@ -734,6 +740,13 @@ struct Staged {
     ptrdiff_t stride = 0;
     int w = 0, h = 0;
     PngKind ka, kb;        // rows(): a / b hold filtered PNG rows of that kind (the device finishes them: tw_submit_png)
+    // on(): a / b hold a JPEG's quantised luma coefficients, bw * bh blocks of 64 int16 (the device runs the inverse DCT:
+    // tw_submit_jpeg)
+    struct JpegHead {
+        int bw = 0, bh = 0;
+        uint16_t quant[64] = {0};
+        bool on() const { return bw > 0; }
+    } ja, jb;
     int tw = 0, th = 0;    // the target's own size when the device reconciles it (tw_submit_*_sized); 0: the pair's size
     std::string err;
     tw_ticket ticket = 0;
@@ -741,9 +754,25 @@ struct Staged {
     bool done = false;  // response pushed
 };
 
+// the rest of a JPEG's decode on the host (what the device does for tw_submit_jpeg): `bytes` from coefficients to gray
+void finish_jpeg_on_host(std::vector<uint8_t>& bytes, Staged::JpegHead& head, int w, int h)
+{
+    JpegLuma l;
+    l.w = w;
+    l.h = h;
+    l.bw = head.bw;
+    l.bh = head.bh;
+    memcpy(l.quant, head.quant, sizeof(l.quant));
+    l.coef.resize(bytes.size() / 2);
+    memcpy(l.coef.data(), bytes.data(), l.coef.size() * 2);
+    jpeg_luma_to_gray(l, bytes);
+    head = Staged::JpegHead();
+}
+
 // the two imreads of a pair are independent: the decode pool runs them as separate tasks (task = 2 * job + image)
 // (`file`: the bytes of the file when the caller has read it already, else null)
-void decode_one(Staged& s, int which, int* tw, int* th, std::string* err, bool device_png, bool png_kinds,
+// (device_jpeg: a JPEG stops at its coefficient plane — Staged::ja / jb — and the device runs the inverse DCT)
+void decode_one(Staged& s, int which, int* tw, int* th, std::string* err, bool device_png, bool png_kinds, bool device_jpeg,
                 const std::vector<uint8_t>* file)
 {
     if (s.req.raw.expect) return;
@@ -753,6 +782,22 @@ void decode_one(Staged& s, int which, int* tw, int* th, std::string* err, bool d
     int& w = which == 0 ? s.w : *tw;
     int& h = which == 0 ? s.h : *th;
     PngKind& kind = which == 0 ? s.ka : s.kb;
+    if (device_jpeg && file && file->size() >= 8 && (*file)[0] == 0xFF && (*file)[1] == 0xD8) {
+        JpegLuma l;
+        if (!decode_jpeg_luma(file->data(), file->size(), l)) {
+            *err = "Can't open " + path;
+            return;
+        }
+        Staged::JpegHead& head = which == 0 ? s.ja : s.jb;
+        w = l.w;
+        h = l.h;
+        head.bw = l.bw;
+        head.bh = l.bh;
+        memcpy(head.quant, l.quant, sizeof(head.quant));
+        img.resize(l.coef.size() * 2);
+        memcpy(img.data(), l.coef.data(), img.size());
+        return;
+    }
     const bool ok = file ? decode_gray_or_png_kind_rows(*file, device_png, png_kinds, img, w, h, kind)
                          : load_gray_or_png_kind_rows(path, device_png, png_kinds, img, w, h, kind);
     if (!ok) *err = "Can't open " + path;
@@ -777,6 +822,10 @@ void prepare(Staged& s, int tw, int th, const std::string& err_a, const std::str
     if (!err_a.empty()) { s.err = err_a; return; }
     if (!err_b.empty()) { s.err = err_b; return; }
     if (abs(s.h - th) > 5 || abs(s.w - tw) > 5) { s.err = "Don't match image size"; return; }
+    // a JPEG beside half-decoded PNG rows (index.js pairs files by relative path: a corner): tw_submit_png takes rows and
+    // gray images, so the JPEG is finished here; so is a JPEG target that the host is to resize
+    if (s.ja.on() && s.kb.rows()) finish_jpeg_on_host(s.a, s.ja, s.w, s.h);
+    if (s.jb.on() && (s.ka.rows() || ((s.h != th || s.w != tw) && !device_reconcile))) finish_jpeg_on_host(s.b, s.jb, tw, th);
     if ((s.h != th || s.w != tw) && device_reconcile) {
         // the <= 5 px reconcile on the device (tw_submit_*_sized): the target stays as it was decoded, filtered rows included
         s.tw = tw;
@@ -839,6 +888,12 @@ void Consumer::run()
     // side measured faster (profiles/png_kinds.md: 1.77 x on a palette corpus, 1.39 x with one palette pair in 32).
     bool png_kinds = true;
     if (const char* ev = getenv("TW_DEVICE_PNG_KINDS")) png_kinds = atoi(ev) != 0;
+    // A JPEG's inverse DCT on the device (tw_submit_jpeg, where the engine exports it): the decode pool stops at the
+    // coefficient plane.  TW_DEVICE_JPEG=0 keeps the whole decode on the host: A/B switch and fallback, same bytes
+    // (profiles/jpeg_device.md has the measurement behind the default).
+    bool device_jpeg = kDeviceJpegDefault;
+    if (const char* ev = getenv("TW_DEVICE_JPEG")) device_jpeg = atoi(ev) != 0;
+    device_jpeg = device_jpeg && tw_submit_jpeg != nullptr;
     tw_engine* eng = nullptr;
     std::string eng_err;
     if (ndev > 0) {
@@ -1147,7 +1202,7 @@ void Consumer::run()
             parallel_for(2 * jobs.size(), [&](size_t i) {
                 const size_t j = i >> 1;
                 decode_one(jobs[j], (int)(i & 1), &tw[j], &th[j], (i & 1) ? &eb[j] : &ea[j], device_png, png_kinds,
-                           op[i].read_ok ? &op[i].file : nullptr);
+                           device_jpeg && eng, op[i].read_ok ? &op[i].file : nullptr);
                 std::vector<uint8_t>().swap(op[i].file);
             });
             bt1 = steady_ns();
@@ -1206,6 +1261,23 @@ void Consumer::run()
                     const tw_png_rows ra = rows_of(s.pa, s.w, s.h, s.ka);
                     const tw_png_rows rb = rows_of(s.pb, s.tw ? s.tw : s.w, s.tw ? s.th : s.h, s.kb);
                     return tw_submit_png(eng, &ra, &rb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
+                }
+                // JPEG(s) that stopped at the coefficient plane: the device runs the inverse DCT (and the reconcile)
+                if (s.ja.on() || s.jb.on()) {
+                    auto luma_of = [](const uint8_t* p, int w, int h, const Staged::JpegHead& jh) {
+                        tw_jpeg_luma l;
+                        l.coef = jh.on() ? (const int16_t*)p : nullptr;
+                        l.gray = jh.on() ? nullptr : p;
+                        l.width = w;
+                        l.height = h;
+                        l.blocks_w = jh.bw;
+                        l.blocks_h = jh.bh;
+                        memcpy(l.quant, jh.quant, sizeof(l.quant));
+                        return l;
+                    };
+                    const tw_jpeg_luma la = luma_of(s.pa, s.w, s.h, s.ja);
+                    const tw_jpeg_luma lb = luma_of(s.pb, s.tw ? s.tw : s.w, s.tw ? s.th : s.h, s.jb);
+                    return tw_submit_jpeg(eng, &la, &lb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
                 }
                 if (s.tw)
                     return tw_submit_u8_sized(eng, s.pa, s.w, s.h, s.stride, s.pb, s.tw, s.th, s.tw, s.req.span, s.req.threshold,

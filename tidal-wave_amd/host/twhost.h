@@ -156,7 +156,20 @@ private:
     bool running_ = true;
 };
 
-// JPEG (baseline / progressive Huffman, 8-bit) -> luma plane, libjpeg's integer IDCT (jpeg_gray.cpp)
+// A JPEG after its entropy decode: the quantised luma coefficients and what the inverse DCT needs (tw_submit_jpeg runs
+// it on the device, jpeg_luma_to_gray here)
+struct JpegLuma {
+    int w = 0, h = 0;
+    int bw = 0, bh = 0;         // luma blocks stored per row and per column: whole MCUs
+    uint16_t quant[64] = {0};   // luma quantisation table, natural order
+    std::vector<int16_t> coef;  // bw * bh blocks, row-major, 64 quantised coefficients each, natural order
+};
+// JPEG (baseline / progressive Huffman, 8-bit) up to and including every refusal (jpeg_gray.cpp); `luma` is untouched on
+// failure
+bool decode_jpeg_luma(const uint8_t* data, size_t n, JpegLuma& luma);
+// the rest: dequantisation, libjpeg's integer IDCT (jidctint), level shift, range limit and the crop to w x h
+void jpeg_luma_to_gray(const JpegLuma& luma, std::vector<uint8_t>& img);
+// the two in sequence: JPEG -> luma plane
 bool decode_jpeg_gray(const uint8_t* data, size_t n, std::vector<uint8_t>& img, int& w, int& h);
 // 8-bit gray decode of a file: PGM (P5), PNG (zlib inflate + unfilter, libpng-1.5 gray conversion) and JPEG.
 // Returns false if the file cannot be opened / decoded ("Can't open <path>", src/opticalflow.cpp:40,47).

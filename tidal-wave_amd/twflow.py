@@ -67,7 +67,7 @@ SYMBOLS = [
     "tw_submit_u8_flow", "tw_submit_png8_flow", "tw_submit_dev_flow",
     "tw_submit_u8_flow_init", "tw_submit_png8_flow_init", "tw_submit_dev_flow_init",
     "tw_submit_u8_sized", "tw_submit_png8_sized", "tw_submit_dev_sized", "tw_stage_resize_u8",
-    "tw_png_on_device", "tw_submit_png", "tw_stage_png_decode",
+    "tw_png_on_device", "tw_submit_png", "tw_stage_png_decode", "tw_submit_jpeg", "tw_stage_jpeg_idct",
     "tw_grid_capacity", "tw_dev_alloc", "tw_dev_free", "tw_dev_upload", "tw_dev_download", "tw_host_alloc", "tw_host_free", "tw_host_register", "tw_host_unregister", "tw_set_option",
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
@@ -100,6 +100,45 @@ class PngRows(C.Structure):
             self.palette = _u8(self._palette)
         n = 0 if self._palette is None else self._palette.size // 3
         self.palette_entries = n if palette_entries is None else palette_entries
+
+
+class JpegLuma(C.Structure):
+    """tw_jpeg_luma: one image of submit_jpeg / stage_jpeg_idct.  coef: the quantised luma coefficients after the entropy
+    decode, an int16 array [bh, bw, 64] (bh x bw stored blocks — whole MCUs — of 64 coefficients in natural order);
+    quant: the 64 entries of the luma table, natural order; w, h: the image's own size.  JpegLuma.from_gray(img) is a plain
+    gray image instead (coef NULL).  The arrays stay alive with the structure."""
+    _fields_ = [("coef", C.POINTER(C.c_int16)), ("gray", C.POINTER(C.c_uint8)), ("width", C.c_int), ("height", C.c_int),
+                ("blocks_w", C.c_int), ("blocks_h", C.c_int), ("quant", C.c_uint16 * 64)]
+
+    def __init__(self, coef, quant, w, h):
+        super().__init__()
+        self._coef = np.ascontiguousarray(coef, np.int16)
+        if self._coef.ndim != 3 or self._coef.shape[2] != 64:
+            raise ValueError("coef must have shape [bh, bw, 64]")
+        self._gray = None
+        self.coef = self._coef.ctypes.data_as(C.POINTER(C.c_int16))
+        self.width, self.height = w, h
+        self.blocks_h, self.blocks_w = self._coef.shape[:2]
+        q = np.ascontiguousarray(quant, np.uint16).reshape(64)
+        C.memmove(self.quant, q.ctypes.data, 128)
+
+    @classmethod
+    def from_gray(cls, img):
+        self = cls.__new__(cls)
+        C.Structure.__init__(self)
+        self._coef = None
+        self._gray = np.ascontiguousarray(_gray(img))
+        self.gray = _u8(self._gray)
+        self.height, self.width = self._gray.shape
+        return self
+
+    @property
+    def w(self):
+        return self.width
+
+    @property
+    def h(self):
+        return self.height
 
 
 def png_on_device(color_type, bit_depth, interlace=0):
@@ -190,6 +229,8 @@ def _bind(path):
     L.tw_png_on_device.restype = C.c_int
     L.tw_submit_png.argtypes = [vp, C.POINTER(PngRows), C.POINTER(PngRows), C.c_int, C.c_double, fip, fop, tkp]
     L.tw_stage_png_decode.argtypes = [vp, C.POINTER(PngRows), C.c_int, u8p]
+    L.tw_submit_jpeg.argtypes = [vp, C.POINTER(JpegLuma), C.POINTER(JpegLuma), C.c_int, C.c_double, fip, fop, tkp]
+    L.tw_stage_jpeg_idct.argtypes = [vp, C.POINTER(JpegLuma), u8p, u8p]
     L.tw_debug_png_kernel_time.argtypes = [vp, C.POINTER(PngRows), C.c_int, C.c_int, fp]
     L.tw_wait.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, fp]
     L.tw_flush.argtypes = [vp]
@@ -525,6 +566,29 @@ class Engine:
         out = np.empty((img.height, img.width), np.uint8)
         self._check(self._L.tw_stage_png_decode(self._h, C.byref(img), waves, _u8(out)))
         return out
+
+    def submit_jpeg(self, expect, target, span=10, threshold=5.0, init=None, out=None):
+        """tw_submit_jpeg: expect, target are JpegLuma (coefficients, or JpegLuma.from_gray) or 2-D uint8 gray images, each
+        at its own size; the pair's size is the expected image's.  init, out: the initial field and the destination of
+        the final flow, as submit's init and flow."""
+        a = expect if isinstance(expect, JpegLuma) else JpegLuma.from_gray(expect)
+        b = target if isinstance(target, JpegLuma) else JpegLuma.from_gray(target)
+        w, h = a.width, a.height
+        tk = C.c_int64()
+        fo = _flow_out(out, w, h)
+        fi, _keep = _flow_in(init, w, h)
+        self._check(self._L.tw_submit_jpeg(self._h, C.byref(a), C.byref(b), span, threshold,
+                                           C.byref(fi) if fi is not None else None,
+                                           C.byref(fo) if fo is not None else None, C.byref(tk)))
+        return (tk.value, w, h, span, threshold)
+
+    def stage_jpeg_idct(self, luma, guard=False):
+        """tw_jpeg_idct alone on one JpegLuma with coefficients: the (h, w) gray image; guard=True: also the 512 device
+        bytes around it (256 in front, 256 behind), which were 0xA5 before the launch."""
+        out = np.empty((luma.height, luma.width), np.uint8)
+        g = np.empty(512, np.uint8) if guard else None
+        self._check(self._L.tw_stage_jpeg_idct(self._h, C.byref(luma), _u8(out), _u8(g) if guard else None))
+        return (out, g) if guard else out
 
     def png_kernel_time(self, img, iters=20, waves=0):
         """tw_debug_png_kernel_time: microseconds of one tw_png_unfilter launch on this PngRows image (event-timed)."""

@@ -1,17 +1,19 @@
 #!/usr/bin/env python3
-"""End-to-end service throughput from FILES (decode included): writes N synthetic 1080p pairs as PNG, runs them
+"""End-to-end service throughput from FILES (decode included): writes N synthetic 1080p pairs as PNG (or JPEG), runs them
 through host/index.js create() (addon -> decode pool -> libtwflow.so) and prints pairs/s.  Needs a GPU + node.
 
-    e2e_files.py [N [DECODE_THREADS]] [--corpus gray|rgba|palette|mixed] [--host DIR] [--json]
+    e2e_files.py [N [DECODE_THREADS]] [--corpus gray|rgba|palette|mixed|jpeg] [--host DIR] [--json]
     e2e_files.py --kernel-time
 
   --corpus   the kind of file: 8-bit gray (the default, what this tool has always written), RGBA, palette-8 with the
-             identity gray palette, or mixed = one pair in 32 palette-8 and the rest RGBA
+             identity gray palette, mixed = one pair in 32 palette-8 and the rest RGBA, or jpeg = baseline quality-90
+             4:2:0 JPEGs of the same images as r = g = b colour files (what a screenshot tool writes)
   --host     the host/ directory whose index.js and addon run (default: this tree's): A/B against another build
   --json     one JSON line instead of the text
   --kernel-time   no files: tw_png_unfilter per 1080p image for RGBA, palette-8 and 1-bit gray rows, event-timed
              (tw_debug_png_kernel_time, 20 launches between two events, the median of 7 such figures)
-The environment goes through unchanged (TW_DEVICE_PNG_KINDS=0 keeps palette files on the host)."""
+The environment goes through unchanged (TW_DEVICE_PNG_KINDS=0 keeps palette files on the host, TW_DEVICE_JPEG=0 / 1 a
+JPEG's inverse DCT on the host / on the device; TW_DEBUG_BATCHTIME=1 prints where each batch's host time goes)."""
 import argparse
 import json
 import os
@@ -35,6 +37,9 @@ def save(img, path, kind):
         im.putpalette([v for i in range(256) for v in (i, i, i)])
     elif kind == "rgba":
         im = Image.fromarray(np.dstack([img, img, img, np.full_like(img, 255)]))
+    elif kind == "jpeg":
+        Image.fromarray(np.dstack([img, img, img])).save(path, "JPEG", quality=90, subsampling=2, progressive=False)
+        return
     else:
         im = Image.fromarray(img)
     im.save(path, compress_level=3)
@@ -64,7 +69,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("n", nargs="?", type=int, default=32)
     ap.add_argument("threads", nargs="?", default="")
-    ap.add_argument("--corpus", default="gray", choices=("gray", "rgba", "palette", "mixed"))
+    ap.add_argument("--corpus", default="gray", choices=("gray", "rgba", "palette", "mixed", "jpeg"))
     ap.add_argument("--host", default=os.path.join(ROOT, "tidal-wave_amd", "host"))
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--kernel-time", action="store_true")
@@ -78,8 +83,9 @@ def main():
         os.makedirs(os.path.join(d, "target", "s"))
         made = {}  # (pair % 4, kind) -> its two files
         for i in range(n):
-            kind = {"gray": "gray", "rgba": "rgba", "palette": "palette"}.get(a.corpus) or ("palette" if i % 32 == 5 else "rgba")
-            pe, pt = os.path.join(d, "expected", "s", "p%04d.png" % i), os.path.join(d, "target", "s", "p%04d.png" % i)
+            kind = {"gray": "gray", "rgba": "rgba", "palette": "palette", "jpeg": "jpeg"}.get(a.corpus) or ("palette" if i % 32 == 5 else "rgba")
+            ext = "jpg" if kind == "jpeg" else "png"
+            pe, pt = os.path.join(d, "expected", "s", "p%04d.%s" % (i, ext)), os.path.join(d, "target", "s", "p%04d.%s" % (i, ext))
             if (i % 4, kind) not in made:
                 img_a, img_b = synth.make_pair(i % 4, 1080, 1920)
                 save(img_a, pe, kind)
@@ -109,7 +115,8 @@ def main():
     rate = n / (out["ms"] / 1e3)
     if a.json:
         print(json.dumps({"corpus": a.corpus, "pairs": n, "decode_threads": threads or "auto", "host": os.path.relpath(a.host, ROOT),
-                          "png_kinds": os.environ.get("TW_DEVICE_PNG_KINDS", "1"), "pairs_per_s": round(rate, 1), "ms": out["ms"],
+                          "png_kinds": os.environ.get("TW_DEVICE_PNG_KINDS", "1"),
+                          "device_jpeg": os.environ.get("TW_DEVICE_JPEG", "default"), "pairs_per_s": round(rate, 1), "ms": out["ms"],
                           "report": out["report"], "errors": out["errors"]}))
         return
     print(r.stdout.strip(), r.stderr.strip()[-3000:])
