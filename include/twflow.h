@@ -365,14 +365,21 @@ tw_status tw_prof_read(tw_engine* e, int kclass, double* ms_total, int* launches
  * every output written once (blur+solve: averaged over the pyrIterations launches of a level — a launch fused with
  * the matrix refresh moves 80 B/px, the last one 28 B/px; flows that never leave the registers are not counted). */
 double tw_algorithmic_bytes(const tw_engine* e, int kclass, int level, int width, int height);
-/* The same for a batch of `npairs` pairs: the model follows the schedule's own choices (one shared predicate in
- * csrc/twflow.hip) — a single pair, a batch too small to fill the chip with tw_flow_iter workgroups or a level whose launches
- * do not cover the batch keeps tw_update_matrices + tw_blur_solve* (UPDATE_MATRICES 60 B/px + the coarser flow, window launches
- * 80 / 28 B/px) where a full batch runs tw_flow_iter (56 B/px, no UPDATE_MATRICES launch).  tw_algorithmic_bytes is this with
- * npairs = the engine's slots. */
+/* The same for a batch of `npairs` pairs: the model reads the schedule's own choice (choose_level_schedule in csrc/twflow.hip,
+ * the function the enqueue executes) — a single pair, a batch too small to fill the chip with tw_flow_iter workgroups or a level
+ * whose launches do not cover the batch keeps tw_update_matrices + tw_blur_solve* (UPDATE_MATRICES 60 B/px + the coarser flow,
+ * window launches 80 / 28 B/px) where a full batch runs tw_flow_iter (56 B/px, no UPDATE_MATRICES launch); a level whose images
+ * the coarser level's launch wrote reads no source image.  tw_algorithmic_bytes is this with npairs = the engine's slots.
+ * The batch these three views describe returns hit records only (no flow destination, no initial field), at span 10 — so the
+ * scan-fused option is assumed with the one span it supports — with no profiling class selected; with TW_LANES=2 they answer
+ * for the first lane's half of the batch, the part the schedule decides for.  A size the engine has no plan for (a degenerate
+ * pyramid level, a smoothing kernel or tile beyond the kernels' limits: every submit of that size is refused) has no schedule:
+ * tw_algorithmic_bytes_launch answers 0 for it, tw_level_runs_flow_iter and tw_level_chunk -1.  Before the engine has
+ * enqueued a batch of the size, each call computes the size's plan geometry on the host (7 - 18 us); afterwards it reads the
+ * engine's plan (0.5 us). */
 double tw_algorithmic_bytes_launch(const tw_engine* e, int kclass, int level, int width, int height, int npairs);
-/* 1 if `level` of a batch of `npairs` pairs of width x height runs tw_flow_iter (whole iterations, no M in HBM), 0 if it runs
- * tw_update_matrices + tw_blur_solve* launches, -1 on a bad argument.  The scan-fused option is assumed with span 10. */
+/* 1 if `level` of such a batch of `npairs` pairs of width x height runs tw_flow_iter (whole iterations, no M in HBM), 0 if it
+ * runs tw_update_matrices + tw_blur_solve* launches, -1 on a bad argument. */
 int tw_level_runs_flow_iter(const tw_engine* e, int width, int height, int level, int npairs);
 /* SURVEY.md 8(d) model of one whole pair (each named stage of the reference reads its inputs once and writes its
  * outputs once; 991.8 MB at 1080p with the defaults): the figure BASELINE.md prices a pair against. */
@@ -381,7 +388,7 @@ double tw_algorithmic_bytes_pair(const tw_engine* e, int width, int height, int 
 double tw_min_traffic_bytes_pair(const tw_engine* e, int width, int height, int span);
 /* Number of pyramid levels (= index of the coarsest level) the engine uses for w x h. */
 int tw_num_levels(const tw_engine* e, int width, int height);
-/* Image pairs one kernel launch covers at `level` (the level-major batch schedule), -1 on error. */
+/* Image pairs one kernel launch covers at `level` at most (the level-major batch schedule), -1 on error.  No device call. */
 int tw_level_chunk(tw_engine* e, int width, int height, int level);
 
 /* Isolated timing of one kernel class at `level` of a width x height pair, `npairs` pairs per launch, on

@@ -109,6 +109,23 @@ int tw_debug_blur_plan(const tw_engine* e, int width, int height, int level, int
  * tests/test_gpu_span_scan.py takes its grids' seams from it. */
 int tw_debug_scan_plan(const tw_engine* e, int width, int height, int span, int npairs, int single_pair, int* out, int n);
 
+/* What a batch of npairs pairs of width x height pixels at `span` launches for each pyramid level, from the one function the
+ * enqueue itself executes (choose_level_schedule).  traits: 1 a pair has a flow destination, 2 a pair has an initial field,
+ * 4 a profiling class is selected, 8 the single-pair buffers do not exist.  out[0] the schedule (0: level-major batch, 1: one
+ * pair on two streams, 2: one pair, twin launches), out[1] lanes, out[2] the coarsest level's index L, out[3] 1 when a single
+ * pair's window launches take tw_blur_solve4q, out[4] 1 when the last level-0 iteration is the scan-fused one (tw_blur_grid),
+ * out[5] 1 when level-0 launches that run tw_flow_iter end in the grid-only iteration, out[6] parts P (a lane's share of the
+ * batch each; the pieces of a cold-start ramp are not known in advance), out[7] = 11 values per row; then P x (L + 1) rows,
+ * part-major, level 0 first: [0] pairs of the part, [1] pairs per launch, [2] launches, [3] pairs of the last launch, [4] where
+ * the level's images come from (0: a pyramid launch of its own, 1: the coarser level's launch wrote them, 2: its launch writes
+ * the next finer level's too — tw_pyr_23 at level 3, tw_pyr_k3f at level 1), [5] 1 when the level starts from
+ * tw_flow_area_init's output, [6] 1 when a launch of [1] pairs runs tw_flow_iter, [7] 1 when the identical-pair flags apply to
+ * it, [8] / [9] the same for the last launch, [10] 1 when the flags apply to the part's tw_pyr_k3f launch.  TW_LAT_QUADS and
+ * TW_GRID_FINAL are read at the call, as every batch reads them.  Returns the number of values written (at most n; 0 for a
+ * null `out`, a non-positive size or pair count, a negative span or a size without a plan), -1 for a null engine.
+ * tests/test_gpu_level_plan.py predicts every family's launches from it. */
+int tw_debug_level_plan(const tw_engine* e, int width, int height, int span, int npairs, int traits, int* out, int n);
+
 /* tw_pair_same's flags of the batch this engine enqueued last: out[j] = 1 where pair j's second image is byte for byte its
  * first over the visible width x height pixels (the batch schedule then computed that pair's polynomial expansions once at
  * the levels tw_flow_iter runs), 0 otherwise — and 0 for every pair of a batch that launched no tw_pair_same (TW_SAME_IMAGE=0,

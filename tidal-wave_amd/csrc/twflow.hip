@@ -316,6 +316,7 @@ struct Plan {
     unsigned long long last_use = 0;  // engine's plan clock at the last get_plan (LRU eviction)
 };
 
+constexpr int TW_MAX_LEVELS = 60;  // the most pyramid levels below level 0 a plan may have (plan_geometry clamps pyrLevels)
 constexpr int HOST_RECS = 1024;  // flagged vectors per pair copied back eagerly
 constexpr int NCTX = 3;          // batches that may be in flight (host-side state only)
 // tw_png_unfilter's table of a batch of `cap` pairs: per image a job, a flag word and a 256-byte gray table
@@ -572,6 +573,10 @@ struct tw_engine {
     std::vector<hipEvent_t> lat_ev;
     int lat_s2_max = 1000;  // TW_LAT_S2_LEVELS: finest..this level's image-only work goes to the second stream
     int ramp = 1;  // TW_RAMP=0: no cold-start ramp (A/B)
+    long long chunk_tiles = 300000;      // TW_CHUNK_TILES: tiles a launch covers before a level is split (pairs_per_launch)
+    int chunk_pairs_lv[TW_MAX_LEVELS + 1] = {};  // TW_CHUNK_PAIRS_LEVELS="p0,p1,...": pairs per launch at level 0, 1, ... (0: the rule)
+    int pyr_gen_th = 0;    // TW_PYR_GEN_TH: tile height of the unstaged pyramid kernel (0: by the row buffer's size; A/B)
+    int lat_evtiming = 0;  // TW_LAT_EVTIMING: the single-pair schedule's hand-off events keep their timestamps (diagnostic)
     int fi_maxseg = 4, fi_minsteps = 16;  // TW_FI_MAXSEG / TW_FI_MINSTEPS: most row segments per strip / fewest steps per segment (A/B)
     int fi_skip = 0;    // TW_FI_SKIP (variants library): timing experiments on tw_flow_iter (results are wrong)
     int fi_nt = 1024;   // TW_FI_NT=512 (variants library): tw_flow_iter as two 512-thread workgroups per CU on 64-output strips (A/B)
@@ -818,7 +823,7 @@ void free_plan(Plan* pl)
 }
 
 // pairs one launch covers at a level of w x h pixels (level index k): enough 8-row x 240-column tiles of two images to cover
-// the 256 CUs many times over.  One rule for the plan and for the byte model (tw_algorithmic_bytes_launch).
+// the 256 CUs many times over.  plan_geometry is its one caller: every reader takes LevelPlan::chunk.
 int pairs_per_launch(const tw_engine* e, int w, int h, int k)
 {
     const long long tiles = (long long)((w + PE_TW - 1) / PE_TW) * ((h + PE_TH - 1) / PE_TH) * 2;
@@ -826,22 +831,159 @@ int pairs_per_launch(const tw_engine* e, int w, int h, int k)
     // (16 pairs per level-0 launch) another +2.5 %, 34000 -> a whole 64-pair batch per launch +1.5 %, a whole
     // 128-pair batch +4 % (round 2): every kernel boundary costs a drain, a fill and an L2 write-back of the dirty
     // M planes, and 288 GB of HBM make the workspace of a whole batch (23 GB at 128 x 1080p) a non-issue.  So a
-    // launch covers the whole batch unless that exceeds 300 000 tiles.
-    long long target = 300000;
-    if (const char* ev = getenv("TW_CHUNK_TILES")) target = std::max(1, atoi(ev));
-    long long c = (target + tiles - 1) / tiles;
-    // TW_CHUNK_PAIRS_LEVELS="p0,p1,...": pairs per launch at level 0, 1, ... (0 / missing: the rule above) — the
-    // round-4 Infinity-Cache experiment (does a level's chain run faster when a chunk's R / M planes fit the 256 MB
-    // memory-side cache between its kernels?  profiles/r04_mall_chunks.md)
-    if (const char* ev = getenv("TW_CHUNK_PAIRS_LEVELS")) {
-        const char* q = ev;
-        for (int lv = 0; lv < k && q; lv++) {
-            q = strchr(q, ',');
-            if (q) q++;
-        }
-        if (q && atoi(q) > 0) c = atoi(q);
-    }
+    // launch covers the whole batch unless that exceeds 300 000 tiles (TW_CHUNK_TILES).
+    long long c = (e->chunk_tiles + tiles - 1) / tiles;
+    // TW_CHUNK_PAIRS_LEVELS: the round-4 Infinity-Cache experiment (does a level's chain run faster when a chunk's R / M
+    // planes fit the 256 MB memory-side cache between its kernels?  profiles/r04_mall_chunks.md)
+    if (e->chunk_pairs_lv[k] > 0) c = e->chunk_pairs_lv[k];
     return (int)std::min<long long>(std::max<long long>(c, 1), e->cap);
+}
+
+// The host tables of a plan on their way to the device: what plan_geometry computes and get_plan uploads.
+struct PlanTables {
+    std::vector<ResizeTab> pyr;  // full resolution -> level k
+    std::vector<ResizeTab> ups;  // level k + 1 -> level k (flow upsampling; none at the coarsest level)
+    AreaTab init;                // full resolution -> the coarsest level (tw_flow_area_init)
+};
+
+// The pure part of a plan: everything that depends only on (parameters, engine switches, cap, w0, h0), with no HIP call
+// and no engine state written.  get_plan uploads `tabs` behind it; tw_level_chunk, tw_level_runs_flow_iter, the byte model
+// and tw_debug_level_plan read the geometry as it stands (device pointers null).  *why: the reason of a refusal.
+tw_status plan_geometry(const tw_engine* e, int w0, int h0, Plan* pl, PlanTables* tabs, const char** why)
+{
+    pl->w0 = w0;
+    pl->h0 = h0;
+    pl->levels = plan_levels(w0, h0, e->p.pyrScale, std::min(std::max(e->p.pyrLevels, 0), TW_MAX_LEVELS));
+    pl->lv.resize(pl->levels + 1);
+    tabs->pyr.resize(pl->levels + 1);
+    tabs->ups.resize(pl->levels + 1);
+    for (int k = 0; k <= pl->levels; k++) {
+        LevelPlan& L = pl->lv[k];
+        level_geometry(w0, h0, e->p.pyrScale, k, &L.w, &L.h, &L.sigma, &L.ksize, &L.scale);
+        if (L.w < 1 || L.h < 1 || L.ksize > PYR_MAXK - 1) {
+            *why = "pyramid level degenerate or smoothing kernel too large";
+            return TW_E_UNSUPPORTED;
+        }
+        L.ld = round_up(L.w, 32);
+        L.ps = (long long)L.ld * L.h;
+        L.chunk = pairs_per_launch(e, L.w, L.h, k);
+    }
+    for (int k = 0; k <= pl->levels; k++) {
+        LevelPlan& L = pl->lv[k];
+        ResizeTab& t = tabs->pyr[k];
+        make_resize_tab(w0, h0, L.w, L.h, t);
+        gaussian_kernel(L.ksize, L.sigma, L.h_taps);
+        L.mode = t.mode;
+        L.xmax = t.xmax;
+        if (L.ksize == 3) memcpy(L.h_kern, L.h_taps.data(), sizeof(L.h_kern));
+        L.nrows_max = pyr_nrows_max(t, L.h, h0, L.ksize / 2);
+        // Round 6: the unstaged kernel takes 4-row tiles when an 8-row tile's row buffer is more than 32 KB (a deep level of a
+        // large image: BASELINE configs[4]'s 39- / 79-tap levels of a 4K pyramid).  Twice the workgroups at 0.6 of the work
+        // each, five / three of them per CU instead of three / two, and the last round of a launch no longer a quarter full
+        // (TW_PYR_GEN_TH=8: the old tiles, A/B).
+        {
+            const size_t rb8 = (size_t)L.nrows_max * (t.mode == 0 ? PYR_TW : 2 * PYR_TW) * 4;
+            L.gen_th = e->pyr_gen_th >= 1 && e->pyr_gen_th <= PYR_TH ? e->pyr_gen_th : (rb8 > 32 * 1024 ? 4 : PYR_TH);
+            L.gen_nrows_max = L.gen_th == PYR_TH ? L.nrows_max : pyr_nrows_max(t, L.h, h0, L.ksize / 2, L.gen_th);
+        }
+        const size_t lds = (size_t)(PYR_MAXK + (size_t)L.nrows_max * (t.mode == 0 ? PYR_TW : 2 * PYR_TW)) * 4;
+        if (lds > 160 * 1024) {
+            *why = "pyramid tile does not fit LDS (scale/kernel too large)";
+            return TW_E_UNSUPPORTED;
+        }
+        {
+            // widest staged source span over the tiles of this level (same formulas as the kernel)
+            const int r = L.ksize / 2;
+            int span = 0;
+            for (int x0 = 0; x0 < L.w; x0 += PYR_TW) {
+                const int xl = std::min(x0, L.w - 1), xr = std::min(x0 + PYR_TW - 1, L.w - 1);
+                const int Xfirst = t.mode == 0 ? xl : t.xofs[xl];
+                const int Xlast = t.mode == 0 ? xr : t.xofs[xr] + 1;
+                const int xlo_a = (Xfirst - r) & ~3;
+                span = std::max(span, ((Xlast + r - xlo_a) / 4 + 1) * 4);
+            }
+            const size_t lds2 = lds + (size_t)L.nrows_max * span;
+            L.pitch_b = (lds2 + (size_t)L.nrows_max * 8 + 64 <= 64 * 1024 && L.ksize <= 63) ? span : 0;
+        }
+        if (k < pl->levels) {
+            const LevelPlan& P = pl->lv[k + 1];
+            ResizeTab& u = tabs->ups[k];
+            make_resize_tab(P.w, P.h, L.w, L.h, u);
+            if (u.mode == 2) {
+                // cannot happen for pyr_scale < 1 (the previous level is never twice as large)
+                *why = "unexpected area-fast flow resize";
+                return TW_E_UNSUPPORTED;
+            }
+            L.uxmax = u.xmax;
+        }
+    }
+    {
+        // tw_flow_area_init: full resolution -> the coarsest level (INTER_AREA).  Mode 1 stages a tile of tw output columns'
+        // iy source rows (both channels) in at most 32 KB of LDS; blocks too large for that read memory directly (tw = 0)
+        const LevelPlan& C = pl->lv[pl->levels];
+        AreaTab& t = tabs->init;
+        make_area_tab(w0, h0, C.w, C.h, t);
+        pl->init_mode = t.mode;
+        pl->init_ix = t.ix;
+        pl->init_iy = t.iy;
+        if (t.mode == 1) {
+            const int fit = 32768 / (t.ix * t.iy * 8);
+            pl->init_tw = fit >= 4 ? std::min(128, fit / 4 * 4) : 0;
+        }
+    }
+    // tw_pyr_23 eligibility: both levels are exact INTER_LINEAR reductions by 4 and 8 (sample columns s*x + s/2 - 1 and
+    // + 1 with weights 0.5 / 0.5, no single-tap tail, rows alike) with the 9- / 19-tap kernels of pyr_scale = 0.5
+    if (pl->levels >= 3 && pl->lv[2].ksize == 9 && pl->lv[3].ksize == 19 && pl->lv[2].w == 2 * pl->lv[3].w &&
+        pl->lv[2].h == 2 * pl->lv[3].h && w0 >= 64 && h0 >= 64) {
+        bool exact = true;
+        for (int k = 2; k <= 3 && exact; k++) {
+            const LevelPlan& L = pl->lv[k];
+            const ResizeTab& t = tabs->pyr[k];
+            const int sc = 1 << k;
+            exact = t.mode == 1 && t.xmax == L.w && L.w * sc == w0 && L.h * sc == h0;
+            for (int x = 0; x < L.w && exact; x++)
+                exact = t.xofs[x] == sc * x + sc / 2 - 1 && t.alpha[2 * x] == 0.5f && t.alpha[2 * x + 1] == 0.5f;
+            for (int y = 0; y < L.h && exact; y++)
+                exact = t.yofs[y] == sc * y + sc / 2 - 1 && t.beta[2 * y] == 0.5f && t.beta[2 * y + 1] == 0.5f;
+        }
+        if (exact) {
+            pl->fused23 = true;
+            memcpy(pl->k19 + 1, pl->lv[3].h_taps.data(), sizeof(float) * 19);
+            memcpy(pl->k9 + 1, pl->lv[2].h_taps.data(), sizeof(float) * 9);
+        }
+    }
+    return TW_OK;
+}
+
+// the device part of a plan: the tables plan_geometry made, uploaded
+tw_status upload_plan_tables(tw_engine* e, Plan* pl, const PlanTables& tabs)
+{
+    for (int k = 0; k <= pl->levels; k++) {
+        LevelPlan& L = pl->lv[k];
+        const ResizeTab& t = tabs.pyr[k];
+        TW_TRY(upload_vec(e, pl, t.xofs, &L.d_xofs));
+        TW_TRY(upload_vec(e, pl, t.yofs, &L.d_yofs));
+        TW_TRY(upload_vec(e, pl, t.alpha, &L.d_alpha));
+        TW_TRY(upload_vec(e, pl, t.beta, &L.d_beta));
+        TW_TRY(upload_vec(e, pl, L.h_taps, &L.d_kern));
+        if (k < pl->levels) {
+            const ResizeTab& u = tabs.ups[k];
+            TW_TRY(upload_vec(e, pl, u.xofs, &L.d_uxofs));
+            TW_TRY(upload_vec(e, pl, u.yofs, &L.d_uyofs));
+            TW_TRY(upload_vec(e, pl, u.alpha, &L.d_ualpha));
+            TW_TRY(upload_vec(e, pl, u.beta, &L.d_ubeta));
+        }
+    }
+    const AreaTab& t = tabs.init;
+    if (t.mode == 2) {
+        TW_TRY(upload_vec(e, pl, t.xstart, &pl->d_ixs));
+        TW_TRY(upload_vec(e, pl, t.xsi, &pl->d_ixi));
+        TW_TRY(upload_vec(e, pl, t.xalpha, &pl->d_ixa));
+        TW_TRY(upload_vec(e, pl, t.ystart, &pl->d_iys));
+        TW_TRY(upload_vec(e, pl, t.ysi, &pl->d_iyi));
+        TW_TRY(upload_vec(e, pl, t.ybeta, &pl->d_iyb));
+    }
+    return TW_OK;
 }
 
 tw_status get_plan(tw_engine* e, int w0, int h0, Plan** out)
@@ -868,134 +1010,15 @@ tw_status get_plan(tw_engine* e, int w0, int h0, Plan** out)
         e->plans.erase(victim);
     }
     Plan* pl = new Plan();
-    pl->w0 = w0;
-    pl->h0 = h0;
     pl->last_use = ++e->plan_clock;
-    const int req = std::min(std::max(e->p.pyrLevels, 0), 60);
-    pl->levels = plan_levels(w0, h0, e->p.pyrScale, req);
-    pl->lv.resize(pl->levels + 1);
-    for (int k = 0; k <= pl->levels; k++) {
-        LevelPlan& L = pl->lv[k];
-        level_geometry(w0, h0, e->p.pyrScale, k, &L.w, &L.h, &L.sigma, &L.ksize, &L.scale);
-        if (L.w < 1 || L.h < 1 || L.ksize > PYR_MAXK - 1) {
-            e->err = "pyramid level degenerate or smoothing kernel too large";
-            free_plan(pl);
-            return TW_E_UNSUPPORTED;
-        }
-        L.ld = round_up(L.w, 32);
-        L.ps = (long long)L.ld * L.h;
-        L.chunk = pairs_per_launch(e, L.w, L.h, k);
-    }
-    for (int k = 0; k <= pl->levels; k++) {
-        LevelPlan& L = pl->lv[k];
-        ResizeTab t;
-        make_resize_tab(w0, h0, L.w, L.h, t);
-        std::vector<float> kern;
-        gaussian_kernel(L.ksize, L.sigma, kern);
-        L.mode = t.mode;
-        L.xmax = t.xmax;
-        if (L.ksize == 3) memcpy(L.h_kern, kern.data(), sizeof(L.h_kern));
-        L.h_taps = kern;
-        L.nrows_max = pyr_nrows_max(t, L.h, h0, L.ksize / 2);
-        // Round 6: the unstaged kernel takes 4-row tiles when an 8-row tile's row buffer is more than 32 KB (a deep level of a
-        // large image: BASELINE configs[4]'s 39- / 79-tap levels of a 4K pyramid).  Twice the workgroups at 0.6 of the work
-        // each, five / three of them per CU instead of three / two, and the last round of a launch no longer a quarter full
-        // (TW_PYR_GEN_TH=8: the old tiles, A/B).
-        {
-            static const int gen_th_env = getenv("TW_PYR_GEN_TH") ? atoi(getenv("TW_PYR_GEN_TH")) : 0;
-            const size_t rb8 = (size_t)L.nrows_max * (t.mode == 0 ? PYR_TW : 2 * PYR_TW) * 4;
-            L.gen_th = gen_th_env >= 1 && gen_th_env <= PYR_TH ? gen_th_env : (rb8 > 32 * 1024 ? 4 : PYR_TH);
-            L.gen_nrows_max = L.gen_th == PYR_TH ? L.nrows_max : pyr_nrows_max(t, L.h, h0, L.ksize / 2, L.gen_th);
-        }
-        const size_t lds = (size_t)(PYR_MAXK + (size_t)L.nrows_max * (t.mode == 0 ? PYR_TW : 2 * PYR_TW)) * 4;
-        if (lds > 160 * 1024) {
-            e->err = "pyramid tile does not fit LDS (scale/kernel too large)";
-            free_plan(pl);
-            return TW_E_UNSUPPORTED;
-        }
-        {
-            // widest staged source span over the tiles of this level (same formulas as the kernel)
-            const int r = L.ksize / 2;
-            int span = 0;
-            for (int x0 = 0; x0 < L.w; x0 += PYR_TW) {
-                const int xl = std::min(x0, L.w - 1), xr = std::min(x0 + PYR_TW - 1, L.w - 1);
-                const int Xfirst = t.mode == 0 ? xl : t.xofs[xl];
-                const int Xlast = t.mode == 0 ? xr : t.xofs[xr] + 1;
-                const int xlo_a = (Xfirst - r) & ~3;
-                span = std::max(span, ((Xlast + r - xlo_a) / 4 + 1) * 4);
-            }
-            const size_t lds2 = lds + (size_t)L.nrows_max * span;
-            L.pitch_b = (lds2 + (size_t)L.nrows_max * 8 + 64 <= 64 * 1024 && L.ksize <= 63) ? span : 0;
-        }
-
-        tw_status s;
-        if ((s = upload_vec(e, pl, t.xofs, &L.d_xofs)) || (s = upload_vec(e, pl, t.yofs, &L.d_yofs)) ||
-            (s = upload_vec(e, pl, t.alpha, &L.d_alpha)) || (s = upload_vec(e, pl, t.beta, &L.d_beta)) ||
-            (s = upload_vec(e, pl, kern, &L.d_kern))) {
-            free_plan(pl);
-            return s;
-        }
-        if (k < pl->levels) {
-            const LevelPlan& P = pl->lv[k + 1];
-            ResizeTab u;
-            make_resize_tab(P.w, P.h, L.w, L.h, u);
-            if (u.mode == 2) {
-                // cannot happen for pyr_scale < 1 (the previous level is never twice as large)
-                e->err = "unexpected area-fast flow resize";
-                free_plan(pl);
-                return TW_E_UNSUPPORTED;
-            }
-            L.uxmax = u.xmax;
-            if ((s = upload_vec(e, pl, u.xofs, &L.d_uxofs)) || (s = upload_vec(e, pl, u.yofs, &L.d_uyofs)) ||
-                (s = upload_vec(e, pl, u.alpha, &L.d_ualpha)) || (s = upload_vec(e, pl, u.beta, &L.d_ubeta))) {
-                free_plan(pl);
-                return s;
-            }
-        }
-    }
-    {
-        // tw_flow_area_init: full resolution -> the coarsest level (INTER_AREA).  Mode 1 stages a tile of tw output columns'
-        // iy source rows (both channels) in at most 32 KB of LDS; blocks too large for that read memory directly (tw = 0)
-        const LevelPlan& C = pl->lv[pl->levels];
-        AreaTab t;
-        make_area_tab(w0, h0, C.w, C.h, t);
-        pl->init_mode = t.mode;
-        pl->init_ix = t.ix;
-        pl->init_iy = t.iy;
-        if (t.mode == 1) {
-            const int fit = 32768 / (t.ix * t.iy * 8);
-            pl->init_tw = fit >= 4 ? std::min(128, fit / 4 * 4) : 0;
-        }
-        tw_status s;
-        if (t.mode == 2 &&
-            ((s = upload_vec(e, pl, t.xstart, &pl->d_ixs)) || (s = upload_vec(e, pl, t.xsi, &pl->d_ixi)) ||
-             (s = upload_vec(e, pl, t.xalpha, &pl->d_ixa)) || (s = upload_vec(e, pl, t.ystart, &pl->d_iys)) ||
-             (s = upload_vec(e, pl, t.ysi, &pl->d_iyi)) || (s = upload_vec(e, pl, t.ybeta, &pl->d_iyb)))) {
-            free_plan(pl);
-            return s;
-        }
-    }
-    // tw_pyr_23 eligibility: both levels are exact INTER_LINEAR reductions by 4 and 8 (sample columns s*x + s/2 - 1 and
-    // + 1 with weights 0.5 / 0.5, no single-tap tail, rows alike) with the 9- / 19-tap kernels of pyr_scale = 0.5
-    if (pl->levels >= 3 && pl->lv[2].ksize == 9 && pl->lv[3].ksize == 19 && pl->lv[2].w == 2 * pl->lv[3].w &&
-        pl->lv[2].h == 2 * pl->lv[3].h && w0 >= 64 && h0 >= 64) {
-        bool exact = true;
-        for (int k = 2; k <= 3 && exact; k++) {
-            const LevelPlan& L = pl->lv[k];
-            ResizeTab t;
-            make_resize_tab(w0, h0, L.w, L.h, t);
-            const int sc = 1 << k;
-            exact = t.mode == 1 && t.xmax == L.w && L.w * sc == w0 && L.h * sc == h0;
-            for (int x = 0; x < L.w && exact; x++)
-                exact = t.xofs[x] == sc * x + sc / 2 - 1 && t.alpha[2 * x] == 0.5f && t.alpha[2 * x + 1] == 0.5f;
-            for (int y = 0; y < L.h && exact; y++)
-                exact = t.yofs[y] == sc * y + sc / 2 - 1 && t.beta[2 * y] == 0.5f && t.beta[2 * y + 1] == 0.5f;
-        }
-        if (exact) {
-            pl->fused23 = true;
-            memcpy(pl->k19 + 1, pl->lv[3].h_taps.data(), sizeof(float) * 19);
-            memcpy(pl->k9 + 1, pl->lv[2].h_taps.data(), sizeof(float) * 9);
-        }
+    PlanTables tabs;
+    const char* why = "";
+    tw_status s = plan_geometry(e, w0, h0, pl, &tabs, &why);
+    if (s) e->err = why;
+    else s = upload_plan_tables(e, pl, tabs);
+    if (s) {
+        free_plan(pl);
+        return s;
     }
     e->plans[key] = pl;
     *out = pl;
@@ -1047,7 +1070,7 @@ tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span)
     }
     while (e->lat_streams && e->lat_ev.size() < pl->lv.size()) {
         hipEvent_t ev = nullptr;
-        TW_HIP(e, hipEventCreateWithFlags(&ev, getenv("TW_LAT_EVTIMING") ? hipEventDefault : hipEventDisableTiming));
+        TW_HIP(e, hipEventCreateWithFlags(&ev, e->lat_evtiming ? hipEventDefault : hipEventDisableTiming));
         e->lat_ev.push_back(ev);
     }
     if (e->box) TW_TRY(grow_device(e, e->Vd, e->Vd_cap, need / 2 * 5, need / 2 * 5 * sizeof(double) + 256));
@@ -1377,7 +1400,7 @@ bool flow_iter_eligible(const tw_engine* e, int w, int h)
 {
     return e->win_m == 15 && !e->box && w >= e->mfree_min_w && h >= 4 * FI_TH;
 }
-// ONE predicate for the schedule (flush_ctx) and the byte model (tw_algorithmic_bytes_launch): does a launch of nc
+// The predicate of choose_level_schedule, its one caller (the byte model reads the choice): does a launch of nc
 // pairs at a level of w x h pixels run tw_flow_iter?  lat: the batch takes the single-pair schedule; grid_only: the level's
 // last iteration is evaluated at the span-grid points only (TW_OPT_SCAN_FUSED_FINAL, level 0).  A launch of fewer workgroups
 // than ~3/4 of the CUs — one or two 1080p pairs — leaves the chip to the 224 x 8 tiles of tw_blur_solve4, of which a single
@@ -1872,7 +1895,7 @@ tw_status export_chunk(tw_engine* e, Ctx& c, hipStream_t st, const LevelPlan& L,
 
 // ---- environment switches of the enqueue path ---------------------------------------------------------
 // Three classes, by WHEN a variable is read: (1) engine fields, read once in tw_engine_create (TW_LANES, TW_MFREE,
-// TW_RAMP, TW_LAT_FUSED, TW_LAT_GRAPH, ...); (2) per batch, below: read at the start of every flush_ctx call, because the
+// TW_RAMP, TW_LAT_FUSED, TW_LAT_GRAPH, TW_CHUNK_TILES, ...); (2) per batch, below: read at the start of every flush_ctx call, because the
 // tests switch them between two batches of one engine; (3) per process, further below: measurement and diagnostic
 // switches read once, when the process enqueues its first batch.
 struct BatchSwitches {
@@ -1885,6 +1908,10 @@ struct BatchSwitches {
           lat_plan(getenv("TW_LAT_PLAN") ? atoi(getenv("TW_LAT_PLAN")) : 1),
           scan_seg(!getenv("TW_SCAN_SEG") || atoi(getenv("TW_SCAN_SEG")) != 0),
           grid_final(!getenv("TW_GRID_FINAL") || atoi(getenv("TW_GRID_FINAL")) != 0)
+    {
+    }
+    BatchSwitches(bool lat_quads_, int lat_plan_, bool scan_seg_, bool grid_final_)  // (no environment read)
+        : lat_quads(lat_quads_), lat_plan(lat_plan_), scan_seg(scan_seg_), grid_final(grid_final_)
     {
     }
 };
@@ -1954,9 +1981,141 @@ FlowDst flow_table_row(const void* data, ptrdiff_t pitch, int layout, char* stag
     return d;
 }
 
+// ---- the level schedule ------------------------------------------------------------------------------------
+// What a batch launches for each pyramid level, as one pure function of the plan's geometry, the engine's switches, the
+// batch's switches and traits, and the pairs of the part (a lane's half of the batch, a piece of the cold-start ramp, or
+// the whole batch): BatchEnqueue executes it, the byte model and tw_level_runs_flow_iter / tw_level_chunk are views of it,
+// and tw_debug_level_plan shows it to the tests.
+enum { LS_BATCH = 0, LS_TWO_STREAM = 1, LS_TWIN = 2 };  // level-major batch; one pair on two streams; one pair, twin launches
+// where a level's images come from: a pyramid launch of its own; the coarser level's launch wrote them; the level's launch
+// writes the next finer level's too (tw_pyr_23 at level 3, tw_pyr_k3f at level 1 — in the twin schedule the head's launches)
+enum { IMG_OWN = 0, IMG_FROM_COARSER = 1, IMG_WITH_FINER = 2 };
+struct BatchTraits {
+    int n, span;
+    bool any_fout, any_init;  // a pair has a flow destination / an initial field
+    bool prof_on;             // a profiling class is selected
+    bool lat_buffers;         // the single-pair buffers (lat_I, lat_R) exist
+};
+struct LaunchChoice {
+    bool flow_iter;  // the launch's iterations are tw_flow_iter (no tw_update_matrices, no M planes)
+    bool same;       // the identical-pair flags apply to the launches of the level
+};
+struct LevelChoice {
+    int per, launches, tail;  // pairs per launch (balanced: 64 pairs with a 63-pair chunk are 32 + 32), launches of the part,
+                              // and the pairs of the last one
+    int images;               // IMG_*
+    bool init;                // the level starts from tw_flow_area_init's output (the coarsest level of a batch with initial fields)
+    LaunchChoice full, last;  // of a launch of `per` pairs / of the last launch's `tail` pairs
+    const LaunchChoice& of(int nc) const { return nc == per ? full : last; }
+};
+struct LevelSchedule {
+    int kind = LS_BATCH, nlanes = 1, levels = 0;
+    bool lat_quads = false;    // a single pair's 224 x 8-tile window launches take tw_blur_solve4q (launch_blur)
+    bool fused_final = false;  // the last level-0 iteration at the span-grid points only (TW_OPT_SCAN_FUSED_FINAL: tw_blur_grid)
+    bool grid_final = false;   // level-0 launches that run tw_flow_iter end in the grid-only iteration (tw_flow_iter<15, 3>)
+    bool same01 = false;       // the identical-pair flags apply to the launch that writes levels 1 and 0 (tw_pyr_k3f)
+    size_t ws_lane = 0;        // a lane's share of the workspace (floats of I)
+    LevelChoice lv[TW_MAX_LEVELS + 1];
+    bool single_pair() const { return kind != LS_BATCH; }
+};
+// TW_LANES=2: the two halves of a batch of at least two pairs on two streams
+int batch_lanes(const tw_engine* e, int n) { return (e->lanes > 1 && n >= 2) ? e->lanes : 1; }
+LevelSchedule choose_level_schedule(const tw_engine* e, const Plan& g, const BatchSwitches& sw, const BatchTraits& t, int npart)
+{
+    LevelSchedule s;
+    const int it = e->p.pyrIterations;
+    s.levels = g.levels;
+    s.nlanes = batch_lanes(e, t.n);
+    for (const LevelPlan& L : g.lv) s.ws_lane = std::max(s.ws_lane, (size_t)L.ps * 2 * L.chunk);
+    // one pair: image-only work (pyramid, polynomial expansion) of all levels on the second stream
+    // (only worth its cross-stream hand-offs when the image-only work is tens of microseconds: >= 0.1 Mpixel)
+    const bool lat = s.nlanes == 1 && t.lat_buffers && single_pair_schedule(e, t.n, g.w0, g.h0, g.levels);
+    // ... or, for the default parameters at sizes whose pyramid halves exactly (1080p: BASELINE config 2), ONE stream of twin
+    // launches: every coarse-level chain kernel carries a piece of the finer levels' image-only work in its own launch
+    // (twflow_kernels.hip.h: tw_twin_*) — no cross-queue hand-off anywhere in the pair
+    const bool twin = lat && e->lat_fused && !e->lat_graph && !t.prof_on && g.levels == 3 && g.fused23 && e->pyr_fused &&
+                      pyr01_fusable(&g) && !e->pyr_generic && e->p.polyN == 7 && !e->poly_f32 && e->poly_variant == 1 &&
+                      e->upd_ny == 2 && e->win_m == 15 && !e->box && it >= 1;
+    s.kind = twin ? LS_TWIN : lat ? LS_TWO_STREAM : LS_BATCH;
+    s.lat_quads = lat && sw.lat_quads;  // (TW_LAT_QUADS=0: tw_blur_solve4 as in a batch)
+    // (a batch with a flow destination needs the last level-0 field itself: never the scan-fused final iteration)
+    s.fused_final = scan_fused_level0(e, t.span) && !t.any_fout;
+    // the grid-only last level-0 iteration: a batch that returns hit records alone reads the last field at the span-grid
+    // points only.  (it >= 2: a single iteration is the upsampling one; span >= FI_TH: at most one grid row per step)
+    s.grid_final = sw.grid_final && !lat && !e->scan_fused && !t.any_fout && it >= 2 && t.span >= FI_TH && e->fi_nt == 1024;
+    for (int k = 0; k <= g.levels; k++) {
+        const LevelPlan& L = g.lv[k];
+        LevelChoice& c = s.lv[k];
+        c.per = lat ? 1 : balanced_launch_pairs(npart, L.chunk);
+        c.launches = (npart + c.per - 1) / c.per;
+        c.tail = npart - c.per * (c.launches - 1);
+        c.images = IMG_OWN;
+        c.init = t.any_init && k == g.levels;
+        const bool grid_only = k == 0 && s.fused_final;
+        for (LaunchChoice* lc : {&c.full, &c.last}) {
+            // THE place "this level runs tw_flow_iter" is decided (level_runs_flow_iter: the CU gate counts the launch's pairs)
+            lc->flow_iter = level_runs_flow_iter(e, L.w, L.h, lc == &c.full ? c.per : c.tail, lat, grid_only);
+            // ... and "the identical-pair flags apply here": only where EVERY reader of the level's second expansions takes the
+            // first in their place — tw_flow_iter does, the update / window kernels (and the scan-fused last iteration's
+            // tw_update_matrices at level 0) do not, and their levels get both expansions
+            lc->same = e->same_image && lc->flow_iter && !grid_only;
+        }
+    }
+    if (twin) {  // tw_pyr_23, then tw_pyr_k3f carried by the coarsest level's expansion (enqueue_twin_head launches exactly
+                 // these; the labels are what the byte model prices a single pair's levels 2 and 0 by)
+        s.lv[3].images = s.lv[1].images = IMG_WITH_FINER;
+        s.lv[2].images = s.lv[0].images = IMG_FROM_COARSER;
+    } else if (!lat) {
+        // levels 3 and 2 from one read of the images (tw_pyr_23): level 3's launch also writes level 2's images, behind its own
+        // in the workspace (sized for level 0: there is room — the last condition), and level 2 skips its pyramid launch.  Only
+        // when one launch covers the part at both levels: the loop is level-major, a second chunk of level 3 would overwrite
+        // the first chunk's level-2 images before level 2 reads them.  (fused23: the plan has at least four levels)
+        if (g.fused23 && e->pyr_fused && g.lv[3].chunk >= npart && g.lv[2].chunk >= npart &&
+            (size_t)(g.lv[3].ps + g.lv[2].ps) * 2 * npart <= s.ws_lane) {
+            s.lv[3].images = IMG_WITH_FINER;
+            s.lv[2].images = IMG_FROM_COARSER;
+        }
+        // levels 1 and 0 likewise (tw_pyr_k3f): level 0's images wait in the M1 region, which nothing else touches while levels
+        // 1 and 0 both run tw_flow_iter (their iterations ping-pong through M0 only) and which is large enough (5 planes per
+        // pair against 2 images of one)
+        if (e->pyr_fused && pyr01_fusable(&g) && !e->pyr_generic && g.lv[1].chunk >= npart && g.lv[0].chunk >= npart &&
+            s.lv[0].full.flow_iter && s.lv[1].full.flow_iter) {
+            s.lv[1].images = IMG_WITH_FINER;
+            s.lv[0].images = IMG_FROM_COARSER;
+            // (tw_pyr_k3f writes both levels: it may skip an image only when both levels skip its expansion)
+            s.same01 = s.lv[0].full.same && s.lv[1].full.same;
+        }
+    }
+    return s;
+}
+// The geometry of a size for the exports: the engine's own plan when a batch has built one (its geometry is plan_geometry's,
+// fixed at engine creation), else computed into *scratch — 0.5 us against 7 - 18 us a call (profiles/level_schedule.md).
+// Null when the size has no plan.
+const Plan* plan_geometry_of(const tw_engine* e, int width, int height, Plan* scratch)
+{
+    const auto it = e->plans.find(std::make_pair(width, height));
+    if (it != e->plans.end()) return it->second;
+    PlanTables tabs;
+    const char* why = "";
+    if (width < 1 || height < 1 || plan_geometry(e, width, height, scratch, &tabs, &why) != TW_OK) return nullptr;
+    return scratch;
+}
+// The choice as the exports see it (tw_level_runs_flow_iter, the byte model): a batch of npairs pairs that returns hit records
+// at span 10 and nothing else, no profiling class selected, the single-pair buffers in place; the per-level answers are those
+// of the batch's first part (the whole batch, or the first lane's half with TW_LANES=2).  Returns the geometry, null without one.
+const Plan* level_schedule_view(const tw_engine* e, int width, int height, int npairs, Plan* scratch, LevelSchedule* s)
+{
+    const Plan* g = plan_geometry_of(e, width, height, scratch);
+    if (!g) return nullptr;
+    const BatchTraits t{npairs, 10, false, false, false, true};
+    *s = choose_level_schedule(e, *g, BatchSwitches(true, 1, true, true), t, npairs / batch_lanes(e, npairs));
+    return g;
+}
+
 // One launch group of the level loop: pairs [j0, j0 + nc) of the batch at level k, on stream ls with lane's workspace
 struct LevelChunk {
     int k, lane, j0, nc;
+    LaunchChoice lc;   // of this launch (choose_level_schedule)
     hipStream_t ls;
     float* I;          // the lane's image workspace (batch schedule)
     float* R;          // polynomial expansions of the chunk's images
@@ -1967,7 +2126,7 @@ struct LevelChunk {
     // scan-fused final iteration (option TW_OPT_SCAN_FUSED_FINAL): nothing but the span grid of the last level-0 flow is
     // read afterwards, so the last window average + solve runs at the grid points only
     bool grid_only;
-    // the grid-only last iteration (tw_flow_iter<15, 3>; BatchEnqueue::grid_final): the chunk's last tw_flow_iter launch writes
+    // the grid-only last iteration (tw_flow_iter<15, 3>; LevelSchedule::grid_final): the chunk's last tw_flow_iter launch writes
     // the span-grid samples and no field — no tw_span_gather launch
     bool grid_last;
     // a batch with initial flow fields: every chunk of the coarsest level starts from tw_flow_area_init's output (zeros
@@ -1990,11 +2149,10 @@ struct BatchEnqueue {
     long long stride;
     int gw = 0, gh = 0;  // the span grid of level 0 (span > 0)
     int ramp_b[4] = {0, 0, 0, 0}, ramp_n = 1;  // cold-start ramp: piece i = pairs [ramp_b[i], ramp_b[i + 1]); ramp_n - 1 pieces
-    // the schedule (choose_schedule)
-    int nlanes = 1;
-    size_t ws_lane = 0;
-    bool prof_on = false, lat = false, lat2 = false, lat_quads = false, fused_final = false;
-    bool grid_final = false;  // level-0 chunks that run tw_flow_iter end in the grid-only iteration (choose_schedule)
+    // the schedule (choose_schedule): the batch-wide fields hold for the whole batch, the per-level ones for the part being
+    // enqueued (enqueue_batch_levels asks again for every part)
+    BatchTraits traits = {};
+    LevelSchedule sched;
     std::vector<size_t> lat_off;  // a level's offset in lat_I (x 5 in lat_R)
     // the side jobs of the twin schedule, in the order the chain needs their results (empty in every other schedule)
     std::vector<SideJob> sideq;
@@ -2242,41 +2400,25 @@ struct BatchEnqueue {
         return TW_OK;
     }
 
-    // which of the three schedules the level loop takes: the batch schedule (on one or two lanes), or for one pair
-    // the two-stream schedule (lat) or the twin launches (lat2)
+    // which of the three schedules the level loop takes, and what it launches per level: choose_level_schedule's answer for
+    // the whole batch (the parts of the batch schedule get their own in enqueue_batch_levels)
     tw_status choose_schedule()
     {
-        nlanes = (e->lanes > 1 && n >= 2) ? e->lanes : 1;
-        if (nlanes > 1) {
+        traits = BatchTraits{n, c.span, c.any_fout, c.any_init, false, e->lat_I != nullptr};
+        for (int i = 0; i < TW_K_COUNT; i++) traits.prof_on = traits.prof_on || e->prof_level[i] != -2;
+        sched = choose_level_schedule(e, *pl, sw, traits, n);
+        if (sched.nlanes > 1) {
             TW_HIP(e, hipEventRecord(e->ev_fork, st));  // uploads + whatever ran before on the main stream
             TW_HIP(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
         }
-        for (const LevelPlan& L : pl->lv) ws_lane = std::max(ws_lane, (size_t)L.ps * 2 * L.chunk);
-        // one pair: image-only work (pyramid, polynomial expansion) of all levels on the second stream
-        // (only worth its cross-stream hand-offs when the image-only work is tens of microseconds: >= 0.1 Mpixel)
-        lat = nlanes == 1 && e->lat_I && single_pair_schedule(e, n, c.w, c.h, pl->levels);
-        for (int i = 0; i < TW_K_COUNT; i++) prof_on = prof_on || e->prof_level[i] != -2;
-        // ... or, for the default parameters at sizes whose pyramid halves exactly (1080p: BASELINE config 2), ONE stream of twin
-        // launches: every coarse-level chain kernel carries a piece of the finer levels' image-only work in its own launch
-        // (twflow_kernels.hip.h: tw_twin_*) — no cross-queue hand-off anywhere in the pair
-        lat2 = lat && e->lat_fused && !e->lat_graph && !prof_on && pl->levels == 3 && pl->fused23 && e->pyr_fused &&
-               pyr01_fusable(pl) && !e->pyr_generic && e->p.polyN == 7 && !e->poly_f32 && e->poly_variant == 1 &&
-               e->upd_ny == 2 && e->win_m == 15 && !e->box && it >= 1;
-        // a single pair's 224 x 8-tile window launches take tw_blur_solve4q (launch_blur; TW_LAT_QUADS=0: tw_blur_solve4 as in a batch)
-        lat_quads = lat && sw.lat_quads;
         lat_off.assign(pl->lv.size(), 0);
-        if (lat) {
+        if (sched.single_pair()) {
             size_t off = 0;
             for (size_t k = 0; k < pl->lv.size(); k++) {
                 lat_off[k] = off;
                 off += (size_t)pl->lv[k].ps * 2;
             }
         }
-        // (a batch with a flow destination needs the last level-0 field itself: never the scan-fused final iteration)
-        fused_final = scan_fused_level0(e, c.span) && !c.any_fout;
-        // the grid-only last level-0 iteration: a batch that returns hit records alone reads the last field at the span-grid
-        // points only.  (it >= 2: a single iteration is the upsampling one; span >= FI_TH: at most one grid row per step)
-        grid_final = sw.grid_final && !lat && !e->scan_fused && !c.any_fout && it >= 2 && c.span >= FI_TH && e->fi_nt == 1024;
         return TW_OK;
     }
 
@@ -2290,7 +2432,7 @@ struct BatchEnqueue {
     tw_status enqueue_or_replay_graph()
     {
         // (destinations / fields would be baked into the graph; a reconciled pair's slots are not what the key describes)
-        if (lat && e->lat_graph && !prof_on && !c.any_fout && !c.any_init && !c.any_resize) {
+        if (sched.single_pair() && e->lat_graph && !traits.prof_on && !c.any_fout && !c.any_init && !c.any_resize) {
             const GraphKey key{c.w, c.h, c.span, stride, e->img_aligned4, e->scan_fused, e->poly_f32};
             auto git = e->lat_graphs.find(key);
             if (git == e->lat_graphs.end()) {
@@ -2349,13 +2491,13 @@ struct BatchEnqueue {
             ProfScope pscope(e, st, TW_K_SCAN, 0);
 #ifdef TW_VARIANTS
             // (scan_fused_level0, not fused_final: a batch with a flow destination keeps its gathered grid either way)
-            if (lat && !scan_fused_level0(e, c.span) && process_switches().scan_direct) {
+            if (sched.single_pair() && !scan_fused_level0(e, c.span) && process_switches().scan_direct) {
                 TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<true>, dim3(n), dim3(1024), 0, st, a);
             } else
 #endif
             {
                 // a single pair: 16 segments, each workgroup counting the hits before its own (tw_span_scan_seg: -5 us of one CU's VALU time)
-                launch_scan(e, st, a, choose_scan(n, lat, a.gw, a.gh, sw.scan_seg), n);
+                launch_scan(e, st, a, choose_scan(n, sched.single_pair(), a.gw, a.gh, sw.scan_seg), n);
             }
         }
         TW_HIP(e, hipEventRecord(c.ev_stop, st));
@@ -2388,8 +2530,8 @@ struct BatchEnqueue {
     // captured hipGraph (enqueue_or_replay_graph), every other batch enqueues it directly.
     tw_status enqueue_levels()
     {
-        if (lat2) return enqueue_twin_pair();
-        if (lat) return enqueue_two_stream_pair();
+        if (sched.kind == LS_TWIN) return enqueue_twin_pair();
+        if (sched.kind == LS_TWO_STREAM) return enqueue_two_stream_pair();
         return enqueue_batch_levels();
     }
 
@@ -2401,7 +2543,9 @@ struct BatchEnqueue {
         ch.lane = lane;
         ch.j0 = j0;
         ch.nc = nc;
+        ch.lc = sched.lv[k].of(nc);
         ch.ls = lane == 0 ? st : e->stream2;
+        const size_t ws_lane = sched.ws_lane;
         ch.I = e->I + ws_lane * lane;
         ch.R = e->R + ws_lane * 5 * lane;
         ch.M0 = e->M[0] + ws_lane / 2 * 5 * lane;
@@ -2409,9 +2553,9 @@ struct BatchEnqueue {
         ch.Vbox = e->Vd ? e->Vd + ws_lane / 2 * 5 * lane : nullptr;
         ch.flow_cur = e->flow[k] + (k == 0 ? (size_t)lane * L.chunk * 2 * L.ps : (size_t)j0 * 2 * L.ps);
         ch.flow_prev = k < pl->levels ? e->flow[k + 1] + (size_t)j0 * 2 * pl->lv[k + 1].ps : nullptr;
-        ch.grid_only = k == 0 && fused_final;
-        ch.grid_last = k == 0 && grid_final && level_mfree(0, nc);
-        ch.init_lv = c.any_init && k == pl->levels;
+        ch.grid_only = k == 0 && sched.fused_final;
+        ch.grid_last = k == 0 && sched.grid_final && ch.lc.flow_iter;
+        ch.init_lv = sched.lv[k].init;
         return ch;
     }
     // a single pair's only chunk of level k: every level's R stays in lat_R until the pair is done
@@ -2421,12 +2565,6 @@ struct BatchEnqueue {
         ch.R = e->lat_R + 5 * lat_off[k];
         return ch;
     }
-    // does level k of a launch of nc pairs run tw_flow_iter?  (level_runs_flow_iter: the predicate the byte model shares)
-    bool level_mfree(int k, int nc) const
-    {
-        const LevelPlan& L = pl->lv[k];
-        return level_runs_flow_iter(e, L.w, L.h, nc, lat, k == 0 && fused_final);
-    }
     float2* grid_of(int j0) const { return e->d_grid + (size_t)j0 * gw * gh; }
 
     // -- the batch schedule: level-major, every level for all pairs of a part before the next finer level starts.  A part
@@ -2435,23 +2573,24 @@ struct BatchEnqueue {
     tw_status enqueue_batch_levels()
     {
         const bool ramp = ramp_n > 2;
+        const int nlanes = sched.nlanes;
         const int nparts = ramp ? ramp_n - 1 : nlanes;
         for (int part = 0; part < nparts; part++) {
             const int lane = ramp ? 0 : part;
             const int lo = ramp ? ramp_b[part] : (int)((long long)n * lane / nlanes);
             const int hi = ramp ? ramp_b[part + 1] : (int)((long long)n * (lane + 1) / nlanes);
             if (ramp) TW_HIP(e, hipStreamWaitEvent(st, part + 1 < nparts ? c.ev_seg[part] : c.ev_h2d, 0));
+            sched = choose_level_schedule(e, *pl, sw, traits, hi - lo);
             TW_TRY(enqueue_pair_same(lane == 0 ? st : e->stream2, lo, hi));
             for (int k = pl->levels; k >= 0; k--) {
                 const LevelPlan& L = pl->lv[k];
                 RoctxRange level_range("tw_level %d (%dx%d)", k, L.w, L.h);
-                // balanced launches: 64 pairs with a 63-pair chunk are 32 + 32, not 63 + 1
-                const int per = balanced_launch_pairs(hi - lo, L.chunk);
+                const int per = sched.lv[k].per;
                 for (int j0 = lo; j0 < hi; j0 += per) {
                     const LevelChunk ch = make_chunk(k, lane, j0, std::min(per, hi - j0));
-                    TW_TRY(enqueue_level_images(ch, hi - lo));
+                    TW_TRY(enqueue_level_images(ch));
                     bool grid_stored = false;
-                    if (level_mfree(k, ch.nc)) enqueue_flow_iter_chain(ch);
+                    if (ch.lc.flow_iter) enqueue_flow_iter_chain(ch);
                     else enqueue_update_blur_chain(ch, &grid_stored);
                     TW_TRY(enqueue_level0_outputs(ch, grid_stored));
                 }
@@ -2480,42 +2619,24 @@ struct BatchEnqueue {
         e->same_valid = true;
         return TW_OK;
     }
-    // the flags of a chunk's pairs for the launches of level k — only where EVERY reader of the level's second expansions
-    // takes the first in their place: tw_flow_iter does, the update / window kernels (enqueue_update_blur_chain, and the
-    // scan-fused last iteration's tw_update_matrices at level 0) do not, and their levels get both expansions as before
-    const unsigned* same_flags_of(const LevelChunk& ch) const { return same_flags_of(ch.k, ch.j0, ch.nc); }
-    const unsigned* same_flags_of(int k, int j0, int nc) const
-    {
-        return (e->same_image && level_mfree(k, nc) && !(k == 0 && fused_final)) ? e->d_same + j0 : nullptr;
-    }
+    // the identical-pair flags of a chunk's pairs, where the schedule lets the chunk's launches read them
+    const unsigned* same_flags_of(const LevelChunk& ch) const { return ch.lc.same ? e->d_same + ch.j0 : nullptr; }
 
-    // pyramid + polynomial expansion of a chunk's images (batch schedule); npart: the pairs of the chunk's part
-    tw_status enqueue_level_images(const LevelChunk& ch, int npart)
+    // pyramid + polynomial expansion of a chunk's images (batch schedule), from where the schedule says they come
+    tw_status enqueue_level_images(const LevelChunk& ch)
     {
         const int k = ch.k, nc = ch.nc;
         const LevelPlan& L = pl->lv[k];
-        // levels 3 and 2 from one read of the images (tw_pyr_23): level 3's launch also writes level 2's
-        // images, behind its own in the workspace (sized for level 0: there is room), and level 2 skips its
-        // pyramid launch.  Only when both levels cover the same pairs per launch.
-        // (one launch per level for this lane: the loop is level-major, a second chunk of level 3 would
-        // overwrite the first chunk's level-2 images before level 2 reads them)
-        const bool f23 = pl->fused23 && e->pyr_fused && pl->lv[3].chunk >= npart && pl->lv[2].chunk >= npart &&
-                         (size_t)(pl->lv[3].ps + pl->lv[2].ps) * 2 * nc <= ws_lane;
-        float* I2side = f23 ? ch.I + (size_t)pl->lv[3].ps * 2 * nc : nullptr;  // (a plan may have fewer than 4 levels: ADVICE r5)
-        // levels 1 and 0 likewise (tw_pyr_k3f): level 0's images wait in the M1 region, which nothing else
-        // touches while levels 1 and 0 both run tw_flow_iter (their iterations ping-pong through M0 only) and
-        // which is large enough (5 planes per pair against 2 images of one)
-        const bool f01 = e->pyr_fused && pyr01_fusable(pl) && !e->pyr_generic && pl->lv[1].chunk >= npart &&
-                         pl->lv[0].chunk >= npart && level_mfree(0, nc) && level_mfree(1, nc);
-        float* I0side = ch.M1;
+        const int images = sched.lv[k].images;
+        // tw_pyr_23 writes level 2's images behind level 3's in the lane's workspace; tw_pyr_k3f leaves level 0's in the M1
+        // region (choose_level_schedule has checked that both fit and stay untouched)
+        float* Iside = images == IMG_OWN ? nullptr : k >= 2 ? ch.I + (size_t)pl->lv[3].ps * 2 * nc : ch.M1;
         const uint8_t* const* srcs = e->d_ptrs + 2 * ch.j0;
-        // (tw_pyr_k3f writes levels 1 and 0 together: it may skip an image only when both levels skip its expansion)
         const unsigned* same = same_flags_of(ch);
-        const unsigned* same01 = same_flags_of(0, ch.j0, nc) ? same : nullptr;
-        if (f23 && k == 3) launch_pyr23(e, ch.ls, pl, srcs, stride, ch.I, I2side, 2 * nc);
-        else if (f01 && k == 1) launch_pyr01(e, ch.ls, pl, srcs, stride, ch.I, I0side, 2 * nc, same01);
-        else if (!(f23 && k == 2) && !(f01 && k == 0)) launch_pyr(e, ch.ls, pl, k, srcs, stride, ch.I, 2 * nc, same);
-        const float* Isrc = (f23 && k == 2) ? I2side : (f01 && k == 0) ? I0side : ch.I;
+        if (images == IMG_WITH_FINER && k == 3) launch_pyr23(e, ch.ls, pl, srcs, stride, ch.I, Iside, 2 * nc);
+        else if (images == IMG_WITH_FINER) launch_pyr01(e, ch.ls, pl, srcs, stride, ch.I, Iside, 2 * nc, sched.same01 ? same : nullptr);
+        else if (images == IMG_OWN) launch_pyr(e, ch.ls, pl, k, srcs, stride, ch.I, 2 * nc, same);
+        const float* Isrc = images == IMG_FROM_COARSER ? Iside : ch.I;
         return launch_polyexp(e, ch.ls, L.w, L.h, L.ld, L.ps, Isrc, ch.R, 2 * nc, k, nullptr, nullptr, same);
     }
 
@@ -2767,9 +2888,9 @@ struct BatchEnqueue {
                 continue;
             }
             b.Vbox = ch.Vbox;
-            b.quads = lat_quads;
+            b.quads = sched.lat_quads;
             GridOut go;
-            if (lat && k == 0 && last && c.span > 0) {
+            if (sched.single_pair() && k == 0 && last && c.span > 0) {
                 // the launch that stores the final flow stores its span-grid samples too: no tw_span_gather launch
                 go = GridOut{grid_of(ch.j0), c.span, gw, gh, grid_stored};
                 b.go = &go;
@@ -3644,6 +3765,15 @@ tw_status tw_engine_create(int device, const tw_params* params, int slots, tw_en
 #endif
     if (const char* ev = getenv("TW_LAT_S2_LEVELS")) e->lat_s2_max = atoi(ev);
     if (const char* ev = getenv("TW_RAMP")) e->ramp = atoi(ev) ? 1 : 0;
+    if (const char* ev = getenv("TW_CHUNK_TILES")) e->chunk_tiles = std::max(1, atoi(ev));
+    if (const char* ev = getenv("TW_CHUNK_PAIRS_LEVELS"))
+        for (int lv = 0; lv <= TW_MAX_LEVELS && ev; lv++) {
+            e->chunk_pairs_lv[lv] = std::max(0, atoi(ev));
+            ev = strchr(ev, ',');
+            if (ev) ev++;
+        }
+    if (const char* ev = getenv("TW_PYR_GEN_TH")) e->pyr_gen_th = atoi(ev);
+    e->lat_evtiming = getenv("TW_LAT_EVTIMING") != nullptr;
     if (const char* ev = getenv("TW_SAME_IMAGE")) e->same_image = atoi(ev) ? 1 : 0;
     if (const char* ev = getenv("TW_FI_MAXSEG")) e->fi_maxseg = std::min(64, std::max(1, atoi(ev)));
     if (const char* ev = getenv("TW_FI_MINSTEPS")) e->fi_minsteps = std::max(2, atoi(ev));
@@ -4225,29 +4355,25 @@ tw_status tw_prof_read(tw_engine* e, int kclass, double* ms_total, int* launches
 int tw_num_levels(const tw_engine* e, int width, int height)
 {
     if (!e) return -1;
-    return plan_levels(width, height, e->p.pyrScale, std::min(std::max(e->p.pyrLevels, 0), 60));
+    return plan_levels(width, height, e->p.pyrScale, std::min(std::max(e->p.pyrLevels, 0), TW_MAX_LEVELS));
 }
 
 int tw_level_chunk(tw_engine* e, int width, int height, int level)
 {
     if (!e) return -1;
-    if (hipSetDevice(e->device) != hipSuccess) return -1;
-    Plan* pl = nullptr;
-    if (get_plan(e, width, height, &pl) != TW_OK || level < 0 || level > pl->levels) return -1;
-    return pl->lv[level].chunk;
+    Plan scratch;
+    const Plan* g = plan_geometry_of(e, width, height, &scratch);
+    return g && level >= 0 && level <= g->levels ? g->lv[level].chunk : -1;
 }
 
 int tw_level_runs_flow_iter(const tw_engine* e, int width, int height, int level, int npairs)
 {
     if (!e || npairs < 1) return -1;
-    const int L = tw_num_levels(e, width, height);
-    if (level < 0 || level > L) return -1;
-    int w, h, ks;
-    double sg, sc;
-    level_geometry(width, height, e->p.pyrScale, level, &w, &h, &sg, &ks, &sc);
-    const int nc = balanced_launch_pairs(npairs, pairs_per_launch(e, w, h, level));
-    return level_runs_flow_iter(e, w, h, nc, single_pair_schedule(e, npairs, width, height, L),
-                                level == 0 && scan_fused_level0(e, 10)) ? 1 : 0;
+    Plan scratch;
+    LevelSchedule s;
+    const Plan* g = level_schedule_view(e, width, height, npairs, &scratch, &s);
+    if (!g || level < 0 || level > g->levels) return -1;
+    return s.lv[level].full.flow_iter ? 1 : 0;
 }
 
 double tw_algorithmic_bytes(const tw_engine* e, int kclass, int level, int width, int height)
@@ -4258,69 +4384,37 @@ double tw_algorithmic_bytes(const tw_engine* e, int kclass, int level, int width
 double tw_algorithmic_bytes_launch(const tw_engine* e, int kclass, int level, int width, int height, int npairs)
 {
     if (!e || npairs < 1) return 0;
-    const int L = tw_num_levels(e, width, height);
-    if (level < 0 || level > L) return 0;
-    int w, h, ks;
-    double sg, sc;
-    level_geometry(width, height, e->p.pyrScale, level, &w, &h, &sg, &ks, &sc);
-    const double N = (double)w * h, N0 = (double)width * height;
+    Plan scratch;
+    LevelSchedule s;
+    const Plan* g = level_schedule_view(e, width, height, npairs, &scratch, &s);
+    if (!g || level < 0 || level > g->levels) return 0;
+    const int L = g->levels;
+    const double N = (double)g->lv[level].w * g->lv[level].h, N0 = (double)width * height;
+    const double Nprev = level < L ? (double)g->lv[level + 1].w * g->lv[level + 1].h : 0;  // the coarser level's pixels
     const int it = e->p.pyrIterations;
-    // as built (round 5), with the SAME predicates as the schedule (flush_ctx): levels that run tw_flow_iter have no
+    // as built, read off the schedule's own choice (choose_level_schedule): levels that run tw_flow_iter have no
     // FarnebackUpdateMatrices launch and no M planes (flow 8N + R0 20N + R1 20N in, flow 8N out = 56N per iteration; the first
-    // one reads the coarser level's flow, 8 N_{k+1}, instead of this level's); levels 3 and 2 of an exact-halving pyramid come
-    // from one read of the images.  A single pair, a small batch or a narrow level keeps tw_update_matrices + tw_blur_solve*.
-    const bool mfree = tw_level_runs_flow_iter(e, width, height, level, npairs) == 1;
-    const bool lat = single_pair_schedule(e, npairs, width, height, L);
-    auto whole_batch = [&](int k) {  // one launch covers the batch at level k
-        int wk, hk;
-        level_geometry(width, height, e->p.pyrScale, k, &wk, &hk, &sg, &ks, &sc);
-        return pairs_per_launch(e, wk, hk, k) >= npairs;
-    };
-    const bool fused23 = e->pyr_fused && L >= 3 && e->p.pyrScale == 0.5 && width % 8 == 0 && height % 8 == 0 && width >= 64 &&
-                         height >= 64 && (lat || (whole_batch(3) && whole_batch(2)));
+    // one reads the coarser level's flow, 8 N_{k+1}, instead of this level's); a level whose images the coarser level's launch
+    // wrote (tw_pyr_23, tw_pyr_k3f) reads no source image.  A single pair, a small batch or a narrow level keeps
+    // tw_update_matrices + tw_blur_solve*.
+    const bool mfree = s.lv[level].full.flow_iter;
     switch (kclass) {
-        case TW_K_PYR: {
-            if (fused23 && level == 2) return 2 * (4 * N);  // written by level 3's launch
-            // levels 1 and 0 from one read (tw_pyr_k3f) when both run tw_flow_iter, level 1 is an exact halving and a launch
-            // covers the batch at both levels (the single-pair schedule's twin launches carry tw_pyr_k3f as well)
-            int w1 = 0, h1 = 0;
-            if (L >= 1) level_geometry(width, height, e->p.pyrScale, 1, &w1, &h1, &sg, &ks, &sc);
-            const bool exact01 = e->pyr_fused && !e->pyr_generic && L >= 1 && width == 2 * w1 && height == 2 * h1 && width >= 16;
-            const bool fused01 = exact01 && (lat ? (e->lat_fused && L == 3 && fused23)
-                                                 : (whole_batch(0) && whole_batch(1) &&
-                                                    tw_level_runs_flow_iter(e, width, height, 0, npairs) == 1 &&
-                                                    tw_level_runs_flow_iter(e, width, height, 1, npairs) == 1));
-            if (fused01 && level == 0) return 2 * (4 * N);  // written by level 1's launch
+        case TW_K_PYR:
+            if (s.lv[level].images == IMG_FROM_COARSER) return 2 * (4 * N);  // written by the coarser level's launch
             return 2 * (N0 + 4 * N);
-        }
         case TW_K_POLYEXP: return 48 * N;  // 2 images x (4 + 20) B/px
-        case TW_K_UPDATE_MATRICES: {
+        case TW_K_UPDATE_MATRICES:
             if (mfree) return 0;
             // R0 20N + R1 20N read, M 20N written; the level's initial flow is read from the coarser level (8 N_{k+1})
             // and is only stored when no iteration follows (the first blur launch recomputes nothing from it: the
             // refresh of iteration 0 uses M, and the flow itself is rewritten by the first solve)
-            double up = it == 0 ? 8 * N : 0;
-            if (level < L) {
-                int pw, ph;
-                level_geometry(width, height, e->p.pyrScale, level + 1, &pw, &ph, &sg, &ks, &sc);
-                up += 8.0 * pw * ph;
-            }
-            return 60 * N + up;
-        }
+            return 60 * N + ((it == 0 ? 8 * N : 0) + 8 * Nprev);
         case TW_K_BLUR_SOLVE:
             // average over the `it` launches of a level.  The last one reads M (20N) and writes the flow (8N).  The
             // others are fused with the FarnebackUpdateMatrices refresh: M 20N + R0 20N + R1 20N read, M 20N
             // written = 80N — the flow they compute stays in registers and is never stored (counting
             // 28N + 68N charged 16N the kernel does not move).
-            if (mfree) {
-                double first = 48 * N;
-                if (level < L) {
-                    int pw, ph;
-                    level_geometry(width, height, e->p.pyrScale, level + 1, &pw, &ph, &sg, &ks, &sc);
-                    first += 8.0 * pw * ph;
-                }
-                return (first + (it - 1) * 56 * N) / it;
-            }
+            if (mfree) return (48 * N + 8 * Nprev + (it - 1) * 56 * N) / it;
             return it > 0 ? (28 * N + (it - 1) * 80 * N) / it : 0;
         default: return 0;
     }
@@ -4459,6 +4553,33 @@ extern "C" int tw_debug_scan_plan(const tw_engine* e, int width, int height, int
     const int v[7] = {c.kernel, gw, gh, (int)c.G, c.S, c.segments, c.rounds};
     int i = 0;
     for (; i < n && i < 7; i++) out[i] = v[i];
+    return i;
+}
+
+extern "C" int tw_debug_level_plan(const tw_engine* e, int width, int height, int span, int npairs, int traits, int* out, int n)
+{
+    if (!e) return -1;
+    if (!out || width < 1 || height < 1 || span < 0 || npairs < 1) return 0;
+    Plan scratch;
+    const Plan* gp = plan_geometry_of(e, width, height, &scratch);
+    if (!gp) return 0;
+    const Plan& g = *gp;
+    const BatchTraits t{npairs, span, (traits & 1) != 0, (traits & 2) != 0, (traits & 4) != 0, !(traits & 8)};
+    const BatchSwitches sw;  // (read at the call, as every batch reads them)
+    const int parts = batch_lanes(e, npairs);
+    std::vector<int> v;
+    for (int part = 0; part < parts; part++) {
+        const int npart = (int)((long long)npairs * (part + 1) / parts) - (int)((long long)npairs * part / parts);
+        const LevelSchedule s = choose_level_schedule(e, g, sw, t, npart);
+        if (part == 0) v = {s.kind, s.nlanes, s.levels, s.lat_quads, s.fused_final, s.grid_final, parts, 11};
+        for (int k = 0; k <= s.levels; k++) {
+            const LevelChoice& c = s.lv[k];
+            v.insert(v.end(), {npart, c.per, c.launches, c.tail, c.images, c.init, c.full.flow_iter, c.full.same, c.last.flow_iter,
+                               c.last.same, s.same01});
+        }
+    }
+    int i = 0;
+    for (; i < n && i < (int)v.size(); i++) out[i] = v[i];
     return i;
 }
 

@@ -75,7 +75,7 @@ SYMBOLS = [
     "tw_stage_flow_iter_grid", "tw_stage_span_scan",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
-    "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time", "tw_debug_scan_plan",
+    "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time", "tw_debug_scan_plan", "tw_debug_level_plan",
 ]
 
 
@@ -289,6 +289,8 @@ def _bind(path):
     L.tw_debug_blur_plan.restype = C.c_int
     L.tw_debug_scan_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.tw_debug_scan_plan.restype = C.c_int
+    L.tw_debug_level_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
+    L.tw_debug_level_plan.restype = C.c_int
     L.tw_debug_same_flags.argtypes = [vp, C.POINTER(C.c_uint), C.c_int]
     L.tw_debug_same_flags.restype = C.c_int
     return L
@@ -297,6 +299,9 @@ def _bind(path):
 FlowIterPlan = collections.namedtuple("FlowIterPlan", "strips segments nt nt_last")
 BlurPlan = collections.namedtuple("BlurPlan", "family block tile_cols rows xsh grid_x grid_y small forced")
 ScanPlan = collections.namedtuple("ScanPlan", "kernel gw gh G S segments rounds")
+# images: 0 a pyramid launch of its own, 1 written by the coarser level's launch, 2 its launch writes the next finer level's too
+LevelPlanRow = collections.namedtuple("LevelPlanRow", "pairs per launches tail images init flow_iter same flow_iter_last same_last same01")
+LevelPlanView = collections.namedtuple("LevelPlanView", "kind nlanes levels lat_quads fused_final grid_final parts")
 
 
 class LaunchCounts(dict):
@@ -782,6 +787,21 @@ class Engine:
         if n != 7:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_scan_plan(%d, %d, %d, %d) returned %d" % (w, h, span, npairs, n))
         return ScanPlan(("tw_span_scan", "tw_span_scan_seg")[v[0]], *v[1:7])
+
+    def level_plan(self, w, h, span, npairs, any_fout=False, any_init=False, prof_on=False):
+        """What a batch of npairs pairs of w x h pixels at `span` launches for each pyramid level, from the function the
+        enqueue itself executes (twflow_debug.h: tw_debug_level_plan): a LevelPlanView whose `parts` (a lane's share of the
+        batch each) hold one LevelPlanRow per level, level 0 first."""
+        cap = 8 + 2 * 61 * 11
+        v = (C.c_int * cap)()
+        traits = (1 if any_fout else 0) | (2 if any_init else 0) | (4 if prof_on else 0)
+        n = self._L.tw_debug_level_plan(self._h, w, h, int(span), npairs, traits, v, cap)
+        if n < 8 or v[7] != 11 or n != 8 + v[6] * (v[2] + 1) * 11:
+            raise TwError(TW_E_BAD_PARAMETER, "tw_debug_level_plan(%d, %d, %d, %d) returned %d" % (w, h, span, npairs, n))
+        rows = [LevelPlanRow(*(v[8 + 11 * i + j] if j < 5 else bool(v[8 + 11 * i + j]) for j in range(11)))
+                for i in range(v[6] * (v[2] + 1))]
+        parts = [rows[p * (v[2] + 1):(p + 1) * (v[2] + 1)] for p in range(v[6])]
+        return LevelPlanView(("batch", "two_stream", "twin")[v[0]], v[1], v[2], bool(v[3]), bool(v[4]), bool(v[5]), parts)
 
     def same_flags(self):
         """tw_pair_same's flags of the batch enqueued last, one per pair: 1 where the pair's second image is byte for byte
