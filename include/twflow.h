@@ -293,6 +293,46 @@ typedef struct tw_jpeg_luma {
 tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* expect, const tw_jpeg_luma* target, int span, double threshold,
                          const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket);
 
+/* Resident images (additive within ABI 4, detected by the symbols).  A tw_image is a gray image the engine keeps in device
+ * memory of its own, so that an image which takes part in many pairs — a baseline compared again and again, the inner frames
+ * of a sequence — is read, decoded and uploaded once.  It belongs to the engine that made it; tw_engine_destroy frees all.
+ * Blocks are 256-byte aligned ranges of chunks the engine allocates (at least 64 MB each) and reuses after release: no device
+ * allocation per image in steady state.  TW_E_NOMEM when the device has no room; budgets and eviction are the caller's.
+ * Handles are looked up in the engine's registry, never dereferenced first: a NULL, released, foreign or garbage pointer
+ * answers TW_E_BAD_PARAMETER, consumes no ticket and leaves the open batch as it was.
+ *
+ * tw_image_keep keeps the expected (TW_KEEP_EXPECT) or target (TW_KEEP_TARGET) image of a submitted pair as its batch sees
+ * it — dense gray at the pair's size, after tw_png_unfilter / tw_jpeg_idct and, for a reconciled target, after tw_resize_u8 —
+ * for tickets of every submit entry point, from the submit that returned the ticket until the tw_wait that collects it (an
+ * unknown or waited ticket, or `which` outside 0..1: TW_E_BAD_PARAMETER).  It is one device-to-device copy on the copy
+ * stream, behind whatever writes the pair's slot and in front of whatever reuses it; when the batch has not been launched
+ * and the slot is written by the batch's decode launches, the copy is queued with them.  The host never waits.  (A device
+ * target that tw_submit_dev_sized reconciles is written on the compute stream when its batch launches: keeping it launches
+ * the open batch.)  Keeping the expected image of a tw_submit_image_* pair returns the same handle once more and copies
+ * nothing; each handle returned is released once.  The kept image of a pair that later answers TW_E_BAD_IMAGE_FORMAT (a
+ * palette index without an entry) has undefined content: release it.
+ * tw_image_create_u8 makes a plain gray host image resident.  A page-locked block the library knows is DMA-ed in place and
+ * stays unchanged until tw_wait of the first pair submitted against the image returns; other memory is copied before the
+ * call returns.
+ * tw_image_release may be called at any time: the block returns to the store once every batch that reads it has been
+ * collected (all its tickets waited) or dropped; the handle is refused from the call on.
+ *
+ * tw_submit_image_png / tw_submit_image_jpeg are tw_submit_png / tw_submit_jpeg with the expected image resident: the pair's
+ * size is the image's; the target is described, checked, refused and reconciled exactly as there (TW_PNG_PLAIN_GRAY rows and
+ * a coefficient-less tw_jpeg_luma are plain gray targets).  Only the target is staged.  Such a pair joins the open batch of
+ * ordinary host pairs of its size, span and threshold; init and out work as for any pair; the result equals the plain call
+ * on the image's bytes bit for bit. */
+typedef struct tw_image tw_image; /* opaque */
+enum { TW_KEEP_EXPECT = 0, TW_KEEP_TARGET = 1 };
+tw_status tw_image_keep(tw_engine* e, tw_ticket ticket, int which, tw_image** out);
+tw_status tw_image_create_u8(tw_engine* e, const uint8_t* gray, int width, int height, ptrdiff_t stride, tw_image** out);
+tw_status tw_image_release(tw_engine* e, tw_image* img);
+tw_status tw_image_size(const tw_engine* e, const tw_image* img, int* width, int* height);
+tw_status tw_submit_image_png(tw_engine* e, const tw_image* expect, const tw_png_rows* target, int span, double threshold,
+                              const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket);
+tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* expect, const tw_jpeg_luma* target, int span, double threshold,
+                               const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 

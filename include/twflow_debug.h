@@ -150,6 +150,12 @@ const char* tw_debug_family_name(int family);
  * Returns the number of values written (at most n), -1 for a null engine. */
 int tw_debug_memory(tw_engine* e, unsigned long long* out, int n);
 
+/* The resident image store of one engine (tw_image_*; its reserved bytes are in tw_debug_memory's out[0]):
+ *   out[0] live images (blocks not yet back in the store)    out[1] bytes in use (blocks, each rounded up to 256)
+ *   out[2] bytes reserved (the chunks)                        out[3] chunk allocations so far
+ * Returns 4, -1 for a null engine or `out`. */
+int tw_debug_resident(tw_engine* e, unsigned long long out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,9 +18,11 @@
 #include <string.h>
 
 #include <array>
+#include <atomic>
 #include <chrono>
 #include <map>
 #include <mutex>
+#include <set>
 #include <string>
 #include <tuple>
 #include <utility>
@@ -316,6 +318,27 @@ struct Plan {
     unsigned long long last_use = 0;  // engine's plan clock at the last get_plan (LRU eviction)
 };
 
+}  // namespace
+
+// tw_image: a dense gray image in a block of the engine's resident store (ResidentStore below).  `handles` counts what
+// tw_image_create_u8 / tw_image_keep handed out and tw_image_release took back; `uses` the batches (and queued keeps) that
+// still read or write the block.  The block returns to the store when both are 0.
+// What the caller holds is `handle`, a number that no engine of the process hands out twice (this record's address would
+// come back from the allocator for the next image, and a released handle has to stay refused); it is never dereferenced.
+struct tw_image {
+    tw_engine* owner = nullptr;
+    tw_image* handle = nullptr;
+    uint8_t* d = nullptr;
+    int w = 0, h = 0;
+    int chunk = 0;
+    size_t off = 0, bytes = 0;
+    int handles = 0, uses = 0;
+};
+
+namespace {
+
+void image_unuse(tw_image* im);
+
 constexpr int TW_MAX_LEVELS = 60;  // the most pyramid levels below level 0 a plan may have (plan_geometry clamps pyrLevels)
 constexpr int HOST_RECS = 1024;  // flagged vectors per pair copied back eagerly
 constexpr int NCTX = 3;          // batches that may be in flight (host-side state only)
@@ -326,6 +349,11 @@ constexpr size_t jpeg_table_bytes(int cap) { return (sizeof(JpegJob) + 128) * 2 
 
 struct Job {
     const uint8_t *h_a = nullptr, *h_b = nullptr;  // host inputs already staged (null for device inputs)
+    // tw_submit_image_*: the pair's expected image is this resident image (h_a null, h_b the staged target); the batch holds
+    // a reference until it is collected or dropped.  keep[q]: a tw_image_keep of image q whose copy is queued when the
+    // batch's decode launches are (the slot is written then), with a reference of its own until it is
+    tw_image* res = nullptr;
+    tw_image* keep[2] = {nullptr, nullptr};
     const uint8_t *d_a = nullptr, *d_b = nullptr;
     long long stride = 0;
     bool waited = false;
@@ -427,11 +455,24 @@ struct Ctx {
     ResizeJob *d_rsz = nullptr, *h_rsz = nullptr;  // [3 * cap]
     PngJob *d_rpng = nullptr, *h_rpng = nullptr;   // [cap]
     bool any_resize = false, any_resize_png = false, any_resize_dev = false;
+    bool any_keep = false;  // a job of the open batch has a tw_image_keep copy to queue at launch
+
+    // the batch is collected or dropped: its resident images may return to the store
+    void release_images()
+    {
+        for (Job& jb : jobs) {
+            for (tw_image*& im : jb.keep)
+                if (im) image_unuse(im), im = nullptr;
+            if (jb.res) image_unuse(jb.res), jb.res = nullptr;
+        }
+        any_keep = false;
+    }
 
     // A new batch in this context: what describes the batch starts over; the device and pinned regions, their capacities
     // and the events survive.
     void begin_batch(int width, int height, int span_, double threshold_, int64_t first)
     {
+        release_images();
         jobs.clear();
         launched = false;
         pending = 0;
@@ -611,6 +652,19 @@ struct tw_engine {
     // the counts were last reset, and the pairs (grid z) of each family's latest launch — what lets a test prove WHICH kernel ran
     unsigned long long launches[TW_DF_COUNT] = {};
     unsigned long long last_grid_z[TW_DF_COUNT] = {};
+    // resident images (tw_image_*): the store's chunks (each one hipMalloc of at least RES_CHUNK bytes, kept until the engine
+    // goes; `free` = offset -> length of its unused ranges, neighbours merged), every image that still owns a block, and the
+    // handles a caller may pass in — a handle is looked up here, never dereferenced first
+    struct ResChunk {
+        uint8_t* base = nullptr;
+        size_t bytes = 0;
+        std::map<size_t, size_t> free;
+    };
+    std::vector<ResChunk> res_chunks;
+    std::set<tw_image*> res_images;         // own a block (handles > 0 or uses > 0)
+    std::map<const tw_image*, tw_image*> res_handles;  // tw_image::handle -> the record, while handles > 0
+    size_t res_in_use = 0, res_reserved = 0;
+    unsigned long long res_chunk_allocs = 0;
 };
 
 namespace {
@@ -636,7 +690,118 @@ namespace {
         }                                                                                 \
     } while (0)
 
+#define TW_TRY(call)                      \
+    do {                                  \
+        const tw_status _st = (call);     \
+        if (_st != TW_OK) return _st;     \
+    } while (0)
+
 size_t staged_image_bytes(int w, int h);
+
+// ---- the resident image store (tw_image_*) ---------------------------------------------------------------------------
+// Blocks are multiples of 256 bytes at multiples of 256 in a chunk (hipMalloc's own alignment is at least that), so a
+// resident image is aligned as a d_img slot is and img_aligned4 and every alignment-dependent kernel choice come out the same.
+constexpr size_t RES_CHUNK = (size_t)64 << 20;  // a chunk is at least this large
+
+void res_free(tw_engine* e, int chunk, size_t off, size_t bytes)
+{
+    std::map<size_t, size_t>& fr = e->res_chunks[chunk].free;
+    auto it = fr.emplace(off, bytes).first;
+    auto nx = std::next(it);
+    if (nx != fr.end() && it->first + it->second == nx->first) {
+        it->second += nx->second;
+        fr.erase(nx);
+    }
+    if (it != fr.begin()) {
+        auto pv = std::prev(it);
+        if (pv->first + pv->second == it->first) {
+            pv->second += it->second;
+            fr.erase(it);
+        }
+    }
+    e->res_in_use -= bytes;
+}
+
+// first fit over the chunks' free ranges, otherwise a new chunk (256 bytes of slack behind it, as every image region has)
+tw_status res_alloc(tw_engine* e, size_t bytes, int* chunk, size_t* off)
+{
+    for (int pass = 0; pass < 2; pass++) {
+        for (size_t k = 0; k < e->res_chunks.size(); k++) {
+            std::map<size_t, size_t>& fr = e->res_chunks[k].free;
+            for (auto it = fr.begin(); it != fr.end(); ++it) {
+                if (it->second < bytes) continue;
+                const size_t o = it->first, len = it->second;
+                fr.erase(it);
+                if (len > bytes) fr[o + bytes] = len - bytes;
+                *chunk = (int)k;
+                *off = o;
+                e->res_in_use += bytes;
+                return TW_OK;
+            }
+        }
+        if (pass) break;
+        tw_engine::ResChunk ch;
+        ch.bytes = std::max(RES_CHUNK, bytes);
+        TW_HIP(e, hipMalloc((void**)&ch.base, ch.bytes + 256));
+        ch.free[0] = ch.bytes;
+        e->res_reserved += ch.bytes + 256;
+        e->res_chunk_allocs++;
+        e->res_chunks.push_back(std::move(ch));
+    }
+    e->err = "resident store: no block";
+    return TW_E_NOMEM;
+}
+
+// a new image of w x h with one handle; its content is whatever the caller queues on the copy stream next
+tw_status image_new(tw_engine* e, int w, int h, tw_image** out)
+{
+    int chunk = 0;
+    size_t off = 0;
+    const size_t bytes = staged_image_bytes(w, h);
+    TW_TRY(res_alloc(e, bytes, &chunk, &off));
+    tw_image* im = new tw_image();
+    im->owner = e;
+    im->d = e->res_chunks[chunk].base + off;
+    im->w = w;
+    im->h = h;
+    im->chunk = chunk;
+    im->off = off;
+    im->bytes = bytes;
+    im->handles = 1;
+    static std::atomic<uintptr_t> next_handle{0x1000};
+    im->handle = (tw_image*)next_handle.fetch_add(16);
+    e->res_images.insert(im);
+    e->res_handles[im->handle] = im;
+    *out = im;
+    return TW_OK;
+}
+
+// the block returns to the store when no handle and no batch is left
+void image_settle(tw_image* im)
+{
+    if (im->handles > 0 || im->uses > 0) return;
+    tw_engine* e = im->owner;
+    res_free(e, im->chunk, im->off, im->bytes);
+    e->res_images.erase(im);
+    delete im;
+}
+
+void image_unuse(tw_image* im)
+{
+    im->uses--;
+    image_settle(im);
+}
+
+// tw_image_keep's copy: w x h bytes at src (rows `pitch` apart) to the image's dense rows, device to device on the copy stream
+tw_status queue_keep_copy(tw_engine* e, tw_image* im, const uint8_t* src, long long pitch)
+{
+    const size_t w = (size_t)im->w, h = (size_t)im->h;
+    if ((size_t)pitch == w) TW_HIP(e, hipMemcpyAsync(im->d, src, w * h, hipMemcpyDeviceToDevice, e->copy_stream));
+    else TW_HIP(e, hipMemcpy2DAsync(im->d, w, src, (size_t)pitch, w, h, hipMemcpyDeviceToDevice, e->copy_stream));
+    e->copy_ops++;
+    return TW_OK;
+}
+
 // tw_jpeg_idct's grid for `nimg` images of up to w x h pixels: a workgroup takes JPEG_WG_BLOCKS adjacent blocks of a block row
 dim3 jpeg_idct_grid(int w, int h, int nimg)
 {
@@ -736,12 +901,6 @@ tw_status d2h_sync(tw_engine* e, void* h, const void* d, size_t n)
     }
     return TW_OK;
 }
-#define TW_TRY(call)                      \
-    do {                                  \
-        const tw_status _st = (call);     \
-        if (_st != TW_OK) return _st;     \
-    } while (0)
-
 // scoped device allocations (per-stage test entry points, slow paths)
 struct Tmp {
     std::vector<void*> v;
@@ -2338,6 +2497,23 @@ struct BatchEnqueue {
         return TW_OK;
     }
 
+    // tw_image_keep of images this batch's decode launches write: their copies, on the copy stream behind those launches
+    // and in front of ev_h2d (a pair of this very batch may read the kept image)
+    tw_status enqueue_kept_copies()
+    {
+        if (!c.any_keep) return TW_OK;
+        for (int j = 0; j < n; j++)
+            for (int q = 0; q < 2; q++) {
+                tw_image*& im = c.jobs[j].keep[q];
+                if (!im) continue;
+                TW_TRY(queue_keep_copy(e, im, c.d_img + npx * (size_t)(2 * j + q), c.w));
+                image_unuse(im);
+                im = nullptr;
+            }
+        c.any_keep = false;
+        return TW_OK;
+    }
+
     tw_status mark_uploads_and_plan_ramp()
     {
         c.copy_ops_at_flush = e->copy_ops;
@@ -2370,8 +2546,8 @@ struct BatchEnqueue {
         bool al4 = (stride % 4) == 0;
         for (int j = 0; j < n; j++) {
             const Job& jb = c.jobs[j];
-            if (jb.h_a) {
-                c.h_ptrs[2 * j] = c.d_img + npx * (2 * j);
+            if (jb.h_b) {
+                c.h_ptrs[2 * j] = jb.res ? jb.res->d : c.d_img + npx * (2 * j);
                 c.h_ptrs[2 * j + 1] = c.d_img + npx * (2 * j + 1);
             } else {
                 c.h_ptrs[2 * j] = jb.d_a;
@@ -2958,6 +3134,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     RoctxRange batch_range("tw_batch %dx%d pairs=%d", c.w, c.h, b.n);
     TW_TRY(b.enqueue_jpeg_idct());
     TW_TRY(b.enqueue_png_unfilter());
+    TW_TRY(b.enqueue_kept_copies());
     TW_TRY(b.mark_uploads_and_plan_ramp());
     TW_TRY(b.upload_tables());
     TW_TRY(b.enqueue_device_target_resizes());
@@ -3167,6 +3344,7 @@ tw_status check_flow_out(tw_engine* e, const tw_flow_out* o, int w, int h, bool*
 struct Submission {
     const uint8_t *h_a = nullptr, *h_b = nullptr;
     const void *d_a = nullptr, *d_b = nullptr;
+    tw_image* res = nullptr;  // tw_submit_image_*: the expected image is this resident image (h_a and d_a null, h_b the target)
     int width = 0, height = 0;
     ptrdiff_t stride = 0;
     int span = 0;
@@ -3190,6 +3368,7 @@ struct Submission {
 // wait, so that the engine stays usable; its tickets answer "unknown ticket".
 void drop_batch(Ctx& c)
 {
+    c.release_images();
     c.pending = 0;
     c.jobs.clear();
 }
@@ -3202,6 +3381,7 @@ struct Submit {
     const Submission& s;
     const bool png;
     const bool jpeg;             // tw_submit_jpeg with at least one coefficient image
+    const bool host;             // a host pair: both images staged, or (tw_submit_image_*) a resident image and a staged target
     const long long eff_stride;  // host images are staged densely; device images are read in place with their stride
     const int tw, th;            // the target's own size (the pair's unless a _sized call says otherwise)
     const ptrdiff_t tstride;
@@ -3212,10 +3392,11 @@ struct Submit {
     Job jb;
 
     Submit(tw_engine* e_, const Submission& s_)
-        : e(e_), s(s_), png(s_.ch_a > 0 || s_.ch_b > 0), jpeg(s_.jl_a || s_.jl_b), eff_stride(s_.h_a ? (long long)s_.width : (long long)s_.stride),
+        : e(e_), s(s_), png(s_.ch_a > 0 || s_.ch_b > 0), jpeg(s_.jl_a || s_.jl_b), host(s_.h_a || s_.res),
+          eff_stride(host ? (long long)s_.width : (long long)s_.stride),
           tw(s_.t_width ? s_.t_width : s_.width), th(s_.t_height ? s_.t_height : s_.height),
           tstride(s_.t_stride ? s_.t_stride : s_.stride),
-          resize(tw != s_.width || th != s_.height || (!s_.h_a && tstride != s_.stride))
+          resize(tw != s_.width || th != s_.height || (!host && tstride != s_.stride))
     {
     }
 
@@ -3268,8 +3449,8 @@ struct Submit {
             return TW_E_DONT_MATCH_SIZE;
         }
         if (tw != s.width || th != s.height) TW_TRY(check_dims(e, tw, th));
-        const bool png_ok = s.h_a && s.h_b && s.ch_a >= 0 && s.ch_a <= 4 && s.ch_b >= 0 && s.ch_b <= 4;
-        if (s.span < 0 || s.stride < s.width || tstride < tw || (!s.h_a && !s.d_a) || (!s.h_b && !s.d_b) ||
+        const bool png_ok = host && s.h_b && s.ch_a >= 0 && s.ch_a <= 4 && s.ch_b >= 0 && s.ch_b <= 4;
+        if (s.span < 0 || s.stride < s.width || tstride < tw || (!host && !s.d_a) || (!s.h_b && !s.d_b) || (s.res && !s.h_b) ||
             ((png || jpeg) && (!png_ok || s.stride != s.width || tstride != tw))) {
             e->err = "bad argument";
             return TW_E_BAD_PARAMETER;
@@ -3373,13 +3554,14 @@ struct Submit {
         jb.tstride = s.h_a ? (long long)tw : (long long)tstride;
         if (resize) TW_TRY(reserve_resize_tables());
         if (jpeg) TW_TRY(reserve_jpeg_tables());
-        if (!s.h_a) return resize ? stage_device_target() : TW_OK;
+        if (!host) return resize ? stage_device_target() : TW_OK;
         const size_t npx = staged_image_bytes(s.width, s.height);
         // (grows only on the first job of a batch: all jobs of a batch have one size)
         TW_TRY(grow_device(e, c->d_img, c->d_img_cap, npx * 2 * e->cap, npx * 2 * e->cap + 256, e->copy_stream));
         TW_TRY(png || jpeg ? stage_png_rows(npx) : stage_gray_pair(npx));
         jb.h_a = s.h_a;
         jb.h_b = s.h_b;
+        jb.res = s.res;  // (book_job takes the batch's reference)
         c->any_host = true;
         e->copy_ops++;
         return TW_OK;
@@ -3420,7 +3602,7 @@ struct Submit {
         const int chs[2] = {s.ch_a, s.ch_b}, bits[2] = {s.bits_a, s.bits_b}, entries[2] = {s.entries_a, s.entries_b};
         const uint8_t* luts[2] = {s.lut_a, s.lut_b};
         const tw_jpeg_luma* jl[2] = {s.jl_a, s.jl_b};
-        for (int q = 0; q < 2; q++) {
+        for (int q = s.res ? 1 : 0; q < 2; q++) {  // (a resident expected image is where it is)
             // an image is handed over as ONE row: it goes through the bounce buffer whole, whatever its size
             const int wq = q ? tw : s.width, hq = q ? th : s.height;
             const size_t nb = jl[q] ? jpeg_coef_bytes(jl[q]) : chs[q] ? png_rows_bytes(wq, hq, chs[q], bits[q]) : (size_t)wq * hq;
@@ -3465,6 +3647,15 @@ struct Submit {
         const size_t w = (size_t)s.width, h = (size_t)s.height, span_bytes = (size_t)s.stride * (h - 1) + w;
         if (resize) return stage_gray_pair_resized(dst_a, dst_b);
         const size_t span_b = (size_t)tstride * (h - 1) + w;
+        if (s.res) {
+            // only the target: page-locked in place, pageable through its slot of the pinned ring (the expected image is resident)
+            if (pin_registry().covers(s.h_b, span_b)) return upload_in_place(dst_b, s.h_b, (size_t)tstride, w, h);
+            TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, npx * 2 * e->cap));
+            uint8_t* db = c->h_img + at + npx;
+            for (size_t y = 0; y < h; y++) memcpy(db + y * w, s.h_b + y * (size_t)tstride, w);
+            TW_HIP(e, hipMemcpyAsync(dst_b, db, w * h, hipMemcpyHostToDevice, e->copy_stream));
+            return TW_OK;
+        }
         if (pin_registry().covers(s.h_a, span_bytes) && pin_registry().covers(s.h_b, span_b)) {
             TW_TRY(upload_in_place(dst_a, s.h_a, (size_t)s.stride, w, h));
             return upload_in_place(dst_b, s.h_b, (size_t)tstride, w, h);
@@ -3492,7 +3683,7 @@ struct Submit {
         if (!c->d_rsz) TW_HIP(e, hipMalloc((void**)&c->d_rsz, sizeof(ResizeJob) * 3 * n + 256));
         if (!c->h_rpng) TW_HIP(e, hipHostMalloc((void**)&c->h_rpng, sizeof(PngJob) * n, hipHostMallocDefault));
         if (!c->d_rpng) TW_HIP(e, hipMalloc((void**)&c->d_rpng, sizeof(PngJob) * n + 256));
-        if (!s.h_a) return TW_OK;  // (a device target is read in place)
+        if (!host) return TW_OK;  // (a device target is read in place)
         const size_t slot = staged_image_bytes(s.width + 5, s.height + 5), nbytes = slot * n;
         const tw_status r = grow_device(e, c->d_tsrc_raw, c->d_tsrc_cap, nbytes, nbytes + 512, e->copy_stream);
         c->d_tsrc = c->d_tsrc_raw ? c->d_tsrc_raw + 256 : nullptr;
@@ -3515,7 +3706,7 @@ struct Submit {
     {
         const size_t j = c->jobs.size();
         uint8_t* tsrc = c->d_tsrc + c->tsrc_slot * j;
-        TW_TRY(upload_rows(dst_a, s.h_a, (size_t)s.stride, (size_t)s.width, (size_t)s.height));
+        if (!s.res) TW_TRY(upload_rows(dst_a, s.h_a, (size_t)s.stride, (size_t)s.width, (size_t)s.height));
         TW_TRY(upload_rows(tsrc, s.h_b, (size_t)tstride, (size_t)tw, (size_t)th));
         c->h_rsz[j] = resize_job(tsrc, tw, th, tw, dst_b, s.width, s.height, s.width);
         TW_HIP(e, hipMemcpyAsync(c->d_rsz + j, c->h_rsz + j, sizeof(ResizeJob), hipMemcpyHostToDevice, e->copy_stream));
@@ -3546,7 +3737,7 @@ struct Submit {
     tw_status mark_ramp()
     {
         const int sz = (int)c->jobs.size() + 1;
-        if (s.h_a && !png && !jpeg && e->ramp && e->cap >= 64 && c->nseg < 2 && (sz == e->cap / 4 || sz == e->cap / 2)) {
+        if (host && !png && !jpeg && e->ramp && e->cap >= 64 && c->nseg < 2 && (sz == e->cap / 4 || sz == e->cap / 2)) {
             TW_HIP(e, hipEventRecord(c->ev_seg[c->nseg], e->copy_stream));
             c->seg_at[c->nseg++] = sz;
         }
@@ -3564,6 +3755,7 @@ struct Submit {
         c->any_fout_host = c->any_fout_host || fo_host;
         c->any_init = c->any_init || s.fi;
         c->any_init_host = c->any_init_host || fi_kind != 0;
+        if (jb.res) jb.res->uses++;
         c->jobs.push_back(jb);
         c->pending++;
         if (s.ticket) *s.ticket = e->next_ticket;
@@ -3872,6 +4064,8 @@ void tw_engine_destroy(tw_engine* e)
     if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
     if (e->d_fdst) (void)hipFree(e->d_fdst);
     if (e->d_fsrc) (void)hipFree(e->d_fsrc);
+    for (tw_image* im : e->res_images) delete im;
+    for (tw_engine::ResChunk& ch : e->res_chunks) (void)hipFree(ch.base);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
     for (auto& kv : e->plans) free_plan(kv.second);
@@ -4067,6 +4261,192 @@ tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* expect, const tw_jpeg
     return submit(e, s);
 }
 
+// ---- resident images ---------------------------------------------------------------------------------------------------
+
+// the engine's own record of a handle the caller passed (null: not one of this engine's live handles)
+static tw_image* find_image(const tw_engine* e, const tw_image* img)
+{
+    auto it = e->res_handles.find(img);
+    if (it != e->res_handles.end()) return it->second;
+    const_cast<tw_engine*>(e)->err = "not a resident image of this engine (null, released or foreign handle)";
+    return nullptr;
+}
+
+tw_status tw_image_keep(tw_engine* e, tw_ticket ticket, int which, tw_image** out)
+{
+    if (!e || !out) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    *out = nullptr;
+    if (which != TW_KEEP_EXPECT && which != TW_KEEP_TARGET) {
+        e->err = "tw_image_keep: which is TW_KEEP_EXPECT or TW_KEEP_TARGET";
+        return TW_E_BAD_PARAMETER;
+    }
+    int j = 0;
+    Ctx* c = find_ctx(e, ticket, &j);
+    if (!c) {
+        e->err = "unknown ticket";
+        return TW_E_BAD_PARAMETER;
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    tw_image* known = which == TW_KEEP_EXPECT ? c->jobs[j].res : nullptr;  // (itself resident: the same block once more)
+    if (!known) known = c->jobs[j].keep[which];                            // (kept before, its copy not yet queued)
+    if (known) {
+        known->handles++;
+        e->res_handles[known->handle] = known;
+        *out = known->handle;
+        return TW_OK;
+    }
+    // where the image is, and when it is there: a host pair's slot of d_img is written on the copy stream — at submit time
+    // (a gray image, a gray target resized there) or by the batch's decode launches; a device pair's images are the caller's,
+    // except a reconciled target, which tw_resize_u8 writes on the compute stream in front of the batch's start event
+    const bool host = c->jobs[j].h_b != nullptr;
+    const bool dev_resized = !host && which == TW_KEEP_TARGET && c->jobs[j].rkind == RSZ_FLUSH_DEV;
+    if (dev_resized && !c->launched) {
+        const tw_status r = flush_ctx(e, *c);
+        if (r) {
+            drop_batch(*c);
+            return r;
+        }
+    }
+    Job& jb = c->jobs[j];
+    const bool at_launch = host && !c->launched &&
+                           (jb.png_ch[which] > 0 || jb.jpg_bw[which] > 0 || (which == TW_KEEP_TARGET && jb.rkind == RSZ_FLUSH_COPY));
+    tw_image* im = nullptr;
+    TW_TRY(image_new(e, c->w, c->h, &im));
+    if (at_launch) {
+        jb.keep[which] = im;
+        im->uses++;
+        c->any_keep = true;
+        *out = im->handle;
+        return TW_OK;
+    }
+    tw_status r = TW_OK;
+    if (dev_resized && hipStreamWaitEvent(e->copy_stream, c->ev_start, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        e->err = "tw_image_keep: hipStreamWaitEvent failed";
+        r = TW_E_DEVICE;
+    }
+    const uint8_t* src = host ? c->d_img + staged_image_bytes(c->w, c->h) * (size_t)(2 * j + which) : which ? jb.d_b : jb.d_a;
+    if (!r) r = queue_keep_copy(e, im, src, host ? (long long)c->w : jb.stride);
+    if (r) {
+        im->handles = 0;
+        e->res_handles.erase(im->handle);
+        image_settle(im);
+        return r;
+    }
+    *out = im->handle;
+    return TW_OK;
+}
+
+tw_status tw_image_create_u8(tw_engine* e, const uint8_t* gray, int width, int height, ptrdiff_t stride, tw_image** out)
+{
+    if (!e || !out) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    *out = nullptr;
+    if (!gray) return TW_E_BAD_PARAMETER;
+    TW_TRY(check_dims(e, width, height));
+    if (stride < width) {
+        e->err = "bad argument";
+        return TW_E_BAD_PARAMETER;
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    tw_image* im = nullptr;
+    TW_TRY(image_new(e, width, height, &im));
+    const Submission none;
+    Submit up(e, none);  // (for its upload step only: page-locked in place, pageable through the bounce buffer)
+    const tw_status r = up.upload_rows(im->d, gray, (size_t)stride, (size_t)width, (size_t)height);
+    if (r) {
+        im->handles = 0;
+        e->res_handles.erase(im->handle);
+        image_settle(im);
+        return r;
+    }
+    e->copy_ops++;
+    *out = im->handle;
+    return TW_OK;
+}
+
+tw_status tw_image_release(tw_engine* e, tw_image* img)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    tw_image* im = find_image(e, img);
+    if (!im) return TW_E_BAD_PARAMETER;
+    if (--im->handles == 0) e->res_handles.erase(im->handle);
+    image_settle(im);
+    return TW_OK;
+}
+
+tw_status tw_image_size(const tw_engine* e, const tw_image* img, int* width, int* height)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    const tw_image* im = find_image(e, img);
+    if (!im) return TW_E_BAD_PARAMETER;
+    if (width) *width = im->w;
+    if (height) *height = im->h;
+    return TW_OK;
+}
+
+// (tw_submit_png's Submission with the expected image a plain gray one that is already where the batch reads it)
+tw_status tw_submit_image_png(tw_engine* e, const tw_image* expect, const tw_png_rows* target, int span, double threshold,
+                              const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    tw_image* im = find_image(e, expect);
+    if (!im) return TW_E_BAD_PARAMETER;
+    PngKind kb;
+    uint8_t lut_b[256];
+    TW_TRY(describe_png(e, target, "target", &kb, lut_b));
+    if (target->width < 1 || target->height < 1) return TW_E_BAD_PARAMETER;
+    Submission s;
+    s.res = im;
+    s.h_b = target->rows;
+    s.width = im->w;
+    s.height = im->h;
+    s.stride = im->w;
+    s.span = span;
+    s.threshold = threshold;
+    s.ch_b = kb.ch;
+    s.bits_b = kb.bits;
+    s.lut_b = kb.table ? lut_b : nullptr;
+    s.entries_b = kb.entries;
+    s.t_width = target->width;
+    s.t_height = target->height;
+    s.t_stride = target->width;
+    s.fo = out;
+    s.fi = init;
+    s.ticket = ticket;
+    return submit(e, s);
+}
+
+// (tw_submit_jpeg's Submission likewise)
+tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* expect, const tw_jpeg_luma* target, int span, double threshold,
+                               const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    tw_image* im = find_image(e, expect);
+    if (!im) return TW_E_BAD_PARAMETER;
+    TW_TRY(check_jpeg_luma(target));
+    Submission s;
+    s.res = im;
+    s.h_b = target->coef ? (const uint8_t*)target->coef : target->gray;
+    s.jl_b = target->coef ? target : nullptr;
+    s.width = im->w;
+    s.height = im->h;
+    s.stride = im->w;
+    s.span = span;
+    s.threshold = threshold;
+    s.t_width = target->width;
+    s.t_height = target->height;
+    s.t_stride = target->width;
+    s.fo = out;
+    s.fi = init;
+    s.ticket = ticket;
+    return submit(e, s);
+}
+
 tw_status tw_submit_dev_sized(tw_engine* e, const void* d_expect, int width, int height, ptrdiff_t stride,
                               const void* d_target, int target_width, int target_height, ptrdiff_t target_stride,
                               int span, double threshold, const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
@@ -4128,6 +4508,7 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
     }
     c->jobs[j].waited = true;
     c->pending--;
+    if (c->pending == 0) c->release_images();  // (the batch is collected: ev_done has passed)
     if (herr != hipSuccess) {
         e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
         return TW_E_DEVICE;
@@ -4669,6 +5050,7 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
         if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cap;
     }
     for (const auto& kv : e->plans) v[0] += kv.second->owned_bytes;
+    v[0] += e->res_reserved;  // (the resident store's chunks: tw_debug_resident)
     v[1] += e->h_bounce_cap;
     v[2] = e->plans.size();
     v[3] = e->h_bounce_cap;
@@ -4684,6 +5066,16 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     int i = 0;
     for (; i < n && i < 8; i++) out[i] = v[i];
     return i;
+}
+
+extern "C" int tw_debug_resident(tw_engine* e, unsigned long long out[4])
+{
+    if (!e || !out) return -1;
+    out[0] = e->res_images.size();
+    out[1] = e->res_in_use;
+    out[2] = e->res_reserved;
+    out[3] = e->res_chunk_allocs;
+    return 4;
 }
 
 // occupancy report of the main kernels (workgroups per CU the runtime admits) — tools/kbench.py

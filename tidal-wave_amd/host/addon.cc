@@ -188,6 +188,8 @@ napi_value construct(napi_env env, napi_callback_info info)
     p.optParam.polyN = get_i32(env, opts, "polyN", 7);
     p.optParam.polySigma = get_f64(env, opts, "polySigma", 1.5);
     p.optParam.flags = get_i32(env, opts, "flags", 256);  // cv::OPTFLOW_FARNEBACK_GAUSSIAN
+    // not in the reference: megabytes of resident expected images per consumer (0: TW_RESIDENT_MB, else off)
+    p.residentMB = get_i32(env, opts, "residentMB", 0);
 
     Broker* b = new Broker();
     b->env = env;

@@ -36,10 +36,21 @@ void jpeg_luma_to_gray(const JpegLuma& luma, std::vector<uint8_t>& img) __attrib
 }
 
 typedef std::chrono::steady_clock stub_clock;
+// a resident image: the stub's host copy of the gray bytes it ever looks at — pixel 0 — and the size
+struct tw_image {
+    int w, h;
+    uint8_t first;
+};
 struct tw_engine {
     int device, cap;
     std::mutex m;
     std::map<tw_ticket, int> open;  // ticket -> width (echoed as the vector's x)
+    struct PairInfo {
+        int w, h;
+        uint8_t first[2];
+    };
+    std::map<tw_ticket, PairInfo> info;  // ticket -> what tw_image_keep keeps of the pair
+    std::map<const tw_image*, tw_image> images;  // live resident images by handle (a number never handed out twice: looked up, never dereferenced)
     std::map<tw_ticket, std::string> bad;  // tw_submit_png: the image ("expected" / "target") the host's finisher refused
     std::string err;
     tw_ticket next = 1;
@@ -71,6 +82,9 @@ static std::atomic<int> g_engines{0};
 static std::atomic<long> g_png_calls{0}, g_png_row_images{0};
 // likewise pairs that came through tw_submit_jpeg, and through it images that were still coefficients
 static std::atomic<long> g_jpeg_calls{0}, g_jpeg_coef_images{0};
+// resident images: tw_image_keep calls that kept one, pairs that came through tw_submit_image_*, tw_image_release calls
+static std::atomic<long> g_res_kept{0}, g_res_image_pairs{0}, g_res_released{0};
+static std::atomic<uintptr_t> g_next_image{0x1000};
 
 extern "C" {
 void tw_default_params(tw_params* p)
@@ -133,6 +147,12 @@ void tw_stub_jpeg_calls(long* pairs, long* coef_images)
     *pairs = g_jpeg_calls;
     *coef_images = g_jpeg_coef_images;
 }
+void tw_stub_resident_calls(long* kept, long* image_pairs, long* released)
+{
+    *kept = g_res_kept;
+    *image_pairs = g_res_image_pairs;
+    *released = g_res_released;
+}
 int tw_grid_capacity(int w, int h, int span) { return span > 0 ? ((h + span - 1) / span) * ((w + span - 1) / span) : 0; }
 tw_status tw_engine_create(int device, const tw_params*, int slots, tw_engine** out)
 {
@@ -155,6 +175,7 @@ tw_status tw_submit_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w, 
     std::lock_guard<std::mutex> lk(e->m);
     *t = e->next++;
     e->open[*t] = w + (a[0] != b[0] ? 1000000 : 0);
+    e->info[*t] = tw_engine::PairInfo{w, h, {a[0], b[0]}};
     if (e->batch_ms > 0) {
         e->batch_of[*t] = e->cur_batch;
         if (++e->cur_count >= e->cap) e->launch_locked();  // a full batch starts by itself, like the engine's
@@ -267,6 +288,87 @@ tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* a, const tw_jpeg_luma
     }
     return tw_submit_u8(e, &first[0], &first[1], a->width, a->height, a->width, span, thr, t);
 }
+// Resident images: the first gray pixel of the pair's image as tw_submit_u8 saw it (a palette image the finisher refused
+// has pixel 0 = 0: undefined content, as the engine's header says)
+tw_status tw_image_keep(tw_engine* e, tw_ticket t, int which, tw_image** out)
+{
+    if (!e || !out) return TW_E_BAD_PARAMETER;
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(e->m);
+    auto it = e->info.find(t);
+    if (it == e->info.end() || which < 0 || which > 1) return TW_E_BAD_PARAMETER;
+    *out = (tw_image*)g_next_image.fetch_add(16);
+    e->images[*out] = tw_image{it->second.w, it->second.h, it->second.first[which]};
+    g_res_kept++;
+    return TW_OK;
+}
+tw_status tw_image_create_u8(tw_engine* e, const uint8_t* gray, int w, int h, ptrdiff_t stride, tw_image** out)
+{
+    if (!e || !out || !gray || w < 1 || h < 1 || stride < w) return TW_E_BAD_PARAMETER;
+    std::lock_guard<std::mutex> lk(e->m);
+    *out = (tw_image*)g_next_image.fetch_add(16);
+    e->images[*out] = tw_image{w, h, gray[0]};
+    return TW_OK;
+}
+tw_status tw_image_release(tw_engine* e, tw_image* img)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    std::lock_guard<std::mutex> lk(e->m);
+    if (!e->images.erase(img)) return TW_E_BAD_PARAMETER;
+    g_res_released++;
+    return TW_OK;
+}
+tw_status tw_image_size(const tw_engine* e, const tw_image* img, int* w, int* h)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    std::lock_guard<std::mutex> lk(const_cast<tw_engine*>(e)->m);
+    auto it = e->images.find(img);
+    if (it == e->images.end()) return TW_E_BAD_PARAMETER;
+    if (w) *w = it->second.w;
+    if (h) *h = it->second.h;
+    return TW_OK;
+}
+// the resident image as a plain gray expected image of one known pixel, then what tw_submit_png / tw_submit_jpeg do
+static bool stub_image_pixel(tw_engine* e, const tw_image* img, tw_image* copy)
+{
+    if (!e) return false;
+    std::lock_guard<std::mutex> lk(e->m);
+    auto it = e->images.find(img);
+    if (it == e->images.end()) return false;
+    *copy = it->second;
+    return true;
+}
+tw_status tw_submit_image_png(tw_engine* e, const tw_image* img, const tw_png_rows* b, int span, double thr, const tw_flow_in* fi,
+                              const tw_flow_out* fo, tw_ticket* t)
+{
+    tw_image im;
+    if (!stub_image_pixel(e, img, &im)) return TW_E_BAD_PARAMETER;
+    tw_png_rows a;
+    a.rows = &im.first;
+    a.width = im.w;
+    a.height = im.h;
+    a.color_type = TW_PNG_PLAIN_GRAY;
+    a.bit_depth = 8;
+    a.palette = nullptr;
+    a.palette_entries = 0;
+    const tw_status r = tw_submit_png(e, &a, b, span, thr, fi, fo, t);
+    if (r == TW_OK) g_res_image_pairs++;
+    return r;
+}
+tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* img, const tw_jpeg_luma* b, int span, double thr, const tw_flow_in* fi,
+                               const tw_flow_out* fo, tw_ticket* t)
+{
+    tw_image im;
+    if (!stub_image_pixel(e, img, &im)) return TW_E_BAD_PARAMETER;
+    tw_jpeg_luma a;
+    memset(&a, 0, sizeof(a));
+    a.gray = &im.first;
+    a.width = im.w;
+    a.height = im.h;
+    const tw_status r = tw_submit_jpeg(e, &a, b, span, thr, fi, fo, t);
+    if (r == TW_OK) g_res_image_pairs++;
+    return r;
+}
 tw_status tw_submit_dev_sized(tw_engine* e, const void* a, int w, int h, ptrdiff_t stride, const void* b, int tw, int th,
                               ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
 {
@@ -290,6 +392,7 @@ tw_status tw_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, int* n, fl
         if (it == e->open.end()) return TW_E_BAD_PARAMETER;
         w = it->second;
         e->open.erase(it);
+        e->info.erase(t);
     }
     if (e->batch_ms > 0) {
         stub_clock::time_point until;

@@ -9,10 +9,13 @@
 #include <string.h>
 
 #include <sched.h>
+#include <sys/stat.h>
 
 #include <algorithm>
 #include <chrono>
 #include <fstream>
+#include <list>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -20,6 +23,11 @@
 
 // additive within ABI 4: an engine library from before tw_submit_jpeg still loads, and JPEGs then stay on the host
 #pragma weak tw_submit_jpeg
+// likewise the resident images: without them every expected image is read, decoded and uploaded each time, as before
+#pragma weak tw_image_keep
+#pragma weak tw_image_release
+#pragma weak tw_submit_image_png
+#pragma weak tw_submit_image_jpeg
 
 namespace twhost {
 
@@ -752,7 +760,45 @@ struct Staged {
     tw_ticket ticket = 0;
     bool submitted = false;
     bool done = false;  // response pushed
+    // resident expected images (Parameter::residentMB): the identity of the expected file ("" : not looked at); hit: the
+    // cache entry whose image stands in for the file (pinned until the pair is submitted); keep: the image this pair's
+    // expected file becomes — kept by the pair that decoded it (kept), used by the pairs behind it that name the same file
+    // (uses_keep) while that pair has not answered; leader: that pair when it sits in this very batch (index before the sort)
+    struct ResEntry;
+    struct Keep {
+        tw_image* img = nullptr;
+        int w = 0, h = 0;
+        bool expect_bad = false;  // the pair that kept it answered "Can't open <expected>": its content is undefined
+    };
+    std::string rkey;
+    ResEntry* hit = nullptr;
+    std::shared_ptr<Keep> keep;
+    int leader = -1;
+    bool follower = false, uses_keep = false;
+    tw_image* kept = nullptr;
+    bool no_expected_file() const { return hit || follower; }
 };
+// One resident expected image of a consumer's cache: an LRU by bytes under the budget
+struct Staged::ResEntry {
+    std::string key;
+    std::vector<std::string> paths;  // every path it was asked for under (hard links share an entry)
+    tw_image* img = nullptr;
+    int w = 0, h = 0;
+    size_t bytes = 0;
+    int pins = 0;  // pairs that looked it up and are not submitted yet
+    std::list<ResEntry*>::iterator lru;
+};
+
+// dev:ino:size:mtime(ns) of a file — what tells a rewritten baseline from the cached one ("" : no such file)
+std::string file_identity(const std::string& path)
+{
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0) return std::string();
+    char buf[160];
+    snprintf(buf, sizeof(buf), "%llx:%llx:%lld:%lld.%09ld", (unsigned long long)st.st_dev, (unsigned long long)st.st_ino,
+             (long long)st.st_size, (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec);
+    return buf;
+}
 
 // the rest of a JPEG's decode on the host (what the device does for tw_submit_jpeg): `bytes` from coefficients to gray
 void finish_jpeg_on_host(std::vector<uint8_t>& bytes, Staged::JpegHead& head, int w, int h)
@@ -776,6 +822,7 @@ void decode_one(Staged& s, int which, int* tw, int* th, std::string* err, bool d
                 const std::vector<uint8_t>* file)
 {
     if (s.req.raw.expect) return;
+    if (which == 0 && s.no_expected_file()) return;  // (a resident image stands in for the file)
     const std::string& path = which == 0 ? s.req.expect_image : s.req.target_image;
     if (path.empty()) { *err = which == 0 ? "ExpectImagePath is empty." : "TargetImagePath is empty."; return; }
     std::vector<uint8_t>& img = which == 0 ? s.a : s.b;
@@ -942,6 +989,68 @@ void Consumer::run()
     // grid-capacity entries per job — 0.5 MB at 1080p / span 10 — cost 0.2 ms of every response, round 4)
     std::unique_ptr<tw_vector[]> hits;
     size_t hits_cap = 0;
+    // Resident expected images (Parameter::residentMB / TW_RESIDENT_MB; 0, the default: off, and nothing below is ever
+    // reached): the expected image of a pair stays on the device under its file's identity, and a later pair that names
+    // the same file skips read, decode, arena copy and upload of it (tw_submit_image_*).  An LRU by bytes; eviction only
+    // releases the handle — the engine returns the block once no batch reads it — so it never waits.
+    typedef Staged::ResEntry ResEntry;
+    const size_t res_budget = shared_ && shared_->residentBytes > 0 ? (size_t)shared_->residentBytes : 0;
+    const bool resident_on = eng && res_budget > 0 && tw_image_keep && tw_image_release && tw_submit_image_png && tw_submit_image_jpeg;
+    std::map<std::string, std::unique_ptr<ResEntry>> res_cache;  // file identity -> entry
+    std::map<std::string, std::string> res_path_key;             // path -> the identity it was last seen with
+    std::list<ResEntry*> res_lru;                                // front: used last
+    std::list<std::unique_ptr<ResEntry>> res_zombies;            // evicted while a pair that looked them up was not submitted yet
+    std::map<std::string, std::shared_ptr<Staged::Keep>> res_pending;  // identity -> the image of a pair that has not answered
+    size_t res_bytes = 0;
+    auto res_evict = [&](ResEntry* en) {
+        res_bytes -= en->bytes;
+        res_lru.erase(en->lru);
+        for (const std::string& p : en->paths) {
+            auto pk = res_path_key.find(p);
+            if (pk != res_path_key.end() && pk->second == en->key) res_path_key.erase(pk);
+        }
+        auto it = res_cache.find(en->key);
+        std::unique_ptr<ResEntry> own = std::move(it->second);
+        res_cache.erase(it);
+        if (own->pins > 0) res_zombies.push_back(std::move(own));
+        else (void)tw_image_release(eng, own->img);
+    };
+    auto res_sweep = [&] {
+        for (auto it = res_zombies.begin(); it != res_zombies.end();)
+            if ((*it)->pins == 0) {
+                (void)tw_image_release(eng, (*it)->img);
+                it = res_zombies.erase(it);
+            } else ++it;
+    };
+    auto res_lookup = [&](const std::string& key, const std::string& path) -> ResEntry* {
+        auto it = res_cache.find(key);
+        if (it == res_cache.end()) return nullptr;
+        ResEntry* en = it->second.get();
+        res_lru.splice(res_lru.begin(), res_lru, en->lru);
+        if (std::find(en->paths.begin(), en->paths.end(), path) == en->paths.end()) en->paths.push_back(path);
+        res_path_key[path] = key;
+        return en;
+    };
+    auto res_insert = [&](const std::string& key, const std::string& path, tw_image* img, int w, int h) {
+        const size_t bytes = ((size_t)w * (size_t)h + 255) / 256 * 256;
+        if (res_cache.count(key) || bytes > res_budget) {  // (a pair of another batch got there first / larger than the budget)
+            (void)tw_image_release(eng, img);
+            return;
+        }
+        while (res_bytes + bytes > res_budget && !res_lru.empty()) res_evict(res_lru.back());
+        std::unique_ptr<ResEntry> en(new ResEntry());
+        en->key = key;
+        en->paths.push_back(path);
+        en->img = img;
+        en->w = w;
+        en->h = h;
+        en->bytes = bytes;
+        res_lru.push_front(en.get());
+        en->lru = res_lru.begin();
+        res_bytes += bytes;
+        res_path_key[path] = key;
+        res_cache[key] = std::move(en);
+    };
     auto finish = [&](Staged& s) {
         if (s.done) return;
         s.done = true;
@@ -957,6 +1066,20 @@ void Consumer::run()
             float sec = 0;
             tw_status r = tw_wait(eng, s.ticket, v, cap, &n, &sec);
             if (shared_) shared_->inflight--;
+            if (s.kept) {
+                // the expected image this pair kept: into the cache when the pair answered OK, released otherwise (a palette
+                // index without an entry leaves it undefined — the pairs that read it meanwhile answer as this one does)
+                s.keep->expect_bad = r == TW_E_BAD_IMAGE_FORMAT && strstr(tw_last_error(eng), "target") == nullptr;
+                s.keep->img = nullptr;
+                auto pk = res_pending.find(s.rkey);
+                if (pk != res_pending.end() && pk->second == s.keep) res_pending.erase(pk);
+                if (r == TW_OK) res_insert(s.rkey, s.req.expect_image, s.kept, s.w, s.h);
+                else (void)tw_image_release(eng, s.kept);
+                s.kept = nullptr;
+            }
+            if (s.uses_keep && s.keep->expect_bad) {
+                s.err = "Can't open " + s.req.expect_image;
+            } else
             if (r == TW_E_BAD_IMAGE_FORMAT && (s.ka.rows() || s.kb.rows())) {
                 // a palette index without a PLTE entry, found by the device: cv::imread fails on that file, and the
                 // ticket's message names it (the expected image first, as the reference opens it first)
@@ -1102,10 +1225,49 @@ void Consumer::run()
                 bool read_ok = false, rows_ok = false;
             };
             std::vector<Opened> op(2 * jobs.size());
+            // Phase 0 (resident expected images): stat every expected file; one that is cached, or that a pair in flight or
+            // earlier in this batch is about to keep, is neither read nor decoded below
+            if (resident_on)
+                for (size_t j = 0; j < jobs.size(); j++) {
+                    Staged& s = jobs[j];
+                    const std::string& path = s.req.expect_image;
+                    if (s.req.raw.expect || path.empty()) continue;
+                    s.rkey = file_identity(path);
+                    auto seen = res_path_key.find(path);
+                    if (seen != res_path_key.end() && seen->second != s.rkey) {  // rewritten (or gone): the old image goes
+                        auto old = res_cache.find(seen->second);
+                        if (old != res_cache.end()) res_evict(old->second.get());
+                        res_path_key.erase(path);
+                    }
+                    if (s.rkey.empty()) continue;  // (no such file: the path below answers "Can't open")
+                    if (ResEntry* en = res_lookup(s.rkey, path)) {
+                        s.hit = en;
+                        en->pins++;
+                        s.w = en->w;
+                        s.h = en->h;
+                        continue;
+                    }
+                    auto pk = res_pending.find(s.rkey);
+                    if (pk != res_pending.end()) {
+                        s.keep = pk->second;
+                        s.follower = true;
+                        s.w = s.keep->w;
+                        s.h = s.keep->h;
+                        continue;
+                    }
+                    for (size_t q = 0; q < j && !s.follower; q++)
+                        if (jobs[q].rkey == s.rkey && !jobs[q].no_expected_file()) {
+                            s.keep = jobs[q].keep;
+                            s.follower = true;
+                            s.leader = (int)q;
+                        }
+                    if (!s.follower) s.keep = std::make_shared<Staged::Keep>();
+                }
+            auto skipped = [&](size_t i) { return !(i & 1) && jobs[i >> 1].no_expected_file(); };
             parallel_for(2 * jobs.size(), [&](size_t i) {
                 const Staged& s = jobs[i >> 1];
                 const std::string& path = (i & 1) ? s.req.target_image : s.req.expect_image;
-                if (s.req.raw.expect || path.empty()) return;
+                if (s.req.raw.expect || path.empty() || skipped(i)) return;
                 Opened& o = op[i];
                 o.read_ok = read_file(path, o.file);
                 if (o.read_ok && device_png && eng && o.file.size() >= 8 && o.file[0] == 0x89 && o.file[1] == 'P')
@@ -1141,7 +1303,9 @@ void Consumer::run()
             };
             bool fast = !op.empty();
             size_t fslot = 0;
-            for (const Opened& o : op) {
+            for (size_t i = 0; i < op.size(); i++) {
+                if (skipped(i)) continue;
+                const Opened& o = op[i];
                 fast = fast && o.rows_ok;
                 fslot = std::max(fslot, (o.st.total + 8 + 255) / 256 * 256);
             }
@@ -1153,6 +1317,7 @@ void Consumer::run()
             if (fast) {
                 // Phase 2 (pool): inflate into the arena slot; every row's filter type is checked as libpng does
                 parallel_for(2 * jobs.size(), [&](size_t i) {
+                    if (skipped(i)) return;
                     Opened& o = op[i];
                     uint8_t* dst = ar.base + fslot * i;
                     bool ok = png_inflate(o.st, dst);
@@ -1168,23 +1333,28 @@ void Consumer::run()
                 bt1 = steady_ns();
                 for (size_t j = 0; j < jobs.size(); j++) {
                     Staged& s = jobs[j];
-                    const PngStream &sa = op[2 * j].st, &sb = op[2 * j + 1].st;
+                    // (a resident expected image: its size is the cache entry's, or that of the pair that keeps it)
+                    const bool no_file = s.no_expected_file();
+                    if (no_file && s.leader >= 0 && !ea[(size_t)s.leader].empty()) ea[j] = "Can't open " + s.req.expect_image;
+                    const PngStream& sa = op[2 * (size_t)(no_file && s.leader >= 0 ? s.leader : (int)j)].st;
+                    const PngStream& sb = op[2 * j + 1].st;
+                    const int ew = no_file && s.leader < 0 ? s.w : sa.w, eh = no_file && s.leader < 0 ? s.h : sa.h;
                     // the reference opens the expected image first: its error wins (src/opticalflow.cpp:26-48)
                     if (!ea[j].empty()) { s.err = ea[j]; continue; }
                     if (!eb[j].empty()) { s.err = eb[j]; continue; }
-                    s.w = sa.w;
-                    s.h = sa.h;
-                    s.ka = sa.kind();
+                    s.w = ew;
+                    s.h = eh;
+                    s.ka = no_file ? PngKind() : sa.kind();
                     s.kb = sb.kind();
                     uint8_t* da = ar.base + fslot * (2 * j);
                     uint8_t* db = da + fslot;
-                    if (sa.w == sb.w && sa.h == sb.h) {
+                    if (ew == sb.w && eh == sb.h) {
                         s.pa = da;
                         s.pb = db;
                         s.stride = s.w;
                         continue;
                     }
-                    if (abs(sa.h - sb.h) > 5 || abs(sa.w - sb.w) > 5) { s.err = "Don't match image size"; continue; }
+                    if (abs(eh - sb.h) > 5 || abs(ew - sb.w) > 5) { s.err = "Don't match image size"; continue; }
                     if (device_reconcile) {  // within 5 px: the pair stays in the arena, the device resizes the target
                         s.pa = da;
                         s.pb = db;
@@ -1194,7 +1364,7 @@ void Consumer::run()
                         continue;
                     }
                     // TW_DEVICE_RECONCILE=0: the reconcile of prepare() on the host, on copies outside the arena
-                    s.a.assign(da, da + sa.total);
+                    if (!no_file) s.a.assign(da, da + sa.total);
                     s.b.assign(db, db + sb.total);
                     prepare(s, sb.w, sb.h, std::string(), std::string(), false);
                 }
@@ -1206,6 +1376,13 @@ void Consumer::run()
                 std::vector<uint8_t>().swap(op[i].file);
             });
             bt1 = steady_ns();
+            for (size_t j = 0; j < jobs.size(); j++) {  // (a pair behind the one that keeps its expected image: that one's size)
+                Staged& s = jobs[j];
+                if (!s.follower || s.leader < 0) continue;
+                if (!ea[(size_t)s.leader].empty()) ea[j] = "Can't open " + s.req.expect_image;
+                s.w = jobs[(size_t)s.leader].w;
+                s.h = jobs[(size_t)s.leader].h;
+            }
             parallel_for(jobs.size(), [&](size_t j) { prepare(jobs[j], tw[j], th[j], ea[j], eb[j], device_reconcile); });
             // The arena is sized AFTER prepare(), over the pairs that decoded and reconciled (a header with
             // huge dimensions over a damaged stream must not size it), and it is bounded: a pair larger than
@@ -1225,7 +1402,7 @@ void Consumer::run()
                 if (std::max(s.a.size(), s.b.size()) > slot || (2 * j + 2) * slot > ar.cap) return;  // stays pageable
                 uint8_t* da = ar.base + slot * (2 * j);
                 uint8_t* db = da + slot;
-                memcpy(da, s.a.data(), s.a.size());
+                if (!s.a.empty()) memcpy(da, s.a.data(), s.a.size());
                 memcpy(db, s.b.data(), s.b.size());
                 s.pa = da;
                 s.pb = db;
@@ -1244,37 +1421,72 @@ void Consumer::run()
             Staged& s = jobs[k];
             if (s.err.empty() && !eng) s.err = eng_err;
             if (!s.err.empty()) continue;
+            auto rows_of = [](const uint8_t* p, int w, int h, const PngKind& k) {
+                tw_png_rows r;
+                r.rows = p;
+                r.width = w;
+                r.height = h;
+                r.color_type = k.color_type;
+                r.bit_depth = k.bit_depth;
+                r.palette = k.plte.empty() ? nullptr : k.plte.data();
+                r.palette_entries = (int)(k.plte.size() / 3);
+                return r;
+            };
+            auto luma_of = [](const uint8_t* p, int w, int h, const Staged::JpegHead& jh) {
+                tw_jpeg_luma l;
+                l.coef = jh.on() ? (const int16_t*)p : nullptr;
+                l.gray = jh.on() ? nullptr : p;
+                l.width = w;
+                l.height = h;
+                l.blocks_w = jh.bw;
+                l.blocks_h = jh.bh;
+                memcpy(l.quant, jh.quant, sizeof(l.quant));
+                return l;
+            };
+            // A pair behind one that was to keep its expected image, and that one failed before it did (its target, the
+            // sizes): this pair is decoded again on its own, expected file included, and goes the ordinary way
+            if (s.follower && !s.keep->img && !res_cache.count(s.rkey)) {
+                s.follower = false;
+                s.leader = -1;
+                s.keep = std::make_shared<Staged::Keep>();
+                s.a.clear();
+                s.b.clear();
+                s.ka = s.kb = PngKind();
+                s.ja = s.jb = Staged::JpegHead();
+                s.tw = s.th = 0;
+                int tw1 = 0, th1 = 0;
+                std::string ea1, eb1;
+                decode_one(s, 0, &tw1, &th1, &ea1, device_png, png_kinds, false, nullptr);
+                decode_one(s, 1, &tw1, &th1, &eb1, device_png, png_kinds, false, nullptr);
+                prepare(s, tw1, th1, ea1, eb1, device_reconcile);
+                if (!s.err.empty()) continue;
+            }
             auto submit = [&]() -> tw_status {
+                // the expected image is resident: only the target goes up, in whatever form it was decoded to
+                tw_image* use = s.hit ? s.hit->img : nullptr;
+                if (!use && s.follower) {
+                    use = s.keep->img;
+                    s.uses_keep = use != nullptr;
+                    if (!use)
+                        if (ResEntry* en = res_lookup(s.rkey, s.req.expect_image)) use = en->img;
+                }
+                if (use) {
+                    const int tw_ = s.tw ? s.tw : s.w, th_ = s.tw ? s.th : s.h;
+                    if (s.jb.on()) {
+                        const tw_jpeg_luma lb = luma_of(s.pb, tw_, th_, s.jb);
+                        return tw_submit_image_jpeg(eng, use, &lb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
+                    }
+                    const tw_png_rows rb = rows_of(s.pb, tw_, th_, s.kb);
+                    return tw_submit_image_png(eng, use, &rb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
+                }
                 // half-decoded PNG(s): the device reconstructs the scanlines, and resizes a target within 5 px of the pair's size
                 if (s.ka.rows() || s.kb.rows()) {
-                    auto rows_of = [](const uint8_t* p, int w, int h, const PngKind& k) {
-                        tw_png_rows r;
-                        r.rows = p;
-                        r.width = w;
-                        r.height = h;
-                        r.color_type = k.color_type;
-                        r.bit_depth = k.bit_depth;
-                        r.palette = k.plte.empty() ? nullptr : k.plte.data();
-                        r.palette_entries = (int)(k.plte.size() / 3);
-                        return r;
-                    };
                     const tw_png_rows ra = rows_of(s.pa, s.w, s.h, s.ka);
                     const tw_png_rows rb = rows_of(s.pb, s.tw ? s.tw : s.w, s.tw ? s.th : s.h, s.kb);
                     return tw_submit_png(eng, &ra, &rb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
                 }
                 // JPEG(s) that stopped at the coefficient plane: the device runs the inverse DCT (and the reconcile)
                 if (s.ja.on() || s.jb.on()) {
-                    auto luma_of = [](const uint8_t* p, int w, int h, const Staged::JpegHead& jh) {
-                        tw_jpeg_luma l;
-                        l.coef = jh.on() ? (const int16_t*)p : nullptr;
-                        l.gray = jh.on() ? nullptr : p;
-                        l.width = w;
-                        l.height = h;
-                        l.blocks_w = jh.bw;
-                        l.blocks_h = jh.bh;
-                        memcpy(l.quant, jh.quant, sizeof(l.quant));
-                        return l;
-                    };
                     const tw_jpeg_luma la = luma_of(s.pa, s.w, s.h, s.ja);
                     const tw_jpeg_luma lb = luma_of(s.pb, s.tw ? s.tw : s.w, s.tw ? s.th : s.h, s.jb);
                     return tw_submit_jpeg(eng, &la, &lb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
@@ -1296,8 +1508,24 @@ void Consumer::run()
             if (r == TW_OK) {
                 s.submitted = true;
                 if (shared_) shared_->inflight++;
+                // a miss: the image the batch sees stays on the device (one device-to-device copy behind its decode), and
+                // enters the cache when the pair has answered OK
+                if (resident_on && !s.rkey.empty() && !s.no_expected_file() && s.keep) {
+                    if (tw_image_keep(eng, s.ticket, TW_KEEP_EXPECT, &s.kept) == TW_OK) {
+                        s.keep->img = s.kept;
+                        s.keep->w = s.w;
+                        s.keep->h = s.h;
+                        res_pending[s.rkey] = s.keep;
+                    } else s.kept = nullptr;
+                }
             } else s.err = std::string(tw_last_error(eng)[0] ? tw_last_error(eng) : tw_strerror(r));
         }
+        for (Staged& s : jobs)  // (submitted or refused: the batch holds the image now, the cache entry may go)
+            if (s.hit) {
+                s.hit->pins--;
+                s.hit = nullptr;
+            }
+        res_sweep();
         if (eng) (void)tw_flush(eng);  // a partly filled batch starts now, not when its first result is asked for
         bt3 = steady_ns();
         const size_t njobs = jobs.size();
@@ -1315,6 +1543,8 @@ void Consumer::run()
     finish_all(prev);
     read_prof(true);
     publish();
+    while (!res_lru.empty()) res_evict(res_lru.back());  // Manager::stop: every resident image goes back
+    res_sweep();
     for (Arena& ar : arena)
         if (eng && ar.base) (void)tw_host_free(eng, ar.base);
     if (eng) tw_engine_destroy(eng);
@@ -1351,6 +1581,11 @@ void Manager::start(const Parameter& p)
     if (const char* ev = getenv("TW_DECODE_THREADS")) dec = atoi(ev);
     if (dec <= 0) dec = std::max(1, std::min(16, (int)std::thread::hardware_concurrency() / n));
     shared_.profile = p.profileKernels;
+    // the budget of every consumer's cache of resident expected images: Parameter::residentMB, else TW_RESIDENT_MB; 0 = off
+    long long res_mb = p.residentMB;
+    if (res_mb <= 0)
+        if (const char* ev = getenv("TW_RESIDENT_MB")) res_mb = atoll(ev);
+    shared_.residentBytes = res_mb > 0 ? res_mb << 20 : 0;
     shared_.stats.assign((size_t)n, ConsumerStats());
     for (int i = 0; i < n; i++) {
         consumers_.push_back(new Consumer(i, requestQueue_, responseQueue_, p.optParam, batch, dec, n, &shared_));

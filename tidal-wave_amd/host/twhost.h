@@ -71,6 +71,9 @@ struct Parameter {
     // bracket the level-0 window-average and polynomial-expansion launches of every consumer's engine with events
     // (tw_prof_select): the queue driver's roofline figures come from them (tools/bench_queue.cpp)
     bool profileKernels = false;
+    // not in the reference: megabytes of device memory each consumer may fill with resident expected images, keyed by the
+    // file's identity (0: TW_RESIDENT_MB, else off — every pair then reads, decodes and uploads both files, as before)
+    int residentMB = 0;
 };
 
 // What one consumer did, as seen by Manager::consumerStats() (a copy; the consumer thread owns the original).
@@ -220,6 +223,7 @@ struct ConsumerShared {
     std::atomic<int> epoch{0};
     std::atomic<long> inflight{0};  // pairs submitted to an engine and not yet collected, over all consumers
     bool profile = false;
+    long long residentBytes = 0;  // the budget of a consumer's resident expected images (0: off)
 };
 
 class Consumer {

@@ -68,6 +68,8 @@ SYMBOLS = [
     "tw_submit_u8_flow_init", "tw_submit_png8_flow_init", "tw_submit_dev_flow_init",
     "tw_submit_u8_sized", "tw_submit_png8_sized", "tw_submit_dev_sized", "tw_stage_resize_u8",
     "tw_png_on_device", "tw_submit_png", "tw_stage_png_decode", "tw_submit_jpeg", "tw_stage_jpeg_idct",
+    "tw_image_keep", "tw_image_create_u8", "tw_image_release", "tw_image_size", "tw_submit_image_png", "tw_submit_image_jpeg",
+    "tw_debug_resident",
     "tw_grid_capacity", "tw_dev_alloc", "tw_dev_free", "tw_dev_upload", "tw_dev_download", "tw_host_alloc", "tw_host_free", "tw_host_register", "tw_host_unregister", "tw_set_option",
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
@@ -232,6 +234,14 @@ def _bind(path):
     L.tw_submit_jpeg.argtypes = [vp, C.POINTER(JpegLuma), C.POINTER(JpegLuma), C.c_int, C.c_double, fip, fop, tkp]
     L.tw_stage_jpeg_idct.argtypes = [vp, C.POINTER(JpegLuma), u8p, u8p]
     L.tw_debug_png_kernel_time.argtypes = [vp, C.POINTER(PngRows), C.c_int, C.c_int, fp]
+    L.tw_image_keep.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(vp)]
+    L.tw_image_create_u8.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_ssize_t, C.POINTER(vp)]
+    L.tw_image_release.argtypes = [vp, vp]
+    L.tw_image_size.argtypes = [vp, vp, ip, ip]
+    L.tw_submit_image_png.argtypes = [vp, vp, C.POINTER(PngRows), C.c_int, C.c_double, fip, fop, tkp]
+    L.tw_submit_image_jpeg.argtypes = [vp, vp, C.POINTER(JpegLuma), C.c_int, C.c_double, fip, fop, tkp]
+    L.tw_debug_resident.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.tw_debug_resident.restype = C.c_int
     L.tw_wait.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, fp]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
@@ -416,6 +426,28 @@ def _gray(a):
     return a
 
 
+KEEP_EXPECT, KEEP_TARGET = 0, 1
+
+
+class Image:
+    """tw_image: a gray image resident in the engine's device memory (Engine.image / Engine.keep).  The engine looks the
+    handle up in its own registry, so a released or foreign Image is refused (TW_E_BAD_PARAMETER), never dereferenced."""
+
+    def __init__(self, engine, handle):
+        self._e, self._h = engine, handle
+
+    @property
+    def size(self):
+        """(width, height)"""
+        w, h = C.c_int(), C.c_int()
+        self._e._check(self._e._L.tw_image_size(self._e._h, self._h, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def release(self):
+        """tw_image_release: the block returns to the engine's store once every batch that reads it has been collected."""
+        self._e._check(self._e._L.tw_image_release(self._e._h, self._h))
+
+
 class Engine:
     """One worker's engine on one GPU (OpticalFlowByGPU of the reference, src/opticalflow.h:62-70)."""
 
@@ -586,6 +618,50 @@ class Engine:
                                            C.byref(fi) if fi is not None else None,
                                            C.byref(fo) if fo is not None else None, C.byref(tk)))
         return (tk.value, w, h, span, threshold)
+
+    # ---- resident images ------------------------------------------------------------------------------
+    def image(self, gray):
+        """tw_image_create_u8: a 2-D uint8 image made resident."""
+        a = _gray(gray)
+        h, w = a.shape
+        out = C.c_void_p()
+        self._check(self._L.tw_image_create_u8(self._h, _u8(a), w, h, a.strides[0], C.byref(out)))
+        return Image(self, out)
+
+    def keep(self, ticket, which="expect"):
+        """tw_image_keep: the expected ("expect") or target ("target") image of a submitted, not yet waited pair, as its
+        batch sees it; `which` may also be the raw integer."""
+        k = {"expect": KEEP_EXPECT, "target": KEEP_TARGET}.get(which, which)
+        out = C.c_void_p()
+        self._check(self._L.tw_image_keep(self._h, ticket[0], int(k), C.byref(out)))
+        return Image(self, out)
+
+    def submit_image(self, img, target, span=10, threshold=5.0, *, flow=None, init=None):
+        """tw_submit_image_png / tw_submit_image_jpeg: the expected image is the resident `img`; target is a 2-D uint8 gray
+        image or a PngRows (tw_submit_image_png), or a JpegLuma (tw_submit_image_jpeg), at its own size.  flow, init: as
+        for submit."""
+        w, h = img.size if img is not None else (0, 0)
+        tk = C.c_int64()
+        fo = _flow_out(flow, w, h) if img is not None else None
+        fi, _keep = _flow_in(init, w, h) if img is not None else (None, None)
+        args = (span, threshold, C.byref(fi) if fi is not None else None, C.byref(fo) if fo is not None else None,
+                C.byref(tk))
+        ih = img._h if img is not None else None
+        if isinstance(target, JpegLuma):
+            self._check(self._L.tw_submit_image_jpeg(self._h, ih, C.byref(target), *args))
+        else:
+            if not isinstance(target, PngRows):
+                b = np.ascontiguousarray(_gray(target))
+                target = PngRows(b, b.shape[1], b.shape[0])
+            self._check(self._L.tw_submit_image_png(self._h, ih, C.byref(target), *args))
+        return (tk.value, w, h, span, threshold)
+
+    def resident(self):
+        """The resident store (twflow_debug.h: tw_debug_resident)."""
+        v = (C.c_uint64 * 4)()
+        if self._L.tw_debug_resident(self._h, v) != 4:
+            raise TwError(TW_E_BAD_PARAMETER, "tw_debug_resident failed")
+        return {"images": int(v[0]), "bytes_in_use": int(v[1]), "bytes_reserved": int(v[2]), "chunk_allocs": int(v[3])}
 
     def stage_jpeg_idct(self, luma, guard=False):
         """tw_jpeg_idct alone on one JpegLuma with coefficients: the (h, w) gray image; guard=True: also the 512 device

@@ -3,6 +3,7 @@
 through host/index.js create() (addon -> decode pool -> libtwflow.so) and prints pairs/s.  Needs a GPU + node.
 
     e2e_files.py [N [DECODE_THREADS]] [--corpus gray|rgba|palette|mixed|jpeg] [--host DIR] [--json]
+                 [--copies] [--passes K] [--resident MB]
     e2e_files.py --kernel-time
 
   --corpus   the kind of file: 8-bit gray (the default, what this tool has always written), RGBA, palette-8 with the
@@ -10,6 +11,13 @@ through host/index.js create() (addon -> decode pool -> libtwflow.so) and prints
              4:2:0 JPEGs of the same images as r = g = b colour files (what a screenshot tool writes)
   --host     the host/ directory whose index.js and addon run (default: this tree's): A/B against another build
   --json     one JSON line instead of the text
+  --copies   the expected files beyond the four distinct ones are COPIES, each a file of its own, not hard links (the
+             targets stay hard links): what a cache keyed by a file's identity needs to see N baselines instead of four
+  --passes   K passes over the same pairs through ONE long-lived TidalWave instance (calc() per pair, dispose() after the
+             last pass) instead of one create() run; pairs/s per pass, and with TW_DEBUG_BATCHTIME=1 in the environment the
+             mean of the batches' "decode" column per pass
+  --resident MB   the instance's residentMB option (resident expected images; implies --passes 2 unless given): pass 1 is
+             all misses, pass 2 all hits when the budget holds the corpus (1080p: 2 MB per expected file)
   --kernel-time   no files: tw_png_unfilter per 1080p image for RGBA, palette-8 and 1-bit gray rows, event-timed
              (tw_debug_png_kernel_time, 20 launches between two events, the median of 7 such figures)
 The environment goes through unchanged (TW_DEVICE_PNG_KINDS=0 keeps palette files on the host, TW_DEVICE_JPEG=0 / 1 a
@@ -73,7 +81,11 @@ def main():
     ap.add_argument("--host", default=os.path.join(ROOT, "tidal-wave_amd", "host"))
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--kernel-time", action="store_true")
+    ap.add_argument("--copies", action="store_true")
+    ap.add_argument("--passes", type=int, default=0)
+    ap.add_argument("--resident", type=int, default=0)
     a = ap.parse_args()
+    passes = a.passes or (2 if a.resident else 0)  # 0: the one create() run this tool has always made
     if a.kernel_time:
         return kernel_time()
     n, threads = a.n, a.threads
@@ -92,7 +104,10 @@ def main():
                 save(img_b, pt, kind)
                 made[(i % 4, kind)] = (pe, pt)
             else:  # the four distinct pairs again (hard links: the decoder reads and inflates every file all the same)
-                os.link(made[(i % 4, kind)][0], pe)
+                if a.copies:
+                    shutil.copyfile(made[(i % 4, kind)][0], pe)
+                else:
+                    os.link(made[(i % 4, kind)][0], pe)
                 os.link(made[(i % 4, kind)][1], pt)
         js = ("var T=require('./index'); var t0=Date.now(); var n=0, err=0;"
               "var t=T.create(process.argv[1],{expectDir:process.argv[2], numThreads:8});"
@@ -100,11 +115,22 @@ def main():
               "var rss0=process.memoryUsage().rss, rssMid=0; setTimeout(function(){rssMid=process.memoryUsage().rss}, 3000);"
               "t.on('finish',function(r){console.log(JSON.stringify({report:r, ms:Date.now()-t0, errors:err, rss_start_MB:rss0>>20, "
               "rss_at_3s_MB:rssMid>>20, rss_end_MB:process.memoryUsage().rss>>20}))});")
+        if passes:
+            js = ("var T=require('./index'), FS=require('fs'), Path=require('path');"
+                  "var tdir=Path.join(process.argv[1],'s'), edir=Path.join(process.argv[2],'s'), passes=+process.argv[3], mb=+process.argv[4];"
+                  "var names=FS.readdirSync(tdir).sort(); var opts={numThreads:8}; if(mb>0) opts.residentMB=mb;"
+                  "var t=new T.TidalWave(opts); var ms=[], pass=0, left=0, t0=0, err=0;"
+                  "function start(){pass++; console.error('TWE2E PASS '+pass); left=names.length; t0=Date.now();"
+                  " names.forEach(function(n){t.calc(Path.join(edir,n), Path.join(tdir,n))})}"
+                  "function one(){if(--left===0){ms.push(Date.now()-t0); if(pass<passes) setTimeout(start,50); else t.dispose()}}"
+                  "t.on('data',one); t.on('error',function(e){err++; console.error(JSON.stringify(e)); one()});"
+                  "t.on('finish',function(r){console.log(JSON.stringify({report:r, ms:ms.reduce(function(x,y){return x+y},0), pass_ms:ms, errors:err}))});"
+                  "start();")
         env = dict(os.environ)
         if threads:
             env["TW_DECODE_THREADS"] = threads
         t0 = time.time()
-        r = subprocess.run(["node", "-e", js, os.path.join(d, "target"), os.path.join(d, "expected")],
+        r = subprocess.run(["node", "-e", js, os.path.join(d, "target"), os.path.join(d, "expected"), str(passes), str(a.resident)],
                            cwd=a.host, capture_output=True, text=True, env=env)
         wall = time.time() - t0
     finally:
@@ -112,6 +138,20 @@ def main():
     if r.returncode != 0 or not r.stdout.strip():
         sys.exit("node failed (%d): %s" % (r.returncode, r.stderr.strip()[-3000:]))
     out = json.loads(r.stdout.strip().splitlines()[-1])
+    if passes:
+        # per pass: pairs/s and, from TW_DEBUG_BATCHTIME's lines, the mean "decode" milliseconds of a batch
+        decode, cur = {}, 0
+        for line in r.stderr.splitlines():
+            if line.startswith("TWE2E PASS "):
+                cur = int(line.split()[-1])
+            elif ": decode " in line and cur:
+                decode.setdefault(cur, []).append(float(line.split(": decode ")[1].split(" ms")[0]))
+        res = {"corpus": a.corpus, "pairs": n, "copies": a.copies, "resident_mb": a.resident, "host": os.path.relpath(a.host, ROOT),
+               "pairs_per_s": [round(n / (ms / 1e3), 1) for ms in out["pass_ms"]], "pass_ms": out["pass_ms"],
+               "decode_ms_per_batch": [round(statistics.mean(decode[k]), 2) if k in decode else None for k in range(1, passes + 1)],
+               "batches": [len(decode.get(k, [])) for k in range(1, passes + 1)], "report": out["report"], "errors": out["errors"]}
+        print(json.dumps(res) if a.json else "\n".join("%s: %s" % kv for kv in res.items()))
+        return
     rate = n / (out["ms"] / 1e3)
     if a.json:
         print(json.dumps({"corpus": a.corpus, "pairs": n, "decode_threads": threads or "auto", "host": os.path.relpath(a.host, ROOT),
