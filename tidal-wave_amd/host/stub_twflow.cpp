@@ -10,10 +10,22 @@
 //                        after the other, and tw_wait returns when the batch's completion time has passed (a timer,
 //                        not a sleep per call) — VERDICT r4 #5: 31.3 ms per 128 pairs per device at 1080p.
 //
+// Two switches for the tests of the consumer's steps (tests/test_host_consumer_steps.py, tools/consumer_trace.py):
+//   TW_STUB_TRACE=<file> every call of the C ABI appends one line to <file>, under one mutex: the engine's device, the
+//                        call's name, its value arguments, the ticket, an image handle's ordinal of creation, and for every
+//                        host image handed over whether it lies inside a live tw_host_alloc block ("pin") and a 64-bit
+//                        FNV-1a of exactly the bytes the call may read; then the status (tw_wait: the count too).
+//                        tw_host_alloc logs its byte count, tw_host_free the ordinal of the block.  Pointers and times are
+//                        not logged.  Off unless set: the timing models are untouched.  Not recorded: the queries that take
+//                        no engine's state and may come from any thread (tw_png_on_device — the decode pool asks it —,
+//                        tw_strerror, tw_last_error, tw_default_params, tw_stub_*).
+//   TW_STUB_BUSY_AT=k    the k-th submit call of each engine answers TW_E_BUSY once and books nothing (the consumer's retry)
+//
 // What "differs" means changed with tw_submit_png: the consumer sends every half-decoded pair through it, and the stub
 // finishes both images with the host layer's own code (one allocation and copy per image) and compares the GRAY of pixel
 // 0, where tw_submit_png8 compares the first raw sample of the filtered rows.  Two RGBA files with equal R bytes and
 // different grays (or the reverse) therefore answer differently through the two calls; the suite's fixtures do not.
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -54,6 +66,7 @@ struct tw_engine {
     std::map<tw_ticket, std::string> bad;  // tw_submit_png: the image ("expected" / "target") the host's finisher refused
     std::string err;
     tw_ticket next = 1;
+    int submit_calls = 0, busy_at = 0;  // TW_STUB_BUSY_AT
     // timer model (TW_STUB_BATCH_MS): the open batch and the completion time of every launched one
     double batch_ms = 0;
     long cur_batch = 0;
@@ -84,22 +97,129 @@ static std::atomic<long> g_png_calls{0}, g_png_row_images{0};
 static std::atomic<long> g_jpeg_calls{0}, g_jpeg_coef_images{0};
 // resident images: tw_image_keep calls that kept one, pairs that came through tw_submit_image_*, tw_image_release calls
 static std::atomic<long> g_res_kept{0}, g_res_image_pairs{0}, g_res_released{0};
-static std::atomic<uintptr_t> g_next_image{0x1000};
+static const uintptr_t kFirstImage = 0x1000, kImageStep = 16;
+static std::atomic<uintptr_t> g_next_image{kFirstImage};
+
+// --- the call recorder (TW_STUB_TRACE) ---
+static const char* const g_trace_path = getenv("TW_STUB_TRACE");
+static std::mutex g_trace_m;
+static FILE* g_trace_file = nullptr;
+struct HostBlock {
+    size_t bytes;
+    long ordinal;
+};
+static std::map<const uint8_t*, HostBlock> g_blocks;  // live tw_host_alloc blocks (kept only while tracing)
+static long g_block_ordinal = 0;
+static inline bool tracing() { return g_trace_path && g_trace_path[0]; }
+static void trace(const tw_engine* e, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+static void trace(const tw_engine* e, const char* fmt, ...)
+{
+    std::lock_guard<std::mutex> lk(g_trace_m);
+    if (!g_trace_file) g_trace_file = fopen(g_trace_path, "a");
+    if (!g_trace_file) return;
+    if (e) fprintf(g_trace_file, "dev=%d ", e->device);
+    else fputs("dev=- ", g_trace_file);
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(g_trace_file, fmt, ap);
+    va_end(ap);
+    fputc('\n', g_trace_file);
+    fflush(g_trace_file);
+}
+static const char* status_name(tw_status r)
+{
+    switch (r) {
+        case TW_OK: return "OK";
+        case TW_E_BUSY: return "BUSY";
+        case TW_E_BAD_PARAMETER: return "BAD_PARAMETER";
+        case TW_E_BAD_IMAGE_FORMAT: return "BAD_IMAGE_FORMAT";
+        case TW_E_DONT_MATCH_SIZE: return "DONT_MATCH_SIZE";
+        case TW_E_UNSUPPORTED: return "UNSUPPORTED";
+        case TW_E_NOMEM: return "NOMEM";
+        case TW_E_DEVICE: return "DEVICE";
+        default: return "OTHER";
+    }
+}
+static long image_ordinal(const tw_image* img) { return img ? (long)(((uintptr_t)img - kFirstImage) / kImageStep) : -1; }
+// "pin=<0|1> fnv=<hash>" of `rows` rows of `row_bytes` at `stride`, plus `tail` bytes at `extra` (a JPEG's quant table)
+static std::string bytes_seen(const void* p, size_t rows, size_t row_bytes, ptrdiff_t stride, const void* extra = nullptr,
+                              size_t tail = 0)
+{
+    if (!p) return "null";
+    const uint8_t* b = (const uint8_t*)p;
+    uint64_t h = 1469598103934665603ull;
+    for (size_t y = 0; y < rows; y++)
+        for (size_t x = 0; x < row_bytes; x++) h = (h ^ b[(ptrdiff_t)y * stride + (ptrdiff_t)x]) * 1099511628211ull;
+    for (size_t x = 0; x < tail; x++) h = (h ^ ((const uint8_t*)extra)[x]) * 1099511628211ull;
+    bool pinned = false;
+    {
+        std::lock_guard<std::mutex> lk(g_trace_m);
+        auto it = g_blocks.upper_bound(b);
+        if (it != g_blocks.begin()) {
+            --it;
+            const size_t last = rows ? (rows - 1) * (size_t)stride + row_bytes : 0;
+            pinned = b + last <= it->first + it->second.bytes;
+        }
+    }
+    char buf[64];
+    snprintf(buf, sizeof(buf), "pin=%d fnv=%016llx", pinned ? 1 : 0, (unsigned long long)h);
+    return buf;
+}
+static size_t png_row_bytes(int color_type, int bit_depth, int w)
+{
+    const size_t samples = color_type == 2 ? 3 : color_type == 4 ? 2 : color_type == 6 ? 4 : 1;
+    return 1 + ((size_t)w * samples * (size_t)bit_depth + 7) / 8;
+}
+static std::string rows_seen(const tw_png_rows* r)
+{
+    if (!r) return "null";
+    const bool gray = r->color_type == TW_PNG_PLAIN_GRAY;
+    const size_t rb = gray ? (size_t)r->width : png_row_bytes(r->color_type, r->bit_depth, r->width);
+    char buf[96];
+    if (gray) snprintf(buf, sizeof(buf), "%dx%d gray ", r->width, r->height);
+    else snprintf(buf, sizeof(buf), "%dx%d ct=%d bd=%d plte=%d ", r->width, r->height, r->color_type, r->bit_depth, r->palette_entries);
+    return buf + bytes_seen(r->rows, r->height > 0 ? (size_t)r->height : 0, r->width > 0 ? rb : 0, (ptrdiff_t)rb);
+}
+static std::string luma_seen(const tw_jpeg_luma* l)
+{
+    if (!l) return "null";
+    char buf[96];
+    if (l->coef) {
+        snprintf(buf, sizeof(buf), "%dx%d coef blocks=%dx%d ", l->width, l->height, l->blocks_w, l->blocks_h);
+        return buf + bytes_seen(l->coef, 1, (size_t)l->blocks_w * (size_t)l->blocks_h * 128, 0, l->quant, 128);
+    }
+    snprintf(buf, sizeof(buf), "%dx%d gray ", l->width, l->height);
+    return buf + bytes_seen(l->gray, l->height > 0 ? (size_t)l->height : 0, l->width > 0 ? (size_t)l->width : 0, l->width);
+}
+// TW_STUB_BUSY_AT: true for the one submit call that is to answer TW_E_BUSY
+static bool busy_now(tw_engine* e)
+{
+    if (!e) return false;
+    std::lock_guard<std::mutex> lk(e->m);
+    return ++e->submit_calls == e->busy_at;
+}
 
 extern "C" {
 void tw_default_params(tw_params* p)
 {
     p->pyrScale = 0.5; p->pyrLevels = 3; p->winSize = 30; p->pyrIterations = 3; p->polyN = 7; p->polySigma = 1.5; p->flags = 256;
 }
-int tw_device_count(void)
+static int stub_device_count()
 {
     const char* ev = getenv("TW_STUB_DEVICES");
     return ev ? atoi(ev) : 8;
 }
+int tw_device_count(void)
+{
+    const int n = stub_device_count();
+    if (tracing()) trace(nullptr, "tw_device_count -> %d", n);
+    return n;
+}
 // TW_STUB_PCI="0000:01:00.0,0000:81:00.0,...": bus id of pretend device i (cycled); unset: "0000:<i>0:00.0"
 tw_status tw_device_pci_bus_id(int device, char* buf, int cap)
 {
-    if (!buf || cap < 16 || device < 0 || device >= tw_device_count()) return TW_E_DEVICE;
+    if (tracing()) trace(nullptr, "tw_device_pci_bus_id device=%d", device);
+    if (!buf || cap < 16 || device < 0 || device >= stub_device_count()) return TW_E_DEVICE;
     const char* ev = getenv("TW_STUB_PCI");
     if (ev && ev[0]) {
         std::string s(ev);
@@ -117,20 +237,50 @@ tw_status tw_device_pci_bus_id(int device, char* buf, int cap)
     }
     return TW_OK;
 }
-tw_status tw_host_alloc(tw_engine*, size_t bytes, void** hptr)
+tw_status tw_host_alloc(tw_engine* e, size_t bytes, void** hptr)
 {
     *hptr = malloc(bytes);
+    if (tracing()) {
+        long ord = -1;
+        if (*hptr) {
+            std::lock_guard<std::mutex> lk(g_trace_m);
+            ord = g_block_ordinal++;
+            g_blocks[(const uint8_t*)*hptr] = HostBlock{bytes, ord};
+        }
+        trace(e, "tw_host_alloc bytes=%zu -> %s block=%ld", bytes, *hptr ? "OK" : "NOMEM", ord);
+    }
     return *hptr ? TW_OK : TW_E_NOMEM;
 }
-tw_status tw_host_free(tw_engine*, void* hptr)
+tw_status tw_host_free(tw_engine* e, void* hptr)
 {
+    if (tracing()) {
+        long ord = -1;
+        {
+            std::lock_guard<std::mutex> lk(g_trace_m);
+            auto it = g_blocks.find((const uint8_t*)hptr);
+            if (it != g_blocks.end()) {
+                ord = it->second.ordinal;
+                g_blocks.erase(it);
+            }
+        }
+        trace(e, "tw_host_free block=%ld -> OK", ord);
+    }
     free(hptr);
     return TW_OK;
 }
-tw_status tw_set_option(tw_engine*, int, int) { return TW_OK; }
-tw_status tw_prof_select(tw_engine*, int, int) { return TW_OK; }
-tw_status tw_prof_read(tw_engine*, int, double* ms, int* n)
+tw_status tw_set_option(tw_engine* e, int option, int value)
 {
+    if (tracing()) trace(e, "tw_set_option option=%d value=%d -> OK", option, value);
+    return TW_OK;
+}
+tw_status tw_prof_select(tw_engine* e, int kernel, int level)
+{
+    if (tracing()) trace(e, "tw_prof_select kernel=%d level=%d -> OK", kernel, level);
+    return TW_OK;
+}
+tw_status tw_prof_read(tw_engine* e, int kernel, double* ms, int* n)
+{
+    if (tracing()) trace(e, "tw_prof_read kernel=%d -> OK", kernel);
     if (ms) *ms = 0;
     if (n) *n = 0;
     return TW_OK;
@@ -153,23 +303,37 @@ void tw_stub_resident_calls(long* kept, long* image_pairs, long* released)
     *image_pairs = g_res_image_pairs;
     *released = g_res_released;
 }
-int tw_grid_capacity(int w, int h, int span) { return span > 0 ? ((h + span - 1) / span) * ((w + span - 1) / span) : 0; }
-tw_status tw_engine_create(int device, const tw_params*, int slots, tw_engine** out)
+int tw_grid_capacity(int w, int h, int span)
+{
+    const int cap = span > 0 ? ((h + span - 1) / span) * ((w + span - 1) / span) : 0;
+    if (tracing()) trace(nullptr, "tw_grid_capacity %dx%d span=%d -> %d", w, h, span, cap);
+    return cap;
+}
+tw_status tw_engine_create(int device, const tw_params* p, int slots, tw_engine** out)
 {
     tw_engine* e = new tw_engine();
     e->device = device;
     e->cap = slots;
     if (const char* ev = getenv("TW_STUB_BATCH_MS")) e->batch_ms = atof(ev);
+    if (const char* ev = getenv("TW_STUB_BUSY_AT")) e->busy_at = atoi(ev);
     g_engines++;
     *out = e;
+    if (tracing())
+        trace(e, "tw_engine_create slots=%d pyrScale=%g pyrLevels=%d winSize=%d pyrIterations=%d polyN=%d polySigma=%g flags=%d -> OK",
+              slots, (double)p->pyrScale, (int)p->pyrLevels, (int)p->winSize, (int)p->pyrIterations, (int)p->polyN,
+              (double)p->polySigma, (int)p->flags);
     return TW_OK;
 }
 void tw_engine_destroy(tw_engine* e)
 {
+    if (tracing()) trace(e, "tw_engine_destroy");
     g_engines--;
     delete e;
 }
-tw_status tw_submit_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w, int h, ptrdiff_t, int, double, tw_ticket* t)
+}  // extern "C"
+
+// What the entry points do once a call is recorded (and not refused by TW_STUB_BUSY_AT): they call one another through these
+static tw_status stub_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w, int h, tw_ticket* t)
 {
     if (!a || !b || w < 1 || h < 1) return TW_E_BAD_PARAMETER;
     std::lock_guard<std::mutex> lk(e->m);
@@ -182,30 +346,22 @@ tw_status tw_submit_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w, 
     }
     return TW_OK;
 }
-tw_status tw_submit_png8(tw_engine* e, const uint8_t* a, int cha, const uint8_t* b, int chb, int w, int h, int span, double thr,
-                         tw_ticket* t)
+// filtered rows: byte 0 is a filter type, byte 1 the first sample — compare those like tw_submit_u8 compares pixel 0
+static tw_status stub_png8(tw_engine* e, const uint8_t* a, int cha, const uint8_t* b, int chb, int w, int h, tw_ticket* t)
 {
-    // filtered rows: byte 0 is a filter type, byte 1 the first sample — compare those like tw_submit_u8 compares pixel 0
-    return tw_submit_u8(e, a + (cha ? 1 : 0), b + (chb ? 1 : 0), w, h, w, span, thr, t);
+    return stub_u8(e, a + (cha ? 1 : 0), b + (chb ? 1 : 0), w, h, t);
 }
 // the _sized calls: OpticalFlow::calculate's size rule, then what tw_submit_u8 / tw_submit_png8 do
 static bool stub_sizes_match(int w, int h, int tw, int th) { return abs(w - tw) <= 5 && abs(h - th) <= 5; }
-tw_status tw_submit_u8_sized(tw_engine* e, const uint8_t* a, int w, int h, ptrdiff_t stride, const uint8_t* b, int tw, int th,
-                             ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
+static tw_status stub_u8_sized(tw_engine* e, const uint8_t* a, int w, int h, const uint8_t* b, int tw, int th, ptrdiff_t tstride,
+                               tw_ticket* t)
 {
     if (tw < 1 || th < 1 || tstride < tw) return TW_E_BAD_PARAMETER;
     if (!stub_sizes_match(w, h, tw, th)) return TW_E_DONT_MATCH_SIZE;
-    return tw_submit_u8(e, a, b, w, h, stride, span, thr, t);
-}
-tw_status tw_submit_png8_sized(tw_engine* e, const uint8_t* a, int cha, int w, int h, const uint8_t* b, int chb, int tw, int th,
-                               int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
-{
-    if (tw < 1 || th < 1) return TW_E_BAD_PARAMETER;
-    if (!stub_sizes_match(w, h, tw, th)) return TW_E_DONT_MATCH_SIZE;
-    return tw_submit_png8(e, a, cha, b, chb, w, h, span, thr, t);
+    return stub_u8(e, a, b, w, h, t);
 }
 // the same table as the library's
-int tw_png_on_device(int color_type, int bit_depth, int interlace)
+extern "C" int tw_png_on_device(int color_type, int bit_depth, int interlace)
 {
     if (interlace != 0) return 0;
     switch (color_type) {
@@ -219,8 +375,7 @@ int tw_png_on_device(int color_type, int bit_depth, int interlace)
 }
 // tw_submit_png: each image is finished to gray with the host layer's own code, then the pair is what tw_submit_u8 sees.
 // A palette index without an entry is remembered for the ticket: tw_wait answers it, as the engine's does.
-tw_status tw_submit_png(tw_engine* e, const tw_png_rows* a, const tw_png_rows* b, int span, double thr, const tw_flow_in*,
-                        const tw_flow_out*, tw_ticket* t)
+static tw_status stub_png(tw_engine* e, const tw_png_rows* a, const tw_png_rows* b, tw_ticket* t)
 {
     if (!a || !b || !a->rows || !b->rows) return TW_E_BAD_PARAMETER;
     if (!stub_sizes_match(a->width, a->height, b->width, b->height)) return TW_E_DONT_MATCH_SIZE;
@@ -249,7 +404,7 @@ tw_status tw_submit_png(tw_engine* e, const tw_png_rows* a, const tw_png_rows* b
         }
         first[q] = g[0];
     }
-    const tw_status r = tw_submit_u8(e, &first[0], &first[1], a->width, a->height, a->width, span, thr, t);
+    const tw_status r = stub_u8(e, &first[0], &first[1], a->width, a->height, t);
     if (r == TW_OK && bad) {
         std::lock_guard<std::mutex> lk(e->m);
         e->bad[*t] = bad;
@@ -258,8 +413,7 @@ tw_status tw_submit_png(tw_engine* e, const tw_png_rows* a, const tw_png_rows* b
 }
 // tw_submit_jpeg: the first gray pixel of a coefficient image is the host layer's own inverse DCT of its block 0, then the
 // pair is what tw_submit_u8 sees
-tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* a, const tw_jpeg_luma* b, int span, double thr, const tw_flow_in*,
-                         const tw_flow_out*, tw_ticket* t)
+static tw_status stub_jpeg(tw_engine* e, const tw_jpeg_luma* a, const tw_jpeg_luma* b, tw_ticket* t)
 {
     const tw_jpeg_luma* im[2] = {a, b};
     for (int q = 0; q < 2; q++) {
@@ -286,31 +440,123 @@ tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* a, const tw_jpeg_luma
         twhost::jpeg_luma_to_gray(l, g);
         first[q] = g[0];
     }
-    return tw_submit_u8(e, &first[0], &first[1], a->width, a->height, a->width, span, thr, t);
+    return stub_u8(e, &first[0], &first[1], a->width, a->height, t);
+}
+
+extern "C" {
+// every submit: refused once by TW_STUB_BUSY_AT or handed on, then recorded with its ticket
+#define STUB_SUBMIT(call) (busy_now(e) ? TW_E_BUSY : (call))
+static void trace_submit(tw_engine* e, const char* name, const std::string& images, int span, double thr, tw_status r, const tw_ticket* t)
+{
+    trace(e, "%s %s span=%d threshold=%g -> %s ticket=%lld", name, images.c_str(), span, thr, status_name(r),
+          r == TW_OK ? (long long)*t : -1LL);
+}
+tw_status tw_submit_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w, int h, ptrdiff_t stride, int span, double thr,
+                       tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(stub_u8(e, a, b, w, h, t));
+    if (tracing()) {
+        char sz[64];
+        snprintf(sz, sizeof(sz), "[%dx%d stride=%td ", w, h, stride);  // (one size and stride for both images)
+        const size_t rows = h > 0 ? (size_t)h : 0, rb = w > 0 ? (size_t)w : 0;
+        trace_submit(e, "tw_submit_u8", "a=" + (sz + bytes_seen(a, rows, rb, stride)) + "] b=" + (sz + bytes_seen(b, rows, rb, stride)) + "]",
+                     span, thr, r, t);
+    }
+    return r;
+}
+tw_status tw_submit_png8(tw_engine* e, const uint8_t* a, int cha, const uint8_t* b, int chb, int w, int h, int span, double thr,
+                         tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(stub_png8(e, a, cha, b, chb, w, h, t));
+    if (tracing()) {
+        char sz[64];
+        snprintf(sz, sizeof(sz), "%dx%d cha=%d chb=%d", w, h, cha, chb);
+        const size_t rows = h > 0 ? (size_t)h : 0, ra = (size_t)(cha ? 1 + w * cha : w), rb = (size_t)(chb ? 1 + w * chb : w);
+        trace_submit(e, "tw_submit_png8", std::string(sz) + " a=[" + bytes_seen(a, rows, ra, (ptrdiff_t)ra) + "] b=[" + bytes_seen(b, rows, rb, (ptrdiff_t)rb) + "]",
+                     span, thr, r, t);
+    }
+    return r;
+}
+tw_status tw_submit_u8_sized(tw_engine* e, const uint8_t* a, int w, int h, ptrdiff_t stride, const uint8_t* b, int tw, int th,
+                             ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(stub_u8_sized(e, a, w, h, b, tw, th, tstride, t));
+    if (tracing()) {
+        char sa[64], sb[64];
+        snprintf(sa, sizeof(sa), "a=[%dx%d stride=%td ", w, h, stride);
+        snprintf(sb, sizeof(sb), "] b=[%dx%d stride=%td ", tw, th, tstride);
+        trace_submit(e, "tw_submit_u8_sized", sa + bytes_seen(a, h > 0 ? (size_t)h : 0, w > 0 ? (size_t)w : 0, stride) + sb +
+                     bytes_seen(b, th > 0 ? (size_t)th : 0, tw > 0 ? (size_t)tw : 0, tstride) + "]", span, thr, r, t);
+    }
+    return r;
+}
+tw_status tw_submit_png8_sized(tw_engine* e, const uint8_t* a, int cha, int w, int h, const uint8_t* b, int chb, int tw, int th,
+                               int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(tw < 1 || th < 1 ? TW_E_BAD_PARAMETER : !stub_sizes_match(w, h, tw, th) ? TW_E_DONT_MATCH_SIZE
+                                                                          : stub_png8(e, a, cha, b, chb, w, h, t));
+    if (tracing()) {
+        char sa[64], sb[64];
+        snprintf(sa, sizeof(sa), "a=[%dx%d ch=%d ", w, h, cha);
+        snprintf(sb, sizeof(sb), "] b=[%dx%d ch=%d ", tw, th, chb);
+        const size_t ra = (size_t)(cha ? 1 + w * cha : w), rb = (size_t)(chb ? 1 + tw * chb : tw);
+        trace_submit(e, "tw_submit_png8_sized", sa + bytes_seen(a, h > 0 ? (size_t)h : 0, ra, (ptrdiff_t)ra) + sb +
+                     bytes_seen(b, th > 0 ? (size_t)th : 0, rb, (ptrdiff_t)rb) + "]", span, thr, r, t);
+    }
+    return r;
+}
+tw_status tw_submit_png(tw_engine* e, const tw_png_rows* a, const tw_png_rows* b, int span, double thr, const tw_flow_in*,
+                        const tw_flow_out*, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(stub_png(e, a, b, t));
+    if (tracing()) trace_submit(e, "tw_submit_png", "a=[" + rows_seen(a) + "] b=[" + rows_seen(b) + "]", span, thr, r, t);
+    return r;
+}
+tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* a, const tw_jpeg_luma* b, int span, double thr, const tw_flow_in*,
+                         const tw_flow_out*, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(stub_jpeg(e, a, b, t));
+    if (tracing()) trace_submit(e, "tw_submit_jpeg", "a=[" + luma_seen(a) + "] b=[" + luma_seen(b) + "]", span, thr, r, t);
+    return r;
 }
 // Resident images: the first gray pixel of the pair's image as tw_submit_u8 saw it (a palette image the finisher refused
 // has pixel 0 = 0: undefined content, as the engine's header says)
-tw_status tw_image_keep(tw_engine* e, tw_ticket t, int which, tw_image** out)
+static tw_status stub_image_keep(tw_engine* e, tw_ticket t, int which, tw_image** out)
 {
     if (!e || !out) return TW_E_BAD_PARAMETER;
     *out = nullptr;
     std::lock_guard<std::mutex> lk(e->m);
     auto it = e->info.find(t);
     if (it == e->info.end() || which < 0 || which > 1) return TW_E_BAD_PARAMETER;
-    *out = (tw_image*)g_next_image.fetch_add(16);
+    *out = (tw_image*)g_next_image.fetch_add(kImageStep);
     e->images[*out] = tw_image{it->second.w, it->second.h, it->second.first[which]};
     g_res_kept++;
     return TW_OK;
 }
-tw_status tw_image_create_u8(tw_engine* e, const uint8_t* gray, int w, int h, ptrdiff_t stride, tw_image** out)
+tw_status tw_image_keep(tw_engine* e, tw_ticket t, int which, tw_image** out)
+{
+    const tw_status r = stub_image_keep(e, t, which, out);
+    if (tracing()) trace(e, "tw_image_keep ticket=%lld which=%d -> %s image=%ld", (long long)t, which, status_name(r), out ? image_ordinal(*out) : -1L);
+    return r;
+}
+static tw_status stub_image_create_u8(tw_engine* e, const uint8_t* gray, int w, int h, ptrdiff_t stride, tw_image** out)
 {
     if (!e || !out || !gray || w < 1 || h < 1 || stride < w) return TW_E_BAD_PARAMETER;
     std::lock_guard<std::mutex> lk(e->m);
-    *out = (tw_image*)g_next_image.fetch_add(16);
+    *out = (tw_image*)g_next_image.fetch_add(kImageStep);
     e->images[*out] = tw_image{w, h, gray[0]};
     return TW_OK;
 }
-tw_status tw_image_release(tw_engine* e, tw_image* img)
+tw_status tw_image_create_u8(tw_engine* e, const uint8_t* gray, int w, int h, ptrdiff_t stride, tw_image** out)
+{
+    const tw_status r = stub_image_create_u8(e, gray, w, h, stride, out);
+    if (tracing())
+        trace(e, "tw_image_create_u8 %dx%d stride=%td [%s] -> %s image=%ld", w, h, stride,
+              bytes_seen(gray, h > 0 ? (size_t)h : 0, w > 0 ? (size_t)w : 0, stride).c_str(), status_name(r),
+              r == TW_OK ? image_ordinal(*out) : -1L);
+    return r;
+}
+static tw_status stub_image_release(tw_engine* e, tw_image* img)
 {
     if (!e) return TW_E_BAD_PARAMETER;
     std::lock_guard<std::mutex> lk(e->m);
@@ -318,8 +564,15 @@ tw_status tw_image_release(tw_engine* e, tw_image* img)
     g_res_released++;
     return TW_OK;
 }
+tw_status tw_image_release(tw_engine* e, tw_image* img)
+{
+    const tw_status r = stub_image_release(e, img);
+    if (tracing()) trace(e, "tw_image_release image=%ld -> %s", image_ordinal(img), status_name(r));
+    return r;
+}
 tw_status tw_image_size(const tw_engine* e, const tw_image* img, int* w, int* h)
 {
+    if (tracing()) trace(e, "tw_image_size image=%ld", image_ordinal(img));
     if (!e) return TW_E_BAD_PARAMETER;
     std::lock_guard<std::mutex> lk(const_cast<tw_engine*>(e)->m);
     auto it = e->images.find(img);
@@ -338,8 +591,7 @@ static bool stub_image_pixel(tw_engine* e, const tw_image* img, tw_image* copy)
     *copy = it->second;
     return true;
 }
-tw_status tw_submit_image_png(tw_engine* e, const tw_image* img, const tw_png_rows* b, int span, double thr, const tw_flow_in* fi,
-                              const tw_flow_out* fo, tw_ticket* t)
+static tw_status stub_image_png(tw_engine* e, const tw_image* img, const tw_png_rows* b, tw_ticket* t)
 {
     tw_image im;
     if (!stub_image_pixel(e, img, &im)) return TW_E_BAD_PARAMETER;
@@ -351,12 +603,19 @@ tw_status tw_submit_image_png(tw_engine* e, const tw_image* img, const tw_png_ro
     a.bit_depth = 8;
     a.palette = nullptr;
     a.palette_entries = 0;
-    const tw_status r = tw_submit_png(e, &a, b, span, thr, fi, fo, t);
+    const tw_status r = stub_png(e, &a, b, t);
     if (r == TW_OK) g_res_image_pairs++;
     return r;
 }
-tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* img, const tw_jpeg_luma* b, int span, double thr, const tw_flow_in* fi,
-                               const tw_flow_out* fo, tw_ticket* t)
+tw_status tw_submit_image_png(tw_engine* e, const tw_image* img, const tw_png_rows* b, int span, double thr, const tw_flow_in*,
+                              const tw_flow_out*, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(stub_image_png(e, img, b, t));
+    if (tracing())
+        trace_submit(e, "tw_submit_image_png", "image=" + std::to_string(image_ordinal(img)) + " b=[" + rows_seen(b) + "]", span, thr, r, t);
+    return r;
+}
+static tw_status stub_image_jpeg(tw_engine* e, const tw_image* img, const tw_jpeg_luma* b, tw_ticket* t)
 {
     tw_image im;
     if (!stub_image_pixel(e, img, &im)) return TW_E_BAD_PARAMETER;
@@ -365,25 +624,40 @@ tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* img, const tw_jpeg_
     a.gray = &im.first;
     a.width = im.w;
     a.height = im.h;
-    const tw_status r = tw_submit_jpeg(e, &a, b, span, thr, fi, fo, t);
+    const tw_status r = stub_jpeg(e, &a, b, t);
     if (r == TW_OK) g_res_image_pairs++;
+    return r;
+}
+tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* img, const tw_jpeg_luma* b, int span, double thr, const tw_flow_in*,
+                               const tw_flow_out*, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(stub_image_jpeg(e, img, b, t));
+    if (tracing())
+        trace_submit(e, "tw_submit_image_jpeg", "image=" + std::to_string(image_ordinal(img)) + " b=[" + luma_seen(b) + "]", span, thr, r, t);
     return r;
 }
 tw_status tw_submit_dev_sized(tw_engine* e, const void* a, int w, int h, ptrdiff_t stride, const void* b, int tw, int th,
                               ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
 {
     // (the stub's "device memory" is host memory: tw_submit_u8 reads pixel 0 of both)
-    return tw_submit_u8_sized(e, (const uint8_t*)a, w, h, stride, (const uint8_t*)b, tw, th, tstride, span, thr, nullptr, nullptr, t);
+    const tw_status r = STUB_SUBMIT(stub_u8_sized(e, (const uint8_t*)a, w, h, (const uint8_t*)b, tw, th, tstride, t));
+    if (tracing()) {
+        char sz[128];
+        snprintf(sz, sizeof(sz), "a=[%dx%d stride=%td] b=[%dx%d stride=%td]", w, h, stride, tw, th, tstride);
+        trace_submit(e, "tw_submit_dev_sized", sz, span, thr, r, t);
+    }
+    return r;
 }
 tw_status tw_flush(tw_engine* e)
 {
+    if (tracing()) trace(e, "tw_flush -> OK");
     if (e->batch_ms > 0) {
         std::lock_guard<std::mutex> lk(e->m);
         e->launch_locked();
     }
     return TW_OK;
 }
-tw_status tw_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, int* n, float* seconds)
+static tw_status stub_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, int* n, float* seconds)
 {
     int w;
     {
@@ -430,5 +704,13 @@ tw_status tw_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, int* n, fl
     }
     if (seconds) *seconds = 1e-4f;
     return TW_OK;
+}
+tw_status tw_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, int* n, float* seconds)
+{
+    int count = 0;
+    const tw_status r = stub_wait(e, t, out, cap, &count, seconds);
+    if (n) *n = count;
+    if (tracing()) trace(e, "tw_wait ticket=%lld cap=%d -> %s count=%d", (long long)t, cap, status_name(r), count);
+    return r;
 }
 }

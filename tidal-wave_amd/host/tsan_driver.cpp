@@ -1,8 +1,9 @@
 // tsan_driver.cpp — drives twhost::Manager (8 consumers on the stub backend of stub_twflow.cpp) under
 // ThreadSanitizer: 1 000 in-memory jobs from two producer threads, a few bad requests, then a second manager that is
-// disposed while its consumers are busy.  The reference's hazards this replaces: unsynchronised isRunning flags
-// (/root/reference/src/message_queue.h:94-96, src/consumer.h:47, src/manager.h:63).  Exit code 0 and no TSAN
-// report = pass (tests/test_host_tsan.py).
+// disposed while its consumers are busy; with a directory of files, those files through the decode pool, and once more with
+// resident expected images on.  The reference's hazards this replaces: unsynchronised isRunning flags
+// (src/message_queue.h:94-96, src/consumer.h:47, src/manager.h:63).  Exit code 0 and no TSAN
+// report = pass (tests/test_host_queue.py::test_host_layer_under_thread_sanitizer).
 #include <stdio.h>
 
 #include <chrono>
@@ -15,6 +16,7 @@
 #include "twhost.h"
 
 using namespace twhost;
+extern "C" void tw_stub_resident_calls(long* kept, long* image_pairs, long* released);
 
 struct Sink {
     std::mutex m;
@@ -129,7 +131,9 @@ int main(int argc, char** argv)
         delete mg;
         if (s.rep.requestCount != 4000 || s.data > 4000) { fprintf(stderr, "dispose: report %d, data %ld\n", s.rep.requestCount, s.data); rc = 1; }
     }
-    if (argc > 1) {
+    // resident == 1: the same with Parameter::residentMB = 1 — e.png is the expected image of every pair, so cache hits,
+    // the pair that keeps the image and the pairs behind it all occur, on four consumers with a cache each
+    for (int resident = 0; resident < 2 && argc > 1; resident++) {
         // FILES through the decode pool (round 4): argv[1] holds e.png / t.png (same size, first pixel differs), t5.png
         // (3 px narrower: the size-reconcile path), pal.png (palette: decoded on the host) and bad.png (damaged).  Batches
         // of pairs the device can finish are inflated straight into the page-locked arena (the fast path); a batch with
@@ -139,6 +143,7 @@ int main(int argc, char** argv)
         Parameter pf = p;
         pf.numThreads = 4;
         pf.batch = 8;
+        pf.residentMB = resident;
         Manager* mg = new Manager(observer(s));
         mg->start(pf);
         const int N = 400;
@@ -162,8 +167,15 @@ int main(int argc, char** argv)
         }
         delete mg;
         if (s.err != want_err || s.data != N - want_err || s.hits < want_hits_min) {
-            fprintf(stderr, "files: data %ld err %ld hits %ld (want %d %d >= %ld)\n", s.data, s.err, s.hits, N - want_err,
-                    want_err, want_hits_min);
+            fprintf(stderr, "files%s: data %ld err %ld hits %ld (want %d %d >= %ld)\n", resident ? " (resident)" : "", s.data, s.err,
+                    s.hits, N - want_err, want_err, want_hits_min);
+            rc = 1;
+        }
+        long kept = 0, image_pairs = 0, released = 0;
+        tw_stub_resident_calls(&kept, &image_pairs, &released);
+        if (kept != released || (resident ? kept < 1 || image_pairs < 1 : kept != 0)) {
+            fprintf(stderr, "files%s: kept %ld, pairs against an image %ld, released %ld\n", resident ? " (resident)" : "", kept,
+                    image_pairs, released);
             rc = 1;
         }
     }

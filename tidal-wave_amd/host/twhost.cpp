@@ -1,6 +1,7 @@
 // twhost.cpp — see twhost.h.  Host-side only: file decode, size reconcile, queueing.  All pixel arithmetic of
 // the hot path happens in libtwflow.so (HIP); there is no CPU flow implementation here.
 #include "twhost.h"
+#include "resident_cache.h"
 #include "tw_inflate.h"
 
 #include <math.h>
@@ -741,21 +742,36 @@ inline long long steady_ns()
 {
     return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+// cv::imread failed on `path` (src/opticalflow.cpp:40,47)
+inline std::string cant_open(const std::string& path) { return "Can't open " + path; }
+// a refused submit or wait: the engine's own words, else the status's
+inline std::string engine_error(const tw_engine* eng, tw_status r)
+{
+    return std::string(tw_last_error(eng)[0] ? tw_last_error(eng) : tw_strerror(r));
+}
+
+// on(): an image's bytes are a JPEG's quantised luma coefficients, bw * bh blocks of 64 int16 (the device runs the inverse
+// DCT: tw_submit_jpeg)
+struct JpegHead {
+    int bw = 0, bh = 0;
+    uint16_t quant[64] = {0};
+    bool on() const { return bw > 0; }
+};
 struct Staged {
     Request req;
-    std::vector<uint8_t> a, b;
-    const uint8_t *pa = nullptr, *pb = nullptr;  // the pair as handed to the engine (a/b or the caller's raw buffers)
+    // One image of the pair: [0] the expected image, [1] the target
+    struct Side {
+        std::vector<uint8_t> bytes;  // the image where the host layer holds it itself (not in the arena, not the caller's)
+        const uint8_t* p = nullptr;  // the image as handed to the engine (bytes, an arena slot or the caller's raw buffer)
+        int w = 0, h = 0;            // the image's own size
+        PngKind kind;                // rows(): filtered PNG rows of that kind (the device finishes them: tw_submit_png)
+        JpegHead jpeg;
+        std::string err;             // why it could not be opened
+    } side[2];
+    const std::string& path(int which) const { return which ? req.target_image : req.expect_image; }
     ptrdiff_t stride = 0;
-    int w = 0, h = 0;
-    PngKind ka, kb;        // rows(): a / b hold filtered PNG rows of that kind (the device finishes them: tw_submit_png)
-    // on(): a / b hold a JPEG's quantised luma coefficients, bw * bh blocks of 64 int16 (the device runs the inverse DCT:
-    // tw_submit_jpeg)
-    struct JpegHead {
-        int bw = 0, bh = 0;
-        uint16_t quant[64] = {0};
-        bool on() const { return bw > 0; }
-    } ja, jb;
-    int tw = 0, th = 0;    // the target's own size when the device reconciles it (tw_submit_*_sized); 0: the pair's size
+    int w = 0, h = 0;                // the pair's size: the expected image's
+    bool device_reconciles = false;  // the target goes up in its own size and the device resizes it (tw_submit_*_sized)
     std::string err;
     tw_ticket ticket = 0;
     bool submitted = false;
@@ -764,212 +780,319 @@ struct Staged {
     // cache entry whose image stands in for the file (pinned until the pair is submitted); keep: the image this pair's
     // expected file becomes — kept by the pair that decoded it (kept), used by the pairs behind it that name the same file
     // (uses_keep) while that pair has not answered; leader: that pair when it sits in this very batch (index before the sort)
-    struct ResEntry;
-    struct Keep {
-        tw_image* img = nullptr;
-        int w = 0, h = 0;
-        bool expect_bad = false;  // the pair that kept it answered "Can't open <expected>": its content is undefined
-    };
     std::string rkey;
-    ResEntry* hit = nullptr;
-    std::shared_ptr<Keep> keep;
+    ResidentCache::Entry* hit = nullptr;
+    std::shared_ptr<ResidentCache::Keep> keep;
     int leader = -1;
     bool follower = false, uses_keep = false;
     tw_image* kept = nullptr;
     bool no_expected_file() const { return hit || follower; }
 };
-// One resident expected image of a consumer's cache: an LRU by bytes under the budget
-struct Staged::ResEntry {
-    std::string key;
-    std::vector<std::string> paths;  // every path it was asked for under (hard links share an entry)
-    tw_image* img = nullptr;
-    int w = 0, h = 0;
-    size_t bytes = 0;
-    int pins = 0;  // pairs that looked it up and are not submitted yet
-    std::list<ResEntry*>::iterator lru;
-};
 
-// dev:ino:size:mtime(ns) of a file — what tells a rewritten baseline from the cached one ("" : no such file)
-std::string file_identity(const std::string& path)
-{
-    struct stat st;
-    if (stat(path.c_str(), &st) != 0) return std::string();
-    char buf[160];
-    snprintf(buf, sizeof(buf), "%llx:%llx:%lld:%lld.%09ld", (unsigned long long)st.st_dev, (unsigned long long)st.st_ino,
-             (long long)st.st_size, (long long)st.st_mtim.tv_sec, (long)st.st_mtim.tv_nsec);
-    return buf;
-}
-
-// the rest of a JPEG's decode on the host (what the device does for tw_submit_jpeg): `bytes` from coefficients to gray
-void finish_jpeg_on_host(std::vector<uint8_t>& bytes, Staged::JpegHead& head, int w, int h)
+// the rest of a JPEG's decode on the host (what the device does for tw_submit_jpeg): the side from coefficients to gray
+void finish_jpeg_on_host(Staged::Side& sd)
 {
     JpegLuma l;
-    l.w = w;
-    l.h = h;
-    l.bw = head.bw;
-    l.bh = head.bh;
-    memcpy(l.quant, head.quant, sizeof(l.quant));
-    l.coef.resize(bytes.size() / 2);
-    memcpy(l.coef.data(), bytes.data(), l.coef.size() * 2);
-    jpeg_luma_to_gray(l, bytes);
-    head = Staged::JpegHead();
+    l.w = sd.w;
+    l.h = sd.h;
+    l.bw = sd.jpeg.bw;
+    l.bh = sd.jpeg.bh;
+    memcpy(l.quant, sd.jpeg.quant, sizeof(l.quant));
+    l.coef.resize(sd.bytes.size() / 2);
+    memcpy(l.coef.data(), sd.bytes.data(), l.coef.size() * 2);
+    jpeg_luma_to_gray(l, sd.bytes);
+    sd.jpeg = JpegHead();
 }
 
-// the two imreads of a pair are independent: the decode pool runs them as separate tasks (task = 2 * job + image)
-// (`file`: the bytes of the file when the caller has read it already, else null)
-// (device_jpeg: a JPEG stops at its coefficient plane — Staged::ja / jb — and the device runs the inverse DCT)
-void decode_one(Staged& s, int which, int* tw, int* th, std::string* err, bool device_png, bool png_kinds, bool device_jpeg,
-                const std::vector<uint8_t>* file)
-{
-    if (s.req.raw.expect) return;
-    if (which == 0 && s.no_expected_file()) return;  // (a resident image stands in for the file)
-    const std::string& path = which == 0 ? s.req.expect_image : s.req.target_image;
-    if (path.empty()) { *err = which == 0 ? "ExpectImagePath is empty." : "TargetImagePath is empty."; return; }
-    std::vector<uint8_t>& img = which == 0 ? s.a : s.b;
-    int& w = which == 0 ? s.w : *tw;
-    int& h = which == 0 ? s.h : *th;
-    PngKind& kind = which == 0 ? s.ka : s.kb;
-    if (device_jpeg && file && file->size() >= 8 && (*file)[0] == 0xFF && (*file)[1] == 0xD8) {
-        JpegLuma l;
-        if (!decode_jpeg_luma(file->data(), file->size(), l)) {
-            *err = "Can't open " + path;
-            return;
-        }
-        Staged::JpegHead& head = which == 0 ? s.ja : s.jb;
-        w = l.w;
-        h = l.h;
-        head.bw = l.bw;
-        head.bh = l.bh;
-        memcpy(head.quant, l.quant, sizeof(head.quant));
-        img.resize(l.coef.size() * 2);
-        memcpy(img.data(), l.coef.data(), img.size());
-        return;
-    }
-    const bool ok = file ? decode_gray_or_png_kind_rows(*file, device_png, png_kinds, img, w, h, kind)
-                         : load_gray_or_png_kind_rows(path, device_png, png_kinds, img, w, h, kind);
-    if (!ok) *err = "Can't open " + path;
-}
-
-// OpticalFlow::calculate up to (not including) calculateInternal: src/opticalflow.cpp:20-68
-void prepare(Staged& s, int tw, int th, const std::string& err_a, const std::string& err_b, bool device_reconcile)
-{
-    if (s.req.raw.expect) {  // in-memory pair: nothing to decode
-        const RawPair& r = s.req.raw;
-        if (!r.target || r.width < 1 || r.height < 1 || r.stride < r.width) { s.err = "bad raw image pair"; return; }
-        s.pa = r.expect;
-        s.pb = r.target;
-        s.w = r.width;
-        s.h = r.height;
-        s.stride = r.stride;
-        return;
-    }
-    // the reference checks and opens the expected image first (src/opticalflow.cpp:26-48): its error wins
-    if (s.req.expect_image.empty()) { s.err = "ExpectImagePath is empty."; return; }
-    if (s.req.target_image.empty()) { s.err = "TargetImagePath is empty."; return; }
-    if (!err_a.empty()) { s.err = err_a; return; }
-    if (!err_b.empty()) { s.err = err_b; return; }
-    if (abs(s.h - th) > 5 || abs(s.w - tw) > 5) { s.err = "Don't match image size"; return; }
-    // a JPEG beside half-decoded PNG rows (index.js pairs files by relative path: a corner): tw_submit_png takes rows and
-    // gray images, so the JPEG is finished here; so is a JPEG target that the host is to resize
-    if (s.ja.on() && s.kb.rows()) finish_jpeg_on_host(s.a, s.ja, s.w, s.h);
-    if (s.jb.on() && (s.ka.rows() || ((s.h != th || s.w != tw) && !device_reconcile))) finish_jpeg_on_host(s.b, s.jb, tw, th);
-    if ((s.h != th || s.w != tw) && device_reconcile) {
-        // the <= 5 px reconcile on the device (tw_submit_*_sized): the target stays as it was decoded, filtered rows included
-        s.tw = tw;
-        s.th = th;
-    } else if (s.h != th || s.w != tw) {
-        // TW_DEVICE_RECONCILE=0: the reconcile resizes the TARGET's gray pixels here (src/opticalflow.cpp:64-68); a target
-        // that is still filtered PNG rows is finished on the host first (the expected image may stay as it is)
-        if (s.kb.rows()) {
-            std::vector<uint8_t> g;
-            if (s.b.size() != s.kb.row_bytes(tw) * (size_t)th || !finish_png_kind_on_host(s.b.data(), tw, th, s.kb, g)) {
-                s.err = "Can't open " + s.req.target_image;
-                return;
-            }
-            s.b.swap(g);
-            s.kb = PngKind();
-        }
-        std::vector<uint8_t> r;
-        resize_u8_linear(s.b, tw, th, r, s.w, s.h);
-        s.b.swap(r);
-    }
-    s.pa = s.a.data();
-    s.pb = s.b.data();
-    s.stride = s.w;
-}
-}  // namespace
-
-void Consumer::run()
-{
-    // device binding happens here, on the worker thread (the reference binds on the main thread:
-    // src/consumer.cpp:22 via src/manager.cpp:56 — SURVEY.md Appendix B#6)
-    const int ndev = tw_device_count();
-    const int dev = ndev > 0 ? id_ % ndev : -1;
-    ConsumerStats mine;  // this thread's own counters; published under the shared mutex
-    mine.id = id_;
-    mine.device = dev;
-    // NUMA placement BEFORE the engine exists: the thread — and with it the decode pool it spawns and, by first touch,
-    // the page-locked staging / result buffers tw_engine_create and tw_submit_u8 allocate — moves to the CPUs of the
-    // GPU's node, so that 8 consumers x ~16 GB/s of pinned H2D do not cross the socket link.  TW_NUMA=0 disables.
-    {
-        const char* ev = getenv("TW_NUMA");
-        const bool on = !ev || atoi(ev) != 0;
-        std::vector<int> cpus;
-        int node = -1;
-        if (dev >= 0 && numa_cpus_of_device(dev, &mine.pciBusId, &node, &cpus) && on && bind_this_thread(cpus))
-            mine.numaNode = node;
-        mine.cpus = this_thread_cpus();
-    }
+// The environment switches of a consumer, read once when it starts
+struct Switches {
+    bool numa;  // TW_NUMA=0: the consumer thread stays where it is
     // PNG scanline reconstruction + gray conversion on the device (tw_submit_png8): the decode pool only inflates.
     // TW_DEVICE_PNG=0 keeps the whole decode on the host (A/B switch; same bytes either way).
-    bool device_png = true;
-    if (const char* ev = getenv("TW_DEVICE_PNG")) device_png = atoi(ev) != 0;
+    bool device_png;
     // The <= 5 px size reconcile of OpticalFlow::calculate on the device (tw_submit_*_sized): an unequal pair stays where it
     // was decoded — page-locked arena, filtered rows — like every other pair.  TW_DEVICE_RECONCILE=0 keeps the host path
     // (finish_png_rows_on_host + resize_u8_linear on copies outside the arena): A/B switch and fallback, same bytes.
-    bool device_reconcile = true;
-    if (const char* ev = getenv("TW_DEVICE_RECONCILE")) device_reconcile = atoi(ev) != 0;
+    bool device_reconcile;
     // Palette, 1- / 2- / 4-bit gray, 16-bit gray and 16-bit gray + alpha files on the device as well (tw_submit_png: whatever
     // tw_png_on_device admits), so that one such file no longer takes its whole batch off the arena path.
     // TW_DEVICE_PNG_KINDS=0 finishes those kinds on the host as before: A/B switch and fallback, same bytes.  The device
     // side measured faster (profiles/png_kinds.md: 1.77 x on a palette corpus, 1.39 x with one palette pair in 32).
-    bool png_kinds = true;
-    if (const char* ev = getenv("TW_DEVICE_PNG_KINDS")) png_kinds = atoi(ev) != 0;
+    bool png_kinds;
     // A JPEG's inverse DCT on the device (tw_submit_jpeg, where the engine exports it): the decode pool stops at the
     // coefficient plane.  TW_DEVICE_JPEG=0 keeps the whole decode on the host: A/B switch and fallback, same bytes
     // (profiles/jpeg_device.md has the measurement behind the default).
-    bool device_jpeg = kDeviceJpegDefault;
-    if (const char* ev = getenv("TW_DEVICE_JPEG")) device_jpeg = atoi(ev) != 0;
-    device_jpeg = device_jpeg && tw_submit_jpeg != nullptr;
+    bool device_jpeg;
+    bool scan_fused_final;  // TW_SCAN_FUSED_FINAL=1: the engine option of that name (create_engine)
+    long fair_slack;        // TW_FAIR_SLACK: pairs a consumer may hold beyond its fair share
+    bool debug_takes;       // TW_DEBUG_TAKES: diagnostic: who takes what, when
+    bool debug_batchtime;   // TW_DEBUG_BATCHTIME: diagnostic: where a batch's host time goes
+    static bool flag(const char* name, bool otherwise)
+    {
+        const char* ev = getenv(name);
+        return ev ? atoi(ev) != 0 : otherwise;
+    }
+    Switches()
+        : numa(flag("TW_NUMA", true)), device_png(flag("TW_DEVICE_PNG", true)), device_reconcile(flag("TW_DEVICE_RECONCILE", true)),
+          png_kinds(flag("TW_DEVICE_PNG_KINDS", true)), device_jpeg(flag("TW_DEVICE_JPEG", kDeviceJpegDefault)),
+          scan_fused_final(flag("TW_SCAN_FUSED_FINAL", false)), fair_slack(getenv("TW_FAIR_SLACK") ? atol(getenv("TW_FAIR_SLACK")) : 0),
+          debug_takes(getenv("TW_DEBUG_TAKES") != nullptr), debug_batchtime(getenv("TW_DEBUG_BATCHTIME") != nullptr)
+    {
+    }
+};
+
+// the two imreads of a pair are independent: the decode pool runs them as separate tasks (task = 2 * job + image), and
+// each writes s.side[which] and nothing else
+// (`file`: the bytes of the file when the caller has read it already, else null)
+// (device_jpeg: a JPEG stops at its coefficient plane — Side::jpeg — and the device runs the inverse DCT)
+void decode_one(Staged& s, int which, const Switches& sw, bool device_jpeg, const std::vector<uint8_t>* file)
+{
+    if (s.req.raw.expect) return;
+    if (which == 0 && s.no_expected_file()) return;  // (a resident image stands in for the file)
+    static const char* const kEmptyPath[2] = {"ExpectImagePath is empty.", "TargetImagePath is empty."};
+    Staged::Side& sd = s.side[which];
+    const std::string& path = s.path(which);
+    if (path.empty()) { sd.err = kEmptyPath[which]; return; }
+    if (device_jpeg && file && file->size() >= 8 && (*file)[0] == 0xFF && (*file)[1] == 0xD8) {
+        JpegLuma l;
+        if (!decode_jpeg_luma(file->data(), file->size(), l)) {
+            sd.err = cant_open(path);
+            return;
+        }
+        sd.w = l.w;
+        sd.h = l.h;
+        sd.jpeg.bw = l.bw;
+        sd.jpeg.bh = l.bh;
+        memcpy(sd.jpeg.quant, l.quant, sizeof(sd.jpeg.quant));
+        sd.bytes.resize(l.coef.size() * 2);
+        memcpy(sd.bytes.data(), l.coef.data(), sd.bytes.size());
+        return;
+    }
+    const bool ok = file ? decode_gray_or_png_kind_rows(*file, sw.device_png, sw.png_kinds, sd.bytes, sd.w, sd.h, sd.kind)
+                         : load_gray_or_png_kind_rows(path, sw.device_png, sw.png_kinds, sd.bytes, sd.w, sd.h, sd.kind);
+    if (!ok) sd.err = cant_open(path);
+}
+
+// What OpticalFlow::calculate does with a pair of these two sizes (src/opticalflow.cpp:50-68)
+enum class SizeRule {
+    Same,
+    DontMatch,          // more than 5 px apart: "Don't match image size"
+    ReconcileOnDevice,  // within 5 px: the target goes up as it was decoded (tw_submit_*_sized)
+    ReconcileOnHost     // TW_DEVICE_RECONCILE=0: the target's gray pixels are resized here
+};
+SizeRule size_rule(int w, int h, int tw, int th, bool device_reconcile)
+{
+    if (w == tw && h == th) return SizeRule::Same;
+    if (abs(h - th) > 5 || abs(w - tw) > 5) return SizeRule::DontMatch;
+    return device_reconcile ? SizeRule::ReconcileOnDevice : SizeRule::ReconcileOnHost;
+}
+
+// A pair behind the one that keeps its expected image, in the same batch: that one's size, and its failure to open the file
+void inherit_from_leader(Staged& s, const std::vector<Staged>& jobs)
+{
+    if (!s.follower || s.leader < 0) return;
+    const Staged::Side& le = jobs[(size_t)s.leader].side[0];
+    if (!le.err.empty()) s.side[0].err = cant_open(s.req.expect_image);
+    s.side[0].w = le.w;
+    s.side[0].h = le.h;
+}
+// the reference checks and opens the expected image first (src/opticalflow.cpp:26-48): its error wins.  true: s.err is set
+bool pair_refused(Staged& s)
+{
+    if (s.req.expect_image.empty()) s.err = "ExpectImagePath is empty.";
+    else if (s.req.target_image.empty()) s.err = "TargetImagePath is empty.";
+    else if (!s.side[0].err.empty()) s.err = s.side[0].err;
+    else if (!s.side[1].err.empty()) s.err = s.side[1].err;
+    return !s.err.empty();
+}
+
+// TW_DEVICE_RECONCILE=0: the reconcile resizes the TARGET's gray pixels here (src/opticalflow.cpp:64-68); a target that is
+// still filtered PNG rows is finished on the host first (the expected image may stay as it is).  Both images are in
+// Side::bytes.  false: s.err is set
+bool reconcile_on_host(Staged& s)
+{
+    Staged::Side& t = s.side[1];
+    if (t.kind.rows()) {
+        std::vector<uint8_t> g;
+        if (t.bytes.size() != t.kind.row_bytes(t.w) * (size_t)t.h || !finish_png_kind_on_host(t.bytes.data(), t.w, t.h, t.kind, g)) {
+            s.err = cant_open(s.req.target_image);
+            return false;
+        }
+        t.bytes.swap(g);
+        t.kind = PngKind();
+    }
+    std::vector<uint8_t> r;
+    resize_u8_linear(t.bytes, t.w, t.h, r, s.w, s.h);
+    t.bytes.swap(r);
+    t.w = s.w;
+    t.h = s.h;
+    return true;
+}
+void point_at_own_bytes(Staged& s)
+{
+    s.side[0].p = s.side[0].bytes.data();
+    s.side[1].p = s.side[1].bytes.data();
+    s.stride = s.w;
+}
+
+// OpticalFlow::calculate up to (not including) calculateInternal: src/opticalflow.cpp:20-68 — for a pair whose images
+// decode_one left in Side::bytes (or the caller's raw buffers)
+void prepare(Staged& s, bool device_reconcile)
+{
+    Staged::Side &e = s.side[0], &t = s.side[1];
+    if (s.req.raw.expect) {  // in-memory pair: nothing to decode
+        const RawPair& r = s.req.raw;
+        if (!r.target || r.width < 1 || r.height < 1 || r.stride < r.width) { s.err = "bad raw image pair"; return; }
+        e.p = r.expect;
+        t.p = r.target;
+        s.w = e.w = t.w = r.width;
+        s.h = e.h = t.h = r.height;
+        s.stride = r.stride;
+        return;
+    }
+    s.w = e.w;
+    s.h = e.h;
+    if (pair_refused(s)) return;
+    const SizeRule rule = size_rule(s.w, s.h, t.w, t.h, device_reconcile);
+    if (rule == SizeRule::DontMatch) { s.err = "Don't match image size"; return; }
+    // a JPEG beside half-decoded PNG rows (index.js pairs files by relative path: a corner): tw_submit_png takes rows and
+    // gray images, so the JPEG is finished here; so is a JPEG target that the host is to resize
+    if (e.jpeg.on() && t.kind.rows()) finish_jpeg_on_host(e);
+    if (t.jpeg.on() && (e.kind.rows() || rule == SizeRule::ReconcileOnHost)) finish_jpeg_on_host(t);
+    // the <= 5 px reconcile on the device (tw_submit_*_sized): the target stays as it was decoded, filtered rows included
+    s.device_reconciles = rule == SizeRule::ReconcileOnDevice;
+    if (rule == SizeRule::ReconcileOnHost && !reconcile_on_host(s)) return;
+    point_at_own_bytes(s);
+}
+
+// Which entry point of the engine a staged pair goes through (`resident`: an image on the device stands in for the
+// expected file, so only the target goes up, in whatever form it was decoded to)
+enum class EntryPoint { ImageJpeg, ImagePng, Png, Jpeg, U8Sized, U8 };
+EntryPoint entry_point(const Staged& s, bool resident)
+{
+    const Staged::Side &e = s.side[0], &t = s.side[1];
+    if (resident) return t.jpeg.on() ? EntryPoint::ImageJpeg : EntryPoint::ImagePng;
+    // half-decoded PNG(s): the device reconstructs the scanlines, and resizes a target within 5 px of the pair's size
+    if (e.kind.rows() || t.kind.rows()) return EntryPoint::Png;
+    // JPEG(s) that stopped at the coefficient plane: the device runs the inverse DCT (and the reconcile)
+    if (e.jpeg.on() || t.jpeg.on()) return EntryPoint::Jpeg;
+    return s.device_reconciles ? EntryPoint::U8Sized : EntryPoint::U8;
+}
+tw_png_rows rows_of(const Staged::Side& sd)
+{
+    tw_png_rows r;
+    r.rows = sd.p;
+    r.width = sd.w;
+    r.height = sd.h;
+    r.color_type = sd.kind.color_type;
+    r.bit_depth = sd.kind.bit_depth;
+    r.palette = sd.kind.plte.empty() ? nullptr : sd.kind.plte.data();
+    r.palette_entries = (int)(sd.kind.plte.size() / 3);
+    return r;
+}
+tw_jpeg_luma luma_of(const Staged::Side& sd)
+{
+    tw_jpeg_luma l;
+    l.coef = sd.jpeg.on() ? (const int16_t*)sd.p : nullptr;
+    l.gray = sd.jpeg.on() ? nullptr : sd.p;
+    l.width = sd.w;
+    l.height = sd.h;
+    l.blocks_w = sd.jpeg.bw;
+    l.blocks_h = sd.jpeg.bh;
+    memcpy(l.quant, sd.jpeg.quant, sizeof(l.quant));
+    return l;
+}
+
+// fn(0) .. fn(ntask - 1) on up to `threads` threads, the caller's among them
+template <class Fn>
+void parallel_for(size_t ntask, size_t threads, const Fn& fn)
+{
+    const size_t nt = std::min(ntask, threads);
+    std::atomic<size_t> next{0};
+    auto worker = [&] {
+        for (size_t i = next++; i < ntask; i = next++) fn(i);
+    };
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < nt; t++) pool.emplace_back(worker);
+    worker();
+    for (std::thread& t : pool) t.join();
+}
+
+// page-locked (tw_host_alloc): the decoded pairs of the batch being filled / the two batches in flight
+struct Arena {
+    uint8_t* base = nullptr;
+    size_t cap = 0;
+};
+// a file of the batch after Phase 1
+struct Opened {
+    std::vector<uint8_t> file;
+    PngStream st;
+    bool read_ok = false, rows_ok = false;
+};
+// What one turn of the consumer's loop works on
+struct Batch {
+    std::vector<Staged> jobs;
+    std::vector<Opened> op;  // [2 * job + image]
+    Arena* arena = nullptr;
+    size_t slot = 0;  // bytes of an arena slot; image i of the batch sits at arena->base + slot * i
+    long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;  // TW_DEBUG_BATCHTIME: taken, decoded, staged, flushed
+    // (a resident image stands in for the expected file of that job: nothing to read, decode or copy)
+    bool skipped(size_t i) const { return !(i & 1) && jobs[i >> 1].no_expected_file(); }
+};
+
+// Consumer::run's state and its steps, in the order run() calls them
+struct ConsumerRun {
+    // the consumer's own (Consumer's members)
+    const int id;
+    MessageQueue<Request>& req;
+    MessageQueue<Response>& res;
+    const tw_params& params;
+    const int batch_size, decode_threads, n_consumers;
+    ConsumerShared* const shared;
+
+    const Switches sw;
+    ConsumerStats mine;  // this thread's own counters; published under the shared mutex
+    int ndev = 0, dev = -1;
     tw_engine* eng = nullptr;
     std::string eng_err;
-    if (ndev > 0) {
-        tw_status r = tw_engine_create(dev, &params_, batch_, &eng);
-        if (r != TW_OK) eng_err = std::string("engine: ") + tw_strerror(r);
-    } else {
-        eng_err = "no HIP device available";
+    bool device_jpeg = false;  // sw.device_jpeg, where the engine exports tw_submit_jpeg
+    bool prof = false;
+    int my_epoch = 0;
+    // one scratch array for the hit records of a job, grown to the largest grid seen: a fresh zero-filled vector of
+    // grid-capacity entries per job — 0.5 MB at 1080p / span 10 — cost 0.2 ms of every response, round 4
+    std::unique_ptr<tw_vector[]> hits;
+    size_t hits_cap = 0;
+    // Resident expected images (Parameter::residentMB / TW_RESIDENT_MB; 0, the default: off, and no step below reaches the
+    // cache): resident_cache.h
+    std::unique_ptr<ResidentCache> cache;
+    // Two batches are kept going: the one just submitted computes while the next one is popped, decoded and
+    // uploaded (the engine itself holds up to three batches).  Responses leave in completion order, as in the
+    // reference.
+    Arena arena[3];
+    int arena_idx = 0;
+    // Batches in flight behind the one being prepared: `prev` was submitted last, `prev2` before it.  Round 4: with one
+    // batch in flight the loop ran at the GPU's LATENCY for a batch (upload -> scanline reconstruction -> flow: ~22 ms for
+    // 32 pairs) instead of at the host's own ~16 ms; the engine takes three batch contexts, so two stay outstanding while
+    // the third is decoded.
+    std::vector<Staged> prev, prev2;
+
+    ConsumerRun(int id_, MessageQueue<Request>& req_, MessageQueue<Response>& res_, const tw_params& p, int batch, int decode_threads_,
+                int n_consumers_, ConsumerShared* shared_)
+        : id(id_), req(req_), res(res_), params(p), batch_size(batch), decode_threads(decode_threads_), n_consumers(n_consumers_),
+          shared(shared_)
+    {
     }
-    // Opt-in (TW_SCAN_FUSED_FINAL=1): the engine option that evaluates the last level-0 iteration at the span-grid points
-    // only.  A consumer hands back vectors, never the flow field, so the option is invisible to the caller (bit-identical
-    // vectors, tests/test_gpu_parity.py::test_scan_fused_final_iteration_option) and worth +3-5 % of GPU throughput; it
-    // stays off by default because the reference's consumer computes the whole field (src/consumer.cpp:54).
-    if (eng)
-        if (const char* ev = getenv("TW_SCAN_FUSED_FINAL"))
-            if (atoi(ev) != 0) (void)tw_set_option(eng, TW_OPT_SCAN_FUSED_FINAL, 1);
-    const bool prof = eng && shared_ && shared_->profile;
-    if (prof) {
-        (void)tw_prof_select(eng, TW_K_BLUR_SOLVE, 0);
-        (void)tw_prof_select(eng, TW_K_POLYEXP, 0);
+
+    void publish()
+    {
+        if (!shared) return;
+        std::lock_guard<std::mutex> lk(shared->m);
+        if ((size_t)id < shared->stats.size()) shared->stats[(size_t)id] = mine;
+        shared->cv.notify_all();
     }
-    int my_epoch = shared_ ? shared_->epoch.load() : 0;
-    auto publish = [&] {
-        if (!shared_) return;
-        std::lock_guard<std::mutex> lk(shared_->m);
-        if ((size_t)id_ < shared_->stats.size()) shared_->stats[(size_t)id_] = mine;
-        shared_->cv.notify_all();
-    };
     // kernel events are read (a device synchronise) only when nothing of ours is in flight
-    auto read_prof = [&](bool keep) {
+    void read_prof(bool keep)
+    {
         if (!prof) return;
         static const int kc[2] = {TW_K_BLUR_SOLVE, TW_K_POLYEXP};
         for (int i = 0; i < 2; i++) {
@@ -980,81 +1103,457 @@ void Consumer::run()
                 mine.profLaunches[i] += n;
             }
         }
-    };
-    mine.ready = true;
-    mine.engineError = eng_err;
-    publish();
+    }
+
+    // device binding happens here, on the worker thread (the reference binds on the main thread:
+    // src/consumer.cpp:22 via src/manager.cpp:56 — SURVEY.md Appendix B#6)
+    void bind_device_and_numa()
+    {
+        ndev = tw_device_count();
+        dev = ndev > 0 ? id % ndev : -1;
+        mine.id = id;
+        mine.device = dev;
+        // NUMA placement BEFORE the engine exists: the thread — and with it the decode pool it spawns and, by first touch,
+        // the page-locked staging / result buffers tw_engine_create and tw_submit_u8 allocate — moves to the CPUs of the
+        // GPU's node, so that 8 consumers x ~16 GB/s of pinned H2D do not cross the socket link.  TW_NUMA=0 disables.
+        std::vector<int> cpus;
+        int node = -1;
+        if (dev >= 0 && numa_cpus_of_device(dev, &mine.pciBusId, &node, &cpus) && sw.numa && bind_this_thread(cpus))
+            mine.numaNode = node;
+        mine.cpus = this_thread_cpus();
+    }
+
+    void create_engine()
+    {
+        device_jpeg = sw.device_jpeg && tw_submit_jpeg != nullptr;
+        if (ndev > 0) {
+            tw_status r = tw_engine_create(dev, &params, batch_size, &eng);
+            if (r != TW_OK) eng_err = std::string("engine: ") + tw_strerror(r);
+        } else {
+            eng_err = "no HIP device available";
+        }
+        // Opt-in (TW_SCAN_FUSED_FINAL=1): the engine option that evaluates the last level-0 iteration at the span-grid points
+        // only.  A consumer hands back vectors, never the flow field, so the option is invisible to the caller (bit-identical
+        // vectors, tests/test_gpu_parity.py::test_scan_fused_final_iteration_option) and worth +3-5 % of GPU throughput; it
+        // stays off by default because the reference's consumer computes the whole field (src/consumer.cpp:54).
+        if (eng && sw.scan_fused_final) (void)tw_set_option(eng, TW_OPT_SCAN_FUSED_FINAL, 1);
+        prof = eng && shared && shared->profile;
+        if (prof) {
+            (void)tw_prof_select(eng, TW_K_BLUR_SOLVE, 0);
+            (void)tw_prof_select(eng, TW_K_POLYEXP, 0);
+        }
+        my_epoch = shared ? shared->epoch.load() : 0;
+        const size_t budget = shared && shared->residentBytes > 0 ? (size_t)shared->residentBytes : 0;
+        const bool resident_on = eng && budget > 0 && tw_image_keep && tw_image_release && tw_submit_image_png && tw_submit_image_jpeg;
+        cache.reset(new ResidentCache(eng, resident_on ? budget : 0));
+        mine.ready = true;
+        mine.engineError = eng_err;
+        publish();
+    }
+
+    // Fair share (round 5; the N = 8 ceiling run on the stub backend, tests/test_host_queue.py): a consumer keeps up to
+    // three batches going, so near the END of a run — or for a run as short as BASELINE config 4's 2 048 pairs on 8 GPUs —
+    // three consumers used to hold nine full batches while five idled (21.6 k instead of 32.7 k pairs/s).  What is left
+    // (queued + in flight everywhere) is shared evenly: a consumer that already holds its share delivers its oldest batch
+    // before it takes more, and never takes more than what brings it up to the share.
+    long own_inflight() const
+    {
+        long k = 0;
+        for (const Staged& s : prev) k += s.submitted && !s.done;
+        for (const Staged& s : prev2) k += s.submitted && !s.done;
+        return k;
+    }
+    long fair_share()
+    {
+        const long total = (long)req.size() + (shared ? shared->inflight.load() : own_inflight());
+        return (total + (long)n_consumers - 1) / (long)n_consumers;
+    }
+    void deliver_down_to_share()
+    {
+        for (long own = own_inflight(); own > 0 && own >= fair_share() + sw.fair_slack; own = own_inflight()) {
+            if (!prev2.empty()) collect_all(prev2);
+            else collect_all(prev);
+        }
+    }
+
+    // The next batch: one job (waiting for it if need be), then whatever is queued up to the take size.  false: the queue stopped
+    bool take_batch(Batch& b)
+    {
+        Request first;
+        if (!req.tryPopNow(first)) {
+            collect_all(prev2);  // nothing queued: deliver what is outstanding before blocking
+            collect_all(prev);
+            read_prof(true);   // idle: nothing of ours is in flight, so the event read's synchronise costs nothing
+            publish();
+            const long long w0 = steady_ns();
+            if (!req.tryPop(first)) return false;
+            if (mine.firstJobNs) mine.waitMs += (double)(steady_ns() - w0) * 1e-6;  // blocked on an empty queue
+        }
+        if (shared && shared->epoch.load() != my_epoch) {
+            // Manager::markEpoch(): counters restart here (the manager marks an epoch only while the queue is empty
+            // and every response has arrived, so nothing of this consumer is in flight)
+            my_epoch = shared->epoch.load();
+            read_prof(false);
+            mine.pairs = mine.batches = 0;
+            mine.firstJobNs = mine.lastResponseNs = 0;
+            mine.waitMs = 0;
+            mine.profMs[0] = mine.profMs[1] = 0;
+            mine.profLaunches[0] = mine.profLaunches[1] = 0;
+        }
+        if (!mine.firstJobNs) mine.firstJobNs = steady_ns();
+        std::vector<Staged>& jobs = b.jobs;
+        jobs.resize(1);
+        jobs[0].req = std::move(first);
+        // a consumer takes at most its share of what is queued, so that a short queue is spread over all GPUs
+        // (ADVICE r1: a greedy grab of `batch` jobs starves the other consumers)
+        // (its share of the queue alone, and — above — of everything that is left including what the engines still hold)
+        // (round 6: the share of the QUEUE ALONE is no longer a limit of its own.  With it a burst of 2 048 jobs on 8 consumers
+        // was handed out as 128, 127, 128, 127, ... and then 1/8 of whatever was left — 112, 98, 85, 49, 42, 25, 21, ... 2, 1,
+        // 1, 1: three consumers ended 20 % short of their 256 and one of them worked the tail off in 30 batches of a few
+        // pairs.  The fair share of EVERYTHING that is left already spreads a short queue: 10 jobs on 8 consumers are 2 each.)
+        const long room = fair_share() + sw.fair_slack - own_inflight();
+        const size_t take = std::max<size_t>(1, std::min<size_t>((size_t)batch_size, (size_t)std::max(1L, room)));
+        if (sw.debug_takes)
+            fprintf(stderr, "take t=%.3f ms consumer %d queue %zu inflight %ld own %ld share %ld -> take %zu\n", (double)(steady_ns() % 10000000000LL) * 1e-6,
+                    id, req.size(), shared ? shared->inflight.load() : -1L, own_inflight(), fair_share(), take);
+        Request more;
+        while (jobs.size() < take && req.tryPopNow(more)) {
+            jobs.emplace_back();
+            jobs.back().req = std::move(more);
+        }
+        if (log_stream())
+            for (const Staged& s : jobs)  // src/consumer.cpp:49
+                TW_LOGF("consume: %s <-> %s\n", s.req.expect_image.c_str(), s.req.target_image.c_str());
+        mine.batches++;
+        b.t0 = b.t1 = b.t2 = b.t3 = steady_ns();
+        return true;
+    }
+
+    // Phase 0 (resident expected images): stat every expected file; one that is cached, or that a pair in flight or
+    // earlier in this batch is about to keep, is neither read nor decoded below
+    void match_resident(Batch& b)
+    {
+        if (!cache->on()) return;
+        std::vector<Staged>& jobs = b.jobs;
+        for (size_t j = 0; j < jobs.size(); j++) {
+            Staged& s = jobs[j];
+            const std::string& path = s.req.expect_image;
+            if (s.req.raw.expect || path.empty()) continue;
+            s.rkey = file_identity(path);
+            cache->note_identity(path, s.rkey);
+            if (s.rkey.empty()) continue;  // (no such file: the path below answers "Can't open")
+            if (ResidentCache::Entry* en = cache->lookup(s.rkey, path)) {
+                s.hit = en;
+                s.w = s.side[0].w = en->w;
+                s.h = s.side[0].h = en->h;
+                continue;
+            }
+            if ((s.keep = cache->find_pending(s.rkey))) {
+                s.follower = true;
+                s.w = s.side[0].w = s.keep->w;
+                s.h = s.side[0].h = s.keep->h;
+                continue;
+            }
+            for (size_t q = 0; q < j && !s.follower; q++)
+                if (jobs[q].rkey == s.rkey && !jobs[q].no_expected_file()) {
+                    s.keep = jobs[q].keep;
+                    s.follower = true;
+                    s.leader = (int)q;
+                }
+            if (!s.follower) s.keep = std::make_shared<ResidentCache::Keep>();
+        }
+    }
+
+    // decode pool: once the flow runs on the GPU the two imreads of a pair are > 99 % of the wall time
+    // (SURVEY §8 f1), so the pairs of a batch are decoded side by side
+    // Phase 1 (pool): read every file.  A PNG the device can finish (tw_png_on_device: not interlaced, no 16-bit
+    // colour) is only PARSED here; when every image of the batch is one, the arena is sized from the headers and the pool
+    // inflates straight into it (round 4: the intermediate buffers — inflate output, its copy, the copy into the
+    // arena, three 2 MB allocations per 1080p image — were a third of a batch's host time).
+    void open_files(Batch& b)
+    {
+        b.op = std::vector<Opened>(2 * b.jobs.size());
+        parallel_for(2 * b.jobs.size(), (size_t)decode_threads, [&](size_t i) {
+            const Staged& s = b.jobs[i >> 1];
+            const std::string& path = s.path((int)(i & 1));
+            if (s.req.raw.expect || path.empty() || b.skipped(i)) return;
+            Opened& o = b.op[i];
+            o.read_ok = read_file(path, o.file);
+            if (o.read_ok && sw.device_png && eng && o.file.size() >= 8 && o.file[0] == 0x89 && o.file[1] == 'P')
+                o.rows_ok = png_parse(o.file, o.st) && o.st.device_rows(sw.png_kinds);
+        });
+        b.arena = &arena[arena_idx];  // (its last user was the batch three back: collected before this one is submitted)
+        arena_idx = (arena_idx + 1) % 3;
+    }
+
+    static constexpr size_t kArenaSlotMax = (size_t)64 << 20;  // one 8192 x 8192 image
+    static constexpr size_t kArenaMax = (size_t)4 << 30;       // per arena, three arenas per consumer
+    // the arena is sized from PNG HEADERS, before anything is inflated.  Up to a 4K RGBA screenshot per
+    // slot (kArenaFullBatchSlot) it is sized for a full batch at once (no regrowth while a batch fills up); a
+    // larger slot gets only what the jobs actually present need, and an arena that an unusual batch blew up is
+    // given back as soon as a batch needs less than a quarter of it — one 8192 x 8192 header pair no longer pins
+    // 3 x 4 GiB per consumer for the life of the process (worst cases: INTEGRATION.md).
+    static constexpr size_t kArenaFullBatchSlot = (size_t)40 << 20;
+    static constexpr size_t kArenaShrinkAbove = (size_t)1 << 30;
+    // the batch's arena holds two slots of `slot` bytes per job, or as much of that as the bounds allow (the only step
+    // that calls tw_host_alloc / tw_host_free, on the consumer's own thread)
+    void size_arena(Batch& b, size_t slot)
+    {
+        Arena& ar = *b.arena;
+        const size_t need = std::min(kArenaMax, slot * 2 * b.jobs.size());
+        if (!eng || !slot) return;
+        const bool oversized = ar.base && ar.cap > kArenaShrinkAbove && need <= ar.cap / 4;
+        if (need <= ar.cap && !oversized) return;
+        if (ar.base) (void)tw_host_free(eng, ar.base);
+        ar.base = nullptr;
+        ar.cap = 0;
+        void* hp = nullptr;
+        // a full batch of this size (no regrowth), within the bound — for ordinary slots only
+        const size_t full = slot <= kArenaFullBatchSlot ? slot * 2 * (size_t)batch_size : need;
+        const size_t want = std::min(kArenaMax, std::max(need, full));
+        if (tw_host_alloc(eng, want, &hp) == TW_OK) {
+            ar.base = (uint8_t*)hp;
+            ar.cap = want;
+        }
+    }
+
+    // The fast path is open when every file of the batch is a PNG whose rows the device finishes and the arena has a slot
+    // for each: b.slot is set and the arena sized from the headers.  false: decode_and_copy
+    bool arena_from_headers(Batch& b)
+    {
+        bool fast = !b.op.empty();
+        size_t fslot = 0;
+        for (size_t i = 0; i < b.op.size(); i++) {
+            if (b.skipped(i)) continue;
+            const Opened& o = b.op[i];
+            fast = fast && o.rows_ok;
+            fslot = std::max(fslot, (o.st.total + 8 + 255) / 256 * 256);
+        }
+        if (!fast || fslot > kArenaSlotMax) return false;
+        size_arena(b, fslot);
+        b.slot = fslot;
+        return b.arena->base && fslot * 2 * b.jobs.size() <= b.arena->cap;
+    }
+    // Phase 2 (pool): inflate into the arena slot; every row's filter type is checked as libpng does
+    void inflate_into_arena(Batch& b)
+    {
+        parallel_for(2 * b.jobs.size(), (size_t)decode_threads, [&](size_t i) {
+            if (b.skipped(i)) return;
+            Opened& o = b.op[i];
+            Staged& s = b.jobs[i >> 1];
+            Staged::Side& sd = s.side[i & 1];
+            uint8_t* dst = b.arena->base + b.slot * i;
+            bool ok = png_inflate(o.st, dst);
+            const size_t rs = o.st.row_bytes();  // the kind's row length
+            for (int y = 0; y < o.st.h && ok; y++) ok = dst[(size_t)y * rs] <= 4;
+            if (!ok) sd.err = cant_open(s.path((int)(i & 1)));
+            sd.w = o.st.w;
+            sd.h = o.st.h;
+            sd.kind = o.st.kind();
+            std::vector<uint8_t>().swap(o.file);
+            std::vector<uint8_t>().swap(o.st.idat);
+        });
+        b.t1 = steady_ns();
+    }
+    // ... and the pairs are staged where they lie: only a pair that the HOST is to reconcile leaves the arena
+    void stage_from_arena(Batch& b)
+    {
+        for (size_t j = 0; j < b.jobs.size(); j++) {
+            Staged& s = b.jobs[j];
+            Staged::Side &e = s.side[0], &t = s.side[1];
+            // (a resident expected image: its size is the cache entry's, or that of the pair that keeps it)
+            inherit_from_leader(s, b.jobs);
+            if (pair_refused(s)) continue;
+            s.w = e.w;
+            s.h = e.h;
+            uint8_t* da = b.arena->base + b.slot * (2 * j);
+            uint8_t* db = da + b.slot;
+            switch (size_rule(s.w, s.h, t.w, t.h, sw.device_reconcile)) {
+                case SizeRule::DontMatch: s.err = "Don't match image size"; continue;
+                case SizeRule::ReconcileOnHost:
+                    // TW_DEVICE_RECONCILE=0: the reconcile on the host, on copies outside the arena
+                    if (!s.no_expected_file()) e.bytes.assign(da, da + b.op[2 * j].st.total);
+                    t.bytes.assign(db, db + b.op[2 * j + 1].st.total);
+                    if (reconcile_on_host(s)) point_at_own_bytes(s);
+                    continue;
+                case SizeRule::ReconcileOnDevice:  // within 5 px: the pair stays in the arena, the device resizes the target
+                    s.device_reconciles = true;
+                    break;
+                case SizeRule::Same: break;
+            }
+            e.p = da;
+            t.p = db;
+            s.stride = s.w;
+        }
+    }
+
+    // The other path: every image is decoded into a buffer of its own, the pair is prepared there, and what fits is copied
+    // into the arena
+    void decode_and_copy(Batch& b)
+    {
+        std::vector<Staged>& jobs = b.jobs;
+        parallel_for(2 * jobs.size(), (size_t)decode_threads, [&](size_t i) {
+            decode_one(jobs[i >> 1], (int)(i & 1), sw, device_jpeg && eng, b.op[i].read_ok ? &b.op[i].file : nullptr);
+            std::vector<uint8_t>().swap(b.op[i].file);
+        });
+        b.t1 = steady_ns();
+        for (Staged& s : jobs) inherit_from_leader(s, jobs);
+        parallel_for(jobs.size(), (size_t)decode_threads, [&](size_t j) { prepare(jobs[j], sw.device_reconcile); });
+        // The arena is sized AFTER prepare(), over the pairs that decoded and reconciled (a header with
+        // huge dimensions over a damaged stream must not size it), and it is bounded: a pair larger than
+        // kArenaSlotMax, or one the bounded arena has no room for, keeps its pageable buffers (tw_submit_u8 stages
+        // those itself — always correct, one memcpy slower).
+        size_t slot = 0;
+        for (const Staged& s : jobs) {
+            if (!s.err.empty() || s.req.raw.expect) continue;
+            // (an image is w * h gray bytes or, still filtered, h rows of its kind's PngKind::row_bytes(w))
+            const size_t nb = (std::max(s.side[0].bytes.size(), s.side[1].bytes.size()) + 255) / 256 * 256;
+            if (nb <= kArenaSlotMax) slot = std::max(slot, nb);
+        }
+        size_arena(b, slot);
+        const Arena& ar = *b.arena;
+        parallel_for(jobs.size(), (size_t)decode_threads, [&](size_t j) {
+            Staged& s = jobs[j];
+            Staged::Side &e = s.side[0], &t = s.side[1];
+            if (!s.err.empty() || s.req.raw.expect || !ar.base || !slot) return;
+            if (std::max(e.bytes.size(), t.bytes.size()) > slot || (2 * j + 2) * slot > ar.cap) return;  // stays pageable
+            uint8_t* da = ar.base + slot * (2 * j);
+            uint8_t* db = da + slot;
+            if (!e.bytes.empty()) memcpy(da, e.bytes.data(), e.bytes.size());
+            memcpy(db, t.bytes.data(), t.bytes.size());
+            e.p = da;
+            t.p = db;
+            std::vector<uint8_t>().swap(e.bytes);
+            std::vector<uint8_t>().swap(t.bytes);
+        });
+    }
+
+    // one engine batch is homogeneous in size: group equal sizes so that a mixed queue makes few batches
+    // (responses are delivered in completion order anyway, like the reference's)
+    // (Staged::leader indexes the batch as it was before this: nothing reads it afterwards)
+    void sort_by_size(Batch& b)
+    {
+        b.t2 = steady_ns();
+        std::stable_sort(b.jobs.begin(), b.jobs.end(), [](const Staged& x, const Staged& y) {
+            return x.w != y.w ? x.w < y.w : x.h < y.h;
+        });
+    }
+
+    // A pair behind one that was to keep its expected image, and that one failed before it did (its target, the
+    // sizes): this pair is decoded again on its own, expected file included, and goes the ordinary way
+    void redecode_orphaned_follower(Staged& s)
+    {
+        s.follower = false;
+        s.leader = -1;
+        s.keep = std::make_shared<ResidentCache::Keep>();
+        s.side[0] = s.side[1] = Staged::Side();
+        s.device_reconciles = false;
+        decode_one(s, 0, sw, false, nullptr);
+        decode_one(s, 1, sw, false, nullptr);
+        prepare(s, sw.device_reconcile);
+    }
+    // the image on the device that stands in for the pair's expected file, if any
+    tw_image* resident_image_of(Staged& s)
+    {
+        if (s.hit) return s.hit->img;
+        if (!s.follower) return nullptr;
+        s.uses_keep = s.keep->img != nullptr;
+        return s.uses_keep ? s.keep->img : cache->image_now(s.rkey, s.req.expect_image);
+    }
+    tw_status submit_to_engine(Staged& s)
+    {
+        const Staged::Side &e = s.side[0], &t = s.side[1];
+        const tw_image* image = resident_image_of(s);
+        const int span = s.req.span;
+        const double thr = s.req.threshold;
+        switch (entry_point(s, image != nullptr)) {
+            case EntryPoint::ImageJpeg: {
+                const tw_jpeg_luma lb = luma_of(t);
+                return tw_submit_image_jpeg(eng, image, &lb, span, thr, nullptr, nullptr, &s.ticket);
+            }
+            case EntryPoint::ImagePng: {
+                const tw_png_rows rb = rows_of(t);
+                return tw_submit_image_png(eng, image, &rb, span, thr, nullptr, nullptr, &s.ticket);
+            }
+            case EntryPoint::Png: {
+                const tw_png_rows ra = rows_of(e), rb = rows_of(t);
+                return tw_submit_png(eng, &ra, &rb, span, thr, nullptr, nullptr, &s.ticket);
+            }
+            case EntryPoint::Jpeg: {
+                const tw_jpeg_luma la = luma_of(e), lb = luma_of(t);
+                return tw_submit_jpeg(eng, &la, &lb, span, thr, nullptr, nullptr, &s.ticket);
+            }
+            case EntryPoint::U8Sized:
+                return tw_submit_u8_sized(eng, e.p, s.w, s.h, s.stride, t.p, t.w, t.h, t.w, span, thr, nullptr, nullptr, &s.ticket);
+            case EntryPoint::U8: break;
+        }
+        return tw_submit_u8(eng, e.p, t.p, s.w, s.h, s.stride, span, thr, &s.ticket);
+    }
+    // a miss: the image the batch sees stays on the device (one device-to-device copy behind its decode), and
+    // enters the cache when the pair has answered OK
+    void keep_expected(Staged& s)
+    {
+        if (!cache->on() || s.rkey.empty() || s.no_expected_file() || !s.keep) return;
+        if (tw_image_keep(eng, s.ticket, TW_KEEP_EXPECT, &s.kept) == TW_OK) cache->open_pending(s.rkey, s.keep, s.kept, s.w, s.h);
+        else s.kept = nullptr;
+    }
+    void submit_pair(Batch& b, size_t k)
+    {
+        Staged& s = b.jobs[k];
+        if (s.err.empty() && !eng) s.err = eng_err;
+        if (!s.err.empty()) return;
+        if (s.follower && !s.keep->img && !cache->has(s.rkey)) {
+            redecode_orphaned_follower(s);
+            if (!s.err.empty()) return;
+        }
+        tw_status r = submit_to_engine(s);
+        if (r == TW_E_BUSY) {
+            // every batch context of the engine is owed to us (each size change opens one): collect what
+            // is outstanding, then this job starts a fresh batch
+            collect_all(prev2);
+            collect_all(prev);
+            for (size_t q = 0; q < k; q++) collect(b.jobs[q]);
+            r = submit_to_engine(s);
+        }
+        if (r == TW_OK) {
+            s.submitted = true;
+            if (shared) shared->inflight++;
+            keep_expected(s);
+        } else s.err = engine_error(eng, r);
+    }
+
+    void unpin_and_flush(Batch& b)
+    {
+        for (Staged& s : b.jobs)  // (submitted or refused: the batch holds the image now, the cache entry may go)
+            if (s.hit) {
+                cache->unpin(s.hit);
+                s.hit = nullptr;
+            }
+        cache->sweep();
+        if (eng) (void)tw_flush(eng);  // a partly filled batch starts now, not when its first result is asked for
+        b.t3 = steady_ns();
+    }
+
+    void deliver_refused_and_rotate(Batch& b)
+    {
+        const size_t njobs = b.jobs.size();
+        for (Staged& s : b.jobs)
+            if (!s.submitted) collect(s);  // errors do not wait for the GPU
+        collect_all(prev2);  // the batch before the previous one: its results have had two batches' time to arrive
+        prev2 = std::move(prev);
+        prev = std::move(b.jobs);
+        if (sw.debug_batchtime)
+            fprintf(stderr, "twhost: consumer %d batch of %zu: decode %.2f ms, prepare + arena %.2f, submit + flush %.2f, "
+                            "previous batch's results %.2f\n", id, njobs, (b.t1 - b.t0) * 1e-6, (b.t2 - b.t1) * 1e-6,
+                    (b.t3 - b.t2) * 1e-6, (steady_ns() - b.t3) * 1e-6);
+    }
+
     // wait for one job and hand its response to the pump
-    // (one scratch array for the hit records of a job, grown to the largest grid seen: a fresh zero-filled vector of
-    // grid-capacity entries per job — 0.5 MB at 1080p / span 10 — cost 0.2 ms of every response, round 4)
-    std::unique_ptr<tw_vector[]> hits;
-    size_t hits_cap = 0;
-    // Resident expected images (Parameter::residentMB / TW_RESIDENT_MB; 0, the default: off, and nothing below is ever
-    // reached): the expected image of a pair stays on the device under its file's identity, and a later pair that names
-    // the same file skips read, decode, arena copy and upload of it (tw_submit_image_*).  An LRU by bytes; eviction only
-    // releases the handle — the engine returns the block once no batch reads it — so it never waits.
-    typedef Staged::ResEntry ResEntry;
-    const size_t res_budget = shared_ && shared_->residentBytes > 0 ? (size_t)shared_->residentBytes : 0;
-    const bool resident_on = eng && res_budget > 0 && tw_image_keep && tw_image_release && tw_submit_image_png && tw_submit_image_jpeg;
-    std::map<std::string, std::unique_ptr<ResEntry>> res_cache;  // file identity -> entry
-    std::map<std::string, std::string> res_path_key;             // path -> the identity it was last seen with
-    std::list<ResEntry*> res_lru;                                // front: used last
-    std::list<std::unique_ptr<ResEntry>> res_zombies;            // evicted while a pair that looked them up was not submitted yet
-    std::map<std::string, std::shared_ptr<Staged::Keep>> res_pending;  // identity -> the image of a pair that has not answered
-    size_t res_bytes = 0;
-    auto res_evict = [&](ResEntry* en) {
-        res_bytes -= en->bytes;
-        res_lru.erase(en->lru);
-        for (const std::string& p : en->paths) {
-            auto pk = res_path_key.find(p);
-            if (pk != res_path_key.end() && pk->second == en->key) res_path_key.erase(pk);
-        }
-        auto it = res_cache.find(en->key);
-        std::unique_ptr<ResEntry> own = std::move(it->second);
-        res_cache.erase(it);
-        if (own->pins > 0) res_zombies.push_back(std::move(own));
-        else (void)tw_image_release(eng, own->img);
-    };
-    auto res_sweep = [&] {
-        for (auto it = res_zombies.begin(); it != res_zombies.end();)
-            if ((*it)->pins == 0) {
-                (void)tw_image_release(eng, (*it)->img);
-                it = res_zombies.erase(it);
-            } else ++it;
-    };
-    auto res_lookup = [&](const std::string& key, const std::string& path) -> ResEntry* {
-        auto it = res_cache.find(key);
-        if (it == res_cache.end()) return nullptr;
-        ResEntry* en = it->second.get();
-        res_lru.splice(res_lru.begin(), res_lru, en->lru);
-        if (std::find(en->paths.begin(), en->paths.end(), path) == en->paths.end()) en->paths.push_back(path);
-        res_path_key[path] = key;
-        return en;
-    };
-    auto res_insert = [&](const std::string& key, const std::string& path, tw_image* img, int w, int h) {
-        const size_t bytes = ((size_t)w * (size_t)h + 255) / 256 * 256;
-        if (res_cache.count(key) || bytes > res_budget) {  // (a pair of another batch got there first / larger than the budget)
-            (void)tw_image_release(eng, img);
-            return;
-        }
-        while (res_bytes + bytes > res_budget && !res_lru.empty()) res_evict(res_lru.back());
-        std::unique_ptr<ResEntry> en(new ResEntry());
-        en->key = key;
-        en->paths.push_back(path);
-        en->img = img;
-        en->w = w;
-        en->h = h;
-        en->bytes = bytes;
-        res_lru.push_front(en.get());
-        en->lru = res_lru.begin();
-        res_bytes += bytes;
-        res_path_key[path] = key;
-        res_cache[key] = std::move(en);
-    };
-    auto finish = [&](Staged& s) {
+    void collect(Staged& s)
+    {
         if (s.done) return;
         s.done = true;
-        Response res;
+        Response out;
         if (s.submitted) {
             const int cap = std::max(1, tw_grid_capacity(s.w, s.h, s.req.span));
             if ((size_t)cap > hits_cap) {
@@ -1065,491 +1564,91 @@ void Consumer::run()
             int n = 0;
             float sec = 0;
             tw_status r = tw_wait(eng, s.ticket, v, cap, &n, &sec);
-            if (shared_) shared_->inflight--;
+            if (shared) shared->inflight--;
             if (s.kept) {
-                // the expected image this pair kept: into the cache when the pair answered OK, released otherwise (a palette
-                // index without an entry leaves it undefined — the pairs that read it meanwhile answer as this one does)
-                s.keep->expect_bad = r == TW_E_BAD_IMAGE_FORMAT && strstr(tw_last_error(eng), "target") == nullptr;
-                s.keep->img = nullptr;
-                auto pk = res_pending.find(s.rkey);
-                if (pk != res_pending.end() && pk->second == s.keep) res_pending.erase(pk);
-                if (r == TW_OK) res_insert(s.rkey, s.req.expect_image, s.kept, s.w, s.h);
-                else (void)tw_image_release(eng, s.kept);
+                cache->settle(s.rkey, s.req.expect_image, s.keep, s.kept, s.w, s.h, r);
                 s.kept = nullptr;
             }
             if (s.uses_keep && s.keep->expect_bad) {
-                s.err = "Can't open " + s.req.expect_image;
-            } else
-            if (r == TW_E_BAD_IMAGE_FORMAT && (s.ka.rows() || s.kb.rows())) {
+                s.err = cant_open(s.req.expect_image);
+            } else if (r == TW_E_BAD_IMAGE_FORMAT && (s.side[0].kind.rows() || s.side[1].kind.rows())) {
                 // a palette index without a PLTE entry, found by the device: cv::imread fails on that file, and the
                 // ticket's message names it (the expected image first, as the reference opens it first)
                 const bool target = strstr(tw_last_error(eng), "target") != nullptr;
-                s.err = "Can't open " + (target ? s.req.target_image : s.req.expect_image);
+                s.err = cant_open(s.path(target));
             } else if (r != TW_OK) {
-                s.err = std::string(tw_last_error(eng)[0] ? tw_last_error(eng) : tw_strerror(r));
+                s.err = engine_error(eng, r);
             } else {
-                res.vectors.resize((size_t)std::min(n, cap));
-                for (size_t i = 0; i < res.vectors.size(); i++) res.vectors[i] = {v[i].x, v[i].y, v[i].dx, v[i].dy};
-                res.status = res.vectors.empty() ? "OK" : "SUSPICIOUS";  // src/consumer.cpp:77
-                res.time = sec;
-                res.expect_image = s.req.expect_image;
-                res.target_image = s.req.target_image;
-                res.span = s.req.span;
-                res.threshold = s.req.threshold;
-                res.height = s.h;
-                res.width = s.w;
+                out.vectors.resize((size_t)std::min(n, cap));
+                for (size_t i = 0; i < out.vectors.size(); i++) out.vectors[i] = {v[i].x, v[i].y, v[i].dx, v[i].dy};
+                out.status = out.vectors.empty() ? "OK" : "SUSPICIOUS";  // src/consumer.cpp:77
+                out.time = sec;
+                out.expect_image = s.req.expect_image;
+                out.target_image = s.req.target_image;
+                out.span = s.req.span;
+                out.threshold = s.req.threshold;
+                out.height = s.h;
+                out.width = s.w;
             }
         }
         if (!s.err.empty()) {
-            res = Response();
-            res.status = "ERROR";  // src/consumer.cpp:85-88
-            res.reason = s.err;
+            out = Response();
+            out.status = "ERROR";  // src/consumer.cpp:85-88
+            out.reason = s.err;
         }
-        TW_LOGF("finish optical flow: %g\n", (double)res.time);  // src/consumer.cpp:55
+        TW_LOGF("finish optical flow: %g\n", (double)out.time);  // src/consumer.cpp:55
         mine.pairs++;
         mine.lastResponseNs = steady_ns();
         publish();  // before the response leaves: whoever has seen N responses sees N pairs in the stats
-        res.pushedNs = mine.lastResponseNs;
-        res_.push(std::move(res));
-    };
-    // Two batches are kept going: the one just submitted computes while the next one is popped, decoded and
-    // uploaded (the engine itself holds up to three batches).  Responses leave in completion order, as in the
-    // reference.
-    struct Arena {
-        uint8_t* base = nullptr;
-        size_t cap = 0;
-    } arena[3];  // page-locked (tw_host_alloc): the decoded pairs of the batch being filled / the two batches in flight
-    int arena_idx = 0;
-    // Batches in flight behind the one being prepared: `prev` was submitted last, `prev2` before it.  Round 4: with one
-    // batch in flight the loop ran at the GPU's LATENCY for a batch (upload -> scanline reconstruction -> flow: ~22 ms for
-    // 32 pairs) instead of at the host's own ~16 ms; the engine takes three batch contexts, so two stay outstanding while
-    // the third is decoded.
-    std::vector<Staged> prev, prev2;
-    auto finish_all = [&](std::vector<Staged>& v) {
-        for (Staged& s : v) finish(s);
-        v.clear();
-    };
-    // Fair share (round 5; the N = 8 ceiling run on the stub backend, tests/test_host_queue.py): a consumer keeps up to
-    // three batches going, so near the END of a run — or for a run as short as BASELINE config 4's 2 048 pairs on 8 GPUs —
-    // three consumers used to hold nine full batches while five idled (21.6 k instead of 32.7 k pairs/s).  What is left
-    // (queued + in flight everywhere) is shared evenly: a consumer that already holds its share delivers its oldest batch
-    // before it takes more, and never takes more than what brings it up to the share.
-    auto own_inflight = [&] {
-        long k = 0;
-        for (const Staged& s : prev) k += s.submitted && !s.done;
-        for (const Staged& s : prev2) k += s.submitted && !s.done;
-        return k;
-    };
-    auto fair_share = [&] {
-        const long total = (long)req_.size() + (shared_ ? shared_->inflight.load() : own_inflight());
-        return (total + (long)n_consumers_ - 1) / (long)n_consumers_;
-    };
-    static const long fair_slack = getenv("TW_FAIR_SLACK") ? atol(getenv("TW_FAIR_SLACK")) : 0;
-    for (;;) {
-        for (long own = own_inflight(); own > 0 && own >= fair_share() + fair_slack; own = own_inflight()) {
-            if (!prev2.empty()) finish_all(prev2);
-            else finish_all(prev);
-        }
-        Request first;
-        if (!req_.tryPopNow(first)) {
-            finish_all(prev2);  // nothing queued: deliver what is outstanding before blocking
-            finish_all(prev);
-            read_prof(true);   // idle: nothing of ours is in flight, so the event read's synchronise costs nothing
-            publish();
-            const long long w0 = steady_ns();
-            if (!req_.tryPop(first)) break;
-            if (mine.firstJobNs) mine.waitMs += (double)(steady_ns() - w0) * 1e-6;  // blocked on an empty queue
-        }
-        if (shared_ && shared_->epoch.load() != my_epoch) {
-            // Manager::markEpoch(): counters restart here (the manager marks an epoch only while the queue is empty
-            // and every response has arrived, so nothing of this consumer is in flight)
-            my_epoch = shared_->epoch.load();
-            read_prof(false);
-            mine.pairs = mine.batches = 0;
-            mine.firstJobNs = mine.lastResponseNs = 0;
-            mine.waitMs = 0;
-            mine.profMs[0] = mine.profMs[1] = 0;
-            mine.profLaunches[0] = mine.profLaunches[1] = 0;
-        }
-        if (!mine.firstJobNs) mine.firstJobNs = steady_ns();
-        std::vector<Staged> jobs(1);
-        jobs[0].req = std::move(first);
-        // a consumer takes at most its share of what is queued, so that a short queue is spread over all GPUs
-        // (ADVICE r1: a greedy grab of `batch` jobs starves the other consumers)
-        // (its share of the queue alone, and — above — of everything that is left including what the engines still hold)
-        // (round 6: the share of the QUEUE ALONE is no longer a limit of its own.  With it a burst of 2 048 jobs on 8 consumers
-        // was handed out as 128, 127, 128, 127, ... and then 1/8 of whatever was left — 112, 98, 85, 49, 42, 25, 21, ... 2, 1,
-        // 1, 1: three consumers ended 20 % short of their 256 and one of them worked the tail off in 30 batches of a few
-        // pairs.  The fair share of EVERYTHING that is left already spreads a short queue: 10 jobs on 8 consumers are 2 each.)
-        const long room = fair_share() + fair_slack - own_inflight();
-        const size_t take = std::max<size_t>(1, std::min<size_t>((size_t)batch_, (size_t)std::max(1L, room)));
-        static const bool debug_takes = getenv("TW_DEBUG_TAKES") != nullptr;  // diagnostic: who takes what, when
-        if (debug_takes)
-            fprintf(stderr, "take t=%.3f ms consumer %d queue %zu inflight %ld own %ld share %ld -> take %zu\n", (double)(steady_ns() % 10000000000LL) * 1e-6,
-                    id_, req_.size(), shared_ ? shared_->inflight.load() : -1L, own_inflight(), fair_share(), take);
-        Request more;
-        while (jobs.size() < take && req_.tryPopNow(more)) {
-            jobs.emplace_back();
-            jobs.back().req = std::move(more);
-        }
-        if (log_stream())
-            for (const Staged& s : jobs)  // src/consumer.cpp:49
-                TW_LOGF("consume: %s <-> %s\n", s.req.expect_image.c_str(), s.req.target_image.c_str());
-        mine.batches++;
-        static const bool batch_time = getenv("TW_DEBUG_BATCHTIME") != nullptr;  // diagnostic: where a batch's host time goes
-        const long long bt0 = steady_ns();
-        long long bt1 = bt0, bt2 = bt0, bt3 = bt0;
-        // decode pool: once the flow runs on the GPU the two imreads of a pair are > 99 % of the wall time
-        // (SURVEY §8 f1), so the pairs of a batch are decoded side by side
-        {
-            std::vector<int> tw(jobs.size(), 0), th(jobs.size(), 0);
-            std::vector<std::string> ea(jobs.size()), eb(jobs.size());
-            auto parallel_for = [&](size_t ntask, const std::function<void(size_t)>& fn) {
-                const size_t nt = std::min(ntask, (size_t)decode_threads_);
-                std::atomic<size_t> next{0};
-                auto worker = [&] {
-                    for (size_t i = next++; i < ntask; i = next++) fn(i);
-                };
-                std::vector<std::thread> pool;
-                for (size_t t = 1; t < nt; t++) pool.emplace_back(worker);
-                worker();
-                for (std::thread& t : pool) t.join();
-            };
-            // Phase 1 (pool): read every file.  A PNG the device can finish (tw_png_on_device: not interlaced, no 16-bit
-            // colour) is only PARSED here; when every image of the batch is one, the arena is sized from the headers and the pool
-            // inflates straight into it (round 4: the intermediate buffers — inflate output, its copy, the copy into the
-            // arena, three 2 MB allocations per 1080p image — were a third of a batch's host time).
-            struct Opened {
-                std::vector<uint8_t> file;
-                PngStream st;
-                bool read_ok = false, rows_ok = false;
-            };
-            std::vector<Opened> op(2 * jobs.size());
-            // Phase 0 (resident expected images): stat every expected file; one that is cached, or that a pair in flight or
-            // earlier in this batch is about to keep, is neither read nor decoded below
-            if (resident_on)
-                for (size_t j = 0; j < jobs.size(); j++) {
-                    Staged& s = jobs[j];
-                    const std::string& path = s.req.expect_image;
-                    if (s.req.raw.expect || path.empty()) continue;
-                    s.rkey = file_identity(path);
-                    auto seen = res_path_key.find(path);
-                    if (seen != res_path_key.end() && seen->second != s.rkey) {  // rewritten (or gone): the old image goes
-                        auto old = res_cache.find(seen->second);
-                        if (old != res_cache.end()) res_evict(old->second.get());
-                        res_path_key.erase(path);
-                    }
-                    if (s.rkey.empty()) continue;  // (no such file: the path below answers "Can't open")
-                    if (ResEntry* en = res_lookup(s.rkey, path)) {
-                        s.hit = en;
-                        en->pins++;
-                        s.w = en->w;
-                        s.h = en->h;
-                        continue;
-                    }
-                    auto pk = res_pending.find(s.rkey);
-                    if (pk != res_pending.end()) {
-                        s.keep = pk->second;
-                        s.follower = true;
-                        s.w = s.keep->w;
-                        s.h = s.keep->h;
-                        continue;
-                    }
-                    for (size_t q = 0; q < j && !s.follower; q++)
-                        if (jobs[q].rkey == s.rkey && !jobs[q].no_expected_file()) {
-                            s.keep = jobs[q].keep;
-                            s.follower = true;
-                            s.leader = (int)q;
-                        }
-                    if (!s.follower) s.keep = std::make_shared<Staged::Keep>();
-                }
-            auto skipped = [&](size_t i) { return !(i & 1) && jobs[i >> 1].no_expected_file(); };
-            parallel_for(2 * jobs.size(), [&](size_t i) {
-                const Staged& s = jobs[i >> 1];
-                const std::string& path = (i & 1) ? s.req.target_image : s.req.expect_image;
-                if (s.req.raw.expect || path.empty() || skipped(i)) return;
-                Opened& o = op[i];
-                o.read_ok = read_file(path, o.file);
-                if (o.read_ok && device_png && eng && o.file.size() >= 8 && o.file[0] == 0x89 && o.file[1] == 'P')
-                    o.rows_ok = png_parse(o.file, o.st) && o.st.device_rows(png_kinds);
-            });
-            constexpr size_t kArenaSlotMax = (size_t)64 << 20;  // one 8192 x 8192 image
-            constexpr size_t kArenaMax = (size_t)4 << 30;       // per arena, three arenas per consumer
-            Arena& ar = arena[arena_idx];  // (its last user was the batch three back: collected below before this one)
-            arena_idx = (arena_idx + 1) % 3;
-            // the arena is sized from PNG HEADERS, before anything is inflated.  Up to a 4K RGBA screenshot per
-            // slot (kArenaFullBatchSlot) it is sized for a full batch at once (no regrowth while a batch fills up); a
-            // larger slot gets only what the jobs actually present need, and an arena that an unusual batch blew up is
-            // given back as soon as a batch needs less than a quarter of it — one 8192 x 8192 header pair no longer pins
-            // 3 x 4 GiB per consumer for the life of the process (worst cases: INTEGRATION.md).
-            constexpr size_t kArenaFullBatchSlot = (size_t)40 << 20;
-            constexpr size_t kArenaShrinkAbove = (size_t)1 << 30;
-            auto ensure_arena = [&](size_t slot) {
-                const size_t need = std::min(kArenaMax, slot * 2 * jobs.size());
-                if (!eng || !slot) return;
-                const bool oversized = ar.base && ar.cap > kArenaShrinkAbove && need <= ar.cap / 4;
-                if (need <= ar.cap && !oversized) return;
-                if (ar.base) (void)tw_host_free(eng, ar.base);
-                ar.base = nullptr;
-                ar.cap = 0;
-                void* hp = nullptr;
-                // a full batch of this size (no regrowth), within the bound — for ordinary slots only
-                const size_t full = slot <= kArenaFullBatchSlot ? slot * 2 * (size_t)batch_ : need;
-                const size_t want = std::min(kArenaMax, std::max(need, full));
-                if (tw_host_alloc(eng, want, &hp) == TW_OK) {
-                    ar.base = (uint8_t*)hp;
-                    ar.cap = want;
-                }
-            };
-            bool fast = !op.empty();
-            size_t fslot = 0;
-            for (size_t i = 0; i < op.size(); i++) {
-                if (skipped(i)) continue;
-                const Opened& o = op[i];
-                fast = fast && o.rows_ok;
-                fslot = std::max(fslot, (o.st.total + 8 + 255) / 256 * 256);
-            }
-            fast = fast && fslot <= kArenaSlotMax;
-            if (fast) {
-                ensure_arena(fslot);
-                fast = ar.base && fslot * 2 * jobs.size() <= ar.cap;
-            }
-            if (fast) {
-                // Phase 2 (pool): inflate into the arena slot; every row's filter type is checked as libpng does
-                parallel_for(2 * jobs.size(), [&](size_t i) {
-                    if (skipped(i)) return;
-                    Opened& o = op[i];
-                    uint8_t* dst = ar.base + fslot * i;
-                    bool ok = png_inflate(o.st, dst);
-                    const size_t rs = o.st.row_bytes();  // the kind's row length
-                    for (int y = 0; y < o.st.h && ok; y++) ok = dst[(size_t)y * rs] <= 4;
-                    if (!ok) {
-                        const Staged& s = jobs[i >> 1];
-                        ((i & 1) ? eb : ea)[i >> 1] = "Can't open " + ((i & 1) ? s.req.target_image : s.req.expect_image);
-                    }
-                    std::vector<uint8_t>().swap(o.file);
-                    std::vector<uint8_t>().swap(o.st.idat);
-                });
-                bt1 = steady_ns();
-                for (size_t j = 0; j < jobs.size(); j++) {
-                    Staged& s = jobs[j];
-                    // (a resident expected image: its size is the cache entry's, or that of the pair that keeps it)
-                    const bool no_file = s.no_expected_file();
-                    if (no_file && s.leader >= 0 && !ea[(size_t)s.leader].empty()) ea[j] = "Can't open " + s.req.expect_image;
-                    const PngStream& sa = op[2 * (size_t)(no_file && s.leader >= 0 ? s.leader : (int)j)].st;
-                    const PngStream& sb = op[2 * j + 1].st;
-                    const int ew = no_file && s.leader < 0 ? s.w : sa.w, eh = no_file && s.leader < 0 ? s.h : sa.h;
-                    // the reference opens the expected image first: its error wins (src/opticalflow.cpp:26-48)
-                    if (!ea[j].empty()) { s.err = ea[j]; continue; }
-                    if (!eb[j].empty()) { s.err = eb[j]; continue; }
-                    s.w = ew;
-                    s.h = eh;
-                    s.ka = no_file ? PngKind() : sa.kind();
-                    s.kb = sb.kind();
-                    uint8_t* da = ar.base + fslot * (2 * j);
-                    uint8_t* db = da + fslot;
-                    if (ew == sb.w && eh == sb.h) {
-                        s.pa = da;
-                        s.pb = db;
-                        s.stride = s.w;
-                        continue;
-                    }
-                    if (abs(eh - sb.h) > 5 || abs(ew - sb.w) > 5) { s.err = "Don't match image size"; continue; }
-                    if (device_reconcile) {  // within 5 px: the pair stays in the arena, the device resizes the target
-                        s.pa = da;
-                        s.pb = db;
-                        s.stride = s.w;
-                        s.tw = sb.w;
-                        s.th = sb.h;
-                        continue;
-                    }
-                    // TW_DEVICE_RECONCILE=0: the reconcile of prepare() on the host, on copies outside the arena
-                    if (!no_file) s.a.assign(da, da + sa.total);
-                    s.b.assign(db, db + sb.total);
-                    prepare(s, sb.w, sb.h, std::string(), std::string(), false);
-                }
-            } else {
-            parallel_for(2 * jobs.size(), [&](size_t i) {
-                const size_t j = i >> 1;
-                decode_one(jobs[j], (int)(i & 1), &tw[j], &th[j], (i & 1) ? &eb[j] : &ea[j], device_png, png_kinds,
-                           device_jpeg && eng, op[i].read_ok ? &op[i].file : nullptr);
-                std::vector<uint8_t>().swap(op[i].file);
-            });
-            bt1 = steady_ns();
-            for (size_t j = 0; j < jobs.size(); j++) {  // (a pair behind the one that keeps its expected image: that one's size)
-                Staged& s = jobs[j];
-                if (!s.follower || s.leader < 0) continue;
-                if (!ea[(size_t)s.leader].empty()) ea[j] = "Can't open " + s.req.expect_image;
-                s.w = jobs[(size_t)s.leader].w;
-                s.h = jobs[(size_t)s.leader].h;
-            }
-            parallel_for(jobs.size(), [&](size_t j) { prepare(jobs[j], tw[j], th[j], ea[j], eb[j], device_reconcile); });
-            // The arena is sized AFTER prepare(), over the pairs that decoded and reconciled (a header with
-            // huge dimensions over a damaged stream must not size it), and it is bounded: a pair larger than
-            // kArenaSlotMax, or one the bounded arena has no room for, keeps its pageable buffers (tw_submit_u8 stages
-            // those itself — always correct, one memcpy slower).
-            size_t slot = 0;
-            for (const Staged& s : jobs) {
-                if (!s.err.empty() || s.req.raw.expect) continue;
-                // (an image is w * h gray bytes or, still filtered, h rows of its kind's PngKind::row_bytes(w))
-                const size_t nb = (std::max(s.a.size(), s.b.size()) + 255) / 256 * 256;
-                if (nb <= kArenaSlotMax) slot = std::max(slot, nb);
-            }
-            ensure_arena(slot);
-            parallel_for(jobs.size(), [&](size_t j) {
-                Staged& s = jobs[j];
-                if (!s.err.empty() || s.req.raw.expect || !ar.base || !slot) return;
-                if (std::max(s.a.size(), s.b.size()) > slot || (2 * j + 2) * slot > ar.cap) return;  // stays pageable
-                uint8_t* da = ar.base + slot * (2 * j);
-                uint8_t* db = da + slot;
-                if (!s.a.empty()) memcpy(da, s.a.data(), s.a.size());
-                memcpy(db, s.b.data(), s.b.size());
-                s.pa = da;
-                s.pb = db;
-                std::vector<uint8_t>().swap(s.a);
-                std::vector<uint8_t>().swap(s.b);
-            });
-            }  // !fast
-        }
-        bt2 = steady_ns();
-        // one engine batch is homogeneous in size: group equal sizes so that a mixed queue makes few batches
-        // (responses are delivered in completion order anyway, like the reference's)
-        std::stable_sort(jobs.begin(), jobs.end(), [](const Staged& x, const Staged& y) {
-            return x.w != y.w ? x.w < y.w : x.h < y.h;
-        });
-        for (size_t k = 0; k < jobs.size(); k++) {
-            Staged& s = jobs[k];
-            if (s.err.empty() && !eng) s.err = eng_err;
-            if (!s.err.empty()) continue;
-            auto rows_of = [](const uint8_t* p, int w, int h, const PngKind& k) {
-                tw_png_rows r;
-                r.rows = p;
-                r.width = w;
-                r.height = h;
-                r.color_type = k.color_type;
-                r.bit_depth = k.bit_depth;
-                r.palette = k.plte.empty() ? nullptr : k.plte.data();
-                r.palette_entries = (int)(k.plte.size() / 3);
-                return r;
-            };
-            auto luma_of = [](const uint8_t* p, int w, int h, const Staged::JpegHead& jh) {
-                tw_jpeg_luma l;
-                l.coef = jh.on() ? (const int16_t*)p : nullptr;
-                l.gray = jh.on() ? nullptr : p;
-                l.width = w;
-                l.height = h;
-                l.blocks_w = jh.bw;
-                l.blocks_h = jh.bh;
-                memcpy(l.quant, jh.quant, sizeof(l.quant));
-                return l;
-            };
-            // A pair behind one that was to keep its expected image, and that one failed before it did (its target, the
-            // sizes): this pair is decoded again on its own, expected file included, and goes the ordinary way
-            if (s.follower && !s.keep->img && !res_cache.count(s.rkey)) {
-                s.follower = false;
-                s.leader = -1;
-                s.keep = std::make_shared<Staged::Keep>();
-                s.a.clear();
-                s.b.clear();
-                s.ka = s.kb = PngKind();
-                s.ja = s.jb = Staged::JpegHead();
-                s.tw = s.th = 0;
-                int tw1 = 0, th1 = 0;
-                std::string ea1, eb1;
-                decode_one(s, 0, &tw1, &th1, &ea1, device_png, png_kinds, false, nullptr);
-                decode_one(s, 1, &tw1, &th1, &eb1, device_png, png_kinds, false, nullptr);
-                prepare(s, tw1, th1, ea1, eb1, device_reconcile);
-                if (!s.err.empty()) continue;
-            }
-            auto submit = [&]() -> tw_status {
-                // the expected image is resident: only the target goes up, in whatever form it was decoded to
-                tw_image* use = s.hit ? s.hit->img : nullptr;
-                if (!use && s.follower) {
-                    use = s.keep->img;
-                    s.uses_keep = use != nullptr;
-                    if (!use)
-                        if (ResEntry* en = res_lookup(s.rkey, s.req.expect_image)) use = en->img;
-                }
-                if (use) {
-                    const int tw_ = s.tw ? s.tw : s.w, th_ = s.tw ? s.th : s.h;
-                    if (s.jb.on()) {
-                        const tw_jpeg_luma lb = luma_of(s.pb, tw_, th_, s.jb);
-                        return tw_submit_image_jpeg(eng, use, &lb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
-                    }
-                    const tw_png_rows rb = rows_of(s.pb, tw_, th_, s.kb);
-                    return tw_submit_image_png(eng, use, &rb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
-                }
-                // half-decoded PNG(s): the device reconstructs the scanlines, and resizes a target within 5 px of the pair's size
-                if (s.ka.rows() || s.kb.rows()) {
-                    const tw_png_rows ra = rows_of(s.pa, s.w, s.h, s.ka);
-                    const tw_png_rows rb = rows_of(s.pb, s.tw ? s.tw : s.w, s.tw ? s.th : s.h, s.kb);
-                    return tw_submit_png(eng, &ra, &rb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
-                }
-                // JPEG(s) that stopped at the coefficient plane: the device runs the inverse DCT (and the reconcile)
-                if (s.ja.on() || s.jb.on()) {
-                    const tw_jpeg_luma la = luma_of(s.pa, s.w, s.h, s.ja);
-                    const tw_jpeg_luma lb = luma_of(s.pb, s.tw ? s.tw : s.w, s.tw ? s.th : s.h, s.jb);
-                    return tw_submit_jpeg(eng, &la, &lb, s.req.span, s.req.threshold, nullptr, nullptr, &s.ticket);
-                }
-                if (s.tw)
-                    return tw_submit_u8_sized(eng, s.pa, s.w, s.h, s.stride, s.pb, s.tw, s.th, s.tw, s.req.span, s.req.threshold,
-                                              nullptr, nullptr, &s.ticket);
-                return tw_submit_u8(eng, s.pa, s.pb, s.w, s.h, s.stride, s.req.span, s.req.threshold, &s.ticket);
-            };
-            tw_status r = submit();
-            if (r == TW_E_BUSY) {
-                // every batch context of the engine is owed to us (each size change opens one): collect what
-                // is outstanding, then this job starts a fresh batch
-                finish_all(prev2);
-                finish_all(prev);
-                for (size_t q = 0; q < k; q++) finish(jobs[q]);
-                r = submit();
-            }
-            if (r == TW_OK) {
-                s.submitted = true;
-                if (shared_) shared_->inflight++;
-                // a miss: the image the batch sees stays on the device (one device-to-device copy behind its decode), and
-                // enters the cache when the pair has answered OK
-                if (resident_on && !s.rkey.empty() && !s.no_expected_file() && s.keep) {
-                    if (tw_image_keep(eng, s.ticket, TW_KEEP_EXPECT, &s.kept) == TW_OK) {
-                        s.keep->img = s.kept;
-                        s.keep->w = s.w;
-                        s.keep->h = s.h;
-                        res_pending[s.rkey] = s.keep;
-                    } else s.kept = nullptr;
-                }
-            } else s.err = std::string(tw_last_error(eng)[0] ? tw_last_error(eng) : tw_strerror(r));
-        }
-        for (Staged& s : jobs)  // (submitted or refused: the batch holds the image now, the cache entry may go)
-            if (s.hit) {
-                s.hit->pins--;
-                s.hit = nullptr;
-            }
-        res_sweep();
-        if (eng) (void)tw_flush(eng);  // a partly filled batch starts now, not when its first result is asked for
-        bt3 = steady_ns();
-        const size_t njobs = jobs.size();
-        for (Staged& s : jobs)
-            if (!s.submitted) finish(s);  // errors do not wait for the GPU
-        finish_all(prev2);  // the batch before the previous one: its results have had two batches' time to arrive
-        prev2 = std::move(prev);
-        prev = std::move(jobs);
-        if (batch_time)
-            fprintf(stderr, "twhost: consumer %d batch of %zu: decode %.2f ms, prepare + arena %.2f, submit + flush %.2f, "
-                            "previous batch's results %.2f\n", id_, njobs, (bt1 - bt0) * 1e-6, (bt2 - bt1) * 1e-6,
-                    (bt3 - bt2) * 1e-6, (steady_ns() - bt3) * 1e-6);
+        out.pushedNs = mine.lastResponseNs;
+        res.push(std::move(out));
     }
-    finish_all(prev2);
-    finish_all(prev);
-    read_prof(true);
-    publish();
-    while (!res_lru.empty()) res_evict(res_lru.back());  // Manager::stop: every resident image goes back
-    res_sweep();
-    for (Arena& ar : arena)
-        if (eng && ar.base) (void)tw_host_free(eng, ar.base);
-    if (eng) tw_engine_destroy(eng);
-    TW_LOGF("finish consumer%d\n", id_);  // src/consumer.cpp:92
+    void collect_all(std::vector<Staged>& v)
+    {
+        for (Staged& s : v) collect(s);
+        v.clear();
+    }
+
+    void shut_down()
+    {
+        collect_all(prev2);
+        collect_all(prev);
+        read_prof(true);
+        publish();
+        cache.reset();  // Manager::stop: every resident image goes back, while the engine exists
+        for (Arena& ar : arena)
+            if (eng && ar.base) (void)tw_host_free(eng, ar.base);
+        if (eng) tw_engine_destroy(eng);
+        TW_LOGF("finish consumer%d\n", id);  // src/consumer.cpp:92
+    }
+};
+}  // namespace
+
+void Consumer::run()
+{
+    ConsumerRun c(id_, req_, res_, params_, batch_, decode_threads_, n_consumers_, shared_);
+    c.bind_device_and_numa();
+    c.create_engine();
+    for (;;) {
+        c.deliver_down_to_share();
+        Batch b;
+        if (!c.take_batch(b)) break;
+        c.match_resident(b);
+        c.open_files(b);
+        if (c.arena_from_headers(b)) {
+            c.inflate_into_arena(b);
+            c.stage_from_arena(b);
+        } else {
+            c.decode_and_copy(b);
+        }
+        c.sort_by_size(b);
+        for (size_t k = 0; k < b.jobs.size(); k++) c.submit_pair(b, k);
+        c.unpin_and_flush(b);
+        c.deliver_refused_and_rotate(b);
+    }
+    c.shut_down();
 }
+
 
 // ---------------------------------------------------------------------------------------------------
 // Manager

@@ -1,0 +1,86 @@
+// consumer_probe.cpp — one twhost::Consumer on the stub backend (host/stub_twflow.cpp), fed so that what it does is the
+// same from run to run: every request is queued BEFORE the thread starts, so the takes are batch, batch, ... and the tail,
+// and every engine call comes from the one consumer thread.  With TW_STUB_TRACE set the stub records those calls; this
+// program prints the other half of the result, the responses in arrival order.  tools/consumer_trace.py builds and runs it
+// (against any commit's twhost.cpp); tests/test_host_consumer_steps.py asserts on a subset of its cases.
+//
+//   consumer_probe <decode threads> <resident budget, bytes> <batch> <script ...>
+//     R <expected> <target>                  a pair of files
+//     M <w> <h> <first a> <first b>          an in-memory pair (gray, filled with 7 except for pixel 0)
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../tidal-wave_amd/host/twhost.h"
+
+using namespace twhost;
+extern "C" void tw_stub_resident_calls(long* kept, long* image_pairs, long* released);
+
+int main(int argc, char** argv)
+{
+    if (argc < 4) return 2;
+    const int decode_threads = atoi(argv[1]);
+    const long long budget = atoll(argv[2]);
+    const int batch = atoi(argv[3]);
+    MessageQueue<Request> req;
+    MessageQueue<Response> res;
+    ConsumerShared shared;
+    shared.residentBytes = budget;
+    shared.stats.assign(1, ConsumerStats());
+    tw_params params;
+    tw_default_params(&params);
+    std::vector<std::unique_ptr<std::vector<uint8_t>>> raw;
+    int asked = 0;
+    for (int i = 4; i < argc; i++) {
+        const std::string op = argv[i];
+        Request r;
+        r.threshold = 5.0;
+        r.span = 10;
+        if (op == "R" && i + 2 < argc) {
+            r.expect_image = argv[i + 1];
+            r.target_image = argv[i + 2];
+            i += 2;
+        } else if (op == "M" && i + 4 < argc) {
+            const int w = atoi(argv[i + 1]), h = atoi(argv[i + 2]);
+            for (int q = 0; q < 2; q++) {
+                raw.emplace_back(new std::vector<uint8_t>((size_t)w * (size_t)h, 7));
+                (*raw.back())[0] = (uint8_t)atoi(argv[i + 3 + q]);
+            }
+            r.expect_image = "raw_expected_" + std::to_string(asked);
+            r.target_image = "raw_target_" + std::to_string(asked);
+            r.raw.expect = raw[raw.size() - 2]->data();
+            r.raw.target = raw[raw.size() - 1]->data();
+            r.raw.width = w;
+            r.raw.height = h;
+            r.raw.stride = w;
+            i += 4;
+        } else {
+            fprintf(stderr, "bad script at %s\n", argv[i]);
+            return 2;
+        }
+        req.push(std::move(r));
+        asked++;
+    }
+    {
+        Consumer c(0, req, res, params, batch, decode_threads, 1, &shared);
+        c.start();
+        for (int k = 0; k < asked; k++) {
+            Response r;
+            if (!res.tryPop(r)) return 3;
+            printf("%s|%s|%s|%s|%dx%d|span %d|threshold %g|", r.status.c_str(), r.reason.c_str(), r.expect_image.c_str(),
+                   r.target_image.c_str(), r.width, r.height, r.span, r.threshold);
+            for (const Vector& v : r.vectors) printf(" (%d,%d,%g,%g)", v.x, v.y, v.dx, v.dy);
+            printf("\n");
+        }
+        req.stop();
+        c.join();
+    }
+    long kept = 0, pairs = 0, released = 0;
+    tw_stub_resident_calls(&kept, &pairs, &released);
+    printf("stopped|kept %ld|image_pairs %ld|released %ld|inflight %ld|pairs %ld|batches %ld\n", kept, pairs, released,
+           shared.inflight.load(), shared.stats[0].pairs, shared.stats[0].batches);
+    return 0;
+}

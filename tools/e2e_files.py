@@ -15,7 +15,7 @@ through host/index.js create() (addon -> decode pool -> libtwflow.so) and prints
              targets stay hard links): what a cache keyed by a file's identity needs to see N baselines instead of four
   --passes   K passes over the same pairs through ONE long-lived TidalWave instance (calc() per pair, dispose() after the
              last pass) instead of one create() run; pairs/s per pass, and with TW_DEBUG_BATCHTIME=1 in the environment the
-             mean of the batches' "decode" column per pass
+             mean of the batches' "decode", "prepare + arena" and "submit + flush" columns per pass
   --resident MB   the instance's residentMB option (resident expected images; implies --passes 2 unless given): pass 1 is
              all misses, pass 2 all hits when the budget holds the corpus (1080p: 2 MB per expected file)
   --kernel-time   no files: tw_png_unfilter per 1080p image for RGBA, palette-8 and 1-bit gray rows, event-timed
@@ -140,15 +140,19 @@ def main():
     out = json.loads(r.stdout.strip().splitlines()[-1])
     if passes:
         # per pass: pairs/s and, from TW_DEBUG_BATCHTIME's lines, the mean "decode" milliseconds of a batch
-        decode, cur = {}, 0
+        decode, prep, submit, cur = {}, {}, {}, 0
         for line in r.stderr.splitlines():
             if line.startswith("TWE2E PASS "):
                 cur = int(line.split()[-1])
             elif ": decode " in line and cur:
                 decode.setdefault(cur, []).append(float(line.split(": decode ")[1].split(" ms")[0]))
+                prep.setdefault(cur, []).append(float(line.split("prepare + arena ")[1].split(",")[0]))
+                submit.setdefault(cur, []).append(float(line.split("submit + flush ")[1].split(",")[0]))
         res = {"corpus": a.corpus, "pairs": n, "copies": a.copies, "resident_mb": a.resident, "host": os.path.relpath(a.host, ROOT),
                "pairs_per_s": [round(n / (ms / 1e3), 1) for ms in out["pass_ms"]], "pass_ms": out["pass_ms"],
                "decode_ms_per_batch": [round(statistics.mean(decode[k]), 2) if k in decode else None for k in range(1, passes + 1)],
+               "prepare_arena_ms_per_batch": [round(statistics.mean(prep[k]), 2) if k in prep else None for k in range(1, passes + 1)],
+               "submit_flush_ms_per_batch": [round(statistics.mean(submit[k]), 2) if k in submit else None for k in range(1, passes + 1)],
                "batches": [len(decode.get(k, [])) for k in range(1, passes + 1)], "report": out["report"], "errors": out["errors"]}
         print(json.dumps(res) if a.json else "\n".join("%s: %s" % kv for kv in res.items()))
         return
