@@ -333,6 +333,51 @@ tw_status tw_submit_image_png(tw_engine* e, const tw_image* expect, const tw_png
 tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* expect, const tw_jpeg_luma* target, int span, double threshold,
                                const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket);
 
+/* Ignore regions (additive within ABI 4, detected by the symbols).  The tw_submit_*_ignore calls are tw_submit_u8_sized /
+ * tw_submit_png / tw_submit_jpeg / tw_submit_image_png / tw_submit_image_jpeg plus rectangles of the pair that may differ — a
+ * clock, an ad slot, a blinking cursor.  Inside every rectangle the target's pixels are replaced by the expected image's
+ * pixels at the same coordinates, on the device (kernel tw_mask_rects, one launch per batch on the copy stream where
+ * tw_png_unfilter runs: it is not in `seconds`), after tw_png_unfilter, tw_jpeg_idct and tw_resize_u8 and before anything
+ * else reads the target: the result equals tw_submit_u8 on the host-decoded, host-resized, host-edited target bit for bit —
+ * vectors, status, the dense field of `out`, the effect of `init`.  A pair that differs only inside its rectangles is an
+ * identical pair to everything downstream.  Only the target is written: a resident expected image stays valid whatever
+ * rectangles later pairs name.
+ * Rectangles are in pair coordinates (the expected image's) and are read before the call returns.  Each is clipped to the
+ * pair's image: x and y may be negative, x + width is computed in 64 bits, and a rectangle that is empty after clipping
+ * (zero area, or wholly outside) is accepted and does nothing.  Rectangles may overlap or touch.
+ * n_ignore == 0 (ignore may be NULL): the call IS the plain call — the same launches, copies and events, no tw_mask_rects
+ * launch, a batch that may ramp as before; so is a call all of whose rectangles are empty after clipping.
+ * Refused with TW_E_BAD_PARAMETER before anything is queued (no ticket consumed, the open batch unchanged): n_ignore < 0 or
+ * above TW_MAX_IGNORE, n_ignore > 0 with ignore == NULL, a negative width or height.
+ * A vector whose grid point (x, y) lies inside a clipped rectangle of its pair is not reported: *n of tw_wait counts what
+ * is left (with out == NULL as well), and `out` of tw_wait receives the first min(*n, cap) of those.  (The flow there is
+ * generally not zero — changes outside reach in through the window — but "ignore" means "do not report from here".)  The
+ * dense field of a tw_flow_out is not touched.
+ * A masked pair joins the open batch of ordinary host pairs of its size, span and threshold; a batch with at least one
+ * masked pair is launched as a PNG batch is: no cold-start ramp.  tw_image_keep(.., TW_KEEP_TARGET, ..) of a masked pair
+ * keeps the target as the batch sees it, after the mask; keeping an expected image is unaffected.  Device pairs
+ * (tw_submit_dev*) are read in place and never written: they have no _ignore call, nor have tw_flow_u8 and tw_diff_u8. */
+typedef struct tw_rect {
+    int x, y, width, height; /* pair coordinates = the expected image's */
+} tw_rect;
+enum { TW_MAX_IGNORE = 32 };
+tw_status tw_submit_u8_ignore(tw_engine* e, const uint8_t* expect, int width, int height, ptrdiff_t stride,
+                              const uint8_t* target, int target_width, int target_height, ptrdiff_t target_stride,
+                              int span, double threshold, const tw_flow_in* init, const tw_flow_out* out,
+                              const tw_rect* ignore, int n_ignore, tw_ticket* ticket);
+tw_status tw_submit_png_ignore(tw_engine* e, const tw_png_rows* expect, const tw_png_rows* target, int span,
+                               double threshold, const tw_flow_in* init, const tw_flow_out* out, const tw_rect* ignore,
+                               int n_ignore, tw_ticket* ticket);
+tw_status tw_submit_jpeg_ignore(tw_engine* e, const tw_jpeg_luma* expect, const tw_jpeg_luma* target, int span,
+                                double threshold, const tw_flow_in* init, const tw_flow_out* out, const tw_rect* ignore,
+                                int n_ignore, tw_ticket* ticket);
+tw_status tw_submit_image_png_ignore(tw_engine* e, const tw_image* expect, const tw_png_rows* target, int span,
+                                     double threshold, const tw_flow_in* init, const tw_flow_out* out,
+                                     const tw_rect* ignore, int n_ignore, tw_ticket* ticket);
+tw_status tw_submit_image_jpeg_ignore(tw_engine* e, const tw_image* expect, const tw_jpeg_luma* target, int span,
+                                      double threshold, const tw_flow_in* init, const tw_flow_out* out,
+                                      const tw_rect* ignore, int n_ignore, tw_ticket* ticket);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 
@@ -464,6 +509,14 @@ tw_status tw_stage_resize_u8(tw_engine* e, const uint8_t* src, int sw, int sh, u
  * entry point set to 0xA5 before the launch — a byte that is not 0xA5 was written outside the image.  (Additive within
  * version 4.) */
 tw_status tw_stage_jpeg_idct(tw_engine* e, const tw_jpeg_luma* img, uint8_t* gray, uint8_t* guard);
+/* The tw_submit_*_ignore calls' kernel alone (tw_mask_rects) on two dense gray images of w x h, placed as a batch places
+ * them (256-byte aligned slots, dense rows of w bytes): `out` receives the edited target, w * h bytes.  `guard`, if not
+ * NULL, receives 512 bytes: the 256 device bytes in front of the target's slot and the 256 behind it, which the entry point
+ * set to 0xA5 before the launch.  The slot's own padding behind the image is checked by the entry point (TW_E_DEVICE when
+ * a byte of it was written).  The argument checks and the clipping of the submit calls; no launch when no rectangle is
+ * left.  (Additive within version 4.) */
+tw_status tw_stage_mask_rects(tw_engine* e, const uint8_t* expect, const uint8_t* target, int w, int h,
+                              const tw_rect* ignore, int n_ignore, uint8_t* out, uint8_t* guard);
 tw_status tw_stage_polyexp(tw_engine* e, const float* I, int w, int h, float* R5);
 tw_status tw_stage_update_matrices(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow2,
                                    int w, int h, float* M5);

@@ -68,6 +68,7 @@ enum tw_debug_family {
     TW_DF_BLUR_SOLVE4Q,    /* tw_blur_solve4q: solve + refresh by the horizontal item's owner — a single pair's level-0 launches (round 6) */
     TW_DF_FLOW_ITER_GRID,  /* tw_flow_iter<15, 3>: a batch's last level-0 iteration at the span-grid points only — ALSO counted in TW_DF_FLOW_ITER */
     TW_DF_JPEG_IDCT,       /* tw_jpeg_idct: a batch's JPEG luma blocks -> gray images (tw_submit_jpeg) */
+    TW_DF_MASK_RECTS,      /* tw_mask_rects: a batch's ignore rectangles, expected image -> target (tw_submit_*_ignore) */
     TW_DF_PAIR_SAME,       /* tw_pair_same: which pairs of a batch part have two byte-identical images */
     TW_DF_RESIZE_U8,       /* tw_resize_u8: a target within 5 px of its pair's size -> the pair's size (tw_submit_*_sized) */
     TW_DF_FLOW_INIT,       /* tw_flow_area_init: tw_submit_*_flow_init fields -> the coarsest level's first flow (zeros without one) */

@@ -346,6 +346,8 @@ constexpr int NCTX = 3;          // batches that may be in flight (host-side sta
 constexpr size_t png_table_bytes(int cap) { return (sizeof(PngJob) + sizeof(unsigned) + 256) * 2 * (size_t)cap; }
 // tw_jpeg_idct's table of such a batch: per image a job and a quantisation table
 constexpr size_t jpeg_table_bytes(int cap) { return (sizeof(JpegJob) + 128) * 2 * (size_t)cap; }
+// tw_mask_rects' table of such a batch: a job per rectangle
+constexpr size_t mask_table_bytes(int cap) { return sizeof(MaskJob) * TW_MAX_IGNORE * (size_t)cap; }
 
 struct Job {
     const uint8_t *h_a = nullptr, *h_b = nullptr;  // host inputs already staged (null for device inputs)
@@ -375,6 +377,8 @@ struct Job {
     long long tstride = 0;
     int rkind = 0;
     const uint8_t* t_src = nullptr;
+    // tw_submit_*_ignore: the pair's rectangles, clipped to the pair's image, the empty ones dropped (x, y, width, height >= 1)
+    std::vector<tw_rect> ign;
 };
 enum { RSZ_NONE = 0, RSZ_SUBMIT = 1, RSZ_FLUSH_COPY = 2, RSZ_FLUSH_DEV = 3 };
 
@@ -456,6 +460,10 @@ struct Ctx {
     PngJob *d_rpng = nullptr, *h_rpng = nullptr;   // [cap]
     bool any_resize = false, any_resize_png = false, any_resize_dev = false;
     bool any_keep = false;  // a job of the open batch has a tw_image_keep copy to queue at launch
+    // tw_submit_*_ignore (both tables created on the first pair with a non-empty rectangle of this context,
+    // mask_table_bytes(cap) long): tw_mask_rects' jobs, one per rectangle of the batch
+    MaskJob *d_msk = nullptr, *h_msk = nullptr;  // h_msk pinned
+    bool any_mask = false;
 
     // the batch is collected or dropped: its resident images may return to the store
     void release_images()
@@ -485,6 +493,7 @@ struct Ctx {
         any_jpeg = false;
         jpg_quants.clear();
         any_resize = any_resize_png = any_resize_dev = false;
+        any_mask = false;
         filt_slot = 0;
         nseg = 0;
         first_ticket = first;
@@ -806,6 +815,36 @@ tw_status queue_keep_copy(tw_engine* e, tw_image* im, const uint8_t* src, long l
 dim3 jpeg_idct_grid(int w, int h, int nimg)
 {
     return dim3((unsigned)((w + 8 * JPEG_WG_BLOCKS - 1) / (8 * JPEG_WG_BLOCKS)), (unsigned)((h + 7) / 8), (unsigned)nimg);
+}
+
+// tw_mask_rects' grid for `nrect` rectangles of up to w x h pixels: a workgroup takes 64 aligned dwords of MASK_ROWS rows; a
+// row of w bytes that starts anywhere in a dword touches at most (w + 6) / 4 dwords
+dim3 mask_rects_grid(int w, int h, int nrect)
+{
+    return dim3((unsigned)(((w + 6) / 4 + 63) / 64), (unsigned)((h + MASK_ROWS - 1) / MASK_ROWS), (unsigned)nrect);
+}
+
+// The rectangles of a tw_submit_*_ignore / tw_stage_mask_rects call, clipped to a w x h image; the empty ones are dropped.
+// Refuses what the calls refuse (include/twflow.h); no HIP call.
+tw_status clip_ignore(tw_engine* e, const tw_rect* ignore, int n_ignore, int w, int h, std::vector<tw_rect>* out)
+{
+    out->clear();
+    if (n_ignore < 0 || n_ignore > TW_MAX_IGNORE || (n_ignore > 0 && !ignore)) {
+        e->err = "bad ignore rectangles (a count outside 0 .. TW_MAX_IGNORE, or a null table)";
+        return TW_E_BAD_PARAMETER;
+    }
+    for (int i = 0; i < n_ignore; i++)
+        if (ignore[i].width < 0 || ignore[i].height < 0) {
+            e->err = "bad ignore rectangle (negative width or height)";
+            return TW_E_BAD_PARAMETER;
+        }
+    for (int i = 0; i < n_ignore; i++) {
+        const tw_rect& r = ignore[i];
+        const long long x0 = std::max<long long>(r.x, 0), x1 = std::min<long long>((long long)r.x + r.width, w);
+        const long long y0 = std::max<long long>(r.y, 0), y1 = std::min<long long>((long long)r.y + r.height, h);
+        if (x0 < x1 && y0 < y1) out->push_back(tw_rect{(int)x0, (int)y0, (int)(x1 - x0), (int)(y1 - y0)});
+    }
+    return TW_OK;
 }
 
 // One row of tw_resize_u8's job table: sw x sh at src -> dw x dh at dst, with cv::resize's scales (inv_scale = (double)dsize /
@@ -2497,6 +2536,57 @@ struct BatchEnqueue {
         return TW_OK;
     }
 
+    // tw_submit_*_ignore: inside every rectangle of the batch the target becomes the expected image, in one launch on the copy
+    // stream — behind the uploads, tw_jpeg_idct, tw_png_unfilter and the targets' resizes, in front of the kept copies and of
+    // ev_h2d: whatever reads a target afterwards (tw_pair_same first) reads the masked one.  Only targets are written: a
+    // resident expected image stays what it is.
+    // A frame sequence inside one batch: the expected image of a masked pair may be an image that tw_image_keep is still to
+    // copy out of an earlier pair's slot (Job::keep: queued behind this step).  The source is then that slot itself; and when
+    // the slot is a masked TARGET, this pair's rectangles wait for that pair's: they go into a later launch (round = that
+    // pair's round + 1).  Every other batch has one round, one launch.
+    tw_status enqueue_mask_rects()
+    {
+        if (!c.any_mask) return TW_OK;
+        std::vector<int> round(n, 0);
+        std::vector<const uint8_t*> src(n, nullptr);
+        int rounds = 1;
+        for (int j = 0; j < n; j++) {
+            const Job& jb = c.jobs[j];
+            if (jb.ign.empty()) continue;
+            src[j] = jb.res ? jb.res->d : c.d_img + npx * (size_t)(2 * j);
+            for (int k = 0; jb.res && c.any_keep && k < j; k++)
+                for (int q = 0; q < 2; q++)
+                    if (c.jobs[k].keep[q] == jb.res) {
+                        src[j] = c.d_img + npx * (size_t)(2 * k + q);
+                        if (q == 1 && !c.jobs[k].ign.empty()) round[j] = round[k] + 1;
+                    }
+            rounds = std::max(rounds, round[j] + 1);
+        }
+        int nr = 0;
+        std::vector<int> first(rounds + 1, 0), wmax(rounds, 1), hmax(rounds, 1);
+        for (int r = 0; r < rounds; r++) {
+            first[r] = nr;
+            for (int j = 0; j < n; j++) {
+                if (round[j] != r) continue;
+                for (const tw_rect& rc : c.jobs[j].ign) {
+                    c.h_msk[nr++] = MaskJob{c.d_img + npx * (size_t)(2 * j + 1), src[j], rc.x, rc.y, rc.x + rc.width, rc.y + rc.height,
+                                            (long long)c.w};
+                    wmax[r] = std::max(wmax[r], rc.width);
+                    hmax[r] = std::max(hmax[r], rc.height);
+                }
+            }
+        }
+        first[rounds] = nr;
+        TW_HIP(e, hipMemcpyAsync(c.d_msk, c.h_msk, sizeof(MaskJob) * (size_t)nr, hipMemcpyHostToDevice, e->copy_stream));
+        for (int r = 0; r < rounds; r++) {
+            MaskArgs ma;
+            ma.jobs = c.d_msk + first[r];
+            TW_LAUNCH(e, TW_DF_MASK_RECTS, tw_mask_rects, mask_rects_grid(wmax[r], hmax[r], first[r + 1] - first[r]),
+                      dim3(64, MASK_ROWS), 0, e->copy_stream, ma);
+        }
+        return TW_OK;
+    }
+
     // tw_image_keep of images this batch's decode launches write: their copies, on the copy stream behind those launches
     // and in front of ev_h2d (a pair of this very batch may read the kept image)
     tw_status enqueue_kept_copies()
@@ -2524,7 +2614,7 @@ struct BatchEnqueue {
         // pause, or a pipeline the host cannot keep filled) — the pairs whose uploads are already marked start now, the
         // rest behind their own marks, instead of all of them behind the batch's last upload (531 MB for 128 pairs of
         // 1080p: ~14 ms of an idle GPU).  A busy stream takes the whole batch in one launch per kernel and level, as before.
-        if (e->ramp && e->lanes == 1 && !c.any_png && !c.any_jpeg && c.nseg > 0 && c.seg_at[0] < n) {
+        if (e->ramp && e->lanes == 1 && !c.any_png && !c.any_jpeg && !c.any_mask && c.nseg > 0 && c.seg_at[0] < n) {
             bool idle = true;
             for (Ctx& o : e->ctx)
                 if (&o != &c && o.launched && hipEventQuery(o.ev_done) == hipErrorNotReady) idle = false;
@@ -3134,6 +3224,7 @@ tw_status flush_ctx(tw_engine* e, Ctx& c)
     RoctxRange batch_range("tw_batch %dx%d pairs=%d", c.w, c.h, b.n);
     TW_TRY(b.enqueue_jpeg_idct());
     TW_TRY(b.enqueue_png_unfilter());
+    TW_TRY(b.enqueue_mask_rects());
     TW_TRY(b.enqueue_kept_copies());
     TW_TRY(b.mark_uploads_and_plan_ramp());
     TW_TRY(b.upload_tables());
@@ -3361,6 +3452,9 @@ struct Submission {
     ptrdiff_t t_stride = 0;
     const tw_flow_out* fo = nullptr;  // tw_submit_*_flow: where the pair's final flow goes, null for the plain calls
     const tw_flow_in* fi = nullptr;   // tw_submit_*_flow_init: the field the pair starts from, null for a zero start
+    // tw_submit_*_ignore: rectangles (pair coordinates) inside which the target becomes the expected image; 0 = the plain call
+    const tw_rect* ignore = nullptr;
+    int n_ignore = 0;
     tw_ticket* ticket = nullptr;
 };
 
@@ -3452,6 +3546,12 @@ struct Submit {
         const bool png_ok = host && s.h_b && s.ch_a >= 0 && s.ch_a <= 4 && s.ch_b >= 0 && s.ch_b <= 4;
         if (s.span < 0 || s.stride < s.width || tstride < tw || (!host && !s.d_a) || (!s.h_b && !s.d_b) || (s.res && !s.h_b) ||
             ((png || jpeg) && (!png_ok || s.stride != s.width || tstride != tw))) {
+            e->err = "bad argument";
+            return TW_E_BAD_PARAMETER;
+        }
+        // (the rectangles are read here, before the call returns; only host pairs have an _ignore call)
+        TW_TRY(clip_ignore(e, s.ignore, s.n_ignore, s.width, s.height, &jb.ign));
+        if (!jb.ign.empty() && !host) {
             e->err = "bad argument";
             return TW_E_BAD_PARAMETER;
         }
@@ -3554,6 +3654,7 @@ struct Submit {
         jb.tstride = s.h_a ? (long long)tw : (long long)tstride;
         if (resize) TW_TRY(reserve_resize_tables());
         if (jpeg) TW_TRY(reserve_jpeg_tables());
+        if (!jb.ign.empty()) TW_TRY(reserve_mask_tables());
         if (!host) return resize ? stage_device_target() : TW_OK;
         const size_t npx = staged_image_bytes(s.width, s.height);
         // (grows only on the first job of a batch: all jobs of a batch have one size)
@@ -3573,6 +3674,14 @@ struct Submit {
         if (!c->h_jpg) TW_HIP(e, hipHostMalloc((void**)&c->h_jpg, jpeg_table_bytes(e->cap), hipHostMallocDefault));
         if (!c->d_jpg) TW_HIP(e, hipMalloc((void**)&c->d_jpg, jpeg_table_bytes(e->cap) + 256));
         c->jpg_quants.reserve(2 * (size_t)e->cap);
+        return TW_OK;
+    }
+
+    // what tw_mask_rects needs once per context
+    tw_status reserve_mask_tables()
+    {
+        if (!c->h_msk) TW_HIP(e, hipHostMalloc((void**)&c->h_msk, mask_table_bytes(e->cap), hipHostMallocDefault));
+        if (!c->d_msk) TW_HIP(e, hipMalloc((void**)&c->d_msk, mask_table_bytes(e->cap) + 256));
         return TW_OK;
     }
 
@@ -3755,6 +3864,7 @@ struct Submit {
         c->any_fout_host = c->any_fout_host || fo_host;
         c->any_init = c->any_init || s.fi;
         c->any_init_host = c->any_init_host || fi_kind != 0;
+        c->any_mask = c->any_mask || !jb.ign.empty();
         if (jb.res) jb.res->uses++;
         c->jobs.push_back(jb);
         c->pending++;
@@ -4036,6 +4146,8 @@ void tw_engine_destroy(tw_engine* e)
         if (c.h_png) (void)hipHostFree(c.h_png);
         if (c.d_jpg) (void)hipFree(c.d_jpg);
         if (c.h_jpg) (void)hipHostFree(c.h_jpg);
+        if (c.d_msk) (void)hipFree(c.d_msk);
+        if (c.h_msk) (void)hipHostFree(c.h_msk);
         if (c.h_pflag) (void)hipHostFree(c.h_pflag);
         if (c.ev_h2d) (void)hipEventDestroy(c.ev_h2d);
         for (hipEvent_t ev : c.ev_seg)
@@ -4165,6 +4277,19 @@ tw_status tw_submit_u8_sized(tw_engine* e, const uint8_t* expect, int width, int
                       .t_stride = target_stride, .fo = out, .fi = init, .ticket = ticket});
 }
 
+// (without rectangles: exactly the Submission tw_submit_u8_sized builds)
+tw_status tw_submit_u8_ignore(tw_engine* e, const uint8_t* expect, int width, int height, ptrdiff_t stride,
+                              const uint8_t* target, int target_width, int target_height, ptrdiff_t target_stride, int span,
+                              double threshold, const tw_flow_in* init, const tw_flow_out* out, const tw_rect* ignore,
+                              int n_ignore, tw_ticket* ticket)
+{
+    if (!expect || !target || target_width < 1 || target_height < 1 || target_stride < 1) return TW_E_BAD_PARAMETER;
+    return submit(e, {.h_a = expect, .h_b = target, .width = width, .height = height, .stride = stride, .span = span,
+                      .threshold = threshold, .t_width = target_width, .t_height = target_height,
+                      .t_stride = target_stride, .fo = out, .fi = init, .ignore = ignore, .n_ignore = n_ignore,
+                      .ticket = ticket});
+}
+
 tw_status tw_submit_png8_sized(tw_engine* e, const uint8_t* expect, int expect_channels, int width, int height,
                                const uint8_t* target, int target_channels, int target_width, int target_height,
                                int span, double threshold, const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
@@ -4191,6 +4316,13 @@ int tw_png_on_device(int color_type, int bit_depth, int interlace)
 // (the 8-bit kinds: exactly the Submission tw_submit_png8_sized builds)
 tw_status tw_submit_png(tw_engine* e, const tw_png_rows* expect, const tw_png_rows* target, int span, double threshold,
                         const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    return tw_submit_png_ignore(e, expect, target, span, threshold, init, out, nullptr, 0, ticket);
+}
+
+tw_status tw_submit_png_ignore(tw_engine* e, const tw_png_rows* expect, const tw_png_rows* target, int span, double threshold,
+                               const tw_flow_in* init, const tw_flow_out* out, const tw_rect* ignore, int n_ignore,
+                               tw_ticket* ticket)
 {
     if (!e) return TW_E_BAD_PARAMETER;
     e->err.clear();
@@ -4220,6 +4352,8 @@ tw_status tw_submit_png(tw_engine* e, const tw_png_rows* expect, const tw_png_ro
     s.t_stride = target->width;
     s.fo = out;
     s.fi = init;
+    s.ignore = ignore;
+    s.n_ignore = n_ignore;
     s.ticket = ticket;
     return submit(e, s);
 }
@@ -4237,6 +4371,13 @@ static tw_status check_jpeg_luma(const tw_jpeg_luma* l)
 // (both images gray: exactly the Submission tw_submit_u8_sized builds for dense rows)
 tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* expect, const tw_jpeg_luma* target, int span, double threshold,
                          const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    return tw_submit_jpeg_ignore(e, expect, target, span, threshold, init, out, nullptr, 0, ticket);
+}
+
+tw_status tw_submit_jpeg_ignore(tw_engine* e, const tw_jpeg_luma* expect, const tw_jpeg_luma* target, int span,
+                                double threshold, const tw_flow_in* init, const tw_flow_out* out, const tw_rect* ignore,
+                                int n_ignore, tw_ticket* ticket)
 {
     if (!e) return TW_E_BAD_PARAMETER;
     e->err.clear();
@@ -4257,6 +4398,8 @@ tw_status tw_submit_jpeg(tw_engine* e, const tw_jpeg_luma* expect, const tw_jpeg
     s.t_stride = target->width;
     s.fo = out;
     s.fi = init;
+    s.ignore = ignore;
+    s.n_ignore = n_ignore;
     s.ticket = ticket;
     return submit(e, s);
 }
@@ -4309,8 +4452,10 @@ tw_status tw_image_keep(tw_engine* e, tw_ticket ticket, int which, tw_image** ou
         }
     }
     Job& jb = c->jobs[j];
+    // (a masked target is what the batch sees only behind the batch's tw_mask_rects launch)
     const bool at_launch = host && !c->launched &&
-                           (jb.png_ch[which] > 0 || jb.jpg_bw[which] > 0 || (which == TW_KEEP_TARGET && jb.rkind == RSZ_FLUSH_COPY));
+                           (jb.png_ch[which] > 0 || jb.jpg_bw[which] > 0 ||
+                            (which == TW_KEEP_TARGET && (jb.rkind == RSZ_FLUSH_COPY || !jb.ign.empty())));
     tw_image* im = nullptr;
     TW_TRY(image_new(e, c->w, c->h, &im));
     if (at_launch) {
@@ -4391,6 +4536,13 @@ tw_status tw_image_size(const tw_engine* e, const tw_image* img, int* width, int
 tw_status tw_submit_image_png(tw_engine* e, const tw_image* expect, const tw_png_rows* target, int span, double threshold,
                               const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
 {
+    return tw_submit_image_png_ignore(e, expect, target, span, threshold, init, out, nullptr, 0, ticket);
+}
+
+tw_status tw_submit_image_png_ignore(tw_engine* e, const tw_image* expect, const tw_png_rows* target, int span,
+                                     double threshold, const tw_flow_in* init, const tw_flow_out* out, const tw_rect* ignore,
+                                     int n_ignore, tw_ticket* ticket)
+{
     if (!e) return TW_E_BAD_PARAMETER;
     e->err.clear();
     tw_image* im = find_image(e, expect);
@@ -4416,6 +4568,8 @@ tw_status tw_submit_image_png(tw_engine* e, const tw_image* expect, const tw_png
     s.t_stride = target->width;
     s.fo = out;
     s.fi = init;
+    s.ignore = ignore;
+    s.n_ignore = n_ignore;
     s.ticket = ticket;
     return submit(e, s);
 }
@@ -4423,6 +4577,13 @@ tw_status tw_submit_image_png(tw_engine* e, const tw_image* expect, const tw_png
 // (tw_submit_jpeg's Submission likewise)
 tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* expect, const tw_jpeg_luma* target, int span, double threshold,
                                const tw_flow_in* init, const tw_flow_out* out, tw_ticket* ticket)
+{
+    return tw_submit_image_jpeg_ignore(e, expect, target, span, threshold, init, out, nullptr, 0, ticket);
+}
+
+tw_status tw_submit_image_jpeg_ignore(tw_engine* e, const tw_image* expect, const tw_jpeg_luma* target, int span,
+                                      double threshold, const tw_flow_in* init, const tw_flow_out* out, const tw_rect* ignore,
+                                      int n_ignore, tw_ticket* ticket)
 {
     if (!e) return TW_E_BAD_PARAMETER;
     e->err.clear();
@@ -4443,6 +4604,8 @@ tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* expect, const tw_jp
     s.t_stride = target->width;
     s.fo = out;
     s.fi = init;
+    s.ignore = ignore;
+    s.n_ignore = n_ignore;
     s.ticket = ticket;
     return submit(e, s);
 }
@@ -4524,7 +4687,35 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
         TW_HIP(e, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
         *seconds = ms * 1e-3f / (float)c->jobs.size();
     }
-    if (c->span > 0) {
+    if (c->span > 0 && !c->jobs[j].ign.empty()) {
+        // a pair with ignore rectangles: a vector whose grid point lies inside one of them is not reported.  All of the
+        // pair's records are read and filtered in order; *n counts what is left (with out == NULL as well)
+        const std::vector<tw_rect>& ign = c->jobs[j].ign;
+        const int cnt = c->h_count[j];
+        const ScanRec* hr = c->h_rec + (size_t)j * HOST_RECS;
+        std::vector<ScanRec> extra;
+        if (cnt > HOST_RECS) {
+            const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
+            extra.resize(cnt);
+            TW_TRY(d2h_sync(e, extra.data(), c->d_rec + (size_t)j * G, (size_t)cnt * sizeof(ScanRec)));
+            hr = extra.data();
+        }
+        int kept = 0;
+        for (int i = 0; i < cnt; i++) {
+            bool inside = false;
+            for (const tw_rect& r : ign)
+                inside = inside || (hr[i].x >= r.x && hr[i].x < r.x + r.width && hr[i].y >= r.y && hr[i].y < r.y + r.height);
+            if (inside) continue;
+            if (out && kept < cap) {
+                out[kept].x = hr[i].x;
+                out[kept].y = hr[i].y;
+                out[kept].dx = hr[i].dx;
+                out[kept].dy = hr[i].dy;
+            }
+            kept++;
+        }
+        if (n) *n = kept;
+    } else if (c->span > 0) {
         const int cnt = c->h_count[j];
         if (n) *n = cnt;
         const int want = std::min(cnt, cap);
@@ -5001,7 +5192,7 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
         "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_iter_grid",
-        "tw_jpeg_idct", "tw_pair_same",
+        "tw_jpeg_idct", "tw_mask_rects", "tw_pair_same",
         "tw_resize_u8", "tw_flow_area_init", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
 }
@@ -5046,6 +5237,8 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
         if (c.h_png) v[1] += png_table_bytes(e->cap);
         if (c.d_jpg) v[0] += jpeg_table_bytes(e->cap) + 256;
         if (c.h_jpg) v[1] += jpeg_table_bytes(e->cap);
+        if (c.d_msk) v[0] += mask_table_bytes(e->cap) + 256;
+        if (c.h_msk) v[1] += mask_table_bytes(e->cap);
         if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cap;
         if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cap;
     }
@@ -5563,6 +5756,60 @@ tw_status tw_stage_jpeg_idct(tw_engine* e, const tw_jpeg_luma* img, uint8_t* gra
     if (guard) {
         TW_TRY(d2h_sync(e, guard, d_raw, 256));
         TW_TRY(d2h_sync(e, guard + 256, d_raw + 256 + npx, 256));
+    }
+    return TW_OK;
+}
+
+tw_status tw_stage_mask_rects(tw_engine* e, const uint8_t* expect, const uint8_t* target, int w, int h, const tw_rect* ignore,
+                              int n_ignore, uint8_t* out, uint8_t* guard)
+{
+    if (!e || !expect || !target || !out) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    TW_TRY(check_dims(e, w, h));
+    std::vector<tw_rect> ign;
+    TW_TRY(clip_ignore(e, ignore, n_ignore, w, h, &ign));
+    TW_HIP(e, hipSetDevice(e->device));
+    // the two images as a batch places them: 256-byte aligned slots of staged_image_bytes, dense rows of w bytes
+    const size_t npx = (size_t)w * h, slot = staged_image_bytes(w, h);
+    Tmp t;
+    uint8_t* d_exp = t.alloc<uint8_t>(slot);
+    uint8_t* d_raw = t.alloc<uint8_t>(slot + 512);  // 256 guard bytes on either side of the target's slot
+    MaskJob* d_tab = t.alloc<MaskJob>(TW_MAX_IGNORE);
+    if (!d_exp || !d_raw || !d_tab) return TW_E_NOMEM;
+    hipStream_t st = e->stream;
+    TW_HIP(e, hipMemsetAsync(d_exp, 0xA5, slot, st));
+    TW_HIP(e, hipMemsetAsync(d_raw, 0xA5, slot + 512, st));  // (the guards and the slot's padding; in front of the launch)
+    TW_HIP(e, hipStreamSynchronize(st));
+    TW_TRY(h2d_sync(e, d_exp, expect, npx));
+    TW_TRY(h2d_sync(e, d_raw + 256, target, npx));
+    if (!ign.empty()) {
+        MaskJob h_tab[TW_MAX_IGNORE];
+        int wmax = 1, hmax = 1;
+        for (size_t i = 0; i < ign.size(); i++) {
+            const tw_rect& r = ign[i];
+            h_tab[i] = MaskJob{d_raw + 256, d_exp, r.x, r.y, r.x + r.width, r.y + r.height, (long long)w};
+            wmax = std::max(wmax, r.width);
+            hmax = std::max(hmax, r.height);
+        }
+        TW_TRY(h2d_sync(e, d_tab, h_tab, sizeof(MaskJob) * ign.size()));
+        MaskArgs ma;
+        ma.jobs = d_tab;
+        TW_LAUNCH(e, TW_DF_MASK_RECTS, tw_mask_rects, mask_rects_grid(wmax, hmax, (int)ign.size()), dim3(64, MASK_ROWS), 0, st, ma);
+        TW_HIP(e, hipGetLastError());
+        TW_HIP(e, hipStreamSynchronize(st));
+    }
+    TW_TRY(d2h_sync(e, out, d_raw + 256, npx));
+    // the slot's padding behind the image belongs to nobody: a byte there that is not 0xA5 was written outside the image
+    std::vector<uint8_t> pad(slot - npx);
+    if (!pad.empty()) TW_TRY(d2h_sync(e, pad.data(), d_raw + 256 + npx, pad.size()));
+    for (uint8_t b : pad)
+        if (b != 0xA5) {
+            e->err = "tw_mask_rects wrote the padding of the target's slot";
+            return TW_E_DEVICE;
+        }
+    if (guard) {
+        TW_TRY(d2h_sync(e, guard, d_raw, 256));
+        TW_TRY(d2h_sync(e, guard + 256, d_raw + 256 + slot, 256));
     }
     return TW_OK;
 }

@@ -5201,4 +5201,49 @@ __global__ __launch_bounds__(8 * JPEG_WG_BLOCKS) void tw_jpeg_idct(JpegArgs a)
     }
 }
 
+// =====================================================================================================
+// tw_mask_rects — ignore regions (tw_submit_*_ignore): inside a rectangle the target's bytes become the expected image's
+//   bytes at the same coordinates, after every decode and resize launch of the batch and before anything else reads the
+//   target.  One launch per batch; grid z is the rectangle (clipped and non-empty: the host builds the table), x and y tile
+//   the LARGEST rectangle of the launch in 256 bytes x MASK_ROWS rows, and a lane outside its own rectangle returns.
+//   Rows are dense (`stride` = the image's width, any value), so every row has its own offset from a 4-byte boundary; both
+//   bases are 256-byte aligned and share the stride, so source and destination share that offset.  A lane owns one ALIGNED
+//   dword of the destination row and loads the same aligned dword of the source (both inside the 256-byte multiple the
+//   image's slot is long).  A dword the rectangle covers in full is one dword store; a dword it covers partly gets BYTE
+//   stores of the covered bytes only — never a read-modify-write: two rectangles of one pair may meet inside a dword and
+//   run concurrently here, and a merged dword would put the neighbour's old bytes back.  Overlapping rectangles store the
+//   same values (nobody writes the source).  Nothing outside the rectangle is written.  2 B per masked pixel.
+// =====================================================================================================
+struct MaskJob {
+    uint8_t* dst;         // the pair's target, 256-byte aligned
+    const uint8_t* src;   // the pair's expected image, 256-byte aligned
+    int x0, y0, x1, y1;   // 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height
+    long long stride;     // bytes between the rows of both images
+};
+struct MaskArgs {
+    const MaskJob* jobs;
+};
+constexpr int MASK_ROWS = 8;  // rows per workgroup (64 lanes x one dword across)
+typedef __attribute__((address_space(1))) uint8_t msk_gu8;
+typedef __attribute__((address_space(1))) unsigned msk_gu32;
+
+__global__ __launch_bounds__(64 * MASK_ROWS) void tw_mask_rects(MaskArgs a)
+{
+    const MaskJob job = a.jobs[blockIdx.z];
+    const int y = job.y0 + (int)blockIdx.y * MASK_ROWS + (int)threadIdx.y;
+    if (y >= job.y1) return;
+    // byte offsets from the (aligned) bases: the row's part of the rectangle is [b0, b1), this lane's dword [d, d + 4)
+    const long long row = (long long)y * job.stride, b0 = row + job.x0, b1 = row + job.x1;
+    const long long d = (b0 & ~3ll) + ((long long)blockIdx.x * 64 + (long long)threadIdx.x) * 4;
+    if (d >= b1) return;
+    const unsigned v = *(const msk_gu32*)((const msk_gu8*)job.src + d);
+    msk_gu8* __restrict__ D = (msk_gu8*)job.dst + d;
+    const int lo = (int)(max(b0, d) - d), hi = (int)(min(b1, d + 4) - d);  // the covered bytes of the dword
+    if (hi - lo == 4) {
+        *(msk_gu32*)D = v;
+    } else {
+        for (int k = lo; k < hi; k++) D[k] = (uint8_t)(v >> (8 * k));
+    }
+}
+
 }  // namespace twk

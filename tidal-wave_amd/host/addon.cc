@@ -258,6 +258,65 @@ napi_value calc(napi_env env, napi_callback_info info)
     return nullptr;
 }
 
+// One {x, y, width, height} object of calcIgnoring's array: four numbers that are 32-bit integers
+bool get_rect(napi_env env, napi_value v, Rect& out)
+{
+    napi_valuetype t;
+    if (napi_typeof(env, v, &t) != napi_ok || t != napi_object) return false;
+    const char* const keys[4] = {"x", "y", "width", "height"};
+    int* const dst[4] = {&out.x, &out.y, &out.width, &out.height};
+    for (int i = 0; i < 4; i++) {
+        napi_value f;
+        double d = 0;
+        if (napi_get_named_property(env, v, keys[i], &f) != napi_ok || napi_typeof(env, f, &t) != napi_ok || t != napi_number ||
+            napi_get_value_double(env, f, &d) != napi_ok || d != (double)(int)d)
+            return false;
+        *dst[i] = (int)d;
+    }
+    return true;
+}
+
+// not in the reference: calc with regions of the pair that may differ, an array of {x, y, width, height} in the expected
+// image's coordinates (the engine applies them: Request::ignore).  A rectangle the engine refuses (a negative size, more
+// than TW_MAX_IGNORE of them) comes back as an 'error' event like any other ERROR
+napi_value calc_ignoring(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4;
+    napi_value argv[4], self;
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, &self, nullptr));
+    if (argc != 3) {
+        napi_throw_type_error(env, nullptr, "3 arguments expected");
+        return nullptr;
+    }
+    std::string a, b;
+    if (!get_string(env, argv[0], a)) {
+        napi_throw_type_error(env, nullptr, "Wrong arguments(expect_image)");
+        return nullptr;
+    }
+    if (!get_string(env, argv[1], b)) {
+        napi_throw_type_error(env, nullptr, "Wrong arguments(target_image)");
+        return nullptr;
+    }
+    bool is_array = false;
+    uint32_t n = 0;
+    std::vector<Rect> rects;
+    bool ok = napi_is_array(env, argv[2], &is_array) == napi_ok && is_array && napi_get_array_length(env, argv[2], &n) == napi_ok;
+    for (uint32_t i = 0; ok && i < n; i++) {
+        napi_value el;
+        Rect r;
+        ok = napi_get_element(env, argv[2], i, &el) == napi_ok && get_rect(env, el, r);
+        if (ok) rects.push_back(r);
+    }
+    if (!ok) {
+        napi_throw_type_error(env, nullptr, "Wrong arguments(ignore)");
+        return nullptr;
+    }
+    Broker* br = nullptr;
+    NAPI_OK(napi_unwrap(env, self, (void**)&br));
+    if (br && br->manager) br->manager->request(a, b, rects);
+    return nullptr;
+}
+
 // Broker::requestDispose, src/broker.cpp:152-158
 napi_value dispose(napi_env env, napi_callback_info info)
 {
@@ -297,10 +356,11 @@ napi_value init(napi_env env, napi_value exports)
 {
     napi_property_descriptor props[] = {
         {"calc", nullptr, calc, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"calcIgnoring", nullptr, calc_ignoring, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"dispose", nullptr, dispose, nullptr, nullptr, nullptr, napi_default, nullptr},
     };
     napi_value cls;
-    NAPI_OK(napi_define_class(env, "TidalWave", NAPI_AUTO_LENGTH, construct, nullptr, 2, props, &cls));
+    NAPI_OK(napi_define_class(env, "TidalWave", NAPI_AUTO_LENGTH, construct, nullptr, 3, props, &cls));
     NAPI_OK(napi_set_named_property(env, exports, "TidalWave", cls));
     napi_value fn;
     NAPI_OK(napi_create_function(env, "decodeGray", NAPI_AUTO_LENGTH, decode_gray, nullptr, &fn));

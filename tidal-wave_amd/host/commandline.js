@@ -1,7 +1,8 @@
 #!/usr/bin/env node
 // commandline.js — the CLI contract of the reference (/root/reference/commandline.js:2-19,41-59): options
 // -threshold -span -pyrScale -pyrLevels -winSize -pyrIterations -polyN -polySigma -flags, two positional
-// paths, pretty JSON per result on stdout.  The reference's own script cannot run (it requires
+// paths, pretty JSON per result on stdout.  Not in the reference: -ignore x,y,w,h (repeatable), a region of every pair
+// that may differ.  The reference's own script cannot run (it requires
 // './opticalflow.js', which does not exist, commandline.js:62); this one drives index.js.  No stdout dup2
 // trick is needed: the native layer here does not print.
 // expect_path / target_path may be two directories (every file of target is paired with the same relative
@@ -24,7 +25,11 @@ function getArgs(argv) {
   var positional = [], options = {};
   for (var i = 0; i < argv.length; i++) {
     var m = /^--?([A-Za-z]+)(?:=(.*))?$/.exec(argv[i]);
-    if (m && supportedOptions.indexOf(m[1]) !== -1) {
+    if (m && m[1] === 'ignore') {
+      var r = parseRegion(m[2] !== undefined ? m[2] : argv[++i]);
+      if (!r) { process.stderr.write('-ignore takes x,y,w,h (four integers)\n' + usage); process.exit(-1); }
+      (options.ignore = options.ignore || []).push(r);
+    } else if (m && supportedOptions.indexOf(m[1]) !== -1) {
       var v = m[2] !== undefined ? m[2] : argv[++i];
       options[m[1]] = Number(v);          // numbers, like minimist does for numeric-looking values
     } else {
@@ -33,6 +38,12 @@ function getArgs(argv) {
   }
   if (positional.length < 2) { process.stderr.write(usage); process.exit(-1); }
   return { expect_path: positional[0], target_path: positional[1], options: options };
+}
+
+// "x,y,w,h" -> {x, y, width, height}; null unless it is four integers (x and y may be negative)
+function parseRegion(s) {
+  var m = /^(-?\d+),(-?\d+),(-?\d+),(-?\d+)$/.exec(String(s));
+  return m ? { x: Number(m[1]), y: Number(m[2]), width: Number(m[3]), height: Number(m[4]) } : null;
 }
 
 function print(o) { process.stdout.write(JSON.stringify(o, null, '  ') + '\n'); }
@@ -51,11 +62,13 @@ function main(args) {
     t = new TW.TidalWave(args.options);
     t.on('data', function() { t.dispose(); });
     t.on('error', function() { t.dispose(); });
-    t.calc(Path.resolve(args.expect_path), Path.resolve(args.target_path));
+    if (args.options.ignore) t.calcIgnoring(Path.resolve(args.expect_path), Path.resolve(args.target_path), args.options.ignore);
+    else t.calc(Path.resolve(args.expect_path), Path.resolve(args.target_path));
   }
   t.on('data', print);
   t.on('error', print);
   t.once('finish', print);
 }
 
-main(getArgs(process.argv.slice(2)));
+module.exports.getArgs = getArgs;
+if (require.main === module) main(getArgs(process.argv.slice(2)));

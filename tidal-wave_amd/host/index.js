@@ -2,6 +2,9 @@
 // create(targetDir, {expectDir | getExpectedPath, ...engine options}) -> EventEmitter with 'data' / 'error' /
 // 'finish'.  The reference walks the target directory with `glob-stream`; that module is not installed here,
 // so the walk uses fs directly (same '**/*.*' semantics: every file whose name contains a dot).
+// Not in the reference: the options `ignore` (an array of {x, y, width, height}, regions of every pair that may differ) or
+// `getIgnoreRegions(shortPath)` (a function returning such an array, or nothing, for one pair); a pair with regions goes
+// through calcIgnoring, every other pair through calc as before.
 'use strict';
 var EventEmitter = require('events').EventEmitter,
   TidalWave = require('./build/Release/tidalwave').TidalWave,
@@ -27,7 +30,14 @@ function create(targetDir, options) {
     throw new Error('An option must have "expectDir" or "getExpectedPath" property.');
   }
 
-  calcAll(t, targetDir, getExpectedPath);
+  var getIgnoreRegions = null;
+  if (Array.isArray(options.ignore)) {
+    getIgnoreRegions = function() { return options.ignore; };
+  } else if (typeof options.getIgnoreRegions === 'function') {
+    getIgnoreRegions = options.getIgnoreRegions;
+  }
+
+  calcAll(t, targetDir, getExpectedPath, getIgnoreRegions);
   return t;
 }
 
@@ -43,7 +53,7 @@ function walk(dir, out) {
   return out;
 }
 
-function calcAll(tidalwave, targetDir, getExpectedPath) {
+function calcAll(tidalwave, targetDir, getExpectedPath, getIgnoreRegions) {
   var base = Path.resolve(targetDir);
   var files = walk(base, []);
   var globEnded = false;
@@ -66,7 +76,9 @@ function calcAll(tidalwave, targetDir, getExpectedPath) {
       // the reference ignores the result of FS.exists (index.js:57-60): a missing expected file still
       // produces a calc and therefore an ERROR "Can't open ..."
       FS.access(expectedFile, function() {
-        tidalwave.calc(expectedFile, target);
+        var regions = getIgnoreRegions ? getIgnoreRegions.call(this, shortPath) : null;
+        if (Array.isArray(regions) && regions.length > 0) tidalwave.calcIgnoring(expectedFile, target, regions);
+        else tidalwave.calc(expectedFile, target);
         requested++;
         done();
       });

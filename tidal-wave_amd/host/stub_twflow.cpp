@@ -636,6 +636,73 @@ tw_status tw_submit_image_jpeg(tw_engine* e, const tw_image* img, const tw_jpeg_
         trace_submit(e, "tw_submit_image_jpeg", "image=" + std::to_string(image_ordinal(img)) + " b=[" + luma_seen(b) + "]", span, thr, r, t);
     return r;
 }
+// Ignore regions: the rectangles are checked as the engine checks them and recorded as given; the stub's one-pixel images
+// have nothing to mask, so the pair is then what the plain call sees
+static bool stub_rects_ok(const tw_rect* ig, int n)
+{
+    if (n < 0 || n > TW_MAX_IGNORE || (n > 0 && !ig)) return false;
+    for (int i = 0; i < n; i++)
+        if (ig[i].width < 0 || ig[i].height < 0) return false;
+    return true;
+}
+static std::string rects_seen(const tw_rect* ig, int n)
+{
+    std::string s = " ignore=" + std::to_string(n) + "[";
+    for (int i = 0; ig && i < n && i <= TW_MAX_IGNORE; i++) {
+        char b[64];
+        snprintf(b, sizeof(b), "%s%d,%d,%d,%d", i ? ";" : "", ig[i].x, ig[i].y, ig[i].width, ig[i].height);
+        s += b;
+    }
+    return s + "]";
+}
+tw_status tw_submit_u8_ignore(tw_engine* e, const uint8_t* a, int w, int h, ptrdiff_t stride, const uint8_t* b, int tw, int th,
+                              ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, const tw_rect* ig,
+                              int n, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(!stub_rects_ok(ig, n) ? TW_E_BAD_PARAMETER : stub_u8_sized(e, a, w, h, b, tw, th, tstride, t));
+    if (tracing()) {
+        char sa[64], sb[64];
+        snprintf(sa, sizeof(sa), "a=[%dx%d stride=%td ", w, h, stride);
+        snprintf(sb, sizeof(sb), "] b=[%dx%d stride=%td ", tw, th, tstride);
+        trace_submit(e, "tw_submit_u8_ignore", sa + bytes_seen(a, h > 0 ? (size_t)h : 0, w > 0 ? (size_t)w : 0, stride) + sb +
+                     bytes_seen(b, th > 0 ? (size_t)th : 0, tw > 0 ? (size_t)tw : 0, tstride) + "]" + rects_seen(ig, n), span, thr, r, t);
+    }
+    return r;
+}
+tw_status tw_submit_png_ignore(tw_engine* e, const tw_png_rows* a, const tw_png_rows* b, int span, double thr, const tw_flow_in*,
+                               const tw_flow_out*, const tw_rect* ig, int n, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(!stub_rects_ok(ig, n) ? TW_E_BAD_PARAMETER : stub_png(e, a, b, t));
+    if (tracing())
+        trace_submit(e, "tw_submit_png_ignore", "a=[" + rows_seen(a) + "] b=[" + rows_seen(b) + "]" + rects_seen(ig, n), span, thr, r, t);
+    return r;
+}
+tw_status tw_submit_jpeg_ignore(tw_engine* e, const tw_jpeg_luma* a, const tw_jpeg_luma* b, int span, double thr,
+                                const tw_flow_in*, const tw_flow_out*, const tw_rect* ig, int n, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(!stub_rects_ok(ig, n) ? TW_E_BAD_PARAMETER : stub_jpeg(e, a, b, t));
+    if (tracing())
+        trace_submit(e, "tw_submit_jpeg_ignore", "a=[" + luma_seen(a) + "] b=[" + luma_seen(b) + "]" + rects_seen(ig, n), span, thr, r, t);
+    return r;
+}
+tw_status tw_submit_image_png_ignore(tw_engine* e, const tw_image* img, const tw_png_rows* b, int span, double thr,
+                                     const tw_flow_in*, const tw_flow_out*, const tw_rect* ig, int n, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(!stub_rects_ok(ig, n) ? TW_E_BAD_PARAMETER : stub_image_png(e, img, b, t));
+    if (tracing())
+        trace_submit(e, "tw_submit_image_png_ignore",
+                     "image=" + std::to_string(image_ordinal(img)) + " b=[" + rows_seen(b) + "]" + rects_seen(ig, n), span, thr, r, t);
+    return r;
+}
+tw_status tw_submit_image_jpeg_ignore(tw_engine* e, const tw_image* img, const tw_jpeg_luma* b, int span, double thr,
+                                      const tw_flow_in*, const tw_flow_out*, const tw_rect* ig, int n, tw_ticket* t)
+{
+    const tw_status r = STUB_SUBMIT(!stub_rects_ok(ig, n) ? TW_E_BAD_PARAMETER : stub_image_jpeg(e, img, b, t));
+    if (tracing())
+        trace_submit(e, "tw_submit_image_jpeg_ignore",
+                     "image=" + std::to_string(image_ordinal(img)) + " b=[" + luma_seen(b) + "]" + rects_seen(ig, n), span, thr, r, t);
+    return r;
+}
 tw_status tw_submit_dev_sized(tw_engine* e, const void* a, int w, int h, ptrdiff_t stride, const void* b, int tw, int th,
                               ptrdiff_t tstride, int span, double thr, const tw_flow_in*, const tw_flow_out*, tw_ticket* t)
 {

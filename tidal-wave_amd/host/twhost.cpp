@@ -29,6 +29,12 @@
 #pragma weak tw_image_release
 #pragma weak tw_submit_image_png
 #pragma weak tw_submit_image_jpeg
+// and the ignore regions: a request that names rectangles answers ERROR on an engine library from before them
+#pragma weak tw_submit_u8_ignore
+#pragma weak tw_submit_png_ignore
+#pragma weak tw_submit_jpeg_ignore
+#pragma weak tw_submit_image_png_ignore
+#pragma weak tw_submit_image_jpeg_ignore
 
 namespace twhost {
 
@@ -1466,6 +1472,7 @@ struct ConsumerRun {
         const tw_image* image = resident_image_of(s);
         const int span = s.req.span;
         const double thr = s.req.threshold;
+        if (!s.req.ignore.empty()) return submit_to_engine_ignoring(s, image);
         switch (entry_point(s, image != nullptr)) {
             case EntryPoint::ImageJpeg: {
                 const tw_jpeg_luma lb = luma_of(t);
@@ -1488,6 +1495,43 @@ struct ConsumerRun {
             case EntryPoint::U8: break;
         }
         return tw_submit_u8(eng, e.p, t.p, s.w, s.h, s.stride, span, thr, &s.ticket);
+    }
+    // A pair with ignore rectangles: the _ignore form of the call it would take without them, the gray fallbacks included
+    // (a file the host had to finish, a host-side reconcile, BMP, PNM and raw pairs all go to tw_submit_u8_ignore): the
+    // device always applies the mask
+    tw_status submit_to_engine_ignoring(Staged& s, const tw_image* image)
+    {
+        const Staged::Side &e = s.side[0], &t = s.side[1];
+        const int span = s.req.span, n = (int)std::min<size_t>(s.req.ignore.size(), (size_t)TW_MAX_IGNORE + 1);
+        const double thr = s.req.threshold;
+        const tw_rect* rects = s.req.ignore.data();
+        if (!tw_submit_u8_ignore || !tw_submit_png_ignore || !tw_submit_jpeg_ignore || !tw_submit_image_png_ignore ||
+            !tw_submit_image_jpeg_ignore)
+            return TW_E_UNSUPPORTED;  // (an engine library from before the ignore regions)
+        switch (entry_point(s, image != nullptr)) {
+            case EntryPoint::ImageJpeg: {
+                const tw_jpeg_luma lb = luma_of(t);
+                return tw_submit_image_jpeg_ignore(eng, image, &lb, span, thr, nullptr, nullptr, rects, n, &s.ticket);
+            }
+            case EntryPoint::ImagePng: {
+                const tw_png_rows rb = rows_of(t);
+                return tw_submit_image_png_ignore(eng, image, &rb, span, thr, nullptr, nullptr, rects, n, &s.ticket);
+            }
+            case EntryPoint::Png: {
+                const tw_png_rows ra = rows_of(e), rb = rows_of(t);
+                return tw_submit_png_ignore(eng, &ra, &rb, span, thr, nullptr, nullptr, rects, n, &s.ticket);
+            }
+            case EntryPoint::Jpeg: {
+                const tw_jpeg_luma la = luma_of(e), lb = luma_of(t);
+                return tw_submit_jpeg_ignore(eng, &la, &lb, span, thr, nullptr, nullptr, rects, n, &s.ticket);
+            }
+            case EntryPoint::U8Sized:
+                return tw_submit_u8_ignore(eng, e.p, s.w, s.h, s.stride, t.p, t.w, t.h, t.w, span, thr, nullptr, nullptr, rects, n,
+                                           &s.ticket);
+            case EntryPoint::U8: break;
+        }
+        return tw_submit_u8_ignore(eng, e.p, s.w, s.h, s.stride, t.p, s.w, s.h, s.stride, span, thr, nullptr, nullptr, rects, n,
+                                   &s.ticket);
     }
     // a miss: the image the batch sees stays on the device (one device-to-device copy behind its decode), and
     // enters the cache when the pair has answered OK
@@ -1733,6 +1777,23 @@ int Manager::request(const std::string& expect_image, const std::string& target_
     r.span = param_.span;
     r.threshold = param_.threshold;
     TW_LOGF("request: %s <-> %s\n", expect_image.c_str(), target_image.c_str());  // src/manager.cpp:74
+    {
+        std::lock_guard<std::mutex> lk(report_m_);
+        report_.requestCount++;
+    }
+    requestQueue_.push(std::move(r));
+    return 0;
+}
+
+int Manager::request(const std::string& expect_image, const std::string& target_image, const std::vector<Rect>& ignore)
+{
+    Request r;
+    r.expect_image = expect_image;
+    r.target_image = target_image;
+    r.span = param_.span;
+    r.threshold = param_.threshold;
+    r.ignore = ignore;
+    TW_LOGF("request: %s <-> %s (%zu ignore regions)\n", expect_image.c_str(), target_image.c_str(), ignore.size());
     {
         std::lock_guard<std::mutex> lk(report_m_);
         report_.requestCount++;

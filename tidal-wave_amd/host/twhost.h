@@ -25,6 +25,8 @@ struct RawPair {
     int width = 0, height = 0;
     ptrdiff_t stride = 0;
 };
+// An ignore rectangle of a pair, in the expected image's coordinates (tw_rect of include/twflow.h)
+using Rect = tw_rect;
 // /root/reference/src/message_queue.h:13-48
 struct Request {
     std::string expect_image;
@@ -32,6 +34,10 @@ struct Request {
     double threshold;
     int span;
     RawPair raw;  // raw.expect != nullptr: the paths above are labels only
+    // not in the reference: regions of the pair that may differ.  Inside them the engine replaces the target's pixels by
+    // the expected image's before the flow and reports no vector from there (the tw_submit_*_ignore calls: the device
+    // applies the mask, the host layer has no implementation of it); empty: the pair goes the way it always went
+    std::vector<Rect> ignore;
 };
 struct Vector {
     int x, y;
@@ -255,6 +261,8 @@ public:
     ~Manager();
     void start(const Parameter& p);
     int request(const std::string& expect_image, const std::string& target_image);
+    // the same with ignore rectangles (Request::ignore); a rectangle the engine refuses comes back as an ERROR response
+    int request(const std::string& expect_image, const std::string& target_image, const std::vector<Rect>& ignore);
     // the same for an in-memory pair (see RawPair); the two names are only echoed in the response
     int requestRaw(const std::string& expect_name, const std::string& target_name, const RawPair& raw);
     int consumerCount() const { return (int)consumers_.size(); }

@@ -46,6 +46,12 @@ class FlowIn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("pitch", C.c_ssize_t), ("layout", C.c_int)]
 
 
+class Rect(C.Structure):
+    # tw_rect (include/twflow.h): an ignore rectangle of the tw_submit_*_ignore calls, in pair coordinates
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int)]
+
+
+MAX_IGNORE = 32
 FLOW_PLANAR, FLOW_INTERLEAVED = 0, 1
 
 
@@ -70,6 +76,8 @@ SYMBOLS = [
     "tw_png_on_device", "tw_submit_png", "tw_stage_png_decode", "tw_submit_jpeg", "tw_stage_jpeg_idct",
     "tw_image_keep", "tw_image_create_u8", "tw_image_release", "tw_image_size", "tw_submit_image_png", "tw_submit_image_jpeg",
     "tw_debug_resident",
+    "tw_submit_u8_ignore", "tw_submit_png_ignore", "tw_submit_jpeg_ignore", "tw_submit_image_png_ignore",
+    "tw_submit_image_jpeg_ignore", "tw_stage_mask_rects",
     "tw_grid_capacity", "tw_dev_alloc", "tw_dev_free", "tw_dev_upload", "tw_dev_download", "tw_host_alloc", "tw_host_free", "tw_host_register", "tw_host_unregister", "tw_set_option",
     "tw_prof_select", "tw_prof_read",
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
@@ -240,6 +248,16 @@ def _bind(path):
     L.tw_image_size.argtypes = [vp, vp, ip, ip]
     L.tw_submit_image_png.argtypes = [vp, vp, C.POINTER(PngRows), C.c_int, C.c_double, fip, fop, tkp]
     L.tw_submit_image_jpeg.argtypes = [vp, vp, C.POINTER(JpegLuma), C.c_int, C.c_double, fip, fop, tkp]
+    rp = C.POINTER(Rect)
+    L.tw_submit_u8_ignore.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_ssize_t, u8p, C.c_int, C.c_int, C.c_ssize_t, C.c_int,
+                                      C.c_double, fip, fop, rp, C.c_int, tkp]
+    L.tw_submit_png_ignore.argtypes = [vp, C.POINTER(PngRows), C.POINTER(PngRows), C.c_int, C.c_double, fip, fop, rp,
+                                       C.c_int, tkp]
+    L.tw_submit_jpeg_ignore.argtypes = [vp, C.POINTER(JpegLuma), C.POINTER(JpegLuma), C.c_int, C.c_double, fip, fop, rp,
+                                        C.c_int, tkp]
+    L.tw_submit_image_png_ignore.argtypes = [vp, vp, C.POINTER(PngRows), C.c_int, C.c_double, fip, fop, rp, C.c_int, tkp]
+    L.tw_submit_image_jpeg_ignore.argtypes = [vp, vp, C.POINTER(JpegLuma), C.c_int, C.c_double, fip, fop, rp, C.c_int, tkp]
+    L.tw_stage_mask_rects.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, rp, C.c_int, u8p, u8p]
     L.tw_debug_resident.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.tw_debug_resident.restype = C.c_int
     L.tw_wait.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, fp]
@@ -417,6 +435,18 @@ def _flow_in(init, w, h):
                   "unit-stride rows, got shape %r strides %r" % (h, w, h, w, shape, strides))
 
 
+def _rects(ignore):
+    """A list of (x, y, w, h) as (tw_rect array or None, count) for the tw_submit_*_ignore calls; the library reads the
+    rectangles before the call returns."""
+    rs = [tuple(int(v) for v in r) for r in ignore]
+    if not rs:
+        return None, 0
+    arr = (Rect * len(rs))()
+    for i, (x, y, w, h) in enumerate(rs):
+        arr[i] = Rect(x, y, w, h)
+    return arr, len(rs)
+
+
 def _gray(a):
     a = np.asarray(a)
     if a.dtype != np.uint8 or a.ndim != 2:
@@ -513,12 +543,26 @@ class Engine:
         t = self.submit(expect, target, span, threshold)
         return self.wait(t)
 
-    def submit(self, expect, target, span=10, threshold=5.0, *, flow=None, init=None, reconcile=False):
-        """flow: where the pair's final flow goes (tw_submit_u8_flow; see _flow_out), kept alive by the caller until wait().
+    def submit(self, expect, target, span=10, threshold=5.0, *, flow=None, init=None, reconcile=False, ignore=None):
+        """ignore: a list of (x, y, w, h) rectangles of the pair that may differ (tw_submit_u8_ignore; None: the plain calls).
+        flow: where the pair's final flow goes (tw_submit_u8_flow; see _flow_out), kept alive by the caller until wait().
         init: the pair's initial flow field (tw_submit_u8_flow_init; see _flow_in), unchanged until wait().
         reconcile: a target of another shape goes to tw_submit_u8_sized, which resizes one within 5 px to the expected
         image's size on the device and refuses any other (the default refuses every shape mismatch here)."""
         a, b = _gray(expect), _gray(target)
+        if ignore is not None:
+            if a.shape != b.shape and not reconcile:
+                raise TwError(TW_E_DONT_MATCH_SIZE, "Don't match image size")
+            h, w = a.shape
+            tk = C.c_int64()
+            fo = _flow_out(flow, w, h)
+            fi, _keep = _flow_in(init, w, h)
+            rs, nr = _rects(ignore)
+            self._check(self._L.tw_submit_u8_ignore(self._h, _u8(a), w, h, a.strides[0], _u8(b), b.shape[1], b.shape[0],
+                                                    b.strides[0], span, threshold,
+                                                    C.byref(fi) if fi is not None else None,
+                                                    C.byref(fo) if fo is not None else None, rs, nr, C.byref(tk)))
+            return (tk.value, w, h, span, threshold)
         if a.shape != b.shape and reconcile:
             h, w = a.shape
             tk = C.c_int64()
@@ -586,13 +630,19 @@ class Engine:
         self._check(self._L.tw_stage_png_unfilter(self._h, _u8(rows), ch, w, h, waves, _u8(out)))
         return out
 
-    def submit_png(self, expect, target, span=10, threshold=5.0, *, flow=None, init=None):
+    def submit_png(self, expect, target, span=10, threshold=5.0, *, flow=None, init=None, ignore=None):
         """tw_submit_png: expect, target are PngRows (any kind png_on_device admits, or PNG_PLAIN_GRAY), each at its own
-        size; the pair's size is the expected image's.  flow, init: as for submit."""
+        size; the pair's size is the expected image's.  flow, init, ignore (tw_submit_png_ignore): as for submit."""
         w, h = expect.width, expect.height
         tk = C.c_int64()
         fo = _flow_out(flow, w, h)
         fi, _keep = _flow_in(init, w, h)
+        if ignore is not None:
+            rs, nr = _rects(ignore)
+            self._check(self._L.tw_submit_png_ignore(self._h, C.byref(expect), C.byref(target), span, threshold,
+                                                     C.byref(fi) if fi is not None else None,
+                                                     C.byref(fo) if fo is not None else None, rs, nr, C.byref(tk)))
+            return (tk.value, w, h, span, threshold)
         self._check(self._L.tw_submit_png(self._h, C.byref(expect), C.byref(target), span, threshold,
                                           C.byref(fi) if fi is not None else None,
                                           C.byref(fo) if fo is not None else None, C.byref(tk)))
@@ -604,16 +654,22 @@ class Engine:
         self._check(self._L.tw_stage_png_decode(self._h, C.byref(img), waves, _u8(out)))
         return out
 
-    def submit_jpeg(self, expect, target, span=10, threshold=5.0, init=None, out=None):
+    def submit_jpeg(self, expect, target, span=10, threshold=5.0, init=None, out=None, ignore=None):
         """tw_submit_jpeg: expect, target are JpegLuma (coefficients, or JpegLuma.from_gray) or 2-D uint8 gray images, each
         at its own size; the pair's size is the expected image's.  init, out: the initial field and the destination of
-        the final flow, as submit's init and flow."""
+        the final flow, as submit's init and flow; ignore (tw_submit_jpeg_ignore): as for submit."""
         a = expect if isinstance(expect, JpegLuma) else JpegLuma.from_gray(expect)
         b = target if isinstance(target, JpegLuma) else JpegLuma.from_gray(target)
         w, h = a.width, a.height
         tk = C.c_int64()
         fo = _flow_out(out, w, h)
         fi, _keep = _flow_in(init, w, h)
+        if ignore is not None:
+            rs, nr = _rects(ignore)
+            self._check(self._L.tw_submit_jpeg_ignore(self._h, C.byref(a), C.byref(b), span, threshold,
+                                                      C.byref(fi) if fi is not None else None,
+                                                      C.byref(fo) if fo is not None else None, rs, nr, C.byref(tk)))
+            return (tk.value, w, h, span, threshold)
         self._check(self._L.tw_submit_jpeg(self._h, C.byref(a), C.byref(b), span, threshold,
                                            C.byref(fi) if fi is not None else None,
                                            C.byref(fo) if fo is not None else None, C.byref(tk)))
@@ -636,10 +692,10 @@ class Engine:
         self._check(self._L.tw_image_keep(self._h, ticket[0], int(k), C.byref(out)))
         return Image(self, out)
 
-    def submit_image(self, img, target, span=10, threshold=5.0, *, flow=None, init=None):
+    def submit_image(self, img, target, span=10, threshold=5.0, *, flow=None, init=None, ignore=None):
         """tw_submit_image_png / tw_submit_image_jpeg: the expected image is the resident `img`; target is a 2-D uint8 gray
-        image or a PngRows (tw_submit_image_png), or a JpegLuma (tw_submit_image_jpeg), at its own size.  flow, init: as
-        for submit."""
+        image or a PngRows (tw_submit_image_png), or a JpegLuma (tw_submit_image_jpeg), at its own size.  flow, init,
+        ignore (the tw_submit_image_*_ignore calls): as for submit."""
         w, h = img.size if img is not None else (0, 0)
         tk = C.c_int64()
         fo = _flow_out(flow, w, h) if img is not None else None
@@ -647,13 +703,17 @@ class Engine:
         args = (span, threshold, C.byref(fi) if fi is not None else None, C.byref(fo) if fo is not None else None,
                 C.byref(tk))
         ih = img._h if img is not None else None
+        if ignore is not None:
+            args = args[:-1] + _rects(ignore) + args[-1:]
         if isinstance(target, JpegLuma):
-            self._check(self._L.tw_submit_image_jpeg(self._h, ih, C.byref(target), *args))
+            call = self._L.tw_submit_image_jpeg if ignore is None else self._L.tw_submit_image_jpeg_ignore
+            self._check(call(self._h, ih, C.byref(target), *args))
         else:
             if not isinstance(target, PngRows):
                 b = np.ascontiguousarray(_gray(target))
                 target = PngRows(b, b.shape[1], b.shape[0])
-            self._check(self._L.tw_submit_image_png(self._h, ih, C.byref(target), *args))
+            call = self._L.tw_submit_image_png if ignore is None else self._L.tw_submit_image_png_ignore
+            self._check(call(self._h, ih, C.byref(target), *args))
         return (tk.value, w, h, span, threshold)
 
     def resident(self):
@@ -669,6 +729,19 @@ class Engine:
         out = np.empty((luma.height, luma.width), np.uint8)
         g = np.empty(512, np.uint8) if guard else None
         self._check(self._L.tw_stage_jpeg_idct(self._h, C.byref(luma), _u8(out), _u8(g) if guard else None))
+        return (out, g) if guard else out
+
+    def stage_mask_rects(self, expect, target, rects, guard=False):
+        """tw_mask_rects alone on two 2-D uint8 images of one shape and a list of (x, y, w, h): the edited target;
+        guard=True: also the 512 device bytes around the target's slot (256 in front, 256 behind), 0xA5 before the launch."""
+        a, b = np.ascontiguousarray(_gray(expect)), np.ascontiguousarray(_gray(target))
+        if a.shape != b.shape:
+            raise TwError(TW_E_DONT_MATCH_SIZE, "Don't match image size")
+        h, w = a.shape
+        out = np.empty((h, w), np.uint8)
+        g = np.empty(512, np.uint8) if guard else None
+        rs, nr = _rects(rects)
+        self._check(self._L.tw_stage_mask_rects(self._h, _u8(a), _u8(b), w, h, rs, nr, _u8(out), _u8(g) if guard else None))
         return (out, g) if guard else out
 
     def png_kernel_time(self, img, iters=20, waves=0):
@@ -761,16 +834,23 @@ class Engine:
     def level_chunk(self, w, h, level):
         return self._L.tw_level_chunk(self._h, w, h, level)
 
-    def wait(self, ticket):
+    def wait(self, ticket, cap=None):
+        """cap: room for that many vectors only (None: a grid's worth, which cannot overflow); the result then has "count",
+        what tw_wait found, and "vector" holds the first min(count, cap)."""
         tk, w, h, span, threshold = ticket
-        cap = max(self._L.tw_grid_capacity(w, h, span), 1)
-        out = (Vector * cap)()
+        given = cap is not None
+        if not given:
+            cap = max(self._L.tw_grid_capacity(w, h, span), 1)
+        out = (Vector * max(cap, 1))()
         n = C.c_int()
         sec = C.c_float()
         self._check(self._L.tw_wait(self._h, tk, out, cap, C.byref(n), C.byref(sec)))
-        vec = [(out[i].x, out[i].y, out[i].dx, out[i].dy) for i in range(n.value)]
-        return {"status": "OK" if n.value == 0 else "SUSPICIOUS", "span": span, "threshold": threshold,
-                "time": sec.value, "height": h, "width": w, "vector": vec}
+        vec = [(out[i].x, out[i].y, out[i].dx, out[i].dy) for i in range(min(n.value, cap))]
+        res = {"status": "OK" if n.value == 0 else "SUSPICIOUS", "span": span, "threshold": threshold,
+               "time": sec.value, "height": h, "width": w, "vector": vec}
+        if given:
+            res["count"] = n.value
+        return res
 
     def wait_count(self, ticket):
         """tw_wait without materialising the vectors (bench inner loop). Returns (n, seconds)."""

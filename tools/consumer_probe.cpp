@@ -7,6 +7,7 @@
 //   consumer_probe <decode threads> <resident budget, bytes> <batch> <script ...>
 //     R <expected> <target>                  a pair of files
 //     M <w> <h> <first a> <first b>          an in-memory pair (gray, filled with 7 except for pixel 0)
+//     I <x,y,w,h[;x,y,w,h ...]>              ignore rectangles of the NEXT pair (Request::ignore)
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -34,11 +35,24 @@ int main(int argc, char** argv)
     tw_default_params(&params);
     std::vector<std::unique_ptr<std::vector<uint8_t>>> raw;
     int asked = 0;
+    std::vector<Rect> ignore;
     for (int i = 4; i < argc; i++) {
         const std::string op = argv[i];
+        if (op == "I" && i + 1 < argc) {
+            const char* p = argv[++i];
+            Rect rc;
+            int used = 0;
+            while (sscanf(p, "%d,%d,%d,%d%n", &rc.x, &rc.y, &rc.width, &rc.height, &used) == 4) {
+                ignore.push_back(rc);
+                p += used;
+                if (*p == ';') p++;
+            }
+            continue;
+        }
         Request r;
         r.threshold = 5.0;
         r.span = 10;
+        r.ignore.swap(ignore);
         if (op == "R" && i + 2 < argc) {
             r.expect_image = argv[i + 1];
             r.target_image = argv[i + 2];

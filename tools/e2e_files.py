@@ -3,7 +3,7 @@
 through host/index.js create() (addon -> decode pool -> libtwflow.so) and prints pairs/s.  Needs a GPU + node.
 
     e2e_files.py [N [DECODE_THREADS]] [--corpus gray|rgba|palette|mixed|jpeg] [--host DIR] [--json]
-                 [--copies] [--passes K] [--resident MB]
+                 [--copies] [--passes K] [--resident MB] [--ignore N]
     e2e_files.py --kernel-time
 
   --corpus   the kind of file: 8-bit gray (the default, what this tool has always written), RGBA, palette-8 with the
@@ -18,6 +18,8 @@ through host/index.js create() (addon -> decode pool -> libtwflow.so) and prints
              mean of the batches' "decode", "prepare + arena" and "submit + flush" columns per pass
   --resident MB   the instance's residentMB option (resident expected images; implies --passes 2 unless given): pass 1 is
              all misses, pass 2 all hits when the budget holds the corpus (1080p: 2 MB per expected file)
+  --ignore N  every pair gets N ignore rectangles of 300 x 200 pixels (index.js's `ignore` option, calcIgnoring per pair with
+             --passes): the cost of the masked path from files; 0 (the default) makes the calls this tool has always made
   --kernel-time   no files: tw_png_unfilter per 1080p image for RGBA, palette-8 and 1-bit gray rows, event-timed
              (tw_debug_png_kernel_time, 20 launches between two events, the median of 7 such figures)
 The environment goes through unchanged (TW_DEVICE_PNG_KINDS=0 keeps palette files on the host, TW_DEVICE_JPEG=0 / 1 a
@@ -84,6 +86,7 @@ def main():
     ap.add_argument("--copies", action="store_true")
     ap.add_argument("--passes", type=int, default=0)
     ap.add_argument("--resident", type=int, default=0)
+    ap.add_argument("--ignore", type=int, default=0)
     a = ap.parse_args()
     passes = a.passes or (2 if a.resident else 0)  # 0: the one create() run this tool has always made
     if a.kernel_time:
@@ -110,7 +113,8 @@ def main():
                     os.link(made[(i % 4, kind)][0], pe)
                 os.link(made[(i % 4, kind)][1], pt)
         js = ("var T=require('./index'); var t0=Date.now(); var n=0, err=0;"
-              "var t=T.create(process.argv[1],{expectDir:process.argv[2], numThreads:8});"
+              "var opts={expectDir:process.argv[2], numThreads:8}; var ig=JSON.parse(process.argv[5]); if(ig.length) opts.ignore=ig;"
+              "var t=T.create(process.argv[1],opts);"
               "t.on('data',function(){n++}); t.on('error',function(e){err++; console.error(JSON.stringify(e))});"
               "var rss0=process.memoryUsage().rss, rssMid=0; setTimeout(function(){rssMid=process.memoryUsage().rss}, 3000);"
               "t.on('finish',function(r){console.log(JSON.stringify({report:r, ms:Date.now()-t0, errors:err, rss_start_MB:rss0>>20, "
@@ -119,18 +123,23 @@ def main():
             js = ("var T=require('./index'), FS=require('fs'), Path=require('path');"
                   "var tdir=Path.join(process.argv[1],'s'), edir=Path.join(process.argv[2],'s'), passes=+process.argv[3], mb=+process.argv[4];"
                   "var names=FS.readdirSync(tdir).sort(); var opts={numThreads:8}; if(mb>0) opts.residentMB=mb;"
+                  "var ig=JSON.parse(process.argv[5]);"
                   "var t=new T.TidalWave(opts); var ms=[], pass=0, left=0, t0=0, err=0;"
                   "function start(){pass++; console.error('TWE2E PASS '+pass); left=names.length; t0=Date.now();"
-                  " names.forEach(function(n){t.calc(Path.join(edir,n), Path.join(tdir,n))})}"
+                  " names.forEach(function(n){if(ig.length) t.calcIgnoring(Path.join(edir,n), Path.join(tdir,n), ig);"
+                  " else t.calc(Path.join(edir,n), Path.join(tdir,n))})}"
                   "function one(){if(--left===0){ms.push(Date.now()-t0); if(pass<passes) setTimeout(start,50); else t.dispose()}}"
                   "t.on('data',one); t.on('error',function(e){err++; console.error(JSON.stringify(e)); one()});"
                   "t.on('finish',function(r){console.log(JSON.stringify({report:r, ms:ms.reduce(function(x,y){return x+y},0), pass_ms:ms, errors:err}))});"
                   "start();")
+        # N rectangles of 300 x 200 spread over the 1080p image (they may overlap from the seventh on)
+        ignore = [{"x": 100 + 450 * (k % 4), "y": 80 + 330 * (k // 4 % 3), "width": 300, "height": 200} for k in range(a.ignore)]
         env = dict(os.environ)
         if threads:
             env["TW_DECODE_THREADS"] = threads
         t0 = time.time()
-        r = subprocess.run(["node", "-e", js, os.path.join(d, "target"), os.path.join(d, "expected"), str(passes), str(a.resident)],
+        r = subprocess.run(["node", "-e", js, os.path.join(d, "target"), os.path.join(d, "expected"), str(passes), str(a.resident),
+                            json.dumps(ignore)],
                            cwd=a.host, capture_output=True, text=True, env=env)
         wall = time.time() - t0
     finally:
@@ -153,7 +162,8 @@ def main():
                "decode_ms_per_batch": [round(statistics.mean(decode[k]), 2) if k in decode else None for k in range(1, passes + 1)],
                "prepare_arena_ms_per_batch": [round(statistics.mean(prep[k]), 2) if k in prep else None for k in range(1, passes + 1)],
                "submit_flush_ms_per_batch": [round(statistics.mean(submit[k]), 2) if k in submit else None for k in range(1, passes + 1)],
-               "batches": [len(decode.get(k, [])) for k in range(1, passes + 1)], "report": out["report"], "errors": out["errors"]}
+               "batches": [len(decode.get(k, [])) for k in range(1, passes + 1)], "report": out["report"], "errors": out["errors"],
+               "ignore": a.ignore}
         print(json.dumps(res) if a.json else "\n".join("%s: %s" % kv for kv in res.items()))
         return
     rate = n / (out["ms"] / 1e3)
@@ -161,7 +171,7 @@ def main():
         print(json.dumps({"corpus": a.corpus, "pairs": n, "decode_threads": threads or "auto", "host": os.path.relpath(a.host, ROOT),
                           "png_kinds": os.environ.get("TW_DEVICE_PNG_KINDS", "1"),
                           "device_jpeg": os.environ.get("TW_DEVICE_JPEG", "default"), "pairs_per_s": round(rate, 1), "ms": out["ms"],
-                          "report": out["report"], "errors": out["errors"]}))
+                          "report": out["report"], "errors": out["errors"], "ignore": a.ignore}))
         return
     print(r.stdout.strip(), r.stderr.strip()[-3000:])
     print("pairs %d  decode_threads %s  corpus %s  service %.1f pairs/s (node wall %.2fs)" %
