@@ -378,6 +378,39 @@ tw_status tw_submit_image_jpeg_ignore(tw_engine* e, const tw_image* expect, cons
                                       double threshold, const tw_flow_in* init, const tw_flow_out* out,
                                       const tw_rect* ignore, int n_ignore, tw_ticket* ticket);
 
+/* Hit regions (additive within ABI 4, detected by the symbols).  With the engine option TW_OPT_REGIONS on (tw_set_option,
+ * below), a batch groups each pair's vectors into regions on the device, so that a caller can act on "three places changed,
+ * here are their boxes" instead of a flat list of grid vectors — the boxes are what a user pastes back as ignore rectangles.
+ * A pair's hits are the vectors tw_wait reports for it (for a pair with ignore rectangles: what is left after them).  With
+ * the option's value `gap` (1 .. 8), two hits are adjacent when their grid coordinates differ by at most gap grid steps in x
+ * and in y (gap 1: 8-connectivity); a region is a connected component of that adjacency.  Regions are ordered by their first
+ * hit in row-major order (y, then x).  Every field is an integer or a float copied from one sample: nothing is summed, the
+ * result does not depend on the order of evaluation.
+ * The kernel (tw_hit_regions: one workgroup per pair, union-find over the pair's span grid) is launched directly behind the
+ * batch's ordered scan, on the same stream, for the same pairs, and is INSIDE `seconds`.  A batch takes the option's value
+ * in force when its first pair is booked, and all its pairs share it; every submit entry point gains the feature unchanged
+ * (tw_submit_dev* too).  With the option off — the default — every entry point launches exactly what it launched before.
+ * tw_wait_regions is tw_wait plus the regions: *n_regions receives the TRUE number of regions of the pair; `regions`
+ * (nullable) the first min(*n_regions, region_cap, TW_MAX_REGIONS) records — only the first TW_MAX_REGIONS are kept per
+ * pair; `region_of` (nullable) min(*n, cap) entries parallel to `out`: the index of each reported vector's region in that
+ * order, which may be TW_MAX_REGIONS or more (the record is then not kept, the index is still right).  On a ticket whose
+ * batch was opened with the option off it answers TW_E_BAD_PARAMETER and does NOT consume the ticket.  Plain tw_wait on a
+ * regions batch works as before.  A batch with span 0 has no hits: *n_regions = 0.  Errors of the pair itself (a palette
+ * index, the device) are answered as tw_wait answers them. */
+typedef struct tw_region {
+    int x, y, width, height; /* pixel box: x = min hit x, y = min hit y,
+                                width  = min(max hit x + span, pair width)  - x,
+                                height = min(max hit y + span, pair height) - y
+                                (each hit stands for its span x span cell, clipped to the image) */
+    int count;               /* hits in the region */
+    int peak_x, peak_y;      /* the hit with the largest float len = dx*dx + dy*dy, as the scan computes it;
+                                among equal len the first in row-major order */
+    float peak_dx, peak_dy;
+} tw_region;                 /* 36 bytes */
+enum { TW_MAX_REGIONS = 256 };
+tw_status tw_wait_regions(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* n, int* region_of,
+                          tw_region* regions, int region_cap, int* n_regions, float* seconds);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 
@@ -399,8 +432,10 @@ tw_status tw_dev_download(tw_engine* e, void* host, const void* dptr, size_t byt
  *   horizontal accumulators (polyN 5 or 7; what OpenCV's CUDA module does).  NOT bit-identical to the CPU reference;
  *   exists so that "what would the kernel cost without its f64 half, and what would it do to the flow" is a number
  *   (bench.py `polyexp_f32_variant`, profiles/r03_polyexp_f32.md).  Value 2 (polyN 7) additionally fuses every
- *   multiply-add (v_pk_fma_f32).  Never on by default, never bench.py's `value`. */
-enum { TW_OPT_SCAN_FUSED_FINAL = 1, TW_OPT_POLYEXP_F32 = 2 };
+ *   multiply-add (v_pk_fma_f32).  Never on by default, never bench.py's `value`.
+ * TW_OPT_REGIONS (default 0): hit regions, above.  0 is off; 1 .. 8 is the gap; any other value answers
+ *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked. */
+enum { TW_OPT_SCAN_FUSED_FINAL = 1, TW_OPT_POLYEXP_F32 = 2, TW_OPT_REGIONS = 3 };
 tw_status tw_set_option(tw_engine* e, int option, int value);
 
 /* Page-locked host memory.  Images handed to tw_submit_u8 from a block tw_host_alloc returned (or that the caller
@@ -547,6 +582,17 @@ tw_status tw_stage_flow_iter_grid(tw_engine* e, const float* R0_5, const float* 
  * stored.  span >= 1; single_pair = 1 takes npairs = 1, else TW_E_BAD_PARAMETER.  (Additive within version 4.) */
 tw_status tw_stage_span_scan(tw_engine* e, const float* fields, int npairs, int w, int h, int span, double threshold,
                              int single_pair, int* counts, int* xy, float* dxy);
+
+/* tw_hit_regions alone, on the caller's own fields: `fields` as for tw_stage_span_scan — uploaded, gathered by tw_span_gather
+ * and scanned by the ordered scan a batch of npairs such pairs would launch — then one tw_hit_regions launch over the same
+ * grid samples with `gap` (1 .. 8) and, per pair j, the n_ignore[j] rectangles ignore[j * TW_MAX_IGNORE ..] (pair coordinates,
+ * clipped as the submit calls clip them; n_ignore == NULL: none).  With G = ceil(w / span) * ceil(h / span): n_regions[npairs];
+ * regions[npairs][TW_MAX_REGIONS]; region_of[npairs][G], entry k of a pair being the region of its k-th hit.  The outputs are
+ * set to 0xff bytes before the launches, so an entry written beyond a pair's share shows.  The label plane lives in LDS for
+ * G <= 32 768 and in device memory above.  (Additive within version 4.) */
+tw_status tw_stage_hit_regions(tw_engine* e, const float* fields, int npairs, int w, int h, int span, double threshold,
+                               int gap, const tw_rect* ignore, const int* n_ignore, int* n_regions, tw_region* regions,
+                               int* region_of);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,7 @@ enum tw_debug_family {
     TW_DF_SPAN_SCAN_SEG,   /* tw_span_scan_seg: a single pair's ordered scan in 16 independent segments (round 6) */
     TW_DF_BLUR_SOLVE4Q,    /* tw_blur_solve4q: solve + refresh by the horizontal item's owner — a single pair's level-0 launches (round 6) */
     TW_DF_FLOW_ITER_GRID,  /* tw_flow_iter<15, 3>: a batch's last level-0 iteration at the span-grid points only — ALSO counted in TW_DF_FLOW_ITER */
+    TW_DF_HIT_REGIONS,     /* tw_hit_regions: the connected components of a batch's hits, behind its ordered scan (TW_OPT_REGIONS) */
     TW_DF_JPEG_IDCT,       /* tw_jpeg_idct: a batch's JPEG luma blocks -> gray images (tw_submit_jpeg) */
     TW_DF_MASK_RECTS,      /* tw_mask_rects: a batch's ignore rectangles, expected image -> target (tw_submit_*_ignore) */
     TW_DF_PAIR_SAME,       /* tw_pair_same: which pairs of a batch part have two byte-identical images */

@@ -348,6 +348,11 @@ constexpr size_t png_table_bytes(int cap) { return (sizeof(PngJob) + sizeof(unsi
 constexpr size_t jpeg_table_bytes(int cap) { return (sizeof(JpegJob) + 128) * 2 * (size_t)cap; }
 // tw_mask_rects' table of such a batch: a job per rectangle
 constexpr size_t mask_table_bytes(int cap) { return sizeof(MaskJob) * TW_MAX_IGNORE * (size_t)cap; }
+// tw_hit_regions' table of such a batch: the pairs' rectangle counts, then TW_MAX_IGNORE clipped rectangles per pair
+constexpr size_t region_rects_off(int cap) { return (sizeof(int) * (size_t)cap + 15) / 16 * 16; }
+constexpr size_t region_table_bytes(int cap) { return region_rects_off(cap) + sizeof(int4) * TW_MAX_IGNORE * (size_t)cap; }
+static_assert(sizeof(RegionRec) == sizeof(tw_region) && sizeof(tw_region) == 36, "tw_region is the kernel's record");
+static_assert(RGN_MAX == TW_MAX_REGIONS && RGN_RECTS == TW_MAX_IGNORE, "the kernel's limits are the header's");
 
 struct Job {
     const uint8_t *h_a = nullptr, *h_b = nullptr;  // host inputs already staged (null for device inputs)
@@ -464,6 +469,19 @@ struct Ctx {
     // mask_table_bytes(cap) long): tw_mask_rects' jobs, one per rectangle of the batch
     MaskJob *d_msk = nullptr, *h_msk = nullptr;  // h_msk pinned
     bool any_mask = false;
+    // hit regions (TW_OPT_REGIONS; all created when the first batch with the option on is launched from this context):
+    // `regions` = the gap of this batch (0: off), taken when its first pair is booked.  The kernel's outputs belong to the
+    // context as d_rec does (tw_wait_regions reads region_of late for a pair with more than HOST_RECS hits): counts [cap],
+    // kept records [cap][TW_MAX_REGIONS], region_of [cap][G]; their eager copies and the rectangle table are pinned
+    int regions = 0;
+    int* d_nreg = nullptr;
+    RegionRec* d_regs = nullptr;
+    int* d_regof = nullptr;
+    size_t d_regof_cap = 0;
+    int* h_nreg = nullptr;        // [cap]
+    RegionRec* h_regs = nullptr;  // [cap][TW_MAX_REGIONS]
+    int* h_regof = nullptr;       // [cap][HOST_RECS]
+    char* h_rgn = nullptr;        // region_table_bytes(cap)
 
     // the batch is collected or dropped: its resident images may return to the store
     void release_images()
@@ -478,8 +496,9 @@ struct Ctx {
 
     // A new batch in this context: what describes the batch starts over; the device and pinned regions, their capacities
     // and the events survive.
-    void begin_batch(int width, int height, int span_, double threshold_, int64_t first)
+    void begin_batch(int width, int height, int span_, double threshold_, int64_t first, int regions_)
     {
+        regions = regions_;
         release_images();
         jobs.clear();
         launched = false;
@@ -653,6 +672,14 @@ struct tw_engine {
     bool same_valid = false;           // ... and whether tw_pair_same ran for it
     float2* d_grid = nullptr;          // [cap][G] dense grid samples (dx,dy)
     size_t d_grid_cap = 0;
+    // hit regions: TW_OPT_REGIONS as tw_set_option left it (the next batch's gap; 0: off), the device copy of a batch's
+    // rectangle table (region_table_bytes(cap), on first use), tw_hit_regions' label planes for grids that do not fit LDS
+    // ([cap][G], on first use), and whether the LDS kernel's dynamic size has been announced to the runtime
+    int regions_gap = 0;
+    char* d_rgn = nullptr;
+    int* d_lab = nullptr;
+    size_t d_lab_cap = 0;
+    bool rgn_attr = false;
     // profiling: per kernel class, -2 = off, -1 = every level, k = level k only
     int prof_level[TW_K_COUNT] = {-2, -2, -2, -2, -2};
     std::vector<ProfPair> prof_pending[TW_K_COUNT];
@@ -2166,6 +2193,23 @@ void launch_scan(tw_engine* e, hipStream_t st, const ScanArgs& a, const ScanChoi
     else
         TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<false>, dim3(npairs), dim3(1024), 0, st, a);
 }
+// tw_hit_regions behind a scan of the same pairs: the label plane in LDS when the grid fits, in a.lab otherwise
+tw_status launch_hit_regions(tw_engine* e, hipStream_t st, const RegionArgs& a, int npairs)
+{
+    const size_t G = (size_t)a.gw * a.gh;
+    if (G <= (size_t)RGN_LDS_POINTS) {
+        if (!e->rgn_attr) {
+            // (more than the 64 KB a launch may take unannounced)
+            TW_HIP(e, hipFuncSetAttribute((const void*)tw_hit_regions<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          RGN_LDS_POINTS * (int)sizeof(int)));
+            e->rgn_attr = true;
+        }
+        TW_LAUNCH(e, TW_DF_HIT_REGIONS, tw_hit_regions<true>, dim3(npairs), dim3(1024), (G * sizeof(int) + 15) / 16 * 16, st, a);
+    } else {
+        TW_LAUNCH(e, TW_DF_HIT_REGIONS, tw_hit_regions<false>, dim3(npairs), dim3(1024), 0, st, a);
+    }
+    return TW_OK;
+}
 
 // One row of tw_flow_export's destination table / tw_flow_area_init's source table: the caller's device memory in place,
 // or (staged != null) this context's staging slot — dense rows in the field's own layout; null for a pair without a field
@@ -2377,9 +2421,29 @@ struct BatchEnqueue {
             // this context has no results outstanding (it is being launched), nothing on the stream uses its records
             const size_t need_rec = (size_t)tw_grid_capacity(c.w, c.h, c.span) * e->cap;
             TW_TRY(grow_device(e, c.d_rec, c.d_rec_cap, need_rec, need_rec * sizeof(ScanRec) + 256));
+            if (c.regions) TW_TRY(reserve_region_buffers(need_rec));
         }
         // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
         if (c.any_fout_host) TW_TRY(grow_device(e, c.d_fstage, c.d_fstage_cap, fslot * e->cap, fslot * e->cap + 256));
+        return TW_OK;
+    }
+
+    // what tw_hit_regions needs: once per engine, once per context, and per grid size (`need_rec` = cap x G, as d_rec)
+    tw_status reserve_region_buffers(size_t need_rec)
+    {
+        const size_t cap = (size_t)e->cap;
+        if (!e->d_rgn) TW_HIP(e, hipMalloc((void**)&e->d_rgn, region_table_bytes(e->cap) + 256));
+        if (!c.h_rgn) TW_HIP(e, hipHostMalloc((void**)&c.h_rgn, region_table_bytes(e->cap), hipHostMallocDefault));
+        if (!c.d_nreg) TW_HIP(e, hipMalloc((void**)&c.d_nreg, sizeof(int) * cap + 256));
+        if (!c.d_regs) TW_HIP(e, hipMalloc((void**)&c.d_regs, sizeof(RegionRec) * TW_MAX_REGIONS * cap + 256));
+        if (!c.h_nreg) TW_HIP(e, hipHostMalloc((void**)&c.h_nreg, sizeof(int) * cap, hipHostMallocDefault));
+        if (!c.h_regs) TW_HIP(e, hipHostMalloc((void**)&c.h_regs, sizeof(RegionRec) * TW_MAX_REGIONS * cap, hipHostMallocDefault));
+        if (!c.h_regof) TW_HIP(e, hipHostMalloc((void**)&c.h_regof, sizeof(int) * HOST_RECS * cap, hipHostMallocDefault));
+        // (this context has no results outstanding, as for d_rec)
+        TW_TRY(grow_device(e, c.d_regof, c.d_regof_cap, need_rec, need_rec * sizeof(int) + 256));
+        // the label planes are the engine's: an earlier batch's launch may still be using them
+        if ((size_t)gw * gh > (size_t)RGN_LDS_POINTS)
+            TW_TRY(grow_device(e, e->d_lab, e->d_lab_cap, need_rec, need_rec * sizeof(int) + 256, e->stream));
         return TW_OK;
     }
 
@@ -2663,6 +2727,18 @@ struct BatchEnqueue {
             }
             TW_HIP(e, hipMemcpyAsync((void*)e->d_fsrc, c.h_fsrc, sizeof(FlowDst) * n, hipMemcpyHostToDevice, st));
         }
+        if (c.regions && c.any_mask && c.span > 0) {
+            // tw_hit_regions leaves out the grid points tw_wait leaves out: the pairs' clipped rectangles, one upload
+            int* cnt = (int*)c.h_rgn;
+            tw_rect* rects = (tw_rect*)(c.h_rgn + region_rects_off(e->cap));
+            for (int j = 0; j < n; j++) {
+                const std::vector<tw_rect>& ign = c.jobs[j].ign;
+                cnt[j] = (int)ign.size();
+                std::copy(ign.begin(), ign.end(), rects + (size_t)j * TW_MAX_IGNORE);
+            }
+            TW_HIP(e, hipMemcpyAsync(e->d_rgn, c.h_rgn, region_rects_off(e->cap) + sizeof(tw_rect) * TW_MAX_IGNORE * (size_t)n,
+                                     hipMemcpyHostToDevice, st));
+        }
         return TW_OK;
     }
 
@@ -2757,13 +2833,33 @@ struct BatchEnqueue {
             ProfScope pscope(e, st, TW_K_SCAN, 0);
 #ifdef TW_VARIANTS
             // (scan_fused_level0, not fused_final: a batch with a flow destination keeps its gathered grid either way)
-            if (sched.single_pair() && !scan_fused_level0(e, c.span) && process_switches().scan_direct) {
+            // (a regions batch keeps the gathered grid: tw_hit_regions reads the samples the scan read)
+            if (sched.single_pair() && !scan_fused_level0(e, c.span) && process_switches().scan_direct && !c.regions) {
                 TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<true>, dim3(n), dim3(1024), 0, st, a);
             } else
 #endif
             {
                 // a single pair: 16 segments, each workgroup counting the hits before its own (tw_span_scan_seg: -5 us of one CU's VALU time)
                 launch_scan(e, st, a, choose_scan(n, sched.single_pair(), a.gw, a.gh, sw.scan_seg), n);
+            }
+            if (c.regions) {
+                // the hits' connected components, directly behind the scan and inside `seconds`
+                RegionArgs ra;
+                ra.g = e->d_grid;
+                ra.span = c.span;
+                ra.gw = gw;
+                ra.gh = gh;
+                ra.w = c.w;
+                ra.h = c.h;
+                ra.gap = c.regions;
+                ra.thr2 = a.thr2;
+                ra.nrect = c.any_mask ? (const int*)e->d_rgn : nullptr;
+                ra.rects = (const int4*)(e->d_rgn + region_rects_off(e->cap));
+                ra.lab = e->d_lab;
+                ra.n_regions = c.d_nreg;
+                ra.regions = c.d_regs;
+                ra.region_of = c.d_regof;
+                TW_TRY(launch_hit_regions(e, st, ra, n));
             }
         }
         TW_HIP(e, hipEventRecord(c.ev_stop, st));
@@ -2778,6 +2874,13 @@ struct BatchEnqueue {
             TW_HIP(e, hipMemcpyAsync(c.h_count, e->d_count, sizeof(int) * n, hipMemcpyDeviceToHost, st));
             TW_HIP(e, hipMemcpy2DAsync(c.h_rec, HOST_RECS * sizeof(ScanRec), c.d_rec, G * sizeof(ScanRec),
                                        nrec * sizeof(ScanRec), n, hipMemcpyDeviceToHost, st));
+            if (c.regions) {
+                // with the hits: every pair's region count, kept records and the region of its first HOST_RECS hits
+                TW_HIP(e, hipMemcpyAsync(c.h_nreg, c.d_nreg, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+                TW_HIP(e, hipMemcpyAsync(c.h_regs, c.d_regs, sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)n, hipMemcpyDeviceToHost, st));
+                TW_HIP(e, hipMemcpy2DAsync(c.h_regof, HOST_RECS * sizeof(int), c.d_regof, G * sizeof(int), nrec * sizeof(int), n,
+                                           hipMemcpyDeviceToHost, st));
+            }
         }
         // a batch with palette images: the flag words tw_png_unfilter set for an index without a PLTE entry (tw_wait)
         if (c.any_plte)
@@ -3611,7 +3714,7 @@ struct Submit {
             e->cur = nxt;
             c = &e->ctx[nxt];
         }
-        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket);
+        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->regions_gap);
         return TW_OK;
     }
 
@@ -4148,6 +4251,13 @@ void tw_engine_destroy(tw_engine* e)
         if (c.h_jpg) (void)hipHostFree(c.h_jpg);
         if (c.d_msk) (void)hipFree(c.d_msk);
         if (c.h_msk) (void)hipHostFree(c.h_msk);
+        if (c.d_nreg) (void)hipFree(c.d_nreg);
+        if (c.d_regs) (void)hipFree(c.d_regs);
+        if (c.d_regof) (void)hipFree(c.d_regof);
+        if (c.h_nreg) (void)hipHostFree(c.h_nreg);
+        if (c.h_regs) (void)hipHostFree(c.h_regs);
+        if (c.h_regof) (void)hipHostFree(c.h_regof);
+        if (c.h_rgn) (void)hipHostFree(c.h_rgn);
         if (c.h_pflag) (void)hipHostFree(c.h_pflag);
         if (c.ev_h2d) (void)hipEventDestroy(c.ev_h2d);
         for (hipEvent_t ev : c.ev_seg)
@@ -4176,6 +4286,8 @@ void tw_engine_destroy(tw_engine* e)
     if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
     if (e->d_fdst) (void)hipFree(e->d_fdst);
     if (e->d_fsrc) (void)hipFree(e->d_fsrc);
+    if (e->d_rgn) (void)hipFree(e->d_rgn);
+    if (e->d_lab) (void)hipFree(e->d_lab);
     for (tw_image* im : e->res_images) delete im;
     for (tw_engine::ResChunk& ch : e->res_chunks) (void)hipFree(ch.base);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -4627,7 +4739,40 @@ tw_status tw_flush(tw_engine* e)
     return flush_ctx(e, e->ctx[e->cur]);
 }
 
-tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* n, float* seconds)
+namespace {
+// where tw_wait_regions' extra results go (tw_wait: none)
+struct RegionsOut {
+    int* region_of;
+    tw_region* regions;
+    int region_cap;
+    int* n_regions;
+};
+// the regions of pair j of a collected batch: `reported` = the vectors the pair reports (what is left after the ignore
+// filter), of which the first min(reported, cap) went to the caller.  tw_hit_regions left the same points out, so its
+// region_of is parallel to the reported vectors.
+tw_status collect_regions(tw_engine* e, Ctx* c, int j, int reported, int cap, const RegionsOut& ro)
+{
+    const int nreg = c->span > 0 ? c->h_nreg[j] : 0;
+    if (ro.n_regions) *ro.n_regions = nreg;
+    if (c->span <= 0) return TW_OK;
+    if (ro.regions) {
+        const int k = std::max(0, std::min(std::min(nreg, ro.region_cap), (int)TW_MAX_REGIONS));
+        memcpy(ro.regions, c->h_regs + (size_t)j * TW_MAX_REGIONS, sizeof(tw_region) * (size_t)k);
+    }
+    const int m = std::max(0, std::min(reported, cap));
+    if (ro.region_of && m > 0) {
+        if (m <= HOST_RECS) {
+            memcpy(ro.region_of, c->h_regof + (size_t)j * HOST_RECS, sizeof(int) * (size_t)m);
+        } else {
+            // rare, as for the records: the context's own plane still has them
+            const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
+            TW_TRY(d2h_sync(e, ro.region_of, c->d_regof + (size_t)j * G, sizeof(int) * (size_t)m));
+        }
+    }
+    return TW_OK;
+}
+
+tw_status wait_ticket(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* n, float* seconds, const RegionsOut* ro)
 {
     if (!e) return TW_E_BAD_PARAMETER;
     int j = 0;
@@ -4635,6 +4780,10 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
     if (!c) {
         e->err = "unknown ticket";
         return TW_E_BAD_PARAMETER;
+    }
+    if (ro && !c->regions) {
+        e->err = "tw_wait_regions: the ticket's batch was opened with TW_OPT_REGIONS off";
+        return TW_E_BAD_PARAMETER;  // (the ticket stays waitable)
     }
     TW_HIP(e, hipSetDevice(e->device));
     tw_status r;
@@ -4715,6 +4864,7 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
             kept++;
         }
         if (n) *n = kept;
+        if (ro) TW_TRY(collect_regions(e, c, j, kept, cap, *ro));
     } else if (c->span > 0) {
         const int cnt = c->h_count[j];
         if (n) *n = cnt;
@@ -4735,10 +4885,25 @@ tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* 
                 out[i].dx = hr[i].dx;  // float widened to double, src/consumer.cpp:72-73
                 out[i].dy = hr[i].dy;
             }
-    } else if (n) {
-        *n = 0;
+        if (ro) TW_TRY(collect_regions(e, c, j, cnt, cap, *ro));
+    } else {
+        if (n) *n = 0;
+        if (ro) TW_TRY(collect_regions(e, c, j, 0, cap, *ro));
     }
     return TW_OK;
+}
+}  // namespace
+
+tw_status tw_wait(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* n, float* seconds)
+{
+    return wait_ticket(e, ticket, out, cap, n, seconds, nullptr);
+}
+
+tw_status tw_wait_regions(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* n, int* region_of, tw_region* regions,
+                          int region_cap, int* n_regions, float* seconds)
+{
+    const RegionsOut ro = {region_of, regions, region_cap, n_regions};
+    return wait_ticket(e, ticket, out, cap, n, seconds, &ro);
 }
 
 tw_status tw_diff_u8(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
@@ -4831,6 +4996,13 @@ tw_status tw_set_option(tw_engine* e, int option, int value)
     switch (option) {
         case TW_OPT_SCAN_FUSED_FINAL: e->scan_fused = value ? 1 : 0; return TW_OK;
         case TW_OPT_POLYEXP_F32: e->poly_f32 = value == 2 ? 2 : (value ? 1 : 0); return TW_OK;
+        case TW_OPT_REGIONS:
+            if (value < 0 || value > 8) {
+                e->err = "TW_OPT_REGIONS: 0 (off) or a gap of 1 .. 8";
+                return TW_E_BAD_PARAMETER;
+            }
+            e->regions_gap = value;
+            return TW_OK;
         default: e->err = "unknown option"; return TW_E_BAD_PARAMETER;
     }
 }
@@ -5192,7 +5364,7 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
         "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_iter_grid",
-        "tw_jpeg_idct", "tw_mask_rects", "tw_pair_same",
+        "tw_hit_regions", "tw_jpeg_idct", "tw_mask_rects", "tw_pair_same",
         "tw_resize_u8", "tw_flow_area_init", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
 }
@@ -5217,6 +5389,8 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     if (e->dbg_stamps) v[0] += 4096 * sizeof(unsigned long long);
     if (e->d_fdst) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
     if (e->d_fsrc) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
+    if (e->d_rgn) v[0] += region_table_bytes(e->cap) + 256;
+    if (e->d_lab) v[0] += e->d_lab_cap * sizeof(int) + 256;
     for (const Ctx& c : e->ctx) {
         if (c.d_istage) v[0] += c.d_istage_cap + 256;
         if (c.h_fsrc) v[1] += sizeof(FlowDst) * (size_t)e->cap;
@@ -5239,6 +5413,13 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
         if (c.h_jpg) v[1] += jpeg_table_bytes(e->cap);
         if (c.d_msk) v[0] += mask_table_bytes(e->cap) + 256;
         if (c.h_msk) v[1] += mask_table_bytes(e->cap);
+        if (c.d_nreg) v[0] += sizeof(int) * (size_t)e->cap + 256;
+        if (c.d_regs) v[0] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cap + 256;
+        if (c.d_regof) v[0] += c.d_regof_cap * sizeof(int) + 256;
+        if (c.h_nreg) v[1] += sizeof(int) * (size_t)e->cap;
+        if (c.h_regs) v[1] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cap;
+        if (c.h_regof) v[1] += sizeof(int) * HOST_RECS * (size_t)e->cap;
+        if (c.h_rgn) v[1] += region_table_bytes(e->cap);
         if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cap;
         if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cap;
     }
@@ -6034,6 +6215,101 @@ tw_status tw_stage_span_scan(tw_engine* e, const float* fields, int npairs, int 
         dxy[2 * i] = hr[i].dx;
         dxy[2 * i + 1] = hr[i].dy;
     }
+    return TW_OK;
+}
+
+tw_status tw_stage_hit_regions(tw_engine* e, const float* fields, int npairs, int w, int h, int span, double threshold, int gap,
+                               const tw_rect* ignore, const int* n_ignore, int* n_regions, tw_region* regions, int* region_of)
+{
+    if (!e || !fields || !n_regions || !regions || !region_of || npairs < 1 || span < 1 || gap < 1 || gap > 8 ||
+        (n_ignore && !ignore))
+        return TW_E_BAD_PARAMETER;
+    tw_status r;
+    if ((r = check_dims(e, w, h))) return r;
+    // the table a batch uploads: per pair a count and TW_MAX_IGNORE clipped rectangles
+    std::vector<char> tab(region_table_bytes(npairs), 0);
+    bool any_rect = false;
+    for (int j = 0; n_ignore && j < npairs; j++) {
+        std::vector<tw_rect> ign;
+        TW_TRY(clip_ignore(e, ignore + (size_t)j * TW_MAX_IGNORE, n_ignore[j], w, h, &ign));
+        ((int*)tab.data())[j] = (int)ign.size();
+        std::copy(ign.begin(), ign.end(), (tw_rect*)(tab.data() + region_rects_off(npairs)) + (size_t)j * TW_MAX_IGNORE);
+        any_rect = any_rect || !ign.empty();
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    Plan* pl = nullptr;
+    if ((r = get_plan(e, w, h, &pl))) return r;
+    const LevelPlan& L = pl->lv[0];
+    const int gw = (w + span - 1) / span, gh = (h + span - 1) / span;
+    const size_t G = (size_t)gw * gh, nrec = G * (size_t)npairs;
+    Tmp t;
+    float* d_f = t.alloc<float>((size_t)L.ps * 2 * npairs);
+    float2* d_g = t.alloc<float2>(nrec);
+    ScanRec* d_rec = t.alloc<ScanRec>(nrec);
+    int* d_cnt = t.alloc<int>(npairs);
+    char* d_tab = t.alloc<char>(tab.size());
+    int* d_lab = G > (size_t)RGN_LDS_POINTS ? t.alloc<int>(nrec) : nullptr;
+    int* d_nreg = t.alloc<int>(npairs);
+    RegionRec* d_regs = t.alloc<RegionRec>((size_t)TW_MAX_REGIONS * npairs);
+    int* d_regof = t.alloc<int>(nrec);
+    if (!d_f || !d_g || !d_rec || !d_cnt || !d_tab || (G > (size_t)RGN_LDS_POINTS && !d_lab) || !d_nreg || !d_regs || !d_regof)
+        return TW_E_NOMEM;
+    for (int j = 0; j < npairs; j++)
+        if ((r = up_planes(e, d_f + (size_t)j * 2 * L.ps, L.ld, L.ps, fields + (size_t)j * 2 * w * h, w, h, 2))) return r;
+    TW_TRY(h2d_sync(e, d_tab, tab.data(), tab.size()));
+    hipStream_t st = e->stream;
+    // (0xff bytes: whatever the launch did not write reads back as -1 / 0xffffffff words)
+    TW_HIP(e, hipMemsetAsync(d_nreg, 0xff, sizeof(int) * (size_t)npairs, st));
+    TW_HIP(e, hipMemsetAsync(d_regs, 0xff, sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)npairs, st));
+    TW_HIP(e, hipMemsetAsync(d_regof, 0xff, nrec * sizeof(int), st));
+    GatherArgs g;
+    g.flow = d_f;
+    g.fzs = 2 * L.ps;
+    g.fps = L.ps;
+    g.ld = L.ld;
+    g.span = span;
+    g.gw = gw;
+    g.gh = gh;
+    g.g = d_g;
+    TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((gw + 63) / 64, (gh + 3) / 4, npairs), dim3(256), 0, st, g);
+    ScanArgs a;
+    a.g = d_g;
+    a.span = span;
+    a.gw = gw;
+    a.gh = gh;
+    a.thr2 = threshold * threshold;
+    a.count = d_cnt;
+    a.rec_zs = (long long)G;
+    a.rec = d_rec;
+    a.flow = d_f;
+    a.fps = L.ps;
+    a.ld = L.ld;
+    launch_scan(e, st, a, choose_scan(npairs, false, gw, gh, BatchSwitches().scan_seg), npairs);
+    RegionArgs ra;
+    ra.g = d_g;
+    ra.span = span;
+    ra.gw = gw;
+    ra.gh = gh;
+    ra.w = w;
+    ra.h = h;
+    ra.gap = gap;
+    ra.thr2 = a.thr2;
+    ra.nrect = any_rect ? (const int*)d_tab : nullptr;
+    ra.rects = (const int4*)(d_tab + region_rects_off(npairs));
+    ra.lab = d_lab;
+    ra.n_regions = d_nreg;
+    ra.regions = d_regs;
+    ra.region_of = d_regof;
+    {
+        // (tw_prof_select(TW_K_SCAN): this launch alone, for tools/regions_prof.py — a batch's scope holds its scan as well)
+        ProfScope pscope(e, st, TW_K_SCAN, 0);
+        TW_TRY(launch_hit_regions(e, st, ra, npairs));
+    }
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    TW_TRY(d2h_sync(e, n_regions, d_nreg, sizeof(int) * (size_t)npairs));
+    TW_TRY(d2h_sync(e, regions, d_regs, sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)npairs));
+    TW_TRY(d2h_sync(e, region_of, d_regof, nrec * sizeof(int)));
     return TW_OK;
 }
 

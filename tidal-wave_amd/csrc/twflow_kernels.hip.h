@@ -5246,4 +5246,242 @@ __global__ __launch_bounds__(64 * MASK_ROWS) void tw_mask_rects(MaskArgs a)
     }
 }
 
+// =====================================================================================================
+// tw_hit_regions — hit regions (TW_OPT_REGIONS): the connected components of a pair's hits, two hits being adjacent when
+//   their grid coordinates differ by at most `gap` in x and in y.  Launched directly behind the ordered scan, on its stream,
+//   for the same pairs: it is INSIDE `seconds`.  One 1024-thread workgroup per pair, no exchange between workgroups.
+//   A hit is what the scan reports — (double)(float)(dx * dx + dy * dy) > thr2 on the dense grid sample — minus the points
+//   inside one of the pair's clipped ignore rectangles (what tw_wait leaves out on the host).
+//   Phases (a workgroup barrier between each; no barrier stands inside a data-dependent loop, every loop around a barrier
+//   has a trip count computed from G alone, so all 1024 threads reach every barrier):
+//     0  label[i] = i for a hit, -1 otherwise
+//     1  union-find: every hit unites itself with the hits of the forward half of its (2 gap + 1)^2 neighbourhood.
+//        unite(a, b) finds both roots, and hangs the larger root under the smaller with ONE atomic min on the larger root's
+//        word; if that word was no root any more (another thread got there first) it goes on with the word's old value.
+//        find() halves the path with atomic mins.  TERMINATION: a word only ever receives values smaller than its own index
+//        and every atomic min that does not end a unite() found a word that another thread had lowered, so the sum of
+//        all labels strictly decreases with every extra round of any thread; there are G finite labels, bounded below
+//        by 0.  Nobody waits for anybody: no thread's progress depends on another lane of its wave.
+//     2  every hit stores its root: the component's smallest row-major index — the key regions are ordered by
+//     3  the roots are ranked in row-major order (wave ballots + per-wave counts through LDS, tw_span_scan's compaction);
+//        a root's word becomes -2 - rank
+//     4  the hits are ranked the same way — region_of[k] of the pair's k-th hit is its root's rank — and folded into the first
+//        RGN_MAX records in LDS: integer min / max of the grid coordinates, a count, and one 64-bit max on
+//        (bits of len) << 32 | (0xffffffff - index): len of a hit is positive and no NaN, so its bits order as the floats
+//        do, and among equal len the smallest index wins.  Nothing is summed in floating point: the records do not depend on
+//        the order of evaluation.
+//     5  the records go out: pixel boxes (a hit stands for its span x span cell, clipped to the image), the peak's sample
+//   The label plane lives in LDS for grids of up to RGN_LDS_POINTS points (<LDS = true>: 128 KB of the CU's 160), in the
+//   workspace `lab` otherwise.  Label words are updated by atomics while other waves read them: in the workspace EVERY
+//   access to them is an agent-scope atomic (loads and stores that bypass the CU's L1, which an L2 atomic never refreshes),
+//   and each wave drains its stores before a barrier.
+// =====================================================================================================
+struct RegionRec {  // = tw_region
+    int x, y, width, height, count, peak_x, peak_y;
+    float peak_dx, peak_dy;
+};
+constexpr int RGN_MAX = 256;             // = TW_MAX_REGIONS
+constexpr int RGN_RECTS = 32;            // = TW_MAX_IGNORE
+constexpr int RGN_LDS_POINTS = 32768;    // the largest grid whose label plane lives in LDS
+struct RegionArgs {
+    const float2* g;     // pair z: dense grid samples at g + z*G
+    int span, gw, gh, w, h, gap;
+    double thr2;
+    const int* nrect;    // [pairs] rectangles of pair z; null: no pair of the launch has one
+    const int4* rects;   // [pairs][RGN_RECTS] x, y, width, height, clipped to the image
+    int* lab;            // <LDS = false>: pair z's label plane at lab + z*G
+    int* n_regions;      // [pairs]
+    RegionRec* regions;  // [pairs][RGN_MAX]
+    int* region_of;      // pair z at region_of + z*G
+};
+
+template <bool LDS>
+__device__ __forceinline__ int rgn_ld(const int* p)
+{
+    return LDS ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+               : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool LDS>
+__device__ __forceinline__ void rgn_st(int* p, int v)
+{
+    if (LDS) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool LDS>
+__device__ __forceinline__ int rgn_min(int* p, int v)
+{
+    return LDS ? __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+               : __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool LDS>
+__device__ __forceinline__ void rgn_sync()
+{
+    if (!LDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's label stores have left before anyone is let through
+    __syncthreads();
+}
+// the root of x's tree; halves the path on the way (a non-root word gets its grandparent: still an ancestor, and smaller)
+template <bool LDS>
+__device__ __forceinline__ int rgn_find(int* lab, int x)
+{
+    for (;;) {
+        const int p = rgn_ld<LDS>(lab + x);
+        if (p == x) return x;
+        const int gp = rgn_ld<LDS>(lab + p);
+        if (gp == p) return p;
+        rgn_min<LDS>(lab + x, gp);
+        x = gp;
+    }
+}
+template <bool LDS>
+__device__ __forceinline__ void rgn_unite(int* lab, int a, int b)
+{
+    for (;;) {
+        a = rgn_find<LDS>(lab, a);
+        b = rgn_find<LDS>(lab, b);
+        if (a == b) return;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = rgn_min<LDS>(lab + a, b);
+        if (old == a) return;  // a was a root and now hangs under b
+        a = old;               // somebody lowered a's word first: what it pointed to still has to meet b
+    }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(1024) void tw_hit_regions(RegionArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) int rgn_lab[];  // <LDS = true>: [G]
+    __shared__ int4 rc[RGN_RECTS];
+    __shared__ int nrc;
+    __shared__ int wcnt[2][16];
+    __shared__ int bx0[RGN_MAX], by0[RGN_MAX], bx1[RGN_MAX], by1[RGN_MAX], bcnt[RGN_MAX];
+    __shared__ unsigned long long bpeak[RGN_MAX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int z = blockIdx.x;
+    const int G = a.gw * a.gh;
+    const float2* __restrict__ gd = a.g + (long long)z * G;
+    int* lab = LDS ? rgn_lab : a.lab + (long long)z * G;
+    const int nr = a.nrect ? min(a.nrect[z], RGN_RECTS) : 0;
+    if (tid == 0) nrc = nr;
+    if (tid < nr) rc[tid] = a.rects[(long long)z * RGN_RECTS + tid];
+    if (tid < RGN_MAX) {
+        bx0[tid] = by0[tid] = 0x7fffffff;
+        bx1[tid] = by1[tid] = -1;
+        bcnt[tid] = 0;
+        bpeak[tid] = 0ull;
+    }
+    __syncthreads();
+    // 0: the hits
+    for (int idx = tid; idx < G; idx += 1024) {
+        const float2 v = gd[idx];
+        const float len = (v.x * v.x) + (v.y * v.y);
+        bool hit = (double)len > a.thr2;
+        if (hit && nrc) {
+            const int gy = idx / a.gw, gx = idx - gy * a.gw;
+            const int px = gx * a.span, py = gy * a.span;
+            for (int r = 0; r < nrc; r++) {
+                const int4 q = rc[r];
+                if (px >= q.x && px < q.x + q.z && py >= q.y && py < q.y + q.w) hit = false;
+            }
+        }
+        rgn_st<LDS>(lab + idx, hit ? idx : -1);
+    }
+    rgn_sync<LDS>();
+    // 1: unions with the forward half of the neighbourhood (the backward half is the neighbour's forward half)
+    for (int idx = tid; idx < G; idx += 1024) {
+        if (rgn_ld<LDS>(lab + idx) < 0) continue;
+        const int gy = idx / a.gw, gx = idx - gy * a.gw;
+        const int y1 = min(gy + a.gap, a.gh - 1), x1 = min(gx + a.gap, a.gw - 1);
+        for (int y2 = gy; y2 <= y1; y2++)
+            for (int x2 = (y2 == gy) ? gx + 1 : max(gx - a.gap, 0); x2 <= x1; x2++) {
+                const int j = y2 * a.gw + x2;
+                if (rgn_ld<LDS>(lab + j) >= 0) rgn_unite<LDS>(lab, idx, j);
+            }
+    }
+    rgn_sync<LDS>();
+    // 2: every hit takes its root (the roots are final: a store only shortens a path others may be walking)
+    for (int idx = tid; idx < G; idx += 1024) {
+        if (rgn_ld<LDS>(lab + idx) < 0) continue;
+        int r = idx;
+        for (int p = rgn_ld<LDS>(lab + r); p != r; p = rgn_ld<LDS>(lab + r)) r = p;
+        if (r != idx) rgn_st<LDS>(lab + idx, r);
+    }
+    rgn_sync<LDS>();
+    // 3: rank the roots in row-major order
+    int nreg = 0;
+    for (int base = 0, it = 0; base < G; base += 1024, it++) {
+        const int idx = base + tid;
+        const bool root = idx < G && rgn_ld<LDS>(lab + idx) == idx;
+        const unsigned long long b = __ballot(root);
+        if (lane == 0) wcnt[it & 1][wave] = __popcll(b);
+        __syncthreads();
+        int pre = 0, tot = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < 16; w2++) {
+            const int cw = wcnt[it & 1][w2];
+            pre += w2 < wave ? cw : 0;
+            tot += cw;
+        }
+        if (root) rgn_st<LDS>(lab + idx, -2 - (nreg + pre + __popcll(b & ((1ull << lane) - 1ull))));
+        nreg += tot;
+    }
+    rgn_sync<LDS>();
+    if (tid == 0) a.n_regions[z] = nreg;
+    // 4: region_of of the k-th hit, and the fold into the kept records
+    int* __restrict__ rof = a.region_of + (long long)z * G;
+    int nhit = 0;
+    for (int base = 0, it = 0; base < G; base += 1024, it++) {
+        const int idx = base + tid;
+        const int L = idx < G ? rgn_ld<LDS>(lab + idx) : -1;
+        const bool hit = L != -1;
+        const unsigned long long b = __ballot(hit);
+        if (lane == 0) wcnt[it & 1][wave] = __popcll(b);
+        __syncthreads();
+        int pre = 0, tot = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < 16; w2++) {
+            const int cw = wcnt[it & 1][w2];
+            pre += w2 < wave ? cw : 0;
+            tot += cw;
+        }
+        if (hit) {
+            const int reg = -2 - (L <= -2 ? L : rgn_ld<LDS>(lab + L));
+            rof[nhit + pre + __popcll(b & ((1ull << lane) - 1ull))] = reg;
+            if (reg < RGN_MAX) {
+                const int gy = idx / a.gw, gx = idx - gy * a.gw;
+                const float2 v = gd[idx];
+                const float len = (v.x * v.x) + (v.y * v.y);
+                atomicMin(&bx0[reg], gx);
+                atomicMin(&by0[reg], gy);
+                atomicMax(&bx1[reg], gx);
+                atomicMax(&by1[reg], gy);
+                atomicAdd(&bcnt[reg], 1);
+                atomicMax(&bpeak[reg], ((unsigned long long)__float_as_uint(len) << 32) | (0xffffffffu - (unsigned)idx));
+            }
+        }
+        nhit += tot;
+    }
+    __syncthreads();
+    // 5: the kept records
+    if (tid < min(nreg, RGN_MAX)) {
+        const int pidx = (int)(0xffffffffu - (unsigned)bpeak[tid]);
+        const int py = pidx / a.gw, px = pidx - py * a.gw;
+        const float2 v = gd[pidx];
+        RegionRec r;
+        r.x = bx0[tid] * a.span;
+        r.y = by0[tid] * a.span;
+        r.width = min(bx1[tid] * a.span + a.span, a.w) - r.x;
+        r.height = min(by1[tid] * a.span + a.span, a.h) - r.y;
+        r.count = bcnt[tid];
+        r.peak_x = px * a.span;
+        r.peak_y = py * a.span;
+        r.peak_dx = v.x;
+        r.peak_dy = v.y;
+        a.regions[(long long)z * RGN_MAX + tid] = r;
+    }
+}
+
 }  // namespace twk

@@ -72,9 +72,36 @@ napi_value convert_result(napi_env env, const Response& r)
         set_i32(env, v, "y", r.vectors[i].y);
         set_f64(env, v, "dx", r.vectors[i].dx);
         set_f64(env, v, "dy", r.vectors[i].dy);
+        // not in the reference (new TidalWave({regions: gap}) only): the index of the vector's region
+        if (r.hasRegions && i < r.regionOf.size()) set_i32(env, v, "region", r.regionOf[i]);
         napi_set_element(env, arr, (uint32_t)i, v);
     }
     napi_set_named_property(env, o, "vector", arr);
+    if (r.hasRegions) {
+        // ... and behind `vector` the regions themselves; without the option the keys and their order are the reference's.
+        // The engine keeps the first TW_MAX_REGIONS (256) records of a pair: a vector's `region` at or beyond regions.length
+        // is still the right index, of a region whose record was cut (INTEGRATION.md "Hit regions")
+        napi_value regs;
+        napi_create_array_with_length(env, r.regions.size(), &regs);
+        for (size_t i = 0; i < r.regions.size(); i++) {
+            const Region& g = r.regions[i];
+            napi_value v, pk;
+            napi_create_object(env, &v);
+            set_i32(env, v, "x", g.x);
+            set_i32(env, v, "y", g.y);
+            set_i32(env, v, "width", g.width);
+            set_i32(env, v, "height", g.height);
+            set_i32(env, v, "count", g.count);
+            napi_create_object(env, &pk);
+            set_i32(env, pk, "x", g.peak_x);
+            set_i32(env, pk, "y", g.peak_y);
+            set_f64(env, pk, "dx", g.peak_dx);
+            set_f64(env, pk, "dy", g.peak_dy);
+            napi_set_named_property(env, v, "peak", pk);
+            napi_set_element(env, regs, (uint32_t)i, v);
+        }
+        napi_set_named_property(env, o, "regions", regs);
+    }
     return o;
 }
 
@@ -190,6 +217,8 @@ napi_value construct(napi_env env, napi_callback_info info)
     p.optParam.flags = get_i32(env, opts, "flags", 256);  // cv::OPTFLOW_FARNEBACK_GAUSSIAN
     // not in the reference: megabytes of resident expected images per consumer (0: TW_RESIDENT_MB, else off)
     p.residentMB = get_i32(env, opts, "residentMB", 0);
+    // not in the reference: group every pair's vectors into regions — 0 (default): off; 1 .. 8: the gap in grid steps
+    p.regions = get_i32(env, opts, "regions", 0);
 
     Broker* b = new Broker();
     b->env = env;

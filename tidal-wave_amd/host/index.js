@@ -4,7 +4,8 @@
 // so the walk uses fs directly (same '**/*.*' semantics: every file whose name contains a dot).
 // Not in the reference: the options `ignore` (an array of {x, y, width, height}, regions of every pair that may differ) or
 // `getIgnoreRegions(shortPath)` (a function returning such an array, or nothing, for one pair); a pair with regions goes
-// through calcIgnoring, every other pair through calc as before.
+// through calcIgnoring, every other pair through calc as before; and `regions` (1 .. 8), which create() hands to the engine with
+// the other engine options: every 'data' result then carries `regions` behind `vector`, and every vector its `region`.
 'use strict';
 var EventEmitter = require('events').EventEmitter,
   TidalWave = require('./build/Release/tidalwave').TidalWave,

@@ -30,6 +30,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <map>
@@ -64,6 +65,8 @@ struct tw_engine {
     std::map<tw_ticket, PairInfo> info;  // ticket -> what tw_image_keep keeps of the pair
     std::map<const tw_image*, tw_image> images;  // live resident images by handle (a number never handed out twice: looked up, never dereferenced)
     std::map<tw_ticket, std::string> bad;  // tw_submit_png: the image ("expected" / "target") the host's finisher refused
+    int regions = 0;                       // TW_OPT_REGIONS as tw_set_option left it
+    std::map<tw_ticket, int> gap_of;       // ticket -> the option's value when the pair was submitted (0: off)
     std::string err;
     tw_ticket next = 1;
     int submit_calls = 0, busy_at = 0;  // TW_STUB_BUSY_AT
@@ -270,8 +273,16 @@ tw_status tw_host_free(tw_engine* e, void* hptr)
 }
 tw_status tw_set_option(tw_engine* e, int option, int value)
 {
-    if (tracing()) trace(e, "tw_set_option option=%d value=%d -> OK", option, value);
-    return TW_OK;
+    tw_status r = TW_OK;
+    if (option == TW_OPT_REGIONS) {
+        if (value < 0 || value > 8) r = TW_E_BAD_PARAMETER;
+        else if (e) {
+            std::lock_guard<std::mutex> lk(e->m);
+            e->regions = value;
+        }
+    }
+    if (tracing()) trace(e, "tw_set_option option=%d value=%d -> %s", option, value, status_name(r));
+    return r;
 }
 tw_status tw_prof_select(tw_engine* e, int kernel, int level)
 {
@@ -340,6 +351,7 @@ static tw_status stub_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w
     *t = e->next++;
     e->open[*t] = w + (a[0] != b[0] ? 1000000 : 0);
     e->info[*t] = tw_engine::PairInfo{w, h, {a[0], b[0]}};
+    if (e->regions) e->gap_of[*t] = e->regions;
     if (e->batch_ms > 0) {
         e->batch_of[*t] = e->cur_batch;
         if (++e->cur_count >= e->cap) e->launch_locked();  // a full batch starts by itself, like the engine's
@@ -734,6 +746,7 @@ static tw_status stub_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, i
         w = it->second;
         e->open.erase(it);
         e->info.erase(t);
+        e->gap_of.erase(t);
     }
     if (e->batch_ms > 0) {
         stub_clock::time_point until;
@@ -778,6 +791,65 @@ tw_status tw_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, int* n, fl
     const tw_status r = stub_wait(e, t, out, cap, &count, seconds);
     if (n) *n = count;
     if (tracing()) trace(e, "tw_wait ticket=%lld cap=%d -> %s count=%d", (long long)t, cap, status_name(r), count);
+    return r;
+}
+// tw_wait plus a plain host flood fill over the vectors the stub reports.  Those vectors are echoes (x = the pair's width, y =
+// the device), not grid points of an image: every one stands for a 1 x 1 cell, nothing is clipped, `gap` counts units of 1.
+// Two differences from the library, neither visible through the stub's echoes of at most one vector per pair: the gap is the
+// option's value when the PAIR was submitted (the library: when the pair's BATCH was opened), and the regions are those of the
+// first cap + 1 vectors, so *n_regions would not be the true count for a pair with more vectors than cap + 1.
+tw_status tw_wait_regions(tw_engine* e, tw_ticket t, tw_vector* out, int cap, int* n, int* region_of, tw_region* regions,
+                          int region_cap, int* n_regions, float* seconds)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    int gap = 0;
+    {
+        std::lock_guard<std::mutex> lk(e->m);
+        auto it = e->gap_of.find(t);
+        if (it != e->gap_of.end()) gap = it->second;
+    }
+    if (!gap) {  // (the ticket stays waitable)
+        if (tracing()) trace(e, "tw_wait_regions ticket=%lld cap=%d -> %s", (long long)t, cap, status_name(TW_E_BAD_PARAMETER));
+        return TW_E_BAD_PARAMETER;
+    }
+    int count = 0;
+    std::vector<tw_vector> v((size_t)(cap > 0 ? cap : 0) + 1);
+    const tw_status r = stub_wait(e, t, v.data(), (int)v.size(), &count, seconds);
+    if (n) *n = count;
+    const int got = r == TW_OK ? std::min(count, (int)v.size()) : 0;
+    std::vector<int> of((size_t)got, -1);
+    std::vector<tw_region> regs;
+    for (int s = 0; s < got; s++) {
+        if (of[s] >= 0) continue;
+        const int id = (int)regs.size();
+        std::vector<int> stack(1, s), members;
+        of[s] = id;
+        while (!stack.empty()) {
+            const int i = stack.back();
+            stack.pop_back();
+            members.push_back(i);
+            for (int k = 0; k < got; k++)
+                if (of[k] < 0 && abs(v[k].x - v[i].x) <= gap && abs(v[k].y - v[i].y) <= gap) of[k] = id, stack.push_back(k);
+        }
+        std::sort(members.begin(), members.end());
+        int x0 = v[s].x, y0 = v[s].y, x1 = v[s].x, y1 = v[s].y, peak = members[0];
+        const auto len = [&](int i) { return (float)v[i].dx * (float)v[i].dx + (float)v[i].dy * (float)v[i].dy; };
+        for (int i : members) {
+            x0 = std::min(x0, v[i].x), y0 = std::min(y0, v[i].y), x1 = std::max(x1, v[i].x), y1 = std::max(y1, v[i].y);
+            if (len(i) > len(peak)) peak = i;
+        }
+        regs.push_back(tw_region{x0, y0, x1 + 1 - x0, y1 + 1 - y0, (int)members.size(), v[peak].x, v[peak].y, (float)v[peak].dx,
+                                 (float)v[peak].dy});
+    }
+    for (int i = 0; i < got && i < cap; i++) {
+        if (out) out[i] = v[i];
+        if (region_of) region_of[i] = of[i];
+    }
+    if (n_regions) *n_regions = (int)regs.size();
+    for (int i = 0; regions && i < (int)regs.size() && i < region_cap && i < TW_MAX_REGIONS; i++) regions[i] = regs[i];
+    if (tracing())
+        trace(e, "tw_wait_regions ticket=%lld cap=%d -> %s count=%d regions=%d", (long long)t, cap, status_name(r), count,
+              (int)regs.size());
     return r;
 }
 }

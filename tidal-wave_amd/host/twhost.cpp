@@ -35,6 +35,7 @@
 #pragma weak tw_submit_jpeg_ignore
 #pragma weak tw_submit_image_png_ignore
 #pragma weak tw_submit_image_jpeg_ignore
+#pragma weak tw_wait_regions
 
 namespace twhost {
 
@@ -1068,6 +1069,10 @@ struct ConsumerRun {
     // grid-capacity entries per job — 0.5 MB at 1080p / span 10 — cost 0.2 ms of every response, round 4
     std::unique_ptr<tw_vector[]> hits;
     size_t hits_cap = 0;
+    // hit regions (ConsumerShared::regions; 0: off): the gap the engine was given, and tw_wait_regions' scratch arrays
+    int regions_gap = 0;
+    std::vector<int> region_of;
+    std::vector<tw_region> region_recs;
     // Resident expected images (Parameter::residentMB / TW_RESIDENT_MB; 0, the default: off, and no step below reaches the
     // cache): resident_cache.h
     std::unique_ptr<ResidentCache> cache;
@@ -1143,6 +1148,19 @@ struct ConsumerRun {
         // vectors, tests/test_gpu_parity.py::test_scan_fused_final_iteration_option) and worth +3-5 % of GPU throughput; it
         // stays off by default because the reference's consumer computes the whole field (src/consumer.cpp:54).
         if (eng && sw.scan_fused_final) (void)tw_set_option(eng, TW_OPT_SCAN_FUSED_FINAL, 1);
+        // Hit regions (Parameter::regions): the option is set once, here; every batch of this engine then carries it and is
+        // collected with tw_wait_regions.  Off: neither call is made.  A library without the call, or one that refuses the
+        // gap, leaves the consumer without an engine: asked-for regions are never silently dropped.
+        regions_gap = eng && shared ? shared->regions : 0;
+        if (regions_gap) {
+            const tw_status r = tw_wait_regions ? tw_set_option(eng, TW_OPT_REGIONS, regions_gap) : TW_E_UNSUPPORTED;
+            if (r != TW_OK) {
+                eng_err = std::string("engine: regions: ") + tw_strerror(r);
+                tw_engine_destroy(eng);
+                eng = nullptr;
+                regions_gap = 0;
+            }
+        }
         prof = eng && shared && shared->profile;
         if (prof) {
             (void)tw_prof_select(eng, TW_K_BLUR_SOLVE, 0);
@@ -1607,7 +1625,14 @@ struct ConsumerRun {
             tw_vector* const v = hits.get();
             int n = 0;
             float sec = 0;
-            tw_status r = tw_wait(eng, s.ticket, v, cap, &n, &sec);
+            int nreg = 0;
+            if (regions_gap) {
+                region_of.resize((size_t)cap);
+                region_recs.resize(TW_MAX_REGIONS);
+            }
+            tw_status r = regions_gap ? tw_wait_regions(eng, s.ticket, v, cap, &n, region_of.data(), region_recs.data(),
+                                                        TW_MAX_REGIONS, &nreg, &sec)
+                                      : tw_wait(eng, s.ticket, v, cap, &n, &sec);
             if (shared) shared->inflight--;
             if (s.kept) {
                 cache->settle(s.rkey, s.req.expect_image, s.keep, s.kept, s.w, s.h, r);
@@ -1633,6 +1658,12 @@ struct ConsumerRun {
                 out.threshold = s.req.threshold;
                 out.height = s.h;
                 out.width = s.w;
+                if (regions_gap) {
+                    out.hasRegions = true;
+                    out.regionCount = nreg;
+                    out.regionOf.assign(region_of.begin(), region_of.begin() + (long)out.vectors.size());
+                    out.regions.assign(region_recs.begin(), region_recs.begin() + std::max(0, std::min(nreg, (int)TW_MAX_REGIONS)));
+                }
             }
         }
         if (!s.err.empty()) {
@@ -1729,6 +1760,7 @@ void Manager::start(const Parameter& p)
     if (res_mb <= 0)
         if (const char* ev = getenv("TW_RESIDENT_MB")) res_mb = atoll(ev);
     shared_.residentBytes = res_mb > 0 ? res_mb << 20 : 0;
+    shared_.regions = p.regions;
     shared_.stats.assign((size_t)n, ConsumerStats());
     for (int i = 0; i < n; i++) {
         consumers_.push_back(new Consumer(i, requestQueue_, responseQueue_, p.optParam, batch, dec, n, &shared_));

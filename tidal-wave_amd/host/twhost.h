@@ -43,8 +43,16 @@ struct Vector {
     int x, y;
     double dx, dy;
 };
+// A region of a pair's vectors (tw_region of include/twflow.h)
+using Region = tw_region;
 struct Response {
     std::vector<Vector> vectors;
+    // not in the reference (Parameter::regions > 0 only; empty otherwise): the vectors grouped into regions on the device —
+    // the kept records (at most TW_MAX_REGIONS), per vector the index of its region, and the pair's true number of regions
+    std::vector<Region> regions;
+    std::vector<int> regionOf;
+    int regionCount = 0;
+    bool hasRegions = false;
     std::string expect_image, target_image;
     float time = 0;
     double threshold = 0;
@@ -80,6 +88,9 @@ struct Parameter {
     // not in the reference: megabytes of device memory each consumer may fill with resident expected images, keyed by the
     // file's identity (0: TW_RESIDENT_MB, else off — every pair then reads, decodes and uploads both files, as before)
     int residentMB = 0;
+    // not in the reference: group every pair's vectors into regions (the engine option TW_OPT_REGIONS) — 0: off, the calls a
+    // consumer makes are exactly the ones it made before; 1 .. 8: the gap, in grid steps, that still joins two vectors
+    int regions = 0;
 };
 
 // What one consumer did, as seen by Manager::consumerStats() (a copy; the consumer thread owns the original).
@@ -230,6 +241,7 @@ struct ConsumerShared {
     std::atomic<long> inflight{0};  // pairs submitted to an engine and not yet collected, over all consumers
     bool profile = false;
     long long residentBytes = 0;  // the budget of a consumer's resident expected images (0: off)
+    int regions = 0;              // Parameter::regions: a consumer sets TW_OPT_REGIONS once and collects with tw_wait_regions
 };
 
 class Consumer {

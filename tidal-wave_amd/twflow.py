@@ -51,8 +51,21 @@ class Rect(C.Structure):
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int)]
 
 
+class Region(C.Structure):
+    # tw_region (include/twflow.h): one connected component of a pair's hits (TW_OPT_REGIONS / tw_wait_regions), 36 bytes
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int), ("count", C.c_int),
+                ("peak_x", C.c_int), ("peak_y", C.c_int), ("peak_dx", C.c_float), ("peak_dy", C.c_float)]
+
+    def as_tuple(self):
+        return (self.x, self.y, self.width, self.height, self.count, self.peak_x, self.peak_y, self.peak_dx, self.peak_dy)
+
+
 MAX_IGNORE = 32
+MAX_REGIONS = 256
 FLOW_PLANAR, FLOW_INTERLEAVED = 0, 1
+# tw_region as a numpy record (36 bytes, no padding)
+REGION_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4"), ("count", "<i4"),
+                         ("peak_x", "<i4"), ("peak_y", "<i4"), ("peak_dx", "<f4"), ("peak_dy", "<f4")])
 
 
 class TwError(RuntimeError):
@@ -66,6 +79,7 @@ _lib = None
 # every symbol include/twflow.h and include/twflow_debug.h (diagnostics, not part of the boundary) declare
 OPT_SCAN_FUSED_FINAL = 1
 OPT_POLYEXP_F32 = 2
+OPT_REGIONS = 3
 
 SYMBOLS = [
     "tw_default_params", "tw_abi_version", "tw_has_variants", "tw_device_count", "tw_device_pci_bus_id", "tw_engine_create", "tw_engine_destroy", "tw_strerror",
@@ -83,6 +97,7 @@ SYMBOLS = [
     "tw_algorithmic_bytes", "tw_algorithmic_bytes_launch", "tw_level_runs_flow_iter", "tw_algorithmic_bytes_pair", "tw_min_traffic_bytes_pair", "tw_num_levels", "tw_level_chunk", "tw_bench_stage", "tw_stage_pyr_level", "tw_stage_pyr_fused23", "tw_stage_pyr_fused01",
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
     "tw_stage_flow_iter_grid", "tw_stage_span_scan",
+    "tw_wait_regions", "tw_stage_hit_regions",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
     "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time", "tw_debug_scan_plan", "tw_debug_level_plan",
@@ -261,6 +276,9 @@ def _bind(path):
     L.tw_debug_resident.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.tw_debug_resident.restype = C.c_int
     L.tw_wait.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, fp]
+    L.tw_wait_regions.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, ip, C.POINTER(Region), C.c_int, ip, fp]
+    L.tw_stage_hit_regions.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, rp, ip, ip,
+                                       C.POINTER(Region), ip]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
     L.tw_level_chunk.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -852,6 +870,29 @@ class Engine:
             res["count"] = n.value
         return res
 
+    def set_regions(self, gap):
+        """TW_OPT_REGIONS: 0 turns hit regions off (the default), 1 .. 8 is the gap; batches opened from now on take it."""
+        self.set_option(OPT_REGIONS, gap)
+
+    def wait_regions(self, ticket, cap=None, region_cap=MAX_REGIONS):
+        """tw_wait_regions: (status, vectors, region_of, regions, n_regions) — vectors as wait() returns them (the first
+        min(count, cap)), region_of parallel to them, regions the kept records as Region.as_tuple() tuples (x, y, width,
+        height, count, peak_x, peak_y, peak_dx, peak_dy), n_regions the pair's true number of regions."""
+        tk, w, h, span, threshold = ticket
+        if cap is None:
+            cap = max(self._L.tw_grid_capacity(w, h, span), 1)
+        out = (Vector * max(cap, 1))()
+        rof = (C.c_int * max(cap, 1))()
+        regs = (Region * max(region_cap, 1))()
+        n, nreg, sec = C.c_int(), C.c_int(), C.c_float()
+        self._check(self._L.tw_wait_regions(self._h, tk, out, cap, C.byref(n), rof, regs, region_cap, C.byref(nreg),
+                                            C.byref(sec)))
+        m = min(n.value, cap)
+        vec = [(out[i].x, out[i].y, out[i].dx, out[i].dy) for i in range(m)]
+        kept = max(0, min(nreg.value, region_cap, MAX_REGIONS))
+        return ("OK" if n.value == 0 else "SUSPICIOUS", vec, [int(rof[i]) for i in range(m)],
+                [regs[i].as_tuple() for i in range(kept)], nreg.value)
+
     def wait_count(self, ticket):
         """tw_wait without materialising the vectors (bench inner loop). Returns (n, seconds)."""
         tk = ticket[0]
@@ -1095,6 +1136,33 @@ class Engine:
                                                int(bool(single_pair)), counts.ctypes.data_as(C.POINTER(C.c_int)),
                                                xy.ctypes.data_as(C.POINTER(C.c_int)), _f(dxy)))
         return counts, xy, dxy
+
+    def stage_hit_regions(self, fields, span, threshold, gap, ignore=None):
+        """tw_hit_regions alone behind the gather and the ordered scan on `fields` (npairs, 2, h, w); ignore: per pair a
+        list of (x, y, w, h), or None.  (n_regions [npairs] int32, regions [npairs, MAX_REGIONS] structured (the fields of
+        tw_region), region_of [npairs, G] int32); what the launch did not write holds 0xff bytes."""
+        fields = np.ascontiguousarray(fields, np.float32)
+        npairs, two, h, w = fields.shape
+        assert two == 2
+        sp = max(int(span), 1)
+        G = (-(-h // sp)) * (-(-w // sp))
+        nreg = np.zeros(npairs, np.int32)
+        regs = np.zeros((npairs, MAX_REGIONS), REGION_DTYPE)
+        rof = np.zeros((npairs, G), np.int32)
+        rects, nign = None, None
+        if ignore is not None:
+            assert len(ignore) == npairs
+            rects = (Rect * (MAX_IGNORE * npairs))()
+            nign = (C.c_int * npairs)()
+            for j, rs in enumerate(ignore):
+                nign[j] = len(rs)
+                for i, r in enumerate(rs[:MAX_IGNORE]):
+                    rects[j * MAX_IGNORE + i] = Rect(*(int(v) for v in r))
+        ip = C.POINTER(C.c_int)
+        self._check(self._L.tw_stage_hit_regions(self._h, _f(fields), npairs, w, h, int(span), float(threshold), int(gap),
+                                                 rects, nign, nreg.ctypes.data_as(ip),
+                                                 regs.ctypes.data_as(C.POINTER(Region)), rof.ctypes.data_as(ip)))
+        return nreg, regs, rof
 
     def stage_blur_solve(self, R0, R1, M, update_matrices):
         R0 = np.ascontiguousarray(R0, np.float32)

@@ -8,6 +8,8 @@
 //     R <expected> <target>                  a pair of files
 //     M <w> <h> <first a> <first b>          an in-memory pair (gray, filled with 7 except for pixel 0)
 //     I <x,y,w,h[;x,y,w,h ...]>              ignore rectangles of the NEXT pair (Request::ignore)
+//     G <gap>                                hit regions for the whole run (ConsumerShared::regions); a response then ends in
+//                                            " regions <count>: [x,y,w,h n=<hits> peak=(x,y,dx,dy)] ... of: <index per vector>"
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -38,6 +40,10 @@ int main(int argc, char** argv)
     std::vector<Rect> ignore;
     for (int i = 4; i < argc; i++) {
         const std::string op = argv[i];
+        if (op == "G" && i + 1 < argc) {
+            shared.regions = atoi(argv[++i]);
+            continue;
+        }
         if (op == "I" && i + 1 < argc) {
             const char* p = argv[++i];
             Rect rc;
@@ -87,6 +93,14 @@ int main(int argc, char** argv)
             printf("%s|%s|%s|%s|%dx%d|span %d|threshold %g|", r.status.c_str(), r.reason.c_str(), r.expect_image.c_str(),
                    r.target_image.c_str(), r.width, r.height, r.span, r.threshold);
             for (const Vector& v : r.vectors) printf(" (%d,%d,%g,%g)", v.x, v.y, v.dx, v.dy);
+            if (r.hasRegions) {
+                printf(" regions %d:", r.regionCount);
+                for (const Region& g : r.regions)
+                    printf(" [%d,%d,%d,%d n=%d peak=(%d,%d,%g,%g)]", g.x, g.y, g.width, g.height, g.count, g.peak_x, g.peak_y,
+                           g.peak_dx, g.peak_dy);
+                printf(" of:");
+                for (int k : r.regionOf) printf(" %d", k);
+            }
             printf("\n");
         }
         req.stop();
