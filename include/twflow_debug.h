@@ -66,6 +66,8 @@ enum tw_debug_family {
     TW_DF_PNG_UNFILTER,
     TW_DF_SPAN_SCAN_SEG,   /* tw_span_scan_seg: a single pair's ordered scan in 16 independent segments (round 6) */
     TW_DF_BLUR_SOLVE4Q,    /* tw_blur_solve4q: solve + refresh by the horizontal item's owner — a single pair's level-0 launches (round 6) */
+    TW_DF_PYR_LEVEL_LDS,   /* tw_pyr_level_lds: the generic level with its source region staged in LDS — ALSO counted in TW_DF_PYR_LEVEL.
+                            * (Here and not at the end: the enum's tail from TW_DF_HIT_REGIONS on is pinned by the tests of the features that added it) */
     TW_DF_FLOW_ITER_GRID,  /* tw_flow_iter<15, 3>: a batch's last level-0 iteration at the span-grid points only — ALSO counted in TW_DF_FLOW_ITER */
     TW_DF_HIT_REGIONS,     /* tw_hit_regions: the connected components of a batch's hits, behind its ordered scan (TW_OPT_REGIONS) */
     TW_DF_JPEG_IDCT,       /* tw_jpeg_idct: a batch's JPEG luma blocks -> gray images (tw_submit_jpeg) */
@@ -100,6 +102,27 @@ int tw_debug_flow_iter_plan(const tw_engine* e, int width, int height, int npair
  * Returns the number of values written (at most min(n, 9); 0 for a null `out` or a non-positive size), -1 for a null engine.
  * tests/test_gpu_blur_dispatch.py proves from it which side of each edge of the choice ran. */
 int tw_debug_blur_plan(const tw_engine* e, int width, int height, int level, int npairs, int update, int quads, int* out, int n);
+
+/* The choice of one pyramid level's launch at `level` of a width x height image whose rows are `stride` bytes apart, from the
+ * one function the launch itself takes its kernel, grid and LDS size from (choose_pyr), and the plan's two fusion decisions:
+ * out[0] the kernel (0: tw_pyr_k3, 3: tw_pyr_taps, 4: tw_pyr_level_lds, 5: tw_pyr_level; 1 = tw_pyr_k3f and 2 = tw_pyr_23 are
+ * never a level's own launch), out[1] its template argument (tw_pyr_k3: the resize mode 0 / 2; tw_pyr_taps: KS = 9 / 19 / 39, or
+ * 0 for the any-size instantiation; 0 otherwise), out[2] the launch-count family (tw_debug_family; a tw_pyr_level_lds launch
+ * is counted in TW_DF_PYR_LEVEL and in TW_DF_PYR_LEVEL_LDS, and this reports the latter), out[3] threads per workgroup,
+ * out[4] output-tile columns, out[5] output-tile rows, out[6] grid x, out[7] grid y, out[8] dynamic LDS bytes, out[9] bytes per
+ * staged source row (0: the kernel stages none), out[10] 1 when the kernel may load whole dwords of the source rows (`stride` a
+ * multiple of 4 and the images the engine enqueued last 4-byte aligned, as a tw_stage_* call's are: engine state, so ask after
+ * the launch; always 0 for tw_pyr_level, which takes no such argument); the level: out[11] width,
+ * out[12] height, out[13] taps of its smoothing kernel, out[14] resize mode (0: same size, 1: INTER_LINEAR, 2: exact 2 x 2
+ * area), out[15] xmax (output columns from xmax on take a single tap), out[16] the row-buffer height the kernel is given; the
+ * size: out[17] 1 when levels 3 and 2 may come from one tw_pyr_23 launch (Plan::fused23), out[18] 1 when levels 1 and 0 may come
+ * from one tw_pyr_k3f launch (pyr01_fusable), out[19] / out[20] threads of a tw_pyr_23 workgroup for a launch of at most two /
+ * of more images, out[21] the index of the coarsest level, out[22] the output rows whose lower source row is clipped to the image's
+ * last row (only a level as high as the image but narrower has any; one as wide but lower has xmax < width).  It depends on TW_PYR_GENERIC, TW_PYR_GEN_TH and TW_PYR23_THREADS
+ * as tw_engine_create read them.  Returns the number of values written (at most min(n, 23); 0 for a null `out`,
+ * a size without a plan or a level the plan does not have), -1 for a null engine.  tests/test_gpu_pyr_dispatch.py proves from
+ * it which side of each edge of the choice ran (tests/pyr_cases.py, profiles/pyr_dispatch.md). */
+int tw_debug_pyr_plan(const tw_engine* e, int width, int height, int level, long long stride, int* out, int n);
 
 /* The choice of the ordered scan's launch for npairs pairs of width x height pixels at `span`, from the one function the
  * launch itself takes its kernel from (choose_scan): out[0] the kernel (0: tw_span_scan, one workgroup per pair; 1:

@@ -47,6 +47,9 @@ def test_abi_version_and_launch_families(twflow):
     assert "tw_debug_scan_plan" in twflow.SYMBOLS and L.tw_debug_scan_plan(None, 64, 64, 10, 1, 0, None, 0) == -1
     # and the level schedule's (choose_level_schedule)
     assert "tw_debug_level_plan" in twflow.SYMBOLS and L.tw_debug_level_plan(None, 64, 64, 10, 1, 0, None, 0) == -1
+    # and a pyramid level's (choose_pyr)
+    assert "tw_debug_pyr_plan" in twflow.SYMBOLS and L.tw_debug_pyr_plan(None, 64, 64, 0, 64, None, 0) == -1
+    assert "tw_pyr_level_lds" in [n.decode() for n in names]
     assert "tw_stage_span_scan" in twflow.SYMBOLS
     assert L.tw_stage_span_scan(None, None, 1, 64, 64, 10, 5.0, 0, None, None, None) == twflow.TW_E_BAD_PARAMETER
 

@@ -180,6 +180,21 @@ def grouped(cnt):
     return out
 
 
+def predict_own_pyramid(e, plan, w, h):
+    """{family: launches} of the pyramid launches of a level's own, each from the family Engine.pyr_plan (choose_pyr, the
+    function launch_pyr itself launches from) names for that level; a staged generic launch counts in tw_pyr_level as well."""
+    want = dict.fromkeys(PYR_OWN + ("tw_pyr_level_lds",), 0)
+    for rows in plan.parts:
+        for k, r in enumerate(rows):
+            if r.images == OWN:
+                fam = e.pyr_plan(w, h, k).family
+                assert fam in want, (k, fam)
+                want[fam] += r.launches
+                if fam == "tw_pyr_level_lds":
+                    want["tw_pyr_level"] += r.launches
+    return want
+
+
 LEVEL_LOOP = ("pyr_own", "tw_pyr_23", "tw_pyr_k3f", "tw_polyexp", "tw_update_matrices", "tw_flow_iter", "tw_flow_iter_ups",
               "tw_flow_iter_zero", "tw_flow_iter_grid", "windows", "tw_blur_grid", "tw_twin", "tw_pair_same", "tw_span_gather")
 
@@ -218,6 +233,14 @@ def test_the_enqueue_launches_what_the_plan_says(twflow, oracle, monkeypatch, ca
         assert cnt["tw_box"] == 0
         want, wz = predict(plan, it, span, e, w, h)
         assert {f: g[f] for f in LEVEL_LOOP} == {f: want.get(f, 0) for f in LEVEL_LOOP}, (case, cnt, want)
+        # every level's pyramid launch of its own comes from the family choose_pyr names for it
+        # (the twin schedule has no such launch: tw_pyr_23 and tw_pyr_k3f write all four levels, predict_twin asserts it)
+        if plan.kind != "twin":
+            own = predict_own_pyramid(e, plan, w, h)
+            assert {f: cnt[f] for f in own} == own, (case, cnt, own)
+            assert sum(own[f] for f in PYR_OWN) == want.get("pyr_own", 0)
+        else:
+            assert g["pyr_own"] == 0 and cnt["tw_pyr_level_lds"] == 0, cnt
         # (tw_flow_iter_grid is ALSO counted in tw_flow_iter, twflow_debug.h: predict() launches it into both, as the counters do)
         for fam, zs in wz.items():
             members = PYR_OWN if fam == "pyr_own" else WINDOWS if fam == "windows" else (fam,)
@@ -234,6 +257,33 @@ def test_the_enqueue_launches_what_the_plan_says(twflow, oracle, monkeypatch, ca
             assert got[i] == oracle.span_scan(f[0], f[1], span, 0.0), (case, i)
         if fout:
             assert np.array_equal(np.array(out).view(np.uint32), oracle_field(oracle, h, w, 1, it).view(np.uint32))
+
+
+def test_own_pyramid_launches_at_pyr_scale_06_come_from_the_planned_families(twflow, oracle, monkeypatch):
+    """pyrScale 0.6, 333 x 257, four pairs: no level halves exactly, so every level launches a pyramid kernel of its own — level 0
+    tw_pyr_k3<0>, level 1 (3 taps, INTER_LINEAR) the staged generic kernel, levels 2 and 3 (5 / 9 taps) the staged generic
+    kernel and tw_pyr_taps — each from the family Engine.pyr_plan names, and the fields are the oracle's."""
+    w, h, n = 333, 257, 4
+    import synth
+    pairs = [synth.make_pair(i, h, w) for i in range(n)]
+    set_env(monkeypatch, {})
+    with twflow.Engine(0, twflow.default_params(pyrScale=0.6), slots=n) as e:
+        plan = e.level_plan(w, h, 0, n, any_fout=True)
+        assert plan.kind == "batch" and plan.levels == 3 and all(r.images == OWN for rows in plan.parts for r in rows), plan
+        fams = [e.pyr_plan(w, h, k).family for k in range(4)]
+        assert fams[0] == "tw_pyr_k3" and set(fams) == {"tw_pyr_k3", "tw_pyr_level_lds", "tw_pyr_taps"}, fams
+        out = e.host_array((n, 2, h, w), np.float32)
+        e.launch_counts(reset=True)
+        tk = [e.submit(a, b, 0, 5.0, flow=out[i]) for i, (a, b) in enumerate(pairs)]
+        for t in tk:
+            e.wait(t)
+        cnt = e.launch_counts(reset=True)
+        own = predict_own_pyramid(e, plan, w, h)
+        assert {f: cnt[f] for f in own} == own and sum(own[f] for f in PYR_OWN) == sum(r.launches for rows in plan.parts for r in rows), (cnt, own)
+        assert cnt["tw_pyr_23"] == 0 and cnt["tw_pyr_k3f"] == 0, cnt
+        for i, (a, b) in enumerate(pairs):
+            f = np.stack(oracle.farneback(a, b, oracle.default_params(pyrScale=0.6)))
+            assert np.array_equal(np.array(out[i]).view(np.uint32), f.view(np.uint32)), i
 
 
 def test_the_cases_reach_every_value_of_the_plan(twflow, monkeypatch):

@@ -49,7 +49,10 @@ def test_stage_pyr_level(twflow, scale):
         def pyr(img, s, levels, k):
             assert (s, levels) == (scale, 6)
             got = e.stage_pyr_level(img, k)
-            ran(e, PYR_FAMILIES)
+            cnt = ran(e, PYR_FAMILIES)
+            # ... and it is the one launch of the family choose_pyr names for this level (tests/test_gpu_pyr_dispatch.py)
+            fam = e.pyr_plan(img.shape[1], img.shape[0], k).family
+            assert cnt[fam] == 1 and sum(cnt[f] for f in PYR_FAMILIES) == 1, (k, fam, cnt)
             return got
         for h0, w0 in ((257, 333),) + (((1080, 1920),) if scale == 0.6 else ()):
             img = np.random.default_rng(h0 + w0).integers(0, 256, (h0, w0)).astype(np.uint8)

@@ -1397,12 +1397,75 @@ void launch_upd_kernel(tw_engine* e, hipStream_t st, int w, int h, int npairs, c
 }
 
 // ---- kernel launch helpers (nz = images or pairs in this launch) -------------------------------------
+// The choice of one pyramid level's launch — the ONE place it is made: launch_pyr launches it and tw_debug_pyr_plan shows it
+// to the tests.  The register kernel for 3-tap levels that copy or halve exactly, the shared-window row filter for staged
+// levels of 7 .. 63 taps that resize, the staged generic kernel where the tile's source region fits plan_geometry's 64 KB LDS
+// budget, the unstaged one otherwise.  (The two launches that write two levels each, tw_pyr_23 and tw_pyr_k3f, are the
+// plan's decisions: Plan::fused23, pyr01_fusable; pyr23_threads is the former's workgroup size.)
+enum PyrKernel { PYR_KN_K3 = 0, PYR_KN_K3F, PYR_KN_23, PYR_KN_TAPS, PYR_KN_LEVEL_LDS, PYR_KN_LEVEL };
+struct PyrChoice {
+    int kernel;     // PyrKernel
+    int targ;       // the template argument: tw_pyr_k3's MODE (0 / 2), tw_pyr_taps' KS (9 / 19 / 39, 0: any size); 0 otherwise
+    int family;     // tw_debug_family (a staged generic launch is ALSO counted in TW_DF_PYR_LEVEL_LDS)
+    int block;      // threads per workgroup
+    int tw, th;     // output-tile columns and rows
+    unsigned gx, gy;
+    size_t lds;     // dynamic LDS bytes
+    int pitch;      // bytes per staged source row as the kernel lays them out (0: nothing is staged)
+    int aligned4;   // whole-dword loads of the source rows allowed
+    int nrows_max;  // row-buffer height the kernel is given
+};
+PyrChoice choose_pyr(const tw_engine* e, const Plan* pl, int k, long long stride)
+{
+    const LevelPlan& L = pl->lv[k];
+    const int P = (L.mode == 0) ? PYR_TW : 2 * PYR_TW;
+    const int aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
+    PyrChoice c{PYR_KN_LEVEL, 0, TW_DF_PYR_LEVEL, 256, PYR_TW, PYR_TH, (unsigned)((L.w + PYR_TW - 1) / PYR_TW),
+                (unsigned)((L.h + PYR_TH - 1) / PYR_TH), 0, 0, aligned4, L.nrows_max};
+    if (L.ksize == 3 && (L.mode == 0 || L.mode == 2) && pl->w0 >= 16 && !e->pyr_generic) {
+        // register-only fast path (3 taps, same-size or exact 2x2 area resize)
+        c.kernel = PYR_KN_K3;
+        c.targ = L.mode;
+        c.family = TW_DF_PYR_K3;
+        c.tw = 256;
+        c.th = L.mode == 0 ? 8 : 4;
+        c.gx = (L.w + 255) / 256;
+        c.gy = (L.h + c.th - 1) / c.th;
+        return c;
+    }
+    if (L.pitch_b > 0 && L.mode != 0 && L.ksize >= 7 && e->pyr_generic == 0) {
+        // coarse levels: shared-window row filter (tw_pyr_taps)
+        const int pd = (L.pitch_b / 4 + 1) | 1;
+        c.kernel = PYR_KN_TAPS;
+        c.targ = (L.ksize == 9 || L.ksize == 19 || L.ksize == 39) ? L.ksize : 0;
+        c.family = TW_DF_PYR_TAPS;
+        c.lds = ((size_t)L.nrows_max * (2 * PYR_TW) + (size_t)L.nrows_max * pd + 4) * 4;
+        c.pitch = pd * 4;
+        return c;
+    }
+    if (L.pitch_b > 0 && e->pyr_generic != 1) {
+        c.kernel = PYR_KN_LEVEL_LDS;
+        c.lds = (size_t)(PYR_MAXK + (size_t)L.nrows_max * P) * 4 + (size_t)L.nrows_max * L.pitch_b;
+        c.pitch = L.pitch_b;
+        return c;
+    }
+    c.th = L.gen_th;
+    c.gy = (L.h + L.gen_th - 1) / L.gen_th;
+    c.nrows_max = L.gen_nrows_max;
+    c.lds = (size_t)(PYR_MAXK + (size_t)L.gen_nrows_max * P) * 4;
+    c.aligned4 = 0;  // (the unstaged kernel takes no such argument: it reads bytes, and unaligned dwords of interior taps)
+    return c;
+}
+// threads of a tw_pyr_23 workgroup: TW_PYR23_THREADS, or 1024 for a launch of one pair's images and 512 for more
+int pyr23_threads(const tw_engine* e, int nimg) { return e->pyr23_threads ? e->pyr23_threads : nimg <= 2 ? 1024 : 512; }
+
 // same: tw_pair_same's flags of the launch's pairs where the level's only reader of the second images honours them (null:
 // every image) — the 3-tap register kernel skips those images, the other kernels compute them as ever
 void launch_pyr(tw_engine* e, hipStream_t st, const Plan* pl, int k, const uint8_t* const* d_srcs, long long stride,
                 float* I, int nimg, const unsigned* same = nullptr)
 {
     const LevelPlan& L = pl->lv[k];
+    const PyrChoice c = choose_pyr(e, pl, k, stride);
     PyrArgs a;
     a.srcs = d_srcs;
     a.dst = I;
@@ -1421,64 +1484,58 @@ void launch_pyr(tw_engine* e, hipStream_t st, const Plan* pl, int k, const uint8
     a.ksize = L.ksize;
     a.mode = L.mode;
     a.xmax = L.xmax;
-    a.nrows_max = L.nrows_max;
-    a.th = PYR_TH;
-    const int P = (L.mode == 0) ? PYR_TW : 2 * PYR_TW;
-    const size_t lds = (size_t)(PYR_MAXK + (size_t)L.nrows_max * P) * 4;
-    dim3 grid((L.w + PYR_TW - 1) / PYR_TW, (L.h + PYR_TH - 1) / PYR_TH, nimg);
+    a.nrows_max = c.nrows_max;
+    a.th = c.th;
+    const dim3 grid(c.gx, c.gy, nimg), block(c.block);
     ProfScope ps(e, st, TW_K_PYR, k);
-    if (L.ksize == 3 && (L.mode == 0 || L.mode == 2) && pl->w0 >= 16 && !e->pyr_generic) {
-        // register-only fast path (3 taps, same-size or exact 2x2 area resize)
-        PyrK3Args b;
-        b.srcs = d_srcs;
-        b.dst = I;
-        b.dst_zs = L.ps;
-        b.stride = stride;
-        b.w0 = pl->w0;
-        b.h0 = pl->h0;
-        b.w = L.w;
-        b.h = L.h;
-        b.ld = L.ld;
-        b.k0 = L.h_kern[1];
-        b.k1 = L.h_kern[0];
-        b.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
-        b.same = same;
-        if (L.mode == 0) TW_LAUNCH(e, TW_DF_PYR_K3, tw_pyr_k3<0>, dim3((L.w + 255) / 256, (L.h + 7) / 8, nimg), dim3(256), 0, st, b);
-        else TW_LAUNCH(e, TW_DF_PYR_K3, tw_pyr_k3<2>, dim3((L.w + 255) / 256, (L.h + 3) / 4, nimg), dim3(256), 0, st, b);
-        return;
-    }
-    if (L.pitch_b > 0 && L.mode != 0 && L.ksize >= 7 && e->pyr_generic == 0) {
-        // coarse levels: shared-window row filter (tw_pyr_taps)
-        PyrTapsArgs b;
-        b.p = a;
-        b.pd = (L.pitch_b / 4 + 1) | 1;
-        b.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
-        b.dbg = e->dbg_stamps;
-        memset(b.kext, 0, sizeof(b.kext));
-        memcpy(b.kext + 1, L.h_taps.data(), sizeof(float) * L.ksize);
-        const size_t lds3 = ((size_t)L.nrows_max * (2 * PYR_TW) + (size_t)L.nrows_max * b.pd + 4) * 4;
-        switch (L.ksize) {
-            case 9: TW_LAUNCH(e, TW_DF_PYR_TAPS, tw_pyr_taps<9>, grid, dim3(256), lds3, st, b); break;
-            case 19: TW_LAUNCH(e, TW_DF_PYR_TAPS, tw_pyr_taps<19>, grid, dim3(256), lds3, st, b); break;
-            case 39: TW_LAUNCH(e, TW_DF_PYR_TAPS, tw_pyr_taps<39>, grid, dim3(256), lds3, st, b); break;
-            default: TW_LAUNCH(e, TW_DF_PYR_TAPS, tw_pyr_taps<0>, grid, dim3(256), lds3, st, b); break;
+    switch (c.kernel) {
+        case PYR_KN_K3: {
+            PyrK3Args b;
+            b.srcs = d_srcs;
+            b.dst = I;
+            b.dst_zs = L.ps;
+            b.stride = stride;
+            b.w0 = pl->w0;
+            b.h0 = pl->h0;
+            b.w = L.w;
+            b.h = L.h;
+            b.ld = L.ld;
+            b.k0 = L.h_kern[1];
+            b.k1 = L.h_kern[0];
+            b.aligned4 = c.aligned4;
+            b.same = same;
+            if (c.targ == 0) TW_LAUNCH(e, TW_DF_PYR_K3, tw_pyr_k3<0>, grid, block, c.lds, st, b);
+            else TW_LAUNCH(e, TW_DF_PYR_K3, tw_pyr_k3<2>, grid, block, c.lds, st, b);
+            return;
         }
-        return;
-    }
-    if (L.pitch_b > 0 && e->pyr_generic != 1) {
-        PyrLdsArgs b;
-        b.p = a;
-        b.pitch_b = L.pitch_b;
-        b.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
-        TW_LAUNCH(e, TW_DF_PYR_LEVEL, tw_pyr_level_lds, grid, dim3(256), lds + (size_t)L.nrows_max * L.pitch_b, st, b);
-        return;
-    }
-    {
-        a.th = L.gen_th;
-        a.nrows_max = L.gen_nrows_max;
-        const size_t lds_g = (size_t)(PYR_MAXK + (size_t)L.gen_nrows_max * P) * 4;
-        const dim3 grid_g((L.w + PYR_TW - 1) / PYR_TW, (L.h + L.gen_th - 1) / L.gen_th, nimg);
-        TW_LAUNCH(e, TW_DF_PYR_LEVEL, tw_pyr_level, grid_g, dim3(256), lds_g, st, a);
+        case PYR_KN_TAPS: {
+            PyrTapsArgs b;
+            b.p = a;
+            b.pd = c.pitch / 4;
+            b.aligned4 = c.aligned4;
+            b.dbg = e->dbg_stamps;
+            memset(b.kext, 0, sizeof(b.kext));
+            memcpy(b.kext + 1, L.h_taps.data(), sizeof(float) * L.ksize);
+            switch (c.targ) {
+                case 9: TW_LAUNCH(e, TW_DF_PYR_TAPS, tw_pyr_taps<9>, grid, block, c.lds, st, b); break;
+                case 19: TW_LAUNCH(e, TW_DF_PYR_TAPS, tw_pyr_taps<19>, grid, block, c.lds, st, b); break;
+                case 39: TW_LAUNCH(e, TW_DF_PYR_TAPS, tw_pyr_taps<39>, grid, block, c.lds, st, b); break;
+                default: TW_LAUNCH(e, TW_DF_PYR_TAPS, tw_pyr_taps<0>, grid, block, c.lds, st, b); break;
+            }
+            return;
+        }
+        case PYR_KN_LEVEL_LDS: {
+            PyrLdsArgs b;
+            b.p = a;
+            b.pitch_b = c.pitch;
+            b.aligned4 = c.aligned4;
+            // counted as the generic level launch that it is, and in a family of its own
+            e->launches[TW_DF_PYR_LEVEL_LDS]++;
+            e->last_grid_z[TW_DF_PYR_LEVEL_LDS] = grid.z;
+            TW_LAUNCH(e, TW_DF_PYR_LEVEL, tw_pyr_level_lds, grid, block, c.lds, st, b);
+            return;
+        }
+        default: TW_LAUNCH(e, TW_DF_PYR_LEVEL, tw_pyr_level, grid, block, c.lds, st, a); return;
     }
 }
 
@@ -1508,7 +1565,7 @@ void launch_pyr23(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* c
     memcpy(a.k9, pl->k9, sizeof(a.k9));
     ProfScope ps(e, st, TW_K_PYR, 3);
     const dim3 grid((L3.w + P23_T3W - 1) / P23_T3W, (L3.h + P23_T3H - 1) / P23_T3H, nimg);
-    const int nt = e->pyr23_threads ? e->pyr23_threads : nimg <= 2 ? 1024 : 512;
+    const int nt = pyr23_threads(e, nimg);
     if (nt == 256) TW_LAUNCH(e, TW_DF_PYR_23, tw_pyr_23<256>, grid, dim3(256), 0, st, a);
     else if (nt == 1024) TW_LAUNCH(e, TW_DF_PYR_23, tw_pyr_23<1024>, grid, dim3(1024), 0, st, a);
     else TW_LAUNCH(e, TW_DF_PYR_23, tw_pyr_23<512>, grid, dim3(512), 0, st, a);
@@ -5287,6 +5344,31 @@ extern "C" int tw_debug_blur_plan(const tw_engine* e, int width, int height, int
     return i;
 }
 
+extern "C" int tw_debug_pyr_plan(const tw_engine* e, int width, int height, int level, long long stride, int* out, int n)
+{
+    if (!e) return -1;
+    if (!out || width < 1 || height < 1 || level < 0) return 0;
+    Plan scratch;
+    const Plan* g = plan_geometry_of(e, width, height, &scratch);
+    if (!g || level > g->levels) return 0;
+    const PyrChoice c = choose_pyr(e, g, level, stride);
+    const LevelPlan& L = g->lv[level];
+    // output rows whose lower source row yofs + 1 lies past the image and is clipped to h0 - 1 (the level's table, made anew:
+    // the plan keeps it on the device only)
+    int yclip = 0;
+    if (L.mode == 1) {
+        ResizeTab t;
+        make_resize_tab(width, height, L.w, L.h, t);
+        for (int y = 0; y < L.h; y++) yclip += t.yofs[y] + 1 > height - 1;
+    }
+    const int v[23] = {c.kernel, c.targ, c.kernel == PYR_KN_LEVEL_LDS ? (int)TW_DF_PYR_LEVEL_LDS : c.family, c.block, c.tw, c.th,
+                       (int)c.gx, (int)c.gy, (int)c.lds, c.pitch, c.aligned4, L.w, L.h, L.ksize, L.mode, L.xmax, c.nrows_max,
+                       g->fused23 ? 1 : 0, pyr01_fusable(g) ? 1 : 0, pyr23_threads(e, 2), pyr23_threads(e, 3), g->levels, yclip};
+    int i = 0;
+    for (; i < n && i < 23; i++) out[i] = v[i];
+    return i;
+}
+
 extern "C" int tw_debug_scan_plan(const tw_engine* e, int width, int height, int span, int npairs, int single_pair, int* out, int n)
 {
     if (!e) return -1;
@@ -5363,7 +5445,7 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_flow_iter_grid",
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pyr_level_lds", "tw_flow_iter_grid",
         "tw_hit_regions", "tw_jpeg_idct", "tw_mask_rects", "tw_pair_same",
         "tw_resize_u8", "tw_flow_area_init", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;

@@ -101,6 +101,7 @@ SYMBOLS = [
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
     "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time", "tw_debug_scan_plan", "tw_debug_level_plan",
+    "tw_debug_pyr_plan",
 ]
 
 
@@ -333,6 +334,8 @@ def _bind(path):
     L.tw_debug_flow_iter_plan.restype = C.c_int
     L.tw_debug_blur_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.tw_debug_blur_plan.restype = C.c_int
+    L.tw_debug_pyr_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_longlong, ip, C.c_int]
+    L.tw_debug_pyr_plan.restype = C.c_int
     L.tw_debug_scan_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.tw_debug_scan_plan.restype = C.c_int
     L.tw_debug_level_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
@@ -344,6 +347,9 @@ def _bind(path):
 
 FlowIterPlan = collections.namedtuple("FlowIterPlan", "strips segments nt nt_last")
 BlurPlan = collections.namedtuple("BlurPlan", "family block tile_cols rows xsh grid_x grid_y small forced")
+PYR_KERNELS = ("tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level_lds", "tw_pyr_level")
+PyrPlan = collections.namedtuple("PyrPlan", "kernel targ family block tile_cols rows grid_x grid_y lds pitch aligned4 w h ksize mode xmax "
+                                 "nrows_max fused23 fused01 threads23_pair threads23_batch levels yclip")
 ScanPlan = collections.namedtuple("ScanPlan", "kernel gw gh G S segments rounds")
 # images: 0 a pyramid launch of its own, 1 written by the coarser level's launch, 2 its launch writes the next finer level's too
 LevelPlanRow = collections.namedtuple("LevelPlanRow", "pairs per launches tail images init flow_iter same flow_iter_last same_last same01")
@@ -974,6 +980,20 @@ class Engine:
         if n != 9:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_blur_plan(%d, %d, %d, %d) returned %d" % (w, h, level, npairs, n))
         return BlurPlan(self._L.tw_debug_family_name(v[0]).decode(), *v[1:8], bool(v[8]))
+
+    def pyr_plan(self, w, h, level, stride=None):
+        """The choice of one pyramid level's launch at `level` of a w x h image (rows `stride` bytes apart, default w), from
+        the function the launch itself uses (twflow_debug.h: tw_debug_pyr_plan): the kernel's name and template argument,
+        its launch-count family, threads, output-tile columns and rows, grid x / y, dynamic LDS bytes, staged-row pitch,
+        aligned4, the level's width, height, taps, resize mode, xmax and row-buffer height, whether the size is eligible
+        for tw_pyr_23 / tw_pyr_k3f, tw_pyr_23's threads for one pair / a batch, the coarsest level's index, the output rows
+        whose lower source row is clipped to the image's last row."""
+        v = (C.c_int * 23)()
+        n = self._L.tw_debug_pyr_plan(self._h, w, h, level, w if stride is None else stride, v, 23)
+        if n != 23:
+            raise TwError(TW_E_BAD_PARAMETER, "tw_debug_pyr_plan(%d, %d, %d) returned %d" % (w, h, level, n))
+        return PyrPlan(PYR_KERNELS[v[0]], v[1], self._L.tw_debug_family_name(v[2]).decode(), *v[3:10], bool(v[10]), *v[11:17],
+                       bool(v[17]), bool(v[18]), *v[19:23])
 
     def scan_plan(self, w, h, span, npairs=1, single_pair=False):
         """The choice of the ordered scan's launch for npairs pairs of w x h pixels at `span`, from the function the launch
