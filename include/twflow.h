@@ -411,6 +411,43 @@ enum { TW_MAX_REGIONS = 256 };
 tw_status tw_wait_regions(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, int* n, int* region_of,
                           tw_region* regions, int region_cap, int* n_regions, float* seconds);
 
+/* Residual (additive within ABI 4, detected by the symbols).  The vectors answer "where did something move by more than
+ * threshold pixels"; a flat repaint moves nothing (no gradient: the flow solves to zero) and a moved block and a rewritten block
+ * look alike.  With the engine option TW_OPT_RESIDUAL on (tw_set_option, below; its value is the tolerance `tol`, 1 .. 254), a
+ * batch also compares each pair's expected image E with its target T sampled ALONG the pair's final level-0 flow — the field
+ * tw_submit_*_flow exports — and reports, per cell of the span grid, how many differing pixels the flow does not explain.  T is
+ * the target as the batch sees it (after decode, reconcile and ignore masking); w x h is the pair's size.  All arithmetic is
+ * integer after one float -> int conversion per flow component, so the result does not depend on the order of evaluation:
+ *   pixel (x, y) with float flow (dx, dy):
+ *     q(d)  = 0 when d is NaN, else round-half-even of min(max(d, -16384.f), 16384.f) * 32.f as int (the product is exact)
+ *     sx    = clamp(32 * x + q(dx), 0, 32 * (w - 1)),  sy = clamp(32 * y + q(dy), 0, 32 * (h - 1))
+ *     ix    = sx >> 5, ax = sx & 31, x1 = min(ix + 1, w - 1);  iy, ay, y1 alike
+ *     v     = (T[iy][ix]*(32-ax)*(32-ay) + T[iy][x1]*ax*(32-ay) + T[y1][ix]*(32-ax)*ay + T[y1][x1]*ax*ay + 512) >> 10
+ *     diff  = |E[y][x] - T[y][x]|,  u = min(diff, |E[y][x] - v|)
+ *   cell of grid point (gx, gy): pixels [gx*span, min((gx+1)*span, w)) x [gy*span, min((gy+1)*span, h)):
+ *     n_diff = #(diff > tol), n_unexplained = #(u > tol), max_diff = max diff, max_unexplained = max u
+ * A cell is reported iff n_diff >= 1, as a tw_change in row-major order (y, then x); a cell whose grid point lies inside a
+ * clipped ignore rectangle of its pair is not reported (the rule vectors follow).  A batch with span 0 has no cells.
+ * Kernels: tw_warp_residual per level-0 chunk (beside tw_flow_export, before the chunk's flow buffer is reused),
+ * tw_change_scan once per batch directly behind the ordered scan (and tw_hit_regions), inside `seconds`.  A residual batch
+ * needs the dense final field: it takes the schedule a batch with a flow destination takes (no grid-only last iteration, no
+ * captured-graph replay of a single pair).  A batch takes the option's value in force when its first pair is booked, and all
+ * its pairs share it; every submit entry point gains the feature unchanged (tw_submit_dev* too: the images are read in place
+ * with their stride).  With the option off — the default — every entry point launches, copies and records exactly what it
+ * did before, and the feature's buffers do not exist.
+ * tw_ticket_changes is valid from the submit that returned the ticket until the wait that collects it.  It launches the open
+ * batch if it has to, as tw_wait does, and waits for the batch; writes the first min(*n_changes, change_cap) records
+ * (`changes` nullable); *n_changes is the TRUE count after the ignore rule.  It does NOT consume the ticket: tw_wait or
+ * tw_wait_regions follows.  On a batch opened with the option off it answers TW_E_BAD_PARAMETER and the ticket stays
+ * waitable; an unknown or already waited ticket answers TW_E_BAD_PARAMETER; errors of the pair itself (a palette index, the
+ * device) are answered as tw_wait answers them. */
+typedef struct tw_change {
+    int x, y;                   /* the cell's grid point: gx * span, gy * span */
+    int n_diff, n_unexplained;  /* pixels of the cell with diff > tol / with u > tol */
+    int max_diff, max_unexplained;
+} tw_change;                    /* 24 bytes */
+tw_status tw_ticket_changes(tw_engine* e, tw_ticket ticket, tw_change* changes, int change_cap, int* n_changes);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 
@@ -434,8 +471,10 @@ tw_status tw_dev_download(tw_engine* e, void* host, const void* dptr, size_t byt
  *   (bench.py `polyexp_f32_variant`, profiles/r03_polyexp_f32.md).  Value 2 (polyN 7) additionally fuses every
  *   multiply-add (v_pk_fma_f32).  Never on by default, never bench.py's `value`.
  * TW_OPT_REGIONS (default 0): hit regions, above.  0 is off; 1 .. 8 is the gap; any other value answers
+ *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked.
+ * TW_OPT_RESIDUAL (default 0): residual, above.  0 is off; 1 .. 254 is the tolerance; any other value answers
  *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked. */
-enum { TW_OPT_SCAN_FUSED_FINAL = 1, TW_OPT_POLYEXP_F32 = 2, TW_OPT_REGIONS = 3 };
+enum { TW_OPT_SCAN_FUSED_FINAL = 1, TW_OPT_POLYEXP_F32 = 2, TW_OPT_REGIONS = 3, TW_OPT_RESIDUAL = 4 };
 tw_status tw_set_option(tw_engine* e, int option, int value);
 
 /* Page-locked host memory.  Images handed to tw_submit_u8 from a block tw_host_alloc returned (or that the caller
@@ -593,6 +632,15 @@ tw_status tw_stage_span_scan(tw_engine* e, const float* fields, int npairs, int 
 tw_status tw_stage_hit_regions(tw_engine* e, const float* fields, int npairs, int w, int h, int span, double threshold,
                                int gap, const tw_rect* ignore, const int* n_ignore, int* n_regions, tw_region* regions,
                                int* region_of);
+
+/* tw_warp_residual and tw_change_scan alone, on the caller's data, synchronously: `expect` and `target` (w x h bytes, rows
+ * `stride` >= w bytes apart) are placed as a batch places a pair's images, `flow2` (planar [2][h][w]: dx, then dy) is uploaded
+ * into level 0's padded planes as tw_stage_span_scan uploads its fields, then one launch of each kernel with `span` (>= 1) and
+ * `tol` (1 .. 254).  With G = ceil(w / span) * ceil(h / span): cells[G][4] (n_diff, n_unexplained, max_diff, max_unexplained of
+ * every cell, row-major), *n_changes, changes[G].  The outputs are set to 0xff bytes before the launches, so a write beyond the
+ * pair's share shows.  (Additive within version 4.) */
+tw_status tw_stage_warp_residual(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h,
+                                 const float* flow2, int span, int tol, int* cells, int* n_changes, tw_change* changes);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,9 @@ enum tw_debug_family {
     TW_DF_BLUR_SOLVE4Q,    /* tw_blur_solve4q: solve + refresh by the horizontal item's owner — a single pair's level-0 launches (round 6) */
     TW_DF_PYR_LEVEL_LDS,   /* tw_pyr_level_lds: the generic level with its source region staged in LDS — ALSO counted in TW_DF_PYR_LEVEL.
                             * (Here and not at the end: the enum's tail from TW_DF_HIT_REGIONS on is pinned by the tests of the features that added it) */
+    TW_DF_WARP_RESIDUAL,   /* tw_warp_residual: a level-0 chunk's differing pixels against the target sampled along the final flow (TW_OPT_RESIDUAL) */
+    TW_DF_CHANGE_SCAN,     /* tw_change_scan: a batch's cells with a differing pixel, compacted in order behind its ordered scan (TW_OPT_RESIDUAL;
+                            * both here for the reason TW_DF_PYR_LEVEL_LDS is) */
     TW_DF_FLOW_ITER_GRID,  /* tw_flow_iter<15, 3>: a batch's last level-0 iteration at the span-grid points only — ALSO counted in TW_DF_FLOW_ITER */
     TW_DF_HIT_REGIONS,     /* tw_hit_regions: the connected components of a batch's hits, behind its ordered scan (TW_OPT_REGIONS) */
     TW_DF_JPEG_IDCT,       /* tw_jpeg_idct: a batch's JPEG luma blocks -> gray images (tw_submit_jpeg) */
@@ -136,7 +139,7 @@ int tw_debug_scan_plan(const tw_engine* e, int width, int height, int span, int 
 
 /* What a batch of npairs pairs of width x height pixels at `span` launches for each pyramid level, from the one function the
  * enqueue itself executes (choose_level_schedule).  traits: 1 a pair has a flow destination, 2 a pair has an initial field,
- * 4 a profiling class is selected, 8 the single-pair buffers do not exist.  out[0] the schedule (0: level-major batch, 1: one
+ * 4 a profiling class is selected, 8 the single-pair buffers do not exist, 16 the batch was opened with TW_OPT_RESIDUAL on.  out[0] the schedule (0: level-major batch, 1: one
  * pair on two streams, 2: one pair, twin launches), out[1] lanes, out[2] the coarsest level's index L, out[3] 1 when a single
  * pair's window launches take tw_blur_solve4q, out[4] 1 when the last level-0 iteration is the scan-fused one (tw_blur_grid),
  * out[5] 1 when level-0 launches that run tw_flow_iter end in the grid-only iteration, out[6] parts P (a lane's share of the

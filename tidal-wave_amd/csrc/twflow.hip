@@ -353,6 +353,7 @@ constexpr size_t region_rects_off(int cap) { return (sizeof(int) * (size_t)cap +
 constexpr size_t region_table_bytes(int cap) { return region_rects_off(cap) + sizeof(int4) * TW_MAX_IGNORE * (size_t)cap; }
 static_assert(sizeof(RegionRec) == sizeof(tw_region) && sizeof(tw_region) == 36, "tw_region is the kernel's record");
 static_assert(RGN_MAX == TW_MAX_REGIONS && RGN_RECTS == TW_MAX_IGNORE, "the kernel's limits are the header's");
+static_assert(sizeof(ChangeRec) == sizeof(tw_change) && sizeof(tw_change) == 24, "tw_change is the kernel's record");
 
 struct Job {
     const uint8_t *h_a = nullptr, *h_b = nullptr;  // host inputs already staged (null for device inputs)
@@ -482,6 +483,16 @@ struct Ctx {
     RegionRec* h_regs = nullptr;  // [cap][TW_MAX_REGIONS]
     int* h_regof = nullptr;       // [cap][HOST_RECS]
     char* h_rgn = nullptr;        // region_table_bytes(cap)
+    // residual (TW_OPT_RESIDUAL; all created when the first batch with the option on is launched from this context):
+    // `residual` = the tolerance of this batch (0: off), taken when its first pair is booked.  tw_change_scan's outputs
+    // belong to the context as d_rec does (tw_ticket_changes reads the records behind the first HOST_RECS late): counts
+    // [cap], records [cap][G]; their eager copies are pinned
+    int residual = 0;
+    int* d_nchg = nullptr;
+    ChangeRec* d_chg = nullptr;
+    size_t d_chg_cap = 0;
+    int* h_nchg = nullptr;       // [cap]
+    ChangeRec* h_chg = nullptr;  // [cap][HOST_RECS]
 
     // the batch is collected or dropped: its resident images may return to the store
     void release_images()
@@ -496,9 +507,10 @@ struct Ctx {
 
     // A new batch in this context: what describes the batch starts over; the device and pinned regions, their capacities
     // and the events survive.
-    void begin_batch(int width, int height, int span_, double threshold_, int64_t first, int regions_)
+    void begin_batch(int width, int height, int span_, double threshold_, int64_t first, int regions_, int residual_)
     {
         regions = regions_;
+        residual = residual_;
         release_images();
         jobs.clear();
         launched = false;
@@ -680,6 +692,12 @@ struct tw_engine {
     int* d_lab = nullptr;
     size_t d_lab_cap = 0;
     bool rgn_attr = false;
+    // residual: TW_OPT_RESIDUAL as tw_set_option left it (the next batch's tolerance; 0: off), and tw_warp_residual's dense
+    // cell plane ([cap][G] cells of four ints, on first use) — the engine's, as d_grid: the batch's own tw_change_scan
+    // consumes it before the next batch's launches write it
+    int residual_tol = 0;
+    int4* d_cells = nullptr;
+    size_t d_cells_cap = 0;
     // profiling: per kernel class, -2 = off, -1 = every level, k = level k only
     int prof_level[TW_K_COUNT] = {-2, -2, -2, -2, -2};
     std::vector<ProfPair> prof_pending[TW_K_COUNT];
@@ -2268,6 +2286,42 @@ tw_status launch_hit_regions(tw_engine* e, hipStream_t st, const RegionArgs& a, 
     return TW_OK;
 }
 
+// tw_warp_residual over pairs whose images are srcs[2z], srcs[2z + 1] and whose final level-0 flow lies in `flow`
+void launch_warp_residual(tw_engine* e, hipStream_t st, const uint8_t* const* srcs, long long stride, const float* flow,
+                          const LevelPlan& L, int span, int tol, int4* cells, int npairs)
+{
+    WarpResidualArgs a;
+    a.srcs = srcs;
+    a.stride = stride;
+    a.flow = flow;
+    a.fzs = 2 * L.ps;
+    a.fps = L.ps;
+    a.ld = L.ld;
+    a.w = L.w;
+    a.h = L.h;
+    a.span = span;
+    a.gw = (L.w + span - 1) / span;
+    a.gh = (L.h + span - 1) / span;
+    a.cx = std::max(1, WR_COLS / span);
+    a.cy = std::max(1, WR_ROWS / span);
+    a.tol = tol;
+    a.cells = cells;
+    TW_LAUNCH(e, TW_DF_WARP_RESIDUAL, tw_warp_residual, dim3((a.gw + a.cx - 1) / a.cx, (a.gh + a.cy - 1) / a.cy, npairs), dim3(256),
+              sizeof(int4) * (size_t)a.cx * a.cy, st, a);
+}
+void launch_change_scan(tw_engine* e, hipStream_t st, const int4* cells, int span, int gw, int gh, int* count, ChangeRec* rec,
+                        int npairs)
+{
+    ChangeScanArgs a;
+    a.cells = cells;
+    a.span = span;
+    a.gw = gw;
+    a.gh = gh;
+    a.count = count;
+    a.rec = rec;
+    TW_LAUNCH(e, TW_DF_CHANGE_SCAN, tw_change_scan, dim3(npairs), dim3(1024), 0, st, a);
+}
+
 // One row of tw_flow_export's destination table / tw_flow_area_init's source table: the caller's device memory in place,
 // or (staged != null) this context's staging slot — dense rows in the field's own layout; null for a pair without a field
 FlowDst flow_table_row(const void* data, ptrdiff_t pitch, int layout, char* staged, int w)
@@ -2294,6 +2348,9 @@ struct BatchTraits {
     bool any_fout, any_init;  // a pair has a flow destination / an initial field
     bool prof_on;             // a profiling class is selected
     bool lat_buffers;         // the single-pair buffers (lat_I, lat_R) exist
+    // the batch reads its dense final level-0 field itself (TW_OPT_RESIDUAL: tw_warp_residual): the schedule a batch with
+    // a flow destination takes, without being one
+    bool residual = false;
 };
 struct LaunchChoice {
     bool flow_iter;  // the launch's iterations are tw_flow_iter (no tw_update_matrices, no M planes)
@@ -2338,10 +2395,10 @@ LevelSchedule choose_level_schedule(const tw_engine* e, const Plan& g, const Bat
     s.kind = twin ? LS_TWIN : lat ? LS_TWO_STREAM : LS_BATCH;
     s.lat_quads = lat && sw.lat_quads;  // (TW_LAT_QUADS=0: tw_blur_solve4 as in a batch)
     // (a batch with a flow destination needs the last level-0 field itself: never the scan-fused final iteration)
-    s.fused_final = scan_fused_level0(e, t.span) && !t.any_fout;
+    s.fused_final = scan_fused_level0(e, t.span) && !t.any_fout && !t.residual;
     // the grid-only last level-0 iteration: a batch that returns hit records alone reads the last field at the span-grid
     // points only.  (it >= 2: a single iteration is the upsampling one; span >= FI_TH: at most one grid row per step)
-    s.grid_final = sw.grid_final && !lat && !e->scan_fused && !t.any_fout && it >= 2 && t.span >= FI_TH && e->fi_nt == 1024;
+    s.grid_final = sw.grid_final && !lat && !e->scan_fused && !t.any_fout && !t.residual && it >= 2 && t.span >= FI_TH && e->fi_nt == 1024;
     for (int k = 0; k <= g.levels; k++) {
         const LevelPlan& L = g.lv[k];
         LevelChoice& c = s.lv[k];
@@ -2479,6 +2536,7 @@ struct BatchEnqueue {
             const size_t need_rec = (size_t)tw_grid_capacity(c.w, c.h, c.span) * e->cap;
             TW_TRY(grow_device(e, c.d_rec, c.d_rec_cap, need_rec, need_rec * sizeof(ScanRec) + 256));
             if (c.regions) TW_TRY(reserve_region_buffers(need_rec));
+            if (c.residual) TW_TRY(reserve_residual_buffers(need_rec));
         }
         // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
         if (c.any_fout_host) TW_TRY(grow_device(e, c.d_fstage, c.d_fstage_cap, fslot * e->cap, fslot * e->cap + 256));
@@ -2501,6 +2559,20 @@ struct BatchEnqueue {
         // the label planes are the engine's: an earlier batch's launch may still be using them
         if ((size_t)gw * gh > (size_t)RGN_LDS_POINTS)
             TW_TRY(grow_device(e, e->d_lab, e->d_lab_cap, need_rec, need_rec * sizeof(int) + 256, e->stream));
+        return TW_OK;
+    }
+
+    // what the residual kernels need: once per context, and per grid size (`need_rec` = cap x G, as d_rec)
+    tw_status reserve_residual_buffers(size_t need_rec)
+    {
+        const size_t cap = (size_t)e->cap;
+        if (!c.d_nchg) TW_HIP(e, hipMalloc((void**)&c.d_nchg, sizeof(int) * cap + 256));
+        if (!c.h_nchg) TW_HIP(e, hipHostMalloc((void**)&c.h_nchg, sizeof(int) * cap, hipHostMallocDefault));
+        if (!c.h_chg) TW_HIP(e, hipHostMalloc((void**)&c.h_chg, sizeof(ChangeRec) * HOST_RECS * cap, hipHostMallocDefault));
+        // (this context has no results outstanding, as for d_rec)
+        TW_TRY(grow_device(e, c.d_chg, c.d_chg_cap, need_rec, need_rec * sizeof(ChangeRec) + 256));
+        // the cell plane is the engine's: an earlier batch's launches may still be using it
+        TW_TRY(grow_device(e, e->d_cells, e->d_cells_cap, need_rec, need_rec * sizeof(int4) + 256, e->stream));
         return TW_OK;
     }
 
@@ -2803,7 +2875,7 @@ struct BatchEnqueue {
     // the whole batch (the parts of the batch schedule get their own in enqueue_batch_levels)
     tw_status choose_schedule()
     {
-        traits = BatchTraits{n, c.span, c.any_fout, c.any_init, false, e->lat_I != nullptr};
+        traits = BatchTraits{n, c.span, c.any_fout, c.any_init, false, e->lat_I != nullptr, c.residual != 0 && c.span > 0};
         for (int i = 0; i < TW_K_COUNT; i++) traits.prof_on = traits.prof_on || e->prof_level[i] != -2;
         sched = choose_level_schedule(e, *pl, sw, traits, n);
         if (sched.nlanes > 1) {
@@ -2831,7 +2903,9 @@ struct BatchEnqueue {
     tw_status enqueue_or_replay_graph()
     {
         // (destinations / fields would be baked into the graph; a reconciled pair's slots are not what the key describes)
-        if (sched.single_pair() && e->lat_graph && !traits.prof_on && !c.any_fout && !c.any_init && !c.any_resize) {
+        // (a residual batch's launches read the context's cell plane and the batch's tolerance: direct as well)
+        if (sched.single_pair() && e->lat_graph && !traits.prof_on && !c.any_fout && !c.any_init && !c.any_resize &&
+            !traits.residual) {
             const GraphKey key{c.w, c.h, c.span, stride, e->img_aligned4, e->scan_fused, e->poly_f32};
             auto git = e->lat_graphs.find(key);
             if (git == e->lat_graphs.end()) {
@@ -2918,6 +2992,8 @@ struct BatchEnqueue {
                 ra.region_of = c.d_regof;
                 TW_TRY(launch_hit_regions(e, st, ra, n));
             }
+            // the batch's cells with a differing pixel, in order: inside `seconds` too
+            if (c.residual) launch_change_scan(e, st, e->d_cells, c.span, gw, gh, c.d_nchg, c.d_chg, n);
         }
         TW_HIP(e, hipEventRecord(c.ev_stop, st));
         return TW_OK;
@@ -2937,6 +3013,12 @@ struct BatchEnqueue {
                 TW_HIP(e, hipMemcpyAsync(c.h_regs, c.d_regs, sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)n, hipMemcpyDeviceToHost, st));
                 TW_HIP(e, hipMemcpy2DAsync(c.h_regof, HOST_RECS * sizeof(int), c.d_regof, G * sizeof(int), nrec * sizeof(int), n,
                                            hipMemcpyDeviceToHost, st));
+            }
+            if (c.residual) {
+                // as the hits: every pair's count and its first HOST_RECS change records
+                TW_HIP(e, hipMemcpyAsync(c.h_nchg, c.d_nchg, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+                TW_HIP(e, hipMemcpy2DAsync(c.h_chg, HOST_RECS * sizeof(ChangeRec), c.d_chg, G * sizeof(ChangeRec),
+                                           nrec * sizeof(ChangeRec), n, hipMemcpyDeviceToHost, st));
             }
         }
         // a batch with palette images: the flag words tw_png_unfilter set for an index without a PLTE entry (tw_wait)
@@ -3369,6 +3451,12 @@ struct BatchEnqueue {
     {
         if (ch.k != 0) return TW_OK;
         if (c.span > 0 && !ch.grid_only && !ch.grid_last && !grid_stored) enqueue_span_gather(ch);
+        // (before the next chunk reuses flow_cur, on the chunk's stream)
+        if (c.residual && c.span > 0) {
+            ProfScope pscope(e, ch.ls, TW_K_SCAN, 0);
+            launch_warp_residual(e, ch.ls, e->d_ptrs + 2 * ch.j0, stride, ch.flow_cur, pl->lv[0], c.span, c.residual,
+                                 e->d_cells + (size_t)ch.j0 * gw * gh, ch.nc);
+        }
         if (c.any_fout) return export_chunk(e, c, ch.ls, pl->lv[0], ch.flow_cur, ch.j0, ch.nc, fslot);
         return TW_OK;
     }
@@ -3771,7 +3859,7 @@ struct Submit {
             e->cur = nxt;
             c = &e->ctx[nxt];
         }
-        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->regions_gap);
+        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->regions_gap, e->residual_tol);
         return TW_OK;
     }
 
@@ -4315,6 +4403,10 @@ void tw_engine_destroy(tw_engine* e)
         if (c.h_regs) (void)hipHostFree(c.h_regs);
         if (c.h_regof) (void)hipHostFree(c.h_regof);
         if (c.h_rgn) (void)hipHostFree(c.h_rgn);
+        if (c.d_nchg) (void)hipFree(c.d_nchg);
+        if (c.d_chg) (void)hipFree(c.d_chg);
+        if (c.h_nchg) (void)hipHostFree(c.h_nchg);
+        if (c.h_chg) (void)hipHostFree(c.h_chg);
         if (c.h_pflag) (void)hipHostFree(c.h_pflag);
         if (c.ev_h2d) (void)hipEventDestroy(c.ev_h2d);
         for (hipEvent_t ev : c.ev_seg)
@@ -4345,6 +4437,7 @@ void tw_engine_destroy(tw_engine* e)
     if (e->d_fsrc) (void)hipFree(e->d_fsrc);
     if (e->d_rgn) (void)hipFree(e->d_rgn);
     if (e->d_lab) (void)hipFree(e->d_lab);
+    if (e->d_cells) (void)hipFree(e->d_cells);
     for (tw_image* im : e->res_images) delete im;
     for (tw_engine::ResChunk& ch : e->res_chunks) (void)hipFree(ch.base);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -4963,6 +5056,70 @@ tw_status tw_wait_regions(tw_engine* e, tw_ticket ticket, tw_vector* out, int ca
     return wait_ticket(e, ticket, out, cap, n, seconds, &ro);
 }
 
+tw_status tw_ticket_changes(tw_engine* e, tw_ticket ticket, tw_change* changes, int change_cap, int* n_changes)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    int j = 0;
+    Ctx* c = find_ctx(e, ticket, &j);
+    if (!c) {
+        e->err = "unknown ticket";
+        return TW_E_BAD_PARAMETER;
+    }
+    if (!c->residual) {
+        e->err = "tw_ticket_changes: the ticket's batch was opened with TW_OPT_RESIDUAL off";
+        return TW_E_BAD_PARAMETER;  // (the ticket stays waitable)
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    tw_status r;
+    if (!c->launched && (r = flush_ctx(e, *c))) {
+        drop_batch(*c);
+        return r;
+    }
+    // (the ticket is not consumed: the wait that collects it does the per-batch bookkeeping of the copy streams)
+    const hipError_t herr = hipEventSynchronize(c->ev_done);
+    if (herr != hipSuccess) {
+        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
+        return TW_E_DEVICE;
+    }
+    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
+        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
+        return TW_E_BAD_IMAGE_FORMAT;
+    }
+    if (c->span <= 0) {
+        if (n_changes) *n_changes = 0;
+        return TW_OK;
+    }
+    const int cnt = c->h_nchg[j];
+    const std::vector<tw_rect>& ign = c->jobs[j].ign;
+    // all of the pair's records when rectangles filter them, else what the caller takes; the eager copy holds the first
+    // HOST_RECS, the context's own plane the rest
+    const int want = ign.empty() ? std::max(0, std::min(cnt, changes ? change_cap : 0)) : cnt;
+    const ChangeRec* hr = c->h_chg + (size_t)j * HOST_RECS;
+    std::vector<ChangeRec> extra;
+    if (want > HOST_RECS) {
+        const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
+        extra.resize(want);
+        TW_TRY(d2h_sync(e, extra.data(), c->d_chg + (size_t)j * G, (size_t)want * sizeof(ChangeRec)));
+        hr = extra.data();
+    }
+    int kept = 0;
+    if (ign.empty()) {
+        if (want > 0) memcpy(changes, hr, sizeof(tw_change) * (size_t)want);
+        kept = cnt;
+    } else {
+        for (int i = 0; i < cnt; i++) {
+            bool inside = false;
+            for (const tw_rect& q : ign)
+                inside = inside || (hr[i].x >= q.x && hr[i].x < q.x + q.width && hr[i].y >= q.y && hr[i].y < q.y + q.height);
+            if (inside) continue;
+            if (changes && kept < change_cap) memcpy(changes + kept, hr + i, sizeof(tw_change));
+            kept++;
+        }
+    }
+    if (n_changes) *n_changes = kept;
+    return TW_OK;
+}
+
 tw_status tw_diff_u8(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
                      ptrdiff_t stride, int span, double threshold, tw_vector* out, int cap, int* n, float* seconds)
 {
@@ -5059,6 +5216,13 @@ tw_status tw_set_option(tw_engine* e, int option, int value)
                 return TW_E_BAD_PARAMETER;
             }
             e->regions_gap = value;
+            return TW_OK;
+        case TW_OPT_RESIDUAL:
+            if (value < 0 || value > 254) {
+                e->err = "TW_OPT_RESIDUAL: 0 (off) or a tolerance of 1 .. 254";
+                return TW_E_BAD_PARAMETER;
+            }
+            e->residual_tol = value;
             return TW_OK;
         default: e->err = "unknown option"; return TW_E_BAD_PARAMETER;
     }
@@ -5390,7 +5554,7 @@ extern "C" int tw_debug_level_plan(const tw_engine* e, int width, int height, in
     const Plan* gp = plan_geometry_of(e, width, height, &scratch);
     if (!gp) return 0;
     const Plan& g = *gp;
-    const BatchTraits t{npairs, span, (traits & 1) != 0, (traits & 2) != 0, (traits & 4) != 0, !(traits & 8)};
+    const BatchTraits t{npairs, span, (traits & 1) != 0, (traits & 2) != 0, (traits & 4) != 0, !(traits & 8), (traits & 16) != 0};
     const BatchSwitches sw;  // (read at the call, as every batch reads them)
     const int parts = batch_lanes(e, npairs);
     std::vector<int> v;
@@ -5445,7 +5609,8 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pyr_level_lds", "tw_flow_iter_grid",
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pyr_level_lds", "tw_warp_residual", "tw_change_scan",
+        "tw_flow_iter_grid",
         "tw_hit_regions", "tw_jpeg_idct", "tw_mask_rects", "tw_pair_same",
         "tw_resize_u8", "tw_flow_area_init", "tw_flow_export"};
     return (family >= 0 && family < TW_DF_COUNT) ? names[family] : nullptr;
@@ -5473,6 +5638,7 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     if (e->d_fsrc) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
     if (e->d_rgn) v[0] += region_table_bytes(e->cap) + 256;
     if (e->d_lab) v[0] += e->d_lab_cap * sizeof(int) + 256;
+    if (e->d_cells) v[0] += e->d_cells_cap * sizeof(int4) + 256;
     for (const Ctx& c : e->ctx) {
         if (c.d_istage) v[0] += c.d_istage_cap + 256;
         if (c.h_fsrc) v[1] += sizeof(FlowDst) * (size_t)e->cap;
@@ -5502,6 +5668,10 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
         if (c.h_regs) v[1] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cap;
         if (c.h_regof) v[1] += sizeof(int) * HOST_RECS * (size_t)e->cap;
         if (c.h_rgn) v[1] += region_table_bytes(e->cap);
+        if (c.d_nchg) v[0] += sizeof(int) * (size_t)e->cap + 256;
+        if (c.d_chg) v[0] += c.d_chg_cap * sizeof(ChangeRec) + 256;
+        if (c.h_nchg) v[1] += sizeof(int) * (size_t)e->cap;
+        if (c.h_chg) v[1] += sizeof(ChangeRec) * HOST_RECS * (size_t)e->cap;
         if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cap;
         if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cap;
     }
@@ -6392,6 +6562,58 @@ tw_status tw_stage_hit_regions(tw_engine* e, const float* fields, int npairs, in
     TW_TRY(d2h_sync(e, n_regions, d_nreg, sizeof(int) * (size_t)npairs));
     TW_TRY(d2h_sync(e, regions, d_regs, sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)npairs));
     TW_TRY(d2h_sync(e, region_of, d_regof, nrec * sizeof(int)));
+    return TW_OK;
+}
+
+tw_status tw_stage_warp_residual(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h,
+                                 const float* flow2, int span, int tol, int* cells, int* n_changes, tw_change* changes)
+{
+    if (!e || !expect || !target || !flow2 || !cells || !n_changes || !changes || span < 1 || tol < 1 || tol > 254)
+        return TW_E_BAD_PARAMETER;
+    tw_status r;
+    if ((r = check_dims(e, w, h))) return r;
+    if (stride < w) return TW_E_BAD_PARAMETER;
+    TW_HIP(e, hipSetDevice(e->device));
+    Plan* pl = nullptr;
+    if ((r = get_plan(e, w, h, &pl))) return r;
+    const LevelPlan& L = pl->lv[0];
+    const int gw = (w + span - 1) / span, gh = (h + span - 1) / span;
+    const size_t G = (size_t)gw * gh;
+    // the pair's two slots, as a batch stages a host pair: dense rows
+    const size_t npx = staged_image_bytes(w, h);
+    std::vector<uint8_t> img(2 * npx, 0);
+    for (int y = 0; y < h; y++) {
+        memcpy(img.data() + (size_t)y * w, expect + (size_t)y * stride, (size_t)w);
+        memcpy(img.data() + npx + (size_t)y * w, target + (size_t)y * stride, (size_t)w);
+    }
+    Tmp t;
+    uint8_t* d_img = t.alloc<uint8_t>(2 * npx);
+    const uint8_t** d_ptrs = t.alloc<const uint8_t*>(2);
+    float* d_f = t.alloc<float>((size_t)L.ps * 2);
+    int4* d_cells = t.alloc<int4>(G);
+    int* d_cnt = t.alloc<int>(1);
+    ChangeRec* d_chg = t.alloc<ChangeRec>(G);
+    if (!d_img || !d_ptrs || !d_f || !d_cells || !d_cnt || !d_chg) return TW_E_NOMEM;
+    TW_TRY(h2d_sync(e, d_img, img.data(), img.size()));
+    const uint8_t* hp[2] = {d_img, d_img + npx};
+    TW_TRY(h2d_sync(e, (void*)d_ptrs, hp, sizeof(hp)));
+    if ((r = up_planes(e, d_f, L.ld, L.ps, flow2, w, h, 2))) return r;
+    hipStream_t st = e->stream;
+    // (0xff bytes: whatever the launches did not write reads back as -1 words)
+    TW_HIP(e, hipMemsetAsync(d_cells, 0xff, G * sizeof(int4), st));
+    TW_HIP(e, hipMemsetAsync(d_cnt, 0xff, sizeof(int), st));
+    TW_HIP(e, hipMemsetAsync(d_chg, 0xff, G * sizeof(ChangeRec), st));
+    {
+        // (tw_prof_select(TW_K_SCAN): these two launches alone, for measurements)
+        ProfScope pscope(e, st, TW_K_SCAN, 0);
+        launch_warp_residual(e, st, d_ptrs, (long long)w, d_f, L, span, tol, d_cells, 1);
+        launch_change_scan(e, st, d_cells, span, gw, gh, d_cnt, d_chg, 1);
+    }
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    TW_TRY(d2h_sync(e, cells, d_cells, G * sizeof(int4)));
+    TW_TRY(d2h_sync(e, n_changes, d_cnt, sizeof(int)));
+    TW_TRY(d2h_sync(e, changes, d_chg, G * sizeof(ChangeRec)));
     return TW_OK;
 }
 

@@ -5484,4 +5484,134 @@ __global__ __launch_bounds__(1024) void tw_hit_regions(RegionArgs a)
     }
 }
 
+// =====================================================================================================
+// Residual (TW_OPT_RESIDUAL): which differing pixels the pair's final flow does not explain (include/twflow.h has the
+// arithmetic; all of it integer after one float -> int conversion per flow component).
+//   tw_warp_residual : per level-0 chunk, grid z = the chunk's pairs.  A workgroup owns a tile of CX x CY whole cells of the
+//     span grid (CX = max(1, 64 / span), CY = max(1, 32 / span): at most 64 x 32 pixels while a cell fits, one cell
+//     otherwise, walked 64 columns x 4 rows at a time), so it stores its cells' four values with plain stores and no
+//     workgroup ever touches another's cell.  Per pixel one byte of E and of T; only where they differ (diff > 0 — nothing
+//     else can count or raise a maximum) the two flow values and the four bytes of T around the quantised sample point.
+//     The cells' sums and maxima are LDS integer atomics: order-free.  Every load is at clamped coordinates; row bases are
+//     64-bit (a device pair's stride * h may pass 2^32).
+//   tw_change_scan : once per batch, one 1024-thread workgroup per pair: the cells with n_diff >= 1 compacted in row-major
+//     order (tw_span_scan's ballots + per-wave counts) into the pair's tw_change records, and their count.
+// =====================================================================================================
+struct ChangeRec {  // = tw_change
+    int x, y, n_diff, n_unexplained, max_diff, max_unexplained;
+};
+constexpr int WR_COLS = 64, WR_ROWS = 32;  // a tile's pixels while a cell is no larger
+struct WarpResidualArgs {
+    const uint8_t* const* srcs;  // pair z: E = srcs[2z], T = srcs[2z + 1]
+    long long stride;
+    const float* flow;           // pair z: 2 planes at flow + z*fzs, rows ld floats apart
+    long long fzs, fps;
+    int ld, w, h, span, gw, gh, cx, cy, tol;
+    int4* cells;                 // pair z: gw*gh cells at cells + z*gw*gh
+};
+// q(d): NaN -> 0, else round-half-even of clamp(d, -16384, 16384) * 32 (the product is exact)
+__device__ __forceinline__ int wr_quant(float d)
+{
+    if (d != d) return 0;
+    return __float2int_rn(fminf(fmaxf(d, -16384.f), 16384.f) * 32.f);
+}
+__global__ __launch_bounds__(256) void tw_warp_residual(WarpResidualArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) int wr_cell[];  // [cx * cy][4]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int z = blockIdx.z;
+    const int ncell = a.cx * a.cy;
+    for (int i = tid; i < 4 * ncell; i += 256) wr_cell[i] = 0;
+    __syncthreads();
+    const uint8_t* __restrict__ E = a.srcs[2 * z];
+    const uint8_t* __restrict__ T = a.srcs[2 * z + 1];
+    const float* __restrict__ fxp = a.flow + (long long)z * a.fzs;
+    const int gx0 = blockIdx.x * a.cx, gy0 = blockIdx.y * a.cy;
+    const int x0 = gx0 * a.span, y0 = gy0 * a.span;
+    // (64-bit: cx * span is at most 64 or one span, but a span is any positive int)
+    const int tw = (int)min((long long)a.cx * a.span, (long long)(a.w - x0));
+    const int th = (int)min((long long)a.cy * a.span, (long long)(a.h - y0));
+    for (int row = wave; row < th; row += 4) {
+        const int y = y0 + row;
+        const int cyl = row / a.span;
+        const uint8_t* __restrict__ er = E + (long long)y * a.stride;
+        const uint8_t* __restrict__ tr = T + (long long)y * a.stride;
+        for (int col = lane; col < tw; col += 64) {
+            const int x = x0 + col;
+            const int ev = er[x];
+            const int diff = abs(ev - (int)tr[x]);
+            if (diff == 0) continue;
+            const long long fo = (long long)y * a.ld + x;
+            const int sx = min(max(32 * x + wr_quant(fxp[fo]), 0), 32 * (a.w - 1));
+            const int sy = min(max(32 * y + wr_quant(fxp[fo + a.fps]), 0), 32 * (a.h - 1));
+            const int ix = sx >> 5, ax = sx & 31, x1 = min(ix + 1, a.w - 1);
+            const int iy = sy >> 5, ay = sy & 31, y1 = min(iy + 1, a.h - 1);
+            const uint8_t* __restrict__ t0 = T + (long long)iy * a.stride;
+            const uint8_t* __restrict__ t1 = T + (long long)y1 * a.stride;
+            const int v = ((int)t0[ix] * (32 - ax) * (32 - ay) + (int)t0[x1] * ax * (32 - ay) + (int)t1[ix] * (32 - ax) * ay +
+                           (int)t1[x1] * ax * ay + 512) >> 10;
+            const int u = min(diff, abs(ev - v));
+            int* cell = wr_cell + 4 * (cyl * a.cx + col / a.span);
+            if (diff > a.tol) atomicAdd(cell, 1);
+            if (u > a.tol) atomicAdd(cell + 1, 1);
+            atomicMax(cell + 2, diff);
+            if (u) atomicMax(cell + 3, u);
+        }
+    }
+    __syncthreads();
+    int4* __restrict__ out = a.cells + (long long)z * a.gw * a.gh;
+    for (int i = tid; i < ncell; i += 256) {
+        const int cyl = i / a.cx, gx = gx0 + (i - cyl * a.cx), gy = gy0 + cyl;
+        if (gx < a.gw && gy < a.gh)
+            out[(long long)gy * a.gw + gx] = make_int4(wr_cell[4 * i], wr_cell[4 * i + 1], wr_cell[4 * i + 2], wr_cell[4 * i + 3]);
+    }
+}
+
+struct ChangeScanArgs {
+    const int4* cells;  // pair z: gw*gh cells at cells + z*gw*gh
+    int span, gw, gh;
+    int* count;         // [pairs]
+    ChangeRec* rec;     // pair z at rec + z*gw*gh
+};
+__global__ __launch_bounds__(1024) void tw_change_scan(ChangeScanArgs a)
+{
+    __shared__ int wcnt[2][16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int z = blockIdx.x;
+    const int G = a.gw * a.gh;
+    const int4* __restrict__ cd = a.cells + (long long)z * G;
+    ChangeRec* __restrict__ rec = a.rec + (long long)z * G;
+    int nchg = 0;
+    // (the trip count comes from G alone: all 1024 threads reach every barrier)
+    for (int base = 0, it = 0; base < G; base += 1024, it++) {
+        const int idx = base + tid;
+        int4 v = make_int4(0, 0, 0, 0);
+        if (idx < G) v = cd[idx];
+        const bool hit = v.x >= 1;
+        const unsigned long long b = __ballot(hit);
+        if (lane == 0) wcnt[it & 1][wave] = __popcll(b);
+        __syncthreads();
+        int pre = 0, tot = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < 16; w2++) {
+            const int cw = wcnt[it & 1][w2];
+            pre += w2 < wave ? cw : 0;
+            tot += cw;
+        }
+        if (hit) {
+            const int gy = idx / a.gw, gx = idx - gy * a.gw;
+            ChangeRec r;
+            r.x = gx * a.span;
+            r.y = gy * a.span;
+            r.n_diff = v.x;
+            r.n_unexplained = v.y;
+            r.max_diff = v.z;
+            r.max_unexplained = v.w;
+            rec[nchg + pre + __popcll(b & ((1ull << lane) - 1ull))] = r;
+        }
+        nchg += tot;
+    }
+    if (tid == 0) a.count[z] = nchg;
+}
+
 }  // namespace twk

@@ -102,6 +102,25 @@ napi_value convert_result(napi_env env, const Response& r)
         }
         napi_set_named_property(env, o, "regions", regs);
     }
+    if (r.hasChanges) {
+        // not in the reference (new TidalWave({residual: tol}) only), behind the reference's keys (and `regions`): the cells
+        // of the span grid with a pixel that differs by more than tol, and how many of them the flow does not explain
+        napi_value chg;
+        napi_create_array_with_length(env, r.changes.size(), &chg);
+        for (size_t i = 0; i < r.changes.size(); i++) {
+            const Change& c = r.changes[i];
+            napi_value v;
+            napi_create_object(env, &v);
+            set_i32(env, v, "x", c.x);
+            set_i32(env, v, "y", c.y);
+            set_i32(env, v, "diff", c.n_diff);
+            set_i32(env, v, "unexplained", c.n_unexplained);
+            set_i32(env, v, "maxDiff", c.max_diff);
+            set_i32(env, v, "maxUnexplained", c.max_unexplained);
+            napi_set_element(env, chg, (uint32_t)i, v);
+        }
+        napi_set_named_property(env, o, "change", chg);
+    }
     return o;
 }
 
@@ -219,6 +238,10 @@ napi_value construct(napi_env env, napi_callback_info info)
     p.residentMB = get_i32(env, opts, "residentMB", 0);
     // not in the reference: group every pair's vectors into regions — 0 (default): off; 1 .. 8: the gap in grid steps
     p.regions = get_i32(env, opts, "regions", 0);
+    // not in the reference: report the changes the flow does not explain — residual 0 (default): off; 1 .. 254: the tolerance
+    // in gray levels.  residualMin n > 0: a pair with at least n unexplained pixels is SUSPICIOUS even without a vector
+    p.residual = get_i32(env, opts, "residual", 0);
+    p.residualMin = get_i32(env, opts, "residualMin", 0);
 
     Broker* b = new Broker();
     b->env = env;

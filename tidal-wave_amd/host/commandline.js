@@ -3,7 +3,9 @@
 // -threshold -span -pyrScale -pyrLevels -winSize -pyrIterations -polyN -polySigma -flags, two positional
 // paths, pretty JSON per result on stdout.  Not in the reference: -ignore x,y,w,h (repeatable), a region of every pair
 // that may differ; -regions N (1 .. 8), the vectors of every pair grouped into regions (`regions` behind `vector`, `region`
-// in every vector), N being the gap in grid steps that still joins two vectors.  The reference's own script cannot run (it requires
+// in every vector), N being the gap in grid steps that still joins two vectors; -residual N (1 .. 254), the cells of every pair
+// with a pixel that differs by more than N gray levels and how many of those the flow does not explain (`change` behind the
+// other keys), and -residualMin N, which makes a pair with at least N unexplained pixels SUSPICIOUS even without a vector.  The reference's own script cannot run (it requires
 // './opticalflow.js', which does not exist, commandline.js:62); this one drives index.js.  No stdout dup2
 // trick is needed: the native layer here does not print.
 // expect_path / target_path may be two directories (every file of target is paired with the same relative
@@ -20,7 +22,7 @@ var usage =
   '  $ node commandline.js -threshold 1.0 -span 10 test/images test/images2\n';
 
 var supportedOptions = ['threshold', 'span', 'pyrScale', 'pyrLevels', 'winSize', 'pyrIterations', 'polyN',
-  'polySigma', 'flags', 'numThreads', 'regions'];
+  'polySigma', 'flags', 'numThreads', 'regions', 'residual', 'residualMin'];
 
 function getArgs(argv) {
   var positional = [], options = {};

@@ -5,7 +5,9 @@
 // Not in the reference: the options `ignore` (an array of {x, y, width, height}, regions of every pair that may differ) or
 // `getIgnoreRegions(shortPath)` (a function returning such an array, or nothing, for one pair); a pair with regions goes
 // through calcIgnoring, every other pair through calc as before; and `regions` (1 .. 8), which create() hands to the engine with
-// the other engine options: every 'data' result then carries `regions` behind `vector`, and every vector its `region`.
+// the other engine options: every 'data' result then carries `regions` behind `vector`, and every vector its `region`;
+// `residual` (1 .. 254) and `residualMin` likewise: every 'data' result then carries `change`, the cells with a pixel that
+// differs by more than `residual` gray levels, and a pair with at least `residualMin` unexplained pixels is SUSPICIOUS.
 'use strict';
 var EventEmitter = require('events').EventEmitter,
   TidalWave = require('./build/Release/tidalwave').TidalWave,

@@ -67,6 +67,8 @@ struct tw_engine {
     std::map<tw_ticket, std::string> bad;  // tw_submit_png: the image ("expected" / "target") the host's finisher refused
     int regions = 0;                       // TW_OPT_REGIONS as tw_set_option left it
     std::map<tw_ticket, int> gap_of;       // ticket -> the option's value when the pair was submitted (0: off)
+    int residual = 0;                      // TW_OPT_RESIDUAL as tw_set_option left it
+    std::map<tw_ticket, int> tol_of;       // ticket -> that option's value when the pair was submitted (0: off)
     std::string err;
     tw_ticket next = 1;
     int submit_calls = 0, busy_at = 0;  // TW_STUB_BUSY_AT
@@ -281,6 +283,13 @@ tw_status tw_set_option(tw_engine* e, int option, int value)
             e->regions = value;
         }
     }
+    if (option == TW_OPT_RESIDUAL) {
+        if (value < 0 || value > 254) r = TW_E_BAD_PARAMETER;
+        else if (e) {
+            std::lock_guard<std::mutex> lk(e->m);
+            e->residual = value;
+        }
+    }
     if (tracing()) trace(e, "tw_set_option option=%d value=%d -> %s", option, value, status_name(r));
     return r;
 }
@@ -352,6 +361,7 @@ static tw_status stub_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w
     e->open[*t] = w + (a[0] != b[0] ? 1000000 : 0);
     e->info[*t] = tw_engine::PairInfo{w, h, {a[0], b[0]}};
     if (e->regions) e->gap_of[*t] = e->regions;
+    if (e->residual) e->tol_of[*t] = e->residual;
     if (e->batch_ms > 0) {
         e->batch_of[*t] = e->cur_batch;
         if (++e->cur_count >= e->cap) e->launch_locked();  // a full batch starts by itself, like the engine's
@@ -747,6 +757,7 @@ static tw_status stub_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, i
         e->open.erase(it);
         e->info.erase(t);
         e->gap_of.erase(t);
+        e->tol_of.erase(t);
     }
     if (e->batch_ms > 0) {
         stub_clock::time_point until;
@@ -850,6 +861,32 @@ tw_status tw_wait_regions(tw_engine* e, tw_ticket t, tw_vector* out, int cap, in
     if (tracing())
         trace(e, "tw_wait_regions ticket=%lld cap=%d -> %s count=%d regions=%d", (long long)t, cap, status_name(r), count,
               (int)regs.size());
+    return r;
+}
+// The change records of a pair that was submitted with TW_OPT_RESIDUAL on; the ticket is not consumed.  The stub compares no
+// pixels: every such pair has ONE record, an echo like its vector — x = the pair's width, y = the device, n_diff =
+// n_unexplained = the tolerance, max_diff = max_unexplained = |first byte of the expected image - first byte of the target|.
+// As for the regions, the tolerance is the option's value when the PAIR was submitted.
+tw_status tw_ticket_changes(tw_engine* e, tw_ticket t, tw_change* changes, int change_cap, int* n_changes)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    tw_status r = TW_OK;
+    tw_change rec = {0, 0, 0, 0, 0, 0};
+    {
+        std::lock_guard<std::mutex> lk(e->m);
+        auto it = e->tol_of.find(t);
+        auto in = e->info.find(t);
+        if (it == e->tol_of.end() || in == e->info.end() || e->open.find(t) == e->open.end()) r = TW_E_BAD_PARAMETER;
+        else {
+            const int d = abs((int)in->second.first[0] - (int)in->second.first[1]);
+            rec = tw_change{in->second.w, e->device, it->second, it->second, d, d};
+        }
+    }
+    if (r == TW_OK) {
+        if (n_changes) *n_changes = 1;
+        if (changes && change_cap > 0) changes[0] = rec;
+    }
+    if (tracing()) trace(e, "tw_ticket_changes ticket=%lld cap=%d -> %s", (long long)t, change_cap, status_name(r));
     return r;
 }
 }

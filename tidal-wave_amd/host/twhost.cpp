@@ -36,6 +36,7 @@
 #pragma weak tw_submit_image_png_ignore
 #pragma weak tw_submit_image_jpeg_ignore
 #pragma weak tw_wait_regions
+#pragma weak tw_ticket_changes
 
 namespace twhost {
 
@@ -1071,6 +1072,10 @@ struct ConsumerRun {
     size_t hits_cap = 0;
     // hit regions (ConsumerShared::regions; 0: off): the gap the engine was given, and tw_wait_regions' scratch arrays
     int regions_gap = 0;
+    // residual (ConsumerShared::residual; 0: off): the tolerance the engine was given, Parameter::residualMin, and
+    // tw_ticket_changes' scratch array
+    int residual_tol = 0, residual_min = 0;
+    std::vector<tw_change> change_recs;
     std::vector<int> region_of;
     std::vector<tw_region> region_recs;
     // Resident expected images (Parameter::residentMB / TW_RESIDENT_MB; 0, the default: off, and no step below reaches the
@@ -1159,6 +1164,19 @@ struct ConsumerRun {
                 tw_engine_destroy(eng);
                 eng = nullptr;
                 regions_gap = 0;
+            }
+        }
+        // Residual (Parameter::residual): as the regions — the option once, here; then tw_ticket_changes before each collecting
+        // wait.  Off: neither call is made.  Asked-for changes are never silently dropped either.
+        residual_tol = eng && shared ? shared->residual : 0;
+        residual_min = shared ? shared->residualMin : 0;
+        if (residual_tol) {
+            const tw_status r = tw_ticket_changes ? tw_set_option(eng, TW_OPT_RESIDUAL, residual_tol) : TW_E_UNSUPPORTED;
+            if (r != TW_OK) {
+                eng_err = std::string("engine: residual: ") + tw_strerror(r);
+                tw_engine_destroy(eng);
+                eng = nullptr;
+                residual_tol = regions_gap = 0;
             }
         }
         prof = eng && shared && shared->profile;
@@ -1630,6 +1648,15 @@ struct ConsumerRun {
                 region_of.resize((size_t)cap);
                 region_recs.resize(TW_MAX_REGIONS);
             }
+            // the changes first: the call leaves the ticket to the wait, which answers a pair's own error as it always did
+            int nchg = 0;
+            tw_status rc = TW_OK;
+            std::string chg_err;
+            if (residual_tol) {
+                change_recs.resize((size_t)cap);
+                rc = tw_ticket_changes(eng, s.ticket, change_recs.data(), cap, &nchg);
+                if (rc != TW_OK) chg_err = engine_error(eng, rc);
+            }
             tw_status r = regions_gap ? tw_wait_regions(eng, s.ticket, v, cap, &n, region_of.data(), region_recs.data(),
                                                         TW_MAX_REGIONS, &nreg, &sec)
                                       : tw_wait(eng, s.ticket, v, cap, &n, &sec);
@@ -1647,10 +1674,16 @@ struct ConsumerRun {
                 s.err = cant_open(s.path(target));
             } else if (r != TW_OK) {
                 s.err = engine_error(eng, r);
+            } else if (rc != TW_OK) {
+                s.err = chg_err;
             } else {
                 out.vectors.resize((size_t)std::min(n, cap));
                 for (size_t i = 0; i < out.vectors.size(); i++) out.vectors[i] = {v[i].x, v[i].y, v[i].dx, v[i].dy};
-                out.status = out.vectors.empty() ? "OK" : "SUSPICIOUS";  // src/consumer.cpp:77
+                if (residual_tol) {
+                    out.hasChanges = true;
+                    out.changes.assign(change_recs.begin(), change_recs.begin() + std::max(0, std::min(nchg, cap)));
+                }
+                out.status = pair_status(out.vectors.size(), out.changes, residual_min);  // src/consumer.cpp:77
                 out.time = sec;
                 out.expect_image = s.req.expect_image;
                 out.target_image = s.req.target_image;
@@ -1761,6 +1794,8 @@ void Manager::start(const Parameter& p)
         if (const char* ev = getenv("TW_RESIDENT_MB")) res_mb = atoll(ev);
     shared_.residentBytes = res_mb > 0 ? res_mb << 20 : 0;
     shared_.regions = p.regions;
+    shared_.residual = p.residual;
+    shared_.residualMin = p.residualMin;
     shared_.stats.assign((size_t)n, ConsumerStats());
     for (int i = 0; i < n; i++) {
         consumers_.push_back(new Consumer(i, requestQueue_, responseQueue_, p.optParam, batch, dec, n, &shared_));

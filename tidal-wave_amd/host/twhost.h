@@ -45,8 +45,14 @@ struct Vector {
 };
 // A region of a pair's vectors (tw_region of include/twflow.h)
 using Region = tw_region;
+// A cell of a pair's span grid with a differing pixel (tw_change of include/twflow.h)
+using Change = tw_change;
 struct Response {
     std::vector<Vector> vectors;
+    // not in the reference (Parameter::residual > 0 only; empty otherwise): the cells with a pixel that differs by more than
+    // the tolerance, each with the number of such pixels the pair's flow does not explain
+    std::vector<Change> changes;
+    bool hasChanges = false;
     // not in the reference (Parameter::regions > 0 only; empty otherwise): the vectors grouped into regions on the device —
     // the kept records (at most TW_MAX_REGIONS), per vector the index of its region, and the pair's true number of regions
     std::vector<Region> regions;
@@ -91,7 +97,22 @@ struct Parameter {
     // not in the reference: group every pair's vectors into regions (the engine option TW_OPT_REGIONS) — 0: off, the calls a
     // consumer makes are exactly the ones it made before; 1 .. 8: the gap, in grid steps, that still joins two vectors
     int regions = 0;
+    // not in the reference: report the changes the flow does not explain (the engine option TW_OPT_RESIDUAL) — 0: off, the
+    // calls a consumer makes are exactly the ones it made before; 1 .. 254: the tolerance in gray levels.  residualMin
+    // (0: the status rule is untouched): a pair whose change records hold at least that many unexplained pixels in total is
+    // SUSPICIOUS even without a vector — a flat repaint moves nothing
+    int residual = 0;
+    int residualMin = 0;
 };
+// Response::status of an answered pair: the reference's rule (src/consumer.cpp:77), and Parameter::residualMin's
+inline const char* pair_status(size_t nvectors, const std::vector<Change>& changes, int residualMin)
+{
+    if (nvectors) return "SUSPICIOUS";
+    if (residualMin <= 0) return "OK";
+    long long unexplained = 0;
+    for (const Change& c : changes) unexplained += c.n_unexplained;
+    return unexplained >= residualMin ? "SUSPICIOUS" : "OK";
+}
 
 // What one consumer did, as seen by Manager::consumerStats() (a copy; the consumer thread owns the original).
 struct ConsumerStats {
@@ -242,6 +263,8 @@ struct ConsumerShared {
     bool profile = false;
     long long residentBytes = 0;  // the budget of a consumer's resident expected images (0: off)
     int regions = 0;              // Parameter::regions: a consumer sets TW_OPT_REGIONS once and collects with tw_wait_regions
+    int residual = 0;             // Parameter::residual: a consumer sets TW_OPT_RESIDUAL once and asks tw_ticket_changes before each collecting wait
+    int residualMin = 0;          // Parameter::residualMin
 };
 
 class Consumer {

@@ -60,6 +60,15 @@ class Region(C.Structure):
         return (self.x, self.y, self.width, self.height, self.count, self.peak_x, self.peak_y, self.peak_dx, self.peak_dy)
 
 
+class Change(C.Structure):
+    # tw_change (include/twflow.h): one span-grid cell with a differing pixel (TW_OPT_RESIDUAL / tw_ticket_changes), 24 bytes
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("n_diff", C.c_int), ("n_unexplained", C.c_int), ("max_diff", C.c_int),
+                ("max_unexplained", C.c_int)]
+
+    def as_tuple(self):
+        return (self.x, self.y, self.n_diff, self.n_unexplained, self.max_diff, self.max_unexplained)
+
+
 MAX_IGNORE = 32
 MAX_REGIONS = 256
 FLOW_PLANAR, FLOW_INTERLEAVED = 0, 1
@@ -80,6 +89,7 @@ _lib = None
 OPT_SCAN_FUSED_FINAL = 1
 OPT_POLYEXP_F32 = 2
 OPT_REGIONS = 3
+OPT_RESIDUAL = 4
 
 SYMBOLS = [
     "tw_default_params", "tw_abi_version", "tw_has_variants", "tw_device_count", "tw_device_pci_bus_id", "tw_engine_create", "tw_engine_destroy", "tw_strerror",
@@ -98,6 +108,7 @@ SYMBOLS = [
     "tw_stage_png_unfilter", "tw_stage_polyexp", "tw_stage_update_matrices", "tw_stage_flow_upsample_update", "tw_stage_blur_solve", "tw_stage_flow_iter",
     "tw_stage_flow_iter_grid", "tw_stage_span_scan",
     "tw_wait_regions", "tw_stage_hit_regions",
+    "tw_ticket_changes", "tw_stage_warp_residual",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
     "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time", "tw_debug_scan_plan", "tw_debug_level_plan",
@@ -280,6 +291,9 @@ def _bind(path):
     L.tw_wait_regions.argtypes = [vp, C.c_int64, C.POINTER(Vector), C.c_int, ip, ip, C.POINTER(Region), C.c_int, ip, fp]
     L.tw_stage_hit_regions.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, rp, ip, ip,
                                        C.POINTER(Region), ip]
+    L.tw_ticket_changes.argtypes = [vp, C.c_int64, C.POINTER(Change), C.c_int, ip]
+    L.tw_stage_warp_residual.argtypes = [vp, u8p, u8p, C.c_ssize_t, C.c_int, C.c_int, fp, C.c_int, C.c_int, ip, ip,
+                                         C.POINTER(Change)]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
     L.tw_level_chunk.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -899,6 +913,23 @@ class Engine:
         return ("OK" if n.value == 0 else "SUSPICIOUS", vec, [int(rof[i]) for i in range(m)],
                 [regs[i].as_tuple() for i in range(kept)], nreg.value)
 
+    def set_residual(self, tol):
+        """TW_OPT_RESIDUAL: 0 turns the residual off (the default), 1 .. 254 is the tolerance; batches opened from now on
+        take it."""
+        self.set_option(OPT_RESIDUAL, tol)
+
+    def changes(self, ticket, cap=None):
+        """tw_ticket_changes, before the wait that collects the ticket: (records, count) — the first min(count, cap) cells
+        with a differing pixel as Change.as_tuple() tuples (x, y, n_diff, n_unexplained, max_diff, max_unexplained) in
+        row-major order, and the pair's true count (cap None: a grid's worth, which cannot overflow)."""
+        tk, w, h, span, threshold = ticket
+        if cap is None:
+            cap = max(self._L.tw_grid_capacity(w, h, span), 1)
+        out = (Change * max(cap, 1))()
+        n = C.c_int()
+        self._check(self._L.tw_ticket_changes(self._h, tk, out, cap, C.byref(n)))
+        return [out[i].as_tuple() for i in range(max(0, min(n.value, cap)))], n.value
+
     def wait_count(self, ticket):
         """tw_wait without materialising the vectors (bench inner loop). Returns (n, seconds)."""
         tk = ticket[0]
@@ -1005,13 +1036,13 @@ class Engine:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_scan_plan(%d, %d, %d, %d) returned %d" % (w, h, span, npairs, n))
         return ScanPlan(("tw_span_scan", "tw_span_scan_seg")[v[0]], *v[1:7])
 
-    def level_plan(self, w, h, span, npairs, any_fout=False, any_init=False, prof_on=False):
+    def level_plan(self, w, h, span, npairs, any_fout=False, any_init=False, prof_on=False, residual=False):
         """What a batch of npairs pairs of w x h pixels at `span` launches for each pyramid level, from the function the
         enqueue itself executes (twflow_debug.h: tw_debug_level_plan): a LevelPlanView whose `parts` (a lane's share of the
         batch each) hold one LevelPlanRow per level, level 0 first."""
         cap = 8 + 2 * 61 * 11
         v = (C.c_int * cap)()
-        traits = (1 if any_fout else 0) | (2 if any_init else 0) | (4 if prof_on else 0)
+        traits = (1 if any_fout else 0) | (2 if any_init else 0) | (4 if prof_on else 0) | (16 if residual else 0)
         n = self._L.tw_debug_level_plan(self._h, w, h, int(span), npairs, traits, v, cap)
         if n < 8 or v[7] != 11 or n != 8 + v[6] * (v[2] + 1) * 11:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_level_plan(%d, %d, %d, %d) returned %d" % (w, h, span, npairs, n))
@@ -1156,6 +1187,34 @@ class Engine:
                                                int(bool(single_pair)), counts.ctypes.data_as(C.POINTER(C.c_int)),
                                                xy.ctypes.data_as(C.POINTER(C.c_int)), _f(dxy)))
         return counts, xy, dxy
+
+    def stage_warp_residual(self, expect, target, flow2, span, tol, stride=None):
+        """tw_warp_residual and tw_change_scan alone: expect / target (h, w) uint8 — with `stride` both are copied into
+        rows that far apart first — flow2 (2, h, w) float32.  (cells [G, 4] int32, n_changes, changes [G, 6] int32: x, y,
+        n_diff, n_unexplained, max_diff, max_unexplained); what the launches did not write holds 0xff bytes."""
+        expect = np.ascontiguousarray(expect, np.uint8)
+        target = np.ascontiguousarray(target, np.uint8)
+        flow2 = np.ascontiguousarray(flow2, np.float32)
+        h, w = expect.shape
+        assert target.shape == (h, w) and flow2.shape == (2, h, w)
+        if stride is None:
+            stride = w
+        else:
+            pe = np.full((h, stride), 0xA5, np.uint8)
+            pt = np.full((h, stride), 0x5A, np.uint8)
+            pe[:, :w] = expect
+            pt[:, :w] = target
+            expect, target = pe, pt
+        sp = max(int(span), 1)
+        G = (-(-h // sp)) * (-(-w // sp))
+        cells = np.zeros((G, 4), np.int32)
+        chg = np.zeros((G, 6), np.int32)
+        n = C.c_int(0)
+        u8p, ip = C.POINTER(C.c_uint8), C.POINTER(C.c_int)
+        self._check(self._L.tw_stage_warp_residual(self._h, expect.ctypes.data_as(u8p), target.ctypes.data_as(u8p), stride, w, h,
+                                                   _f(flow2), int(span), int(tol), cells.ctypes.data_as(ip), C.byref(n),
+                                                   chg.ctypes.data_as(C.POINTER(Change))))
+        return cells, n.value, chg
 
     def stage_hit_regions(self, fields, span, threshold, gap, ignore=None):
         """tw_hit_regions alone behind the gather and the ordered scan on `fields` (npairs, 2, h, w); ignore: per pair a

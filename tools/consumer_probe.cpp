@@ -8,6 +8,8 @@
 //     R <expected> <target>                  a pair of files
 //     M <w> <h> <first a> <first b>          an in-memory pair (gray, filled with 7 except for pixel 0)
 //     I <x,y,w,h[;x,y,w,h ...]>              ignore rectangles of the NEXT pair (Request::ignore)
+//     D <tol> <min>                          residual for the whole run (ConsumerShared::residual, ::residualMin); a response then
+//                                            ends in " changes <count>: [x,y diff=<n> unexplained=<n> max=<diff>,<unexplained>] ..."
 //     G <gap>                                hit regions for the whole run (ConsumerShared::regions); a response then ends in
 //                                            " regions <count>: [x,y,w,h n=<hits> peak=(x,y,dx,dy)] ... of: <index per vector>"
 #include <stdio.h>
@@ -42,6 +44,11 @@ int main(int argc, char** argv)
         const std::string op = argv[i];
         if (op == "G" && i + 1 < argc) {
             shared.regions = atoi(argv[++i]);
+            continue;
+        }
+        if (op == "D" && i + 2 < argc) {
+            shared.residual = atoi(argv[++i]);
+            shared.residualMin = atoi(argv[++i]);
             continue;
         }
         if (op == "I" && i + 1 < argc) {
@@ -100,6 +107,11 @@ int main(int argc, char** argv)
                            g.peak_dx, g.peak_dy);
                 printf(" of:");
                 for (int k : r.regionOf) printf(" %d", k);
+            }
+            if (r.hasChanges) {
+                printf(" changes %zu:", r.changes.size());
+                for (const Change& c : r.changes)
+                    printf(" [%d,%d diff=%d unexplained=%d max=%d,%d]", c.x, c.y, c.n_diff, c.n_unexplained, c.max_diff, c.max_unexplained);
             }
             printf("\n");
         }

@@ -156,6 +156,12 @@ def cases(f):
     return c
 
 
+def with_residual(case, tol, minimum=0):
+    """the case with the residual on for the whole run (the probe's D: ConsumerShared::residual, ::residualMin)"""
+    env, budget, script = case
+    return env, budget, ["D", tol, minimum] + list(script)
+
+
 def run_case(exe, case, threads, workdir, batch=4):
     """(responses as printed, the trace's text) of one case; every path under `workdir` or the tree reads <dir> / <root>"""
     env_more, budget, script = case
