@@ -113,9 +113,10 @@ int tw_debug_blur_plan(const tw_engine* e, int width, int height, int level, int
  * 0 for the any-size instantiation; 0 otherwise), out[2] the launch-count family (tw_debug_family; a tw_pyr_level_lds launch
  * is counted in TW_DF_PYR_LEVEL and in TW_DF_PYR_LEVEL_LDS, and this reports the latter), out[3] threads per workgroup,
  * out[4] output-tile columns, out[5] output-tile rows, out[6] grid x, out[7] grid y, out[8] dynamic LDS bytes, out[9] bytes per
- * staged source row (0: the kernel stages none), out[10] 1 when the kernel may load whole dwords of the source rows (`stride` a
- * multiple of 4 and the images the engine enqueued last 4-byte aligned, as a tw_stage_* call's are: engine state, so ask after
- * the launch; always 0 for tw_pyr_level, which takes no such argument); the level: out[11] width,
+ * staged source row (0: the kernel stages none), out[10] 1 when the kernel may load whole dwords of the source rows of
+ * images at 4-byte-aligned addresses — the answer is for such images, as a tw_stage_* call's and every staged host image are, so
+ * `stride` a multiple of 4 decides; a batch of device images at other addresses takes the byte path whatever this says, and no
+ * launch changes the answer; always 0 for tw_pyr_level, which takes no such argument); the level: out[11] width,
  * out[12] height, out[13] taps of its smoothing kernel, out[14] resize mode (0: same size, 1: INTER_LINEAR, 2: exact 2 x 2
  * area), out[15] xmax (output columns from xmax on take a single tap), out[16] the row-buffer height the kernel is given; the
  * size: out[17] 1 when levels 3 and 2 may come from one tw_pyr_23 launch (Plan::fused23), out[18] 1 when levels 1 and 0 may come

@@ -312,3 +312,25 @@ def test_the_cases_reach_every_value_of_the_plan(twflow, monkeypatch):
     assert _PLANS["24_scan_fused_final"].fused_final and not _PLANS["24_flow_destination"].grid_final
     assert not _PLANS["24_grid_final_0"].grid_final and _PLANS["24_default"].grid_final
     assert _PLANS["24_default"].parts[0][0].flow_iter and _PLANS["32_default"].parts[0][1].images == WITH_FINER
+
+
+def test_an_engine_reads_its_switches_once(twflow, monkeypatch):
+    """An engine's switches are read when it is created: its plans do not move when the environment does, and an engine
+    created afterwards takes the new values (no launches: the plan exports only)."""
+    for name in SWITCHES + ("TW_FI_MAXSEG", "TW_RAMP"):
+        monkeypatch.delenv(name, raising=False)
+
+    def plans(e):
+        return {"level": e.level_plan(1920, 1080, 10, 16), "flow_iter": e.flow_iter_plan(1920, 1080, 16),
+                "blur": e.blur_plan(1920, 1080, 2, 16), "pyr": e.pyr_plan(1920, 1080, 3)}
+
+    with twflow.Engine(0, twflow.default_params(), slots=16) as first:
+        before = plans(first)
+        for name, value in (("TW_MFREE", "0"), ("TW_PYR_GENERIC", "1"), ("TW_LANES", "2"), ("TW_FI_MAXSEG", "8"),
+                            ("TW_CHUNK_TILES", "1000")):
+            monkeypatch.setenv(name, value)
+        assert plans(first) == before
+        with twflow.Engine(0, twflow.default_params(), slots=16) as second:
+            after = plans(second)
+        assert after["level"] != before["level"] and after["pyr"] != before["pyr"], (before, after)
+        assert plans(first) == before

@@ -44,6 +44,33 @@ def same_bits(got, want, what):
             what, int(bad.sum()), got.size, at, float(got[at]), float(want[at])))
 
 
+# ---- tw_engine_create refuses the switches of kernels the default library does not carry -------------------------------------------
+VARIANT_SWITCHES = [("TW_POLY_VARIANT", "0"), ("TW_BLUR_VARIANT", "8"), ("TW_BLUR_PIPE", "3"), ("TW_BLUR_SMALL", "2"),
+                    ("TW_BLUR_SMALL_LEVELS", "-1,3"), ("TW_UPD_NY", "1")]
+
+
+@pytest.mark.parametrize("name,value", VARIANT_SWITCHES)
+def test_the_default_library_refuses_a_variants_switch(twflow, monkeypatch, name, value):
+    import ctypes as C
+    L = twflow.lib()
+    assert L.tw_has_variants() == 0
+    monkeypatch.setenv(name, value)
+    h = C.c_void_p(1)
+    assert L.tw_engine_create(0, None, 1, C.byref(h)) == twflow.TW_E_UNSUPPORTED
+    assert not h.value
+
+
+def test_the_default_library_admits_the_default_values_of_those_switches(twflow, monkeypatch):
+    import ctypes as C
+    L = twflow.lib()
+    assert L.tw_has_variants() == 0
+    monkeypatch.setenv("TW_UPD_NY", "2")
+    monkeypatch.setenv("TW_BLUR_SMALL", "1")
+    h = C.c_void_p()
+    assert L.tw_engine_create(0, None, 1, C.byref(h)) == twflow.TW_OK and h.value
+    L.tw_engine_destroy(h)
+
+
 # ---- part 1: tw_stage_polyexp over polyN x polySigma -----------------------------------------------------------------------
 STAGE_SIGMAS = (0.0, 1.1, 1.5, 3.0)
 TILE_ROWS = [(7, 239), (8, 240), (9, 241), (15, 479), (16, 480), (17, 481)]  # (h, w) around 8 rows x 240 columns

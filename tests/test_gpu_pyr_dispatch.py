@@ -198,5 +198,35 @@ def test_the_plan_refuses_what_it_cannot_answer(twflow, engines):
     assert L.tw_debug_pyr_plan(e._h, 64, 64, -1, 64, v, 23) == 0 and L.tw_debug_pyr_plan(e._h, 0, 64, 0, 64, v, 23) == 0
     assert L.tw_debug_pyr_plan(e._h, 64, 64, 1, 64, v, 5) == 5
     # an odd row stride forbids whole-dword loads whatever the image's address
-    e.stage_pyr_level(np.zeros((64, 64), np.uint8), 1)
     assert e.pyr_plan(64, 64, 1).aligned4 and not e.pyr_plan(64, 64, 1, stride=65).aligned4
+
+
+def test_the_plan_does_not_depend_on_what_ran_before(twflow, oracle):
+    """tw_debug_pyr_plan answers for 4-byte-aligned image addresses, before any launch and after a batch at odd addresses (whose
+    launches take the byte path); and that batch leaves nothing behind for the launches after it: a stage call and an aligned
+    pair equal the oracle, the pair launch for launch what a fresh engine does.  64 x 64: levels 0 and 1, both tw_pyr_k3."""
+    import ctypes as C
+    w = h = 64
+    base = np.random.default_rng(64).integers(0, 256, (h, w + 8), dtype=np.uint8)
+    a, b = np.ascontiguousarray(base[:, 8:]), np.ascontiguousarray(base[:, :w])  # noise and a copy shifted by 8 pixels
+    want = oracle.span_scan(*oracle.farneback(a, b), 10, 5.0)
+    assert len(want) > 0
+
+    def plans(e):
+        return [e.pyr_plan(w, h, k) for k in (0, 1)]
+
+    with twflow.Engine(0, twflow.default_params(), slots=1) as e, twflow.Engine(0, twflow.default_params(), slots=1) as fresh:
+        before = plans(e)
+        assert all(p.kernel == "tw_pyr_k3" and p.aligned4 for p in before), before
+        assert not any(e.pyr_plan(w, h, k, stride=65).aligned4 for k in (0, 1))
+        # a device pair at odd addresses
+        da, db = (e.upload(np.concatenate([np.zeros(1, np.uint8), g.ravel()])) for g in (a, b))
+        res = e.wait(e.submit_dev(C.c_void_p(da.value + 1), C.c_void_p(db.value + 1), w, h, w, 10, 5.0))
+        assert res["vector"] == want
+        assert plans(e) == before
+        same_bits(e.stage_pyr_level(a, 1), oracle.pyr_level(a, oracle.level_plan(w, h)[1]), "level 1 after a batch at odd addresses")
+        e.launch_counts(reset=True)
+        assert e.diff(a, b, 10, 5.0)["vector"] == want
+        assert fresh.diff(a, b, 10, 5.0)["vector"] == want
+        got, ref = e.launch_counts(), fresh.launch_counts()
+        assert got == ref and got.last_z == ref.last_z, (got, ref)

@@ -589,42 +589,25 @@ struct RoctxRange {
     }
 };
 
-}  // namespace
-
-struct tw_engine {
-    int device = 0;
+// What is fixed when an engine is created: the parameters, what follows from them and from the device, and the engine's
+// environment switches.  make_engine_config fills it, tw_engine holds it const, and the choice functions (choose_pyr,
+// choose_blur, choose_level_schedule, ...) take it in place of the engine: they cannot read what an earlier batch left behind.
+struct EngineConfig {
     tw_params p;
     int cap = 1;  // pairs per batch ("slots")
-    hipStream_t stream = nullptr;
-    Ctx ctx[NCTX];
-    int cur = 0;  // context accepting submissions
-    int64_t next_ticket = 1;
-    std::map<std::pair<int, int>, Plan*> plans;
-    unsigned long long plan_clock = 0;
+    int cu_count = 256;
     PolyCoef pc;
     WinCoef wc;
     int win_m = 15;
     int box = 0;           // flags without 256: box window (FarnebackUpdateFlow_Blur), scan kernels
-    double* Vd = nullptr;  // running column sums of the box window (5 double planes per pair of a chunk)
-    int copy_sync_skipped = 0;    // batches since the host last synchronised the copy stream (tw_wait)
-    long long copy_ops = 0;       // host images queued on the copy stream so far
-    uint8_t* h_bounce = nullptr;  // pinned bounce buffer of tw_submit_png8's pageable inputs
-    size_t h_bounce_cap = 0;
-    size_t Vd_cap = 0;
-    int img_aligned4 = 0;  // every image pointer and the row stride of the batch being enqueued are 4-byte aligned
     int lanes = 1;         // TW_LANES=2: the two halves of a batch run on two streams (memory-bound kernels of one
                            // half overlap the VALU-bound blur of the other); per-kernel hipEvent durations then
                            // include the co-running kernel
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int upd_ny = 2;        // TW_UPD_NY: pixels per lane of tw_update_matrices (1 or 2)
-    int scan_fused = 0;    // TW_OPT_SCAN_FUSED_FINAL
-    int poly_f32 = 0;      // TW_OPT_POLYEXP_F32 (measurement variant: float accumulators, not bit-exact)
     long long mfree_min_px = 0;  // TW_MFREE_MIN_PX: smallest level (pixels) that takes tw_flow_iter
     int mfree_min_w = 320;       // TW_MFREE_MIN_W: narrowest level (columns; strips are 160 outputs wide) that takes it
     int mfree = 1;         // TW_MFREE=0: every level runs update + blur launches again (A/B; tw_flow_iter, no M in HBM, is the
                            // default); 2: tw_flow_iter also for launches of a few workgroups (tests, tools/fuzz_parity.py)
-    int cu_count = 256;
     int pyr23_threads = 0;    // TW_PYR23_THREADS=256 / 512 / 1024: waves per tw_pyr_23 workgroup (A/B); 0 = 512, and 1024 for a
                               // single pair (432 workgroups: sixteen waves cover the staging latency, -0.5 us of 10.6)
     int blur_cm = 0;       // TW_BLUR_CM=1: tw_blur_solve4y (51-tap window) walks an XCD's tiles column-major (A/B)
@@ -632,26 +615,18 @@ struct tw_engine {
     int pyr_generic = 0;   // TW_PYR_GENERIC=1: always the generic pyramid kernel, 2: tw_pyr_level_lds for every level (A/B)
     int blur_variant = 4;  // 4: tw_blur_solve4 (default); 8: tw_blur_solve8 (packed f32) — TW_BLUR_VARIANT
     int pp_waves = 512;    // TW_PP_WAVES: below this many waves of 96x8 tiles a level takes the plane-parallel kernel
-    unsigned long long* dbg_stamps = nullptr;  // TW_DEBUG_STAMPS=1: phase stamps of tw_pyr_taps (diagnostic runs only)
+    int debug_stamps = 0;  // TW_DEBUG_STAMPS=1: tw_engine_create allocates tw_engine::dbg_stamps (diagnostic runs only)
     int blur_nomask = 0;   // TW_BLUR_NOMASK
     int blur_pipe = 0;     // TW_BLUR_PIPE: tiles a workgroup of tw_blur_solve4p walks (0: tw_blur_solve4 for every launch)
     int blur_small = -1;   // TW_BLUR_SMALL: force the small-grid tile choice of the 31-tap blur (-1: by grid size)
     int blur_small_lv[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // TW_BLUR_SMALL_LEVELS="a,b,c,d": the same per pyramid level
     int poly_variant = 1;  // 1: tw_polyexp_pk<N,8> (packed f32, default); 2: tw_polyexp_pk<N,16>; 0: tw_polyexp (scalar f32) — TW_POLY_VARIANT
-    std::string err;
-    // device workspace, shared by all batches (execution is ordered on one stream)
-    size_t ws_elems = 0;                 // capacity of I (floats); R = 5x, M = 5x each
-    float *I = nullptr, *R = nullptr, *M[2] = {nullptr, nullptr};
-    std::vector<float*> flow;            // per level, cap (levels>=1) or chunk0 (level 0) pairs x 2 planes
-    std::vector<size_t> flow_cap;
+    int poly_f32 = 0;      // TW_POLYEXP_F32: what EngineOptions::poly_f32 starts as (measurement runs)
     // single-pair latency schedule (BASELINE config 2): a batch of one pair runs the pyramid + polynomial expansion of
     // every level on stream2 (they depend only on the images) while the main stream walks the flow chain coarse to
     // fine; needs every level's I and R at once (TW_LATENCY_STREAMS=0: everything on one stream)
     int lat_streams = 1;
     long long lat_min_px = 100000;  // TW_LATENCY_MIN_PX
-    float *lat_I = nullptr, *lat_R = nullptr;
-    size_t lat_cap = 0;  // floats in lat_I (lat_R holds 5x)
-    std::vector<hipEvent_t> lat_ev;
     int lat_s2_max = 1000;  // TW_LAT_S2_LEVELS: finest..this level's image-only work goes to the second stream
     int ramp = 1;  // TW_RAMP=0: no cold-start ramp (A/B)
     long long chunk_tiles = 300000;      // TW_CHUNK_TILES: tiles a launch covers before a level is split (pairs_per_launch)
@@ -663,8 +638,143 @@ struct tw_engine {
     int fi_nt = 1024;   // TW_FI_NT=512 (variants library): tw_flow_iter as two 512-thread workgroups per CU on 64-output strips (A/B)
     int lat_fused = 1;  // TW_LAT_FUSED=0: the two-stream single-pair schedule of rounds 2-4 instead of the twin launches (A/B)
     int lat_graph = 0;  // TW_LAT_GRAPH=1: replay the single-pair schedule from a captured hipGraph (measured SLOWER on
-                        // ROCm 7.2: 0.55 ms vs 0.37 ms — profiles/r03_latency.md — so it is opt-in, kept for re-measuring)
+                        // ROCm 7.2: 0.55 ms vs 0.37 ms — profiles/r03_latency.md — so it is opt-in, kept for re-measuring);
+                        // in use while tw_engine::graph_capture_failed is unset (tw_engine::graph_replay)
+    int same_image = 1;    // TW_SAME_IMAGE=0: no tw_pair_same launch, both images of every pair processed (A/B)
+};
+
+// What tw_set_option changes between batches (its only writer besides the engine's constructor).
+struct EngineOptions {
+    int scan_fused = 0;    // TW_OPT_SCAN_FUSED_FINAL
+    int poly_f32 = 0;      // TW_OPT_POLYEXP_F32 (measurement variant: float accumulators, not bit-exact)
+    int regions_gap = 0;   // TW_OPT_REGIONS: the next batch's gap (0: off)
+    int residual_tol = 0;  // TW_OPT_RESIDUAL: the next batch's tolerance (0: off)
+};
+
+// the parameters an engine admits (tw_engine_create asks before it touches the device; make_engine_config asks for itself)
+tw_status check_params(const tw_params& p)
+{
+    if (!(p.pyrScale < 1) || !(p.pyrScale > 0)) return TW_E_UNSUPPORTED;  // CV_Assert(pyr_scale < 1)
+    if (p.polyN < 1 || p.polyN > 7) return TW_E_UNSUPPORTED;
+    if (p.winSize < 2 || p.winSize / 2 > 32) return TW_E_UNSUPPORTED;
+    if (p.pyrIterations < 0 || p.pyrLevels < 0) return TW_E_BAD_PARAMETER;
+    return TW_OK;
+}
+
+// THE reader of the engine's environment switches, and the place to add one: validates the parameters, reads every TW_*
+// engine switch once with its clamp, and refuses what the library as built cannot run (*why: the refusal's message).
+// No HIP call and no state: the same arguments and environment give the same value.
+tw_status make_engine_config(const tw_params& p, int slots, int cu_count, EngineConfig* out, std::string* why)
+{
+    if (const tw_status st = check_params(p)) return st;
+    EngineConfig& c = *out;
+    c.p = p;
+    c.cap = std::min(256, std::max(1, slots));
+    c.cu_count = cu_count;
+    polyexp_setup(p.polyN, p.polySigma, c.pc);
+    window_kernel(p.winSize, c.wc);
+    c.win_m = p.winSize / 2;
+    c.box = (p.flags & 256) ? 0 : 1;
+    if (const char* ev = getenv("TW_BLUR_VARIANT")) c.blur_variant = atoi(ev);
+    if (const char* ev = getenv("TW_PYR_GENERIC")) c.pyr_generic = atoi(ev);
+    if (const char* ev = getenv("TW_PYR_FUSED")) c.pyr_fused = atoi(ev) != 0;
+    if (const char* ev = getenv("TW_BLUR_CM")) c.blur_cm = atoi(ev);
+    if (const char* ev = getenv("TW_PYR23_THREADS")) c.pyr23_threads = atoi(ev) == 256 ? 256 : atoi(ev) == 1024 ? 1024 : atoi(ev) == 512 ? 512 : 0;
+    if (const char* ev = getenv("TW_MFREE")) c.mfree = atoi(ev);
+    if (const char* ev = getenv("TW_MFREE_MIN_PX")) c.mfree_min_px = atoll(ev);
+    if (const char* ev = getenv("TW_MFREE_MIN_W")) c.mfree_min_w = std::max(31, atoi(ev));
+    if (c.pyr_generic) c.pyr_fused = 0;
+    if (const char* ev = getenv("TW_POLY_VARIANT")) c.poly_variant = atoi(ev);
+    if (const char* ev = getenv("TW_BLUR_SMALL")) c.blur_small = atoi(ev);
+    if (const char* ev = getenv("TW_BLUR_SMALL_LEVELS")) {
+        int k = 0;
+        for (const char* q = ev; *q && k < 8; k++) {
+            c.blur_small_lv[k] = atoi(q);
+            while (*q && *q != ',') q++;
+            if (*q == ',') q++;
+        }
+    }
+    if (const char* ev = getenv("TW_PP_WAVES")) c.pp_waves = atoi(ev);
+    if (const char* ev = getenv("TW_BLUR_NOMASK")) c.blur_nomask = atoi(ev);
+    if (const char* ev = getenv("TW_BLUR_PIPE")) c.blur_pipe = atoi(ev);
+    if (const char* ev = getenv("TW_POLYEXP_F32")) c.poly_f32 = atoi(ev) == 2 ? 2 : (atoi(ev) ? 1 : 0);  // = TW_OPT_POLYEXP_F32 (measurement runs)
+    if (const char* ev = getenv("TW_DEBUG_STAMPS")) c.debug_stamps = atoi(ev) != 0;
+    if (const char* ev = getenv("TW_UPD_NY")) c.upd_ny = atoi(ev) == 1 ? 1 : 2;
+    if (const char* ev = getenv("TW_LANES")) c.lanes = std::min(2, std::max(1, atoi(ev)));
+    if (const char* ev = getenv("TW_LATENCY_STREAMS")) c.lat_streams = atoi(ev) ? 1 : 0;
+    if (const char* ev = getenv("TW_LATENCY_MIN_PX")) c.lat_min_px = atoll(ev);
+    if (const char* ev = getenv("TW_LAT_GRAPH")) c.lat_graph = atoi(ev) ? 1 : 0;
+    if (const char* ev = getenv("TW_LAT_FUSED")) c.lat_fused = atoi(ev) ? 1 : 0;
+#ifdef TW_VARIANTS
+    if (const char* ev = getenv("TW_FI_NT")) c.fi_nt = atoi(ev) == 512 ? 512 : 1024;
+    if (const char* ev = getenv("TW_FI_SKIP")) c.fi_skip = atoi(ev);
+#endif
+    if (const char* ev = getenv("TW_LAT_S2_LEVELS")) c.lat_s2_max = atoi(ev);
+    if (const char* ev = getenv("TW_RAMP")) c.ramp = atoi(ev) ? 1 : 0;
+    if (const char* ev = getenv("TW_CHUNK_TILES")) c.chunk_tiles = std::max(1, atoi(ev));
+    if (const char* ev = getenv("TW_CHUNK_PAIRS_LEVELS"))
+        for (int lv = 0; lv <= TW_MAX_LEVELS && ev; lv++) {
+            c.chunk_pairs_lv[lv] = std::max(0, atoi(ev));
+            ev = strchr(ev, ',');
+            if (ev) ev++;
+        }
+    if (const char* ev = getenv("TW_PYR_GEN_TH")) c.pyr_gen_th = atoi(ev);
+    c.lat_evtiming = getenv("TW_LAT_EVTIMING") != nullptr;
+    if (const char* ev = getenv("TW_SAME_IMAGE")) c.same_image = atoi(ev) ? 1 : 0;
+    if (const char* ev = getenv("TW_FI_MAXSEG")) c.fi_maxseg = std::min(64, std::max(1, atoi(ev)));
+    if (const char* ev = getenv("TW_FI_MINSTEPS")) c.fi_minsteps = std::max(2, atoi(ev));
+#ifndef TW_VARIANTS
+    // The measured-slower A/B kernels are compiled only into `make VARIANTS=1` builds (libtwflow_variants.so): a
+    // default build refuses their switches instead of silently running something else.
+    {
+        bool bad_lv = false;
+        for (int v : c.blur_small_lv) bad_lv = bad_lv || v == 2 || v == 3 || v == 5;
+        const bool bad = bad_lv || (c.blur_variant != 4) || (c.poly_variant != 1) || (c.blur_pipe != 0) || (c.blur_small == 2 || c.blur_small == 3 ||
+                         c.blur_small == 5) || c.upd_ny == 1;
+        if (bad) {
+            *why = "twflow: TW_BLUR_VARIANT / TW_POLY_VARIANT / TW_BLUR_PIPE / TW_BLUR_SMALL=2,3,5 / TW_UPD_NY=1 select kernels "
+                   "that are only in a VARIANTS=1 build (tidal-wave_amd/libtwflow_variants.so)\n";
+            return TW_E_UNSUPPORTED;
+        }
+    }
+#endif
+    return TW_OK;
+}
+
+}  // namespace
+
+struct tw_engine {
+    const EngineConfig cfg;  // fixed at creation (make_engine_config)
+    EngineOptions opt;       // tw_set_option
+    explicit tw_engine(const EngineConfig& c) : cfg(c) { opt.poly_f32 = c.poly_f32; }
+    int device = 0;
+    hipStream_t stream = nullptr;
+    Ctx ctx[NCTX];
+    int cur = 0;  // context accepting submissions
+    int64_t next_ticket = 1;
+    std::map<std::pair<int, int>, Plan*> plans;
+    unsigned long long plan_clock = 0;
+    double* Vd = nullptr;  // running column sums of the box window (5 double planes per pair of a chunk)
+    int copy_sync_skipped = 0;    // batches since the host last synchronised the copy stream (tw_wait)
+    long long copy_ops = 0;       // host images queued on the copy stream so far
+    uint8_t* h_bounce = nullptr;  // pinned bounce buffer of tw_submit_png8's pageable inputs
+    size_t h_bounce_cap = 0;
+    size_t Vd_cap = 0;
+    hipStream_t stream2 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    unsigned long long* dbg_stamps = nullptr;  // TW_DEBUG_STAMPS=1: phase stamps of tw_pyr_taps (diagnostic runs only)
+    std::string err;
+    // device workspace, shared by all batches (execution is ordered on one stream)
+    size_t ws_elems = 0;                 // capacity of I (floats); R = 5x, M = 5x each
+    float *I = nullptr, *R = nullptr, *M[2] = {nullptr, nullptr};
+    std::vector<float*> flow;            // per level, cap (levels>=1) or chunk0 (level 0) pairs x 2 planes
+    std::vector<size_t> flow_cap;
+    float *lat_I = nullptr, *lat_R = nullptr;  // the single-pair schedule's buffers: every level's I and R at once
+    size_t lat_cap = 0;  // floats in lat_I (lat_R holds 5x)
+    std::vector<hipEvent_t> lat_ev;
     std::map<GraphKey, hipGraphExec_t> lat_graphs;  // captured single-pair schedules (dropped whenever a buffer moves)
+    bool graph_capture_failed = false;  // this runtime could not capture the schedule: direct launches from then on
+    bool graph_replay() const { return cfg.lat_graph && !graph_capture_failed; }  // TW_LAT_GRAPH=1 still in use
     hipStream_t copy_stream = nullptr;  // host -> device image uploads, overlapped with the compute stream
     // tw_submit_*_flow: device -> host copies of the flow fields (created when a host destination is first seen, so that
     // an engine that never asks for one keeps its queue use), the copies queued there so far, batches since the host last
@@ -679,23 +789,20 @@ struct tw_engine {
     // identical pairs (tw_pair_same): 1 where a pair's second image is byte for byte its first — the batch schedule then
     // computes that pair's pyramid levels and polynomial expansions once, at the levels tw_flow_iter runs (it reads R0 as R1)
     unsigned* d_same = nullptr;        // [cap], of the batch enqueued last; all 0 until a batch schedule fills it
-    int same_image = 1;                // TW_SAME_IMAGE=0: no tw_pair_same launch, both images of every pair processed (A/B)
     int same_n = 0;                    // pairs of the batch enqueued last (tw_debug_same_flags)
     bool same_valid = false;           // ... and whether tw_pair_same ran for it
     float2* d_grid = nullptr;          // [cap][G] dense grid samples (dx,dy)
     size_t d_grid_cap = 0;
-    // hit regions: TW_OPT_REGIONS as tw_set_option left it (the next batch's gap; 0: off), the device copy of a batch's
+    // hit regions (the next batch's gap is opt.regions_gap): the device copy of a batch's
     // rectangle table (region_table_bytes(cap), on first use), tw_hit_regions' label planes for grids that do not fit LDS
     // ([cap][G], on first use), and whether the LDS kernel's dynamic size has been announced to the runtime
-    int regions_gap = 0;
     char* d_rgn = nullptr;
     int* d_lab = nullptr;
     size_t d_lab_cap = 0;
     bool rgn_attr = false;
-    // residual: TW_OPT_RESIDUAL as tw_set_option left it (the next batch's tolerance; 0: off), and tw_warp_residual's dense
+    // residual (the next batch's tolerance is opt.residual_tol): tw_warp_residual's dense
     // cell plane ([cap][G] cells of four ints, on first use) — the engine's, as d_grid: the batch's own tw_change_scan
     // consumes it before the next batch's launches write it
-    int residual_tol = 0;
     int4* d_cells = nullptr;
     size_t d_cells_cap = 0;
     // profiling: per kernel class, -2 = off, -1 = every level, k = level k only
@@ -754,7 +861,7 @@ size_t staged_image_bytes(int w, int h);
 
 // ---- the resident image store (tw_image_*) ---------------------------------------------------------------------------
 // Blocks are multiples of 256 bytes at multiples of 256 in a chunk (hipMalloc's own alignment is at least that), so a
-// resident image is aligned as a d_img slot is and img_aligned4 and every alignment-dependent kernel choice come out the same.
+// resident image is aligned as a d_img slot is and BatchEnqueue::aligned4 and every alignment-dependent kernel choice come out the same.
 constexpr size_t RES_CHUNK = (size_t)64 << 20;  // a chunk is at least this large
 
 void res_free(tw_engine* e, int chunk, size_t off, size_t bytes)
@@ -1067,7 +1174,7 @@ void free_plan(Plan* pl)
 
 // pairs one launch covers at a level of w x h pixels (level index k): enough 8-row x 240-column tiles of two images to cover
 // the 256 CUs many times over.  plan_geometry is its one caller: every reader takes LevelPlan::chunk.
-int pairs_per_launch(const tw_engine* e, int w, int h, int k)
+int pairs_per_launch(const EngineConfig& cfg, int w, int h, int k)
 {
     const long long tiles = (long long)((w + PE_TW - 1) / PE_TW) * ((h + PE_TH - 1) / PE_TH) * 2;
     // measured at 1080p: 4096 -> 16384 tiles per launch is +11 % pairs/s (fewer tails and gaps), 16384 -> 34000
@@ -1075,11 +1182,11 @@ int pairs_per_launch(const tw_engine* e, int w, int h, int k)
     // 128-pair batch +4 % (round 2): every kernel boundary costs a drain, a fill and an L2 write-back of the dirty
     // M planes, and 288 GB of HBM make the workspace of a whole batch (23 GB at 128 x 1080p) a non-issue.  So a
     // launch covers the whole batch unless that exceeds 300 000 tiles (TW_CHUNK_TILES).
-    long long c = (e->chunk_tiles + tiles - 1) / tiles;
+    long long c = (cfg.chunk_tiles + tiles - 1) / tiles;
     // TW_CHUNK_PAIRS_LEVELS: the round-4 Infinity-Cache experiment (does a level's chain run faster when a chunk's R / M
     // planes fit the 256 MB memory-side cache between its kernels?  profiles/r04_mall_chunks.md)
-    if (e->chunk_pairs_lv[k] > 0) c = e->chunk_pairs_lv[k];
-    return (int)std::min<long long>(std::max<long long>(c, 1), e->cap);
+    if (cfg.chunk_pairs_lv[k] > 0) c = cfg.chunk_pairs_lv[k];
+    return (int)std::min<long long>(std::max<long long>(c, 1), cfg.cap);
 }
 
 // The host tables of a plan on their way to the device: what plan_geometry computes and get_plan uploads.
@@ -1092,24 +1199,24 @@ struct PlanTables {
 // The pure part of a plan: everything that depends only on (parameters, engine switches, cap, w0, h0), with no HIP call
 // and no engine state written.  get_plan uploads `tabs` behind it; tw_level_chunk, tw_level_runs_flow_iter, the byte model
 // and tw_debug_level_plan read the geometry as it stands (device pointers null).  *why: the reason of a refusal.
-tw_status plan_geometry(const tw_engine* e, int w0, int h0, Plan* pl, PlanTables* tabs, const char** why)
+tw_status plan_geometry(const EngineConfig& cfg, int w0, int h0, Plan* pl, PlanTables* tabs, const char** why)
 {
     pl->w0 = w0;
     pl->h0 = h0;
-    pl->levels = plan_levels(w0, h0, e->p.pyrScale, std::min(std::max(e->p.pyrLevels, 0), TW_MAX_LEVELS));
+    pl->levels = plan_levels(w0, h0, cfg.p.pyrScale, std::min(std::max(cfg.p.pyrLevels, 0), TW_MAX_LEVELS));
     pl->lv.resize(pl->levels + 1);
     tabs->pyr.resize(pl->levels + 1);
     tabs->ups.resize(pl->levels + 1);
     for (int k = 0; k <= pl->levels; k++) {
         LevelPlan& L = pl->lv[k];
-        level_geometry(w0, h0, e->p.pyrScale, k, &L.w, &L.h, &L.sigma, &L.ksize, &L.scale);
+        level_geometry(w0, h0, cfg.p.pyrScale, k, &L.w, &L.h, &L.sigma, &L.ksize, &L.scale);
         if (L.w < 1 || L.h < 1 || L.ksize > PYR_MAXK - 1) {
             *why = "pyramid level degenerate or smoothing kernel too large";
             return TW_E_UNSUPPORTED;
         }
         L.ld = round_up(L.w, 32);
         L.ps = (long long)L.ld * L.h;
-        L.chunk = pairs_per_launch(e, L.w, L.h, k);
+        L.chunk = pairs_per_launch(cfg, L.w, L.h, k);
     }
     for (int k = 0; k <= pl->levels; k++) {
         LevelPlan& L = pl->lv[k];
@@ -1126,7 +1233,7 @@ tw_status plan_geometry(const tw_engine* e, int w0, int h0, Plan* pl, PlanTables
         // (TW_PYR_GEN_TH=8: the old tiles, A/B).
         {
             const size_t rb8 = (size_t)L.nrows_max * (t.mode == 0 ? PYR_TW : 2 * PYR_TW) * 4;
-            L.gen_th = e->pyr_gen_th >= 1 && e->pyr_gen_th <= PYR_TH ? e->pyr_gen_th : (rb8 > 32 * 1024 ? 4 : PYR_TH);
+            L.gen_th = cfg.pyr_gen_th >= 1 && cfg.pyr_gen_th <= PYR_TH ? cfg.pyr_gen_th : (rb8 > 32 * 1024 ? 4 : PYR_TH);
             L.gen_nrows_max = L.gen_th == PYR_TH ? L.nrows_max : pyr_nrows_max(t, L.h, h0, L.ksize / 2, L.gen_th);
         }
         const size_t lds = (size_t)(PYR_MAXK + (size_t)L.nrows_max * (t.mode == 0 ? PYR_TW : 2 * PYR_TW)) * 4;
@@ -1256,7 +1363,7 @@ tw_status get_plan(tw_engine* e, int w0, int h0, Plan** out)
     pl->last_use = ++e->plan_clock;
     PlanTables tabs;
     const char* why = "";
-    tw_status s = plan_geometry(e, w0, h0, pl, &tabs, &why);
+    tw_status s = plan_geometry(e->cfg, w0, h0, pl, &tabs, &why);
     if (s) e->err = why;
     else s = upload_plan_tables(e, pl, tabs);
     if (s) {
@@ -1273,18 +1380,18 @@ tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span)
 {
     size_t need = 0;
     for (const LevelPlan& L : pl->lv) need = std::max(need, (size_t)L.ps * 2 * L.chunk);
-    need *= e->lanes;  // one workspace per lane, carved from the same allocations
-    bool grow = need > e->ws_elems || e->flow.size() < pl->lv.size() || (e->box && need / 2 * 5 > e->Vd_cap);
+    need *= e->cfg.lanes;  // one workspace per lane, carved from the same allocations
+    bool grow = need > e->ws_elems || e->flow.size() < pl->lv.size() || (e->cfg.box && need / 2 * 5 > e->Vd_cap);
     if (!grow)
         for (size_t k = 0; k < pl->lv.size(); k++) {
-            const size_t fc = (size_t)pl->lv[k].ps * 2 * (k == 0 ? pl->lv[0].chunk * e->lanes : e->cap);
+            const size_t fc = (size_t)pl->lv[k].ps * 2 * (k == 0 ? pl->lv[0].chunk * e->cfg.lanes : e->cfg.cap);
             if (fc > e->flow_cap[k]) grow = true;
         }
     const size_t G = span > 0 ? (size_t)tw_grid_capacity(pl->w0, pl->h0, span) : 0;
-    if (G * e->cap > e->d_grid_cap) grow = true;
+    if (G * e->cfg.cap > e->d_grid_cap) grow = true;
     size_t need_lat = 0;
     for (const LevelPlan& L : pl->lv) need_lat += (size_t)L.ps * 2;
-    if (e->lat_streams && (need_lat > e->lat_cap || e->lat_ev.size() < pl->lv.size())) grow = true;
+    if (e->cfg.lat_streams && (need_lat > e->lat_cap || e->lat_ev.size() < pl->lv.size())) grow = true;
     if (!grow) return TW_OK;
     TW_HIP(e, hipStreamSynchronize(e->stream));
     TW_HIP(e, hipStreamSynchronize(e->stream2));
@@ -1302,7 +1409,7 @@ tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span)
         TW_HIP(e, hipMalloc((void**)&e->M[1], need / 2 * 5 * 4 + 256));
         e->ws_elems = need;
     }
-    if (e->lat_streams && need_lat > e->lat_cap) {
+    if (e->cfg.lat_streams && need_lat > e->lat_cap) {
         if (e->lat_I) (void)hipFree(e->lat_I);
         if (e->lat_R) (void)hipFree(e->lat_R);
         e->lat_I = e->lat_R = nullptr;
@@ -1311,21 +1418,21 @@ tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span)
         TW_HIP(e, hipMalloc((void**)&e->lat_R, need_lat * 5 * 4 + 256));
         e->lat_cap = need_lat;
     }
-    while (e->lat_streams && e->lat_ev.size() < pl->lv.size()) {
+    while (e->cfg.lat_streams && e->lat_ev.size() < pl->lv.size()) {
         hipEvent_t ev = nullptr;
-        TW_HIP(e, hipEventCreateWithFlags(&ev, e->lat_evtiming ? hipEventDefault : hipEventDisableTiming));
+        TW_HIP(e, hipEventCreateWithFlags(&ev, e->cfg.lat_evtiming ? hipEventDefault : hipEventDisableTiming));
         e->lat_ev.push_back(ev);
     }
-    if (e->box) TW_TRY(grow_device(e, e->Vd, e->Vd_cap, need / 2 * 5, need / 2 * 5 * sizeof(double) + 256));
+    if (e->cfg.box) TW_TRY(grow_device(e, e->Vd, e->Vd_cap, need / 2 * 5, need / 2 * 5 * sizeof(double) + 256));
     if (e->flow.size() < pl->lv.size()) {
         e->flow.resize(pl->lv.size(), nullptr);
         e->flow_cap.resize(pl->lv.size(), 0);
     }
     for (size_t k = 0; k < pl->lv.size(); k++) {
-        const size_t fc = (size_t)pl->lv[k].ps * 2 * (k == 0 ? pl->lv[0].chunk * e->lanes : e->cap);
+        const size_t fc = (size_t)pl->lv[k].ps * 2 * (k == 0 ? pl->lv[0].chunk * e->cfg.lanes : e->cfg.cap);
         TW_TRY(grow_device(e, e->flow[k], e->flow_cap[k], fc, fc * 4 + 256));
     }
-    return grow_device(e, e->d_grid, e->d_grid_cap, G * e->cap, G * e->cap * sizeof(float2) + 256);
+    return grow_device(e, e->d_grid, e->d_grid_cap, G * e->cfg.cap, G * e->cfg.cap * sizeof(float2) + 256);
 }
 
 // ---- profiling hooks -------------------------------------------------------------------------------
@@ -1399,7 +1506,7 @@ void launch_upd_kernel(tw_engine* e, hipStream_t st, int w, int h, int npairs, c
                        bool* side_used = nullptr)
 {
 #ifdef TW_VARIANTS
-    if (e->upd_ny == 1) {
+    if (e->cfg.upd_ny == 1) {
         TW_LAUNCH(e, TW_DF_UPDATE_MATRICES, (tw_update_matrices<UP, 1>), dim3((w + 63) / 64, (h + 3) / 4, npairs), dim3(256), 0, st, a);
         return;
     }
@@ -1433,14 +1540,15 @@ struct PyrChoice {
     int aligned4;   // whole-dword loads of the source rows allowed
     int nrows_max;  // row-buffer height the kernel is given
 };
-PyrChoice choose_pyr(const tw_engine* e, const Plan* pl, int k, long long stride)
+// img_al4: every image address of the launch is 4-byte aligned (the row stride decides with it)
+PyrChoice choose_pyr(const EngineConfig& cfg, const Plan* pl, int k, long long stride, int img_al4)
 {
     const LevelPlan& L = pl->lv[k];
     const int P = (L.mode == 0) ? PYR_TW : 2 * PYR_TW;
-    const int aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
+    const int aligned4 = (stride % 4 == 0) ? img_al4 : 0;
     PyrChoice c{PYR_KN_LEVEL, 0, TW_DF_PYR_LEVEL, 256, PYR_TW, PYR_TH, (unsigned)((L.w + PYR_TW - 1) / PYR_TW),
                 (unsigned)((L.h + PYR_TH - 1) / PYR_TH), 0, 0, aligned4, L.nrows_max};
-    if (L.ksize == 3 && (L.mode == 0 || L.mode == 2) && pl->w0 >= 16 && !e->pyr_generic) {
+    if (L.ksize == 3 && (L.mode == 0 || L.mode == 2) && pl->w0 >= 16 && !cfg.pyr_generic) {
         // register-only fast path (3 taps, same-size or exact 2x2 area resize)
         c.kernel = PYR_KN_K3;
         c.targ = L.mode;
@@ -1451,7 +1559,7 @@ PyrChoice choose_pyr(const tw_engine* e, const Plan* pl, int k, long long stride
         c.gy = (L.h + c.th - 1) / c.th;
         return c;
     }
-    if (L.pitch_b > 0 && L.mode != 0 && L.ksize >= 7 && e->pyr_generic == 0) {
+    if (L.pitch_b > 0 && L.mode != 0 && L.ksize >= 7 && cfg.pyr_generic == 0) {
         // coarse levels: shared-window row filter (tw_pyr_taps)
         const int pd = (L.pitch_b / 4 + 1) | 1;
         c.kernel = PYR_KN_TAPS;
@@ -1461,7 +1569,7 @@ PyrChoice choose_pyr(const tw_engine* e, const Plan* pl, int k, long long stride
         c.pitch = pd * 4;
         return c;
     }
-    if (L.pitch_b > 0 && e->pyr_generic != 1) {
+    if (L.pitch_b > 0 && cfg.pyr_generic != 1) {
         c.kernel = PYR_KN_LEVEL_LDS;
         c.lds = (size_t)(PYR_MAXK + (size_t)L.nrows_max * P) * 4 + (size_t)L.nrows_max * L.pitch_b;
         c.pitch = L.pitch_b;
@@ -1475,15 +1583,15 @@ PyrChoice choose_pyr(const tw_engine* e, const Plan* pl, int k, long long stride
     return c;
 }
 // threads of a tw_pyr_23 workgroup: TW_PYR23_THREADS, or 1024 for a launch of one pair's images and 512 for more
-int pyr23_threads(const tw_engine* e, int nimg) { return e->pyr23_threads ? e->pyr23_threads : nimg <= 2 ? 1024 : 512; }
+int pyr23_threads(const EngineConfig& cfg, int nimg) { return cfg.pyr23_threads ? cfg.pyr23_threads : nimg <= 2 ? 1024 : 512; }
 
 // same: tw_pair_same's flags of the launch's pairs where the level's only reader of the second images honours them (null:
 // every image) — the 3-tap register kernel skips those images, the other kernels compute them as ever
-void launch_pyr(tw_engine* e, hipStream_t st, const Plan* pl, int k, const uint8_t* const* d_srcs, long long stride,
+void launch_pyr(tw_engine* e, hipStream_t st, const Plan* pl, int k, const uint8_t* const* d_srcs, long long stride, int img_al4,
                 float* I, int nimg, const unsigned* same = nullptr)
 {
     const LevelPlan& L = pl->lv[k];
-    const PyrChoice c = choose_pyr(e, pl, k, stride);
+    const PyrChoice c = choose_pyr(e->cfg, pl, k, stride, img_al4);
     PyrArgs a;
     a.srcs = d_srcs;
     a.dst = I;
@@ -1559,7 +1667,7 @@ void launch_pyr(tw_engine* e, hipStream_t st, const Plan* pl, int k, const uint8
 
 // levels 3 and 2 of `nimg` images from one read of each image (tw_pyr_23; pl->fused23): I3 / I2 = the level images,
 // z-th at + z * ps of the level
-void launch_pyr23(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* const* d_srcs, long long stride, float* I3,
+void launch_pyr23(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* const* d_srcs, long long stride, int img_al4, float* I3,
                   float* I2, int nimg)
 {
     const LevelPlan &L3 = pl->lv[3], &L2 = pl->lv[2];
@@ -1578,12 +1686,12 @@ void launch_pyr23(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* c
     a.w2 = L2.w;
     a.h2 = L2.h;
     a.ld2 = L2.ld;
-    a.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
+    a.aligned4 = (stride % 4 == 0) ? img_al4 : 0;
     memcpy(a.k19, pl->k19, sizeof(a.k19));
     memcpy(a.k9, pl->k9, sizeof(a.k9));
     ProfScope ps(e, st, TW_K_PYR, 3);
     const dim3 grid((L3.w + P23_T3W - 1) / P23_T3W, (L3.h + P23_T3H - 1) / P23_T3H, nimg);
-    const int nt = pyr23_threads(e, nimg);
+    const int nt = pyr23_threads(e->cfg, nimg);
     if (nt == 256) TW_LAUNCH(e, TW_DF_PYR_23, tw_pyr_23<256>, grid, dim3(256), 0, st, a);
     else if (nt == 1024) TW_LAUNCH(e, TW_DF_PYR_23, tw_pyr_23<1024>, grid, dim3(1024), 0, st, a);
     else TW_LAUNCH(e, TW_DF_PYR_23, tw_pyr_23<512>, grid, dim3(512), 0, st, a);
@@ -1601,13 +1709,13 @@ tw_status launch_polyexp(tw_engine* e, hipStream_t st, int w, int h, int ld, lon
     a.h = h;
     a.ld = ld;
     a.ps = ps;
-    a.c = e->pc;
+    a.c = e->cfg.pc;
     dim3 grid((w + PE_TW - 1) / PE_TW, (h + PE_TH - 1) / PE_TH, nimg);
     ProfScope pscope(e, st, TW_K_POLYEXP, level);
 #ifdef TW_VARIANTS
-    if (e->poly_variant == 0) {
+    if (e->cfg.poly_variant == 0) {
         // scalar-f32 kernel (A/B: TW_POLY_VARIANT=0)
-        switch (e->p.polyN) {
+        switch (e->cfg.p.polyN) {
             case 1: TW_LAUNCH(e, TW_DF_POLYEXP, tw_polyexp<1>, grid, dim3(256), 0, st, a); break;
             case 2: TW_LAUNCH(e, TW_DF_POLYEXP, tw_polyexp<2>, grid, dim3(256), 0, st, a); break;
             case 3: TW_LAUNCH(e, TW_DF_POLYEXP, tw_polyexp<3>, grid, dim3(256), 0, st, a); break;
@@ -1620,12 +1728,12 @@ tw_status launch_polyexp(tw_engine* e, hipStream_t st, int w, int h, int ld, lon
         return TW_OK;
     }
 #endif
-    if (e->poly_f32) {
+    if (e->opt.poly_f32) {
         // measurement variant (TW_OPT_POLYEXP_F32): float horizontal accumulators — NOT bit-exact, never the default
-        switch (e->p.polyN) {
+        switch (e->cfg.p.polyN) {
             case 5: TW_LAUNCH(e, TW_DF_POLYEXP, (tw_polyexp_pk<5, 8, 1>), grid, dim3(256), 0, st, a); break;
             case 7:
-                if (e->poly_f32 == 2) TW_LAUNCH(e, TW_DF_POLYEXP, (tw_polyexp_pk<7, 8, 2>), grid, dim3(256), 0, st, a);
+                if (e->opt.poly_f32 == 2) TW_LAUNCH(e, TW_DF_POLYEXP, (tw_polyexp_pk<7, 8, 2>), grid, dim3(256), 0, st, a);
                 else TW_LAUNCH(e, TW_DF_POLYEXP, (tw_polyexp_pk<7, 8, 1>), grid, dim3(256), 0, st, a);
                 break;
             default: e->err = "TW_OPT_POLYEXP_F32 needs polyN 5 or 7"; return TW_E_UNSUPPORTED;
@@ -1635,7 +1743,7 @@ tw_status launch_polyexp(tw_engine* e, hipStream_t st, int w, int h, int ld, lon
     // packed-f32 kernel, 240 x 8 tiles; TW_POLY_VARIANT=2 selects 240 x 16 tiles (960 two-by-two items = 15 full
     // waves of the horizontal pass, 30-row window per 16 output rows, 48 KB LDS: measured equal within the noise)
 #ifdef TW_VARIANTS
-    const bool t16 = e->poly_variant == 2;
+    const bool t16 = e->cfg.poly_variant == 2;
     if (t16) grid.y = (h + 15) / 16;
 #define TW_PK_CASE(n)                                                                        \
     case n:                                                                                  \
@@ -1646,13 +1754,13 @@ tw_status launch_polyexp(tw_engine* e, hipStream_t st, int w, int h, int ld, lon
 #define TW_PK_CASE(n)                                                                        \
     case n: TW_LAUNCH(e, TW_DF_POLYEXP, (tw_polyexp_pk<n, 8, 0>), grid, dim3(256), 0, st, a); break;
 #endif
-    if (side && side_used && side->kind == 2 && e->p.polyN == 7 && e->poly_variant == 1) {
+    if (side && side_used && side->kind == 2 && e->cfg.p.polyN == 7 && e->cfg.poly_variant == 1) {
         const TwinGrid t = make_twin(grid, *side);
         TW_LAUNCH(e, TW_DF_TWIN, tw_twin_poly_k3f, dim3(t.nA8 + side->n()), dim3(256), 0, st, a, side->ka, t);
         *side_used = true;
         return TW_OK;
     }
-    switch (e->p.polyN) {
+    switch (e->cfg.p.polyN) {
         TW_PK_CASE(1) TW_PK_CASE(2) TW_PK_CASE(3) TW_PK_CASE(4) TW_PK_CASE(5) TW_PK_CASE(6) TW_PK_CASE(7)
         default: e->err = "polyN must be 1..7"; return TW_E_UNSUPPORTED;
     }
@@ -1666,7 +1774,7 @@ bool pyr01_fusable(const Plan* pl)
     return pl->levels >= 1 && pl->lv[0].ksize == 3 && pl->lv[1].ksize == 3 && pl->lv[0].mode == 0 && pl->lv[1].mode == 2 &&
            pl->w0 == 2 * pl->lv[1].w && pl->h0 == 2 * pl->lv[1].h && pl->w0 >= 16;
 }
-void launch_pyr01(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* const* d_srcs, long long stride, float* I1,
+void launch_pyr01(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* const* d_srcs, long long stride, int img_al4, float* I1,
                   float* I0, int nimg, const unsigned* same = nullptr)
 {
     const LevelPlan &L0 = pl->lv[0], &L1 = pl->lv[1];
@@ -1687,7 +1795,7 @@ void launch_pyr01(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* c
     a.a1 = L0.h_kern[0];
     a.b0 = L1.h_kern[1];
     a.b1 = L1.h_kern[0];
-    a.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
+    a.aligned4 = (stride % 4 == 0) ? img_al4 : 0;
     a.same = same;
     ProfScope ps(e, st, TW_K_PYR, 1);
     TW_LAUNCH(e, TW_DF_PYR_K3F, tw_pyr_k3f, dim3((L1.w + 255) / 256, (L1.h + 3) / 4, nimg), dim3(256), 0, st, a);
@@ -1696,33 +1804,33 @@ void launch_pyr01(tw_engine* e, hipStream_t st, const Plan* pl, const uint8_t* c
 // One whole iteration of the flow update without M in HBM (tw_flow_iter; round 5): flow_out = solve(window average of
 // FarnebackUpdateMatrices(R0, R1, flow_in)).  flow_in: a flow buffer, or (prev != nullptr) the bilinear upsample x
 // 1/pyr_scale of the coarser level's flow computed in place of the load, or zero (both null: the coarsest level).
-bool flow_iter_eligible(const tw_engine* e, int w, int h)
+bool flow_iter_eligible(const EngineConfig& cfg, int w, int h)
 {
-    return e->win_m == 15 && !e->box && w >= e->mfree_min_w && h >= 4 * FI_TH;
+    return cfg.win_m == 15 && !cfg.box && w >= cfg.mfree_min_w && h >= 4 * FI_TH;
 }
 // The predicate of choose_level_schedule, its one caller (the byte model reads the choice): does a launch of nc
 // pairs at a level of w x h pixels run tw_flow_iter?  lat: the batch takes the single-pair schedule; grid_only: the level's
 // last iteration is evaluated at the span-grid points only (TW_OPT_SCAN_FUSED_FINAL, level 0).  A launch of fewer workgroups
 // than ~3/4 of the CUs — one or two 1080p pairs — leaves the chip to the 224 x 8 tiles of tw_blur_solve4, of which a single
 // pair already makes 1 215 (TW_MFREE=2 lifts that gate: tests, tools/fuzz_parity.py).
-bool level_runs_flow_iter(const tw_engine* e, int w, int h, int nc, bool lat, bool grid_only)
+bool level_runs_flow_iter(const EngineConfig& cfg, int w, int h, int nc, bool lat, bool grid_only)
 {
-    const int it = e->p.pyrIterations;
-    const int fi_out = (e->fi_nt == 512 ? FI_SC_512 : FI_SC) - 30;
+    const int it = cfg.p.pyrIterations;
+    const int fi_out = (cfg.fi_nt == 512 ? FI_SC_512 : FI_SC) - 30;
     const long long fi_wgs = (long long)((w + fi_out - 1) / fi_out) * std::min(4, std::max(1, h / (16 * FI_TH))) * nc;
-    return e->mfree && !lat && it > (grid_only ? 1 : 0) && flow_iter_eligible(e, w, h) &&
-           (fi_wgs * 4 >= (long long)e->cu_count * 3 || e->mfree == 2) &&
-           (e->mfree_min_px <= 0 || (long long)w * h >= e->mfree_min_px);
+    return cfg.mfree && !lat && it > (grid_only ? 1 : 0) && flow_iter_eligible(cfg, w, h) &&
+           (fi_wgs * 4 >= (long long)cfg.cu_count * 3 || cfg.mfree == 2) &&
+           (cfg.mfree_min_px <= 0 || (long long)w * h >= cfg.mfree_min_px);
 }
 // does a batch of n pairs of w0 x h0 pixels take the single-pair schedule (its image-only work beside the flow chain)?
-bool single_pair_schedule(const tw_engine* e, int n, int w0, int h0, int levels)
+bool single_pair_schedule(const EngineConfig& cfg, int n, int w0, int h0, int levels)
 {
-    return n == 1 && e->lat_streams && levels >= 1 && (long long)w0 * h0 >= e->lat_min_px;
+    return n == 1 && cfg.lat_streams && levels >= 1 && (long long)w0 * h0 >= cfg.lat_min_px;
 }
 // the last level-0 iteration at the span-grid points only?
-bool scan_fused_level0(const tw_engine* e, int span)
+bool scan_fused_level0(const EngineConfig& cfg, int scan_fused, int span)
 {
-    return e->p.pyrIterations > 0 && e->scan_fused && span == 10 && e->win_m == 15 && !e->box;
+    return cfg.p.pyrIterations > 0 && scan_fused && span == 10 && cfg.win_m == 15 && !cfg.box;
 }
 // pairs per launch when n pairs are split into balanced launches of at most `chunk` (64 pairs with a 63-pair chunk are 32 + 32)
 int balanced_launch_pairs(int n, int chunk)
@@ -1775,19 +1883,19 @@ UpdArgs upd_args(const float* R, float* flow, float* M, int w, int h, int ld, lo
 struct FlowIterPlan {
     int strips, segments, nt, nt_last;  // nt: steps of FI_TH rows per segment; nt_last: steps of the last segment
 };
-FlowIterPlan flow_iter_plan(const tw_engine* e, int w, int h, int npairs)
+FlowIterPlan flow_iter_plan(const EngineConfig& cfg, int w, int h, int npairs)
 {
-    const int OUT = (e->fi_nt == 512 ? FI_SC_512 : FI_SC) - 30;
-    const int slots = e->cu_count * (e->fi_nt == 512 ? 2 : 1);  // workgroups resident at once
+    const int OUT = (cfg.fi_nt == 512 ? FI_SC_512 : FI_SC) - 30;
+    const int slots = cfg.cu_count * (cfg.fi_nt == 512 ? 2 : 1);  // workgroups resident at once
     const int nstrips = (w + OUT - 1) / OUT, nsteps = (h + FI_TH - 1) / FI_TH;
     // Row segments per strip: one 1024-thread workgroup per CU is resident, so the launch runs in rounds of (CU count)
     // workgroups; a segment pays NCH = 7 chunks of M for its window's warm-up.  Take the split (1 .. 4) with the least
     // (rounds x (steps + warm-up)) — 128 pairs x 12 strips of 1080p: 2 segments = 12.0 rounds of 108 + 7 steps.
     int best_seg = 1;
     double best_cost = 1e300;
-    for (int sg = 1; sg <= e->fi_maxseg; sg++) {
+    for (int sg = 1; sg <= cfg.fi_maxseg; sg++) {
         const int nt = (nsteps + sg - 1) / sg;
-        if (sg > 1 && nt < e->fi_minsteps) break;
+        if (sg > 1 && nt < cfg.fi_minsteps) break;
         const long long wgs = (long long)nstrips * sg * npairs;
         const long long rounds = (wgs + slots - 1) / slots;
         const double cost = (double)rounds * (nt + 7 * 0.25);  // a warm-up chunk is a quarter of a step (phase C only)
@@ -1826,12 +1934,12 @@ void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long l
     a.fps_in = fps_in;
     a.fps_out = fps_out;
     a.zero_flow = (!flow_in && !ups) ? 1 : 0;
-    a.c = e->wc;
+    a.c = e->cfg.wc;
 #ifdef TW_VARIANTS
-    a.dbg_skip = e->fi_skip;                     // TW_FI_SKIP (timing experiments; read once in tw_engine_create)
+    a.dbg_skip = e->cfg.fi_skip;                     // TW_FI_SKIP (timing experiments)
     a.dbg = (unsigned long long*)e->dbg_stamps;  // TW_DEBUG_STAMPS=1
 #endif
-    const FlowIterPlan fp = flow_iter_plan(e, w, h, npairs);
+    const FlowIterPlan fp = flow_iter_plan(e->cfg, w, h, npairs);
     a.nt = fp.nt;
     const dim3 grid(fp.strips, fp.segments, npairs);
     ProfScope pscope(e, st, TW_K_BLUR_SOLVE, level);
@@ -1849,7 +1957,7 @@ void launch_flow_iter(tw_engine* e, hipStream_t st, int w, int h, int ld, long l
         return;
     }
 #ifdef TW_VARIANTS
-    if (e->fi_nt == 512) {  // measured 23 % slower (profiles/r05_m_free.md): variants library only
+    if (e->cfg.fi_nt == 512) {  // measured 23 % slower (profiles/r05_m_free.md): variants library only
         if (ups) TW_LAUNCH(e, TW_DF_FLOW_ITER_UPS, (tw_flow_iter<15, 1, 512>), grid, dim3(512), 0, st, a);
         else if (a.zero_flow) TW_LAUNCH(e, TW_DF_FLOW_ITER_ZERO, (tw_flow_iter<15, 2, 512>), grid, dim3(512), 0, st, a);
         else TW_LAUNCH(e, TW_DF_FLOW_ITER, (tw_flow_iter<15, 0, 512>), grid, dim3(512), 0, st, a);
@@ -1963,42 +2071,42 @@ struct BlurChoice {
                           // 4: plane-parallel 32x8 (320 threads), 5: plane-parallel 96x8 (640 threads)
     bool forced;          // ... set by TW_BLUR_SMALL_LEVELS / TW_BLUR_SMALL, not by the grid's size
 };
-BlurChoice choose_blur(const tw_engine* e, int w, int h, int npairs, int level, bool update, bool quads)
+BlurChoice choose_blur(const EngineConfig& cfg, int w, int h, int npairs, int level, bool update, bool quads)
 {
     BlurChoice c{&kGenericWindow, 0, dim3(), 0, 0, false};
-    if (e->box) {
+    if (cfg.box) {
         c.k = &kBoxWindow;
         c.grid = dim3((w + 63) / 64, 5, npairs);
         return c;
     }
     const bool wide = w > 480;
-    if (e->win_m == 15) {
+    if (cfg.win_m == 15) {
         // Small grids (a single pair, the coarse levels): a level that would launch fewer than two workgroups per
         // CU takes smaller tiles, so that more CUs share it and each workgroup's serial V -> H -> S chain is shorter
         // (BASELINE config 2, single-pair latency).  Batched launches always have enough tiles and keep the big ones.
         auto nwg = [&](int tw, int th) { return (long long)((w + tw - 1) / tw) * ((h + th - 1) / th) * npairs; };
         c.forced = true;
-        if (level >= 0 && level < 8 && e->blur_small_lv[level] >= 0) c.small = e->blur_small_lv[level];
-        else if (e->blur_small >= 0) c.small = e->blur_small;
+        if (level >= 0 && level < 8 && cfg.blur_small_lv[level] >= 0) c.small = cfg.blur_small_lv[level];
+        else if (cfg.blur_small >= 0) c.small = cfg.blur_small;
         else {
             c.forced = false;
             if (wide && nwg(224, 8) >= 1024) c.small = 0;  // four 256-thread workgroups per CU: throughput regime
-            else if (nwg(96, 8) * 2 >= e->pp_waves) c.small = wide ? 1 : 0;  // enough 2-wave workgroups to keep every SIMD busy
+            else if (nwg(96, 8) * 2 >= cfg.pp_waves) c.small = wide ? 1 : 0;  // enough 2-wave workgroups to keep every SIMD busy
             else c.small = 4;  // otherwise many small plane-parallel workgroups (5 waves per 32x8 pixels)
         }
         if (c.small > 5) c.small = 4;
     }
     for (int i = 0; i < kBlurKernelRows; i++) {
         const BlurKernel& r = kBlurKernels[(kProductBlurRows + i) % kBlurKernelRows];  // the variants rows first
-        if (r.m == e->win_m && (r.wide == ANY || r.wide == (int)wide) && (r.small == ANY || r.small == c.small) && (!r.quads || quads) &&
-            (!r.variant || r.variant == e->blur_variant) && (!r.pipe || (update && r.pipe == e->blur_pipe)) && w >= r.min_w) {
+        if (r.m == cfg.win_m && (r.wide == ANY || r.wide == (int)wide) && (r.small == ANY || r.small == c.small) && (!r.quads || quads) &&
+            (!r.variant || r.variant == cfg.blur_variant) && (!r.pipe || (update && r.pipe == cfg.blur_pipe)) && w >= r.min_w) {
             c.k = &r;
             break;
         }
     }
     if (c.k->shift) c.xsh = tile_shift(w, c.k->tw);
     c.grid = dim3((w + c.xsh + c.k->tw - 1) / c.k->tw, (h + c.k->th - 1) / c.k->th, npairs);
-    if (c.k == &kGenericWindow) c.lds = (size_t)5 * BS_TH * (64 + 2 * e->win_m) * 4;
+    if (c.k == &kGenericWindow) c.lds = (size_t)5 * BS_TH * (64 + 2 * cfg.win_m) * 4;
     return c;
 }
 
@@ -2030,7 +2138,7 @@ struct BlurLaunch {
 void launch_box_window(tw_engine* e, hipStream_t st, const BlurLaunch& in)
 {
     double* V = in.Vbox ? in.Vbox : e->Vd;  // TW_LANES=2: each lane (stream) has its own column sums
-    const BoxArgs b{in.Min, V, in.flow, in.w, in.h, in.ld, in.ps, in.ps, e->win_m, 1. / ((double)e->p.winSize * e->p.winSize)};
+    const BoxArgs b{in.Min, V, in.flow, in.w, in.h, in.ld, in.ps, in.ps, e->cfg.win_m, 1. / ((double)e->cfg.p.winSize * e->cfg.p.winSize)};
     {
         ProfScope pscope(e, st, TW_K_BLUR_SOLVE, in.level);
         TW_LAUNCH(e, TW_DF_BOX, tw_box_vscan, dim3((in.w + 63) / 64, 5, in.npairs), dim3(64), 0, st, b);
@@ -2056,14 +2164,14 @@ void launch_blur(tw_engine* e, hipStream_t st, const BlurLaunch& in)
     a.fps = in.ps;
     a.update = in.update;
     a.store_flow = in.store_flow;
-    a.m = e->win_m;
-    a.nomask = e->blur_nomask;
-    a.cm = e->blur_cm;
+    a.m = e->cfg.win_m;
+    a.nomask = e->cfg.blur_nomask;
+    a.cm = e->cfg.blur_cm;
     a.grid = nullptr;
     a.gspan = a.gw = a.gh = 0;
     a.gmagic = 0;
-    a.c = e->wc;
-    const BlurChoice c = choose_blur(e, in.w, in.h, in.npairs, in.level, in.update != 0, in.quads);
+    a.c = e->cfg.wc;
+    const BlurChoice c = choose_blur(e->cfg, in.w, in.h, in.npairs, in.level, in.update != 0, in.quads);
     if (c.k == &kBoxWindow) return launch_box_window(e, st, in);
     a.xsh = a.rot = c.xsh;
     if (c.k->grid_out && in.go && in.go->span > 1 && in.w < 65536 && in.h < 65536) {
@@ -2097,10 +2205,10 @@ void launch_update(tw_engine* e, hipStream_t st, const Plan* pl, int k, const fl
     FlowUps ups;
     if (up) {
         const LevelPlan& P = pl->lv[k + 1];
-        ups = FlowUps{prev, P.w, P.h, P.ld, P.ps, L.d_uxofs, L.d_uyofs, L.d_ualpha, L.d_ubeta, L.uxmax, (float)(1. / e->p.pyrScale)};
+        ups = FlowUps{prev, P.w, P.h, P.ld, P.ps, L.d_uxofs, L.d_uyofs, L.d_ualpha, L.d_ubeta, L.uxmax, (float)(1. / e->cfg.p.pyrScale)};
     }
     UpdArgs a = upd_args(R, flow, M, L.w, L.h, L.ld, L.ps, up ? &ups : nullptr);
-    a.store_flow = e->p.pyrIterations == 0 ? 1 : 0;
+    a.store_flow = e->cfg.p.pyrIterations == 0 ? 1 : 0;
     ProfScope pscope(e, st, TW_K_UPDATE_MATRICES, k);
     if (up) {
         launch_upd_kernel<true>(e, st, L.w, L.h, npairs, a, side, side_used);
@@ -2194,10 +2302,11 @@ tw_status export_chunk(tw_engine* e, Ctx& c, hipStream_t st, const LevelPlan& L,
 }
 
 // ---- environment switches of the enqueue path ---------------------------------------------------------
-// Three classes, by WHEN a variable is read: (1) engine fields, read once in tw_engine_create (TW_LANES, TW_MFREE,
-// TW_RAMP, TW_LAT_FUSED, TW_LAT_GRAPH, TW_CHUNK_TILES, ...); (2) per batch, below: read at the start of every flush_ctx call, because the
-// tests switch them between two batches of one engine; (3) per process, further below: measurement and diagnostic
-// switches read once, when the process enqueues its first batch.
+// Three classes, by WHEN a variable is read: (1) per engine, EngineConfig: read once by make_engine_config when the engine
+// is created and const afterwards (TW_LANES, TW_MFREE, TW_RAMP, TW_LAT_FUSED, TW_LAT_GRAPH, TW_CHUNK_TILES, ...); (2) per
+// batch, below: read at the start of every flush_ctx call, because the tests switch them between two batches of one
+// engine; (3) per process, further below: measurement and diagnostic switches read once, when the process enqueues its
+// first batch (and TW_ROCTX, by Roctx).  What tw_set_option changes between batches is no environment switch: EngineOptions.
 struct BatchSwitches {
     bool lat_quads;  // TW_LAT_QUADS=0: a single pair's 224 x 8-tile window launches take tw_blur_solve4 as in a batch
     int lat_plan;    // TW_LAT_PLAN: which launches carry the twin schedule's side jobs (plan_twin_side_jobs)
@@ -2335,7 +2444,7 @@ FlowDst flow_table_row(const void* data, ptrdiff_t pitch, int layout, char* stag
 }
 
 // ---- the level schedule ------------------------------------------------------------------------------------
-// What a batch launches for each pyramid level, as one pure function of the plan's geometry, the engine's switches, the
+// What a batch launches for each pyramid level, as one pure function of the plan's geometry, the engine's configuration, the
 // batch's switches and traits, and the pairs of the part (a lane's half of the batch, a piece of the cold-start ramp, or
 // the whole batch): BatchEnqueue executes it, the byte model and tw_level_runs_flow_iter / tw_level_chunk are views of it,
 // and tw_debug_level_plan shows it to the tests.
@@ -2351,6 +2460,10 @@ struct BatchTraits {
     // the batch reads its dense final level-0 field itself (TW_OPT_RESIDUAL: tw_warp_residual): the schedule a batch with
     // a flow destination takes, without being one
     bool residual = false;
+    // what the schedule reads of the engine besides its configuration (with_engine_state): TW_OPT_SCAN_FUSED_FINAL and
+    // TW_OPT_POLYEXP_F32 as tw_set_option left them, and whether single pairs replay a captured graph (TW_LAT_GRAPH=1)
+    int scan_fused = 0, poly_f32 = 0;
+    bool graph_replay = false;
 };
 struct LaunchChoice {
     bool flow_iter;  // the launch's iterations are tw_flow_iter (no tw_update_matrices, no M planes)
@@ -2375,30 +2488,30 @@ struct LevelSchedule {
     bool single_pair() const { return kind != LS_BATCH; }
 };
 // TW_LANES=2: the two halves of a batch of at least two pairs on two streams
-int batch_lanes(const tw_engine* e, int n) { return (e->lanes > 1 && n >= 2) ? e->lanes : 1; }
-LevelSchedule choose_level_schedule(const tw_engine* e, const Plan& g, const BatchSwitches& sw, const BatchTraits& t, int npart)
+int batch_lanes(const EngineConfig& cfg, int n) { return (cfg.lanes > 1 && n >= 2) ? cfg.lanes : 1; }
+LevelSchedule choose_level_schedule(const EngineConfig& cfg, const Plan& g, const BatchSwitches& sw, const BatchTraits& t, int npart)
 {
     LevelSchedule s;
-    const int it = e->p.pyrIterations;
+    const int it = cfg.p.pyrIterations;
     s.levels = g.levels;
-    s.nlanes = batch_lanes(e, t.n);
+    s.nlanes = batch_lanes(cfg, t.n);
     for (const LevelPlan& L : g.lv) s.ws_lane = std::max(s.ws_lane, (size_t)L.ps * 2 * L.chunk);
     // one pair: image-only work (pyramid, polynomial expansion) of all levels on the second stream
     // (only worth its cross-stream hand-offs when the image-only work is tens of microseconds: >= 0.1 Mpixel)
-    const bool lat = s.nlanes == 1 && t.lat_buffers && single_pair_schedule(e, t.n, g.w0, g.h0, g.levels);
+    const bool lat = s.nlanes == 1 && t.lat_buffers && single_pair_schedule(cfg, t.n, g.w0, g.h0, g.levels);
     // ... or, for the default parameters at sizes whose pyramid halves exactly (1080p: BASELINE config 2), ONE stream of twin
     // launches: every coarse-level chain kernel carries a piece of the finer levels' image-only work in its own launch
     // (twflow_kernels.hip.h: tw_twin_*) — no cross-queue hand-off anywhere in the pair
-    const bool twin = lat && e->lat_fused && !e->lat_graph && !t.prof_on && g.levels == 3 && g.fused23 && e->pyr_fused &&
-                      pyr01_fusable(&g) && !e->pyr_generic && e->p.polyN == 7 && !e->poly_f32 && e->poly_variant == 1 &&
-                      e->upd_ny == 2 && e->win_m == 15 && !e->box && it >= 1;
+    const bool twin = lat && cfg.lat_fused && !t.graph_replay && !t.prof_on && g.levels == 3 && g.fused23 && cfg.pyr_fused &&
+                      pyr01_fusable(&g) && !cfg.pyr_generic && cfg.p.polyN == 7 && !t.poly_f32 && cfg.poly_variant == 1 &&
+                      cfg.upd_ny == 2 && cfg.win_m == 15 && !cfg.box && it >= 1;
     s.kind = twin ? LS_TWIN : lat ? LS_TWO_STREAM : LS_BATCH;
     s.lat_quads = lat && sw.lat_quads;  // (TW_LAT_QUADS=0: tw_blur_solve4 as in a batch)
     // (a batch with a flow destination needs the last level-0 field itself: never the scan-fused final iteration)
-    s.fused_final = scan_fused_level0(e, t.span) && !t.any_fout && !t.residual;
+    s.fused_final = scan_fused_level0(cfg, t.scan_fused, t.span) && !t.any_fout && !t.residual;
     // the grid-only last level-0 iteration: a batch that returns hit records alone reads the last field at the span-grid
     // points only.  (it >= 2: a single iteration is the upsampling one; span >= FI_TH: at most one grid row per step)
-    s.grid_final = sw.grid_final && !lat && !e->scan_fused && !t.any_fout && !t.residual && it >= 2 && t.span >= FI_TH && e->fi_nt == 1024;
+    s.grid_final = sw.grid_final && !lat && !t.scan_fused && !t.any_fout && !t.residual && it >= 2 && t.span >= FI_TH && cfg.fi_nt == 1024;
     for (int k = 0; k <= g.levels; k++) {
         const LevelPlan& L = g.lv[k];
         LevelChoice& c = s.lv[k];
@@ -2410,11 +2523,11 @@ LevelSchedule choose_level_schedule(const tw_engine* e, const Plan& g, const Bat
         const bool grid_only = k == 0 && s.fused_final;
         for (LaunchChoice* lc : {&c.full, &c.last}) {
             // THE place "this level runs tw_flow_iter" is decided (level_runs_flow_iter: the CU gate counts the launch's pairs)
-            lc->flow_iter = level_runs_flow_iter(e, L.w, L.h, lc == &c.full ? c.per : c.tail, lat, grid_only);
+            lc->flow_iter = level_runs_flow_iter(cfg, L.w, L.h, lc == &c.full ? c.per : c.tail, lat, grid_only);
             // ... and "the identical-pair flags apply here": only where EVERY reader of the level's second expansions takes the
             // first in their place — tw_flow_iter does, the update / window kernels (and the scan-fused last iteration's
             // tw_update_matrices at level 0) do not, and their levels get both expansions
-            lc->same = e->same_image && lc->flow_iter && !grid_only;
+            lc->same = cfg.same_image && lc->flow_iter && !grid_only;
         }
     }
     if (twin) {  // tw_pyr_23, then tw_pyr_k3f carried by the coarsest level's expansion (enqueue_twin_head launches exactly
@@ -2426,7 +2539,7 @@ LevelSchedule choose_level_schedule(const tw_engine* e, const Plan& g, const Bat
         // in the workspace (sized for level 0: there is room — the last condition), and level 2 skips its pyramid launch.  Only
         // when one launch covers the part at both levels: the loop is level-major, a second chunk of level 3 would overwrite
         // the first chunk's level-2 images before level 2 reads them.  (fused23: the plan has at least four levels)
-        if (g.fused23 && e->pyr_fused && g.lv[3].chunk >= npart && g.lv[2].chunk >= npart &&
+        if (g.fused23 && cfg.pyr_fused && g.lv[3].chunk >= npart && g.lv[2].chunk >= npart &&
             (size_t)(g.lv[3].ps + g.lv[2].ps) * 2 * npart <= s.ws_lane) {
             s.lv[3].images = IMG_WITH_FINER;
             s.lv[2].images = IMG_FROM_COARSER;
@@ -2434,7 +2547,7 @@ LevelSchedule choose_level_schedule(const tw_engine* e, const Plan& g, const Bat
         // levels 1 and 0 likewise (tw_pyr_k3f): level 0's images wait in the M1 region, which nothing else touches while levels
         // 1 and 0 both run tw_flow_iter (their iterations ping-pong through M0 only) and which is large enough (5 planes per
         // pair against 2 images of one)
-        if (e->pyr_fused && pyr01_fusable(&g) && !e->pyr_generic && g.lv[1].chunk >= npart && g.lv[0].chunk >= npart &&
+        if (cfg.pyr_fused && pyr01_fusable(&g) && !cfg.pyr_generic && g.lv[1].chunk >= npart && g.lv[0].chunk >= npart &&
             s.lv[0].full.flow_iter && s.lv[1].full.flow_iter) {
             s.lv[1].images = IMG_WITH_FINER;
             s.lv[0].images = IMG_FROM_COARSER;
@@ -2443,6 +2556,15 @@ LevelSchedule choose_level_schedule(const tw_engine* e, const Plan& g, const Bat
         }
     }
     return s;
+}
+// The traits a schedule takes from the engine's options and state, the ONE place they are read: what tw_set_option left, and
+// whether TW_LAT_GRAPH=1 is still in use.  Its callers are BatchEnqueue's choose step and the two views below it.
+BatchTraits with_engine_state(const tw_engine* e, BatchTraits t)
+{
+    t.scan_fused = e->opt.scan_fused;
+    t.poly_f32 = e->opt.poly_f32;
+    t.graph_replay = e->graph_replay();
+    return t;
 }
 // The geometry of a size for the exports: the engine's own plan when a batch has built one (its geometry is plan_geometry's,
 // fixed at engine creation), else computed into *scratch — 0.5 us against 7 - 18 us a call (profiles/level_schedule.md).
@@ -2453,7 +2575,7 @@ const Plan* plan_geometry_of(const tw_engine* e, int width, int height, Plan* sc
     if (it != e->plans.end()) return it->second;
     PlanTables tabs;
     const char* why = "";
-    if (width < 1 || height < 1 || plan_geometry(e, width, height, scratch, &tabs, &why) != TW_OK) return nullptr;
+    if (width < 1 || height < 1 || plan_geometry(e->cfg, width, height, scratch, &tabs, &why) != TW_OK) return nullptr;
     return scratch;
 }
 // The choice as the exports see it (tw_level_runs_flow_iter, the byte model): a batch of npairs pairs that returns hit records
@@ -2463,8 +2585,8 @@ const Plan* level_schedule_view(const tw_engine* e, int width, int height, int n
 {
     const Plan* g = plan_geometry_of(e, width, height, scratch);
     if (!g) return nullptr;
-    const BatchTraits t{npairs, 10, false, false, false, true};
-    *s = choose_level_schedule(e, *g, BatchSwitches(true, 1, true, true), t, npairs / batch_lanes(e, npairs));
+    const BatchTraits t = with_engine_state(e, BatchTraits{npairs, 10, false, false, false, true});
+    *s = choose_level_schedule(e->cfg, *g, BatchSwitches(true, 1, true, true), t, npairs / batch_lanes(e->cfg, npairs));
     return g;
 }
 
@@ -2503,6 +2625,7 @@ struct BatchEnqueue {
     const size_t fslot;  // bytes of a pair's slot in the flow staging regions
     Plan* pl = nullptr;
     long long stride;
+    int aligned4 = 0;    // every image pointer and the row stride of the batch are 4-byte aligned (upload_tables)
     int gw = 0, gh = 0;  // the span grid of level 0 (span > 0)
     int ramp_b[4] = {0, 0, 0, 0}, ramp_n = 1;  // cold-start ramp: piece i = pairs [ramp_b[i], ramp_b[i + 1]); ramp_n - 1 pieces
     // the schedule (choose_schedule): the batch-wide fields hold for the whole batch, the per-level ones for the part being
@@ -2516,7 +2639,7 @@ struct BatchEnqueue {
     SideJob empty_side;  // (a member: engines of several host threads enqueue at once)
 
     BatchEnqueue(tw_engine* e_, Ctx& c_)
-        : e(e_), c(c_), st(e_->stream), n((int)c_.jobs.size()), it(e_->p.pyrIterations), npx(staged_image_bytes(c_.w, c_.h)),
+        : e(e_), c(c_), st(e_->stream), n((int)c_.jobs.size()), it(e_->cfg.p.pyrIterations), npx(staged_image_bytes(c_.w, c_.h)),
           fslot(flow_stage_slot(c_.w, c_.h)), stride(c_.jobs[0].stride)
     {
         empty_side.kind = 1;
@@ -2533,22 +2656,22 @@ struct BatchEnqueue {
             gw = (pl->lv[0].w + c.span - 1) / c.span;
             gh = (pl->lv[0].h + c.span - 1) / c.span;
             // this context has no results outstanding (it is being launched), nothing on the stream uses its records
-            const size_t need_rec = (size_t)tw_grid_capacity(c.w, c.h, c.span) * e->cap;
+            const size_t need_rec = (size_t)tw_grid_capacity(c.w, c.h, c.span) * e->cfg.cap;
             TW_TRY(grow_device(e, c.d_rec, c.d_rec_cap, need_rec, need_rec * sizeof(ScanRec) + 256));
             if (c.regions) TW_TRY(reserve_region_buffers(need_rec));
             if (c.residual) TW_TRY(reserve_residual_buffers(need_rec));
         }
         // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
-        if (c.any_fout_host) TW_TRY(grow_device(e, c.d_fstage, c.d_fstage_cap, fslot * e->cap, fslot * e->cap + 256));
+        if (c.any_fout_host) TW_TRY(grow_device(e, c.d_fstage, c.d_fstage_cap, fslot * e->cfg.cap, fslot * e->cfg.cap + 256));
         return TW_OK;
     }
 
     // what tw_hit_regions needs: once per engine, once per context, and per grid size (`need_rec` = cap x G, as d_rec)
     tw_status reserve_region_buffers(size_t need_rec)
     {
-        const size_t cap = (size_t)e->cap;
-        if (!e->d_rgn) TW_HIP(e, hipMalloc((void**)&e->d_rgn, region_table_bytes(e->cap) + 256));
-        if (!c.h_rgn) TW_HIP(e, hipHostMalloc((void**)&c.h_rgn, region_table_bytes(e->cap), hipHostMallocDefault));
+        const size_t cap = (size_t)e->cfg.cap;
+        if (!e->d_rgn) TW_HIP(e, hipMalloc((void**)&e->d_rgn, region_table_bytes(e->cfg.cap) + 256));
+        if (!c.h_rgn) TW_HIP(e, hipHostMalloc((void**)&c.h_rgn, region_table_bytes(e->cfg.cap), hipHostMallocDefault));
         if (!c.d_nreg) TW_HIP(e, hipMalloc((void**)&c.d_nreg, sizeof(int) * cap + 256));
         if (!c.d_regs) TW_HIP(e, hipMalloc((void**)&c.d_regs, sizeof(RegionRec) * TW_MAX_REGIONS * cap + 256));
         if (!c.h_nreg) TW_HIP(e, hipHostMalloc((void**)&c.h_nreg, sizeof(int) * cap, hipHostMallocDefault));
@@ -2565,7 +2688,7 @@ struct BatchEnqueue {
     // what the residual kernels need: once per context, and per grid size (`need_rec` = cap x G, as d_rec)
     tw_status reserve_residual_buffers(size_t need_rec)
     {
-        const size_t cap = (size_t)e->cap;
+        const size_t cap = (size_t)e->cfg.cap;
         if (!c.d_nchg) TW_HIP(e, hipMalloc((void**)&c.d_nchg, sizeof(int) * cap + 256));
         if (!c.h_nchg) TW_HIP(e, hipHostMalloc((void**)&c.h_nchg, sizeof(int) * cap, hipHostMallocDefault));
         if (!c.h_chg) TW_HIP(e, hipHostMalloc((void**)&c.h_chg, sizeof(ChangeRec) * HOST_RECS * cap, hipHostMallocDefault));
@@ -2668,7 +2791,7 @@ struct BatchEnqueue {
     tw_status enqueue_png_target_resizes()
     {
         if (!c.any_resize_png) return TW_OK;
-        ResizeJob* hr = c.h_rsz + e->cap;
+        ResizeJob* hr = c.h_rsz + e->cfg.cap;
         // the filtered targets in order of their size: targets of one size share a launch (a page that grew by a few
         // pixels grew in every screenshot of a run), one workgroup per image as in the batch-wide launch
         std::vector<int> order;
@@ -2693,7 +2816,7 @@ struct BatchEnqueue {
         }
         if (!order.empty())
             TW_HIP(e, hipMemcpyAsync(c.d_rpng, c.h_rpng, sizeof(PngJob) * order.size(), hipMemcpyHostToDevice, e->copy_stream));
-        TW_HIP(e, hipMemcpyAsync(c.d_rsz + e->cap, hr, sizeof(ResizeJob) * (size_t)n, hipMemcpyHostToDevice, e->copy_stream));
+        TW_HIP(e, hipMemcpyAsync(c.d_rsz + e->cfg.cap, hr, sizeof(ResizeJob) * (size_t)n, hipMemcpyHostToDevice, e->copy_stream));
         for (size_t k0 = 0; k0 < order.size();) {
             const Job& jb = c.jobs[order[k0]];
             size_t k1 = k0 + 1;
@@ -2708,7 +2831,7 @@ struct BatchEnqueue {
             else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, grid, dim3(64), 0, e->copy_stream, pa);
             k0 = k1;
         }
-        launch_resize(e->copy_stream, c.d_rsz + e->cap, n);
+        launch_resize(e->copy_stream, c.d_rsz + e->cfg.cap, n);
         return TW_OK;
     }
 
@@ -2717,15 +2840,15 @@ struct BatchEnqueue {
     tw_status enqueue_device_target_resizes()
     {
         if (!c.any_resize_dev) return TW_OK;
-        ResizeJob* hr = c.h_rsz + 2 * (size_t)e->cap;
+        ResizeJob* hr = c.h_rsz + 2 * (size_t)e->cfg.cap;
         for (int j = 0; j < n; j++) {
             const Job& jb = c.jobs[j];
             hr[j] = ResizeJob{};
             if (jb.rkind == RSZ_FLUSH_DEV)
                 hr[j] = resize_job(jb.t_src, jb.tw, jb.th, jb.tstride, const_cast<uint8_t*>(jb.d_b), c.w, c.h, jb.stride);
         }
-        TW_HIP(e, hipMemcpyAsync(c.d_rsz + 2 * (size_t)e->cap, hr, sizeof(ResizeJob) * (size_t)n, hipMemcpyHostToDevice, st));
-        launch_resize(st, c.d_rsz + 2 * (size_t)e->cap, n);
+        TW_HIP(e, hipMemcpyAsync(c.d_rsz + 2 * (size_t)e->cfg.cap, hr, sizeof(ResizeJob) * (size_t)n, hipMemcpyHostToDevice, st));
+        launch_resize(st, c.d_rsz + 2 * (size_t)e->cfg.cap, n);
         return TW_OK;
     }
 
@@ -2807,7 +2930,7 @@ struct BatchEnqueue {
         // pause, or a pipeline the host cannot keep filled) — the pairs whose uploads are already marked start now, the
         // rest behind their own marks, instead of all of them behind the batch's last upload (531 MB for 128 pairs of
         // 1080p: ~14 ms of an idle GPU).  A busy stream takes the whole batch in one launch per kernel and level, as before.
-        if (e->ramp && e->lanes == 1 && !c.any_png && !c.any_jpeg && !c.any_mask && c.nseg > 0 && c.seg_at[0] < n) {
+        if (e->cfg.ramp && e->cfg.lanes == 1 && !c.any_png && !c.any_jpeg && !c.any_mask && c.nseg > 0 && c.seg_at[0] < n) {
             bool idle = true;
             for (Ctx& o : e->ctx)
                 if (&o != &c && o.launched && hipEventQuery(o.ev_done) == hipErrorNotReady) idle = false;
@@ -2838,7 +2961,7 @@ struct BatchEnqueue {
             }
             al4 = al4 && ((uintptr_t)c.h_ptrs[2 * j] % 4 == 0) && ((uintptr_t)c.h_ptrs[2 * j + 1] % 4 == 0);
         }
-        e->img_aligned4 = al4 ? 1 : 0;
+        aligned4 = al4 ? 1 : 0;
         TW_HIP(e, hipMemcpyAsync((void*)e->d_ptrs, c.h_ptrs, sizeof(void*) * 2 * n, hipMemcpyHostToDevice, st));
         if (c.any_fout) {
             for (int j = 0; j < n; j++) {
@@ -2859,13 +2982,13 @@ struct BatchEnqueue {
         if (c.regions && c.any_mask && c.span > 0) {
             // tw_hit_regions leaves out the grid points tw_wait leaves out: the pairs' clipped rectangles, one upload
             int* cnt = (int*)c.h_rgn;
-            tw_rect* rects = (tw_rect*)(c.h_rgn + region_rects_off(e->cap));
+            tw_rect* rects = (tw_rect*)(c.h_rgn + region_rects_off(e->cfg.cap));
             for (int j = 0; j < n; j++) {
                 const std::vector<tw_rect>& ign = c.jobs[j].ign;
                 cnt[j] = (int)ign.size();
                 std::copy(ign.begin(), ign.end(), rects + (size_t)j * TW_MAX_IGNORE);
             }
-            TW_HIP(e, hipMemcpyAsync(e->d_rgn, c.h_rgn, region_rects_off(e->cap) + sizeof(tw_rect) * TW_MAX_IGNORE * (size_t)n,
+            TW_HIP(e, hipMemcpyAsync(e->d_rgn, c.h_rgn, region_rects_off(e->cfg.cap) + sizeof(tw_rect) * TW_MAX_IGNORE * (size_t)n,
                                      hipMemcpyHostToDevice, st));
         }
         return TW_OK;
@@ -2875,9 +2998,9 @@ struct BatchEnqueue {
     // the whole batch (the parts of the batch schedule get their own in enqueue_batch_levels)
     tw_status choose_schedule()
     {
-        traits = BatchTraits{n, c.span, c.any_fout, c.any_init, false, e->lat_I != nullptr, c.residual != 0 && c.span > 0};
+        traits = with_engine_state(e, BatchTraits{n, c.span, c.any_fout, c.any_init, false, e->lat_I != nullptr, c.residual != 0 && c.span > 0});
         for (int i = 0; i < TW_K_COUNT; i++) traits.prof_on = traits.prof_on || e->prof_level[i] != -2;
-        sched = choose_level_schedule(e, *pl, sw, traits, n);
+        sched = choose_level_schedule(e->cfg, *pl, sw, traits, n);
         if (sched.nlanes > 1) {
             TW_HIP(e, hipEventRecord(e->ev_fork, st));  // uploads + whatever ran before on the main stream
             TW_HIP(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
@@ -2904,9 +3027,9 @@ struct BatchEnqueue {
     {
         // (destinations / fields would be baked into the graph; a reconciled pair's slots are not what the key describes)
         // (a residual batch's launches read the context's cell plane and the batch's tolerance: direct as well)
-        if (sched.single_pair() && e->lat_graph && !traits.prof_on && !c.any_fout && !c.any_init && !c.any_resize &&
+        if (sched.single_pair() && traits.graph_replay && !traits.prof_on && !c.any_fout && !c.any_init && !c.any_resize &&
             !traits.residual) {
-            const GraphKey key{c.w, c.h, c.span, stride, e->img_aligned4, e->scan_fused, e->poly_f32};
+            const GraphKey key{c.w, c.h, c.span, stride, aligned4, traits.scan_fused, traits.poly_f32};
             auto git = e->lat_graphs.find(key);
             if (git == e->lat_graphs.end()) {
                 hipGraph_t graph = nullptr;
@@ -2928,7 +3051,7 @@ struct BatchEnqueue {
                     git = e->lat_graphs.emplace(key, exec).first;
                 } else {
                     (void)hipGetLastError();
-                    e->lat_graph = 0;  // this runtime cannot capture the schedule: direct launches from now on
+                    e->graph_capture_failed = true;  // this runtime cannot capture the schedule: direct launches from now on
                 }
             }
             if (git != e->lat_graphs.end()) {
@@ -2965,7 +3088,7 @@ struct BatchEnqueue {
 #ifdef TW_VARIANTS
             // (scan_fused_level0, not fused_final: a batch with a flow destination keeps its gathered grid either way)
             // (a regions batch keeps the gathered grid: tw_hit_regions reads the samples the scan read)
-            if (sched.single_pair() && !scan_fused_level0(e, c.span) && process_switches().scan_direct && !c.regions) {
+            if (sched.single_pair() && !scan_fused_level0(e->cfg, traits.scan_fused, c.span) && process_switches().scan_direct && !c.regions) {
                 TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<true>, dim3(n), dim3(1024), 0, st, a);
             } else
 #endif
@@ -2985,7 +3108,7 @@ struct BatchEnqueue {
                 ra.gap = c.regions;
                 ra.thr2 = a.thr2;
                 ra.nrect = c.any_mask ? (const int*)e->d_rgn : nullptr;
-                ra.rects = (const int4*)(e->d_rgn + region_rects_off(e->cap));
+                ra.rects = (const int4*)(e->d_rgn + region_rects_off(e->cfg.cap));
                 ra.lab = e->d_lab;
                 ra.n_regions = c.d_nreg;
                 ra.regions = c.d_regs;
@@ -3088,7 +3211,7 @@ struct BatchEnqueue {
             const int lo = ramp ? ramp_b[part] : (int)((long long)n * lane / nlanes);
             const int hi = ramp ? ramp_b[part + 1] : (int)((long long)n * (lane + 1) / nlanes);
             if (ramp) TW_HIP(e, hipStreamWaitEvent(st, part + 1 < nparts ? c.ev_seg[part] : c.ev_h2d, 0));
-            sched = choose_level_schedule(e, *pl, sw, traits, hi - lo);
+            sched = choose_level_schedule(e->cfg, *pl, sw, traits, hi - lo);
             TW_TRY(enqueue_pair_same(lane == 0 ? st : e->stream2, lo, hi));
             for (int k = pl->levels; k >= 0; k--) {
                 const LevelPlan& L = pl->lv[k];
@@ -3115,7 +3238,7 @@ struct BatchEnqueue {
     // (behind the part's uploads, on the part's stream)
     tw_status enqueue_pair_same(hipStream_t ls, int lo, int hi)
     {
-        if (!e->same_image || hi <= lo) return TW_OK;
+        if (!e->cfg.same_image || hi <= lo) return TW_OK;
         TW_HIP(e, hipMemsetD32Async((hipDeviceptr_t)(e->d_same + lo), 1, hi - lo, ls));
         PairSameArgs a;
         a.srcs = e->d_ptrs + 2 * lo;
@@ -3141,9 +3264,9 @@ struct BatchEnqueue {
         float* Iside = images == IMG_OWN ? nullptr : k >= 2 ? ch.I + (size_t)pl->lv[3].ps * 2 * nc : ch.M1;
         const uint8_t* const* srcs = e->d_ptrs + 2 * ch.j0;
         const unsigned* same = same_flags_of(ch);
-        if (images == IMG_WITH_FINER && k == 3) launch_pyr23(e, ch.ls, pl, srcs, stride, ch.I, Iside, 2 * nc);
-        else if (images == IMG_WITH_FINER) launch_pyr01(e, ch.ls, pl, srcs, stride, ch.I, Iside, 2 * nc, sched.same01 ? same : nullptr);
-        else if (images == IMG_OWN) launch_pyr(e, ch.ls, pl, k, srcs, stride, ch.I, 2 * nc, same);
+        if (images == IMG_WITH_FINER && k == 3) launch_pyr23(e, ch.ls, pl, srcs, stride, aligned4, ch.I, Iside, 2 * nc);
+        else if (images == IMG_WITH_FINER) launch_pyr01(e, ch.ls, pl, srcs, stride, aligned4, ch.I, Iside, 2 * nc, sched.same01 ? same : nullptr);
+        else if (images == IMG_OWN) launch_pyr(e, ch.ls, pl, k, srcs, stride, aligned4, ch.I, 2 * nc, same);
         const float* Isrc = images == IMG_FROM_COARSER ? Iside : ch.I;
         return launch_polyexp(e, ch.ls, L.w, L.h, L.ld, L.ps, Isrc, ch.R, 2 * nc, k, nullptr, nullptr, same);
     }
@@ -3158,7 +3281,7 @@ struct BatchEnqueue {
         if (pl->levels >= 1) TW_TRY(enqueue_pair_images(pl->levels - 1));
         for (int k = pl->levels; k >= 0; k--) {
             RoctxRange level_range("tw_level %d (%dx%d)", k, pl->lv[k].w, pl->lv[k].h);
-            if (k < pl->levels && k <= e->lat_s2_max) TW_HIP(e, hipStreamWaitEvent(st, e->lat_ev[k], 0));
+            if (k < pl->levels && k <= e->cfg.lat_s2_max) TW_HIP(e, hipStreamWaitEvent(st, e->lat_ev[k], 0));
             const LevelChunk ch = pair_chunk(k);
             bool grid_stored = false;
             enqueue_update_blur_chain(ch, &grid_stored);
@@ -3175,9 +3298,9 @@ struct BatchEnqueue {
     tw_status enqueue_pair_images(int k)
     {
         const LevelPlan& L = pl->lv[k];
-        const bool second = k < pl->levels && k <= e->lat_s2_max;
+        const bool second = k < pl->levels && k <= e->cfg.lat_s2_max;
         hipStream_t ws = second ? e->stream2 : st;
-        launch_pyr(e, ws, pl, k, e->d_ptrs, stride, e->lat_I + lat_off[k], 2);
+        launch_pyr(e, ws, pl, k, e->d_ptrs, stride, aligned4, e->lat_I + lat_off[k], 2);
         TW_TRY(launch_polyexp(e, ws, L.w, L.h, L.ld, L.ps, e->lat_I + lat_off[k], e->lat_R + 5 * lat_off[k], 2, k));
         if (second) TW_HIP(e, hipEventRecord(e->lat_ev[k], e->stream2));
         return TW_OK;
@@ -3202,7 +3325,7 @@ struct BatchEnqueue {
     // levels 3 and 2 of both images (tw_pyr_23), then the coarsest level's expansion, which carries the level 0 / 1 images
     tw_status enqueue_twin_head()
     {
-        launch_pyr23(e, st, pl, e->d_ptrs, stride, e->lat_I + lat_off[3], e->lat_I + lat_off[2], 2);
+        launch_pyr23(e, st, pl, e->d_ptrs, stride, aligned4, e->lat_I + lat_off[3], e->lat_I + lat_off[2], 2);
         const LevelPlan &L0 = pl->lv[0], &L1 = pl->lv[1], &L3 = pl->lv[3];
         SideJob j;
         j.kind = 2;
@@ -3224,7 +3347,7 @@ struct BatchEnqueue {
         a.a1 = L0.h_kern[0];
         a.b0 = L1.h_kern[1];
         a.b1 = L1.h_kern[0];
-        a.aligned4 = (stride % 4 == 0) ? e->img_aligned4 : 0;
+        a.aligned4 = (stride % 4 == 0) ? aligned4 : 0;
         j.g = VGrid{(unsigned)((L1.w + 255) / 256), (unsigned)((L1.h + 3) / 4), 2u, 0u, 0u};
         bool used = false;
         TW_TRY(launch_polyexp(e, st, L3.w, L3.h, L3.ld, L3.ps, e->lat_I + lat_off[3], e->lat_R + 5 * lat_off[3], 2, 3, &j, &used));
@@ -3248,7 +3371,7 @@ struct BatchEnqueue {
         // 1 (default, round 6): level 1's expansion in `it` bands on level 3's window launches, level 0's in `it` bands (of both
         // images) on LEVEL 1's window launches (tw_twin_s4_poly: 680 two-wave workgroups leave the chip three quarters idle);
         // levels 2's launches and level 1's update carry nothing (they fill the chip: a carried job costs 0.7 of itself there).
-        const BlurChoice c1 = choose_blur(e, pl->lv[1].w, pl->lv[1].h, 1, 1, true, false);
+        const BlurChoice c1 = choose_blur(e->cfg, pl->lv[1].w, pl->lv[1].h, 1, 1, true, false);
         const bool l1_twin = c1.small == 1 && !c1.forced;  // level 1 takes the 96 x 8 tiles by its size, not by a switch
         if (sw.lat_plan >= 1 && l1_twin && bands_env == 0) {
             push_side_bands(1, gy1, it, 3);
@@ -3282,7 +3405,7 @@ struct BatchEnqueue {
         j.pa.h = L.h;
         j.pa.ld = L.ld;
         j.pa.ps = L.ps;
-        j.pa.c = e->pc;
+        j.pa.c = e->cfg.pc;
         j.g = VGrid{(unsigned)((L.w + PE_TW - 1) / PE_TW), (unsigned)ny, (unsigned)nz, (unsigned)y0, (unsigned)z0};
         sideq.push_back(j);
     }
@@ -3332,7 +3455,7 @@ struct BatchEnqueue {
         if (k < pl->levels) {
             const LevelPlan& Pv = pl->lv[k + 1];
             ups = FlowUps{ch.flow_prev, Pv.w, Pv.h, Pv.ld, Pv.ps, L.d_uxofs, L.d_uyofs, L.d_ualpha, L.d_ubeta, L.uxmax,
-                          (float)(1. / e->p.pyrScale)};
+                          (float)(1. / e->cfg.p.pyrScale)};
         }
         for (int i = 0; i < nfi; i++) {
             float* out = buf[(nfi - 1 - i) & 1];
@@ -3421,7 +3544,7 @@ struct BatchEnqueue {
         g.gh = gh;
         g.gzs = (long long)g.gw * g.gh;
         g.g = grid_of(ch.j0);
-        g.c = e->wc;
+        g.c = e->cfg.wc;
         ProfScope pscope(e, ch.ls, TW_K_BLUR_SOLVE, 0);
         TW_LAUNCH(e, TW_DF_BLUR_GRID, (tw_blur_grid<15, 10, 2>), dim3((g.gw + 21) / 22, (g.gh + 1) / 2, ch.nc), dim3(256), 0, ch.ls, g);
     }
@@ -3823,13 +3946,13 @@ struct Submit {
         TW_HIP(e, hipSetDevice(e->device));
         if (s.fo) {
             TW_TRY(check_flow_out(e, s.fo, s.width, s.height, &fo_host));
-            if (!e->d_fdst) TW_HIP(e, hipMalloc((void**)&e->d_fdst, sizeof(FlowDst) * (size_t)e->cap + 256));
+            if (!e->d_fdst) TW_HIP(e, hipMalloc((void**)&e->d_fdst, sizeof(FlowDst) * (size_t)e->cfg.cap + 256));
             if (fo_host && !e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
         }
         if (s.fi) {
             TW_TRY(check_flow_field(e, s.fi->data, s.fi->pitch, s.fi->layout, s.width, s.height, "initial flow field",
                                     &fi_kind));
-            if (!e->d_fsrc) TW_HIP(e, hipMalloc((void**)&e->d_fsrc, sizeof(FlowDst) * (size_t)e->cap + 256));
+            if (!e->d_fsrc) TW_HIP(e, hipMalloc((void**)&e->d_fsrc, sizeof(FlowDst) * (size_t)e->cfg.cap + 256));
         }
         return TW_OK;
     }
@@ -3839,7 +3962,7 @@ struct Submit {
     bool fits(const Ctx& b) const
     {
         return !b.launched && !b.jobs.empty() && b.w == s.width && b.h == s.height && b.span == s.span &&
-               b.threshold == s.threshold && b.jobs[0].stride == eff_stride && (int)b.jobs.size() < e->cap &&
+               b.threshold == s.threshold && b.jobs[0].stride == eff_stride && (int)b.jobs.size() < e->cfg.cap &&
                (!(png || jpeg) || b.filt_slot == 0 || filt_need() <= b.filt_slot);
     }
 
@@ -3859,7 +3982,7 @@ struct Submit {
             e->cur = nxt;
             c = &e->ctx[nxt];
         }
-        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->regions_gap, e->residual_tol);
+        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->opt.regions_gap, e->opt.residual_tol);
         return TW_OK;
     }
 
@@ -3867,11 +3990,11 @@ struct Submit {
     tw_status reserve_context_tables()
     {
         if (s.fo) {
-            if (!c->h_fdst) TW_HIP(e, hipHostMalloc((void**)&c->h_fdst, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
+            if (!c->h_fdst) TW_HIP(e, hipHostMalloc((void**)&c->h_fdst, sizeof(FlowDst) * (size_t)e->cfg.cap, hipHostMallocDefault));
             if (!c->ev_fexp) TW_HIP(e, hipEventCreateWithFlags(&c->ev_fexp, hipEventDisableTiming));
             if (!c->ev_d2h) TW_HIP(e, hipEventCreateWithFlags(&c->ev_d2h, hipEventDisableTiming));
         }
-        if (s.fi && !c->h_fsrc) TW_HIP(e, hipHostMalloc((void**)&c->h_fsrc, sizeof(FlowDst) * (size_t)e->cap, hipHostMallocDefault));
+        if (s.fi && !c->h_fsrc) TW_HIP(e, hipHostMalloc((void**)&c->h_fsrc, sizeof(FlowDst) * (size_t)e->cfg.cap, hipHostMallocDefault));
         return TW_OK;
     }
 
@@ -3882,7 +4005,7 @@ struct Submit {
         if (!s.fi || fi_kind == 0) return TW_OK;
         const size_t fslot = flow_stage_slot(s.width, s.height);
         // (grows only on the first host field of a batch: one size per batch; this context's earlier ones are waited)
-        TW_TRY(grow_device(e, c->d_istage, c->d_istage_cap, fslot * e->cap, fslot * e->cap + 256, e->copy_stream));
+        TW_TRY(grow_device(e, c->d_istage, c->d_istage_cap, fslot * e->cfg.cap, fslot * e->cfg.cap + 256, e->copy_stream));
         char* dst = c->d_istage + fslot * c->jobs.size();
         const size_t row = flow_row_bytes(s.width, s.fi->layout), rows = flow_rows(s.height, s.fi->layout);
         TW_TRY(fi_kind == 1 ? upload_in_place(dst, s.fi->data, (size_t)s.fi->pitch, row, rows)
@@ -3906,7 +4029,7 @@ struct Submit {
         if (!host) return resize ? stage_device_target() : TW_OK;
         const size_t npx = staged_image_bytes(s.width, s.height);
         // (grows only on the first job of a batch: all jobs of a batch have one size)
-        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, npx * 2 * e->cap, npx * 2 * e->cap + 256, e->copy_stream));
+        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, npx * 2 * e->cfg.cap, npx * 2 * e->cfg.cap + 256, e->copy_stream));
         TW_TRY(png || jpeg ? stage_png_rows(npx) : stage_gray_pair(npx));
         jb.h_a = s.h_a;
         jb.h_b = s.h_b;
@@ -3919,17 +4042,17 @@ struct Submit {
     // what tw_jpeg_idct needs once per context
     tw_status reserve_jpeg_tables()
     {
-        if (!c->h_jpg) TW_HIP(e, hipHostMalloc((void**)&c->h_jpg, jpeg_table_bytes(e->cap), hipHostMallocDefault));
-        if (!c->d_jpg) TW_HIP(e, hipMalloc((void**)&c->d_jpg, jpeg_table_bytes(e->cap) + 256));
-        c->jpg_quants.reserve(2 * (size_t)e->cap);
+        if (!c->h_jpg) TW_HIP(e, hipHostMalloc((void**)&c->h_jpg, jpeg_table_bytes(e->cfg.cap), hipHostMallocDefault));
+        if (!c->d_jpg) TW_HIP(e, hipMalloc((void**)&c->d_jpg, jpeg_table_bytes(e->cfg.cap) + 256));
+        c->jpg_quants.reserve(2 * (size_t)e->cfg.cap);
         return TW_OK;
     }
 
     // what tw_mask_rects needs once per context
     tw_status reserve_mask_tables()
     {
-        if (!c->h_msk) TW_HIP(e, hipHostMalloc((void**)&c->h_msk, mask_table_bytes(e->cap), hipHostMallocDefault));
-        if (!c->d_msk) TW_HIP(e, hipMalloc((void**)&c->d_msk, mask_table_bytes(e->cap) + 256));
+        if (!c->h_msk) TW_HIP(e, hipHostMalloc((void**)&c->h_msk, mask_table_bytes(e->cfg.cap), hipHostMallocDefault));
+        if (!c->d_msk) TW_HIP(e, hipMalloc((void**)&c->d_msk, mask_table_bytes(e->cfg.cap) + 256));
         return TW_OK;
     }
 
@@ -3940,10 +4063,10 @@ struct Submit {
         const size_t j = c->jobs.size();
         if (c->filt_slot == 0) {
             // first filtered image of this batch: slots as large as the region allows, at least what it needs
-            const size_t slot = std::max(filt_need(), c->d_filt_cap / (2 * (size_t)e->cap) / 256 * 256);
+            const size_t slot = std::max(filt_need(), c->d_filt_cap / (2 * (size_t)e->cfg.cap) / 256 * 256);
             // 256 bytes of slack on either side: tw_png_unfilter fetches whole 16-byte groups and may read a few
             // bytes before the first and after the last row of an image
-            const size_t nbytes = slot * 2 * (size_t)e->cap;
+            const size_t nbytes = slot * 2 * (size_t)e->cfg.cap;
             const tw_status r = grow_device(e, c->d_filt_raw, c->d_filt_cap, nbytes, nbytes + 512, e->copy_stream);
             c->d_filt = c->d_filt_raw ? c->d_filt_raw + 256 : nullptr;  // (whatever became of the region)
             if (r) return r;
@@ -4007,7 +4130,7 @@ struct Submit {
         if (s.res) {
             // only the target: page-locked in place, pageable through its slot of the pinned ring (the expected image is resident)
             if (pin_registry().covers(s.h_b, span_b)) return upload_in_place(dst_b, s.h_b, (size_t)tstride, w, h);
-            TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, npx * 2 * e->cap));
+            TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, npx * 2 * e->cfg.cap));
             uint8_t* db = c->h_img + at + npx;
             for (size_t y = 0; y < h; y++) memcpy(db + y * w, s.h_b + y * (size_t)tstride, w);
             TW_HIP(e, hipMemcpyAsync(dst_b, db, w * h, hipMemcpyHostToDevice, e->copy_stream));
@@ -4020,7 +4143,7 @@ struct Submit {
         // pageable: not through the bounce buffer — the pair is copied to its own slots of the context's pinned ring
         // (nothing to wait for) and goes up as one transfer of both images, queued now: it overlaps the caller's next
         // submit and whatever the compute stream is still doing for the previous batch
-        TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, npx * 2 * e->cap));
+        TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, npx * 2 * e->cfg.cap));
         uint8_t* da = c->h_img + at;
         for (size_t y = 0; y < h; y++) {
             memcpy(da + y * w, s.h_a + y * (size_t)s.stride, w);
@@ -4035,7 +4158,7 @@ struct Submit {
     // reconciled pair of a batch: all of a batch's slots have one size; this context's earlier batches are waited)
     tw_status reserve_resize_tables()
     {
-        const size_t n = (size_t)e->cap;
+        const size_t n = (size_t)e->cfg.cap;
         if (!c->h_rsz) TW_HIP(e, hipHostMalloc((void**)&c->h_rsz, sizeof(ResizeJob) * 3 * n, hipHostMallocDefault));
         if (!c->d_rsz) TW_HIP(e, hipMalloc((void**)&c->d_rsz, sizeof(ResizeJob) * 3 * n + 256));
         if (!c->h_rpng) TW_HIP(e, hipHostMalloc((void**)&c->h_rpng, sizeof(PngJob) * n, hipHostMallocDefault));
@@ -4081,7 +4204,7 @@ struct Submit {
     tw_status stage_device_target()
     {
         const size_t dslot = ((size_t)eff_stride * (size_t)s.height + 255) / 256 * 256;
-        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, dslot * 2 * e->cap, dslot * 2 * e->cap + 256, e->copy_stream));
+        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, dslot * 2 * e->cfg.cap, dslot * 2 * e->cfg.cap + 256, e->copy_stream));
         jb.t_src = (const uint8_t*)s.d_b;
         jb.d_b = c->d_img + dslot * (2 * c->jobs.size() + 1);
         jb.rkind = RSZ_FLUSH_DEV;
@@ -4094,7 +4217,7 @@ struct Submit {
     tw_status mark_ramp()
     {
         const int sz = (int)c->jobs.size() + 1;
-        if (host && !png && !jpeg && e->ramp && e->cap >= 64 && c->nseg < 2 && (sz == e->cap / 4 || sz == e->cap / 2)) {
+        if (host && !png && !jpeg && e->cfg.ramp && e->cfg.cap >= 64 && c->nseg < 2 && (sz == e->cfg.cap / 4 || sz == e->cfg.cap / 2)) {
             TW_HIP(e, hipEventRecord(c->ev_seg[c->nseg], e->copy_stream));
             c->seg_at[c->nseg++] = sz;
         }
@@ -4122,7 +4245,7 @@ struct Submit {
 
     tw_status launch_if_full()
     {
-        const tw_status r = (int)c->jobs.size() == e->cap ? flush_ctx(e, *c) : TW_OK;
+        const tw_status r = (int)c->jobs.size() == e->cfg.cap ? flush_ctx(e, *c) : TW_OK;
         if (r) drop_batch(*c);
         return r;
     }
@@ -4240,99 +4363,29 @@ tw_status tw_engine_create(int device, const tw_params* params, int slots, tw_en
     tw_params p;
     if (params) p = *params;
     else tw_default_params(&p);
-    if (!(p.pyrScale < 1) || !(p.pyrScale > 0)) return TW_E_UNSUPPORTED;  // CV_Assert(pyr_scale < 1)
-    if (p.polyN < 1 || p.polyN > 7) return TW_E_UNSUPPORTED;
-    if (p.winSize < 2 || p.winSize / 2 > 32) return TW_E_UNSUPPORTED;
-    if (p.pyrIterations < 0 || p.pyrLevels < 0) return TW_E_BAD_PARAMETER;
-    if (slots < 1) slots = 1;
-    if (slots > 256) slots = 256;
-    int n = 0;
+    // the statuses in this order: parameters (before the device is touched), device, what the configuration refuses
+    if (const tw_status st = check_params(p)) return st;
+    int n = 0, cus = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return TW_E_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return TW_E_DEVICE;
-    tw_engine* e = new tw_engine();
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+    EngineConfig cfg;
+    std::string why;
+    if (const tw_status st = make_engine_config(p, slots, cus, &cfg, &why)) {
+        fputs(why.c_str(), stderr);
+        return st;
+    }
+    slots = cfg.cap;  // (clamped to 1 .. 256)
+    tw_engine* e = new tw_engine(cfg);
     e->device = device;
-    e->p = p;
-    e->cap = slots;
-    polyexp_setup(p.polyN, p.polySigma, e->pc);
-    window_kernel(p.winSize, e->wc);
-    e->win_m = p.winSize / 2;
-    e->box = (p.flags & 256) ? 0 : 1;
-    if (const char* ev = getenv("TW_BLUR_VARIANT")) e->blur_variant = atoi(ev);
-    if (const char* ev = getenv("TW_PYR_GENERIC")) e->pyr_generic = atoi(ev);
-    if (const char* ev = getenv("TW_PYR_FUSED")) e->pyr_fused = atoi(ev) != 0;
-    if (const char* ev = getenv("TW_BLUR_CM")) e->blur_cm = atoi(ev);
-    if (const char* ev = getenv("TW_PYR23_THREADS")) e->pyr23_threads = atoi(ev) == 256 ? 256 : atoi(ev) == 1024 ? 1024 : atoi(ev) == 512 ? 512 : 0;
-    if (const char* ev = getenv("TW_MFREE")) e->mfree = atoi(ev);
-    if (const char* ev = getenv("TW_MFREE_MIN_PX")) e->mfree_min_px = atoll(ev);
-    if (const char* ev = getenv("TW_MFREE_MIN_W")) e->mfree_min_w = std::max(31, atoi(ev));
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) e->cu_count = cus;
-    }
-    if (e->pyr_generic) e->pyr_fused = 0;
-    if (const char* ev = getenv("TW_POLY_VARIANT")) e->poly_variant = atoi(ev);
-    if (const char* ev = getenv("TW_BLUR_SMALL")) e->blur_small = atoi(ev);
-    if (const char* ev = getenv("TW_BLUR_SMALL_LEVELS")) {
-        int k = 0;
-        for (const char* q = ev; *q && k < 8; k++) {
-            e->blur_small_lv[k] = atoi(q);
-            while (*q && *q != ',') q++;
-            if (*q == ',') q++;
-        }
-    }
-    if (const char* ev = getenv("TW_PP_WAVES")) e->pp_waves = atoi(ev);
-    if (const char* ev = getenv("TW_BLUR_NOMASK")) e->blur_nomask = atoi(ev);
-    if (const char* ev = getenv("TW_BLUR_PIPE")) e->blur_pipe = atoi(ev);
-    if (const char* ev = getenv("TW_POLYEXP_F32")) e->poly_f32 = atoi(ev) == 2 ? 2 : (atoi(ev) ? 1 : 0);  // = TW_OPT_POLYEXP_F32 (measurement runs)
-#ifndef TW_VARIANTS
-    // The measured-slower A/B kernels are compiled only into `make VARIANTS=1` builds (libtwflow_variants.so): a
-    // default build refuses their switches instead of silently running something else.
-    {
-        bool bad_lv = false;
-        for (int v : e->blur_small_lv) bad_lv = bad_lv || v == 2 || v == 3 || v == 5;
-        const bool bad = bad_lv || (e->blur_variant != 4) || (e->poly_variant != 1) || (e->blur_pipe != 0) || (e->blur_small == 2 || e->blur_small == 3 ||
-                         e->blur_small == 5) || (getenv("TW_UPD_NY") && atoi(getenv("TW_UPD_NY")) == 1);
-        if (bad) {
-            fprintf(stderr, "twflow: TW_BLUR_VARIANT / TW_POLY_VARIANT / TW_BLUR_PIPE / TW_BLUR_SMALL=2,3,5 / TW_UPD_NY=1 select kernels "
-                            "that are only in a VARIANTS=1 build (tidal-wave_amd/libtwflow_variants.so)\n");
-            delete e;
-            return TW_E_UNSUPPORTED;
-        }
-    }
-#endif
-    if (const char* ev = getenv("TW_DEBUG_STAMPS"))
-        if (atoi(ev) && hipMalloc((void**)&e->dbg_stamps, 4096 * sizeof(unsigned long long)) == hipSuccess)
-            (void)hipMemset(e->dbg_stamps, 0, 4096 * sizeof(unsigned long long));
-    if (const char* ev = getenv("TW_UPD_NY")) e->upd_ny = atoi(ev) == 1 ? 1 : 2;
-    if (const char* ev = getenv("TW_LANES")) e->lanes = std::min(2, std::max(1, atoi(ev)));
-    if (const char* ev = getenv("TW_LATENCY_STREAMS")) e->lat_streams = atoi(ev) ? 1 : 0;
-    if (const char* ev = getenv("TW_LATENCY_MIN_PX")) e->lat_min_px = atoll(ev);
-    if (const char* ev = getenv("TW_LAT_GRAPH")) e->lat_graph = atoi(ev) ? 1 : 0;
-    if (const char* ev = getenv("TW_LAT_FUSED")) e->lat_fused = atoi(ev) ? 1 : 0;
-#ifdef TW_VARIANTS
-    if (const char* ev = getenv("TW_FI_NT")) e->fi_nt = atoi(ev) == 512 ? 512 : 1024;
-    if (const char* ev = getenv("TW_FI_SKIP")) e->fi_skip = atoi(ev);
-#endif
-    if (const char* ev = getenv("TW_LAT_S2_LEVELS")) e->lat_s2_max = atoi(ev);
-    if (const char* ev = getenv("TW_RAMP")) e->ramp = atoi(ev) ? 1 : 0;
-    if (const char* ev = getenv("TW_CHUNK_TILES")) e->chunk_tiles = std::max(1, atoi(ev));
-    if (const char* ev = getenv("TW_CHUNK_PAIRS_LEVELS"))
-        for (int lv = 0; lv <= TW_MAX_LEVELS && ev; lv++) {
-            e->chunk_pairs_lv[lv] = std::max(0, atoi(ev));
-            ev = strchr(ev, ',');
-            if (ev) ev++;
-        }
-    if (const char* ev = getenv("TW_PYR_GEN_TH")) e->pyr_gen_th = atoi(ev);
-    e->lat_evtiming = getenv("TW_LAT_EVTIMING") != nullptr;
-    if (const char* ev = getenv("TW_SAME_IMAGE")) e->same_image = atoi(ev) ? 1 : 0;
-    if (const char* ev = getenv("TW_FI_MAXSEG")) e->fi_maxseg = std::min(64, std::max(1, atoi(ev)));
-    if (const char* ev = getenv("TW_FI_MINSTEPS")) e->fi_minsteps = std::max(2, atoi(ev));
+    if (cfg.debug_stamps && hipMalloc((void**)&e->dbg_stamps, 4096 * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemset(e->dbg_stamps, 0, 4096 * sizeof(unsigned long long));
     // the main stream carries the dependent flow chain: highest priority, so that its small launches are not queued
     // behind the second stream's image-only work
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
     bool ok = hipStreamCreateWithPriority(&e->stream, hipStreamNonBlocking, prio_hi) == hipSuccess &&
-              hipStreamCreateWithPriority(&e->stream2, hipStreamNonBlocking, e->lanes > 1 ? prio_hi : prio_lo) == hipSuccess &&
+              hipStreamCreateWithPriority(&e->stream2, hipStreamNonBlocking, e->cfg.lanes > 1 ? prio_hi : prio_lo) == hipSuccess &&
               hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) == hipSuccess &&
@@ -5208,21 +5261,21 @@ tw_status tw_set_option(tw_engine* e, int option, int value)
 {
     if (!e) return TW_E_BAD_PARAMETER;
     switch (option) {
-        case TW_OPT_SCAN_FUSED_FINAL: e->scan_fused = value ? 1 : 0; return TW_OK;
-        case TW_OPT_POLYEXP_F32: e->poly_f32 = value == 2 ? 2 : (value ? 1 : 0); return TW_OK;
+        case TW_OPT_SCAN_FUSED_FINAL: e->opt.scan_fused = value ? 1 : 0; return TW_OK;
+        case TW_OPT_POLYEXP_F32: e->opt.poly_f32 = value == 2 ? 2 : (value ? 1 : 0); return TW_OK;
         case TW_OPT_REGIONS:
             if (value < 0 || value > 8) {
                 e->err = "TW_OPT_REGIONS: 0 (off) or a gap of 1 .. 8";
                 return TW_E_BAD_PARAMETER;
             }
-            e->regions_gap = value;
+            e->opt.regions_gap = value;
             return TW_OK;
         case TW_OPT_RESIDUAL:
             if (value < 0 || value > 254) {
                 e->err = "TW_OPT_RESIDUAL: 0 (off) or a tolerance of 1 .. 254";
                 return TW_E_BAD_PARAMETER;
             }
-            e->residual_tol = value;
+            e->opt.residual_tol = value;
             return TW_OK;
         default: e->err = "unknown option"; return TW_E_BAD_PARAMETER;
     }
@@ -5320,7 +5373,7 @@ tw_status tw_prof_read(tw_engine* e, int kclass, double* ms_total, int* launches
 int tw_num_levels(const tw_engine* e, int width, int height)
 {
     if (!e) return -1;
-    return plan_levels(width, height, e->p.pyrScale, std::min(std::max(e->p.pyrLevels, 0), TW_MAX_LEVELS));
+    return plan_levels(width, height, e->cfg.p.pyrScale, std::min(std::max(e->cfg.p.pyrLevels, 0), TW_MAX_LEVELS));
 }
 
 int tw_level_chunk(tw_engine* e, int width, int height, int level)
@@ -5343,7 +5396,7 @@ int tw_level_runs_flow_iter(const tw_engine* e, int width, int height, int level
 
 double tw_algorithmic_bytes(const tw_engine* e, int kclass, int level, int width, int height)
 {
-    return e ? tw_algorithmic_bytes_launch(e, kclass, level, width, height, e->cap) : 0;
+    return e ? tw_algorithmic_bytes_launch(e, kclass, level, width, height, e->cfg.cap) : 0;
 }
 
 double tw_algorithmic_bytes_launch(const tw_engine* e, int kclass, int level, int width, int height, int npairs)
@@ -5356,7 +5409,7 @@ double tw_algorithmic_bytes_launch(const tw_engine* e, int kclass, int level, in
     const int L = g->levels;
     const double N = (double)g->lv[level].w * g->lv[level].h, N0 = (double)width * height;
     const double Nprev = level < L ? (double)g->lv[level + 1].w * g->lv[level + 1].h : 0;  // the coarser level's pixels
-    const int it = e->p.pyrIterations;
+    const int it = e->cfg.p.pyrIterations;
     // as built, read off the schedule's own choice (choose_level_schedule): levels that run tw_flow_iter have no
     // FarnebackUpdateMatrices launch and no M planes (flow 8N + R0 20N + R1 20N in, flow 8N out = 56N per iteration; the first
     // one reads the coarser level's flow, 8 N_{k+1}, instead of this level's); a level whose images the coarser level's launch
@@ -5392,17 +5445,17 @@ double tw_algorithmic_bytes_pair(const tw_engine* e, int width, int height, int 
 {
     if (!e) return 0;
     const int L = tw_num_levels(e, width, height);
-    const int it = e->p.pyrIterations;
+    const int it = e->cfg.p.pyrIterations;
     double tot = 0;
     for (int k = 0; k <= L; k++) {
         int w, h, ks;
         double sg, sc;
-        level_geometry(width, height, e->p.pyrScale, k, &w, &h, &sg, &ks, &sc);
+        level_geometry(width, height, e->cfg.p.pyrScale, k, &w, &h, &sg, &ks, &sc);
         const double N = (double)w * h, N0 = (double)width * height;
         double up = 8 * N;  // memset at the coarsest level
         if (k < L) {
             int pw, ph;
-            level_geometry(width, height, e->p.pyrScale, k + 1, &pw, &ph, &sg, &ks, &sc);
+            level_geometry(width, height, e->cfg.p.pyrScale, k + 1, &pw, &ph, &sg, &ks, &sc);
             up = 8.0 * pw * ph + 8 * N;
         }
         tot += 2 * (N0 + 4 * N) + 48 * N + up + it * (68 + 28) * N;
@@ -5417,7 +5470,7 @@ double tw_min_traffic_bytes_pair(const tw_engine* e, int width, int height, int 
 {
     if (!e) return 0;
     const int L = tw_num_levels(e, width, height);
-    const int it = e->p.pyrIterations;
+    const int it = e->cfg.p.pyrIterations;
     double tot = 0;
     for (int k = 0; k <= L; k++) {
         tot += tw_algorithmic_bytes(e, TW_K_PYR, k, width, height);
@@ -5490,7 +5543,7 @@ extern "C" int tw_debug_flow_iter_plan(const tw_engine* e, int width, int height
 {
     if (!e) return -1;
     if (!out || width < 1 || height < 1 || npairs < 1) return 0;
-    const FlowIterPlan fp = flow_iter_plan(e, width, height, npairs);
+    const FlowIterPlan fp = flow_iter_plan(e->cfg, width, height, npairs);
     const int v[4] = {fp.strips, fp.segments, fp.nt, fp.nt_last};
     int i = 0;
     for (; i < n && i < 4; i++) out[i] = v[i];
@@ -5501,7 +5554,7 @@ extern "C" int tw_debug_blur_plan(const tw_engine* e, int width, int height, int
 {
     if (!e) return -1;
     if (!out || width < 1 || height < 1 || npairs < 1) return 0;
-    const BlurChoice c = choose_blur(e, width, height, npairs, level, update != 0, quads != 0);
+    const BlurChoice c = choose_blur(e->cfg, width, height, npairs, level, update != 0, quads != 0);
     const int v[9] = {c.k->family, c.k->block, c.k->tw, c.k->th, c.xsh, (int)c.grid.x, (int)c.grid.y, c.small, c.forced ? 1 : 0};
     int i = 0;
     for (; i < n && i < 9; i++) out[i] = v[i];
@@ -5515,7 +5568,7 @@ extern "C" int tw_debug_pyr_plan(const tw_engine* e, int width, int height, int 
     Plan scratch;
     const Plan* g = plan_geometry_of(e, width, height, &scratch);
     if (!g || level > g->levels) return 0;
-    const PyrChoice c = choose_pyr(e, g, level, stride);
+    const PyrChoice c = choose_pyr(e->cfg, g, level, stride, 1);  // (4-byte-aligned image addresses: include/twflow_debug.h)
     const LevelPlan& L = g->lv[level];
     // output rows whose lower source row yofs + 1 lies past the image and is clipped to h0 - 1 (the level's table, made anew:
     // the plan keeps it on the device only)
@@ -5527,7 +5580,7 @@ extern "C" int tw_debug_pyr_plan(const tw_engine* e, int width, int height, int 
     }
     const int v[23] = {c.kernel, c.targ, c.kernel == PYR_KN_LEVEL_LDS ? (int)TW_DF_PYR_LEVEL_LDS : c.family, c.block, c.tw, c.th,
                        (int)c.gx, (int)c.gy, (int)c.lds, c.pitch, c.aligned4, L.w, L.h, L.ksize, L.mode, L.xmax, c.nrows_max,
-                       g->fused23 ? 1 : 0, pyr01_fusable(g) ? 1 : 0, pyr23_threads(e, 2), pyr23_threads(e, 3), g->levels, yclip};
+                       g->fused23 ? 1 : 0, pyr01_fusable(g) ? 1 : 0, pyr23_threads(e->cfg, 2), pyr23_threads(e->cfg, 3), g->levels, yclip};
     int i = 0;
     for (; i < n && i < 23; i++) out[i] = v[i];
     return i;
@@ -5554,13 +5607,14 @@ extern "C" int tw_debug_level_plan(const tw_engine* e, int width, int height, in
     const Plan* gp = plan_geometry_of(e, width, height, &scratch);
     if (!gp) return 0;
     const Plan& g = *gp;
-    const BatchTraits t{npairs, span, (traits & 1) != 0, (traits & 2) != 0, (traits & 4) != 0, !(traits & 8), (traits & 16) != 0};
+    const BatchTraits t = with_engine_state(
+        e, BatchTraits{npairs, span, (traits & 1) != 0, (traits & 2) != 0, (traits & 4) != 0, !(traits & 8), (traits & 16) != 0});
     const BatchSwitches sw;  // (read at the call, as every batch reads them)
-    const int parts = batch_lanes(e, npairs);
+    const int parts = batch_lanes(e->cfg, npairs);
     std::vector<int> v;
     for (int part = 0; part < parts; part++) {
         const int npart = (int)((long long)npairs * (part + 1) / parts) - (int)((long long)npairs * part / parts);
-        const LevelSchedule s = choose_level_schedule(e, g, sw, t, npart);
+        const LevelSchedule s = choose_level_schedule(e->cfg, g, sw, t, npart);
         if (part == 0) v = {s.kind, s.nlanes, s.levels, s.lat_quads, s.fused_final, s.grid_final, parts, 11};
         for (int k = 0; k <= s.levels; k++) {
             const LevelChoice& c = s.lv[k];
@@ -5630,50 +5684,50 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     for (size_t k = 0; k < e->flow.size(); k++)
         if (e->flow[k]) v[0] += e->flow_cap[k] * 4 + 256;
     if (e->d_grid) v[0] += e->d_grid_cap * sizeof(float2) + 256;
-    if (e->d_ptrs) v[0] += sizeof(void*) * 2 * (size_t)e->cap + 256;
-    if (e->d_count) v[0] += sizeof(int) * (size_t)e->cap + 256;
-    if (e->d_same) v[0] += sizeof(unsigned) * (size_t)e->cap + 256;
+    if (e->d_ptrs) v[0] += sizeof(void*) * 2 * (size_t)e->cfg.cap + 256;
+    if (e->d_count) v[0] += sizeof(int) * (size_t)e->cfg.cap + 256;
+    if (e->d_same) v[0] += sizeof(unsigned) * (size_t)e->cfg.cap + 256;
     if (e->dbg_stamps) v[0] += 4096 * sizeof(unsigned long long);
-    if (e->d_fdst) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
-    if (e->d_fsrc) v[0] += sizeof(FlowDst) * (size_t)e->cap + 256;
-    if (e->d_rgn) v[0] += region_table_bytes(e->cap) + 256;
+    if (e->d_fdst) v[0] += sizeof(FlowDst) * (size_t)e->cfg.cap + 256;
+    if (e->d_fsrc) v[0] += sizeof(FlowDst) * (size_t)e->cfg.cap + 256;
+    if (e->d_rgn) v[0] += region_table_bytes(e->cfg.cap) + 256;
     if (e->d_lab) v[0] += e->d_lab_cap * sizeof(int) + 256;
     if (e->d_cells) v[0] += e->d_cells_cap * sizeof(int4) + 256;
     for (const Ctx& c : e->ctx) {
         if (c.d_istage) v[0] += c.d_istage_cap + 256;
-        if (c.h_fsrc) v[1] += sizeof(FlowDst) * (size_t)e->cap;
+        if (c.h_fsrc) v[1] += sizeof(FlowDst) * (size_t)e->cfg.cap;
         if (c.d_fstage) v[0] += c.d_fstage_cap + 256;
-        if (c.h_fdst) v[1] += sizeof(FlowDst) * (size_t)e->cap;
+        if (c.h_fdst) v[1] += sizeof(FlowDst) * (size_t)e->cfg.cap;
         if (c.d_img) v[0] += c.d_img_cap + 256;
         if (c.d_tsrc_raw) v[0] += c.d_tsrc_cap + 512;
-        if (c.d_rsz) v[0] += sizeof(ResizeJob) * 3 * (size_t)e->cap + 256;
-        if (c.h_rsz) v[1] += sizeof(ResizeJob) * 3 * (size_t)e->cap;
-        if (c.d_rpng) v[0] += sizeof(PngJob) * (size_t)e->cap + 256;
-        if (c.h_rpng) v[1] += sizeof(PngJob) * (size_t)e->cap;
+        if (c.d_rsz) v[0] += sizeof(ResizeJob) * 3 * (size_t)e->cfg.cap + 256;
+        if (c.h_rsz) v[1] += sizeof(ResizeJob) * 3 * (size_t)e->cfg.cap;
+        if (c.d_rpng) v[0] += sizeof(PngJob) * (size_t)e->cfg.cap + 256;
+        if (c.h_rpng) v[1] += sizeof(PngJob) * (size_t)e->cfg.cap;
         if (c.d_filt_raw) v[0] += c.d_filt_cap + 512;
-        if (c.d_png) v[0] += png_table_bytes(e->cap) + 256;
+        if (c.d_png) v[0] += png_table_bytes(e->cfg.cap) + 256;
         if (c.d_rec) v[0] += c.d_rec_cap * sizeof(ScanRec) + 256;
         if (c.h_img) v[1] += c.h_img_cap;
-        if (c.h_ptrs) v[1] += sizeof(void*) * 2 * (size_t)e->cap;
-        if (c.h_count) v[1] += sizeof(int) * (size_t)e->cap;
-        if (c.h_png) v[1] += png_table_bytes(e->cap);
-        if (c.d_jpg) v[0] += jpeg_table_bytes(e->cap) + 256;
-        if (c.h_jpg) v[1] += jpeg_table_bytes(e->cap);
-        if (c.d_msk) v[0] += mask_table_bytes(e->cap) + 256;
-        if (c.h_msk) v[1] += mask_table_bytes(e->cap);
-        if (c.d_nreg) v[0] += sizeof(int) * (size_t)e->cap + 256;
-        if (c.d_regs) v[0] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cap + 256;
+        if (c.h_ptrs) v[1] += sizeof(void*) * 2 * (size_t)e->cfg.cap;
+        if (c.h_count) v[1] += sizeof(int) * (size_t)e->cfg.cap;
+        if (c.h_png) v[1] += png_table_bytes(e->cfg.cap);
+        if (c.d_jpg) v[0] += jpeg_table_bytes(e->cfg.cap) + 256;
+        if (c.h_jpg) v[1] += jpeg_table_bytes(e->cfg.cap);
+        if (c.d_msk) v[0] += mask_table_bytes(e->cfg.cap) + 256;
+        if (c.h_msk) v[1] += mask_table_bytes(e->cfg.cap);
+        if (c.d_nreg) v[0] += sizeof(int) * (size_t)e->cfg.cap + 256;
+        if (c.d_regs) v[0] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cfg.cap + 256;
         if (c.d_regof) v[0] += c.d_regof_cap * sizeof(int) + 256;
-        if (c.h_nreg) v[1] += sizeof(int) * (size_t)e->cap;
-        if (c.h_regs) v[1] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cap;
-        if (c.h_regof) v[1] += sizeof(int) * HOST_RECS * (size_t)e->cap;
-        if (c.h_rgn) v[1] += region_table_bytes(e->cap);
-        if (c.d_nchg) v[0] += sizeof(int) * (size_t)e->cap + 256;
+        if (c.h_nreg) v[1] += sizeof(int) * (size_t)e->cfg.cap;
+        if (c.h_regs) v[1] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cfg.cap;
+        if (c.h_regof) v[1] += sizeof(int) * HOST_RECS * (size_t)e->cfg.cap;
+        if (c.h_rgn) v[1] += region_table_bytes(e->cfg.cap);
+        if (c.d_nchg) v[0] += sizeof(int) * (size_t)e->cfg.cap + 256;
         if (c.d_chg) v[0] += c.d_chg_cap * sizeof(ChangeRec) + 256;
-        if (c.h_nchg) v[1] += sizeof(int) * (size_t)e->cap;
-        if (c.h_chg) v[1] += sizeof(ChangeRec) * HOST_RECS * (size_t)e->cap;
-        if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cap;
-        if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cap;
+        if (c.h_nchg) v[1] += sizeof(int) * (size_t)e->cfg.cap;
+        if (c.h_chg) v[1] += sizeof(ChangeRec) * HOST_RECS * (size_t)e->cfg.cap;
+        if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cfg.cap;
+        if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cfg.cap;
     }
     for (const auto& kv : e->plans) v[0] += kv.second->owned_bytes;
     v[0] += e->res_reserved;  // (the resident store's chunks: tw_debug_resident)
@@ -5833,17 +5887,30 @@ extern "C" tw_status tw_bench_stage(tw_engine* e, int kclass, int width, int hei
         TW_TRY(h2d_sync(e, (void*)tab, ht.data(), sizeof(void*) * ht.size()));
     }
     hipStream_t st = e->stream;
-    hipEvent_t ea, eb;
+    // profiling off while the stage is timed, and two events: both given back on every way out
+    struct Borrowed {
+        tw_engine* e;
+        int saved[TW_K_COUNT];
+        hipEvent_t ea = nullptr, eb = nullptr;
+        explicit Borrowed(tw_engine* e_) : e(e_)
+        {
+            memcpy(saved, e->prof_level, sizeof(saved));
+            for (int i = 0; i < TW_K_COUNT; i++) e->prof_level[i] = -2;
+        }
+        ~Borrowed()
+        {
+            memcpy(e->prof_level, saved, sizeof(saved));
+            if (ea) (void)hipEventDestroy(ea);
+            if (eb) (void)hipEventDestroy(eb);
+        }
+    } borrowed(e);
+    hipEvent_t &ea = borrowed.ea, &eb = borrowed.eb;
     TW_HIP(e, hipEventCreate(&ea));
     TW_HIP(e, hipEventCreate(&eb));
-    int saved[TW_K_COUNT];
-    memcpy(saved, e->prof_level, sizeof(saved));
-    for (int i = 0; i < TW_K_COUNT; i++) e->prof_level[i] = -2;
     auto once = [&](int i) -> tw_status {
         switch (kclass) {
             case TW_K_PYR:
-                e->img_aligned4 = (npx0 % 4 == 0) ? 1 : 0;
-                launch_pyr(e, st, pl, level, tab, width, I, 2 * npairs);
+                launch_pyr(e, st, pl, level, tab, width, npx0 % 4 == 0, I, 2 * npairs);
                 break;
             case TW_K_POLYEXP: return launch_polyexp(e, st, L.w, L.h, L.ld, L.ps, I, R, 2 * npairs, level);
             case TW_K_UPDATE_MATRICES: launch_update(e, st, pl, level, R, fl, pf, M0, npairs); break;
@@ -5851,13 +5918,13 @@ extern "C" tw_status tw_bench_stage(tw_engine* e, int kclass, int width, int hei
                 if (flags & 12) {
                     // flags 4: one M-free iteration (tw_flow_iter) from the synthetic flow field into the M1 workspace;
                     // flags 8: the same with the upsample of the coarser level's flow fused (first iteration of a level)
-                    if (!flow_iter_eligible(e, L.w, L.h)) return TW_E_UNSUPPORTED;
+                    if (!flow_iter_eligible(e->cfg, L.w, L.h)) return TW_E_UNSUPPORTED;
                     FlowUps ups;
                     const bool up = (flags & 8) && level < pl->levels;
                     if (up) {
                         const LevelPlan& Pv = pl->lv[level + 1];
                         ups = FlowUps{pf, Pv.w, Pv.h, Pv.ld, Pv.ps, L.d_uxofs, L.d_uyofs, L.d_ualpha, L.d_ubeta, L.uxmax,
-                                      (float)(1. / e->p.pyrScale)};
+                                      (float)(1. / e->cfg.p.pyrScale)};
                     }
                     launch_flow_iter(e, st, L.w, L.h, L.ld, L.ps, R, up ? nullptr : fl, L.ps, M1, L.ps, up ? &ups : nullptr,
                                      npairs, level);
@@ -5891,9 +5958,6 @@ extern "C" tw_status tw_bench_stage(tw_engine* e, int kclass, int width, int hei
     float ms = 0;
     TW_HIP(e, hipEventElapsedTime(&ms, ea, eb));
     *avg_us = ms * 1e3f / iters;
-    memcpy(e->prof_level, saved, sizeof(saved));
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
     return TW_OK;
 }
 
@@ -5915,8 +5979,7 @@ tw_status run_pyr_stage(tw_engine* e, const Plan* pl, const uint8_t* img, int w0
     const uint8_t* hp = d_img;
     TW_TRY(h2d_sync(e, (void*)d_tab, &hp, sizeof(hp)));
     hipStream_t st = e->stream;
-    e->img_aligned4 = 1;  // hipMalloc'ed image, dense rows: the kernel itself checks stride % 4
-    launch(st, d_tab, d_I);
+    launch(st, d_tab, d_I);  // (every launch with aligned4 = 1: a hipMalloc'ed image; the kernel itself checks stride % 4)
     TW_HIP(e, hipGetLastError());
     TW_HIP(e, hipStreamSynchronize(st));
     for (size_t i = 0; i < N; i++) {
@@ -5943,7 +6006,7 @@ tw_status stage_flow_ups(tw_engine* e, Tmp& t, const float* prev2, int pw, int p
     TW_TRY(h2d_sync(e, d_yo, u.yofs.data(), (size_t)h * 4));
     TW_TRY(h2d_sync(e, d_al, u.alpha.data(), (size_t)w * 8));
     TW_TRY(h2d_sync(e, d_be, u.beta.data(), (size_t)h * 8));
-    *ups = FlowUps{d_p, pw, ph, pld, pps, d_xo, d_yo, d_al, d_be, u.xmax, (float)(1. / e->p.pyrScale)};
+    *ups = FlowUps{d_p, pw, ph, pld, pps, d_xo, d_yo, d_al, d_be, u.xmax, (float)(1. / e->cfg.p.pyrScale)};
     return TW_OK;
 }
 }  // namespace
@@ -5962,7 +6025,7 @@ tw_status tw_stage_pyr_level(tw_engine* e, const uint8_t* img, int w0, int h0, i
     const int levels[1] = {level};
     float* const out[1] = {I};
     if ((r = run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
-            launch_pyr(e, st, pl, level, d_tab, w0, d_I[0], 1);
+            launch_pyr(e, st, pl, level, d_tab, w0, 1, d_I[0], 1);
         })))
         return r;
     if (w) *w = pl->lv[level].w;
@@ -5985,7 +6048,7 @@ tw_status tw_stage_pyr_fused23(tw_engine* e, const uint8_t* img, int w0, int h0,
     const int levels[2] = {3, 2};
     float* const out[2] = {I3, I2};
     return run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
-        launch_pyr23(e, st, pl, d_tab, w0, d_I[0], d_I[1], 1);
+        launch_pyr23(e, st, pl, d_tab, w0, 1, d_I[0], d_I[1], 1);
     });
 }
 
@@ -6004,7 +6067,7 @@ tw_status tw_stage_pyr_fused01(tw_engine* e, const uint8_t* img, int w0, int h0,
     const int levels[2] = {0, 1};
     float* const out[2] = {I0, I1};
     return run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
-        launch_pyr01(e, st, pl, d_tab, w0, d_I[1], d_I[0], 1);
+        launch_pyr01(e, st, pl, d_tab, w0, 1, d_I[1], d_I[0], 1);
     });
 }
 
@@ -6334,7 +6397,7 @@ tw_status tw_stage_blur_solve(tw_engine* e, const float* R0_5, const float* R1_5
         return r;
     BlurLaunch b{w, h, ld, ps, d_M, d_Mo, d_f, d_R, update_matrices ? 1 : 0, -1, 1};
     b.store_flow = 1;  // the stage returns the flow of a refreshing launch as well
-    if (e->box && !(b.Vbox = t.alloc<double>((size_t)ps * 5))) return TW_E_NOMEM;  // no engine workspace here
+    if (e->cfg.box && !(b.Vbox = t.alloc<double>((size_t)ps * 5))) return TW_E_NOMEM;  // no engine workspace here
     hipStream_t st = e->stream;
     launch_blur(e, st, b);
     TW_HIP(e, hipGetLastError());
@@ -6350,7 +6413,7 @@ tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5,
     if (!e || !R0_5 || !R1_5 || !flow_out2 || (flow_in2 && prev2)) return TW_E_BAD_PARAMETER;
     tw_status r;
     if ((r = check_dims(e, w, h)) || (prev2 && (r = check_dims(e, pw, ph)))) return r;
-    if (!flow_iter_eligible(e, w, h)) {
+    if (!flow_iter_eligible(e->cfg, w, h)) {
         e->err = "tw_stage_flow_iter: winSize 30/31 Gaussian window and a level of at least TW_MFREE_MIN_W (320) x 20 pixels";
         return TW_E_UNSUPPORTED;
     }
@@ -6380,7 +6443,7 @@ tw_status tw_stage_flow_iter_grid(tw_engine* e, const float* R0_5, const float* 
     if (!e || !R0_5 || !R1_5 || !flow_in2 || !grid_out || span < FI_TH) return TW_E_BAD_PARAMETER;
     tw_status r;
     if ((r = check_dims(e, w, h))) return r;
-    if (!flow_iter_eligible(e, w, h) || e->fi_nt != 1024) {
+    if (!flow_iter_eligible(e->cfg, w, h) || e->cfg.fi_nt != 1024) {
         e->err = "tw_stage_flow_iter_grid: winSize 30/31 Gaussian window and a level of at least TW_MFREE_MIN_W (320) x 20 pixels";
         return TW_E_UNSUPPORTED;
     }

@@ -1016,7 +1016,9 @@ class Engine:
         """The choice of one pyramid level's launch at `level` of a w x h image (rows `stride` bytes apart, default w), from
         the function the launch itself uses (twflow_debug.h: tw_debug_pyr_plan): the kernel's name and template argument,
         its launch-count family, threads, output-tile columns and rows, grid x / y, dynamic LDS bytes, staged-row pitch,
-        aligned4, the level's width, height, taps, resize mode, xmax and row-buffer height, whether the size is eligible
+        aligned4 (whole-dword loads of the source rows: answered for images at 4-byte-aligned addresses, so the stride alone
+        decides, and nothing the engine ran before changes it), the level's width, height, taps, resize mode, xmax and
+        row-buffer height, whether the size is eligible
         for tw_pyr_23 / tw_pyr_k3f, tw_pyr_23's threads for one pair / a batch, the coarsest level's index, the output rows
         whose lower source row is clipped to the image's last row."""
         v = (C.c_int * 23)()
