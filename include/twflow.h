@@ -448,6 +448,41 @@ typedef struct tw_change {
 } tw_change;                    /* 24 bytes */
 tw_status tw_ticket_changes(tw_engine* e, tw_ticket ticket, tw_change* changes, int change_cap, int* n_changes);
 
+/* Shift (additive within ABI 4, detected by the symbols).  The engine reproduces Farneback, and with it Farneback's reach: at
+ * the default parameters a displacement of a few tens of pixels.  A page whose content moved as a whole by more (an inserted
+ * banner, a scroll) has a flow that is garbage everywhere.  With the engine option TW_OPT_SHIFT on (tw_set_option, below; its
+ * value is the search radius R in pixels, 1 .. 1024), a batch estimates one integer translation per pair on the device, checks
+ * it on the pixels, and starts the pair's flow from it — after decode, reconcile and ignore masking, before the pyramid.
+ * E, T are the pair's expected and target images as the batch sees them, w x h bytes (row padding is never read).  All integer:
+ *   profiles  rowE[y] = sum_x E[y][x], colE[x] = sum_y E[y][x]; rowT, colT alike (uint32)
+ *   search    once per axis of length L with profiles pE, pT: r = min(R, L / 2); for d in [-r, r]: n(d) = L - |d|,
+ *             cost(d) = sum_{i = max(0, -d)}^{min(L, L - d) - 1} |pE[i] - pT[i + d]|.  Candidates in the order 0, -1, +1, -2, +2,
+ *             ...; one replaces the best only when cost(d) * n(best) < cost(best) * n(d) in unsigned 64 bits (ties: the smaller
+ *             |d|, then the negative one).  dy from the row profiles, dx from the column profiles; the sign is the flow's:
+ *             E[y][x] ~ T[y + dy][x + dx]
+ *   accept    sad_0 = sum |E - T| over the image, n_0 = w * h.  (dx, dy) != (0, 0): sad_s = sum |E[y][x] - T[y + dy][x + dx]|
+ *             over the overlap rectangle, n_s its area, applied = sad_s * n_0 <= (sad_0 >> 1) * n_s in unsigned 64 bits (the
+ *             shift at least halves the mean absolute difference).  (0, 0): applied = 0, sad_s = sad_0, n_s = n_0
+ *   seed      a pair with applied = 1 and no tw_flow_in of its own computes exactly what tw_submit_*_flow_init computes for it
+ *             with the full-resolution constant field ((float)dx, (float)dy), bit for bit; every other pair starts from zero.
+ *             A pair with its own tw_flow_in keeps it: its shift is measured and reported with applied = 0.
+ * Kernels: tw_shift_profiles, tw_shift_search, tw_shift_verify per batch part behind its uploads; tw_flow_shift_init at every
+ * chunk of the coarsest level.  A shift batch takes the schedule a batch with an initial field takes (no captured-graph replay
+ * of a single pair).  A batch takes the option's value in force when its first pair is booked, and all its pairs share it;
+ * every submit entry point gains the feature unchanged.  With the option off — the default — every entry point launches,
+ * copies and records exactly what it did before, and the feature's buffers do not exist.
+ * tw_ticket_shift is valid from the submit that returned the ticket until the wait that collects it.  It launches the open
+ * batch if it has to, as tw_wait does, and waits for the batch.  It does NOT consume the ticket.  On a batch opened with the
+ * option off it answers TW_E_BAD_PARAMETER and the ticket stays waitable; an unknown or already waited ticket answers
+ * TW_E_BAD_PARAMETER; errors of the pair itself are answered as tw_wait answers them. */
+typedef struct tw_shift {
+    int dx, dy;          /* the two searches' answers */
+    int applied;         /* 1: the pair's flow started from (dx, dy) */
+    int n_shift, n_zero; /* overlap area at (dx, dy); w * h */
+    uint64_t sad_shift, sad_zero;
+} tw_shift;              /* 40 bytes */
+tw_status tw_ticket_shift(tw_engine* e, tw_ticket ticket, tw_shift* out);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 
@@ -473,8 +508,10 @@ tw_status tw_dev_download(tw_engine* e, void* host, const void* dptr, size_t byt
  * TW_OPT_REGIONS (default 0): hit regions, above.  0 is off; 1 .. 8 is the gap; any other value answers
  *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked.
  * TW_OPT_RESIDUAL (default 0): residual, above.  0 is off; 1 .. 254 is the tolerance; any other value answers
+ *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked.
+ * TW_OPT_SHIFT (default 0): shift, above.  0 is off; 1 .. 1024 is the search radius in pixels; any other value answers
  *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked. */
-enum { TW_OPT_SCAN_FUSED_FINAL = 1, TW_OPT_POLYEXP_F32 = 2, TW_OPT_REGIONS = 3, TW_OPT_RESIDUAL = 4 };
+enum { TW_OPT_SCAN_FUSED_FINAL = 1, TW_OPT_POLYEXP_F32 = 2, TW_OPT_REGIONS = 3, TW_OPT_RESIDUAL = 4, TW_OPT_SHIFT = 5 };
 tw_status tw_set_option(tw_engine* e, int option, int value);
 
 /* Page-locked host memory.  Images handed to tw_submit_u8 from a block tw_host_alloc returned (or that the caller
@@ -641,6 +678,15 @@ tw_status tw_stage_hit_regions(tw_engine* e, const float* fields, int npairs, in
  * pair's share shows.  (Additive within version 4.) */
 tw_status tw_stage_warp_residual(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h,
                                  const float* flow2, int span, int tol, int* cells, int* n_changes, tw_change* changes);
+
+/* tw_shift_profiles, tw_shift_search and tw_shift_verify alone, on the caller's pair, synchronously: `expect` and `target`
+ * (w x h bytes, rows `stride` >= w bytes apart) go up as they are and are read in place with their stride, then the launches
+ * a batch part makes with `radius` (1 .. 1024).  `profiles` (nullable): [colE[w], colT[w], rowE[h], rowT[h]].  *out: the pair's
+ * record.  The outputs are set to 0xff bytes before the launches (the sums the kernels accumulate into are then zeroed as a
+ * batch zeroes them), so a write beyond the pair's share shows.  force_global = 1 takes the search's device-memory path
+ * whatever the length.  (Additive within version 4.) */
+tw_status tw_stage_shift(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h, int radius,
+                         int force_global, uint32_t* profiles, tw_shift* out);
 
 #ifdef __cplusplus
 }

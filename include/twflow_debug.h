@@ -68,6 +68,11 @@ enum tw_debug_family {
     TW_DF_BLUR_SOLVE4Q,    /* tw_blur_solve4q: solve + refresh by the horizontal item's owner — a single pair's level-0 launches (round 6) */
     TW_DF_PYR_LEVEL_LDS,   /* tw_pyr_level_lds: the generic level with its source region staged in LDS — ALSO counted in TW_DF_PYR_LEVEL.
                             * (Here and not at the end: the enum's tail from TW_DF_HIT_REGIONS on is pinned by the tests of the features that added it) */
+    TW_DF_SHIFT_PROFILES,  /* tw_shift_profiles: a batch part's row and column sums of both images (TW_OPT_SHIFT) */
+    TW_DF_SHIFT_SEARCH,    /* tw_shift_search: each pair's best integer shift per axis, from the profiles (TW_OPT_SHIFT) */
+    TW_DF_SHIFT_VERIFY,    /* tw_shift_verify<0> + <1>: the pixel sums at (0, 0) and at the shift, then areas and `applied` — two launches per part (TW_OPT_SHIFT) */
+    TW_DF_FLOW_SHIFT_INIT, /* tw_flow_shift_init: a coarsest-level chunk's first flow of the pairs whose shift was applied (TW_OPT_SHIFT; the four
+                            * here, in front of TW_DF_WARP_RESIDUAL, for the reason TW_DF_PYR_LEVEL_LDS is: no pinned neighbourhood moves) */
     TW_DF_WARP_RESIDUAL,   /* tw_warp_residual: a level-0 chunk's differing pixels against the target sampled along the final flow (TW_OPT_RESIDUAL) */
     TW_DF_CHANGE_SCAN,     /* tw_change_scan: a batch's cells with a differing pixel, compacted in order behind its ordered scan (TW_OPT_RESIDUAL;
                             * both here for the reason TW_DF_PYR_LEVEL_LDS is) */
@@ -139,7 +144,7 @@ int tw_debug_pyr_plan(const tw_engine* e, int width, int height, int level, long
 int tw_debug_scan_plan(const tw_engine* e, int width, int height, int span, int npairs, int single_pair, int* out, int n);
 
 /* What a batch of npairs pairs of width x height pixels at `span` launches for each pyramid level, from the one function the
- * enqueue itself executes (choose_level_schedule).  traits: 1 a pair has a flow destination, 2 a pair has an initial field,
+ * enqueue itself executes (choose_level_schedule).  traits: 1 a pair has a flow destination, 2 a pair has an initial field (or the batch was opened with TW_OPT_SHIFT on: the same schedule),
  * 4 a profiling class is selected, 8 the single-pair buffers do not exist, 16 the batch was opened with TW_OPT_RESIDUAL on.  out[0] the schedule (0: level-major batch, 1: one
  * pair on two streams, 2: one pair, twin launches), out[1] lanes, out[2] the coarsest level's index L, out[3] 1 when a single
  * pair's window launches take tw_blur_solve4q, out[4] 1 when the last level-0 iteration is the scan-fused one (tw_blur_grid),
@@ -154,6 +159,15 @@ int tw_debug_scan_plan(const tw_engine* e, int width, int height, int span, int 
  * null `out`, a non-positive size or pair count, a negative span or a size without a plan), -1 for a null engine.
  * tests/test_gpu_level_plan.py predicts every family's launches from it. */
 int tw_debug_level_plan(const tw_engine* e, int width, int height, int span, int npairs, int traits, int* out, int n);
+
+/* How tw_shift_search runs for a pair of width x height pixels at search radius `radius` (TW_OPT_SHIFT), a pure function of its
+ * arguments (no engine): out[0] 1 when the x axis (the column profiles, length width) keeps both profiles in LDS, out[1] the
+ * same for the y axis (the row profiles, length height), out[2] / out[3] the radius r = min(radius, L / 2) searched per axis,
+ * out[4] grid x (the axes), out[5] threads per workgroup, out[6] the LDS budget in bytes (an axis stays in LDS while 8 * L fits
+ * it), out[7] / out[8] tw_shift_profiles' grid x / y, out[9] tw_shift_verify<0>'s grid x.  Returns the number of values written
+ * (at most min(n, 10); 0 for a null `out`, a non-positive size or a radius outside 1 .. 1024).  tests/test_gpu_shift.py takes
+ * the lengths above the LDS limit from it. */
+int tw_debug_shift_plan(int width, int height, int radius, int* out, int n);
 
 /* tw_pair_same's flags of the batch this engine enqueued last: out[j] = 1 where pair j's second image is byte for byte its
  * first over the visible width x height pixels (the batch schedule then computed that pair's polynomial expansions once at

@@ -354,6 +354,8 @@ constexpr size_t region_table_bytes(int cap) { return region_rects_off(cap) + si
 static_assert(sizeof(RegionRec) == sizeof(tw_region) && sizeof(tw_region) == 36, "tw_region is the kernel's record");
 static_assert(RGN_MAX == TW_MAX_REGIONS && RGN_RECTS == TW_MAX_IGNORE, "the kernel's limits are the header's");
 static_assert(sizeof(ChangeRec) == sizeof(tw_change) && sizeof(tw_change) == 24, "tw_change is the kernel's record");
+static_assert(sizeof(ShiftRec) == sizeof(tw_shift) && sizeof(tw_shift) == 40 && offsetof(ShiftRec, sad_shift) == offsetof(tw_shift, sad_shift),
+              "tw_shift is the kernel's record");
 
 struct Job {
     const uint8_t *h_a = nullptr, *h_b = nullptr;  // host inputs already staged (null for device inputs)
@@ -493,6 +495,10 @@ struct Ctx {
     size_t d_chg_cap = 0;
     int* h_nchg = nullptr;       // [cap]
     ChangeRec* h_chg = nullptr;  // [cap][HOST_RECS]
+    // shift (TW_OPT_SHIFT): `shift` = the search radius of this batch (0: off), taken when its first pair is booked; the
+    // pinned copy of the batch's records ([cap], created when the first batch with the option on is launched from this context)
+    int shift = 0;
+    ShiftRec* h_shift = nullptr;
 
     // the batch is collected or dropped: its resident images may return to the store
     void release_images()
@@ -507,10 +513,11 @@ struct Ctx {
 
     // A new batch in this context: what describes the batch starts over; the device and pinned regions, their capacities
     // and the events survive.
-    void begin_batch(int width, int height, int span_, double threshold_, int64_t first, int regions_, int residual_)
+    void begin_batch(int width, int height, int span_, double threshold_, int64_t first, int regions_, int residual_, int shift_)
     {
         regions = regions_;
         residual = residual_;
+        shift = shift_;
         release_images();
         jobs.clear();
         launched = false;
@@ -649,6 +656,7 @@ struct EngineOptions {
     int poly_f32 = 0;      // TW_OPT_POLYEXP_F32 (measurement variant: float accumulators, not bit-exact)
     int regions_gap = 0;   // TW_OPT_REGIONS: the next batch's gap (0: off)
     int residual_tol = 0;  // TW_OPT_RESIDUAL: the next batch's tolerance (0: off)
+    int shift_radius = 0;  // TW_OPT_SHIFT: the next batch's search radius (0: off)
 };
 
 // the parameters an engine admits (tw_engine_create asks before it touches the device; make_engine_config asks for itself)
@@ -805,6 +813,12 @@ struct tw_engine {
     // consumes it before the next batch's launches write it
     int4* d_cells = nullptr;
     size_t d_cells_cap = 0;
+    // shift (the next batch's radius is opt.shift_radius): the records of the batch being enqueued ([cap]) and the four
+    // profiles of each of its pairs ([cap][2 (w + h)] words), both on first use and the engine's, as d_cells: the batch's own
+    // launches consume them, and its result copy reads the records, before the next batch's launches write them
+    ShiftRec* d_shift = nullptr;
+    unsigned* d_sprof = nullptr;
+    size_t d_sprof_cap = 0;
     // profiling: per kernel class, -2 = off, -1 = every level, k = level k only
     int prof_level[TW_K_COUNT] = {-2, -2, -2, -2, -2};
     std::vector<ProfPair> prof_pending[TW_K_COUNT];
@@ -2221,12 +2235,12 @@ void launch_update(tw_engine* e, hipStream_t st, const Plan* pl, int k, const fl
 // tw_submit_*_flow_init: the first flow of pairs [j0, j0 + nc) at the coarsest level — each pair's init field resized and
 // scaled (tw_flow_area_init), zeros for a pair without one — into `flow` (planar, the level's ld / ps), the buffer the
 // level's first FarnebackUpdateMatrices or first tw_flow_iter reads
-void launch_area_init(tw_engine* e, hipStream_t st, const Plan* pl, float* flow, int j0, int nc)
+AreaInitArgs area_init_args(const tw_engine* e, const Plan* pl, float* flow, int j0)
 {
     const LevelPlan& L = pl->lv[pl->levels];
     AreaInitArgs a;
     memset(&a, 0, sizeof(a));
-    a.src = e->d_fsrc + j0;
+    a.src = e->d_fsrc ? e->d_fsrc + j0 : nullptr;
     a.flow = flow;
     a.fps = L.ps;
     a.ld = L.ld;
@@ -2246,12 +2260,30 @@ void launch_area_init(tw_engine* e, hipStream_t st, const Plan* pl, float* flow,
     a.ystart = pl->d_iys;
     a.ysi = pl->d_iyi;
     a.ybeta = pl->d_iyb;
+    return a;
+}
+void launch_area_init(tw_engine* e, hipStream_t st, const Plan* pl, float* flow, int j0, int nc)
+{
+    const LevelPlan& L = pl->lv[pl->levels];
+    const AreaInitArgs a = area_init_args(e, pl, flow, j0);
     if (a.mode == 1 && a.tw > 0) {
         const size_t lds = (size_t)a.tw * a.ix * a.iy * 2 * sizeof(float);
         TW_LAUNCH(e, TW_DF_FLOW_INIT, tw_flow_area_init, dim3((L.w + a.tw - 1) / a.tw, L.h, nc), dim3(256), lds, st, a);
     } else {
         TW_LAUNCH(e, TW_DF_FLOW_INIT, tw_flow_area_init, dim3((L.w + 63) / 64, (L.h + 3) / 4, nc), dim3(256), 0, st, a);
     }
+}
+
+// TW_OPT_SHIFT: the first flow of the pairs [j0, j0 + nc) whose shift was applied, with tw_flow_area_init's arithmetic on their
+// constant field; `zero_rest`: zeros for the others too (no tw_flow_area_init launch wrote the chunk)
+void launch_shift_init(tw_engine* e, hipStream_t st, const Plan* pl, float* flow, int j0, int nc, bool zero_rest)
+{
+    const LevelPlan& L = pl->lv[pl->levels];
+    ShiftInitArgs a;
+    a.g = area_init_args(e, pl, flow, j0);
+    a.rec = e->d_shift + j0;
+    a.zero_rest = zero_rest ? 1 : 0;
+    TW_LAUNCH(e, TW_DF_FLOW_SHIFT_INIT, tw_flow_shift_init, dim3((L.w + 63) / 64, (L.h + 3) / 4, nc), dim3(256), 0, st, a);
 }
 
 // a flow field's rows in either layout: bytes of a row of w pixels, rows of a field of h pixel rows
@@ -2429,6 +2461,50 @@ void launch_change_scan(tw_engine* e, hipStream_t st, const int4* cells, int spa
     a.count = count;
     a.rec = rec;
     TW_LAUNCH(e, TW_DF_CHANGE_SCAN, tw_change_scan, dim3(npairs), dim3(1024), 0, st, a);
+}
+
+// The plan of the shift estimation's launches (tw_debug_shift_plan shows it to the tests): whether an axis of length L keeps both
+// profiles in LDS, and the grids
+bool shift_axis_in_lds(int L) { return (size_t)L * 2 * sizeof(unsigned) <= (size_t)SS_LDS_BYTES; }
+dim3 shift_profiles_grid(int w, int h, int nimages) { return dim3((w + 1023) / 1024, (h + SP_ROWS - 1) / SP_ROWS, nimages); }
+// tw_shift_profiles, tw_shift_search, tw_shift_verify<0> and <1> over npairs pairs whose images are srcs[2z], srcs[2z + 1]:
+// their profiles into `prof`, their records into `rec` (both zeroed here first, in stream order: the kernels accumulate).
+// `own`: the pairs' rows of the initial-field table (a pair with a field of its own is never applied), null when no pair has
+tw_status launch_shift_estimate(tw_engine* e, hipStream_t st, const uint8_t* const* srcs, long long stride, int aligned4, int w,
+                                int h, int radius, bool force_global, unsigned* prof, ShiftRec* rec, const FlowDst* own, int npairs)
+{
+    const size_t P = 2 * ((size_t)w + h);
+    TW_HIP(e, hipMemsetAsync(prof, 0, P * sizeof(unsigned) * npairs, st));
+    TW_HIP(e, hipMemsetAsync(rec, 0, sizeof(ShiftRec) * npairs, st));
+    ShiftProfArgs pa;
+    pa.srcs = srcs;
+    pa.stride = stride;
+    pa.w = w;
+    pa.h = h;
+    pa.aligned4 = aligned4;
+    pa.prof = prof;
+    TW_LAUNCH(e, TW_DF_SHIFT_PROFILES, tw_shift_profiles, shift_profiles_grid(w, h, 2 * npairs), dim3(256), 0, st, pa);
+    ShiftSearchArgs sa;
+    sa.prof = prof;
+    sa.w = w;
+    sa.h = h;
+    sa.radius = radius;
+    sa.lds[0] = !force_global && shift_axis_in_lds(w) ? 1 : 0;
+    sa.lds[1] = !force_global && shift_axis_in_lds(h) ? 1 : 0;
+    sa.rec = rec;
+    const size_t lds = sizeof(unsigned) * 2 * (size_t)std::max(sa.lds[0] ? w : 0, sa.lds[1] ? h : 0);
+    TW_LAUNCH(e, TW_DF_SHIFT_SEARCH, tw_shift_search, dim3(2, npairs), dim3(1024), lds, st, sa);
+    ShiftVerifyArgs va;
+    va.srcs = srcs;
+    va.stride = stride;
+    va.w = w;
+    va.h = h;
+    va.npairs = npairs;
+    va.rec = rec;
+    va.own = own;
+    TW_LAUNCH(e, TW_DF_SHIFT_VERIFY, tw_shift_verify<0>, dim3((h + SV_ROWS - 1) / SV_ROWS, npairs), dim3(256), 0, st, va);
+    TW_LAUNCH(e, TW_DF_SHIFT_VERIFY, tw_shift_verify<1>, dim3((npairs + 255) / 256), dim3(256), 0, st, va);
+    return TW_OK;
 }
 
 // One row of tw_flow_export's destination table / tw_flow_area_init's source table: the caller's device memory in place,
@@ -2661,6 +2737,7 @@ struct BatchEnqueue {
             if (c.regions) TW_TRY(reserve_region_buffers(need_rec));
             if (c.residual) TW_TRY(reserve_residual_buffers(need_rec));
         }
+        if (c.shift) TW_TRY(reserve_shift_buffers());
         // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
         if (c.any_fout_host) TW_TRY(grow_device(e, c.d_fstage, c.d_fstage_cap, fslot * e->cfg.cap, fslot * e->cfg.cap + 256));
         return TW_OK;
@@ -2696,6 +2773,18 @@ struct BatchEnqueue {
         TW_TRY(grow_device(e, c.d_chg, c.d_chg_cap, need_rec, need_rec * sizeof(ChangeRec) + 256));
         // the cell plane is the engine's: an earlier batch's launches may still be using it
         TW_TRY(grow_device(e, e->d_cells, e->d_cells_cap, need_rec, need_rec * sizeof(int4) + 256, e->stream));
+        return TW_OK;
+    }
+
+    // what the shift kernels need: the engine's records and profiles (an earlier batch's launches may still be using them),
+    // the context's pinned copy of the records
+    tw_status reserve_shift_buffers()
+    {
+        const size_t cap = (size_t)e->cfg.cap;
+        if (!e->d_shift) TW_HIP(e, hipMalloc((void**)&e->d_shift, sizeof(ShiftRec) * cap + 256));
+        if (!c.h_shift) TW_HIP(e, hipHostMalloc((void**)&c.h_shift, sizeof(ShiftRec) * cap, hipHostMallocDefault));
+        const size_t need = 2 * ((size_t)c.w + c.h) * cap;
+        TW_TRY(grow_device(e, e->d_sprof, e->d_sprof_cap, need, need * sizeof(unsigned) + 256, e->stream));
         return TW_OK;
     }
 
@@ -2998,7 +3087,7 @@ struct BatchEnqueue {
     // the whole batch (the parts of the batch schedule get their own in enqueue_batch_levels)
     tw_status choose_schedule()
     {
-        traits = with_engine_state(e, BatchTraits{n, c.span, c.any_fout, c.any_init, false, e->lat_I != nullptr, c.residual != 0 && c.span > 0});
+        traits = with_engine_state(e, BatchTraits{n, c.span, c.any_fout, c.any_init || c.shift != 0, false, e->lat_I != nullptr, c.residual != 0 && c.span > 0});
         for (int i = 0; i < TW_K_COUNT; i++) traits.prof_on = traits.prof_on || e->prof_level[i] != -2;
         sched = choose_level_schedule(e->cfg, *pl, sw, traits, n);
         if (sched.nlanes > 1) {
@@ -3026,8 +3115,9 @@ struct BatchEnqueue {
     tw_status enqueue_or_replay_graph()
     {
         // (destinations / fields would be baked into the graph; a reconciled pair's slots are not what the key describes)
-        // (a residual batch's launches read the context's cell plane and the batch's tolerance: direct as well)
-        if (sched.single_pair() && traits.graph_replay && !traits.prof_on && !c.any_fout && !c.any_init && !c.any_resize &&
+        // (a residual batch's launches read the context's cell plane and the batch's tolerance: direct as well; a shift batch is
+        // a batch with an initial field: traits.any_init)
+        if (sched.single_pair() && traits.graph_replay && !traits.prof_on && !c.any_fout && !traits.any_init && !c.any_resize &&
             !traits.residual) {
             const GraphKey key{c.w, c.h, c.span, stride, aligned4, traits.scan_fused, traits.poly_f32};
             auto git = e->lat_graphs.find(key);
@@ -3144,6 +3234,8 @@ struct BatchEnqueue {
                                            nrec * sizeof(ChangeRec), n, hipMemcpyDeviceToHost, st));
             }
         }
+        // the shift records come back with the batch's other results (tw_ticket_shift)
+        if (c.shift) TW_HIP(e, hipMemcpyAsync(c.h_shift, e->d_shift, sizeof(ShiftRec) * n, hipMemcpyDeviceToHost, st));
         // a batch with palette images: the flag words tw_png_unfilter set for an index without a PLTE entry (tw_wait)
         if (c.any_plte)
             TW_HIP(e, hipMemcpyAsync(c.h_pflag, c.d_png + 2 * (size_t)n, sizeof(unsigned) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -3161,6 +3253,7 @@ struct BatchEnqueue {
     // captured hipGraph (enqueue_or_replay_graph), every other batch enqueues it directly.
     tw_status enqueue_levels()
     {
+        if (sched.single_pair()) TW_TRY(enqueue_shift_estimate(st, 0, n));  // (the flow chain's stream: behind the uploads)
         if (sched.kind == LS_TWIN) return enqueue_twin_pair();
         if (sched.kind == LS_TWO_STREAM) return enqueue_two_stream_pair();
         return enqueue_batch_levels();
@@ -3213,6 +3306,7 @@ struct BatchEnqueue {
             if (ramp) TW_HIP(e, hipStreamWaitEvent(st, part + 1 < nparts ? c.ev_seg[part] : c.ev_h2d, 0));
             sched = choose_level_schedule(e->cfg, *pl, sw, traits, hi - lo);
             TW_TRY(enqueue_pair_same(lane == 0 ? st : e->stream2, lo, hi));
+            TW_TRY(enqueue_shift_estimate(lane == 0 ? st : e->stream2, lo, hi));
             for (int k = pl->levels; k >= 0; k--) {
                 const LevelPlan& L = pl->lv[k];
                 RoctxRange level_range("tw_level %d (%dx%d)", k, L.w, L.h);
@@ -3249,6 +3343,26 @@ struct BatchEnqueue {
         TW_LAUNCH(e, TW_DF_PAIR_SAME, tw_pair_same, dim3((c.h + PS_ROWS - 1) / PS_ROWS, 1, hi - lo), dim3(256), 0, ls, a);
         e->same_valid = true;
         return TW_OK;
+    }
+    // TW_OPT_SHIFT: the translation of the pairs [lo, hi) of a part, estimated and checked where the images are (behind the
+    // part's uploads, on the part's stream) — the records every coarsest-level chunk of the part reads (enqueue_first_flow)
+    tw_status enqueue_shift_estimate(hipStream_t ls, int lo, int hi)
+    {
+        if (!c.shift || hi <= lo) return TW_OK;
+        ProfScope pscope(e, ls, TW_K_SCAN, 0);  // (tw_prof_select(TW_K_SCAN): tools/shift_prof.py times the feature's launches)
+        return launch_shift_estimate(e, ls, e->d_ptrs + 2 * lo, stride, aligned4, c.w, c.h, c.shift, false,
+                                     e->d_sprof + 2 * ((size_t)c.w + c.h) * lo, e->d_shift + lo, c.any_init ? e->d_fsrc + lo : nullptr,
+                                     hi - lo);
+    }
+    // a chunk of the coarsest level of a batch that starts from a first flow: the pairs' own fields resized (zeros without
+    // one), then the applied shifts of the others
+    void enqueue_first_flow(const LevelChunk& ch, float* flow)
+    {
+        if (c.any_init) launch_area_init(e, ch.ls, pl, flow, ch.j0, ch.nc);
+        if (c.shift) {
+            ProfScope pscope(e, ch.ls, TW_K_SCAN, 0);
+            launch_shift_init(e, ch.ls, pl, flow, ch.j0, ch.nc, !c.any_init);
+        }
     }
     // the identical-pair flags of a chunk's pairs, where the schedule lets the chunk's launches read them
     const unsigned* same_flags_of(const LevelChunk& ch) const { return ch.lc.same ? e->d_same + ch.j0 : nullptr; }
@@ -3450,7 +3564,7 @@ struct BatchEnqueue {
         const LevelPlan& L = pl->lv[k];
         const int nfi = ch.grid_only ? it - 1 : it;
         float* buf[2] = {ch.flow_cur, ch.M0};  // iteration i writes buf[(nfi - 1 - i) & 1]: the last one the flow buffer
-        if (ch.init_lv) launch_area_init(e, ch.ls, pl, buf[nfi & 1], ch.j0, nc);  // (what iteration 0 reads)
+        if (ch.init_lv) enqueue_first_flow(ch, buf[nfi & 1]);  // (what iteration 0 reads)
         FlowUps ups;
         if (k < pl->levels) {
             const LevelPlan& Pv = pl->lv[k + 1];
@@ -3493,7 +3607,7 @@ struct BatchEnqueue {
     {
         const int k = ch.k, nc = ch.nc;
         const LevelPlan& L = pl->lv[k];
-        if (ch.init_lv) launch_area_init(e, ch.ls, pl, ch.flow_cur, ch.j0, nc);
+        if (ch.init_lv) enqueue_first_flow(ch, ch.flow_cur);
         if (k >= 1 && side_ok(k, false)) {
             bool used = false;
             launch_update(e, ch.ls, pl, k, ch.R, ch.flow_cur, ch.flow_prev, ch.M0, nc, side_peek(), &used, ch.init_lv);
@@ -3982,7 +4096,7 @@ struct Submit {
             e->cur = nxt;
             c = &e->ctx[nxt];
         }
-        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->opt.regions_gap, e->opt.residual_tol);
+        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->opt.regions_gap, e->opt.residual_tol, e->opt.shift_radius);
         return TW_OK;
     }
 
@@ -4460,6 +4574,7 @@ void tw_engine_destroy(tw_engine* e)
         if (c.d_chg) (void)hipFree(c.d_chg);
         if (c.h_nchg) (void)hipHostFree(c.h_nchg);
         if (c.h_chg) (void)hipHostFree(c.h_chg);
+        if (c.h_shift) (void)hipHostFree(c.h_shift);
         if (c.h_pflag) (void)hipHostFree(c.h_pflag);
         if (c.ev_h2d) (void)hipEventDestroy(c.ev_h2d);
         for (hipEvent_t ev : c.ev_seg)
@@ -4491,6 +4606,8 @@ void tw_engine_destroy(tw_engine* e)
     if (e->d_rgn) (void)hipFree(e->d_rgn);
     if (e->d_lab) (void)hipFree(e->d_lab);
     if (e->d_cells) (void)hipFree(e->d_cells);
+    if (e->d_shift) (void)hipFree(e->d_shift);
+    if (e->d_sprof) (void)hipFree(e->d_sprof);
     for (tw_image* im : e->res_images) delete im;
     for (tw_engine::ResChunk& ch : e->res_chunks) (void)hipFree(ch.base);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -5173,6 +5290,50 @@ tw_status tw_ticket_changes(tw_engine* e, tw_ticket ticket, tw_change* changes, 
     return TW_OK;
 }
 
+tw_status tw_ticket_shift(tw_engine* e, tw_ticket ticket, tw_shift* out)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    if (!out) {
+        e->err = "tw_ticket_shift: null out";
+        return TW_E_BAD_PARAMETER;
+    }
+    int j = 0;
+    Ctx* c = find_ctx(e, ticket, &j);
+    if (!c) {
+        e->err = "unknown ticket";
+        return TW_E_BAD_PARAMETER;
+    }
+    if (!c->shift) {
+        e->err = "tw_ticket_shift: the ticket's batch was opened with TW_OPT_SHIFT off";
+        return TW_E_BAD_PARAMETER;  // (the ticket stays waitable)
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    tw_status r;
+    if (!c->launched && (r = flush_ctx(e, *c))) {
+        drop_batch(*c);
+        return r;
+    }
+    // (the ticket is not consumed: the wait that collects it does the per-batch bookkeeping of the copy streams)
+    const hipError_t herr = hipEventSynchronize(c->ev_done);
+    if (herr != hipSuccess) {
+        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
+        return TW_E_DEVICE;
+    }
+    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
+        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
+        return TW_E_BAD_IMAGE_FORMAT;
+    }
+    const ShiftRec& s = c->h_shift[j];
+    out->dx = s.dx;
+    out->dy = s.dy;
+    out->applied = s.applied;
+    out->n_shift = s.n_shift;
+    out->n_zero = s.n_zero;
+    out->sad_shift = s.sad_shift;
+    out->sad_zero = s.sad_zero;
+    return TW_OK;
+}
+
 tw_status tw_diff_u8(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
                      ptrdiff_t stride, int span, double threshold, tw_vector* out, int cap, int* n, float* seconds)
 {
@@ -5276,6 +5437,13 @@ tw_status tw_set_option(tw_engine* e, int option, int value)
                 return TW_E_BAD_PARAMETER;
             }
             e->opt.residual_tol = value;
+            return TW_OK;
+        case TW_OPT_SHIFT:
+            if (value < 0 || value > 1024) {
+                e->err = "TW_OPT_SHIFT: 0 (off) or a search radius of 1 .. 1024";
+                return TW_E_BAD_PARAMETER;
+            }
+            e->opt.shift_radius = value;
             return TW_OK;
         default: e->err = "unknown option"; return TW_E_BAD_PARAMETER;
     }
@@ -5657,13 +5825,25 @@ extern "C" int tw_debug_same_flags(tw_engine* e, unsigned* out, int n)
     return m;
 }
 
+extern "C" int tw_debug_shift_plan(int width, int height, int radius, int* out, int n)
+{
+    if (!out || width < 1 || height < 1 || radius < 1 || radius > 1024) return 0;
+    const dim3 pg = shift_profiles_grid(width, height, 2);
+    const int v[10] = {shift_axis_in_lds(width) ? 1 : 0, shift_axis_in_lds(height) ? 1 : 0, std::min(radius, width / 2),
+                       std::min(radius, height / 2), 2, 1024, SS_LDS_BYTES, (int)pg.x, (int)pg.y, (height + SV_ROWS - 1) / SV_ROWS};
+    const int m = std::max(0, std::min(n, 10));
+    for (int i = 0; i < m; i++) out[i] = v[i];
+    return m;
+}
+
 extern "C" const char* tw_debug_family_name(int family)
 {
     static const char* const names[TW_DF_COUNT] = {
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pyr_level_lds", "tw_warp_residual", "tw_change_scan",
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pyr_level_lds",
+        "tw_shift_profiles", "tw_shift_search", "tw_shift_verify", "tw_flow_shift_init", "tw_warp_residual", "tw_change_scan",
         "tw_flow_iter_grid",
         "tw_hit_regions", "tw_jpeg_idct", "tw_mask_rects", "tw_pair_same",
         "tw_resize_u8", "tw_flow_area_init", "tw_flow_export"};
@@ -5693,6 +5873,8 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     if (e->d_rgn) v[0] += region_table_bytes(e->cfg.cap) + 256;
     if (e->d_lab) v[0] += e->d_lab_cap * sizeof(int) + 256;
     if (e->d_cells) v[0] += e->d_cells_cap * sizeof(int4) + 256;
+    if (e->d_shift) v[0] += sizeof(ShiftRec) * (size_t)e->cfg.cap + 256;
+    if (e->d_sprof) v[0] += e->d_sprof_cap * sizeof(unsigned) + 256;
     for (const Ctx& c : e->ctx) {
         if (c.d_istage) v[0] += c.d_istage_cap + 256;
         if (c.h_fsrc) v[1] += sizeof(FlowDst) * (size_t)e->cfg.cap;
@@ -5726,6 +5908,7 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
         if (c.d_chg) v[0] += c.d_chg_cap * sizeof(ChangeRec) + 256;
         if (c.h_nchg) v[1] += sizeof(int) * (size_t)e->cfg.cap;
         if (c.h_chg) v[1] += sizeof(ChangeRec) * HOST_RECS * (size_t)e->cfg.cap;
+        if (c.h_shift) v[1] += sizeof(ShiftRec) * (size_t)e->cfg.cap;
         if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cfg.cap;
         if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cfg.cap;
     }
@@ -6677,6 +6860,64 @@ tw_status tw_stage_warp_residual(tw_engine* e, const uint8_t* expect, const uint
     TW_TRY(d2h_sync(e, cells, d_cells, G * sizeof(int4)));
     TW_TRY(d2h_sync(e, n_changes, d_cnt, sizeof(int)));
     TW_TRY(d2h_sync(e, changes, d_chg, G * sizeof(ChangeRec)));
+    return TW_OK;
+}
+
+tw_status tw_stage_shift(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h, int radius,
+                         int force_global, uint32_t* profiles, tw_shift* out)
+{
+    if (!e || !expect || !target || !out || radius < 1 || radius > 1024) return TW_E_BAD_PARAMETER;
+    tw_status r;
+    if ((r = check_dims(e, w, h))) return r;
+    if (stride < w) return TW_E_BAD_PARAMETER;
+    TW_HIP(e, hipSetDevice(e->device));
+    // both images as they are, rows `stride` apart (the last row ends at its last pixel), each at a 256-byte boundary
+    const size_t ibytes = (size_t)(h - 1) * (size_t)stride + (size_t)w, slot = (ibytes + 255) / 256 * 256;
+    const size_t P = 2 * ((size_t)w + h);
+    Tmp t;
+    uint8_t* d_img = t.alloc<uint8_t>(2 * slot);
+    const uint8_t** d_ptrs = t.alloc<const uint8_t*>(2);
+    // the pair's share and one more behind it, which no launch may touch
+    unsigned* d_prof = t.alloc<unsigned>(2 * P);
+    ShiftRec* d_rec = t.alloc<ShiftRec>(2);
+    if (!d_img || !d_ptrs || !d_prof || !d_rec) return TW_E_NOMEM;
+    TW_TRY(h2d_sync(e, d_img, expect, ibytes));
+    TW_TRY(h2d_sync(e, d_img + slot, target, ibytes));
+    const uint8_t* hp[2] = {d_img, d_img + slot};
+    TW_TRY(h2d_sync(e, (void*)d_ptrs, hp, sizeof(hp)));
+    hipStream_t st = e->stream;
+    TW_HIP(e, hipMemsetAsync(d_prof, 0xff, 2 * P * sizeof(unsigned), st));
+    TW_HIP(e, hipMemsetAsync(d_rec, 0xff, 2 * sizeof(ShiftRec), st));
+    {
+        // (tw_prof_select(TW_K_SCAN): these launches alone, for measurements)
+        ProfScope pscope(e, st, TW_K_SCAN, 0);
+        TW_TRY(launch_shift_estimate(e, st, d_ptrs, (long long)stride, stride % 4 == 0 ? 1 : 0, w, h, radius, force_global != 0,
+                                     d_prof, d_rec, nullptr, 1));
+    }
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    std::vector<unsigned> hprof(2 * P);
+    ShiftRec hrec[2];
+    TW_TRY(d2h_sync(e, hprof.data(), d_prof, 2 * P * sizeof(unsigned)));
+    TW_TRY(d2h_sync(e, hrec, d_rec, sizeof(hrec)));
+    for (size_t i = P; i < 2 * P; i++)
+        if (hprof[i] != 0xffffffffu) {
+            e->err = "tw_stage_shift: a launch wrote beyond the pair's profiles";
+            return TW_E_DEVICE;
+        }
+    for (size_t i = 0; i < sizeof(ShiftRec); i++)
+        if (((const unsigned char*)&hrec[1])[i] != 0xff) {
+            e->err = "tw_stage_shift: a launch wrote beyond the pair's record";
+            return TW_E_DEVICE;
+        }
+    if (profiles) memcpy(profiles, hprof.data(), P * sizeof(unsigned));
+    out->dx = hrec[0].dx;
+    out->dy = hrec[0].dy;
+    out->applied = hrec[0].applied;
+    out->n_shift = hrec[0].n_shift;
+    out->n_zero = hrec[0].n_zero;
+    out->sad_shift = hrec[0].sad_shift;
+    out->sad_zero = hrec[0].sad_zero;
     return TW_OK;
 }
 

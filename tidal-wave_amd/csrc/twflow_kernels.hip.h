@@ -5614,4 +5614,265 @@ __global__ __launch_bounds__(1024) void tw_change_scan(ChangeScanArgs a)
     if (tid == 0) a.count[z] = nchg;
 }
 
+// =====================================================================================================
+// Shift (TW_OPT_SHIFT): a pair's global integer translation, found where the images are (include/twflow.h has the
+// definition; all of it integer, so no result depends on the order of evaluation).
+//   tw_shift_profiles : per batch part, grid z = the part's IMAGES (2 per pair).  A workgroup owns a band of SP_ROWS rows and
+//     1024 columns; a thread owns four adjacent columns (one dword load where pointers and stride are 4-byte aligned, byte
+//     loads otherwise and for a row's last partial quad: padding is never read).  Row sums: the lanes' quads reduced across the
+//     wave, one integer atomic per wave and row; column sums: registers over the band, one integer atomic per column and band.
+//     The profiles are zero when the launch starts (the host sets them in stream order).
+//   tw_shift_search : one 1024-thread workgroup per pair and axis.  A wave owns every 16th candidate of the visit order
+//     0, -1, +1, -2, ...; its lanes stride the overlap, and the 64-bit cost is reduced across the wave.  The winner is the
+//     candidate with the least cost / n (cross-multiplied in 64 bits), the earliest in visit order among equals — what
+//     replacing on strict improvement in visit order gives, in any order of evaluation.  Profiles in LDS when the host says
+//     they fit (ShiftSearchArgs::lds), else read from memory.
+//   tw_shift_verify<0> : bands of SV_ROWS rows; the sums of |E - T| at (0, 0) and over the overlap at (dx, dy), reduced per
+//     workgroup, one 64-bit integer atomic each.  tw_shift_verify<1> : one thread per pair, behind it: areas and `applied`.
+//   tw_flow_shift_init : the coarsest level's first flow of the pairs whose shift was applied — tw_flow_area_init's own
+//     arithmetic on the constant field ((float)dx, (float)dy), which in float is not a constant in general.
+// =====================================================================================================
+struct ShiftRec {  // = tw_shift (`work` is its padding word)
+    int dx, dy, applied, n_shift, n_zero;
+    unsigned work;
+    unsigned long long sad_shift, sad_zero;
+};
+constexpr int SP_ROWS = 64, SV_ROWS = 16;
+constexpr int SS_LDS_BYTES = 48 * 1024;  // tw_shift_search keeps both profiles of an axis in LDS up to here
+struct ShiftProfArgs {
+    const uint8_t* const* srcs;  // image z: srcs[z] (pair z >> 1)
+    long long stride;
+    int w, h, aligned4;
+    unsigned* prof;              // pair p: [colE[w], colT[w], rowE[h], rowT[h]] at prof + p * 2 * (w + h)
+};
+__global__ __launch_bounds__(256) void tw_shift_profiles(ShiftProfArgs a)
+{
+    const int z = blockIdx.z, q = z & 1;
+    const uint8_t* __restrict__ S = a.srcs[z];
+    unsigned* __restrict__ P = a.prof + (long long)(z >> 1) * 2 * ((long long)a.w + a.h);
+    unsigned* __restrict__ col = P + (long long)q * a.w;
+    unsigned* __restrict__ row = P + 2ll * a.w + (long long)q * a.h;
+    const int x0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+    const int y0 = blockIdx.y * SP_ROWS, y1 = min(a.h, y0 + SP_ROWS);
+    const int nx = min(4, a.w - x0);  // (<= 0: the thread has no column, and still takes part in the wave's sums)
+    unsigned c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    for (int y = y0; y < y1; y++) {
+        const uint8_t* __restrict__ r = S + (long long)y * a.stride + x0;
+        unsigned b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+        if (nx == 4 && a.aligned4) {
+            const unsigned d = *(const unsigned*)r;
+            b0 = d & 0xffu;
+            b1 = (d >> 8) & 0xffu;
+            b2 = (d >> 16) & 0xffu;
+            b3 = d >> 24;
+        } else {
+            if (nx > 0) b0 = r[0];
+            if (nx > 1) b1 = r[1];
+            if (nx > 2) b2 = r[2];
+            if (nx > 3) b3 = r[3];
+        }
+        c0 += b0;
+        c1 += b1;
+        c2 += b2;
+        c3 += b3;
+        unsigned s = (b0 + b1) + (b2 + b3);
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        if ((threadIdx.x & 63) == 0 && s) atomicAdd(row + y, s);
+    }
+    if (nx > 0 && c0) atomicAdd(col + x0, c0);
+    if (nx > 1 && c1) atomicAdd(col + x0 + 1, c1);
+    if (nx > 2 && c2) atomicAdd(col + x0 + 2, c2);
+    if (nx > 3 && c3) atomicAdd(col + x0 + 3, c3);
+}
+
+struct ShiftSearchArgs {
+    const unsigned* prof;  // as ShiftProfArgs::prof
+    int w, h, radius;
+    int lds[2];            // axis 0 (x: the column profiles), axis 1 (y: the row profiles): both profiles in LDS
+    ShiftRec* rec;         // pair p
+};
+// candidate k of the visit order 0, -1, +1, -2, +2, ...
+__device__ __forceinline__ int shift_cand(int k) { return (k & 1) ? -((k + 1) >> 1) : (k >> 1); }
+// is (ca, na, ka) in front of (cb, nb, kb): a smaller cost per element, or the same and earlier in visit order
+__device__ __forceinline__ bool shift_better(unsigned long long ca, int na, int ka, unsigned long long cb, int nb, int kb)
+{
+    const unsigned long long l = ca * (unsigned long long)nb, r = cb * (unsigned long long)na;
+    return l < r || (l == r && ka < kb);
+}
+__global__ __launch_bounds__(1024) void tw_shift_search(ShiftSearchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned ss_prof[];  // [2][L] when the axis' profiles fit
+    __shared__ unsigned long long ss_cost[16];
+    __shared__ int ss_k[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int axis = blockIdx.x, p = blockIdx.y;
+    const int L = axis == 0 ? a.w : a.h;
+    const unsigned* __restrict__ gE = a.prof + (long long)p * 2 * ((long long)a.w + a.h) + (axis == 0 ? 0ll : 2ll * a.w);
+    const unsigned* __restrict__ gT = gE + L;
+    const bool lds = a.lds[axis] != 0;
+    if (lds) {
+        for (int i = tid; i < 2 * L; i += 1024) ss_prof[i] = gE[i];
+        __syncthreads();
+    }
+    const int r = min(a.radius, L / 2), ncand = 2 * r + 1;
+    unsigned long long bc = 0;
+    int bk = -1;  // (wave-uniform: every lane holds the reduced cost)
+    for (int k = wave; k < ncand; k += 16) {
+        const int d = shift_cand(k);
+        const int lo = max(0, -d), hi = min(L, L - d);
+        unsigned long long c = 0;
+        if (lds) {
+            for (int i = lo + lane; i < hi; i += 64) {
+                const unsigned e = ss_prof[i], t = ss_prof[L + i + d];
+                c += e > t ? e - t : t - e;
+            }
+        } else {
+            for (int i = lo + lane; i < hi; i += 64) {
+                const unsigned e = gE[i], t = gT[i + d];
+                c += e > t ? e - t : t - e;
+            }
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned clo = __shfl_xor((unsigned)c, off), chi = __shfl_xor((unsigned)(c >> 32), off);
+            c += ((unsigned long long)chi << 32) | clo;
+        }
+        if (bk < 0 || shift_better(c, L - abs(d), k, bc, L - abs(shift_cand(bk)), bk)) {
+            bc = c;
+            bk = k;
+        }
+    }
+    if (lane == 0) {
+        ss_cost[wave] = bc;
+        ss_k[wave] = bk;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        // (wave 0 owns candidate 0: ss_k[0] >= 0 always)
+        bc = ss_cost[0];
+        bk = ss_k[0];
+        for (int v = 1; v < 16; v++) {
+            const int k = ss_k[v];
+            if (k >= 0 && shift_better(ss_cost[v], L - abs(shift_cand(k)), k, bc, L - abs(shift_cand(bk)), bk)) {
+                bc = ss_cost[v];
+                bk = k;
+            }
+        }
+        if (axis == 0) a.rec[p].dx = shift_cand(bk);
+        else a.rec[p].dy = shift_cand(bk);
+    }
+}
+
+struct ShiftVerifyArgs {
+    const uint8_t* const* srcs;  // pair p: E = srcs[2p], T = srcs[2p + 1]
+    long long stride;
+    int w, h, npairs;
+    ShiftRec* rec;               // pair p; the sums are zero when tw_shift_verify<0> starts
+    const FlowDst* own;          // pair p has an initial field of its own (p non-null): never applied; null: no pair has
+};
+template <int PHASE>
+__global__ __launch_bounds__(256) void tw_shift_verify(ShiftVerifyArgs a)
+{
+    if (PHASE == 1) {
+        const int p = blockIdx.x * 256 + threadIdx.x;
+        if (p >= a.npairs) return;
+        ShiftRec r = a.rec[p];
+        const unsigned long long n0 = (unsigned long long)a.w * (unsigned long long)a.h;
+        const unsigned long long ns = (unsigned long long)(a.w - abs(r.dx)) * (unsigned long long)(a.h - abs(r.dy));
+        int applied = 0;
+        if (r.dx != 0 || r.dy != 0) applied = r.sad_shift * n0 <= (r.sad_zero >> 1) * ns ? 1 : 0;
+        else r.sad_shift = r.sad_zero;
+        if (a.own && a.own[p].p) applied = 0;
+        r.applied = applied;
+        r.n_shift = (int)ns;
+        r.n_zero = (int)n0;
+        r.work = 0;
+        a.rec[p] = r;
+        return;
+    }
+    __shared__ unsigned long long sv_sum[2][4];
+    const int p = blockIdx.y;
+    const uint8_t* __restrict__ E = a.srcs[2 * p];
+    const uint8_t* __restrict__ T = a.srcs[2 * p + 1];
+    const int dx = a.rec[p].dx, dy = a.rec[p].dy;
+    const bool moved = dx != 0 || dy != 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int xa = max(0, -dx), xb = min(a.w, a.w - dx);  // the overlap's columns of E
+    const int y1 = min(a.h, ((int)blockIdx.x + 1) * SV_ROWS);
+    unsigned long long s0 = 0, ss = 0;
+    for (int y = blockIdx.x * SV_ROWS + wave; y < y1; y += 4) {
+        const uint8_t* __restrict__ er = E + (long long)y * a.stride;
+        const uint8_t* __restrict__ tr = T + (long long)y * a.stride;
+        const bool in = moved && y + dy >= 0 && y + dy < a.h;
+        const uint8_t* __restrict__ ts = T + (long long)(in ? y + dy : y) * a.stride;
+        unsigned r0 = 0, rs = 0;  // (a row's sums: at most 255 * 32768)
+        for (int x = lane; x < a.w; x += 64) {
+            const int ev = er[x];
+            r0 += (unsigned)abs(ev - (int)tr[x]);
+            if (in && x >= xa && x < xb) rs += (unsigned)abs(ev - (int)ts[x + dx]);
+        }
+        s0 += r0;
+        ss += rs;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        s0 += ((unsigned long long)__shfl_xor((unsigned)(s0 >> 32), off) << 32) | __shfl_xor((unsigned)s0, off);
+        ss += ((unsigned long long)__shfl_xor((unsigned)(ss >> 32), off) << 32) | __shfl_xor((unsigned)ss, off);
+    }
+    if (lane == 0) {
+        sv_sum[0][wave] = s0;
+        sv_sum[1][wave] = ss;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s0 = (sv_sum[0][0] + sv_sum[0][1]) + (sv_sum[0][2] + sv_sum[0][3]);
+        ss = (sv_sum[1][0] + sv_sum[1][1]) + (sv_sum[1][2] + sv_sum[1][3]);
+        if (s0) atomicAdd(&a.rec[p].sad_zero, s0);
+        if (ss) atomicAdd(&a.rec[p].sad_shift, ss);
+    }
+}
+
+struct ShiftInitArgs {
+    AreaInitArgs g;       // tw_flow_area_init's arguments for the launch's pairs (src unused; flow = pair z's planes)
+    const ShiftRec* rec;  // pair z
+    int zero_rest;        // write zeros for the pairs it does not seed (no tw_flow_area_init launch wrote them)
+};
+__global__ __launch_bounds__(256) void tw_flow_shift_init(ShiftInitArgs s)
+{
+    const AreaInitArgs& a = s.g;
+    const ShiftRec r = s.rec[blockIdx.z];
+    if (!r.applied && !s.zero_rest) return;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.w || y >= a.h) return;
+    float* __restrict__ out = a.flow + (long long)blockIdx.z * 2 * a.fps;
+    float v[2] = {0.f, 0.f};
+    if (r.applied) {
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            const float f = (float)(c == 0 ? r.dx : r.dy);
+            float t;
+            if (a.mode == 0) {
+                t = f;
+            } else if (a.mode == 1) {
+                t = area_fast_sum(a.ix * a.iy, [&](int) { return f; });
+                t = t * a.inv_area;
+            } else {
+                t = 0.f;
+                const int j0 = a.ystart[y], j1 = a.ystart[y + 1], k0 = a.xstart[x], k1 = a.xstart[x + 1];
+                for (int j = j0; j < j1; j++) {
+                    float b = 0.f;
+                    for (int k = k0; k < k1; k++) {
+                        const float m = f * a.xalpha[k];
+                        b = b + m;
+                    }
+                    const float bb = a.ybeta[j] * b;
+                    t = j == j0 ? bb : t + bb;
+                }
+            }
+            v[c] = area_scale(a, t);
+        }
+    }
+    out[(long long)y * a.ld + x] = v[0];
+    out[a.fps + (long long)y * a.ld + x] = v[1];
+}
+
+
 }  // namespace twk

@@ -121,6 +121,17 @@ napi_value convert_result(napi_env env, const Response& r)
         }
         napi_set_named_property(env, o, "change", chg);
     }
+    if (r.hasShift) {
+        // not in the reference (new TidalWave({shift: R}) only), behind every other key: the pair's global translation as the
+        // device estimated it, and whether the flow started from it
+        napi_value sh, ap;
+        napi_create_object(env, &sh);
+        set_i32(env, sh, "x", r.shift.x);
+        set_i32(env, sh, "y", r.shift.y);
+        napi_get_boolean(env, r.shift.applied, &ap);
+        napi_set_named_property(env, sh, "applied", ap);
+        napi_set_named_property(env, o, "shift", sh);
+    }
     return o;
 }
 
@@ -242,6 +253,9 @@ napi_value construct(napi_env env, napi_callback_info info)
     // in gray levels.  residualMin n > 0: a pair with at least n unexplained pixels is SUSPICIOUS even without a vector
     p.residual = get_i32(env, opts, "residual", 0);
     p.residualMin = get_i32(env, opts, "residualMin", 0);
+    // not in the reference: start every pair's flow from its global shift, found on the device — 0 (default): off; 1 .. 1024:
+    // the search radius in pixels
+    p.shift = get_i32(env, opts, "shift", 0);
 
     Broker* b = new Broker();
     b->env = env;

@@ -5,7 +5,8 @@
 // that may differ; -regions N (1 .. 8), the vectors of every pair grouped into regions (`regions` behind `vector`, `region`
 // in every vector), N being the gap in grid steps that still joins two vectors; -residual N (1 .. 254), the cells of every pair
 // with a pixel that differs by more than N gray levels and how many of those the flow does not explain (`change` behind the
-// other keys), and -residualMin N, which makes a pair with at least N unexplained pixels SUSPICIOUS even without a vector.  The reference's own script cannot run (it requires
+// other keys), and -residualMin N, which makes a pair with at least N unexplained pixels SUSPICIOUS even without a vector; -shift N (1 .. 1024),
+// every pair's flow started from its global shift of at most N pixels, found on the device (`shift` behind the other keys).  The reference's own script cannot run (it requires
 // './opticalflow.js', which does not exist, commandline.js:62); this one drives index.js.  No stdout dup2
 // trick is needed: the native layer here does not print.
 // expect_path / target_path may be two directories (every file of target is paired with the same relative
@@ -22,7 +23,7 @@ var usage =
   '  $ node commandline.js -threshold 1.0 -span 10 test/images test/images2\n';
 
 var supportedOptions = ['threshold', 'span', 'pyrScale', 'pyrLevels', 'winSize', 'pyrIterations', 'polyN',
-  'polySigma', 'flags', 'numThreads', 'regions', 'residual', 'residualMin'];
+  'polySigma', 'flags', 'numThreads', 'regions', 'residual', 'residualMin', 'shift'];
 
 function getArgs(argv) {
   var positional = [], options = {};

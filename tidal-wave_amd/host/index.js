@@ -7,7 +7,9 @@
 // through calcIgnoring, every other pair through calc as before; and `regions` (1 .. 8), which create() hands to the engine with
 // the other engine options: every 'data' result then carries `regions` behind `vector`, and every vector its `region`;
 // `residual` (1 .. 254) and `residualMin` likewise: every 'data' result then carries `change`, the cells with a pixel that
-// differs by more than `residual` gray levels, and a pair with at least `residualMin` unexplained pixels is SUSPICIOUS.
+// differs by more than `residual` gray levels, and a pair with at least `residualMin` unexplained pixels is SUSPICIOUS;
+// `shift` (1 .. 1024, the search radius in pixels): every pair's flow starts from its global integer shift, found and checked on the
+// device, and every 'data' result carries `shift: {x, y, applied}` behind the other keys.  `status` is unchanged by it.
 'use strict';
 var EventEmitter = require('events').EventEmitter,
   TidalWave = require('./build/Release/tidalwave').TidalWave,

@@ -69,6 +69,8 @@ struct tw_engine {
     std::map<tw_ticket, int> gap_of;       // ticket -> the option's value when the pair was submitted (0: off)
     int residual = 0;                      // TW_OPT_RESIDUAL as tw_set_option left it
     std::map<tw_ticket, int> tol_of;       // ticket -> that option's value when the pair was submitted (0: off)
+    int shift = 0;                         // TW_OPT_SHIFT as tw_set_option left it
+    std::map<tw_ticket, tw_shift> shift_of;  // ticket -> the pair's record, computed when it was submitted with the option on
     std::string err;
     tw_ticket next = 1;
     int submit_calls = 0, busy_at = 0;  // TW_STUB_BUSY_AT
@@ -290,6 +292,13 @@ tw_status tw_set_option(tw_engine* e, int option, int value)
             e->residual = value;
         }
     }
+    if (option == TW_OPT_SHIFT) {
+        if (value < 0 || value > 1024) r = TW_E_BAD_PARAMETER;
+        else if (e) {
+            std::lock_guard<std::mutex> lk(e->m);
+            e->shift = value;
+        }
+    }
     if (tracing()) trace(e, "tw_set_option option=%d value=%d -> %s", option, value, status_name(r));
     return r;
 }
@@ -352,16 +361,69 @@ void tw_engine_destroy(tw_engine* e)
 }
 }  // extern "C"
 
-// What the entry points do once a call is recorded (and not refused by TW_STUB_BUSY_AT): they call one another through these
-static tw_status stub_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w, int h, tw_ticket* t)
+// TW_OPT_SHIFT on the CPU, the definition of include/twflow.h restated: the profiles, the search of one axis, the acceptance
+// check.  Plain loops: the stub is where the host tests run, not a fast path.
+static int stub_shift_search(const std::vector<uint32_t>& pE, const std::vector<uint32_t>& pT, int R)
+{
+    const int L = (int)pE.size(), r = std::min(R, L / 2);
+    int best = 0;
+    uint64_t bc = 0, bn = 0;
+    for (int k = 0; k <= 2 * r; k++) {
+        const int d = (k & 1) ? -((k + 1) / 2) : k / 2;  // 0, -1, +1, -2, +2, ...
+        uint64_t c = 0;
+        for (int i = std::max(0, -d); i < std::min(L, L - d); i++) c += pE[i] > pT[i + d] ? pE[i] - pT[i + d] : pT[i + d] - pE[i];
+        const uint64_t n = (uint64_t)(L - abs(d));
+        if (k == 0 || c * bn < bc * n) best = d, bc = c, bn = n;
+    }
+    return best;
+}
+static uint64_t stub_shift_sad(const uint8_t* a, const uint8_t* b, int w, int h, ptrdiff_t stride, int dx, int dy)
+{
+    uint64_t s = 0;
+    for (int y = std::max(0, -dy); y < std::min(h, h - dy); y++)
+        for (int x = std::max(0, -dx); x < std::min(w, w - dx); x++)
+            s += (uint64_t)abs((int)a[y * stride + x] - (int)b[(y + dy) * stride + (x + dx)]);
+    return s;
+}
+static tw_shift stub_shift(const uint8_t* a, const uint8_t* b, int w, int h, ptrdiff_t stride, int R)
+{
+    std::vector<uint32_t> colE(w, 0), colT(w, 0), rowE(h, 0), rowT(h, 0);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            colE[x] += a[y * stride + x];
+            rowE[y] += a[y * stride + x];
+            colT[x] += b[y * stride + x];
+            rowT[y] += b[y * stride + x];
+        }
+    tw_shift s;
+    memset(&s, 0, sizeof(s));
+    s.dx = stub_shift_search(colE, colT, R);
+    s.dy = stub_shift_search(rowE, rowT, R);
+    s.n_zero = w * h;
+    s.sad_zero = stub_shift_sad(a, b, w, h, stride, 0, 0);
+    s.n_shift = (w - abs(s.dx)) * (h - abs(s.dy));
+    s.sad_shift = stub_shift_sad(a, b, w, h, stride, s.dx, s.dy);
+    if (s.dx != 0 || s.dy != 0) s.applied = s.sad_shift * (uint64_t)s.n_zero <= (s.sad_zero >> 1) * (uint64_t)s.n_shift ? 1 : 0;
+    return s;
+}
+
+// What the entry points do once a call is recorded (and not refused by TW_STUB_BUSY_AT): they call one another through these.
+// stride > 0: a and b are whole images of w x h bytes (tw_submit_u8); 0: only their first bytes are there (every other
+// entry point hands on a pair's first pixels), and a shift record is then that of the 1 x 1 pair of those two bytes
+static tw_status stub_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w, int h, tw_ticket* t, ptrdiff_t stride = 0)
 {
     if (!a || !b || w < 1 || h < 1) return TW_E_BAD_PARAMETER;
+    if (stride && stride < w) return TW_E_BAD_PARAMETER;
     std::lock_guard<std::mutex> lk(e->m);
+    const int radius = e->shift;
+    tw_shift sh;
+    if (radius) sh = stride ? stub_shift(a, b, w, h, stride, radius) : stub_shift(a, b, 1, 1, 1, radius);
     *t = e->next++;
     e->open[*t] = w + (a[0] != b[0] ? 1000000 : 0);
     e->info[*t] = tw_engine::PairInfo{w, h, {a[0], b[0]}};
     if (e->regions) e->gap_of[*t] = e->regions;
     if (e->residual) e->tol_of[*t] = e->residual;
+    if (radius) e->shift_of[*t] = sh;
     if (e->batch_ms > 0) {
         e->batch_of[*t] = e->cur_batch;
         if (++e->cur_count >= e->cap) e->launch_locked();  // a full batch starts by itself, like the engine's
@@ -476,7 +538,7 @@ static void trace_submit(tw_engine* e, const char* name, const std::string& imag
 tw_status tw_submit_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w, int h, ptrdiff_t stride, int span, double thr,
                        tw_ticket* t)
 {
-    const tw_status r = STUB_SUBMIT(stub_u8(e, a, b, w, h, t));
+    const tw_status r = STUB_SUBMIT(stub_u8(e, a, b, w, h, t, stride));
     if (tracing()) {
         char sz[64];
         snprintf(sz, sizeof(sz), "[%dx%d stride=%td ", w, h, stride);  // (one size and stride for both images)
@@ -758,6 +820,7 @@ static tw_status stub_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, i
         e->info.erase(t);
         e->gap_of.erase(t);
         e->tol_of.erase(t);
+        e->shift_of.erase(t);
     }
     if (e->batch_ms > 0) {
         stub_clock::time_point until;
@@ -887,6 +950,22 @@ tw_status tw_ticket_changes(tw_engine* e, tw_ticket t, tw_change* changes, int c
         if (changes && change_cap > 0) changes[0] = rec;
     }
     if (tracing()) trace(e, "tw_ticket_changes ticket=%lld cap=%d -> %s", (long long)t, change_cap, status_name(r));
+    return r;
+}
+// The shift record of a pair that was submitted with TW_OPT_SHIFT on; the ticket is not consumed.  The definition of
+// include/twflow.h computed on the CPU when the pair was submitted (stub_shift) — on the whole images where the entry point
+// has them (tw_submit_u8), on the pair's first pixels otherwise.  The stub computes no flow, so nothing starts from the shift.
+tw_status tw_ticket_shift(tw_engine* e, tw_ticket t, tw_shift* out)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    tw_status r = TW_OK;
+    {
+        std::lock_guard<std::mutex> lk(e->m);
+        auto it = e->shift_of.find(t);
+        if (!out || it == e->shift_of.end() || e->open.find(t) == e->open.end()) r = TW_E_BAD_PARAMETER;
+        else *out = it->second;
+    }
+    if (tracing()) trace(e, "tw_ticket_shift ticket=%lld -> %s", (long long)t, status_name(r));
     return r;
 }
 }

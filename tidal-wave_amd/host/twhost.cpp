@@ -37,6 +37,7 @@
 #pragma weak tw_submit_image_jpeg_ignore
 #pragma weak tw_wait_regions
 #pragma weak tw_ticket_changes
+#pragma weak tw_ticket_shift
 
 namespace twhost {
 
@@ -1076,6 +1077,8 @@ struct ConsumerRun {
     // tw_ticket_changes' scratch array
     int residual_tol = 0, residual_min = 0;
     std::vector<tw_change> change_recs;
+    // shift (ConsumerShared::shift; 0: off): the search radius the engine was given
+    int shift_radius = 0;
     std::vector<int> region_of;
     std::vector<tw_region> region_recs;
     // Resident expected images (Parameter::residentMB / TW_RESIDENT_MB; 0, the default: off, and no step below reaches the
@@ -1177,6 +1180,18 @@ struct ConsumerRun {
                 tw_engine_destroy(eng);
                 eng = nullptr;
                 residual_tol = regions_gap = 0;
+            }
+        }
+        // Shift (Parameter::shift): as the residual — the option once, here; then tw_ticket_shift before each collecting wait.
+        // Off: neither call is made.  An asked-for shift is never silently dropped either.
+        shift_radius = eng && shared ? shared->shift : 0;
+        if (shift_radius) {
+            const tw_status r = tw_ticket_shift ? tw_set_option(eng, TW_OPT_SHIFT, shift_radius) : TW_E_UNSUPPORTED;
+            if (r != TW_OK) {
+                eng_err = std::string("engine: shift: ") + tw_strerror(r);
+                tw_engine_destroy(eng);
+                eng = nullptr;
+                shift_radius = residual_tol = regions_gap = 0;
             }
         }
         prof = eng && shared && shared->profile;
@@ -1657,6 +1672,12 @@ struct ConsumerRun {
                 rc = tw_ticket_changes(eng, s.ticket, change_recs.data(), cap, &nchg);
                 if (rc != TW_OK) chg_err = engine_error(eng, rc);
             }
+            // ... and the pair's shift, likewise
+            tw_shift shift_rec;
+            if (shift_radius && rc == TW_OK) {
+                rc = tw_ticket_shift(eng, s.ticket, &shift_rec);
+                if (rc != TW_OK) chg_err = engine_error(eng, rc);
+            }
             tw_status r = regions_gap ? tw_wait_regions(eng, s.ticket, v, cap, &n, region_of.data(), region_recs.data(),
                                                         TW_MAX_REGIONS, &nreg, &sec)
                                       : tw_wait(eng, s.ticket, v, cap, &n, &sec);
@@ -1683,6 +1704,11 @@ struct ConsumerRun {
                     out.hasChanges = true;
                     out.changes.assign(change_recs.begin(), change_recs.begin() + std::max(0, std::min(nchg, cap)));
                 }
+                if (shift_radius) {
+                    out.hasShift = true;
+                    out.shift = Shift{shift_rec.dx, shift_rec.dy, shift_rec.applied != 0};
+                }
+                // (the shift leaves the status alone: a moved page has vectors above the threshold and is SUSPICIOUS as ever)
                 out.status = pair_status(out.vectors.size(), out.changes, residual_min);  // src/consumer.cpp:77
                 out.time = sec;
                 out.expect_image = s.req.expect_image;
@@ -1796,6 +1822,7 @@ void Manager::start(const Parameter& p)
     shared_.regions = p.regions;
     shared_.residual = p.residual;
     shared_.residualMin = p.residualMin;
+    shared_.shift = p.shift;
     shared_.stats.assign((size_t)n, ConsumerStats());
     for (int i = 0; i < n; i++) {
         consumers_.push_back(new Consumer(i, requestQueue_, responseQueue_, p.optParam, batch, dec, n, &shared_));

@@ -47,8 +47,17 @@ struct Vector {
 using Region = tw_region;
 // A cell of a pair's span grid with a differing pixel (tw_change of include/twflow.h)
 using Change = tw_change;
+// A pair's estimated global translation (tw_shift of include/twflow.h): the two searches' answers, and whether the pair's flow
+// started from them
+struct Shift {
+    int x = 0, y = 0;
+    bool applied = false;
+};
 struct Response {
     std::vector<Vector> vectors;
+    // not in the reference (Parameter::shift > 0 only): the pair's integer translation, estimated and checked on the device
+    Shift shift;
+    bool hasShift = false;
     // not in the reference (Parameter::residual > 0 only; empty otherwise): the cells with a pixel that differs by more than
     // the tolerance, each with the number of such pixels the pair's flow does not explain
     std::vector<Change> changes;
@@ -103,6 +112,10 @@ struct Parameter {
     // SUSPICIOUS even without a vector — a flat repaint moves nothing
     int residual = 0;
     int residualMin = 0;
+    // not in the reference: start every pair's flow from its global integer shift, found on the device (the engine option
+    // TW_OPT_SHIFT) — 0: off, the calls a consumer makes are exactly the ones it made before; 1 .. 1024: the search radius in
+    // pixels.  Response::status is unchanged by it
+    int shift = 0;
 };
 // Response::status of an answered pair: the reference's rule (src/consumer.cpp:77), and Parameter::residualMin's
 inline const char* pair_status(size_t nvectors, const std::vector<Change>& changes, int residualMin)
@@ -265,6 +278,7 @@ struct ConsumerShared {
     int regions = 0;              // Parameter::regions: a consumer sets TW_OPT_REGIONS once and collects with tw_wait_regions
     int residual = 0;             // Parameter::residual: a consumer sets TW_OPT_RESIDUAL once and asks tw_ticket_changes before each collecting wait
     int residualMin = 0;          // Parameter::residualMin
+    int shift = 0;                // Parameter::shift: a consumer sets TW_OPT_SHIFT once and asks tw_ticket_shift before each collecting wait
 };
 
 class Consumer {

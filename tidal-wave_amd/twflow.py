@@ -69,6 +69,15 @@ class Change(C.Structure):
         return (self.x, self.y, self.n_diff, self.n_unexplained, self.max_diff, self.max_unexplained)
 
 
+class Shift(C.Structure):
+    # tw_shift (include/twflow.h): a pair's estimated translation and its acceptance check (TW_OPT_SHIFT / tw_ticket_shift), 40 bytes
+    _fields_ = [("dx", C.c_int), ("dy", C.c_int), ("applied", C.c_int), ("n_shift", C.c_int), ("n_zero", C.c_int),
+                ("sad_shift", C.c_uint64), ("sad_zero", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.dx, self.dy, self.applied, self.n_shift, self.n_zero, self.sad_shift, self.sad_zero)
+
+
 MAX_IGNORE = 32
 MAX_REGIONS = 256
 FLOW_PLANAR, FLOW_INTERLEAVED = 0, 1
@@ -90,6 +99,7 @@ OPT_SCAN_FUSED_FINAL = 1
 OPT_POLYEXP_F32 = 2
 OPT_REGIONS = 3
 OPT_RESIDUAL = 4
+OPT_SHIFT = 5
 
 SYMBOLS = [
     "tw_default_params", "tw_abi_version", "tw_has_variants", "tw_device_count", "tw_device_pci_bus_id", "tw_engine_create", "tw_engine_destroy", "tw_strerror",
@@ -109,6 +119,7 @@ SYMBOLS = [
     "tw_stage_flow_iter_grid", "tw_stage_span_scan",
     "tw_wait_regions", "tw_stage_hit_regions",
     "tw_ticket_changes", "tw_stage_warp_residual",
+    "tw_ticket_shift", "tw_stage_shift", "tw_debug_shift_plan",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
     "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time", "tw_debug_scan_plan", "tw_debug_level_plan",
@@ -294,6 +305,10 @@ def _bind(path):
     L.tw_ticket_changes.argtypes = [vp, C.c_int64, C.POINTER(Change), C.c_int, ip]
     L.tw_stage_warp_residual.argtypes = [vp, u8p, u8p, C.c_ssize_t, C.c_int, C.c_int, fp, C.c_int, C.c_int, ip, ip,
                                          C.POINTER(Change)]
+    L.tw_ticket_shift.argtypes = [vp, C.c_int64, C.POINTER(Shift)]
+    L.tw_stage_shift.argtypes = [vp, u8p, u8p, C.c_ssize_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                 C.POINTER(Shift)]
+    L.tw_debug_shift_plan.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
     L.tw_level_chunk.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -360,6 +375,7 @@ def _bind(path):
 
 
 FlowIterPlan = collections.namedtuple("FlowIterPlan", "strips segments nt nt_last")
+ShiftPlan = collections.namedtuple("ShiftPlan", "lds_x lds_y rx ry grid_x block lds_budget prof_grid_x prof_grid_y verify_grid_x")
 BlurPlan = collections.namedtuple("BlurPlan", "family block tile_cols rows xsh grid_x grid_y small forced")
 PYR_KERNELS = ("tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level_lds", "tw_pyr_level")
 PyrPlan = collections.namedtuple("PyrPlan", "kernel targ family block tile_cols rows grid_x grid_y lds pitch aligned4 w h ksize mode xmax "
@@ -930,6 +946,18 @@ class Engine:
         self._check(self._L.tw_ticket_changes(self._h, tk, out, cap, C.byref(n)))
         return [out[i].as_tuple() for i in range(max(0, min(n.value, cap)))], n.value
 
+    def set_shift(self, radius):
+        """TW_OPT_SHIFT: 0 turns the shift estimation off (the default), 1 .. 1024 is the search radius in pixels; batches
+        opened from now on take it."""
+        self.set_option(OPT_SHIFT, radius)
+
+    def shift(self, ticket):
+        """tw_ticket_shift, before the wait that collects the ticket: the pair's Shift.as_tuple() — (dx, dy, applied, n_shift,
+        n_zero, sad_shift, sad_zero)."""
+        out = Shift()
+        self._check(self._L.tw_ticket_shift(self._h, ticket[0], C.byref(out)))
+        return out.as_tuple()
+
     def wait_count(self, ticket):
         """tw_wait without materialising the vectors (bench inner loop). Returns (n, seconds)."""
         tk = ticket[0]
@@ -1038,13 +1066,14 @@ class Engine:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_scan_plan(%d, %d, %d, %d) returned %d" % (w, h, span, npairs, n))
         return ScanPlan(("tw_span_scan", "tw_span_scan_seg")[v[0]], *v[1:7])
 
-    def level_plan(self, w, h, span, npairs, any_fout=False, any_init=False, prof_on=False, residual=False):
+    def level_plan(self, w, h, span, npairs, any_fout=False, any_init=False, prof_on=False, residual=False, shift=False):
         """What a batch of npairs pairs of w x h pixels at `span` launches for each pyramid level, from the function the
         enqueue itself executes (twflow_debug.h: tw_debug_level_plan): a LevelPlanView whose `parts` (a lane's share of the
         batch each) hold one LevelPlanRow per level, level 0 first."""
         cap = 8 + 2 * 61 * 11
         v = (C.c_int * cap)()
-        traits = (1 if any_fout else 0) | (2 if any_init else 0) | (4 if prof_on else 0) | (16 if residual else 0)
+        # (a batch opened with TW_OPT_SHIFT on takes the schedule a batch with an initial field takes)
+        traits = (1 if any_fout else 0) | (2 if any_init or shift else 0) | (4 if prof_on else 0) | (16 if residual else 0)
         n = self._L.tw_debug_level_plan(self._h, w, h, int(span), npairs, traits, v, cap)
         if n < 8 or v[7] != 11 or n != 8 + v[6] * (v[2] + 1) * 11:
             raise TwError(TW_E_BAD_PARAMETER, "tw_debug_level_plan(%d, %d, %d, %d) returned %d" % (w, h, span, npairs, n))
@@ -1217,6 +1246,38 @@ class Engine:
                                                    _f(flow2), int(span), int(tol), cells.ctypes.data_as(ip), C.byref(n),
                                                    chg.ctypes.data_as(C.POINTER(Change))))
         return cells, n.value, chg
+
+    def stage_shift(self, expect, target, radius, stride=None, force_global=False, pad=0xEE):
+        """tw_shift_profiles, tw_shift_search and tw_shift_verify alone: expect / target (h, w) uint8 — with `stride` both are
+        copied into rows that far apart first, the padding filled with `pad`.  (profiles: (colE [w], colT [w], rowE [h], rowT [h])
+        uint32, the record as Shift.as_tuple()).  The call itself answers a device error when a launch wrote beyond the pair's
+        share of the 0xff-filled outputs."""
+        expect = np.ascontiguousarray(expect, np.uint8)
+        target = np.ascontiguousarray(target, np.uint8)
+        h, w = expect.shape
+        assert target.shape == (h, w)
+        if stride is None:
+            stride = w
+        else:
+            pe = np.full((h, stride), pad, np.uint8)
+            pt = np.full((h, stride), pad, np.uint8)
+            pe[:, :w] = expect
+            pt[:, :w] = target
+            expect, target = pe, pt
+        prof = np.zeros(2 * (w + h), np.uint32)
+        out = Shift()
+        u8p = C.POINTER(C.c_uint8)
+        self._check(self._L.tw_stage_shift(self._h, expect.ctypes.data_as(u8p), target.ctypes.data_as(u8p), stride, w, h,
+                                           int(radius), int(bool(force_global)), prof.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                           C.byref(out)))
+        return (prof[:w], prof[w:2 * w], prof[2 * w:2 * w + h], prof[2 * w + h:]), out.as_tuple()
+
+    def shift_plan(self, w, h, radius):
+        """How tw_shift_search runs for a w x h pair at `radius` (twflow_debug.h: tw_debug_shift_plan), a pure host function."""
+        v = (C.c_int * 10)()
+        if self._L.tw_debug_shift_plan(int(w), int(h), int(radius), v, 10) != 10:
+            raise ValueError("no shift plan for %dx%d at radius %d" % (w, h, radius))
+        return ShiftPlan(bool(v[0]), bool(v[1]), *v[2:10])
 
     def stage_hit_regions(self, fields, span, threshold, gap, ignore=None):
         """tw_hit_regions alone behind the gather and the ordered scan on `fields` (npairs, 2, h, w); ignore: per pair a

@@ -10,6 +10,8 @@
 //     I <x,y,w,h[;x,y,w,h ...]>              ignore rectangles of the NEXT pair (Request::ignore)
 //     D <tol> <min>                          residual for the whole run (ConsumerShared::residual, ::residualMin); a response then
 //                                            ends in " changes <count>: [x,y diff=<n> unexplained=<n> max=<diff>,<unexplained>] ..."
+//     S <radius>                             shift for the whole run (ConsumerShared::shift); a response then ends in
+//                                            " shift <x>,<y> applied=<0|1>"
 //     G <gap>                                hit regions for the whole run (ConsumerShared::regions); a response then ends in
 //                                            " regions <count>: [x,y,w,h n=<hits> peak=(x,y,dx,dy)] ... of: <index per vector>"
 #include <stdio.h>
@@ -49,6 +51,10 @@ int main(int argc, char** argv)
         if (op == "D" && i + 2 < argc) {
             shared.residual = atoi(argv[++i]);
             shared.residualMin = atoi(argv[++i]);
+            continue;
+        }
+        if (op == "S" && i + 1 < argc) {
+            shared.shift = atoi(argv[++i]);
             continue;
         }
         if (op == "I" && i + 1 < argc) {
@@ -113,6 +119,7 @@ int main(int argc, char** argv)
                 for (const Change& c : r.changes)
                     printf(" [%d,%d diff=%d unexplained=%d max=%d,%d]", c.x, c.y, c.n_diff, c.n_unexplained, c.max_diff, c.max_unexplained);
             }
+            if (r.hasShift) printf(" shift %d,%d applied=%d", r.shift.x, r.shift.y, r.shift.applied ? 1 : 0);
             printf("\n");
         }
         req.stop();

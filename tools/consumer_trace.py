@@ -162,6 +162,12 @@ def with_residual(case, tol, minimum=0):
     return env, budget, ["D", tol, minimum] + list(script)
 
 
+def with_shift(case, radius):
+    """the case with the shift on for the whole run (the probe's S: ConsumerShared::shift)"""
+    env, budget, script = case
+    return env, budget, ["S", radius] + list(script)
+
+
 def run_case(exe, case, threads, workdir, batch=4):
     """(responses as printed, the trace's text) of one case; every path under `workdir` or the tree reads <dir> / <root>"""
     env_more, budget, script = case
