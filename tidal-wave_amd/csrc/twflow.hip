@@ -6109,6 +6109,13 @@ extern "C" tw_status tw_bench_stage(tw_engine* e, int kclass, int width, int hei
                         ups = FlowUps{pf, Pv.w, Pv.h, Pv.ld, Pv.ps, L.d_uxofs, L.d_uyofs, L.d_ualpha, L.d_ubeta, L.uxmax,
                                       (float)(1. / e->cfg.p.pyrScale)};
                     }
+                    if ((flags & 20) == 20) {
+                        // flags 4 + 16: the grid-only iteration (tw_flow_iter's MODE 3) at span 10, samples into the scan's grid
+                        const FlowIterGrid gp{grid, span, (L.w + span - 1) / span, (L.h + span - 1) / span};
+                        if (level != 0) return TW_E_UNSUPPORTED;
+                        launch_flow_iter(e, st, L.w, L.h, L.ld, L.ps, R, fl, L.ps, nullptr, L.ps, nullptr, npairs, level, nullptr, &gp);
+                        break;
+                    }
                     launch_flow_iter(e, st, L.w, L.h, L.ld, L.ps, R, up ? nullptr : fl, L.ps, M1, L.ps, up ? &ups : nullptr,
                                      npairs, level);
                     break;

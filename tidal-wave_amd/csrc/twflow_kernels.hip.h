@@ -2292,6 +2292,19 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         {TW_FI_P(0, 0), TW_FI_P(0, 0), TW_FI_P(0, 1), TW_FI_P(0, 2), TW_FI_P(0, 3), TW_FI_P(0, 4), TW_FI_P(1, 0), TW_FI_P(1, 1), TW_FI_P(1, 2), TW_FI_P(1, 3),
          TW_FI_P(2, 1), TW_FI_P(2, 1), TW_FI_P(2, 1), TW_FI_P(2, 1), TW_FI_P(2, 1)},
     };
+    // MODE 3 (the grid-only iteration; step_grid below): its step has next to no arithmetic between a load and its use, so
+    // what the combine reads must have been issued a step earlier, R0 like the taps.  TW_FI_GDIST picks a preset (A/B builds):
+    //   0  one R0 set, loaded at the head of the step whose combine reads it (the schedule of profiles/grid_final.md)
+    //   1  two R0 sets that swap roles from step to step like the tap sets; the next chunk's five planes at the head of the step
+    //   2  the same, the five planes behind the combine (where MODE 1's UDIST preset 1 has them)
+    // Level 0 of 1080p, 128 pairs per launch, us per pair (profiles/grid_ahead.md): preset 0 27.9, 1 24.4, 2 23.8; the launch's
+    // loads alone 23.7.  (The input flow a step ahead as well — two flow variables that swap roles — measured 24.9 on top of
+    // preset 1 and 23.7 on top of preset 2, inside the lease's spread, and is not kept.)
+#ifndef TW_FI_GDIST
+#define TW_FI_GDIST 2
+#endif
+    static_assert(TW_FI_GDIST >= 0 && TW_FI_GDIST <= 2, "TW_FI_GDIST: presets 0 .. 2");
+    constexpr bool G_R0_AHEAD = TW_FI_GDIST != 0, G_R0_LATE = TW_FI_GDIST == 2;
     constexpr int TH = FI_TH, SC = NT == 1024 ? FI_SC : FI_SC_512, P = NT == 1024 ? FI_PITCH : FI_PITCH_512, OUT = SC - 2 * MH,
                   RING = TH + 2 * MH, NCH = RING / TH, NB = NCH + 1;
     static_assert(RING % TH == 0 && SC <= P && TH * SC <= NT && TH == 5 && OUT % 4 == 0 && 5 * TH * (OUT / 4) <= NT && (NB & (NB - 1)) == 0, "geometry");
@@ -2490,7 +2503,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             flow_issue(NCH + 1, f2);
             ytab_issue(NCH + 2);
             flow_value(fnext, dx, dy);
-            gather_head(NCH, dx, dy, q, T, false);
+            // (MODE 3 with R0 a step ahead: chunk NCH's R0 goes out here, into the set step 0 combines from)
+            if constexpr (MODE == 3 && G_R0_AHEAD) gather_head(NCH, dx, dy, q, T, true);
+            else gather_head(NCH, dx, dy, q, T, false);
 #pragma unroll
             for (int ch = 0; ch < 5; ch++) gather_plane(ch, T);
             flow_value(f2, dxb, dyb);
@@ -2516,8 +2531,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         //                  into block Y;  barrier;  S: wave 15, one lane per grid column, the 2x2 solve in double and the
         //                  float2 store into the grid — beside C on the other waves;  barrier
         //   any other step C;  barrier
-        // Every value is the expression of MODE 0's V, H and S in their order.  The step's loads go out in three groups (before V,
-        // H and C): there is no arithmetic left that a burst of them could starve.
+        // Every value is the expression of MODE 0's V, H and S in their order.  The step's loads go out in groups (before V, H
+        // and C, and with TW_FI_GDIST 2 the next chunk's R0 behind C): there is no arithmetic left that a burst of them could starve.
         static_assert(NT == 1024 && DEEP && SPLIT && OUT / FI_TH <= 32, "the grid-only iteration: 1024 threads, two tap sets, wave 15 free");
         const int span = a.span;
         // THE ONE PLACE that says which steps are grid steps: r* of step st (and its grid row gy), -1 for a step without one.
@@ -2543,7 +2558,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 if (grid_row(st, gy) >= 0) {
                     TW_FI_SYNC();  // (V)
                     TW_FI_SYNC();  // (H)
-                    if (sth) {
+                    if (sth && !TW_FI_SKIP(8)) {
                         const double g11 = blk[s0][0][0][gi], g12 = blk[s0][1][0][gi], g22 = blk[s0][2][0][gi],
                                      h1 = blk[s0][3][0][gi], h2 = blk[s0][4][0][gi];
                         const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
@@ -2572,24 +2587,39 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             blk[bX][cr][0][cc] = sv;
         };
         // One step; the registers' roles are step_deep's: (dxc, dyc, Tc) the chunk this step turns into M (st + NCH), its taps
-        // issued a step ago; Tn the chunk after it, its taps go out during this step; R0 of chunk st + NCH first of all (the
-        // combine waits for nothing younger), the flow of chunk st + NCH + 2 before it.
-        auto step_grid = [&](int st, float& dxc, float& dyc, UpdTaps& Tc, UpdTaps& Tn) {
+        // issued a step ago; Tn the chunk after it, its taps go out during this step.
+        // R0 (TW_FI_GDIST != 0): qc = the R0 planes of chunk st + NCH, issued a step ago (chunk NCH's by the prologue); qn = those
+        // of chunk st + NCH + 1, issued in this step — at its head or behind the combine.  The two sets swap roles from step to step
+        // as in `step` below: the loop is unrolled by two, the swap is a renaming.  In a step without a grid row nothing but the
+        // barrier lies between the head and the combine: with one set (preset 0: qc and qn are the same registers, R0 of chunk
+        // st + NCH first of all) every wave sat in s_waitcnt on loads it had just issued and the memory pipe ran empty.
+        // The flow of chunk st + NCH + 2 goes out first of all and becomes (dxc, dyc) at the end of the step: the one load the
+        // step still waits for, with the whole step between issue and use.
+        // All loads are unconditional: in a segment's last steps they fetch chunks nobody needs, row_of clamps them into the image.
+        // With TW_FI_GDIST != 0 they are unconditional for the lanes without a pixel as well (lth: the last 10 lanes of wave 14
+        // load what pixel (cr, cc) = (0, 0) loads and use none of it).  Under `if (cth)` each group of loads sits behind an
+        // s_cbranch_execz that no wave of this loop ever takes, and where the two paths join the compiler's s_waitcnt counting
+        // forgets the group: the combine then waited vmcnt(7) — for ten of the seventeen loads of its own step — on
+        // registers loaded a step before.  Only the LDS writes (V's row, the combine) keep their `if (cth)`.
+        const bool lth = G_R0_AHEAD || cth;
+        auto step_grid = [&](int st, float& dxc, float& dyc, UpdTaps& Tc, UpdTaps& Tn, float (&qc)[5], float (&qn)[5]) {
             const bool more = st + 1 < nsteps;
             const int s0 = st & (NB - 1), bX = (st + NCH) & (NB - 1);
             int gy;
             const int rs = grid_row(st, gy);
-            if (cth) {
+            if (lth) {
                 flow_issue(st + NCH + 2, fnext);
-                gq = (unsigned)(row_of(st + NCH) * a.ld + xc) * 4u;
+                if constexpr (!G_R0_LATE) {
+                    gq = (unsigned)(row_of(st + NCH + (G_R0_AHEAD ? 1 : 0)) * a.ld + xc) * 4u;
 #pragma unroll
-                for (int ch = 0; ch < 5; ch++) gather_r0(ch, q);
+                    for (int ch = 0; ch < 5; ch++) gather_r0(ch, qn);
+                }
 #pragma unroll
                 for (int u = 0; u < 4; u++) gather_half(u >> 1, u & 1, Tn);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (rs >= 0) {
-                if (cth) {
+                if (cth && !TW_FI_SKIP(4)) {
                     switch (rs) {
                     case 0: v_row(std::integral_constant<int, 0>(), s0, bX); break;
                     case 1: v_row(std::integral_constant<int, 1>(), s0, bX); break;
@@ -2600,13 +2630,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 }
                 TW_FI_SYNC();  // (V)
             }
-            if (cth) {
+            if (lth) {
 #pragma unroll
                 for (int u = 4; u < 7; u++) gather_half(u >> 1, u & 1, Tn);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (rs >= 0) {
-                if (gth) {
+                if (gth && !TW_FI_SKIP(4)) {
                     const float* v = &blk[bX][gp][0][ghx + MH];
                     float sum = v[0] * c.k[0];
 #pragma unroll
@@ -2615,25 +2645,33 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 }
                 TW_FI_SYNC();  // (H)
             }
-            if (cth) {
+            if (lth) {
 #pragma unroll
                 for (int u = 7; u < 10; u++) gather_half(u >> 1, u & 1, Tn);
                 __builtin_amdgcn_sched_barrier(0);
-                if (more) combine_store(st + NCH, dxc, dyc, q, Tc);
+                if (more && cth && !TW_FI_SKIP(1)) combine_store(st + NCH, dxc, dyc, qc, Tc);
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (G_R0_LATE) {
+                    gq = (unsigned)(row_of(st + NCH + 1) * a.ld + xc) * 4u;
+#pragma unroll
+                    for (int ch = 0; ch < 5; ch++) gather_r0(ch, qn);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 flow_value(fnext, dxc, dyc);
-                gather_head(st + NCH + 2, dxc, dyc, q, Tc, false);
+                gather_head(st + NCH + 2, dxc, dyc, qn, Tc, false);
                 __builtin_amdgcn_sched_barrier(0);
             }
             TW_FI_SYNC();  // (C, S)
         };
+        float qb[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        float(&q2)[5] = G_R0_AHEAD ? qb : q;  // (preset 0: one R0 set in both roles)
         int st = 0;
 #pragma unroll 1
         for (; st + 1 < nsteps; st += 2) {
-            step_grid(st, dx, dy, T, Tb);
-            step_grid(st + 1, dxb, dyb, Tb, T);
+            step_grid(st, dx, dy, T, Tb, q, q2);
+            step_grid(st + 1, dxb, dyb, Tb, T, q2, q);
         }
-        if (st < nsteps) step_grid(st, dx, dy, T, Tb);
+        if (st < nsteps) step_grid(st, dx, dy, T, Tb, q, q2);
         return;
     }
 

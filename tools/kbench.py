@@ -32,7 +32,7 @@ def main():
                 if only_lv >= 0 and lv != only_lv:
                     continue
                 n = e.level_chunk(W, H, lv)
-                for flags in ((0, 2, 4, 8) if kc == T.K_BLUR_SOLVE else (0,)):
+                for flags in ((0, 2, 4, 8, 20) if kc == T.K_BLUR_SOLVE else (0,)):
                     if only_flags >= 0 and flags != only_flags:
                         continue
                     try:
@@ -47,7 +47,9 @@ def main():
                             b = 56 * w * h * n   # tw_flow_iter: flow 8 + R0 20 + R1 20 in, flow 8 out
                         if flags & 8:
                             b = 50 * w * h * n   # ... with the coarser level's flow (2 B/px) instead of this level's
-                    name = T.KERNEL_NAMES[kc] + ("(no refresh)" if flags & 2 else "(M-free)" if flags & 4 else
+                        if flags & 16:
+                            b = 48 * w * h * n   # the grid-only iteration (level 0, span 10): no flow out
+                    name = T.KERNEL_NAMES[kc] + ("(no refresh)" if flags & 2 else "(M-free grid)" if flags & 16 else "(M-free)" if flags & 4 else
                                                  "(M-free+ups)" if flags & 8 else "")
                     print("%-20s %5d %6d %10.1f %10.2f %8.0f" % (name[:20], lv, n, us, us / n, b / us / 1e3 if b else 0))
 
