@@ -483,6 +483,60 @@ typedef struct tw_shift {
 } tw_shift;              /* 40 bytes */
 tw_status tw_ticket_shift(tw_engine* e, tw_ticket ticket, tw_shift* out);
 
+/* Diff image (additive within ABI 4, detected by the symbols).  The engine answers a pair with lists of numbers; a user of a
+ * screenshot diff wants the page with the changes marked on it.  The gray images as the batch sees them — after tw_png_unfilter,
+ * tw_jpeg_idct, tw_resize_u8 and tw_mask_rects — exist only in device memory, and so do all hit records of a pair with more than
+ * the eagerly copied ones.  tw_ticket_overlay renders one pair's picture there, on request, after the batch has finished: a
+ * batch launches, copies and records exactly what it did before, no engine option turns anything on, and a caller who renders
+ * only the suspicious pairs pays nothing for the others.
+ * E, T are the pair's expected and target images as the batch sees them, w x h.  `rects` are the pair's ignore rectangles after
+ * clipping; `hits` are the vectors tw_wait would report for the pair (after the ignore rule) — ALL of them, in their float
+ * precision, not only the ones a small `cap` would take; `regions` are the records tw_wait_regions would return (at most
+ * TW_MAX_REGIONS boxes) when the batch was opened with TW_OPT_REGIONS on, none otherwise; tol is 0 .. 255.  All arithmetic is
+ * integer after one float -> int conversion per vector component, and every layer has one colour, so the result does not
+ * depend on the order of evaluation.  Colours are (r, g, b):
+ *   base, every pixel (x, y):  e = E[y][x], t = T[y][x], d = |e - t|, g = 128 + (t >> 1)
+ *       inside a clipped ignore rectangle      (g - 48, g - 48, g)
+ *       else d > tol                           (255, 192 - (d >> 1), 0)
+ *       else                                   (g, g, g)
+ *   boxes (over base): the one-pixel outline of every region's box [x, x+width) x [y, y+height)   (0, 160, 0)
+ *       (a box of width 1 or height 1 is a line, a box without area draws nothing)
+ *   vectors (over boxes): for every hit (x, y, dx, dy)                                            (0, 0, 255)
+ *       q(v) = 0 when v is NaN, else (int) round-half-even of min(max(v, -1024.f), 1024.f)
+ *       rx = q(dx), ry = q(dy), n = max(|rx|, |ry|)
+ *       marker: the 3 x 3 square centred on (x, y)
+ *       line:   for i = 0 .. n:  (x + floor((2*i*rx + n) / (2*n)), y + floor((2*i*ry + n) / (2*n)))     (n = 0: the origin only)
+ *   pixels outside the image are dropped (of a box, a marker and a line alike)
+ * The priority is vectors over boxes over base.  TW_OVERLAY_MAX_LEN is the clamp of q: a line has at most 1025 pixels.
+ * Kernels: tw_overlay_base (2 bytes in, 3 bytes out per pixel), then tw_overlay_marks once for the boxes and once for the
+ * vectors, in stream order — on the engine's device-to-host stream, where the call does not queue behind later batches.
+ *
+ * tw_ticket_hits and tw_ticket_overlay follow tw_ticket_changes' contract: valid from the submit that returned the ticket until
+ * the wait that collects it; they launch the open batch if they have to, as tw_wait does, and wait for the batch; they do NOT
+ * consume the ticket; an unknown or already waited ticket answers TW_E_BAD_PARAMETER; errors of the pair itself (a palette
+ * index: TW_E_BAD_IMAGE_FORMAT; the device) are answered as tw_wait answers them, and the ticket stays waitable.  Both work
+ * on every batch, whatever options it was opened with.  A batch with span 0 has no hits: *n = 0, the image is the base.
+ * tw_ticket_hits: *n receives the TRUE count tw_wait would put into its *n.
+ * tw_ticket_overlay is synchronous: when it returns TW_OK the image is in out->data, `height` rows of 3 * width bytes,
+ * out->pitch bytes apart.  pitch >= 3 * width, any value (odd ones too); bytes of the pitch behind a row are never written.
+ * out->data is device memory of the engine's device that holds the whole image (written in place), a page-locked host block
+ * the library knows (tw_host_alloc / tw_host_register: written by DMA), or any other host memory (through the engine's
+ * page-locked bounce buffer: the runtime is never handed a pageable pointer).  Host destinations are rendered into a device
+ * staging buffer of the engine's, created by the first such call and kept until tw_engine_destroy.  Refused with
+ * TW_E_BAD_PARAMETER before anything is launched: a null out or data, a pitch below 3 * width, an unknown format, tol
+ * outside 0 .. 255, device memory of another device or one that does not hold the image.  Calling it twice for one ticket
+ * gives the same bytes.  The images of a tw_submit_dev* pair are the caller's: the caller keeps them valid and unchanged
+ * until the call returns (a device target that tw_resize_u8 reconciled lives in engine memory and needs nothing). */
+#define TW_OVERLAY_MAX_LEN 1024
+enum { TW_OVERLAY_RGB8 = 0 }; /* r, g, b bytes per pixel */
+typedef struct tw_overlay_out {
+    void* data;      /* device memory of the engine's device, or host memory */
+    ptrdiff_t pitch; /* bytes between rows; >= 3 * width */
+    int format;      /* TW_OVERLAY_RGB8 */
+} tw_overlay_out;
+tw_status tw_ticket_hits(tw_engine* e, tw_ticket ticket, int* n);
+tw_status tw_ticket_overlay(tw_engine* e, tw_ticket ticket, int tol, const tw_overlay_out* out);
+
 /* Number of grid points ceil(h/span)*ceil(w/span): the capacity that can never overflow. */
 int tw_grid_capacity(int width, int height, int span);
 

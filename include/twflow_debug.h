@@ -66,6 +66,9 @@ enum tw_debug_family {
     TW_DF_PNG_UNFILTER,
     TW_DF_SPAN_SCAN_SEG,   /* tw_span_scan_seg: a single pair's ordered scan in 16 independent segments (round 6) */
     TW_DF_BLUR_SOLVE4Q,    /* tw_blur_solve4q: solve + refresh by the horizontal item's owner — a single pair's level-0 launches (round 6) */
+    TW_DF_OVERLAY_BASE,    /* tw_overlay_base: one pair's diff image, the base layer (tw_ticket_overlay) */
+    TW_DF_OVERLAY_MARKS,   /* tw_overlay_marks<0> the region boxes, <1> the vectors: one launch each, only when the pair has any (both in
+                            * front of TW_DF_PYR_LEVEL_LDS for the reason it stands here itself: no pinned neighbourhood moves) */
     TW_DF_PYR_LEVEL_LDS,   /* tw_pyr_level_lds: the generic level with its source region staged in LDS — ALSO counted in TW_DF_PYR_LEVEL.
                             * (Here and not at the end: the enum's tail from TW_DF_HIT_REGIONS on is pinned by the tests of the features that added it) */
     TW_DF_SHIFT_PROFILES,  /* tw_shift_profiles: a batch part's row and column sums of both images (TW_OPT_SHIFT) */
@@ -169,6 +172,32 @@ int tw_debug_level_plan(const tw_engine* e, int width, int height, int span, int
  * the lengths above the LDS limit from it. */
 int tw_debug_shift_plan(int width, int height, int radius, int* out, int n);
 
+/* How tw_overlay_base runs for a width x height pair whose images lie at the addresses `expect` and `target` with rows `stride`
+ * bytes apart, into a destination at the address `dst` with rows `pitch` bytes apart — a pure function of its arguments (no
+ * engine, no device), the one the launch itself asks (choose_overlay): out[0] 1 when a lane loads one dword of each image and
+ * stores three (all three addresses, the stride and the pitch are multiples of 4), 0 for the byte path; out[1] pixels per lane,
+ * out[2] threads per workgroup, out[3] grid x, out[4] grid y.  Returns the number of values written (at most min(n, 5); 0 for
+ * a null `out` or a non-positive size).  tests/test_gpu_overlay.py proves from it that both paths ran. */
+int tw_debug_overlay_plan(unsigned long long expect, unsigned long long target, long long stride, unsigned long long dst,
+                          long long pitch, int width, int height, int* out, int n);
+
+/* A hit record as the ordered scan leaves it in device memory: what tw_stage_overlay takes. */
+typedef struct tw_overlay_hit {
+    int x, y;
+    float dx, dy;
+} tw_overlay_hit;
+
+/* tw_overlay_base and tw_overlay_marks alone (include/twflow.h, "Diff image"), on host arrays: expect / target are height rows
+ * of `stride` bytes, uploaded to device addresses `misalign` (0 .. 3) bytes behind a 256-byte boundary, so that a test reaches
+ * the byte path; rects (n_rects <= TW_MAX_IGNORE) are clipped as a submit clips them; hits (n_hits >= 0, any values) and regions
+ * (n_regions <= TW_MAX_REGIONS) are drawn as the header says, a hit inside a clipped rectangle left out.  `out` holds height
+ * rows `pitch` bytes apart — pitch * height bytes, which go up before the launches and come back behind them, so the caller
+ * sees every byte the kernels did not write as it was.  *path (nullable) receives the base kernel's path as
+ * tw_debug_overlay_plan's out[0] names it.  The statuses of tw_ticket_overlay's argument check. */
+tw_status tw_stage_overlay(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height, ptrdiff_t stride,
+                           int misalign, const tw_rect* rects, int n_rects, const tw_overlay_hit* hits, int n_hits,
+                           const tw_region* regions, int n_regions, int tol, uint8_t* out, ptrdiff_t pitch, int* path);
+
 /* tw_pair_same's flags of the batch this engine enqueued last: out[j] = 1 where pair j's second image is byte for byte its
  * first over the visible width x height pixels (the batch schedule then computed that pair's polynomial expansions once at
  * the levels tw_flow_iter runs), 0 otherwise — and 0 for every pair of a batch that launched no tw_pair_same (TW_SAME_IMAGE=0,
@@ -186,7 +215,8 @@ tw_status tw_debug_png_kernel_time(tw_engine* e, const tw_png_rows* img, int wav
 const char* tw_debug_family_name(int family);
 
 /* The library's own byte accounting of one engine (what it has allocated and still holds), for the leak test:
- *   out[0] device bytes (workspace, flow planes, batch contexts, tables, plans)      out[1] page-locked host bytes it allocated
+ *   out[0] device bytes (workspace, flow planes, batch contexts, tables, plans,
+ *          the diff image's staging once a host destination was asked for)           out[1] page-locked host bytes it allocated
  *   out[2] cached plans                                                              out[3] bounce-buffer capacity (in out[1])
  *   out[4] entries of the process-wide page-lock table (tw_host_alloc / tw_host_register)   out[5] their bytes
  *   out[6] pooled profiling events                                                   out[7] captured single-pair graphs

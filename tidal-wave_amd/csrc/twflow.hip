@@ -819,6 +819,10 @@ struct tw_engine {
     ShiftRec* d_shift = nullptr;
     unsigned* d_sprof = nullptr;
     size_t d_sprof_cap = 0;
+    // diff image (tw_ticket_overlay): the staging a picture for a HOST destination is rendered into (dense rows of
+    // round_up(3 w, 4) bytes), created by the first such call and grown on demand; device destinations are written in place
+    uint8_t* d_ovl = nullptr;
+    size_t d_ovl_cap = 0;
     // profiling: per kernel class, -2 = off, -1 = every level, k = level k only
     int prof_level[TW_K_COUNT] = {-2, -2, -2, -2, -2};
     std::vector<ProfPair> prof_pending[TW_K_COUNT];
@@ -4608,6 +4612,7 @@ void tw_engine_destroy(tw_engine* e)
     if (e->d_cells) (void)hipFree(e->d_cells);
     if (e->d_shift) (void)hipFree(e->d_shift);
     if (e->d_sprof) (void)hipFree(e->d_sprof);
+    if (e->d_ovl) (void)hipFree(e->d_ovl);
     for (tw_image* im : e->res_images) delete im;
     for (tw_engine::ResChunk& ch : e->res_chunks) (void)hipFree(ch.base);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -5334,6 +5339,258 @@ tw_status tw_ticket_shift(tw_engine* e, tw_ticket ticket, tw_shift* out)
     return TW_OK;
 }
 
+namespace {
+// ---- diff image (tw_ticket_overlay, tw_stage_overlay) ---------------------------------------------------------------
+// How tw_overlay_base runs: a pure function of the addresses, the strides and the size (tw_debug_overlay_plan shows it).
+struct OverlayChoice {
+    int vec;  // 1: dword loads and stores; 0: the byte path
+    int px, threads, gx, gy;
+};
+OverlayChoice choose_overlay(uintptr_t E, uintptr_t T, long long stride, uintptr_t dst, long long pitch, int w, int h)
+{
+    OverlayChoice c;
+    c.vec = (E % 4 == 0 && T % 4 == 0 && dst % 4 == 0 && stride % 4 == 0 && pitch % 4 == 0) ? 1 : 0;
+    c.px = OVL_PX;
+    c.threads = 64 * OVL_ROWS;
+    c.gx = (w + 64 * OVL_PX - 1) / (64 * OVL_PX);
+    c.gy = (h + OVL_ROWS - 1) / OVL_ROWS;
+    return c;
+}
+static_assert(OVL_RECTS == TW_MAX_IGNORE && OVL_MAX_LEN == TW_OVERLAY_MAX_LEN, "the kernel's limits are the header's");
+static_assert(sizeof(tw_overlay_hit) == sizeof(ScanRec) && offsetof(tw_overlay_hit, dx) == offsetof(ScanRec, dx),
+              "tw_overlay_hit is the scan's record");
+
+// one picture: everything device memory, the rectangles clipped (clip_ignore)
+struct OverlayJob {
+    const uint8_t *E, *T;
+    long long stride;
+    uint8_t* dst;
+    long long pitch;
+    int w, h, tol;
+    const std::vector<tw_rect>* rects;
+    const RegionRec* d_regions;
+    int n_regions;
+    const ScanRec* d_hits;
+    int n_hits;
+};
+// The launches of one picture on `st`, in the order that is the layers' priority: the base, the boxes when there are any,
+// the vectors when there are any.  Returns the base kernel's path (OverlayChoice::vec).
+int launch_overlay(tw_engine* e, hipStream_t st, const OverlayJob& j)
+{
+    OverlayRects rc;
+    rc.n = (int)std::min<size_t>(j.rects->size(), OVL_RECTS);
+    for (int i = 0; i < rc.n; i++) {
+        const tw_rect& r = (*j.rects)[i];
+        rc.r[i] = make_int4(r.x, r.y, r.width, r.height);
+    }
+    const OverlayChoice ch = choose_overlay((uintptr_t)j.E, (uintptr_t)j.T, j.stride, (uintptr_t)j.dst, j.pitch, j.w, j.h);
+    OverlayBaseArgs b;
+    b.E = j.E;
+    b.T = j.T;
+    b.stride = j.stride;
+    b.dst = j.dst;
+    b.pitch = j.pitch;
+    b.w = j.w;
+    b.h = j.h;
+    b.tol = j.tol;
+    b.rc = rc;
+    const dim3 grid(ch.gx, ch.gy, 1);
+    if (ch.vec) TW_LAUNCH(e, TW_DF_OVERLAY_BASE, tw_overlay_base<true>, grid, dim3(ch.threads), 0, st, b);
+    else TW_LAUNCH(e, TW_DF_OVERLAY_BASE, tw_overlay_base<false>, grid, dim3(ch.threads), 0, st, b);
+    OverlayMarksArgs m;
+    m.dst = j.dst;
+    m.pitch = j.pitch;
+    m.w = j.w;
+    m.h = j.h;
+    m.regions = j.d_regions;
+    m.n_regions = j.n_regions;
+    m.hits = j.d_hits;
+    m.n_hits = j.n_hits;
+    m.rc = rc;
+    if (j.n_regions > 0) {
+        // a box has at most 2 (w + h) outline pixels; eight workgroups stride the largest
+        const int gx = std::max(1, std::min(8, (2 * (j.w + j.h) + 255) / 256));
+        TW_LAUNCH(e, TW_DF_OVERLAY_MARKS, tw_overlay_marks<0>, dim3(gx, j.n_regions, 1), dim3(256), 0, st, m);
+    }
+    if (j.n_hits > 0)
+        TW_LAUNCH(e, TW_DF_OVERLAY_MARKS, tw_overlay_marks<1>, dim3((j.n_hits + OVL_HITS_PER_WG - 1) / OVL_HITS_PER_WG, 1, 1),
+                  dim3(64 * OVL_HITS_PER_WG), 0, st, m);
+    return ch.vec;
+}
+
+// A picture's destination, checked before anything is launched as check_flow_field checks a flow field.  *kind = 0: device
+// memory of this engine's device that holds the whole image; 1: a page-locked host block the library knows; 2: any other
+// host memory.
+tw_status check_overlay_out(tw_engine* e, const void* data, ptrdiff_t pitch, int w, int h, int* kind)
+{
+    const size_t row = 3 * (size_t)w;
+    if (!data || pitch < (ptrdiff_t)row) {
+        e->err = "bad diff image destination (null data, or a pitch below 3 * width)";
+        return TW_E_BAD_PARAMETER;
+    }
+    const size_t extent = (size_t)pitch * (size_t)(h - 1) + row;
+    if (pin_registry().covers(data, extent)) {
+        *kind = 1;
+        return TW_OK;
+    }
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, data) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        *kind = 2;
+        return TW_OK;
+    }
+    if (at.device != e->device) {
+        e->err = "diff image destination is memory of another device";
+        return TW_E_BAD_PARAMETER;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(data)) != hipSuccess ||
+        (uintptr_t)data + extent > (uintptr_t)base + size) {
+        (void)hipGetLastError();
+        e->err = "diff image destination does not hold the whole image";
+        return TW_E_BAD_PARAMETER;
+    }
+    *kind = 0;
+    return TW_OK;
+}
+
+// What tw_ticket_hits and tw_ticket_overlay share with tw_ticket_changes: the ticket's batch is launched if it has to be and
+// waited for, the pair's own errors are answered as tw_wait answers them, and the ticket is NOT consumed (the wait that
+// collects it does the per-batch bookkeeping of the copy streams).
+tw_status ticket_finished(tw_engine* e, Ctx* c, int j)
+{
+    tw_status r;
+    if (!c->launched && (r = flush_ctx(e, *c))) {
+        drop_batch(*c);
+        return r;
+    }
+    const hipError_t herr = hipEventSynchronize(c->ev_done);
+    if (herr != hipSuccess) {
+        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
+        return TW_E_DEVICE;
+    }
+    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
+        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
+        return TW_E_BAD_IMAGE_FORMAT;
+    }
+    return TW_OK;
+}
+}  // namespace
+
+tw_status tw_ticket_hits(tw_engine* e, tw_ticket ticket, int* n)
+{
+    if (!e || !n) return TW_E_BAD_PARAMETER;
+    int j = 0;
+    Ctx* c = find_ctx(e, ticket, &j);
+    if (!c) {
+        e->err = "unknown ticket";
+        return TW_E_BAD_PARAMETER;
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    TW_TRY(ticket_finished(e, c, j));
+    if (c->span <= 0) {
+        *n = 0;
+        return TW_OK;
+    }
+    const int cnt = c->h_count[j];
+    const std::vector<tw_rect>& ign = c->jobs[j].ign;
+    if (ign.empty()) {
+        *n = cnt;
+        return TW_OK;
+    }
+    // as tw_wait counts a pair with rectangles: all of its records, the eager copy's or the context's own plane's
+    const ScanRec* hr = c->h_rec + (size_t)j * HOST_RECS;
+    std::vector<ScanRec> extra;
+    if (cnt > HOST_RECS) {
+        const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
+        extra.resize(cnt);
+        TW_TRY(d2h_sync(e, extra.data(), c->d_rec + (size_t)j * G, (size_t)cnt * sizeof(ScanRec)));
+        hr = extra.data();
+    }
+    int kept = 0;
+    for (int i = 0; i < cnt; i++) {
+        bool inside = false;
+        for (const tw_rect& r : ign)
+            inside = inside || (hr[i].x >= r.x && hr[i].x < r.x + r.width && hr[i].y >= r.y && hr[i].y < r.y + r.height);
+        kept += inside ? 0 : 1;
+    }
+    *n = kept;
+    return TW_OK;
+}
+
+tw_status tw_ticket_overlay(tw_engine* e, tw_ticket ticket, int tol, const tw_overlay_out* out)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    if (!out || !out->data || out->format != TW_OVERLAY_RGB8 || tol < 0 || tol > 255) {
+        e->err = "tw_ticket_overlay: a null destination, an unknown format, or tol outside 0 .. 255";
+        return TW_E_BAD_PARAMETER;
+    }
+    int j = 0;
+    Ctx* c = find_ctx(e, ticket, &j);
+    if (!c) {
+        e->err = "unknown ticket";
+        return TW_E_BAD_PARAMETER;
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    const int w = c->w, h = c->h;
+    int kind = 0;
+    TW_TRY(check_overlay_out(e, out->data, out->pitch, w, h, &kind));
+    TW_TRY(ticket_finished(e, c, j));
+    // The batch is over and its context is not reused before the ticket is collected: the pair's images are where the batch
+    // read them — a host pair's slots of d_img (a resident expected image in its block), a device pair's own memory (a
+    // reconciled device target in its d_img slot) — and all its hit records in the context's plane.
+    const Job& jb = c->jobs[j];
+    const bool host = jb.h_b != nullptr;
+    const size_t npx = staged_image_bytes(w, h);
+    OverlayJob oj;
+    oj.E = host ? (jb.res ? jb.res->d : c->d_img + npx * (size_t)(2 * j)) : jb.d_a;
+    oj.T = host ? c->d_img + npx * (size_t)(2 * j + 1) : jb.d_b;
+    oj.stride = host ? (long long)w : jb.stride;
+    oj.w = w;
+    oj.h = h;
+    oj.tol = tol;
+    oj.rects = &jb.ign;
+    oj.n_hits = c->span > 0 ? c->h_count[j] : 0;
+    oj.d_hits = oj.n_hits > 0 ? c->d_rec + (size_t)j * (size_t)tw_grid_capacity(w, h, c->span) : nullptr;
+    oj.n_regions = (c->regions && c->span > 0) ? std::max(0, std::min(c->h_nreg[j], (int)TW_MAX_REGIONS)) : 0;
+    oj.d_regions = oj.n_regions > 0 ? c->d_regs + (size_t)j * TW_MAX_REGIONS : nullptr;
+    // on the device-to-host stream: the compute stream may hold later batches' kernels, and the process has no queue to spare
+    // for a further stream
+    if (!e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
+    hipStream_t st = e->d2h_stream;
+    const size_t row = 3 * (size_t)w, spitch = (row + 3) / 4 * 4;
+    if (kind == 0) {
+        oj.dst = (uint8_t*)out->data;
+        oj.pitch = out->pitch;
+    } else {
+        const size_t need = spitch * (size_t)h;
+        TW_TRY(grow_device(e, e->d_ovl, e->d_ovl_cap, need, need + 256, st));
+        oj.dst = e->d_ovl;
+        oj.pitch = (long long)spitch;
+    }
+    (void)launch_overlay(e, st, oj);
+    TW_HIP(e, hipGetLastError());
+    if (kind == 1) {
+        TW_HIP(e, hipMemcpy2DAsync(out->data, (size_t)out->pitch, e->d_ovl, spitch, row, (size_t)h, hipMemcpyDeviceToHost, st));
+    } else if (kind == 2) {
+        // pageable: whole staging rows come down into the bounce buffer, the CPU copies each row's 3 w bytes out
+        const size_t per = std::max<size_t>(1, BOUNCE_CHUNK / spitch);
+        TW_TRY(bounce_reserve(e, std::min((size_t)h, per) * spitch));
+        for (size_t r0 = 0; r0 < (size_t)h; r0 += per) {
+            const size_t nr = std::min(per, (size_t)h - r0);
+            TW_HIP(e, hipMemcpyAsync(e->h_bounce, e->d_ovl + r0 * spitch, nr * spitch, hipMemcpyDeviceToHost, st));
+            TW_HIP(e, hipStreamSynchronize(st));
+            for (size_t y = 0; y < nr; y++)
+                memcpy((uint8_t*)out->data + (r0 + y) * (size_t)out->pitch, e->h_bounce + y * spitch, row);
+        }
+    }
+    // the call is synchronous; and a host-side synchronise is what releases the stream's per-command bookkeeping (wait_ticket)
+    TW_HIP(e, hipStreamSynchronize(st));
+    return TW_OK;
+}
+
 tw_status tw_diff_u8(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height,
                      ptrdiff_t stride, int span, double threshold, tw_vector* out, int cap, int* n, float* seconds)
 {
@@ -5836,13 +6093,25 @@ extern "C" int tw_debug_shift_plan(int width, int height, int radius, int* out, 
     return m;
 }
 
+extern "C" int tw_debug_overlay_plan(unsigned long long expect, unsigned long long target, long long stride,
+                                     unsigned long long dst, long long pitch, int width, int height, int* out, int n)
+{
+    if (!out || width < 1 || height < 1) return 0;
+    const OverlayChoice c = choose_overlay((uintptr_t)expect, (uintptr_t)target, stride, (uintptr_t)dst, pitch, width, height);
+    const int v[5] = {c.vec, c.px, c.threads, c.gx, c.gy};
+    const int m = std::max(0, std::min(n, 5));
+    for (int i = 0; i < m; i++) out[i] = v[i];
+    return m;
+}
+
 extern "C" const char* tw_debug_family_name(int family)
 {
     static const char* const names[TW_DF_COUNT] = {
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q", "tw_pyr_level_lds",
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q",
+        "tw_overlay_base", "tw_overlay_marks", "tw_pyr_level_lds",
         "tw_shift_profiles", "tw_shift_search", "tw_shift_verify", "tw_flow_shift_init", "tw_warp_residual", "tw_change_scan",
         "tw_flow_iter_grid",
         "tw_hit_regions", "tw_jpeg_idct", "tw_mask_rects", "tw_pair_same",
@@ -5875,6 +6144,7 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
     if (e->d_cells) v[0] += e->d_cells_cap * sizeof(int4) + 256;
     if (e->d_shift) v[0] += sizeof(ShiftRec) * (size_t)e->cfg.cap + 256;
     if (e->d_sprof) v[0] += e->d_sprof_cap * sizeof(unsigned) + 256;
+    if (e->d_ovl) v[0] += e->d_ovl_cap + 256;
     for (const Ctx& c : e->ctx) {
         if (c.d_istage) v[0] += c.d_istage_cap + 256;
         if (c.h_fsrc) v[1] += sizeof(FlowDst) * (size_t)e->cfg.cap;
@@ -6926,6 +7196,56 @@ tw_status tw_stage_shift(tw_engine* e, const uint8_t* expect, const uint8_t* tar
     out->sad_shift = hrec[0].sad_shift;
     out->sad_zero = hrec[0].sad_zero;
     return TW_OK;
+}
+
+tw_status tw_stage_overlay(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height, ptrdiff_t stride,
+                           int misalign, const tw_rect* rects, int n_rects, const tw_overlay_hit* hits, int n_hits,
+                           const tw_region* regions, int n_regions, int tol, uint8_t* out, ptrdiff_t pitch, int* path)
+{
+    if (!e || !expect || !target || !out) return TW_E_BAD_PARAMETER;
+    e->err.clear();
+    TW_TRY(check_dims(e, width, height));
+    if (stride < width || misalign < 0 || misalign > 3 || n_hits < 0 || (n_hits > 0 && !hits) || n_regions < 0 ||
+        n_regions > TW_MAX_REGIONS || (n_regions > 0 && !regions) || tol < 0 || tol > 255 || pitch < 3 * (ptrdiff_t)width) {
+        e->err = "tw_stage_overlay: bad argument";
+        return TW_E_BAD_PARAMETER;
+    }
+    std::vector<tw_rect> ign;
+    TW_TRY(clip_ignore(e, rects, n_rects, width, height, &ign));
+    TW_HIP(e, hipSetDevice(e->device));
+    const size_t img = (size_t)stride * (size_t)(height - 1) + (size_t)width, obytes = (size_t)pitch * (size_t)height;
+    Tmp t;
+    uint8_t* d_E = t.alloc<uint8_t>(img + 4);
+    uint8_t* d_T = t.alloc<uint8_t>(img + 4);
+    uint8_t* d_out = t.alloc<uint8_t>(obytes);
+    ScanRec* d_hits = t.alloc<ScanRec>((size_t)std::max(n_hits, 1));
+    RegionRec* d_regs = t.alloc<RegionRec>((size_t)std::max(n_regions, 1));
+    if (!d_E || !d_T || !d_out || !d_hits || !d_regs) return TW_E_NOMEM;
+    TW_TRY(h2d_sync(e, d_E + misalign, expect, img));
+    TW_TRY(h2d_sync(e, d_T + misalign, target, img));
+    TW_TRY(h2d_sync(e, d_out, out, obytes));
+    if (n_hits > 0) TW_TRY(h2d_sync(e, d_hits, hits, sizeof(ScanRec) * (size_t)n_hits));
+    if (n_regions > 0) TW_TRY(h2d_sync(e, d_regs, regions, sizeof(RegionRec) * (size_t)n_regions));
+    OverlayJob oj;
+    oj.E = d_E + misalign;
+    oj.T = d_T + misalign;
+    oj.stride = (long long)stride;
+    oj.dst = d_out;
+    oj.pitch = (long long)pitch;
+    oj.w = width;
+    oj.h = height;
+    oj.tol = tol;
+    oj.rects = &ign;
+    oj.d_regions = d_regs;
+    oj.n_regions = n_regions;
+    oj.d_hits = d_hits;
+    oj.n_hits = n_hits;
+    hipStream_t st = e->stream;
+    const int vec = launch_overlay(e, st, oj);
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    if (path) *path = vec;
+    return d2h_sync(e, out, d_out, obytes);
 }
 
 }  // extern "C"

@@ -5912,5 +5912,150 @@ __global__ __launch_bounds__(256) void tw_flow_shift_init(ShiftInitArgs s)
     out[a.fps + (long long)y * a.ld + x] = v[1];
 }
 
+// =====================================================================================================
+// tw_overlay_base / tw_overlay_marks — one pair's diff image (tw_ticket_overlay; the semantics are include/twflow.h's, "Diff
+//   image"), rendered on request after the pair's batch has finished.  RGB bytes, rows `pitch` bytes apart; nothing behind a
+//   row's 3 w bytes is written.
+//   tw_overlay_base: every pixel's base colour, 2 bytes in, 3 bytes out.  A lane owns OVL_PX = 4 consecutive pixels of a row
+//   (64 lanes across, OVL_ROWS rows per workgroup).  <VEC = true>: both images, the destination, the stride and the pitch
+//   are multiples of 4, so the lane's pixels are one aligned dword of each image and three aligned dwords of the destination
+//   (a row's last 1 .. 3 pixels go byte by byte: the dword would read past the row and the stores past its 3 w bytes).
+//   <VEC = false>: byte loads and byte stores, any address.  The pair's clipped rectangles come by value (at most 32: 512 bytes
+//   of kernel arguments, read as scalars — the loop over them is wave-uniform).
+//   tw_overlay_marks<0>: the outline of every region box, one workgroup row (grid y) per box, the perimeter strided over
+//   grid x.  tw_overlay_marks<1>: the vectors, one wave per hit record — it reads the record from the batch's own plane,
+//   leaves a hit inside a clipped rectangle out (what tw_wait leaves out), and its lanes stride the line's n + 1 pixels and
+//   the marker's 9.  Each launch stores ONE colour, so marks that overlap inside a launch need no order; the priority
+//   vectors over boxes over base is the stream order of the three launches.
+// =====================================================================================================
+constexpr int OVL_PX = 4;           // pixels per lane of tw_overlay_base
+constexpr int OVL_ROWS = 4;         // rows per workgroup of tw_overlay_base
+constexpr int OVL_RECTS = 32;       // = TW_MAX_IGNORE
+constexpr int OVL_MAX_LEN = 1024;   // = TW_OVERLAY_MAX_LEN
+constexpr int OVL_HITS_PER_WG = 4;  // waves per workgroup of tw_overlay_marks<1>
+struct OverlayRects {
+    int n;
+    int4 r[OVL_RECTS];  // x, y, width, height, clipped to the image, none empty
+};
+struct OverlayBaseArgs {
+    const uint8_t* E;
+    const uint8_t* T;
+    long long stride;
+    uint8_t* dst;
+    long long pitch;
+    int w, h, tol;
+    OverlayRects rc;
+};
+struct OverlayMarksArgs {
+    uint8_t* dst;
+    long long pitch;
+    int w, h;
+    const RegionRec* regions;  // <0>: the boxes
+    int n_regions;
+    const ScanRec* hits;  // <1>: the pair's ordered hit records
+    int n_hits;
+    OverlayRects rc;
+};
+
+__device__ __forceinline__ bool ovl_inside(const OverlayRects& rc, int x, int y)
+{
+    bool in = false;
+    for (int i = 0; i < rc.n; i++) {
+        const int4 r = rc.r[i];
+        in = in || (x >= r.x && x < r.x + r.z && y >= r.y && y < r.y + r.w);
+    }
+    return in;
+}
+// r | g << 8 | b << 16 of one base pixel
+__device__ __forceinline__ unsigned ovl_base_rgb(int e, int t, int tol, bool inside)
+{
+    const int d = e > t ? e - t : t - e, g = 128 + (t >> 1);
+    if (inside) return (unsigned)(g - 48) | (unsigned)(g - 48) << 8 | (unsigned)g << 16;
+    if (d > tol) return 255u | (unsigned)(192 - (d >> 1)) << 8;
+    return (unsigned)g * 0x010101u;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(64 * OVL_ROWS) void tw_overlay_base(OverlayBaseArgs a)
+{
+    const int y = (int)blockIdx.y * OVL_ROWS + (int)(threadIdx.x >> 6);
+    const int x0 = ((int)blockIdx.x * 64 + (int)(threadIdx.x & 63)) * OVL_PX;
+    if (y >= a.h || x0 >= a.w) return;
+    const uint8_t* __restrict__ E = a.E + (long long)y * a.stride + x0;
+    const uint8_t* __restrict__ T = a.T + (long long)y * a.stride + x0;
+    uint8_t* __restrict__ D = a.dst + (long long)y * a.pitch + 3ll * x0;
+    const int npx = min(OVL_PX, a.w - x0);
+    if (VEC && npx == OVL_PX) {
+        const unsigned ev = *(const unsigned*)E, tv = *(const unsigned*)T;
+        unsigned c[OVL_PX];
+#pragma unroll
+        for (int k = 0; k < OVL_PX; k++)
+            c[k] = ovl_base_rgb((int)((ev >> (8 * k)) & 255u), (int)((tv >> (8 * k)) & 255u), a.tol, ovl_inside(a.rc, x0 + k, y));
+        // 12 bytes: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+        unsigned* __restrict__ D4 = (unsigned*)D;
+        D4[0] = c[0] | c[1] << 24;
+        D4[1] = c[1] >> 8 | c[2] << 16;
+        D4[2] = c[2] >> 16 | c[3] << 8;
+    } else {
+        for (int k = 0; k < npx; k++) {
+            const unsigned c = ovl_base_rgb((int)E[k], (int)T[k], a.tol, ovl_inside(a.rc, x0 + k, y));
+            D[3 * k] = (uint8_t)c;
+            D[3 * k + 1] = (uint8_t)(c >> 8);
+            D[3 * k + 2] = (uint8_t)(c >> 16);
+        }
+    }
+}
+
+__device__ __forceinline__ void ovl_put(const OverlayMarksArgs& a, long long x, long long y, uint8_t r, uint8_t g, uint8_t b)
+{
+    if (x < 0 || y < 0 || x >= a.w || y >= a.h) return;  // pixels outside the image are dropped
+    uint8_t* __restrict__ D = a.dst + y * a.pitch + 3 * x;
+    D[0] = r;
+    D[1] = g;
+    D[2] = b;
+}
+// q of the header: NaN -> 0, else round-half-even of the component clamped to +-OVL_MAX_LEN
+__device__ __forceinline__ int ovl_q(float v)
+{
+    if (v != v) return 0;
+    return (int)__builtin_rintf(fminf(fmaxf(v, -(float)OVL_MAX_LEN), (float)OVL_MAX_LEN));
+}
+// floor(p / q) for q > 0
+__device__ __forceinline__ int ovl_floordiv(int p, int q)
+{
+    const int d = p / q;
+    return d - ((p % q) < 0 ? 1 : 0);
+}
+
+template <int LAYER>
+__global__ __launch_bounds__(256) void tw_overlay_marks(OverlayMarksArgs a)
+{
+    if (LAYER == 0) {
+        if ((int)blockIdx.y >= a.n_regions) return;
+        const RegionRec r = a.regions[blockIdx.y];
+        if (r.width < 1 || r.height < 1) return;
+        const long long bw = r.width, bh = r.height, per = 2 * (bw + bh);
+        for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < per; p += (long long)gridDim.x * 256) {
+            long long x, y;
+            if (p < bw) x = r.x + p, y = r.y;
+            else if (p < 2 * bw) x = r.x + (p - bw), y = r.y + bh - 1;
+            else if (p < 2 * bw + bh) x = r.x, y = r.y + (p - 2 * bw);
+            else x = r.x + bw - 1, y = r.y + (p - 2 * bw - bh);
+            ovl_put(a, x, y, 0, 160, 0);
+        }
+    } else {
+        const int k = (int)blockIdx.x * OVL_HITS_PER_WG + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+        if (k >= a.n_hits) return;
+        const ScanRec h = a.hits[k];
+        if (ovl_inside(a.rc, h.x, h.y)) return;  // the ignore rule: tw_wait does not report this hit
+        const int rx = ovl_q(h.dx), ry = ovl_q(h.dy);
+        const int n = max(abs(rx), abs(ry));
+        if (lane < 9) ovl_put(a, (long long)h.x + (lane % 3 - 1), (long long)h.y + (lane / 3 - 1), 0, 0, 255);
+        // (n = 0: the origin only, which the marker has drawn)
+        for (int i = lane; n > 0 && i <= n; i += 64)
+            ovl_put(a, (long long)h.x + ovl_floordiv(2 * i * rx + n, 2 * n), (long long)h.y + ovl_floordiv(2 * i * ry + n, 2 * n), 0, 0,
+                    255);
+    }
+}
 
 }  // namespace twk

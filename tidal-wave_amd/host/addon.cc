@@ -132,6 +132,11 @@ napi_value convert_result(napi_env env, const Response& r)
         napi_set_named_property(env, sh, "applied", ap);
         napi_set_named_property(env, o, "shift", sh);
     }
+    if (!r.overlay.empty()) {
+        // not in the reference (new TidalWave({overlay: dir}) only, SUSPICIOUS pairs only), behind every other key: the path of
+        // the pair's diff image
+        set_str(env, o, "overlay", r.overlay);
+    }
     return o;
 }
 
@@ -212,6 +217,23 @@ double get_f64(napi_env env, napi_value opts, const char* k, double def)
     return d;
 }
 
+std::string get_str(napi_env env, napi_value opts, const char* k, const std::string& def)
+{
+    napi_valuetype t;
+    if (!opts || napi_typeof(env, opts, &t) != napi_ok || t != napi_object) return def;
+    bool has = false;
+    napi_value v;
+    if (napi_has_named_property(env, opts, k, &has) != napi_ok || !has) return def;
+    if (napi_get_named_property(env, opts, k, &v) != napi_ok || napi_typeof(env, v, &t) != napi_ok || t != napi_string)
+        return def;
+    size_t n = 0;
+    if (napi_get_value_string_utf8(env, v, nullptr, 0, &n) != napi_ok) return def;
+    std::string s(n + 1, '\0');
+    napi_get_value_string_utf8(env, v, &s[0], n + 1, &n);
+    s.resize(n);
+    return s;
+}
+
 void finalize(napi_env, void* data, void*)
 {
     Broker* b = (Broker*)data;
@@ -256,6 +278,10 @@ napi_value construct(napi_env env, napi_callback_info info)
     // not in the reference: start every pair's flow from its global shift, found on the device — 0 (default): off; 1 .. 1024:
     // the search radius in pixels
     p.shift = get_i32(env, opts, "shift", 0);
+    // not in the reference: a directory for the diff images of SUSPICIOUS pairs, rendered on the device ("" / absent: off), and
+    // the gray-level difference above which a pixel is painted as changed (0 .. 255)
+    p.overlayDir = get_str(env, opts, "overlay", "");
+    p.overlayTol = get_i32(env, opts, "overlayTol", 16);
 
     Broker* b = new Broker();
     b->env = env;

@@ -6,7 +6,10 @@
 // in every vector), N being the gap in grid steps that still joins two vectors; -residual N (1 .. 254), the cells of every pair
 // with a pixel that differs by more than N gray levels and how many of those the flow does not explain (`change` behind the
 // other keys), and -residualMin N, which makes a pair with at least N unexplained pixels SUSPICIOUS even without a vector; -shift N (1 .. 1024),
-// every pair's flow started from its global shift of at most N pixels, found on the device (`shift` behind the other keys).  The reference's own script cannot run (it requires
+// every pair's flow started from its global shift of at most N pixels, found on the device (`shift` behind the other keys);
+// -overlay DIR, a diff image of every SUSPICIOUS pair, rendered on the device and written to DIR (created if missing) as a PNG
+// whose path is the result's last key `overlay`, and -overlayTol N (0 .. 255, default 16), the gray-level difference above
+// which a pixel is painted as changed.  The reference's own script cannot run (it requires
 // './opticalflow.js', which does not exist, commandline.js:62); this one drives index.js.  No stdout dup2
 // trick is needed: the native layer here does not print.
 // expect_path / target_path may be two directories (every file of target is paired with the same relative
@@ -23,7 +26,7 @@ var usage =
   '  $ node commandline.js -threshold 1.0 -span 10 test/images test/images2\n';
 
 var supportedOptions = ['threshold', 'span', 'pyrScale', 'pyrLevels', 'winSize', 'pyrIterations', 'polyN',
-  'polySigma', 'flags', 'numThreads', 'regions', 'residual', 'residualMin', 'shift'];
+  'polySigma', 'flags', 'numThreads', 'regions', 'residual', 'residualMin', 'shift', 'overlayTol'];
 
 function getArgs(argv) {
   var positional = [], options = {};
@@ -33,6 +36,8 @@ function getArgs(argv) {
       var r = parseRegion(m[2] !== undefined ? m[2] : argv[++i]);
       if (!r) { process.stderr.write('-ignore takes x,y,w,h (four integers)\n' + usage); process.exit(-1); }
       (options.ignore = options.ignore || []).push(r);
+    } else if (m && m[1] === 'overlay') {
+      options.overlay = Path.resolve(String(m[2] !== undefined ? m[2] : argv[++i]));   // a directory, not a number
     } else if (m && supportedOptions.indexOf(m[1]) !== -1) {
       var v = m[2] !== undefined ? m[2] : argv[++i];
       options[m[1]] = Number(v);          // numbers, like minimist does for numeric-looking values
@@ -54,6 +59,7 @@ function print(o) { process.stdout.write(JSON.stringify(o, null, '  ') + '\n'); 
 
 function main(args) {
   var TW = require('./index');
+  if (args.options.overlay) FS.mkdirSync(args.options.overlay, { recursive: true });
   var isDir = false;
   try { isDir = FS.statSync(args.target_path).isDirectory(); } catch (e) { /* reported as an ERROR response */ }
   var t;

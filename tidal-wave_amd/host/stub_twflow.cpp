@@ -968,4 +968,48 @@ tw_status tw_ticket_shift(tw_engine* e, tw_ticket t, tw_shift* out)
     if (tracing()) trace(e, "tw_ticket_shift ticket=%lld -> %s", (long long)t, status_name(r));
     return r;
 }
+// The diff image calls; neither consumes the ticket.  tw_ticket_hits echoes the count the ticket's tw_wait will give; a pair
+// whose tw_wait will answer a bad palette index answers it here too, and stays waitable.  The stub renders nothing:
+// tw_ticket_overlay writes pixel (x, y) as (x & 255, y & 255, tol) into host memory, the bytes behind a row untouched.
+static tw_status stub_ticket_state(tw_engine* e, tw_ticket t, int* width, int* height, int* count)
+{
+    std::lock_guard<std::mutex> lk(e->m);
+    auto op = e->open.find(t);
+    if (op == e->open.end()) return TW_E_BAD_PARAMETER;
+    auto bad = e->bad.find(t);
+    if (bad != e->bad.end()) {
+        e->err = "bad palette index in the " + bad->second + " image";
+        return TW_E_BAD_IMAGE_FORMAT;
+    }
+    auto in = e->info.find(t);
+    if (width) *width = in != e->info.end() ? in->second.w : 0;
+    if (height) *height = in != e->info.end() ? in->second.h : 0;
+    if (count) *count = op->second >= 1000000 ? 1 : 0;
+    return TW_OK;
+}
+tw_status tw_ticket_hits(tw_engine* e, tw_ticket t, int* n)
+{
+    if (!e || !n) return TW_E_BAD_PARAMETER;
+    int count = 0;
+    const tw_status r = stub_ticket_state(e, t, nullptr, nullptr, &count);
+    if (r == TW_OK) *n = count;
+    if (tracing()) trace(e, "tw_ticket_hits ticket=%lld -> %s count=%d", (long long)t, status_name(r), count);
+    return r;
+}
+tw_status tw_ticket_overlay(tw_engine* e, tw_ticket t, int tol, const tw_overlay_out* out)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    int w = 0, h = 0;
+    tw_status r = TW_OK;
+    if (!out || !out->data || out->format != TW_OVERLAY_RGB8 || tol < 0 || tol > 255) r = TW_E_BAD_PARAMETER;
+    if (r == TW_OK) r = stub_ticket_state(e, t, &w, &h, nullptr);
+    if (r == TW_OK && out->pitch < 3 * (ptrdiff_t)w) r = TW_E_BAD_PARAMETER;
+    if (r == TW_OK)
+        for (int y = 0; y < h; y++) {
+            uint8_t* row = (uint8_t*)out->data + (ptrdiff_t)y * out->pitch;
+            for (int x = 0; x < w; x++) row[3 * x] = (uint8_t)(x & 255), row[3 * x + 1] = (uint8_t)(y & 255), row[3 * x + 2] = (uint8_t)tol;
+        }
+    if (tracing()) trace(e, "tw_ticket_overlay ticket=%lld tol=%d -> %s %dx%d", (long long)t, tol, status_name(r), w, h);
+    return r;
+}
 }

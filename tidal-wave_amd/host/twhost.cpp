@@ -3,6 +3,7 @@
 #include "twhost.h"
 #include "resident_cache.h"
 #include "tw_inflate.h"
+#include "tw_png_write.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -11,6 +12,7 @@
 
 #include <sched.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <chrono>
@@ -38,6 +40,8 @@
 #pragma weak tw_wait_regions
 #pragma weak tw_ticket_changes
 #pragma weak tw_ticket_shift
+#pragma weak tw_ticket_hits
+#pragma weak tw_ticket_overlay
 
 namespace twhost {
 
@@ -1079,6 +1083,10 @@ struct ConsumerRun {
     std::vector<tw_change> change_recs;
     // shift (ConsumerShared::shift; 0: off): the search radius the engine was given
     int shift_radius = 0;
+    // diff images (ConsumerShared::overlayDir; empty: off): the directory, the tolerance, and tw_ticket_overlay's pixels
+    std::string overlay_dir;
+    int overlay_tol = 16;
+    std::vector<uint8_t> overlay_px;
     std::vector<int> region_of;
     std::vector<tw_region> region_recs;
     // Resident expected images (Parameter::residentMB / TW_RESIDENT_MB; 0, the default: off, and no step below reaches the
@@ -1194,6 +1202,27 @@ struct ConsumerRun {
                 shift_radius = residual_tol = regions_gap = 0;
             }
         }
+        // Diff images (Parameter::overlayDir): no option to set — the picture is rendered per ticket, on request.  Off: neither
+        // call is made.  Asked-for pictures are never silently dropped either: a library without the calls, a tolerance outside
+        // 0 .. 255, or a directory that does not exist or cannot be written to leaves the consumer without an engine.  (A picture
+        // that fails later — the disk fills up, the device refuses — is logged and the pair answered without the key.)
+        overlay_dir = eng && shared ? shared->overlayDir : std::string();
+        overlay_tol = shared ? shared->overlayTol : 16;
+        std::string overlay_err;
+        if (!overlay_dir.empty()) {
+            struct stat st;
+            if (!tw_ticket_hits || !tw_ticket_overlay) overlay_err = tw_strerror(TW_E_UNSUPPORTED);
+            else if (overlay_tol < 0 || overlay_tol > 255) overlay_err = tw_strerror(TW_E_BAD_PARAMETER);
+            else if (stat(overlay_dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode) || access(overlay_dir.c_str(), W_OK | X_OK) != 0)
+                overlay_err = "not a writable directory: " + overlay_dir;
+        }
+        if (!overlay_err.empty()) {
+            eng_err = "engine: overlay: " + overlay_err;
+            tw_engine_destroy(eng);
+            eng = nullptr;
+            overlay_dir.clear();
+            shift_radius = residual_tol = regions_gap = 0;
+        }
         prof = eng && shared && shared->profile;
         if (prof) {
             (void)tw_prof_select(eng, TW_K_BLUR_SOLVE, 0);
@@ -1251,7 +1280,7 @@ struct ConsumerRun {
             // and every response has arrived, so nothing of this consumer is in flight)
             my_epoch = shared->epoch.load();
             read_prof(false);
-            mine.pairs = mine.batches = 0;
+            mine.pairs = mine.batches = mine.overlayFailures = 0;
             mine.firstJobNs = mine.lastResponseNs = 0;
             mine.waitMs = 0;
             mine.profMs[0] = mine.profMs[1] = 0;
@@ -1678,6 +1707,30 @@ struct ConsumerRun {
                 rc = tw_ticket_shift(eng, s.ticket, &shift_rec);
                 if (rc != TW_OK) chg_err = engine_error(eng, rc);
             }
+            // ... and the diff image: the count the wait will report, with the changes, is the status the pair will get; a
+            // pair that will be SUSPICIOUS gets its picture.  A pair's own error is left to the wait.
+            std::string overlay_file;
+            if (!overlay_dir.empty() && rc == TW_OK) {
+                int nh = 0;
+                if (tw_ticket_hits(eng, s.ticket, &nh) == TW_OK) {
+                    std::vector<Change> so_far;
+                    if (residual_tol) so_far.assign(change_recs.begin(), change_recs.begin() + std::max(0, std::min(nchg, cap)));
+                    if (!strcmp(pair_status((size_t)std::max(nh, 0), so_far, residual_min), "SUSPICIOUS")) {
+                        const ptrdiff_t pitch = 3 * (ptrdiff_t)s.w;
+                        overlay_px.resize((size_t)pitch * (size_t)s.h);
+                        const tw_overlay_out oo = {overlay_px.data(), pitch, TW_OVERLAY_RGB8};
+                        const std::string path = overlay_path(overlay_dir, s.req.target_image);
+                        const tw_status ro = tw_ticket_overlay(eng, s.ticket, overlay_tol, &oo);
+                        if (ro == TW_OK && png_write_rgb8(path, overlay_px.data(), s.w, s.h, pitch)) {
+                            overlay_file = path;
+                        } else {
+                            // the pair keeps its answer; the missing picture is said aloud (TW_LOG) and counted
+                            mine.overlayFailures++;
+                            TW_LOGF("overlay: %s: %s\n", path.c_str(), ro == TW_OK ? "cannot write the file" : engine_error(eng, ro).c_str());
+                        }
+                    }
+                }
+            }
             tw_status r = regions_gap ? tw_wait_regions(eng, s.ticket, v, cap, &n, region_of.data(), region_recs.data(),
                                                         TW_MAX_REGIONS, &nreg, &sec)
                                       : tw_wait(eng, s.ticket, v, cap, &n, &sec);
@@ -1717,6 +1770,7 @@ struct ConsumerRun {
                 out.threshold = s.req.threshold;
                 out.height = s.h;
                 out.width = s.w;
+                out.overlay = overlay_file;
                 if (regions_gap) {
                     out.hasRegions = true;
                     out.regionCount = nreg;
@@ -1823,6 +1877,8 @@ void Manager::start(const Parameter& p)
     shared_.residual = p.residual;
     shared_.residualMin = p.residualMin;
     shared_.shift = p.shift;
+    shared_.overlayDir = p.overlayDir;
+    shared_.overlayTol = p.overlayTol;
     shared_.stats.assign((size_t)n, ConsumerStats());
     for (int i = 0; i < n; i++) {
         consumers_.push_back(new Consumer(i, requestQueue_, responseQueue_, p.optParam, batch, dec, n, &shared_));

@@ -74,6 +74,9 @@ struct Response {
     int span = 0;
     std::string status, reason;
     int width = 0, height = 0;
+    // not in the reference (Parameter::overlayDir set, SUSPICIOUS pairs only; empty otherwise): the path of the pair's diff
+    // image, a PNG rendered on the device (tw_ticket_overlay)
+    std::string overlay;
     long long pushedNs = 0;  // host-internal: when the consumer handed the response to the pump (steady clock)
 };
 // How long responses sat between a consumer's push and the observer's callback since the last markEpoch() — the one
@@ -116,7 +119,32 @@ struct Parameter {
     // TW_OPT_SHIFT) — 0: off, the calls a consumer makes are exactly the ones it made before; 1 .. 1024: the search radius in
     // pixels.  Response::status is unchanged by it
     int shift = 0;
+    // not in the reference: a directory for diff images (empty: off, the calls a consumer makes are exactly the ones it made
+    // before).  With it a consumer asks tw_ticket_hits in front of each collecting wait — behind tw_ticket_changes, so that the
+    // status pair_status will give is known — and for a pair that will be SUSPICIOUS renders the picture on the device
+    // (tw_ticket_overlay at tolerance overlayTol, 0 .. 255) and writes it to overlay_path(overlayDir, target_image);
+    // Response::overlay carries that path.  Other pairs get no call, no file and no path.  The directory must exist and be
+    // writable when the consumers start: otherwise, as for a tolerance outside 0 .. 255, a consumer has no engine and every pair
+    // answers ERROR ("engine: overlay: ...").  A picture that fails later (a full disk) leaves its pair's answer without the
+    // path; it is logged under TW_LOG and counted in ConsumerStats::overlayFailures.
+    std::string overlayDir;
+    int overlayTol = 16;
 };
+// Where the diff image of a pair goes: <dir>/<16 hex digits of the FNV-1a-64 hash of the target_image string>-<the target's
+// base name without its extension>.png — two targets of one base name in different directories do not collide.
+inline std::string overlay_path(const std::string& dir, const std::string& target_image)
+{
+    unsigned long long hsh = 14695981039346656037ull;
+    for (unsigned char c : target_image) hsh = (hsh ^ c) * 1099511628211ull;
+    const size_t slash = target_image.find_last_of("/\\");
+    std::string base = slash == std::string::npos ? target_image : target_image.substr(slash + 1);
+    const size_t dot = base.find_last_of('.');
+    if (dot != std::string::npos && dot > 0) base.resize(dot);
+    static const char hex[] = "0123456789abcdef";
+    std::string name(16, '0');
+    for (int i = 0; i < 16; i++) name[(size_t)i] = hex[(hsh >> (60 - 4 * i)) & 15];
+    return dir + "/" + name + "-" + base + ".png";
+}
 // Response::status of an answered pair: the reference's rule (src/consumer.cpp:77), and Parameter::residualMin's
 inline const char* pair_status(size_t nvectors, const std::vector<Change>& changes, int residualMin)
 {
@@ -135,6 +163,7 @@ struct ConsumerStats {
     std::string engineError;
     long pairs = 0;           // responses pushed since the last Manager::markEpoch()
     long batches = 0;         // engine batches submitted since then
+    long overlayFailures = 0; // diff images of SUSPICIOUS pairs that could not be rendered or written since then (Parameter::overlayDir)
     // event-bracketed level-0 launches since then: [0] window average + solve, [1] polynomial expansion
     double profMs[2] = {0, 0};
     int profLaunches[2] = {0, 0};
@@ -279,6 +308,8 @@ struct ConsumerShared {
     int residual = 0;             // Parameter::residual: a consumer sets TW_OPT_RESIDUAL once and asks tw_ticket_changes before each collecting wait
     int residualMin = 0;          // Parameter::residualMin
     int shift = 0;                // Parameter::shift: a consumer sets TW_OPT_SHIFT once and asks tw_ticket_shift before each collecting wait
+    std::string overlayDir;       // Parameter::overlayDir: a consumer asks tw_ticket_hits before each collecting wait, tw_ticket_overlay for SUSPICIOUS pairs
+    int overlayTol = 16;          // Parameter::overlayTol
 };
 
 class Consumer {

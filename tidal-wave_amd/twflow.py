@@ -78,6 +78,15 @@ class Shift(C.Structure):
         return (self.dx, self.dy, self.applied, self.n_shift, self.n_zero, self.sad_shift, self.sad_zero)
 
 
+class OverlayOut(C.Structure):
+    # tw_overlay_out (include/twflow.h): destination of a pair's diff image (tw_ticket_overlay)
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_ssize_t), ("format", C.c_int)]
+
+
+OVERLAY_RGB8 = 0
+OVERLAY_MAX_LEN = 1024
+# tw_overlay_hit (include/twflow_debug.h): a hit record as the ordered scan leaves it (16 bytes)
+OVERLAY_HIT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("dx", "<f4"), ("dy", "<f4")])
 MAX_IGNORE = 32
 MAX_REGIONS = 256
 FLOW_PLANAR, FLOW_INTERLEAVED = 0, 1
@@ -120,6 +129,7 @@ SYMBOLS = [
     "tw_wait_regions", "tw_stage_hit_regions",
     "tw_ticket_changes", "tw_stage_warp_residual",
     "tw_ticket_shift", "tw_stage_shift", "tw_debug_shift_plan",
+    "tw_ticket_hits", "tw_ticket_overlay", "tw_stage_overlay", "tw_debug_overlay_plan",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
     "tw_debug_blur_plan", "tw_debug_same_flags", "tw_debug_png_kernel_time", "tw_debug_scan_plan", "tw_debug_level_plan",
@@ -309,6 +319,12 @@ def _bind(path):
     L.tw_stage_shift.argtypes = [vp, u8p, u8p, C.c_ssize_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
                                  C.POINTER(Shift)]
     L.tw_debug_shift_plan.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int]
+    L.tw_ticket_hits.argtypes = [vp, C.c_int64, ip]
+    L.tw_ticket_overlay.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(OverlayOut)]
+    L.tw_stage_overlay.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, rp, C.c_int, vp, C.c_int,
+                                   C.POINTER(Region), C.c_int, C.c_int, u8p, C.c_ssize_t, ip]
+    L.tw_debug_overlay_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_longlong, C.c_uint64, C.c_longlong, C.c_int, C.c_int, ip,
+                                        C.c_int]
     L.tw_flush.argtypes = [vp]
     L.tw_bench_stage.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
     L.tw_level_chunk.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -957,6 +973,78 @@ class Engine:
         out = Shift()
         self._check(self._L.tw_ticket_shift(self._h, ticket[0], C.byref(out)))
         return out.as_tuple()
+
+    def hits(self, ticket):
+        """tw_ticket_hits, before the wait that collects the ticket: the count tw_wait will report for the pair (after the
+        ignore rule).  Does not consume the ticket."""
+        n = C.c_int(0)
+        self._check(self._L.tw_ticket_hits(self._h, ticket[0], C.byref(n)))
+        return n.value
+
+    def overlay(self, ticket, tol, out=None, pitch=None):
+        """tw_ticket_overlay, before the wait that collects the ticket: the pair's diff image (include/twflow.h, "Diff image")
+        as an (h, w, 3) uint8 array.  out None: a fresh numpy array (pageable memory: through the bounce buffer); a uint8
+        numpy array of at least pitch * (h - 1) + 3 * w bytes: rendered into it with rows `pitch` bytes apart (default
+        3 * w) and returned as a view of its pixels; a raw address (int / c_void_p: device memory, or a tw_host_alloc
+        block): rendered there, returns None.  Does not consume the ticket."""
+        tk, w, h = ticket[0], ticket[1], ticket[2]
+        pitch = 3 * w if pitch is None else int(pitch)
+        view = None
+        if out is None:
+            out = np.empty(pitch * h, np.uint8)
+        if isinstance(out, np.ndarray):
+            assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= pitch * (h - 1) + 3 * w
+            flat = out.reshape(-1)
+            view = np.lib.stride_tricks.as_strided(flat, (h, w, 3), (pitch, 3, 1), writeable=False)
+            addr = flat.ctypes.data
+        else:
+            addr = out.value if isinstance(out, C.c_void_p) else int(out)
+        oo = OverlayOut(addr, pitch, OVERLAY_RGB8)
+        self._check(self._L.tw_ticket_overlay(self._h, tk, int(tol), C.byref(oo)))
+        return view
+
+    def overlay_plan(self, expect_addr, target_addr, stride, dst_addr, pitch, w, h):
+        """How tw_overlay_base runs for these addresses, strides and size (twflow_debug.h: tw_debug_overlay_plan), a pure host
+        function: (vec4, pixels per lane, threads, grid x, grid y)."""
+        v = (C.c_int * 5)()
+        if self._L.tw_debug_overlay_plan(int(expect_addr), int(target_addr), int(stride), int(dst_addr), int(pitch), int(w),
+                                         int(h), v, 5) != 5:
+            raise ValueError("no overlay plan for %dx%d" % (w, h))
+        return tuple(v)
+
+    def stage_overlay(self, expect, target, rects, hits, regions, tol, pitch=None, stride=None, misalign=0, fill=0xA5):
+        """tw_overlay_base and tw_overlay_marks alone: expect / target (h, w) uint8 — with `stride` both are copied into rows
+        that far apart first — at device addresses `misalign` bytes off a 256-byte boundary; rects: (x, y, w, h) tuples;
+        hits: (x, y, dx, dy) rows (a float32-exact array or tuples); regions: (x, y, width, height) boxes.  Returns (buf,
+        path): buf [h, pitch] uint8, pre-filled with `fill` — the picture is buf[:, :3 * w] — and the base kernel's path
+        (1: dwords, 0: bytes)."""
+        expect = np.ascontiguousarray(expect, np.uint8)
+        target = np.ascontiguousarray(target, np.uint8)
+        h, w = expect.shape
+        assert target.shape == (h, w)
+        if stride is None:
+            stride = w
+        else:
+            pe = np.full((h, stride), 0xEE, np.uint8)
+            pt = np.full((h, stride), 0xEE, np.uint8)
+            pe[:, :w] = expect
+            pt[:, :w] = target
+            expect, target = pe, pt
+        pitch = 3 * w if pitch is None else int(pitch)
+        rs = (Rect * max(len(rects), 1))(*[Rect(*(int(v) for v in r)) for r in rects])
+        hrec = np.zeros(max(len(hits), 1), OVERLAY_HIT_DTYPE)
+        for i, hrow in enumerate(hits):
+            hrec[i] = (int(hrow[0]), int(hrow[1]), np.float32(hrow[2]), np.float32(hrow[3]))
+        regs = (Region * max(len(regions), 1))()
+        for i, r in enumerate(regions):
+            regs[i].x, regs[i].y, regs[i].width, regs[i].height = (int(v) for v in r[:4])
+        buf = np.full((h, max(pitch, 0)), fill, np.uint8)
+        path = C.c_int(-1)
+        u8p = C.POINTER(C.c_uint8)
+        self._check(self._L.tw_stage_overlay(self._h, expect.ctypes.data_as(u8p), target.ctypes.data_as(u8p), w, h, stride,
+                                             int(misalign), rs, len(rects), hrec.ctypes.data_as(C.c_void_p), len(hits), regs,
+                                             len(regions), int(tol), buf.ctypes.data_as(u8p), pitch, C.byref(path)))
+        return buf, path.value
 
     def wait_count(self, ticket):
         """tw_wait without materialising the vectors (bench inner loop). Returns (n, seconds)."""

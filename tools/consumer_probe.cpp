@@ -12,6 +12,8 @@
 //                                            ends in " changes <count>: [x,y diff=<n> unexplained=<n> max=<diff>,<unexplained>] ..."
 //     S <radius>                             shift for the whole run (ConsumerShared::shift); a response then ends in
 //                                            " shift <x>,<y> applied=<0|1>"
+//     O <dir> <tol>                          diff images for the whole run (ConsumerShared::overlayDir, ::overlayTol); the response
+//                                            of a pair that got one then ends in " overlay <path>"
 //     G <gap>                                hit regions for the whole run (ConsumerShared::regions); a response then ends in
 //                                            " regions <count>: [x,y,w,h n=<hits> peak=(x,y,dx,dy)] ... of: <index per vector>"
 #include <stdio.h>
@@ -55,6 +57,11 @@ int main(int argc, char** argv)
         }
         if (op == "S" && i + 1 < argc) {
             shared.shift = atoi(argv[++i]);
+            continue;
+        }
+        if (op == "O" && i + 2 < argc) {
+            shared.overlayDir = argv[++i];
+            shared.overlayTol = atoi(argv[++i]);
             continue;
         }
         if (op == "I" && i + 1 < argc) {
@@ -120,6 +127,7 @@ int main(int argc, char** argv)
                     printf(" [%d,%d diff=%d unexplained=%d max=%d,%d]", c.x, c.y, c.n_diff, c.n_unexplained, c.max_diff, c.max_unexplained);
             }
             if (r.hasShift) printf(" shift %d,%d applied=%d", r.shift.x, r.shift.y, r.shift.applied ? 1 : 0);
+            if (!r.overlay.empty()) printf(" overlay %s", r.overlay.c_str());
             printf("\n");
         }
         req.stop();

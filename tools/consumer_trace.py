@@ -168,6 +168,12 @@ def with_shift(case, radius):
     return env, budget, ["S", radius] + list(script)
 
 
+def with_overlay(case, directory, tol=16):
+    """the case with diff images on for the whole run (the probe's O: ConsumerShared::overlayDir, ::overlayTol)"""
+    env, budget, script = case
+    return env, budget, ["O", directory, tol] + list(script)
+
+
 def run_case(exe, case, threads, workdir, batch=4):
     """(responses as printed, the trace's text) of one case; every path under `workdir` or the tree reads <dir> / <root>"""
     env_more, budget, script = case
