@@ -21,6 +21,7 @@
 #include <atomic>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -278,6 +279,68 @@ void window_kernel(int block_size, WinCoef& wc)
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Owners of an engine's HIP resources: a member of tw_engine, Ctx or Plan that holds device memory, page-locked memory, an
+// event or a stream is one of these.  Each frees what it holds when it goes, so `delete e` is the whole of an engine's
+// release; each converts to the bare pointer / handle, so kernel arguments, pointer arithmetic and HIP calls read as they
+// would with one.  None can be copied.
+// ---------------------------------------------------------------------------------------------------
+struct DeviceMem {
+    static hipError_t malloc(void** p, size_t n) { return hipMalloc(p, n); }
+    static void free(void* p) { (void)hipFree(p); }
+    static size_t& books(tw_engine* e);  // tw_engine::dev_bytes
+};
+struct PinnedMem {
+    static hipError_t malloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+    static void free(void* p) { (void)hipHostFree(p); }
+    static size_t& books(tw_engine* e);  // tw_engine::pin_bytes
+};
+
+// One allocation: the pointer, its capacity in the buffer's own unit (what grow() compares; 0 for a make() buffer) and its
+// size in bytes as allocated, slack included.  make() and grow() enter that size in the engine's books (tw_debug_memory) at
+// the moment the allocation is made and take it out when they free; alloc() leaves the books to the caller (a plan's tables
+// and the resident store's chunks have totals of their own).  Defined behind tw_engine, which they need whole.
+template <typename T, typename Mem>
+struct Buf {
+    T* p = nullptr;
+    size_t cap = 0, bytes = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap), bytes(o.bytes) { o.p = nullptr, o.cap = o.bytes = 0; }
+    ~Buf()
+    {
+        if (p) Mem::free((void*)p);
+    }
+    operator T*() const { return p; }
+    tw_status alloc(tw_engine* e, size_t nbytes);
+    tw_status make(tw_engine* e, size_t nbytes);
+    tw_status grow(tw_engine* e, size_t new_cap, size_t nbytes, hipStream_t sync = nullptr);
+    void release(tw_engine* e);
+};
+template <typename T>
+using DevBuf = Buf<T, DeviceMem>;
+template <typename T>
+using PinBuf = Buf<T, PinnedMem>;
+
+// An event or a stream.  It is created where it is used, with that site's flags (`&x.h` is what the create call fills).
+template <typename H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept
+    {
+        std::swap(h, o.h);
+        return *this;
+    }
+    ~Handle()
+    {
+        if (h) (void)Destroy(h);
+    }
+    operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+
+// ---------------------------------------------------------------------------------------------------
 // Plan: everything that depends only on (w0, h0, params)
 // ---------------------------------------------------------------------------------------------------
 struct LevelPlan {
@@ -313,8 +376,8 @@ struct Plan {
     int init_mode = 0, init_ix = 1, init_iy = 1, init_tw = 0;
     int *d_ixs = nullptr, *d_ixi = nullptr, *d_iys = nullptr, *d_iyi = nullptr;
     float *d_ixa = nullptr, *d_iyb = nullptr;
-    std::vector<void*> owned;  // device allocations
-    size_t owned_bytes = 0;    // ... and their total size (tw_debug_memory)
+    std::vector<DevBuf<char>> owned;  // device allocations (freed with the plan)
+    size_t owned_bytes = 0;           // ... and their total size (tw_debug_memory)
     unsigned long long last_use = 0;  // engine's plan clock at the last get_plan (LRU eviction)
 };
 
@@ -392,7 +455,7 @@ enum { RSZ_NONE = 0, RSZ_SUBMIT = 1, RSZ_FLUSH_COPY = 2, RSZ_FLUSH_DEV = 3 };
 
 // One batch of pairs: host-side state that must outlive the asynchronous execution.
 struct Ctx {
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_done = nullptr;
+    Event ev_start, ev_stop, ev_done;
     std::vector<Job> jobs;
     int64_t first_ticket = 0;
     bool launched = false;
@@ -402,103 +465,102 @@ struct Ctx {
     bool any_host = false;
     // device copy of the batch's host images (one region per context: the next batch uploads while this one
     // computes) and the event that marks its uploads complete on the copy stream
-    uint8_t* d_img = nullptr;
-    size_t d_img_cap = 0;
-    hipEvent_t ev_h2d = nullptr;
+    DevBuf<uint8_t> d_img;
+    Event ev_h2d;
     // cold-start ramp (round 6): the copy stream is marked when a quarter and a half of a full batch's uploads have been
     // queued (Submit::mark_ramp); a batch that is launched into an IDLE compute stream goes out in up to three pieces, each
     // behind its own mark, instead of waiting for the last upload of the whole batch (flush_ctx)
-    hipEvent_t ev_seg[2] = {nullptr, nullptr};
+    Event ev_seg[2];
     int seg_at[2] = {0, 0};  // pairs queued when the mark was recorded
     int nseg = 0;
     // tw_submit_png8: filtered PNG rows of the batch (2 slots of filt_slot bytes per job) and the job table of
     // tw_png_unfilter, which reconstructs them into d_img on the copy stream before ev_h2d
-    uint8_t *d_filt = nullptr, *d_filt_raw = nullptr;  // d_filt = d_filt_raw + 256 (slack on both sides)
-    size_t d_filt_cap = 0, filt_slot = 0;  // filt_slot: bytes per image of the open batch (0: no filtered image yet)
+    DevBuf<uint8_t> d_filt_raw;
+    uint8_t* d_filt() const { return d_filt_raw ? d_filt_raw + 256 : nullptr; }  // (slack on both sides)
+    size_t filt_slot = 0;  // bytes per image of the open batch (0: no filtered image yet)
     // Both tables are png_table_bytes(cap) long: behind the 2n jobs of a batch with table kinds (tw_submit_png: palette,
     // 1- / 2- / 4-bit gray) go one flag word per image, zero, and the batch's 256-byte gray tables — one upload, as before.
     // The flag words of a batch with palette images come back to h_pflag behind the batch's results.
-    PngJob* d_png = nullptr;
-    PngJob* h_png = nullptr;  // pinned
+    DevBuf<PngJob> d_png;
+    PinBuf<PngJob> h_png;
     bool any_png = false, any_plte = false;
     std::vector<std::array<uint8_t, 256>> png_luts;  // the open batch's gray tables, in the order they were submitted
-    unsigned* h_pflag = nullptr;                     // pinned, [2*cap]
+    PinBuf<unsigned> h_pflag;                        // [2*cap]
     // tw_submit_jpeg (both tables created on the first coefficient image of this context, jpeg_table_bytes(cap) long): the
     // batch's coefficient planes share the d_filt slots with filtered PNG rows; behind the 2n jobs of tw_jpeg_idct go the
     // batch's quantisation tables — one upload, as the gray tables above
-    JpegJob *d_jpg = nullptr, *h_jpg = nullptr;  // h_jpg pinned
+    DevBuf<JpegJob> d_jpg;
+    PinBuf<JpegJob> h_jpg;
     bool any_jpeg = false;
     std::vector<std::array<uint16_t, 64>> jpg_quants;  // the open batch's tables, in the order they were submitted
     long long copy_ops_at_flush = 0;  // tw_engine::copy_ops when this batch was launched
     // ordered hit records of the batch [cap][G]: tw_wait reads them late when a pair has more than HOST_RECS hits,
     // so they belong to the context, not to the engine (a later batch must not overwrite them)
-    ScanRec* d_rec = nullptr;
-    size_t d_rec_cap = 0;
+    DevBuf<ScanRec> d_rec;
     // pinned host memory
-    uint8_t* h_img = nullptr;
-    size_t h_img_cap = 0;
-    const uint8_t** h_ptrs = nullptr;  // [2*cap]
-    int* h_count = nullptr;            // [cap]
-    ScanRec* h_rec = nullptr;          // [cap][HOST_RECS]
+    PinBuf<uint8_t> h_img;
+    PinBuf<const uint8_t*> h_ptrs;  // [2*cap]
+    PinBuf<int> h_count;            // [cap]
+    PinBuf<ScanRec> h_rec;          // [cap][HOST_RECS]
     // tw_submit_*_flow (all created on first use): the per-pair destination table (pinned, [cap]; uploaded to
     // tw_engine::d_fdst), and for host destinations the HBM staging the export writes (cap slots of dense rows in the
     // destination's layout), the event behind each chunk's export that the device-to-host copies wait for, and the
     // event behind the batch's last copy that tw_wait waits for
     bool any_fout = false, any_fout_host = false;
-    FlowDst* h_fdst = nullptr;
-    char* d_fstage = nullptr;
-    size_t d_fstage_cap = 0;
-    hipEvent_t ev_fexp = nullptr, ev_d2h = nullptr;
+    PinBuf<FlowDst> h_fdst;
+    DevBuf<char> d_fstage;
+    Event ev_fexp, ev_d2h;
     long long d2h_ops_at_flush = 0;  // tw_engine::d2h_ops when this batch was launched
     // tw_submit_*_flow_init (created on first use): the per-pair source table of tw_flow_area_init (pinned, [cap]; uploaded
     // to tw_engine::d_fsrc), and the HBM staging of host fields (cap slots of dense rows in the field's layout), filled on
     // the copy stream behind the same marks as the pairs' images
     bool any_init = false, any_init_host = false;
-    FlowDst* h_fsrc = nullptr;
-    char* d_istage = nullptr;
-    size_t d_istage_cap = 0;
+    PinBuf<FlowDst> h_fsrc;
+    DevBuf<char> d_istage;
     // tw_submit_*_sized (all created on the first reconciled pair of this context): d_tsrc = `cap` slots of tsrc_slot bytes
-    // for host targets of up to (w + 5) x (h + 5) pixels at their own size (d_tsrc = d_tsrc_raw + 256), and tw_resize_u8's
+    // for host targets of up to (w + 5) x (h + 5) pixels at their own size (256 bytes of slack in front, as d_filt), and tw_resize_u8's
     // job tables, three of [cap] each — one entry per launch at submit time, the batch's PNG targets, the batch's device
     // targets (three, because each is written while the one before may still be on its way to the device) — with the
     // table of the PNG targets' own tw_png_unfilter launches
-    uint8_t *d_tsrc = nullptr, *d_tsrc_raw = nullptr;
-    size_t d_tsrc_cap = 0, tsrc_slot = 0;
-    ResizeJob *d_rsz = nullptr, *h_rsz = nullptr;  // [3 * cap]
-    PngJob *d_rpng = nullptr, *h_rpng = nullptr;   // [cap]
+    DevBuf<uint8_t> d_tsrc_raw;
+    uint8_t* d_tsrc() const { return d_tsrc_raw ? d_tsrc_raw + 256 : nullptr; }
+    size_t tsrc_slot = 0;
+    DevBuf<ResizeJob> d_rsz;  // [3 * cap]
+    PinBuf<ResizeJob> h_rsz;
+    DevBuf<PngJob> d_rpng;  // [cap]
+    PinBuf<PngJob> h_rpng;
     bool any_resize = false, any_resize_png = false, any_resize_dev = false;
     bool any_keep = false;  // a job of the open batch has a tw_image_keep copy to queue at launch
     // tw_submit_*_ignore (both tables created on the first pair with a non-empty rectangle of this context,
     // mask_table_bytes(cap) long): tw_mask_rects' jobs, one per rectangle of the batch
-    MaskJob *d_msk = nullptr, *h_msk = nullptr;  // h_msk pinned
+    DevBuf<MaskJob> d_msk;
+    PinBuf<MaskJob> h_msk;
     bool any_mask = false;
     // hit regions (TW_OPT_REGIONS; all created when the first batch with the option on is launched from this context):
     // `regions` = the gap of this batch (0: off), taken when its first pair is booked.  The kernel's outputs belong to the
     // context as d_rec does (tw_wait_regions reads region_of late for a pair with more than HOST_RECS hits): counts [cap],
     // kept records [cap][TW_MAX_REGIONS], region_of [cap][G]; their eager copies and the rectangle table are pinned
     int regions = 0;
-    int* d_nreg = nullptr;
-    RegionRec* d_regs = nullptr;
-    int* d_regof = nullptr;
-    size_t d_regof_cap = 0;
-    int* h_nreg = nullptr;        // [cap]
-    RegionRec* h_regs = nullptr;  // [cap][TW_MAX_REGIONS]
-    int* h_regof = nullptr;       // [cap][HOST_RECS]
-    char* h_rgn = nullptr;        // region_table_bytes(cap)
+    DevBuf<int> d_nreg;
+    DevBuf<RegionRec> d_regs;
+    DevBuf<int> d_regof;
+    PinBuf<int> h_nreg;        // [cap]
+    PinBuf<RegionRec> h_regs;  // [cap][TW_MAX_REGIONS]
+    PinBuf<int> h_regof;       // [cap][HOST_RECS]
+    PinBuf<char> h_rgn;        // region_table_bytes(cap)
     // residual (TW_OPT_RESIDUAL; all created when the first batch with the option on is launched from this context):
     // `residual` = the tolerance of this batch (0: off), taken when its first pair is booked.  tw_change_scan's outputs
     // belong to the context as d_rec does (tw_ticket_changes reads the records behind the first HOST_RECS late): counts
     // [cap], records [cap][G]; their eager copies are pinned
     int residual = 0;
-    int* d_nchg = nullptr;
-    ChangeRec* d_chg = nullptr;
-    size_t d_chg_cap = 0;
-    int* h_nchg = nullptr;       // [cap]
-    ChangeRec* h_chg = nullptr;  // [cap][HOST_RECS]
+    DevBuf<int> d_nchg;
+    DevBuf<ChangeRec> d_chg;
+    PinBuf<int> h_nchg;       // [cap]
+    PinBuf<ChangeRec> h_chg;  // [cap][HOST_RECS]
     // shift (TW_OPT_SHIFT): `shift` = the search radius of this batch (0: off), taken when its first pair is booked; the
     // pinned copy of the batch's records ([cap], created when the first batch with the option on is launched from this context)
     int shift = 0;
-    ShiftRec* h_shift = nullptr;
+    PinBuf<ShiftRec> h_shift;
 
     // the batch is collected or dropped: its resident images may return to the store
     void release_images()
@@ -539,7 +601,7 @@ struct Ctx {
 };
 
 struct ProfPair {
-    hipEvent_t a, b;
+    Event a, b;
 };
 
 // what a captured single-pair schedule depends on besides the engine's (fixed) parameters and workspace addresses
@@ -756,77 +818,71 @@ struct tw_engine {
     EngineOptions opt;       // tw_set_option
     explicit tw_engine(const EngineConfig& c) : cfg(c) { opt.poly_f32 = c.poly_f32; }
     int device = 0;
-    hipStream_t stream = nullptr;
+    // what the engine has allocated, in bytes as allocated: Buf::make / grow / release keep them (tw_debug_memory reports them)
+    size_t dev_bytes = 0, pin_bytes = 0;
+    Stream stream;
     Ctx ctx[NCTX];
     int cur = 0;  // context accepting submissions
     int64_t next_ticket = 1;
-    std::map<std::pair<int, int>, Plan*> plans;
+    std::map<std::pair<int, int>, std::unique_ptr<Plan>> plans;
     unsigned long long plan_clock = 0;
-    double* Vd = nullptr;  // running column sums of the box window (5 double planes per pair of a chunk)
+    DevBuf<double> Vd;  // running column sums of the box window (5 double planes per pair of a chunk)
     int copy_sync_skipped = 0;    // batches since the host last synchronised the copy stream (tw_wait)
     long long copy_ops = 0;       // host images queued on the copy stream so far
-    uint8_t* h_bounce = nullptr;  // pinned bounce buffer of tw_submit_png8's pageable inputs
-    size_t h_bounce_cap = 0;
-    size_t Vd_cap = 0;
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    unsigned long long* dbg_stamps = nullptr;  // TW_DEBUG_STAMPS=1: phase stamps of tw_pyr_taps (diagnostic runs only)
+    PinBuf<uint8_t> h_bounce;     // bounce buffer of tw_submit_png8's pageable inputs (capacity in bytes)
+    Stream stream2;
+    Event ev_fork, ev_join;
+    DevBuf<unsigned long long> dbg_stamps;  // TW_DEBUG_STAMPS=1: phase stamps of tw_pyr_taps (diagnostic runs only)
     std::string err;
     // device workspace, shared by all batches (execution is ordered on one stream)
     size_t ws_elems = 0;                 // capacity of I (floats); R = 5x, M = 5x each
-    float *I = nullptr, *R = nullptr, *M[2] = {nullptr, nullptr};
-    std::vector<float*> flow;            // per level, cap (levels>=1) or chunk0 (level 0) pairs x 2 planes
-    std::vector<size_t> flow_cap;
-    float *lat_I = nullptr, *lat_R = nullptr;  // the single-pair schedule's buffers: every level's I and R at once
+    DevBuf<float> I, R, M[2];
+    std::vector<DevBuf<float>> flow;     // per level, cap (levels>=1) or chunk0 (level 0) pairs x 2 planes
+    DevBuf<float> lat_I, lat_R;  // the single-pair schedule's buffers: every level's I and R at once
     size_t lat_cap = 0;  // floats in lat_I (lat_R holds 5x)
-    std::vector<hipEvent_t> lat_ev;
+    std::vector<Event> lat_ev;
     std::map<GraphKey, hipGraphExec_t> lat_graphs;  // captured single-pair schedules (dropped whenever a buffer moves)
     bool graph_capture_failed = false;  // this runtime could not capture the schedule: direct launches from then on
     bool graph_replay() const { return cfg.lat_graph && !graph_capture_failed; }  // TW_LAT_GRAPH=1 still in use
-    hipStream_t copy_stream = nullptr;  // host -> device image uploads, overlapped with the compute stream
+    Stream copy_stream;  // host -> device image uploads, overlapped with the compute stream
     // tw_submit_*_flow: device -> host copies of the flow fields (created when a host destination is first seen, so that
     // an engine that never asks for one keeps its queue use), the copies queued there so far, batches since the host last
     // synchronised it, and the device copy of a batch's destination table ([cap], created on first use)
-    hipStream_t d2h_stream = nullptr;
+    Stream d2h_stream;
     long long d2h_ops = 0;
     int d2h_sync_skipped = 0;
-    FlowDst* d_fdst = nullptr;
-    FlowDst* d_fsrc = nullptr;  // tw_submit_*_flow_init: the device copy of a batch's init source table ([cap], on first use)
-    const uint8_t** d_ptrs = nullptr;  // [2*cap]
-    int* d_count = nullptr;            // [cap]
+    DevBuf<FlowDst> d_fdst;
+    DevBuf<FlowDst> d_fsrc;  // tw_submit_*_flow_init: the device copy of a batch's init source table ([cap], on first use)
+    DevBuf<const uint8_t*> d_ptrs;  // [2*cap]
+    DevBuf<int> d_count;            // [cap]
     // identical pairs (tw_pair_same): 1 where a pair's second image is byte for byte its first — the batch schedule then
     // computes that pair's pyramid levels and polynomial expansions once, at the levels tw_flow_iter runs (it reads R0 as R1)
-    unsigned* d_same = nullptr;        // [cap], of the batch enqueued last; all 0 until a batch schedule fills it
+    DevBuf<unsigned> d_same;           // [cap], of the batch enqueued last; all 0 until a batch schedule fills it
     int same_n = 0;                    // pairs of the batch enqueued last (tw_debug_same_flags)
     bool same_valid = false;           // ... and whether tw_pair_same ran for it
-    float2* d_grid = nullptr;          // [cap][G] dense grid samples (dx,dy)
-    size_t d_grid_cap = 0;
+    DevBuf<float2> d_grid;             // [cap][G] dense grid samples (dx,dy)
     // hit regions (the next batch's gap is opt.regions_gap): the device copy of a batch's
     // rectangle table (region_table_bytes(cap), on first use), tw_hit_regions' label planes for grids that do not fit LDS
     // ([cap][G], on first use), and whether the LDS kernel's dynamic size has been announced to the runtime
-    char* d_rgn = nullptr;
-    int* d_lab = nullptr;
-    size_t d_lab_cap = 0;
+    DevBuf<char> d_rgn;
+    DevBuf<int> d_lab;
     bool rgn_attr = false;
     // residual (the next batch's tolerance is opt.residual_tol): tw_warp_residual's dense
     // cell plane ([cap][G] cells of four ints, on first use) — the engine's, as d_grid: the batch's own tw_change_scan
     // consumes it before the next batch's launches write it
-    int4* d_cells = nullptr;
-    size_t d_cells_cap = 0;
+    DevBuf<int4> d_cells;
     // shift (the next batch's radius is opt.shift_radius): the records of the batch being enqueued ([cap]) and the four
     // profiles of each of its pairs ([cap][2 (w + h)] words), both on first use and the engine's, as d_cells: the batch's own
     // launches consume them, and its result copy reads the records, before the next batch's launches write them
-    ShiftRec* d_shift = nullptr;
-    unsigned* d_sprof = nullptr;
-    size_t d_sprof_cap = 0;
+    DevBuf<ShiftRec> d_shift;
+    DevBuf<unsigned> d_sprof;
     // diff image (tw_ticket_overlay): the staging a picture for a HOST destination is rendered into (dense rows of
     // round_up(3 w, 4) bytes), created by the first such call and grown on demand; device destinations are written in place
-    uint8_t* d_ovl = nullptr;
-    size_t d_ovl_cap = 0;
+    DevBuf<uint8_t> d_ovl;
     // profiling: per kernel class, -2 = off, -1 = every level, k = level k only
     int prof_level[TW_K_COUNT] = {-2, -2, -2, -2, -2};
     std::vector<ProfPair> prof_pending[TW_K_COUNT];
-    std::vector<hipEvent_t> prof_free;
+    std::vector<Event> prof_free;
     // diagnostics (include/twflow_debug.h: tw_debug_launch_counts): launches per kernel family since the engine was created /
     // the counts were last reset, and the pairs (grid z) of each family's latest launch — what lets a test prove WHICH kernel ran
     unsigned long long launches[TW_DF_COUNT] = {};
@@ -835,7 +891,7 @@ struct tw_engine {
     // goes; `free` = offset -> length of its unused ranges, neighbours merged), every image that still owns a block, and the
     // handles a caller may pass in — a handle is looked up here, never dereferenced first
     struct ResChunk {
-        uint8_t* base = nullptr;
+        DevBuf<uint8_t> base;
         size_t bytes = 0;
         std::map<size_t, size_t> free;
     };
@@ -921,7 +977,7 @@ tw_status res_alloc(tw_engine* e, size_t bytes, int* chunk, size_t* off)
         if (pass) break;
         tw_engine::ResChunk ch;
         ch.bytes = std::max(RES_CHUNK, bytes);
-        TW_HIP(e, hipMalloc((void**)&ch.base, ch.bytes + 256));
+        TW_TRY(ch.base.alloc(e, ch.bytes + 256));  // (the store's own total: res_reserved)
         ch.free[0] = ch.bytes;
         e->res_reserved += ch.bytes + 256;
         e->res_chunk_allocs++;
@@ -1035,32 +1091,46 @@ ResizeJob resize_job(const uint8_t* src, int sw, int sh, long long spitch, uint8
     return rj;
 }
 
+// ---- Buf: the engine's allocations and its books ---------------------------------------------------------------------
+size_t& DeviceMem::books(tw_engine* e) { return e->dev_bytes; }
+size_t& PinnedMem::books(tw_engine* e) { return e->pin_bytes; }
+
+template <typename T, typename Mem>
+tw_status Buf<T, Mem>::alloc(tw_engine* e, size_t nbytes)
+{
+    TW_HIP(e, Mem::malloc((void**)&p, nbytes));
+    bytes = nbytes;
+    return TW_OK;
+}
+// A buffer that is made once: `nbytes` (the caller's size, slack included) unless it exists already.
+template <typename T, typename Mem>
+tw_status Buf<T, Mem>::make(tw_engine* e, size_t nbytes)
+{
+    if (p) return TW_OK;
+    TW_TRY(alloc(e, nbytes));
+    Mem::books(e) += bytes;
+    return TW_OK;
+}
+template <typename T, typename Mem>
+void Buf<T, Mem>::release(tw_engine* e)
+{
+    if (p) Mem::free((void*)p);
+    Mem::books(e) -= bytes;
+    p = nullptr;
+    cap = bytes = 0;
+}
 // The one "grow this buffer" step (buffers grow, never shrink): when `new_cap` (in the buffer's own unit) exceeds `cap`,
 // wait for `sync` if one is given (the stream whose queued work may still touch the old buffer), free the buffer and
-// allocate `bytes` (the caller's size, slack included).  Pointer and capacity are cleared BEFORE the allocation, so that
-// a failed one leaves an empty buffer, not a dangling one, and the next call tries again.
-template <typename T>
-tw_status grow_device(tw_engine* e, T*& p, size_t& cap, size_t new_cap, size_t bytes, hipStream_t sync = nullptr)
+// allocate `nbytes`.  Pointer and capacity are cleared BEFORE the allocation, so that a failed one leaves an empty buffer,
+// not a dangling one, and the next call tries again.
+template <typename T, typename Mem>
+tw_status Buf<T, Mem>::grow(tw_engine* e, size_t new_cap, size_t nbytes, hipStream_t sync)
 {
     if (new_cap <= cap) return TW_OK;
     if (sync) TW_HIP(e, hipStreamSynchronize(sync));
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    TW_HIP(e, hipMalloc((void**)&p, bytes));
+    release(e);
+    TW_TRY(make(e, nbytes));
     cap = new_cap;
-    return TW_OK;
-}
-// ... and the same for page-locked host memory
-template <typename T>
-tw_status grow_pinned(tw_engine* e, T*& p, size_t& cap, size_t bytes)
-{
-    if (bytes <= cap) return TW_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    TW_HIP(e, hipHostMalloc((void**)&p, bytes, hipHostMallocDefault));
-    cap = bytes;
     return TW_OK;
 }
 
@@ -1075,7 +1145,7 @@ bool host_range_is_page_locked(const void* p, size_t n);  // PinRegistry::covers
 constexpr size_t BOUNCE_CHUNK = 8u << 20;
 tw_status bounce_reserve(tw_engine* e, size_t bytes)
 {
-    return grow_pinned(e, e->h_bounce, e->h_bounce_cap, bytes);
+    return e->h_bounce.grow(e, bytes, bytes);
 }
 // synchronous host -> device / device -> host copies of any host pointer (null stream, like the hipMemcpy they replace)
 tw_status h2d_sync(tw_engine* e, void* d, const void* h, size_t n)
@@ -1129,12 +1199,12 @@ struct Tmp {
 template <typename T>
 tw_status upload_vec(tw_engine* e, Plan* pl, const std::vector<T>& v, T** out)
 {
-    void* d = nullptr;
-    TW_HIP(e, hipMalloc(&d, v.size() * sizeof(T) + 16));
-    pl->owned.push_back(d);
-    pl->owned_bytes += v.size() * sizeof(T) + 16;
-    TW_TRY(h2d_sync(e, d, v.data(), v.size() * sizeof(T)));
-    *out = (T*)d;
+    DevBuf<char> d;
+    TW_TRY(d.alloc(e, v.size() * sizeof(T) + 16));  // (the plan's own total: owned_bytes)
+    pl->owned_bytes += d.bytes;
+    TW_TRY(h2d_sync(e, d.p, v.data(), v.size() * sizeof(T)));
+    *out = (T*)d.p;
+    pl->owned.push_back(std::move(d));
     return TW_OK;
 }
 
@@ -1182,12 +1252,6 @@ void drop_graphs(tw_engine* e)
 {
     for (auto& kv : e->lat_graphs) (void)hipGraphExecDestroy(kv.second);
     e->lat_graphs.clear();
-}
-
-void free_plan(Plan* pl)
-{
-    for (void* d : pl->owned) (void)hipFree(d);
-    delete pl;
 }
 
 // pairs one launch covers at a level of w x h pixels (level index k): enough 8-row x 240-column tiles of two images to cover
@@ -1360,7 +1424,7 @@ tw_status get_plan(tw_engine* e, int w0, int h0, Plan** out)
     auto it = e->plans.find(key);
     if (it != e->plans.end()) {
         it->second->last_use = ++e->plan_clock;
-        *out = it->second;
+        *out = it->second.get();
         return TW_OK;
     }
     if (e->plans.size() >= 64) {
@@ -1374,22 +1438,18 @@ tw_status get_plan(tw_engine* e, int w0, int h0, Plan** out)
         TW_HIP(e, hipStreamSynchronize(e->stream));
         TW_HIP(e, hipStreamSynchronize(e->stream2));
         drop_graphs(e);
-        free_plan(victim->second);
         e->plans.erase(victim);
     }
-    Plan* pl = new Plan();
+    std::unique_ptr<Plan> pl(new Plan());
     pl->last_use = ++e->plan_clock;
     PlanTables tabs;
     const char* why = "";
-    tw_status s = plan_geometry(e->cfg, w0, h0, pl, &tabs, &why);
+    tw_status s = plan_geometry(e->cfg, w0, h0, pl.get(), &tabs, &why);
     if (s) e->err = why;
-    else s = upload_plan_tables(e, pl, tabs);
-    if (s) {
-        free_plan(pl);
-        return s;
-    }
-    e->plans[key] = pl;
-    *out = pl;
+    else s = upload_plan_tables(e, pl.get(), tabs);
+    if (s) return s;
+    *out = pl.get();
+    e->plans[key] = std::move(pl);
     return TW_OK;
 }
 
@@ -1399,14 +1459,14 @@ tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span)
     size_t need = 0;
     for (const LevelPlan& L : pl->lv) need = std::max(need, (size_t)L.ps * 2 * L.chunk);
     need *= e->cfg.lanes;  // one workspace per lane, carved from the same allocations
-    bool grow = need > e->ws_elems || e->flow.size() < pl->lv.size() || (e->cfg.box && need / 2 * 5 > e->Vd_cap);
+    bool grow = need > e->ws_elems || e->flow.size() < pl->lv.size() || (e->cfg.box && need / 2 * 5 > e->Vd.cap);
     if (!grow)
         for (size_t k = 0; k < pl->lv.size(); k++) {
             const size_t fc = (size_t)pl->lv[k].ps * 2 * (k == 0 ? pl->lv[0].chunk * e->cfg.lanes : e->cfg.cap);
-            if (fc > e->flow_cap[k]) grow = true;
+            if (fc > e->flow[k].cap) grow = true;
         }
     const size_t G = span > 0 ? (size_t)tw_grid_capacity(pl->w0, pl->h0, span) : 0;
-    if (G * e->cfg.cap > e->d_grid_cap) grow = true;
+    if (G * e->cfg.cap > e->d_grid.cap) grow = true;
     size_t need_lat = 0;
     for (const LevelPlan& L : pl->lv) need_lat += (size_t)L.ps * 2;
     if (e->cfg.lat_streams && (need_lat > e->lat_cap || e->lat_ev.size() < pl->lv.size())) grow = true;
@@ -1414,55 +1474,44 @@ tw_status reserve_workspace(tw_engine* e, const Plan* pl, int span)
     TW_HIP(e, hipStreamSynchronize(e->stream));
     TW_HIP(e, hipStreamSynchronize(e->stream2));
     drop_graphs(e);
-    if (need > e->ws_elems) {
-        if (e->I) (void)hipFree(e->I);
-        if (e->R) (void)hipFree(e->R);
-        if (e->M[0]) (void)hipFree(e->M[0]);
-        if (e->M[1]) (void)hipFree(e->M[1]);
-        e->I = e->R = e->M[0] = e->M[1] = nullptr;
+    if (need > e->ws_elems) {  // (all four go before the first comes back; ws_elems stands for all four)
         e->ws_elems = 0;
-        TW_HIP(e, hipMalloc((void**)&e->I, need * 4 + 256));
-        TW_HIP(e, hipMalloc((void**)&e->R, need * 5 * 4 + 256));
-        TW_HIP(e, hipMalloc((void**)&e->M[0], need / 2 * 5 * 4 + 256));
-        TW_HIP(e, hipMalloc((void**)&e->M[1], need / 2 * 5 * 4 + 256));
+        for (DevBuf<float>* b : {&e->I, &e->R, &e->M[0], &e->M[1]}) b->release(e);
+        TW_TRY(e->I.make(e, need * 4 + 256));
+        TW_TRY(e->R.make(e, need * 5 * 4 + 256));
+        TW_TRY(e->M[0].make(e, need / 2 * 5 * 4 + 256));
+        TW_TRY(e->M[1].make(e, need / 2 * 5 * 4 + 256));
         e->ws_elems = need;
     }
     if (e->cfg.lat_streams && need_lat > e->lat_cap) {
-        if (e->lat_I) (void)hipFree(e->lat_I);
-        if (e->lat_R) (void)hipFree(e->lat_R);
-        e->lat_I = e->lat_R = nullptr;
         e->lat_cap = 0;
-        TW_HIP(e, hipMalloc((void**)&e->lat_I, need_lat * 4 + 256));
-        TW_HIP(e, hipMalloc((void**)&e->lat_R, need_lat * 5 * 4 + 256));
+        for (DevBuf<float>* b : {&e->lat_I, &e->lat_R}) b->release(e);
+        TW_TRY(e->lat_I.make(e, need_lat * 4 + 256));
+        TW_TRY(e->lat_R.make(e, need_lat * 5 * 4 + 256));
         e->lat_cap = need_lat;
     }
     while (e->cfg.lat_streams && e->lat_ev.size() < pl->lv.size()) {
-        hipEvent_t ev = nullptr;
-        TW_HIP(e, hipEventCreateWithFlags(&ev, e->cfg.lat_evtiming ? hipEventDefault : hipEventDisableTiming));
-        e->lat_ev.push_back(ev);
+        Event ev;
+        TW_HIP(e, hipEventCreateWithFlags(&ev.h, e->cfg.lat_evtiming ? hipEventDefault : hipEventDisableTiming));
+        e->lat_ev.push_back(std::move(ev));
     }
-    if (e->cfg.box) TW_TRY(grow_device(e, e->Vd, e->Vd_cap, need / 2 * 5, need / 2 * 5 * sizeof(double) + 256));
-    if (e->flow.size() < pl->lv.size()) {
-        e->flow.resize(pl->lv.size(), nullptr);
-        e->flow_cap.resize(pl->lv.size(), 0);
-    }
+    if (e->cfg.box) TW_TRY(e->Vd.grow(e, need / 2 * 5, need / 2 * 5 * sizeof(double) + 256));
+    if (e->flow.size() < pl->lv.size()) e->flow.resize(pl->lv.size());
     for (size_t k = 0; k < pl->lv.size(); k++) {
         const size_t fc = (size_t)pl->lv[k].ps * 2 * (k == 0 ? pl->lv[0].chunk * e->cfg.lanes : e->cfg.cap);
-        TW_TRY(grow_device(e, e->flow[k], e->flow_cap[k], fc, fc * 4 + 256));
+        TW_TRY(e->flow[k].grow(e, fc, fc * 4 + 256));
     }
-    return grow_device(e, e->d_grid, e->d_grid_cap, G * e->cfg.cap, G * e->cfg.cap * sizeof(float2) + 256);
+    return e->d_grid.grow(e, G * e->cfg.cap, G * e->cfg.cap * sizeof(float2) + 256);
 }
 
 // ---- profiling hooks -------------------------------------------------------------------------------
-hipEvent_t prof_event(tw_engine* e)
+Event prof_event(tw_engine* e)
 {
+    Event ev;
     if (!e->prof_free.empty()) {
-        hipEvent_t ev = e->prof_free.back();
+        ev = std::move(e->prof_free.back());
         e->prof_free.pop_back();
-        return ev;
-    }
-    hipEvent_t ev = nullptr;
-    (void)hipEventCreate(&ev);
+    } else (void)hipEventCreate(&ev.h);
     return ev;
 }
 
@@ -1485,7 +1534,7 @@ struct ProfScope {
     {
         if (on) {
             (void)hipEventRecord(pp.b, st);
-            e->prof_pending[kc].push_back(pp);
+            e->prof_pending[kc].push_back(std::move(pp));
         }
     }
 };
@@ -2652,7 +2701,7 @@ BatchTraits with_engine_state(const tw_engine* e, BatchTraits t)
 const Plan* plan_geometry_of(const tw_engine* e, int width, int height, Plan* scratch)
 {
     const auto it = e->plans.find(std::make_pair(width, height));
-    if (it != e->plans.end()) return it->second;
+    if (it != e->plans.end()) return it->second.get();
     PlanTables tabs;
     const char* why = "";
     if (width < 1 || height < 1 || plan_geometry(e->cfg, width, height, scratch, &tabs, &why) != TW_OK) return nullptr;
@@ -2737,13 +2786,13 @@ struct BatchEnqueue {
             gh = (pl->lv[0].h + c.span - 1) / c.span;
             // this context has no results outstanding (it is being launched), nothing on the stream uses its records
             const size_t need_rec = (size_t)tw_grid_capacity(c.w, c.h, c.span) * e->cfg.cap;
-            TW_TRY(grow_device(e, c.d_rec, c.d_rec_cap, need_rec, need_rec * sizeof(ScanRec) + 256));
+            TW_TRY(c.d_rec.grow(e, need_rec, need_rec * sizeof(ScanRec) + 256));
             if (c.regions) TW_TRY(reserve_region_buffers(need_rec));
             if (c.residual) TW_TRY(reserve_residual_buffers(need_rec));
         }
         if (c.shift) TW_TRY(reserve_shift_buffers());
         // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
-        if (c.any_fout_host) TW_TRY(grow_device(e, c.d_fstage, c.d_fstage_cap, fslot * e->cfg.cap, fslot * e->cfg.cap + 256));
+        if (c.any_fout_host) TW_TRY(c.d_fstage.grow(e, fslot * e->cfg.cap, fslot * e->cfg.cap + 256));
         return TW_OK;
     }
 
@@ -2751,18 +2800,18 @@ struct BatchEnqueue {
     tw_status reserve_region_buffers(size_t need_rec)
     {
         const size_t cap = (size_t)e->cfg.cap;
-        if (!e->d_rgn) TW_HIP(e, hipMalloc((void**)&e->d_rgn, region_table_bytes(e->cfg.cap) + 256));
-        if (!c.h_rgn) TW_HIP(e, hipHostMalloc((void**)&c.h_rgn, region_table_bytes(e->cfg.cap), hipHostMallocDefault));
-        if (!c.d_nreg) TW_HIP(e, hipMalloc((void**)&c.d_nreg, sizeof(int) * cap + 256));
-        if (!c.d_regs) TW_HIP(e, hipMalloc((void**)&c.d_regs, sizeof(RegionRec) * TW_MAX_REGIONS * cap + 256));
-        if (!c.h_nreg) TW_HIP(e, hipHostMalloc((void**)&c.h_nreg, sizeof(int) * cap, hipHostMallocDefault));
-        if (!c.h_regs) TW_HIP(e, hipHostMalloc((void**)&c.h_regs, sizeof(RegionRec) * TW_MAX_REGIONS * cap, hipHostMallocDefault));
-        if (!c.h_regof) TW_HIP(e, hipHostMalloc((void**)&c.h_regof, sizeof(int) * HOST_RECS * cap, hipHostMallocDefault));
+        TW_TRY(e->d_rgn.make(e, region_table_bytes(e->cfg.cap) + 256));
+        TW_TRY(c.h_rgn.make(e, region_table_bytes(e->cfg.cap)));
+        TW_TRY(c.d_nreg.make(e, sizeof(int) * cap + 256));
+        TW_TRY(c.d_regs.make(e, sizeof(RegionRec) * TW_MAX_REGIONS * cap + 256));
+        TW_TRY(c.h_nreg.make(e, sizeof(int) * cap));
+        TW_TRY(c.h_regs.make(e, sizeof(RegionRec) * TW_MAX_REGIONS * cap));
+        TW_TRY(c.h_regof.make(e, sizeof(int) * HOST_RECS * cap));
         // (this context has no results outstanding, as for d_rec)
-        TW_TRY(grow_device(e, c.d_regof, c.d_regof_cap, need_rec, need_rec * sizeof(int) + 256));
+        TW_TRY(c.d_regof.grow(e, need_rec, need_rec * sizeof(int) + 256));
         // the label planes are the engine's: an earlier batch's launch may still be using them
         if ((size_t)gw * gh > (size_t)RGN_LDS_POINTS)
-            TW_TRY(grow_device(e, e->d_lab, e->d_lab_cap, need_rec, need_rec * sizeof(int) + 256, e->stream));
+            TW_TRY(e->d_lab.grow(e, need_rec, need_rec * sizeof(int) + 256, e->stream));
         return TW_OK;
     }
 
@@ -2770,13 +2819,13 @@ struct BatchEnqueue {
     tw_status reserve_residual_buffers(size_t need_rec)
     {
         const size_t cap = (size_t)e->cfg.cap;
-        if (!c.d_nchg) TW_HIP(e, hipMalloc((void**)&c.d_nchg, sizeof(int) * cap + 256));
-        if (!c.h_nchg) TW_HIP(e, hipHostMalloc((void**)&c.h_nchg, sizeof(int) * cap, hipHostMallocDefault));
-        if (!c.h_chg) TW_HIP(e, hipHostMalloc((void**)&c.h_chg, sizeof(ChangeRec) * HOST_RECS * cap, hipHostMallocDefault));
+        TW_TRY(c.d_nchg.make(e, sizeof(int) * cap + 256));
+        TW_TRY(c.h_nchg.make(e, sizeof(int) * cap));
+        TW_TRY(c.h_chg.make(e, sizeof(ChangeRec) * HOST_RECS * cap));
         // (this context has no results outstanding, as for d_rec)
-        TW_TRY(grow_device(e, c.d_chg, c.d_chg_cap, need_rec, need_rec * sizeof(ChangeRec) + 256));
+        TW_TRY(c.d_chg.grow(e, need_rec, need_rec * sizeof(ChangeRec) + 256));
         // the cell plane is the engine's: an earlier batch's launches may still be using it
-        TW_TRY(grow_device(e, e->d_cells, e->d_cells_cap, need_rec, need_rec * sizeof(int4) + 256, e->stream));
+        TW_TRY(e->d_cells.grow(e, need_rec, need_rec * sizeof(int4) + 256, e->stream));
         return TW_OK;
     }
 
@@ -2785,10 +2834,10 @@ struct BatchEnqueue {
     tw_status reserve_shift_buffers()
     {
         const size_t cap = (size_t)e->cfg.cap;
-        if (!e->d_shift) TW_HIP(e, hipMalloc((void**)&e->d_shift, sizeof(ShiftRec) * cap + 256));
-        if (!c.h_shift) TW_HIP(e, hipHostMalloc((void**)&c.h_shift, sizeof(ShiftRec) * cap, hipHostMallocDefault));
+        TW_TRY(e->d_shift.make(e, sizeof(ShiftRec) * cap + 256));
+        TW_TRY(c.h_shift.make(e, sizeof(ShiftRec) * cap));
         const size_t need = 2 * ((size_t)c.w + c.h) * cap;
-        TW_TRY(grow_device(e, e->d_sprof, e->d_sprof_cap, need, need * sizeof(unsigned) + 256, e->stream));
+        TW_TRY(e->d_sprof.grow(e, need, need * sizeof(unsigned) + 256, e->stream));
         return TW_OK;
     }
 
@@ -2802,7 +2851,7 @@ struct BatchEnqueue {
                 PngJob& pj = c.h_png[2 * j + q];
                 // (a target of another size has a launch of its own below: the batch-wide one sees a gray image)
                 pj.ch = q && c.jobs[j].rkind == RSZ_FLUSH_COPY ? 0 : c.jobs[j].png_ch[q];
-                pj.src = c.d_filt ? c.d_filt + c.filt_slot * (size_t)(2 * j + q) : nullptr;
+                pj.src = c.d_filt() ? c.d_filt() + c.filt_slot * (size_t)(2 * j + q) : nullptr;
                 pj.dst = c.d_img + npx * (size_t)(2 * j + q);
                 fill_png_kind(pj, j, q);
             }
@@ -2840,8 +2889,8 @@ struct BatchEnqueue {
                 jj = JpegJob{};
                 if (jb.jpg_bw[q] == 0) continue;
                 const bool own_size = q && jb.rkind == RSZ_FLUSH_COPY;
-                jj.coef = (const int16_t*)(c.d_filt + c.filt_slot * (size_t)(2 * j + q));
-                jj.dst = own_size ? c.d_tsrc + c.tsrc_slot * (size_t)j : c.d_img + npx * (size_t)(2 * j + q);
+                jj.coef = (const int16_t*)(c.d_filt() + c.filt_slot * (size_t)(2 * j + q));
+                jj.dst = own_size ? c.d_tsrc() + c.tsrc_slot * (size_t)j : c.d_img + npx * (size_t)(2 * j + q);
                 jj.quant = d_quants + 64 * (size_t)jb.jpg_q[q];
                 jj.w = own_size ? jb.tw : c.w;
                 jj.h = own_size ? jb.th : c.h;
@@ -2892,7 +2941,7 @@ struct BatchEnqueue {
             const Job& jb = c.jobs[j];
             const bool on = jb.rkind == RSZ_FLUSH_COPY;
             hr[j] = ResizeJob{};
-            if (on) hr[j] = resize_job(c.d_tsrc + c.tsrc_slot * (size_t)j, jb.tw, jb.th, jb.tw,
+            if (on) hr[j] = resize_job(c.d_tsrc() + c.tsrc_slot * (size_t)j, jb.tw, jb.th, jb.tw,
                                        c.d_img + npx * (size_t)(2 * j + 1), c.w, c.h, c.w);
             if (on && jb.png_ch[1] > 0) order.push_back(j);
         }
@@ -2903,8 +2952,8 @@ struct BatchEnqueue {
             const int j = order[k];
             PngJob& pj = c.h_rpng[k];
             pj.ch = c.jobs[j].png_ch[1];
-            pj.src = c.d_filt + c.filt_slot * (size_t)(2 * j + 1);
-            pj.dst = c.d_tsrc + c.tsrc_slot * (size_t)j;
+            pj.src = c.d_filt() + c.filt_slot * (size_t)(2 * j + 1);
+            pj.dst = c.d_tsrc() + c.tsrc_slot * (size_t)j;
             fill_png_kind(pj, j, 1);
         }
         if (!order.empty())
@@ -3074,7 +3123,7 @@ struct BatchEnqueue {
         }
         if (c.regions && c.any_mask && c.span > 0) {
             // tw_hit_regions leaves out the grid points tw_wait leaves out: the pairs' clipped rectangles, one upload
-            int* cnt = (int*)c.h_rgn;
+            int* cnt = (int*)c.h_rgn.p;
             tw_rect* rects = (tw_rect*)(c.h_rgn + region_rects_off(e->cfg.cap));
             for (int j = 0; j < n; j++) {
                 const std::vector<tw_rect>& ign = c.jobs[j].ign;
@@ -3201,7 +3250,7 @@ struct BatchEnqueue {
                 ra.h = c.h;
                 ra.gap = c.regions;
                 ra.thr2 = a.thr2;
-                ra.nrect = c.any_mask ? (const int*)e->d_rgn : nullptr;
+                ra.nrect = c.any_mask ? (const int*)e->d_rgn.p : nullptr;
                 ra.rects = (const int4*)(e->d_rgn + region_rects_off(e->cfg.cap));
                 ra.lab = e->d_lab;
                 ra.n_regions = c.d_nreg;
@@ -4064,13 +4113,13 @@ struct Submit {
         TW_HIP(e, hipSetDevice(e->device));
         if (s.fo) {
             TW_TRY(check_flow_out(e, s.fo, s.width, s.height, &fo_host));
-            if (!e->d_fdst) TW_HIP(e, hipMalloc((void**)&e->d_fdst, sizeof(FlowDst) * (size_t)e->cfg.cap + 256));
-            if (fo_host && !e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
+            TW_TRY(e->d_fdst.make(e, sizeof(FlowDst) * (size_t)e->cfg.cap + 256));
+            if (fo_host && !e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream.h, hipStreamNonBlocking));
         }
         if (s.fi) {
             TW_TRY(check_flow_field(e, s.fi->data, s.fi->pitch, s.fi->layout, s.width, s.height, "initial flow field",
                                     &fi_kind));
-            if (!e->d_fsrc) TW_HIP(e, hipMalloc((void**)&e->d_fsrc, sizeof(FlowDst) * (size_t)e->cfg.cap + 256));
+            TW_TRY(e->d_fsrc.make(e, sizeof(FlowDst) * (size_t)e->cfg.cap + 256));
         }
         return TW_OK;
     }
@@ -4108,11 +4157,11 @@ struct Submit {
     tw_status reserve_context_tables()
     {
         if (s.fo) {
-            if (!c->h_fdst) TW_HIP(e, hipHostMalloc((void**)&c->h_fdst, sizeof(FlowDst) * (size_t)e->cfg.cap, hipHostMallocDefault));
-            if (!c->ev_fexp) TW_HIP(e, hipEventCreateWithFlags(&c->ev_fexp, hipEventDisableTiming));
-            if (!c->ev_d2h) TW_HIP(e, hipEventCreateWithFlags(&c->ev_d2h, hipEventDisableTiming));
+            TW_TRY(c->h_fdst.make(e, sizeof(FlowDst) * (size_t)e->cfg.cap));
+            if (!c->ev_fexp) TW_HIP(e, hipEventCreateWithFlags(&c->ev_fexp.h, hipEventDisableTiming));
+            if (!c->ev_d2h) TW_HIP(e, hipEventCreateWithFlags(&c->ev_d2h.h, hipEventDisableTiming));
         }
-        if (s.fi && !c->h_fsrc) TW_HIP(e, hipHostMalloc((void**)&c->h_fsrc, sizeof(FlowDst) * (size_t)e->cfg.cap, hipHostMallocDefault));
+        if (s.fi) TW_TRY(c->h_fsrc.make(e, sizeof(FlowDst) * (size_t)e->cfg.cap));
         return TW_OK;
     }
 
@@ -4123,7 +4172,7 @@ struct Submit {
         if (!s.fi || fi_kind == 0) return TW_OK;
         const size_t fslot = flow_stage_slot(s.width, s.height);
         // (grows only on the first host field of a batch: one size per batch; this context's earlier ones are waited)
-        TW_TRY(grow_device(e, c->d_istage, c->d_istage_cap, fslot * e->cfg.cap, fslot * e->cfg.cap + 256, e->copy_stream));
+        TW_TRY(c->d_istage.grow(e, fslot * e->cfg.cap, fslot * e->cfg.cap + 256, e->copy_stream));
         char* dst = c->d_istage + fslot * c->jobs.size();
         const size_t row = flow_row_bytes(s.width, s.fi->layout), rows = flow_rows(s.height, s.fi->layout);
         TW_TRY(fi_kind == 1 ? upload_in_place(dst, s.fi->data, (size_t)s.fi->pitch, row, rows)
@@ -4147,7 +4196,7 @@ struct Submit {
         if (!host) return resize ? stage_device_target() : TW_OK;
         const size_t npx = staged_image_bytes(s.width, s.height);
         // (grows only on the first job of a batch: all jobs of a batch have one size)
-        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, npx * 2 * e->cfg.cap, npx * 2 * e->cfg.cap + 256, e->copy_stream));
+        TW_TRY(c->d_img.grow(e, npx * 2 * e->cfg.cap, npx * 2 * e->cfg.cap + 256, e->copy_stream));
         TW_TRY(png || jpeg ? stage_png_rows(npx) : stage_gray_pair(npx));
         jb.h_a = s.h_a;
         jb.h_b = s.h_b;
@@ -4160,8 +4209,8 @@ struct Submit {
     // what tw_jpeg_idct needs once per context
     tw_status reserve_jpeg_tables()
     {
-        if (!c->h_jpg) TW_HIP(e, hipHostMalloc((void**)&c->h_jpg, jpeg_table_bytes(e->cfg.cap), hipHostMallocDefault));
-        if (!c->d_jpg) TW_HIP(e, hipMalloc((void**)&c->d_jpg, jpeg_table_bytes(e->cfg.cap) + 256));
+        TW_TRY(c->h_jpg.make(e, jpeg_table_bytes(e->cfg.cap)));
+        TW_TRY(c->d_jpg.make(e, jpeg_table_bytes(e->cfg.cap) + 256));
         c->jpg_quants.reserve(2 * (size_t)e->cfg.cap);
         return TW_OK;
     }
@@ -4169,8 +4218,8 @@ struct Submit {
     // what tw_mask_rects needs once per context
     tw_status reserve_mask_tables()
     {
-        if (!c->h_msk) TW_HIP(e, hipHostMalloc((void**)&c->h_msk, mask_table_bytes(e->cfg.cap), hipHostMallocDefault));
-        if (!c->d_msk) TW_HIP(e, hipMalloc((void**)&c->d_msk, mask_table_bytes(e->cfg.cap) + 256));
+        TW_TRY(c->h_msk.make(e, mask_table_bytes(e->cfg.cap)));
+        TW_TRY(c->d_msk.make(e, mask_table_bytes(e->cfg.cap) + 256));
         return TW_OK;
     }
 
@@ -4181,18 +4230,16 @@ struct Submit {
         const size_t j = c->jobs.size();
         if (c->filt_slot == 0) {
             // first filtered image of this batch: slots as large as the region allows, at least what it needs
-            const size_t slot = std::max(filt_need(), c->d_filt_cap / (2 * (size_t)e->cfg.cap) / 256 * 256);
+            const size_t slot = std::max(filt_need(), c->d_filt_raw.cap / (2 * (size_t)e->cfg.cap) / 256 * 256);
             // 256 bytes of slack on either side: tw_png_unfilter fetches whole 16-byte groups and may read a few
             // bytes before the first and after the last row of an image
             const size_t nbytes = slot * 2 * (size_t)e->cfg.cap;
-            const tw_status r = grow_device(e, c->d_filt_raw, c->d_filt_cap, nbytes, nbytes + 512, e->copy_stream);
-            c->d_filt = c->d_filt_raw ? c->d_filt_raw + 256 : nullptr;  // (whatever became of the region)
-            if (r) return r;
+            TW_TRY(c->d_filt_raw.grow(e, nbytes, nbytes + 512, e->copy_stream));
             // (only now — a failed synchronise / allocation above leaves filt_slot at 0, so that the next
             // filtered image of this batch tries again instead of copying to a null region)
             c->filt_slot = slot;
         }
-        if (!c->d_filt) {
+        if (!c->d_filt()) {
             e->err = "tw_submit_png8: no device region for the filtered rows";
             return TW_E_NOMEM;
         }
@@ -4205,8 +4252,8 @@ struct Submit {
             const int wq = q ? tw : s.width, hq = q ? th : s.height;
             const size_t nb = jl[q] ? jpeg_coef_bytes(jl[q]) : chs[q] ? png_rows_bytes(wq, hq, chs[q], bits[q]) : (size_t)wq * hq;
             // (a gray target of another size waits in its d_tsrc slot for the batch's tw_resize_u8 launch)
-            uint8_t* dst = chs[q] || jl[q] ? c->d_filt + c->filt_slot * (2 * j + q)
-                                  : (q && resize) ? c->d_tsrc + c->tsrc_slot * j : c->d_img + npx * (2 * j + q);
+            uint8_t* dst = chs[q] || jl[q] ? c->d_filt() + c->filt_slot * (2 * j + q)
+                                  : (q && resize) ? c->d_tsrc() + c->tsrc_slot * j : c->d_img + npx * (2 * j + q);
             TW_TRY(pin_registry().covers(src[q], nb) ? upload_in_place(dst, src[q], nb, nb, 1)
                                                      : upload_through_bounce((char*)dst, src[q], nb, nb, 1));
         }
@@ -4248,7 +4295,7 @@ struct Submit {
         if (s.res) {
             // only the target: page-locked in place, pageable through its slot of the pinned ring (the expected image is resident)
             if (pin_registry().covers(s.h_b, span_b)) return upload_in_place(dst_b, s.h_b, (size_t)tstride, w, h);
-            TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, npx * 2 * e->cfg.cap));
+            TW_TRY(c->h_img.grow(e, npx * 2 * e->cfg.cap, npx * 2 * e->cfg.cap));
             uint8_t* db = c->h_img + at + npx;
             for (size_t y = 0; y < h; y++) memcpy(db + y * w, s.h_b + y * (size_t)tstride, w);
             TW_HIP(e, hipMemcpyAsync(dst_b, db, w * h, hipMemcpyHostToDevice, e->copy_stream));
@@ -4261,7 +4308,7 @@ struct Submit {
         // pageable: not through the bounce buffer — the pair is copied to its own slots of the context's pinned ring
         // (nothing to wait for) and goes up as one transfer of both images, queued now: it overlaps the caller's next
         // submit and whatever the compute stream is still doing for the previous batch
-        TW_TRY(grow_pinned(e, c->h_img, c->h_img_cap, npx * 2 * e->cfg.cap));
+        TW_TRY(c->h_img.grow(e, npx * 2 * e->cfg.cap, npx * 2 * e->cfg.cap));
         uint8_t* da = c->h_img + at;
         for (size_t y = 0; y < h; y++) {
             memcpy(da + y * w, s.h_a + y * (size_t)s.stride, w);
@@ -4277,15 +4324,13 @@ struct Submit {
     tw_status reserve_resize_tables()
     {
         const size_t n = (size_t)e->cfg.cap;
-        if (!c->h_rsz) TW_HIP(e, hipHostMalloc((void**)&c->h_rsz, sizeof(ResizeJob) * 3 * n, hipHostMallocDefault));
-        if (!c->d_rsz) TW_HIP(e, hipMalloc((void**)&c->d_rsz, sizeof(ResizeJob) * 3 * n + 256));
-        if (!c->h_rpng) TW_HIP(e, hipHostMalloc((void**)&c->h_rpng, sizeof(PngJob) * n, hipHostMallocDefault));
-        if (!c->d_rpng) TW_HIP(e, hipMalloc((void**)&c->d_rpng, sizeof(PngJob) * n + 256));
+        TW_TRY(c->h_rsz.make(e, sizeof(ResizeJob) * 3 * n));
+        TW_TRY(c->d_rsz.make(e, sizeof(ResizeJob) * 3 * n + 256));
+        TW_TRY(c->h_rpng.make(e, sizeof(PngJob) * n));
+        TW_TRY(c->d_rpng.make(e, sizeof(PngJob) * n + 256));
         if (!host) return TW_OK;  // (a device target is read in place)
         const size_t slot = staged_image_bytes(s.width + 5, s.height + 5), nbytes = slot * n;
-        const tw_status r = grow_device(e, c->d_tsrc_raw, c->d_tsrc_cap, nbytes, nbytes + 512, e->copy_stream);
-        c->d_tsrc = c->d_tsrc_raw ? c->d_tsrc_raw + 256 : nullptr;
-        if (r) return r;
+        TW_TRY(c->d_tsrc_raw.grow(e, nbytes, nbytes + 512, e->copy_stream));
         c->tsrc_slot = slot;
         return TW_OK;
     }
@@ -4303,7 +4348,7 @@ struct Submit {
     tw_status stage_gray_pair_resized(uint8_t* dst_a, uint8_t* dst_b)
     {
         const size_t j = c->jobs.size();
-        uint8_t* tsrc = c->d_tsrc + c->tsrc_slot * j;
+        uint8_t* tsrc = c->d_tsrc() + c->tsrc_slot * j;
         if (!s.res) TW_TRY(upload_rows(dst_a, s.h_a, (size_t)s.stride, (size_t)s.width, (size_t)s.height));
         TW_TRY(upload_rows(tsrc, s.h_b, (size_t)tstride, (size_t)tw, (size_t)th));
         c->h_rsz[j] = resize_job(tsrc, tw, th, tw, dst_b, s.width, s.height, s.width);
@@ -4322,7 +4367,7 @@ struct Submit {
     tw_status stage_device_target()
     {
         const size_t dslot = ((size_t)eff_stride * (size_t)s.height + 255) / 256 * 256;
-        TW_TRY(grow_device(e, c->d_img, c->d_img_cap, dslot * 2 * e->cfg.cap, dslot * 2 * e->cfg.cap + 256, e->copy_stream));
+        TW_TRY(c->d_img.grow(e, dslot * 2 * e->cfg.cap, dslot * 2 * e->cfg.cap + 256, e->copy_stream));
         jb.t_src = (const uint8_t*)s.d_b;
         jb.d_b = c->d_img + dslot * (2 * c->jobs.size() + 1);
         jb.rkind = RSZ_FLUSH_DEV;
@@ -4496,35 +4541,34 @@ tw_status tw_engine_create(int device, const tw_params* params, int slots, tw_en
     slots = cfg.cap;  // (clamped to 1 .. 256)
     tw_engine* e = new tw_engine(cfg);
     e->device = device;
-    if (cfg.debug_stamps && hipMalloc((void**)&e->dbg_stamps, 4096 * sizeof(unsigned long long)) == hipSuccess)
+    if (cfg.debug_stamps && e->dbg_stamps.make(e, 4096 * sizeof(unsigned long long)) == TW_OK)
         (void)hipMemset(e->dbg_stamps, 0, 4096 * sizeof(unsigned long long));
     // the main stream carries the dependent flow chain: highest priority, so that its small launches are not queued
     // behind the second stream's image-only work
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    bool ok = hipStreamCreateWithPriority(&e->stream, hipStreamNonBlocking, prio_hi) == hipSuccess &&
-              hipStreamCreateWithPriority(&e->stream2, hipStreamNonBlocking, e->cfg.lanes > 1 ? prio_hi : prio_lo) == hipSuccess &&
-              hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) == hipSuccess &&
-              hipMalloc((void**)&e->d_ptrs, sizeof(void*) * 2 * slots + 256) == hipSuccess &&
-              hipMalloc((void**)&e->d_count, sizeof(int) * slots + 256) == hipSuccess &&
-              hipMalloc((void**)&e->d_same, sizeof(unsigned) * slots + 256) == hipSuccess &&
+    bool ok = hipStreamCreateWithPriority(&e->stream.h, hipStreamNonBlocking, prio_hi) == hipSuccess &&
+              hipStreamCreateWithPriority(&e->stream2.h, hipStreamNonBlocking, e->cfg.lanes > 1 ? prio_hi : prio_lo) == hipSuccess &&
+              hipStreamCreateWithFlags(&e->copy_stream.h, hipStreamNonBlocking) == hipSuccess &&
+              hipEventCreateWithFlags(&e->ev_fork.h, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&e->ev_join.h, hipEventDisableTiming) == hipSuccess &&
+              e->d_ptrs.make(e, sizeof(void*) * 2 * slots + 256) == TW_OK &&
+              e->d_count.make(e, sizeof(int) * slots + 256) == TW_OK &&
+              e->d_same.make(e, sizeof(unsigned) * slots + 256) == TW_OK &&
               hipMemset(e->d_same, 0, sizeof(unsigned) * slots + 256) == hipSuccess;
     for (Ctx& c : e->ctx) {
-        ok = ok && hipEventCreate(&c.ev_start) == hipSuccess && hipEventCreate(&c.ev_stop) == hipSuccess &&
-             hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&c.ev_h2d, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&c.ev_seg[0], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&c.ev_seg[1], hipEventDisableTiming) == hipSuccess &&
-             hipHostMalloc((void**)&c.h_ptrs, sizeof(void*) * 2 * slots, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&c.h_count, sizeof(int) * slots, hipHostMallocDefault) == hipSuccess &&
+        ok = ok && hipEventCreate(&c.ev_start.h) == hipSuccess && hipEventCreate(&c.ev_stop.h) == hipSuccess &&
+             hipEventCreateWithFlags(&c.ev_done.h, hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&c.ev_h2d.h, hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&c.ev_seg[0].h, hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&c.ev_seg[1].h, hipEventDisableTiming) == hipSuccess &&
+             c.h_ptrs.make(e, sizeof(void*) * 2 * slots) == TW_OK &&
+             c.h_count.make(e, sizeof(int) * slots) == TW_OK &&
              (c.png_luts.reserve(2 * (size_t)slots), true) &&
-             hipHostMalloc((void**)&c.h_png, png_table_bytes(slots), hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&c.h_pflag, sizeof(unsigned) * 2 * (size_t)slots, hipHostMallocDefault) == hipSuccess &&
-             hipMalloc((void**)&c.d_png, png_table_bytes(slots) + 256) == hipSuccess &&
-             hipHostMalloc((void**)&c.h_rec, sizeof(ScanRec) * HOST_RECS * (size_t)slots, hipHostMallocDefault) ==
-                 hipSuccess;
+             c.h_png.make(e, png_table_bytes(slots)) == TW_OK &&
+             c.h_pflag.make(e, sizeof(unsigned) * 2 * (size_t)slots) == TW_OK &&
+             c.d_png.make(e, png_table_bytes(slots) + 256) == TW_OK &&
+             c.h_rec.make(e, sizeof(ScanRec) * HOST_RECS * (size_t)slots) == TW_OK;
     }
     if (!ok) {
         tw_engine_destroy(e);
@@ -4540,90 +4584,7 @@ void tw_engine_destroy(tw_engine* e)
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
     drop_graphs(e);
-    if (e->I) (void)hipFree(e->I);
-    if (e->R) (void)hipFree(e->R);
-    if (e->M[0]) (void)hipFree(e->M[0]);
-    if (e->M[1]) (void)hipFree(e->M[1]);
-    for (float* f : e->flow)
-        if (f) (void)hipFree(f);
-    if (e->d_ptrs) (void)hipFree((void*)e->d_ptrs);
-    if (e->d_count) (void)hipFree(e->d_count);
-    if (e->d_same) (void)hipFree(e->d_same);
-    if (e->d_grid) (void)hipFree(e->d_grid);
-    if (e->Vd) (void)hipFree(e->Vd);
-    if (e->h_bounce) (void)hipHostFree(e->h_bounce);
-    if (e->dbg_stamps) (void)hipFree(e->dbg_stamps);
-    if (e->lat_I) (void)hipFree(e->lat_I);
-    if (e->lat_R) (void)hipFree(e->lat_R);
-    for (hipEvent_t ev : e->lat_ev) (void)hipEventDestroy(ev);
-    for (Ctx& c : e->ctx) {
-        if (c.h_img) (void)hipHostFree(c.h_img);
-        if (c.d_img) (void)hipFree(c.d_img);
-        if (c.d_rec) (void)hipFree(c.d_rec);
-        if (c.d_filt_raw) (void)hipFree(c.d_filt_raw);
-        if (c.d_png) (void)hipFree(c.d_png);
-        if (c.h_png) (void)hipHostFree(c.h_png);
-        if (c.d_jpg) (void)hipFree(c.d_jpg);
-        if (c.h_jpg) (void)hipHostFree(c.h_jpg);
-        if (c.d_msk) (void)hipFree(c.d_msk);
-        if (c.h_msk) (void)hipHostFree(c.h_msk);
-        if (c.d_nreg) (void)hipFree(c.d_nreg);
-        if (c.d_regs) (void)hipFree(c.d_regs);
-        if (c.d_regof) (void)hipFree(c.d_regof);
-        if (c.h_nreg) (void)hipHostFree(c.h_nreg);
-        if (c.h_regs) (void)hipHostFree(c.h_regs);
-        if (c.h_regof) (void)hipHostFree(c.h_regof);
-        if (c.h_rgn) (void)hipHostFree(c.h_rgn);
-        if (c.d_nchg) (void)hipFree(c.d_nchg);
-        if (c.d_chg) (void)hipFree(c.d_chg);
-        if (c.h_nchg) (void)hipHostFree(c.h_nchg);
-        if (c.h_chg) (void)hipHostFree(c.h_chg);
-        if (c.h_shift) (void)hipHostFree(c.h_shift);
-        if (c.h_pflag) (void)hipHostFree(c.h_pflag);
-        if (c.ev_h2d) (void)hipEventDestroy(c.ev_h2d);
-        for (hipEvent_t ev : c.ev_seg)
-            if (ev) (void)hipEventDestroy(ev);
-        if (c.h_ptrs) (void)hipHostFree((void*)c.h_ptrs);
-        if (c.h_count) (void)hipHostFree(c.h_count);
-        if (c.h_rec) (void)hipHostFree(c.h_rec);
-        if (c.d_fstage) (void)hipFree(c.d_fstage);
-        if (c.h_fdst) (void)hipHostFree(c.h_fdst);
-        if (c.d_istage) (void)hipFree(c.d_istage);
-        if (c.h_fsrc) (void)hipHostFree(c.h_fsrc);
-        if (c.d_tsrc_raw) (void)hipFree(c.d_tsrc_raw);
-        if (c.d_rsz) (void)hipFree(c.d_rsz);
-        if (c.h_rsz) (void)hipHostFree(c.h_rsz);
-        if (c.d_rpng) (void)hipFree(c.d_rpng);
-        if (c.h_rpng) (void)hipHostFree(c.h_rpng);
-        if (c.ev_fexp) (void)hipEventDestroy(c.ev_fexp);
-        if (c.ev_d2h) (void)hipEventDestroy(c.ev_d2h);
-        if (c.ev_start) (void)hipEventDestroy(c.ev_start);
-        if (c.ev_stop) (void)hipEventDestroy(c.ev_stop);
-        if (c.ev_done) (void)hipEventDestroy(c.ev_done);
-    }
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    if (e->stream2) (void)hipStreamDestroy(e->stream2);
-    if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
-    if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
-    if (e->d_fdst) (void)hipFree(e->d_fdst);
-    if (e->d_fsrc) (void)hipFree(e->d_fsrc);
-    if (e->d_rgn) (void)hipFree(e->d_rgn);
-    if (e->d_lab) (void)hipFree(e->d_lab);
-    if (e->d_cells) (void)hipFree(e->d_cells);
-    if (e->d_shift) (void)hipFree(e->d_shift);
-    if (e->d_sprof) (void)hipFree(e->d_sprof);
-    if (e->d_ovl) (void)hipFree(e->d_ovl);
     for (tw_image* im : e->res_images) delete im;
-    for (tw_engine::ResChunk& ch : e->res_chunks) (void)hipFree(ch.base);
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    for (auto& kv : e->plans) free_plan(kv.second);
-    for (auto& pend : e->prof_pending)
-        for (ProfPair& pp : pend) {
-            (void)hipEventDestroy(pp.a);
-            (void)hipEventDestroy(pp.b);
-        }
-    for (hipEvent_t ev : e->prof_free) (void)hipEventDestroy(ev);
     delete e;
 }
 
@@ -5558,7 +5519,7 @@ tw_status tw_ticket_overlay(tw_engine* e, tw_ticket ticket, int tol, const tw_ov
     oj.d_regions = oj.n_regions > 0 ? c->d_regs + (size_t)j * TW_MAX_REGIONS : nullptr;
     // on the device-to-host stream: the compute stream may hold later batches' kernels, and the process has no queue to spare
     // for a further stream
-    if (!e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
+    if (!e->d2h_stream) TW_HIP(e, hipStreamCreateWithFlags(&e->d2h_stream.h, hipStreamNonBlocking));
     hipStream_t st = e->d2h_stream;
     const size_t row = 3 * (size_t)w, spitch = (row + 3) / 4 * 4;
     if (kind == 0) {
@@ -5566,7 +5527,7 @@ tw_status tw_ticket_overlay(tw_engine* e, tw_ticket ticket, int tol, const tw_ov
         oj.pitch = out->pitch;
     } else {
         const size_t need = spitch * (size_t)h;
-        TW_TRY(grow_device(e, e->d_ovl, e->d_ovl_cap, need, need + 256, st));
+        TW_TRY(e->d_ovl.grow(e, need, need + 256, st));
         oj.dst = e->d_ovl;
         oj.pitch = (long long)spitch;
     }
@@ -5786,8 +5747,8 @@ tw_status tw_prof_read(tw_engine* e, int kclass, double* ms_total, int* launches
             tot += ms;
             cnt++;
         }
-        e->prof_free.push_back(pp.a);
-        e->prof_free.push_back(pp.b);
+        e->prof_free.push_back(std::move(pp.a));
+        e->prof_free.push_back(std::move(pp.b));
     }
     e->prof_pending[kclass].clear();
     if (ms_total) *ms_total = tot;
@@ -6123,70 +6084,14 @@ extern "C" int tw_debug_memory(tw_engine* e, unsigned long long* out, int n)
 {
     if (!e || !out) return -1;
     unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // device: the level workspace (I + 5 I for R + 2 x 2.5 I for M), the single-pair schedule's I / R, the box window's column
-    // sums, flow planes, the dense grid, pointer / count tables, debug stamps, every context's images, filtered rows, PNG job
-    // table, records, flow staging and initial-field staging, the flow destination and source tables, and the plans' tables
-    // (each allocation with the slack it was made with)
-    if (e->I) v[0] += (e->ws_elems * 4 + 256) + (e->ws_elems * 5 * 4 + 256) + 2 * (e->ws_elems / 2 * 5 * 4 + 256);
-    if (e->lat_I) v[0] += (e->lat_cap * 4 + 256) + (e->lat_cap * 5 * 4 + 256);
-    if (e->Vd) v[0] += e->Vd_cap * sizeof(double) + 256;
-    for (size_t k = 0; k < e->flow.size(); k++)
-        if (e->flow[k]) v[0] += e->flow_cap[k] * 4 + 256;
-    if (e->d_grid) v[0] += e->d_grid_cap * sizeof(float2) + 256;
-    if (e->d_ptrs) v[0] += sizeof(void*) * 2 * (size_t)e->cfg.cap + 256;
-    if (e->d_count) v[0] += sizeof(int) * (size_t)e->cfg.cap + 256;
-    if (e->d_same) v[0] += sizeof(unsigned) * (size_t)e->cfg.cap + 256;
-    if (e->dbg_stamps) v[0] += 4096 * sizeof(unsigned long long);
-    if (e->d_fdst) v[0] += sizeof(FlowDst) * (size_t)e->cfg.cap + 256;
-    if (e->d_fsrc) v[0] += sizeof(FlowDst) * (size_t)e->cfg.cap + 256;
-    if (e->d_rgn) v[0] += region_table_bytes(e->cfg.cap) + 256;
-    if (e->d_lab) v[0] += e->d_lab_cap * sizeof(int) + 256;
-    if (e->d_cells) v[0] += e->d_cells_cap * sizeof(int4) + 256;
-    if (e->d_shift) v[0] += sizeof(ShiftRec) * (size_t)e->cfg.cap + 256;
-    if (e->d_sprof) v[0] += e->d_sprof_cap * sizeof(unsigned) + 256;
-    if (e->d_ovl) v[0] += e->d_ovl_cap + 256;
-    for (const Ctx& c : e->ctx) {
-        if (c.d_istage) v[0] += c.d_istage_cap + 256;
-        if (c.h_fsrc) v[1] += sizeof(FlowDst) * (size_t)e->cfg.cap;
-        if (c.d_fstage) v[0] += c.d_fstage_cap + 256;
-        if (c.h_fdst) v[1] += sizeof(FlowDst) * (size_t)e->cfg.cap;
-        if (c.d_img) v[0] += c.d_img_cap + 256;
-        if (c.d_tsrc_raw) v[0] += c.d_tsrc_cap + 512;
-        if (c.d_rsz) v[0] += sizeof(ResizeJob) * 3 * (size_t)e->cfg.cap + 256;
-        if (c.h_rsz) v[1] += sizeof(ResizeJob) * 3 * (size_t)e->cfg.cap;
-        if (c.d_rpng) v[0] += sizeof(PngJob) * (size_t)e->cfg.cap + 256;
-        if (c.h_rpng) v[1] += sizeof(PngJob) * (size_t)e->cfg.cap;
-        if (c.d_filt_raw) v[0] += c.d_filt_cap + 512;
-        if (c.d_png) v[0] += png_table_bytes(e->cfg.cap) + 256;
-        if (c.d_rec) v[0] += c.d_rec_cap * sizeof(ScanRec) + 256;
-        if (c.h_img) v[1] += c.h_img_cap;
-        if (c.h_ptrs) v[1] += sizeof(void*) * 2 * (size_t)e->cfg.cap;
-        if (c.h_count) v[1] += sizeof(int) * (size_t)e->cfg.cap;
-        if (c.h_png) v[1] += png_table_bytes(e->cfg.cap);
-        if (c.d_jpg) v[0] += jpeg_table_bytes(e->cfg.cap) + 256;
-        if (c.h_jpg) v[1] += jpeg_table_bytes(e->cfg.cap);
-        if (c.d_msk) v[0] += mask_table_bytes(e->cfg.cap) + 256;
-        if (c.h_msk) v[1] += mask_table_bytes(e->cfg.cap);
-        if (c.d_nreg) v[0] += sizeof(int) * (size_t)e->cfg.cap + 256;
-        if (c.d_regs) v[0] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cfg.cap + 256;
-        if (c.d_regof) v[0] += c.d_regof_cap * sizeof(int) + 256;
-        if (c.h_nreg) v[1] += sizeof(int) * (size_t)e->cfg.cap;
-        if (c.h_regs) v[1] += sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)e->cfg.cap;
-        if (c.h_regof) v[1] += sizeof(int) * HOST_RECS * (size_t)e->cfg.cap;
-        if (c.h_rgn) v[1] += region_table_bytes(e->cfg.cap);
-        if (c.d_nchg) v[0] += sizeof(int) * (size_t)e->cfg.cap + 256;
-        if (c.d_chg) v[0] += c.d_chg_cap * sizeof(ChangeRec) + 256;
-        if (c.h_nchg) v[1] += sizeof(int) * (size_t)e->cfg.cap;
-        if (c.h_chg) v[1] += sizeof(ChangeRec) * HOST_RECS * (size_t)e->cfg.cap;
-        if (c.h_shift) v[1] += sizeof(ShiftRec) * (size_t)e->cfg.cap;
-        if (c.h_pflag) v[1] += sizeof(unsigned) * 2 * (size_t)e->cfg.cap;
-        if (c.h_rec) v[1] += sizeof(ScanRec) * HOST_RECS * (size_t)e->cfg.cap;
-    }
+    // device and pinned: what Buf::make / grow allocated for the engine and its contexts, each allocation with the slack it
+    // was made with (the bounce buffer among the pinned), plus the totals of the plans' tables and of the resident store
+    v[0] = e->dev_bytes;
+    v[1] = e->pin_bytes;
     for (const auto& kv : e->plans) v[0] += kv.second->owned_bytes;
     v[0] += e->res_reserved;  // (the resident store's chunks: tw_debug_resident)
-    v[1] += e->h_bounce_cap;
     v[2] = e->plans.size();
-    v[3] = e->h_bounce_cap;
+    v[3] = e->h_bounce.cap;
     {
         PinRegistry& r = pin_registry();
         std::lock_guard<std::mutex> lk(r.m);
