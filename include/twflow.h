@@ -483,6 +483,53 @@ typedef struct tw_shift {
 } tw_shift;              /* 40 bytes */
 tw_status tw_ticket_shift(tw_engine* e, tw_ticket ticket, tw_shift* out);
 
+/* Shift bands (additive within ABI 4, detected by the symbols).  One translation per pair does not explain a page with an
+ * inserted banner or a grown paragraph: everything below the insertion moved, nothing above it did.  With the engine option
+ * TW_OPT_SHIFT_BANDS on (its value B is the band height in rows: 32 .. 1024, a multiple of 16) in a batch that also has
+ * TW_OPT_SHIFT on (whose value is the radius R), the batch estimates one vertical shift per band of B rows, checks each on the
+ * pixels, and starts the pair's flow from the bands.  With TW_OPT_SHIFT off the option is ignored: no launch, no buffer.
+ * E, T, w, h as in "Shift".  All integer:
+ *   global    the pair's tw_shift record is computed and reported exactly as without bands (dx, dy, both sums, `applied` by
+ *             the global rule); with bands on the seed comes from the bands only, and the record's `applied` is just that
+ *             rule's verdict
+ *   columns   dx = the pair's global dx, applied or not.  xa = max(0, -dx), xb = min(w, w - dx), nblk = ceil((xb - xa) / 64)
+ *   bands     band b covers rows [b B, min((b + 1) B, h)): rows_b rows; nb = ceil(h / B) bands
+ *   signature for every row y and block k < nblk: sigE[y][k] = sum of E[y][x] over x in [xa + 64 k, min(xa + 64 (k + 1), xb)),
+ *             sigT[y][k] = sum of T[y][x + dx] over the same x (each at most 16 320: uint16)
+ *   search    per band, r = min(R, h / 2): candidates d in the order 0, -1, +1, -2, +2, ...; lo = max(b B, -d),
+ *             hi = min(b B + rows_b, h - d), n(d) = hi - lo; a candidate with n(d) < ceil(rows_b / 2) is skipped (d = 0 never
+ *             is); cost(d) = sum over i in [lo, hi) and k of |sigE[i][k] - sigT[i + d][k]| in 64 bits; a candidate replaces
+ *             the best only when cost(d) * n(best) < cost(best) * n(d) in unsigned 64 bits.  The winner — the least cost per
+ *             row, the earliest in visit order among equals — is dy_b
+ *   accept    per band: sad_zero = sum |E - T| over the band's rows and all w columns, n_zero = rows_b * w.
+ *             (dx, dy_b) == (0, 0): applied = 0, sad_shift = sad_zero, n_shift = n_zero (the band did not move: a zero seed is
+ *             right).  Otherwise sad_shift = sum |E[y][x] - T[y + dy_b][x + dx]| over the rows [lo, hi) of dy_b and the columns
+ *             [xa, xb), n_shift = (hi - lo) * (xb - xa), applied = sad_shift * n_zero <= (sad_zero >> 2) * n_shift in unsigned
+ *             64 bits: the shift must at least quarter the band's mean absolute difference (stricter than the page's halving,
+ *             because a band has far fewer pixels)
+ *   seed      a pair without a tw_flow_in of its own computes exactly what tw_submit_*_flow_init computes for it with the
+ *             full-resolution field F[y][x] = ((float)dx, (float)dy_b) for y in a band with applied = 1 and (0, 0) elsewhere,
+ *             bit for bit.  A pair with its own field keeps it: its bands are measured and all reported with applied = 0.
+ *             There is no fall-back to the global shift.
+ * Kernels: tw_band_rows, tw_band_search, tw_band_verify per batch part behind its tw_shift_verify; tw_flow_band_init at every
+ * chunk of the coarsest level, in tw_flow_shift_init's place.  The option is read when a batch's first pair is booked, and all
+ * pairs of the batch share it.  With the option off — the default — every entry point launches, copies, records and allocates
+ * exactly what it did before.
+ * Known limits: a band that straddles the insertion usually answers applied = 0, and so does a band whose content has left
+ * the image — but a wrong shift can be accepted there (a few in a hundred such bands); the flow there is garbage either way.
+ * The move is vertical only, plus the one global dx.  Bands do not constrain each other.
+ * tw_ticket_shift_bands follows tw_ticket_shift's contract: valid until the wait that collects the ticket, launches the open
+ * batch if it has to, waits for it, does NOT consume the ticket.  *n is the true nb; the first min(nb, cap) records are
+ * written.  On a batch without bands it answers TW_E_BAD_PARAMETER and the ticket stays waitable; an unknown or already waited
+ * ticket, a null n, or a null out with cap > 0 answers TW_E_BAD_PARAMETER. */
+typedef struct tw_shift_band {
+    int y, rows;          /* b * B, rows_b */
+    int dy, applied;      /* the band's search answer; 1: the band's rows of the pair's start field are (dx, dy) */
+    int n_shift, n_zero;  /* overlap area at (dx, dy); rows_b * w */
+    uint64_t sad_shift, sad_zero;
+} tw_shift_band;          /* 40 bytes */
+tw_status tw_ticket_shift_bands(tw_engine* e, tw_ticket ticket, tw_shift_band* out, int cap, int* n);
+
 /* Diff image (additive within ABI 4, detected by the symbols).  The engine answers a pair with lists of numbers; a user of a
  * screenshot diff wants the page with the changes marked on it.  The gray images as the batch sees them — after tw_png_unfilter,
  * tw_jpeg_idct, tw_resize_u8 and tw_mask_rects — exist only in device memory, and so do all hit records of a pair with more than
@@ -564,8 +611,18 @@ tw_status tw_dev_download(tw_engine* e, void* host, const void* dptr, size_t byt
  * TW_OPT_RESIDUAL (default 0): residual, above.  0 is off; 1 .. 254 is the tolerance; any other value answers
  *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked.
  * TW_OPT_SHIFT (default 0): shift, above.  0 is off; 1 .. 1024 is the search radius in pixels; any other value answers
- *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked. */
-enum { TW_OPT_SCAN_FUSED_FINAL = 1, TW_OPT_POLYEXP_F32 = 2, TW_OPT_REGIONS = 3, TW_OPT_RESIDUAL = 4, TW_OPT_SHIFT = 5 };
+ *   TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked.
+ * TW_OPT_SHIFT_BANDS (default 0): shift bands, above.  0 is off; 32 .. 1024 and a multiple of 16 is the band height in rows;
+ *   any other value answers TW_E_BAD_PARAMETER and leaves the option as it was.  Read when a batch's first pair is booked;
+ *   ignored in a batch opened with TW_OPT_SHIFT off. */
+enum {
+    TW_OPT_SCAN_FUSED_FINAL = 1,
+    TW_OPT_POLYEXP_F32 = 2,
+    TW_OPT_REGIONS = 3,
+    TW_OPT_RESIDUAL = 4,
+    TW_OPT_SHIFT = 5,
+    TW_OPT_SHIFT_BANDS = 6
+};
 tw_status tw_set_option(tw_engine* e, int option, int value);
 
 /* Page-locked host memory.  Images handed to tw_submit_u8 from a block tw_host_alloc returned (or that the caller
@@ -741,6 +798,15 @@ tw_status tw_stage_warp_residual(tw_engine* e, const uint8_t* expect, const uint
  * whatever the length.  (Additive within version 4.) */
 tw_status tw_stage_shift(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h, int radius,
                          int force_global, uint32_t* profiles, tw_shift* out);
+
+/* The global estimation as tw_stage_shift runs it, then tw_band_rows, tw_band_search and tw_band_verify alone, on the caller's
+ * pair, synchronously, with `radius` (1 .. 1024) and the band height `band` (32 .. 1024, a multiple of 16).  `sig` (nullable):
+ * [sigE[h][nblk], sigT[h][nblk]] at the pair's dx.  *global: the pair's tw_shift record; bands[nb]: the band records;
+ * *n_bands = nb.  The outputs are set to 0xff bytes before the launches (the band records are then zeroed as a batch zeroes
+ * them), and the call answers TW_E_DEVICE when a launch wrote beyond the pair's share.  force_global = 1 takes the device-memory
+ * path of both searches.  (Additive within version 4.) */
+tw_status tw_stage_shift_bands(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h, int radius,
+                               int band, int force_global, uint16_t* sig, tw_shift* global, tw_shift_band* bands, int* n_bands);
 
 #ifdef __cplusplus
 }

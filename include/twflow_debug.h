@@ -65,6 +65,11 @@ enum tw_debug_family {
     TW_DF_SPAN_SCAN,
     TW_DF_PNG_UNFILTER,
     TW_DF_SPAN_SCAN_SEG,   /* tw_span_scan_seg: a single pair's ordered scan in 16 independent segments (round 6) */
+    TW_DF_BAND_ROWS,       /* tw_band_rows: a batch part's row signatures of both images, 64 columns per entry (TW_OPT_SHIFT_BANDS) */
+    TW_DF_BAND_SEARCH,     /* tw_band_search: each band's best vertical shift, from the signatures (TW_OPT_SHIFT_BANDS) */
+    TW_DF_BAND_VERIFY,     /* tw_band_verify<0> + <1>: each band's pixel sums at (0, 0) and at its shift, then areas and `applied` — two launches per part (TW_OPT_SHIFT_BANDS) */
+    TW_DF_FLOW_BAND_INIT,  /* tw_flow_band_init: a coarsest-level chunk's first flow from the bands, in tw_flow_shift_init's place (TW_OPT_SHIFT_BANDS; the
+                            * four here, in front of TW_DF_BLUR_SOLVE4Q: the chain from there to TW_DF_COUNT is pinned by tests, nothing in front of it is) */
     TW_DF_BLUR_SOLVE4Q,    /* tw_blur_solve4q: solve + refresh by the horizontal item's owner — a single pair's level-0 launches (round 6) */
     TW_DF_OVERLAY_BASE,    /* tw_overlay_base: one pair's diff image, the base layer (tw_ticket_overlay) */
     TW_DF_OVERLAY_MARKS,   /* tw_overlay_marks<0> the region boxes, <1> the vectors: one launch each, only when the pair has any (both in
@@ -171,6 +176,16 @@ int tw_debug_level_plan(const tw_engine* e, int width, int height, int span, int
  * (at most min(n, 10); 0 for a null `out`, a non-positive size or a radius outside 1 .. 1024).  tests/test_gpu_shift.py takes
  * the lengths above the LDS limit from it. */
 int tw_debug_shift_plan(int width, int height, int radius, int* out, int n);
+
+/* How the band launches run for a pair of width x height pixels at search radius `radius` and band height `band`
+ * (TW_OPT_SHIFT_BANDS), a pure function of its arguments (no engine): out[0] nb = ceil(height / band), out[1] nblk at dx = 0 =
+ * ceil(width / 64), out[2] 1 when tw_band_search stages a band's signatures in LDS, out[3] the bytes that takes — 2 * nblk *
+ * (rows + min(height, rows + 2 r)) with rows = min(band, height), r = min(radius, height / 2) — out[4] the LDS budget in bytes
+ * (staged while out[3] <= out[4]), out[5] r, out[6] tw_band_rows' grid x (grid z = the images), out[7] tw_band_search's
+ * threads per workgroup (grid: nb x pairs), out[8] tw_band_verify<0>'s grid x (chunks of 16 rows).  Returns the number of
+ * values written (at most min(n, 9); 0 for a null `out`, a non-positive size, a radius outside 1 .. 1024 or a band height that
+ * TW_OPT_SHIFT_BANDS refuses). */
+int tw_debug_band_plan(int width, int height, int radius, int band, int* out, int n);
 
 /* How tw_overlay_base runs for a width x height pair whose images lie at the addresses `expect` and `target` with rows `stride`
  * bytes apart, into a destination at the address `dst` with rows `pitch` bytes apart — a pure function of its arguments (no

@@ -419,6 +419,9 @@ static_assert(RGN_MAX == TW_MAX_REGIONS && RGN_RECTS == TW_MAX_IGNORE, "the kern
 static_assert(sizeof(ChangeRec) == sizeof(tw_change) && sizeof(tw_change) == 24, "tw_change is the kernel's record");
 static_assert(sizeof(ShiftRec) == sizeof(tw_shift) && sizeof(tw_shift) == 40 && offsetof(ShiftRec, sad_shift) == offsetof(tw_shift, sad_shift),
               "tw_shift is the kernel's record");
+static_assert(sizeof(BandRec) == sizeof(tw_shift_band) && sizeof(tw_shift_band) == 40 && offsetof(BandRec, sad_shift) == offsetof(tw_shift_band, sad_shift) &&
+                  offsetof(BandRec, n_zero) == offsetof(tw_shift_band, n_zero),
+              "tw_shift_band is the kernel's record");
 
 struct Job {
     const uint8_t *h_a = nullptr, *h_b = nullptr;  // host inputs already staged (null for device inputs)
@@ -561,6 +564,11 @@ struct Ctx {
     // pinned copy of the batch's records ([cap], created when the first batch with the option on is launched from this context)
     int shift = 0;
     PinBuf<ShiftRec> h_shift;
+    // shift bands (TW_OPT_SHIFT_BANDS): `bands` = the band height of this batch (0: off — always when `shift` is), taken when
+    // its first pair is booked; the pinned copy of the batch's band records ([cap][nb], grown when a batch needs more)
+    int bands = 0;
+    int nbands() const { return bands ? (h + bands - 1) / bands : 0; }
+    PinBuf<BandRec> h_bands;
 
     // the batch is collected or dropped: its resident images may return to the store
     void release_images()
@@ -575,11 +583,12 @@ struct Ctx {
 
     // A new batch in this context: what describes the batch starts over; the device and pinned regions, their capacities
     // and the events survive.
-    void begin_batch(int width, int height, int span_, double threshold_, int64_t first, int regions_, int residual_, int shift_)
+    void begin_batch(int width, int height, int span_, double threshold_, int64_t first, int regions_, int residual_, int shift_, int bands_)
     {
         regions = regions_;
         residual = residual_;
         shift = shift_;
+        bands = shift_ ? bands_ : 0;
         release_images();
         jobs.clear();
         launched = false;
@@ -719,6 +728,7 @@ struct EngineOptions {
     int regions_gap = 0;   // TW_OPT_REGIONS: the next batch's gap (0: off)
     int residual_tol = 0;  // TW_OPT_RESIDUAL: the next batch's tolerance (0: off)
     int shift_radius = 0;  // TW_OPT_SHIFT: the next batch's search radius (0: off)
+    int shift_bands = 0;   // TW_OPT_SHIFT_BANDS: the next batch's band height in rows (0: off)
 };
 
 // the parameters an engine admits (tw_engine_create asks before it touches the device; make_engine_config asks for itself)
@@ -867,6 +877,7 @@ struct tw_engine {
     DevBuf<char> d_rgn;
     DevBuf<int> d_lab;
     bool rgn_attr = false;
+    bool band_attr = false;  // ... and tw_band_search's
     // residual (the next batch's tolerance is opt.residual_tol): tw_warp_residual's dense
     // cell plane ([cap][G] cells of four ints, on first use) — the engine's, as d_grid: the batch's own tw_change_scan
     // consumes it before the next batch's launches write it
@@ -876,6 +887,10 @@ struct tw_engine {
     // launches consume them, and its result copy reads the records, before the next batch's launches write them
     DevBuf<ShiftRec> d_shift;
     DevBuf<unsigned> d_sprof;
+    // shift bands (the next batch's band height is opt.shift_bands): the band records of the batch being enqueued ([cap][nb])
+    // and its pairs' row signatures ([cap][2][h][ceil(w / 64)] uint16), on first use and the engine's, as d_shift and d_sprof
+    DevBuf<BandRec> d_bands;
+    DevBuf<unsigned short> d_bsig;
     // diff image (tw_ticket_overlay): the staging a picture for a HOST destination is rendered into (dense rows of
     // round_up(3 w, 4) bytes), created by the first such call and grown on demand; device destinations are written in place
     DevBuf<uint8_t> d_ovl;
@@ -2339,6 +2354,21 @@ void launch_shift_init(tw_engine* e, hipStream_t st, const Plan* pl, float* flow
     TW_LAUNCH(e, TW_DF_FLOW_SHIFT_INIT, tw_flow_shift_init, dim3((L.w + 63) / 64, (L.h + 3) / 4, nc), dim3(256), 0, st, a);
 }
 
+// TW_OPT_SHIFT_BANDS: the first flow of the pairs [j0, j0 + nc) from their bands' shifts, in tw_flow_shift_init's place
+void launch_band_init(tw_engine* e, hipStream_t st, const Plan* pl, float* flow, int j0, int nc, int band, int nb, bool zero_rest)
+{
+    const LevelPlan& L = pl->lv[pl->levels];
+    BandInitArgs a;
+    a.g = area_init_args(e, pl, flow, j0);
+    a.rec = e->d_shift + j0;
+    a.bands = e->d_bands + (size_t)j0 * nb;
+    a.band = band;
+    a.nb = nb;
+    a.magic = (unsigned)((1ull << 32) / (unsigned)band) + 1u;
+    a.zero_rest = zero_rest ? 1 : 0;
+    TW_LAUNCH(e, TW_DF_FLOW_BAND_INIT, tw_flow_band_init, dim3((L.w + 63) / 64, (L.h + 3) / 4, nc), dim3(256), 0, st, a);
+}
+
 // a flow field's rows in either layout: bytes of a row of w pixels, rows of a field of h pixel rows
 size_t flow_row_bytes(int w, int layout) { return (size_t)w * (layout == TW_FLOW_INTERLEAVED ? 8 : 4); }
 size_t flow_rows(int h, int layout) { return (size_t)h * (layout == TW_FLOW_INTERLEAVED ? 1 : 2); }
@@ -2557,6 +2587,68 @@ tw_status launch_shift_estimate(tw_engine* e, hipStream_t st, const uint8_t* con
     va.own = own;
     TW_LAUNCH(e, TW_DF_SHIFT_VERIFY, tw_shift_verify<0>, dim3((h + SV_ROWS - 1) / SV_ROWS, npairs), dim3(256), 0, st, va);
     TW_LAUNCH(e, TW_DF_SHIFT_VERIFY, tw_shift_verify<1>, dim3((npairs + 255) / 256), dim3(256), 0, st, va);
+    return TW_OK;
+}
+
+// The plan of the band launches (tw_debug_band_plan shows it to the tests): bands, signature blocks per row at dx = 0, and
+// whether tw_band_search stages a band's signatures in LDS — the band's rows of sigE and the rows of sigT within the radius,
+// clipped to the image, at the widest rows (dx = 0), two bytes each
+int band_count(int h, int band) { return (h + band - 1) / band; }
+int band_blocks(int w) { return (w + 63) / 64; }
+size_t band_search_lds_bytes(int w, int h, int radius, int band)
+{
+    const int rows = std::min(band, h), r = std::min(radius, h / 2);
+    return sizeof(unsigned short) * (size_t)band_blocks(w) * ((size_t)rows + std::min(h, rows + 2 * r));
+}
+bool band_search_in_lds(int w, int h, int radius, int band) { return band_search_lds_bytes(w, h, radius, band) <= (size_t)BS_LDS_BYTES; }
+// tw_band_rows, tw_band_search, tw_band_verify<0> and <1> over npairs pairs, behind launch_shift_estimate on the same stream
+// (`rec` holds the pairs' dx): their signatures into `sig`, their band records into `bands` (zeroed here first, in stream
+// order: tw_band_verify<0> accumulates)
+tw_status launch_band_estimate(tw_engine* e, hipStream_t st, const uint8_t* const* srcs, long long stride, int w, int h, int radius,
+                               int band, bool force_global, const ShiftRec* rec, unsigned short* sig, BandRec* bands,
+                               const FlowDst* own, int npairs)
+{
+    const int nb = band_count(h, band), nblk0 = band_blocks(w);
+    TW_HIP(e, hipMemsetAsync(bands, 0, sizeof(BandRec) * (size_t)nb * npairs, st));
+    BandRowsArgs ra;
+    ra.srcs = srcs;
+    ra.stride = stride;
+    ra.w = w;
+    ra.h = h;
+    ra.nblk0 = nblk0;
+    ra.rec = rec;
+    ra.sig = sig;
+    TW_LAUNCH(e, TW_DF_BAND_ROWS, tw_band_rows, dim3((unsigned)(((size_t)h * nblk0 + 255) / 256), 1, 2 * npairs), dim3(256), 0, st, ra);
+    BandSearchArgs sa;
+    sa.sig = sig;
+    sa.rec = rec;
+    sa.w = w;
+    sa.h = h;
+    sa.nblk0 = nblk0;
+    sa.radius = radius;
+    sa.band = band;
+    sa.nb = nb;
+    sa.lds = !force_global && band_search_in_lds(w, h, radius, band) ? 1 : 0;
+    sa.bands = bands;
+    if (sa.lds && !e->band_attr) {
+        // (more than the 64 KB a launch may take unannounced)
+        TW_HIP(e, hipFuncSetAttribute((const void*)tw_band_search, hipFuncAttributeMaxDynamicSharedMemorySize, BS_LDS_BYTES));
+        e->band_attr = true;
+    }
+    TW_LAUNCH(e, TW_DF_BAND_SEARCH, tw_band_search, dim3(nb, npairs), dim3(1024), sa.lds ? band_search_lds_bytes(w, h, radius, band) : 0, st, sa);
+    BandVerifyArgs va;
+    va.srcs = srcs;
+    va.stride = stride;
+    va.w = w;
+    va.h = h;
+    va.npairs = npairs;
+    va.band = band;
+    va.nb = nb;
+    va.rec = rec;
+    va.bands = bands;
+    va.own = own;
+    TW_LAUNCH(e, TW_DF_BAND_VERIFY, tw_band_verify<0>, dim3((h + BV_ROWS - 1) / BV_ROWS, npairs), dim3(256), 0, st, va);
+    TW_LAUNCH(e, TW_DF_BAND_VERIFY, tw_band_verify<1>, dim3((npairs * nb + 255) / 256), dim3(256), 0, st, va);
     return TW_OK;
 }
 
@@ -2791,6 +2883,7 @@ struct BatchEnqueue {
             if (c.residual) TW_TRY(reserve_residual_buffers(need_rec));
         }
         if (c.shift) TW_TRY(reserve_shift_buffers());
+        if (c.bands) TW_TRY(reserve_band_buffers());
         // as d_rec above: nothing outstanding reads this context's staging (tw_wait waited for its copies)
         if (c.any_fout_host) TW_TRY(c.d_fstage.grow(e, fslot * e->cfg.cap, fslot * e->cfg.cap + 256));
         return TW_OK;
@@ -2838,6 +2931,17 @@ struct BatchEnqueue {
         TW_TRY(c.h_shift.make(e, sizeof(ShiftRec) * cap));
         const size_t need = 2 * ((size_t)c.w + c.h) * cap;
         TW_TRY(e->d_sprof.grow(e, need, need * sizeof(unsigned) + 256, e->stream));
+        return TW_OK;
+    }
+
+    // what the band kernels need, as the shift kernels' buffers: the engine's records and signatures, the context's pinned copy
+    tw_status reserve_band_buffers()
+    {
+        const size_t cap = (size_t)e->cfg.cap;
+        const size_t nrec = (size_t)c.nbands() * cap, nsig = 2 * (size_t)c.h * band_blocks(c.w) * cap;
+        TW_TRY(e->d_bands.grow(e, nrec, nrec * sizeof(BandRec) + 256, e->stream));
+        TW_TRY(c.h_bands.grow(e, nrec, nrec * sizeof(BandRec)));
+        TW_TRY(e->d_bsig.grow(e, nsig, nsig * sizeof(unsigned short) + 256, e->stream));
         return TW_OK;
     }
 
@@ -3289,6 +3393,7 @@ struct BatchEnqueue {
         }
         // the shift records come back with the batch's other results (tw_ticket_shift)
         if (c.shift) TW_HIP(e, hipMemcpyAsync(c.h_shift, e->d_shift, sizeof(ShiftRec) * n, hipMemcpyDeviceToHost, st));
+        if (c.bands) TW_HIP(e, hipMemcpyAsync(c.h_bands, e->d_bands, sizeof(BandRec) * (size_t)c.nbands() * n, hipMemcpyDeviceToHost, st));
         // a batch with palette images: the flag words tw_png_unfilter set for an index without a PLTE entry (tw_wait)
         if (c.any_plte)
             TW_HIP(e, hipMemcpyAsync(c.h_pflag, c.d_png + 2 * (size_t)n, sizeof(unsigned) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -3403,9 +3508,14 @@ struct BatchEnqueue {
     {
         if (!c.shift || hi <= lo) return TW_OK;
         ProfScope pscope(e, ls, TW_K_SCAN, 0);  // (tw_prof_select(TW_K_SCAN): tools/shift_prof.py times the feature's launches)
-        return launch_shift_estimate(e, ls, e->d_ptrs + 2 * lo, stride, aligned4, c.w, c.h, c.shift, false,
-                                     e->d_sprof + 2 * ((size_t)c.w + c.h) * lo, e->d_shift + lo, c.any_init ? e->d_fsrc + lo : nullptr,
-                                     hi - lo);
+        const FlowDst* own = c.any_init ? e->d_fsrc + lo : nullptr;
+        TW_TRY(launch_shift_estimate(e, ls, e->d_ptrs + 2 * lo, stride, aligned4, c.w, c.h, c.shift, false,
+                                     e->d_sprof + 2 * ((size_t)c.w + c.h) * lo, e->d_shift + lo, own, hi - lo));
+        if (!c.bands) return TW_OK;
+        // TW_OPT_SHIFT_BANDS: a shift per band of rows behind it, from the pairs' dx
+        return launch_band_estimate(e, ls, e->d_ptrs + 2 * lo, stride, c.w, c.h, c.shift, c.bands, false, e->d_shift + lo,
+                                    e->d_bsig + 2 * (size_t)c.h * band_blocks(c.w) * lo, e->d_bands + (size_t)c.nbands() * lo, own,
+                                    hi - lo);
     }
     // a chunk of the coarsest level of a batch that starts from a first flow: the pairs' own fields resized (zeros without
     // one), then the applied shifts of the others
@@ -3414,7 +3524,8 @@ struct BatchEnqueue {
         if (c.any_init) launch_area_init(e, ch.ls, pl, flow, ch.j0, ch.nc);
         if (c.shift) {
             ProfScope pscope(e, ch.ls, TW_K_SCAN, 0);
-            launch_shift_init(e, ch.ls, pl, flow, ch.j0, ch.nc, !c.any_init);
+            if (c.bands) launch_band_init(e, ch.ls, pl, flow, ch.j0, ch.nc, c.bands, c.nbands(), !c.any_init);
+            else launch_shift_init(e, ch.ls, pl, flow, ch.j0, ch.nc, !c.any_init);
         }
     }
     // the identical-pair flags of a chunk's pairs, where the schedule lets the chunk's launches read them
@@ -4149,7 +4260,8 @@ struct Submit {
             e->cur = nxt;
             c = &e->ctx[nxt];
         }
-        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->opt.regions_gap, e->opt.residual_tol, e->opt.shift_radius);
+        c->begin_batch(s.width, s.height, s.span, s.threshold, e->next_ticket, e->opt.regions_gap, e->opt.residual_tol, e->opt.shift_radius,
+                       e->opt.shift_bands);
         return TW_OK;
     }
 
@@ -5300,6 +5412,55 @@ tw_status tw_ticket_shift(tw_engine* e, tw_ticket ticket, tw_shift* out)
     return TW_OK;
 }
 
+tw_status tw_ticket_shift_bands(tw_engine* e, tw_ticket ticket, tw_shift_band* out, int cap, int* n)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    if (!n || cap < 0 || (!out && cap > 0)) {
+        e->err = "tw_ticket_shift_bands: null n, or null out with cap > 0";
+        return TW_E_BAD_PARAMETER;
+    }
+    int j = 0;
+    Ctx* c = find_ctx(e, ticket, &j);
+    if (!c) {
+        e->err = "unknown ticket";
+        return TW_E_BAD_PARAMETER;
+    }
+    if (!c->bands) {
+        e->err = "tw_ticket_shift_bands: the ticket's batch was opened without TW_OPT_SHIFT_BANDS and TW_OPT_SHIFT on";
+        return TW_E_BAD_PARAMETER;  // (the ticket stays waitable)
+    }
+    TW_HIP(e, hipSetDevice(e->device));
+    tw_status r;
+    if (!c->launched && (r = flush_ctx(e, *c))) {
+        drop_batch(*c);
+        return r;
+    }
+    // (as tw_ticket_shift: the ticket is not consumed)
+    const hipError_t herr = hipEventSynchronize(c->ev_done);
+    if (herr != hipSuccess) {
+        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
+        return TW_E_DEVICE;
+    }
+    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
+        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
+        return TW_E_BAD_IMAGE_FORMAT;
+    }
+    const int nb = c->nbands();
+    const BandRec* s = c->h_bands + (size_t)j * nb;
+    for (int b = 0; b < std::min(nb, cap); b++) {
+        out[b].y = s[b].y;
+        out[b].rows = s[b].rows;
+        out[b].dy = s[b].dy;
+        out[b].applied = s[b].applied;
+        out[b].n_shift = s[b].n_shift;
+        out[b].n_zero = s[b].n_zero;
+        out[b].sad_shift = s[b].sad_shift;
+        out[b].sad_zero = s[b].sad_zero;
+    }
+    *n = nb;
+    return TW_OK;
+}
+
 namespace {
 // ---- diff image (tw_ticket_overlay, tw_stage_overlay) ---------------------------------------------------------------
 // How tw_overlay_base runs: a pure function of the addresses, the strides and the size (tw_debug_overlay_plan shows it).
@@ -5662,6 +5823,13 @@ tw_status tw_set_option(tw_engine* e, int option, int value)
                 return TW_E_BAD_PARAMETER;
             }
             e->opt.shift_radius = value;
+            return TW_OK;
+        case TW_OPT_SHIFT_BANDS:
+            if (value != 0 && (value < 32 || value > 1024 || value % 16 != 0)) {
+                e->err = "TW_OPT_SHIFT_BANDS: 0 (off) or a band height of 32 .. 1024 rows, a multiple of 16";
+                return TW_E_BAD_PARAMETER;
+            }
+            e->opt.shift_bands = value;
             return TW_OK;
         default: e->err = "unknown option"; return TW_E_BAD_PARAMETER;
     }
@@ -6054,6 +6222,23 @@ extern "C" int tw_debug_shift_plan(int width, int height, int radius, int* out, 
     return m;
 }
 
+extern "C" int tw_debug_band_plan(int width, int height, int radius, int band, int* out, int n)
+{
+    if (!out || width < 1 || height < 1 || radius < 1 || radius > 1024 || band < 32 || band > 1024 || band % 16 != 0) return 0;
+    const int v[9] = {band_count(height, band),
+                      band_blocks(width),
+                      band_search_in_lds(width, height, radius, band) ? 1 : 0,
+                      (int)std::min<size_t>(band_search_lds_bytes(width, height, radius, band), INT_MAX),
+                      BS_LDS_BYTES,
+                      std::min(radius, height / 2),
+                      (int)(((size_t)height * band_blocks(width) + 255) / 256),
+                      1024,
+                      (height + BV_ROWS - 1) / BV_ROWS};
+    const int m = std::max(0, std::min(n, 9));
+    for (int i = 0; i < m; i++) out[i] = v[i];
+    return m;
+}
+
 extern "C" int tw_debug_overlay_plan(unsigned long long expect, unsigned long long target, long long stride,
                                      unsigned long long dst, long long pitch, int width, int height, int* out, int n)
 {
@@ -6071,7 +6256,8 @@ extern "C" const char* tw_debug_family_name(int family)
         "tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level", "tw_polyexp", "tw_update_matrices",
         "tw_flow_iter", "tw_flow_iter_ups", "tw_flow_iter_zero", "tw_blur_solve4", "tw_blur_solve4y", "tw_blur_solve8",
         "tw_blur_solve_pp", "tw_blur_solve_generic", "tw_blur_variant", "tw_blur_grid", "tw_box", "tw_twin",
-        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg", "tw_blur_solve4q",
+        "tw_span_gather", "tw_span_scan", "tw_png_unfilter", "tw_span_scan_seg",
+        "tw_band_rows", "tw_band_search", "tw_band_verify", "tw_flow_band_init", "tw_blur_solve4q",
         "tw_overlay_base", "tw_overlay_marks", "tw_pyr_level_lds",
         "tw_shift_profiles", "tw_shift_search", "tw_shift_verify", "tw_flow_shift_init", "tw_warp_residual", "tw_change_scan",
         "tw_flow_iter_grid",
@@ -7100,6 +7286,89 @@ tw_status tw_stage_shift(tw_engine* e, const uint8_t* expect, const uint8_t* tar
     out->n_zero = hrec[0].n_zero;
     out->sad_shift = hrec[0].sad_shift;
     out->sad_zero = hrec[0].sad_zero;
+    return TW_OK;
+}
+
+tw_status tw_stage_shift_bands(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h, int radius,
+                               int band, int force_global, uint16_t* sig, tw_shift* global, tw_shift_band* bands, int* n_bands)
+{
+    if (!e || !expect || !target || !global || !bands || !n_bands || radius < 1 || radius > 1024) return TW_E_BAD_PARAMETER;
+    if (band < 32 || band > 1024 || band % 16 != 0) return TW_E_BAD_PARAMETER;
+    tw_status r;
+    if ((r = check_dims(e, w, h))) return r;
+    if (stride < w) return TW_E_BAD_PARAMETER;
+    TW_HIP(e, hipSetDevice(e->device));
+    // as tw_stage_shift: both images as they are, each at a 256-byte boundary
+    const size_t ibytes = (size_t)(h - 1) * (size_t)stride + (size_t)w, slot = (ibytes + 255) / 256 * 256;
+    const size_t P = 2 * ((size_t)w + h);
+    const int nb = band_count(h, band), nblk0 = band_blocks(w);
+    const size_t S = 2 * (size_t)h * nblk0;
+    Tmp t;
+    uint8_t* d_img = t.alloc<uint8_t>(2 * slot);
+    const uint8_t** d_ptrs = t.alloc<const uint8_t*>(2);
+    // the pair's share of each output and one more behind it, which no launch may touch
+    unsigned* d_prof = t.alloc<unsigned>(2 * P);
+    ShiftRec* d_rec = t.alloc<ShiftRec>(2);
+    unsigned short* d_sig = t.alloc<unsigned short>(2 * S);
+    BandRec* d_bands = t.alloc<BandRec>(2 * (size_t)nb);
+    if (!d_img || !d_ptrs || !d_prof || !d_rec || !d_sig || !d_bands) return TW_E_NOMEM;
+    TW_TRY(h2d_sync(e, d_img, expect, ibytes));
+    TW_TRY(h2d_sync(e, d_img + slot, target, ibytes));
+    const uint8_t* hp[2] = {d_img, d_img + slot};
+    TW_TRY(h2d_sync(e, (void*)d_ptrs, hp, sizeof(hp)));
+    hipStream_t st = e->stream;
+    TW_HIP(e, hipMemsetAsync(d_prof, 0xff, 2 * P * sizeof(unsigned), st));
+    TW_HIP(e, hipMemsetAsync(d_rec, 0xff, 2 * sizeof(ShiftRec), st));
+    TW_HIP(e, hipMemsetAsync(d_sig, 0xff, 2 * S * sizeof(unsigned short), st));
+    TW_HIP(e, hipMemsetAsync(d_bands, 0xff, 2 * (size_t)nb * sizeof(BandRec), st));
+    {
+        // (tw_prof_select(TW_K_SCAN): these launches alone, for measurements)
+        ProfScope pscope(e, st, TW_K_SCAN, 0);
+        TW_TRY(launch_shift_estimate(e, st, d_ptrs, (long long)stride, stride % 4 == 0 ? 1 : 0, w, h, radius, force_global != 0,
+                                     d_prof, d_rec, nullptr, 1));
+        TW_TRY(launch_band_estimate(e, st, d_ptrs, (long long)stride, w, h, radius, band, force_global != 0, d_rec, d_sig, d_bands,
+                                    nullptr, 1));
+    }
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    std::vector<unsigned> hprof(2 * P);
+    std::vector<unsigned short> hsig(2 * S);
+    std::vector<BandRec> hb(2 * (size_t)nb);
+    ShiftRec hrec[2];
+    TW_TRY(d2h_sync(e, hprof.data(), d_prof, 2 * P * sizeof(unsigned)));
+    TW_TRY(d2h_sync(e, hrec, d_rec, sizeof(hrec)));
+    TW_TRY(d2h_sync(e, hsig.data(), d_sig, 2 * S * sizeof(unsigned short)));
+    TW_TRY(d2h_sync(e, hb.data(), d_bands, 2 * (size_t)nb * sizeof(BandRec)));
+    bool clean = true;
+    for (size_t i = P; i < 2 * P; i++) clean = clean && hprof[i] == 0xffffffffu;
+    for (size_t i = S; i < 2 * S; i++) clean = clean && hsig[i] == 0xffffu;
+    for (size_t i = 0; i < sizeof(ShiftRec); i++) clean = clean && ((const unsigned char*)&hrec[1])[i] == 0xff;
+    for (size_t i = 0; i < (size_t)nb * sizeof(BandRec); i++) clean = clean && ((const unsigned char*)&hb[nb])[i] == 0xff;
+    if (!clean) {
+        e->err = "tw_stage_shift_bands: a launch wrote beyond the pair's share";
+        return TW_E_DEVICE;
+    }
+    // the signatures' rows are nblk apart in each image's share of h * nblk0; behind them the share is zero
+    const int dx = hrec[0].dx, nblk = (std::min(w, w - dx) - std::max(0, -dx) + 63) / 64;
+    for (int q = 0; q < 2; q++) {
+        const unsigned short* s = hsig.data() + (size_t)q * h * nblk0;
+        for (size_t i = (size_t)h * nblk; i < (size_t)h * nblk0; i++)
+            if (s[i] != 0) {
+                e->err = "tw_stage_shift_bands: the rest of an image's signatures is not zero";
+                return TW_E_DEVICE;
+            }
+        if (sig) memcpy(sig + (size_t)q * h * nblk, s, (size_t)h * nblk * sizeof(unsigned short));
+    }
+    global->dx = hrec[0].dx;
+    global->dy = hrec[0].dy;
+    global->applied = hrec[0].applied;
+    global->n_shift = hrec[0].n_shift;
+    global->n_zero = hrec[0].n_zero;
+    global->sad_shift = hrec[0].sad_shift;
+    global->sad_zero = hrec[0].sad_zero;
+    static_assert(sizeof(BandRec) == sizeof(tw_shift_band), "copied as bytes");
+    memcpy(bands, hb.data(), (size_t)nb * sizeof(BandRec));
+    *n_bands = nb;
     return TW_OK;
 }
 

@@ -5913,6 +5913,304 @@ __global__ __launch_bounds__(256) void tw_flow_shift_init(ShiftInitArgs s)
 }
 
 // =====================================================================================================
+// Shift bands (TW_OPT_SHIFT_BANDS): one vertical shift per band of B rows, behind the pair's global shift (include/twflow.h has
+// the definition; all of it integer).  dx is the pair's global dx (ShiftRec::dx, final since tw_shift_search), xa / xb the
+// overlap's columns of E, nblk = ceil((xb - xa) / 64) <= nblk0 = ceil(w / 64).
+//   tw_band_rows : grid z = the part's IMAGES.  A lane owns one (row, block) of one image: the sum of its (at most) 64 bytes,
+//     E from column xa + 64 k, T from xa + dx + 64 k — 16-byte loads where the lane's first byte is 16-byte aligned and the
+//     block is whole, dword loads where it is 4-byte aligned, byte loads otherwise (padding is never read).  An image's
+//     signatures are [h][nblk] uint16, rows nblk apart, in a share of h * nblk0; the rest of the share is written as zeros, so
+//     the launch writes the whole buffer.
+//   tw_band_search : one 1024-thread workgroup per (pair, band).  A wave owns every 16th candidate of the visit order; with
+//     rows nblk apart a candidate's elements are one contiguous run of both images' signatures, which the lanes stride.  The
+//     winner by shift_better with the candidate's row count.  A skipped candidate (too few rows) takes part in nothing, and the
+//     order among the others is their index in the visit order, so the rule holds.  The band's rows of sigE and the rows of
+//     sigT it can reach are staged in LDS when the host says they fit (BandSearchArgs::lds).
+//   tw_band_verify<0> : chunks of BV_ROWS rows (a chunk lies in one band: B is a multiple of 16); |E - T| at (0, 0) over the
+//     whole rows and at (dx, dy_b) over the overlap, one 64-bit integer atomic each per workgroup.  <1> : one thread per
+//     (pair, band), behind it: areas and `applied`.
+//   tw_flow_band_init : tw_flow_shift_init with a source value that depends on the source row's band.  A workgroup first
+//     turns the pair's records into the two values per band in LDS; a source row's band is row / B by a multiply with the
+//     host's floor(2^32 / B) + 1 (exact for rows below 2^15 and B up to 2^10).
+// =====================================================================================================
+struct BandRec {  // = tw_shift_band
+    int y, rows, dy, applied, n_shift, n_zero;
+    unsigned long long sad_shift, sad_zero;
+};
+constexpr int BV_ROWS = 16;
+constexpr int BS_LDS_BYTES = 96 * 1024;  // tw_band_search stages a band's signatures in LDS up to here (announced to the runtime)
+constexpr int BI_BANDS = 1024;           // the most bands a pair has: 32768 rows in bands of 32
+struct BandRowsArgs {
+    const uint8_t* const* srcs;  // image z: srcs[z] (pair z >> 1)
+    long long stride;
+    int w, h, nblk0;
+    const ShiftRec* rec;         // pair p (dx)
+    unsigned short* sig;         // pair p, image q: h * nblk0 entries at sig + (2 p + q) * h * nblk0
+};
+// the sum of a dword's four bytes
+__device__ __forceinline__ unsigned band_sum4(unsigned d)
+{
+    const unsigned t = (d & 0x00ff00ffu) + ((d >> 8) & 0x00ff00ffu);
+    return (t & 0xffffu) + (t >> 16);
+}
+__global__ __launch_bounds__(256) void tw_band_rows(BandRowsArgs a)
+{
+    const int z = blockIdx.z, q = z & 1;
+    const long long share = (long long)a.h * a.nblk0;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= share) return;
+    const int dx = a.rec[z >> 1].dx;
+    const int xa = max(0, -dx), xb = min(a.w, a.w - dx), nblk = (xb - xa + 63) >> 6;
+    unsigned short* __restrict__ out = a.sig + (long long)z * share;
+    if (i >= (long long)a.h * nblk) {
+        out[i] = 0;
+        return;
+    }
+    const int y = (int)(i / nblk), k = (int)(i - (long long)y * nblk);
+    const int x0 = xa + 64 * k, cnt = min(64, xb - x0);
+    const uint8_t* __restrict__ p = a.srcs[z] + (long long)y * a.stride + x0 + (q ? dx : 0);
+    unsigned s = 0;
+    const unsigned al = (unsigned)(uintptr_t)p;
+    if (cnt == 64 && (al & 15u) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint4 v = ((const uint4*)p)[j];
+            s += (band_sum4(v.x) + band_sum4(v.y)) + (band_sum4(v.z) + band_sum4(v.w));
+        }
+    } else if (cnt == 64 && (al & 3u) == 0) {
+#pragma unroll
+        for (int j = 0; j < 16; j++) s += band_sum4(((const unsigned*)p)[j]);
+    } else {
+        for (int j = 0; j < cnt; j++) s += p[j];
+    }
+    out[i] = (unsigned short)s;
+}
+
+struct BandSearchArgs {
+    const unsigned short* sig;  // as BandRowsArgs::sig
+    const ShiftRec* rec;        // pair p (dx)
+    int w, h, nblk0, radius, band, nb;
+    int lds;                    // the band's rows of sigE and the rows of sigT within its reach are staged in LDS
+    BandRec* bands;             // pair p, band b: bands[p * nb + b]
+};
+__global__ __launch_bounds__(1024) void tw_band_search(BandSearchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned short bs_sig[];  // [rows_b][nblk] of E, then [t1 - t0][nblk] of T
+    __shared__ unsigned long long bs_cost[16];
+    __shared__ int bs_k[16], bs_n[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, p = blockIdx.y;
+    const int dx = a.rec[p].dx;
+    const int xa = max(0, -dx), xb = min(a.w, a.w - dx), nblk = (xb - xa + 63) >> 6;
+    const int y0 = b * a.band, rows = min(a.band, a.h - y0);
+    const int r = min(a.radius, a.h / 2), ncand = 2 * r + 1;
+    const long long share = (long long)a.h * a.nblk0;
+    const unsigned short* __restrict__ gE = a.sig + (long long)p * 2 * share;
+    const unsigned short* __restrict__ gT = gE + share;
+    // E's row i is at sE + (i - e0) * nblk, T's row i at sT + (i - t0) * nblk
+    const unsigned short* __restrict__ sE = gE;
+    const unsigned short* __restrict__ sT = gT;
+    int e0 = 0, t0 = 0;
+    if (a.lds) {
+        e0 = y0;
+        t0 = max(0, y0 - r);
+        const int t1 = min(a.h, y0 + rows + r);
+        const int ne = rows * nblk, nt = (t1 - t0) * nblk;
+        for (int i = tid; i < ne; i += 1024) bs_sig[i] = gE[(long long)e0 * nblk + i];
+        for (int i = tid; i < nt; i += 1024) bs_sig[ne + i] = gT[(long long)t0 * nblk + i];
+        __syncthreads();
+        sE = bs_sig;
+        sT = bs_sig + ne;
+    }
+    const int need = (rows + 1) >> 1;
+    unsigned long long bc = 0;
+    int bk = -1, bn = 0;  // (wave-uniform: every lane holds the reduced cost)
+    for (int k = wave; k < ncand; k += 16) {
+        const int d = shift_cand(k);
+        const int lo = max(y0, -d), hi = min(y0 + rows, a.h - d), n = hi - lo;
+        if (k != 0 && n < need) continue;
+        const unsigned short* __restrict__ pe = sE + (long long)(lo - e0) * nblk;
+        const unsigned short* __restrict__ pt = sT + (long long)(lo + d - t0) * nblk;
+        const int ne = n * nblk;
+        unsigned long long c = 0;
+        for (int i = lane; i < ne; i += 64) {
+            const int e = pe[i], t = pt[i];
+            c += (unsigned)abs(e - t);
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned clo = __shfl_xor((unsigned)c, off), chi = __shfl_xor((unsigned)(c >> 32), off);
+            c += ((unsigned long long)chi << 32) | clo;
+        }
+        if (bk < 0 || shift_better(c, n, k, bc, bn, bk)) {
+            bc = c;
+            bk = k;
+            bn = n;
+        }
+    }
+    if (lane == 0) {
+        bs_cost[wave] = bc;
+        bs_k[wave] = bk;
+        bs_n[wave] = bn;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        // (wave 0 owns candidate 0, which is never skipped: bs_k[0] >= 0 always)
+        bc = bs_cost[0];
+        bk = bs_k[0];
+        bn = bs_n[0];
+        for (int v = 1; v < 16; v++) {
+            const int k = bs_k[v];
+            if (k >= 0 && shift_better(bs_cost[v], bs_n[v], k, bc, bn, bk)) {
+                bc = bs_cost[v];
+                bk = k;
+                bn = bs_n[v];
+            }
+        }
+        BandRec* __restrict__ o = a.bands + (long long)p * a.nb + b;
+        o->y = y0;
+        o->rows = rows;
+        o->dy = shift_cand(bk);
+    }
+}
+
+struct BandVerifyArgs {
+    const uint8_t* const* srcs;  // pair p: E = srcs[2p], T = srcs[2p + 1]
+    long long stride;
+    int w, h, npairs, band, nb;
+    const ShiftRec* rec;         // pair p (dx)
+    BandRec* bands;              // pair p, band b; the sums are zero when tw_band_verify<0> starts
+    const FlowDst* own;          // as ShiftVerifyArgs::own
+};
+template <int PHASE>
+__global__ __launch_bounds__(256) void tw_band_verify(BandVerifyArgs a)
+{
+    if (PHASE == 1) {
+        const int i = blockIdx.x * 256 + threadIdx.x;
+        if (i >= a.npairs * a.nb) return;
+        const int p = i / a.nb;
+        BandRec r = a.bands[i];
+        const int dx = a.rec[p].dx;
+        const int lo = max(r.y, -r.dy), hi = min(r.y + r.rows, a.h - r.dy);
+        const unsigned long long n0 = (unsigned long long)r.rows * (unsigned long long)a.w;
+        unsigned long long ns = n0;
+        int applied = 0;
+        if (dx != 0 || r.dy != 0) {
+            ns = (unsigned long long)(hi - lo) * (unsigned long long)(a.w - abs(dx));
+            applied = r.sad_shift * n0 <= (r.sad_zero >> 2) * ns ? 1 : 0;
+        } else {
+            r.sad_shift = r.sad_zero;
+        }
+        if (a.own && a.own[p].p) applied = 0;
+        r.applied = applied;
+        r.n_shift = (int)ns;
+        r.n_zero = (int)n0;
+        a.bands[i] = r;
+        return;
+    }
+    __shared__ unsigned long long bv_sum[2][4];
+    const int p = blockIdx.y;
+    const uint8_t* __restrict__ E = a.srcs[2 * p];
+    const uint8_t* __restrict__ T = a.srcs[2 * p + 1];
+    BandRec* __restrict__ rec = a.bands + (long long)p * a.nb + ((int)blockIdx.x * BV_ROWS) / a.band;
+    const int dx = a.rec[p].dx, dy = rec->dy;
+    const bool moved = dx != 0 || dy != 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int xa = max(0, -dx), xb = min(a.w, a.w - dx);  // the overlap's columns of E
+    const int y1 = min(a.h, ((int)blockIdx.x + 1) * BV_ROWS);
+    unsigned long long s0 = 0, ss = 0;
+    for (int y = blockIdx.x * BV_ROWS + wave; y < y1; y += 4) {
+        const uint8_t* __restrict__ er = E + (long long)y * a.stride;
+        const uint8_t* __restrict__ tr = T + (long long)y * a.stride;
+        const bool in = moved && y + dy >= 0 && y + dy < a.h;
+        const uint8_t* __restrict__ ts = T + (long long)(in ? y + dy : y) * a.stride;
+        unsigned r0 = 0, rs = 0;  // (a row's sums: at most 255 * 32768)
+        for (int x = lane; x < a.w; x += 64) {
+            const int ev = er[x];
+            r0 += (unsigned)abs(ev - (int)tr[x]);
+            if (in && x >= xa && x < xb) rs += (unsigned)abs(ev - (int)ts[x + dx]);
+        }
+        s0 += r0;
+        ss += rs;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        s0 += ((unsigned long long)__shfl_xor((unsigned)(s0 >> 32), off) << 32) | __shfl_xor((unsigned)s0, off);
+        ss += ((unsigned long long)__shfl_xor((unsigned)(ss >> 32), off) << 32) | __shfl_xor((unsigned)ss, off);
+    }
+    if (lane == 0) {
+        bv_sum[0][wave] = s0;
+        bv_sum[1][wave] = ss;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s0 = (bv_sum[0][0] + bv_sum[0][1]) + (bv_sum[0][2] + bv_sum[0][3]);
+        ss = (bv_sum[1][0] + bv_sum[1][1]) + (bv_sum[1][2] + bv_sum[1][3]);
+        if (s0) atomicAdd(&rec->sad_zero, s0);
+        if (ss) atomicAdd(&rec->sad_shift, ss);
+    }
+}
+
+struct BandInitArgs {
+    AreaInitArgs g;        // as ShiftInitArgs::g
+    const ShiftRec* rec;   // pair z (dx)
+    const BandRec* bands;  // pair z, band b: bands[z * nb + b]
+    int band, nb;
+    unsigned magic;        // floor(2^32 / band) + 1: row / band == __umulhi(row, magic)
+    int zero_rest;         // as ShiftInitArgs::zero_rest
+};
+__global__ __launch_bounds__(256) void tw_flow_band_init(BandInitArgs s)
+{
+    __shared__ float bi_val[2][BI_BANDS];  // band b of the pair: the explicit field's (x, y) value in its rows
+    const AreaInitArgs& a = s.g;
+    const BandRec* __restrict__ bands = s.bands + (long long)blockIdx.z * s.nb;
+    const int dx = s.rec[blockIdx.z].dx;
+    int any = 0;
+    for (int b = threadIdx.x; b < s.nb; b += 256) {
+        const int applied = bands[b].applied;
+        bi_val[0][b] = applied ? (float)dx : 0.f;
+        bi_val[1][b] = applied ? (float)bands[b].dy : 0.f;
+        any |= applied;
+    }
+    const bool seeds = __syncthreads_or(any) != 0;
+    if (!seeds && !s.zero_rest) return;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.w || y >= a.h) return;
+    float* __restrict__ out = a.flow + (long long)blockIdx.z * 2 * a.fps;
+    float v[2] = {0.f, 0.f};
+    if (seeds) {
+        const unsigned magic = s.magic;
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            // the explicit field's value in source row sr
+            auto F = [&](int sr) { return bi_val[c][__umulhi((unsigned)sr, magic)]; };
+            float t;
+            if (a.mode == 0) {
+                t = F(y);
+            } else if (a.mode == 1) {
+                const int ix = a.ix, sy0 = y * a.iy;
+                t = area_fast_sum(ix * a.iy, [&](int k) { return F(sy0 + k / ix); });
+                t = t * a.inv_area;
+            } else {
+                t = 0.f;
+                const int j0 = a.ystart[y], j1 = a.ystart[y + 1], k0 = a.xstart[x], k1 = a.xstart[x + 1];
+                for (int j = j0; j < j1; j++) {
+                    const float f = F(a.ysi[j]);
+                    float b = 0.f;
+                    for (int k = k0; k < k1; k++) {
+                        const float m = f * a.xalpha[k];
+                        b = b + m;
+                    }
+                    const float bb = a.ybeta[j] * b;
+                    t = j == j0 ? bb : t + bb;
+                }
+            }
+            v[c] = area_scale(a, t);
+        }
+    }
+    out[(long long)y * a.ld + x] = v[0];
+    out[a.fps + (long long)y * a.ld + x] = v[1];
+}
+
+// =====================================================================================================
 // tw_overlay_base / tw_overlay_marks — one pair's diff image (tw_ticket_overlay; the semantics are include/twflow.h's, "Diff
 //   image"), rendered on request after the pair's batch has finished.  RGB bytes, rows `pitch` bytes apart; nothing behind a
 //   row's 3 w bytes is written.

@@ -132,6 +132,22 @@ napi_value convert_result(napi_env env, const Response& r)
         napi_set_named_property(env, sh, "applied", ap);
         napi_set_named_property(env, o, "shift", sh);
     }
+    if (r.hasBands) {
+        // not in the reference (new TidalWave({shift: R, shiftBands: B}) only), behind `shift`: one vertical shift per band of B rows
+        napi_value arr;
+        napi_create_array_with_length(env, r.bands.size(), &arr);
+        for (size_t i = 0; i < r.bands.size(); i++) {
+            napi_value bo, ap;
+            napi_create_object(env, &bo);
+            set_i32(env, bo, "y", r.bands[i].y);
+            set_i32(env, bo, "rows", r.bands[i].rows);
+            set_i32(env, bo, "dy", r.bands[i].dy);
+            napi_get_boolean(env, r.bands[i].applied, &ap);
+            napi_set_named_property(env, bo, "applied", ap);
+            napi_set_element(env, arr, (uint32_t)i, bo);
+        }
+        napi_set_named_property(env, o, "bands", arr);
+    }
     if (!r.overlay.empty()) {
         // not in the reference (new TidalWave({overlay: dir}) only, SUSPICIOUS pairs only), behind every other key: the path of
         // the pair's diff image
@@ -278,6 +294,8 @@ napi_value construct(napi_env env, napi_callback_info info)
     // not in the reference: start every pair's flow from its global shift, found on the device — 0 (default): off; 1 .. 1024:
     // the search radius in pixels
     p.shift = get_i32(env, opts, "shift", 0);
+    // ... and from one vertical shift per band of `shiftBands` rows (32 .. 1024, a multiple of 16; needs `shift`) — 0 (default): off
+    p.shiftBands = get_i32(env, opts, "shiftBands", 0);
     // not in the reference: a directory for the diff images of SUSPICIOUS pairs, rendered on the device ("" / absent: off), and
     // the gray-level difference above which a pixel is painted as changed (0 .. 255)
     p.overlayDir = get_str(env, opts, "overlay", "");

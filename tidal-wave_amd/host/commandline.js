@@ -6,7 +6,8 @@
 // in every vector), N being the gap in grid steps that still joins two vectors; -residual N (1 .. 254), the cells of every pair
 // with a pixel that differs by more than N gray levels and how many of those the flow does not explain (`change` behind the
 // other keys), and -residualMin N, which makes a pair with at least N unexplained pixels SUSPICIOUS even without a vector; -shift N (1 .. 1024),
-// every pair's flow started from its global shift of at most N pixels, found on the device (`shift` behind the other keys);
+// every pair's flow started from its global shift of at most N pixels, found on the device (`shift` behind the other keys); -shiftBands N (32 .. 1024, a multiple of 16; with -shift), one vertical shift
+// per band of N rows instead (`bands` behind `shift`);
 // -overlay DIR, a diff image of every SUSPICIOUS pair, rendered on the device and written to DIR (created if missing) as a PNG
 // whose path is the result's last key `overlay`, and -overlayTol N (0 .. 255, default 16), the gray-level difference above
 // which a pixel is painted as changed.  The reference's own script cannot run (it requires
@@ -26,7 +27,7 @@ var usage =
   '  $ node commandline.js -threshold 1.0 -span 10 test/images test/images2\n';
 
 var supportedOptions = ['threshold', 'span', 'pyrScale', 'pyrLevels', 'winSize', 'pyrIterations', 'polyN',
-  'polySigma', 'flags', 'numThreads', 'regions', 'residual', 'residualMin', 'shift', 'overlayTol'];
+  'polySigma', 'flags', 'numThreads', 'regions', 'residual', 'residualMin', 'shift', 'shiftBands', 'overlayTol'];
 
 function getArgs(argv) {
   var positional = [], options = {};

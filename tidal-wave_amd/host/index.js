@@ -9,7 +9,9 @@
 // `residual` (1 .. 254) and `residualMin` likewise: every 'data' result then carries `change`, the cells with a pixel that
 // differs by more than `residual` gray levels, and a pair with at least `residualMin` unexplained pixels is SUSPICIOUS;
 // `shift` (1 .. 1024, the search radius in pixels): every pair's flow starts from its global integer shift, found and checked on the
-// device, and every 'data' result carries `shift: {x, y, applied}` behind the other keys.  `status` is unchanged by it;
+// device, and every 'data' result carries `shift: {x, y, applied}` behind the other keys; `shiftBands` (32 .. 1024, a multiple of 16, with `shift`): the flow starts
+// from one vertical shift per band of that many rows instead, and every 'data' result carries `bands: [{y, rows, dy, applied}, ...]`
+// behind `shift`.  `status` is unchanged by it;
 // `overlay` (an existing directory) and `overlayTol` (0 .. 255, default 16): every SUSPICIOUS pair's diff image is rendered on the
 // device and written there as a PNG, and its 'data' result carries the file's path as `overlay`, the last key.
 'use strict';

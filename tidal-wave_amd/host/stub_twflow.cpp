@@ -71,6 +71,8 @@ struct tw_engine {
     std::map<tw_ticket, int> tol_of;       // ticket -> that option's value when the pair was submitted (0: off)
     int shift = 0;                         // TW_OPT_SHIFT as tw_set_option left it
     std::map<tw_ticket, tw_shift> shift_of;  // ticket -> the pair's record, computed when it was submitted with the option on
+    int bands = 0;                         // TW_OPT_SHIFT_BANDS as tw_set_option left it
+    std::map<tw_ticket, std::vector<tw_shift_band>> bands_of;  // ticket -> the pair's band records, likewise (both options on)
     std::string err;
     tw_ticket next = 1;
     int submit_calls = 0, busy_at = 0;  // TW_STUB_BUSY_AT
@@ -299,6 +301,13 @@ tw_status tw_set_option(tw_engine* e, int option, int value)
             e->shift = value;
         }
     }
+    if (option == TW_OPT_SHIFT_BANDS) {
+        if (value != 0 && (value < 32 || value > 1024 || value % 16 != 0)) r = TW_E_BAD_PARAMETER;
+        else if (e) {
+            std::lock_guard<std::mutex> lk(e->m);
+            e->bands = value;
+        }
+    }
     if (tracing()) trace(e, "tw_set_option option=%d value=%d -> %s", option, value, status_name(r));
     return r;
 }
@@ -407,6 +416,61 @@ static tw_shift stub_shift(const uint8_t* a, const uint8_t* b, int w, int h, ptr
     return s;
 }
 
+// TW_OPT_SHIFT_BANDS on the CPU, the definition of include/twflow.h restated: the row signatures at the pair's global dx, the
+// search of each band, its acceptance check.  sig (nullable): [sigE[h][nblk], sigT[h][nblk]].
+static std::vector<tw_shift_band> stub_bands(const uint8_t* a, const uint8_t* b, int w, int h, ptrdiff_t stride, int R, int B, int dx,
+                                             uint16_t* sig = nullptr)
+{
+    const int xa = std::max(0, -dx), xb = std::min(w, w - dx), nblk = (xb - xa + 63) / 64;
+    std::vector<uint16_t> sE((size_t)h * nblk, 0), sT((size_t)h * nblk, 0);
+    for (int y = 0; y < h; y++)
+        for (int x = xa; x < xb; x++) {
+            sE[(size_t)y * nblk + (x - xa) / 64] += a[y * stride + x];
+            sT[(size_t)y * nblk + (x - xa) / 64] += b[y * stride + x + dx];
+        }
+    if (sig) {
+        memcpy(sig, sE.data(), sE.size() * sizeof(uint16_t));
+        memcpy(sig + sE.size(), sT.data(), sT.size() * sizeof(uint16_t));
+    }
+    const int r = std::min(R, h / 2);
+    std::vector<tw_shift_band> out;
+    for (int y0 = 0; y0 < h; y0 += B) {
+        const int rows = std::min(B, h - y0), need = (rows + 1) / 2;
+        int best = 0;
+        uint64_t bc = 0, bn = 0;
+        for (int k = 0; k <= 2 * r; k++) {
+            const int d = (k & 1) ? -((k + 1) / 2) : k / 2;  // 0, -1, +1, -2, +2, ...
+            const int lo = std::max(y0, -d), hi = std::min(y0 + rows, h - d);
+            if (k != 0 && hi - lo < need) continue;
+            uint64_t c = 0;
+            for (int i = lo; i < hi; i++)
+                for (int j = 0; j < nblk; j++) c += (uint64_t)abs((int)sE[(size_t)i * nblk + j] - (int)sT[(size_t)(i + d) * nblk + j]);
+            const uint64_t n = (uint64_t)(hi - lo);
+            if (k == 0 || c * bn < bc * n) best = d, bc = c, bn = n;
+        }
+        tw_shift_band s;
+        memset(&s, 0, sizeof(s));
+        s.y = y0;
+        s.rows = rows;
+        s.dy = best;
+        s.n_zero = rows * w;
+        for (int y = y0; y < y0 + rows; y++)
+            for (int x = 0; x < w; x++) s.sad_zero += (uint64_t)abs((int)a[y * stride + x] - (int)b[y * stride + x]);
+        s.n_shift = s.n_zero;
+        s.sad_shift = s.sad_zero;
+        if (dx != 0 || best != 0) {
+            const int lo = std::max(y0, -best), hi = std::min(y0 + rows, h - best);
+            s.n_shift = (hi - lo) * (xb - xa);
+            s.sad_shift = 0;
+            for (int y = lo; y < hi; y++)
+                for (int x = xa; x < xb; x++) s.sad_shift += (uint64_t)abs((int)a[y * stride + x] - (int)b[(y + best) * stride + x + dx]);
+            s.applied = s.sad_shift * (uint64_t)s.n_zero <= (s.sad_zero >> 2) * (uint64_t)s.n_shift ? 1 : 0;
+        }
+        out.push_back(s);
+    }
+    return out;
+}
+
 // What the entry points do once a call is recorded (and not refused by TW_STUB_BUSY_AT): they call one another through these.
 // stride > 0: a and b are whole images of w x h bytes (tw_submit_u8); 0: only their first bytes are there (every other
 // entry point hands on a pair's first pixels), and a shift record is then that of the 1 x 1 pair of those two bytes
@@ -418,12 +482,16 @@ static tw_status stub_u8(tw_engine* e, const uint8_t* a, const uint8_t* b, int w
     const int radius = e->shift;
     tw_shift sh;
     if (radius) sh = stride ? stub_shift(a, b, w, h, stride, radius) : stub_shift(a, b, 1, 1, 1, radius);
+    // (the bands take effect only with the shift on; as the shift record, on the whole images where they are there)
+    std::vector<tw_shift_band> bd;
+    if (radius && e->bands) bd = stride ? stub_bands(a, b, w, h, stride, radius, e->bands, sh.dx) : stub_bands(a, b, 1, 1, 1, radius, e->bands, sh.dx);
     *t = e->next++;
     e->open[*t] = w + (a[0] != b[0] ? 1000000 : 0);
     e->info[*t] = tw_engine::PairInfo{w, h, {a[0], b[0]}};
     if (e->regions) e->gap_of[*t] = e->regions;
     if (e->residual) e->tol_of[*t] = e->residual;
     if (radius) e->shift_of[*t] = sh;
+    if (!bd.empty()) e->bands_of[*t] = bd;
     if (e->batch_ms > 0) {
         e->batch_of[*t] = e->cur_batch;
         if (++e->cur_count >= e->cap) e->launch_locked();  // a full batch starts by itself, like the engine's
@@ -821,6 +889,7 @@ static tw_status stub_wait(tw_engine* e, tw_ticket t, tw_vector* out, int cap, i
         e->gap_of.erase(t);
         e->tol_of.erase(t);
         e->shift_of.erase(t);
+        e->bands_of.erase(t);
     }
     if (e->batch_ms > 0) {
         stub_clock::time_point until;
@@ -967,6 +1036,49 @@ tw_status tw_ticket_shift(tw_engine* e, tw_ticket t, tw_shift* out)
     }
     if (tracing()) trace(e, "tw_ticket_shift ticket=%lld -> %s", (long long)t, status_name(r));
     return r;
+}
+// The band records of a pair that was submitted with TW_OPT_SHIFT and TW_OPT_SHIFT_BANDS on; the ticket is not consumed.  The
+// definition computed on the CPU when the pair was submitted (stub_bands), as tw_ticket_shift's record.
+tw_status tw_ticket_shift_bands(tw_engine* e, tw_ticket t, tw_shift_band* out, int cap, int* n)
+{
+    if (!e) return TW_E_BAD_PARAMETER;
+    tw_status r = TW_OK;
+    {
+        std::lock_guard<std::mutex> lk(e->m);
+        auto it = e->bands_of.find(t);
+        if (!n || cap < 0 || (!out && cap > 0) || it == e->bands_of.end() || e->open.find(t) == e->open.end()) r = TW_E_BAD_PARAMETER;
+        else {
+            const int nb = (int)it->second.size();
+            for (int i = 0; i < std::min(nb, cap); i++) out[i] = it->second[i];
+            *n = nb;
+        }
+    }
+    if (tracing()) trace(e, "tw_ticket_shift_bands ticket=%lld cap=%d -> %s", (long long)t, cap, status_name(r));
+    return r;
+}
+// The stage entry on the CPU: the global record and the bands of the caller's pair (no guards to check: nothing is launched)
+tw_status tw_stage_shift_bands(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h, int radius,
+                               int band, int, uint16_t* sig, tw_shift* global, tw_shift_band* bands, int* n_bands)
+{
+    if (!e || !expect || !target || !global || !bands || !n_bands || radius < 1 || radius > 1024) return TW_E_BAD_PARAMETER;
+    if (band < 32 || band > 1024 || band % 16 != 0 || w < 1 || h < 1 || stride < w) return TW_E_BAD_PARAMETER;
+    *global = stub_shift(expect, target, w, h, stride, radius);
+    const std::vector<tw_shift_band> bd = stub_bands(expect, target, w, h, stride, radius, band, global->dx, sig);
+    for (size_t i = 0; i < bd.size(); i++) bands[i] = bd[i];
+    *n_bands = (int)bd.size();
+    return TW_OK;
+}
+// (a pure host function in the library too; the stub launches nothing: the LDS decision and the grids are the library's rule)
+int tw_debug_band_plan(int width, int height, int radius, int band, int* out, int n)
+{
+    if (!out || width < 1 || height < 1 || radius < 1 || radius > 1024 || band < 32 || band > 1024 || band % 16 != 0) return 0;
+    const int nblk = (width + 63) / 64, rows = std::min(band, height), r = std::min(radius, height / 2);
+    const long long bytes = 2ll * nblk * (rows + std::min(height, rows + 2 * r));
+    const int v[9] = {(height + band - 1) / band, nblk, bytes <= 96 * 1024 ? 1 : 0, (int)std::min(bytes, 2147483647ll), 96 * 1024, r,
+                      (int)(((long long)height * nblk + 255) / 256), 1024, (height + 15) / 16};
+    const int m = std::max(0, std::min(n, 9));
+    for (int i = 0; i < m; i++) out[i] = v[i];
+    return m;
 }
 // The diff image calls; neither consumes the ticket.  tw_ticket_hits echoes the count the ticket's tw_wait will give; a pair
 // whose tw_wait will answer a bad palette index answers it here too, and stays waitable.  The stub renders nothing:

@@ -40,6 +40,7 @@
 #pragma weak tw_wait_regions
 #pragma weak tw_ticket_changes
 #pragma weak tw_ticket_shift
+#pragma weak tw_ticket_shift_bands
 #pragma weak tw_ticket_hits
 #pragma weak tw_ticket_overlay
 
@@ -1083,6 +1084,10 @@ struct ConsumerRun {
     std::vector<tw_change> change_recs;
     // shift (ConsumerShared::shift; 0: off): the search radius the engine was given
     int shift_radius = 0;
+    // shift bands (ConsumerShared::shiftBands; 0: off, and always off without the shift): the band height the engine was given,
+    // and tw_ticket_shift_bands' scratch array
+    int shift_bands = 0;
+    std::vector<tw_shift_band> band_recs;
     // diff images (ConsumerShared::overlayDir; empty: off): the directory, the tolerance, and tw_ticket_overlay's pixels
     std::string overlay_dir;
     int overlay_tol = 16;
@@ -1202,6 +1207,18 @@ struct ConsumerRun {
                 shift_radius = residual_tol = regions_gap = 0;
             }
         }
+        // Shift bands (Parameter::shiftBands): the option once, behind TW_OPT_SHIFT; then tw_ticket_shift_bands behind
+        // tw_ticket_shift.  Off, or without the shift: neither call is made
+        shift_bands = eng && shared && shift_radius ? shared->shiftBands : 0;
+        if (shift_bands) {
+            const tw_status r = tw_ticket_shift_bands ? tw_set_option(eng, TW_OPT_SHIFT_BANDS, shift_bands) : TW_E_UNSUPPORTED;
+            if (r != TW_OK) {
+                eng_err = std::string("engine: shiftBands: ") + tw_strerror(r);
+                tw_engine_destroy(eng);
+                eng = nullptr;
+                shift_bands = shift_radius = residual_tol = regions_gap = 0;
+            }
+        }
         // Diff images (Parameter::overlayDir): no option to set — the picture is rendered per ticket, on request.  Off: neither
         // call is made.  Asked-for pictures are never silently dropped either: a library without the calls, a tolerance outside
         // 0 .. 255, or a directory that does not exist or cannot be written to leaves the consumer without an engine.  (A picture
@@ -1221,7 +1238,7 @@ struct ConsumerRun {
             tw_engine_destroy(eng);
             eng = nullptr;
             overlay_dir.clear();
-            shift_radius = residual_tol = regions_gap = 0;
+            shift_bands = shift_radius = residual_tol = regions_gap = 0;
         }
         prof = eng && shared && shared->profile;
         if (prof) {
@@ -1707,6 +1724,17 @@ struct ConsumerRun {
                 rc = tw_ticket_shift(eng, s.ticket, &shift_rec);
                 if (rc != TW_OK) chg_err = engine_error(eng, rc);
             }
+            // ... and its bands (a pair's own height decides their number: asked again when the array was too short)
+            int nbands = 0;
+            if (shift_bands && rc == TW_OK) {
+                if (band_recs.empty()) band_recs.resize(64);
+                rc = tw_ticket_shift_bands(eng, s.ticket, band_recs.data(), (int)band_recs.size(), &nbands);
+                if (rc == TW_OK && nbands > (int)band_recs.size()) {
+                    band_recs.resize((size_t)nbands);
+                    rc = tw_ticket_shift_bands(eng, s.ticket, band_recs.data(), nbands, &nbands);
+                }
+                if (rc != TW_OK) chg_err = engine_error(eng, rc);
+            }
             // ... and the diff image: the count the wait will report, with the changes, is the status the pair will get; a
             // pair that will be SUSPICIOUS gets its picture.  A pair's own error is left to the wait.
             std::string overlay_file;
@@ -1760,6 +1788,14 @@ struct ConsumerRun {
                 if (shift_radius) {
                     out.hasShift = true;
                     out.shift = Shift{shift_rec.dx, shift_rec.dy, shift_rec.applied != 0};
+                }
+                if (shift_bands) {
+                    out.hasBands = true;
+                    for (int b = 0; b < nbands; b++) {
+                        ShiftBand sb;
+                        sb.y = band_recs[b].y, sb.rows = band_recs[b].rows, sb.dy = band_recs[b].dy, sb.applied = band_recs[b].applied != 0;
+                        out.bands.push_back(sb);
+                    }
                 }
                 // (the shift leaves the status alone: a moved page has vectors above the threshold and is SUSPICIOUS as ever)
                 out.status = pair_status(out.vectors.size(), out.changes, residual_min);  // src/consumer.cpp:77
@@ -1877,6 +1913,7 @@ void Manager::start(const Parameter& p)
     shared_.residual = p.residual;
     shared_.residualMin = p.residualMin;
     shared_.shift = p.shift;
+    shared_.shiftBands = p.shiftBands;
     shared_.overlayDir = p.overlayDir;
     shared_.overlayTol = p.overlayTol;
     shared_.stats.assign((size_t)n, ConsumerStats());

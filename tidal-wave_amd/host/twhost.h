@@ -53,8 +53,17 @@ struct Shift {
     int x = 0, y = 0;
     bool applied = false;
 };
+// One band of a pair's rows and its vertical shift (tw_shift_band of include/twflow.h): the band's first row and height, the
+// band search's answer, and whether the band's rows of the pair's start field were (Shift::x, dy)
+struct ShiftBand {
+    int y = 0, rows = 0, dy = 0;
+    bool applied = false;
+};
 struct Response {
     std::vector<Vector> vectors;
+    // not in the reference (Parameter::shift > 0 and Parameter::shiftBands > 0 only): the pair's bands, top to bottom
+    std::vector<ShiftBand> bands;
+    bool hasBands = false;
     // not in the reference (Parameter::shift > 0 only): the pair's integer translation, estimated and checked on the device
     Shift shift;
     bool hasShift = false;
@@ -119,6 +128,10 @@ struct Parameter {
     // TW_OPT_SHIFT) — 0: off, the calls a consumer makes are exactly the ones it made before; 1 .. 1024: the search radius in
     // pixels.  Response::status is unchanged by it
     int shift = 0;
+    // not in the reference: with `shift` on, start every pair's flow from one vertical shift per band of this many rows (the
+    // engine option TW_OPT_SHIFT_BANDS) — 0: off, the calls a consumer makes are exactly the ones it made before; 32 .. 1024,
+    // a multiple of 16: the band height.  Ignored while `shift` is 0
+    int shiftBands = 0;
     // not in the reference: a directory for diff images (empty: off, the calls a consumer makes are exactly the ones it made
     // before).  With it a consumer asks tw_ticket_hits in front of each collecting wait — behind tw_ticket_changes, so that the
     // status pair_status will give is known — and for a pair that will be SUSPICIOUS renders the picture on the device
@@ -308,6 +321,7 @@ struct ConsumerShared {
     int residual = 0;             // Parameter::residual: a consumer sets TW_OPT_RESIDUAL once and asks tw_ticket_changes before each collecting wait
     int residualMin = 0;          // Parameter::residualMin
     int shift = 0;                // Parameter::shift: a consumer sets TW_OPT_SHIFT once and asks tw_ticket_shift before each collecting wait
+    int shiftBands = 0;           // Parameter::shiftBands: a consumer sets TW_OPT_SHIFT_BANDS once behind TW_OPT_SHIFT and asks tw_ticket_shift_bands behind tw_ticket_shift
     std::string overlayDir;       // Parameter::overlayDir: a consumer asks tw_ticket_hits before each collecting wait, tw_ticket_overlay for SUSPICIOUS pairs
     int overlayTol = 16;          // Parameter::overlayTol
 };

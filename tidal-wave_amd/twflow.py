@@ -87,6 +87,15 @@ OVERLAY_RGB8 = 0
 OVERLAY_MAX_LEN = 1024
 # tw_overlay_hit (include/twflow_debug.h): a hit record as the ordered scan leaves it (16 bytes)
 OVERLAY_HIT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("dx", "<f4"), ("dy", "<f4")])
+class ShiftBand(C.Structure):
+    # tw_shift_band (include/twflow.h): one band's vertical shift and its acceptance check (TW_OPT_SHIFT_BANDS / tw_ticket_shift_bands), 40 bytes
+    _fields_ = [("y", C.c_int), ("rows", C.c_int), ("dy", C.c_int), ("applied", C.c_int), ("n_shift", C.c_int), ("n_zero", C.c_int),
+                ("sad_shift", C.c_uint64), ("sad_zero", C.c_uint64)]
+
+    def as_tuple(self):
+        return (self.y, self.rows, self.dy, self.applied, self.n_shift, self.n_zero, self.sad_shift, self.sad_zero)
+
+
 MAX_IGNORE = 32
 MAX_REGIONS = 256
 FLOW_PLANAR, FLOW_INTERLEAVED = 0, 1
@@ -109,6 +118,7 @@ OPT_POLYEXP_F32 = 2
 OPT_REGIONS = 3
 OPT_RESIDUAL = 4
 OPT_SHIFT = 5
+OPT_SHIFT_BANDS = 6
 
 SYMBOLS = [
     "tw_default_params", "tw_abi_version", "tw_has_variants", "tw_device_count", "tw_device_pci_bus_id", "tw_engine_create", "tw_engine_destroy", "tw_strerror",
@@ -129,6 +139,7 @@ SYMBOLS = [
     "tw_wait_regions", "tw_stage_hit_regions",
     "tw_ticket_changes", "tw_stage_warp_residual",
     "tw_ticket_shift", "tw_stage_shift", "tw_debug_shift_plan",
+    "tw_ticket_shift_bands", "tw_stage_shift_bands", "tw_debug_band_plan",
     "tw_ticket_hits", "tw_ticket_overlay", "tw_stage_overlay", "tw_debug_overlay_plan",
     "tw_debug_graphs", "tw_debug_occupancy", "tw_debug_stamps", "tw_debug_stamps_ex", "tw_debug_copy_rate",
     "tw_debug_launch_counts", "tw_debug_family_name", "tw_debug_memory", "tw_debug_check_size", "tw_debug_flow_iter_plan",
@@ -319,6 +330,10 @@ def _bind(path):
     L.tw_stage_shift.argtypes = [vp, u8p, u8p, C.c_ssize_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
                                  C.POINTER(Shift)]
     L.tw_debug_shift_plan.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int]
+    L.tw_ticket_shift_bands.argtypes = [vp, C.c_int64, C.POINTER(ShiftBand), C.c_int, ip]
+    L.tw_stage_shift_bands.argtypes = [vp, u8p, u8p, C.c_ssize_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_uint16), C.POINTER(Shift), C.POINTER(ShiftBand), ip]
+    L.tw_debug_band_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.tw_ticket_hits.argtypes = [vp, C.c_int64, ip]
     L.tw_ticket_overlay.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(OverlayOut)]
     L.tw_stage_overlay.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_ssize_t, C.c_int, rp, C.c_int, vp, C.c_int,
@@ -392,6 +407,7 @@ def _bind(path):
 
 FlowIterPlan = collections.namedtuple("FlowIterPlan", "strips segments nt nt_last")
 ShiftPlan = collections.namedtuple("ShiftPlan", "lds_x lds_y rx ry grid_x block lds_budget prof_grid_x prof_grid_y verify_grid_x")
+BandPlan = collections.namedtuple("BandPlan", "nb nblk lds lds_bytes lds_budget r rows_grid_x block verify_grid_x")
 BlurPlan = collections.namedtuple("BlurPlan", "family block tile_cols rows xsh grid_x grid_y small forced")
 PYR_KERNELS = ("tw_pyr_k3", "tw_pyr_k3f", "tw_pyr_23", "tw_pyr_taps", "tw_pyr_level_lds", "tw_pyr_level")
 PyrPlan = collections.namedtuple("PyrPlan", "kernel targ family block tile_cols rows grid_x grid_y lds pitch aligned4 w h ksize mode xmax "
@@ -967,6 +983,20 @@ class Engine:
         opened from now on take it."""
         self.set_option(OPT_SHIFT, radius)
 
+    def set_shift_bands(self, band):
+        """TW_OPT_SHIFT_BANDS: 0 turns the per-band shifts off (the default), 32 .. 1024 (a multiple of 16) is the band height
+        in rows; batches opened from now on take it, and it takes effect in a batch that also has TW_OPT_SHIFT on."""
+        self.set_option(OPT_SHIFT_BANDS, band)
+
+    def shift_bands(self, ticket):
+        """tw_ticket_shift_bands, before the wait that collects the ticket: the pair's ShiftBand.as_tuple() per band — (y, rows,
+        dy, applied, n_shift, n_zero, sad_shift, sad_zero)."""
+        n = C.c_int(0)
+        self._check(self._L.tw_ticket_shift_bands(self._h, ticket[0], None, 0, C.byref(n)))
+        out = (ShiftBand * max(1, n.value))()
+        self._check(self._L.tw_ticket_shift_bands(self._h, ticket[0], out, n.value, C.byref(n)))
+        return [out[i].as_tuple() for i in range(n.value)]
+
     def shift(self, ticket):
         """tw_ticket_shift, before the wait that collects the ticket: the pair's Shift.as_tuple() — (dx, dy, applied, n_shift,
         n_zero, sad_shift, sad_zero)."""
@@ -1359,6 +1389,46 @@ class Engine:
                                            int(radius), int(bool(force_global)), prof.ctypes.data_as(C.POINTER(C.c_uint32)),
                                            C.byref(out)))
         return (prof[:w], prof[w:2 * w], prof[2 * w:2 * w + h], prof[2 * w + h:]), out.as_tuple()
+
+    def stage_shift_bands(self, expect, target, radius, band, stride=None, force_global=False, pad=0xEE):
+        """The global estimation, then tw_band_rows, tw_band_search and tw_band_verify alone (tw_stage_shift_bands): expect /
+        target (h, w) uint8, strided as in stage_shift.  ((sigE, sigT) each (h, nblk) uint16 at the pair's dx, the global record
+        as Shift.as_tuple(), the band records as ShiftBand.as_tuple() each).  The call itself answers a device error when a
+        launch wrote beyond the pair's share of the 0xff-filled outputs."""
+        expect = np.ascontiguousarray(expect, np.uint8)
+        target = np.ascontiguousarray(target, np.uint8)
+        h, w = expect.shape
+        assert target.shape == (h, w)
+        if stride is None:
+            stride = w
+        else:
+            pe = np.full((h, stride), pad, np.uint8)
+            pt = np.full((h, stride), pad, np.uint8)
+            pe[:, :w] = expect
+            pt[:, :w] = target
+            expect, target = pe, pt
+        nblk0, nb = (w + 63) // 64, (h + int(band) - 1) // int(band)
+        sig = np.zeros(2 * h * nblk0, np.uint16)
+        glob = Shift()
+        bands = (ShiftBand * nb)()
+        n = C.c_int(0)
+        u8p = C.POINTER(C.c_uint8)
+        self._check(self._L.tw_stage_shift_bands(self._h, expect.ctypes.data_as(u8p), target.ctypes.data_as(u8p), stride, w, h,
+                                                 int(radius), int(band), int(bool(force_global)),
+                                                 sig.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(glob), bands, C.byref(n)))
+        assert n.value == nb
+        dx = glob.dx
+        nblk = (min(w, w - dx) - max(0, -dx) + 63) // 64
+        sig = sig[:2 * h * nblk].reshape(2, h, nblk)
+        return (sig[0], sig[1]), glob.as_tuple(), [bands[i].as_tuple() for i in range(nb)]
+
+    def band_plan(self, w, h, radius, band):
+        """How the band launches run for a w x h pair at `radius` and band height `band` (twflow_debug.h: tw_debug_band_plan), a
+        pure host function."""
+        v = (C.c_int * 9)()
+        if self._L.tw_debug_band_plan(int(w), int(h), int(radius), int(band), v, 9) != 9:
+            raise ValueError("no band plan for %dx%d at radius %d, band %d" % (w, h, radius, band))
+        return BandPlan(v[0], v[1], bool(v[2]), *v[3:9])
 
     def shift_plan(self, w, h, radius):
         """How tw_shift_search runs for a w x h pair at `radius` (twflow_debug.h: tw_debug_shift_plan), a pure host function."""

@@ -14,6 +14,8 @@
 //                                            " shift <x>,<y> applied=<0|1>"
 //     O <dir> <tol>                          diff images for the whole run (ConsumerShared::overlayDir, ::overlayTol); the response
 //                                            of a pair that got one then ends in " overlay <path>"
+//     B <rows>                               shift bands for the whole run (ConsumerShared::shiftBands); a response then ends in
+//                                            " bands <count>: [y,rows dy=<dy> applied=<0|1>] ..."
 //     G <gap>                                hit regions for the whole run (ConsumerShared::regions); a response then ends in
 //                                            " regions <count>: [x,y,w,h n=<hits> peak=(x,y,dx,dy)] ... of: <index per vector>"
 #include <stdio.h>
@@ -62,6 +64,10 @@ int main(int argc, char** argv)
         if (op == "O" && i + 2 < argc) {
             shared.overlayDir = argv[++i];
             shared.overlayTol = atoi(argv[++i]);
+            continue;
+        }
+        if (op == "B" && i + 1 < argc) {
+            shared.shiftBands = atoi(argv[++i]);
             continue;
         }
         if (op == "I" && i + 1 < argc) {
@@ -127,6 +133,10 @@ int main(int argc, char** argv)
                     printf(" [%d,%d diff=%d unexplained=%d max=%d,%d]", c.x, c.y, c.n_diff, c.n_unexplained, c.max_diff, c.max_unexplained);
             }
             if (r.hasShift) printf(" shift %d,%d applied=%d", r.shift.x, r.shift.y, r.shift.applied ? 1 : 0);
+            if (r.hasBands) {
+                printf(" bands %zu:", r.bands.size());
+                for (const ShiftBand& b : r.bands) printf(" [%d,%d dy=%d applied=%d]", b.y, b.rows, b.dy, b.applied ? 1 : 0);
+            }
             if (!r.overlay.empty()) printf(" overlay %s", r.overlay.c_str());
             printf("\n");
         }

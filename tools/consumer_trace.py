@@ -174,6 +174,12 @@ def with_overlay(case, directory, tol=16):
     return env, budget, ["O", directory, tol] + list(script)
 
 
+def with_shift_bands(case, radius, rows):
+    """the case with the shift and its bands on for the whole run (the probe's S and B: ConsumerShared::shift, ::shiftBands)"""
+    env, budget, script = case
+    return env, budget, ["S", radius, "B", rows] + list(script)
+
+
 def run_case(exe, case, threads, workdir, batch=4):
     """(responses as printed, the trace's text) of one case; every path under `workdir` or the tree reads <dir> / <root>"""
     env_more, budget, script = case
