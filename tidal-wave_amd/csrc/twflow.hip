@@ -4108,7 +4108,7 @@ struct Submission {
 };
 
 // A batch that cannot be launched (unsupported plan, out of memory) is dropped, not retried by every later submit or
-// wait, so that the engine stays usable; its tickets answer "unknown ticket".
+// wait, so that the engine stays usable; its tickets are unknown from then on (find_ticket).
 void drop_batch(Ctx& c)
 {
     c.release_images();
@@ -4543,16 +4543,104 @@ tw_status submit(tw_engine* e, const Submission& s)
     return b.launch_if_full();
 }
 
-Ctx* find_ctx(tw_engine* e, tw_ticket t, int* idx)
+// The batch context and job index of a ticket that is out and not yet collected; any other ticket is refused.  A call that
+// belongs to an option names the batch's setting of it and what it says of a batch opened with the option off (such a
+// refusal leaves the ticket waitable).
+tw_status find_ticket(tw_engine* e, tw_ticket t, Ctx** ctx, int* idx, int Ctx::*option = nullptr, const char* off = nullptr)
 {
     for (Ctx& c : e->ctx) {
         const int64_t j = t - c.first_ticket;
         if (c.pending > 0 && j >= 0 && j < (int64_t)c.jobs.size() && !c.jobs[j].waited) {
+            if (option && !(c.*option)) {
+                e->err = off;
+                return TW_E_BAD_PARAMETER;
+            }
+            *ctx = &c;
             *idx = (int)j;
-            return &c;
+            return TW_OK;
         }
     }
-    return nullptr;
+    e->err = "unknown ticket";
+    return TW_E_BAD_PARAMETER;
+}
+// ---- what the calls on a ticket share (tw_wait, tw_wait_regions, tw_ticket_*) ------------------------------------------
+// A pair's own error, which every call on its ticket answers once the batch has finished: what libpng refuses while it reads
+// the rows (the reference opens the expected image first: it wins)
+tw_status pair_error(tw_engine* e, const Ctx* c, int j)
+{
+    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
+        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
+        return TW_E_BAD_IMAGE_FORMAT;
+    }
+    return TW_OK;
+}
+// What the calls that leave a ticket waitable share (tw_ticket_changes, _shift, _shift_bands, _hits, _overlay): the ticket's
+// batch is launched if it has to be and waited for, the pair's own errors are answered as tw_wait answers them, and the ticket
+// is NOT consumed (the wait that collects it does the per-batch bookkeeping of the copy streams).
+tw_status ticket_finished(tw_engine* e, Ctx* c, int j)
+{
+    tw_status r;
+    if (!c->launched && (r = flush_ctx(e, *c))) {
+        drop_batch(*c);
+        return r;
+    }
+    const hipError_t herr = hipEventSynchronize(c->ev_done);
+    if (herr != hipSuccess) {
+        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
+        return TW_E_DEVICE;
+    }
+    return pair_error(e, c, j);
+}
+// *recs = the first `want` records of pair j of a finished batch.  The eager copy (`eager`: [cap][HOST_RECS]) holds a pair's
+// first HOST_RECS; more than that is rare and comes in one synchronous copy from the context's own plane (`plane`: [cap][G],
+// untouched until the batch is collected) into `storage`.
+template <typename Rec>
+tw_status pair_records(tw_engine* e, const Ctx* c, int j, const Rec* eager, const Rec* plane, int want, std::vector<Rec>& storage,
+                       const Rec** recs)
+{
+    *recs = eager + (size_t)j * HOST_RECS;
+    if (want <= HOST_RECS) return TW_OK;
+    const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
+    storage.resize(want);
+    *recs = storage.data();
+    return d2h_sync(e, storage.data(), plane + (size_t)j * G, (size_t)want * sizeof(Rec));
+}
+// The ignore rule on a pair's records: one whose point lies inside one of the pair's clipped rectangles is not reported.
+// keep(record, its index among the kept) for every other record, in order; returns how many those are.
+template <typename Rec, typename F>
+int outside_rects(const std::vector<tw_rect>& ign, const Rec* rec, int cnt, F keep)
+{
+    int kept = 0;
+    for (int i = 0; i < cnt; i++) {
+        bool inside = false;
+        for (const tw_rect& r : ign)
+            inside = inside || (rec[i].x >= r.x && rec[i].x < r.x + r.width && rec[i].y >= r.y && rec[i].y < r.y + r.height);
+        if (!inside) keep(rec[i], kept++);
+    }
+    return kept;
+}
+tw_vector to_tw_vector(const ScanRec& r)
+{
+    return {r.x, r.y, r.dx, r.dy};  // (float widened to double, src/consumer.cpp:72-73)
+}
+static_assert(sizeof(BandRec) == sizeof(tw_shift_band) && offsetof(BandRec, y) == offsetof(tw_shift_band, y) &&
+                  offsetof(BandRec, rows) == offsetof(tw_shift_band, rows) && offsetof(BandRec, dy) == offsetof(tw_shift_band, dy) &&
+                  offsetof(BandRec, applied) == offsetof(tw_shift_band, applied) &&
+                  offsetof(BandRec, n_shift) == offsetof(tw_shift_band, n_shift) &&
+                  offsetof(BandRec, n_zero) == offsetof(tw_shift_band, n_zero) &&
+                  offsetof(BandRec, sad_shift) == offsetof(tw_shift_band, sad_shift) &&
+                  offsetof(BandRec, sad_zero) == offsetof(tw_shift_band, sad_zero),
+              "band records go to the caller as bytes");
+// a shift record into the caller's tw_shift, field by field: the caller's padding word stays as it is
+void to_tw_shift(const ShiftRec& s, tw_shift* o)
+{
+    o->dx = s.dx;
+    o->dy = s.dy;
+    o->applied = s.applied;
+    o->n_shift = s.n_shift;
+    o->n_zero = s.n_zero;
+    o->sad_shift = s.sad_shift;
+    o->sad_zero = s.sad_zero;
 }
 
 }  // namespace
@@ -4935,11 +5023,8 @@ tw_status tw_image_keep(tw_engine* e, tw_ticket ticket, int which, tw_image** ou
         return TW_E_BAD_PARAMETER;
     }
     int j = 0;
-    Ctx* c = find_ctx(e, ticket, &j);
-    if (!c) {
-        e->err = "unknown ticket";
-        return TW_E_BAD_PARAMETER;
-    }
+    Ctx* c = nullptr;
+    TW_TRY(find_ticket(e, ticket, &c, &j));
     TW_HIP(e, hipSetDevice(e->device));
     tw_image* known = which == TW_KEEP_EXPECT ? c->jobs[j].res : nullptr;  // (itself resident: the same block once more)
     if (!known) known = c->jobs[j].keep[which];                            // (kept before, its copy not yet queued)
@@ -5174,15 +5259,9 @@ tw_status wait_ticket(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, i
 {
     if (!e) return TW_E_BAD_PARAMETER;
     int j = 0;
-    Ctx* c = find_ctx(e, ticket, &j);
-    if (!c) {
-        e->err = "unknown ticket";
-        return TW_E_BAD_PARAMETER;
-    }
-    if (ro && !c->regions) {
-        e->err = "tw_wait_regions: the ticket's batch was opened with TW_OPT_REGIONS off";
-        return TW_E_BAD_PARAMETER;  // (the ticket stays waitable)
-    }
+    Ctx* c = nullptr;
+    TW_TRY(find_ticket(e, ticket, &c, &j, ro ? &Ctx::regions : nullptr,
+                       "tw_wait_regions: the ticket's batch was opened with TW_OPT_REGIONS off"));
     TW_HIP(e, hipSetDevice(e->device));
     tw_status r;
     if (!c->launched && (r = flush_ctx(e, *c))) {
@@ -5223,11 +5302,7 @@ tw_status wait_ticket(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, i
         e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
         return TW_E_DEVICE;
     }
-    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
-        // what libpng refuses while it reads the rows (the reference opens the expected image first: it wins)
-        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
-        return TW_E_BAD_IMAGE_FORMAT;
-    }
+    TW_TRY(pair_error(e, c, j));
     if (seconds) {
         // device compute time of the batch, shared equally by its pairs (exact for a batch of one)
         float ms = 0.f;
@@ -5237,52 +5312,23 @@ tw_status wait_ticket(tw_engine* e, tw_ticket ticket, tw_vector* out, int cap, i
     if (c->span > 0 && !c->jobs[j].ign.empty()) {
         // a pair with ignore rectangles: a vector whose grid point lies inside one of them is not reported.  All of the
         // pair's records are read and filtered in order; *n counts what is left (with out == NULL as well)
-        const std::vector<tw_rect>& ign = c->jobs[j].ign;
         const int cnt = c->h_count[j];
-        const ScanRec* hr = c->h_rec + (size_t)j * HOST_RECS;
+        const ScanRec* hr = nullptr;
         std::vector<ScanRec> extra;
-        if (cnt > HOST_RECS) {
-            const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
-            extra.resize(cnt);
-            TW_TRY(d2h_sync(e, extra.data(), c->d_rec + (size_t)j * G, (size_t)cnt * sizeof(ScanRec)));
-            hr = extra.data();
-        }
-        int kept = 0;
-        for (int i = 0; i < cnt; i++) {
-            bool inside = false;
-            for (const tw_rect& r : ign)
-                inside = inside || (hr[i].x >= r.x && hr[i].x < r.x + r.width && hr[i].y >= r.y && hr[i].y < r.y + r.height);
-            if (inside) continue;
-            if (out && kept < cap) {
-                out[kept].x = hr[i].x;
-                out[kept].y = hr[i].y;
-                out[kept].dx = hr[i].dx;
-                out[kept].dy = hr[i].dy;
-            }
-            kept++;
-        }
+        TW_TRY(pair_records<ScanRec>(e, c, j, c->h_rec, c->d_rec, cnt, extra, &hr));
+        const int kept = outside_rects(c->jobs[j].ign, hr, cnt, [&](const ScanRec& r, int k) {
+            if (out && k < cap) out[k] = to_tw_vector(r);
+        });
         if (n) *n = kept;
         if (ro) TW_TRY(collect_regions(e, c, j, kept, cap, *ro));
     } else if (c->span > 0) {
         const int cnt = c->h_count[j];
         if (n) *n = cnt;
-        const int want = std::min(cnt, cap);
-        const ScanRec* hr = c->h_rec + (size_t)j * HOST_RECS;
+        const int want = out ? std::min(cnt, cap) : 0;
+        const ScanRec* hr = nullptr;
         std::vector<ScanRec> extra;
-        if (want > HOST_RECS && out) {
-            // rare: more hits than the eager copy holds; the batch context's own record region still has them
-            const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
-            extra.resize(want);
-            TW_TRY(d2h_sync(e, extra.data(), c->d_rec + (size_t)j * G, (size_t)want * sizeof(ScanRec)));
-            hr = extra.data();
-        }
-        if (out)
-            for (int i = 0; i < want; i++) {
-                out[i].x = hr[i].x;
-                out[i].y = hr[i].y;
-                out[i].dx = hr[i].dx;  // float widened to double, src/consumer.cpp:72-73
-                out[i].dy = hr[i].dy;
-            }
+        TW_TRY(pair_records<ScanRec>(e, c, j, c->h_rec, c->d_rec, want, extra, &hr));
+        for (int i = 0; i < want; i++) out[i] = to_tw_vector(hr[i]);
         if (ro) TW_TRY(collect_regions(e, c, j, cnt, cap, *ro));
     } else {
         if (n) *n = 0;
@@ -5308,61 +5354,29 @@ tw_status tw_ticket_changes(tw_engine* e, tw_ticket ticket, tw_change* changes, 
 {
     if (!e) return TW_E_BAD_PARAMETER;
     int j = 0;
-    Ctx* c = find_ctx(e, ticket, &j);
-    if (!c) {
-        e->err = "unknown ticket";
-        return TW_E_BAD_PARAMETER;
-    }
-    if (!c->residual) {
-        e->err = "tw_ticket_changes: the ticket's batch was opened with TW_OPT_RESIDUAL off";
-        return TW_E_BAD_PARAMETER;  // (the ticket stays waitable)
-    }
+    Ctx* c = nullptr;
+    TW_TRY(find_ticket(e, ticket, &c, &j, &Ctx::residual,
+                       "tw_ticket_changes: the ticket's batch was opened with TW_OPT_RESIDUAL off"));
     TW_HIP(e, hipSetDevice(e->device));
-    tw_status r;
-    if (!c->launched && (r = flush_ctx(e, *c))) {
-        drop_batch(*c);
-        return r;
-    }
-    // (the ticket is not consumed: the wait that collects it does the per-batch bookkeeping of the copy streams)
-    const hipError_t herr = hipEventSynchronize(c->ev_done);
-    if (herr != hipSuccess) {
-        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
-        return TW_E_DEVICE;
-    }
-    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
-        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
-        return TW_E_BAD_IMAGE_FORMAT;
-    }
+    TW_TRY(ticket_finished(e, c, j));
     if (c->span <= 0) {
         if (n_changes) *n_changes = 0;
         return TW_OK;
     }
     const int cnt = c->h_nchg[j];
     const std::vector<tw_rect>& ign = c->jobs[j].ign;
-    // all of the pair's records when rectangles filter them, else what the caller takes; the eager copy holds the first
-    // HOST_RECS, the context's own plane the rest
+    // all of the pair's records when rectangles filter them, else what the caller takes
     const int want = ign.empty() ? std::max(0, std::min(cnt, changes ? change_cap : 0)) : cnt;
-    const ChangeRec* hr = c->h_chg + (size_t)j * HOST_RECS;
+    const ChangeRec* hr = nullptr;
     std::vector<ChangeRec> extra;
-    if (want > HOST_RECS) {
-        const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
-        extra.resize(want);
-        TW_TRY(d2h_sync(e, extra.data(), c->d_chg + (size_t)j * G, (size_t)want * sizeof(ChangeRec)));
-        hr = extra.data();
-    }
-    int kept = 0;
+    TW_TRY(pair_records<ChangeRec>(e, c, j, c->h_chg, c->d_chg, want, extra, &hr));
+    int kept = cnt;
     if (ign.empty()) {
         if (want > 0) memcpy(changes, hr, sizeof(tw_change) * (size_t)want);
-        kept = cnt;
     } else {
-        for (int i = 0; i < cnt; i++) {
-            bool inside = false;
-            for (const tw_rect& q : ign)
-                inside = inside || (hr[i].x >= q.x && hr[i].x < q.x + q.width && hr[i].y >= q.y && hr[i].y < q.y + q.height);
-            if (inside) continue;
-            if (changes && kept < change_cap) memcpy(changes + kept, hr + i, sizeof(tw_change));
-            kept++;
-        }
+        kept = outside_rects(ign, hr, cnt, [&](const ChangeRec& r, int k) {
+            if (changes && k < change_cap) memcpy(changes + k, &r, sizeof(tw_change));
+        });
     }
     if (n_changes) *n_changes = kept;
     return TW_OK;
@@ -5376,39 +5390,11 @@ tw_status tw_ticket_shift(tw_engine* e, tw_ticket ticket, tw_shift* out)
         return TW_E_BAD_PARAMETER;
     }
     int j = 0;
-    Ctx* c = find_ctx(e, ticket, &j);
-    if (!c) {
-        e->err = "unknown ticket";
-        return TW_E_BAD_PARAMETER;
-    }
-    if (!c->shift) {
-        e->err = "tw_ticket_shift: the ticket's batch was opened with TW_OPT_SHIFT off";
-        return TW_E_BAD_PARAMETER;  // (the ticket stays waitable)
-    }
+    Ctx* c = nullptr;
+    TW_TRY(find_ticket(e, ticket, &c, &j, &Ctx::shift, "tw_ticket_shift: the ticket's batch was opened with TW_OPT_SHIFT off"));
     TW_HIP(e, hipSetDevice(e->device));
-    tw_status r;
-    if (!c->launched && (r = flush_ctx(e, *c))) {
-        drop_batch(*c);
-        return r;
-    }
-    // (the ticket is not consumed: the wait that collects it does the per-batch bookkeeping of the copy streams)
-    const hipError_t herr = hipEventSynchronize(c->ev_done);
-    if (herr != hipSuccess) {
-        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
-        return TW_E_DEVICE;
-    }
-    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
-        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
-        return TW_E_BAD_IMAGE_FORMAT;
-    }
-    const ShiftRec& s = c->h_shift[j];
-    out->dx = s.dx;
-    out->dy = s.dy;
-    out->applied = s.applied;
-    out->n_shift = s.n_shift;
-    out->n_zero = s.n_zero;
-    out->sad_shift = s.sad_shift;
-    out->sad_zero = s.sad_zero;
+    TW_TRY(ticket_finished(e, c, j));
+    to_tw_shift(c->h_shift[j], out);
     return TW_OK;
 }
 
@@ -5420,43 +5406,13 @@ tw_status tw_ticket_shift_bands(tw_engine* e, tw_ticket ticket, tw_shift_band* o
         return TW_E_BAD_PARAMETER;
     }
     int j = 0;
-    Ctx* c = find_ctx(e, ticket, &j);
-    if (!c) {
-        e->err = "unknown ticket";
-        return TW_E_BAD_PARAMETER;
-    }
-    if (!c->bands) {
-        e->err = "tw_ticket_shift_bands: the ticket's batch was opened without TW_OPT_SHIFT_BANDS and TW_OPT_SHIFT on";
-        return TW_E_BAD_PARAMETER;  // (the ticket stays waitable)
-    }
+    Ctx* c = nullptr;
+    TW_TRY(find_ticket(e, ticket, &c, &j, &Ctx::bands,
+                       "tw_ticket_shift_bands: the ticket's batch was opened without TW_OPT_SHIFT_BANDS and TW_OPT_SHIFT on"));
     TW_HIP(e, hipSetDevice(e->device));
-    tw_status r;
-    if (!c->launched && (r = flush_ctx(e, *c))) {
-        drop_batch(*c);
-        return r;
-    }
-    // (as tw_ticket_shift: the ticket is not consumed)
-    const hipError_t herr = hipEventSynchronize(c->ev_done);
-    if (herr != hipSuccess) {
-        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
-        return TW_E_DEVICE;
-    }
-    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
-        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
-        return TW_E_BAD_IMAGE_FORMAT;
-    }
+    TW_TRY(ticket_finished(e, c, j));
     const int nb = c->nbands();
-    const BandRec* s = c->h_bands + (size_t)j * nb;
-    for (int b = 0; b < std::min(nb, cap); b++) {
-        out[b].y = s[b].y;
-        out[b].rows = s[b].rows;
-        out[b].dy = s[b].dy;
-        out[b].applied = s[b].applied;
-        out[b].n_shift = s[b].n_shift;
-        out[b].n_zero = s[b].n_zero;
-        out[b].sad_shift = s[b].sad_shift;
-        out[b].sad_zero = s[b].sad_zero;
-    }
+    if (std::min(nb, cap) > 0) memcpy(out, c->h_bands + (size_t)j * nb, sizeof(BandRec) * (size_t)std::min(nb, cap));
     *n = nb;
     return TW_OK;
 }
@@ -5577,39 +5533,14 @@ tw_status check_overlay_out(tw_engine* e, const void* data, ptrdiff_t pitch, int
     *kind = 0;
     return TW_OK;
 }
-
-// What tw_ticket_hits and tw_ticket_overlay share with tw_ticket_changes: the ticket's batch is launched if it has to be and
-// waited for, the pair's own errors are answered as tw_wait answers them, and the ticket is NOT consumed (the wait that
-// collects it does the per-batch bookkeeping of the copy streams).
-tw_status ticket_finished(tw_engine* e, Ctx* c, int j)
-{
-    tw_status r;
-    if (!c->launched && (r = flush_ctx(e, *c))) {
-        drop_batch(*c);
-        return r;
-    }
-    const hipError_t herr = hipEventSynchronize(c->ev_done);
-    if (herr != hipSuccess) {
-        e->err = std::string("hipEventSynchronize: ") + hipGetErrorString(herr);
-        return TW_E_DEVICE;
-    }
-    if (c->any_plte && (c->h_pflag[2 * j] || c->h_pflag[2 * j + 1])) {
-        e->err = std::string("bad palette index in the ") + (c->h_pflag[2 * j] ? "expected" : "target") + " image";
-        return TW_E_BAD_IMAGE_FORMAT;
-    }
-    return TW_OK;
-}
 }  // namespace
 
 tw_status tw_ticket_hits(tw_engine* e, tw_ticket ticket, int* n)
 {
     if (!e || !n) return TW_E_BAD_PARAMETER;
     int j = 0;
-    Ctx* c = find_ctx(e, ticket, &j);
-    if (!c) {
-        e->err = "unknown ticket";
-        return TW_E_BAD_PARAMETER;
-    }
+    Ctx* c = nullptr;
+    TW_TRY(find_ticket(e, ticket, &c, &j));
     TW_HIP(e, hipSetDevice(e->device));
     TW_TRY(ticket_finished(e, c, j));
     if (c->span <= 0) {
@@ -5622,23 +5553,11 @@ tw_status tw_ticket_hits(tw_engine* e, tw_ticket ticket, int* n)
         *n = cnt;
         return TW_OK;
     }
-    // as tw_wait counts a pair with rectangles: all of its records, the eager copy's or the context's own plane's
-    const ScanRec* hr = c->h_rec + (size_t)j * HOST_RECS;
+    // as tw_wait counts a pair with rectangles: over all of its records
+    const ScanRec* hr = nullptr;
     std::vector<ScanRec> extra;
-    if (cnt > HOST_RECS) {
-        const size_t G = (size_t)tw_grid_capacity(c->w, c->h, c->span);
-        extra.resize(cnt);
-        TW_TRY(d2h_sync(e, extra.data(), c->d_rec + (size_t)j * G, (size_t)cnt * sizeof(ScanRec)));
-        hr = extra.data();
-    }
-    int kept = 0;
-    for (int i = 0; i < cnt; i++) {
-        bool inside = false;
-        for (const tw_rect& r : ign)
-            inside = inside || (hr[i].x >= r.x && hr[i].x < r.x + r.width && hr[i].y >= r.y && hr[i].y < r.y + r.height);
-        kept += inside ? 0 : 1;
-    }
-    *n = kept;
+    TW_TRY(pair_records<ScanRec>(e, c, j, c->h_rec, c->d_rec, cnt, extra, &hr));
+    *n = outside_rects(ign, hr, cnt, [](const ScanRec&, int) {});
     return TW_OK;
 }
 
@@ -5650,11 +5569,8 @@ tw_status tw_ticket_overlay(tw_engine* e, tw_ticket ticket, int tol, const tw_ov
         return TW_E_BAD_PARAMETER;
     }
     int j = 0;
-    Ctx* c = find_ctx(e, ticket, &j);
-    if (!c) {
-        e->err = "unknown ticket";
-        return TW_E_BAD_PARAMETER;
-    }
+    Ctx* c = nullptr;
+    TW_TRY(find_ticket(e, ticket, &c, &j));
     TW_HIP(e, hipSetDevice(e->device));
     const int w = c->w, h = c->h;
     int kind = 0;
@@ -6560,6 +6476,55 @@ tw_status stage_flow_ups(tw_engine* e, Tmp& t, const float* prev2, int pw, int p
     *ups = FlowUps{d_p, pw, ph, pld, pps, d_xo, d_yo, d_al, d_be, u.xmax, (float)(1. / e->cfg.p.pyrScale)};
     return TW_OK;
 }
+// The shift stage entry points give every output the pair's share and one more behind it, set to 0xff, which no launch may
+// touch: is the share at p still that?
+bool still_ff(const void* p, size_t bytes)
+{
+    for (size_t i = 0; i < bytes; i++)
+        if (((const unsigned char*)p)[i] != 0xff) return false;
+    return true;
+}
+// What tw_stage_shift and tw_stage_shift_bands start with, and what it leaves on the host.
+struct ShiftStage {
+    Tmp t;
+    size_t P = 0;                 // a pair's profile words: 2 (w + h)
+    std::vector<unsigned> hprof;  // [2][P]: the pair's share, the guard share
+    ShiftRec hrec[2];             // likewise
+};
+// Both images as they are, rows `stride` apart (the last row ends at its last pixel), each at a 256-byte boundary, behind their
+// pointer table; the guarded profiles and records; launch_shift_estimate and then behind(stream, table, records) — the
+// caller's further launches — under one scope; the profiles and the records read back.
+template <typename F>
+tw_status run_shift_stage(tw_engine* e, ShiftStage& s, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h,
+                          int radius, int force_global, F behind)
+{
+    const size_t ibytes = (size_t)(h - 1) * (size_t)stride + (size_t)w, slot = (ibytes + 255) / 256 * 256;
+    const size_t P = s.P = 2 * ((size_t)w + h);
+    uint8_t* d_img = s.t.alloc<uint8_t>(2 * slot);
+    const uint8_t** d_ptrs = s.t.alloc<const uint8_t*>(2);
+    unsigned* d_prof = s.t.alloc<unsigned>(2 * P);
+    ShiftRec* d_rec = s.t.alloc<ShiftRec>(2);
+    if (!d_img || !d_ptrs || !d_prof || !d_rec) return TW_E_NOMEM;
+    TW_TRY(h2d_sync(e, d_img, expect, ibytes));
+    TW_TRY(h2d_sync(e, d_img + slot, target, ibytes));
+    const uint8_t* hp[2] = {d_img, d_img + slot};
+    TW_TRY(h2d_sync(e, (void*)d_ptrs, hp, sizeof(hp)));
+    hipStream_t st = e->stream;
+    TW_HIP(e, hipMemsetAsync(d_prof, 0xff, 2 * P * sizeof(unsigned), st));
+    TW_HIP(e, hipMemsetAsync(d_rec, 0xff, 2 * sizeof(ShiftRec), st));
+    {
+        // (tw_prof_select(TW_K_SCAN): these launches alone, for measurements)
+        ProfScope pscope(e, st, TW_K_SCAN, 0);
+        TW_TRY(launch_shift_estimate(e, st, d_ptrs, (long long)stride, stride % 4 == 0 ? 1 : 0, w, h, radius, force_global != 0,
+                                     d_prof, d_rec, nullptr, 1));
+        TW_TRY(behind(st, d_ptrs, d_rec));
+    }
+    TW_HIP(e, hipGetLastError());
+    TW_HIP(e, hipStreamSynchronize(st));
+    s.hprof.resize(2 * P);
+    TW_TRY(d2h_sync(e, s.hprof.data(), d_prof, 2 * P * sizeof(unsigned)));
+    return d2h_sync(e, s.hrec, d_rec, sizeof(s.hrec));
+}
 }  // namespace
 
 extern "C" {
@@ -7239,53 +7204,19 @@ tw_status tw_stage_shift(tw_engine* e, const uint8_t* expect, const uint8_t* tar
     if ((r = check_dims(e, w, h))) return r;
     if (stride < w) return TW_E_BAD_PARAMETER;
     TW_HIP(e, hipSetDevice(e->device));
-    // both images as they are, rows `stride` apart (the last row ends at its last pixel), each at a 256-byte boundary
-    const size_t ibytes = (size_t)(h - 1) * (size_t)stride + (size_t)w, slot = (ibytes + 255) / 256 * 256;
-    const size_t P = 2 * ((size_t)w + h);
-    Tmp t;
-    uint8_t* d_img = t.alloc<uint8_t>(2 * slot);
-    const uint8_t** d_ptrs = t.alloc<const uint8_t*>(2);
-    // the pair's share and one more behind it, which no launch may touch
-    unsigned* d_prof = t.alloc<unsigned>(2 * P);
-    ShiftRec* d_rec = t.alloc<ShiftRec>(2);
-    if (!d_img || !d_ptrs || !d_prof || !d_rec) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_img, expect, ibytes));
-    TW_TRY(h2d_sync(e, d_img + slot, target, ibytes));
-    const uint8_t* hp[2] = {d_img, d_img + slot};
-    TW_TRY(h2d_sync(e, (void*)d_ptrs, hp, sizeof(hp)));
-    hipStream_t st = e->stream;
-    TW_HIP(e, hipMemsetAsync(d_prof, 0xff, 2 * P * sizeof(unsigned), st));
-    TW_HIP(e, hipMemsetAsync(d_rec, 0xff, 2 * sizeof(ShiftRec), st));
-    {
-        // (tw_prof_select(TW_K_SCAN): these launches alone, for measurements)
-        ProfScope pscope(e, st, TW_K_SCAN, 0);
-        TW_TRY(launch_shift_estimate(e, st, d_ptrs, (long long)stride, stride % 4 == 0 ? 1 : 0, w, h, radius, force_global != 0,
-                                     d_prof, d_rec, nullptr, 1));
+    ShiftStage stage;
+    TW_TRY(run_shift_stage(e, stage, expect, target, stride, w, h, radius, force_global,
+                           [](hipStream_t, const uint8_t**, ShiftRec*) { return TW_OK; }));
+    if (!still_ff(stage.hprof.data() + stage.P, stage.P * sizeof(unsigned))) {
+        e->err = "tw_stage_shift: a launch wrote beyond the pair's profiles";
+        return TW_E_DEVICE;
     }
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    std::vector<unsigned> hprof(2 * P);
-    ShiftRec hrec[2];
-    TW_TRY(d2h_sync(e, hprof.data(), d_prof, 2 * P * sizeof(unsigned)));
-    TW_TRY(d2h_sync(e, hrec, d_rec, sizeof(hrec)));
-    for (size_t i = P; i < 2 * P; i++)
-        if (hprof[i] != 0xffffffffu) {
-            e->err = "tw_stage_shift: a launch wrote beyond the pair's profiles";
-            return TW_E_DEVICE;
-        }
-    for (size_t i = 0; i < sizeof(ShiftRec); i++)
-        if (((const unsigned char*)&hrec[1])[i] != 0xff) {
-            e->err = "tw_stage_shift: a launch wrote beyond the pair's record";
-            return TW_E_DEVICE;
-        }
-    if (profiles) memcpy(profiles, hprof.data(), P * sizeof(unsigned));
-    out->dx = hrec[0].dx;
-    out->dy = hrec[0].dy;
-    out->applied = hrec[0].applied;
-    out->n_shift = hrec[0].n_shift;
-    out->n_zero = hrec[0].n_zero;
-    out->sad_shift = hrec[0].sad_shift;
-    out->sad_zero = hrec[0].sad_zero;
+    if (!still_ff(&stage.hrec[1], sizeof(ShiftRec))) {
+        e->err = "tw_stage_shift: a launch wrote beyond the pair's record";
+        return TW_E_DEVICE;
+    }
+    if (profiles) memcpy(profiles, stage.hprof.data(), stage.P * sizeof(unsigned));
+    to_tw_shift(stage.hrec[0], out);
     return TW_OK;
 }
 
@@ -7298,58 +7229,32 @@ tw_status tw_stage_shift_bands(tw_engine* e, const uint8_t* expect, const uint8_
     if ((r = check_dims(e, w, h))) return r;
     if (stride < w) return TW_E_BAD_PARAMETER;
     TW_HIP(e, hipSetDevice(e->device));
-    // as tw_stage_shift: both images as they are, each at a 256-byte boundary
-    const size_t ibytes = (size_t)(h - 1) * (size_t)stride + (size_t)w, slot = (ibytes + 255) / 256 * 256;
-    const size_t P = 2 * ((size_t)w + h);
     const int nb = band_count(h, band), nblk0 = band_blocks(w);
     const size_t S = 2 * (size_t)h * nblk0;
-    Tmp t;
-    uint8_t* d_img = t.alloc<uint8_t>(2 * slot);
-    const uint8_t** d_ptrs = t.alloc<const uint8_t*>(2);
-    // the pair's share of each output and one more behind it, which no launch may touch
-    unsigned* d_prof = t.alloc<unsigned>(2 * P);
-    ShiftRec* d_rec = t.alloc<ShiftRec>(2);
-    unsigned short* d_sig = t.alloc<unsigned short>(2 * S);
-    BandRec* d_bands = t.alloc<BandRec>(2 * (size_t)nb);
-    if (!d_img || !d_ptrs || !d_prof || !d_rec || !d_sig || !d_bands) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_img, expect, ibytes));
-    TW_TRY(h2d_sync(e, d_img + slot, target, ibytes));
-    const uint8_t* hp[2] = {d_img, d_img + slot};
-    TW_TRY(h2d_sync(e, (void*)d_ptrs, hp, sizeof(hp)));
-    hipStream_t st = e->stream;
-    TW_HIP(e, hipMemsetAsync(d_prof, 0xff, 2 * P * sizeof(unsigned), st));
-    TW_HIP(e, hipMemsetAsync(d_rec, 0xff, 2 * sizeof(ShiftRec), st));
-    TW_HIP(e, hipMemsetAsync(d_sig, 0xff, 2 * S * sizeof(unsigned short), st));
-    TW_HIP(e, hipMemsetAsync(d_bands, 0xff, 2 * (size_t)nb * sizeof(BandRec), st));
-    {
-        // (tw_prof_select(TW_K_SCAN): these launches alone, for measurements)
-        ProfScope pscope(e, st, TW_K_SCAN, 0);
-        TW_TRY(launch_shift_estimate(e, st, d_ptrs, (long long)stride, stride % 4 == 0 ? 1 : 0, w, h, radius, force_global != 0,
-                                     d_prof, d_rec, nullptr, 1));
-        TW_TRY(launch_band_estimate(e, st, d_ptrs, (long long)stride, w, h, radius, band, force_global != 0, d_rec, d_sig, d_bands,
-                                    nullptr, 1));
-    }
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    std::vector<unsigned> hprof(2 * P);
+    // the signatures and the band records are guarded as the profiles and the pair's record are
+    ShiftStage stage;
+    unsigned short* d_sig = stage.t.alloc<unsigned short>(2 * S);
+    BandRec* d_bands = stage.t.alloc<BandRec>(2 * (size_t)nb);
+    if (!d_sig || !d_bands) return TW_E_NOMEM;
+    TW_HIP(e, hipMemsetAsync(d_sig, 0xff, 2 * S * sizeof(unsigned short), e->stream));
+    TW_HIP(e, hipMemsetAsync(d_bands, 0xff, 2 * (size_t)nb * sizeof(BandRec), e->stream));
+    TW_TRY(run_shift_stage(e, stage, expect, target, stride, w, h, radius, force_global,
+                           [&](hipStream_t st, const uint8_t** d_ptrs, ShiftRec* d_rec) {
+                               return launch_band_estimate(e, st, d_ptrs, (long long)stride, w, h, radius, band, force_global != 0,
+                                                           d_rec, d_sig, d_bands, nullptr, 1);
+                           }));
     std::vector<unsigned short> hsig(2 * S);
     std::vector<BandRec> hb(2 * (size_t)nb);
-    ShiftRec hrec[2];
-    TW_TRY(d2h_sync(e, hprof.data(), d_prof, 2 * P * sizeof(unsigned)));
-    TW_TRY(d2h_sync(e, hrec, d_rec, sizeof(hrec)));
     TW_TRY(d2h_sync(e, hsig.data(), d_sig, 2 * S * sizeof(unsigned short)));
     TW_TRY(d2h_sync(e, hb.data(), d_bands, 2 * (size_t)nb * sizeof(BandRec)));
-    bool clean = true;
-    for (size_t i = P; i < 2 * P; i++) clean = clean && hprof[i] == 0xffffffffu;
-    for (size_t i = S; i < 2 * S; i++) clean = clean && hsig[i] == 0xffffu;
-    for (size_t i = 0; i < sizeof(ShiftRec); i++) clean = clean && ((const unsigned char*)&hrec[1])[i] == 0xff;
-    for (size_t i = 0; i < (size_t)nb * sizeof(BandRec); i++) clean = clean && ((const unsigned char*)&hb[nb])[i] == 0xff;
-    if (!clean) {
+    if (!still_ff(stage.hprof.data() + stage.P, stage.P * sizeof(unsigned)) ||
+        !still_ff(hsig.data() + S, S * sizeof(unsigned short)) || !still_ff(&stage.hrec[1], sizeof(ShiftRec)) ||
+        !still_ff(&hb[nb], (size_t)nb * sizeof(BandRec))) {
         e->err = "tw_stage_shift_bands: a launch wrote beyond the pair's share";
         return TW_E_DEVICE;
     }
     // the signatures' rows are nblk apart in each image's share of h * nblk0; behind them the share is zero
-    const int dx = hrec[0].dx, nblk = (std::min(w, w - dx) - std::max(0, -dx) + 63) / 64;
+    const int dx = stage.hrec[0].dx, nblk = (std::min(w, w - dx) - std::max(0, -dx) + 63) / 64;
     for (int q = 0; q < 2; q++) {
         const unsigned short* s = hsig.data() + (size_t)q * h * nblk0;
         for (size_t i = (size_t)h * nblk; i < (size_t)h * nblk0; i++)
@@ -7359,14 +7264,7 @@ tw_status tw_stage_shift_bands(tw_engine* e, const uint8_t* expect, const uint8_
             }
         if (sig) memcpy(sig + (size_t)q * h * nblk, s, (size_t)h * nblk * sizeof(unsigned short));
     }
-    global->dx = hrec[0].dx;
-    global->dy = hrec[0].dy;
-    global->applied = hrec[0].applied;
-    global->n_shift = hrec[0].n_shift;
-    global->n_zero = hrec[0].n_zero;
-    global->sad_shift = hrec[0].sad_shift;
-    global->sad_zero = hrec[0].sad_zero;
-    static_assert(sizeof(BandRec) == sizeof(tw_shift_band), "copied as bytes");
+    to_tw_shift(stage.hrec[0], global);
     memcpy(bands, hb.data(), (size_t)nb * sizeof(BandRec));
     *n_bands = nb;
     return TW_OK;

@@ -4494,6 +4494,36 @@ __device__ __forceinline__ float area_fast_sum(int area, F S)
     for (; k < area; k++) sum = sum + S(k);
     return sum;
 }
+// One channel's value at (x, y) of the coarsest level, by the mode's rule above and convertTo(scale); S(sy, sx) = the source
+// field's element in row sy, column sx.  tw_flow_area_init's direct path (S reads the pair's field) and the two seeding
+// kernels (S is the field a shift stands for) share it, so a seeded pair gets what the explicit field would give, bit for bit.
+template <typename F>
+__device__ __forceinline__ float area_init_value(const AreaInitArgs& a, int x, int y, F S)
+{
+    float t;
+    if (a.mode == 0) {
+        t = S(y, x);
+    } else if (a.mode == 1) {
+        const long long sy0 = (long long)y * a.iy, sx0 = (long long)x * a.ix;
+        const int ix = a.ix;
+        t = area_fast_sum(ix * a.iy, [&](int k) { const int r = k / ix; return S(sy0 + r, sx0 + (k - r * ix)); });
+        t = t * a.inv_area;
+    } else {
+        t = 0.f;
+        const int j0 = a.ystart[y], j1 = a.ystart[y + 1], k0 = a.xstart[x], k1 = a.xstart[x + 1];
+        for (int j = j0; j < j1; j++) {
+            const int sy = a.ysi[j];
+            float b = 0.f;
+            for (int k = k0; k < k1; k++) {
+                const float m = S(sy, a.xsi[k]) * a.xalpha[k];
+                b = b + m;
+            }
+            const float bb = a.ybeta[j] * b;
+            t = j == j0 ? bb : t + bb;
+        }
+    }
+    return area_scale(a, t);
+}
 
 __global__ __launch_bounds__(256) void tw_flow_area_init(AreaInitArgs a)
 {
@@ -4560,31 +4590,8 @@ __global__ __launch_bounds__(256) void tw_flow_area_init(AreaInitArgs a)
     float v[2] = {0.f, 0.f};
     if (d.p) {
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
-            float s;
-            if (a.mode == 0) {
-                s = area_src(d, a.h0, y, x, c);
-            } else if (a.mode == 1) {
-                const long long sy0 = (long long)y * a.iy, sx0 = (long long)x * a.ix;
-                const int ix = a.ix;
-                s = area_fast_sum(ix * a.iy, [&](int k) { const int r = k / ix; return area_src(d, a.h0, sy0 + r, sx0 + (k - r * ix), c); });
-                s = s * a.inv_area;
-            } else {
-                s = 0.f;
-                const int j0 = a.ystart[y], j1 = a.ystart[y + 1], k0 = a.xstart[x], k1 = a.xstart[x + 1];
-                for (int j = j0; j < j1; j++) {
-                    const int sy = a.ysi[j];
-                    float b = 0.f;
-                    for (int k = k0; k < k1; k++) {
-                        const float t = area_src(d, a.h0, sy, a.xsi[k], c) * a.xalpha[k];
-                        b = b + t;
-                    }
-                    const float bb = a.ybeta[j] * b;
-                    s = j == j0 ? bb : s + bb;
-                }
-            }
-            v[c] = area_scale(a, s);
-        }
+        for (int c = 0; c < 2; c++)
+            v[c] = area_init_value(a, x, y, [&](long long sy, long long sx) { return area_src(d, a.h0, sy, sx, c); });
     }
     out[(long long)y * a.ld + x] = v[0];
     out[a.fps + (long long)y * a.ld + x] = v[1];
@@ -5661,14 +5668,15 @@ __global__ __launch_bounds__(1024) void tw_change_scan(ChangeScanArgs a)
 //     wave, one integer atomic per wave and row; column sums: registers over the band, one integer atomic per column and band.
 //     The profiles are zero when the launch starts (the host sets them in stream order).
 //   tw_shift_search : one 1024-thread workgroup per pair and axis.  A wave owns every 16th candidate of the visit order
-//     0, -1, +1, -2, ...; its lanes stride the overlap, and the 64-bit cost is reduced across the wave.  The winner is the
-//     candidate with the least cost / n (cross-multiplied in 64 bits), the earliest in visit order among equals — what
-//     replacing on strict improvement in visit order gives, in any order of evaluation.  Profiles in LDS when the host says
-//     they fit (ShiftSearchArgs::lds), else read from memory.
-//   tw_shift_verify<0> : bands of SV_ROWS rows; the sums of |E - T| at (0, 0) and over the overlap at (dx, dy), reduced per
-//     workgroup, one 64-bit integer atomic each.  tw_shift_verify<1> : one thread per pair, behind it: areas and `applied`.
-//   tw_flow_shift_init : the coarsest level's first flow of the pairs whose shift was applied — tw_flow_area_init's own
-//     arithmetic on the constant field ((float)dx, (float)dy), which in float is not a constant in general.
+//     0, -1, +1, -2, ...; its lanes stride the overlap, and the 64-bit cost is reduced across the wave (wave_sum64).  The
+//     winner (ShiftBest, shift_pick) is the candidate with the least cost / n (cross-multiplied in 64 bits), the earliest in
+//     visit order among equals — what replacing on strict improvement in visit order gives, in any order of evaluation.
+//     Profiles in LDS when the host says they fit (ShiftSearchArgs::lds), else read from memory.
+//   tw_shift_verify<0> : bands of SV_ROWS rows through shift_row_sad at the pair's (dx, dy).  tw_shift_verify<1> : one thread
+//     per pair, behind it: areas and `applied` (shift_applied: the shift must halve the mean absolute difference).
+//   tw_flow_shift_init : the coarsest level's first flow of the pairs whose shift was applied — area_init_value on the
+//     constant field ((float)dx, (float)dy), which in float is not a constant in general.
+// The band kernels below use the same pieces: wave_sum64, ShiftBest / shift_pick, shift_row_sad, shift_applied.
 // =====================================================================================================
 struct ShiftRec {  // = tw_shift (`work` is its padding word)
     int dx, dy, applied, n_shift, n_zero;
@@ -5677,6 +5685,116 @@ struct ShiftRec {  // = tw_shift (`work` is its padding word)
 };
 constexpr int SP_ROWS = 64, SV_ROWS = 16;
 constexpr int SS_LDS_BYTES = 48 * 1024;  // tw_shift_search keeps both profiles of an axis in LDS up to here
+
+// v of lane ^ off (a 64-bit value crosses lanes as two halves), and the sum of v over the wave's 64 lanes, in every lane
+__device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, int off)
+{
+    return ((unsigned long long)__shfl_xor((unsigned)(v >> 32), off) << 32) | __shfl_xor((unsigned)v, off);
+}
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+    for (int off = 32; off >= 1; off >>= 1) v += shfl_xor64(v, off);
+    return v;
+}
+// candidate k of the visit order 0, -1, +1, -2, +2, ...
+__device__ __forceinline__ int shift_cand(int k) { return (k & 1) ? -((k + 1) >> 1) : (k >> 1); }
+// is (ca, na, ka) in front of (cb, nb, kb): a smaller cost per element, or the same and earlier in visit order
+__device__ __forceinline__ bool shift_better(unsigned long long ca, int na, int ka, unsigned long long cb, int nb, int kb)
+{
+    const unsigned long long l = ca * (unsigned long long)nb, r = cb * (unsigned long long)na;
+    return l < r || (l == r && ka < kb);
+}
+// A search's running best: cost c of candidate k over n elements (k < 0: none yet).  Wave-uniform in the candidate loop,
+// where every lane holds the reduced cost.
+struct ShiftBest {
+    unsigned long long c = 0;
+    int k = -1, n = 0;
+    __device__ __forceinline__ void take(unsigned long long c2, int k2, int n2)
+    {
+        if (k < 0 || shift_better(c2, n2, k2, c, n, k)) {
+            c = c2;
+            k = k2;
+            n = n2;
+        }
+    }
+};
+// The winner among the bests of a 1024-thread workgroup's 16 waves, in thread 0 (the other threads get -1).  Wave 0 owns
+// candidate 0, which no search skips, so its slot always holds a candidate.
+__device__ __forceinline__ int shift_pick(const ShiftBest& mine)
+{
+    __shared__ unsigned long long sp_cost[16];
+    __shared__ int sp_k[16], sp_n[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        sp_cost[wave] = mine.c;
+        sp_k[wave] = mine.k;
+        sp_n[wave] = mine.n;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return -1;
+    ShiftBest b = {sp_cost[0], sp_k[0], sp_n[0]};
+    for (int v = 1; v < 16; v++) {
+        const int k = sp_k[v];  // (< 0: the wave had no candidate)
+        if (k >= 0 && shift_better(sp_cost[v], sp_n[v], k, b.c, b.n, b.k)) b = {sp_cost[v], k, sp_n[v]};
+    }
+    return b.k;
+}
+// Rows [y_begin, y_end) of a pair in one 256-thread workgroup, a wave per row: the sums of |E - T| at (0, 0) over the whole
+// rows and at (dx, dy) over the overlap, reduced per wave, then over the four waves in LDS; one 64-bit integer atomic each
+// (none for a sum of zero: the destinations are zero when the launch starts).
+__device__ __forceinline__ void shift_row_sad(const uint8_t* __restrict__ E, const uint8_t* __restrict__ T, long long stride, int w,
+                                              int h, int y_begin, int y_end, int dx, int dy, unsigned long long* sad_zero,
+                                              unsigned long long* sad_shift)
+{
+    __shared__ unsigned long long sv_sum[2][4];
+    const bool moved = dx != 0 || dy != 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int xa = max(0, -dx), xb = min(w, w - dx);  // the overlap's columns of E
+    unsigned long long s0 = 0, ss = 0;
+    for (int y = y_begin + wave; y < y_end; y += 4) {
+        const uint8_t* __restrict__ er = E + (long long)y * stride;
+        const uint8_t* __restrict__ tr = T + (long long)y * stride;
+        const bool in = moved && y + dy >= 0 && y + dy < h;
+        const uint8_t* __restrict__ ts = T + (long long)(in ? y + dy : y) * stride;
+        unsigned r0 = 0, rs = 0;  // (a row's sums: at most 255 * 32768)
+        for (int x = lane; x < w; x += 64) {
+            const int ev = er[x];
+            r0 += (unsigned)abs(ev - (int)tr[x]);
+            if (in && x >= xa && x < xb) rs += (unsigned)abs(ev - (int)ts[x + dx]);
+        }
+        s0 += r0;
+        ss += rs;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {  // (both sums step by step: the shuffles of one hide behind the other's)
+        s0 += shfl_xor64(s0, off);
+        ss += shfl_xor64(ss, off);
+    }
+    if (lane == 0) {
+        sv_sum[0][wave] = s0;
+        sv_sum[1][wave] = ss;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s0 = (sv_sum[0][0] + sv_sum[0][1]) + (sv_sum[0][2] + sv_sum[0][3]);
+        ss = (sv_sum[1][0] + sv_sum[1][1]) + (sv_sum[1][2] + sv_sum[1][3]);
+        if (s0) atomicAdd(sad_zero, s0);
+        if (ss) atomicAdd(sad_shift, ss);
+    }
+}
+// `applied` of a record whose sums are final: over n0 elements at (0, 0) and ns at the shift, the shift's mean absolute
+// difference is at most 1 / 2^s of the unshifted one (s = 1: the global shift, 2: a band).  A shift of nothing is not applied
+// and reports the unshifted sum; pair p with an initial field of its own (own[p].p non-null; own null: no pair has one)
+// never applies one.
+__device__ __forceinline__ int shift_applied(bool moved, unsigned long long& sad_shift, unsigned long long sad_zero,
+                                             unsigned long long n0, unsigned long long ns, int s, const FlowDst* own, int p)
+{
+    int applied = 0;
+    if (moved) applied = sad_shift * n0 <= (sad_zero >> s) * ns ? 1 : 0;
+    else sad_shift = sad_zero;
+    if (own && own[p].p) applied = 0;
+    return applied;
+}
+
 struct ShiftProfArgs {
     const uint8_t* const* srcs;  // image z: srcs[z] (pair z >> 1)
     long long stride;
@@ -5729,19 +5847,9 @@ struct ShiftSearchArgs {
     int lds[2];            // axis 0 (x: the column profiles), axis 1 (y: the row profiles): both profiles in LDS
     ShiftRec* rec;         // pair p
 };
-// candidate k of the visit order 0, -1, +1, -2, +2, ...
-__device__ __forceinline__ int shift_cand(int k) { return (k & 1) ? -((k + 1) >> 1) : (k >> 1); }
-// is (ca, na, ka) in front of (cb, nb, kb): a smaller cost per element, or the same and earlier in visit order
-__device__ __forceinline__ bool shift_better(unsigned long long ca, int na, int ka, unsigned long long cb, int nb, int kb)
-{
-    const unsigned long long l = ca * (unsigned long long)nb, r = cb * (unsigned long long)na;
-    return l < r || (l == r && ka < kb);
-}
 __global__ __launch_bounds__(1024) void tw_shift_search(ShiftSearchArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned ss_prof[];  // [2][L] when the axis' profiles fit
-    __shared__ unsigned long long ss_cost[16];
-    __shared__ int ss_k[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int axis = blockIdx.x, p = blockIdx.y;
     const int L = axis == 0 ? a.w : a.h;
@@ -5753,8 +5861,7 @@ __global__ __launch_bounds__(1024) void tw_shift_search(ShiftSearchArgs a)
         __syncthreads();
     }
     const int r = min(a.radius, L / 2), ncand = 2 * r + 1;
-    unsigned long long bc = 0;
-    int bk = -1;  // (wave-uniform: every lane holds the reduced cost)
+    ShiftBest best;
     for (int k = wave; k < ncand; k += 16) {
         const int d = shift_cand(k);
         const int lo = max(0, -d), hi = min(L, L - d);
@@ -5770,31 +5877,10 @@ __global__ __launch_bounds__(1024) void tw_shift_search(ShiftSearchArgs a)
                 c += e > t ? e - t : t - e;
             }
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            const unsigned clo = __shfl_xor((unsigned)c, off), chi = __shfl_xor((unsigned)(c >> 32), off);
-            c += ((unsigned long long)chi << 32) | clo;
-        }
-        if (bk < 0 || shift_better(c, L - abs(d), k, bc, L - abs(shift_cand(bk)), bk)) {
-            bc = c;
-            bk = k;
-        }
+        best.take(wave_sum64(c), k, L - abs(d));
     }
-    if (lane == 0) {
-        ss_cost[wave] = bc;
-        ss_k[wave] = bk;
-    }
-    __syncthreads();
+    const int bk = shift_pick(best);
     if (tid == 0) {
-        // (wave 0 owns candidate 0: ss_k[0] >= 0 always)
-        bc = ss_cost[0];
-        bk = ss_k[0];
-        for (int v = 1; v < 16; v++) {
-            const int k = ss_k[v];
-            if (k >= 0 && shift_better(ss_cost[v], L - abs(shift_cand(k)), k, bc, L - abs(shift_cand(bk)), bk)) {
-                bc = ss_cost[v];
-                bk = k;
-            }
-        }
         if (axis == 0) a.rec[p].dx = shift_cand(bk);
         else a.rec[p].dy = shift_cand(bk);
     }
@@ -5816,56 +5902,17 @@ __global__ __launch_bounds__(256) void tw_shift_verify(ShiftVerifyArgs a)
         ShiftRec r = a.rec[p];
         const unsigned long long n0 = (unsigned long long)a.w * (unsigned long long)a.h;
         const unsigned long long ns = (unsigned long long)(a.w - abs(r.dx)) * (unsigned long long)(a.h - abs(r.dy));
-        int applied = 0;
-        if (r.dx != 0 || r.dy != 0) applied = r.sad_shift * n0 <= (r.sad_zero >> 1) * ns ? 1 : 0;
-        else r.sad_shift = r.sad_zero;
-        if (a.own && a.own[p].p) applied = 0;
-        r.applied = applied;
+        r.applied = shift_applied(r.dx != 0 || r.dy != 0, r.sad_shift, r.sad_zero, n0, ns, 1, a.own, p);
         r.n_shift = (int)ns;
         r.n_zero = (int)n0;
         r.work = 0;
         a.rec[p] = r;
         return;
     }
-    __shared__ unsigned long long sv_sum[2][4];
-    const int p = blockIdx.y;
-    const uint8_t* __restrict__ E = a.srcs[2 * p];
-    const uint8_t* __restrict__ T = a.srcs[2 * p + 1];
-    const int dx = a.rec[p].dx, dy = a.rec[p].dy;
-    const bool moved = dx != 0 || dy != 0;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int xa = max(0, -dx), xb = min(a.w, a.w - dx);  // the overlap's columns of E
-    const int y1 = min(a.h, ((int)blockIdx.x + 1) * SV_ROWS);
-    unsigned long long s0 = 0, ss = 0;
-    for (int y = blockIdx.x * SV_ROWS + wave; y < y1; y += 4) {
-        const uint8_t* __restrict__ er = E + (long long)y * a.stride;
-        const uint8_t* __restrict__ tr = T + (long long)y * a.stride;
-        const bool in = moved && y + dy >= 0 && y + dy < a.h;
-        const uint8_t* __restrict__ ts = T + (long long)(in ? y + dy : y) * a.stride;
-        unsigned r0 = 0, rs = 0;  // (a row's sums: at most 255 * 32768)
-        for (int x = lane; x < a.w; x += 64) {
-            const int ev = er[x];
-            r0 += (unsigned)abs(ev - (int)tr[x]);
-            if (in && x >= xa && x < xb) rs += (unsigned)abs(ev - (int)ts[x + dx]);
-        }
-        s0 += r0;
-        ss += rs;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        s0 += ((unsigned long long)__shfl_xor((unsigned)(s0 >> 32), off) << 32) | __shfl_xor((unsigned)s0, off);
-        ss += ((unsigned long long)__shfl_xor((unsigned)(ss >> 32), off) << 32) | __shfl_xor((unsigned)ss, off);
-    }
-    if (lane == 0) {
-        sv_sum[0][wave] = s0;
-        sv_sum[1][wave] = ss;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        s0 = (sv_sum[0][0] + sv_sum[0][1]) + (sv_sum[0][2] + sv_sum[0][3]);
-        ss = (sv_sum[1][0] + sv_sum[1][1]) + (sv_sum[1][2] + sv_sum[1][3]);
-        if (s0) atomicAdd(&a.rec[p].sad_zero, s0);
-        if (ss) atomicAdd(&a.rec[p].sad_shift, ss);
-    }
+    const int p = blockIdx.y, y0 = blockIdx.x * SV_ROWS;
+    ShiftRec* rec = a.rec + p;
+    shift_row_sad(a.srcs[2 * p], a.srcs[2 * p + 1], a.stride, a.w, a.h, y0, min(a.h, y0 + SV_ROWS), rec->dx, rec->dy,
+                  &rec->sad_zero, &rec->sad_shift);
 }
 
 struct ShiftInitArgs {
@@ -5886,26 +5933,7 @@ __global__ __launch_bounds__(256) void tw_flow_shift_init(ShiftInitArgs s)
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             const float f = (float)(c == 0 ? r.dx : r.dy);
-            float t;
-            if (a.mode == 0) {
-                t = f;
-            } else if (a.mode == 1) {
-                t = area_fast_sum(a.ix * a.iy, [&](int) { return f; });
-                t = t * a.inv_area;
-            } else {
-                t = 0.f;
-                const int j0 = a.ystart[y], j1 = a.ystart[y + 1], k0 = a.xstart[x], k1 = a.xstart[x + 1];
-                for (int j = j0; j < j1; j++) {
-                    float b = 0.f;
-                    for (int k = k0; k < k1; k++) {
-                        const float m = f * a.xalpha[k];
-                        b = b + m;
-                    }
-                    const float bb = a.ybeta[j] * b;
-                    t = j == j0 ? bb : t + bb;
-                }
-            }
-            v[c] = area_scale(a, t);
+            v[c] = area_init_value(a, x, y, [&](long long, long long) { return f; });
         }
     }
     out[(long long)y * a.ld + x] = v[0];
@@ -5923,12 +5951,12 @@ __global__ __launch_bounds__(256) void tw_flow_shift_init(ShiftInitArgs s)
 //     the launch writes the whole buffer.
 //   tw_band_search : one 1024-thread workgroup per (pair, band).  A wave owns every 16th candidate of the visit order; with
 //     rows nblk apart a candidate's elements are one contiguous run of both images' signatures, which the lanes stride.  The
-//     winner by shift_better with the candidate's row count.  A skipped candidate (too few rows) takes part in nothing, and the
-//     order among the others is their index in the visit order, so the rule holds.  The band's rows of sigE and the rows of
-//     sigT it can reach are staged in LDS when the host says they fit (BandSearchArgs::lds).
-//   tw_band_verify<0> : chunks of BV_ROWS rows (a chunk lies in one band: B is a multiple of 16); |E - T| at (0, 0) over the
-//     whole rows and at (dx, dy_b) over the overlap, one 64-bit integer atomic each per workgroup.  <1> : one thread per
-//     (pair, band), behind it: areas and `applied`.
+//     winner as tw_shift_search's (ShiftBest, shift_pick), n the candidate's row count.  A skipped candidate (too few rows)
+//     takes part in nothing, and the order among the others is their index in the visit order, so the rule holds.  The band's
+//     rows of sigE and the rows of sigT it can reach are staged in LDS when the host says they fit (BandSearchArgs::lds).
+//   tw_band_verify<0> : chunks of BV_ROWS rows (a chunk lies in one band: B is a multiple of 16) through shift_row_sad at
+//     (dx, dy_b).  <1> : one thread per (pair, band), behind it: areas and `applied` (shift_applied: the shift must quarter
+//     the band's mean absolute difference).
 //   tw_flow_band_init : tw_flow_shift_init with a source value that depends on the source row's band.  A workgroup first
 //     turns the pair's records into the two values per band in LDS; a source row's band is row / B by a multiply with the
 //     host's floor(2^32 / B) + 1 (exact for rows below 2^15 and B up to 2^10).
@@ -5996,8 +6024,6 @@ struct BandSearchArgs {
 __global__ __launch_bounds__(1024) void tw_band_search(BandSearchArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned short bs_sig[];  // [rows_b][nblk] of E, then [t1 - t0][nblk] of T
-    __shared__ unsigned long long bs_cost[16];
-    __shared__ int bs_k[16], bs_n[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x, p = blockIdx.y;
     const int dx = a.rec[p].dx;
@@ -6023,8 +6049,7 @@ __global__ __launch_bounds__(1024) void tw_band_search(BandSearchArgs a)
         sT = bs_sig + ne;
     }
     const int need = (rows + 1) >> 1;
-    unsigned long long bc = 0;
-    int bk = -1, bn = 0;  // (wave-uniform: every lane holds the reduced cost)
+    ShiftBest best;
     for (int k = wave; k < ncand; k += 16) {
         const int d = shift_cand(k);
         const int lo = max(y0, -d), hi = min(y0 + rows, a.h - d), n = hi - lo;
@@ -6037,35 +6062,10 @@ __global__ __launch_bounds__(1024) void tw_band_search(BandSearchArgs a)
             const int e = pe[i], t = pt[i];
             c += (unsigned)abs(e - t);
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            const unsigned clo = __shfl_xor((unsigned)c, off), chi = __shfl_xor((unsigned)(c >> 32), off);
-            c += ((unsigned long long)chi << 32) | clo;
-        }
-        if (bk < 0 || shift_better(c, n, k, bc, bn, bk)) {
-            bc = c;
-            bk = k;
-            bn = n;
-        }
+        best.take(wave_sum64(c), k, n);
     }
-    if (lane == 0) {
-        bs_cost[wave] = bc;
-        bs_k[wave] = bk;
-        bs_n[wave] = bn;
-    }
-    __syncthreads();
+    const int bk = shift_pick(best);
     if (tid == 0) {
-        // (wave 0 owns candidate 0, which is never skipped: bs_k[0] >= 0 always)
-        bc = bs_cost[0];
-        bk = bs_k[0];
-        bn = bs_n[0];
-        for (int v = 1; v < 16; v++) {
-            const int k = bs_k[v];
-            if (k >= 0 && shift_better(bs_cost[v], bs_n[v], k, bc, bn, bk)) {
-                bc = bs_cost[v];
-                bk = k;
-                bn = bs_n[v];
-            }
-        }
         BandRec* __restrict__ o = a.bands + (long long)p * a.nb + b;
         o->y = y0;
         o->rows = rows;
@@ -6092,61 +6092,19 @@ __global__ __launch_bounds__(256) void tw_band_verify(BandVerifyArgs a)
         const int dx = a.rec[p].dx;
         const int lo = max(r.y, -r.dy), hi = min(r.y + r.rows, a.h - r.dy);
         const unsigned long long n0 = (unsigned long long)r.rows * (unsigned long long)a.w;
+        const bool moved = dx != 0 || r.dy != 0;
         unsigned long long ns = n0;
-        int applied = 0;
-        if (dx != 0 || r.dy != 0) {
-            ns = (unsigned long long)(hi - lo) * (unsigned long long)(a.w - abs(dx));
-            applied = r.sad_shift * n0 <= (r.sad_zero >> 2) * ns ? 1 : 0;
-        } else {
-            r.sad_shift = r.sad_zero;
-        }
-        if (a.own && a.own[p].p) applied = 0;
-        r.applied = applied;
+        if (moved) ns = (unsigned long long)(hi - lo) * (unsigned long long)(a.w - abs(dx));
+        r.applied = shift_applied(moved, r.sad_shift, r.sad_zero, n0, ns, 2, a.own, p);
         r.n_shift = (int)ns;
         r.n_zero = (int)n0;
         a.bands[i] = r;
         return;
     }
-    __shared__ unsigned long long bv_sum[2][4];
-    const int p = blockIdx.y;
-    const uint8_t* __restrict__ E = a.srcs[2 * p];
-    const uint8_t* __restrict__ T = a.srcs[2 * p + 1];
-    BandRec* __restrict__ rec = a.bands + (long long)p * a.nb + ((int)blockIdx.x * BV_ROWS) / a.band;
-    const int dx = a.rec[p].dx, dy = rec->dy;
-    const bool moved = dx != 0 || dy != 0;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int xa = max(0, -dx), xb = min(a.w, a.w - dx);  // the overlap's columns of E
-    const int y1 = min(a.h, ((int)blockIdx.x + 1) * BV_ROWS);
-    unsigned long long s0 = 0, ss = 0;
-    for (int y = blockIdx.x * BV_ROWS + wave; y < y1; y += 4) {
-        const uint8_t* __restrict__ er = E + (long long)y * a.stride;
-        const uint8_t* __restrict__ tr = T + (long long)y * a.stride;
-        const bool in = moved && y + dy >= 0 && y + dy < a.h;
-        const uint8_t* __restrict__ ts = T + (long long)(in ? y + dy : y) * a.stride;
-        unsigned r0 = 0, rs = 0;  // (a row's sums: at most 255 * 32768)
-        for (int x = lane; x < a.w; x += 64) {
-            const int ev = er[x];
-            r0 += (unsigned)abs(ev - (int)tr[x]);
-            if (in && x >= xa && x < xb) rs += (unsigned)abs(ev - (int)ts[x + dx]);
-        }
-        s0 += r0;
-        ss += rs;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        s0 += ((unsigned long long)__shfl_xor((unsigned)(s0 >> 32), off) << 32) | __shfl_xor((unsigned)s0, off);
-        ss += ((unsigned long long)__shfl_xor((unsigned)(ss >> 32), off) << 32) | __shfl_xor((unsigned)ss, off);
-    }
-    if (lane == 0) {
-        bv_sum[0][wave] = s0;
-        bv_sum[1][wave] = ss;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        s0 = (bv_sum[0][0] + bv_sum[0][1]) + (bv_sum[0][2] + bv_sum[0][3]);
-        ss = (bv_sum[1][0] + bv_sum[1][1]) + (bv_sum[1][2] + bv_sum[1][3]);
-        if (s0) atomicAdd(&rec->sad_zero, s0);
-        if (ss) atomicAdd(&rec->sad_shift, ss);
-    }
+    const int p = blockIdx.y, y0 = blockIdx.x * BV_ROWS;
+    BandRec* rec = a.bands + (long long)p * a.nb + y0 / a.band;
+    shift_row_sad(a.srcs[2 * p], a.srcs[2 * p + 1], a.stride, a.w, a.h, y0, min(a.h, y0 + BV_ROWS), a.rec[p].dx, rec->dy,
+                  &rec->sad_zero, &rec->sad_shift);
 }
 
 struct BandInitArgs {
@@ -6179,32 +6137,8 @@ __global__ __launch_bounds__(256) void tw_flow_band_init(BandInitArgs s)
     if (seeds) {
         const unsigned magic = s.magic;
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
-            // the explicit field's value in source row sr
-            auto F = [&](int sr) { return bi_val[c][__umulhi((unsigned)sr, magic)]; };
-            float t;
-            if (a.mode == 0) {
-                t = F(y);
-            } else if (a.mode == 1) {
-                const int ix = a.ix, sy0 = y * a.iy;
-                t = area_fast_sum(ix * a.iy, [&](int k) { return F(sy0 + k / ix); });
-                t = t * a.inv_area;
-            } else {
-                t = 0.f;
-                const int j0 = a.ystart[y], j1 = a.ystart[y + 1], k0 = a.xstart[x], k1 = a.xstart[x + 1];
-                for (int j = j0; j < j1; j++) {
-                    const float f = F(a.ysi[j]);
-                    float b = 0.f;
-                    for (int k = k0; k < k1; k++) {
-                        const float m = f * a.xalpha[k];
-                        b = b + m;
-                    }
-                    const float bb = a.ybeta[j] * b;
-                    t = j == j0 ? bb : t + bb;
-                }
-            }
-            v[c] = area_scale(a, t);
-        }
+        for (int c = 0; c < 2; c++)  // (the explicit field's value depends on the source row alone)
+            v[c] = area_init_value(a, x, y, [&](long long sy, long long) { return bi_val[c][__umulhi((unsigned)sy, magic)]; });
     }
     out[(long long)y * a.ld + x] = v[0];
     out[a.fps + (long long)y * a.ld + x] = v[1];
