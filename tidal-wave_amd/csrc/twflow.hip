@@ -2492,6 +2492,63 @@ void launch_scan(tw_engine* e, hipStream_t st, const ScanArgs& a, const ScanChoi
     else
         TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<false>, dim3(npairs), dim3(1024), 0, st, a);
 }
+// The span-grid chain's arguments, filled in one place each: a batch (enqueue_span_gather, enqueue_scan), the stage entry
+// points and tw_bench_stage launch what these three build, so a stage test runs the batch's own arguments.
+// tw_span_gather: npairs fields of two planes in level L's layout, one behind the other at `flow`, sampled every `span`
+// pixels into gw x gh points per pair at `grid`
+void launch_span_gather(tw_engine* e, hipStream_t st, const float* flow, const LevelPlan& L, int span, int gw, int gh, float2* grid,
+                        int npairs)
+{
+    GatherArgs g;
+    g.flow = flow;
+    g.fzs = 2 * L.ps;
+    g.fps = L.ps;
+    g.ld = L.ld;
+    g.span = span;
+    g.gw = gw;
+    g.gh = gh;
+    g.g = grid;
+    TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((gw + 63) / 64, (gh + 3) / 4, npairs), dim3(256), 0, st, g);
+}
+// the scan of those grids: a pair's records lie its whole grid apart; flow, fps and ld are read by tw_span_scan<true> alone
+ScanArgs scan_args(const float2* grid, int span, int gw, int gh, double thr2, int* count, ScanRec* rec, const float* flow, long long fps,
+                   int ld)
+{
+    ScanArgs a;
+    a.g = grid;
+    a.span = span;
+    a.gw = gw;
+    a.gh = gh;
+    a.thr2 = thr2;
+    a.count = count;
+    a.rec_zs = (long long)gw * gh;
+    a.rec = rec;
+    a.flow = flow;
+    a.fps = fps;
+    a.ld = ld;
+    return a;
+}
+// tw_hit_regions behind the scan `a` of w x h images: nrect null when no pair has a rectangle
+RegionArgs region_args(const ScanArgs& a, int w, int h, int gap, const int* nrect, const int4* rects, int* lab, int* n_regions,
+                       RegionRec* regions, int* region_of)
+{
+    RegionArgs ra;
+    ra.g = a.g;
+    ra.span = a.span;
+    ra.gw = a.gw;
+    ra.gh = a.gh;
+    ra.w = w;
+    ra.h = h;
+    ra.gap = gap;
+    ra.thr2 = a.thr2;
+    ra.nrect = nrect;
+    ra.rects = rects;
+    ra.lab = lab;
+    ra.n_regions = n_regions;
+    ra.regions = regions;
+    ra.region_of = region_of;
+    return ra;
+}
 // tw_hit_regions behind a scan of the same pairs: the label plane in LDS when the grid fits, in a.lab otherwise
 tw_status launch_hit_regions(tw_engine* e, hipStream_t st, const RegionArgs& a, int npairs)
 {
@@ -2508,6 +2565,17 @@ tw_status launch_hit_regions(tw_engine* e, hipStream_t st, const RegionArgs& a, 
         TW_LAUNCH(e, TW_DF_HIT_REGIONS, tw_hit_regions<false>, dim3(npairs), dim3(1024), 0, st, a);
     }
     return TW_OK;
+}
+
+// tw_png_unfilter over nimages jobs of a.w x a.h pixels, one workgroup per image.  waves 0: as many waves per image as the
+// 128 KB of LDS row buffers allow for this width; 1, 4 or 16: that many (a.w <= PNG_LDS_PIXELS / waves is the caller's check)
+void launch_png_unfilter(tw_engine* e, hipStream_t st, const PngArgs& a, int nimages, int waves = 0)
+{
+    if (waves == 0) waves = a.w <= PNG_LDS_PIXELS / 16 ? 16 : (a.w <= PNG_LDS_PIXELS / 4 ? 4 : 1);
+    const dim3 grid((unsigned)nimages);
+    if (waves == 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, grid, dim3(1024), 0, st, a);
+    else if (waves == 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, grid, dim3(256), 0, st, a);
+    else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, grid, dim3(64), 0, st, a);
 }
 
 // tw_warp_residual over pairs whose images are srcs[2z], srcs[2z + 1] and whose final level-0 flow lies in `flow`
@@ -2971,10 +3039,7 @@ struct BatchEnqueue {
         pa.jobs = c.d_png;
         pa.w = c.w;
         pa.h = c.h;
-        // waves per image: as many as the 128 KB of LDS row buffers allow for this width
-        if (c.w <= PNG_LDS_PIXELS / 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, dim3(2 * n), dim3(1024), 0, e->copy_stream, pa);
-        else if (c.w <= PNG_LDS_PIXELS / 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, dim3(2 * n), dim3(256), 0, e->copy_stream, pa);
-        else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(2 * n), dim3(64), 0, e->copy_stream, pa);
+        launch_png_unfilter(e, e->copy_stream, pa, 2 * n);
         return enqueue_png_target_resizes();
     }
 
@@ -3071,10 +3136,7 @@ struct BatchEnqueue {
             pa.jobs = c.d_rpng + k0;
             pa.w = jb.tw;
             pa.h = jb.th;
-            const dim3 grid((unsigned)(k1 - k0));
-            if (jb.tw <= PNG_LDS_PIXELS / 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, grid, dim3(1024), 0, e->copy_stream, pa);
-            else if (jb.tw <= PNG_LDS_PIXELS / 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, grid, dim3(256), 0, e->copy_stream, pa);
-            else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, grid, dim3(64), 0, e->copy_stream, pa);
+            launch_png_unfilter(e, e->copy_stream, pa, (int)(k1 - k0));
             k0 = k1;
         }
         launch_resize(e->copy_stream, c.d_rsz + e->cfg.cap, n);
@@ -3319,18 +3381,7 @@ struct BatchEnqueue {
     {
         if (c.span > 0) {
             const LevelPlan& L = pl->lv[0];
-            ScanArgs a;
-            a.g = e->d_grid;
-            a.span = c.span;
-            a.gw = gw;
-            a.gh = gh;
-            a.thr2 = c.threshold * c.threshold;
-            a.count = e->d_count;
-            a.rec_zs = (long long)a.gw * a.gh;
-            a.rec = c.d_rec;
-            a.flow = e->flow[0];
-            a.fps = L.ps;
-            a.ld = L.ld;
+            const ScanArgs a = scan_args(e->d_grid, c.span, gw, gh, c.threshold * c.threshold, e->d_count, c.d_rec, e->flow[0], L.ps, L.ld);
             ProfScope pscope(e, st, TW_K_SCAN, 0);
 #ifdef TW_VARIANTS
             // (scan_fused_level0, not fused_final: a batch with a flow destination keeps its gathered grid either way)
@@ -3345,21 +3396,9 @@ struct BatchEnqueue {
             }
             if (c.regions) {
                 // the hits' connected components, directly behind the scan and inside `seconds`
-                RegionArgs ra;
-                ra.g = e->d_grid;
-                ra.span = c.span;
-                ra.gw = gw;
-                ra.gh = gh;
-                ra.w = c.w;
-                ra.h = c.h;
-                ra.gap = c.regions;
-                ra.thr2 = a.thr2;
-                ra.nrect = c.any_mask ? (const int*)e->d_rgn.p : nullptr;
-                ra.rects = (const int4*)(e->d_rgn + region_rects_off(e->cfg.cap));
-                ra.lab = e->d_lab;
-                ra.n_regions = c.d_nreg;
-                ra.regions = c.d_regs;
-                ra.region_of = c.d_regof;
+                const RegionArgs ra = region_args(a, c.w, c.h, c.regions, c.any_mask ? (const int*)e->d_rgn.p : nullptr,
+                                                  (const int4*)(e->d_rgn + region_rects_off(e->cfg.cap)), e->d_lab, c.d_nreg, c.d_regs,
+                                                  c.d_regof);
                 TW_TRY(launch_hit_regions(e, st, ra, n));
             }
             // the batch's cells with a differing pixel, in order: inside `seconds` too
@@ -3833,18 +3872,8 @@ struct BatchEnqueue {
     // 4.8 + 7.3 us for the gather on 81 workgroups + the scan; gpurun_out/r7lat)
     void enqueue_span_gather(const LevelChunk& ch)
     {
-        const LevelPlan& L = pl->lv[ch.k];
-        GatherArgs g;
-        g.flow = ch.flow_cur;
-        g.fzs = 2 * L.ps;
-        g.fps = L.ps;
-        g.ld = L.ld;
-        g.span = c.span;
-        g.gw = gw;
-        g.gh = gh;
-        g.g = grid_of(ch.j0);
         ProfScope pscope(e, ch.ls, TW_K_SCAN, 0);
-        TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((g.gw + 63) / 64, (g.gh + 3) / 4, ch.nc), dim3(256), 0, ch.ls, g);
+        launch_span_gather(e, ch.ls, ch.flow_cur, pl->lv[ch.k], c.span, gw, gh, grid_of(ch.j0), ch.nc);
     }
 
     // what leaves a level-0 chunk once its chain is enqueued: the span-grid samples, the flow fields
@@ -5954,35 +5983,6 @@ double tw_min_traffic_bytes_pair(const tw_engine* e, int width, int height, int 
 
 }  // extern "C"
 
-// ---- per-stage entry points (tests) --------------------------------------------------------------------
-namespace {
-// (through the engine's page-locked bounce buffer, like tw_flow_u8: the runtime is never handed a pageable pointer for a
-// pitched copy — round 4)
-tw_status up_planes(tw_engine* e, float* d, int ld, long long ps, const float* h, int w, int hh, int planes)
-{
-    const size_t plane = (size_t)w * hh * 4;
-    tw_status r = bounce_reserve(e, plane);
-    if (r) return r;
-    for (int c = 0; c < planes; c++) {
-        memcpy(e->h_bounce, h + (size_t)c * w * hh, plane);
-        TW_HIP(e, hipMemcpy2D(d + c * ps, (size_t)ld * 4, e->h_bounce, (size_t)w * 4, (size_t)w * 4, hh, hipMemcpyHostToDevice));
-    }
-    return TW_OK;
-}
-tw_status down_planes(tw_engine* e, float* h, const float* d, int ld, long long ps, int w, int hh, int planes)
-{
-    const size_t plane = (size_t)w * hh * 4;
-    tw_status r = bounce_reserve(e, plane);
-    if (r) return r;
-    for (int c = 0; c < planes; c++) {
-        TW_HIP(e, hipMemcpy2D(e->h_bounce, (size_t)w * 4, d + c * ps, (size_t)ld * 4, (size_t)w * 4, hh, hipMemcpyDeviceToHost));
-        memcpy(h + (size_t)c * w * hh, e->h_bounce, plane);
-    }
-    return TW_OK;
-}
-}  // namespace
-
-
 // diagnostic: the phase stamps of the last tw_pyr_taps launch (TW_DEBUG_STAMPS=1), 64 workgroups x 4 stamps
 extern "C" int tw_debug_stamps(tw_engine* e, unsigned long long* out)
 {
@@ -6401,14 +6401,9 @@ extern "C" tw_status tw_bench_stage(tw_engine* e, int kclass, int width, int hei
                                               level, npairs});
                 break;
             case TW_K_SCAN: {
-                GatherArgs g;
-                g.flow = fl; g.fzs = 2 * L.ps; g.fps = L.ps; g.ld = L.ld; g.span = span;
-                g.gw = (L.w + span - 1) / span; g.gh = (L.h + span - 1) / span; g.g = grid;
-                TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((g.gw + 63) / 64, (g.gh + 3) / 4, npairs), dim3(256), 0, st, g);
-                ScanArgs a;
-                a.g = grid; a.span = span; a.gw = g.gw; a.gh = g.gh; a.thr2 = 4.0; a.count = cnt;
-                a.rec = rec; a.rec_zs = (long long)a.gw * a.gh;
-                a.flow = nullptr; a.fps = 0; a.ld = 0;
+                const int gw = (L.w + span - 1) / span, gh = (L.h + span - 1) / span;
+                launch_span_gather(e, st, fl, L, span, gw, gh, grid, npairs);
+                const ScanArgs a = scan_args(grid, span, gw, gh, 4.0, cnt, rec, nullptr, 0, 0);
                 TW_LAUNCH(e, TW_DF_SPAN_SCAN, tw_span_scan<false>, dim3(npairs), dim3(1024), 0, st, a);
             } break;
         }
@@ -6428,896 +6423,5 @@ extern "C" tw_status tw_bench_stage(tw_engine* e, int kclass, int width, int hei
     return TW_OK;
 }
 
-namespace {
-// The pyramid stage entry points: upload the image and the one-entry pointer table the kernels read it through, run `launch`
-// (table, device planes) into one plane per entry of `levels`, and download them to `out`.
-template <size_t N, typename F>
-tw_status run_pyr_stage(tw_engine* e, const Plan* pl, const uint8_t* img, int w0, int h0, const int (&levels)[N], float* const (&out)[N],
-                        F launch)
-{
-    Tmp t;
-    uint8_t* d_img = t.alloc<uint8_t>((size_t)w0 * h0);
-    float* d_I[N];
-    bool ok = d_img != nullptr;
-    for (size_t i = 0; i < N; i++) ok = (d_I[i] = t.alloc<float>((size_t)pl->lv[levels[i]].ps)) && ok;
-    const uint8_t** d_tab = t.alloc<const uint8_t*>(1);
-    if (!ok || !d_tab) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_img, img, (size_t)w0 * h0));
-    const uint8_t* hp = d_img;
-    TW_TRY(h2d_sync(e, (void*)d_tab, &hp, sizeof(hp)));
-    hipStream_t st = e->stream;
-    launch(st, d_tab, d_I);  // (every launch with aligned4 = 1: a hipMalloc'ed image; the kernel itself checks stride % 4)
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    for (size_t i = 0; i < N; i++) {
-        const LevelPlan& L = pl->lv[levels[i]];
-        TW_TRY(down_planes(e, out[i], d_I[i], L.ld, L.ps, L.w, L.h, 1));
-    }
-    return TW_OK;
-}
-// The coarser level's flow (pw x ph) and the resize tables to a w x h level, uploaded into `t`: TW_E_UNSUPPORTED for an
-// area-fast resize, which no kernel upsamples
-tw_status stage_flow_ups(tw_engine* e, Tmp& t, const float* prev2, int pw, int ph, int w, int h, FlowUps* ups)
-{
-    ResizeTab u;
-    make_resize_tab(pw, ph, w, h, u);
-    if (u.mode == 2) return TW_E_UNSUPPORTED;
-    const int pld = round_up(pw, 32);
-    const long long pps = (long long)pld * ph;
-    float* d_p = t.alloc<float>(pps * 2);
-    int *d_xo = t.alloc<int>(w), *d_yo = t.alloc<int>(h);
-    float *d_al = t.alloc<float>(2 * (size_t)w), *d_be = t.alloc<float>(2 * (size_t)h);
-    if (!d_p || !d_xo || !d_yo || !d_al || !d_be) return TW_E_NOMEM;
-    TW_TRY(up_planes(e, d_p, pld, pps, prev2, pw, ph, 2));
-    TW_TRY(h2d_sync(e, d_xo, u.xofs.data(), (size_t)w * 4));
-    TW_TRY(h2d_sync(e, d_yo, u.yofs.data(), (size_t)h * 4));
-    TW_TRY(h2d_sync(e, d_al, u.alpha.data(), (size_t)w * 8));
-    TW_TRY(h2d_sync(e, d_be, u.beta.data(), (size_t)h * 8));
-    *ups = FlowUps{d_p, pw, ph, pld, pps, d_xo, d_yo, d_al, d_be, u.xmax, (float)(1. / e->cfg.p.pyrScale)};
-    return TW_OK;
-}
-// The shift stage entry points give every output the pair's share and one more behind it, set to 0xff, which no launch may
-// touch: is the share at p still that?
-bool still_ff(const void* p, size_t bytes)
-{
-    for (size_t i = 0; i < bytes; i++)
-        if (((const unsigned char*)p)[i] != 0xff) return false;
-    return true;
-}
-// What tw_stage_shift and tw_stage_shift_bands start with, and what it leaves on the host.
-struct ShiftStage {
-    Tmp t;
-    size_t P = 0;                 // a pair's profile words: 2 (w + h)
-    std::vector<unsigned> hprof;  // [2][P]: the pair's share, the guard share
-    ShiftRec hrec[2];             // likewise
-};
-// Both images as they are, rows `stride` apart (the last row ends at its last pixel), each at a 256-byte boundary, behind their
-// pointer table; the guarded profiles and records; launch_shift_estimate and then behind(stream, table, records) — the
-// caller's further launches — under one scope; the profiles and the records read back.
-template <typename F>
-tw_status run_shift_stage(tw_engine* e, ShiftStage& s, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h,
-                          int radius, int force_global, F behind)
-{
-    const size_t ibytes = (size_t)(h - 1) * (size_t)stride + (size_t)w, slot = (ibytes + 255) / 256 * 256;
-    const size_t P = s.P = 2 * ((size_t)w + h);
-    uint8_t* d_img = s.t.alloc<uint8_t>(2 * slot);
-    const uint8_t** d_ptrs = s.t.alloc<const uint8_t*>(2);
-    unsigned* d_prof = s.t.alloc<unsigned>(2 * P);
-    ShiftRec* d_rec = s.t.alloc<ShiftRec>(2);
-    if (!d_img || !d_ptrs || !d_prof || !d_rec) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_img, expect, ibytes));
-    TW_TRY(h2d_sync(e, d_img + slot, target, ibytes));
-    const uint8_t* hp[2] = {d_img, d_img + slot};
-    TW_TRY(h2d_sync(e, (void*)d_ptrs, hp, sizeof(hp)));
-    hipStream_t st = e->stream;
-    TW_HIP(e, hipMemsetAsync(d_prof, 0xff, 2 * P * sizeof(unsigned), st));
-    TW_HIP(e, hipMemsetAsync(d_rec, 0xff, 2 * sizeof(ShiftRec), st));
-    {
-        // (tw_prof_select(TW_K_SCAN): these launches alone, for measurements)
-        ProfScope pscope(e, st, TW_K_SCAN, 0);
-        TW_TRY(launch_shift_estimate(e, st, d_ptrs, (long long)stride, stride % 4 == 0 ? 1 : 0, w, h, radius, force_global != 0,
-                                     d_prof, d_rec, nullptr, 1));
-        TW_TRY(behind(st, d_ptrs, d_rec));
-    }
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    s.hprof.resize(2 * P);
-    TW_TRY(d2h_sync(e, s.hprof.data(), d_prof, 2 * P * sizeof(unsigned)));
-    return d2h_sync(e, s.hrec, d_rec, sizeof(s.hrec));
-}
-}  // namespace
-
-extern "C" {
-
-tw_status tw_stage_pyr_level(tw_engine* e, const uint8_t* img, int w0, int h0, int level, float* I, int* w, int* h)
-{
-    if (!e || !img || !I) return TW_E_BAD_PARAMETER;
-    tw_status r = check_dims(e, w0, h0);
-    if (r) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    Plan* pl = nullptr;
-    if ((r = get_plan(e, w0, h0, &pl))) return r;
-    if (level < 0 || level > pl->levels) return TW_E_BAD_PARAMETER;
-    const int levels[1] = {level};
-    float* const out[1] = {I};
-    if ((r = run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
-            launch_pyr(e, st, pl, level, d_tab, w0, 1, d_I[0], 1);
-        })))
-        return r;
-    if (w) *w = pl->lv[level].w;
-    if (h) *h = pl->lv[level].h;
-    return TW_OK;
-}
-
-tw_status tw_stage_pyr_fused23(tw_engine* e, const uint8_t* img, int w0, int h0, float* I3, float* I2)
-{
-    if (!e || !img || !I3 || !I2) return TW_E_BAD_PARAMETER;
-    tw_status r = check_dims(e, w0, h0);
-    if (r) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    Plan* pl = nullptr;
-    if ((r = get_plan(e, w0, h0, &pl))) return r;
-    if (!pl->fused23) {
-        e->err = "tw_stage_pyr_fused23: levels 2 and 3 of this size are not exact reductions by 4 and 8";
-        return TW_E_UNSUPPORTED;
-    }
-    const int levels[2] = {3, 2};
-    float* const out[2] = {I3, I2};
-    return run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
-        launch_pyr23(e, st, pl, d_tab, w0, 1, d_I[0], d_I[1], 1);
-    });
-}
-
-tw_status tw_stage_pyr_fused01(tw_engine* e, const uint8_t* img, int w0, int h0, float* I0, float* I1)
-{
-    if (!e || !img || !I0 || !I1) return TW_E_BAD_PARAMETER;
-    tw_status r = check_dims(e, w0, h0);
-    if (r) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    Plan* pl = nullptr;
-    if ((r = get_plan(e, w0, h0, &pl))) return r;
-    if (!pyr01_fusable(pl)) {
-        e->err = "tw_stage_pyr_fused01: level 1 of this size / these parameters is not an exact halving with 3-tap smoothing";
-        return TW_E_UNSUPPORTED;
-    }
-    const int levels[2] = {0, 1};
-    float* const out[2] = {I0, I1};
-    return run_pyr_stage(e, pl, img, w0, h0, levels, out, [&](hipStream_t st, const uint8_t** d_tab, float* const* d_I) {
-        launch_pyr01(e, st, pl, d_tab, w0, 1, d_I[1], d_I[0], 1);
-    });
-}
-
-// one image through tw_png_unfilter, synchronously (lut: the 256 gray values of a table kind, else null)
-// (iters > 0: the launch is repeated that many times between two events and *avg_us is the time of one; gray may be null)
-static tw_status stage_png(tw_engine* e, const uint8_t* rows, int w, int h, const PngKind& k, const uint8_t* lut, int waves,
-                           uint8_t* gray, int iters = 0, float* avg_us = nullptr)
-{
-    tw_status r = check_dims(e, w, h);
-    if (r) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    const size_t nb = png_rows_bytes(w, h, k.ch, k.bits);
-    for (int y = 0; y < h; y++)
-        if (rows[(size_t)y * png_row_bytes(w, k.ch, k.bits)] > 4) {
-            e->err = "bad PNG filter type";
-            return TW_E_BAD_IMAGE_FORMAT;
-        }
-    if (waves == 0) waves = w <= PNG_LDS_PIXELS / 16 ? 16 : (w <= PNG_LDS_PIXELS / 4 ? 4 : 1);
-    if ((waves != 1 && waves != 4 && waves != 16) || w > PNG_LDS_PIXELS / waves) return TW_E_BAD_PARAMETER;
-    Tmp t;
-    uint8_t* d_rows_raw = t.alloc<uint8_t>(nb + 512);  // the kernel may read a few bytes before / after the rows
-    uint8_t* d_rows = d_rows_raw ? d_rows_raw + 256 : nullptr;
-    uint8_t* d_gray = t.alloc<uint8_t>(staged_image_bytes(w, h));
-    PngJob* d_job = t.alloc<PngJob>(1);
-    unsigned* d_tab = lut ? t.alloc<unsigned>(1 + 64) : nullptr;  // the flag word, then the gray table
-    if (!d_rows || !d_gray || !d_job || (lut && !d_tab)) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_rows, rows, nb));
-    unsigned h_tab[1 + 64] = {0u};
-    if (lut) {
-        memcpy(h_tab + 1, lut, 256);
-        TW_TRY(h2d_sync(e, d_tab, h_tab, sizeof(h_tab)));
-    }
-    PngJob pj;
-    pj.src = d_rows;
-    pj.dst = d_gray;
-    pj.ch = k.ch;
-    pj.bits = k.bits;
-    pj.lut = lut ? (const uint8_t*)(d_tab + 1) : nullptr;
-    pj.flag = d_tab;
-    pj.entries = k.entries;
-    pj.pad = 0;
-    TW_TRY(h2d_sync(e, d_job, &pj, sizeof(pj)));
-    PngArgs pa;
-    pa.jobs = d_job;
-    pa.w = w;
-    pa.h = h;
-    hipStream_t st = e->stream;
-    auto launch = [&]() -> tw_status {
-        if (waves == 16) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<16>, dim3(1), dim3(1024), 0, st, pa);
-        else if (waves == 4) TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<4>, dim3(1), dim3(256), 0, st, pa);
-        else TW_LAUNCH(e, TW_DF_PNG_UNFILTER, tw_png_unfilter<1>, dim3(1), dim3(64), 0, st, pa);
-        return TW_OK;
-    };
-    TW_TRY(launch());
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    if (iters > 0 && avg_us) {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        TW_HIP(e, hipEventCreate(&ev0));
-        if (hipEventCreate(&ev1) != hipSuccess) {
-            (void)hipEventDestroy(ev0);
-            return TW_E_DEVICE;
-        }
-        tw_status tr = TW_OK;
-        hipError_t he = hipEventRecord(ev0, st);
-        for (int i = 0; i < iters && tr == TW_OK; i++) tr = launch();
-        if (he == hipSuccess) he = hipEventRecord(ev1, st);
-        if (he == hipSuccess) he = hipEventSynchronize(ev1);
-        float ms = 0.f;
-        if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev0, ev1);
-        (void)hipEventDestroy(ev0);
-        (void)hipEventDestroy(ev1);
-        if (tr) return tr;
-        TW_HIP(e, he);
-        *avg_us = ms * 1e3f / (float)iters;
-    }
-    if (gray) TW_TRY(d2h_sync(e, gray, d_gray, (size_t)w * h));
-    if (lut) {
-        TW_TRY(d2h_sync(e, h_tab, d_tab, sizeof(unsigned)));
-        if (h_tab[0]) {
-            e->err = "bad palette index";
-            return TW_E_BAD_IMAGE_FORMAT;
-        }
-    }
-    return TW_OK;
-}
-
-tw_status tw_stage_png_unfilter(tw_engine* e, const uint8_t* rows, int channels, int w, int h, int waves, uint8_t* gray)
-{
-    if (!e || !rows || !gray || channels < 1 || channels > 4) return TW_E_BAD_PARAMETER;
-    PngKind k;
-    k.ch = channels;
-    return stage_png(e, rows, w, h, k, nullptr, waves, gray);
-}
-
-tw_status tw_debug_png_kernel_time(tw_engine* e, const tw_png_rows* img, int waves, int iters, float* avg_us)
-{
-    if (!e || !avg_us || iters < 1) return TW_E_BAD_PARAMETER;
-    e->err.clear();
-    PngKind k;
-    uint8_t lut[256];
-    TW_TRY(describe_png(e, img, "the", &k, lut));
-    if (k.ch == 0) return TW_E_BAD_PARAMETER;
-    return stage_png(e, img->rows, img->width, img->height, k, k.table ? lut : nullptr, waves, nullptr, iters, avg_us);
-}
-
-tw_status tw_stage_png_decode(tw_engine* e, const tw_png_rows* img, int waves, uint8_t* gray)
-{
-    if (!e || !gray) return TW_E_BAD_PARAMETER;
-    e->err.clear();
-    PngKind k;
-    uint8_t lut[256];
-    TW_TRY(describe_png(e, img, "the", &k, lut));
-    if (k.ch == 0) return TW_E_BAD_PARAMETER;  // (a plain gray image has nothing to decode)
-    return stage_png(e, img->rows, img->width, img->height, k, k.table ? lut : nullptr, waves, gray);
-}
-
-tw_status tw_stage_resize_u8(tw_engine* e, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh)
-{
-    if (!e || !src || !dst) return TW_E_BAD_PARAMETER;
-    TW_TRY(check_dims(e, sw, sh));
-    TW_TRY(check_dims(e, dw, dh));
-    if (std::abs(sw - dw) > 5 || std::abs(sh - dh) > 5) {
-        e->err = "Don't match image size";
-        return TW_E_DONT_MATCH_SIZE;
-    }
-    TW_HIP(e, hipSetDevice(e->device));
-    Tmp t;
-    uint8_t* d_src = t.alloc<uint8_t>(staged_image_bytes(sw, sh));
-    uint8_t* d_dst = t.alloc<uint8_t>(staged_image_bytes(dw, dh));
-    ResizeJob* d_job = t.alloc<ResizeJob>(1);
-    if (!d_src || !d_dst || !d_job) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_src, src, (size_t)sw * sh));
-    const ResizeJob rj = resize_job(d_src, sw, sh, sw, d_dst, dw, dh, dw);
-    TW_TRY(h2d_sync(e, d_job, &rj, sizeof(rj)));
-    ResizeArgs ra;
-    ra.jobs = d_job;
-    hipStream_t st = e->stream;
-    TW_LAUNCH(e, TW_DF_RESIZE_U8, tw_resize_u8, dim3((dw + 255) / 256, (dh + RSZ_ROWS - 1) / RSZ_ROWS, 1), dim3(64, RSZ_ROWS),
-              0, st, ra);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    TW_TRY(d2h_sync(e, dst, d_dst, (size_t)dw * dh));
-    return TW_OK;
-}
-
-tw_status tw_stage_jpeg_idct(tw_engine* e, const tw_jpeg_luma* img, uint8_t* gray, uint8_t* guard)
-{
-    if (!e || !gray) return TW_E_BAD_PARAMETER;
-    e->err.clear();
-    TW_TRY(check_jpeg_luma(img));
-    if (!img->coef) return TW_E_BAD_PARAMETER;  // (a plain gray image has nothing to decode)
-    const int w = img->width, h = img->height;
-    TW_TRY(check_dims(e, w, h));
-    TW_HIP(e, hipSetDevice(e->device));
-    const size_t ncoef = (size_t)img->blocks_w * (size_t)img->blocks_h * 64, npx = (size_t)w * h;
-    Tmp t;
-    int16_t* d_coef = t.alloc<int16_t>(ncoef);
-    uint8_t* d_raw = t.alloc<uint8_t>(npx + 512);  // 256 guard bytes on either side of the image
-    char* d_tab = t.alloc<char>(sizeof(JpegJob) + 128);
-    if (!d_coef || !d_raw || !d_tab) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_coef, img->coef, ncoef * sizeof(int16_t)));
-    hipStream_t st = e->stream;
-    TW_HIP(e, hipMemsetAsync(d_raw, 0xA5, npx + 512, st));  // (in front of the launch, on its stream)
-    char h_tab[sizeof(JpegJob) + 128];
-    JpegJob jj{};
-    jj.coef = d_coef;
-    jj.dst = d_raw + 256;
-    jj.quant = (const uint16_t*)(d_tab + sizeof(JpegJob));
-    jj.w = w;
-    jj.h = h;
-    jj.bw = img->blocks_w;
-    memcpy(h_tab, &jj, sizeof(jj));
-    memcpy(h_tab + sizeof(JpegJob), img->quant, 128);
-    TW_TRY(h2d_sync(e, d_tab, h_tab, sizeof(h_tab)));
-    JpegArgs ja;
-    ja.jobs = (const JpegJob*)d_tab;
-    TW_LAUNCH(e, TW_DF_JPEG_IDCT, tw_jpeg_idct, jpeg_idct_grid(w, h, 1), dim3(8 * JPEG_WG_BLOCKS), 0, st, ja);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    TW_TRY(d2h_sync(e, gray, d_raw + 256, npx));
-    if (guard) {
-        TW_TRY(d2h_sync(e, guard, d_raw, 256));
-        TW_TRY(d2h_sync(e, guard + 256, d_raw + 256 + npx, 256));
-    }
-    return TW_OK;
-}
-
-tw_status tw_stage_mask_rects(tw_engine* e, const uint8_t* expect, const uint8_t* target, int w, int h, const tw_rect* ignore,
-                              int n_ignore, uint8_t* out, uint8_t* guard)
-{
-    if (!e || !expect || !target || !out) return TW_E_BAD_PARAMETER;
-    e->err.clear();
-    TW_TRY(check_dims(e, w, h));
-    std::vector<tw_rect> ign;
-    TW_TRY(clip_ignore(e, ignore, n_ignore, w, h, &ign));
-    TW_HIP(e, hipSetDevice(e->device));
-    // the two images as a batch places them: 256-byte aligned slots of staged_image_bytes, dense rows of w bytes
-    const size_t npx = (size_t)w * h, slot = staged_image_bytes(w, h);
-    Tmp t;
-    uint8_t* d_exp = t.alloc<uint8_t>(slot);
-    uint8_t* d_raw = t.alloc<uint8_t>(slot + 512);  // 256 guard bytes on either side of the target's slot
-    MaskJob* d_tab = t.alloc<MaskJob>(TW_MAX_IGNORE);
-    if (!d_exp || !d_raw || !d_tab) return TW_E_NOMEM;
-    hipStream_t st = e->stream;
-    TW_HIP(e, hipMemsetAsync(d_exp, 0xA5, slot, st));
-    TW_HIP(e, hipMemsetAsync(d_raw, 0xA5, slot + 512, st));  // (the guards and the slot's padding; in front of the launch)
-    TW_HIP(e, hipStreamSynchronize(st));
-    TW_TRY(h2d_sync(e, d_exp, expect, npx));
-    TW_TRY(h2d_sync(e, d_raw + 256, target, npx));
-    if (!ign.empty()) {
-        MaskJob h_tab[TW_MAX_IGNORE];
-        int wmax = 1, hmax = 1;
-        for (size_t i = 0; i < ign.size(); i++) {
-            const tw_rect& r = ign[i];
-            h_tab[i] = MaskJob{d_raw + 256, d_exp, r.x, r.y, r.x + r.width, r.y + r.height, (long long)w};
-            wmax = std::max(wmax, r.width);
-            hmax = std::max(hmax, r.height);
-        }
-        TW_TRY(h2d_sync(e, d_tab, h_tab, sizeof(MaskJob) * ign.size()));
-        MaskArgs ma;
-        ma.jobs = d_tab;
-        TW_LAUNCH(e, TW_DF_MASK_RECTS, tw_mask_rects, mask_rects_grid(wmax, hmax, (int)ign.size()), dim3(64, MASK_ROWS), 0, st, ma);
-        TW_HIP(e, hipGetLastError());
-        TW_HIP(e, hipStreamSynchronize(st));
-    }
-    TW_TRY(d2h_sync(e, out, d_raw + 256, npx));
-    // the slot's padding behind the image belongs to nobody: a byte there that is not 0xA5 was written outside the image
-    std::vector<uint8_t> pad(slot - npx);
-    if (!pad.empty()) TW_TRY(d2h_sync(e, pad.data(), d_raw + 256 + npx, pad.size()));
-    for (uint8_t b : pad)
-        if (b != 0xA5) {
-            e->err = "tw_mask_rects wrote the padding of the target's slot";
-            return TW_E_DEVICE;
-        }
-    if (guard) {
-        TW_TRY(d2h_sync(e, guard, d_raw, 256));
-        TW_TRY(d2h_sync(e, guard + 256, d_raw + 256 + slot, 256));
-    }
-    return TW_OK;
-}
-
-tw_status tw_stage_polyexp(tw_engine* e, const float* I, int w, int h, float* R5)
-{
-    if (!e || !I || !R5) return TW_E_BAD_PARAMETER;
-    tw_status r = check_dims(e, w, h);
-    if (r) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    const int ld = round_up(w, 32);
-    const long long ps = (long long)ld * h;
-    Tmp t;
-    float* d_I = t.alloc<float>((size_t)ps);
-    float* d_R = t.alloc<float>((size_t)ps * 5);
-    if (!d_I || !d_R) return TW_E_NOMEM;
-    if ((r = up_planes(e, d_I, ld, ps, I, w, h, 1))) return r;
-    hipStream_t st = e->stream;
-    if ((r = launch_polyexp(e, st, w, h, ld, ps, d_I, d_R, 1, -1))) return r;
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    return down_planes(e, R5, d_R, ld, ps, w, h, 5);
-}
-
-tw_status tw_stage_update_matrices(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow2, int w,
-                                   int h, float* M5)
-{
-    if (!e || !R0_5 || !R1_5 || !flow2 || !M5) return TW_E_BAD_PARAMETER;
-    tw_status r = check_dims(e, w, h);
-    if (r) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    const int ld = round_up(w, 32);
-    const long long ps = (long long)ld * h;
-    Tmp t;
-    float *d_R = t.alloc<float>(ps * 10), *d_M = t.alloc<float>(ps * 5), *d_f = t.alloc<float>(ps * 2);
-    if (!d_R || !d_M || !d_f) return TW_E_NOMEM;
-    if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
-        (r = up_planes(e, d_f, ld, ps, flow2, w, h, 2)))
-        return r;
-    const UpdArgs a = upd_args(d_R, d_f, d_M, w, h, ld, ps);
-    hipStream_t st = e->stream;
-    launch_upd_kernel<false>(e, st, w, h, 1, a);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    return down_planes(e, M5, d_M, ld, ps, w, h, 5);
-}
-
-tw_status tw_stage_flow_upsample_update(tw_engine* e, const float* R0_5, const float* R1_5, const float* prevflow2,
-                                        int pw, int ph, int w, int h, float* flow2, float* M5)
-{
-    if (!e || !R0_5 || !R1_5 || !prevflow2 || !flow2 || !M5) return TW_E_BAD_PARAMETER;
-    tw_status r;
-    if ((r = check_dims(e, w, h)) || (r = check_dims(e, pw, ph))) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    const int ld = round_up(w, 32);
-    const long long ps = (long long)ld * h;
-    Tmp t;
-    FlowUps ups;
-    if ((r = stage_flow_ups(e, t, prevflow2, pw, ph, w, h, &ups))) return r;
-    float *d_R = t.alloc<float>(ps * 10), *d_M = t.alloc<float>(ps * 5), *d_f = t.alloc<float>(ps * 2);
-    if (!d_R || !d_M || !d_f) return TW_E_NOMEM;
-    if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5))) return r;
-    UpdArgs a = upd_args(d_R, d_f, d_M, w, h, ld, ps, &ups);
-    a.store_flow = 1;
-    hipStream_t st = e->stream;
-    launch_upd_kernel<true>(e, st, w, h, 1, a);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    if ((r = down_planes(e, flow2, d_f, ld, ps, w, h, 2))) return r;
-    return down_planes(e, M5, d_M, ld, ps, w, h, 5);
-}
-
-tw_status tw_stage_blur_solve(tw_engine* e, const float* R0_5, const float* R1_5, const float* M5, int w, int h,
-                              int update_matrices, float* flow2, float* Mout5)
-{
-    if (!e || !R0_5 || !R1_5 || !M5 || !flow2) return TW_E_BAD_PARAMETER;
-    if (update_matrices && !Mout5) return TW_E_BAD_PARAMETER;
-    tw_status r = check_dims(e, w, h);
-    if (r) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    const int ld = round_up(w, 32);
-    const long long ps = (long long)ld * h;
-    Tmp t;
-    float *d_R = t.alloc<float>(ps * 10), *d_M = t.alloc<float>(ps * 5), *d_Mo = t.alloc<float>(ps * 5),
-          *d_f = t.alloc<float>(ps * 2);
-    if (!d_R || !d_M || !d_Mo || !d_f) return TW_E_NOMEM;
-    if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
-        (r = up_planes(e, d_M, ld, ps, M5, w, h, 5)))
-        return r;
-    BlurLaunch b{w, h, ld, ps, d_M, d_Mo, d_f, d_R, update_matrices ? 1 : 0, -1, 1};
-    b.store_flow = 1;  // the stage returns the flow of a refreshing launch as well
-    if (e->cfg.box && !(b.Vbox = t.alloc<double>((size_t)ps * 5))) return TW_E_NOMEM;  // no engine workspace here
-    hipStream_t st = e->stream;
-    launch_blur(e, st, b);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    if ((r = down_planes(e, flow2, d_f, ld, ps, w, h, 2))) return r;
-    if (update_matrices) return down_planes(e, Mout5, d_Mo, ld, ps, w, h, 5);
-    return TW_OK;
-}
-
-tw_status tw_stage_flow_iter(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow_in2, const float* prev2,
-                             int pw, int ph, int w, int h, float* flow_out2)
-{
-    if (!e || !R0_5 || !R1_5 || !flow_out2 || (flow_in2 && prev2)) return TW_E_BAD_PARAMETER;
-    tw_status r;
-    if ((r = check_dims(e, w, h)) || (prev2 && (r = check_dims(e, pw, ph)))) return r;
-    if (!flow_iter_eligible(e->cfg, w, h)) {
-        e->err = "tw_stage_flow_iter: winSize 30/31 Gaussian window and a level of at least TW_MFREE_MIN_W (320) x 20 pixels";
-        return TW_E_UNSUPPORTED;
-    }
-    TW_HIP(e, hipSetDevice(e->device));
-    const int ld = round_up(w, 32);
-    const long long ps = (long long)ld * h;
-    Tmp t;
-    float *d_R = t.alloc<float>(ps * 10), *d_fi = t.alloc<float>(ps * 2), *d_fo = t.alloc<float>(ps * 2);
-    if (!d_R || !d_fi || !d_fo) return TW_E_NOMEM;
-    if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5))) return r;
-    if (flow_in2 && (r = up_planes(e, d_fi, ld, ps, flow_in2, w, h, 2))) return r;
-    FlowUps ups;
-    if (prev2) {
-        if (pw < 1 || ph < 1) return TW_E_BAD_PARAMETER;
-        if ((r = stage_flow_ups(e, t, prev2, pw, ph, w, h, &ups))) return r;
-    }
-    hipStream_t st = e->stream;
-    launch_flow_iter(e, st, w, h, ld, ps, d_R, flow_in2 ? d_fi : nullptr, ps, d_fo, ps, prev2 ? &ups : nullptr, 1, -1);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    return down_planes(e, flow_out2, d_fo, ld, ps, w, h, 2);
-}
-
-tw_status tw_stage_flow_iter_grid(tw_engine* e, const float* R0_5, const float* R1_5, const float* flow_in2, int w, int h, int span,
-                                  float* grid_out)
-{
-    if (!e || !R0_5 || !R1_5 || !flow_in2 || !grid_out || span < FI_TH) return TW_E_BAD_PARAMETER;
-    tw_status r;
-    if ((r = check_dims(e, w, h))) return r;
-    if (!flow_iter_eligible(e->cfg, w, h) || e->cfg.fi_nt != 1024) {
-        e->err = "tw_stage_flow_iter_grid: winSize 30/31 Gaussian window and a level of at least TW_MFREE_MIN_W (320) x 20 pixels";
-        return TW_E_UNSUPPORTED;
-    }
-    TW_HIP(e, hipSetDevice(e->device));
-    const int ld = round_up(w, 32);
-    const long long ps = (long long)ld * h;
-    const int gw = (w + span - 1) / span, gh = (h + span - 1) / span;
-    const size_t npts = (size_t)gw * gh;
-    Tmp t;
-    float *d_R = t.alloc<float>(ps * 10), *d_fi = t.alloc<float>(ps * 2);
-    float2* d_g = t.alloc<float2>(npts);
-    if (!d_R || !d_fi || !d_g) return TW_E_NOMEM;
-    if ((r = up_planes(e, d_R, ld, ps, R0_5, w, h, 5)) || (r = up_planes(e, d_R + 5 * ps, ld, ps, R1_5, w, h, 5)) ||
-        (r = up_planes(e, d_fi, ld, ps, flow_in2, w, h, 2)))
-        return r;
-    hipStream_t st = e->stream;
-    // (0xff bytes: a point the launch did not write reads back as NaN)
-    TW_HIP(e, hipMemsetAsync(d_g, 0xff, npts * sizeof(float2), st));
-    const FlowIterGrid gp{d_g, span, gw, gh};
-    launch_flow_iter(e, st, w, h, ld, ps, d_R, d_fi, ps, nullptr, ps, nullptr, 1, -1, nullptr, &gp);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    TW_HIP(e, hipMemcpy(grid_out, d_g, npts * sizeof(float2), hipMemcpyDeviceToHost));
-    return TW_OK;
-}
-
-tw_status tw_stage_span_scan(tw_engine* e, const float* fields, int npairs, int w, int h, int span, double threshold, int single_pair,
-                             int* counts, int* xy, float* dxy)
-{
-    if (!e || !fields || !counts || !xy || !dxy || npairs < 1 || span < 1 || (single_pair != 0 && single_pair != 1) ||
-        (single_pair && npairs != 1))
-        return TW_E_BAD_PARAMETER;
-    tw_status r;
-    if ((r = check_dims(e, w, h))) return r;
-    TW_HIP(e, hipSetDevice(e->device));
-    Plan* pl = nullptr;
-    if ((r = get_plan(e, w, h, &pl))) return r;
-    const LevelPlan& L = pl->lv[0];
-    const int gw = (w + span - 1) / span, gh = (h + span - 1) / span;
-    const size_t G = (size_t)gw * gh, nrec = G * (size_t)npairs;
-    Tmp t;
-    float* d_f = t.alloc<float>((size_t)L.ps * 2 * npairs);
-    float2* d_g = t.alloc<float2>(nrec);
-    ScanRec* d_rec = t.alloc<ScanRec>(nrec);
-    int* d_cnt = t.alloc<int>(npairs);
-    if (!d_f || !d_g || !d_rec || !d_cnt) return TW_E_NOMEM;
-    for (int j = 0; j < npairs; j++)
-        if ((r = up_planes(e, d_f + (size_t)j * 2 * L.ps, L.ld, L.ps, fields + (size_t)j * 2 * w * h, w, h, 2))) return r;
-    hipStream_t st = e->stream;
-    // (0xff bytes: a count the scan did not store reads back as -1, a record it did not write as four 0xffffffff words)
-    TW_HIP(e, hipMemsetAsync(d_cnt, 0xff, sizeof(int) * (size_t)npairs, st));
-    TW_HIP(e, hipMemsetAsync(d_rec, 0xff, nrec * sizeof(ScanRec), st));
-    GatherArgs g;
-    g.flow = d_f;
-    g.fzs = 2 * L.ps;
-    g.fps = L.ps;
-    g.ld = L.ld;
-    g.span = span;
-    g.gw = gw;
-    g.gh = gh;
-    g.g = d_g;
-    TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((gw + 63) / 64, (gh + 3) / 4, npairs), dim3(256), 0, st, g);
-    ScanArgs a;
-    a.g = d_g;
-    a.span = span;
-    a.gw = gw;
-    a.gh = gh;
-    a.thr2 = threshold * threshold;
-    a.count = d_cnt;
-    a.rec_zs = (long long)G;
-    a.rec = d_rec;
-    a.flow = d_f;
-    a.fps = L.ps;
-    a.ld = L.ld;
-    launch_scan(e, st, a, choose_scan(npairs, single_pair != 0, gw, gh, BatchSwitches().scan_seg), npairs);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    TW_TRY(d2h_sync(e, counts, d_cnt, sizeof(int) * (size_t)npairs));
-    std::vector<ScanRec> hr(nrec);
-    TW_TRY(d2h_sync(e, hr.data(), d_rec, nrec * sizeof(ScanRec)));
-    for (size_t i = 0; i < nrec; i++) {
-        xy[2 * i] = hr[i].x;
-        xy[2 * i + 1] = hr[i].y;
-        dxy[2 * i] = hr[i].dx;
-        dxy[2 * i + 1] = hr[i].dy;
-    }
-    return TW_OK;
-}
-
-tw_status tw_stage_hit_regions(tw_engine* e, const float* fields, int npairs, int w, int h, int span, double threshold, int gap,
-                               const tw_rect* ignore, const int* n_ignore, int* n_regions, tw_region* regions, int* region_of)
-{
-    if (!e || !fields || !n_regions || !regions || !region_of || npairs < 1 || span < 1 || gap < 1 || gap > 8 ||
-        (n_ignore && !ignore))
-        return TW_E_BAD_PARAMETER;
-    tw_status r;
-    if ((r = check_dims(e, w, h))) return r;
-    // the table a batch uploads: per pair a count and TW_MAX_IGNORE clipped rectangles
-    std::vector<char> tab(region_table_bytes(npairs), 0);
-    bool any_rect = false;
-    for (int j = 0; n_ignore && j < npairs; j++) {
-        std::vector<tw_rect> ign;
-        TW_TRY(clip_ignore(e, ignore + (size_t)j * TW_MAX_IGNORE, n_ignore[j], w, h, &ign));
-        ((int*)tab.data())[j] = (int)ign.size();
-        std::copy(ign.begin(), ign.end(), (tw_rect*)(tab.data() + region_rects_off(npairs)) + (size_t)j * TW_MAX_IGNORE);
-        any_rect = any_rect || !ign.empty();
-    }
-    TW_HIP(e, hipSetDevice(e->device));
-    Plan* pl = nullptr;
-    if ((r = get_plan(e, w, h, &pl))) return r;
-    const LevelPlan& L = pl->lv[0];
-    const int gw = (w + span - 1) / span, gh = (h + span - 1) / span;
-    const size_t G = (size_t)gw * gh, nrec = G * (size_t)npairs;
-    Tmp t;
-    float* d_f = t.alloc<float>((size_t)L.ps * 2 * npairs);
-    float2* d_g = t.alloc<float2>(nrec);
-    ScanRec* d_rec = t.alloc<ScanRec>(nrec);
-    int* d_cnt = t.alloc<int>(npairs);
-    char* d_tab = t.alloc<char>(tab.size());
-    int* d_lab = G > (size_t)RGN_LDS_POINTS ? t.alloc<int>(nrec) : nullptr;
-    int* d_nreg = t.alloc<int>(npairs);
-    RegionRec* d_regs = t.alloc<RegionRec>((size_t)TW_MAX_REGIONS * npairs);
-    int* d_regof = t.alloc<int>(nrec);
-    if (!d_f || !d_g || !d_rec || !d_cnt || !d_tab || (G > (size_t)RGN_LDS_POINTS && !d_lab) || !d_nreg || !d_regs || !d_regof)
-        return TW_E_NOMEM;
-    for (int j = 0; j < npairs; j++)
-        if ((r = up_planes(e, d_f + (size_t)j * 2 * L.ps, L.ld, L.ps, fields + (size_t)j * 2 * w * h, w, h, 2))) return r;
-    TW_TRY(h2d_sync(e, d_tab, tab.data(), tab.size()));
-    hipStream_t st = e->stream;
-    // (0xff bytes: whatever the launch did not write reads back as -1 / 0xffffffff words)
-    TW_HIP(e, hipMemsetAsync(d_nreg, 0xff, sizeof(int) * (size_t)npairs, st));
-    TW_HIP(e, hipMemsetAsync(d_regs, 0xff, sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)npairs, st));
-    TW_HIP(e, hipMemsetAsync(d_regof, 0xff, nrec * sizeof(int), st));
-    GatherArgs g;
-    g.flow = d_f;
-    g.fzs = 2 * L.ps;
-    g.fps = L.ps;
-    g.ld = L.ld;
-    g.span = span;
-    g.gw = gw;
-    g.gh = gh;
-    g.g = d_g;
-    TW_LAUNCH(e, TW_DF_SPAN_GATHER, tw_span_gather, dim3((gw + 63) / 64, (gh + 3) / 4, npairs), dim3(256), 0, st, g);
-    ScanArgs a;
-    a.g = d_g;
-    a.span = span;
-    a.gw = gw;
-    a.gh = gh;
-    a.thr2 = threshold * threshold;
-    a.count = d_cnt;
-    a.rec_zs = (long long)G;
-    a.rec = d_rec;
-    a.flow = d_f;
-    a.fps = L.ps;
-    a.ld = L.ld;
-    launch_scan(e, st, a, choose_scan(npairs, false, gw, gh, BatchSwitches().scan_seg), npairs);
-    RegionArgs ra;
-    ra.g = d_g;
-    ra.span = span;
-    ra.gw = gw;
-    ra.gh = gh;
-    ra.w = w;
-    ra.h = h;
-    ra.gap = gap;
-    ra.thr2 = a.thr2;
-    ra.nrect = any_rect ? (const int*)d_tab : nullptr;
-    ra.rects = (const int4*)(d_tab + region_rects_off(npairs));
-    ra.lab = d_lab;
-    ra.n_regions = d_nreg;
-    ra.regions = d_regs;
-    ra.region_of = d_regof;
-    {
-        // (tw_prof_select(TW_K_SCAN): this launch alone, for tools/regions_prof.py — a batch's scope holds its scan as well)
-        ProfScope pscope(e, st, TW_K_SCAN, 0);
-        TW_TRY(launch_hit_regions(e, st, ra, npairs));
-    }
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    TW_TRY(d2h_sync(e, n_regions, d_nreg, sizeof(int) * (size_t)npairs));
-    TW_TRY(d2h_sync(e, regions, d_regs, sizeof(RegionRec) * TW_MAX_REGIONS * (size_t)npairs));
-    TW_TRY(d2h_sync(e, region_of, d_regof, nrec * sizeof(int)));
-    return TW_OK;
-}
-
-tw_status tw_stage_warp_residual(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h,
-                                 const float* flow2, int span, int tol, int* cells, int* n_changes, tw_change* changes)
-{
-    if (!e || !expect || !target || !flow2 || !cells || !n_changes || !changes || span < 1 || tol < 1 || tol > 254)
-        return TW_E_BAD_PARAMETER;
-    tw_status r;
-    if ((r = check_dims(e, w, h))) return r;
-    if (stride < w) return TW_E_BAD_PARAMETER;
-    TW_HIP(e, hipSetDevice(e->device));
-    Plan* pl = nullptr;
-    if ((r = get_plan(e, w, h, &pl))) return r;
-    const LevelPlan& L = pl->lv[0];
-    const int gw = (w + span - 1) / span, gh = (h + span - 1) / span;
-    const size_t G = (size_t)gw * gh;
-    // the pair's two slots, as a batch stages a host pair: dense rows
-    const size_t npx = staged_image_bytes(w, h);
-    std::vector<uint8_t> img(2 * npx, 0);
-    for (int y = 0; y < h; y++) {
-        memcpy(img.data() + (size_t)y * w, expect + (size_t)y * stride, (size_t)w);
-        memcpy(img.data() + npx + (size_t)y * w, target + (size_t)y * stride, (size_t)w);
-    }
-    Tmp t;
-    uint8_t* d_img = t.alloc<uint8_t>(2 * npx);
-    const uint8_t** d_ptrs = t.alloc<const uint8_t*>(2);
-    float* d_f = t.alloc<float>((size_t)L.ps * 2);
-    int4* d_cells = t.alloc<int4>(G);
-    int* d_cnt = t.alloc<int>(1);
-    ChangeRec* d_chg = t.alloc<ChangeRec>(G);
-    if (!d_img || !d_ptrs || !d_f || !d_cells || !d_cnt || !d_chg) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_img, img.data(), img.size()));
-    const uint8_t* hp[2] = {d_img, d_img + npx};
-    TW_TRY(h2d_sync(e, (void*)d_ptrs, hp, sizeof(hp)));
-    if ((r = up_planes(e, d_f, L.ld, L.ps, flow2, w, h, 2))) return r;
-    hipStream_t st = e->stream;
-    // (0xff bytes: whatever the launches did not write reads back as -1 words)
-    TW_HIP(e, hipMemsetAsync(d_cells, 0xff, G * sizeof(int4), st));
-    TW_HIP(e, hipMemsetAsync(d_cnt, 0xff, sizeof(int), st));
-    TW_HIP(e, hipMemsetAsync(d_chg, 0xff, G * sizeof(ChangeRec), st));
-    {
-        // (tw_prof_select(TW_K_SCAN): these two launches alone, for measurements)
-        ProfScope pscope(e, st, TW_K_SCAN, 0);
-        launch_warp_residual(e, st, d_ptrs, (long long)w, d_f, L, span, tol, d_cells, 1);
-        launch_change_scan(e, st, d_cells, span, gw, gh, d_cnt, d_chg, 1);
-    }
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    TW_TRY(d2h_sync(e, cells, d_cells, G * sizeof(int4)));
-    TW_TRY(d2h_sync(e, n_changes, d_cnt, sizeof(int)));
-    TW_TRY(d2h_sync(e, changes, d_chg, G * sizeof(ChangeRec)));
-    return TW_OK;
-}
-
-tw_status tw_stage_shift(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h, int radius,
-                         int force_global, uint32_t* profiles, tw_shift* out)
-{
-    if (!e || !expect || !target || !out || radius < 1 || radius > 1024) return TW_E_BAD_PARAMETER;
-    tw_status r;
-    if ((r = check_dims(e, w, h))) return r;
-    if (stride < w) return TW_E_BAD_PARAMETER;
-    TW_HIP(e, hipSetDevice(e->device));
-    ShiftStage stage;
-    TW_TRY(run_shift_stage(e, stage, expect, target, stride, w, h, radius, force_global,
-                           [](hipStream_t, const uint8_t**, ShiftRec*) { return TW_OK; }));
-    if (!still_ff(stage.hprof.data() + stage.P, stage.P * sizeof(unsigned))) {
-        e->err = "tw_stage_shift: a launch wrote beyond the pair's profiles";
-        return TW_E_DEVICE;
-    }
-    if (!still_ff(&stage.hrec[1], sizeof(ShiftRec))) {
-        e->err = "tw_stage_shift: a launch wrote beyond the pair's record";
-        return TW_E_DEVICE;
-    }
-    if (profiles) memcpy(profiles, stage.hprof.data(), stage.P * sizeof(unsigned));
-    to_tw_shift(stage.hrec[0], out);
-    return TW_OK;
-}
-
-tw_status tw_stage_shift_bands(tw_engine* e, const uint8_t* expect, const uint8_t* target, ptrdiff_t stride, int w, int h, int radius,
-                               int band, int force_global, uint16_t* sig, tw_shift* global, tw_shift_band* bands, int* n_bands)
-{
-    if (!e || !expect || !target || !global || !bands || !n_bands || radius < 1 || radius > 1024) return TW_E_BAD_PARAMETER;
-    if (band < 32 || band > 1024 || band % 16 != 0) return TW_E_BAD_PARAMETER;
-    tw_status r;
-    if ((r = check_dims(e, w, h))) return r;
-    if (stride < w) return TW_E_BAD_PARAMETER;
-    TW_HIP(e, hipSetDevice(e->device));
-    const int nb = band_count(h, band), nblk0 = band_blocks(w);
-    const size_t S = 2 * (size_t)h * nblk0;
-    // the signatures and the band records are guarded as the profiles and the pair's record are
-    ShiftStage stage;
-    unsigned short* d_sig = stage.t.alloc<unsigned short>(2 * S);
-    BandRec* d_bands = stage.t.alloc<BandRec>(2 * (size_t)nb);
-    if (!d_sig || !d_bands) return TW_E_NOMEM;
-    TW_HIP(e, hipMemsetAsync(d_sig, 0xff, 2 * S * sizeof(unsigned short), e->stream));
-    TW_HIP(e, hipMemsetAsync(d_bands, 0xff, 2 * (size_t)nb * sizeof(BandRec), e->stream));
-    TW_TRY(run_shift_stage(e, stage, expect, target, stride, w, h, radius, force_global,
-                           [&](hipStream_t st, const uint8_t** d_ptrs, ShiftRec* d_rec) {
-                               return launch_band_estimate(e, st, d_ptrs, (long long)stride, w, h, radius, band, force_global != 0,
-                                                           d_rec, d_sig, d_bands, nullptr, 1);
-                           }));
-    std::vector<unsigned short> hsig(2 * S);
-    std::vector<BandRec> hb(2 * (size_t)nb);
-    TW_TRY(d2h_sync(e, hsig.data(), d_sig, 2 * S * sizeof(unsigned short)));
-    TW_TRY(d2h_sync(e, hb.data(), d_bands, 2 * (size_t)nb * sizeof(BandRec)));
-    if (!still_ff(stage.hprof.data() + stage.P, stage.P * sizeof(unsigned)) ||
-        !still_ff(hsig.data() + S, S * sizeof(unsigned short)) || !still_ff(&stage.hrec[1], sizeof(ShiftRec)) ||
-        !still_ff(&hb[nb], (size_t)nb * sizeof(BandRec))) {
-        e->err = "tw_stage_shift_bands: a launch wrote beyond the pair's share";
-        return TW_E_DEVICE;
-    }
-    // the signatures' rows are nblk apart in each image's share of h * nblk0; behind them the share is zero
-    const int dx = stage.hrec[0].dx, nblk = (std::min(w, w - dx) - std::max(0, -dx) + 63) / 64;
-    for (int q = 0; q < 2; q++) {
-        const unsigned short* s = hsig.data() + (size_t)q * h * nblk0;
-        for (size_t i = (size_t)h * nblk; i < (size_t)h * nblk0; i++)
-            if (s[i] != 0) {
-                e->err = "tw_stage_shift_bands: the rest of an image's signatures is not zero";
-                return TW_E_DEVICE;
-            }
-        if (sig) memcpy(sig + (size_t)q * h * nblk, s, (size_t)h * nblk * sizeof(unsigned short));
-    }
-    to_tw_shift(stage.hrec[0], global);
-    memcpy(bands, hb.data(), (size_t)nb * sizeof(BandRec));
-    *n_bands = nb;
-    return TW_OK;
-}
-
-tw_status tw_stage_overlay(tw_engine* e, const uint8_t* expect, const uint8_t* target, int width, int height, ptrdiff_t stride,
-                           int misalign, const tw_rect* rects, int n_rects, const tw_overlay_hit* hits, int n_hits,
-                           const tw_region* regions, int n_regions, int tol, uint8_t* out, ptrdiff_t pitch, int* path)
-{
-    if (!e || !expect || !target || !out) return TW_E_BAD_PARAMETER;
-    e->err.clear();
-    TW_TRY(check_dims(e, width, height));
-    if (stride < width || misalign < 0 || misalign > 3 || n_hits < 0 || (n_hits > 0 && !hits) || n_regions < 0 ||
-        n_regions > TW_MAX_REGIONS || (n_regions > 0 && !regions) || tol < 0 || tol > 255 || pitch < 3 * (ptrdiff_t)width) {
-        e->err = "tw_stage_overlay: bad argument";
-        return TW_E_BAD_PARAMETER;
-    }
-    std::vector<tw_rect> ign;
-    TW_TRY(clip_ignore(e, rects, n_rects, width, height, &ign));
-    TW_HIP(e, hipSetDevice(e->device));
-    const size_t img = (size_t)stride * (size_t)(height - 1) + (size_t)width, obytes = (size_t)pitch * (size_t)height;
-    Tmp t;
-    uint8_t* d_E = t.alloc<uint8_t>(img + 4);
-    uint8_t* d_T = t.alloc<uint8_t>(img + 4);
-    uint8_t* d_out = t.alloc<uint8_t>(obytes);
-    ScanRec* d_hits = t.alloc<ScanRec>((size_t)std::max(n_hits, 1));
-    RegionRec* d_regs = t.alloc<RegionRec>((size_t)std::max(n_regions, 1));
-    if (!d_E || !d_T || !d_out || !d_hits || !d_regs) return TW_E_NOMEM;
-    TW_TRY(h2d_sync(e, d_E + misalign, expect, img));
-    TW_TRY(h2d_sync(e, d_T + misalign, target, img));
-    TW_TRY(h2d_sync(e, d_out, out, obytes));
-    if (n_hits > 0) TW_TRY(h2d_sync(e, d_hits, hits, sizeof(ScanRec) * (size_t)n_hits));
-    if (n_regions > 0) TW_TRY(h2d_sync(e, d_regs, regions, sizeof(RegionRec) * (size_t)n_regions));
-    OverlayJob oj;
-    oj.E = d_E + misalign;
-    oj.T = d_T + misalign;
-    oj.stride = (long long)stride;
-    oj.dst = d_out;
-    oj.pitch = (long long)pitch;
-    oj.w = width;
-    oj.h = height;
-    oj.tol = tol;
-    oj.rects = &ign;
-    oj.d_regions = d_regs;
-    oj.n_regions = n_regions;
-    oj.d_hits = d_hits;
-    oj.n_hits = n_hits;
-    hipStream_t st = e->stream;
-    const int vec = launch_overlay(e, st, oj);
-    TW_HIP(e, hipGetLastError());
-    TW_HIP(e, hipStreamSynchronize(st));
-    if (path) *path = vec;
-    return d2h_sync(e, out, d_out, obytes);
-}
-
-}  // extern "C"
+// ---- per-stage entry points (tests) --------------------------------------------------------------------
+#include "twflow_stage.hip.h"
