@@ -5,6 +5,7 @@ tools/consumer_trace.py, which compares two versions of twhost.cpp over all of t
 subset is run and what the record shows is asserted.  CPU only.  The last test compiles a small program against
 host/resident_cache.h and the stub alone.
 """
+import json
 import os
 import re
 import shutil
@@ -185,6 +186,20 @@ def test_a_damaged_expected_image_is_named_first(world):
     lines, _, _ = run(world, "empty_and_missing")
     assert sorted(ln.split("|")[1] for ln in lines if ln.startswith("ERROR")) == sorted(
         ["ExpectImagePath is empty.", "TargetImagePath is empty.", "Can't open " + d + "missing.png", "Can't open " + d + "missing.png"])
+
+
+def test_with_the_extras_on_the_calls_and_the_answers_are_those_of_the_commit_before_the_steps(world):
+    """tests/golden/consumer_extras_parent.json: CT.EXTRAS_CASES under every configuration of CT.extras_configs — each extra
+    alone, all together, each refusal — recorded from the twhost.cpp in which create_engine and collect were one body each
+    (profiles/consumer_extras.md).  Responses, call trace and diff images, for 1 and for 4 decode threads."""
+    with open(os.path.join(ROOT, "tests", "golden", "consumer_extras_parent.json")) as f:
+        parent = json.load(f)
+    assert sorted(parent) == sorted(c + "/" + n for c in CT.extras_configs("") for n in CT.EXTRAS_CASES)
+    # (run_extras_row asserts that a refused configuration answers "engine: <field>: ..." and submits nothing, extras_rows that
+    # with all on every tw_ticket_* call and tw_wait_regions are made)
+    rows, differ = CT.extras_rows(world["exe"], world["files"], world["dir"])
+    assert differ == []
+    assert rows == parent, sorted(k for k in parent if rows[k] != parent[k])
 
 
 CACHE_PROGRAM = r'''

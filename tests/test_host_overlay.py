@@ -1,4 +1,4 @@
-"""Diff images in the host layer (Parameter::overlayDir / overlayTol, Response::overlay, new TidalWave({overlay: dir}), the
+"""Diff images in the host layer (Parameter::extras.overlayDir / overlayTol, Response::overlay, new TidalWave({overlay: dir}), the
 CLI's -overlay / -overlayTol), asserted from the engine's side as tests/test_host_shift.py does: the stub backend records
 every call of the C ABI (TW_STUB_TRACE) and tools/consumer_probe.cpp feeds one consumer.  CPU only, but for the last test.
 
@@ -10,44 +10,19 @@ import os
 import re
 import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tidal-wave_amd", "host")
-ADDON = os.path.join(HOST, "build", "Release", "tidalwave.node")
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import consumer_trace as CT  # noqa: E402
+import host_probe as HP
+from host_probe import CT, HOST, ROOT, calls, name_of, needs_node, run
 
-needs_node = pytest.mark.skipif(shutil.which("node") is None or not os.path.exists(ADDON),
-                                reason="node or the built addon is not available")
 NEW = ("tw_ticket_hits", "tw_ticket_overlay")
 
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    os.makedirs(os.path.join(HOST, "build"), exist_ok=True)
-    d = str(tmp_path_factory.mktemp("host_overlay"))
-    exe = CT.build(os.path.join(HOST, "build", "consumer_probe_overlay"))
-    f = CT.write_files(d)
-    return {"exe": exe, "dir": d, "files": f, "cases": CT.cases(f)}
-
-
-def run(world, case, threads=1):
-    out, trace = CT.run_case(world["exe"], case, threads, world["dir"])
-    return out.strip().splitlines()[:-1], trace.strip().splitlines()
-
-
-def name_of(t):
-    return t.split(" ", 2)[1]
-
-
-def calls(trace, name):
-    return [t for t in trace if name_of(t) == name]
+    return HP.make_world(tmp_path_factory, "overlay")
 
 
 def fnv1a64(s):
@@ -58,13 +33,7 @@ def fnv1a64(s):
 
 
 def test_overlay_off_makes_the_calls_of_the_parent_cases(world):
-    with open(os.path.join(ROOT, "tests", "golden", "consumer_trace_parent.json")) as f:
-        parent = json.load(f)
-    for name in ("fast_ten_rgb", "raw_mixed_with_files", "narrower3_png_reconcile1", "device_jpeg1", "three_sizes_interleaved",
-                 "resident_twelve_share_expected", "busy_at_third_submit"):
-        out, text = CT.run_case(world["exe"], world["cases"][name], 1, world["dir"])
-        assert not any(n in text for n in NEW) and " overlay " not in out
-        assert {"responses": CT.sha(out), "trace": CT.sha(text), "lines": text.count("\n")} == parent[name], name
+    HP.assert_off_is_the_parent(world, NEW, " overlay ")
 
 
 def check_on(world, case, sub, tol, more=()):

@@ -1,4 +1,4 @@
-"""Hit regions in the host layer (Parameter::regions, Response::regions / regionOf, new TidalWave({regions: gap}), the CLI's
+"""Hit regions in the host layer (Parameter::extras.regions, Response::regions / regionOf, new TidalWave({regions: gap}), the CLI's
 -regions), asserted from the engine's side as tests/test_host_ignore.py does: the stub backend records every call of the C
 ABI (TW_STUB_TRACE) and tools/consumer_probe.cpp feeds one consumer.  CPU only, except for the last test: the result object of
 the real addon, through the CLI on the golden pair, needs the GPU.
@@ -8,55 +8,24 @@ hashes of the commit before the ignore regions, and the probe's existing cases m
 """
 import json
 import os
-import shutil
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tidal-wave_amd", "host")
-ADDON = os.path.join(HOST, "build", "Release", "tidalwave.node")
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import consumer_trace as CT  # noqa: E402
+import host_probe as HP
+from host_probe import CT, HOST, ROOT, calls, needs_node, run
 
 W, H = CT.W, CT.H
-needs_node = pytest.mark.skipif(shutil.which("node") is None or not os.path.exists(ADDON),
-                                reason="node or the built addon is not available")
 
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    os.makedirs(os.path.join(HOST, "build"), exist_ok=True)
-    d = str(tmp_path_factory.mktemp("host_regions"))
-    exe = CT.build(os.path.join(HOST, "build", "consumer_probe_regions"))
-    f = CT.write_files(d)
-    return {"exe": exe, "dir": d, "files": f, "cases": CT.cases(f)}
-
-
-def run(world, case, threads=1):
-    out, trace = CT.run_case(world["exe"], case, threads, world["dir"])
-    return out.strip().splitlines()[:-1], trace.strip().splitlines()
-
-
-def calls(trace, name):
-    return [t for t in trace if t.split(" ", 2)[1] == name]
+    return HP.make_world(tmp_path_factory, "regions")
 
 
 def test_regions_off_makes_the_calls_of_the_parent_cases(world):
-    with open(os.path.join(ROOT, "tests", "golden", "consumer_trace_parent.json")) as f:
-        parent = json.load(f)
-    for name in ("fast_ten_rgb", "raw_mixed_with_files", "narrower3_png_reconcile1", "device_jpeg1", "three_sizes_interleaved",
-                 "resident_twelve_share_expected", "busy_at_third_submit"):
-        out, text = CT.run_case(world["exe"], world["cases"][name], 1, world["dir"])
-        assert "tw_wait_regions" not in text and "tw_set_option" not in text and " regions " not in out
-        assert {"responses": CT.sha(out), "trace": CT.sha(text), "lines": text.count("\n")} == parent[name], name
     # ... and "G 0" is off too
-    env, budget, script = world["cases"]["fast_ten_rgb"]
-    out, text = CT.run_case(world["exe"], (env, budget, ["G", 0] + list(script)), 1, world["dir"])
-    assert {"responses": CT.sha(out), "trace": CT.sha(text), "lines": text.count("\n")} == parent["fast_ten_rgb"]
+    HP.assert_off_is_the_parent(world, ("tw_wait_regions", "tw_set_option"), " regions ", [lambda c: CT.with_regions(c, 0)])
 
 
 @pytest.mark.parametrize("name", ["fast_ten_rgb", "raw_mixed_with_files", "resident_twelve_share_expected", "damaged_both"])

@@ -1,4 +1,4 @@
-"""The residual in the host layer (Parameter::residual / ::residualMin, Response::changes, new TidalWave({residual: tol,
+"""The residual in the host layer (Parameter::extras.residual / ::residualMin, Response::changes, new TidalWave({residual: tol,
 residualMin: n}), the CLI's -residual / -residualMin), asserted from the engine's side as tests/test_host_regions.py does:
 the stub backend records every call of the C ABI (TW_STUB_TRACE) and tools/consumer_probe.cpp feeds one consumer.  CPU only.
 
@@ -7,54 +7,23 @@ hashes of the commit before the ignore regions, and the probe's existing cases m
 """
 import json
 import os
-import shutil
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tidal-wave_amd", "host")
-ADDON = os.path.join(HOST, "build", "Release", "tidalwave.node")
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import consumer_trace as CT  # noqa: E402
-
-needs_node = pytest.mark.skipif(shutil.which("node") is None or not os.path.exists(ADDON),
-                                reason="node or the built addon is not available")
+import host_probe as HP
+from host_probe import CT, HOST, ROOT, calls, needs_node, run
 
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    os.makedirs(os.path.join(HOST, "build"), exist_ok=True)
-    d = str(tmp_path_factory.mktemp("host_residual"))
-    exe = CT.build(os.path.join(HOST, "build", "consumer_probe_residual"))
-    f = CT.write_files(d)
-    return {"exe": exe, "dir": d, "files": f, "cases": CT.cases(f)}
-
-
-def run(world, case, threads=1):
-    out, trace = CT.run_case(world["exe"], case, threads, world["dir"])
-    return out.strip().splitlines()[:-1], trace.strip().splitlines()
-
-
-def calls(trace, name):
-    return [t for t in trace if t.split(" ", 2)[1] == name]
+    return HP.make_world(tmp_path_factory, "residual")
 
 
 def test_residual_off_makes_the_calls_of_the_parent_cases(world):
-    with open(os.path.join(ROOT, "tests", "golden", "consumer_trace_parent.json")) as f:
-        parent = json.load(f)
-    for name in ("fast_ten_rgb", "raw_mixed_with_files", "narrower3_png_reconcile1", "device_jpeg1", "three_sizes_interleaved",
-                 "resident_twelve_share_expected", "busy_at_third_submit"):
-        out, text = CT.run_case(world["exe"], world["cases"][name], 1, world["dir"])
-        assert "tw_ticket_changes" not in text and "tw_set_option" not in text and " changes " not in out
-        assert {"responses": CT.sha(out), "trace": CT.sha(text), "lines": text.count("\n")} == parent[name], name
     # ... and "D 0 0" is off too; residualMin without the residual changes nothing
-    for tol, minimum in ((0, 0), (0, 5)):
-        out, text = CT.run_case(world["exe"], CT.with_residual(world["cases"]["fast_ten_rgb"], tol, minimum), 1, world["dir"])
-        assert {"responses": CT.sha(out), "trace": CT.sha(text), "lines": text.count("\n")} == parent["fast_ten_rgb"]
+    HP.assert_off_is_the_parent(world, ("tw_ticket_changes", "tw_set_option"), " changes ",
+                                [lambda c: CT.with_residual(c, 0, 0), lambda c: CT.with_residual(c, 0, 5)])
 
 
 @pytest.mark.parametrize("name", ["fast_ten_rgb", "raw_mixed_with_files", "resident_twelve_share_expected", "damaged_both"])

@@ -286,20 +286,20 @@ napi_value construct(napi_env env, napi_callback_info info)
     // not in the reference: megabytes of resident expected images per consumer (0: TW_RESIDENT_MB, else off)
     p.residentMB = get_i32(env, opts, "residentMB", 0);
     // not in the reference: group every pair's vectors into regions — 0 (default): off; 1 .. 8: the gap in grid steps
-    p.regions = get_i32(env, opts, "regions", 0);
+    p.extras.regions = get_i32(env, opts, "regions", 0);
     // not in the reference: report the changes the flow does not explain — residual 0 (default): off; 1 .. 254: the tolerance
     // in gray levels.  residualMin n > 0: a pair with at least n unexplained pixels is SUSPICIOUS even without a vector
-    p.residual = get_i32(env, opts, "residual", 0);
-    p.residualMin = get_i32(env, opts, "residualMin", 0);
+    p.extras.residual = get_i32(env, opts, "residual", 0);
+    p.extras.residualMin = get_i32(env, opts, "residualMin", 0);
     // not in the reference: start every pair's flow from its global shift, found on the device — 0 (default): off; 1 .. 1024:
     // the search radius in pixels
-    p.shift = get_i32(env, opts, "shift", 0);
+    p.extras.shift = get_i32(env, opts, "shift", 0);
     // ... and from one vertical shift per band of `shiftBands` rows (32 .. 1024, a multiple of 16; needs `shift`) — 0 (default): off
-    p.shiftBands = get_i32(env, opts, "shiftBands", 0);
+    p.extras.shiftBands = get_i32(env, opts, "shiftBands", 0);
     // not in the reference: a directory for the diff images of SUSPICIOUS pairs, rendered on the device ("" / absent: off), and
     // the gray-level difference above which a pixel is painted as changed (0 .. 255)
-    p.overlayDir = get_str(env, opts, "overlay", "");
-    p.overlayTol = get_i32(env, opts, "overlayTol", 16);
+    p.extras.overlayDir = get_str(env, opts, "overlay", "");
+    p.extras.overlayTol = get_i32(env, opts, "overlayTol", 16);
 
     Broker* b = new Broker();
     b->env = env;

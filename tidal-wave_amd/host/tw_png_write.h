@@ -1,4 +1,4 @@
-// tw_png_write.h — a PNG writer for the diff images of tw_ticket_overlay (Parameter::overlayDir): colour type 2, depth 8, no
+// tw_png_write.h — a PNG writer for the diff images of tw_ticket_overlay (PairExtras::overlayDir): colour type 2, depth 8, no
 // interlace, every row with filter type 0, the zlib stream made of STORED deflate blocks.  No compression on purpose: stored
 // blocks open in every viewer, the file is written for suspicious pairs only, and its cost is a CRC and an Adler-32 over the
 // pixels.  Header-only, so that every program that links the fixed list of host sources keeps building.

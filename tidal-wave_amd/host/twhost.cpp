@@ -1054,6 +1054,41 @@ struct Batch {
     bool skipped(size_t i) const { return !(i & 1) && jobs[i >> 1].no_expected_file(); }
 };
 
+// What the calls of the per-pair extras write into, kept from pair to pair: tw_ticket_changes' and tw_ticket_shift_bands'
+// records, tw_wait_regions' two arrays, tw_ticket_overlay's pixels (sized by the pair that gets a picture), and the counts
+// and the shift record of the pair being collected
+struct ExtrasScratch {
+    std::vector<tw_change> change_recs;
+    std::vector<tw_shift_band> band_recs;
+    std::vector<int> region_of;
+    std::vector<tw_region> region_recs;
+    std::vector<uint8_t> overlay_px;
+    int nchg = 0, nbands = 0, nreg = 0;
+    tw_shift shift_rec;
+    // for a pair of `cap` grid points, with `x` in force
+    void reserve(int cap, const PairExtras& x)
+    {
+        nchg = nbands = nreg = 0;
+        if (x.regions) {
+            region_of.resize((size_t)cap);
+            region_recs.resize(TW_MAX_REGIONS);
+        }
+        if (x.residual) change_recs.resize((size_t)cap);
+        if (x.shiftBands && band_recs.empty()) band_recs.resize(64);
+    }
+};
+// What ask_extras learnt: the first failing call's status and the engine's words for it
+struct Asked {
+    tw_status status = TW_OK;
+    std::string message;
+};
+// What the collecting wait answered: the number of vectors (in ConsumerRun::hits) and the pair's time
+struct Waited {
+    tw_status status = TW_OK;
+    int n = 0;
+    float sec = 0;
+};
+
 // Consumer::run's state and its steps, in the order run() calls them
 struct ConsumerRun {
     // the consumer's own (Consumer's members)
@@ -1076,24 +1111,10 @@ struct ConsumerRun {
     // grid-capacity entries per job — 0.5 MB at 1080p / span 10 — cost 0.2 ms of every response, round 4
     std::unique_ptr<tw_vector[]> hits;
     size_t hits_cap = 0;
-    // hit regions (ConsumerShared::regions; 0: off): the gap the engine was given, and tw_wait_regions' scratch arrays
-    int regions_gap = 0;
-    // residual (ConsumerShared::residual; 0: off): the tolerance the engine was given, Parameter::residualMin, and
-    // tw_ticket_changes' scratch array
-    int residual_tol = 0, residual_min = 0;
-    std::vector<tw_change> change_recs;
-    // shift (ConsumerShared::shift; 0: off): the search radius the engine was given
-    int shift_radius = 0;
-    // shift bands (ConsumerShared::shiftBands; 0: off, and always off without the shift): the band height the engine was given,
-    // and tw_ticket_shift_bands' scratch array
-    int shift_bands = 0;
-    std::vector<tw_shift_band> band_recs;
-    // diff images (ConsumerShared::overlayDir; empty: off): the directory, the tolerance, and tw_ticket_overlay's pixels
-    std::string overlay_dir;
-    int overlay_tol = 16;
-    std::vector<uint8_t> overlay_px;
-    std::vector<int> region_of;
-    std::vector<tw_region> region_recs;
+    // the extras in force on `eng` (ConsumerShared::extras once set_extras and check_overlay have passed; all off without an
+    // engine), and what their calls write into
+    PairExtras extras;
+    ExtrasScratch scratch;
     // Resident expected images (Parameter::residentMB / TW_RESIDENT_MB; 0, the default: off, and no step below reaches the
     // cache): resident_cache.h
     std::unique_ptr<ResidentCache> cache;
@@ -1169,77 +1190,59 @@ struct ConsumerRun {
         // vectors, tests/test_gpu_parity.py::test_scan_fused_final_iteration_option) and worth +3-5 % of GPU throughput; it
         // stays off by default because the reference's consumer computes the whole field (src/consumer.cpp:54).
         if (eng && sw.scan_fused_final) (void)tw_set_option(eng, TW_OPT_SCAN_FUSED_FINAL, 1);
-        // Hit regions (Parameter::regions): the option is set once, here; every batch of this engine then carries it and is
-        // collected with tw_wait_regions.  Off: neither call is made.  A library without the call, or one that refuses the
-        // gap, leaves the consumer without an engine: asked-for regions are never silently dropped.
-        regions_gap = eng && shared ? shared->regions : 0;
-        if (regions_gap) {
-            const tw_status r = tw_wait_regions ? tw_set_option(eng, TW_OPT_REGIONS, regions_gap) : TW_E_UNSUPPORTED;
-            if (r != TW_OK) {
-                eng_err = std::string("engine: regions: ") + tw_strerror(r);
-                tw_engine_destroy(eng);
-                eng = nullptr;
-                regions_gap = 0;
-            }
+    }
+
+    // The first refusal of an extra: the consumer goes on without an engine (every pair answers `reason`) and with no extra in
+    // force; no option call follows
+    void drop_engine(const std::string& reason)
+    {
+        eng_err = reason;
+        tw_engine_destroy(eng);
+        eng = nullptr;
+        extras = PairExtras();
+    }
+    // The extras that are engine options (PairExtras): each is set once, here, in this order; every batch of the engine then
+    // carries it.  One that is off makes no call, and the bands are off while the shift is.
+    void set_extras()
+    {
+        if (!eng || !shared) return;
+        extras = shared->extras;
+        if (!extras.shift) extras.shiftBands = 0;
+        const struct {
+            const char* label;  // in the error text
+            int option;
+            int PairExtras::*setting;
+            bool linked;  // the library has the call that collects the extra
+        } rows[] = {
+            {"regions", TW_OPT_REGIONS, &PairExtras::regions, tw_wait_regions != nullptr},
+            {"residual", TW_OPT_RESIDUAL, &PairExtras::residual, tw_ticket_changes != nullptr},
+            {"shift", TW_OPT_SHIFT, &PairExtras::shift, tw_ticket_shift != nullptr},
+            {"shiftBands", TW_OPT_SHIFT_BANDS, &PairExtras::shiftBands, tw_ticket_shift_bands != nullptr},
+        };
+        for (const auto& row : rows) {
+            const int value = extras.*row.setting;
+            if (!value) continue;
+            const tw_status r = row.linked ? tw_set_option(eng, row.option, value) : TW_E_UNSUPPORTED;
+            if (r != TW_OK) return drop_engine(std::string("engine: ") + row.label + ": " + tw_strerror(r));
         }
-        // Residual (Parameter::residual): as the regions — the option once, here; then tw_ticket_changes before each collecting
-        // wait.  Off: neither call is made.  Asked-for changes are never silently dropped either.
-        residual_tol = eng && shared ? shared->residual : 0;
-        residual_min = shared ? shared->residualMin : 0;
-        if (residual_tol) {
-            const tw_status r = tw_ticket_changes ? tw_set_option(eng, TW_OPT_RESIDUAL, residual_tol) : TW_E_UNSUPPORTED;
-            if (r != TW_OK) {
-                eng_err = std::string("engine: residual: ") + tw_strerror(r);
-                tw_engine_destroy(eng);
-                eng = nullptr;
-                residual_tol = regions_gap = 0;
-            }
-        }
-        // Shift (Parameter::shift): as the residual — the option once, here; then tw_ticket_shift before each collecting wait.
-        // Off: neither call is made.  An asked-for shift is never silently dropped either.
-        shift_radius = eng && shared ? shared->shift : 0;
-        if (shift_radius) {
-            const tw_status r = tw_ticket_shift ? tw_set_option(eng, TW_OPT_SHIFT, shift_radius) : TW_E_UNSUPPORTED;
-            if (r != TW_OK) {
-                eng_err = std::string("engine: shift: ") + tw_strerror(r);
-                tw_engine_destroy(eng);
-                eng = nullptr;
-                shift_radius = residual_tol = regions_gap = 0;
-            }
-        }
-        // Shift bands (Parameter::shiftBands): the option once, behind TW_OPT_SHIFT; then tw_ticket_shift_bands behind
-        // tw_ticket_shift.  Off, or without the shift: neither call is made
-        shift_bands = eng && shared && shift_radius ? shared->shiftBands : 0;
-        if (shift_bands) {
-            const tw_status r = tw_ticket_shift_bands ? tw_set_option(eng, TW_OPT_SHIFT_BANDS, shift_bands) : TW_E_UNSUPPORTED;
-            if (r != TW_OK) {
-                eng_err = std::string("engine: shiftBands: ") + tw_strerror(r);
-                tw_engine_destroy(eng);
-                eng = nullptr;
-                shift_bands = shift_radius = residual_tol = regions_gap = 0;
-            }
-        }
-        // Diff images (Parameter::overlayDir): no option to set — the picture is rendered per ticket, on request.  Off: neither
-        // call is made.  Asked-for pictures are never silently dropped either: a library without the calls, a tolerance outside
-        // 0 .. 255, or a directory that does not exist or cannot be written to leaves the consumer without an engine.  (A picture
-        // that fails later — the disk fills up, the device refuses — is logged and the pair answered without the key.)
-        overlay_dir = eng && shared ? shared->overlayDir : std::string();
-        overlay_tol = shared ? shared->overlayTol : 16;
-        std::string overlay_err;
-        if (!overlay_dir.empty()) {
-            struct stat st;
-            if (!tw_ticket_hits || !tw_ticket_overlay) overlay_err = tw_strerror(TW_E_UNSUPPORTED);
-            else if (overlay_tol < 0 || overlay_tol > 255) overlay_err = tw_strerror(TW_E_BAD_PARAMETER);
-            else if (stat(overlay_dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode) || access(overlay_dir.c_str(), W_OK | X_OK) != 0)
-                overlay_err = "not a writable directory: " + overlay_dir;
-        }
-        if (!overlay_err.empty()) {
-            eng_err = "engine: overlay: " + overlay_err;
-            tw_engine_destroy(eng);
-            eng = nullptr;
-            overlay_dir.clear();
-            shift_bands = shift_radius = residual_tol = regions_gap = 0;
-        }
+    }
+    // Diff images have no option to set — the picture is rendered per ticket, on request.  What can be known to fail is refused
+    // now: a library without the calls, a tolerance outside 0 .. 255, a directory that does not exist or cannot be written to.
+    // (A picture that fails later — the disk fills up, the device refuses — is logged and the pair answered without the key.)
+    std::string check_overlay() const
+    {
+        struct stat st;
+        const std::string& dir = extras.overlayDir;
+        if (dir.empty()) return std::string();
+        if (!tw_ticket_hits || !tw_ticket_overlay) return tw_strerror(TW_E_UNSUPPORTED);
+        if (extras.overlayTol < 0 || extras.overlayTol > 255) return tw_strerror(TW_E_BAD_PARAMETER);
+        if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode) || access(dir.c_str(), W_OK | X_OK) != 0)
+            return "not a writable directory: " + dir;
+        return std::string();
+    }
+    // Profiling selection, the epoch, the resident cache — and the consumer says that it is ready
+    void finish_start()
+    {
         prof = eng && shared && shared->profile;
         if (prof) {
             (void)tw_prof_select(eng, TW_K_BLUR_SOLVE, 0);
@@ -1689,6 +1692,116 @@ struct ConsumerRun {
                     (b.t3 - b.t2) * 1e-6, (steady_ns() - b.t3) * 1e-6);
     }
 
+    // Before the wait, the extras that are read from the ticket — the changes, then the shift, then its bands — up to the first
+    // that fails.  Each call leaves the ticket to the wait, which answers a pair's own error as it always did.
+    Asked ask_extras(const Staged& s, int cap)
+    {
+        Asked a;
+        ExtrasScratch& x = scratch;
+        if (extras.residual) a.status = tw_ticket_changes(eng, s.ticket, x.change_recs.data(), cap, &x.nchg);
+        if (extras.shift && a.status == TW_OK) a.status = tw_ticket_shift(eng, s.ticket, &x.shift_rec);
+        if (extras.shiftBands && a.status == TW_OK) {
+            // (a pair's own height decides the number of its bands: asked again when the array was too short)
+            a.status = tw_ticket_shift_bands(eng, s.ticket, x.band_recs.data(), (int)x.band_recs.size(), &x.nbands);
+            if (a.status == TW_OK && x.nbands > (int)x.band_recs.size()) {
+                x.band_recs.resize((size_t)x.nbands);
+                a.status = tw_ticket_shift_bands(eng, s.ticket, x.band_recs.data(), x.nbands, &x.nbands);
+            }
+        }
+        if (a.status != TW_OK) a.message = engine_error(eng, a.status);
+        return a;
+    }
+    // The diff image: the count the wait will report, with the changes so far, is the status the pair will get, and a pair that
+    // will be SUSPICIOUS gets its picture.  Returns the file's path, empty where there is none; a picture that fails is said
+    // aloud (TW_LOG) and counted, and the pair keeps its answer.  A pair's own error is left to the wait.
+    std::string draw_overlay(const Staged& s, int cap)
+    {
+        int nh = 0;
+        if (tw_ticket_hits(eng, s.ticket, &nh) != TW_OK) return std::string();
+        ExtrasScratch& x = scratch;
+        std::vector<Change> so_far;
+        if (extras.residual) so_far.assign(x.change_recs.begin(), x.change_recs.begin() + std::max(0, std::min(x.nchg, cap)));
+        if (strcmp(pair_status((size_t)std::max(nh, 0), so_far, extras.residualMin), "SUSPICIOUS")) return std::string();
+        const ptrdiff_t pitch = 3 * (ptrdiff_t)s.w;
+        x.overlay_px.resize((size_t)pitch * (size_t)s.h);
+        const tw_overlay_out oo = {x.overlay_px.data(), pitch, TW_OVERLAY_RGB8};
+        const std::string path = overlay_path(extras.overlayDir, s.req.target_image);
+        const tw_status ro = tw_ticket_overlay(eng, s.ticket, extras.overlayTol, &oo);
+        if (ro == TW_OK && png_write_rgb8(path, x.overlay_px.data(), s.w, s.h, pitch)) return path;
+        mine.overlayFailures++;
+        TW_LOGF("overlay: %s: %s\n", path.c_str(), ro == TW_OK ? "cannot write the file" : engine_error(eng, ro).c_str());
+        return std::string();
+    }
+    // The collecting wait — with the regions on, the one that returns them — and what hangs on its answer: the count of pairs
+    // in flight and the resident image this pair kept
+    Waited wait_pair(Staged& s, int cap)
+    {
+        Waited w;
+        ExtrasScratch& x = scratch;
+        w.status = extras.regions ? tw_wait_regions(eng, s.ticket, hits.get(), cap, &w.n, x.region_of.data(), x.region_recs.data(),
+                                                    TW_MAX_REGIONS, &x.nreg, &w.sec)
+                                  : tw_wait(eng, s.ticket, hits.get(), cap, &w.n, &w.sec);
+        if (shared) shared->inflight--;
+        if (s.kept) {
+            cache->settle(s.rkey, s.req.expect_image, s.keep, s.kept, s.w, s.h, w.status);
+            s.kept = nullptr;
+        }
+        return w;
+    }
+    // Why a waited-for pair answers ERROR, or empty: a shared expected image that turned out bad, a bad palette index that the
+    // engine names, the wait's own error, an extra's error — in this order
+    std::string pair_error(const Staged& s, tw_status waited, const Asked& asked)
+    {
+        if (s.uses_keep && s.keep->expect_bad) return cant_open(s.req.expect_image);
+        if (waited == TW_E_BAD_IMAGE_FORMAT && (s.side[0].kind.rows() || s.side[1].kind.rows())) {
+            // a palette index without a PLTE entry, found by the device: cv::imread fails on that file, and the
+            // ticket's message names it (the expected image first, as the reference opens it first)
+            const bool target = strstr(tw_last_error(eng), "target") != nullptr;
+            return cant_open(s.path(target));
+        }
+        if (waited != TW_OK) return engine_error(eng, waited);
+        return asked.message;
+    }
+    void fill_response(Response& out, const Staged& s, const Waited& w, int cap, const std::string& overlay_file)
+    {
+        const ExtrasScratch& x = scratch;
+        const tw_vector* const v = hits.get();
+        out.vectors.resize((size_t)std::min(w.n, cap));
+        for (size_t i = 0; i < out.vectors.size(); i++) out.vectors[i] = {v[i].x, v[i].y, v[i].dx, v[i].dy};
+        if (extras.residual) {
+            out.hasChanges = true;
+            out.changes.assign(x.change_recs.begin(), x.change_recs.begin() + std::max(0, std::min(x.nchg, cap)));
+        }
+        if (extras.shift) {
+            out.hasShift = true;
+            out.shift = Shift{x.shift_rec.dx, x.shift_rec.dy, x.shift_rec.applied != 0};
+        }
+        if (extras.shiftBands) {
+            out.hasBands = true;
+            for (int b = 0; b < x.nbands; b++) {
+                ShiftBand sb;
+                sb.y = x.band_recs[b].y, sb.rows = x.band_recs[b].rows, sb.dy = x.band_recs[b].dy, sb.applied = x.band_recs[b].applied != 0;
+                out.bands.push_back(sb);
+            }
+        }
+        if (extras.regions) {
+            out.hasRegions = true;
+            out.regionCount = x.nreg;
+            out.regionOf.assign(x.region_of.begin(), x.region_of.begin() + (long)out.vectors.size());
+            out.regions.assign(x.region_recs.begin(), x.region_recs.begin() + std::max(0, std::min(x.nreg, (int)TW_MAX_REGIONS)));
+        }
+        // (the shift leaves the status alone: a moved page has vectors above the threshold and is SUSPICIOUS as ever)
+        out.status = pair_status(out.vectors.size(), out.changes, extras.residualMin);  // src/consumer.cpp:77
+        out.time = w.sec;
+        out.expect_image = s.req.expect_image;
+        out.target_image = s.req.target_image;
+        out.span = s.req.span;
+        out.threshold = s.req.threshold;
+        out.height = s.h;
+        out.width = s.w;
+        out.overlay = overlay_file;
+    }
+
     // wait for one job and hand its response to the pump
     void collect(Staged& s)
     {
@@ -1701,119 +1814,13 @@ struct ConsumerRun {
                 hits.reset(new tw_vector[(size_t)cap]);
                 hits_cap = (size_t)cap;
             }
-            tw_vector* const v = hits.get();
-            int n = 0;
-            float sec = 0;
-            int nreg = 0;
-            if (regions_gap) {
-                region_of.resize((size_t)cap);
-                region_recs.resize(TW_MAX_REGIONS);
-            }
-            // the changes first: the call leaves the ticket to the wait, which answers a pair's own error as it always did
-            int nchg = 0;
-            tw_status rc = TW_OK;
-            std::string chg_err;
-            if (residual_tol) {
-                change_recs.resize((size_t)cap);
-                rc = tw_ticket_changes(eng, s.ticket, change_recs.data(), cap, &nchg);
-                if (rc != TW_OK) chg_err = engine_error(eng, rc);
-            }
-            // ... and the pair's shift, likewise
-            tw_shift shift_rec;
-            if (shift_radius && rc == TW_OK) {
-                rc = tw_ticket_shift(eng, s.ticket, &shift_rec);
-                if (rc != TW_OK) chg_err = engine_error(eng, rc);
-            }
-            // ... and its bands (a pair's own height decides their number: asked again when the array was too short)
-            int nbands = 0;
-            if (shift_bands && rc == TW_OK) {
-                if (band_recs.empty()) band_recs.resize(64);
-                rc = tw_ticket_shift_bands(eng, s.ticket, band_recs.data(), (int)band_recs.size(), &nbands);
-                if (rc == TW_OK && nbands > (int)band_recs.size()) {
-                    band_recs.resize((size_t)nbands);
-                    rc = tw_ticket_shift_bands(eng, s.ticket, band_recs.data(), nbands, &nbands);
-                }
-                if (rc != TW_OK) chg_err = engine_error(eng, rc);
-            }
-            // ... and the diff image: the count the wait will report, with the changes, is the status the pair will get; a
-            // pair that will be SUSPICIOUS gets its picture.  A pair's own error is left to the wait.
-            std::string overlay_file;
-            if (!overlay_dir.empty() && rc == TW_OK) {
-                int nh = 0;
-                if (tw_ticket_hits(eng, s.ticket, &nh) == TW_OK) {
-                    std::vector<Change> so_far;
-                    if (residual_tol) so_far.assign(change_recs.begin(), change_recs.begin() + std::max(0, std::min(nchg, cap)));
-                    if (!strcmp(pair_status((size_t)std::max(nh, 0), so_far, residual_min), "SUSPICIOUS")) {
-                        const ptrdiff_t pitch = 3 * (ptrdiff_t)s.w;
-                        overlay_px.resize((size_t)pitch * (size_t)s.h);
-                        const tw_overlay_out oo = {overlay_px.data(), pitch, TW_OVERLAY_RGB8};
-                        const std::string path = overlay_path(overlay_dir, s.req.target_image);
-                        const tw_status ro = tw_ticket_overlay(eng, s.ticket, overlay_tol, &oo);
-                        if (ro == TW_OK && png_write_rgb8(path, overlay_px.data(), s.w, s.h, pitch)) {
-                            overlay_file = path;
-                        } else {
-                            // the pair keeps its answer; the missing picture is said aloud (TW_LOG) and counted
-                            mine.overlayFailures++;
-                            TW_LOGF("overlay: %s: %s\n", path.c_str(), ro == TW_OK ? "cannot write the file" : engine_error(eng, ro).c_str());
-                        }
-                    }
-                }
-            }
-            tw_status r = regions_gap ? tw_wait_regions(eng, s.ticket, v, cap, &n, region_of.data(), region_recs.data(),
-                                                        TW_MAX_REGIONS, &nreg, &sec)
-                                      : tw_wait(eng, s.ticket, v, cap, &n, &sec);
-            if (shared) shared->inflight--;
-            if (s.kept) {
-                cache->settle(s.rkey, s.req.expect_image, s.keep, s.kept, s.w, s.h, r);
-                s.kept = nullptr;
-            }
-            if (s.uses_keep && s.keep->expect_bad) {
-                s.err = cant_open(s.req.expect_image);
-            } else if (r == TW_E_BAD_IMAGE_FORMAT && (s.side[0].kind.rows() || s.side[1].kind.rows())) {
-                // a palette index without a PLTE entry, found by the device: cv::imread fails on that file, and the
-                // ticket's message names it (the expected image first, as the reference opens it first)
-                const bool target = strstr(tw_last_error(eng), "target") != nullptr;
-                s.err = cant_open(s.path(target));
-            } else if (r != TW_OK) {
-                s.err = engine_error(eng, r);
-            } else if (rc != TW_OK) {
-                s.err = chg_err;
-            } else {
-                out.vectors.resize((size_t)std::min(n, cap));
-                for (size_t i = 0; i < out.vectors.size(); i++) out.vectors[i] = {v[i].x, v[i].y, v[i].dx, v[i].dy};
-                if (residual_tol) {
-                    out.hasChanges = true;
-                    out.changes.assign(change_recs.begin(), change_recs.begin() + std::max(0, std::min(nchg, cap)));
-                }
-                if (shift_radius) {
-                    out.hasShift = true;
-                    out.shift = Shift{shift_rec.dx, shift_rec.dy, shift_rec.applied != 0};
-                }
-                if (shift_bands) {
-                    out.hasBands = true;
-                    for (int b = 0; b < nbands; b++) {
-                        ShiftBand sb;
-                        sb.y = band_recs[b].y, sb.rows = band_recs[b].rows, sb.dy = band_recs[b].dy, sb.applied = band_recs[b].applied != 0;
-                        out.bands.push_back(sb);
-                    }
-                }
-                // (the shift leaves the status alone: a moved page has vectors above the threshold and is SUSPICIOUS as ever)
-                out.status = pair_status(out.vectors.size(), out.changes, residual_min);  // src/consumer.cpp:77
-                out.time = sec;
-                out.expect_image = s.req.expect_image;
-                out.target_image = s.req.target_image;
-                out.span = s.req.span;
-                out.threshold = s.req.threshold;
-                out.height = s.h;
-                out.width = s.w;
-                out.overlay = overlay_file;
-                if (regions_gap) {
-                    out.hasRegions = true;
-                    out.regionCount = nreg;
-                    out.regionOf.assign(region_of.begin(), region_of.begin() + (long)out.vectors.size());
-                    out.regions.assign(region_recs.begin(), region_recs.begin() + std::max(0, std::min(nreg, (int)TW_MAX_REGIONS)));
-                }
-            }
+            scratch.reserve(cap, extras);
+            const Asked asked = ask_extras(s, cap);
+            const std::string overlay_file =
+                !extras.overlayDir.empty() && asked.status == TW_OK ? draw_overlay(s, cap) : std::string();
+            const Waited w = wait_pair(s, cap);
+            s.err = pair_error(s, w.status, asked);
+            if (s.err.empty()) fill_response(out, s, w, cap, overlay_file);
         }
         if (!s.err.empty()) {
             out = Response();
@@ -1853,6 +1860,10 @@ void Consumer::run()
     ConsumerRun c(id_, req_, res_, params_, batch_, decode_threads_, n_consumers_, shared_);
     c.bind_device_and_numa();
     c.create_engine();
+    c.set_extras();
+    const std::string overlay_err = c.check_overlay();
+    if (!overlay_err.empty()) c.drop_engine("engine: overlay: " + overlay_err);
+    c.finish_start();
     for (;;) {
         c.deliver_down_to_share();
         Batch b;
@@ -1909,13 +1920,7 @@ void Manager::start(const Parameter& p)
     if (res_mb <= 0)
         if (const char* ev = getenv("TW_RESIDENT_MB")) res_mb = atoll(ev);
     shared_.residentBytes = res_mb > 0 ? res_mb << 20 : 0;
-    shared_.regions = p.regions;
-    shared_.residual = p.residual;
-    shared_.residualMin = p.residualMin;
-    shared_.shift = p.shift;
-    shared_.shiftBands = p.shiftBands;
-    shared_.overlayDir = p.overlayDir;
-    shared_.overlayTol = p.overlayTol;
+    shared_.extras = p.extras;
     shared_.stats.assign((size_t)n, ConsumerStats());
     for (int i = 0; i < n; i++) {
         consumers_.push_back(new Consumer(i, requestQueue_, responseQueue_, p.optParam, batch, dec, n, &shared_));

@@ -61,17 +61,17 @@ struct ShiftBand {
 };
 struct Response {
     std::vector<Vector> vectors;
-    // not in the reference (Parameter::shift > 0 and Parameter::shiftBands > 0 only): the pair's bands, top to bottom
+    // not in the reference (PairExtras::shift > 0 and ::shiftBands > 0 only): the pair's bands, top to bottom
     std::vector<ShiftBand> bands;
     bool hasBands = false;
-    // not in the reference (Parameter::shift > 0 only): the pair's integer translation, estimated and checked on the device
+    // not in the reference (PairExtras::shift > 0 only): the pair's integer translation, estimated and checked on the device
     Shift shift;
     bool hasShift = false;
-    // not in the reference (Parameter::residual > 0 only; empty otherwise): the cells with a pixel that differs by more than
+    // not in the reference (PairExtras::residual > 0 only; empty otherwise): the cells with a pixel that differs by more than
     // the tolerance, each with the number of such pixels the pair's flow does not explain
     std::vector<Change> changes;
     bool hasChanges = false;
-    // not in the reference (Parameter::regions > 0 only; empty otherwise): the vectors grouped into regions on the device —
+    // not in the reference (PairExtras::regions > 0 only; empty otherwise): the vectors grouped into regions on the device —
     // the kept records (at most TW_MAX_REGIONS), per vector the index of its region, and the pair's true number of regions
     std::vector<Region> regions;
     std::vector<int> regionOf;
@@ -83,7 +83,7 @@ struct Response {
     int span = 0;
     std::string status, reason;
     int width = 0, height = 0;
-    // not in the reference (Parameter::overlayDir set, SUSPICIOUS pairs only; empty otherwise): the path of the pair's diff
+    // not in the reference (PairExtras::overlayDir set, SUSPICIOUS pairs only; empty otherwise): the path of the pair's diff
     // image, a PNG rendered on the device (tw_ticket_overlay)
     std::string overlay;
     long long pushedNs = 0;  // host-internal: when the consumer handed the response to the pump (steady clock)
@@ -97,6 +97,38 @@ struct PumpStats {
 };
 struct Report {
     int requestCount = 0, dataCount = 0, errorCount = 0;
+};
+
+// The per-pair extras, none of them in the reference: what a consumer asks of its engine for every pair beyond the vectors.
+// Parameter carries them in, Manager::start copies them whole into ConsumerShared, and a consumer keeps the copy that is in
+// force on its engine.  Common to all: off (the defaults) means that the calls a consumer makes are exactly the ones it made
+// before the extra existed; an extra that is asked for is never silently dropped — a library without its calls, or a value
+// the engine refuses, leaves the consumer without an engine and every pair answers ERROR ("engine: <field>: ...").
+struct PairExtras {
+    // group every pair's vectors into regions (the engine option TW_OPT_REGIONS, collected with tw_wait_regions) — 0: off;
+    // 1 .. 8: the gap, in grid steps, that still joins two vectors
+    int regions = 0;
+    // report the changes the flow does not explain (TW_OPT_RESIDUAL, tw_ticket_changes before each collecting wait) — 0: off;
+    // 1 .. 254: the tolerance in gray levels.  residualMin (0: the status rule is untouched): a pair whose change records hold
+    // at least that many unexplained pixels in total is SUSPICIOUS even without a vector — a flat repaint moves nothing
+    int residual = 0;
+    int residualMin = 0;
+    // start every pair's flow from its global integer shift, found on the device (TW_OPT_SHIFT, tw_ticket_shift behind
+    // tw_ticket_changes) — 0: off; 1 .. 1024: the search radius in pixels.  Response::status is unchanged by it
+    int shift = 0;
+    // with `shift` on, start every pair's flow from one vertical shift per band of this many rows (TW_OPT_SHIFT_BANDS, set
+    // behind TW_OPT_SHIFT; tw_ticket_shift_bands behind tw_ticket_shift) — 0: off; 32 .. 1024, a multiple of 16: the band
+    // height.  Ignored while `shift` is 0
+    int shiftBands = 0;
+    // a directory for diff images (empty: off).  With it a consumer asks tw_ticket_hits in front of each collecting wait —
+    // behind tw_ticket_changes, so that the status pair_status will give is known — and for a pair that will be SUSPICIOUS
+    // renders the picture on the device (tw_ticket_overlay at tolerance overlayTol, 0 .. 255) and writes it to
+    // overlay_path(overlayDir, target_image); Response::overlay carries that path.  Other pairs get no call, no file and no
+    // path.  The directory must exist and be writable when the consumers start: that, like a tolerance outside 0 .. 255, is
+    // a refusal ("engine: overlay: ...").  A picture that fails later (a full disk) leaves its pair's answer without the
+    // path; it is logged under TW_LOG and counted in ConsumerStats::overlayFailures.
+    std::string overlayDir;
+    int overlayTol = 16;
 };
 
 // struct Parameter of the reference (src/manager.h): per-instance options resolved by the broker
@@ -115,33 +147,8 @@ struct Parameter {
     // not in the reference: megabytes of device memory each consumer may fill with resident expected images, keyed by the
     // file's identity (0: TW_RESIDENT_MB, else off — every pair then reads, decodes and uploads both files, as before)
     int residentMB = 0;
-    // not in the reference: group every pair's vectors into regions (the engine option TW_OPT_REGIONS) — 0: off, the calls a
-    // consumer makes are exactly the ones it made before; 1 .. 8: the gap, in grid steps, that still joins two vectors
-    int regions = 0;
-    // not in the reference: report the changes the flow does not explain (the engine option TW_OPT_RESIDUAL) — 0: off, the
-    // calls a consumer makes are exactly the ones it made before; 1 .. 254: the tolerance in gray levels.  residualMin
-    // (0: the status rule is untouched): a pair whose change records hold at least that many unexplained pixels in total is
-    // SUSPICIOUS even without a vector — a flat repaint moves nothing
-    int residual = 0;
-    int residualMin = 0;
-    // not in the reference: start every pair's flow from its global integer shift, found on the device (the engine option
-    // TW_OPT_SHIFT) — 0: off, the calls a consumer makes are exactly the ones it made before; 1 .. 1024: the search radius in
-    // pixels.  Response::status is unchanged by it
-    int shift = 0;
-    // not in the reference: with `shift` on, start every pair's flow from one vertical shift per band of this many rows (the
-    // engine option TW_OPT_SHIFT_BANDS) — 0: off, the calls a consumer makes are exactly the ones it made before; 32 .. 1024,
-    // a multiple of 16: the band height.  Ignored while `shift` is 0
-    int shiftBands = 0;
-    // not in the reference: a directory for diff images (empty: off, the calls a consumer makes are exactly the ones it made
-    // before).  With it a consumer asks tw_ticket_hits in front of each collecting wait — behind tw_ticket_changes, so that the
-    // status pair_status will give is known — and for a pair that will be SUSPICIOUS renders the picture on the device
-    // (tw_ticket_overlay at tolerance overlayTol, 0 .. 255) and writes it to overlay_path(overlayDir, target_image);
-    // Response::overlay carries that path.  Other pairs get no call, no file and no path.  The directory must exist and be
-    // writable when the consumers start: otherwise, as for a tolerance outside 0 .. 255, a consumer has no engine and every pair
-    // answers ERROR ("engine: overlay: ...").  A picture that fails later (a full disk) leaves its pair's answer without the
-    // path; it is logged under TW_LOG and counted in ConsumerStats::overlayFailures.
-    std::string overlayDir;
-    int overlayTol = 16;
+    // not in the reference: what a consumer asks of its engine for every pair, beyond the vectors
+    PairExtras extras;
 };
 // Where the diff image of a pair goes: <dir>/<16 hex digits of the FNV-1a-64 hash of the target_image string>-<the target's
 // base name without its extension>.png — two targets of one base name in different directories do not collide.
@@ -158,7 +165,7 @@ inline std::string overlay_path(const std::string& dir, const std::string& targe
     for (int i = 0; i < 16; i++) name[(size_t)i] = hex[(hsh >> (60 - 4 * i)) & 15];
     return dir + "/" + name + "-" + base + ".png";
 }
-// Response::status of an answered pair: the reference's rule (src/consumer.cpp:77), and Parameter::residualMin's
+// Response::status of an answered pair: the reference's rule (src/consumer.cpp:77), and PairExtras::residualMin's
 inline const char* pair_status(size_t nvectors, const std::vector<Change>& changes, int residualMin)
 {
     if (nvectors) return "SUSPICIOUS";
@@ -176,7 +183,7 @@ struct ConsumerStats {
     std::string engineError;
     long pairs = 0;           // responses pushed since the last Manager::markEpoch()
     long batches = 0;         // engine batches submitted since then
-    long overlayFailures = 0; // diff images of SUSPICIOUS pairs that could not be rendered or written since then (Parameter::overlayDir)
+    long overlayFailures = 0; // diff images of SUSPICIOUS pairs that could not be rendered or written since then (PairExtras::overlayDir)
     // event-bracketed level-0 launches since then: [0] window average + solve, [1] polynomial expansion
     double profMs[2] = {0, 0};
     int profLaunches[2] = {0, 0};
@@ -317,13 +324,7 @@ struct ConsumerShared {
     std::atomic<long> inflight{0};  // pairs submitted to an engine and not yet collected, over all consumers
     bool profile = false;
     long long residentBytes = 0;  // the budget of a consumer's resident expected images (0: off)
-    int regions = 0;              // Parameter::regions: a consumer sets TW_OPT_REGIONS once and collects with tw_wait_regions
-    int residual = 0;             // Parameter::residual: a consumer sets TW_OPT_RESIDUAL once and asks tw_ticket_changes before each collecting wait
-    int residualMin = 0;          // Parameter::residualMin
-    int shift = 0;                // Parameter::shift: a consumer sets TW_OPT_SHIFT once and asks tw_ticket_shift before each collecting wait
-    int shiftBands = 0;           // Parameter::shiftBands: a consumer sets TW_OPT_SHIFT_BANDS once behind TW_OPT_SHIFT and asks tw_ticket_shift_bands behind tw_ticket_shift
-    std::string overlayDir;       // Parameter::overlayDir: a consumer asks tw_ticket_hits before each collecting wait, tw_ticket_overlay for SUSPICIOUS pairs
-    int overlayTol = 16;          // Parameter::overlayTol
+    PairExtras extras;            // Parameter::extras
 };
 
 class Consumer {

@@ -8,15 +8,15 @@
 //     R <expected> <target>                  a pair of files
 //     M <w> <h> <first a> <first b>          an in-memory pair (gray, filled with 7 except for pixel 0)
 //     I <x,y,w,h[;x,y,w,h ...]>              ignore rectangles of the NEXT pair (Request::ignore)
-//     D <tol> <min>                          residual for the whole run (ConsumerShared::residual, ::residualMin); a response then
+//     D <tol> <min>                          residual for the whole run (PairExtras::residual, ::residualMin); a response then
 //                                            ends in " changes <count>: [x,y diff=<n> unexplained=<n> max=<diff>,<unexplained>] ..."
-//     S <radius>                             shift for the whole run (ConsumerShared::shift); a response then ends in
+//     S <radius>                             shift for the whole run (PairExtras::shift); a response then ends in
 //                                            " shift <x>,<y> applied=<0|1>"
-//     O <dir> <tol>                          diff images for the whole run (ConsumerShared::overlayDir, ::overlayTol); the response
+//     O <dir> <tol>                          diff images for the whole run (PairExtras::overlayDir, ::overlayTol); the response
 //                                            of a pair that got one then ends in " overlay <path>"
-//     B <rows>                               shift bands for the whole run (ConsumerShared::shiftBands); a response then ends in
+//     B <rows>                               shift bands for the whole run (PairExtras::shiftBands); a response then ends in
 //                                            " bands <count>: [y,rows dy=<dy> applied=<0|1>] ..."
-//     G <gap>                                hit regions for the whole run (ConsumerShared::regions); a response then ends in
+//     G <gap>                                hit regions for the whole run (PairExtras::regions); a response then ends in
 //                                            " regions <count>: [x,y,w,h n=<hits> peak=(x,y,dx,dy)] ... of: <index per vector>"
 #include <stdio.h>
 #include <stdlib.h>
@@ -49,25 +49,25 @@ int main(int argc, char** argv)
     for (int i = 4; i < argc; i++) {
         const std::string op = argv[i];
         if (op == "G" && i + 1 < argc) {
-            shared.regions = atoi(argv[++i]);
+            shared.extras.regions = atoi(argv[++i]);
             continue;
         }
         if (op == "D" && i + 2 < argc) {
-            shared.residual = atoi(argv[++i]);
-            shared.residualMin = atoi(argv[++i]);
+            shared.extras.residual = atoi(argv[++i]);
+            shared.extras.residualMin = atoi(argv[++i]);
             continue;
         }
         if (op == "S" && i + 1 < argc) {
-            shared.shift = atoi(argv[++i]);
+            shared.extras.shift = atoi(argv[++i]);
             continue;
         }
         if (op == "O" && i + 2 < argc) {
-            shared.overlayDir = argv[++i];
-            shared.overlayTol = atoi(argv[++i]);
+            shared.extras.overlayDir = argv[++i];
+            shared.extras.overlayTol = atoi(argv[++i]);
             continue;
         }
         if (op == "B" && i + 1 < argc) {
-            shared.shiftBands = atoi(argv[++i]);
+            shared.extras.shiftBands = atoi(argv[++i]);
             continue;
         }
         if (op == "I" && i + 1 < argc) {

@@ -4,17 +4,23 @@
     python tools/consumer_trace.py [--twhost PATH/TO/twhost.cpp] [--include DIR] [--out DIR]
 
 builds tools/consumer_probe.cpp against the given twhost.cpp (default: the tree's; `git show REV:tidal-wave_amd/host/twhost.cpp`
-into a scratch directory gives any other commit's — headers it includes beyond the tree's go into --include) and THIS
+into a scratch directory gives any other commit's — headers it includes beyond the tree's go into --include; the probe is
+built against the tree's twhost.h, so the other commit's must lay out ConsumerShared as the tree's does) and THIS
 tree's stub, runs every case below with 1 and with 4 decode threads, and prints one table row per case: the SHA-256 of the
 responses in arrival order, the SHA-256 of the stub's call trace (TW_STUB_TRACE) and the trace's line count.  Two versions
-behave alike when their tables are equal; within one table the 1-thread and 4-thread columns must be equal too.
+behave alike when their tables are equal; within one table the 1-thread and 4-thread columns must be equal too.  A second
+table runs EXTRAS_CASES with the per-pair extras on (extras_configs: each alone, all together, every refusal), with the hash of
+the diff images where there are some; --extras-json writes it as tests/golden/consumer_extras_parent.json holds it.
 
 The files of the cases are written here (at most 40 x 30 pixels); the JPEGs are the committed fixtures of tests/golden/jpeg.
 tests/test_host_consumer_steps.py imports the cases and asserts on their traces.
 """
 import argparse
 import hashlib
+import json
 import os
+import re
+import shutil
 import struct
 import subprocess
 import sys
@@ -156,28 +162,120 @@ def cases(f):
     return c
 
 
+def with_regions(case, gap):
+    """the case with hit regions on for the whole run (the probe's G: PairExtras::regions)"""
+    env, budget, script = case
+    return env, budget, ["G", gap] + list(script)
+
+
 def with_residual(case, tol, minimum=0):
-    """the case with the residual on for the whole run (the probe's D: ConsumerShared::residual, ::residualMin)"""
+    """the case with the residual on for the whole run (the probe's D: PairExtras::residual, ::residualMin)"""
     env, budget, script = case
     return env, budget, ["D", tol, minimum] + list(script)
 
 
 def with_shift(case, radius):
-    """the case with the shift on for the whole run (the probe's S: ConsumerShared::shift)"""
+    """the case with the shift on for the whole run (the probe's S: PairExtras::shift)"""
     env, budget, script = case
     return env, budget, ["S", radius] + list(script)
 
 
 def with_overlay(case, directory, tol=16):
-    """the case with diff images on for the whole run (the probe's O: ConsumerShared::overlayDir, ::overlayTol)"""
+    """the case with diff images on for the whole run (the probe's O: PairExtras::overlayDir, ::overlayTol)"""
     env, budget, script = case
     return env, budget, ["O", directory, tol] + list(script)
 
 
 def with_shift_bands(case, radius, rows):
-    """the case with the shift and its bands on for the whole run (the probe's S and B: ConsumerShared::shift, ::shiftBands)"""
+    """the case with the shift and its bands on for the whole run (the probe's S and B: PairExtras::shift, ::shiftBands)"""
     env, budget, script = case
     return env, budget, ["S", radius, "B", rows] + list(script)
+
+
+# The second table: the per-pair extras ON.  EXTRAS_CASES under every configuration of extras_configs, 1 and 4 decode threads.
+EXTRAS_CASES = ("fast_ten_rgb", "raw_mixed_with_files", "damaged_both", "empty_and_missing", "three_sizes_interleaved",
+                "resident_twelve_share_expected", "resident_bad_palette_expected", "busy_at_third_submit", "narrower3_png_reconcile1")
+# configuration -> the label of "engine: <label>: ..." that every pair of it answers
+REFUSED = {"refused_gap9": "regions", "refused_tolerance255": "residual", "refused_radius1025": "shift", "refused_bands33": "shiftBands",
+           "refused_overlay_tol256": "overlay", "refused_overlay_dir_missing": "overlay"}
+ALL_ON_CALLS = ("tw_ticket_changes", "tw_ticket_shift", "tw_ticket_shift_bands", "tw_ticket_hits", "tw_ticket_overlay", "tw_wait_regions")
+
+
+def extras_configs(odir):
+    """name -> (the function that turns a case into the one with these extras on, whether it writes diff images into `odir`)"""
+    def all_on(c):
+        return with_overlay(with_shift_bands(with_residual(with_regions(c, 2), 12, 0), 64, 48), odir, 16)
+
+    missing = os.path.join(odir, "missing")
+    return {
+        "regions2": (lambda c: with_regions(c, 2), False),
+        "residual12_min0": (lambda c: with_residual(c, 12, 0), False),
+        "residual12_min1": (lambda c: with_residual(c, 12, 1), False),
+        "shift64": (lambda c: with_shift(c, 64), False),
+        "shift64_bands48": (lambda c: with_shift_bands(c, 64, 48), False),
+        "overlay16": (lambda c: with_overlay(c, odir, 16), True),
+        "all_on": (all_on, True),
+        "refused_gap9": (lambda c: with_regions(c, 9), False),
+        "refused_tolerance255": (lambda c: with_residual(c, 255), False),
+        "refused_radius1025": (lambda c: with_shift(c, 1025), False),
+        "refused_bands33": (lambda c: with_shift_bands(c, 64, 33), False),
+        "refused_overlay_tol256": (lambda c: with_overlay(c, odir, 256), True),
+        "refused_overlay_dir_missing": (lambda c: with_overlay(c, missing, 16), False),
+        "bands48_without_shift": (lambda c: (c[0], c[1], ["B", 48] + list(c[2])), False),
+    }
+
+
+def run_extras_row(exe, config, case, threads, workdir):
+    """(responses, trace, SHA-256 of the diff images or None) of one case under one configuration.  A diff image's name starts
+    with a hash of its target's full path, which differs from one work directory to the next: the responses read <fnv> there,
+    and the pictures are hashed in the order of the rest of their names (then of their bytes), those rests included."""
+    odir = os.path.join(workdir, "overlays")
+    shutil.rmtree(odir, ignore_errors=True)
+    os.makedirs(odir)
+    turn_on, pictures = extras_configs(odir)[config]
+    out, text = run_case(exe, turn_on(case), threads, workdir)
+    out = re.sub(r"/[0-9a-f]{16}-", "/<fnv>-", out)
+    png = None
+    if pictures:
+        h = hashlib.sha256()
+        for rest, data in sorted((n[17:], open(os.path.join(odir, n), "rb").read()) for n in os.listdir(odir)):
+            h.update(rest.encode() + b"\0" + data)
+        png = h.hexdigest()[:16]
+    if config in REFUSED:
+        lines = out.strip().splitlines()[:-1]
+        label = "ERROR|engine: %s: " % REFUSED[config]  # (a pair whose files cannot be read says so, engine or no engine)
+        unread = ("ERROR|Can't open ", "ERROR|ExpectImagePath is empty.", "ERROR|TargetImagePath is empty.")
+        assert any(ln.startswith(label) for ln in lines) and all(ln.startswith((label,) + unread) for ln in lines), (config, lines[:2])
+        assert " tw_submit_" not in text and " tw_wait" not in text and not (pictures and os.listdir(odir)), config
+    return out, text, png
+
+
+def extras_rows(exe, f, workdir, out_dir=None):
+    """"<configuration>/<case>" -> {"responses", "trace", "lines"[, "png"]} at 1 decode thread, and the rows whose 4-thread
+    run differs from it"""
+    rows, differ = {}, []
+    all_cases = cases(f)
+    for config in extras_configs(""):
+        seen = set()
+        for name in EXTRAS_CASES:
+            got = []
+            for threads in (1, 4):
+                out, text, png = run_extras_row(exe, config, all_cases[name], threads, workdir)
+                row = {"responses": sha(out), "trace": sha(text), "lines": text.count("\n")}
+                if png is not None:
+                    row["png"] = png
+                got.append(row)
+                seen.update(t.split(" ", 2)[1] for t in text.strip().splitlines())
+                if out_dir:
+                    os.makedirs(out_dir, exist_ok=True)
+                    with open(os.path.join(out_dir, "%s.%s.%d.txt" % (config, name, threads)), "w") as o:
+                        o.write(out + "---\n" + text)
+            rows[config + "/" + name] = got[0]
+            if got[0] != got[1]:
+                differ.append(config + "/" + name)
+        # the golden must not pin an accident: with everything on, every call of the extras is really made
+        assert config != "all_on" or all(c in seen for c in ALL_ON_CALLS), sorted(seen)
+    return rows, differ
 
 
 def run_case(exe, case, threads, workdir, batch=4):
@@ -207,6 +305,7 @@ def main():
     ap.add_argument("--twhost", help="the twhost.cpp to build against (default: the tree's)")
     ap.add_argument("--include", help="a directory of headers that twhost.cpp includes, searched after host/")
     ap.add_argument("--out", help="keep every case's responses and trace in this directory")
+    ap.add_argument("--extras-json", help="write the rows of the second table (the extras on) to this file, as tests/golden/consumer_extras_parent.json")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="consumer_trace_") as d:
         exe = build(os.path.join(d, "consumer_probe"), args.twhost, args.include)
@@ -226,7 +325,17 @@ def main():
             same = same and row[:3] == row[3:]
             print("| %s | %s |" % (name, " | ".join(row)))
         print("\n1 and 4 decode threads: %s" % ("the same in every row" if same else "DIFFERENT"))
-        return 0 if same else 1
+        rows, differ = extras_rows(exe, f, d, args.out)
+        print("\n| configuration / case | responses | trace | lines | diff images |")
+        print("|---|---|---|---|---|")
+        for name, row in rows.items():
+            print("| %s | %s | %s | %d | %s |" % (name, row["responses"], row["trace"], row["lines"], row.get("png", "")))
+        print("\nthe extras on, 1 and 4 decode threads: %s" % ("the same in every row" if not differ else "DIFFERENT in " + ", ".join(differ)))
+        if args.extras_json:
+            with open(args.extras_json, "w") as o:
+                json.dump({k: v for k, v in rows.items() if k not in differ}, o, indent=1, sort_keys=True)
+                o.write("\n")
+        return 0 if same and not differ else 1
 
 
 if __name__ == "__main__":
